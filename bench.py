@@ -17,6 +17,10 @@ f32-MFMA path's (tests/test_gpu_parity.py, profiles/*split_fp16_parity.txt).  `-
 only; by default its throughput is measured in the same run and reported as `f32_mfma_path` next to the headline.
 
 Inputs are resident in HBM before the timed region starts.  Prints ONE JSON line on rank 0.
+
+`--dump-outputs DIR` writes, after the timed steps, the end states the timed rollout returns (the state after its last step) as
+DIR/end_states.npy, and those of the f32-MFMA leg as DIR/f32_mfma_path_end_states.npy when that leg runs.  Inputs (coordinates,
+conditions, noise seed) are fixed by the arguments, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -36,6 +40,7 @@ FLOP_PER_MOL_EVAL = F * F * (L * (30 * E_M + 24 * A) + (2 * 4 + 4) * A + 4 * A) 
 FLOP_PER_EDGE_LAYER = 30 * F * F
 PEAK_F32_MFMA_TFLOPS = 157.3                                                                      # MI355X_MICROARCH.md
 PEAK_F16_MFMA_TFLOPS = 2500.0                                                                     # dense fp16/bf16 MFMA, same guide
+DUMP_BYTES = 64 << 20                                                                             # --dump-outputs: all files together
 
 
 def parse():
@@ -50,7 +55,24 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the drift rel-L2 leg (reference fixture + 64-molecule oracle sample)")
     ap.add_argument("--cpu-sample", type=int, default=512, help="molecules in the CPU-oracle sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the end states of the timed rollout(s) to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy, float32, for each [N, A, 3] array.  An array larger than its share of DUMP_BYTES is written as a fixed,
+    seeded sample of its trajectories (same rows for the same arguments, ascending order)."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 4096                 # room for the .npy headers
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], share // a[0].nbytes, replace=False))
+            a = a[rows]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def cpu_baseline(ti, flat, template, sample_mols, steps=4):
@@ -138,7 +160,9 @@ def main():
     x0 = torch.from_numpy(syn.molecule_coords(B, A, seed=rank)).to(dev)
     cond = torch.from_numpy(syn.ambient_cond(B, A)).to(dev)
     out = torch.empty((1, B, A, 3), dtype=torch.float32, device=dev)
-    grid = ti.engine.time_grid(0.0, 1.0, 1001)            # config 4: 1000-step grid; we time K of its steps
+    # config 4: 1000-step grid; we time K of its steps.  W + K > 1000 takes a finer grid on the same interval, so that exactly
+    # K steps are timed whatever K is
+    grid = ti.engine.time_grid(0.0, 1.0, max(1001, args.warmup + args.steps + 1))
     gdev = "cpu" if shared_gpu_test else dev
     gathered = [torch.empty((B, A, 3), dtype=torch.float32, device=gdev) for _ in range(world)] if world > 1 else None
 
@@ -174,22 +198,29 @@ def main():
             dt = float(tmax.item())
         prof = {k: eng.profile_read(k) for k in ("painn_edge", "painn_update", "painn_embed", "painn_readout")}
         assert bool(torch.isfinite(out).all())
+        end = None
+        if args.dump_outputs and rank == 0:                   # what a caller of the timed rollout receives: all end states
+            end = (torch.cat(gathered) if world > 1 else out[0]).cpu().numpy()
         parity = drift_rel_l2(ti, eng, flat, template) if rank == 0 and world == 1 and not args.no_parity else None
         layout = eng.template_for(B)
         eng.close()
-        return dt, prof, parity, layout
+        return dt, prof, parity, layout, end
 
-    elapsed, prof, parity, layout = measure(args.precision)
+    elapsed, prof, parity, layout, end = measure(args.precision)
+    dumps = {"end_states": end}
     n_edge, ms_edge = prof["painn_edge"]
     n_upd, ms_upd = prof["painn_update"]
     f32_leg = None
     if args.precision != "f32" and not args.no_f32_leg:
-        dt32, prof32, parity32, layout32 = measure("f32")
+        dt32, prof32, parity32, layout32, dumps["f32_mfma_path_end_states"] = measure("f32")
         f32_leg = {"value": world * B * args.steps / dt32, "ms_per_step": 1e3 * dt32 / args.steps,
                    "edge_kernel_avg_ms": prof32["painn_edge"][1] / max(prof32["painn_edge"][0], 1), "edge_row_layout": layout32,
                    "edge_kernel_frac_of_f32_mfma_peak": B * E_M * FLOP_PER_EDGE_LAYER / (prof32["painn_edge"][1] / max(prof32["painn_edge"][0], 1) * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS}
         if parity32:
             f32_leg["drift_rel_l2"] = parity32
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumps)
 
     if rank == 0:
         value = world * B * args.steps / elapsed
@@ -213,7 +244,7 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32 state and accumulation; matrix products on fp16 MFMA with 2-way split fp32 operands (hi + lo halves, 3 products)" if split else "f32", "data": "synthetic",
             "config": {"workload": f"mdqm9 ambient sampler: {B} molecules/GPU x 18 atoms (fully connected, 306 edges), cPaiNN F=128 L=5, "
-                                   "Euler-Maruyama steps of the 1000-step grid, T1 over a 6-rung ladder",
+                                   f"Euler-Maruyama steps of the {len(grid) - 1}-step grid, T1 over a 6-rung ladder",
                        "trajectories_per_gpu": B, "atoms": A, "n_features": F, "score_layers": L, "scheme": "em", "eps": args.eps,
                        "sharding": f"dp{world} over independent trajectories, final RCCL all-gather of end states"},
             "whole_step_tflops": FLOP_PER_MOL_EVAL * B * args.steps * world / elapsed / 1e12,
