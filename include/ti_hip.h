@@ -15,6 +15,11 @@
  *                                                                          mdqm9/thermo/latent/integrators.py:41-89
  *   ti_painn_drift_div / _jvp         ODEWrapper.compute_divergence        mdqm9/thermo/{ambient,latent}/models/ode_wrapper.py:59-91
  *   ti_painn_rollout_dlogp            MoleculeIntegrator.rollout(return_dlogp=True), ODEWrapper.forward (b, -div)
+ *   ti_painn_drift_tv / _div_tv       cPaiNN.forward / ODEWrapper.compute_divergence with one batch.t per molecule
+ *                                     (mdqm9/thermo/ambient/losses.py:45-70 feeds such batches)
+ *   ti_adw_drift_tv                   FCNetMultiBeta.forward with per-row ts                adw/thermo/models/simple.py:38-41
+ *   TI_SCHEME_DOPRI5_TRAJ             the reference's dopri5 integration (integrators.py, odeint per mini-batch) evaluated for every
+ *   + ti_rollout_step_counts          trajectory as if it were alone in its batch (a batch size of 1)
  *
  * Conventions
  *   - Plain pointers and sizes only; no exceptions cross the ABI.  Every int-returning call returns TI_OK (0) or a
@@ -71,7 +76,14 @@ enum { TI_SCHEME_EULER = 0, TI_SCHEME_HEUN = 1, TI_SCHEME_EM = 2,
         *              by Hairer's rule, quartic dense output evaluated at the grid times (the grid only selects output times);
         *   MIDPOINT : fixed grid, y += dt f(t + dt/2, y + dt/2 f(t, y));
         *   RK4      : fixed grid, the 3/8-rule (torchdiffeq's `rk4`). */
-       TI_SCHEME_DOPRI5 = 3, TI_SCHEME_MIDPOINT = 4, TI_SCHEME_RK4 = 5 };
+       TI_SCHEME_DOPRI5 = 3, TI_SCHEME_MIDPOINT = 4, TI_SCHEME_RK4 = 5,
+       /*   DOPRI5_TRAJ: DOPRI5 with per-trajectory step control -- every trajectory (a molecule's 3A coordinates, an adw particle; plus
+        *              its dlogp entry) has its own initial step, error ratio (its own mixed norm), accept / reject decisions, step sizes
+        *              and dense output, i.e. exactly what DOPRI5 gives for that trajectory in a batch of one; the result does not depend
+        *              on the batch, its order or the sharding.  The batch runs until its last trajectory has reached the end of the
+        *              grid (finished ones are evaluated along, never written); *n_fevals counts batched evaluations (2 + 6 x the most
+        *              attempts any trajectory took); ti_rollout_step_counts returns the per-trajectory counts.  Same rtol / atol. */
+       TI_SCHEME_DOPRI5_TRAJ = 6 };
 
 typedef struct ti_handle ti_handle;
 
@@ -143,6 +155,10 @@ int ti_adw_drift(ti_handle* h, const float* x, float t, const float* beta0, cons
  * (ODEWrapper.compute_divergence, adw/thermo/models/ode_wrapper.py:55-67, without its 1e-2 factor) */
 int ti_adw_drift_div(ti_handle* h, const float* x, float t, const float* beta0, const float* beta1, int64_t B, float* out,
                      float* out_div, int mem);
+/* ti_adw_drift / ti_adw_drift_div with one time per row: t [B] fp32 [host|device] (FCNetMultiBeta.forward with per-row ts,
+ * adw/thermo/models/simple.py:38-41); out_div may be NULL.  A uniform t equals ti_adw_drift(_div) bit for bit. */
+int ti_adw_drift_tv(ti_handle* h, const float* x, const float* t, const float* beta0, const float* beta1, int64_t B, float* out,
+                    float* out_div, int mem);
 /* out_path: [rows, B] fp32 with rows = ti_rollout_rows(...) */
 int ti_adw_rollout(ti_handle* h, const ti_rollout_desc* desc, const float* x0, const float* beta0, const float* beta1,
                    int64_t B, float* out_path, int64_t* n_fevals);
@@ -160,6 +176,10 @@ ti_handle* ti_painn_create(const ti_painn_desc* desc, const float* weights, size
                            const int32_t* atom_ids, int device);
 /* x: [B,A,3]; cond: [B,A,n_cond] per-node conditioning (ambient: T0,T1; latent multi-T: T; single-T: NULL); out: [B,A,3] */
 int ti_painn_drift(ti_handle* h, const float* x, float t, const float* cond, int64_t B, float* out, int mem);
+/* ti_painn_drift with one time per molecule: t [B] fp32 [host|device] -- the reference's per-node batch.t, constant within a molecule
+ * (cPaiNN.forward, cpainn.py:23-115; the training losses feed one t per molecule, mdqm9/thermo/ambient/losses.py:45-70).
+ * A uniform t equals ti_painn_drift bit for bit, and row b equals ti_painn_drift at t[b] (same B, same layout). */
+int ti_painn_drift_tv(ti_handle* h, const float* x, const float* t, const float* cond, int64_t B, float* out, int mem);
 /* out_path: [rows, B, A, 3]; *n_fevals = drift evaluations taken (DOPRI5: 2 + 6 per attempted step) */
 int ti_painn_rollout(ti_handle* h, const ti_rollout_desc* desc, const float* x0, const float* cond, int64_t B,
                      float* out_path, int64_t* n_fevals);
@@ -173,6 +193,8 @@ int ti_painn_drift_jvp(ti_handle* h, const float* x, const float* xdot, float t,
  * latent/models/ode_wrapper.py:57-86), WITHOUT the ambient wrapper's 1e-2 factor.  Tangent state is processed in chunks of
  * molecules sized to TI_JVP_WS_GB gigabytes of HBM (environment, default 48). */
 int ti_painn_drift_div(ti_handle* h, const float* x, float t, const float* cond, int64_t B, float* out, float* out_div, int mem);
+/* ti_painn_drift_div with one time per molecule, t [B] (ODEWrapper.compute_divergence at a per-molecule batch.t) */
+int ti_painn_drift_div_tv(ti_handle* h, const float* x, const float* t, const float* cond, int64_t B, float* out, float* out_div, int mem);
 /* MoleculeIntegrator.rollout(return_dlogp=True) (ambient/integrators.py:36-68, latent/integrators.py:57-89) on the fixed
  * grid of `desc` (EULER, HEUN, MIDPOINT, RK4 or the adaptive DOPRI5; EM is refused): second state d(dlogp)/dt = -div_scale * div, or with reverse_ode the pair
  * (-b, +div_scale * div) (ode_wrapper.py:49; the caller passes the descending grid linspace(end, start)).
@@ -181,6 +203,9 @@ int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* desc, const floa
                            float div_scale, float out_scale, int reverse_ode, float* out_path, float* out_dlogp, int64_t* n_fevals);
 
 /* ---- shared ------------------------------------------------------------------------------------------------------ */
+/* Accepted and rejected step counts [B] (host) of every trajectory of the last TI_SCHEME_DOPRI5_TRAJ rollout on this handle
+ * (torchdiffeq's per-solve counts of a batch-of-one run); TI_E_ARG if B differs from that rollout's batch. */
+int ti_rollout_step_counts(ti_handle* h, int64_t* accepted, int64_t* rejected, int64_t B);
 void ti_destroy(ti_handle* h);
 /* Streams.  A handle enqueues all device work on ONE stream: its own (created non-blocking at create()) or, with
  * ti_set_stream(h, s, TI_STREAM_EXTERNAL), the caller's hipStream_t `s` -- where s == NULL then means the legacy null stream

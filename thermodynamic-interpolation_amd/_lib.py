@@ -18,6 +18,7 @@ SO_PATH = os.environ.get("TI_LIB_PATH") or os.path.join(HERE, "libti_hip.so")
 TI_OK, TI_E_ARG, TI_E_HIP, TI_E_NAN, TI_E_ALLOC, TI_E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 MEM_HOST, MEM_DEVICE = 0, 1
 SCHEMES = {"euler": 0, "heun": 1, "em": 2, "dopri5": 3, "midpoint": 4, "rk4": 5}
+SCHEME_DOPRI5_TRAJ = 6           # dopri5 with per-trajectory step control (engine: scheme="dopri5", step_control="trajectory")
 PRECISIONS = {"f32": 0, "f16x2": 1, "f16": 2}
 KERNELS = {"painn_edge": 0, "painn_update": 1, "painn_embed": 2, "painn_readout": 3, "adw": 4, "integrate": 5,
            "painn_jvp_edge": 6, "painn_jvp_update": 7, "painn_jvp_readout": 8, "painn_jvp_filter": 9}
@@ -29,6 +30,7 @@ ABI_SYMBOLS = [
     "ti_painn_create", "ti_painn_drift", "ti_painn_rollout", "ti_painn_drift_jvp", "ti_painn_drift_div", "ti_painn_rollout_dlogp",
     "ti_destroy", "ti_set_stream", "ti_wait_stream", "ti_painn_set_template", "ti_painn_template_for", "ti_reserve", "ti_profile_enable", "ti_profile_read",
     "ti_painn_debug_tap", "ti_painn_debug_read", "ti_painn_debug_poison", "ti_selftest",
+    "ti_painn_drift_tv", "ti_painn_drift_div_tv", "ti_adw_drift_tv", "ti_rollout_step_counts",
 ]
 
 
@@ -114,6 +116,10 @@ def lib():
     L.ti_painn_debug_read.argtypes = [vp, C.c_int, fp, C.c_size_t]
     L.ti_painn_debug_poison.argtypes = [vp, C.c_int64, C.c_float]
     L.ti_selftest.argtypes = [C.c_int]
+    L.ti_painn_drift_tv.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int]
+    L.ti_painn_drift_div_tv.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int]
+    L.ti_adw_drift_tv.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int]
+    L.ti_rollout_step_counts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]
     _lib = L
     return L
 

@@ -252,7 +252,8 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_kernel(c
 // 16 atoms per wave on the r16 primitives and the precision's matrix path (f32 16x16x4, split fp16, fp16).  (Until round 2 these two ran
 // 32 rows per wave on the f32 32x32x2 MFMA whatever the precision: a lone wave spent 1.8 us per weight chunk there against 0.3 us here,
 // which is what a small batch pays -- 80 + 35 us of a 620 us evaluation of 12 molecules.)
-template <int NBK, int NSEG, int PREC>
+// TV: the time of node nd is p.tv[nd / A] (one time per molecule, the reference's per-node batch.t); else the scalar p.t.
+template <int NBK, int NSEG, int PREC, bool TV = false>
 __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_embed16_kernel(const EmbedParams p)
 {
     constexpr bool H16 = PREC == 2;
@@ -286,7 +287,8 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_embed16_kernel(
                 r16::posenc_set(in, u / p.temp_length, q);
                 op.set(in);
             } else {
-                r16::posenc_set(in, p.t / p.time_length, q);     // batch.t = t * ones_like(atoms)
+                const float tn = TV ? p.tv[nd / p.A] : p.t;     // batch.t = t * ones_like(atoms), or one t per molecule
+                r16::posenc_set(in, tn / p.time_length, q);
                 op.set(in);
             }
         }
@@ -448,6 +450,15 @@ static hipError_t configure_nb()
         if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 2>, n2)) != hipSuccess) return e;
         if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 2>, n2)) != hipSuccess) return e;
         if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 2>, n2)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 0, true>, n0)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 0, true>, n0)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 0, true>, n0)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 1, true>, n0)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 1, true>, n0)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 1, true>, n0)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 2, true>, n2)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 2, true>, n2)) != hipSuccess) return e;
+        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 2, true>, n2)) != hipSuccess) return e;
         if ((e = set_lds(painn_readout16_kernel<2 * NB, 0>, n0)) != hipSuccess) return e;
         if ((e = set_lds(painn_readout16_kernel<2 * NB, 1>, n0)) != hipSuccess) return e;
         if ((e = set_lds(painn_readout16_kernel<2 * NB, 2>, n2)) != hipSuccess) return e;
@@ -491,14 +502,20 @@ hipError_t configure_painn_kernels(int NBv)
 // prec: include/ti_hip.h TI_PREC_* (0 f32, 1 f16x2, 2 f16 storage mode: the state tensors are fp16)
 static size_t node16_lds_bytes(int NB, bool h16) { return 2 * 2 * (size_t)update_chunk4(NB, h16) * 16; }      // PipeDMA<.., SC = 2>: two superchunks
 
-template <int NB, int PREC>
+template <int NB, int PREC, bool TV>
 static void launch_embed16(int nseg, const EmbedParams& p, hipStream_t st)
 {
     const dim3 g((unsigned)((p.N + 63) / 64));                 // 4 waves x 16 atoms per workgroup
     const size_t l = node16_lds_bytes(NB, PREC == 2);
-    if (nseg == 4) hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 4, PREC>), g, dim3(256), l, st, p);
-    else if (nseg == 3) hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 3, PREC>), g, dim3(256), l, st, p);
-    else hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 2, PREC>), g, dim3(256), l, st, p);
+    if (nseg == 4) hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 4, PREC, TV>), g, dim3(256), l, st, p);
+    else if (nseg == 3) hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 3, PREC, TV>), g, dim3(256), l, st, p);
+    else hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 2, PREC, TV>), g, dim3(256), l, st, p);
+}
+template <int NB, int PREC>
+static void launch_embed16(int nseg, const EmbedParams& p, hipStream_t st)
+{
+    if (p.tv) launch_embed16<NB, PREC, true>(nseg, p, st);
+    else launch_embed16<NB, PREC, false>(nseg, p, st);
 }
 
 hipError_t launch_embed(int NBv, int nseg, int prec, const EmbedParams& p, hipStream_t st)

@@ -4,6 +4,7 @@
 // There is deliberately no CPU fallback in this file: every entry point either runs the HIP kernels or fails.
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -192,6 +193,10 @@ struct ti_handle {
     long long jvp_cap = 0, last_VB = 0; int last_D = 1;
     // Runge-Kutta drivers (rollout_rk): stage derivatives, dense-output coefficients, reduction scratch
     DevBuf<float> rk_ws; DevBuf<double> rk_red;
+    // per-trajectory dopri5 (rollout_rk_traj): controller state, stage times, status words, grid, host-output staging, and the
+    // accepted / rejected counts of the last such rollout (ti_rollout_step_counts)
+    DevBuf<TrajCtl> rk_ctl; DevBuf<float> rk_tv, rk_path, rk_dpath; DevBuf<int> rk_status; DevBuf<double> rk_grid;
+    std::vector<int64_t> traj_accepted, traj_rejected;
 
     // ---- adw
     ti_adw_desc ad{};
@@ -199,6 +204,7 @@ struct ti_handle {
     float a_be_b_out = 0.f, a_b_out = 0.f;
     Stream st_be{}, st_net{};
     DevBuf<float> ax, ab1, ab2, axt, aemb_u, abeta0_u, abeta1_u, adl, ad1, ad2; DevBuf<int32_t> aidx;
+    DevBuf<float> abeta0_r, abeta1_r, aemb_r, atv;                  // per-row conditioning / beta embedding / times (per-row t)
 
     ~ti_handle()
     {
@@ -648,8 +654,9 @@ struct JvpRun {            // one tangent pass riding on a drift evaluation
 
 // one drift evaluation, everything on h->stream; x_dev / out_dev are device pointers [B*A*3].  With `jr` the tangent
 // kernels run in lock step: each reads the primal state its layer's primal kernel is about to overwrite.
+// tv (device, [B], may be NULL): one time per molecule instead of t (the embed kernel's per-molecule instantiation).
 void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, float* out_dev,
-                     const JvpRun* jr = nullptr)
+                     const JvpRun* jr = nullptr, const float* tv = nullptr)
 {
     const int A = h->d.n_atoms, F = h->d.n_features, L = h->d.n_layers, NB = h->NB;
     const long long N = B * A, groups = (B + h->G - 1) / h->G * h->parts;         // edge-kernel waves: (molecule group, part)
@@ -686,7 +693,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
         p.stream = h->S(h->st_embed16); p.nch = h->st_embed16.nch; p.mlp = h->vec(h->embed);
         p.pb0 = L > 0 ? h->F(h->phi[0].b0) : h->F(h->embed.b2);
         p.atom_emb = h->F(h->atom_emb); p.atom_ids = h->atom_ids.p; p.cond = cond_dev; p.ncond = h->ncond; p.A = A; p.N = N;
-        p.t = t; p.temp_length = h->d.temp_length; p.time_length = h->d.time_length; p.temp_mean = h->d.temp_mean; p.temp_range = h->d.temp_range;
+        p.t = t; p.tv = tv; p.temp_length = h->d.temp_length; p.time_length = h->d.time_length; p.temp_mean = h->d.temp_mean; p.temp_range = h->d.temp_range;
         p.s = h->s.p; p.P = h->P.p;
         Timed tm(h, TI_KERNEL_PAINN_EMBED);
         HIP_CHECK(launch_embed(NB, h->nE, prec, p, st));
@@ -815,7 +822,8 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
 }
 
 // drift and exact divergence: 3A unit-seed tangent passes per molecule, in chunks that fit the tangent HBM budget
-void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, float* out_dev, float* div_dev)
+void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, float* out_dev, float* div_dev,
+                         const float* tv = nullptr)
 {
     const int A = h->d.n_atoms, D = 3 * A;
     const long long chunk = jvp_chunk_molecules(h, D);
@@ -824,7 +832,7 @@ void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float*
         ensure_jvp_ws(h, bc, D);
         JvpRun jr{D, nullptr, h->tout.p};
         painn_drift_dev(h, x_dev + (size_t)b0 * A * 3, t, cond_dev ? cond_dev + (size_t)b0 * A * h->ncond : nullptr, bc,
-                        out_dev + (size_t)b0 * A * 3, &jr);
+                        out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr);
         HIP_CHECK(launch_div_reduce(h->tout.p, bc, D, h->G, div_dev + b0, h->stream));
     }
     h->last_B = std::min(chunk, B);
@@ -871,6 +879,26 @@ void adw_drift_dev(ti_handle* h, const float* x_dev, float t, long long U, long 
 {
     adw_mlp_launch(h, true, h->abeta0_u.p, h->abeta1_u.p, nullptr, nullptr, t, U, h->aemb_u.p, nullptr);   // beta_embed([b0, b1, t])
     adw_mlp_launch(h, false, x_dev, nullptr, h->aemb_u.p, h->aidx.p, t, B, out_dev, out_div);             // net([x, t, embed])
+}
+
+// per-row times: beta_embed([b0_i, b1_i, t_i]) per row (no dedupe: the time differs per row), then net([x_i, t_i, emb_i]).
+// beta0 / beta1 / tv are device pointers [B].
+void adw_drift_tv_dev(ti_handle* h, const float* x_dev, const float* tv, const float* beta0, const float* beta1, long long B, float* out_dev,
+                      float* out_div)
+{
+    if (h->aemb_r.n < (size_t)B) h->aemb_r.alloc(B);
+    adw_mlp_launch(h, true, beta0, beta1, tv, nullptr, 0.f, B, h->aemb_r.p, nullptr);          // a2 = emb[r] = t_r
+    adw_mlp_launch(h, false, x_dev, tv, h->aemb_r.p, nullptr, 0.f, B, out_dev, out_div);       // a1 = in1[r] = t_r
+}
+
+// device copies of per-row beta0 / beta1 (host memory is staged into the handle; device pointers are used as they are)
+void adw_rows_dev(ti_handle* h, const float* beta0, const float* beta1, long long B, int mem, const float** b0d, const float** b1d)
+{
+    if (mem == TI_MEM_DEVICE) { *b0d = beta0; *b1d = beta1; return; }
+    if (h->abeta0_r.n < (size_t)B) { h->abeta0_r.alloc(B); h->abeta1_r.alloc(B); }
+    HIP_CHECK(hipMemcpyAsync(h->abeta0_r.p, beta0, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->abeta1_r.p, beta1, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    *b0d = h->abeta0_r.p; *b1d = h->abeta1_r.p;
 }
 
 void ensure_adw_ws(ti_handle* h, long long B)
@@ -1102,12 +1130,129 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
     return flag ? fail(TI_E_NAN, "non-finite value in the final state") : TI_OK;
 }
 
+// ---- dopri5 with per-trajectory step control (TI_SCHEME_DOPRI5_TRAJ): trajectory b of m floats (plus its dlogp entry) runs the
+// algorithm of rollout_rk above on its own -- initial step from its own norms, its own accept / reject decisions, step sizes and
+// dense output (ode_kernels.hip, TrajRkParams) -- inside batched drift launches that take one stage time per trajectory
+// (drift(x, tv, out, out_div), tv a device array [B]).  The batch takes as many attempts as its hardest trajectory; a finished
+// (frozen) trajectory is evaluated along but never written again.  One small status read-back per attempt, as in rollout_rk.
+template <typename DriftTv>
+int rollout_rk_traj(ti_handle* h, const ti_rollout_desc* rd, float* x, long long B, long long m, float* out_path, int64_t* n_fevals,
+                    DriftTv&& drift, DlogpAux aux = DlogpAux())
+{
+    hipStream_t st = h->stream;
+    const int nseg = aux.dl ? 2 : 1, N = rd->n_step;
+    const size_t n = (size_t)B * m, ndl = aux.dl ? (size_t)B : 0, sn[2] = {n, ndl};
+    const size_t per = 14;                                   // per segment k[7], ytmp, ynew, coef[5]
+    if (h->rk_ws.n < per * (n + ndl)) h->rk_ws.alloc(per * (n + ndl));
+    if (h->rk_ctl.n < (size_t)B) h->rk_ctl.alloc(B);
+    if (h->rk_tv.n < (size_t)B) h->rk_tv.alloc(B);
+    if (h->rk_status.n < (size_t)TRAJ_ST_N) h->rk_status.alloc(TRAJ_ST_N);
+    const int total_rows = (int)ti_rollout_rows(N, rd->save_every);
+    const bool host_out = rd->mem == TI_MEM_HOST;            // rows are written on the device and copied out as they complete
+    float* path_dev = out_path;
+    float* dl_dev = aux.out;
+    if (host_out) {
+        if (h->rk_path.n < (size_t)total_rows * n) h->rk_path.alloc((size_t)total_rows * n);
+        path_dev = h->rk_path.p;
+        if (aux.dl) { if (h->rk_dpath.n < (size_t)total_rows * ndl) h->rk_dpath.alloc((size_t)total_rows * ndl); dl_dev = h->rk_dpath.p; }
+    }
+    const double sign = (N > 1 && rd->t_grid[1] < rd->t_grid[0]) ? -1.0 : 1.0;
+    {
+        std::vector<double> g(N);
+        for (int i = 0; i < N; ++i) g[i] = sign * (double)rd->t_grid[i];
+        h->rk_grid.upload(g);
+    }
+    TrajRkParams p{};
+    p.nseg = nseg; p.B = B; p.ctl = h->rk_ctl.p; p.tv = h->rk_tv.p; p.status = h->rk_status.p; p.grid = h->rk_grid.p;
+    p.n_grid = N; p.save_every = rd->save_every; p.total_rows = total_rows; p.sign = sign; p.t_first = sign * (double)rd->t_grid[0];
+    p.rtol = rd->rtol; p.atol = rd->atol; p.max_attempts = 10000000LL;
+    {
+        float* w = h->rk_ws.p;
+        float* y[2] = {x, aux.dl};
+        for (int s2 = 0; s2 < nseg; ++s2) {
+            TrajSeg& g = p.seg[s2];
+            for (int j = 0; j < 7; ++j) { g.k[j] = w; w += sn[s2]; }
+            g.ytmp = w; w += sn[s2]; g.ynew = w; w += sn[s2]; g.coef = w; w += 5 * sn[s2];
+            g.y = y[s2]; g.m = s2 ? 1 : m; g.out = s2 ? dl_dev : path_dev; g.out_scale = s2 ? aux.out_scale : 1.0f;
+        }
+    }
+    if (aux.dl) HIP_CHECK(hipMemsetAsync(aux.dl, 0, ndl * sizeof(float), st));
+    int64_t fe = 0;
+    auto F = [&](int which) {                                // k[which] = f(s, y_in) at the stage times in rk_tv
+        float* yin[2] = {which == 0 ? p.seg[0].y : which == 6 ? p.seg[0].ynew : p.seg[0].ytmp,
+                         aux.dl ? (which == 0 ? p.seg[1].y : which == 6 ? p.seg[1].ynew : p.seg[1].ytmp) : nullptr};
+        drift(yin[0], h->rk_tv.p, p.seg[0].k[which], aux.dl ? aux.d1 : nullptr); ++fe;
+        if (aux.dl) HIP_CHECK(launch_scale(p.seg[1].k[which], aux.d1, (float)(-sign) * aux.div_scale, (long long)ndl, st));
+        if (sign < 0) HIP_CHECK(launch_scale(p.seg[0].k[which], p.seg[0].k[which], -1.0f, (long long)n, st));
+    };
+    auto wants_row0 = rd->save_every > 0 || N == 1;
+    if (wants_row0) {
+        HIP_CHECK(hipMemcpyAsync(path_dev, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (aux.dl) HIP_CHECK(launch_scale(dl_dev, aux.dl, aux.out_scale, (long long)ndl, st));
+    }
+    {
+        const float t0f = (float)(sign * (double)(float)p.t_first);
+        uint32_t bits; std::memcpy(&bits, &t0f, 4);
+        HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->rk_tv.p), (int)bits, (size_t)B, st));
+    }
+    F(0);
+    HIP_CHECK(launch_traj_init(p, 0, st));                    // _select_initial_step, per trajectory
+    F(1);
+    HIP_CHECK(launch_traj_init(p, 1, st));
+    float c_err[7], c_mid[7];
+    for (int j = 0; j < 7; ++j) { c_err[j] = (float)dp5::c_error[j]; c_mid[j] = (float)dp5::c_mid[j]; }
+    int status[TRAJ_ST_N] = {0, 0, INT_MAX, INT_MAX, INT_MAX, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(h->rk_status.p, status, sizeof(status), hipMemcpyHostToDevice, st));
+    int copied = 0;                                           // rows already copied to the host
+    auto copy_rows = [&](int upto) {
+        if (!host_out || upto <= copied) return;
+        HIP_CHECK(hipMemcpyAsync(out_path + (size_t)copied * n, path_dev + (size_t)copied * n, (size_t)(upto - copied) * n * sizeof(float),
+                                 hipMemcpyDeviceToHost, st));
+        if (aux.dl) HIP_CHECK(hipMemcpyAsync(aux.out + (size_t)copied * ndl, dl_dev + (size_t)copied * ndl, (size_t)(upto - copied) * ndl * sizeof(float),
+                                             hipMemcpyDeviceToHost, st));
+        copied = upto;
+    };
+    for (bool active = N > 1; active;) {
+        HIP_CHECK(hipMemsetAsync(h->rk_status.p, 0, 2 * sizeof(int), st));        // active count, rows missing
+        for (int sidx = 0; sidx < 6; ++sidx) {                                   // _runge_kutta_step, every trajectory with its own dt
+            float c[6];
+            for (int j = 0; j <= sidx; ++j) c[j] = (float)dp5::beta[sidx][j];
+            HIP_CHECK(launch_traj_stage(p, c, sidx + 1, (float)dp5::alpha[sidx], dp5::alpha[sidx] == 1.0, sidx == 5, sidx == 0, st));
+            F(sidx == 5 ? 6 : sidx + 1);
+        }
+        HIP_CHECK(launch_traj_advance(p, c_err, c_mid, st));
+        HIP_CHECK(hipMemcpyAsync(status, h->rk_status.p, sizeof(status), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (status[TRAJ_ST_UNDERFLOW] != INT_MAX)
+            return fail(TI_E_NAN, "dopri5 (per trajectory): step size underflow in trajectory " + std::to_string(status[TRAJ_ST_UNDERFLOW]));
+        if (status[TRAJ_ST_NAN] != INT_MAX)
+            return fail(TI_E_NAN, "dopri5 (per trajectory): non-finite error estimate in trajectory " + std::to_string(status[TRAJ_ST_NAN]));
+        if (status[TRAJ_ST_LIMIT] != INT_MAX)
+            return fail(TI_E_NAN, "dopri5 (per trajectory): more than 1e7 step attempts in trajectory " + std::to_string(status[TRAJ_ST_LIMIT]));
+        copy_rows(total_rows - status[TRAJ_ST_MISSING]);                          // completed-row watermark
+        active = status[TRAJ_ST_ACTIVE] > 0;
+    }
+    copy_rows(total_rows);
+    std::vector<TrajCtl> ctl(B);
+    HIP_CHECK(hipMemcpyAsync(ctl.data(), h->rk_ctl.p, (size_t)B * sizeof(TrajCtl), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemsetAsync(h->nanflag.p, 0, sizeof(int), st));
+    HIP_CHECK(launch_nan_check(x, (long long)n, h->nanflag.p, st));
+    int flag = 0;
+    HIP_CHECK(hipMemcpyAsync(&flag, h->nanflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    h->traj_accepted.resize(B); h->traj_rejected.resize(B);
+    for (long long b = 0; b < B; ++b) { h->traj_accepted[b] = ctl[b].accepted; h->traj_rejected[b] = ctl[b].rejected; }
+    if (n_fevals) *n_fevals = fe;
+    return flag ? fail(TI_E_NAN, "non-finite value in the final state") : TI_OK;
+}
+
 int check_rollout_desc(const ti_rollout_desc* rd)
 {
     if (!rd || !rd->t_grid) return fail(TI_E_ARG, "rollout desc / t_grid is NULL");
     if (rd->n_step < 1) return fail(TI_E_ARG, "n_step must be >= 1");
-    if (rd->scheme < TI_SCHEME_EULER || rd->scheme > TI_SCHEME_RK4) return fail(TI_E_ARG, "unknown scheme");
-    if (rd->scheme == TI_SCHEME_DOPRI5 && !(rd->rtol > 0.f && rd->atol > 0.f)) return fail(TI_E_ARG, "dopri5 needs rtol > 0 and atol > 0");
+    if (rd->scheme < TI_SCHEME_EULER || rd->scheme > TI_SCHEME_DOPRI5_TRAJ) return fail(TI_E_ARG, "unknown scheme");
+    const bool adaptive = rd->scheme == TI_SCHEME_DOPRI5 || rd->scheme == TI_SCHEME_DOPRI5_TRAJ;
+    if (adaptive && !(rd->rtol > 0.f && rd->atol > 0.f)) return fail(TI_E_ARG, "dopri5 needs rtol > 0 and atol > 0");
     if (rd->scheme >= TI_SCHEME_DOPRI5)
         for (int k = 0; k + 2 < rd->n_step; ++k)
             if ((rd->t_grid[k + 1] > rd->t_grid[k]) != (rd->t_grid[k + 2] > rd->t_grid[k + 1]) || rd->t_grid[k + 1] == rd->t_grid[k])
@@ -1253,11 +1398,36 @@ int ti_painn_drift(ti_handle* h, const float* x, float t, const float* cond, int
     });
 }
 
+int ti_painn_drift_tv(ti_handle* h, const float* x, const float* t, const float* cond, int64_t B, float* out, int mem)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (B < 0 || (B > 0 && (!x || !t || !out || (h->ncond > 0 && !cond)))) return fail(TI_E_ARG, "NULL buffer");
+    if (B == 0) return TI_OK;
+    return guarded([&]() -> int {
+        set_device(h);
+        select_template(h, B);
+        ensure_painn_ws(h, B);
+        const size_t n = (size_t)B * h->d.n_atoms * 3, nc = (size_t)B * h->d.n_atoms * h->ncond;
+        const float *xd = x, *cd = cond, *td = t; float* od = out;
+        if (mem == TI_MEM_HOST) {
+            if (h->rk_tv.n < (size_t)B) h->rk_tv.alloc(B);
+            HIP_CHECK(hipMemcpyAsync(h->x.p, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            if (nc) HIP_CHECK(hipMemcpyAsync(h->cond.p, cond, nc * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(h->rk_tv.p, t, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            xd = h->x.p; cd = h->cond.p; td = h->rk_tv.p; od = h->b1.p;
+        }
+        painn_drift_dev(h, xd, 0.f, cd, B, od, nullptr, td);
+        if (mem == TI_MEM_HOST && h->tap < 0) HIP_CHECK(hipMemcpyAsync(out, od, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return TI_OK;
+    });
+}
+
 int ti_painn_rollout(ti_handle* h, const ti_rollout_desc* rd, const float* x0, const float* cond, int64_t B, float* out_path,
                      int64_t* n_fevals)
 {
+    if (int rc = check_rollout_desc(rd)) return rc;          // first: needs no handle
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
-    if (int rc = check_rollout_desc(rd)) return rc;
     if (B < 0 || (B > 0 && (!x0 || !out_path || (h->ncond > 0 && !cond)))) return fail(TI_E_ARG, "NULL buffer");
     if (B == 0) { if (n_fevals) *n_fevals = 0; return TI_OK; }
     return guarded([&]() -> int {
@@ -1272,7 +1442,9 @@ int ti_painn_rollout(ti_handle* h, const ti_rollout_desc* rd, const float* x0, c
         if (rd->mem == TI_MEM_HOST && nc) { HIP_CHECK(hipMemcpyAsync(h->cond.p, cond, nc * sizeof(float), hipMemcpyHostToDevice, h->stream)); cd = h->cond.p; }
         const int saved_tap = h->tap; h->tap = -1;
         auto drift = [&](const float* xs, float t, float* o, float*) { painn_drift_dev(h, xs, t, cd, B, o); };
-        const int rc = rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift)
+        auto drift_tv = [&](const float* xs, const float* tv, float* o, float*) { painn_drift_dev(h, xs, 0.f, cd, B, o, nullptr, tv); };
+        const int rc = rd->scheme == TI_SCHEME_DOPRI5_TRAJ ? rollout_rk_traj(h, rd, h->x.p, B, A * 3, out_path, n_fevals, drift_tv)
+                     : rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift)
                                                       : rollout_common(h, rd, h->x.p, h->b1.p, h->b2.p, h->xt.p, n, B, A * 3, A, out_path, n_fevals, drift);
         h->tap = saved_tap;
         return rc;
@@ -1338,6 +1510,36 @@ int ti_painn_drift_div(ti_handle* h, const float* x, float t, const float* cond,
     });
 }
 
+int ti_painn_drift_div_tv(ti_handle* h, const float* x, const float* t, const float* cond, int64_t B, float* out, float* out_div, int mem)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (h->d.precision == TI_PREC_F16) return fail(TI_E_UNSUPPORTED, "the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)");
+    if (B < 0 || (B > 0 && (!x || !t || !out || !out_div || (h->ncond > 0 && !cond)))) return fail(TI_E_ARG, "NULL buffer");
+    if (B == 0) return TI_OK;
+    if (h->tap >= 0) return fail(TI_E_ARG, "debug taps apply to ti_painn_drift / ti_painn_drift_jvp only");
+    return guarded([&]() -> int {
+        set_device(h);
+        select_template(h, B, false);
+        ensure_painn_ws(h, B);
+        const size_t n = (size_t)B * h->d.n_atoms * 3, nc = (size_t)B * h->d.n_atoms * h->ncond;
+        const float *xd = x, *cd = cond, *td = t; float *od = out, *dd = out_div;
+        if (mem == TI_MEM_HOST) {
+            if (h->rk_tv.n < (size_t)B) h->rk_tv.alloc(B);
+            HIP_CHECK(hipMemcpyAsync(h->x.p, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            if (nc) HIP_CHECK(hipMemcpyAsync(h->cond.p, cond, nc * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(h->rk_tv.p, t, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            xd = h->x.p; cd = h->cond.p; td = h->rk_tv.p; od = h->b1.p; dd = h->divb.p;
+        }
+        painn_drift_div_dev(h, xd, 0.f, cd, B, od, dd, td);
+        if (mem == TI_MEM_HOST) {
+            HIP_CHECK(hipMemcpyAsync(out, od, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipMemcpyAsync(out_div, dd, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return TI_OK;
+    });
+}
+
 int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float* x0, const float* cond, int64_t B, float div_scale,
                            float out_scale, int reverse_ode, float* out_path, float* out_dlogp, int64_t* n_fevals)
 {
@@ -1368,7 +1570,15 @@ int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float*
                 HIP_CHECK(launch_scale(dv, dv, -1.0f, (long long)B, h->stream));
             }
         };
-        const int rc = rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift, aux)
+        auto drift_tv = [&](const float* xs, const float* tv, float* o, float* dv) {
+            painn_drift_div_dev(h, xs, 0.f, cd, B, o, dv, tv);
+            if (reverse_ode) {
+                HIP_CHECK(launch_scale(o, o, -1.0f, (long long)n, h->stream));
+                HIP_CHECK(launch_scale(dv, dv, -1.0f, (long long)B, h->stream));
+            }
+        };
+        const int rc = rd->scheme == TI_SCHEME_DOPRI5_TRAJ ? rollout_rk_traj(h, rd, h->x.p, B, A * 3, out_path, n_fevals, drift_tv, aux)
+                     : rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift, aux)
                                                       : rollout_common(h, rd, h->x.p, h->b1.p, h->b2.p, h->xt.p, n, B, A * 3, A, out_path, n_fevals, drift, aux);
         h->tap = saved_tap;
         return rc;
@@ -1553,6 +1763,34 @@ int ti_adw_drift_div(ti_handle* h, const float* x, float t, const float* beta0, 
     return adw_drift_impl(h, x, t, beta0, beta1, B, out, out_div, mem);
 }
 
+int ti_adw_drift_tv(ti_handle* h, const float* x, const float* t, const float* beta0, const float* beta1, int64_t B, float* out,
+                    float* out_div, int mem)
+{
+    if (!h || h->kind != 1) return fail(TI_E_ARG, "not an adw handle");
+    if (B < 0 || (B > 0 && (!x || !t || !beta0 || !beta1 || !out))) return fail(TI_E_ARG, "NULL buffer");
+    if (B == 0) return TI_OK;
+    return guarded([&]() -> int {
+        set_device(h);
+        ensure_adw_ws(h, B);
+        const float *b0d = nullptr, *b1d = nullptr;
+        adw_rows_dev(h, beta0, beta1, B, mem, &b0d, &b1d);
+        const float *xd = x, *td = t; float* od = out; float* dd = out_div;
+        if (mem == TI_MEM_HOST) {
+            if (h->atv.n < (size_t)B) h->atv.alloc(B);
+            HIP_CHECK(hipMemcpyAsync(h->ax.p, x, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(h->atv.p, t, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            xd = h->ax.p; td = h->atv.p; od = h->ab1.p; dd = out_div ? h->ad1.p : nullptr;
+        }
+        adw_drift_tv_dev(h, xd, td, b0d, b1d, B, od, dd);
+        if (mem == TI_MEM_HOST) {
+            HIP_CHECK(hipMemcpyAsync(out, od, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            if (out_div) HIP_CHECK(hipMemcpyAsync(out_div, dd, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return TI_OK;
+    });
+}
+
 static int adw_rollout_impl(ti_handle* h, const ti_rollout_desc* rd, const float* x0, const float* beta0, const float* beta1, int64_t B,
                             float* out_path, float* out_dlogp, int64_t* n_fevals)
 {
@@ -1572,6 +1810,12 @@ static int adw_rollout_impl(ti_handle* h, const ti_rollout_desc* rd, const float
         DevBuf<float> scaled_tmp;                    // dlogp * 1e2 staging for the saved rows
         if (out_dlogp) { scaled_tmp.alloc(B); aux.dl = h->adl.p; aux.d1 = h->ad1.p; aux.d2 = h->ad2.p; aux.scaled = scaled_tmp.p; aux.out = out_dlogp; }
         auto drift = [&](const float* xs, float t, float* o, float* dv) { adw_drift_dev(h, xs, t, U, B, o, dv); };
+        if (rd->scheme == TI_SCHEME_DOPRI5_TRAJ) {
+            const float *b0d = nullptr, *b1d = nullptr;
+            adw_rows_dev(h, beta0, beta1, B, rd->mem, &b0d, &b1d);
+            auto drift_tv = [&](const float* xs, const float* tv, float* o, float* dv) { adw_drift_tv_dev(h, xs, tv, b0d, b1d, B, o, dv); };
+            return rollout_rk_traj(h, rd, h->ax.p, B, 1, out_path, n_fevals, drift_tv, aux);
+        }
         if (rd->scheme >= TI_SCHEME_DOPRI5) return rollout_rk(h, rd, h->ax.p, (size_t)B, out_path, n_fevals, drift, aux);
         return rollout_common(h, rd, h->ax.p, h->ab1.p, h->ab2.p, h->axt.p, (size_t)B, B, 1, 0, out_path, n_fevals, drift, aux);
     });
@@ -1591,6 +1835,16 @@ int ti_adw_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float* x
 }
 
 // --------------------------------------------------------------------------------------------------------- shared
+int ti_rollout_step_counts(ti_handle* h, int64_t* accepted, int64_t* rejected, int64_t B)
+{
+    if (!h || !accepted || !rejected) return fail(TI_E_ARG, "NULL argument");
+    if (B != (int64_t)h->traj_accepted.size())
+        return fail(TI_E_ARG, "B = " + std::to_string(B) + " does not match the last per-trajectory rollout (" + std::to_string(h->traj_accepted.size()) + " trajectories)");
+    std::copy(h->traj_accepted.begin(), h->traj_accepted.end(), accepted);
+    std::copy(h->traj_rejected.begin(), h->traj_rejected.end(), rejected);
+    return TI_OK;
+}
+
 void ti_destroy(ti_handle* h)
 {
     if (!h) return;

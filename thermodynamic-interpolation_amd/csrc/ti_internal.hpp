@@ -97,6 +97,7 @@ struct EmbedParams {
     const float* atom_emb; const int32_t* atom_ids; const float* cond;
     int ncond, A; long long N;
     float t, temp_length, time_length, temp_mean, temp_range;
+    const float* tv;                        // non-NULL: per-molecule times [B] (node nd reads tv[nd / A]) instead of t
     float* s; float* P;
 };
 
@@ -219,5 +220,46 @@ hipError_t launch_scaled_sumsq(double* out, double* partial, const float* a, con
 hipError_t launch_interp_fit(float* coef /*[5][n]*/, const float* y0, const float* y1, const float* f0, const float* f1, const RkComb& mid,
                              float dt, long long n, hipStream_t st);
 hipError_t launch_interp_eval(float* out, const float* coef, float x, long long n, hipStream_t st);
+
+// ---- per-trajectory dopri5 (ode_kernels.hip; driver: ti_api.hip rollout_rk_traj).  Every trajectory b runs the shared algorithm
+// on its own: segment s holds m_s floats per trajectory (segment 0: x, 3A or 1; segment 1: its dlogp entry, m = 1), laid out
+// trajectory-major.  Controller state is fp64 in the integration variable s = sign * t.  A trajectory whose interval has passed the
+// last grid time is frozen: its state, k and path rows are never written again (it still rides along in the batched drift launches).
+struct TrajCtl {
+    double t0, t1, dt;              // interval [t0, t1] of the last accepted step (dense output), next step size
+    double h0, d1;                  // initial-step scratch (_select_initial_step)
+    int next;                       // next grid index to emit; == n_grid: finished
+    int rows;                       // path rows written so far
+    int accepted, rejected;
+};
+struct TrajSeg {
+    float *y, *ytmp, *ynew, *coef;  // coef: [5][B*m]
+    float* k[7];
+    float* out;                     // path rows [rows][B*m] (device: the caller's buffer or a staging copy)
+    long long m;
+    float out_scale;                // rows are written * out_scale (the dlogp convention; 1 for x)
+};
+enum { TRAJ_ST_ACTIVE = 0, TRAJ_ST_MISSING = 1, TRAJ_ST_UNDERFLOW = 2, TRAJ_ST_NAN = 3, TRAJ_ST_LIMIT = 4, TRAJ_ST_N = 8 };
+struct TrajRkParams {
+    TrajSeg seg[2]; int nseg;
+    long long B;
+    TrajCtl* ctl;
+    float* tv;                      // [B] fp32 drift time of each trajectory for the next evaluation (original t, sign applied)
+    int* status;                    // [TRAJ_ST_N]: active count, most rows any trajectory still owes (reset per attempt); the first
+                                    // trajectory that underflowed / got a NaN ratio / passed the attempt limit (INT_MAX: none)
+    const double* grid;             // [n_grid] sign * t_grid
+    int n_grid, save_every, total_rows;
+    double sign, t_first;
+    float rtol, atol;
+    long long max_attempts;
+};
+// phase 0: d0, d1, h0 from y and k[0], ytmp = y + h0 k[0], tv = t_first + h0;  phase 1: d2 from k[1], dt, controller reset
+hipError_t launch_traj_init(const TrajRkParams& p, int phase, hipStream_t st);
+// stage input y + sum_{j<nk} (c_j dt_b) k_j into ytmp (to_ynew = 0) or ynew, and tv[b] = t_b + alpha dt_b (alpha_one: one ulp
+// below t_b + dt_b); frozen trajectories copy y.  stage 0 also checks step underflow and the attempt limit.
+hipError_t launch_traj_stage(const TrajRkParams& p, const float* c, int nk, float alpha, int alpha_one, int to_ynew, int stage0,
+                             hipStream_t st);
+// error ratio, accept / reject, dense-output fit, FSAL copy, step factor, emission of the grid rows the accepted step crossed
+hipError_t launch_traj_advance(const TrajRkParams& p, const float* c_error /*[7]*/, const float* c_mid /*[7]*/, hipStream_t st);
 
 }  // namespace ti

@@ -4,9 +4,10 @@ One process per GPU (``torch.distributed``; backend "nccl" is RCCL over xGMI on 
 reference has no distributed path at all; trajectories never interact (edges never cross molecules), so
 there is no exchange step during integration and none is invented here.  Per-trajectory RNG is keyed by the GLOBAL
 trajectory index (``traj_offset``; a trajectory continued by a second call passes ``step_offset``), and ``pin_template`` fixes
-the edge-row layout to the one the GLOBAL batch would get, so fixed-step samples are bit-identical for every rank count
-(the adaptive ``dopri5`` chooses its steps from rank-local error norms, like the reference does per mini-batch: there the
-agreement is to solver tolerance).
+the edge-row layout to the one the GLOBAL batch would get, so fixed-step samples are bit-identical for every rank count.
+The adaptive ``dopri5`` has two modes: step_control='batch' chooses its steps from rank-local error norms, like the reference does
+per mini-batch (agreement to solver tolerance across rank counts); step_control='trajectory' gives every trajectory its own steps,
+which is shard-local by construction and needs no collective: with ``pin_template`` it is bit-identical for every rank count.
 """
 from __future__ import annotations
 

@@ -7,7 +7,9 @@
 
 Differences, on purpose: `method` comes from ``config.method`` (default 'dopri5' like the reference's hard-coded solver; any
 name of thermo._common.SUPPORTED works); files are written once per call instead of re-saving the growing concatenation after every batch
-(O(n_batches^2) I/O in the reference); datasets are the numpy ones of ``data.py``.
+(O(n_batches^2) I/O in the reference); datasets are the numpy ones of ``data.py``.  ``config.step_control`` (optional, default
+'batch'): 'trajectory' gives every molecule / particle its own dopri5 step sizes, so its sample and dlogp equal the reference's at
+batch size 1 whatever ``batch_size`` is.
 """
 from __future__ import annotations
 
@@ -41,7 +43,7 @@ def sample_ambient(config, b, dataset):
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
-                                         save_every=getattr(config, "save_every", 1))
+                                         save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"))
     latent_noises, latent_dlogps, samples, dlogps, n_fevals = [], [], [], [], 0
     b.eval()
     for batch in dataset.batches(config.batch_size, shuffle=True, seed=config.seed):
@@ -65,7 +67,7 @@ def sample_latent(config, b, dataset):
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
-                                         save_every=getattr(config, "save_every", 1))
+                                         save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"))
     samples, dlogps = [], []
     b.eval()
     for batch in dataset.batches(config.batch_size, seed=config.seed, drop_last=True):
@@ -84,7 +86,8 @@ def sample_adw(config, b, x0s_batches):
     """`x0s_batches`: iterable of (x0s [B,1], beta0s [B,1]) like the reference's test loader (adw/sample.py:41-43)."""
     assert len(config.beta0s) == len(config.beta1s) == 1            # adw/sample.py:24
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
-                                         atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp))
+                                         atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),
+                                         step_control=getattr(config, "step_control", "batch"))
     initial, samples, dlogps = [], [], []
     b.eval()
     for x0s, beta0s in x0s_batches:

@@ -36,14 +36,31 @@ def _time_grid_numpy(start: float, end: float, n_step: int) -> np.ndarray:
     return np.where(i < n_step // 2, lo, hi).astype(np.float32)
 
 
-def _rollout_desc(scheme, t_grid, save_every, mem, eps, seed, traj_offset, com_free_noise, rtol=0.0, atol=0.0, step_offset=0):
-    t_grid = np.ascontiguousarray(t_grid, np.float32)
-    if t_grid.ndim != 1 or t_grid.size < 1:
-        raise ValueError("t_grid must be a non-empty 1-D array")
+STEP_CONTROLS = ("batch", "trajectory")
+
+
+def scheme_code(scheme, step_control="batch"):
+    """TI_SCHEME_* of a scheme name.  step_control: 'batch' (one step size for the whole call, torchdiffeq's odeint per mini-batch)
+    or 'trajectory' (dopri5 only: every trajectory gets the steps a batch of one would take -- TI_SCHEME_DOPRI5_TRAJ)."""
+    if step_control not in STEP_CONTROLS:
+        raise ValueError(f"unknown step_control {step_control!r}; expected one of {STEP_CONTROLS}")
     if isinstance(scheme, str):
         if scheme not in _lib.SCHEMES:
             raise ValueError(f"unknown scheme {scheme!r}; expected one of {sorted(_lib.SCHEMES)}")
         scheme = _lib.SCHEMES[scheme]
+    if step_control == "trajectory":
+        if scheme != _lib.SCHEMES["dopri5"]:
+            raise ValueError("step_control='trajectory' needs the adaptive scheme 'dopri5'")
+        scheme = _lib.SCHEME_DOPRI5_TRAJ
+    return scheme
+
+
+def _rollout_desc(scheme, t_grid, save_every, mem, eps, seed, traj_offset, com_free_noise, rtol=0.0, atol=0.0, step_offset=0,
+                  step_control="batch"):
+    t_grid = np.ascontiguousarray(t_grid, np.float32)
+    if t_grid.ndim != 1 or t_grid.size < 1:
+        raise ValueError("t_grid must be a non-empty 1-D array")
+    scheme = scheme_code(scheme, step_control)
     rd = _lib.RolloutDesc(scheme, t_grid.size, int(save_every), mem, float(eps), int(bool(com_free_noise)), int(seed),
                           int(traj_offset), _lib.fptr(t_grid), float(rtol), float(atol), int(step_offset))
     rd._keep = t_grid
@@ -115,6 +132,21 @@ class _Engine:
         _lib.check(_lib.lib().ti_profile_read(self.h, _lib.KERNELS[kernel], C.byref(n), C.byref(ms)))
         return n.value, ms.value
 
+    def step_counts(self, B: int):
+        """(accepted [B], rejected [B]) int64 step counts of every trajectory of the last step_control='trajectory' rollout."""
+        acc, rej = np.zeros(int(B), np.int64), np.zeros(int(B), np.int64)
+        p = C.POINTER(C.c_int64)
+        _lib.check(_lib.lib().ti_rollout_step_counts(self.h, acc.ctypes.data_as(p), rej.ctypes.data_as(p), int(B)))
+        return acc, rej
+
+    def _times(self, t, B):
+        """A 1-D time vector of length B (one time per molecule / row) as a buffer spec, or None for a scalar t."""
+        if (tuple(t.shape) if hasattr(t, "shape") else np.shape(t)) == ():
+            return None
+        if len(t.shape) != 1 or int(t.shape[0]) != B:
+            raise ValueError(f"t must be a scalar or a 1-D array of length B = {B}")
+        return (t, (B,), False, "t")
+
 
 class PainnEngine(_Engine):
     """cPaiNN drift + fixed-step integrator for one molecular species (homogeneous batches)."""
@@ -161,23 +193,30 @@ class PainnEngine(_Engine):
         return (cond if self.ncond else None, (B, self.A, self.ncond), False, "cond")
 
     def drift(self, x, t, cond=None, out=None):
-        """x [B,A,3] -> drift [B,A,3] at time t."""
+        """x [B,A,3] -> drift [B,A,3] at time t: a scalar, or a 1-D array of B times (one per molecule)."""
         B = self._check_x(x)
         if out is None:
             out = _alloc_like(x if hasattr(x, "data_ptr") and x.is_cuda else None, (B, self.A, 3))
+        tv = self._times(t, B)
+        if tv is not None:
+            (xp, tp, cp, op), dev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), tv, self._cond_spec(cond, B), (out, (B, self.A, 3), True, "out"))
+            _lib.check(_lib.lib().ti_painn_drift_tv(self.h, xp, tp, cp, B, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+            return out
         (xp, cp, op), dev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), self._cond_spec(cond, B), (out, (B, self.A, 3), True, "out"))
         _lib.check(_lib.lib().ti_painn_drift(self.h, xp, float(t), cp, B, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return out
 
     def rollout(self, x0, cond, t_grid, scheme="euler", save_every=1, eps=0.0, seed=0, traj_offset=0, com_free_noise=False, out=None,
-                rtol=1e-4, atol=1e-4, step_offset=0):
+                rtol=1e-4, atol=1e-4, step_offset=0, step_control="batch"):
         """Returns (path [rows,B,A,3], n_fevals).  scheme: 'euler' | 'heun' | 'em' | 'midpoint' | 'rk4' on the grid, or 'dopri5'
         (adaptive, tolerances rtol / atol; the grid then only selects the output times).  step_offset: EM noise counter of the
-        call's first step (pass the number of steps already taken when continuing a trajectory)."""
+        call's first step (pass the number of steps already taken when continuing a trajectory).  step_control='trajectory' (dopri5
+        only): every molecule gets its own step sizes -- the result a batch of one gives; n_fevals then counts batched evaluations
+        and step_counts(B) returns the per-molecule accepted / rejected steps."""
         B = self._check_x(x0, "x0")
         on_gpu = hasattr(x0, "data_ptr") and x0.is_cuda
         rd = _rollout_desc(scheme, t_grid, save_every, _lib.MEM_DEVICE if on_gpu else _lib.MEM_HOST, eps, seed, traj_offset, com_free_noise,
-                           rtol, atol, step_offset)
+                           rtol, atol, step_offset, step_control)
         rows = int(_lib.lib().ti_rollout_rows(rd.n_step, rd.save_every))
         if out is None:
             out = _alloc_like(x0 if on_gpu else None, (rows, B, self.A, 3))
@@ -198,21 +237,29 @@ class PainnEngine(_Engine):
         return out, tan
 
     def drift_div(self, x, t, cond=None):
-        """(b(x) [B,A,3], div [B]) with div = sum_ij d b_ij / d x_ij -- the reference's compute_divergence without its 1e-2."""
+        """(b(x) [B,A,3], div [B]) with div = sum_ij d b_ij / d x_ij -- the reference's compute_divergence without its 1e-2.
+        t: a scalar or one time per molecule ([B])."""
         B = self._check_x(x)
         like = x if hasattr(x, "data_ptr") and x.is_cuda else None
         out, div = _alloc_like(like, (B, self.A, 3)), _alloc_like(like, (B,))
+        tv = self._times(t, B)
+        if tv is not None:
+            (xp, tp, cp, op, dp), dev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), tv, self._cond_spec(cond, B), (out, None, True, "out"),
+                                                         (div, None, True, "out_div"))
+            _lib.check(_lib.lib().ti_painn_drift_div_tv(self.h, xp, tp, cp, B, op, dp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+            return out, div
         (xp, cp, op, dp), dev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), self._cond_spec(cond, B), (out, None, True, "out"), (div, None, True, "out_div"))
         _lib.check(_lib.lib().ti_painn_drift_div(self.h, xp, float(t), cp, B, op, dp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return out, div
 
     def rollout_dlogp(self, x0, cond, t_grid, scheme="euler", save_every=1, div_scale=1.0, out_scale=1.0, reverse_ode=False,
-                      rtol=1e-4, atol=1e-4):
+                      rtol=1e-4, atol=1e-4, step_control="batch"):
         """Two-state rollout (x, dlogp): returns (path [rows,B,A,3], dlogp [rows,B], n_fevals).  d(dlogp)/dt = -div_scale * div
         (reverse_ode: (-b, +div_scale * div) on the descending grid the caller passes), dlogp is written * out_scale."""
         B = self._check_x(x0, "x0")
         on_gpu = hasattr(x0, "data_ptr") and x0.is_cuda
-        rd = _rollout_desc(scheme, t_grid, save_every, _lib.MEM_DEVICE if on_gpu else _lib.MEM_HOST, 0.0, 0, 0, False, rtol, atol)
+        rd = _rollout_desc(scheme, t_grid, save_every, _lib.MEM_DEVICE if on_gpu else _lib.MEM_HOST, 0.0, 0, 0, False, rtol, atol,
+                           step_control=step_control)
         rows = int(_lib.lib().ti_rollout_rows(rd.n_step, rd.save_every))
         out, dl = _alloc_like(x0 if on_gpu else None, (rows, B, self.A, 3)), _alloc_like(x0 if on_gpu else None, (rows, B))
         (xp, cp, op, dp), dev, keep = self._ptrs((x0, (B, self.A, 3), False, "x0"), self._cond_spec(cond, B), (out, None, True, "out"), (dl, None, True, "out_dlogp"))
@@ -252,12 +299,19 @@ class AdwEngine(_Engine):
             raise _lib.TiError(-1, _lib.last_error())
 
     def drift(self, x, t, beta0, beta1, out=None, return_div=False):
-        """b(x, t) [B]; with return_div also d b / d x (the 1-D divergence, reference scaling NOT applied)."""
+        """b(x, t) [B]; with return_div also d b / d x (the 1-D divergence, reference scaling NOT applied).  t: a scalar or one
+        time per row ([B])."""
         B = int(x.shape[0])
         like = x if hasattr(x, "data_ptr") and x.is_cuda else None
         if out is None:
             out = _alloc_like(like, (B,))
         div = _alloc_like(like, (B,)) if return_div else None
+        tv = self._times(t, B)
+        if tv is not None:
+            (xp, tp, b0p, b1p, op, dp), dev, keep = self._ptrs((x, (B,), False, "x"), tv, (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
+                                                               (out, (B,), True, "out"), (div, None, True, "out_div"))
+            _lib.check(_lib.lib().ti_adw_drift_tv(self.h, xp, tp, b0p, b1p, B, op, dp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+            return (out, div) if return_div else out
         (xp, b0p, b1p, op, dp), dev, keep = self._ptrs((x, (B,), False, "x"), (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
                                                        (out, (B,), True, "out"), (div, None, True, "out_div"))
         mem = _lib.MEM_DEVICE if dev else _lib.MEM_HOST
@@ -268,12 +322,13 @@ class AdwEngine(_Engine):
         return out, div
 
     def rollout(self, x0, beta0, beta1, t_grid, scheme="euler", save_every=1, eps=0.0, seed=0, traj_offset=0, out=None,
-                return_dlogp=False, rtol=1e-4, atol=1e-4, step_offset=0):
-        """(path [rows,B], n_fevals), or (path, dlogp [rows,B] (already * 1e2 like the reference), n_fevals)."""
+                return_dlogp=False, rtol=1e-4, atol=1e-4, step_offset=0, step_control="batch"):
+        """(path [rows,B], n_fevals), or (path, dlogp [rows,B] (already * 1e2 like the reference), n_fevals).  step_control='trajectory'
+        (dopri5 only): every particle gets the steps a batch of one would take (see PainnEngine.rollout)."""
         B = int(x0.shape[0])
         on_gpu = hasattr(x0, "data_ptr") and x0.is_cuda
         rd = _rollout_desc(scheme, t_grid, save_every, _lib.MEM_DEVICE if on_gpu else _lib.MEM_HOST, eps, seed, traj_offset, False, rtol, atol,
-                           step_offset)
+                           step_offset, step_control)
         rows = int(_lib.lib().ti_rollout_rows(rd.n_step, rd.save_every))
         if out is None:
             out = _alloc_like(x0 if on_gpu else None, (rows, B))

@@ -21,6 +21,18 @@ def check_method(method: str) -> str:
     raise ValueError(f"unknown method {method!r}; expected one of {SUPPORTED}")
 
 
+STEP_CONTROLS = ("batch", "trajectory")
+
+
+def check_step_control(step_control: str, method: str) -> str:
+    """'batch' (one step size per call, the reference's behaviour) or 'trajectory' (dopri5 only: per-trajectory step control)."""
+    if step_control not in STEP_CONTROLS:
+        raise ValueError(f"unknown step_control {step_control!r}; expected one of {STEP_CONTROLS}")
+    if step_control == "trajectory" and method != "dopri5":
+        raise ValueError(f"step_control='trajectory' needs method='dopri5' (got {method!r}): the fixed-grid schemes take no step decisions")
+    return step_control
+
+
 def is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "detach")
 

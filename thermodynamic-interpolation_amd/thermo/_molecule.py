@@ -19,6 +19,26 @@ from . import _common as C
 DEFAULT_TEMPS = [300, 400, 500, 600, 700, 800, 900, 1000]
 
 
+def molecule_times(t, B, A, like=None):
+    """batch.t (per node [N], or one value) -> one float for a uniform time, else the [B] float32 per-molecule times (a CUDA tensor
+    when `like` is one).  A time that varies inside a molecule raises ValueError (the drift takes one time per molecule)."""
+    tn = C.to_numpy(t, np.float32).ravel()
+    if tn.size == 0:
+        raise ValueError("batch.t is empty")
+    if np.ptp(tn) == 0.0:
+        return float(tn[0])
+    if tn.size != B * A:
+        raise ValueError(f"batch.t must hold one value or one per node ({B * A}), got {tn.size}")
+    per = tn.reshape(B, A)
+    if np.any(per != per[:, :1]):
+        raise ValueError("batch.t must be constant within each molecule (one time per molecule)")
+    tv = np.ascontiguousarray(per[:, 0])
+    if C.is_cuda(like):
+        import torch
+        return torch.from_numpy(tv).to(like.device)
+    return tv
+
+
 def split_batch(batch, atom_key: str):
     """-> (B, A, edge_src[E_m], edge_dst[E_m], edge_type[E_m], atom_ids[A]); raises ValueError for heterogeneous batches."""
     bidx = C.to_numpy(batch.batch, np.int64)
@@ -114,13 +134,12 @@ class PaiNNShell:
         return np.ascontiguousarray(np.stack(cols, axis=-1))
 
     def forward(self, batch):
-        """Evaluates the drift at batch.x, time batch.t (one value per call) and writes batch.output [N,3] like the reference."""
+        """Evaluates the drift at batch.x, time batch.t (per node: one value for the call, or one value per molecule) and writes
+        batch.output [N,3] like the reference."""
         B, A, src, dst, ety, ids = split_batch(batch, self.ATOM_KEY)
-        t = C.to_numpy(batch.t, np.float64).ravel()
-        if np.ptp(t) != 0.0:
-            raise NotImplementedError("per-molecule times are a training-only input; the sampling path evaluates one t per call")
         x = C.as_f32(batch.x, (B, A, 3))                  # a CUDA batch is evaluated in place, no host round trip
-        out = self.engine_for(A, src, dst, ety, ids).drift(x, float(t[0]), self.cond_of(batch, B, A, C.is_cuda(x)))
+        t = molecule_times(batch.t, B, A, x)
+        out = self.engine_for(A, src, dst, ety, ids).drift(x, t, self.cond_of(batch, B, A, C.is_cuda(x)))
         batch.output = C.like(out.reshape(B * A, 3), batch.x)
         return batch
 
@@ -137,14 +156,17 @@ class ODEWrapperBase:
         self.b, self.return_dlogp, self.reverse_ode = b, return_dlogp, reverse_ode
 
     def _eval(self, batch, x, t, with_div):
+        """t: one float, or batch.t-like per-node times (one value per molecule)."""
         B, A, src, dst, ety, ids = split_batch(batch, self.b.ATOM_KEY)
         xs = C.as_f32(x, (B, A, 3))
+        if not isinstance(t, float):
+            t = molecule_times(t, B, A, xs)
         eng = self.b.engine_for(A, src, dst, ety, ids)
         cond = self.b.cond_of(batch, B, A, C.is_cuda(xs))
         if with_div:
-            out, div = eng.drift_div(xs, float(t), cond)
+            out, div = eng.drift_div(xs, t, cond)
             return out.reshape(B * A, 3), div
-        return eng.drift(xs, float(t), cond).reshape(B * A, 3), None
+        return eng.drift(xs, t, cond).reshape(B * A, 3), None
 
     def forward(self, integration_time, states, batch, n_steps=None):
         if n_steps is not None:
@@ -162,8 +184,8 @@ class ODEWrapperBase:
 
     @classmethod
     def compute_divergence(cls, b, batch):
-        t = float(C.to_numpy(batch.t).reshape(-1)[0])
-        _, div = cls(b)._eval(batch, batch.x, t, True)
+        """div * DIV_SCALE at batch.x and batch.t (one time per call or per molecule, like cPaiNN.forward)."""
+        _, div = cls(b)._eval(batch, batch.x, batch.t, True)
         return C.like(div * cls.DIV_SCALE if C.is_torch(div) else div * np.float32(cls.DIV_SCALE), batch.x)
 
     @staticmethod
@@ -181,20 +203,29 @@ class MoleculeIntegratorBase:
 
     return_dlogp=True integrates the second state of the reference ODEWrapper with the same scheme: d(dlogp)/dt = -DIV_SCALE *
     div b (exact divergence, 3A forward-mode passes per molecule on the GPU), returned * SCALE_DLOGP as [n_saved, B].  With
-    reverse_ode the pair is (-b, +DIV_SCALE * div) on linspace(end, start) (ode_wrapper.py:49, integrators.py:40-43)."""
+    reverse_ode the pair is (-b, +DIV_SCALE * div) on linspace(end, start) (ode_wrapper.py:49, integrators.py:40-43).
+
+    step_control (keyword-only, build-defined): 'batch' (default) -- one step size for the whole batch, the reference's single
+    odeint per mini-batch, so a molecule's result depends on its batch; 'trajectory' (method='dopri5' only) -- every molecule gets
+    its own step sizes, accept / reject decisions and dense output: what the reference computes for it at batch size 1, the same
+    bits for any batch, order or sharding.  self.n_steps_per_molecule then holds (accepted, rejected) [B] of the last rollout."""
     SCALE_DLOGP = 1.0      # integrators.py:68 (ambient: 1e2)
     DIV_SCALE = 1.0        # ode_wrapper.py:91 (ambient: 1e-2)
 
     def __init__(self, b, method: str = "dopri5", n_step: int = 100, atol: float = 1e-4, rtol: float = 1e-4, start: float = 0.0,
                  end: float = 1.0, return_dlogp: bool = False, reverse_ode: bool = False, *, eps: float = 0.0, seed: int = 0,
-                 save_every: int = 1, com_free_noise: bool = False):
+                 save_every: int = 1, com_free_noise: bool = False, step_control: str = "batch"):
         self.method = C.check_method(method)
+        self.step_control = C.check_step_control(step_control, self.method)
         if return_dlogp and self.method == "em" and eps > 0:
             raise ValueError("return_dlogp=True needs a deterministic scheme ('euler' or 'heun')")
         self.b = b
         self.start, self.end, self.rtol, self.atol = start, end, rtol, atol
         self.n_step, self.return_dlogp, self.reverse_ode = n_step, return_dlogp, reverse_ode
         self.eps, self.seed, self.save_every, self.com_free_noise = eps, seed, save_every, com_free_noise
+
+    def _record_counts(self, eng, B):
+        self.n_steps_per_molecule = eng.step_counts(B) if self.step_control == "trajectory" else None
 
     def _rollout(self, batch, traj_offset=0):
         B, A, src, dst, ety, ids = split_batch(batch, self.b.ATOM_KEY)
@@ -208,10 +239,13 @@ class MoleculeIntegratorBase:
                 grid = _engine.time_grid(self.end, self.start, self.n_step)
             path, dl, nfe = eng.rollout_dlogp(x0, self.b.cond_of(batch, B, A, gpu), grid, scheme="euler" if self.method == "em" else self.method,
                                               save_every=self.save_every, div_scale=self.DIV_SCALE, out_scale=self.SCALE_DLOGP,
-                                              reverse_ode=self.reverse_ode, rtol=self.rtol, atol=self.atol)
+                                              reverse_ode=self.reverse_ode, rtol=self.rtol, atol=self.atol, step_control=self.step_control)
+            self._record_counts(eng, B)
             return C.like(path.reshape(path.shape[0], B * A, 3), batch.x0), C.like(dl, batch.x0), nfe
         path, nfe = eng.rollout(x0, self.b.cond_of(batch, B, A, gpu), grid, scheme=self.method, save_every=self.save_every, eps=self.eps,
-                                seed=self.seed, traj_offset=traj_offset, com_free_noise=self.com_free_noise, rtol=self.rtol, atol=self.atol)
+                                seed=self.seed, traj_offset=traj_offset, com_free_noise=self.com_free_noise, rtol=self.rtol, atol=self.atol,
+                                step_control=self.step_control)
+        self._record_counts(eng, B)
         xts = C.like(path.reshape(path.shape[0], B * A, 3), batch.x0)
         dlogp = batch.x0.new_zeros(B) if gpu else C.like(np.zeros(B, np.float32) * self.SCALE_DLOGP, batch.x0)      # reference: zeros(batch_size) (* 1e2 in ambient)
         return xts, dlogp, nfe

@@ -80,14 +80,17 @@ class FCNetMultiBeta:
 
     def forward(self, x0s, xts, ts, beta0s, beta1s):
         """net([xts, ts, beta_embed([beta0s, beta1s, ts])]) -> [B, 1].  ``x0s`` is unused, as in the reference (simple.py:38-41).
-        ``ts`` must hold one value (the sampler always passes ones_like(x) * t, ode_wrapper.py:47)."""
-        t = C.to_numpy(ts, np.float64).ravel()
-        if t.size and np.ptp(t) != 0.0:
-            raise NotImplementedError("per-row times are a training-only input; the sampling path evaluates one t per call")
+        ``ts``: one value (the sampler passes ones_like(x) * t, ode_wrapper.py:47) or one per row (what training feeds)."""
+        t = C.to_numpy(ts, np.float32).ravel()
         x = np.ascontiguousarray(C.to_numpy(xts, np.float32).reshape(-1))
         b0 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta0s, np.float32).reshape(-1), x.shape))
         b1 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta1s, np.float32).reshape(-1), x.shape))
-        out = self.engine().drift(x, float(t[0]) if t.size else 0.0, b0, b1)
+        if t.size > 1 and np.ptp(t) != 0.0:
+            if t.size != x.size:
+                raise ValueError(f"ts must hold one value or one per row ({x.size}), got {t.size}")
+            out = self.engine().drift(x, np.ascontiguousarray(t), b0, b1)
+        else:
+            out = self.engine().drift(x, float(t[0]) if t.size else 0.0, b0, b1)
         return C.like(out.reshape(-1, 1), xts)
 
     __call__ = forward
@@ -125,11 +128,16 @@ class StandardIntegrator:
     0 keeps the end state only).  With return_dlogp=True the second ODE state d(dlogp)/dt = -div * 1e-2 is integrated with the
     same scheme and returned * 1e2 as [n_saved, B, 1], like the reference (integrators.py:38-68).  With return_dlogp=False the
     reference evaluates ``None * 1e2`` and raises (integrators.py:42,68); here dlogp is returned as None instead.
+    ``step_control`` (keyword-only): 'batch' (default, one step size per call like the reference's odeint) or 'trajectory'
+    (method='dopri5' only: every particle gets the steps the reference takes for it at batch size 1; the per-particle
+    (accepted, rejected) counts of the last rollout are then in ``n_steps_per_particle``).
     """
 
     def __init__(self, b, method: str = "dopri5", n_step: int = 100, atol: float = 1e-4, rtol: float = 1e-4, start: float = 0.0,
-                 end: float = 1.0, return_dlogp=False, *, eps: float = 0.0, seed: int = 0, save_every: int = 1):
+                 end: float = 1.0, return_dlogp=False, *, eps: float = 0.0, seed: int = 0, save_every: int = 1,
+                 step_control: str = "batch"):
         self.method = C.check_method(method)
+        self.step_control = C.check_step_control(step_control, self.method)
         self.ode_wrapper = ODEWrapper(b, return_dlogp=return_dlogp)
         self.start, self.end, self.rtol, self.atol = start, end, rtol, atol
         self.n_step, self.return_dlogp = n_step, return_dlogp
@@ -151,7 +159,9 @@ class StandardIntegrator:
         grid = _engine.time_grid(self.start, self.end, self.n_step)
         res = self.ode_wrapper.b.engine().rollout(x0, b0, b1, grid, scheme=self.method,
                                                   save_every=self.save_every, eps=self.eps, seed=self.seed, traj_offset=traj_offset,
-                                                  return_dlogp=bool(self.return_dlogp), rtol=self.rtol, atol=self.atol)
+                                                  return_dlogp=bool(self.return_dlogp), rtol=self.rtol, atol=self.atol,
+                                                  step_control=self.step_control)
         self.n_fevals = res[-1]
+        self.n_steps_per_particle = self.ode_wrapper.b.engine().step_counts(B) if self.step_control == "trajectory" else None
         dlogp = C.like(res[1][:, :, None], x0s) if self.return_dlogp else None
         return C.like(res[0][:, :, None], x0s), dlogp
