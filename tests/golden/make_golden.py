@@ -2,7 +2,7 @@
 """Generate the golden vectors under tests/golden/ by running the REFERENCE drift networks on CPU.
 
 Run in the build container only (the reference lives at /root/reference and never travels):
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [--out DIR]
 
 What is pinned: the reference *drift networks* (importable) -- not the reference integrator
 (torchdiffeq, absent here).  Trajectories below are hand-rolled explicit Euler / Heun loops over the reference
@@ -29,6 +29,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
+# --out DIR writes the fixtures there instead (a reproduction check against the committed ones)
+OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else HERE
 sys.path.insert(0, ROOT)
 ti = importlib.import_module("thermodynamic-interpolation_amd")
 syn, W = ti.synthetic, ti.weights
@@ -200,7 +202,10 @@ def rollout_reference(ode, batch, n_step, scheme):
 
 
 def painn_case(name, variant, F, L, A, B, template, temp_length, temperatures, *, seed, ts=(0.0, 0.25, 1.0),
-               intermediates=False, traj_steps=0, ctor_init=False, sigma=0.3, atom_ids=None, recipe=None, close_pair=None):
+               intermediates=False, traj_steps=0, ctor_init=False, sigma=0.3, atom_ids=None, recipe=None, close_pair=None, edit=None):
+    """intermediates: True records every im:: key of run_with_intermediates, a tuple of names only those (keeps wide fixtures small).
+    edit: a function of the synthetic state dict that returns a modified copy (a change a suffix recipe cannot express); the result
+    is stored as sd::* like the constructor cases."""
     src, dst, etype = template
     atom_ids = np.arange(A, dtype=np.int32) if atom_ids is None else np.asarray(atom_ids, np.int32)
     x = syn.molecule_coords(B, A, seed=seed, sigma=sigma)
@@ -222,6 +227,10 @@ def painn_case(name, variant, F, L, A, B, template, temp_length, temperatures, *
             out[f"sd::{k}"] = v.numpy().copy()
     else:
         sd = syn.painn_state_dict(variant, F, L, 25, seed)
+        if edit is not None:
+            sd = edit(sd)
+            for k, v in sd.items():
+                out[f"sd::{k}"] = np.array(v)
         if recipe:                        # weights = synthetic weights with some tensors rescaled (synthetic.scale_state_dict)
             sd = syn.scale_state_dict(sd, recipe)
             out["recipe_keys"] = np.asarray([k for k, _ in recipe])
@@ -235,14 +244,15 @@ def painn_case(name, variant, F, L, A, B, template, temp_length, temperatures, *
         b2 = AmbientODE.reset_batch(batch.clone(), batch.x0, torch.tensor(float(ts[1]))) if variant == W.AMBIENT \
             else LatentODE.reset_batch(batch.clone(), batch.x0, torch.tensor(float(ts[1])))
         for k, v in run_with_intermediates(model, b2).items():
-            out[f"im::{k}"] = v
+            if intermediates is True or k in intermediates:
+                out[f"im::{k}"] = v
     if traj_steps:
         for scheme in ("euler", "heun"):
             grid, path = rollout_reference(ode, batch, traj_steps, scheme)
             out[f"traj_{scheme}"] = path.reshape(traj_steps, B, A, 3)
             out["traj_grid"] = grid
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
-    print(f"{name}: drift0 |b|={np.linalg.norm(out['drift_0']):.5f}  size={os.path.getsize(os.path.join(HERE, name + '.npz')) / 1024:.0f} KiB")
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print(f"{name}: drift0 |b|={np.linalg.norm(out['drift_0']):.5f}  size={os.path.getsize(os.path.join(OUT, name + '.npz')) / 1024:.0f} KiB")
 
 
 def adw_case(name, hidden, layers, B, *, seed, ctor_init=False, traj_steps=11):
@@ -294,8 +304,8 @@ def adw_case(name, hidden, layers, B, *, seed, ctor_init=False, traj_steps=11):
             path.append(xs.numpy()[:, 0].copy())
         out[f"traj_{scheme}"] = np.stack(path)
     out["traj_grid"] = grid.numpy().copy()
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
-    print(f"{name}: |b|={np.linalg.norm(out['drift_0']):.5f}  size={os.path.getsize(os.path.join(HERE, name + '.npz')) / 1024:.0f} KiB")
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print(f"{name}: |b|={np.linalg.norm(out['drift_0']):.5f}  size={os.path.getsize(os.path.join(OUT, name + '.npz')) / 1024:.0f} KiB")
 
 
 def painn_div_case(name, variant, F, L, A, B, template, temp_length, temperatures, *, seed, t=0.25, traj_steps=4, sigma=0.3,
@@ -348,8 +358,8 @@ def painn_div_case(name, variant, F, L, A, B, template, temp_length, temperature
             out[f"traj_{tag}"] = np.stack(path).reshape(traj_steps, B, A, 3)
             out[f"dlogp_{tag}"] = np.stack(dls)
             out[f"grid{'_rev' if reverse else ''}"] = grid.numpy().copy()
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
-    print(f"{name}: negdiv_scaled={out['negdiv_scaled']}  size={os.path.getsize(os.path.join(HERE, name + '.npz')) / 1024:.0f} KiB")
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print(f"{name}: negdiv_scaled={out['negdiv_scaled']}  size={os.path.getsize(os.path.join(OUT, name + '.npz')) / 1024:.0f} KiB")
 
 
 def div_cases():
@@ -362,15 +372,32 @@ def div_cases():
     painn_div_case("div_ambient_full", W.AMBIENT, 128, 5, 18, 1, fc(18), 100, TEMPS, seed=0, traj_steps=2)      # the headline shape
 
 
+RANGE_BIG = [("net.2.embedding.weight", 3e3), ("net.7.mlp.mlp.6.weight", 3e3), ("net.7.mlp.mlp.6.bias", 3e3),
+             ("phi.mlp.6.weight", 60.0), ("phi.mlp.6.bias", 60.0), ("w.mlp.6.weight", 60.0), ("w.mlp.6.bias", 60.0)]
+RANGE_TINY = [("net.2.embedding.weight", 1e-7), ("net.7.mlp.mlp.6.weight", 1e-7), ("net.7.mlp.mlp.6.bias", 1e-7),
+              ("phi.mlp.6.weight", 1e-4), ("phi.mlp.6.bias", 1e-4), ("w.mlp.6.weight", 1e-4), ("w.mlp.6.bias", 1e-4)]
+
+
+def lnaff_recipe(f, L, harsh=False, which=(1, 4)):
+    """LayerNorm affines (positions `which` of every message / update MLP) times f; `harsh` also the bias of the Linear after the first."""
+    r = []
+    for blk in ("phi", "w"):
+        r += [(f"{blk}.mlp.{i}.{wb}", f) for i in which for wb in ("weight", "bias")]
+        if harsh:
+            r += [(f"{blk}.mlp.3.bias", f)]
+    for l in range(L):
+        r += [(f"layers.{2 * l + 1}.mlp.mlp.{i}.{wb}", f) for i in which for wb in ("weight", "bias")]
+        if harsh:
+            r += [(f"layers.{2 * l + 1}.mlp.mlp.3.bias", f)]
+    return r
+
+
 def range_cases():
     """Magnitude edge cases for the operand path of the matrix products: the un-normalised residual streams
     s, e and |Vv| (cpainn.py:306-308,363-374) driven to 1e3..1e4 and down to 1e-6..1e-9 by rescaled weights, and an edge of
     length 1e-4.  The intermediates are recorded so the test can assert that the streams really reach those magnitudes."""
     fc = syn.fully_connected_template
-    big = [("net.2.embedding.weight", 3e3), ("net.7.mlp.mlp.6.weight", 3e3), ("net.7.mlp.mlp.6.bias", 3e3),
-           ("phi.mlp.6.weight", 60.0), ("phi.mlp.6.bias", 60.0), ("w.mlp.6.weight", 60.0), ("w.mlp.6.bias", 60.0)]
-    tiny = [("net.2.embedding.weight", 1e-7), ("net.7.mlp.mlp.6.weight", 1e-7), ("net.7.mlp.mlp.6.bias", 1e-7),
-            ("phi.mlp.6.weight", 1e-4), ("phi.mlp.6.bias", 1e-4), ("w.mlp.6.weight", 1e-4), ("w.mlp.6.bias", 1e-4)]
+    big, tiny = RANGE_BIG, RANGE_TINY
     painn_case("range_big", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=21, intermediates=True, recipe=big)
     painn_case("range_big_f128", W.AMBIENT, 128, 2, 5, 2, fc(5), 100, TEMPS, seed=22, intermediates=True, recipe=big)
     painn_case("range_tiny", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=23, intermediates=True, recipe=tiny)
@@ -387,18 +414,7 @@ def lnaff_cases():
     absolutely).  `harsh` also shrinks the bias of the Linear that follows, so that W h is not swamped by it and the second LayerNorm
     really amplifies what the product lost.  hidden_absmax is recorded so the test can assert the magnitudes were reached."""
     fc = syn.fully_connected_template
-
-    def recipe(f, L, harsh=False, which=(1, 4)):
-        r = []
-        for blk in ("phi", "w"):
-            r += [(f"{blk}.mlp.{i}.{wb}", f) for i in which for wb in ("weight", "bias")]
-            if harsh:
-                r += [(f"{blk}.mlp.3.bias", f)]
-        for l in range(L):
-            r += [(f"layers.{2 * l + 1}.mlp.mlp.{i}.{wb}", f) for i in which for wb in ("weight", "bias")]
-            if harsh:
-                r += [(f"layers.{2 * l + 1}.mlp.mlp.3.bias", f)]
-        return r
+    recipe = lnaff_recipe
     for tag, f, which in (("1em5", 1e-5, (1, 4)), ("1em3", 1e-3, (1, 4)), ("1e3", 1e3, (1,))):
         # (1e3 on the FIRST LayerNorm of each MLP only: on both, the reference itself overflows to NaN within two layers)
         painn_case(f"lnaff_{tag}_f32", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=31, intermediates=True, recipe=recipe(f, 2, which=which))
@@ -411,6 +427,57 @@ def lnaff_cases():
     painn_case("lnaff_harsh_f128", W.AMBIENT, 128, 2, 5, 2, fc(5), 100, TEMPS, seed=34, intermediates=True, recipe=recipe(1e-5, 2, True))
 
 
+def zero_phi0_edit(sd, s_factor=1.0):
+    """phi's first Linear [F, 2F] acts on [s[src] | e] (cpainn.py:276-282): its e half (columns F:2F) and its bias times 1e-15, the s half
+    times s_factor.  The per-atom P = s W_s^T + b0 then stays O(s_factor) beside a near-zero e-half product (what the one-accumulator
+    weight format's power of two for that matrix must be bounded by)."""
+    out = dict(sd)
+    for k, v in sd.items():
+        if k.endswith("phi.mlp.0.weight"):
+            w = np.array(v)
+            F = w.shape[1] // 2
+            w[:, F:] *= np.float32(1e-15)
+            if s_factor != 1.0:
+                w[:, :F] *= np.float32(s_factor)
+            out[k] = w
+        elif k.endswith("phi.mlp.0.bias"):
+            out[k] = np.array(v) * np.float32(1e-15)
+    return out
+
+
+def f256_cases():
+    """The mdqm9 configs' width (n_features 256, score_layers 5, 25 atoms: config/ambient/10506_settings_no_*.json,
+    config/latent/10506_latent_allTs_settings.json), the magnitude recipes at F = 256 with a middle layer (L = 3), and near-zero
+    e-half / bias of phi's first Linear at F = 32.  Stage intermediates only at 6 atoms (and only the keys the tests read for the
+    magnitude cases): the wide fixtures stay small."""
+    fc = syn.fully_connected_template
+    painn_case("ambient_f256", W.AMBIENT, 256, 5, 25, 2, fc(25), 100, TEMPS, seed=40, traj_steps=4)
+    painn_case("ambient_f256_taps", W.AMBIENT, 256, 5, 6, 2, fc(6), 100, TEMPS, seed=41, intermediates=True)
+    # (sigma 0.5, not the unit variance of the other latent fixtures: at this width the reference's own fp32 drift of unit-variance
+    # coordinates sits 1.0 - 1.2e-5 from exact arithmetic -- the sinusoidal encoding of long edges -- above the 1e-5 bar it is held to)
+    painn_case("latent_f256", W.LATENT_MULTI, 256, 5, 25, 2, fc(25), 75, TEMPS, seed=42, sigma=0.5)
+    # reference autograd's double backward sums in a thread-count dependent order (last bits of the divergence move between runs):
+    # one thread, so that the fixture reproduces bit for bit
+    nt = torch.get_num_threads()
+    torch.set_num_threads(1)
+    painn_div_case("div_ambient_f256", W.AMBIENT, 256, 5, 25, 1, fc(25), 100, TEMPS, seed=43, traj_steps=2)
+    torch.set_num_threads(nt)
+    rng = ("e_msg0", "s_msg0", "v_msg0", "v_upd1")
+    # (t = 0.5 for the last time: at t = 1 the reference's own fp32 drift of this case sits 1.1e-5 from exact arithmetic, above the bar)
+    painn_case("range_big_f256", W.AMBIENT, 256, 3, 5, 2, fc(5), 100, TEMPS, seed=44, ts=(0.0, 0.25, 0.5), intermediates=rng,
+               recipe=RANGE_BIG)
+    painn_case("range_tiny_f256", W.AMBIENT, 256, 3, 5, 2, fc(5), 100, TEMPS, seed=45, intermediates=rng, recipe=RANGE_TINY)
+    hid = ("hidden_names", "hidden_absmax")
+    painn_case("lnaff_1em5_f256", W.AMBIENT, 256, 3, 5, 2, fc(5), 100, TEMPS, seed=46, intermediates=hid, recipe=lnaff_recipe(1e-5, 3))
+    painn_case("lnaff_harsh_f256", W.AMBIENT, 256, 3, 5, 2, fc(5), 100, TEMPS, seed=47, intermediates=hid,
+               recipe=lnaff_recipe(1e-5, 3, True))
+    p_in = ("s_embed", "s_upd0", "hidden_names", "hidden_absmax")          # the s each layer's P is formed from
+    painn_case("lnaff_zero_phi0_f32", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=36, intermediates=p_in, edit=zero_phi0_edit)
+    # the same with the s half times 32: |P| of 10 - 30, so that a factor of 2^60 on P overflows the LayerNorm's fp32 sum of squares
+    painn_case("lnaff_zero_phi0_bigp_f32", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=37, intermediates=p_in,
+               edit=lambda sd: zero_phi0_edit(sd, 32.0))
+
+
 TEMPS = [300, 400, 500, 600, 700, 800, 900, 1000]
 
 if __name__ == "__main__":
@@ -420,6 +487,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--lnaff-only" in sys.argv:    # only the LayerNorm-affine cases
         lnaff_cases()
+        sys.exit(0)
+    if "--f256-only" in sys.argv:     # only the F = 256 / five-layer cases and the phi.W0 bias case
+        f256_cases()
         sys.exit(0)
     if "--div-only" in sys.argv:      # only the divergence fixtures (the drift fixtures above are unchanged by them)
         div_cases()
@@ -448,3 +518,4 @@ if __name__ == "__main__":
     div_cases()
     range_cases()
     lnaff_cases()
+    f256_cases()

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
 DIV_ATOL = 2e-5
-DIV_CASES = ["div_ambient_small", "div_ambient_sparse", "div_ambient_f128", "div_latent_multi", "div_latent_single"]
+DIV_CASES = ["div_ambient_small", "div_ambient_sparse", "div_ambient_f128", "div_latent_multi", "div_latent_single", "div_ambient_f256"]
 
 
 def make_pair(g, precision="f32"):

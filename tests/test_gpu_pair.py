@@ -91,6 +91,9 @@ def test_pair_rollout_vs_reference_trajectory(name, scheme):
 def test_pair_magnitude_edge_cases_vs_reference(name, precision):
     g = load_golden(name)
     eng = pair_engine(g, precision)
+    if eng.template_for(int(g["B"])) != "pair":
+        assert int(g["F"]) > 128                             # the only fixtures without one: F = 256
+        pytest.skip("no pair-major layout at this width")
     orc = oracle_from_golden(g)
     for i, t in enumerate(g["ts"]):
         ref = g[f"drift_{i}"]

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 DRIFT_TOL = 1e-5
 PAINN_CASES = ["ambient_small", "ambient_sparse", "ambient_a9", "ambient_a25", "ambient_full", "ambient_ctor", "ambient_b1",
-               "latent_multi", "latent_single", "latent_full", "latent_ctor"]
+               "latent_multi", "latent_single", "latent_full", "latent_ctor", "ambient_f256", "ambient_f256_taps", "latent_f256"]
 
 
 def engine_from_golden(g, device=0):
@@ -75,7 +75,7 @@ def test_painn_drift_vs_reference_golden(name):
         assert err < DRIFT_TOL, (name, i, err)
 
 
-@pytest.mark.parametrize("name", ["ambient_small", "ambient_sparse", "latent_multi"])
+@pytest.mark.parametrize("name", ["ambient_small", "ambient_sparse", "latent_multi", "ambient_f256_taps"])
 def test_painn_stage_taps_vs_oracle_and_golden(name):
     """s, v, e after the embed stage and after every message / update block."""
     g = load_golden(name)
@@ -107,7 +107,7 @@ def test_painn_stage_taps_vs_oracle_and_golden(name):
     assert rel_l2(eng.drift(g["x"], t, g["cond"]), g["drift_1"]) < DRIFT_TOL
 
 
-@pytest.mark.parametrize("name", ["ambient_small", "ambient_a9", "ambient_full", "latent_multi"])
+@pytest.mark.parametrize("name", ["ambient_small", "ambient_a9", "ambient_full", "latent_multi", "ambient_f256"])
 @pytest.mark.parametrize("scheme", ["euler", "heun"])
 def test_painn_rollout_vs_reference_trajectory(name, scheme):
     g = load_golden(name)
@@ -420,7 +420,8 @@ def test_wide_workgroups_at_small_feature_widths(F, monkeypatch):
     assert per_mol.max() < 3e-5
 
 
-RANGE_CASES = ["range_big", "range_big_f128", "range_tiny", "range_tiny_f128", "range_close", "range_latent_big"]
+RANGE_CASES = ["range_big", "range_big_f128", "range_tiny", "range_tiny_f128", "range_close", "range_latent_big", "range_big_f256",
+               "range_tiny_f256"]
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x2"])
@@ -452,7 +453,21 @@ def test_magnitude_edge_cases_vs_reference(name, precision):
 
 
 LNAFF_CASES = ["lnaff_1em5_f32", "lnaff_1em5_f128", "lnaff_1em3_f32", "lnaff_1em3_f128", "lnaff_1e3_f32", "lnaff_1e3_f128",
-               "lnaff_harsh_f32", "lnaff_harsh_f128", "lnaff_zero_w_f32"]
+               "lnaff_harsh_f32", "lnaff_harsh_f128", "lnaff_zero_w_f32", "lnaff_1em5_f256", "lnaff_harsh_f256", "lnaff_zero_phi0_f32",
+               "lnaff_zero_phi0_bigp_f32"]
+
+
+def phi0_inputs(g):
+    """Per layer: phi's first Linear split into its s half and e half (torch layout [F, 2F] on [s[src] | e], cpainn.py:276-282), its
+    bias, and the per-atom P = s W_s^T + b0 in fp64 from the fixture's own s (the embed output, then each update's output)."""
+    F, L = int(g["F"]), int(g["L"])
+    out = []
+    for l in range(L):
+        key = next(k for k in g if k.startswith("sd::") and k.endswith(f"layers.{2 * l}.phi.mlp.0.weight"))
+        w, b = g[key].astype(np.float64), g[key[:-6] + "bias"].astype(np.float64)
+        s = g["im::s_embed" if l == 0 else f"im::s_upd{l - 1}"].astype(np.float64)
+        out.append((w[:, :F], w[:, F:], b, s @ w[:, :F].T + b))
+    return out
 
 
 def check_lnaff_magnitudes(name, g):
@@ -460,6 +475,16 @@ def check_lnaff_magnitudes(name, g):
     h = g["im::hidden_absmax"]
     if "zero_w" in name:
         return                                              # (a weight-scale case, not an activation-magnitude one)
+    if "zero_phi0" in name:                                 # near-zero e half and bias of phi's first Linear beside an O(1) s half
+        for w_s, w_e, b, P in phi0_inputs(g):
+            assert np.abs(w_e).max() < 1e-15 and np.abs(b).max() < 1e-15 and np.abs(w_s).max() > 0.05
+            if "bigp" in name:
+                # the power of two of the one-accumulator format tops out at 2^60 (ti_api.hip: matrix_pow2_scale): were P scaled by
+                # that, the LayerNorm's fp32 sum of squares over a row of P would leave the fp32 range
+                assert (P ** 2).sum(axis=1).max() * 2.0 ** 120 > np.finfo(np.float32).max
+            else:
+                assert 0.1 < np.abs(P).max() < 3.0          # P is O(1)
+        return
     if "1em5" in name or "harsh" in name:
         assert h.max() < 6.1e-5                             # every hidden row below fp16's smallest normal number
     elif "1em3" in name:

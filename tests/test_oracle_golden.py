@@ -10,7 +10,9 @@ PAINN_CASES = ["ambient_small", "ambient_sparse", "ambient_a9", "ambient_a25", "
                "latent_multi", "latent_single", "latent_full", "latent_ctor",
                "range_big", "range_big_f128", "range_tiny", "range_tiny_f128", "range_close", "range_latent_big",
                "lnaff_1em5_f32", "lnaff_1em5_f128", "lnaff_1em3_f32", "lnaff_1em3_f128", "lnaff_1e3_f32", "lnaff_1e3_f128",
-               "lnaff_harsh_f32", "lnaff_harsh_f128", "lnaff_zero_w_f32"]
+               "lnaff_harsh_f32", "lnaff_harsh_f128", "lnaff_zero_w_f32",
+               "ambient_f256", "ambient_f256_taps", "latent_f256", "range_big_f256", "range_tiny_f256", "lnaff_1em5_f256", "lnaff_harsh_f256",
+               "lnaff_zero_phi0_f32", "lnaff_zero_phi0_bigp_f32"]
 # fp32 tolerance.  SURVEY.md §8c proposed 1e-6, but the reference's own fp32 forward sits 0.4e-6 (F=32) to 6e-6
 # (latent, F=128, unit-variance coordinates) away from exact arithmetic (the oracle's fp64 mode) because of GEMM summation
 # order and sin/cos of large arguments; two fp32 evaluations cannot agree better than that.  So: below the north-star bar
@@ -39,7 +41,7 @@ def test_painn_drift_matches_reference(name):
         assert close_f32(e32, e64), (name, i, e32, e64)
 
 
-@pytest.mark.parametrize("name", ["ambient_small", "ambient_sparse", "latent_multi"])
+@pytest.mark.parametrize("name", ["ambient_small", "ambient_sparse", "latent_multi", "ambient_f256_taps"])
 def test_painn_intermediates_match_reference(name):
     g = load_golden(name)
     o = make_oracle(g)
@@ -57,7 +59,7 @@ def test_painn_intermediates_match_reference(name):
             assert rel_l2(taps["e"].reshape(-1, F), g[f"im::e_{tag}"]) < 3e-6, tag
 
 
-@pytest.mark.parametrize("name", ["ambient_small", "ambient_a9", "ambient_full", "latent_multi"])
+@pytest.mark.parametrize("name", ["ambient_small", "ambient_a9", "ambient_full", "latent_multi", "ambient_f256"])
 @pytest.mark.parametrize("scheme", ["euler", "heun"])
 def test_painn_fixed_step_trajectory(name, scheme):
     g = load_golden(name)
@@ -175,13 +177,22 @@ def test_painn_dlogp_trajectory(name, scheme):
         np.testing.assert_array_equal(dl_last[0], dl[-1])
 
 
-def test_painn_divergence_headline_shape_matches_reference_autograd():
-    """F = 128, L = 5, A = 18 (the bench shape), one molecule: 54 reference double-backward passes vs 54 oracle forward-mode
-    passes.  fp32 oracle only (the fp64 pass and the rollouts of this size are left to the GPU suite: ~30 s each on 8 cores)."""
-    g = load_golden("div_ambient_full")
+@pytest.mark.parametrize("name", ["div_ambient_full", "div_ambient_f256"])
+def test_painn_divergence_headline_shape_matches_reference_autograd(name):
+    """F = 128, L = 5, A = 18 (the bench shape) and F = 256, L = 5, A = 25 (the mdqm9 configs), one molecule: 54 / 75 reference
+    double-backward passes vs as many oracle forward-mode passes.  fp32 oracle only (the fp64 pass and the rollouts of this size are
+    left to the GPU suite: ~30 s each on 8 cores)."""
+    g = load_golden(name)
     o = make_oracle(g)
     scale = float(g["div_scale"])
     ref_div = -g["negdiv_scaled"].astype(np.float64) / scale
     b32, d32 = o.drift_div(g["x"], float(g["t"]), g["cond"], precision=32)
     assert rel_l2(b32, g["drift"]) < TOL_BAR
     assert (np.abs(d32 - ref_div) < DIV_ATOL * (np.abs(ref_div) + 1.0)).all(), (d32, ref_div)
+
+
+@pytest.mark.parametrize("name", ["lnaff_zero_phi0_f32", "lnaff_zero_phi0_bigp_f32", "lnaff_1em5_f256", "lnaff_harsh_f256"])
+def test_lnaff_fixtures_reach_their_magnitudes(name):
+    """The fixture-side check of the GPU magnitude tests (test_gpu_parity.check_lnaff_magnitudes), here without a GPU."""
+    from test_gpu_parity import check_lnaff_magnitudes
+    check_lnaff_magnitudes(name, load_golden(name))

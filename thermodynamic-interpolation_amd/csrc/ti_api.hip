@@ -83,10 +83,11 @@ void pack_chunk16_split1(std::vector<float>& dst, const float* W, int ld, int n_
                 }
 }
 // power of two that brings the largest |entry| of W[0..rows)[col0..col0+cols) into [2^13, 2^14)   (1 for an all-zero matrix).
-// `bias` (n_bias entries, may be NULL) is the vector that is multiplied by the same factor in the kernel (the layer's bias row, or for
-// phi's first Linear the per-atom P = s W^T + b it is added to): the factor is capped so that S |b| stays <= 2^14 -- a near-zero matrix
-// beside O(1) biases (a pruned or freshly initialised layer) would otherwise scale the biases to 1e18 and overflow the LayerNorm's sum
-// of squares; what the cap costs is precision of a product that is negligible beside that bias anyway.
+// `bias` (n_bias entries, may be NULL) is the layer's bias row, which the kernel multiplies by the same factor: the factor is capped so
+// that S |b| stays <= 2^14 -- a near-zero matrix beside O(1) biases (a pruned or freshly initialised layer) would otherwise scale the
+// biases to 1e18 and overflow the LayerNorm's sum of squares; what the cap costs is precision of a product that is negligible beside
+// that bias anyway.  phi's first Linear packs only its e half (columns F..2F), but the kernel multiplies the per-atom P = s W_s^T + b0
+// by the same factor, so its factor is taken over all 2F columns and b0: S |W_s| <= 2^14 bounds S |P| by 2^14 (|s|_1 + 1).
 float matrix_pow2_scale(const float* W, int ld, int rows, int col0, int cols, const float* bias = nullptr, int n_bias = 0)
 {
     float mx = 0.f, mb = 0.f;
@@ -479,7 +480,7 @@ void pack_painn(ti_handle* h, const float* wts)
         h->st_edge.push_back(end_stream16(o));
         if (edge_uses_one_chain(NB, prec)) {         // the same chunks in the one-accumulator format, each matrix scaled by its own power of two
             const float S[6] = {matrix_pow2_scale(wts + h->w[l].W0, F, F, 0, F, wts + h->w[l].b0, F), matrix_pow2_scale(wts + h->w[l].W1, F, F, 0, F, wts + h->w[l].b1, F),
-                                matrix_pow2_scale(wts + h->phi[l].W0, 2 * F, F, F, F, wts + h->phi[l].b0, F), matrix_pow2_scale(wts + h->phi[l].W1, F, F, 0, F, wts + h->phi[l].b1, F),
+                                matrix_pow2_scale(wts + h->phi[l].W0, 2 * F, F, 0, 2 * F, wts + h->phi[l].b0, F), matrix_pow2_scale(wts + h->phi[l].W1, F, F, 0, F, wts + h->phi[l].b1, F),
                                 matrix_pow2_scale(wts + h->phi[l].W2, F, 5 * F, 0, F, wts + h->phi[l].b2, 5 * F), matrix_pow2_scale(wts + h->w[l].W2, F, 5 * F, 0, F, wts + h->w[l].b2, 5 * F)};
             auto layer1 = [&](size_t W, int ld, int n_rows, int col0, float sc) { for (int nbo = 0; nbo < NB; ++nbo) pack_chunk16_split1(pk, wts + W, ld, n_rows, 32 * nbo, col0, NBK, sc); };
             o = begin_stream();
