@@ -18,6 +18,8 @@
  *   ti_painn_drift_tv / _div_tv       cPaiNN.forward / ODEWrapper.compute_divergence with one batch.t per molecule
  *                                     (mdqm9/thermo/ambient/losses.py:45-70 feeds such batches)
  *   ti_adw_drift_tv                   FCNetMultiBeta.forward with per-row ts                adw/thermo/models/simple.py:38-41
+ *   ti_painn_drift_div_est / _est_tv  no reference counterpart: Hutchinson's estimate of the divergence ODEWrapper.compute_divergence
+ *   ti_painn_rollout_dlogp_est        computes exactly (the FFJORD estimator; the reference ships the exact one only)
  *   TI_SCHEME_DOPRI5_TRAJ             the reference's dopri5 integration (integrators.py, odeint per mini-batch) evaluated for every
  *   + ti_rollout_step_counts          trajectory as if it were alone in its batch (a batch size of 1)
  *
@@ -201,6 +203,31 @@ int ti_painn_drift_div_tv(ti_handle* h, const float* x, const float* t, const fl
  * out_dlogp [rows, B] = state * out_scale.  Reference values: ambient div_scale 1e-2, out_scale 1e2; latent 1, 1. */
 int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* desc, const float* x0, const float* cond, int64_t B,
                            float div_scale, float out_scale, int reverse_ode, float* out_path, float* out_dlogp, int64_t* n_fevals);
+
+/* Hutchinson's trace estimator, an unbiased but noisy replacement for the exact divergence above: k = n_probes Rademacher
+ * probes per molecule instead of 3A unit seeds (k tangent directions per evaluation instead of 3A).  Definition:
+ *   probe p in [0, k) of trajectory b (global id traj_offset + b), atom a, component c:
+ *     eps[b,p,a,c] = +1 if N(probe_seed, traj_offset + b, p, 3a + c) >= 0 else -1      (exactly 0 -> +1)
+ *   with N the Philox normal of TI_SCHEME_EM, the probe index in its step slot and the component index 3a + c that the molecule
+ *   noise uses (oracle.normal(probe_seed, traj, p, 3a + c) regenerates every probe on the host);
+ *   out_div[b] = (1/k) sum_p sum_{a,c} eps[b,p,a,c] (J_b eps[b,p])[a,c],  J_b = d b(x_b) / d x_b  -- WITHOUT the 1e-2 factor, like
+ *   ti_painn_drift_div.  E[out_div] = tr J_b; the variance is (2/k) sum_{i != j} ((J_ij + J_ji) / 2)^2.
+ * The probes depend on (probe_seed, global trajectory id) only and are FIXED for the whole call (the FFJORD convention): a rollout
+ * draws them once, from desc->traj_offset, and uses them at every evaluation, so the dlogp state follows a deterministic ODE -- every
+ * scheme (the fixed-grid ones as well as DOPRI5 / DOPRI5_TRAJ, whose error control applies unchanged) integrates it as it integrates
+ * the exact one; a chained call with the same ids reuses the same probes, and the result does not depend on the batch composition,
+ * order or sharding once the template is pinned.  Redrawing per step is not offered.  n_probes < 1: TI_E_ARG; TI_PREC_F16:
+ * TI_E_UNSUPPORTED.  The sum over probes and components runs in a fixed order (deterministic). */
+int ti_painn_drift_div_est(ti_handle* h, const float* x, float t, const float* cond, int64_t B, int32_t n_probes, uint64_t probe_seed,
+                           int64_t traj_offset, float* out, float* out_div, int mem);
+/* ti_painn_drift_div_est with one time per molecule, t [B] [host|device] */
+int ti_painn_drift_div_est_tv(ti_handle* h, const float* x, const float* t, const float* cond, int64_t B, int32_t n_probes,
+                              uint64_t probe_seed, int64_t traj_offset, float* out, float* out_div, int mem);
+/* ti_painn_rollout_dlogp with the estimate in place of the exact divergence (same schemes, EM refused, same scales and reverse_ode);
+ * the probes of trajectory b are those of global id desc->traj_offset + b. */
+int ti_painn_rollout_dlogp_est(ti_handle* h, const ti_rollout_desc* desc, int32_t n_probes, uint64_t probe_seed, const float* x0,
+                               const float* cond, int64_t B, float div_scale, float out_scale, int reverse_ode, float* out_path,
+                               float* out_dlogp, int64_t* n_fevals);
 
 /* ---- shared ------------------------------------------------------------------------------------------------------ */
 /* Accepted and rejected step counts [B] (host) of every trajectory of the last TI_SCHEME_DOPRI5_TRAJ rollout on this handle

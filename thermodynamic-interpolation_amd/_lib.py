@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "ti_destroy", "ti_set_stream", "ti_wait_stream", "ti_painn_set_template", "ti_painn_template_for", "ti_reserve", "ti_profile_enable", "ti_profile_read",
     "ti_painn_debug_tap", "ti_painn_debug_read", "ti_painn_debug_poison", "ti_selftest",
     "ti_painn_drift_tv", "ti_painn_drift_div_tv", "ti_adw_drift_tv", "ti_rollout_step_counts",
+    "ti_painn_drift_div_est", "ti_painn_drift_div_est_tv", "ti_painn_rollout_dlogp_est",
 ]
 
 
@@ -120,6 +121,10 @@ def lib():
     L.ti_painn_drift_div_tv.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int]
     L.ti_adw_drift_tv.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int]
     L.ti_rollout_step_counts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]
+    L.ti_painn_drift_div_est.argtypes = [vp, vp, C.c_float, vp, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, vp, vp, C.c_int]
+    L.ti_painn_drift_div_est_tv.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, vp, vp, C.c_int]
+    L.ti_painn_rollout_dlogp_est.argtypes = [vp, C.POINTER(RolloutDesc), C.c_int32, C.c_uint64, vp, vp, C.c_int64, C.c_float, C.c_float,
+                                             C.c_int, vp, vp, C.POINTER(C.c_int64)]
     _lib = L
     return L
 

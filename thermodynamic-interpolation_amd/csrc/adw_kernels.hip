@@ -197,6 +197,17 @@ __global__ void noise_kernel(float* __restrict__ x, float sigma, uint64_t seed, 
     }
 }
 
+// Rademacher probes of the Hutchinson estimator (include/ti_hip.h ti_painn_drift_div_est): eps[b][p][i] = sign of
+// ti_normal(seed, traj0 + b, p, i) (0 -> +1), i = 3 atom + component -- the component index noise_kernel draws for a molecule.
+__global__ void probe_kernel(float* __restrict__ eps, uint64_t seed, long long traj0, long long B, int k, int comps)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * k * comps) return;
+    const long long bp = i / comps, b = bp / k;
+    const int c = (int)(i - bp * comps), pr = (int)(bp - b * k);
+    eps[i] = ti_normal(seed, traj0 + b, pr, c) >= 0.0f ? 1.0f : -1.0f;
+}
+
 __global__ void scale_kernel(float* __restrict__ y, const float* __restrict__ x, float a, long long n)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -296,6 +307,12 @@ hipError_t launch_axpy(float* y, const float* x, float a, const float* b, long l
 hipError_t launch_heun(float* x, float hdt, const float* b1, const float* b2, long long n, hipStream_t st)
 {
     if (n > 0) hipLaunchKernelGGL(heun_kernel, grid1(n, 256), dim3(256), 0, st, x, hdt, b1, b2, n);
+    return hipGetLastError();
+}
+hipError_t launch_probes(float* eps, uint64_t seed, long long traj0, long long B, int k, int comps, hipStream_t st)
+{
+    const long long n = B * k * comps;
+    if (n > 0) hipLaunchKernelGGL(probe_kernel, grid1(n, 256), dim3(256), 0, st, eps, seed, traj0, B, k, comps);
     return hipGetLastError();
 }
 hipError_t launch_noise(float* x, float sigma, uint64_t seed, long long traj0, int step, long long B, int comps, int atoms_for_com,

@@ -262,10 +262,12 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_edge_kernel
             const float ry = p.x[nsrc * 3 + 1] - p.x[ndst * 3 + 1];
             const float rz = p.x[nsrc * 3 + 2] - p.x[ndst * 3 + 2];
             float tx, ty, tz;
-            if (p.xdot) {
-                tx = p.xdot[nsrc * 3 + 0] - p.xdot[ndst * 3 + 0];
-                ty = p.xdot[nsrc * 3 + 1] - p.xdot[ndst * 3 + 1];
-                tz = p.xdot[nsrc * 3 + 2] - p.xdot[ndst * 3 + 2];
+            if (p.xdot) {                                           // xdot [B][D][A][3]: direction dsel of molecule pm
+                const float* xd = p.xdot + (size_t)(pm * p.D + dsel) * p.A * 3;
+                const int xs = row_src(meta) * 3, xt = row_dst(meta) * 3;
+                tx = xd[xs + 0] - xd[xt + 0];
+                ty = xd[xs + 1] - xd[xt + 1];
+                tz = xd[xs + 2] - xd[xt + 2];
             } else {                                                // unit seed on (atom, component) = (dsel / 3, dsel % 3)
                 const int sa = dsel / 3, sc = dsel - 3 * sa;
                 const float sg = (float)((row_src(meta) == sa) - (row_dst(meta) == sa));
@@ -945,6 +947,26 @@ __global__ void painn_div_reduce_kernel(const float* __restrict__ tout, long lon
     div[b] = acc;
 }
 
+// Hutchinson contraction (include/ti_hip.h ti_painn_drift_div_est): est[b] = (1/k) sum_p sum_i eps[b][p][i] tangent[(b, p)][i] with
+// D = k explicit directions.  One wave per molecule: lane l takes the entries i = l, l + 64, ... of probe 0, 1, ... in that order
+// (fp64), then a fixed butterfly -- deterministic, and independent of where the molecule sits in the batch.
+__global__ void __launch_bounds__(256) painn_hutch_reduce_kernel(const float* __restrict__ tout, const float* __restrict__ eps, long long B,
+                                                                int k, int n3, int G, float* __restrict__ est)
+{
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;                                             // whole waves leave together
+    const long long pg = b / G, m = b - pg * G;
+    double acc = 0.0;
+    for (int pr = 0; pr < k; ++pr) {
+        const float* tg = tout + (size_t)((pg * k + pr) * G + m) * n3;
+        const float* ev = eps + (size_t)(b * k + pr) * n3;
+        for (int i = lane; i < n3; i += 64) acc += (double)ev[i] * (double)tg[i];
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) est[b] = (float)(acc / k);
+}
+
 // ================================================================================================== launchers
 static size_t jvp_edge_lds(int NB) { return 4 * (size_t)256 * NB * 16 + 4 * 128 * 4 + EV::COUNT * (size_t)32 * NB * 4; }
 static size_t jvp_node_lds(int NB, int count)
@@ -1053,6 +1075,12 @@ hipError_t launch_jvp_readout(int NBv, bool split, const JvpReadoutParams& p, hi
 hipError_t launch_div_reduce(const float* tout, long long B, int D, int G, float* div, hipStream_t st)
 {
     hipLaunchKernelGGL(painn_div_reduce_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, tout, B, D, G, div);
+    return hipGetLastError();
+}
+
+hipError_t launch_hutch_reduce(const float* tout, const float* eps, long long B, int k, int A, int G, float* est, hipStream_t st)
+{
+    hipLaunchKernelGGL(painn_hutch_reduce_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, tout, eps, B, k, 3 * A, G, est);
     return hipGetLastError();
 }
 

@@ -192,6 +192,7 @@ struct ti_handle {
     std::vector<Stream> st_jvp_update, st_jvp_phi; Stream st_jvp_readout{}; std::vector<int> jvp_phi_pad;
     DevBuf<float> jvp_ro_vecs, ts, tP, tv, tdsacc, tdvacc, tcacc, te, tout, wq, phist, nodest, divb, dl, dlscaled, div2;
     long long jvp_cap = 0, last_VB = 0; int last_D = 1;
+    DevBuf<float> probes;                        // Hutchinson probes of the current call [B][k][3A] (painn_make_probes)
     // Runge-Kutta drivers (rollout_rk): stage derivatives, dense-output coefficients, reduction scratch
     DevBuf<float> rk_ws; DevBuf<double> rk_red;
     // per-trajectory dopri5 (rollout_rk_traj): controller state, stage times, status words, grid, host-output staging, and the
@@ -649,7 +650,7 @@ long long jvp_chunk_molecules(const ti_handle* h, int D)
 
 struct JvpRun {            // one tangent pass riding on a drift evaluation
     int D;                 // seed directions per molecule
-    const float* xdot;     // D == 1: explicit direction [B*A*3] (device); NULL: unit seeds, D = 3A
+    const float* xdot;     // D explicit directions [B][D][A][3] (device; D = 1: ti_painn_drift_jvp, D = k: Hutchinson probes); NULL: unit seeds, D = 3A
     float* tout;           // [B*D*A*3] tangent of the drift (device)
 };
 
@@ -835,6 +836,34 @@ void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float*
         painn_drift_dev(h, x_dev + (size_t)b0 * A * 3, t, cond_dev ? cond_dev + (size_t)b0 * A * h->ncond : nullptr, bc,
                         out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr);
         HIP_CHECK(launch_div_reduce(h->tout.p, bc, D, h->G, div_dev + b0, h->stream));
+    }
+    h->last_B = std::min(chunk, B);
+}
+
+// Hutchinson probes of trajectories traj0 .. traj0 + B - 1 into h->probes [B][k][3A] (include/ti_hip.h ti_painn_drift_div_est),
+// drawn once per API call: a rollout integrates with the same probes at every evaluation
+void painn_make_probes(ti_handle* h, long long B, int k, uint64_t seed, long long traj0)
+{
+    const int n3 = 3 * h->d.n_atoms;
+    if (h->probes.n < (size_t)B * k * n3) h->probes.alloc((size_t)B * k * n3);
+    HIP_CHECK(launch_probes(h->probes.p, seed, traj0, B, k, n3, h->stream));
+}
+
+// drift and Hutchinson estimate of the divergence along the k probes of h->probes: D = k explicit tangent directions per molecule,
+// in chunks sized for k directions
+void painn_drift_div_est_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, int k, float* out_dev,
+                             float* est_dev, const float* tv = nullptr)
+{
+    const int A = h->d.n_atoms;
+    const long long chunk = jvp_chunk_molecules(h, k);
+    for (long long b0 = 0; b0 < B; b0 += chunk) {
+        const long long bc = std::min(chunk, B - b0);
+        ensure_jvp_ws(h, bc, k);
+        const float* eps = h->probes.p + (size_t)b0 * k * A * 3;
+        JvpRun jr{k, eps, h->tout.p};
+        painn_drift_dev(h, x_dev + (size_t)b0 * A * 3, t, cond_dev ? cond_dev + (size_t)b0 * A * h->ncond : nullptr, bc,
+                        out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr);
+        HIP_CHECK(launch_hutch_reduce(h->tout.p, eps, bc, k, A, h->G, est_dev + b0, h->stream));
     }
     h->last_B = std::min(chunk, B);
 }
@@ -1541,8 +1570,10 @@ int ti_painn_drift_div_tv(ti_handle* h, const float* x, const float* t, const fl
     });
 }
 
-int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float* x0, const float* cond, int64_t B, float div_scale,
-                           float out_scale, int reverse_ode, float* out_path, float* out_dlogp, int64_t* n_fevals)
+// ti_painn_rollout_dlogp (n_probes == 0: exact divergence) and ti_painn_rollout_dlogp_est (n_probes >= 1: Hutchinson estimate)
+static int painn_rollout_dlogp_impl(ti_handle* h, const ti_rollout_desc* rd, int n_probes, uint64_t probe_seed, const float* x0,
+                                    const float* cond, int64_t B, float div_scale, float out_scale, int reverse_ode, float* out_path,
+                                    float* out_dlogp, int64_t* n_fevals)
 {
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
     if (h->d.precision == TI_PREC_F16) return fail(TI_E_UNSUPPORTED, "the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)");
@@ -1561,18 +1592,21 @@ int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float*
         const float* cd = cond;
         if (rd->mem == TI_MEM_HOST && nc) { HIP_CHECK(hipMemcpyAsync(h->cond.p, cond, nc * sizeof(float), hipMemcpyHostToDevice, h->stream)); cd = h->cond.p; }
         const int saved_tap = h->tap; h->tap = -1;
+        if (n_probes > 0) painn_make_probes(h, B, n_probes, probe_seed, rd->traj_offset);
         DlogpAux aux;
         aux.dl = h->dl.p; aux.d1 = h->divb.p; aux.d2 = h->div2.p; aux.scaled = h->dlscaled.p; aux.out = out_dlogp;
         aux.n_dl = (size_t)B; aux.div_scale = div_scale; aux.out_scale = out_scale;
         auto drift = [&](const float* xs, float t, float* o, float* dv) {
-            painn_drift_div_dev(h, xs, t, cd, B, o, dv);
+            if (n_probes > 0) painn_drift_div_est_dev(h, xs, t, cd, B, n_probes, o, dv);
+            else painn_drift_div_dev(h, xs, t, cd, B, o, dv);
             if (reverse_ode) {      // (-b, +div): ode_wrapper.py:49
                 HIP_CHECK(launch_scale(o, o, -1.0f, (long long)n, h->stream));
                 HIP_CHECK(launch_scale(dv, dv, -1.0f, (long long)B, h->stream));
             }
         };
         auto drift_tv = [&](const float* xs, const float* tv, float* o, float* dv) {
-            painn_drift_div_dev(h, xs, 0.f, cd, B, o, dv, tv);
+            if (n_probes > 0) painn_drift_div_est_dev(h, xs, 0.f, cd, B, n_probes, o, dv, tv);
+            else painn_drift_div_dev(h, xs, 0.f, cd, B, o, dv, tv);
             if (reverse_ode) {
                 HIP_CHECK(launch_scale(o, o, -1.0f, (long long)n, h->stream));
                 HIP_CHECK(launch_scale(dv, dv, -1.0f, (long long)B, h->stream));
@@ -1584,6 +1618,71 @@ int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float*
         h->tap = saved_tap;
         return rc;
     });
+}
+
+int ti_painn_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float* x0, const float* cond, int64_t B, float div_scale,
+                           float out_scale, int reverse_ode, float* out_path, float* out_dlogp, int64_t* n_fevals)
+{
+    return painn_rollout_dlogp_impl(h, rd, 0, 0, x0, cond, B, div_scale, out_scale, reverse_ode, out_path, out_dlogp, n_fevals);
+}
+
+int ti_painn_rollout_dlogp_est(ti_handle* h, const ti_rollout_desc* rd, int32_t n_probes, uint64_t probe_seed, const float* x0,
+                               const float* cond, int64_t B, float div_scale, float out_scale, int reverse_ode, float* out_path,
+                               float* out_dlogp, int64_t* n_fevals)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (h->d.precision == TI_PREC_F16) return fail(TI_E_UNSUPPORTED, "the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)");
+    if (n_probes < 1) return fail(TI_E_ARG, "n_probes must be >= 1");
+    return painn_rollout_dlogp_impl(h, rd, n_probes, probe_seed, x0, cond, B, div_scale, out_scale, reverse_ode, out_path, out_dlogp, n_fevals);
+}
+
+// ti_painn_drift_div_est (tv == NULL) / ti_painn_drift_div_est_tv
+static int painn_drift_div_est_impl(ti_handle* h, const float* x, float t, const float* tv, const float* cond, int64_t B, int32_t n_probes,
+                                    uint64_t probe_seed, int64_t traj_offset, float* out, float* out_div, int mem, bool per_mol_t)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (h->d.precision == TI_PREC_F16) return fail(TI_E_UNSUPPORTED, "the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)");
+    if (n_probes < 1) return fail(TI_E_ARG, "n_probes must be >= 1");
+    if (B < 0 || (B > 0 && (!x || (per_mol_t && !tv) || !out || !out_div || (h->ncond > 0 && !cond)))) return fail(TI_E_ARG, "NULL buffer");
+    if (B == 0) return TI_OK;
+    if (h->tap >= 0) return fail(TI_E_ARG, "debug taps apply to ti_painn_drift / ti_painn_drift_jvp only");
+    return guarded([&]() -> int {
+        set_device(h);
+        select_template(h, B, false);
+        ensure_painn_ws(h, B);
+        const size_t n = (size_t)B * h->d.n_atoms * 3, nc = (size_t)B * h->d.n_atoms * h->ncond;
+        const float *xd = x, *cd = cond, *td = tv; float *od = out, *dd = out_div;
+        if (mem == TI_MEM_HOST) {
+            HIP_CHECK(hipMemcpyAsync(h->x.p, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            if (nc) HIP_CHECK(hipMemcpyAsync(h->cond.p, cond, nc * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            if (per_mol_t) {
+                if (h->rk_tv.n < (size_t)B) h->rk_tv.alloc(B);
+                HIP_CHECK(hipMemcpyAsync(h->rk_tv.p, tv, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                td = h->rk_tv.p;
+            }
+            xd = h->x.p; cd = h->cond.p; od = h->b1.p; dd = h->divb.p;
+        }
+        painn_make_probes(h, B, n_probes, probe_seed, traj_offset);
+        painn_drift_div_est_dev(h, xd, t, cd, B, n_probes, od, dd, per_mol_t ? td : nullptr);
+        if (mem == TI_MEM_HOST) {
+            HIP_CHECK(hipMemcpyAsync(out, od, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipMemcpyAsync(out_div, dd, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return TI_OK;
+    });
+}
+
+int ti_painn_drift_div_est(ti_handle* h, const float* x, float t, const float* cond, int64_t B, int32_t n_probes, uint64_t probe_seed,
+                           int64_t traj_offset, float* out, float* out_div, int mem)
+{
+    return painn_drift_div_est_impl(h, x, t, nullptr, cond, B, n_probes, probe_seed, traj_offset, out, out_div, mem, false);
+}
+
+int ti_painn_drift_div_est_tv(ti_handle* h, const float* x, const float* t, const float* cond, int64_t B, int32_t n_probes,
+                              uint64_t probe_seed, int64_t traj_offset, float* out, float* out_div, int mem)
+{
+    return painn_drift_div_est_impl(h, x, 0.f, t, cond, B, n_probes, probe_seed, traj_offset, out, out_div, mem, true);
 }
 
 int ti_painn_debug_tap(ti_handle* h, int stage)

@@ -131,7 +131,8 @@ hipError_t launch_readout(int NB, int prec, const ReadoutParams& p, hipStream_t 
 hipError_t configure_painn_kernels(int NB);     // dynamic-LDS attributes
 
 // ---- forward-mode derivative of the drift (painn_jvp_kernels.hip; virtual-molecule layout described there).
-// D = 3A and xdot == NULL: unit seeds (direction d -> atom d/3, component d%3); D = 1 with xdot [B*A][3]: that direction.
+// D = 3A and xdot == NULL: unit seeds (direction d -> atom d/3, component d%3); otherwise D explicit directions xdot [B][D][A][3]
+// (D = 1: ti_painn_drift_jvp; D = k: the Hutchinson probes).
 // Tangent arrays are laid out like their primal twins over ceil(B/G)*D*G virtual molecules; primal arrays are read only.
 struct JvpFilterParams {                    // primal pass of one layer's message block (painn_jvp_filter_kernel)
     const float4* stream; int nch; const float* vecs; const float* edge_emb;      // the primal edge stream / vector block
@@ -180,6 +181,8 @@ hipError_t launch_jvp_node(int NB, bool split, const JvpNodeParams& p, hipStream
 hipError_t launch_jvp_update(int NB, bool split, const JvpUpdateParams& p, hipStream_t st);
 hipError_t launch_jvp_readout(int NB, bool split, const JvpReadoutParams& p, hipStream_t st);
 hipError_t launch_div_reduce(const float* tout, long long B, int D, int G, float* div, hipStream_t st);
+// est[b] = (1/k) sum_{p,i} eps[b][p][i] tout[virtual molecule (b, p)][i], eps [B][k][3A]; one wave per molecule, fixed order
+hipError_t launch_hutch_reduce(const float* tout, const float* eps, long long B, int k, int A, int G, float* est, hipStream_t st);
 hipError_t configure_painn_jvp_kernels(int NB);
 
 // ---- adw (adw_kernels.hip).  One kernel evaluates  Linear(3->H), SiLU, [Linear(H->H), SiLU] x n_hidden, Linear(H->1)
@@ -202,6 +205,8 @@ hipError_t launch_axpy(float* y, const float* x, float a, const float* b, long l
 hipError_t launch_heun(float* x, float hdt, const float* b1, const float* b2, long long n, hipStream_t st);      // x += hdt*(b1+b2)
 hipError_t launch_noise(float* x, float sigma, uint64_t seed, long long traj0, int step, long long B, int comps_per_traj,
                         int atoms_for_com /*0 = no COM removal*/, hipStream_t st);
+// eps [B][k][comps] = +1 / -1 by the sign of the noise normal (seed, traj0 + b, step = p, component i); 0 -> +1
+hipError_t launch_probes(float* eps, uint64_t seed, long long traj0, long long B, int k, int comps, hipStream_t st);
 hipError_t launch_scale(float* y, const float* x, float a, long long n, hipStream_t st);                            // y = a*x
 hipError_t launch_selftest(float* out /*[64*16]*/, hipStream_t st);
 hipError_t launch_split_selftest(unsigned* out /*[2], zeroed: differing halves, subnormal-product mismatches*/, hipStream_t st);

@@ -9,7 +9,9 @@ Differences, on purpose: `method` comes from ``config.method`` (default 'dopri5'
 name of thermo._common.SUPPORTED works); files are written once per call instead of re-saving the growing concatenation after every batch
 (O(n_batches^2) I/O in the reference); datasets are the numpy ones of ``data.py``.  ``config.step_control`` (optional, default
 'batch'): 'trajectory' gives every molecule / particle its own dopri5 step sizes, so its sample and dlogp equal the reference's at
-batch size 1 whatever ``batch_size`` is.
+batch size 1 whatever ``batch_size`` is.  ``config.divergence`` / ``n_probes`` / ``probe_seed`` (optional, default 'exact' / 1 / 0):
+'hutchinson' estimates dlogp with n_probes Rademacher probes per molecule (MoleculeIntegratorBase); the molecules of successive
+batches then get consecutive trajectory ids, so no two molecules of a run share probes.
 """
 from __future__ import annotations
 
@@ -39,18 +41,26 @@ def _regroup(sample, batch_idx):
     return np.array([sample[:, batch_idx == i] for i in range(int(batch_idx.max()) + 1)])
 
 
+def _divergence_kw(config):
+    return dict(divergence=getattr(config, "divergence", "exact"), n_probes=getattr(config, "n_probes", 1),
+                probe_seed=getattr(config, "probe_seed", 0))
+
+
 def sample_ambient(config, b, dataset):
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
-                                         save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"))
+                                         save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"),
+                                         **_divergence_kw(config))
+    hutch, traj = integrator.divergence == "hutchinson", 0
     latent_noises, latent_dlogps, samples, dlogps, n_fevals = [], [], [], [], 0
     b.eval()
     for batch in dataset.batches(config.batch_size, shuffle=True, seed=config.seed):
         bidx = batch.batch
         latent_noises.append(np.array([batch.latent_z[bidx == i] for i in range(int(bidx.max()) + 1)]))
         latent_dlogps.append(batch.latent_dlogp)
-        sample, dlogp, n_fevals, _ = integrator.rollout(batch)
+        sample, dlogp, n_fevals, _ = integrator.rollout(batch, traj) if hutch else integrator.rollout(batch)
+        traj += int(C.to_numpy(bidx).max()) + 1
         samples.append(_regroup(sample, bidx))
         if config.return_dlogp:
             dlogps.append(C.to_numpy(dlogp)[-1, :])
@@ -67,11 +77,14 @@ def sample_latent(config, b, dataset):
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
-                                         save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"))
+                                         save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"),
+                                         **_divergence_kw(config))
+    hutch, traj = integrator.divergence == "hutchinson", 0
     samples, dlogps = [], []
     b.eval()
     for batch in dataset.batches(config.batch_size, seed=config.seed, drop_last=True):
-        sample, dlogp, bidx = integrator.rollout(batch)
+        sample, dlogp, bidx = integrator.rollout(batch, traj) if hutch else integrator.rollout(batch)
+        traj += int(C.to_numpy(bidx).max()) + 1
         samples.append(_regroup(sample, bidx))
         if config.return_dlogp:
             dlogps.append(C.to_numpy(dlogp)[-1, :])                     # sample_latent.py:76-77

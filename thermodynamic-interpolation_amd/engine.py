@@ -268,6 +268,40 @@ class PainnEngine(_Engine):
                                                      op, dp, C.byref(nfe)))
         return out, dl, nfe.value
 
+    # ---- Hutchinson's estimate of the divergence (include/ti_hip.h ti_painn_drift_div_est): k Rademacher probes per molecule,
+    # keyed by (probe_seed, traj_offset + b, probe); unbiased but noisy -- drift_div / rollout_dlogp stay the exact path
+    def drift_div_est(self, x, t, cond=None, n_probes=1, probe_seed=0, traj_offset=0):
+        """(b(x) [B,A,3], est [B]) with est = (1/k) sum_p eps_p^T J eps_p, E[est] = div (no 1e-2 factor).  t: a scalar or [B]."""
+        B = self._check_x(x)
+        like = x if hasattr(x, "data_ptr") and x.is_cuda else None
+        out, div = _alloc_like(like, (B, self.A, 3)), _alloc_like(like, (B,))
+        tv = self._times(t, B)
+        mem = lambda dev: _lib.MEM_DEVICE if dev else _lib.MEM_HOST
+        if tv is not None:
+            (xp, tp, cp, op, dp), dev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), tv, self._cond_spec(cond, B), (out, None, True, "out"),
+                                                         (div, None, True, "out_div"))
+            _lib.check(_lib.lib().ti_painn_drift_div_est_tv(self.h, xp, tp, cp, B, int(n_probes), int(probe_seed), int(traj_offset), op, dp, mem(dev)))
+            return out, div
+        (xp, cp, op, dp), dev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), self._cond_spec(cond, B), (out, None, True, "out"), (div, None, True, "out_div"))
+        _lib.check(_lib.lib().ti_painn_drift_div_est(self.h, xp, float(t), cp, B, int(n_probes), int(probe_seed), int(traj_offset), op, dp, mem(dev)))
+        return out, div
+
+    def rollout_dlogp_est(self, x0, cond, t_grid, n_probes=1, probe_seed=0, traj_offset=0, scheme="euler", save_every=1, div_scale=1.0,
+                          out_scale=1.0, reverse_ode=False, rtol=1e-4, atol=1e-4, step_control="batch"):
+        """rollout_dlogp with drift_div_est in place of the exact divergence; the probes of molecule b are those of global id
+        traj_offset + b, fixed for the whole call.  Returns (path [rows,B,A,3], dlogp [rows,B], n_fevals)."""
+        B = self._check_x(x0, "x0")
+        on_gpu = hasattr(x0, "data_ptr") and x0.is_cuda
+        rd = _rollout_desc(scheme, t_grid, save_every, _lib.MEM_DEVICE if on_gpu else _lib.MEM_HOST, 0.0, 0, traj_offset, False, rtol, atol,
+                           step_control=step_control)
+        rows = int(_lib.lib().ti_rollout_rows(rd.n_step, rd.save_every))
+        out, dl = _alloc_like(x0 if on_gpu else None, (rows, B, self.A, 3)), _alloc_like(x0 if on_gpu else None, (rows, B))
+        (xp, cp, op, dp), dev, keep = self._ptrs((x0, (B, self.A, 3), False, "x0"), self._cond_spec(cond, B), (out, None, True, "out"), (dl, None, True, "out_dlogp"))
+        nfe = C.c_int64(0)
+        _lib.check(_lib.lib().ti_painn_rollout_dlogp_est(self.h, C.byref(rd), int(n_probes), int(probe_seed), xp, cp, B, float(div_scale),
+                                                         float(out_scale), int(bool(reverse_ode)), op, dp, C.byref(nfe)))
+        return out, dl, nfe.value
+
     # ---- parity-test taps
     def debug_tap(self, stage: int):
         _lib.check(_lib.lib().ti_painn_debug_tap(self.h, int(stage)))

@@ -33,6 +33,21 @@ def check_step_control(step_control: str, method: str) -> str:
     return step_control
 
 
+DIVERGENCES = ("exact", "hutchinson")
+
+
+def check_divergence(divergence: str, n_probes, return_dlogp: bool):
+    """'exact' (3A forward-mode passes per molecule, the default) or 'hutchinson' (n_probes Rademacher probes per molecule, fixed for
+    the call: unbiased but noisy; include/ti_hip.h ti_painn_drift_div_est).  -> (divergence, n_probes)."""
+    if divergence not in DIVERGENCES:
+        raise ValueError(f"unknown divergence {divergence!r}; expected one of {DIVERGENCES}")
+    if isinstance(n_probes, bool) or not isinstance(n_probes, (int, np.integer)) or n_probes < 1:
+        raise ValueError(f"n_probes must be an int >= 1, got {n_probes!r}")
+    if divergence == "hutchinson" and not return_dlogp:
+        raise ValueError("divergence='hutchinson' estimates dlogp: it needs return_dlogp=True")
+    return divergence, int(n_probes)
+
+
 def is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "detach")
 

@@ -208,15 +208,22 @@ class MoleculeIntegratorBase:
     step_control (keyword-only, build-defined): 'batch' (default) -- one step size for the whole batch, the reference's single
     odeint per mini-batch, so a molecule's result depends on its batch; 'trajectory' (method='dopri5' only) -- every molecule gets
     its own step sizes, accept / reject decisions and dense output: what the reference computes for it at batch size 1, the same
-    bits for any batch, order or sharding.  self.n_steps_per_molecule then holds (accepted, rejected) [B] of the last rollout."""
+    bits for any batch, order or sharding.  self.n_steps_per_molecule then holds (accepted, rejected) [B] of the last rollout.
+
+    divergence (keyword-only, build-defined; needs return_dlogp=True for 'hutchinson'): 'exact' (default) or 'hutchinson' --
+    Hutchinson's estimate with n_probes Rademacher probes per molecule (k tangent passes instead of 3A), drawn from (probe_seed,
+    traj_offset + b) once per rollout and fixed along it.  Unbiased but noisy: each molecule's dlogp carries an estimator error."""
     SCALE_DLOGP = 1.0      # integrators.py:68 (ambient: 1e2)
     DIV_SCALE = 1.0        # ode_wrapper.py:91 (ambient: 1e-2)
 
     def __init__(self, b, method: str = "dopri5", n_step: int = 100, atol: float = 1e-4, rtol: float = 1e-4, start: float = 0.0,
                  end: float = 1.0, return_dlogp: bool = False, reverse_ode: bool = False, *, eps: float = 0.0, seed: int = 0,
-                 save_every: int = 1, com_free_noise: bool = False, step_control: str = "batch"):
+                 save_every: int = 1, com_free_noise: bool = False, step_control: str = "batch", divergence: str = "exact",
+                 n_probes: int = 1, probe_seed: int = 0):
         self.method = C.check_method(method)
         self.step_control = C.check_step_control(step_control, self.method)
+        self.divergence, self.n_probes = C.check_divergence(divergence, n_probes, return_dlogp)
+        self.probe_seed = int(probe_seed)
         if return_dlogp and self.method == "em" and eps > 0:
             raise ValueError("return_dlogp=True needs a deterministic scheme ('euler' or 'heun')")
         self.b = b
@@ -237,9 +244,14 @@ class MoleculeIntegratorBase:
         if self.return_dlogp:
             if self.reverse_ode:
                 grid = _engine.time_grid(self.end, self.start, self.n_step)
-            path, dl, nfe = eng.rollout_dlogp(x0, self.b.cond_of(batch, B, A, gpu), grid, scheme="euler" if self.method == "em" else self.method,
-                                              save_every=self.save_every, div_scale=self.DIV_SCALE, out_scale=self.SCALE_DLOGP,
-                                              reverse_ode=self.reverse_ode, rtol=self.rtol, atol=self.atol, step_control=self.step_control)
+            kw = dict(scheme="euler" if self.method == "em" else self.method, save_every=self.save_every, div_scale=self.DIV_SCALE,
+                      out_scale=self.SCALE_DLOGP, reverse_ode=self.reverse_ode, rtol=self.rtol, atol=self.atol, step_control=self.step_control)
+            cond = self.b.cond_of(batch, B, A, gpu)
+            if self.divergence == "hutchinson":
+                path, dl, nfe = eng.rollout_dlogp_est(x0, cond, grid, n_probes=self.n_probes, probe_seed=self.probe_seed,
+                                                      traj_offset=traj_offset, **kw)
+            else:
+                path, dl, nfe = eng.rollout_dlogp(x0, cond, grid, **kw)
             self._record_counts(eng, B)
             return C.like(path.reshape(path.shape[0], B * A, 3), batch.x0), C.like(dl, batch.x0), nfe
         path, nfe = eng.rollout(x0, self.b.cond_of(batch, B, A, gpu), grid, scheme=self.method, save_every=self.save_every, eps=self.eps,
