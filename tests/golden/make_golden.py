@@ -309,13 +309,16 @@ def adw_case(name, hidden, layers, B, *, seed, ctor_init=False, traj_steps=11):
 
 
 def painn_div_case(name, variant, F, L, A, B, template, temp_length, temperatures, *, seed, t=0.25, traj_steps=4, sigma=0.3,
-                   atom_ids=None):
+                   atom_ids=None, recipe=None, close_pair=None, edit=None):
     """Exact divergence / dlogp fixtures: the reference ODEWrapper with return_dlogp=True evaluated at (x, t)
     -> (b, -div * scale) in fp32 like the reference (the reference modules do not run in fp64: AddEquivariantFeatures
-    allocates float32, so the rounding-noise yardstick is the oracle's fp64 build); plus hand-rolled Euler / Heun loops over the two-state wrapper, forward and (latent) reverse_ode."""
+    allocates float32, so the rounding-noise yardstick is the oracle's fp64 build); plus hand-rolled Euler / Heun loops over the two-state wrapper, forward and (latent) reverse_ode.
+    recipe, close_pair and edit as in painn_case (the magnitude edge cases); without them the fixture is what it always was."""
     src, dst, etype = template
     atom_ids = np.arange(A, dtype=np.int32) if atom_ids is None else np.asarray(atom_ids, np.int32)
     x = syn.molecule_coords(B, A, seed=seed, sigma=sigma)
+    if close_pair is not None:
+        x[:, 1] = x[:, 0] + np.asarray([close_pair, 0.0, 0.0], np.float32)
     if variant == W.AMBIENT:
         cond = syn.ambient_cond(B, A)
     elif variant == W.LATENT_MULTI:
@@ -326,7 +329,16 @@ def painn_div_case(name, variant, F, L, A, B, template, temp_length, temperature
                temperatures=np.asarray(temperatures, np.float32), time_length=10.0, length_scale=10.0,
                edge_src=src, edge_dst=dst, edge_type=etype, atom_ids=atom_ids, x=x, cond=cond, t=np.float32(t),
                div_scale=np.float32(1e-2 if variant == W.AMBIENT else 1.0))
-    model = build_model(variant, F, L, temp_length, temperatures, syn.painn_state_dict(variant, F, L, 25, seed))
+    sd = syn.painn_state_dict(variant, F, L, 25, seed)
+    if edit is not None:
+        sd = edit(sd)
+        for k, v in sd.items():
+            out[f"sd::{k}"] = np.array(v)
+    if recipe:
+        sd = syn.scale_state_dict(sd, recipe)
+        out["recipe_keys"] = np.asarray([k for k, _ in recipe])
+        out["recipe_factors"] = np.asarray([f for _, f in recipe], np.float64)
+    model = build_model(variant, F, L, temp_length, temperatures, sd)
     Ode = AmbientODE if variant == W.AMBIENT else LatentODE
     batch = make_batch(variant, x, cond, src, dst, etype, atom_ids)
 
@@ -478,6 +490,38 @@ def f256_cases():
                edit=lambda sd: zero_phi0_edit(sd, 32.0))
 
 
+def div_range_cases():
+    """The exact divergence at the magnitude edges the drift is pinned at (range_*, lnaff_*): the drift fixtures' recipes, seeds and
+    shapes, evaluated by the reference's double backward at t = 0.25 like every other divergence fixture.  Deviations from the drift
+    recipes: all but two cases carry one-step rollouts only (traj_steps = 2).  Three-step Euler / Heun loops stay on range_tiny and
+    lnaff_1em5_f32; range_big's drift throws the atoms to |x| ~ 1e5 in one step, after which two fp32 evaluations of the
+    trajectory share no digits (0.95 rel-L2 between the oracle and the reference over three steps, 0.54 for one Heun step).  The two F = 256 cases
+    (the NBK = 16 tangent instantiations) hold one molecule instead of two, so that the reference's double backward stays short.
+    One torch thread: the reference's double backward sums in a thread-count dependent order (see div_ambient_f256)."""
+    fc = syn.fully_connected_template
+    nt = torch.get_num_threads()
+    torch.set_num_threads(1)
+    big, tiny = RANGE_BIG, RANGE_TINY
+    painn_div_case("div_range_big", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=21, recipe=big, traj_steps=2)
+    painn_div_case("div_range_big_f128", W.AMBIENT, 128, 2, 5, 2, fc(5), 100, TEMPS, seed=22, recipe=big, traj_steps=2)
+    painn_div_case("div_range_tiny", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=23, recipe=tiny)
+    painn_div_case("div_range_tiny_f128", W.AMBIENT, 128, 2, 5, 2, fc(5), 100, TEMPS, seed=24, recipe=tiny, traj_steps=2)
+    painn_div_case("div_range_close", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=25, close_pair=1e-4, traj_steps=2)
+    painn_div_case("div_range_latent_big", W.LATENT_MULTI, 32, 2, 6, 2, fc(6), 75, TEMPS, seed=26, sigma=1.0, traj_steps=2,
+                   recipe=[(k.replace("net.7.", "net.6."), f) for k, f in big])
+    painn_div_case("div_lnaff_1em5_f32", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=31, recipe=lnaff_recipe(1e-5, 2))
+    painn_div_case("div_lnaff_harsh_f128", W.AMBIENT, 128, 2, 5, 2, fc(5), 100, TEMPS, seed=34, recipe=lnaff_recipe(1e-5, 2, True),
+                   traj_steps=2)
+    painn_div_case("div_lnaff_zero_w_f32", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=35, traj_steps=2,
+                   recipe=[("phi.mlp.3.weight", 1e-15), ("w.mlp.0.weight", 1e-15), ("w.mlp.6.weight", 1e-12)])
+    painn_div_case("div_lnaff_zero_phi0_bigp_f32", W.AMBIENT, 32, 2, 6, 3, fc(6), 100, TEMPS, seed=37, traj_steps=2,
+                   edit=lambda sd: zero_phi0_edit(sd, 32.0))
+    painn_div_case("div_range_big_f256", W.AMBIENT, 256, 3, 5, 1, fc(5), 100, TEMPS, seed=44, recipe=big, traj_steps=2)
+    painn_div_case("div_lnaff_harsh_f256", W.AMBIENT, 256, 3, 5, 1, fc(5), 100, TEMPS, seed=47, recipe=lnaff_recipe(1e-5, 3, True),
+                   traj_steps=2)
+    torch.set_num_threads(nt)
+
+
 TEMPS = [300, 400, 500, 600, 700, 800, 900, 1000]
 
 if __name__ == "__main__":
@@ -493,6 +537,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--div-only" in sys.argv:      # only the divergence fixtures (the drift fixtures above are unchanged by them)
         div_cases()
+        sys.exit(0)
+    if "--div-range-only" in sys.argv:    # only the divergence fixtures at the magnitude edges
+        div_range_cases()
         sys.exit(0)
     if "--div-full-only" in sys.argv:
         painn_div_case("div_ambient_full", W.AMBIENT, 128, 5, 18, 1, syn.fully_connected_template(18), 100, TEMPS, seed=0, traj_steps=2)
@@ -519,3 +566,4 @@ if __name__ == "__main__":
     range_cases()
     lnaff_cases()
     f256_cases()
+    div_range_cases()

@@ -49,7 +49,7 @@ def oracle_estimate(orc, x, t, cond, eps):
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x2"])
-@pytest.mark.parametrize("name", ["div_ambient_full", "div_latent_multi", "div_ambient_f256"])
+@pytest.mark.parametrize("name", ["div_ambient_full", "div_latent_multi", "div_ambient_f256", "div_range_big_f128", "div_lnaff_harsh_f128"])
 def test_estimator_identity_vs_fp64_oracle(name, precision):
     g = load_golden(name)
     eng, orc = make_pair(g, precision)

@@ -196,3 +196,93 @@ def test_lnaff_fixtures_reach_their_magnitudes(name):
     """The fixture-side check of the GPU magnitude tests (test_gpu_parity.check_lnaff_magnitudes), here without a GPU."""
     from test_gpu_parity import check_lnaff_magnitudes
     check_lnaff_magnitudes(name, load_golden(name))
+
+
+# ------------------------------------------------------------------------------- exact divergence at the magnitude edges
+# The drift's range_* / lnaff_* recipes, evaluated by the reference's double backward (make_golden.py div_range_cases).  Not in
+# DIV_CASES: their divergences run from 1e-9 to 1e10, so neither the `+ 1` floor of DIV_ATOL nor a fixed absolute bar means anything.
+DIV_RANGE_CASES = ["div_range_big", "div_range_big_f128", "div_range_tiny", "div_range_tiny_f128", "div_range_close",
+                   "div_range_latent_big", "div_lnaff_1em5_f32", "div_lnaff_harsh_f128", "div_lnaff_zero_w_f32",
+                   "div_lnaff_zero_phi0_bigp_f32", "div_range_big_f256", "div_lnaff_harsh_f256"]
+# the cases whose Euler / Heun loops stay meaningful (range_big's drift throws its atoms to |x| ~ 1e5 in one step)
+DIV_RANGE_TRAJ = ["div_range_tiny", "div_lnaff_1em5_f32"]
+# relative bar against the case's own scale S = sum_i |d b_i / d x_i| (a trace of 3A entries of either sign rounds like S, not like it)
+DIV_REL = 2e-5
+
+
+def divergence_scale(o, g, precision=64):
+    """S [B] = sum_i |J_ii| from unit-seed JVPs of the oracle."""
+    B, A, t = int(g["B"]), int(g["A"]), float(g["t"])
+    S = np.zeros(B)
+    for i in range(3 * A):
+        e = np.zeros((B, A, 3), np.float32)
+        e.reshape(B, -1)[:, i] = 1.0
+        S += np.abs(o.jvp(g["x"], e, t, g["cond"], precision=precision)[1].reshape(B, -1)[:, i].astype(np.float64))
+    return S
+
+
+def unit_seed_tangent_taps(o, g):
+    """{stream: [max |tangent| over the case per stage]} of the fp64 oracle's tangent taps (ts, tv, te after every message / update
+    stage) along all 3A unit seeds."""
+    B, A, L, t = int(g["B"]), int(g["A"]), int(g["L"]), float(g["t"])
+    out = {k: np.zeros(2 * L) for k in ("s", "v", "e")}
+    for i in range(3 * A):
+        e = np.zeros((B, A, 3), np.float32)
+        e.reshape(B, -1)[:, i] = 1.0
+        for st in range(1, 2 * L + 1):
+            _, _, taps = o.jvp(g["x"], e, t, g["cond"], precision=64, tap_stage=st)
+            for k in out:
+                out[k][st - 1] = max(out[k][st - 1], float(np.abs(taps[k]).max()))
+    return out
+
+
+@pytest.mark.parametrize("name", DIV_RANGE_CASES)
+def test_painn_divergence_magnitude_edges_match_reference_autograd(name):
+    g = load_golden(name)
+    o = make_oracle(g)
+    ref_div = -g["negdiv_scaled"].astype(np.float64) / float(g["div_scale"])
+    b32, d32 = o.drift_div(g["x"], float(g["t"]), g["cond"], precision=32)
+    b64, d64 = o.drift_div(g["x"], float(g["t"]), g["cond"], precision=64)
+    S = divergence_scale(o, g)
+    # exact arithmetic against the reference's fp32 autograd, on the case's own scale (not vacuous for |div| << 1)
+    assert (np.abs(d64 - ref_div) < DIV_REL * S).all(), (name, d64, ref_div, S)
+    # the fp32 oracle: within 3x the fp32 floor -- the larger of the two fp32 evaluations' distances to exact arithmetic -- or the
+    # case's own DIV_REL * S (which takes the place of DIV_ATOL: an absolute 2e-5 would pass anything at |div| ~ 1e-9)
+    floor = max(float(np.abs(ref_div - d64).max()), float(np.abs(d32 - d64).max()))
+    bar = np.maximum(DIV_REL * S, 3.0 * floor)
+    assert (np.abs(d32 - ref_div) < bar).all(), (name, d32, ref_div, bar)
+    assert (bar < 0.1 * S).all(), (name, bar, S)
+    assert np.isfinite(b32).all() and rel_l2(b64, g["drift"]) < TOL_BAR
+
+
+@pytest.mark.parametrize("name", DIV_RANGE_TRAJ)
+@pytest.mark.parametrize("scheme", ["euler", "heun"])
+def test_painn_dlogp_trajectory_magnitude_edges(name, scheme):
+    g = load_golden(name)
+    o = make_oracle(g)
+    scale = float(g["div_scale"])
+    S = divergence_scale(o, g) * scale
+    grid = g["grid"]
+    path, dl, _ = o.rollout_dlogp(g["x"], g["cond"], grid, scheme=scheme, div_scale=scale, precision=64)
+    ref, ref_dl = g[f"traj_{scheme}"], g[f"dlogp_{scheme}"]
+    assert rel_l2(path - path[0], ref - ref[0]) < 5e-6
+    # dlogp after k steps is a sum of k divergences of size ~S (dt <= 1): on that scale
+    assert (np.abs(dl - ref_dl) < DIV_REL * S).all(), (name, dl, ref_dl, S)
+
+
+@pytest.mark.parametrize("name", [n for n in DIV_RANGE_CASES if n.endswith(("_big", "_big_f128", "_big_f256")) or "_tiny" in n or "lnaff_1em5" in n or "lnaff_harsh" in n])
+def test_div_range_fixtures_reach_their_magnitudes(name):
+    """The cases reach what they claim: the tangents the tangent kernels split as operands (te, tv, ts along unit seeds) leave the
+    fp16 range in the *_big cases (> 65504: an unscaled hi half is inf) and fall below 1e-7 in the *_tiny cases (an unscaled lo half is
+    an fp16 subnormal).  In the LayerNorm-affine cases the LayerNorm outputs and their tangents are scaled by the 1e-5 affines, so the
+    tangent rows that enter the next products are tiny, not large: the edge-feature tangent stays below 1e-7."""
+    g = load_golden(name)
+    mx = unit_seed_tangent_taps(make_oracle(g), g)
+    top = max(float(v.max()) for v in mx.values())
+    least = min(float(v.max()) for v in mx.values())
+    if "_big" in name:
+        assert top > 65504.0, (name, mx)
+    elif "_tiny" in name:
+        assert least < 1e-7, (name, mx)
+    else:
+        assert float(mx["e"].max()) < 1e-7, (name, mx)

@@ -717,6 +717,7 @@ struct Opnd {                                   // fp32 operand: the activation 
     Act<NBK> a;
     __device__ __forceinline__ void set(const Act<NBK>& x) { a = x; }
     __device__ __forceinline__ float set_scaled(const Act<NBK>& x) { a = x; return 1.0f; }
+    __device__ __forceinline__ float set_tangent(const Act<NBK>& x) { a = x; return 1.0f; }
     __device__ __forceinline__ f32x4 value(int nb, float) const { return a.b[nb]; }          // the block the operand was set from (exact)
 };
 template <int NBK>
@@ -741,16 +742,34 @@ struct Opnd<NBK, true> {                        // split operand: hi and scaled-
     // subnormals (tests/golden/range_*.npz).
     __device__ __forceinline__ float set_scaled(const Act<NBK>& x)
     {
+        const unsigned e = row_exponent(x);
+        // rows below 2^-63 (incl. all-zero rows) are left unscaled -- their products vanish beside any bias -- and 2^k stops at
+        // 2^63, so that scale, 1 / scale and (accumulator init) / scale stay far inside the fp32 range
+        return set_pow2(x, e < 64u ? 127u : e > 190u ? 190u : e);
+    }
+    // For TANGENT rows (painn_jvp_kernels.hip): as set_scaled, over every normal exponent.  A tangent is linear in the seed direction
+    // and no bias is summed beside its products (the caller adds the scaled product to what it holds, gemm_*_sc), so a row of
+    // 1e-30 matters as much as one of 1; and with the row's own power of two at any scale, jvp(x, 2^k xdot) = 2^k jvp(x, xdot) bit
+    // for bit.  Only all-zero (and fp32-subnormal) rows stay unscaled; the exponent stops at 2^126 so that 1 / scale stays normal.
+    __device__ __forceinline__ float set_tangent(const Act<NBK>& x)
+    {
+        const unsigned e = row_exponent(x);
+        return set_pow2(x, e == 0u ? 127u : e > 253u ? 253u : e);
+    }
+    // biased exponent of the row's largest |value| (this lane's 16*NBK values and those of the 3 lanes that share its row)
+    __device__ __forceinline__ static unsigned row_exponent(const Act<NBK>& x)
+    {
         float m = 0.f;
 #pragma unroll
         for (int nb = 0; nb < NBK; ++nb)
 #pragma unroll
             for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(x.b[nb][r]));
         m = xquarters_max(m);
-        const unsigned e = (__builtin_bit_cast(unsigned, m) >> 23) & 0xffu;            // biased exponent of the row maximum
-        // rows below 2^-63 (incl. all-zero rows) are left unscaled -- their products vanish beside any bias -- and 2^k stops at
-        // 2^63, so that scale, 1 / scale and (accumulator init) / scale stay far inside the fp32 range
-        const unsigned ec = e < 64u ? 127u : e > 190u ? 190u : e;
+        return (__builtin_bit_cast(unsigned, m) >> 23) & 0xffu;
+    }
+    // split x / 2^(ec - 127); returns 2^(ec - 127)
+    __device__ __forceinline__ float set_pow2(const Act<NBK>& x, unsigned ec)
+    {
         const float inv = __builtin_bit_cast(float, (254u - ec) << 23), scale = __builtin_bit_cast(float, ec << 23);
 #pragma unroll
         for (int m2 = 0; m2 < NBK / 2; ++m2)
@@ -1196,6 +1215,62 @@ __device__ __forceinline__ void gemm_fl2(f32x4& a0, f32x4& a1, f32x4& t0, f32x4&
     const h8* wl = reinterpret_cast<const h8*>(wl4);
     gemm_pair_split_block<NBK, true>(a0, t0, in, tin, wl, lane);
     gemm_pair_split_block<NBK, true>(a1, t1, in, tin, wl + NBK * 64, lane);
+}
+
+// ---- acc += (product of an operand set by set_scaled / set_tangent) * its scale.  The split operand's product is formed from zero and
+// scaled before it is added; an fp32 operand has scale 1 and its product accumulates into acc directly (the same bits as gemm_bt).
+template <int NBK, bool SPLIT>
+__device__ __forceinline__ void gemm_bt_sc(f32x4& acc0, f32x4& acc1, const Opnd<NBK, SPLIT>& in, float sc, const f32x4* wl, int lane)
+{
+    if constexpr (SPLIT) {
+        f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+        gemm_bt(a0, a1, in, wl, lane);
+        acc0 += a0 * sc; acc1 += a1 * sc;
+    } else {
+        gemm_bt(acc0, acc1, in, wl, lane);
+    }
+}
+// The flipped product holds rows 4 q + r of the block in the registers of lane (j, q), not row j: each element takes the scale of its
+// own row, read from the lane of quarter 0 that holds that row (every quarter of a row holds the same scale).
+__device__ __forceinline__ f32x4 flipped_row_scales(float sc, int lane)
+{
+    f32x4 s;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        s[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((4 * (lane >> 4) + r) << 2, __builtin_bit_cast(int, sc)));
+    return s;
+}
+template <int NBK, bool SPLIT>
+__device__ __forceinline__ void gemm_fl_sc(f32x4& acc0, f32x4& acc1, const Opnd<NBK, SPLIT>& in, float sc, const f32x4* wl, int lane)
+{
+    if constexpr (SPLIT) {
+        f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+        gemm_fl(a0, a1, in, wl, lane);
+        const f32x4 s = flipped_row_scales(sc, lane);
+        acc0 += a0 * s; acc1 += a1 * s;
+    } else {
+        gemm_fl(acc0, acc1, in, wl, lane);
+    }
+}
+// (value, tangent) pair against one chunk, each with its own scale
+template <int NBK, bool SPLIT, bool FLIP = false>
+__device__ __forceinline__ void gemm_bt2_sc(f32x4& a0, f32x4& a1, f32x4& t0, f32x4& t1, const Opnd<NBK, SPLIT>& in, float sc,
+                                            const Opnd<NBK, SPLIT>& tin, float tsc, const f32x4* wl, int lane)
+{
+    if constexpr (SPLIT) {
+        f32x4 x0 = {0, 0, 0, 0}, x1 = {0, 0, 0, 0}, y0 = {0, 0, 0, 0}, y1 = {0, 0, 0, 0};
+        if (FLIP) {
+            gemm_fl2(x0, x1, y0, y1, in, tin, wl, lane);
+            const f32x4 s = flipped_row_scales(sc, lane), ts = flipped_row_scales(tsc, lane);
+            a0 += x0 * s; a1 += x1 * s; t0 += y0 * ts; t1 += y1 * ts;
+        } else {
+            gemm_bt2(x0, x1, y0, y1, in, tin, wl, lane);
+            a0 += x0 * sc; a1 += x1 * sc; t0 += y0 * tsc; t1 += y1 * tsc;
+        }
+    } else {
+        if (FLIP) gemm_fl2(a0, a1, t0, t1, in, tin, wl, lane);
+        else      gemm_bt2(a0, a1, t0, t1, in, tin, wl, lane);
+    }
 }
 
 // ---- two operand sets (the two directions of a pair block) against the pipe's current chunk, every matrix path

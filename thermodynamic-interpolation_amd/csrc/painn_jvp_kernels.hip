@@ -100,21 +100,23 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_filter_kernel(const JvpFilte
         const float dist = sqrtf(rx * rx + ry * ry + rz * rz);
         // ---- filter branch, (value, d/d|r|) pair
         OP g2, tg2;
+        float tg2sc;
         {
             A16 t1, u1;
             {
                 OP enc, tenc;
+                float tsc;
                 {
                     A16 t, u;
                     r16::posenc_dual(t, u, dist / p.length_scale, 1.0f / p.length_scale, q);      // seed d|r| = 1
-                    enc.set(t); tenc.set(u);
+                    enc.set(t); tsc = tenc.set_tangent(u);
                 }
 #pragma unroll
                 for (int c = 0; c < NB; ++c) {
                     const f32x4* wl = pipe.acquire();
                     f32x4 a0 = r16::load_block(vec + EV::W_B0 * F, 2 * c, q), a1 = r16::load_block(vec + EV::W_B0 * F, 2 * c + 1, q);
                     f32x4 b0 = Z4, b1 = Z4;
-                    r16::gemm_bt2(a0, a1, b0, b1, enc, tenc, wl, lane);
+                    r16::gemm_bt2_sc(a0, a1, b0, b1, enc, 1.0f, tenc, tsc, wl, lane);
                     t1.b[2 * c] = a0; t1.b[2 * c + 1] = a1; u1.b[2 * c] = b0; u1.b[2 * c + 1] = b1;
                     pipe.release();
                 }
@@ -122,19 +124,20 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_filter_kernel(const JvpFilte
             r16::ln_silu_dual(t1, u1, vec + EV::W_G0 * F, vec + EV::W_BE0 * F, q);
             {
                 OP g1, tg1;
-                g1.set(t1); tg1.set(u1);
+                g1.set(t1);
+                const float tsc = tg1.set_tangent(u1);
 #pragma unroll
                 for (int c = 0; c < NB; ++c) {
                     const f32x4* wl = pipe.acquire();
                     f32x4 a0 = r16::load_block(vec + EV::W_B1 * F, 2 * c, q), a1 = r16::load_block(vec + EV::W_B1 * F, 2 * c + 1, q);
                     f32x4 b0 = Z4, b1 = Z4;
-                    r16::gemm_bt2(a0, a1, b0, b1, g1, tg1, wl, lane);
+                    r16::gemm_bt2_sc(a0, a1, b0, b1, g1, 1.0f, tg1, tsc, wl, lane);
                     t1.b[2 * c] = a0; t1.b[2 * c + 1] = a1; u1.b[2 * c] = b0; u1.b[2 * c + 1] = b1;
                     pipe.release();
                 }
             }
             r16::ln_silu_dual(t1, u1, vec + EV::W_G1 * F, vec + EV::W_BE1 * F, q);
-            g2.set(t1); tg2.set(u1);
+            g2.set(t1); tg2sc = tg2.set_tangent(u1);
         }
         // ---- phi branch forward, LayerNorm statistics parked for the tangent passes
         OP h2;
@@ -151,13 +154,13 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_filter_kernel(const JvpFilte
                 OP ein;
                 if (first) r16::load_set(t1, p.edge_emb + row_type(meta) * F, q);
                 else       r16::load_set(t1, p.e + (prow0 + j) * F, q);
-                ein.set(t1);
+                const float esc = ein.set_scaled(t1);                          // e: an un-normalised stream
                 const float* prow = p.P + (size_t)nsrc * F;
 #pragma unroll
                 for (int c = 0; c < NB; ++c) {
                     const f32x4* wl = pipe.acquire();
                     f32x4 a0 = r16::load_block(prow, 2 * c, q), a1 = r16::load_block(prow, 2 * c + 1, q);
-                    r16::gemm_bt(a0, a1, ein, wl, lane);
+                    r16::gemm_bt_sc(a0, a1, ein, esc, wl, lane);
                     t1.b[2 * c] = a0; t1.b[2 * c + 1] = a1;
                     pipe.release();
                 }
@@ -193,7 +196,7 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_filter_kernel(const JvpFilte
             r16::gemm_fl(a0, a1, h2, wl0, lane);
             pipe.release();
             const f32x4* wl1 = pipe.acquire();
-            r16::gemm_fl2(b0, b1, tb0, tb1, g2, tg2, wl1, lane);
+            r16::gemm_bt2_sc<NBK, SPLIT, true>(b0, b1, tb0, tb1, g2, 1.0f, tg2, tg2sc, wl1, lane);
             pipe.release();
             const float* bp = vec + (EV::P_B2 + c) * F + 32 * nbo + j;
             const float* bw = vec + (EV::W_B2 + c) * F + 32 * nbo + j;
@@ -283,6 +286,7 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_edge_kernel
         }
         // ---- tangent of phi's hidden layers (first layer: s and e do not depend on x yet, the whole tangent is zero)
         OP th2;
+        float th2sc = 1.0f;
         if (!first) {
             const f32x4* stp = reinterpret_cast<const f32x4*>(p.st) + ((size_t)(pg * p.nblk + blk) * 4 * NBK) * 64 + lane;
             auto stat = [&](int which, A16& v) {
@@ -293,13 +297,13 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_edge_kernel
             {
                 OP tein;
                 r16::load_set(u1, p.te + (trow0 + j) * F, q);
-                tein.set(u1);
+                const float tsc = tein.set_tangent(u1);
                 const float* tprow = p.tP + (size_t)((vmg * p.G + row_mol(meta)) * p.A + row_src(meta)) * F;
 #pragma unroll
                 for (int c = 0; c < NB; ++c) {
                     const f32x4* wl = pipe.acquire();
                     f32x4 b0 = r16::load_block(tprow, 2 * c, q), b1 = r16::load_block(tprow, 2 * c + 1, q);
-                    r16::gemm_bt(b0, b1, tein, wl, lane);
+                    r16::gemm_bt_sc(b0, b1, tein, tsc, wl, lane);
                     u1.b[2 * c] = b0; u1.b[2 * c + 1] = b1;
                     pipe.release();
                 }
@@ -311,12 +315,12 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_edge_kernel
             }
             {
                 OP th1;
-                th1.set(u1);
+                const float tsc = th1.set_tangent(u1);
 #pragma unroll
                 for (int c = 0; c < NB; ++c) {
                     const f32x4* wl = pipe.acquire();
                     f32x4 b0 = Z4, b1 = Z4;
-                    r16::gemm_bt(b0, b1, th1, wl, lane);
+                    r16::gemm_bt_sc(b0, b1, th1, tsc, wl, lane);
                     u1.b[2 * c] = b0; u1.b[2 * c + 1] = b1;
                     pipe.release();
                 }
@@ -326,7 +330,7 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_edge_kernel
                 stat(2, nn); stat(3, kk);
                 r16::ln_tangent(u1, nn, kk);
             }
-            th2.set(u1);
+            th2sc = th2.set_tangent(u1);
         } else {
 #pragma unroll
             for (int c = 0; c < 2 * NB; ++c) { (void)pipe.acquire(); pipe.release(); }      // keep the stream in phase
@@ -366,7 +370,7 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_edge_kernel
             const f32x4 A0 = g[0], A1 = g[64], B0 = g[128], B1 = g[192], Q0 = g[256], Q1 = g[320];
             f32x4 ta0 = Z4, ta1 = Z4;
             const f32x4* wl = pipe.acquire();
-            if (!first) r16::gemm_fl(ta0, ta1, th2, wl, lane);
+            if (!first) r16::gemm_fl_sc(ta0, ta1, th2, th2sc, wl, lane);
             pipe.release();
             r0 = A0 * B0; r1 = A1 * B1;
             d0 = ta0 * B0 + A0 * (dd * Q0); d1 = ta1 * B1 + A1 * (dd * Q1);
@@ -514,17 +518,18 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_node_kernel(const JvpNodePar
 #pragma unroll 1
     for (int c = 0; c < 3; ++c) {
         OP ve;
+        float vsc;                                  // v is an un-normalised stream
         {
             A16 t;
             veff(c, t);
-            ve.set(t);
+            vsc = ve.set_scaled(t);
         }
         A16 vv;
 #pragma unroll
         for (int ch = 0; ch < NB; ++ch) {
             const f32x4* wl = pipe.acquire();
             f32x4 a0 = Z4, a1 = Z4;
-            r16::gemm_bt(a0, a1, ve, wl, lane);
+            r16::gemm_bt_sc(a0, a1, ve, vsc, wl, lane);
             vv.b[2 * ch] = a0; vv.b[2 * ch + 1] = a1;
             n2.b[2 * ch] += a0 * a0; n2.b[2 * ch + 1] += a1 * a1;
             pipe.release();
@@ -555,26 +560,27 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_node_kernel(const JvpNodePar
         for (int nb = 0; nb < NBK; ++nb) t.b[nb] = r16::load_block(vec + UV::B0 * F, nb, q);
         {
             OP nn;
-            nn.set(n2);
+            const float nsc = nn.set_scaled(n2);
 #pragma unroll
             for (int ch = 0; ch < NB; ++ch) {
                 const f32x4* wl = pipe.acquire();
-                r16::gemm_bt(t.b[2 * ch], t.b[2 * ch + 1], nn, wl, lane);
+                r16::gemm_bt_sc(t.b[2 * ch], t.b[2 * ch + 1], nn, nsc, wl, lane);
                 pipe.release();
             }
         }
         {
             OP ss;
+            float ssc;
             {
                 A16 x;
 #pragma unroll
                 for (int nb = 0; nb < NBK; ++nb) x.b[nb] = r16::load_block(sb, nb, q) + r16::load_block(ab, nb, q);
-                ss.set(x);
+                ssc = ss.set_scaled(x);
             }
 #pragma unroll
             for (int ch = 0; ch < NB; ++ch) {
                 const f32x4* wl = pipe.acquire();
-                r16::gemm_bt(t.b[2 * ch], t.b[2 * ch + 1], ss, wl, lane);
+                r16::gemm_bt_sc(t.b[2 * ch], t.b[2 * ch + 1], ss, ssc, wl, lane);
                 pipe.release();
             }
         }
@@ -629,17 +635,18 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_node_kernel(const JvpNodePar
 #pragma unroll 1
     for (int c = 0; c < 3; ++c) {
         OP ve;
+        float vsc;
         {
             A16 t;
             veff(c, t);
-            ve.set(t);
+            vsc = ve.set_scaled(t);
         }
         A16 uv;
 #pragma unroll
         for (int ch = 0; ch < NB; ++ch) {
             const f32x4* wl = pipe.acquire();
             f32x4 a0 = Z4, a1 = Z4;
-            r16::gemm_bt(a0, a1, ve, wl, lane);
+            r16::gemm_bt_sc(a0, a1, ve, vsc, wl, lane);
             uv.b[2 * ch] = a0; uv.b[2 * ch + 1] = a1;
             pipe.release();
         }
@@ -702,12 +709,12 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             OP tve;
-            tve.set(u[c]);
+            const float tsc = tve.set_tangent(u[c]);
 #pragma unroll
             for (int ch = 0; ch < NB; ++ch) {
                 const f32x4* wl = pipe.acquire();
                 f32x4 b0 = Z4, b1 = Z4;
-                r16::gemm_bt(b0, b1, tve, wl, lane);
+                r16::gemm_bt_sc(b0, b1, tve, tsc, wl, lane);
                 tn.b[2 * ch] += stat(c, 2 * ch) * b0; tn.b[2 * ch + 1] += stat(c, 2 * ch + 1) * b1;
                 pipe.release();
             }
@@ -716,17 +723,18 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
     // ---- phase B: tangent of MLP([ |vv| , s + ds ])
     A16 tsn;                                        // ts + tds, then ts after the update (phase D's operand): read once, kept in registers
     OP th2;
+    float th2sc;
     {
         A16 u;
 #pragma unroll
         for (int nb = 0; nb < NBK; ++nb) u.b[nb] = Z4;
         {
             OP tnn;
-            tnn.set(tn);
+            const float tsc = tnn.set_tangent(tn);
 #pragma unroll
             for (int ch = 0; ch < NB; ++ch) {
                 const f32x4* wl = pipe.acquire();
-                r16::gemm_bt(u.b[2 * ch], u.b[2 * ch + 1], tnn, wl, lane);
+                r16::gemm_bt_sc(u.b[2 * ch], u.b[2 * ch + 1], tnn, tsc, wl, lane);
                 pipe.release();
             }
         }
@@ -734,11 +742,11 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
             OP tss;
 #pragma unroll
             for (int nb = 0; nb < NBK; ++nb) tsn.b[nb] = r16::load_block(tsb, nb, q) + r16::load_block(tab, nb, q);
-            tss.set(tsn);
+            const float tsc = tss.set_tangent(tsn);
 #pragma unroll
             for (int ch = 0; ch < NB; ++ch) {
                 const f32x4* wl = pipe.acquire();
-                r16::gemm_bt(u.b[2 * ch], u.b[2 * ch + 1], tss, wl, lane);
+                r16::gemm_bt_sc(u.b[2 * ch], u.b[2 * ch + 1], tss, tsc, wl, lane);
                 pipe.release();
             }
         }
@@ -750,12 +758,12 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
         }
         {
             OP th1;
-            th1.set(u);
+            const float tsc = th1.set_tangent(u);
 #pragma unroll
             for (int ch = 0; ch < NB; ++ch) {
                 const f32x4* wl = pipe.acquire();
                 f32x4 b0 = Z4, b1 = Z4;
-                r16::gemm_bt(b0, b1, th1, wl, lane);
+                r16::gemm_bt_sc(b0, b1, th1, tsc, wl, lane);
                 u.b[2 * ch] = b0; u.b[2 * ch + 1] = b1;
                 pipe.release();
             }
@@ -766,18 +774,18 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
             for (int nb = 0; nb < NBK; ++nb) { nn.b[nb] = stat(6, nb); kk.b[nb] = stat(7, nb); }
             r16::ln_tangent(u, nn, kk);
         }
-        th2.set(u);
+        th2sc = th2.set_tangent(u);
     }
     // ---- output chunks: ts += 2 n n' q + n^2 q' + add'
 #pragma unroll
     for (int ch = 0; ch < NB; ++ch) {
         const f32x4* wl = pipe.acquire();
         f32x4 tq0 = Z4, tq1 = Z4;
-        r16::gemm_bt(tq0, tq1, th2, wl, lane);
+        r16::gemm_bt_sc(tq0, tq1, th2, th2sc, wl, lane);
         pipe.release();
         wl = pipe.acquire();
         f32x4 ta0 = Z4, ta1 = Z4;
-        r16::gemm_bt(ta0, ta1, th2, wl, lane);
+        r16::gemm_bt_sc(ta0, ta1, th2, th2sc, wl, lane);
         pipe.release();
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -801,7 +809,7 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
     for (int ch = 0; ch < NB; ++ch) {
         const f32x4* wl = pipe.acquire();
         f32x4 b0 = Z4, b1 = Z4;
-        r16::gemm_bt(b0, b1, th2, wl, lane);
+        r16::gemm_bt_sc(b0, b1, th2, th2sc, wl, lane);
         tgg.b[2 * ch] = b0; tgg.b[2 * ch + 1] = b1;
         pipe.release();
     }
@@ -811,12 +819,12 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
         OP tve;
         A16 u;                                      // the parked tv_eff row: operand and addend, read once
         r16::load_set(u, tdb + c * F, q);
-        tve.set(u);
+        const float tsc = tve.set_tangent(u);
 #pragma unroll
         for (int ch = 0; ch < NB; ++ch) {
             const f32x4* wl = pipe.acquire();
             f32x4 b0 = Z4, b1 = Z4;
-            r16::gemm_bt(b0, b1, tve, wl, lane);
+            r16::gemm_bt_sc(b0, b1, tve, tsc, wl, lane);
             pipe.release();
             if (ok) {
                 r16::store_block(tvb + c * F, 2 * ch, q, u.b[2 * ch] + (b0 * stat(9, 2 * ch) + stat(10 + c, 2 * ch) * tgg.b[2 * ch]));
@@ -837,12 +845,12 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_update_kern
     // ---- phase D: tangent of P for the next message block (no bias)
     if (p.has_next) {
         OP sn;
-        sn.set(tsn);                                // the rows written above, still in registers
+        const float tsc = sn.set_tangent(tsn);      // the rows written above, still in registers
 #pragma unroll
         for (int ch = 0; ch < NB; ++ch) {
             const f32x4* wl = pipe.acquire();
             f32x4 a0 = Z4, a1 = Z4;
-            r16::gemm_bt(a0, a1, sn, wl, lane);
+            r16::gemm_bt_sc(a0, a1, sn, tsc, wl, lane);
             pipe.release();
             if (ok) { r16::store_block(p.tP + (size_t)nd * F, 2 * ch, q, a0); r16::store_block(p.tP + (size_t)nd * F, 2 * ch + 1, q, a1); }
         }
@@ -879,18 +887,19 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_readout_ker
     A16 t, u;
     {
         OP ss, tss;
+        float ssc, tsc;
         {
             A16 x, y;
             r16::load_set(x, p.s + pn * F, q);
             r16::load_set(y, p.ts + (size_t)nd * F, q);
-            ss.set(x); tss.set(y);
+            ssc = ss.set_scaled(x); tsc = tss.set_tangent(y);
         }
 #pragma unroll
         for (int ch = 0; ch < NB; ++ch) {
             const f32x4* wl = pipe.acquire();
             f32x4 a0 = r16::load_block(vec + RV::B0 * F, 2 * ch, q), a1 = r16::load_block(vec + RV::B0 * F, 2 * ch + 1, q);
             f32x4 b0 = Z4, b1 = Z4;
-            r16::gemm_bt2(a0, a1, b0, b1, ss, tss, wl, lane);
+            r16::gemm_bt2_sc(a0, a1, b0, b1, ss, ssc, tss, tsc, wl, lane);
             t.b[2 * ch] = a0; t.b[2 * ch + 1] = a1; u.b[2 * ch] = b0; u.b[2 * ch + 1] = b1;
             pipe.release();
         }
@@ -898,13 +907,14 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_readout_ker
     r16::ln_silu_dual(t, u, vec + RV::G0 * F, vec + RV::BE0 * F, q);
     {
         OP h1, th1;
-        h1.set(t); th1.set(u);
+        h1.set(t);
+        const float tsc = th1.set_tangent(u);
 #pragma unroll
         for (int ch = 0; ch < NB; ++ch) {
             const f32x4* wl = pipe.acquire();
             f32x4 a0 = r16::load_block(vec + RV::B1 * F, 2 * ch, q), a1 = r16::load_block(vec + RV::B1 * F, 2 * ch + 1, q);
             f32x4 b0 = Z4, b1 = Z4;
-            r16::gemm_bt2(a0, a1, b0, b1, h1, th1, wl, lane);
+            r16::gemm_bt2_sc(a0, a1, b0, b1, h1, 1.0f, th1, tsc, wl, lane);
             t.b[2 * ch] = a0; t.b[2 * ch + 1] = a1; u.b[2 * ch] = b0; u.b[2 * ch + 1] = b1;
             pipe.release();
         }
