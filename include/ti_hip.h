@@ -8,6 +8,7 @@
  *   ti_adw_create / ti_adw_drift      FCNetMultiBeta.__init__/forward      adw/thermo/models/simple.py:11-41
  *                                     + ODEWrapper.forward                 adw/thermo/models/ode_wrapper.py:30-52
  *   ti_adw_rollout                    StandardIntegrator.rollout           adw/thermo/integrators.py:33-68
+ *   ti_adw_create_nd                  FCNetMultiBeta(d, d, H, L), 1 <= d <= 16  adw/thermo/models/simple.py:11-41
  *   ti_painn_create / ti_painn_drift  cPaiNN.__init__/forward              mdqm9/thermo/ambient/models/cpainn.py:23-115
  *                                                                          mdqm9/thermo/latent/models/cpainn.py:23-108
  *                                     + ODEWrapper.forward/reset_batch     mdqm9/thermo/{ambient,latent}/models/ode_wrapper.py
@@ -46,6 +47,7 @@
  *            readout MLP(F,F,2)  Vr[1,F]
  *            nE = 4 (ambient: atom|T0|T1|t), 3 (latent multi-T: atom|T|t), 2 (latent single-T: atom|t)
  *   adw   :  beta_embed: W[H,3] b[H] W[H,H] b[H] W[1,H] b[1] ;  net: W[H,3] b[H] (W[H,H] b[H]) x (num_layers-1) W[1,H] b[1]
+ *            dimension d (ti_adw_create_nd):  net: W[H,d+2] b[H] (W[H,H] b[H]) x (num_layers-1) W[d,H] b[d]  (inputs [x, t, embed])
  *            passed as fp64 (the reference trains/saves in float64, adw/train.py:29); the device computes in fp32.
  */
 #ifndef TI_HIP_H
@@ -149,9 +151,16 @@ int ti_version(void);
 int ti_device_count(void);
 const char* ti_last_error(void);
 
-/* ---- adw: 1-D asymmetric double well ------------------------------------------------------------------------ */
+/* ---- adw: asymmetric double well (1-D) and FCNetMultiBeta toy systems in d dimensions ----------------------------- */
 ti_handle* ti_adw_create(const ti_adw_desc* desc, const double* weights, size_t n_weights, int device);
-/* b[i] = net([x_i, t, beta_embed([beta0_i, beta1_i, t])]);  x,beta0,beta1,out: [B] fp32 [host|device] */
+/* FCNetMultiBeta(d, d, H, L): the drift of a d-dimensional toy system, 1 <= d <= 16 (TI_E_UNSUPPORTED otherwise); the weight
+ * count is that of the layout above (TI_E_ARG otherwise).  Both are checked before any device call.  ti_adw_create is dim = 1.
+ * With a d-dimensional handle the adw calls below take  x, out, x0: [B, d] row-major;  out_path: [rows, B, d];
+ * beta0, beta1, t, out_div: [B];  out_dlogp: [rows, B].  out_div[i] = sum_k d b_ik / d x_ik, the exact divergence (forward mode,
+ * d directions).  EM noise: coordinate k of a particle is component k of the TI_SCHEME_EM draw.  DOPRI5_TRAJ: a particle's
+ * error ratio is the rms over its d entries, maxed with its dlogp entry's. */
+ti_handle* ti_adw_create_nd(const ti_adw_desc* desc, int32_t dim, const double* weights, size_t n_weights, int device);
+/* b[i] = net([x_i, t, beta_embed([beta0_i, beta1_i, t])]);  x,beta0,beta1,out: [B] fp32 [host|device] ([B, d] x / out: see above) */
 int ti_adw_drift(ti_handle* h, const float* x, float t, const float* beta0, const float* beta1, int64_t B, float* out, int mem);
 /* also out_div[i] = d b_i / d x_i, the exact divergence of the 1-D drift by forward-mode differentiation of `net`
  * (ODEWrapper.compute_divergence, adw/thermo/models/ode_wrapper.py:55-67, without its 1e-2 factor) */

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "ti_painn_debug_tap", "ti_painn_debug_read", "ti_painn_debug_poison", "ti_selftest",
     "ti_painn_drift_tv", "ti_painn_drift_div_tv", "ti_adw_drift_tv", "ti_rollout_step_counts",
     "ti_painn_drift_div_est", "ti_painn_drift_div_est_tv", "ti_painn_rollout_dlogp_est",
+    "ti_adw_create_nd",
 ]
 
 
@@ -100,6 +101,8 @@ def lib():
     L.ti_painn_rollout_dlogp.argtypes = [vp, C.POINTER(RolloutDesc), vp, vp, C.c_int64, C.c_float, C.c_float, C.c_int, vp, vp, C.POINTER(C.c_int64)]
     L.ti_adw_create.restype = vp
     L.ti_adw_create.argtypes = [C.POINTER(AdwDesc), C.POINTER(C.c_double), C.c_size_t, C.c_int]
+    L.ti_adw_create_nd.restype = vp
+    L.ti_adw_create_nd.argtypes = [C.POINTER(AdwDesc), C.c_int32, C.POINTER(C.c_double), C.c_size_t, C.c_int]
     L.ti_adw_drift.argtypes = [vp, vp, C.c_float, vp, vp, C.c_int64, vp, C.c_int]
     L.ti_adw_rollout.argtypes = [vp, C.POINTER(RolloutDesc), vp, vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.ti_adw_drift_div.argtypes = [vp, vp, C.c_float, vp, vp, C.c_int64, vp, vp, C.c_int]

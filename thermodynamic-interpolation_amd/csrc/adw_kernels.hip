@@ -99,7 +99,156 @@ __global__ __launch_bounds__(256, (NBK <= 8 && !TAN) ? 2 : 1) void adw_mlp_kerne
     pipe.drain();
 }
 
-static size_t adw_lds_bytes(int NB, int n_hidden) { return 2 * (size_t)256 * NB * 16 + (size_t)(5 + n_hidden) * 32 * NB * 4; }
+// ---- d-dimensional net (FCNetMultiBeta(d, d, H, L), 2 <= d <= 16).  Inputs [x_0 .. x_{d-1}, t, embed], outputs d.
+// Vector block (floats): w_in [H][Kpad] (Kpad = d + 2 rounded up to 4, zero columns) | b_in [H] | b_hidden [n_hidden][H] |
+// w_out [d][H] | b_out [d] (padded to 4).  The beta embedding stays on adw_mlp_kernel (3 inputs, 1 output).
+// TAN: out_div = sum_i d out_i / d x_i, forward mode.  Direction i starts as silu'(z) * W_in[:, i] and needs only output i.  The
+// directions run in groups of G (a register budget: G tangent sets + their operands beside the primal's); every group recomputes the
+// primal, and each hidden-layer weight chunk from pipe.acquire() feeds the primal and all G tangent products of that chunk.  The
+// weight stream is cyclic (PipeDMA), so a group simply streams the hidden layers again.
+constexpr int ADW_MAX_DIM = 16, ADW_KMAX4 = (ADW_MAX_DIM + 2 + 3) / 4;
+__host__ __device__ constexpr int adw_tan_group(int NBK) { return NBK >= 16 ? 1 : NBK >= 8 ? 2 : NBK >= 4 ? 4 : 8; }
+
+template <int NBK, bool SPLIT, bool TAN, int G>
+__global__ __launch_bounds__(256, (NBK <= 8 && !TAN) ? 2 : 1) void adw_mlp_nd_kernel(const AdwParams p)
+{
+    constexpr int H = 16 * NBK, NB = (H + 31) / 32, WAVES = 4, T = 64 * WAVES, CH4 = 256 * NB, GT = TAN ? G : 1;
+    using A16 = r16::Act<NBK>;
+    using OP = r16::Opnd<NBK, SPLIT>;
+    extern __shared__ f32x4 lds[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 15, q = lane >> 4;
+    const int d = p.dim, kp4 = (d + 5) / 4, Kpad = 4 * kp4;
+    float* vec = reinterpret_cast<float*>(lds + 2 * CH4);
+    const int nvec4 = ((Kpad + 1 + p.n_hidden + d) * H + 4 * ((d + 3) / 4)) / 4;
+    for (int i = threadIdx.x; i < nvec4; i += T) reinterpret_cast<f32x4*>(vec)[i] = reinterpret_cast<const f32x4*>(p.vecs)[i];
+    PipeDMA<NB, T, 1> pipe;
+    if (p.nch > 0) pipe.init(reinterpret_cast<const f32x4*>(p.stream), p.nch, lds, wave, lane);
+    else __syncthreads();
+    const float* w_in = vec;
+    const float* b_in = vec + Kpad * H;
+    const float* b_hid = b_in + H;
+    const float* w_out = b_hid + (size_t)p.n_hidden * H;
+    const float* b_out = w_out + (size_t)d * H;
+
+    const long long row = ((long long)blockIdx.x * WAVES + wave) * 16 + j;
+    const bool ok = row < p.B;
+    const long long r = ok ? row : p.B - 1;
+    const float a1 = p.in1 ? p.in1[r] : p.t;
+    const float a2 = p.idx ? p.emb[p.idx[r]] : (p.emb ? p.emb[r] : p.t);
+    float a[4 * ADW_KMAX4];
+#pragma unroll
+    for (int c = 0; c < 4 * ADW_KMAX4; ++c) a[c] = c < d ? p.x[r * d + c] : c == d ? a1 : c == d + 1 ? a2 : 0.f;
+
+    auto act = [](float z, float& y, float& dy) {
+        const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+        y = z * sg;
+        dy = fmaf(y, 1.0f - sg, sg);
+    };
+    float dsum = 0.f;
+    for (int g0 = 0; g0 < (TAN ? d : 1); g0 += GT) {
+        A16 cur, tan[GT];
+        // input layer (K = Kpad): FMAs over whole f32x4 columns, straight into the register layout
+#pragma unroll
+        for (int nb = 0; nb < NBK; ++nb) {
+            const f32x4 bb = r16::load_block(b_in, nb, q);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float* w = w_in + (size_t)(16 * nb + 4 * q + k) * Kpad;
+                float z = bb[k];
+#pragma unroll
+                for (int c4 = 0; c4 < ADW_KMAX4; ++c4)
+                    if (c4 < kp4) {
+                        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + 4 * c4);
+                        z = fmaf(wv.w, a[4 * c4 + 3], fmaf(wv.z, a[4 * c4 + 2], fmaf(wv.y, a[4 * c4 + 1], fmaf(wv.x, a[4 * c4], z))));
+                    }
+                float y, dy;
+                act(z, y, dy);
+                cur.b[nb][k] = y;
+                if constexpr (TAN) {
+#pragma unroll
+                    for (int g = 0; g < GT; ++g) tan[g].b[nb][k] = g0 + g < d ? dy * w[g0 + g] : 0.f;
+                }
+            }
+        }
+        // hidden layers
+        for (int l = 0; l < p.n_hidden; ++l) {
+            OP in, tin[GT];
+            in.set(cur);
+            if constexpr (TAN) {
+#pragma unroll
+                for (int g = 0; g < GT; ++g) tin[g].set(tan[g]);
+            }
+            const float* bias = b_hid + (size_t)l * H;
+#pragma unroll
+            for (int ch = 0; ch < NB; ++ch) {
+                const f32x4* wl = pipe.acquire();
+                f32x4 z0 = r16::load_block(bias, 2 * ch, q), z1 = r16::load_block(bias, 2 * ch + 1, q);
+                r16::gemm_bt(z0, z1, in, wl, lane);
+                f32x4 t0[GT], t1[GT];
+                if constexpr (TAN) {
+#pragma unroll
+                    for (int g = 0; g < GT; ++g) {
+                        t0[g] = f32x4{0, 0, 0, 0}; t1[g] = f32x4{0, 0, 0, 0};
+                        r16::gemm_bt(t0[g], t1[g], tin[g], wl, lane);
+                    }
+                }
+                pipe.release();
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float y0, dy0, y1, dy1;
+                    act(z0[k], y0, dy0); cur.b[2 * ch][k] = y0;
+                    act(z1[k], y1, dy1); cur.b[2 * ch + 1][k] = y1;
+                    if constexpr (TAN) {
+#pragma unroll
+                        for (int g = 0; g < GT; ++g) { tan[g].b[2 * ch][k] = dy0 * t0[g][k]; tan[g].b[2 * ch + 1][k] = dy1 * t1[g][k]; }
+                    }
+                }
+            }
+        }
+        // output layer: one dot product per component for the primal (first group only), one per direction for the tangents
+        if (g0 == 0) {
+            for (int i = 0; i < d; ++i) {
+                const float* wo = w_out + (size_t)i * H;
+                float o = 0.f;
+#pragma unroll
+                for (int nb = 0; nb < NBK; ++nb) {
+                    const f32x4 w = r16::load_block(wo, nb, q);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o = fmaf(cur.b[nb][k], w[k], o);
+                }
+                o = r16::xquarters(o) + b_out[i];
+                if (ok && q == 0) p.out[row * d + i] = o;
+            }
+        }
+        if constexpr (TAN) {
+#pragma unroll
+            for (int g = 0; g < GT; ++g) {
+                if (g0 + g >= d) break;
+                const float* wo = w_out + (size_t)(g0 + g) * H;
+#pragma unroll
+                for (int nb = 0; nb < NBK; ++nb) {
+                    const f32x4 w = r16::load_block(wo, nb, q);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) dsum = fmaf(tan[g].b[nb][k], w[k], dsum);
+                }
+            }
+        }
+    }
+    if constexpr (TAN) {
+        dsum = r16::xquarters(dsum);
+        if (ok && q == 0) p.out_div[row] = dsum;
+    }
+    pipe.drain();
+}
+
+// floats of the per-MLP vector block: dim 1 (adw_mlp_kernel) w_in [H][3] b_in b_hidden w_out; dim > 1 as adw_mlp_nd_kernel above
+static size_t adw_vec_floats(int H, int n_hidden, int dim)
+{
+    if (dim <= 1) return (size_t)(5 + n_hidden) * H;
+    return (size_t)(4 * ((dim + 5) / 4) + 1 + n_hidden + dim) * H + 4 * ((dim + 3) / 4);
+}
+size_t adw_vec_floats_host(int H, int n_hidden, int dim) { return adw_vec_floats(H, n_hidden, dim); }
+static size_t adw_lds_bytes(int NB, int n_hidden, int dim = 1) { return 2 * (size_t)256 * NB * 16 + adw_vec_floats(32 * NB, n_hidden, dim) * 4; }
 
 #define TI_DISPATCH_NB(NBv, ...) \
     switch (NBv) {                                                            \
@@ -117,13 +266,16 @@ static hipError_t adw_set_attrs(size_t bytes)
 #define TI_SET(k) if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) != hipSuccess) return e
     TI_SET((adw_mlp_kernel<NBK, false, false>)); TI_SET((adw_mlp_kernel<NBK, true, false>));
     TI_SET((adw_mlp_kernel<NBK, false, true>)); TI_SET((adw_mlp_kernel<NBK, true, true>));
+    constexpr int G = adw_tan_group(NBK);
+    TI_SET((adw_mlp_nd_kernel<NBK, false, false, G>)); TI_SET((adw_mlp_nd_kernel<NBK, true, false, G>));
+    TI_SET((adw_mlp_nd_kernel<NBK, false, true, G>)); TI_SET((adw_mlp_nd_kernel<NBK, true, true, G>));
 #undef TI_SET
     return hipSuccess;
 }
 
-hipError_t configure_adw_kernels(int NBv, int max_hidden)
+hipError_t configure_adw_kernels(int NBv, int max_hidden, int dim)
 {
-    TI_DISPATCH_NB(NBv, return (adw_set_attrs<2 * NB>(adw_lds_bytes(NB, max_hidden))));
+    TI_DISPATCH_NB(NBv, return (adw_set_attrs<2 * NB>(std::max(adw_lds_bytes(NB, max_hidden), adw_lds_bytes(NB, max_hidden, dim)))));
     return hipSuccess;
 }
 
@@ -131,8 +283,21 @@ hipError_t launch_adw(int NBv, bool split, const AdwParams& p, hipStream_t st)
 {
     TI_DISPATCH_NB(NBv, {
         const dim3 g((unsigned)((p.B + 63) / 64));
-        const size_t l = adw_lds_bytes(NB, p.n_hidden);
         const bool tanv = p.out_div != nullptr;
+        if (p.dim > 1) {
+            if (p.dim > ADW_MAX_DIM) return hipErrorInvalidValue;
+            const size_t l = adw_lds_bytes(NB, p.n_hidden, p.dim);
+            constexpr int G = adw_tan_group(2 * NB);
+            if (split) {
+                if (tanv) hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, true, true, G>), g, dim3(256), l, st, p);
+                else hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, true, false, G>), g, dim3(256), l, st, p);
+            } else {
+                if (tanv) hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, false, true, G>), g, dim3(256), l, st, p);
+                else hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, false, false, G>), g, dim3(256), l, st, p);
+            }
+            break;
+        }
+        const size_t l = adw_lds_bytes(NB, p.n_hidden);
         if (split) {
             if (tanv) hipLaunchKernelGGL((adw_mlp_kernel<2 * NB, true, true>), g, dim3(256), l, st, p);
             else hipLaunchKernelGGL((adw_mlp_kernel<2 * NB, true, false>), g, dim3(256), l, st, p);

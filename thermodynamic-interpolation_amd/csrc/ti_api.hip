@@ -204,6 +204,7 @@ struct ti_handle {
     ti_adw_desc ad{};
     size_t a_be_vecs = 0, a_net_vecs = 0;          // offsets of the per-MLP vector blocks in `flat`
     float a_be_b_out = 0.f, a_b_out = 0.f;
+    int a_dim = 1;                                 // d of FCNetMultiBeta(d, d, H, L): floats per particle of x / b
     Stream st_be{}, st_net{};
     DevBuf<float> ax, ab1, ab2, axt, aemb_u, abeta0_u, abeta1_u, adl, ad1, ad2; DevBuf<int32_t> aidx;
     DevBuf<float> abeta0_r, abeta1_r, aemb_r, atv;                  // per-row conditioning / beta embedding / times (per-row t)
@@ -878,6 +879,7 @@ void adw_mlp_launch(ti_handle* h, bool embed, const float* a0, const float* in1,
     p.vecs = h->F(embed ? h->a_be_vecs : h->a_net_vecs);
     p.b_out = embed ? h->a_be_b_out : h->a_b_out; p.n_hidden = embed ? 1 : h->ad.num_layers - 1; p.B = rows;
     p.x = a0; p.in1 = in1; p.emb = emb; p.idx = idx; p.t = t; p.out = out; p.out_div = out_div;
+    p.dim = embed ? 1 : h->a_dim;
     Timed tm(h, TI_KERNEL_ADW);
     HIP_CHECK(launch_adw(h->NB, h->ad.precision == TI_PREC_F16X2, p, h->stream));
 }
@@ -904,7 +906,7 @@ long long adw_set_cond(ti_handle* h, const float* beta0, const float* beta1, lon
     return (long long)u0.size();
 }
 
-// out_div (may be NULL): d b / d x, the divergence of the 1-D drift (beta_embed does not depend on x)
+// out_div (may be NULL): sum_i d b_i / d x_i, the divergence of the drift (beta_embed does not depend on x); x / out [B][d]
 void adw_drift_dev(ti_handle* h, const float* x_dev, float t, long long U, long long B, float* out_dev, float* out_div)
 {
     adw_mlp_launch(h, true, h->abeta0_u.p, h->abeta1_u.p, nullptr, nullptr, t, U, h->aemb_u.p, nullptr);   // beta_embed([b0, b1, t])
@@ -934,7 +936,8 @@ void adw_rows_dev(ti_handle* h, const float* beta0, const float* beta1, long lon
 void ensure_adw_ws(ti_handle* h, long long B)
 {
     if (B <= h->cap) return;
-    h->ax.alloc(B); h->ab1.alloc(B); h->ab2.alloc(B); h->axt.alloc(B); h->adl.alloc(B); h->ad1.alloc(B); h->ad2.alloc(B);
+    const size_t n = (size_t)B * h->a_dim;             // state floats; the divergence / dlogp buffers hold one per particle
+    h->ax.alloc(n); h->ab1.alloc(n); h->ab2.alloc(n); h->axt.alloc(n); h->adl.alloc(B); h->ad1.alloc(B); h->ad2.alloc(B);
     h->cap = B;
 }
 
@@ -1779,17 +1782,24 @@ int ti_painn_debug_read(ti_handle* h, int what, float* out, size_t n_floats)
 // ------------------------------------------------------------------------------------------------------------ adw
 ti_handle* ti_adw_create(const ti_adw_desc* d, const double* weights, size_t n_weights, int device)
 {
+    return ti_adw_create_nd(d, 1, weights, n_weights, device);
+}
+
+ti_handle* ti_adw_create_nd(const ti_adw_desc* d, int32_t dim, const double* weights, size_t n_weights, int device)
+{
     ti_handle* out = nullptr;
     const int rc = guarded([&]() -> int {
         if (!d || !weights) return fail(TI_E_ARG, "NULL argument");
+        if (dim < 1 || dim > 16) return fail(TI_E_UNSUPPORTED, "dim must be 1..16 (FCNetMultiBeta(d, d, H, L)), got " + std::to_string(dim));
         const int H = d->hidden_size, nl = d->num_layers;
         if (H != 32 && H != 64 && H != 128 && H != 256) return fail(TI_E_UNSUPPORTED, "hidden_size must be 32, 64, 128 or 256");
         if (nl < 1) return fail(TI_E_ARG, "num_layers must be >= 1");
         if (d->precision != TI_PREC_F32 && d->precision != TI_PREC_F16X2) return fail(TI_E_ARG, "unknown precision");
-        const size_t need = (size_t)H * 3 + H + (size_t)H * H + H + H + 1 + (size_t)H * 3 + H + (size_t)(nl - 1) * ((size_t)H * H + H) + H + 1;
+        const size_t need = (size_t)H * 3 + H + (size_t)H * H + H + H + 1 + (size_t)H * (dim + 2) + H + (size_t)(nl - 1) * ((size_t)H * H + H) +
+                            (size_t)dim * H + dim;
         if (n_weights != need) return fail(TI_E_ARG, "weight count mismatch: expected " + std::to_string(need) + ", got " + std::to_string(n_weights));
         std::unique_ptr<ti_handle> h(new_handle(1, device));
-        h->ad = *d; h->NB = H / 32;
+        h->ad = *d; h->NB = H / 32; h->a_dim = dim;
         std::vector<float> w(n_weights);
         for (size_t i = 0; i < n_weights; ++i) w[i] = (float)weights[i];        // the device computes in fp32
         const int NB = h->NB, NBK = H / 16;
@@ -1798,10 +1808,17 @@ ti_handle* ti_adw_create(const ti_adw_desc* d, const double* weights, size_t n_w
         auto chunk16 = [&](const float* W, int row0) {
             if (split) pack_chunk16_split(pk, W, H, H, row0, 0, NBK); else pack_chunk16(pk, W, H, H, row0, 0, NBK);
         };
-        // one MLP block: canonical order  W_in[H,3] b_in[H] (W_h[H,H] b_h[H]) x n_hidden  W_out[1,H] b_out[1]
-        auto take_mlp = [&](size_t& o, int n_hidden, size_t& vec_off, Stream& st, float& b_out) {
+        // one MLP block: canonical order  W_in[H,K] b_in[H] (W_h[H,H] b_h[H]) x n_hidden  W_out[D,H] b_out[D]  (K = D + 2)
+        // D = 1: vector block w_in [H][3] | b_in | b_hidden | w_out, b_out a kernel argument.  D > 1: w_in [H][Kpad] (zero
+        // columns up to a multiple of 4) | b_in | b_hidden | w_out [D][H] | b_out [D] (zeros up to a multiple of 4).
+        auto take_mlp = [&](size_t& o, int n_hidden, size_t& vec_off, Stream& st, float& b_out, int D) {
             vec_off = nat.size();
-            nat.insert(nat.end(), &w[o], &w[o] + (size_t)H * 3); o += (size_t)H * 3;      // w_in
+            const int K = D + 2, Kpad = D == 1 ? 3 : (K + 3) / 4 * 4;
+            for (int f = 0; f < H; ++f) {                                               // w_in
+                nat.insert(nat.end(), &w[o + (size_t)f * K], &w[o + (size_t)f * K] + K);
+                nat.insert(nat.end(), (size_t)(Kpad - K), 0.f);
+            }
+            o += (size_t)H * K;
             nat.insert(nat.end(), &w[o], &w[o] + H); o += H;                              // b_in
             st.off4 = pk.size() / 4;
             std::vector<float> bh;
@@ -1812,15 +1829,18 @@ ti_handle* ti_adw_create(const ti_adw_desc* d, const double* weights, size_t n_w
             }
             st.nch = n_hidden * NB;
             nat.insert(nat.end(), bh.begin(), bh.end());
-            nat.insert(nat.end(), &w[o], &w[o] + H); o += H;                              // w_out
-            b_out = w[o]; o += 1;
+            nat.insert(nat.end(), &w[o], &w[o] + (size_t)D * H); o += (size_t)D * H;      // w_out
+            if (D == 1) { b_out = w[o]; o += 1; return; }
+            nat.insert(nat.end(), &w[o], &w[o] + D); o += D;                               // b_out
+            nat.insert(nat.end(), (size_t)((D + 3) / 4 * 4 - D), 0.f);
+            b_out = 0.f;
         };
         size_t o = 0;
-        take_mlp(o, 1, h->a_be_vecs, h->st_be, h->a_be_b_out);
-        take_mlp(o, nl - 1, h->a_net_vecs, h->st_net, h->a_b_out);
+        take_mlp(o, 1, h->a_be_vecs, h->st_be, h->a_be_b_out, 1);
+        take_mlp(o, nl - 1, h->a_net_vecs, h->st_net, h->a_b_out, dim);
         if (pk.empty()) pk.assign(4, 0.f);
         h->flat.upload(nat); h->packed.upload(pk);
-        HIP_CHECK(configure_adw_kernels(NB, std::max(1, nl - 1)));
+        HIP_CHECK(configure_adw_kernels(NB, std::max(1, nl - 1), dim));
         out = h.release();
         return TI_OK;
     });
@@ -1838,13 +1858,14 @@ static int adw_drift_impl(ti_handle* h, const float* x, float t, const float* be
         ensure_adw_ws(h, B);
         const long long U = adw_set_cond(h, beta0, beta1, B, mem);
         const float* xd = x; float* od = out; float* dd = out_div;
+        const size_t n = (size_t)B * h->a_dim;
         if (mem == TI_MEM_HOST) {
-            HIP_CHECK(hipMemcpyAsync(h->ax.p, x, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(h->ax.p, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
             xd = h->ax.p; od = h->ab1.p; dd = out_div ? h->ad1.p : nullptr;
         }
         adw_drift_dev(h, xd, t, U, B, od, dd);
         if (mem == TI_MEM_HOST) {
-            HIP_CHECK(hipMemcpyAsync(out, od, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipMemcpyAsync(out, od, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
             if (out_div) HIP_CHECK(hipMemcpyAsync(out_div, dd, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         }
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1875,15 +1896,16 @@ int ti_adw_drift_tv(ti_handle* h, const float* x, const float* t, const float* b
         const float *b0d = nullptr, *b1d = nullptr;
         adw_rows_dev(h, beta0, beta1, B, mem, &b0d, &b1d);
         const float *xd = x, *td = t; float* od = out; float* dd = out_div;
+        const size_t n = (size_t)B * h->a_dim;
         if (mem == TI_MEM_HOST) {
             if (h->atv.n < (size_t)B) h->atv.alloc(B);
-            HIP_CHECK(hipMemcpyAsync(h->ax.p, x, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(h->ax.p, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
             HIP_CHECK(hipMemcpyAsync(h->atv.p, t, B * sizeof(float), hipMemcpyHostToDevice, h->stream));
             xd = h->ax.p; td = h->atv.p; od = h->ab1.p; dd = out_div ? h->ad1.p : nullptr;
         }
         adw_drift_tv_dev(h, xd, td, b0d, b1d, B, od, dd);
         if (mem == TI_MEM_HOST) {
-            HIP_CHECK(hipMemcpyAsync(out, od, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipMemcpyAsync(out, od, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
             if (out_div) HIP_CHECK(hipMemcpyAsync(out_div, dd, B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         }
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -1905,8 +1927,11 @@ static int adw_rollout_impl(ti_handle* h, const ti_rollout_desc* rd, const float
         ensure_adw_ws(h, B);
         const long long U = adw_set_cond(h, beta0, beta1, B, rd->mem);
         const hipMemcpyKind in_kind = rd->mem == TI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        HIP_CHECK(hipMemcpyAsync(h->ax.p, x0, B * sizeof(float), in_kind, h->stream));
+        const int D = h->a_dim;
+        const size_t n = (size_t)B * D;
+        HIP_CHECK(hipMemcpyAsync(h->ax.p, x0, n * sizeof(float), in_kind, h->stream));
         DlogpAux aux;
+        aux.n_dl = (size_t)B;                        // one dlogp entry per particle
         DevBuf<float> scaled_tmp;                    // dlogp * 1e2 staging for the saved rows
         if (out_dlogp) { scaled_tmp.alloc(B); aux.dl = h->adl.p; aux.d1 = h->ad1.p; aux.d2 = h->ad2.p; aux.scaled = scaled_tmp.p; aux.out = out_dlogp; }
         auto drift = [&](const float* xs, float t, float* o, float* dv) { adw_drift_dev(h, xs, t, U, B, o, dv); };
@@ -1914,10 +1939,10 @@ static int adw_rollout_impl(ti_handle* h, const ti_rollout_desc* rd, const float
             const float *b0d = nullptr, *b1d = nullptr;
             adw_rows_dev(h, beta0, beta1, B, rd->mem, &b0d, &b1d);
             auto drift_tv = [&](const float* xs, const float* tv, float* o, float* dv) { adw_drift_tv_dev(h, xs, tv, b0d, b1d, B, o, dv); };
-            return rollout_rk_traj(h, rd, h->ax.p, B, 1, out_path, n_fevals, drift_tv, aux);
+            return rollout_rk_traj(h, rd, h->ax.p, B, D, out_path, n_fevals, drift_tv, aux);
         }
-        if (rd->scheme >= TI_SCHEME_DOPRI5) return rollout_rk(h, rd, h->ax.p, (size_t)B, out_path, n_fevals, drift, aux);
-        return rollout_common(h, rd, h->ax.p, h->ab1.p, h->ab2.p, h->axt.p, (size_t)B, B, 1, 0, out_path, n_fevals, drift, aux);
+        if (rd->scheme >= TI_SCHEME_DOPRI5) return rollout_rk(h, rd, h->ax.p, n, out_path, n_fevals, drift, aux);
+        return rollout_common(h, rd, h->ax.p, h->ab1.p, h->ab2.p, h->axt.p, n, B, D, 0, out_path, n_fevals, drift, aux);
     });
 }
 

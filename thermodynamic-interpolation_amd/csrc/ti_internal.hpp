@@ -196,9 +196,12 @@ struct AdwParams {
     float t;
     float* out;
     float* out_div;                         // non-NULL: also d out / d a0 (forward-mode tangent)
+    int dim;                                // 0 / 1: the layout above.  2..16: the d-dimensional net (adw_mlp_nd_kernel): x and out
+                                            // [B][dim], vecs w_in [H][Kpad] | b_in | b_hidden | w_out [dim][H] | b_out [dim], and
+                                            // out_div = sum_i d out_i / d x_i
 };
 hipError_t launch_adw(int NB, bool split, const AdwParams& p, hipStream_t st);
-hipError_t configure_adw_kernels(int NB, int max_hidden);
+hipError_t configure_adw_kernels(int NB, int max_hidden, int dim);
 
 // ---- integrator kernels (integrate_kernels.hip)
 hipError_t launch_axpy(float* y, const float* x, float a, const float* b, long long n, hipStream_t st);          // y = x + a*b

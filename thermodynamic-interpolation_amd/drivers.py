@@ -97,6 +97,9 @@ def sample_latent(config, b, dataset):
 
 def sample_adw(config, b, x0s_batches):
     """`x0s_batches`: iterable of (x0s [B,1], beta0s [B,1]) like the reference's test loader (adw/sample.py:41-43)."""
+    if getattr(b, "dim", 1) != 1:
+        raise NotImplementedError(f"sample_adw writes the 1-D double well's samples (component 0, adw/sample.py:59); "
+                                  f"a d = {b.dim} model would lose coordinates: use StandardIntegrator.rollout directly")
     assert len(config.beta0s) == len(config.beta1s) == 1            # adw/sample.py:24
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),

@@ -319,35 +319,44 @@ class PainnEngine(_Engine):
 
 
 class AdwEngine(_Engine):
-    """FCNetMultiBeta drift (+ exact divergence) and fixed-step integrator for the 1-D double well."""
+    """FCNetMultiBeta drift (+ exact divergence) and fixed-step / adaptive integrators: the 1-D double well (dim = 1) and
+    FCNetMultiBeta(d, d, H, L) toy systems in d = dim <= 16 dimensions."""
 
-    def __init__(self, hidden, num_layers, flat_weights_f64, device=0, precision="f32"):
+    def __init__(self, hidden, num_layers, flat_weights_f64, device=0, precision="f32", dim=1):
         if precision not in _lib.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
-        self.hidden, self.num_layers, self.precision = int(hidden), int(num_layers), precision
+        self.hidden, self.num_layers, self.precision, self.dim = int(hidden), int(num_layers), precision, int(dim)
         self.desc = _lib.AdwDesc(self.hidden, self.num_layers, _lib.PRECISIONS[precision])
         w = np.ascontiguousarray(flat_weights_f64, np.float64)
         self.device = int(device)
-        self.h = _lib.lib().ti_adw_create(C.byref(self.desc), w.ctypes.data_as(C.POINTER(C.c_double)), w.size, self.device)
+        if self.dim == 1:
+            self.h = _lib.lib().ti_adw_create(C.byref(self.desc), w.ctypes.data_as(C.POINTER(C.c_double)), w.size, self.device)
+        else:
+            self.h = _lib.lib().ti_adw_create_nd(C.byref(self.desc), self.dim, w.ctypes.data_as(C.POINTER(C.c_double)), w.size, self.device)
         if not self.h:
             raise _lib.TiError(-1, _lib.last_error())
 
+    def _xs(self, *lead):
+        """shape of a state array: lead dims + (d,) for d > 1; the 1-D engine keeps the flat [.., B] shapes"""
+        return tuple(lead) + ((self.dim,) if self.dim > 1 else ())
+
     def drift(self, x, t, beta0, beta1, out=None, return_div=False):
-        """b(x, t) [B]; with return_div also d b / d x (the 1-D divergence, reference scaling NOT applied).  t: a scalar or one
-        time per row ([B])."""
+        """b(x, t) [B] ([B, d] for d > 1); with return_div also the divergence sum_i d b_i / d x_i [B] (reference scaling NOT
+        applied).  t: a scalar or one time per row ([B])."""
         B = int(x.shape[0])
+        xs = self._xs(B)
         like = x if hasattr(x, "data_ptr") and x.is_cuda else None
         if out is None:
-            out = _alloc_like(like, (B,))
+            out = _alloc_like(like, xs)
         div = _alloc_like(like, (B,)) if return_div else None
         tv = self._times(t, B)
         if tv is not None:
-            (xp, tp, b0p, b1p, op, dp), dev, keep = self._ptrs((x, (B,), False, "x"), tv, (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
-                                                               (out, (B,), True, "out"), (div, None, True, "out_div"))
+            (xp, tp, b0p, b1p, op, dp), dev, keep = self._ptrs((x, xs, False, "x"), tv, (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
+                                                               (out, xs, True, "out"), (div, None, True, "out_div"))
             _lib.check(_lib.lib().ti_adw_drift_tv(self.h, xp, tp, b0p, b1p, B, op, dp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
             return (out, div) if return_div else out
-        (xp, b0p, b1p, op, dp), dev, keep = self._ptrs((x, (B,), False, "x"), (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
-                                                       (out, (B,), True, "out"), (div, None, True, "out_div"))
+        (xp, b0p, b1p, op, dp), dev, keep = self._ptrs((x, xs, False, "x"), (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
+                                                       (out, xs, True, "out"), (div, None, True, "out_div"))
         mem = _lib.MEM_DEVICE if dev else _lib.MEM_HOST
         if not return_div:
             _lib.check(_lib.lib().ti_adw_drift(self.h, xp, float(t), b0p, b1p, B, op, mem))
@@ -357,18 +366,18 @@ class AdwEngine(_Engine):
 
     def rollout(self, x0, beta0, beta1, t_grid, scheme="euler", save_every=1, eps=0.0, seed=0, traj_offset=0, out=None,
                 return_dlogp=False, rtol=1e-4, atol=1e-4, step_offset=0, step_control="batch"):
-        """(path [rows,B], n_fevals), or (path, dlogp [rows,B] (already * 1e2 like the reference), n_fevals).  step_control='trajectory'
-        (dopri5 only): every particle gets the steps a batch of one would take (see PainnEngine.rollout)."""
+        """(path [rows,B] ([rows,B,d] for d > 1), n_fevals), or (path, dlogp [rows,B] (already * 1e2 like the reference), n_fevals).
+        step_control='trajectory' (dopri5 only): every particle gets the steps a batch of one would take (see PainnEngine.rollout)."""
         B = int(x0.shape[0])
         on_gpu = hasattr(x0, "data_ptr") and x0.is_cuda
         rd = _rollout_desc(scheme, t_grid, save_every, _lib.MEM_DEVICE if on_gpu else _lib.MEM_HOST, eps, seed, traj_offset, False, rtol, atol,
                            step_offset, step_control)
         rows = int(_lib.lib().ti_rollout_rows(rd.n_step, rd.save_every))
         if out is None:
-            out = _alloc_like(x0 if on_gpu else None, (rows, B))
+            out = _alloc_like(x0 if on_gpu else None, self._xs(rows, B))
         dl = _alloc_like(x0 if on_gpu else None, (rows, B)) if return_dlogp else None
-        (xp, b0p, b1p, op, dp), dev, keep = self._ptrs((x0, (B,), False, "x0"), (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
-                                                       (out, (rows, B), True, "out"), (dl, None, True, "out_dlogp"))
+        (xp, b0p, b1p, op, dp), dev, keep = self._ptrs((x0, self._xs(B), False, "x0"), (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
+                                                       (out, self._xs(rows, B), True, "out"), (dl, None, True, "out_dlogp"))
         nfe = C.c_int64(0)
         if not return_dlogp:
             _lib.check(_lib.lib().ti_adw_rollout(self.h, C.byref(rd), xp, b0p, b1p, B, op, C.byref(nfe)))

@@ -18,13 +18,21 @@ from . import _common as C
 
 
 class FCNetMultiBeta:
-    """Weights-only shell with the reference constructor signature and state_dict key layout."""
+    """Weights-only shell with the reference constructor signature and state_dict key layout.  This mirror keeps the reference
+    sampler's 1-D contract (its ODEWrapper.forward only concatenates at in_size = 1); the d-dimensional model is
+    thermo.adw_nd.FCNetMultiBeta, which the ODEWrapper and StandardIntegrator below drive as well."""
+
+    @staticmethod
+    def _check_sizes(in_size, out_size):
+        if in_size != 1 or out_size != 1:
+            raise NotImplementedError("the HIP path covers the reference's 1-D double well (in_size = out_size = 1) here; "
+                                      "FCNetMultiBeta(d, d, H, L) for 1 <= d <= 16 is thermo.adw_nd.FCNetMultiBeta")
 
     def __init__(self, in_size, out_size, hidden_size, num_layers):
-        if in_size != 1 or out_size != 1:
-            raise NotImplementedError("the HIP path covers the reference's 1-D double well (in_size = out_size = 1)")
+        self._check_sizes(in_size, out_size)
         self.in_size, self.out_size, self.hidden_size, self.num_layers = in_size, out_size, hidden_size, num_layers
-        self._spec = _W.adw_param_spec(hidden_size, num_layers)
+        self.dim = int(in_size)
+        self._spec = _W.adw_param_spec(hidden_size, num_layers, self.dim, self.dim)
         # the reference initialises with torch's default Linear init; weights normally arrive via load_state_dict / torch.load
         self._sd = _syn.make_state_dict(self._spec, seed=0, dtype=np.float64)
         self._engine, self._device = None, 0
@@ -45,9 +53,9 @@ class FCNetMultiBeta:
     def from_torch_module(cls, module):
         """Build from a reference ``FCNetMultiBeta`` instance (what ``torch.load(config.sampling_model)`` returns)."""
         sd = module.state_dict()
-        hidden = int(sd["net.0.weight"].shape[0])
+        hidden, d = int(sd["net.0.weight"].shape[0]), int(sd["net.0.weight"].shape[1]) - 2
         n_lin = sum(1 for k in sd if k.startswith("net.") and k.endswith(".weight"))
-        return cls(1, 1, hidden, n_lin - 1).load_state_dict(sd)
+        return cls(d, d, hidden, n_lin - 1).load_state_dict(sd)
 
     def eval(self):
         self.training = False
@@ -75,12 +83,15 @@ class FCNetMultiBeta:
     def engine(self) -> _engine.AdwEngine:
         if self._engine is None:
             flat = _W.flatten_state_dict(self._sd, self._spec, dtype=np.float64)
-            self._engine = _engine.AdwEngine(self.hidden_size, self.num_layers, flat, device=self._device, precision=self.precision)
+            self._engine = _engine.AdwEngine(self.hidden_size, self.num_layers, flat, device=self._device, precision=self.precision,
+                                             dim=self.dim)
         return self._engine
 
     def forward(self, x0s, xts, ts, beta0s, beta1s):
-        """net([xts, ts, beta_embed([beta0s, beta1s, ts])]) -> [B, 1].  ``x0s`` is unused, as in the reference (simple.py:38-41).
+        """net([xts, ts, beta_embed([beta0s, beta1s, ts])]) -> [B, d].  ``x0s`` is unused, as in the reference (simple.py:38-41).
         ``ts``: one value (the sampler passes ones_like(x) * t, ode_wrapper.py:47) or one per row (what training feeds)."""
+        if self.dim > 1:
+            return self._forward_nd(xts, ts, beta0s, beta1s)
         t = C.to_numpy(ts, np.float32).ravel()
         x = np.ascontiguousarray(C.to_numpy(xts, np.float32).reshape(-1))
         b0 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta0s, np.float32).reshape(-1), x.shape))
@@ -92,6 +103,22 @@ class FCNetMultiBeta:
         else:
             out = self.engine().drift(x, float(t[0]) if t.size else 0.0, b0, b1)
         return C.like(out.reshape(-1, 1), xts)
+
+    def _forward_nd(self, xts, ts, beta0s, beta1s):
+        x = np.ascontiguousarray(C.to_numpy(xts, np.float32).reshape(-1, self.dim))
+        B = x.shape[0]
+        t = C.to_numpy(ts, np.float32).reshape(B, -1) if np.size(C.to_numpy(ts)) > 1 else C.to_numpy(ts, np.float32).ravel()
+        if t.ndim == 2:                          # [B, 1], or ones_like(x) * t: every column of a row must agree
+            if np.any(t != t[:, :1]):
+                raise ValueError("ts must hold one value or one per row")
+            t = t[:, 0]
+        b0 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta0s, np.float32).reshape(-1), (B,)))
+        b1 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta1s, np.float32).reshape(-1), (B,)))
+        if t.size > 1 and np.ptp(t) != 0.0:
+            out = self.engine().drift(x, np.ascontiguousarray(t), b0, b1)
+        else:
+            out = self.engine().drift(x, float(t[0]) if t.size else 0.0, b0, b1)
+        return C.like(out, xts)
 
     __call__ = forward
 
@@ -106,6 +133,8 @@ class ODEWrapper:
     def forward(self, integration_time, states, x0s, beta0s, beta1s):
         xs = states[0] if isinstance(states, (tuple, list)) else states
         t = float(integration_time)
+        if self.b.dim > 1:
+            return self._forward_nd(xs, t, beta0s, beta1s)
         if not self.return_dlogp:
             ts = np.full(C.to_numpy(xs).shape, t, np.float32)
             return self.b.forward(x0s, xs, ts, beta0s, beta1s)
@@ -116,11 +145,31 @@ class ODEWrapper:
         b, div = C.like(b.reshape(-1, 1), xs), C.like(div * np.float32(1e-2), xs)
         return (b, -div) if not self.reverse_ode else (-b, div)
 
+    def _forward_nd(self, xs, t, beta0s, beta1s):
+        d = self.b.dim
+        if len(xs.shape) != 2 or xs.shape[1] != d:
+            raise ValueError(f"xs must be [batch, {d}]")
+        B = int(xs.shape[0])
+        if C.is_cuda(xs):                                    # stay in HBM, as StandardIntegrator.rollout does
+            import torch
+            x = xs.detach().to(torch.float32).contiguous()
+            b0 = torch.as_tensor(beta0s, device=x.device).to(torch.float32).reshape(-1).expand(B).contiguous()
+            b1 = torch.as_tensor(beta1s, device=x.device).to(torch.float32).reshape(-1).expand(B).contiguous()
+        else:
+            x = np.ascontiguousarray(C.to_numpy(xs, np.float32))
+            b0 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta0s, np.float32).reshape(-1), (B,)))
+            b1 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta1s, np.float32).reshape(-1), (B,)))
+        if not self.return_dlogp:
+            return C.like(self.b.engine().drift(x, t, b0, b1), xs)
+        b, div = self.b.engine().drift(x, t, b0, b1, return_div=True)
+        b, div = C.like(b, xs), C.like((div * np.float32(1e-2)).reshape(B, 1), xs)
+        return (b, -div) if not self.reverse_ode else (-b, div)
+
     __call__ = forward
 
 
 class StandardIntegrator:
-    """rollout(x0s, beta0s, beta1s) -> (x [n_saved, B, 1], dlogp)   -- reference: (x [n_step, B, 1], dlogp * 1e2).
+    """rollout(x0s [B, d], beta0s, beta1s) -> (x [n_saved, B, d], dlogp)   -- reference: (x [n_step, B, d], dlogp * 1e2).
 
     ``method``: 'dopri5' (adaptive, rtol / atol; the grid selects the output times) or 'euler' | 'midpoint' | 'rk4' | 'heun' | 'em'
     on the grid torch.linspace(start, end, n_step) (n_step - 1 steps).  Extra keyword
@@ -144,16 +193,17 @@ class StandardIntegrator:
         self.eps, self.seed, self.save_every = eps, seed, save_every
 
     def rollout(self, x0s, beta0s, beta1s, traj_offset: int = 0):
-        if len(x0s.shape) != 2 or x0s.shape[1] != 1:
-            raise ValueError("x0s must be [batch, 1]")
+        d = self.ode_wrapper.b.dim
+        if len(x0s.shape) != 2 or x0s.shape[1] != d:
+            raise ValueError(f"x0s must be [batch, {d}]")
         B = int(x0s.shape[0])
         if C.is_cuda(x0s):                                   # stay in HBM: data_ptr() in, CUDA tensors out
             import torch
-            x0 = x0s.detach().to(torch.float32).reshape(B).contiguous()
+            x0 = x0s.detach().to(torch.float32).reshape((B,) if d == 1 else (B, d)).contiguous()
             b0 = torch.as_tensor(beta0s, device=x0.device).to(torch.float32).reshape(-1).expand(B).contiguous()
             b1 = torch.as_tensor(beta1s, device=x0.device).to(torch.float32).reshape(-1).expand(B).contiguous()
         else:
-            x0 = np.ascontiguousarray(C.to_numpy(x0s, np.float32)[:, 0])
+            x0 = np.ascontiguousarray(C.to_numpy(x0s, np.float32)[:, 0] if d == 1 else C.to_numpy(x0s, np.float32))
             b0 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta0s, np.float32).reshape(-1), (B,)))
             b1 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta1s, np.float32).reshape(-1), (B,)))
         grid = _engine.time_grid(self.start, self.end, self.n_step)
@@ -164,4 +214,4 @@ class StandardIntegrator:
         self.n_fevals = res[-1]
         self.n_steps_per_particle = self.ode_wrapper.b.engine().step_counts(B) if self.step_control == "trajectory" else None
         dlogp = C.like(res[1][:, :, None], x0s) if self.return_dlogp else None
-        return C.like(res[0][:, :, None], x0s), dlogp
+        return C.like(res[0][:, :, None] if d == 1 else res[0], x0s), dlogp
