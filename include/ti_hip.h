@@ -263,6 +263,15 @@ enum { TI_TEMPLATE_AUTO = -1, TI_TEMPLATE_THROUGHPUT = 0, TI_TEMPLATE_LATENCY = 
 int ti_painn_set_template(ti_handle* h, int which);
 /* the layout ti_painn_drift / ti_painn_rollout would choose for a batch of B molecules (TI_TEMPLATE_THROUGHPUT / _LATENCY / _PAIR) */
 int ti_painn_template_for(ti_handle* h, int64_t B);
+/* Per-molecule edge sets over the handle's template.  mask [B][A]: bit s of mask[b*A + d] = edge s -> d exists in molecule b.
+ * Template edges whose bit is clear contribute nothing to molecule b (drift, JVP, exact and Hutchinson divergence, every
+ * rollout scheme, both dopri5 step controls); bits of pairs outside the template are ignored.  The mask is copied into the
+ * handle and stays in force for later calls whose B equals its B (another B: TI_E_ARG); mask == NULL clears it.
+ * Molecule indices are local to the call, like x0: a traj_offset shard passes its slice of the mask.  The pair layout is
+ * eligible only while every molecule's set is symmetric over the template (checked here); a call on a handle pinned to
+ * TI_TEMPLATE_PAIR with an asymmetric mask in force returns TI_E_UNSUPPORTED.  A NULL or non-painn handle, B < 1 with a
+ * non-NULL mask, or an unknown mem: TI_E_ARG before any device work.  An all-ones mask gives the unmasked results bit for bit. */
+int ti_painn_set_edge_mask(ti_handle* h, const uint32_t* mask, int64_t B, int mem);
 /* Pre-size the HBM workspace for batches up to B trajectories (otherwise grown on demand). */
 int ti_reserve(ti_handle* h, int64_t B);
 /* Live kernel timing with HIP events on the handle's stream (bench.py roofline leg). */

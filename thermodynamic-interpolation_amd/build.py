@@ -10,8 +10,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libti_hip.so")
 SOURCES = ["ti_api.hip", "painn_kernels.hip", "painn_edge_nb1.hip", "painn_edge_nb2.hip", "painn_edge_nb4.hip", "painn_edge_nb8.hip",
-           "painn_pair_nb1.hip", "painn_pair_nb2.hip", "painn_pair_nb4.hip", "painn_jvp_kernels.hip", "adw_kernels.hip", "ode_kernels.hip"]
-HEADERS = ["mfma_chain.hpp", "ti_internal.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", os.path.join("..", "..", "include", "ti_hip.h")]
+           "painn_pair_nb1.hip", "painn_pair_nb2.hip", "painn_pair_nb4.hip", "painn_jvp_kernels.hip", "adw_kernels.hip", "ode_kernels.hip",
+           # masked twins of the message kernels (per-molecule edge sets), in translation units of their own
+           "painn_edge_mask_nb1.hip", "painn_edge_mask_nb2.hip", "painn_edge_mask_nb4.hip", "painn_edge_mask_nb8.hip",
+           "painn_pair_mask_nb1.hip", "painn_pair_mask_nb2.hip", "painn_pair_mask_nb4.hip"]
+HEADERS = ["mfma_chain.hpp", "ti_internal.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp",
+           "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_jvp_edge_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
 # -packed-fp32-ops off: v_pk_{fma,mul,add}_f32 do NOT run next to another wave's matrix instructions on gfx950 (a wave of them and a
 # wave of 16x16x32 fp16 MFMAs on one SIMD take the SUM of their times; scalar v_fma_f32, conversions and transcendentals overlap:
 # tools/micro/coexec_classes.hip, profiles/r03i_microbench_coexec.txt), and register pairs cost the message kernels registers (pair
@@ -22,7 +26,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Xclang", "-tar
 # kernel into lanes of a VGPR, and that build faults on the device in its first launch (HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION,
 # profiles/r02h_f256_one_chain_fault.txt); the same source with the lane spills switched off allocates them to registers (no scratch) and
 # passes every stage at 1.6e-6 (profiles/r03e_f256_one_chain_no_lane_spill.txt).  DESIGN.md 3.4.
-EXTRA_FLAGS = {"painn_edge_nb8.hip": ["-mllvm", "-amdgpu-spill-sgpr-to-vgpr=0"]}
+EXTRA_FLAGS = {"painn_edge_nb8.hip": ["-mllvm", "-amdgpu-spill-sgpr-to-vgpr=0"], "painn_edge_mask_nb8.hip": ["-mllvm", "-amdgpu-spill-sgpr-to-vgpr=0"]}
 
 
 def hipcc() -> str:

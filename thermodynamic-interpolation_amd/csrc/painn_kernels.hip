@@ -25,6 +25,16 @@ hipError_t launch_edge_nb4(bool, bool, int, const EdgeParams&, hipStream_t); hip
 hipError_t configure_pair_nb1(); hipError_t configure_pair_nb2(); hipError_t configure_pair_nb4();
 hipError_t launch_pair_nb1(bool, bool, int, const EdgeParams&, hipStream_t); hipError_t launch_pair_nb2(bool, bool, int, const EdgeParams&, hipStream_t);
 hipError_t launch_pair_nb4(bool, bool, int, const EdgeParams&, hipStream_t);
+// their masked twins (per-molecule edge sets, ti_painn_set_edge_mask): painn_edge_mask_nb*.hip, painn_pair_mask_nb*.hip
+hipError_t configure_edge_mask_nb1(); hipError_t configure_edge_mask_nb2(); hipError_t configure_edge_mask_nb4(); hipError_t configure_edge_mask_nb8();
+hipError_t launch_edge_mask_nb1(bool, bool, int, const EdgeParams&, hipStream_t);
+hipError_t launch_edge_mask_nb2(bool, bool, int, const EdgeParams&, hipStream_t);
+hipError_t launch_edge_mask_nb4(bool, bool, int, const EdgeParams&, hipStream_t);
+hipError_t launch_edge_mask_nb8(bool, bool, int, const EdgeParams&, hipStream_t);
+hipError_t configure_pair_mask_nb1(); hipError_t configure_pair_mask_nb2(); hipError_t configure_pair_mask_nb4();
+hipError_t launch_pair_mask_nb1(bool, bool, int, const EdgeParams&, hipStream_t);
+hipError_t launch_pair_mask_nb2(bool, bool, int, const EdgeParams&, hipStream_t);
+hipError_t launch_pair_mask_nb4(bool, bool, int, const EdgeParams&, hipStream_t);
 
 // ================================================================================================== update kernel
 // v <- v + dv  with  dv = dvacc + cacc x v   (the cross product with v[dst] factors out of the edge sum),
@@ -465,6 +475,8 @@ static hipError_t configure_nb()
     }
     if ((e = (NB == 1 ? configure_edge_nb1() : NB == 2 ? configure_edge_nb2() : NB == 4 ? configure_edge_nb4() : configure_edge_nb8())) != hipSuccess) return e;
     if ((e = (NB == 1 ? configure_pair_nb1() : NB == 2 ? configure_pair_nb2() : NB == 4 ? configure_pair_nb4() : hipSuccess)) != hipSuccess) return e;
+    if ((e = (NB == 1 ? configure_edge_mask_nb1() : NB == 2 ? configure_edge_mask_nb2() : NB == 4 ? configure_edge_mask_nb4() : configure_edge_mask_nb8())) != hipSuccess) return e;
+    if ((e = (NB == 1 ? configure_pair_mask_nb1() : NB == 2 ? configure_pair_mask_nb2() : NB == 4 ? configure_pair_mask_nb4() : hipSuccess)) != hipSuccess) return e;
     const size_t bu = update_lds_bytes(NB, false), bh = update_lds_bytes(NB, true);
     if ((e = set_lds(painn_update_kernel<2 * NB, true, 0>, bu)) != hipSuccess) return e;
     if ((e = set_lds(painn_update_kernel<2 * NB, false, 0>, bu)) != hipSuccess) return e;
@@ -529,8 +541,15 @@ hipError_t launch_embed(int NBv, int nseg, int prec, const EmbedParams& p, hipSt
     return hipGetLastError();
 }
 
-hipError_t launch_edge(int NBv, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
+hipError_t launch_edge(int NBv, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked)
 {
+    if (masked) switch (NBv) {
+        case 1: return launch_edge_mask_nb1(first, last, prec, p, st);
+        case 2: return launch_edge_mask_nb2(first, last, prec, p, st);
+        case 4: return launch_edge_mask_nb4(first, last, prec, p, st);
+        case 8: return launch_edge_mask_nb8(first, last, prec, p, st);
+        default: return hipErrorInvalidValue;
+    }
     switch (NBv) {
         case 1: return launch_edge_nb1(first, last, prec, p, st);
         case 2: return launch_edge_nb2(first, last, prec, p, st);
@@ -571,8 +590,14 @@ hipError_t launch_pair_reduce(const PairReduceParams& p, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_pair(int NBv, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
+hipError_t launch_pair(int NBv, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked)
 {
+    if (masked) switch (NBv) {
+        case 1: return launch_pair_mask_nb1(first, last, prec, p, st);
+        case 2: return launch_pair_mask_nb2(first, last, prec, p, st);
+        case 4: return launch_pair_mask_nb4(first, last, prec, p, st);
+        default: return hipErrorInvalidValue;
+    }
     switch (NBv) {
         case 1: return launch_pair_nb1(first, last, prec, p, st);
         case 2: return launch_pair_nb2(first, last, prec, p, st);

@@ -23,6 +23,7 @@ static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };      // -> TI_E_UNSUPPORTED (guarded)
 #define HIP_CHECK(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
     throw HipError(std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
 
@@ -167,6 +168,7 @@ struct ti_handle {
     struct Tpl {
         int G = 1, P = 1, nblk = 0;
         DevBuf<uint32_t> rows; DevBuf<int32_t> slotnode;
+        std::vector<uint32_t> rows_h;             // host copy of `rows` (masked_rows)
         std::vector<int> part_of, part_start, part_len;     // per sorted edge: its part; per part: first sorted edge, edges
         std::vector<int> pos;                     // row of (molecule-in-group m, sorted edge k) inside its part: pos[m * part_len + (k - part_start)]
         int max_slots = 0;                        // most destination atoms in any row block (<= EDGE_MAX_SLOTS)
@@ -181,6 +183,11 @@ struct ti_handle {
     // every atom has incoming edges: the edge kernels' first touch of an accumulator replaces its contents (ti_internal.hpp
     // SLOT_FIRST_TOUCH) and nothing zeroes the accumulators between layers or calls; otherwise the update kernel zeroes them as before
     bool first_touch = false;
+    // per-molecule edge sets (ti_painn_set_edge_mask): [emask_B][A] words, in force for calls over emask_B molecules (0: no mask);
+    // emask_sym: every molecule's set is symmetric over the template (the pair layout is eligible).  mrows[t]: the row words of
+    // template t per (group, part) of those molecules with the absent edges switched off (masked_rows), built on first use.
+    std::vector<uint32_t> emask; long long emask_B = 0; bool emask_sym = true;
+    DevBuf<uint32_t> mrows[3]; bool mrows_ok[3] = {false, false, false};
     struct { const uint32_t* p = nullptr; } rows; struct { const int32_t* p = nullptr; } slotnode;
     DevBuf<int32_t> atom_ids;
     std::vector<int> perm;        // sorted row -> original edge index
@@ -323,7 +330,7 @@ void build_templates(ti_handle* h, const int32_t* src, const int32_t* dst, const
         std::vector<uint32_t> rw((size_t)std::max(T.nblk, 1) * RB); std::vector<int32_t> sn(rw.size());
         T.max_slots = fill_part(h, src, dst, etype, bestG, 0, E, T.nblk, T.pos, rw.data(), sn.data());
         if (T.nblk == 0) { rw[0] = (uint32_t)63 << 18; sn[0] = -1; }
-        T.rows.upload(rw); T.slotnode.upload(sn);
+        T.rows.upload(rw); T.slotnode.upload(sn); T.rows_h = rw;
     }
     // ---- latency template: one molecule per group, its destination atoms cut into P ranges of near-equal row count; the
     // largest P <= 8 whose padding waste stays <= 15 % (parts need whole row blocks).  Built only if it offers more waves.
@@ -363,7 +370,7 @@ void build_templates(ti_handle* h, const int32_t* src, const int32_t* dst, const
                 T.max_slots = std::max(T.max_slots, fill_part(h, src, dst, etype, 1, best_cut[q], best_cut[q + 1], best_nblk, pos,
                                                               rw.data() + (size_t)q * best_nblk * RB, sn.data() + (size_t)q * best_nblk * RB));
             }
-            T.rows.upload(rw); T.slotnode.upload(sn);
+            T.rows.upload(rw); T.slotnode.upload(sn); T.rows_h = rw;
             h->n_tpl = 2;
         }
     }
@@ -378,11 +385,22 @@ static bool build_pair_template(ti_handle* h, const int32_t* src, const int32_t*
     if (!ti::build_pair_template(h->d.n_atoms, h->d.n_edges, src, dst, etype, pt, h->first_touch && !pair_uses_partials())) return false;
     ti_handle::Tpl& T = h->tpl[2];
     T.G = pt.G; T.P = 1; T.nblk = pt.nblk; T.max_slots = 4;
-    T.rows.upload(pt.rows); T.slotnode.upload(pt.slotnode);
+    T.rows.upload(pt.rows); T.slotnode.upload(pt.slotnode); T.rows_h = pt.rows;
     h->pair_pos = pt.pair_pos; h->pair_fill = pt.fill;
     h->pair_plist.upload(pt.plist); h->pair_kmax = pt.kmax;
     return true;
 }
+
+// The layout the handle is pinned to (ti_painn_set_template, or TI_TEMPLATE in the environment), TI_TEMPLATE_AUTO if none.
+int pinned_template(const ti_handle* h)
+{
+    int want = h->pinned_tpl;
+    if (const char* e = std::getenv("TI_TEMPLATE"))
+        want = std::strcmp(e, "latency") == 0 ? 1 : std::strcmp(e, "throughput") == 0 ? 0 : std::strcmp(e, "pair") == 0 ? 2 : want;
+    return want;
+}
+// an edge mask is in force whose molecules' sets are not all symmetric: the pair rows (one w factor for both directions) cannot take it
+bool mask_blocks_pair(const ti_handle* h) { return h->emask_B > 0 && !h->emask_sym; }
 
 // Template for a call over B molecules: the latency template while the throughput one would leave SIMDs without a wave
 // (fewer groups than the 1024 SIMDs of the chip); TI_TEMPLATE=throughput|latency pins it (tests, reproducibility across shards).
@@ -390,7 +408,7 @@ int template_for(const ti_handle* h, long long B, bool allow_pair = true)
 {
     int dir_pick = 0;                        // among the directed layouts: latency while the throughput one would leave SIMDs idle
     if (h->n_tpl > 1) dir_pick = (B + h->tpl[0].G - 1) / h->tpl[0].G < 1024 ? 1 : 0;
-    const bool pair_ok = h->has_pair && allow_pair;
+    const bool pair_ok = h->has_pair && allow_pair && !mask_blocks_pair(h);
     // pair-major rows once they fill the chip (one wave per group of G molecules) and cost less than the directed rows: a pair block
     // runs 84 chunk products for 16 pairs where a directed block runs 56 for 16 edges, at half the weight-chunk visits per edge
     int pick = dir_pick;
@@ -398,9 +416,7 @@ int template_for(const ti_handle* h, long long B, bool allow_pair = true)
         const ti_handle::Tpl &T = h->tpl[2], &D = h->tpl[0];
         if ((B + T.G - 1) / T.G >= 1024 && 1.5 * T.nblk / T.G <= (double)D.nblk / D.G) pick = 2;
     }
-    int want = h->pinned_tpl;
-    if (const char* e = std::getenv("TI_TEMPLATE"))
-        want = std::strcmp(e, "latency") == 0 ? 1 : std::strcmp(e, "throughput") == 0 ? 0 : std::strcmp(e, "pair") == 0 ? 2 : want;
+    const int want = pinned_template(h);
     if (want == TI_TEMPLATE_THROUGHPUT) pick = 0;
     else if (want == TI_TEMPLATE_LATENCY) pick = h->n_tpl > 1 ? 1 : 0;
     else if (want == TI_TEMPLATE_PAIR) pick = pair_ok ? 2 : dir_pick;
@@ -410,10 +426,49 @@ int template_for(const ti_handle* h, long long B, bool allow_pair = true)
 // allow_pair = false: the divergence / tangent entry points (their kernels walk directed rows)
 void select_template(ti_handle* h, long long B, bool allow_pair = true)
 {
+    if (h->emask_B > 0 && B != h->emask_B)
+        throw std::invalid_argument("the edge mask in force is for " + std::to_string(h->emask_B) + " molecules, the call has " + std::to_string(B));
+    if (allow_pair && h->has_pair && mask_blocks_pair(h) && pinned_template(h) == TI_TEMPLATE_PAIR)
+        throw Unsupported("the pair layout is pinned, and the edge mask in force is not symmetric for every molecule");
     const int pick = template_for(h, B, allow_pair);
     const ti_handle::Tpl& T = h->tpl[pick];
     h->active = pick; h->G = T.G; h->parts = T.P; h->nblk = T.nblk; h->rows.p = T.rows.p; h->slotnode.p = T.slotnode.p;
     h->max_slots = T.max_slots;
+}
+
+// Row words of template t for the emask_B molecules of the edge mask, per (group, part) -- [groups][P][nblk * 16] -- with every edge
+// absent from its molecule switched off: slot 63 in directed rows (weight 0 in the per-atom sums, like padding), the valid bit cleared
+// in pair rows (w factor 0).  The masked twins of the message kernels read these instead of the template's shared rows.
+const uint32_t* masked_rows(ti_handle* h, int t)
+{
+    if (h->mrows_ok[t]) return h->mrows[t].p;
+    const ti_handle::Tpl& T = h->tpl[t];
+    const long long B = h->emask_B, groups = (B + T.G - 1) / T.G;
+    const int A = h->d.n_atoms;
+    const size_t per = (size_t)T.nblk * ti::EDGE_ROWS_PER_BLOCK;
+    std::vector<uint32_t> out((size_t)groups * T.P * per);
+    const uint32_t* m = h->emask.data();
+    for (long long g = 0; g < groups; ++g)
+        for (int part = 0; part < T.P; ++part) {
+            const uint32_t* src = T.rows_h.data() + (size_t)part * per;
+            uint32_t* dst = out.data() + ((size_t)g * T.P + part) * per;
+            for (size_t i = 0; i < per; ++i) {
+                uint32_t w = src[i];
+                if (w & 1u) {
+                    if (t == 2) {
+                        const long long mol = g * T.G + ti::prow_molI(w);
+                        if (mol < B && !((m[mol * A + ti::prow_atomJ(w)] >> ti::prow_atomI(w)) & 1u)) w &= ~1u;
+                    } else {
+                        const long long mol = g * T.G + ti::row_mol(w);
+                        if (mol < B && !((m[mol * A + ti::row_dst(w)] >> ti::row_src(w)) & 1u)) w |= 63u << 18;
+                    }
+                }
+                dst[i] = w;
+            }
+        }
+    h->mrows[t].upload(out);
+    h->mrows_ok[t] = true;
+    return h->mrows[t].p;
 }
 
 // row of (molecule m, sorted edge k) in the e / te layout of the active template
@@ -658,14 +713,20 @@ struct JvpRun {            // one tangent pass riding on a drift evaluation
 // one drift evaluation, everything on h->stream; x_dev / out_dev are device pointers [B*A*3].  With `jr` the tangent
 // kernels run in lock step: each reads the primal state its layer's primal kernel is about to overwrite.
 // tv (device, [B], may be NULL): one time per molecule instead of t (the embed kernel's per-molecule instantiation).
+// b0: the call's first molecule of this batch (the divergence passes run the call in chunks): the edge mask rows it starts at.
 void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, float* out_dev,
-                     const JvpRun* jr = nullptr, const float* tv = nullptr)
+                     const JvpRun* jr = nullptr, const float* tv = nullptr, long long b0 = 0)
 {
     const int A = h->d.n_atoms, F = h->d.n_features, L = h->d.n_layers, NB = h->NB;
     const long long N = B * A, groups = (B + h->G - 1) / h->G * h->parts;         // edge-kernel waves: (molecule group, part)
     hipStream_t st = h->stream;
     const bool split = h->d.precision == TI_PREC_F16X2;
     const int prec = h->d.precision;
+    const uint32_t* mrows = nullptr;          // edge mask in force: the masked twins of the message kernels, on per-group row words
+    if (h->emask_B > 0) {
+        if (b0 % h->G) throw std::invalid_argument("an edge mask needs whole molecule groups per tangent pass (raise TI_JVP_WS_GB)");
+        mrows = masked_rows(h, h->active) + (size_t)(b0 / h->G) * h->parts * h->nblk * ti::EDGE_ROWS_PER_BLOCK;
+    }
     if (jr && prec == TI_PREC_F16) throw std::invalid_argument("the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)");
     if (jr && h->active == 2) throw std::logic_error("tangent passes walk directed edge rows (select_template(.., allow_pair = false))");
     const long long VB = jr ? jvp_virtual_molecules(h, B, jr->D) : 0, VN = VB * A, vgroups = VB / h->G * h->parts;
@@ -722,8 +783,9 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
             p.x = x_dev; p.xdot = jr->xdot; p.P = h->P.p; p.v = h->v.p; p.e = h->e.p; p.wq = reinterpret_cast<const float4*>(h->wq.p);
             p.st = reinterpret_cast<const float4*>(h->phist.p); p.tP = h->tP.p; p.tv = h->tv.p;
             p.te = h->te.p; p.tdsacc = h->tdsacc.p; p.tdvacc = h->tdvacc.p; p.tcacc = h->tcacc.p;
+            if (mrows) p.rows = mrows;
             Timed tm(h, TI_KERNEL_PAINN_JVP_EDGE);
-            HIP_CHECK(launch_jvp_edge(NB, split, p, st));
+            HIP_CHECK(launch_jvp_edge(NB, split, p, st, mrows != nullptr));
         }
         if (h->nblk > 0) {
             EdgeParams p{};
@@ -736,6 +798,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
                 p.stream = h->S(h->st_edge1[l]); p.nch = h->st_edge1[l].nch; p.vecs = h->edge_vecs1.p + (size_t)l * 21 * F;
                 for (int i = 0; i < 6; ++i) p.wscale[i] = h->edge_scale[(size_t)l * 6 + i];
             }
+            if (mrows) p.rows = mrows;
             Timed tm(h, TI_KERNEL_PAINN_EDGE);
 #ifdef TI_STAMPS      // diagnostic build only: stamps of layer 2's launch, printed to stderr
             static DevBuf<unsigned long long> stamp_buf;
@@ -761,7 +824,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
 #endif
             if (h->active == 2) {
                 p.part = h->part.p;
-                HIP_CHECK(launch_pair(NB, l == 0, l == L - 1, prec, p, st));
+                HIP_CHECK(launch_pair(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr));
 #ifdef TI_STAMPS
                 dump_stamps();
 #endif
@@ -772,7 +835,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
                 HIP_CHECK(launch_pair_reduce(r, st));
                 }
             } else {
-                HIP_CHECK(launch_edge(NB, l == 0, l == L - 1, prec, p, st));
+                HIP_CHECK(launch_edge(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr));
 #ifdef TI_STAMPS
                 dump_stamps();
 #endif
@@ -835,7 +898,7 @@ void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float*
         ensure_jvp_ws(h, bc, D);
         JvpRun jr{D, nullptr, h->tout.p};
         painn_drift_dev(h, x_dev + (size_t)b0 * A * 3, t, cond_dev ? cond_dev + (size_t)b0 * A * h->ncond : nullptr, bc,
-                        out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr);
+                        out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr, b0);
         HIP_CHECK(launch_div_reduce(h->tout.p, bc, D, h->G, div_dev + b0, h->stream));
     }
     h->last_B = std::min(chunk, B);
@@ -863,7 +926,7 @@ void painn_drift_div_est_dev(ti_handle* h, const float* x_dev, float t, const fl
         const float* eps = h->probes.p + (size_t)b0 * k * A * 3;
         JvpRun jr{k, eps, h->tout.p};
         painn_drift_dev(h, x_dev + (size_t)b0 * A * 3, t, cond_dev ? cond_dev + (size_t)b0 * A * h->ncond : nullptr, bc,
-                        out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr);
+                        out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr, b0);
         HIP_CHECK(launch_hutch_reduce(h->tout.p, eps, bc, k, A, h->G, est_dev + b0, h->stream));
     }
     h->last_B = std::min(chunk, B);
@@ -1301,6 +1364,7 @@ int guarded(Fn&& fn)
 {
     try { return fn(); }
     catch (const HipError& e) { return fail(TI_E_HIP, e.what()); }
+    catch (const Unsupported& e) { return fail(TI_E_UNSUPPORTED, e.what()); }
     catch (const std::bad_alloc&) { return fail(TI_E_ALLOC, "host allocation failed"); }
     catch (const std::exception& e) { return fail(TI_E_ARG, e.what()); }
 }
@@ -2013,7 +2077,44 @@ int ti_painn_set_template(ti_handle* h, int which)
 int ti_painn_template_for(ti_handle* h, int64_t B)
 {
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (h->has_pair && mask_blocks_pair(h) && pinned_template(h) == TI_TEMPLATE_PAIR)
+        return fail(TI_E_UNSUPPORTED, "the pair layout is pinned, and the edge mask in force is not symmetric for every molecule");
     return template_for(h, B);
+}
+
+int ti_painn_set_edge_mask(ti_handle* h, const uint32_t* mask, int64_t B, int mem)
+{
+    // the arguments first, then the handle: each refusal has its own message, checkable without a device
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (mask && B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (!mask) {
+        h->emask_B = 0; h->emask_sym = true; h->emask.clear();
+        for (int t = 0; t < 3; ++t) { h->mrows_ok[t] = false; h->mrows[t].release(); }
+        return TI_OK;
+    }
+    return guarded([&]() -> int {
+        set_device(h);
+        const int A = h->d.n_atoms;
+        std::vector<uint32_t> m((size_t)B * A);
+        if (mem == TI_MEM_DEVICE) HIP_CHECK(hipMemcpy(m.data(), mask, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        else std::memcpy(m.data(), mask, m.size() * sizeof(uint32_t));
+        // symmetric over the template: for every template edge s -> d whose reverse is one too, both bits agree in every molecule
+        std::vector<uint32_t> in_tpl(A, 0);          // bit s of in_tpl[d]: s -> d is a template edge
+        for (size_t k = 0; k < h->esrc.size(); ++k) in_tpl[h->edst[k]] |= 1u << h->esrc[k];
+        bool sym = true;
+        for (long long b = 0; b < B && sym; ++b)
+            for (int d = 0; d < A && sym; ++d)
+                for (int s2 = 0; s2 < A; ++s2) {
+                    if (!((in_tpl[d] >> s2) & 1u) || !((in_tpl[s2] >> d) & 1u)) continue;
+                    if (((m[(size_t)b * A + d] >> s2) & 1u) != ((m[(size_t)b * A + s2] >> d) & 1u)) { sym = false; break; }
+                }
+        if (h->emask_B == B && m == h->emask) return TI_OK;            // the same mask again (a mirror class sets it before every call)
+        HIP_CHECK(hipStreamSynchronize(h->stream));                   // no launch in flight still reads the row words about to be replaced
+        h->emask.swap(m); h->emask_B = B; h->emask_sym = sym;
+        for (int t = 0; t < 3; ++t) h->mrows_ok[t] = false;
+        return TI_OK;
+    });
 }
 
 int ti_profile_enable(ti_handle* h, int on)

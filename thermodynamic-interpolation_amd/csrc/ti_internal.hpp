@@ -120,10 +120,12 @@ struct ReadoutParams {
 // launchers (painn_kernels.hip).  F = 32*NB; return hipError_t of the launch.
 // prec = TI_PREC_* of include/ti_hip.h; with TI_PREC_F16 the state tensors s, P, v, e behind the float* fields are fp16
 hipError_t launch_embed(int NB, int nseg, int prec, const EmbedParams& p, hipStream_t st);
-hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
+// masked: the masked twins of the message kernels (per-molecule edge sets, ti_painn_set_edge_mask); p.rows then holds row words per
+// (group, part) instead of the template's (ti_api.hip: masked_rows)
+hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false);
 bool edge_uses_one_chain(int NB, int prec);      // message kernel on the one-accumulator split format (painn_edge_kernel.hpp: edge_one_chain)
 // pair-major message kernel (painn_pair_kernel.hpp): same EdgeParams, rows / slotnode of the pair template, same weight stream
-hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
+hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false);
 bool pair_kernel_exists(int NB, int prec);
 bool pair_uses_partials();          // the pair kernel writes per-(block, slot) partial sums that launch_pair_reduce adds up (else: atomics, first touch)
 hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st);
@@ -176,7 +178,7 @@ struct JvpReadoutParams {
     float* tout;                            // [virtual nodes][3]
 };
 hipError_t launch_jvp_filter(int NB, bool split, const JvpFilterParams& p, hipStream_t st);
-hipError_t launch_jvp_edge(int NB, bool split, const JvpEdgeParams& p, hipStream_t st);
+hipError_t launch_jvp_edge(int NB, bool split, const JvpEdgeParams& p, hipStream_t st, bool masked = false);
 hipError_t launch_jvp_node(int NB, bool split, const JvpNodeParams& p, hipStream_t st);
 hipError_t launch_jvp_update(int NB, bool split, const JvpUpdateParams& p, hipStream_t st);
 hipError_t launch_jvp_readout(int NB, bool split, const JvpReadoutParams& p, hipStream_t st);

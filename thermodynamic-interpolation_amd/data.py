@@ -92,17 +92,25 @@ def _remove_com(x):
 
 def make_batch(variant: str, x0, template, *, T0=None, T1=None, T=None, atom_ids=None, latent_z=None, latent_dlogp=None):
     """Attribute bag with the fields the reference batches carry (numpy arrays): x0/x [N,3] (COM removed per molecule,
-    mdqm9_ambient.py:161), atoms | atom_number [N], T0/T1 | T [N], edge_index [2,E], edge_type [E], batch [N]."""
+    mdqm9_ambient.py:161), atoms | atom_number [N], T0/T1 | T [N], edge_index [2,E], edge_type [E], batch [N].
+    `template`: one (src, dst, type) for every molecule, or a list of B of them (each molecule its own graph)."""
     x0 = _remove_com(np.asarray(x0, np.float32))
     B, A, _ = x0.shape
-    src, dst, et = template
     ids = np.arange(A, dtype=np.int64) if atom_ids is None else np.asarray(atom_ids, np.int64)
-    off = (np.arange(B, dtype=np.int64) * A)[:, None]
     b = types.SimpleNamespace()
     b.x0 = x0.reshape(B * A, 3)
     b.x = b.x0.copy()
-    b.edge_index = np.stack([(src[None, :] + off).ravel(), (dst[None, :] + off).ravel()]).astype(np.int64)
-    b.edge_type = np.tile(np.asarray(et, np.int64), B)
+    if isinstance(template, list):
+        if len(template) != B:
+            raise ValueError(f"{len(template)} per-molecule templates for {B} molecules")
+        b.edge_index = np.concatenate([np.stack([np.asarray(s_, np.int64), np.asarray(d_, np.int64)]) + m * A
+                                       for m, (s_, d_, _) in enumerate(template)], axis=1)
+        b.edge_type = np.concatenate([np.asarray(t_, np.int64) for _, _, t_ in template])
+    else:
+        src, dst, et = template
+        off = (np.arange(B, dtype=np.int64) * A)[:, None]
+        b.edge_index = np.stack([(src[None, :] + off).ravel(), (dst[None, :] + off).ravel()]).astype(np.int64)
+        b.edge_type = np.tile(np.asarray(et, np.int64), B)
     b.batch = np.repeat(np.arange(B, dtype=np.int64), A)
     if variant == "ambient":
         b.atoms = np.tile(ids, B)
@@ -151,7 +159,11 @@ class MDQM9SamplerDataset:
     """Ambient sampling dataset (MDQM9SamplerDataset, mdqm9_ambient.py:110-170): frames at T0 as starting points, to be carried to
     T1.  Bonds come from a mol block (`sdf_path/sdf_filename`, record = molecule id) or are passed explicitly.  With
     `use_latent_trajs` the starting points are the end states of the latent sampler (latent -> ambient chaining): its first frames
-    and dlogps travel along as `latent_z` / `latent_dlogp`."""
+    and dlogps travel along as `latent_z` / `latent_dlogp`.
+
+    With a finite `cutoff` every sample gets its own graph, built like the reference's (mdqm9_ambient.py:160-170): the radius
+    graph of the centred, scaled coordinates its x0 holds, plus the bonds, coalesced with max.  A batch whose graphs all equal
+    frame 0's is the batch a single template gives."""
 
     def __init__(self, traj_filename, traj_path, split="test", T0=300, T1=400, scale=False, cutoff=np.inf, sdf_path=None,
                  sdf_filename="mdqm9.sdf", bond_index=None, bonds=None, use_latent_trajs=False, n_latent_samples=10_000,
@@ -167,7 +179,21 @@ class MDQM9SamplerDataset:
         if bond_index is None and sdf_path is not None:
             bond_index, bonds = bonds_from_molblock(read_sdf_record(os.path.join(sdf_path, sdf_filename), int(traj_filename.split(".")[0])))
         self.template = build_edge_template(self.data[0], cutoff, bond_index, bonds)
+        self.cutoff, self.bond_index, self.bonds = float(cutoff), bond_index, bonds
         self.atom_ids = np.arange(self.data.shape[1])                        # distinguish=True (mdqm9_ambient.py:219-220)
+
+    def graph_of(self, i):
+        """(src, dst, type) of sample i: the graph of the coordinates its x0 holds (centred float32, as make_batch stores them)."""
+        return build_edge_template(_remove_com(np.asarray(self.data[i], np.float32)), self.cutoff, self.bond_index, self.bonds)
+
+    def _templates(self, idx):
+        """The one template of the batch `idx` when every sample has frame 0's graph (always for an infinite cutoff), else one per sample."""
+        if not np.isfinite(self.cutoff):
+            return self.template
+        graphs = [self.graph_of(i) for i in idx]
+        if all(all(np.array_equal(a, b) for a, b in zip(g, self.template)) for g in graphs):
+            return self.template
+        return graphs
 
     def __len__(self):
         return len(self.data)
@@ -178,7 +204,7 @@ class MDQM9SamplerDataset:
             idx = order[i:i + batch_size]
             if drop_last and len(idx) < batch_size:
                 return
-            yield make_batch("ambient", self.data[idx], self.template, T0=self.T0, T1=self.T1, atom_ids=self.atom_ids,
+            yield make_batch("ambient", self.data[idx], self._templates(idx), T0=self.T0, T1=self.T1, atom_ids=self.atom_ids,
                              latent_z=self.data0[idx], latent_dlogp=self.dlogp0[idx])
 
 

@@ -180,7 +180,42 @@ class PainnEngine(_Engine):
 
     def template_for(self, B: int) -> str:
         """The layout a drift / rollout call over B molecules would use."""
-        return {0: "throughput", 1: "latency", 2: "pair"}[_lib.lib().ti_painn_template_for(self.h, int(B))]
+        rc = _lib.lib().ti_painn_template_for(self.h, int(B))
+        if rc < 0:
+            _lib.check(rc)
+        return {0: "throughput", 1: "latency", 2: "pair"}[rc]
+
+    def set_edge_mask(self, mask):
+        """Per-molecule edge sets over this engine's template: mask [B, A] uint32 (or int32, same bits), bit s of mask[b, d] set when
+        the edge s -> d exists in molecule b; template edges whose bit is clear contribute nothing to molecule b.  It stays in force
+        for every later call over B molecules (another B is refused) until set_edge_mask(None).  A numpy array is copied; a CUDA
+        tensor is read on the device."""
+        L = _lib.lib()
+        if mask is None:
+            _lib.check(L.ti_painn_set_edge_mask(self.h, None, 0, _lib.MEM_HOST))
+            return
+        if hasattr(mask, "data_ptr"):                                 # torch.Tensor without importing torch
+            if str(mask.dtype) not in ("torch.int32", "torch.uint32"):
+                raise TypeError(f"mask must be int32 or uint32, got {mask.dtype}")
+            if len(mask.shape) != 2 or int(mask.shape[1]) != self.A:
+                raise ValueError(f"mask must be [B,{self.A}], got {tuple(mask.shape)}")
+            B = int(mask.shape[0])
+            if mask.is_cuda:
+                if mask.device.index != self.device:
+                    raise ValueError(f"mask lives on cuda:{mask.device.index} but this engine was created on device {self.device}")
+                mask = mask.contiguous()
+                import torch
+                torch.cuda.current_stream(self.device).synchronize()
+                _lib.check(L.ti_painn_set_edge_mask(self.h, C.c_void_p(mask.data_ptr()), B, _lib.MEM_DEVICE))
+                return
+            mask = mask.numpy()
+        m = np.asarray(mask)
+        if m.dtype not in (np.uint32, np.int32):
+            raise TypeError(f"mask must be uint32 or int32, got {m.dtype}")
+        if m.ndim != 2 or m.shape[1] != self.A:
+            raise ValueError(f"mask must be [B,{self.A}], got {m.shape}")
+        m = np.ascontiguousarray(m.view(np.uint32))
+        _lib.check(L.ti_painn_set_edge_mask(self.h, C.c_void_p(m.ctypes.data), int(m.shape[0]), _lib.MEM_HOST))
 
     def _check_x(self, x, name="x"):
         if x is None or len(x.shape) != 3 or tuple(x.shape[1:]) != (self.A, 3):

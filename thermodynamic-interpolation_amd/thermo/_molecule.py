@@ -5,7 +5,8 @@ The reference batch is a PyG ``Batch``; here any object with the attributes the 
     x0 / x [N,3] f32, atoms | atom_number [N] i64, T0,T1 | T [N], edge_index [2,E] i64 (edge_index[0] = source),
     edge_type [E] i64, batch [N] i64.
 Every batch is homogeneous (one species per run); ``split_batch`` verifies that and extracts the
-per-molecule template the C ABI takes.
+per-molecule template the C ABI takes.  ``split_graph_batch`` also takes batches whose molecules have different edge sets (the
+reference's finite-cutoff radius graphs): a superset template plus a per-molecule edge mask.
 """
 from __future__ import annotations
 
@@ -70,6 +71,62 @@ def split_batch(batch, atom_key: str):
     return B, A, src[0].astype(np.int32), dst[0].astype(np.int32), ty[0].astype(np.int32), at[0].astype(np.int32)
 
 
+def split_graph_batch(batch, atom_key: str):
+    """-> (B, A, edge_src[E], edge_dst[E], edge_type[E], atom_ids[A], mask [B, A] uint32 | None).
+
+    A batch whose molecules all have the same graph (same edges in the same order) gives split_batch's template and mask None.
+    Otherwise the template is the superset: the complete directed graph on A atoms sorted by (src, dst), each pair with the type
+    the batch shows (type 0 where no molecule has the pair; it is masked everywhere), and bit s of mask[b, d] is set when molecule b
+    has the edge s -> d.  Bonds are in every molecule, so the superset is the same for every batch of a species.  Edges are assigned
+    to molecules through batch.batch[edge_index[0]]; molecules may hold different numbers of edges.  Raises ValueError when the
+    molecules differ in atom ids or give one pair different types."""
+    try:
+        return (*split_batch(batch, atom_key), None)
+    except ValueError:
+        pass
+    bidx = C.to_numpy(batch.batch, np.int64)
+    N = bidx.size
+    if N == 0:
+        raise ValueError("empty batch")
+    B = int(bidx.max()) + 1
+    if N % B or not np.array_equal(bidx, np.repeat(np.arange(B), N // B)):
+        raise ValueError("batch.batch must be molecule-major with equally sized molecules (one species per run)")
+    A = N // B
+    if A > 32:
+        raise ValueError(f"per-molecule edge sets need A <= 32 atoms, got {A}")
+    ei = C.to_numpy(batch.edge_index, np.int64)
+    et = C.to_numpy(batch.edge_type, np.int64)
+    if ei.ndim != 2 or ei.shape[0] != 2 or ei.shape[1] != et.size:
+        raise ValueError("edge_index must be [2, E] and edge_type [E]")
+    at = C.to_numpy(getattr(batch, atom_key), np.int64).reshape(B, A)
+    if (at != at[0]).any():
+        raise ValueError("molecules of the batch differ in atom ids; the sampler handles one species per batch")
+    if ei.size and (ei.min() < 0 or ei.max() >= N):
+        raise ValueError("edge_index points outside the batch")
+    mol = bidx[ei[0]]
+    if (bidx[ei[1]] != mol).any():
+        raise ValueError("edges cross molecule boundaries")
+    src, dst = ei[0] - mol * A, ei[1] - mol * A
+    if (src == dst).any():
+        raise ValueError("self loops are not supported in batches with per-molecule edge sets")
+    if et.size and (et.min() < 0 or et.max() > 3):
+        raise ValueError("edge types must be in 0..3 (the edge-type embedding has 4 rows, cpainn.py:70)")
+    # every pair's type, from one counting pass per type (vectorised: a batch holds up to ~2e7 edges)
+    pair = src * A + dst
+    seen = np.stack([np.bincount(pair[et == t], minlength=A * A) > 0 for t in range(4)])      # [type, pair]
+    clash = np.nonzero(seen.sum(axis=0) > 1)[0]
+    if clash.size:
+        raise ValueError(f"molecules of the batch differ in the type of the edge {clash[0] // A} -> {clash[0] % A}")
+    ty = np.where(seen.any(axis=0), seen.argmax(axis=0), 0).reshape(A, A)   # type 0 where no molecule has the pair
+    # bit s of mask[b, d]: a sum of distinct powers of two below 2^32, exact in the float64 weights of bincount
+    mask = np.bincount(mol * A + dst, weights=np.ldexp(1.0, src), minlength=B * A).astype(np.uint32).reshape(B, A)
+    if int(np.unpackbits(mask.view(np.uint8)).sum()) != src.size:
+        raise ValueError("a molecule of the batch holds an edge twice (coalesce the graph first)")
+    s_all, d_all = np.nonzero(~np.eye(A, dtype=bool))                   # (src, dst) order, no self loops
+    etype = ty[s_all, d_all]
+    return B, A, s_all.astype(np.int32), d_all.astype(np.int32), etype.astype(np.int32), at[0].astype(np.int32), mask
+
+
 class PaiNNShell:
     """Weights-only stand-in for the reference ``cPaiNN`` modules (subclasses fix the variant)."""
     VARIANT = _W.AMBIENT
@@ -122,6 +179,12 @@ class PaiNNShell:
                                                      temperatures=self.temperatures, device=self._device, precision=self.precision)
         return self._engines[key]
 
+    def engine_with_mask(self, A, src, dst, ety, ids, mask) -> _engine.PainnEngine:
+        """engine_for with a batch's per-molecule edge mask set (split_graph_batch; None clears it: a uniform batch)."""
+        eng = self.engine_for(A, src, dst, ety, ids)
+        eng.set_edge_mask(mask)
+        return eng
+
     def cond_of(self, batch, B, A, on_gpu=False):
         """[B, A, n_cond] float32 conditioning; a CUDA tensor when `on_gpu` (the batch lives on the GPU), else numpy."""
         if not self.COND_KEYS:
@@ -136,10 +199,10 @@ class PaiNNShell:
     def forward(self, batch):
         """Evaluates the drift at batch.x, time batch.t (per node: one value for the call, or one value per molecule) and writes
         batch.output [N,3] like the reference."""
-        B, A, src, dst, ety, ids = split_batch(batch, self.ATOM_KEY)
+        B, A, src, dst, ety, ids, mask = split_graph_batch(batch, self.ATOM_KEY)
         x = C.as_f32(batch.x, (B, A, 3))                  # a CUDA batch is evaluated in place, no host round trip
         t = molecule_times(batch.t, B, A, x)
-        out = self.engine_for(A, src, dst, ety, ids).drift(x, t, self.cond_of(batch, B, A, C.is_cuda(x)))
+        out = self.engine_with_mask(A, src, dst, ety, ids, mask).drift(x, t, self.cond_of(batch, B, A, C.is_cuda(x)))
         batch.output = C.like(out.reshape(B * A, 3), batch.x)
         return batch
 
@@ -157,11 +220,11 @@ class ODEWrapperBase:
 
     def _eval(self, batch, x, t, with_div):
         """t: one float, or batch.t-like per-node times (one value per molecule)."""
-        B, A, src, dst, ety, ids = split_batch(batch, self.b.ATOM_KEY)
+        B, A, src, dst, ety, ids, mask = split_graph_batch(batch, self.b.ATOM_KEY)
         xs = C.as_f32(x, (B, A, 3))
         if not isinstance(t, float):
             t = molecule_times(t, B, A, xs)
-        eng = self.b.engine_for(A, src, dst, ety, ids)
+        eng = self.b.engine_with_mask(A, src, dst, ety, ids, mask)
         cond = self.b.cond_of(batch, B, A, C.is_cuda(xs))
         if with_div:
             out, div = eng.drift_div(xs, t, cond)
@@ -235,12 +298,12 @@ class MoleculeIntegratorBase:
         self.n_steps_per_molecule = eng.step_counts(B) if self.step_control == "trajectory" else None
 
     def _rollout(self, batch, traj_offset=0):
-        B, A, src, dst, ety, ids = split_batch(batch, self.b.ATOM_KEY)
+        B, A, src, dst, ety, ids, mask = split_graph_batch(batch, self.b.ATOM_KEY)
         x0 = C.as_f32(batch.x0, (B, A, 3))               # CUDA batches stay in HBM: data_ptr() in, CUDA tensors out
         gpu = C.is_cuda(x0)
         # without dlogp the reference always integrates on linspace(start, end) (integrators.py:54-55), reverse_ode or not
         grid = _engine.time_grid(self.start, self.end, self.n_step)
-        eng = self.b.engine_for(A, src, dst, ety, ids)
+        eng = self.b.engine_with_mask(A, src, dst, ety, ids, mask)
         if self.return_dlogp:
             if self.reverse_ode:
                 grid = _engine.time_grid(self.end, self.start, self.n_step)
