@@ -39,6 +39,7 @@ hipError_t launch_pair_mask_nb4(bool, bool, int, const EdgeParams&, hipStream_t)
 // ================================================================================================== update kernel
 // v <- v + dv  with  dv = dvacc + cacc x v   (the cross product with v[dst] factors out of the edge sum),
 // s <- s + dsacc, then Update.forward (cpainn.py:345-376); finally P for the next layer's message block.
+// FOLDED: the message kernel has already added the cross term to dvacc (pair_folds_cross, ti_internal.hpp): dv = dvacc, cacc unused.
 // 16 atoms per wave on the r16 primitives (f32 or split-fp16 matrix path), 4 waves per workgroup, 2 workgroups per CU.
 // The three spatial components share every visit of the U / V weight chunks.
 struct UV {                                         // per-layer vector block in LDS, x F floats
@@ -50,7 +51,7 @@ struct UV {                                         // per-layer vector block in
 // (the fp16 storage mode's hi-only chunks are half the size: four per barrier at F = 128, same LDS bytes)
 __host__ __device__ constexpr int update_superchunk(int NB, bool H16) { return H16 && NB == 4 ? 4 : 2; }
 __host__ __device__ constexpr int update_chunk4(int NB, bool H16) { return (H16 ? 128 : 256) * NB; }
-template <int NBK, bool HAS_NEXT, int PREC>
+template <int NBK, bool HAS_NEXT, int PREC, bool FOLDED = false>
 __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_kernel(const UpdateParams p)
 {
     constexpr bool H16 = PREC == 2;                 // s, v, P are fp16 in HBM (the accumulators stay fp32), hi-only weight chunks
@@ -87,13 +88,14 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_kernel(c
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     vv[c] = p.first_layer ? f32x4{0, 0, 0, 0} : r16::load_state<H16>(p.v, vo + c * F, nb, q);
-                    kk[c] = p.first_layer ? f32x4{0, 0, 0, 0} : r16::load_block(cb + c * F, nb, q);
+                    kk[c] = p.first_layer || FOLDED ? f32x4{0, 0, 0, 0} : r16::load_block(cb + c * F, nb, q);
                 }
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
                     const f32x4 dd = r16::load_block(db + c * F, nb, q);
-                    t[c].b[nb] = (vv[c] + dd) + (kk[c1] * vv[c2] - kk[c2] * vv[c1]);      // torch.cross(edge_dir, v[dst]) summed over edges
+                    if (FOLDED) t[c].b[nb] = vv[c] + dd;
+                    else t[c].b[nb] = (vv[c] + dd) + (kk[c1] * vv[c2] - kk[c2] * vv[c1]);      // torch.cross(edge_dir, v[dst]) summed over edges
                     if (ok) r16::store_block(db + c * F, nb, q, t[c].b[nb]);
                 }
             }
@@ -229,8 +231,10 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_kernel(c
                 if (p.zero_acc) {
                     r16::store_block(db + c * F, 2 * ch, q, f32x4{0, 0, 0, 0});
                     r16::store_block(db + c * F, 2 * ch + 1, q, f32x4{0, 0, 0, 0});
-                    r16::store_block(cb + c * F, 2 * ch, q, f32x4{0, 0, 0, 0});
-                    r16::store_block(cb + c * F, 2 * ch + 1, q, f32x4{0, 0, 0, 0});
+                    if (!FOLDED) {
+                        r16::store_block(cb + c * F, 2 * ch, q, f32x4{0, 0, 0, 0});
+                        r16::store_block(cb + c * F, 2 * ch + 1, q, f32x4{0, 0, 0, 0});
+                    }
                 }
             }
             pipe.release();
@@ -482,6 +486,8 @@ static hipError_t configure_nb()
     if ((e = set_lds(painn_update_kernel<2 * NB, false, 0>, bu)) != hipSuccess) return e;
     if ((e = set_lds(painn_update_kernel<2 * NB, true, 1>, bu)) != hipSuccess) return e;
     if ((e = set_lds(painn_update_kernel<2 * NB, false, 1>, bu)) != hipSuccess) return e;
+    if ((e = set_lds(painn_update_kernel<2 * NB, true, 1, true>, bu)) != hipSuccess) return e;
+    if ((e = set_lds(painn_update_kernel<2 * NB, false, 1, true>, bu)) != hipSuccess) return e;
     if ((e = set_lds(painn_update_kernel<2 * NB, true, 2>, bh)) != hipSuccess) return e;
     if ((e = set_lds(painn_update_kernel<2 * NB, false, 2>, bh)) != hipSuccess) return e;
 
@@ -607,8 +613,9 @@ hipError_t launch_pair(int NBv, bool first, bool last, int prec, const EdgeParam
 }
 bool pair_kernel_exists(int NB, int prec) { return NB <= 4 && (prec == TI_PREC_F32 || prec == TI_PREC_F16X2); }
 
-hipError_t launch_update(int NBv, bool has_next, int prec, const UpdateParams& p, hipStream_t st)
+hipError_t launch_update(int NBv, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded)
 {
+    if (folded && !pair_folds_cross(prec)) return hipErrorInvalidValue;
     TI_DISPATCH_NB(NBv, {
         (void)WAVES;
         const dim3 g((unsigned)((p.N + 63) / 64));                 // 4 waves x 16 atoms per workgroup
@@ -616,6 +623,9 @@ hipError_t launch_update(int NBv, bool has_next, int prec, const UpdateParams& p
         if (prec == 2) {
             if (has_next) hipLaunchKernelGGL((painn_update_kernel<2 * NB, true, 2>), g, dim3(256), l, st, p);
             else hipLaunchKernelGGL((painn_update_kernel<2 * NB, false, 2>), g, dim3(256), l, st, p);
+        } else if (prec == 1 && folded) {
+            if (has_next) hipLaunchKernelGGL((painn_update_kernel<2 * NB, true, 1, true>), g, dim3(256), l, st, p);
+            else hipLaunchKernelGGL((painn_update_kernel<2 * NB, false, 1, true>), g, dim3(256), l, st, p);
         } else if (prec == 1) {
             if (has_next) hipLaunchKernelGGL((painn_update_kernel<2 * NB, true, 1>), g, dim3(256), l, st, p);
             else hipLaunchKernelGGL((painn_update_kernel<2 * NB, false, 1>), g, dim3(256), l, st, p);

@@ -41,7 +41,14 @@ __host__ __device__ constexpr bool pair_build_exists(int NB, int WAVES, int PREC
 #endif
 __host__ __device__ constexpr int pair_superchunk() { return 2; }
 __host__ __device__ constexpr int pair_ring(int WAVES) { return WAVES == 8 ? TI_PAIR_NBUF : 2; }
-static size_t pair_lds_bytes(int NB, int WAVES) { return (size_t)pair_ring(WAVES) * pair_superchunk() * edge_chunk4(NB, false) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4; }
+// + the builds that fold the cross term (pair_folds_cross): per wave, the 12 dv sums of every lane parked across the cross-gate products.
+// At F = 128 that costs the 4-wave build its second workgroup per CU (87.5 KB); it runs below 2048 groups, where a launch has at most
+// two workgroups per CU to place.
+static size_t pair_lds_bytes(int NB, int WAVES, int PREC)
+{
+    return (size_t)pair_ring(WAVES) * pair_superchunk() * edge_chunk4(NB, false) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4 +
+           (pair_folds_cross(PREC) ? (size_t)WAVES * 12 * 64 * 4 : 0);
+}
 
 template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(const EdgeParams p)
@@ -65,7 +72,7 @@ static hipError_t configure_pair_prec()
 {
     if constexpr (!pair_build_exists(NB, EW, PREC)) return hipSuccess;
     else if constexpr (MASK) {
-    const size_t be = pair_lds_bytes(NB, EW);
+    const size_t be = pair_lds_bytes(NB, EW, PREC);
     hipError_t e;
     if ((e = set_lds_edge(painn_pair_mask_kernel<2 * NB, true, false, PREC, EW>, be)) != hipSuccess) return e;
     if ((e = set_lds_edge(painn_pair_mask_kernel<2 * NB, false, false, PREC, EW>, be)) != hipSuccess) return e;
@@ -73,7 +80,7 @@ static hipError_t configure_pair_prec()
     if ((e = set_lds_edge(painn_pair_mask_kernel<2 * NB, true, true, PREC, EW>, be)) != hipSuccess) return e;
     return hipSuccess;
     } else {
-    const size_t be = pair_lds_bytes(NB, EW);
+    const size_t be = pair_lds_bytes(NB, EW, PREC);
     hipError_t e;
     if ((e = set_lds_edge(painn_pair_kernel<2 * NB, true, false, PREC, EW>, be)) != hipSuccess) return e;
     if ((e = set_lds_edge(painn_pair_kernel<2 * NB, false, false, PREC, EW>, be)) != hipSuccess) return e;
@@ -96,7 +103,7 @@ static void launch_pair_p(bool first, bool last, const EdgeParams& p, hipStream_
 {
     if constexpr (pair_build_exists(NB, EW, PREC)) {
     const dim3 g((unsigned)((p.n_groups + EW - 1) / EW)), t(64 * EW);          // one wave = one group of G molecules
-    const size_t l = pair_lds_bytes(NB, EW);
+    const size_t l = pair_lds_bytes(NB, EW, PREC);
     if constexpr (MASK) {
     if (first && last) hipLaunchKernelGGL((painn_pair_mask_kernel<2 * NB, true, true, PREC, EW>), g, t, l, st, p);
     else if (first) hipLaunchKernelGGL((painn_pair_mask_kernel<2 * NB, true, false, PREC, EW>), g, t, l, st, p);

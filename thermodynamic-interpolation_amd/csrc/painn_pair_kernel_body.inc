@@ -225,6 +225,11 @@
         // at 11 - 13 k cycles against 3 - 5 k for the others).  The f32 path is bound by its matrix instructions and short of registers:
         // it keeps the gathers next to their use.
         constexpr bool GATHER_EARLY = PREC != 0;
+        // the cross-gate slice folded into dv (pair_folds_cross, ti_internal.hpp): the split path, which holds v[dst] of both directions
+        // in registers; layer 0 has no such slice.  The f32 path sums cg * dir into cacc for the update kernel to cross.
+        constexpr bool FOLD = pair_folds_cross(PREC) && !FIRST;
+        f32x4* const zpark = reinterpret_cast<f32x4*>(vec + EV::COUNT * F) + wave * 3 * 64 + lane;     // FOLD: [3][64 lanes] f32x4 per wave
+        static_assert(!FOLD || GATHER_EARLY, "the fold crosses with the v[dst] rows that the early gathers hold");
         const long long nJq = snJ >= 0 ? node_of(slot_mol(snJ), snJ & 255) : nIq;   // J slot q's atom: lane row q fetches it for all four
         const float wrow = (meta & 1u) ? inv_out : 0.0f;                 // the same row factor in the row layout (lane (j, q): row j)
 
@@ -268,7 +273,7 @@
                 }
             }
             TI_STAMP();
-            {   // equivariant message: sum_e (sed * dir_e + gates * v[src_e]) -> dvacc ; sum_e cg * dir_e -> cacc
+            {   // equivariant message: sum_e (sed * dir_e + gates * v[src_e]) -> dvacc ; sum_e cg * dir_e -> cacc, or folded into dvacc
                 f32x4 sA0, sA1, sB0, sB1, gA0 = {0, 0, 0, 0}, gA1 = {0, 0, 0, 0}, gB0 = {0, 0, 0, 0}, gB1 = {0, 0, 0, 0};
                 out3(1, nbo, sA0, sA1, sB0, sB1);
                 float vI[3][2], vJ[3][2];                // v of I[q] (source of direction A for the lane's four rows) and of J[q]
@@ -318,11 +323,54 @@
                     zB[c][0] = sumB(v0); zB[c][1] = sumB(v1);
                     if (!GATHER_EARLY) putB(zB[c][0], zB[c][1], (1 + c) * F + fo);
                 }
+                TI_STAMP();
+                if constexpr (FOLD) {
+                    // cross term folded: every row a lane sums for one slot has the same destination, so the slot's block sum of
+                    // cg * dir is crossed with v[dst] here -- sum_rows cg (dir x v[dst]) = (sum_rows cg dir) x v[dst] -- and added to
+                    // the dv sums before their atomics.  v[dst]: J[q] for direction A (vJ, lane row q holds J slot q after sumA), I[q]
+                    // for direction B (vI).  12 FMAs per lane instead of 12 accumulator atomics and the update kernel's cacc read.
+                    // The 12 dv sums wait in LDS while the products run (held in registers, they made the middle and the last layer
+                    // spill 45 registers); edge_dir is read from LDS again after them for the same reason.
+                    zpark[0] = f32x4{zA[0][0], zA[0][1], zA[1][0], zA[1][1]};
+                    zpark[64] = f32x4{zA[2][0], zA[2][1], zB[0][0], zB[0][1]};
+                    zpark[128] = f32x4{zB[1][0], zB[1][1], zB[2][0], zB[2][1]};
+                    f32x4 cA0, cA1, cB0, cB1;
+                    out3(4, nbo, cA0, cA1, cB0, cB1);
+                    f32x4 dc[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) dc[r] = *reinterpret_cast<const f32x4*>(scratch + (4 * q + r) * 4);
+                    {
+                        const f32x4 z0 = zpark[0], z1 = zpark[64], z2 = zpark[128];
+                        zA[0][0] = z0[0]; zA[0][1] = z0[1]; zA[1][0] = z0[2]; zA[1][1] = z0[3];
+                        zA[2][0] = z1[0]; zA[2][1] = z1[1]; zB[0][0] = z1[2]; zB[0][1] = z1[3];
+                        zB[1][0] = z2[0]; zB[1][1] = z2[1]; zB[2][0] = z2[2]; zB[2][1] = z2[3];
+                    }
+                    float kA[3][2], kB[3][2];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        f32x4 a0, a1, b0, b1;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            a0[r] = cA0[r] * dc[r][c]; a1[r] = cA1[r] * dc[r][c];
+                            b0[r] = -(cB0[r] * dc[r][c]); b1[r] = -(cB1[r] * dc[r][c]);
+                        }
+                        kA[c][0] = sumA(a0); kA[c][1] = sumA(a1);
+                        kB[c][0] = sumB(b0); kB[c][1] = sumB(b1);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {     // torch.cross(edge_dir, v[dst]) summed over the slot's rows of this block
+                            zA[c][h] += kA[c1][h] * vJ[c2][h] - kA[c2][h] * vJ[c1][h];
+                            zB[c][h] += kB[c1][h] * vI[c2][h] - kB[c2][h] * vI[c1][h];
+                        }
+                    }
+                }
                 if (GATHER_EARLY)
 #pragma unroll
                     for (int c = 0; c < 3; ++c) { putA(zA[c][0], zA[c][1], (1 + c) * F + fo); putB(zB[c][0], zB[c][1], (1 + c) * F + fo); }
-                TI_STAMP();
-                if (!FIRST) {
+                if (!FIRST && !FOLD) {
                     f32x4 cA0, cA1, cB0, cB1;
                     out3(4, nbo, cA0, cA1, cB0, cB1);
 #pragma unroll

@@ -831,7 +831,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
                 if (pair_uses_partials()) {
                 PairReduceParams r{};
                 r.part = h->part.p; r.plist = h->pair_plist.p; r.kmax = h->pair_kmax; r.G = h->G; r.A = A; r.F = F; r.nblk = h->nblk;
-                r.has_c = l > 0; r.B = B; r.dsacc = h->dsacc.p; r.dvacc = h->dvacc.p; r.cacc = h->cacc.p;
+                r.has_c = l > 0 && !pair_folds_cross(prec); r.B = B; r.dsacc = h->dsacc.p; r.dvacc = h->dvacc.p; r.cacc = h->cacc.p;
                 HIP_CHECK(launch_pair_reduce(r, st));
                 }
             } else {
@@ -865,8 +865,11 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
             p.stream = h->S(h->st_update[l]); p.nch = h->st_update[l].nch; p.vecs = h->upd_vecs.p + (size_t)l * 10 * F;
             p.N = N; p.s = h->s.p; p.v = h->v.p; p.dsacc = h->dsacc.p; p.dvacc = h->dvacc.p; p.cacc = h->cacc.p; p.P = h->P.p;
             p.first_layer = l == 0; p.zero_acc = !ft;
+            // after a pair launch that folded the cross term into dvacc, the update kernel that reads neither cacc nor its cross product
+            // (cacc is then not written in this layer; the tangent passes, which read it, run on directed launches only)
+            const bool folded = h->nblk > 0 && h->active == 2 && l > 0 && pair_folds_cross(prec);
             Timed tm(h, TI_KERNEL_PAINN_UPDATE);
-            HIP_CHECK(launch_update(NB, l + 1 < L, prec, p, st));
+            HIP_CHECK(launch_update(NB, l + 1 < L, prec, p, st, folded));
         }
         if (h->tap == 2 + 2 * l) return;
     }

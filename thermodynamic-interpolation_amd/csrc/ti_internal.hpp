@@ -73,7 +73,8 @@ struct EdgeParams {
     const float* v;                         // [B*A][3][F]
     float* dsacc;                           // [B*A][F]   += sum ds   (added to s by the update kernel)
     float* dvacc;                           // [B*A][3][F] += sum (sed*dir + gates*v[src])
-    float* cacc;                            // [B*A][3][F] += sum cg*dir   (crossed with v[dst] in the update kernel)
+    float* cacc;                            // [B*A][3][F] += sum cg*dir   (crossed with v[dst] in the update kernel; not written by a
+                                            //   pair launch that folds the cross term, pair_folds_cross)
     float* e;                               // [n_groups*nblk*16][F]
     float* enc;                             // [n_groups*nblk][operand registers][64] parked encoding operand of every row block (layer 0 writes, the others read)
     float wscale[6];                        // TI_PREC_F16X2: powers of two the host scaled w.W0, w.W1, phi.W0(e), phi.W1, phi.W2, w.W2 by (else 1)
@@ -128,7 +129,13 @@ bool edge_uses_one_chain(int NB, int prec);      // message kernel on the one-ac
 hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false);
 bool pair_kernel_exists(int NB, int prec);
 bool pair_uses_partials();          // the pair kernel writes per-(block, slot) partial sums that launch_pair_reduce adds up (else: atomics, first touch)
-hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st);
+// the pair kernel at this precision adds (sum cg*dir) x v[dst] to dvacc itself, per row block and slot (painn_pair_kernel_body.inc,
+// FOLD), and leaves cacc alone: the update kernel after it must be the folded one (launch_update(.., folded = true)).  The split path
+// only: it holds v[dst] of both directions in registers.  Its 4- and 8-wave builds both fold, so that a slice of groups evaluated
+// alone stays bit for bit what it is in a larger batch.  The f32 path keeps the cross-gate sums in cacc.
+__host__ __device__ constexpr bool pair_folds_cross(int prec) { return prec == TI_PREC_F16X2; }
+// folded: the message launch before it already added the cross term to dvacc (pair_folds_cross); cacc is then neither read nor reset
+hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded = false);
 hipError_t launch_readout(int NB, int prec, const ReadoutParams& p, hipStream_t st);
 hipError_t configure_painn_kernels(int NB);     // dynamic-LDS attributes
 
