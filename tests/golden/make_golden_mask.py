@@ -3,7 +3,10 @@
 on a batch whose molecules have different radius graphs (a finite `cutoff`).
 
 Run in the build container only, like make_golden.py (whose shims and helpers this imports):
-    python tests/golden/make_golden_mask.py [--out DIR]
+    python tests/golden/make_golden_mask.py [--out DIR] [--f256-only]
+
+--out DIR writes the fixtures into DIR instead of tests/golden (make_golden.py reads the flag); --f256-only writes only the two
+fixtures at the mdqm9 configs' width.
 
 Each molecule goes through the reference's per-sample processing (mdqm9_ambient.py:160-170): COM removal, then its own
 `AddRadiusGraph(cutoff)`, `AddBondGraph()`, `Coalesce()` (mdqm9/thermo/utils.py), and the molecules are collated like a DataLoader
@@ -11,7 +14,10 @@ batch (edge indices offset by the molecule's first node).  torch_geometric is ab
 functions those transforms call are restated from their documented semantics -- `radius_graph(x, r, batch)` (ordered pairs j -> i,
 i != j, same molecule, |x_i - x_j| <= r; the cutoff is placed in a gap of the distances, so < and <= agree) and
 `utils.coalesce(edge_index, edge_attr, reduce="max")` (sort by (row, col), merge duplicates with max).
-Cases: ambient (F = 32, L = 2, A = 9, B = 4) and latent (F = 32, L = 2, A = 7, B = 3); the cutoff keeps 40-80 % of the pairs, bonds are
+Cases: ambient (F = 32, L = 2, A = 9, B = 4) and latent (F = 32, L = 2, A = 7, B = 3); with --f256-only, ambient (F = 256, L = 5, A = 25,
+B = 3) and latent (F = 256, L = 5, A = 18, B = 3, coordinates with sigma 0.5 as in make_golden.py's latent_f256: at unit variance the
+reference's own fp32 drift misses the 1e-5 bar).  The F = 256 divergence is taken on one thread: on several, the reference's autograd
+divergence changes in its last bits from run to run (make_golden.py --f256-only does the same).  The cutoff keeps 40-80 % of the pairs, bonds are
 a chain with types 1-3 and the last atom has no bond; in molecule 0 that atom sits far from the others and has no incoming edge.
 Stored: the collated graph, the drift of the reference ODEWrapper at three times, the reference compute_divergence (autograd), and a
 hand-rolled fixed-step Euler trajectory over the wrapper on the reference grid.
@@ -88,8 +94,8 @@ def reference_graphs(x, cutoff, bond_index, bonds):
     return torch.cat(ei, dim=1), torch.cat(et)
 
 
-def mask_case(name, variant, F, L, A, B, temp_length, *, seed, keep=0.45, traj_steps=4):
-    x = syn.molecule_coords(B, A, seed=seed)
+def mask_case(name, variant, F, L, A, B, temp_length, *, seed, keep=0.45, traj_steps=4, sigma=0.3, div_threads=None):
+    x = syn.molecule_coords(B, A, seed=seed, sigma=sigma)
     x[0, A - 1] += 25.0                                      # molecule 0: the bond-free last atom far away -> no incoming edge
     x = (x - x.mean(axis=1, keepdims=True)).astype(np.float32)
     cutoff = gap_cutoff(x, keep)
@@ -128,7 +134,10 @@ def mask_case(name, variant, F, L, A, B, temp_length, *, seed, keep=0.45, traj_s
     tdiv = float(ts[1])
     b2 = Ode.reset_batch(batch.clone(), batch.x0.clone(), torch.tensor(tdiv))
     out["div_t"] = np.float32(tdiv)
+    nt = torch.get_num_threads()
+    torch.set_num_threads(div_threads or nt)
     out["div"] = Ode.compute_divergence(model, b2).detach().numpy().copy()          # ambient: * 1e-2 like the reference
+    torch.set_num_threads(nt)
     grid, path = mg.rollout_reference(ode, batch, traj_steps, "euler")
     out["traj_grid"], out["traj_euler"] = grid, path.reshape(traj_steps, B, A, 3)
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
@@ -138,5 +147,9 @@ def mask_case(name, variant, F, L, A, B, temp_length, *, seed, keep=0.45, traj_s
 
 if __name__ == "__main__":
     torch.set_num_threads(8)
+    if "--f256-only" in sys.argv:       # the mdqm9 configs' width: n_features 256, score_layers 5
+        mask_case("mask_ambient_f256", W.AMBIENT, 256, 5, 25, 3, 100, seed=52, div_threads=1)
+        mask_case("mask_latent_f256", W.LATENT_MULTI, 256, 5, 18, 3, 75, seed=53, sigma=0.5, div_threads=1)
+        sys.exit(0)
     mask_case("mask_ambient", W.AMBIENT, 32, 2, 9, 4, 100, seed=50)
     mask_case("mask_latent", W.LATENT_MULTI, 32, 2, 7, 3, 75, seed=51)

@@ -243,7 +243,7 @@ def test_masked_f256_kernels_hold_no_sgpr_in_vgpr_lanes(code_objects):
 
 
 # ------------------------------------------------------------------------------------------------------------ reference graphs
-@pytest.mark.parametrize("name", ["mask_ambient", "mask_latent"])
+@pytest.mark.parametrize("name", ["mask_ambient", "mask_latent", "mask_ambient_f256", "mask_latent_f256"])
 def test_reference_graphs_of_the_golden_batch(name, tmp_path):
     """tests/golden/make_golden_mask.py ran the reference's per-sample AddRadiusGraph / AddBondGraph / Coalesce: the dataset's per-sample
     graphs and split_graph_batch's mask must reproduce them."""

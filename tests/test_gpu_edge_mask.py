@@ -35,7 +35,7 @@ def golden_batch(g, t):
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x2"])
-@pytest.mark.parametrize("name", ["mask_ambient", "mask_latent"])
+@pytest.mark.parametrize("name", ["mask_ambient", "mask_latent", "mask_ambient_f256", "mask_latent_f256"])
 def test_mirror_classes_against_the_reference_on_finite_cutoff_graphs(name, precision):
     """tests/golden/make_golden_mask.py: the reference's own graph construction (radius graph per sample, bonds, coalesce) and its
     cPaiNN / ODEWrapper on a batch whose molecules keep 40-80 % of their pairs, one with an atom without incoming edges."""

@@ -395,11 +395,13 @@ def test_edge_templates_agree(F, L, A, B, variant, precision, monkeypatch):
 @pytest.mark.parametrize("F", [32, 64])
 def test_wide_workgroups_at_small_feature_widths(F, monkeypatch):
     """Launches with >= 2048 molecule groups use the 8-wave edge kernels (painn_kernels.hip: launch_edge); the headline shape
-    covers F = 128 (race screen above), this covers the F = 32 / 64 builds, whose weight superchunks stay two chunks deep."""
+    covers F = 128 (race screen above), this covers the F = 32 / 64 builds, whose weight superchunks stay two chunks deep.
+    The wide build is the NS = 2 form only (painn_edge_kernel.hpp: launch_edge_nb), so the destination runs must be long: 25 atoms
+    (24 rows each, at most two destination atoms per 16-row block).  6 atoms (5-row runs, up to four per block) never reach it."""
     ti = pkg()
     syn, W = ti.synthetic, ti.weights
     monkeypatch.setenv("TI_TEMPLATE", "throughput")
-    L, A, B = 2, 6, 8 * 2048 + 5                       # E = 30 -> G = 8 molecules per group (240 rows, no padding): 2049 groups
+    L, A, B = 2, 25, 2 * 2048 + 1                      # E = 600 -> G = 2 molecules per group (75 full blocks): 2049 groups
     src, dst, et = syn.fully_connected_template(A)
     flat = W.flatten_state_dict(syn.painn_state_dict(0, F, L, 25, seed=F), W.painn_param_spec(0, F, L, 25))
     x, cond = syn.molecule_coords(B, A, seed=1), syn.ambient_cond(B, A)

@@ -286,3 +286,38 @@ def test_div_range_fixtures_reach_their_magnitudes(name):
         assert least < 1e-7, (name, mx)
     else:
         assert float(mx["e"].max()) < 1e-7, (name, mx)
+
+
+# ------------------------------------------------------------------------------------------------------------ finite-cutoff graphs
+MASK_CASES = ["mask_ambient", "mask_latent", "mask_ambient_f256", "mask_latent_f256"]
+
+
+@pytest.mark.parametrize("name", MASK_CASES)
+def test_painn_oracle_on_each_molecules_own_graph_matches_the_reference(name):
+    """tests/golden/make_golden_mask.py: the reference's collated finite-cutoff batch (every molecule its own radius + bond graph).  The
+    oracle, given each molecule's own edges, reproduces the reference's drift at every time and its compute_divergence (ambient: times
+    ODEWrapper.DIV_SCALE) -- the per-molecule reference the masked GPU kernels are measured against."""
+    ti = pkg()
+    g = load_golden(name)
+    variant, F, L, A, B = (int(g[k]) for k in ("variant", "F", "L", "A", "B"))
+    flat = ti.weights.flatten_state_dict(ti.synthetic.painn_state_dict(variant, F, L, 25, int(g["seed"])),
+                                         ti.weights.painn_param_spec(variant, F, L, 25))
+    ei, et = g["edge_index"], g["edge_type"]
+    mol = g["batch"][ei[0]]
+    scale = (ti.thermo.ambient if variant == 0 else ti.thermo.latent).ODEWrapper.DIV_SCALE
+    ref_div = g["div"].astype(np.float64) / scale
+    sizes = set()
+    for b in range(B):
+        own = mol == b
+        sizes.add(int(own.sum()))
+        o = oracle.PainnOracle(variant, F, L, A, ei[0][own] - b * A, ei[1][own] - b * A, et[own], g["atom_ids"][b * A:(b + 1) * A], flat,
+                               temp_length=float(g["temp_length"]), temperatures=g["temperatures"])
+        xb, cb = g["x"][b:b + 1], g["cond"][b:b + 1]
+        for i, t in enumerate(g["ts"]):
+            ref = g[f"drift_{i}"][b:b + 1]
+            e32, e64 = rel_l2(o.drift(xb, float(t), cb), ref), rel_l2(o.drift(xb, float(t), cb, precision=64), ref)
+            assert e64 < TOL_BAR, (name, b, i, e64)
+            assert close_f32(e32, e64), (name, b, i, e32, e64)
+        _, d = o.drift_div(xb, float(g["div_t"]), cb, precision=64)
+        assert abs(float(d[0]) - ref_div[b]) < DIV_ATOL * (abs(ref_div[b]) + 1.0), (name, b, float(d[0]), ref_div[b])
+    assert len(sizes) > 1                                   # the molecules really have different graphs
