@@ -272,6 +272,36 @@ int ti_painn_template_for(ti_handle* h, int64_t B);
  * TI_TEMPLATE_PAIR with an asymmetric mask in force returns TI_E_UNSUPPORTED.  A NULL or non-painn handle, B < 1 with a
  * non-NULL mask, or an unknown mem: TI_E_ARG before any device work.  An all-ones mask gives the unmasked results bit for bit. */
 int ti_painn_set_edge_mask(ti_handle* h, const uint32_t* mask, int64_t B, int mem);
+/* Mixed-species batches: per-molecule atom counts, edge sets and edge types over the handle's template (A = the largest molecule).
+ * n_atoms [B], each in 1..A: atoms a >= n_atoms[b] of molecule b are PAD atoms.  mask [B][A] as in ti_painn_set_edge_mask; NULL:
+ * every template edge between real atoms.  The library clears every bit that touches a pad atom itself.  pair_type [B][A][A]
+ * (bytes, 0..3): pair_type[(b*A + s)*A + d] is the type of the edge s -> d in molecule b; NULL: the template's types; entries of
+ * absent edges are ignored.  This call and ti_painn_set_edge_mask write the same per-molecule graph state and the later call
+ * replaces the earlier one completely (set_edge_mask: all n_atoms = A, template types); n_atoms == NULL clears the state.  `mem`
+ * says where all three arrays live.  TI_E_ARG before any device work: a NULL or non-painn handle, B < 1, a count outside 1..A, a
+ * type above 3 (host arrays; device arrays are checked after their copy), an unknown mem; a later call with another B: TI_E_ARG.
+ * The pair layout is eligible only while every molecule's mask AND types are symmetric (TI_E_UNSUPPORTED on a handle pinned to it
+ * otherwise, as for masks).
+ *   Pad atoms in every output: a pad atom's drift (and tangent) is written as exactly +0 by the library, its coordinates in every
+ *     out_path row are those of x0, it receives no EM noise, and with com_free_noise the centre of mass is taken over the
+ *     n_atoms[b] real atoms.
+ *   Independence from pad inputs: every result on real atoms (drift, JVP, exact and Hutchinson divergence, every rollout) is
+ *     bit-identical whatever finite coordinates, directions and cond values the pad atoms carry, coinciding ones included: the
+ *     kernels never see them.  The library evaluates the network on a copy in which pad atom a of molecule b sits at
+ *     x[b][0] + (100 (a - n_atoms[b] + 1), 0, 0) with cond 0 (and tangent direction 0), every row that touches it switched off.
+ *   Adaptive solvers: TI_SCHEME_DOPRI5 takes the error ratio and Hairer's initial step as the rms over the sum_b 3 n_atoms[b]
+ *     real entries (torchdiffeq's norm of the reference's flat [N,3] state); TI_SCHEME_DOPRI5_TRAJ takes trajectory b's rms over
+ *     its 3 n_atoms[b] entries (maxed with its dlogp entry, as before).  Its path, dlogp and step counts do not depend on what
+ *     the other molecules of the call are: they are bit for bit those of a batch of the same B that holds only its species, on the
+ *     same handle and pinned layout, with the molecule at the same index.  On TI_TEMPLATE_LATENCY (one molecule per row group) they
+ *     are also those of any smaller batch and any index.  TI_TEMPLATE_THROUGHPUT and TI_TEMPLATE_PAIR pack several molecules into
+ *     one row group and a molecule's per-atom sums follow its place in the group, as they do without masks: a batch that moves it
+ *     to another place in its group agrees to fp32 round-off only (1e-6 absolute on a path), mixed species or not.  The same holds
+ *     for the Hutchinson estimate below.
+ *   Hutchinson: real component (a, c) of trajectory id traj_offset + b draws N(probe_seed, id, p, 3a + c) as before (the probes it
+ *     would get alone); pad components are 0.  Exact divergence: the 3 n_atoms[b] real unit seeds are summed, pads are skipped.
+ *   With every n_atoms[b] == A and pair_type == NULL every entry point returns the bits ti_painn_set_edge_mask(mask) returns. */
+int ti_painn_set_molecules(ti_handle* h, const int32_t* n_atoms, const uint32_t* mask, const uint8_t* pair_type, int64_t B, int mem);
 /* Pre-size the HBM workspace for batches up to B trajectories (otherwise grown on demand). */
 int ti_reserve(ti_handle* h, int64_t B);
 /* Live kernel timing with HIP events on the handle's stream (bench.py roofline leg). */

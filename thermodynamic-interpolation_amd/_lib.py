@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "ti_painn_debug_tap", "ti_painn_debug_read", "ti_painn_debug_poison", "ti_selftest",
     "ti_painn_drift_tv", "ti_painn_drift_div_tv", "ti_adw_drift_tv", "ti_rollout_step_counts",
     "ti_painn_drift_div_est", "ti_painn_drift_div_est_tv", "ti_painn_rollout_dlogp_est",
-    "ti_adw_create_nd", "ti_painn_set_edge_mask",
+    "ti_adw_create_nd", "ti_painn_set_edge_mask", "ti_painn_set_molecules",
 ]
 
 
@@ -129,6 +129,7 @@ def lib():
     L.ti_painn_rollout_dlogp_est.argtypes = [vp, C.POINTER(RolloutDesc), C.c_int32, C.c_uint64, vp, vp, C.c_int64, C.c_float, C.c_float,
                                              C.c_int, vp, vp, C.POINTER(C.c_int64)]
     L.ti_painn_set_edge_mask.argtypes = [vp, vp, C.c_int64, C.c_int]
+    L.ti_painn_set_molecules.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int]
     _lib = L
     return L
 

@@ -373,6 +373,69 @@ __global__ void probe_kernel(float* __restrict__ eps, uint64_t seed, long long t
     eps[i] = ti_normal(seed, traj0 + b, pr, c) >= 0.0f ? 1.0f : -1.0f;
 }
 
+// ---- mixed-species batches (ti_painn_set_molecules): arrays of [mols][A][comps] floats; molecule i of the array has n_atoms[i / rep]
+// real atoms, the atoms behind them are pads
+__global__ void park_pads_kernel(float* __restrict__ dst, const float* __restrict__ src, const int32_t* __restrict__ n_atoms, long long mols,
+                                 int rep, int A, int comps, int park_coords)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= mols * A * comps) return;
+    const long long node = i / comps, mol = node / A;
+    const int c = (int)(i - node * comps), a = (int)(node - mol * A), n = n_atoms[mol / rep];
+    float v = src[i];
+    if (a >= n) {
+        v = 0.0f;
+        if (park_coords) v = __fadd_rn(src[mol * A * comps + c], c == 0 ? 100.0f * (float)(a - n + 1) : 0.0f);      // beside real atom 0
+    }
+    dst[i] = v;
+}
+__global__ void zero_pads_kernel(float* __restrict__ y, const int32_t* __restrict__ n_atoms, long long mols, int rep, int A, int comps)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= mols * A * comps) return;
+    const long long node = i / comps, mol = node / A;
+    if ((int)(node - mol * A) >= n_atoms[mol / rep]) y[i] = 0.0f;
+}
+__global__ void copy_pads_kernel(float* __restrict__ dst, const float* __restrict__ src, const int32_t* __restrict__ n_atoms, long long mols,
+                                 int A, int comps)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= mols * A * comps) return;
+    const long long node = i / comps, mol = node / A;
+    if ((int)(node - mol * A) >= n_atoms[mol]) dst[i] = src[i];
+}
+// noise_kernel over the 3 n_atoms[m] real components of molecule m (rows of [A][3]): the draws (seed, traj, step, 3a + c) a batch of
+// its species alone would make, the centre of mass over its real atoms, nothing on pads
+__global__ void noise_ragged_kernel(float* __restrict__ x, float sigma, uint64_t seed, long long traj0, int step, long long B, int A, int com_free,
+                                    const int32_t* __restrict__ n_atoms)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= B) return;
+    const int n = n_atoms[m], comps = 3 * n;
+    float com[3] = {0.f, 0.f, 0.f};
+    if (com_free) {
+        for (int c = 0; c < comps; ++c) com[c % 3] += ti_normal(seed, traj0 + m, step, c);
+        for (int k = 0; k < 3; ++k) com[k] = com[k] / (float)n;
+    }
+    for (int c = 0; c < comps; ++c) {
+        float z = ti_normal(seed, traj0 + m, step, c);
+        if (com_free) z -= com[c % 3];
+        x[m * 3 * A + c] = __fadd_rn(x[m * 3 * A + c], __fmul_rn(sigma, z));
+    }
+}
+// painn_div_reduce_kernel (painn_jvp_kernels.hip) over the real unit seeds: div[b] = sum_{d < 3 n_atoms[b]} tout[(b, d)][d], D = 3A
+__global__ void div_reduce_ragged_kernel(const float* __restrict__ tout, long long B, int D, int G, const int32_t* __restrict__ n_atoms,
+                                         float* __restrict__ div)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const long long pg = b / G, m = b - pg * G;
+    const int nd = 3 * n_atoms[b];
+    float acc = 0.f;
+    for (int d = 0; d < nd; ++d) acc += tout[(size_t)(((pg * D + d) * G + m)) * D + d];
+    div[b] = acc;
+}
+
 __global__ void scale_kernel(float* __restrict__ y, const float* __restrict__ x, float a, long long n)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -484,6 +547,36 @@ hipError_t launch_noise(float* x, float sigma, uint64_t seed, long long traj0, i
                         hipStream_t st)
 {
     if (B > 0) hipLaunchKernelGGL(noise_kernel, grid1(B, 128), dim3(128), 0, st, x, sigma, seed, traj0, step, B, comps, atoms_for_com);
+    return hipGetLastError();
+}
+hipError_t launch_park_pads(float* dst, const float* src, const int32_t* n_atoms, long long mols, int rep, int A, int comps, int park_coords,
+                            hipStream_t st)
+{
+    const long long n = mols * A * comps;
+    if (n > 0) hipLaunchKernelGGL(park_pads_kernel, grid1(n, 256), dim3(256), 0, st, dst, src, n_atoms, mols, rep, A, comps, park_coords);
+    return hipGetLastError();
+}
+hipError_t launch_zero_pads(float* y, const int32_t* n_atoms, long long mols, int rep, int A, int comps, hipStream_t st)
+{
+    const long long n = mols * A * comps;
+    if (n > 0) hipLaunchKernelGGL(zero_pads_kernel, grid1(n, 256), dim3(256), 0, st, y, n_atoms, mols, rep, A, comps);
+    return hipGetLastError();
+}
+hipError_t launch_copy_pads(float* dst, const float* src, const int32_t* n_atoms, long long mols, int A, int comps, hipStream_t st)
+{
+    const long long n = mols * A * comps;
+    if (n > 0) hipLaunchKernelGGL(copy_pads_kernel, grid1(n, 256), dim3(256), 0, st, dst, src, n_atoms, mols, A, comps);
+    return hipGetLastError();
+}
+hipError_t launch_noise_ragged(float* x, float sigma, uint64_t seed, long long traj0, int step, long long B, int A, int com,
+                               const int32_t* n_atoms, hipStream_t st)
+{
+    if (B > 0) hipLaunchKernelGGL(noise_ragged_kernel, grid1(B, 128), dim3(128), 0, st, x, sigma, seed, traj0, step, B, A, com, n_atoms);
+    return hipGetLastError();
+}
+hipError_t launch_div_reduce_ragged(const float* tout, long long B, int D, int G, const int32_t* n_atoms, float* div, hipStream_t st)
+{
+    if (B > 0) hipLaunchKernelGGL(div_reduce_ragged_kernel, grid1(B, 256), dim3(256), 0, st, tout, B, D, G, n_atoms, div);
     return hipGetLastError();
 }
 hipError_t launch_scale(float* y, const float* x, float a, long long n, hipStream_t st)

@@ -11,35 +11,9 @@
 // bits in any batch, permutation or shard.
 #include <climits>
 
-#include "ti_internal.hpp"
+#include "ode_device.hpp"
 
 namespace ti {
-
-namespace {
-
-constexpr int RED_BLOCK = 256;
-
-__device__ __forceinline__ float comb(const RkComb& c, long long i)
-{
-    float acc = c.c[0] * c.k[0][i];
-    for (int j = 1; j < c.nk; ++j) acc = fmaf(c.c[j], c.k[j][i], acc);
-    return acc;
-}
-
-// block sum in a fixed tree order; result valid in thread 0
-__device__ __forceinline__ double block_sum(double v)
-{
-    __shared__ double sm[RED_BLOCK];
-    sm[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = RED_BLOCK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sm[0];
-}
-
-}  // namespace
 
 // y = y0 + sum_j c_j k_j
 __global__ void rk_combo_kernel(float* __restrict__ y, const float* __restrict__ y0, RkComb c, long long n)
@@ -151,25 +125,6 @@ hipError_t launch_interp_eval(float* out, const float* coef, float x, long long 
 // ================================================================================================ per-trajectory dopri5
 namespace {
 
-constexpr int TRAJ_WAVES = 4;          // trajectories per 256-thread block (one wave each)
-struct Coef7 { float c[7]; };
-
-// sum_{j<nk} (c_j dt) k_j[i]: the coefficients scaled by the trajectory's fp32 step like comb() above (beta_ij * dt in fp32)
-__device__ __forceinline__ float comb_dt(float* const* k, const float* c, int nk, float dt, long long i)
-{
-    float acc = (c[0] * dt) * k[0][i];
-    for (int j = 1; j < nk; ++j) acc = fmaf(c[j] * dt, k[j][i], acc);
-    return acc;
-}
-
-// butterfly over the wave: fp addition commutes, so every lane ends with the same bits; the order is fixed
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // misc.py _mixed_norm of _rms_norm over the segments of trajectory b: max_s sqrt(sum_j term(s, i_j)^2 / m_s); a NaN propagates
 template <typename Term>
 __device__ double traj_norm(const TrajRkParams& p, long long b, int lane, Term term)
@@ -186,11 +141,6 @@ __device__ double traj_norm(const TrajRkParams& p, long long b, int lane, Term t
         best = (rms != rms || best != best) ? __longlong_as_double(0x7ff8000000000000LL) : fmax(best, rms);
     }
     return best;
-}
-
-__device__ __forceinline__ bool traj_wants_row(const TrajRkParams& p, int i)
-{
-    return p.save_every > 0 ? (i % p.save_every == 0 || i == p.n_grid - 1) : i == p.n_grid - 1;
 }
 
 }  // namespace

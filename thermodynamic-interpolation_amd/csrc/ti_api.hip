@@ -188,6 +188,12 @@ struct ti_handle {
     // template t per (group, part) of those molecules with the absent edges switched off (masked_rows), built on first use.
     std::vector<uint32_t> emask; long long emask_B = 0; bool emask_sym = true;
     DevBuf<uint32_t> mrows[3]; bool mrows_ok[3] = {false, false, false};
+    // mixed species (ti_painn_set_molecules), part of the same per-molecule graph state: natoms [emask_B] atom counts (empty: all A),
+    // ptype [emask_B][A][A] edge types (empty: the template's).  ragged: some molecule has pad atoms -- only then the drift runs on
+    // parked copies of x / cond / xdot (xpark, cpark, dpark), zeroes the pad rows of its outputs, and the integrators take their
+    // ragged twins; natoms_dev is the device copy of natoms the kernels read.
+    std::vector<int32_t> natoms; std::vector<uint8_t> ptype; bool ragged = false; long long n_real = 0;
+    DevBuf<int32_t> natoms_dev; DevBuf<float> xpark, cpark, dpark;
     struct { const uint32_t* p = nullptr; } rows; struct { const int32_t* p = nullptr; } slotnode;
     DevBuf<int32_t> atom_ids;
     std::vector<int> perm;        // sorted row -> original edge index
@@ -437,7 +443,7 @@ void select_template(ti_handle* h, long long B, bool allow_pair = true)
 }
 
 // Row words of template t for the emask_B molecules of the edge mask, per (group, part) -- [groups][P][nblk * 16] -- with every edge
-// absent from its molecule switched off: slot 63 in directed rows (weight 0 in the per-atom sums, like padding), the valid bit cleared
+// absent from its molecule (every edge of a pad atom among them: set_graph_state cleared their bits) switched off: slot 63 in directed rows (weight 0 in the per-atom sums, like padding), the valid bit cleared
 // in pair rows (w factor 0).  The masked twins of the message kernels read these instead of the template's shared rows.
 const uint32_t* masked_rows(ti_handle* h, int t)
 {
@@ -448,6 +454,7 @@ const uint32_t* masked_rows(ti_handle* h, int t)
     const size_t per = (size_t)T.nblk * ti::EDGE_ROWS_PER_BLOCK;
     std::vector<uint32_t> out((size_t)groups * T.P * per);
     const uint32_t* m = h->emask.data();
+    const uint8_t* pt = h->ptype.empty() ? nullptr : h->ptype.data();      // per-molecule edge types of the present rows (ti_painn_set_molecules)
     for (long long g = 0; g < groups; ++g)
         for (int part = 0; part < T.P; ++part) {
             const uint32_t* src = T.rows_h.data() + (size_t)part * per;
@@ -458,9 +465,11 @@ const uint32_t* masked_rows(ti_handle* h, int t)
                     if (t == 2) {
                         const long long mol = g * T.G + ti::prow_molI(w);
                         if (mol < B && !((m[mol * A + ti::prow_atomJ(w)] >> ti::prow_atomI(w)) & 1u)) w &= ~1u;
+                        else if (mol < B && pt) w = (w & ~(3u << 17)) | ((uint32_t)pt[((size_t)mol * A + ti::prow_atomI(w)) * A + ti::prow_atomJ(w)] << 17);
                     } else {
                         const long long mol = g * T.G + ti::row_mol(w);
                         if (mol < B && !((m[mol * A + ti::row_dst(w)] >> ti::row_src(w)) & 1u)) w |= 63u << 18;
+                        else if (mol < B && pt) w = (w & ~(3u << 16)) | ((uint32_t)pt[((size_t)mol * A + ti::row_src(w)) * A + ti::row_dst(w)] << 16);
                     }
                 }
                 dst[i] = w;
@@ -729,6 +738,26 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
     }
     if (jr && prec == TI_PREC_F16) throw std::invalid_argument("the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)");
     if (jr && h->active == 2) throw std::logic_error("tangent passes walk directed edge rows (select_template(.., allow_pair = false))");
+    // mixed species: the kernels below never see what the caller left in pad atoms.  They read copies in which every pad atom is
+    // parked beside its molecule's atom 0 (distinct, finite places: an off row's 0 * value stays 0) with cond 0 and direction 0.
+    const int32_t* nat = h->ragged ? h->natoms_dev.p + b0 : nullptr;
+    const float* xdot = jr ? jr->xdot : nullptr;
+    if (nat) {
+        const size_t n3 = (size_t)B * A * 3, nc = (size_t)B * A * h->ncond;
+        if (h->xpark.n < n3) h->xpark.alloc(n3);
+        HIP_CHECK(launch_park_pads(h->xpark.p, x_dev, nat, B, 1, A, 3, 1, st));
+        x_dev = h->xpark.p;
+        if (nc) {
+            if (h->cpark.n < nc) h->cpark.alloc(nc);
+            HIP_CHECK(launch_park_pads(h->cpark.p, cond_dev, nat, B, 1, A, h->ncond, 0, st));
+            cond_dev = h->cpark.p;
+        }
+        if (xdot) {
+            if (h->dpark.n < n3 * jr->D) h->dpark.alloc(n3 * jr->D);
+            HIP_CHECK(launch_park_pads(h->dpark.p, xdot, nat, B * jr->D, jr->D, A, 3, 0, st));
+            xdot = h->dpark.p;
+        }
+    }
     const long long VB = jr ? jvp_virtual_molecules(h, B, jr->D) : 0, VN = VB * A, vgroups = VB / h->G * h->parts;
     if (jr) {
         ensure_jvp_ws(h, B, jr->D);
@@ -772,15 +801,17 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
                 p.edge_emb = h->F(h->edge_emb); p.rows = h->rows.p; p.nblk = h->nblk; p.G = h->G; p.parts = h->parts; p.A = A; p.first = l == 0; p.last = l == L - 1;
                 p.B = B; p.n_groups = groups; p.length_scale = h->d.length_scale; p.x = x_dev; p.P = h->P.p; p.e = h->e.p;
                 p.wq = reinterpret_cast<float4*>(h->wq.p); p.st = reinterpret_cast<float4*>(h->phist.p);
+                const bool typed = mrows && !h->ptype.empty();      // per-molecule edge types: the filter pass reads them from the row words
+                if (typed) p.rows = mrows;
                 Timed tm(h, TI_KERNEL_PAINN_JVP_FILTER);
-                HIP_CHECK(launch_jvp_filter(NB, split, p, st));
+                HIP_CHECK(launch_jvp_filter(NB, split, p, st, typed));
             }
             JvpEdgeParams p{};
             p.stream = h->S(h->st_jvp_phi[l]); p.nch = h->st_jvp_phi[l].nch; p.pad = h->jvp_phi_pad[l]; p.vecs = h->edge_vecs.p + (size_t)l * 21 * F;
             p.edge_emb = h->F(h->edge_emb); p.rows = h->rows.p; p.slotnode = h->slotnode.p;
             p.nblk = h->nblk; p.G = h->G; p.parts = h->parts; p.A = A; p.D = jr->D; p.first = l == 0; p.last = l == L - 1;
             p.B = B; p.n_groups = vgroups;
-            p.x = x_dev; p.xdot = jr->xdot; p.P = h->P.p; p.v = h->v.p; p.e = h->e.p; p.wq = reinterpret_cast<const float4*>(h->wq.p);
+            p.x = x_dev; p.xdot = xdot; p.P = h->P.p; p.v = h->v.p; p.e = h->e.p; p.wq = reinterpret_cast<const float4*>(h->wq.p);
             p.st = reinterpret_cast<const float4*>(h->phist.p); p.tP = h->tP.p; p.tv = h->tv.p;
             p.te = h->te.p; p.tdsacc = h->tdsacc.p; p.tdvacc = h->tdvacc.p; p.tcacc = h->tcacc.p;
             if (mrows) p.rows = mrows;
@@ -888,6 +919,10 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
         Timed tm(h, TI_KERNEL_PAINN_READOUT);
         HIP_CHECK(launch_readout(NB, prec, p, st));
     }
+    if (nat) {            // a pad atom's drift (and the tangent of an explicit direction) is +0 whatever the network made of it
+        HIP_CHECK(launch_zero_pads(out_dev, nat, B, 1, A, 3, st));
+        if (jr && jr->D == 1) HIP_CHECK(launch_zero_pads(jr->tout, nat, B, 1, A, 3, st));
+    }
 }
 
 // drift and exact divergence: 3A unit-seed tangent passes per molecule, in chunks that fit the tangent HBM budget
@@ -902,7 +937,8 @@ void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float*
         JvpRun jr{D, nullptr, h->tout.p};
         painn_drift_dev(h, x_dev + (size_t)b0 * A * 3, t, cond_dev ? cond_dev + (size_t)b0 * A * h->ncond : nullptr, bc,
                         out_dev + (size_t)b0 * A * 3, &jr, tv ? tv + b0 : nullptr, b0);
-        HIP_CHECK(launch_div_reduce(h->tout.p, bc, D, h->G, div_dev + b0, h->stream));
+        if (h->ragged) HIP_CHECK(launch_div_reduce_ragged(h->tout.p, bc, D, h->G, h->natoms_dev.p + b0, div_dev + b0, h->stream));
+        else HIP_CHECK(launch_div_reduce(h->tout.p, bc, D, h->G, div_dev + b0, h->stream));
     }
     h->last_B = std::min(chunk, B);
 }
@@ -914,6 +950,7 @@ void painn_make_probes(ti_handle* h, long long B, int k, uint64_t seed, long lon
     const int n3 = 3 * h->d.n_atoms;
     if (h->probes.n < (size_t)B * k * n3) h->probes.alloc((size_t)B * k * n3);
     HIP_CHECK(launch_probes(h->probes.p, seed, traj0, B, k, n3, h->stream));
+    if (h->ragged) HIP_CHECK(launch_zero_pads(h->probes.p, h->natoms_dev.p, B * k, k, h->d.n_atoms, 3, h->stream));      // pad components: 0
 }
 
 // drift and Hutchinson estimate of the divergence along the k probes of h->probes: D = k explicit tangent directions per molecule,
@@ -1016,10 +1053,16 @@ struct DlogpAux {
     float div_scale = 1e-2f, out_scale = 100.0f;  // d(dlogp)/dt = -div_scale * div, written * out_scale
 };
 
+// Mixed-species batches (ti_painn_set_molecules): device atom counts [B] of a state [B][A][3], and the number of real floats in it.
+// n == NULL: every entry is real.  The drift already returns +0 on pad atoms, so the fixed-step updates leave them where they are;
+// what changes is the EM noise, the adaptive solvers' norms and their dense output.
+struct Ragged { const int32_t* n = nullptr; int A = 0; size_t n_real = 0; };
+Ragged ragged_of(const ti_handle* h) { return h->ragged ? Ragged{h->natoms_dev.p, h->d.n_atoms, (size_t)h->n_real * 3} : Ragged{}; }
+
 // drift(x_dev, t, out_b, out_div) evaluates the drift (and the divergence if out_div != NULL); state arrays have n floats
 template <typename Drift>
 int rollout_common(ti_handle* h, const ti_rollout_desc* rd, float* x, float* b1, float* b2, float* xt, size_t n, long long B, int comps,
-                   int atoms_for_com, float* out_path, int64_t* n_fevals, Drift&& drift, DlogpAux aux = DlogpAux())
+                   int atoms_for_com, float* out_path, int64_t* n_fevals, Drift&& drift, DlogpAux aux = DlogpAux(), Ragged rg = Ragged())
 {
     hipStream_t st = h->stream;
     const hipMemcpyKind out_kind = rd->mem == TI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -1046,7 +1089,10 @@ int rollout_common(ti_handle* h, const ti_rollout_desc* rd, float* x, float* b1,
             Timed tm(h, TI_KERNEL_INTEGRATE);
             HIP_CHECK(launch_axpy(x, x, dt, b1, (long long)n, st));
             if (aux.dl) HIP_CHECK(launch_axpy(aux.dl, aux.dl, -dt * aux.div_scale, aux.d1, (long long)ndl, st));
-            if (rd->scheme == TI_SCHEME_EM && rd->eps > 0.0f)
+            if (rd->scheme == TI_SCHEME_EM && rd->eps > 0.0f && rg.n)
+                HIP_CHECK(launch_noise_ragged(x, std::sqrt(2.0f * rd->eps * std::fabs(dt)), rd->seed, rd->traj_offset, (int)(rd->step_offset + k), B, rg.A,
+                                              rd->com_free_noise ? 1 : 0, rg.n, st));
+            else if (rd->scheme == TI_SCHEME_EM && rd->eps > 0.0f)
                 HIP_CHECK(launch_noise(x, std::sqrt(2.0f * rd->eps * std::fabs(dt)), rd->seed, rd->traj_offset, (int)(rd->step_offset + k), B, comps,
                                        rd->com_free_noise ? atoms_for_com : 0, st));
         }
@@ -1083,7 +1129,7 @@ constexpr double c_mid[7] = {6025192743. / 30085553152. / 2, 0., 51252292925. / 
 
 template <typename Drift>
 int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, float* out_path, int64_t* n_fevals, Drift&& drift,
-               DlogpAux aux = DlogpAux())
+               DlogpAux aux = DlogpAux(), Ragged rg = Ragged())
 {
     hipStream_t st = h->stream;
     const hipMemcpyKind out_kind = rd->mem == TI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -1163,22 +1209,27 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
             double best = 0.0;
             for (int s2 = 0; s2 < nseg; ++s2) {
                 launch_one(s2);
-                best = std::max(best, std::sqrt(fetch() / (double)sn[s2]));
+                best = std::max(best, std::sqrt(fetch() / (double)(s2 == 0 && rg.n ? rg.n_real : sn[s2])));      // rms over the real entries
             }
             return best;
         };
         const double t_first = sign * (double)rd->t_grid[0];
         F((float)t_first, y, KP(0));
         // _select_initial_step(func, t0, y0, order - 1 = 4, rtol, atol, norm, f0)
-        const double d0 = norm_of([&](int s2) { HIP_CHECK(launch_scaled_sumsq(red + RED_PARTIALS, red, y[s2], nullptr, y[s2], rtol, atol, (long long)sn[s2], st)); });
-        const double d1 = norm_of([&](int s2) { HIP_CHECK(launch_scaled_sumsq(red + RED_PARTIALS, red, k[s2][0], nullptr, y[s2], rtol, atol, (long long)sn[s2], st)); });
+        // segment 0 of a mixed-species batch takes the ragged sums (pad entries skipped)
+        auto scaled_sumsq = [&](int s2, const float* a, const float* b2) {
+            if (s2 == 0 && rg.n) HIP_CHECK(launch_scaled_sumsq_ragged(red + RED_PARTIALS, red, a, b2, y[s2], rtol, atol, (long long)sn[s2], rg.n, 3 * rg.A, st));
+            else HIP_CHECK(launch_scaled_sumsq(red + RED_PARTIALS, red, a, b2, y[s2], rtol, atol, (long long)sn[s2], st));
+        };
+        const double d0 = norm_of([&](int s2) { scaled_sumsq(s2, y[s2], nullptr); });
+        const double d1 = norm_of([&](int s2) { scaled_sumsq(s2, k[s2][0], nullptr); });
         const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
         {
             const double one[1] = {1.};
             for (int s2 = 0; s2 < nseg; ++s2) HIP_CHECK(launch_rk_combo(ytmp[s2], y[s2], comb(s2, 1, one, h0), (long long)sn[s2], st));
         }
         F((float)(t_first + h0), ytmp, KP(1));
-        const double d2 = norm_of([&](int s2) { HIP_CHECK(launch_scaled_sumsq(red + RED_PARTIALS, red, k[s2][1], k[s2][0], y[s2], rtol, atol, (long long)sn[s2], st)); }) / h0;
+        const double d2 = norm_of([&](int s2) { scaled_sumsq(s2, k[s2][1], k[s2][0]); }) / h0;
         const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3) : std::pow(0.01 / std::max(d1, d2), 1.0 / 5.0);
         double dt = std::min(100.0 * h0, h1);
         double t0 = t_first, t1 = t_first;            // interpolation interval of the last accepted step
@@ -1198,7 +1249,8 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
                     F(ti, dst, KP(sidx + 1));
                 }
                 const double ratio = norm_of([&](int s2) {                  // _compute_error_ratio
-                    HIP_CHECK(launch_rk_ratio_sumsq(red + RED_PARTIALS, red, y[s2], ynew[s2], comb(s2, 7, dp5::c_error, dtf), rtol, atol, (long long)sn[s2], st));
+                    if (s2 == 0 && rg.n) HIP_CHECK(launch_rk_ratio_sumsq_ragged(red + RED_PARTIALS, red, y[s2], ynew[s2], comb(s2, 7, dp5::c_error, dtf), rtol, atol, (long long)sn[s2], rg.n, 3 * rg.A, st));
+                    else HIP_CHECK(launch_rk_ratio_sumsq(red + RED_PARTIALS, red, y[s2], ynew[s2], comb(s2, 7, dp5::c_error, dtf), rtol, atol, (long long)sn[s2], st));
                 });
                 if (!(ratio == ratio)) return fail(TI_E_NAN, "dopri5: non-finite error estimate");
                 if (ratio <= 1.0) {                                          // accept: dense output, FSAL
@@ -1216,6 +1268,7 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
             if (wants_row(i)) {                                              // _interp_evaluate at the requested time
                 const float xrel = (float)((next_t - t0) / (t1 - t0));
                 for (int s2 = 0; s2 < nseg; ++s2) HIP_CHECK(launch_interp_eval(ytmp[s2], coef[s2], xrel, (long long)sn[s2], st));
+                if (rg.n) HIP_CHECK(launch_copy_pads(ytmp[0], y[0], rg.n, (long long)(n / (3 * rg.A)), rg.A, 3, st));      // pads: the state, not its fit
                 save_from(ytmp);
             }
         }
@@ -1236,7 +1289,7 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
 // (frozen) trajectory is evaluated along but never written again.  One small status read-back per attempt, as in rollout_rk.
 template <typename DriftTv>
 int rollout_rk_traj(ti_handle* h, const ti_rollout_desc* rd, float* x, long long B, long long m, float* out_path, int64_t* n_fevals,
-                    DriftTv&& drift, DlogpAux aux = DlogpAux())
+                    DriftTv&& drift, DlogpAux aux = DlogpAux(), Ragged rg = Ragged())
 {
     hipStream_t st = h->stream;
     const int nseg = aux.dl ? 2 : 1, N = rd->n_step;
@@ -1295,9 +1348,9 @@ int rollout_rk_traj(ti_handle* h, const ti_rollout_desc* rd, float* x, long long
         HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->rk_tv.p), (int)bits, (size_t)B, st));
     }
     F(0);
-    HIP_CHECK(launch_traj_init(p, 0, st));                    // _select_initial_step, per trajectory
+    HIP_CHECK(rg.n ? launch_traj_init_ragged(p, 0, rg.n, st) : launch_traj_init(p, 0, st));                    // _select_initial_step, per trajectory
     F(1);
-    HIP_CHECK(launch_traj_init(p, 1, st));
+    HIP_CHECK(rg.n ? launch_traj_init_ragged(p, 1, rg.n, st) : launch_traj_init(p, 1, st));
     float c_err[7], c_mid[7];
     for (int j = 0; j < 7; ++j) { c_err[j] = (float)dp5::c_error[j]; c_mid[j] = (float)dp5::c_mid[j]; }
     int status[TRAJ_ST_N] = {0, 0, INT_MAX, INT_MAX, INT_MAX, 0, 0, 0};
@@ -1316,10 +1369,11 @@ int rollout_rk_traj(ti_handle* h, const ti_rollout_desc* rd, float* x, long long
         for (int sidx = 0; sidx < 6; ++sidx) {                                   // _runge_kutta_step, every trajectory with its own dt
             float c[6];
             for (int j = 0; j <= sidx; ++j) c[j] = (float)dp5::beta[sidx][j];
-            HIP_CHECK(launch_traj_stage(p, c, sidx + 1, (float)dp5::alpha[sidx], dp5::alpha[sidx] == 1.0, sidx == 5, sidx == 0, st));
+            HIP_CHECK(rg.n ? launch_traj_stage_ragged(p, c, sidx + 1, (float)dp5::alpha[sidx], dp5::alpha[sidx] == 1.0, sidx == 5, sidx == 0, rg.n, st)
+                           : launch_traj_stage(p, c, sidx + 1, (float)dp5::alpha[sidx], dp5::alpha[sidx] == 1.0, sidx == 5, sidx == 0, st));
             F(sidx == 5 ? 6 : sidx + 1);
         }
-        HIP_CHECK(launch_traj_advance(p, c_err, c_mid, st));
+        HIP_CHECK(rg.n ? launch_traj_advance_ragged(p, c_err, c_mid, rg.n, st) : launch_traj_advance(p, c_err, c_mid, st));
         HIP_CHECK(hipMemcpyAsync(status, h->rk_status.p, sizeof(status), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         if (status[TRAJ_ST_UNDERFLOW] != INT_MAX)
@@ -1541,11 +1595,12 @@ int ti_painn_rollout(ti_handle* h, const ti_rollout_desc* rd, const float* x0, c
         const float* cd = cond;
         if (rd->mem == TI_MEM_HOST && nc) { HIP_CHECK(hipMemcpyAsync(h->cond.p, cond, nc * sizeof(float), hipMemcpyHostToDevice, h->stream)); cd = h->cond.p; }
         const int saved_tap = h->tap; h->tap = -1;
+        const Ragged rg = ragged_of(h);
         auto drift = [&](const float* xs, float t, float* o, float*) { painn_drift_dev(h, xs, t, cd, B, o); };
         auto drift_tv = [&](const float* xs, const float* tv, float* o, float*) { painn_drift_dev(h, xs, 0.f, cd, B, o, nullptr, tv); };
-        const int rc = rd->scheme == TI_SCHEME_DOPRI5_TRAJ ? rollout_rk_traj(h, rd, h->x.p, B, A * 3, out_path, n_fevals, drift_tv)
-                     : rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift)
-                                                      : rollout_common(h, rd, h->x.p, h->b1.p, h->b2.p, h->xt.p, n, B, A * 3, A, out_path, n_fevals, drift);
+        const int rc = rd->scheme == TI_SCHEME_DOPRI5_TRAJ ? rollout_rk_traj(h, rd, h->x.p, B, A * 3, out_path, n_fevals, drift_tv, DlogpAux(), rg)
+                     : rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift, DlogpAux(), rg)
+                                                      : rollout_common(h, rd, h->x.p, h->b1.p, h->b2.p, h->xt.p, n, B, A * 3, A, out_path, n_fevals, drift, DlogpAux(), rg);
         h->tap = saved_tap;
         return rc;
     });
@@ -1662,6 +1717,7 @@ static int painn_rollout_dlogp_impl(ti_handle* h, const ti_rollout_desc* rd, int
         const float* cd = cond;
         if (rd->mem == TI_MEM_HOST && nc) { HIP_CHECK(hipMemcpyAsync(h->cond.p, cond, nc * sizeof(float), hipMemcpyHostToDevice, h->stream)); cd = h->cond.p; }
         const int saved_tap = h->tap; h->tap = -1;
+        const Ragged rg = ragged_of(h);
         if (n_probes > 0) painn_make_probes(h, B, n_probes, probe_seed, rd->traj_offset);
         DlogpAux aux;
         aux.dl = h->dl.p; aux.d1 = h->divb.p; aux.d2 = h->div2.p; aux.scaled = h->dlscaled.p; aux.out = out_dlogp;
@@ -1682,9 +1738,9 @@ static int painn_rollout_dlogp_impl(ti_handle* h, const ti_rollout_desc* rd, int
                 HIP_CHECK(launch_scale(dv, dv, -1.0f, (long long)B, h->stream));
             }
         };
-        const int rc = rd->scheme == TI_SCHEME_DOPRI5_TRAJ ? rollout_rk_traj(h, rd, h->x.p, B, A * 3, out_path, n_fevals, drift_tv, aux)
-                     : rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift, aux)
-                                                      : rollout_common(h, rd, h->x.p, h->b1.p, h->b2.p, h->xt.p, n, B, A * 3, A, out_path, n_fevals, drift, aux);
+        const int rc = rd->scheme == TI_SCHEME_DOPRI5_TRAJ ? rollout_rk_traj(h, rd, h->x.p, B, A * 3, out_path, n_fevals, drift_tv, aux, rg)
+                     : rd->scheme >= TI_SCHEME_DOPRI5 ? rollout_rk(h, rd, h->x.p, n, out_path, n_fevals, drift, aux, rg)
+                                                      : rollout_common(h, rd, h->x.p, h->b1.p, h->b2.p, h->xt.p, n, B, A * 3, A, out_path, n_fevals, drift, aux, rg);
         h->tap = saved_tap;
         return rc;
     });
@@ -2085,38 +2141,93 @@ int ti_painn_template_for(ti_handle* h, int64_t B)
     return template_for(h, B);
 }
 
+// The per-molecule graph state both setters below write: mask m [B][A] (bits of pad atoms cleared here), atom counts (empty: all A),
+// edge types (empty: the template's).  Replaces whatever was in force.
+static int set_graph_state(ti_handle* h, std::vector<uint32_t>& m, std::vector<int32_t>& natoms, std::vector<uint8_t>& ptype, long long B)
+{
+    const int A = h->d.n_atoms;
+    long long n_real = (long long)B * A; bool ragged = false;
+    if (!natoms.empty()) {
+        n_real = 0;
+        for (long long b = 0; b < B; ++b) {
+            const int n = natoms[b];
+            n_real += n; ragged = ragged || n < A;
+            const uint32_t real = n >= 32 ? 0xffffffffu : (1u << n) - 1u;         // sources that are real atoms
+            for (int d = 0; d < A; ++d) m[(size_t)b * A + d] = d < n ? m[(size_t)b * A + d] & real : 0u;
+        }
+    }
+    // symmetric over the template: for every template edge s -> d whose reverse is one too, both bits (and, where the edge is present,
+    // both types) agree in every molecule
+    std::vector<uint32_t> in_tpl(A, 0);          // bit s of in_tpl[d]: s -> d is a template edge
+    for (size_t k = 0; k < h->esrc.size(); ++k) in_tpl[h->edst[k]] |= 1u << h->esrc[k];
+    bool sym = true;
+    for (long long b = 0; b < B && sym; ++b)
+        for (int d = 0; d < A && sym; ++d)
+            for (int s2 = 0; s2 < A; ++s2) {
+                if (!((in_tpl[d] >> s2) & 1u) || !((in_tpl[s2] >> d) & 1u)) continue;
+                const uint32_t on = (m[(size_t)b * A + d] >> s2) & 1u;
+                if (on != ((m[(size_t)b * A + s2] >> d) & 1u)) { sym = false; break; }
+                if (on && !ptype.empty() && ptype[((size_t)b * A + s2) * A + d] != ptype[((size_t)b * A + d) * A + s2]) { sym = false; break; }
+            }
+    if (h->emask_B == B && m == h->emask && natoms == h->natoms && ptype == h->ptype) return TI_OK;      // the same state again (a mirror class sets it before every call)
+    HIP_CHECK(hipStreamSynchronize(h->stream));                   // no launch in flight still reads the row words about to be replaced
+    h->emask.swap(m); h->emask_B = B; h->emask_sym = sym;
+    h->natoms.swap(natoms); h->ptype.swap(ptype); h->ragged = ragged; h->n_real = n_real;
+    if (ragged) h->natoms_dev.upload(h->natoms); else h->natoms_dev.release();
+    for (int t = 0; t < 3; ++t) h->mrows_ok[t] = false;
+    return TI_OK;
+}
+
+static void clear_graph_state(ti_handle* h)
+{
+    h->emask_B = 0; h->emask_sym = true; h->emask.clear(); h->natoms.clear(); h->ptype.clear(); h->ragged = false; h->n_real = 0;
+    for (int t = 0; t < 3; ++t) { h->mrows_ok[t] = false; h->mrows[t].release(); }
+}
+
 int ti_painn_set_edge_mask(ti_handle* h, const uint32_t* mask, int64_t B, int mem)
 {
     // the arguments first, then the handle: each refusal has its own message, checkable without a device
     if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
     if (mask && B < 1) return fail(TI_E_ARG, "B < 1");
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
-    if (!mask) {
-        h->emask_B = 0; h->emask_sym = true; h->emask.clear();
-        for (int t = 0; t < 3; ++t) { h->mrows_ok[t] = false; h->mrows[t].release(); }
-        return TI_OK;
-    }
+    if (!mask) { clear_graph_state(h); return TI_OK; }
     return guarded([&]() -> int {
         set_device(h);
         const int A = h->d.n_atoms;
         std::vector<uint32_t> m((size_t)B * A);
         if (mem == TI_MEM_DEVICE) HIP_CHECK(hipMemcpy(m.data(), mask, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         else std::memcpy(m.data(), mask, m.size() * sizeof(uint32_t));
-        // symmetric over the template: for every template edge s -> d whose reverse is one too, both bits agree in every molecule
-        std::vector<uint32_t> in_tpl(A, 0);          // bit s of in_tpl[d]: s -> d is a template edge
-        for (size_t k = 0; k < h->esrc.size(); ++k) in_tpl[h->edst[k]] |= 1u << h->esrc[k];
-        bool sym = true;
-        for (long long b = 0; b < B && sym; ++b)
-            for (int d = 0; d < A && sym; ++d)
-                for (int s2 = 0; s2 < A; ++s2) {
-                    if (!((in_tpl[d] >> s2) & 1u) || !((in_tpl[s2] >> d) & 1u)) continue;
-                    if (((m[(size_t)b * A + d] >> s2) & 1u) != ((m[(size_t)b * A + s2] >> d) & 1u)) { sym = false; break; }
-                }
-        if (h->emask_B == B && m == h->emask) return TI_OK;            // the same mask again (a mirror class sets it before every call)
-        HIP_CHECK(hipStreamSynchronize(h->stream));                   // no launch in flight still reads the row words about to be replaced
-        h->emask.swap(m); h->emask_B = B; h->emask_sym = sym;
-        for (int t = 0; t < 3; ++t) h->mrows_ok[t] = false;
-        return TI_OK;
+        std::vector<int32_t> none; std::vector<uint8_t> no_types;
+        return set_graph_state(h, m, none, no_types, B);
+    });
+}
+
+int ti_painn_set_molecules(ti_handle* h, const int32_t* n_atoms, const uint32_t* mask, const uint8_t* pair_type, int64_t B, int mem)
+{
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (n_atoms && B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (!n_atoms) { clear_graph_state(h); return TI_OK; }
+    return guarded([&]() -> int {
+        set_device(h);
+        const int A = h->d.n_atoms;
+        auto fetch = [&](void* dst, const void* src, size_t bytes) {
+            if (mem == TI_MEM_DEVICE) HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+            else std::memcpy(dst, src, bytes);
+        };
+        std::vector<int32_t> na((size_t)B);
+        fetch(na.data(), n_atoms, na.size() * sizeof(int32_t));
+        for (long long b = 0; b < B; ++b)
+            if (na[b] < 1 || na[b] > A) return fail(TI_E_ARG, "n_atoms[" + std::to_string(b) + "] = " + std::to_string(na[b]) + " is outside 1.." + std::to_string(A));
+        std::vector<uint8_t> pt;
+        if (pair_type) {
+            pt.resize((size_t)B * A * A);
+            fetch(pt.data(), pair_type, pt.size());
+            for (size_t i = 0; i < pt.size(); ++i) if (pt[i] > 3) return fail(TI_E_ARG, "pair_type above 3 (molecule " + std::to_string(i / ((size_t)A * A)) + ")");
+        }
+        std::vector<uint32_t> m((size_t)B * A, 0xffffffffu);       // NULL: every template edge (between real atoms, set_graph_state)
+        if (mask) fetch(m.data(), mask, m.size() * sizeof(uint32_t));
+        return set_graph_state(h, m, na, pt, B);
     });
 }
 

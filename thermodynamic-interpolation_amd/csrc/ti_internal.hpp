@@ -184,7 +184,8 @@ struct JvpReadoutParams {
     const float *s, *v, *ts, *tv;
     float* tout;                            // [virtual nodes][3]
 };
-hipError_t launch_jvp_filter(int NB, bool split, const JvpFilterParams& p, hipStream_t st);
+// masked: p.rows holds row words per (group, part) with each molecule's own edge types (ti_painn_set_molecules with pair_type)
+hipError_t launch_jvp_filter(int NB, bool split, const JvpFilterParams& p, hipStream_t st, bool masked = false);
 hipError_t launch_jvp_edge(int NB, bool split, const JvpEdgeParams& p, hipStream_t st, bool masked = false);
 hipError_t launch_jvp_node(int NB, bool split, const JvpNodeParams& p, hipStream_t st);
 hipError_t launch_jvp_update(int NB, bool split, const JvpUpdateParams& p, hipStream_t st);
@@ -223,6 +224,17 @@ hipError_t launch_scale(float* y, const float* x, float a, long long n, hipStrea
 hipError_t launch_selftest(float* out /*[64*16]*/, hipStream_t st);
 hipError_t launch_split_selftest(unsigned* out /*[2], zeroed: differing halves, subnormal-product mismatches*/, hipStream_t st);
 hipError_t launch_nan_check(const float* x, long long n, int* flag, hipStream_t st);
+// ---- mixed-species batches (ti_painn_set_molecules): arrays of [mols][A][comps] floats, molecule i has n_atoms[i / rep] real atoms
+// dst = src on real atoms; on pad atoms 0, or with park_coords (comps = 3) the parking place x[mol][0] + (100 (a - n + 1), 0, 0)
+hipError_t launch_park_pads(float* dst, const float* src, const int32_t* n_atoms, long long mols, int rep, int A, int comps, int park_coords,
+                            hipStream_t st);
+hipError_t launch_zero_pads(float* y, const int32_t* n_atoms, long long mols, int rep, int A, int comps, hipStream_t st);      // y = +0 on pads
+hipError_t launch_copy_pads(float* dst, const float* src, const int32_t* n_atoms, long long mols, int A, int comps, hipStream_t st);   // dst = src on pads
+// launch_noise over the 3 n_atoms[b] real components of each molecule ([B][A][3]); com: centre of mass over the real atoms
+hipError_t launch_noise_ragged(float* x, float sigma, uint64_t seed, long long traj0, int step, long long B, int A, int com,
+                               const int32_t* n_atoms, hipStream_t st);
+// launch_div_reduce (D = 3A unit seeds) summing the 3 n_atoms[b] real directions of each molecule only
+hipError_t launch_div_reduce_ragged(const float* tout, long long B, int D, int G, const int32_t* n_atoms, float* div, hipStream_t st);
 
 // ---- Runge-Kutta pieces (ode_kernels.hip)
 struct RkComb { const float* k[7]; float c[7]; int nk; };     // sum_j c[j] * k[j][i], j < nk
@@ -234,6 +246,12 @@ hipError_t launch_rk_ratio_sumsq(double* out, double* partial, const float* y0, 
 // *out = sum_i ((a_i - b_i) / (atol + rtol |y0_i|))^2   (b may be NULL)
 hipError_t launch_scaled_sumsq(double* out, double* partial, const float* a, const float* b, const float* y0, float rtol, float atol,
                                long long n, hipStream_t st);
+// ragged twins (ode_ragged_kernels.hip, ti_painn_set_molecules): the state is [B][m] with m = 3A floats per molecule of which the first
+// 3 n_atoms[b] are real; pad entries are skipped in the same summation order (the caller divides by the real count)
+hipError_t launch_rk_ratio_sumsq_ragged(double* out, double* partial, const float* y0, const float* y1, const RkComb& c, float rtol, float atol,
+                                        long long n, const int32_t* n_atoms, int m, hipStream_t st);
+hipError_t launch_scaled_sumsq_ragged(double* out, double* partial, const float* a, const float* b, const float* y0, float rtol, float atol,
+                                      long long n, const int32_t* n_atoms, int m, hipStream_t st);
 hipError_t launch_interp_fit(float* coef /*[5][n]*/, const float* y0, const float* y1, const float* f0, const float* f1, const RkComb& mid,
                              float dt, long long n, hipStream_t st);
 hipError_t launch_interp_eval(float* out, const float* coef, float x, long long n, hipStream_t st);
@@ -278,5 +296,10 @@ hipError_t launch_traj_stage(const TrajRkParams& p, const float* c, int nk, floa
                              hipStream_t st);
 // error ratio, accept / reject, dense-output fit, FSAL copy, step factor, emission of the grid rows the accepted step crossed
 hipError_t launch_traj_advance(const TrajRkParams& p, const float* c_error /*[7]*/, const float* c_mid /*[7]*/, hipStream_t st);
+// ragged twins of the three (ode_ragged_kernels.hip): segment 0's norms over the first 3 n_atoms[b] of its m entries, pad entries kept
+hipError_t launch_traj_init_ragged(const TrajRkParams& p, int phase, const int32_t* n_atoms, hipStream_t st);
+hipError_t launch_traj_stage_ragged(const TrajRkParams& p, const float* c, int nk, float alpha, int alpha_one, int to_ynew, int stage0,
+                                    const int32_t* n_atoms, hipStream_t st);
+hipError_t launch_traj_advance_ragged(const TrajRkParams& p, const float* c_error, const float* c_mid, const int32_t* n_atoms, hipStream_t st);
 
 }  // namespace ti

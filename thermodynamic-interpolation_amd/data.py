@@ -127,6 +127,31 @@ def make_batch(variant: str, x0, template, *, T0=None, T1=None, T=None, atom_ids
     return b
 
 
+def concat_species_batches(items):
+    """One mixed-species batch from per-species sampler items (make_batch results, or the batches a dataset yields): node arrays
+    and per-molecule arrays concatenated in order, edge_index shifted by the nodes before it, batch renumbered -- what PyG's
+    Batch.from_data_list gives the reference for a list of molecules of different species.  Every item must carry the same fields."""
+    items = list(items)
+    if not items:
+        raise ValueError("no items")
+    out = types.SimpleNamespace()
+    n_nodes = [int(np.asarray(it.batch).size) for it in items]
+    n_mols = [int(np.asarray(it.batch).max()) + 1 for it in items]
+    node_off, mol_off = np.concatenate([[0], np.cumsum(n_nodes)[:-1]]), np.concatenate([[0], np.cumsum(n_mols)[:-1]])
+    keys = set(vars(items[0]))
+    if any(set(vars(it)) != keys for it in items):
+        raise ValueError("the items carry different fields")
+    for k in sorted(keys):
+        vals = [np.asarray(getattr(it, k)) for it in items]
+        if k == "edge_index":
+            out.edge_index = np.concatenate([v + o for v, o in zip(vals, node_off)], axis=1)
+        elif k == "batch":
+            out.batch = np.concatenate([v + o for v, o in zip(vals, mol_off)])
+        else:
+            out.__dict__[k] = np.concatenate(vals, axis=0)
+    return out
+
+
 def load_trajectory(traj_path: str, split: str, traj_filename: str, T: int, scale: bool) -> np.ndarray:
     """[n_frames, A, 3] frames at temperature T from ``{traj_path}/{split}/{traj_filename}`` ([8, n_frames, A, 3], axis 0 =
     TEMPERATURES), centred, optionally scaled (get_mdqm9_trajs, mdqm9_ambient.py:202-211)."""

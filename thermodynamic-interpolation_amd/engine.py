@@ -217,6 +217,39 @@ class PainnEngine(_Engine):
         m = np.ascontiguousarray(m.view(np.uint32))
         _lib.check(L.ti_painn_set_edge_mask(self.h, C.c_void_p(m.ctypes.data), int(m.shape[0]), _lib.MEM_HOST))
 
+    def set_molecules(self, n_atoms, mask=None, pair_type=None):
+        """Mixed-species batches over this engine's template (A = the largest molecule): n_atoms [B] in 1..A -- atoms a >= n_atoms[b]
+        of molecule b are pad atoms (drift exactly 0, never moved, no noise; what they carry never reaches a real atom); mask [B, A]
+        as in set_edge_mask (None: every template edge between real atoms); pair_type [B, A, A] in 0..3, the type of the edge s -> d
+        of molecule b at [b, s, d] (None: the template's types).  Replaces an edge mask in force and is replaced by set_edge_mask;
+        set_molecules(None) clears it.  Host arrays (numpy, or CPU tensors) are copied."""
+        L = _lib.lib()
+        if n_atoms is None:
+            _lib.check(L.ti_painn_set_molecules(self.h, None, None, None, 0, _lib.MEM_HOST))
+            return
+        host = lambda a: a.detach().cpu().numpy() if hasattr(a, "data_ptr") else np.asarray(a)
+        n = np.ascontiguousarray(host(n_atoms), np.int32)
+        if n.ndim != 1 or n.size < 1:
+            raise ValueError("n_atoms must be a non-empty 1-D array")
+        B = int(n.size)
+        m = t = None
+        if mask is not None:
+            m = host(mask)
+            if m.dtype not in (np.uint32, np.int32):
+                raise TypeError(f"mask must be uint32 or int32, got {m.dtype}")
+            if m.shape != (B, self.A):
+                raise ValueError(f"mask must be [{B},{self.A}], got {m.shape}")
+            m = np.ascontiguousarray(m.view(np.uint32))
+        if pair_type is not None:
+            t = host(pair_type)
+            if t.shape != (B, self.A, self.A):
+                raise ValueError(f"pair_type must be [{B},{self.A},{self.A}], got {t.shape}")
+            if t.size and (t.min() < 0 or t.max() > 3):
+                raise ValueError("pair_type entries must be in 0..3")
+            t = np.ascontiguousarray(t, np.uint8)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        _lib.check(L.ti_painn_set_molecules(self.h, ptr(n), ptr(m), ptr(t), B, _lib.MEM_HOST))
+
     def _check_x(self, x, name="x"):
         if x is None or len(x.shape) != 3 or tuple(x.shape[1:]) != (self.A, 3):
             raise ValueError(f"{name} must be [B,{self.A},3]")

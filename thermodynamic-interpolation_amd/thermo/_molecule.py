@@ -127,6 +127,130 @@ def split_graph_batch(batch, atom_key: str):
     return B, A, s_all.astype(np.int32), d_all.astype(np.int32), etype.astype(np.int32), at[0].astype(np.int32), mask
 
 
+class SpeciesBatch:
+    """What split_species_batch returns: the engine's template (B, A, src, dst, etype, atom_ids), the per-molecule graph state
+    (mask [B, A] uint32 | None, n_atoms [B] int32 | None, pair_type [B, A, A] uint8 | None) and the index maps between the
+    reference's flat node order [N] and the padded [B, A] layout: node_index [N] = b * A + a of every flat node (pads are the
+    padded positions no node maps to).  n_atoms is None for a batch split_graph_batch accepts: its result, unchanged."""
+
+    def __init__(self, B, A, src, dst, etype, atom_ids, mask, n_atoms=None, pair_type=None, node_index=None):
+        self.B, self.A, self.src, self.dst, self.etype, self.atom_ids, self.mask = B, A, src, dst, etype, atom_ids, mask
+        self.n_atoms, self.pair_type = n_atoms, pair_type
+        self.node_index = np.arange(B * A, dtype=np.int64) if node_index is None else node_index
+        self.N = int(self.node_index.size)
+
+    def template(self):
+        return self.B, self.A, self.src, self.dst, self.etype, self.atom_ids, self.mask
+
+    def pad(self, flat, comps, dtype=np.float32):
+        """[N, comps] (or [N]) per-node values -> [B, A, comps], zeros on pad atoms; a CUDA tensor stays on its device."""
+        if C.is_cuda(flat):
+            import torch
+            v = flat.detach().to(torch.float32).reshape(self.N, comps)
+            if self.n_atoms is None:
+                return v.reshape(self.B, self.A, comps).contiguous()
+            out = v.new_zeros((self.B * self.A, comps))
+            out[torch.from_numpy(self.node_index).to(v.device)] = v
+            return out.reshape(self.B, self.A, comps)
+        v = C.to_numpy(flat).astype(dtype, copy=False).reshape(self.N, comps)
+        if self.n_atoms is None:
+            return np.ascontiguousarray(v.reshape(self.B, self.A, comps))
+        out = np.zeros((self.B * self.A, comps), dtype)
+        out[self.node_index] = v
+        return out.reshape(self.B, self.A, comps)
+
+    def unpad(self, padded):
+        """[..., B, A, 3] -> [..., N, 3] in the reference's flat node order, pads removed."""
+        lead = tuple(padded.shape[:-3])
+        flat = padded.reshape(lead + (self.B * self.A, 3))
+        if self.n_atoms is None:
+            return flat
+        if C.is_torch(flat):
+            import torch
+            return flat[..., torch.from_numpy(self.node_index).to(flat.device), :]
+        return flat[..., self.node_index, :]
+
+    def molecule_values(self, per_node):
+        """[N] per-node values -> [B, A] with every pad carrying its molecule's first value (so 'constant within a molecule' holds)."""
+        v = C.to_numpy(per_node).ravel()
+        if self.n_atoms is None or v.size != self.N:
+            return v
+        first = np.concatenate([[0], np.cumsum(self.n_atoms)[:-1]])
+        out = np.repeat(v[first], self.A)
+        out[self.node_index] = v
+        return out
+
+
+def _is_mixed(batch) -> bool:
+    """True for the two things split_graph_batch refuses and split_species_batch takes: molecules of different size, or equally
+    sized molecules that give one atom pair different edge types.  Anything else, malformed batches included, is split_graph_batch's
+    to accept or to refuse with its own message."""
+    bidx = C.to_numpy(batch.batch, np.int64)
+    N = bidx.size
+    if N == 0 or bidx.min() < 0:
+        return False
+    B = int(bidx.max()) + 1
+    if N % B or not np.array_equal(bidx, np.repeat(np.arange(B), N // B)):
+        return True                                            # sizes differ (or the order is wrong: refused below)
+    A = N // B
+    ei = C.to_numpy(batch.edge_index, np.int64)
+    et = C.to_numpy(batch.edge_type, np.int64)
+    if ei.ndim != 2 or ei.shape[0] != 2 or ei.shape[1] != et.size or not ei.size or ei.min() < 0 or ei.max() >= N:
+        return False
+    if (ei[0] // A != ei[1] // A).any() or et.min() < 0 or et.max() > 3:
+        return False
+    pair = (ei[0] % A) * A + ei[1] % A
+    seen = np.stack([np.bincount(pair[et == t], minlength=A * A) > 0 for t in range(4)])
+    return bool((seen.sum(axis=0) > 1).any())
+
+
+def split_species_batch(batch, atom_key: str) -> SpeciesBatch:
+    """A reference-style batch whose molecules may differ in size, graph and edge types -> SpeciesBatch.
+
+    A batch split_graph_batch accepts takes that path unchanged (n_atoms None).  Otherwise A is the largest molecule, the template
+    the complete directed graph on A atoms sorted by (src, dst) with type 0 (every present edge carries its own type in pair_type),
+    atom_ids = arange(A): the reference's distinguish=True atom features, so every molecule's atoms must be numbered 0 .. n_b - 1
+    and A must not exceed the model's n_types.  bit s of mask[b, d] is set when molecule b has the edge s -> d; pads have no bits."""
+    if not _is_mixed(batch):
+        return SpeciesBatch(*split_graph_batch(batch, atom_key))       # today's path, today's refusals
+    bidx = C.to_numpy(batch.batch, np.int64)
+    N = bidx.size
+    B = int(bidx.max()) + 1
+    n_atoms = np.bincount(bidx, minlength=B)
+    if bidx.min() < 0 or (n_atoms < 1).any() or not np.array_equal(bidx, np.repeat(np.arange(B), n_atoms)):
+        raise ValueError("batch.batch must be molecule-major: 0 .. B - 1 in order, no molecule empty")
+    A = int(n_atoms.max())
+    if A > 32:
+        raise ValueError(f"mixed-species batches need A <= 32 atoms, got {A}")
+    first = np.concatenate([[0], np.cumsum(n_atoms)[:-1]])
+    local = np.arange(N, dtype=np.int64) - first[bidx]
+    atoms = C.to_numpy(getattr(batch, atom_key), np.int64)
+    if atoms.shape != (N,) or (atoms != local).any():
+        raise ValueError("a mixed-species batch needs every molecule's atom ids to be 0 .. n_atoms - 1 (distinguish=True)")
+    ei = C.to_numpy(batch.edge_index, np.int64)
+    et = C.to_numpy(batch.edge_type, np.int64)
+    if ei.ndim != 2 or ei.shape[0] != 2 or ei.shape[1] != et.size:
+        raise ValueError("edge_index must be [2, E] and edge_type [E]")
+    if ei.size and (ei.min() < 0 or ei.max() >= N):
+        raise ValueError("edge_index points outside the batch")
+    mol = bidx[ei[0]]
+    if (bidx[ei[1]] != mol).any():
+        raise ValueError("edges cross molecule boundaries")
+    src, dst = local[ei[0]], local[ei[1]]
+    if (src == dst).any():
+        raise ValueError("self loops are not supported in mixed-species batches")
+    if et.size and (et.min() < 0 or et.max() > 3):
+        raise ValueError("edge types must be in 0..3 (the edge-type embedding has 4 rows, cpainn.py:70)")
+    mask = np.bincount(mol * A + dst, weights=np.ldexp(1.0, src), minlength=B * A).astype(np.uint32).reshape(B, A)
+    if int(np.unpackbits(mask.view(np.uint8)).sum()) != src.size:
+        raise ValueError("a molecule of the batch holds an edge twice (coalesce the graph first)")
+    pair_type = np.zeros((B, A, A), np.uint8)
+    pair_type[mol, src, dst] = et
+    s_all, d_all = np.nonzero(~np.eye(A, dtype=bool))
+    return SpeciesBatch(B, A, s_all.astype(np.int32), d_all.astype(np.int32), np.zeros(s_all.size, np.int32), np.arange(A, dtype=np.int32),
+                        mask, n_atoms.astype(np.int32), pair_type, bidx * A + local)
+
+
 class PaiNNShell:
     """Weights-only stand-in for the reference ``cPaiNN`` modules (subclasses fix the variant)."""
     VARIANT = _W.AMBIENT
@@ -185,10 +309,27 @@ class PaiNNShell:
         eng.set_edge_mask(mask)
         return eng
 
-    def cond_of(self, batch, B, A, on_gpu=False):
-        """[B, A, n_cond] float32 conditioning; a CUDA tensor when `on_gpu` (the batch lives on the GPU), else numpy."""
+    def engine_of(self, sb: SpeciesBatch) -> _engine.PainnEngine:
+        """The engine of a split_species_batch result with its per-molecule graph state set (a uniform batch: engine_with_mask)."""
+        if sb.n_atoms is None:
+            return self.engine_with_mask(sb.A, sb.src, sb.dst, sb.etype, sb.atom_ids, sb.mask)
+        if sb.A > self.n_types:
+            raise ValueError(f"the largest molecule has {sb.A} atoms but the model embeds n_types = {self.n_types} atom ids")
+        eng = self.engine_for(sb.A, sb.src, sb.dst, sb.etype, sb.atom_ids)
+        eng.set_molecules(sb.n_atoms, sb.mask, sb.pair_type)
+        return eng
+
+    def cond_of(self, batch, B, A, on_gpu=False, sb=None):
+        """[B, A, n_cond] float32 conditioning; a CUDA tensor when `on_gpu` (the batch lives on the GPU), else numpy.  sb: the
+        batch's SpeciesBatch when its molecules differ in size (pads get 0)."""
         if not self.COND_KEYS:
             return None
+        if sb is not None and sb.n_atoms is not None:
+            cols = [sb.pad(getattr(batch, k), 1) for k in self.COND_KEYS]
+            if on_gpu:
+                import torch
+                return torch.cat(cols, dim=-1).contiguous()
+            return np.ascontiguousarray(np.concatenate(cols, axis=-1))
         if on_gpu:
             import torch
             cols = [getattr(batch, k).detach().to(torch.float32).reshape(B, A) for k in self.COND_KEYS]
@@ -199,11 +340,12 @@ class PaiNNShell:
     def forward(self, batch):
         """Evaluates the drift at batch.x, time batch.t (per node: one value for the call, or one value per molecule) and writes
         batch.output [N,3] like the reference."""
-        B, A, src, dst, ety, ids, mask = split_graph_batch(batch, self.ATOM_KEY)
-        x = C.as_f32(batch.x, (B, A, 3))                  # a CUDA batch is evaluated in place, no host round trip
-        t = molecule_times(batch.t, B, A, x)
-        out = self.engine_with_mask(A, src, dst, ety, ids, mask).drift(x, t, self.cond_of(batch, B, A, C.is_cuda(x)))
-        batch.output = C.like(out.reshape(B * A, 3), batch.x)
+        sb = split_species_batch(batch, self.ATOM_KEY)
+        B, A = sb.B, sb.A
+        x = sb.pad(batch.x, 3) if sb.n_atoms is not None else C.as_f32(batch.x, (B, A, 3))      # a CUDA batch is evaluated in place, no host round trip
+        t = molecule_times(sb.molecule_values(batch.t), B, A, x)
+        out = self.engine_of(sb).drift(x, t, self.cond_of(batch, B, A, C.is_cuda(x), sb))
+        batch.output = C.like(sb.unpad(out), batch.x)
         return batch
 
     __call__ = forward
@@ -220,16 +362,17 @@ class ODEWrapperBase:
 
     def _eval(self, batch, x, t, with_div):
         """t: one float, or batch.t-like per-node times (one value per molecule)."""
-        B, A, src, dst, ety, ids, mask = split_graph_batch(batch, self.b.ATOM_KEY)
-        xs = C.as_f32(x, (B, A, 3))
+        sb = split_species_batch(batch, self.b.ATOM_KEY)
+        B, A = sb.B, sb.A
+        xs = sb.pad(x, 3) if sb.n_atoms is not None else C.as_f32(x, (B, A, 3))
         if not isinstance(t, float):
-            t = molecule_times(t, B, A, xs)
-        eng = self.b.engine_with_mask(A, src, dst, ety, ids, mask)
-        cond = self.b.cond_of(batch, B, A, C.is_cuda(xs))
+            t = molecule_times(sb.molecule_values(t), B, A, xs)
+        eng = self.b.engine_of(sb)
+        cond = self.b.cond_of(batch, B, A, C.is_cuda(xs), sb)
         if with_div:
             out, div = eng.drift_div(xs, t, cond)
-            return out.reshape(B * A, 3), div
-        return eng.drift(xs, t, cond).reshape(B * A, 3), None
+            return sb.unpad(out), div
+        return sb.unpad(eng.drift(xs, t, cond)), None
 
     def forward(self, integration_time, states, batch, n_steps=None):
         if n_steps is not None:
@@ -298,29 +441,30 @@ class MoleculeIntegratorBase:
         self.n_steps_per_molecule = eng.step_counts(B) if self.step_control == "trajectory" else None
 
     def _rollout(self, batch, traj_offset=0):
-        B, A, src, dst, ety, ids, mask = split_graph_batch(batch, self.b.ATOM_KEY)
-        x0 = C.as_f32(batch.x0, (B, A, 3))               # CUDA batches stay in HBM: data_ptr() in, CUDA tensors out
+        sb = split_species_batch(batch, self.b.ATOM_KEY)
+        B, A = sb.B, sb.A
+        x0 = sb.pad(batch.x0, 3) if sb.n_atoms is not None else C.as_f32(batch.x0, (B, A, 3))      # CUDA batches stay in HBM: data_ptr() in, CUDA tensors out
         gpu = C.is_cuda(x0)
         # without dlogp the reference always integrates on linspace(start, end) (integrators.py:54-55), reverse_ode or not
         grid = _engine.time_grid(self.start, self.end, self.n_step)
-        eng = self.b.engine_with_mask(A, src, dst, ety, ids, mask)
+        eng = self.b.engine_of(sb)
         if self.return_dlogp:
             if self.reverse_ode:
                 grid = _engine.time_grid(self.end, self.start, self.n_step)
             kw = dict(scheme="euler" if self.method == "em" else self.method, save_every=self.save_every, div_scale=self.DIV_SCALE,
                       out_scale=self.SCALE_DLOGP, reverse_ode=self.reverse_ode, rtol=self.rtol, atol=self.atol, step_control=self.step_control)
-            cond = self.b.cond_of(batch, B, A, gpu)
+            cond = self.b.cond_of(batch, B, A, gpu, sb)
             if self.divergence == "hutchinson":
                 path, dl, nfe = eng.rollout_dlogp_est(x0, cond, grid, n_probes=self.n_probes, probe_seed=self.probe_seed,
                                                       traj_offset=traj_offset, **kw)
             else:
                 path, dl, nfe = eng.rollout_dlogp(x0, cond, grid, **kw)
             self._record_counts(eng, B)
-            return C.like(path.reshape(path.shape[0], B * A, 3), batch.x0), C.like(dl, batch.x0), nfe
-        path, nfe = eng.rollout(x0, self.b.cond_of(batch, B, A, gpu), grid, scheme=self.method, save_every=self.save_every, eps=self.eps,
+            return C.like(sb.unpad(path), batch.x0), C.like(dl, batch.x0), nfe
+        path, nfe = eng.rollout(x0, self.b.cond_of(batch, B, A, gpu, sb), grid, scheme=self.method, save_every=self.save_every, eps=self.eps,
                                 seed=self.seed, traj_offset=traj_offset, com_free_noise=self.com_free_noise, rtol=self.rtol, atol=self.atol,
                                 step_control=self.step_control)
         self._record_counts(eng, B)
-        xts = C.like(path.reshape(path.shape[0], B * A, 3), batch.x0)
+        xts = C.like(sb.unpad(path), batch.x0)
         dlogp = batch.x0.new_zeros(B) if gpu else C.like(np.zeros(B, np.float32) * self.SCALE_DLOGP, batch.x0)      # reference: zeros(batch_size) (* 1e2 in ambient)
         return xts, dlogp, nfe
