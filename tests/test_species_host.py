@@ -158,6 +158,27 @@ def test_engine_set_molecules_checks_shapes_before_the_library():
         eng.set_molecules([2, 4])
 
 
+# ------------------------------------------------------------------------------------------------------------ the edge-size problem
+def test_edge_problem_of_the_gpu_suite_holds_on_its_own():
+    """What tests/test_gpu_species_edges.py relies on, checked without a GPU: five kinds whose 3n straddle lane 64; the one-atom kind has no
+    edge and its fp64 drift, tangent and divergence are exactly 0 (refs() asserts it); pads carry no mask bit; the restatement of
+    per-trajectory dopri5 with dlogp finishes on it (zero drift: the 1e-6 initial step, tenfold growth) with other attempts than a
+    kind that moves; the chunk budget's bounds."""
+    import test_gpu_species_edges as E
+    ks, _ = E.kinds()
+    assert [3 * q.n for q in ks] == [3, 6, 63, 66, 75] and not ks[0].on.any()
+    assert all((q.on == q.on.T).all() and (q.pt == q.pt.T).all() for q in ks)      # symmetric: the pair layout is eligible
+    for what in ("drift", "jvp", "div"):
+        assert len(E.refs(what)) == 5
+    m = E.mix(261, "far")
+    assert (m.x[~m.real] == -1e4).all() and (m.mask[~m.real] == 0).all() and (m.mask >> m.n_atoms[:, None].astype(np.uint32) == 0).all()
+    assert (np.bincount(m.kind) >= 52).all() and m.kind[256] != m.kind[0]
+    path0, dl0, att0 = E.traj_ref(0, True, False)
+    assert (path0 == 0).all() and (dl0 == 0).all() and att0 == 7                   # 44 evaluations
+    assert E.traj_ref(1, True, False)[2] != att0
+    assert 0.001 <= float(E._budget_gb(4)) < float(E._budget_gb(75))
+
+
 # ------------------------------------------------------------------------------------------------------------ code objects
 @pytest.fixture(scope="module")
 def code_objects():
