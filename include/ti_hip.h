@@ -302,6 +302,52 @@ int ti_painn_set_edge_mask(ti_handle* h, const uint32_t* mask, int64_t B, int me
  *     would get alone); pad components are 0.  Exact divergence: the 3 n_atoms[b] real unit seeds are summed, pads are skipped.
  *   With every n_atoms[b] == A and pair_type == NULL every entry point returns the bits ti_painn_set_edge_mask(mask) returns. */
 int ti_painn_set_molecules(ti_handle* h, const int32_t* n_atoms, const uint32_t* mask, const uint8_t* pair_type, int64_t B, int mem);
+/* ---- observables: per-molecule collective variables (CVs), importance weights, weighted histograms ----------------------------
+ * No reference FFI counterpart; what they compute is the reference's analysis layer: internal coordinates
+ * (mdqm9/analysis/utils/mol_geometry.py compute_distance / compute_angle / compute_torsion, histogrammed by z_matrix.py:43-45 and
+ * results_00031.py:140-149), the effective sample size (mdqm9/analysis/utils/ess.py:32-35) and the adw free-energy profile.
+ * All of them run on the handle's stream and device, take a painn or an adw handle, compute in fp64 from the fp32 inputs, use no
+ * atomics and repeat bit for bit; a per-molecule value does not depend on the other molecules of the batch, the batch-wide sums
+ * (weights, histograms) are taken in an order fixed by B.  Arguments are validated before any device work.
+ *
+ * A CV descriptor is five int32 (kind, i, j, k, l); unused slots are ignored.  x [B,A,3] (painn) or [B,d] (adw):
+ *   RMSD           minimal RMSD over PROPER rotations of molecule b to ref [A,3] over the atoms a with select[a] != 0 (select == NULL:
+ *                  all), both sets centred over those atoms: sqrt(max(|x|^2 + |ref|^2 - 2 lambda, 0) / count), lambda the largest
+ *                  eigenvalue of Horn's 4x4 quaternion matrix of the covariance (fixed-sweep Jacobi; rank-deficient covariances --
+ *                  one or two atoms, collinear or planar sets -- included).  A mirror image does not give 0.  No selected atom: NaN.
+ *   DIST(i,j)      |x_j - x_i|
+ *   ANGLE(i,j,k)   the angle at j between j->i and j->k, radians in [0, pi]
+ *   TORSION(i,j,k,l)  atan2(|b2| b1.(b2 x b3), (b1 x b2).(b2 x b3)), b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k; radians in (-pi, pi]
+ *   COORD(c)       adw handles only, and the only kind they take: component c of a particle, 0 <= c < d
+ * Mixed-species batches (ti_painn_set_molecules in force, B equal to its B): RMSD runs over the real selected atoms of molecule b;
+ * a descriptor that names a pad atom of molecule b yields NaN for that molecule; pad coordinates are never read.
+ * TI_E_ARG: an index outside 0..A-1 (COORD: 0..d-1), an unknown kind, a geometric kind on an adw handle or COORD on a painn handle,
+ * RMSD without ref, K < 1, a NULL buffer. */
+enum { TI_OBS_RMSD = 0, TI_OBS_DIST = 1, TI_OBS_ANGLE = 2, TI_OBS_TORSION = 3, TI_OBS_COORD = 4 };
+/* desc [K][5], ref [A,3] fp32 and select [A] int32 (both may be NULL): host memory.  x and out_cv [B,K] fp32: [host|device] by mem. */
+int ti_obs_cv(ti_handle* h, const int32_t* desc, int32_t K, const float* ref, const int32_t* select, const float* x, int64_t B,
+              float* out_cv, int mem);
+/* Importance weights of logw [B] fp32 [host|device] (e.g. -dlogp plus an energy term): m = max logw, w = exp(logw - m), two-pass
+ * fixed-order fp64 sums; out_w [B] fp32 [host|device] = w / sum w (may be NULL); *out_ess (host) = (sum w)^2 / sum w^2, calc_ESS of
+ * the reference.  A non-finite entry: TI_E_NAN, the message names the first such index. */
+int ti_obs_weights(ti_handle* h, const float* logw, int64_t B, float* out_w, double* out_ess, int mem);
+/* Weighted histogram of values[i * stride], i < B (fp32 [host|device]; a column of a [B,K] CV array has stride K), over n_bins equal
+ * bins on [lo, hi), 1 <= n_bins <= 256, edges e_k = lo + ((hi - lo) k) / n_bins in fp64; a value equal to an interior edge goes to
+ * the upper bin.  Weights: the normalised exp(logw) of ti_obs_weights (same refusal), or 1 / B with logw == NULL.  out_hist
+ * [n_bins] and out_tails [3] (host, double): the weight per bin; the weight below lo, at or above hi, and of non-finite values (which
+ * are not binned) -- sum(out_hist) + sum(out_tails) = 1 to round-off.  n_bins outside 1..256 or hi <= lo: TI_E_ARG. */
+int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* logw, int64_t B, int32_t n_bins, double lo, double hi,
+                double* out_hist, double* out_tails, int mem);
+/* Observer: with one attached, every rollout entry point (ti_painn_rollout, _dlogp, _dlogp_est, ti_adw_rollout, _dlogp) also
+ * evaluates the K CVs on the state at the grid points i with i % every == 0 and at the last one -- ti_rollout_rows(n_step, every)
+ * rows, whatever save_every is -- and writes them to out_cv [rows, B, K] fp32 ([host|device] by mem; the caller sizes it for the
+ * rollouts that follow and keeps it alive).  Where a path row is written at the same grid point, the CVs are those of exactly
+ * that row (dopri5: of the dense output evaluated there).  desc, ref and select as in ti_obs_cv, copied into the handle; every >= 0
+ * (0: the last grid point only).  desc == NULL detaches.  Path, dlogp and n_fevals of a rollout do not depend on the observer, and
+ * without one a rollout takes exactly the launches it took before.  TI_SCHEME_DOPRI5_TRAJ writes its rows per trajectory inside a
+ * kernel: with an observer attached it returns TI_E_UNSUPPORTED. */
+int ti_obs_set_observer(ti_handle* h, const int32_t* desc, int32_t K, const float* ref, const int32_t* select, int32_t every,
+                        float* out_cv, int mem);
 /* Pre-size the HBM workspace for batches up to B trajectories (otherwise grown on demand). */
 int ti_reserve(ti_handle* h, int64_t B);
 /* Live kernel timing with HIP events on the handle's stream (bench.py roofline leg). */

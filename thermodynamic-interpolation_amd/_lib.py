@@ -33,7 +33,10 @@ ABI_SYMBOLS = [
     "ti_painn_drift_tv", "ti_painn_drift_div_tv", "ti_adw_drift_tv", "ti_rollout_step_counts",
     "ti_painn_drift_div_est", "ti_painn_drift_div_est_tv", "ti_painn_rollout_dlogp_est",
     "ti_adw_create_nd", "ti_painn_set_edge_mask", "ti_painn_set_molecules",
+    "ti_obs_cv", "ti_obs_weights", "ti_obs_hist", "ti_obs_set_observer",
 ]
+# CV descriptor kinds (TI_OBS_*)
+OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
 
 
 class PainnDesc(C.Structure):
@@ -130,6 +133,11 @@ def lib():
                                              C.c_int, vp, vp, C.POINTER(C.c_int64)]
     L.ti_painn_set_edge_mask.argtypes = [vp, vp, C.c_int64, C.c_int]
     L.ti_painn_set_molecules.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int]
+    L.ti_obs_cv.argtypes = [vp, ip, C.c_int32, fp, ip, vp, C.c_int64, vp, C.c_int]
+    L.ti_obs_weights.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_double), C.c_int]
+    L.ti_obs_hist.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.c_int]
+    L.ti_obs_set_observer.argtypes = [vp, ip, C.c_int32, fp, ip, C.c_int32, vp, C.c_int]
     _lib = L
     return L
 

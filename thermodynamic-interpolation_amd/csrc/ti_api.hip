@@ -222,6 +222,13 @@ struct ti_handle {
     DevBuf<float> ax, ab1, ab2, axt, aemb_u, abeta0_u, abeta1_u, adl, ad1, ad2; DevBuf<int32_t> aidx;
     DevBuf<float> abeta0_r, abeta1_r, aemb_r, atv;                  // per-row conditioning / beta embedding / times (per-row t)
 
+    // ---- observables (ti_obs_*): descriptor sets as validated and uploaded by obs_upload -- [0] of the last ti_obs_cv call, [1] the
+    // attached observer (K == 0: none) with its row stride `every` and the caller's out_cv; staging for host buffers; fp64 scratch:
+    // red = (max, first bad index, sum w, sum w^2, hist [n_bins + 3]), part = per-block partials
+    struct ObsSet { int K = 0; bool has_ref = false, has_sel = false; DevBuf<int32_t> desc, sel; DevBuf<float> ref; } obs[2];
+    int obs_every = 0, obs_mem = TI_MEM_HOST; float* obs_out = nullptr;
+    DevBuf<float> obs_x, obs_cv, obs_val, obs_logw, obs_w; DevBuf<double> obs_red, obs_part;
+
     ~ti_handle()
     {
         for (auto& v2 : ev) for (auto& pr : v2) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -1060,6 +1067,73 @@ struct Ragged { const int32_t* n = nullptr; int A = 0; size_t n_real = 0; };
 Ragged ragged_of(const ti_handle* h) { return h->ragged ? Ragged{h->natoms_dev.p, h->d.n_atoms, (size_t)h->n_real * 3} : Ragged{}; }
 
 // drift(x_dev, t, out_b, out_div) evaluates the drift (and the divergence if out_div != NULL); state arrays have n floats
+// ------------------------------------------------------------------------------------------------ observables
+int obs_floats_per_traj(const ti_handle* h) { return h->kind == 0 ? 3 * h->d.n_atoms : h->a_dim; }
+
+// Validates desc [K][5] against the handle (before any device work) and uploads it with ref / select into set `which`.
+int obs_upload(ti_handle* h, int which, const int32_t* desc, int K, const float* ref, const int32_t* select)
+{
+    if (K < 1) return fail(TI_E_ARG, "K must be >= 1");
+    const int A = h->kind == 0 ? h->d.n_atoms : 1, dim = h->a_dim;
+    bool rmsd = false;
+    for (int k = 0; k < K; ++k) {
+        const int32_t* d = desc + 5 * k;
+        const int kind = d[0];
+        if (kind < TI_OBS_RMSD || kind > TI_OBS_COORD) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": unknown kind " + std::to_string(kind));
+        if (h->kind == 1) {
+            if (kind != TI_OBS_COORD) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": an adw handle takes COORD(c) only");
+            if (d[1] < 0 || d[1] >= dim) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": component outside 0.." + std::to_string(dim - 1));
+            continue;
+        }
+        if (kind == TI_OBS_COORD) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": COORD(c) is for adw handles");
+        if (kind == TI_OBS_RMSD) { rmsd = true; continue; }
+        const int na = kind == TI_OBS_DIST ? 2 : kind == TI_OBS_ANGLE ? 3 : 4;
+        for (int j = 0; j < na; ++j)
+            if (d[1 + j] < 0 || d[1 + j] >= A) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": atom index outside 0.." + std::to_string(A - 1));
+    }
+    if (rmsd && !ref) return fail(TI_E_ARG, "an RMSD descriptor needs ref");
+    set_device(h);
+    ti_handle::ObsSet& o = h->obs[which];
+    o.K = 0;
+    o.desc.upload(std::vector<int32_t>(desc, desc + 5 * (size_t)K));
+    o.has_ref = rmsd; o.has_sel = rmsd && select;
+    if (o.has_ref) o.ref.upload(std::vector<float>(ref, ref + 3 * (size_t)A));
+    if (o.has_sel) o.sel.upload(std::vector<int32_t>(select, select + A));
+    o.K = K;
+    return TI_OK;
+}
+
+// cv_dev [B][K] = the CVs of set `which` on x_dev [B][m]; enqueued on the handle's stream
+void obs_cv_dev(ti_handle* h, int which, const float* x_dev, long long B, float* cv_dev)
+{
+    const ti_handle::ObsSet& o = h->obs[which];
+    if (h->kind == 0 && h->emask_B > 0 && B != h->emask_B)
+        throw std::invalid_argument("the molecule state in force is for " + std::to_string(h->emask_B) + " molecules, the call has " + std::to_string(B));
+    ObsCvParams p{};
+    p.x = x_dev; p.B = B; p.A = h->kind == 0 ? h->d.n_atoms : 1; p.m = obs_floats_per_traj(h); p.K = o.K;
+    p.desc = o.desc.p; p.ref = o.has_ref ? o.ref.p : nullptr; p.sel = o.has_sel ? o.sel.p : nullptr;
+    p.n_atoms = h->kind == 0 && h->ragged ? h->natoms_dev.p : nullptr;
+    p.cv = cv_dev;
+    HIP_CHECK(launch_obs_cv(p, h->stream));
+}
+
+// The attached observer of a rollout over B trajectories: at(i, x) writes the CV row of grid point i when the observer wants one.
+struct Observer {
+    ti_handle* h; long long B; int N; int64_t row = 0;
+    bool on() const { return h->obs[1].K > 0; }
+    bool wants(int i) const { return on() && (h->obs_every > 0 ? (i % h->obs_every == 0 || i == N - 1) : i == N - 1); }
+    void at(int i, const float* x_dev)
+    {
+        if (!wants(i)) return;
+        const size_t nk = (size_t)B * h->obs[1].K;
+        float* dst = h->obs_out + (size_t)(row++) * nk;
+        if (h->obs_mem == TI_MEM_DEVICE) { obs_cv_dev(h, 1, x_dev, B, dst); return; }
+        if (h->obs_cv.n < nk) h->obs_cv.alloc(nk);
+        obs_cv_dev(h, 1, x_dev, B, h->obs_cv.p);
+        HIP_CHECK(hipMemcpyAsync(dst, h->obs_cv.p, nk * sizeof(float), hipMemcpyDeviceToHost, h->stream));     // pageable: done on return
+    }
+};
+
 template <typename Drift>
 int rollout_common(ti_handle* h, const ti_rollout_desc* rd, float* x, float* b1, float* b2, float* xt, size_t n, long long B, int comps,
                    int atoms_for_com, float* out_path, int64_t* n_fevals, Drift&& drift, DlogpAux aux = DlogpAux(), Ragged rg = Ragged())
@@ -1076,7 +1150,9 @@ int rollout_common(ti_handle* h, const ti_rollout_desc* rd, float* x, float* b1,
         }
         HIP_CHECK(hipMemcpyAsync(out_path + (size_t)(row++) * n, x, n * sizeof(float), out_kind, st));
     };
+    Observer obs{h, B, rd->n_step};
     if (rd->save_every > 0) save();
+    if (obs.on()) obs.at(0, x);
     for (int k = 0; k < rd->n_step - 1; ++k) {
         const float dt = rd->t_grid[k + 1] - rd->t_grid[k];
         drift(x, rd->t_grid[k], b1, aux.d1); ++fe;
@@ -1098,6 +1174,7 @@ int rollout_common(ti_handle* h, const ti_rollout_desc* rd, float* x, float* b1,
         }
         const int step = k + 1;
         if (rd->save_every > 0 && (step % rd->save_every == 0 || step == rd->n_step - 1)) save();
+        if (obs.on()) obs.at(step, x);
     }
     if (rd->save_every <= 0) save();
     HIP_CHECK(hipMemsetAsync(h->nanflag.p, 0, sizeof(int), st));
@@ -1178,7 +1255,9 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
     double* red = h->rk_red.p;
     auto fetch = [&]() { double v = 0; HIP_CHECK(hipMemcpyAsync(&v, red + RED_PARTIALS, sizeof(double), hipMemcpyDeviceToHost, st)); HIP_CHECK(hipStreamSynchronize(st)); return v; };
     const float rtol = rd->rtol, atol = rd->atol;
+    Observer obs{h, (long long)(n / (size_t)obs_floats_per_traj(h)), N};
     if (wants_row(0)) save_from(y);
+    if (obs.on()) obs.at(0, y[0]);
 
     if (rd->scheme == TI_SCHEME_MIDPOINT || rd->scheme == TI_SCHEME_RK4) {
         // FixedGridODESolver with step_size = None: one step per grid interval (solvers.py; fixed_grid.py Midpoint / RK4)
@@ -1202,6 +1281,7 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
                 for (int s2 = 0; s2 < nseg; ++s2) HIP_CHECK(launch_rk_combo(y[s2], y[s2], comb(s2, 4, cs, dt), (long long)sn[s2], st));
             }
             if (wants_row(i + 1)) save_from(y);
+            if (obs.on()) obs.at(i + 1, y[0]);
         }
     } else {
         // ---- dopri5: RKAdaptiveStepsizeODESolver (rk_common.py) ----
@@ -1270,6 +1350,11 @@ int rollout_rk(ti_handle* h, const ti_rollout_desc* rd, float* x, size_t n, floa
                 for (int s2 = 0; s2 < nseg; ++s2) HIP_CHECK(launch_interp_eval(ytmp[s2], coef[s2], xrel, (long long)sn[s2], st));
                 if (rg.n) HIP_CHECK(launch_copy_pads(ytmp[0], y[0], rg.n, (long long)(n / (3 * rg.A)), rg.A, 3, st));      // pads: the state, not its fit
                 save_from(ytmp);
+                if (obs.on()) obs.at(i, ytmp[0]);
+            } else if (obs.wants(i)) {                                       // an observer row where no path row is written: x only
+                const float xrel = (float)((next_t - t0) / (t1 - t0));
+                HIP_CHECK(launch_interp_eval(ytmp[0], coef[0], xrel, (long long)sn[0], st));
+                obs.at(i, ytmp[0]);
             }
         }
     }
@@ -1582,6 +1667,8 @@ int ti_painn_rollout(ti_handle* h, const ti_rollout_desc* rd, const float* x0, c
 {
     if (int rc = check_rollout_desc(rd)) return rc;          // first: needs no handle
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (rd->scheme == TI_SCHEME_DOPRI5_TRAJ && h->obs[1].K > 0)
+        return fail(TI_E_UNSUPPORTED, "TI_SCHEME_DOPRI5_TRAJ writes its rows per trajectory inside a kernel: detach the observer (ti_obs_set_observer)");
     if (B < 0 || (B > 0 && (!x0 || !out_path || (h->ncond > 0 && !cond)))) return fail(TI_E_ARG, "NULL buffer");
     if (B == 0) { if (n_fevals) *n_fevals = 0; return TI_OK; }
     return guarded([&]() -> int {
@@ -1704,6 +1791,8 @@ static int painn_rollout_dlogp_impl(ti_handle* h, const ti_rollout_desc* rd, int
     if (h->d.precision == TI_PREC_F16) return fail(TI_E_UNSUPPORTED, "the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)");
     if (int rc = check_rollout_desc(rd)) return rc;
     if (rd->scheme == TI_SCHEME_EM) return fail(TI_E_UNSUPPORTED, "dlogp is defined for the deterministic schemes only (EULER, HEUN)");
+    if (rd->scheme == TI_SCHEME_DOPRI5_TRAJ && h->obs[1].K > 0)
+        return fail(TI_E_UNSUPPORTED, "TI_SCHEME_DOPRI5_TRAJ writes its rows per trajectory inside a kernel: detach the observer (ti_obs_set_observer)");
     if (B < 0 || (B > 0 && (!x0 || !out_path || !out_dlogp || (h->ncond > 0 && !cond)))) return fail(TI_E_ARG, "NULL buffer");
     if (B == 0) { if (n_fevals) *n_fevals = 0; return TI_OK; }
     return guarded([&]() -> int {
@@ -2041,6 +2130,8 @@ static int adw_rollout_impl(ti_handle* h, const ti_rollout_desc* rd, const float
 {
     if (!h || h->kind != 1) return fail(TI_E_ARG, "not an adw handle");
     if (int rc = check_rollout_desc(rd)) return rc;
+    if (rd->scheme == TI_SCHEME_DOPRI5_TRAJ && h->obs[1].K > 0)
+        return fail(TI_E_UNSUPPORTED, "TI_SCHEME_DOPRI5_TRAJ writes its rows per trajectory inside a kernel: detach the observer (ti_obs_set_observer)");
     if (B < 0 || (B > 0 && (!x0 || !beta0 || !beta1 || !out_path))) return fail(TI_E_ARG, "NULL buffer");
     if (out_dlogp && rd->scheme == TI_SCHEME_EM && rd->eps > 0.f)
         return fail(TI_E_UNSUPPORTED, "dlogp is defined for a deterministic flow: EM needs eps = 0");
@@ -2080,6 +2171,134 @@ int ti_adw_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float* x
 {
     if (!out_dlogp) return fail(TI_E_ARG, "out_dlogp is NULL");
     return adw_rollout_impl(h, rd, x0, beta0, beta1, B, out_path, out_dlogp, n_fevals);
+}
+
+// ---------------------------------------------------------------------------------------------------- observables
+int ti_obs_cv(ti_handle* h, const int32_t* desc, int32_t K, const float* ref, const int32_t* select, const float* x, int64_t B,
+              float* out_cv, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (!desc) return fail(TI_E_ARG, "desc is NULL");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 0 || (B > 0 && (!x || !out_cv))) return fail(TI_E_ARG, "NULL buffer");
+    return guarded([&]() -> int {
+        if (int rc = obs_upload(h, 0, desc, K, ref, select)) return rc;
+        if (B == 0) return TI_OK;
+        const size_t n = (size_t)B * obs_floats_per_traj(h), nk = (size_t)B * K;
+        const float* xd = x; float* od = out_cv;
+        if (mem == TI_MEM_HOST) {
+            if (h->obs_x.n < n) h->obs_x.alloc(n);
+            if (h->obs_cv.n < nk) h->obs_cv.alloc(nk);
+            HIP_CHECK(hipMemcpyAsync(h->obs_x.p, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            xd = h->obs_x.p; od = h->obs_cv.p;
+        }
+        obs_cv_dev(h, 0, xd, B, od);
+        if (mem == TI_MEM_HOST) HIP_CHECK(hipMemcpyAsync(out_cv, od, nk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return TI_OK;
+    });
+}
+
+// (max, first bad index, sum w, sum w^2) of logw_dev into h->obs_red[0..3] and `norm`; TI_E_NAN on a non-finite entry
+static int obs_norm_dev(ti_handle* h, const float* logw_dev, long long B, double norm[4])
+{
+    hipStream_t st = h->stream;
+    if (h->obs_red.n < 4 + 259) h->obs_red.alloc(4 + 259);
+    if (h->obs_part.n < (size_t)OBS_MAX_BLOCKS * 259) h->obs_part.alloc((size_t)OBS_MAX_BLOCKS * 259);
+    HIP_CHECK(launch_obs_logw_max(h->obs_red.p, h->obs_part.p, logw_dev, B, st));
+    HIP_CHECK(hipMemcpyAsync(norm, h->obs_red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (norm[1] < (double)B) return fail(TI_E_NAN, "non-finite logw at index " + std::to_string((long long)norm[1]));
+    HIP_CHECK(launch_obs_logw_sums(h->obs_red.p + 2, h->obs_part.p, logw_dev, h->obs_red.p, B, st));
+    HIP_CHECK(hipMemcpyAsync(norm + 2, h->obs_red.p + 2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    // the kernels that follow read (max, sum w) as one pair
+    HIP_CHECK(hipMemcpyAsync(h->obs_red.p + 1, h->obs_red.p + 2, sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return TI_OK;
+}
+
+int ti_obs_weights(ti_handle* h, const float* logw, int64_t B, float* out_w, double* out_ess, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!logw || !out_ess) return fail(TI_E_ARG, "NULL buffer");
+    return guarded([&]() -> int {
+        set_device(h);
+        const float* ld = logw; float* wd = out_w;
+        if (mem == TI_MEM_HOST) {
+            if (h->obs_logw.n < (size_t)B) h->obs_logw.alloc(B);
+            HIP_CHECK(hipMemcpyAsync(h->obs_logw.p, logw, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            ld = h->obs_logw.p;
+            if (out_w) { if (h->obs_w.n < (size_t)B) h->obs_w.alloc(B); wd = h->obs_w.p; }
+        }
+        double norm[4];
+        if (int rc = obs_norm_dev(h, ld, B, norm)) return rc;
+        *out_ess = norm[2] * norm[2] / norm[3];
+        if (out_w) {
+            HIP_CHECK(launch_obs_weights(wd, ld, h->obs_red.p, B, h->stream));
+            if (mem == TI_MEM_HOST) HIP_CHECK(hipMemcpyAsync(out_w, wd, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        return TI_OK;
+    });
+}
+
+int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* logw, int64_t B, int32_t n_bins, double lo, double hi,
+                double* out_hist, double* out_tails, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (n_bins < 1 || n_bins > 256) return fail(TI_E_ARG, "n_bins must be in 1..256");
+    if (!(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi)) return fail(TI_E_ARG, "the range needs finite lo < hi");
+    if (B < 1 || stride < 1) return fail(TI_E_ARG, "B < 1 or stride < 1");
+    if (!values || !out_hist || !out_tails) return fail(TI_E_ARG, "NULL buffer");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const float *vd = values, *ld = logw;
+        long long sd = stride;
+        if (mem == TI_MEM_HOST) {                      // the column only: B floats, not B * stride
+            if (h->obs_val.n < (size_t)B) h->obs_val.alloc(B);
+            std::vector<float> col((size_t)B);
+            for (int64_t i = 0; i < B; ++i) col[i] = values[i * stride];
+            HIP_CHECK(hipMemcpy(h->obs_val.p, col.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice));
+            vd = h->obs_val.p; sd = 1;
+            if (logw) {
+                if (h->obs_logw.n < (size_t)B) h->obs_logw.alloc(B);
+                HIP_CHECK(hipMemcpyAsync(h->obs_logw.p, logw, (size_t)B * sizeof(float), hipMemcpyHostToDevice, st));
+                ld = h->obs_logw.p;
+            }
+        }
+        double norm[4];
+        if (logw) { if (int rc = obs_norm_dev(h, ld, B, norm)) return rc; }
+        else {
+            if (h->obs_red.n < 4 + 259) h->obs_red.alloc(4 + 259);
+            if (h->obs_part.n < (size_t)OBS_MAX_BLOCKS * 259) h->obs_part.alloc((size_t)OBS_MAX_BLOCKS * 259);
+        }
+        HIP_CHECK(launch_obs_whist(h->obs_red.p + 4, h->obs_part.p, vd, sd, ld, h->obs_red.p, B, n_bins, lo, hi, st));
+        std::vector<double> out((size_t)n_bins + 3);
+        HIP_CHECK(hipMemcpyAsync(out.data(), h->obs_red.p + 4, out.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::copy(out.begin(), out.begin() + n_bins, out_hist);
+        std::copy(out.begin() + n_bins, out.end(), out_tails);
+        return TI_OK;
+    });
+}
+
+int ti_obs_set_observer(ti_handle* h, const int32_t* desc, int32_t K, const float* ref, const int32_t* select, int32_t every,
+                        float* out_cv, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (!desc) { h->obs[1].K = 0; h->obs_out = nullptr; return TI_OK; }
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (every < 0) return fail(TI_E_ARG, "every must be >= 0");
+    if (!out_cv) return fail(TI_E_ARG, "out_cv is NULL");
+    return guarded([&]() -> int {
+        if (int rc = obs_upload(h, 1, desc, K, ref, select)) return rc;
+        h->obs_every = every; h->obs_mem = mem; h->obs_out = out_cv;
+        return TI_OK;
+    });
 }
 
 // --------------------------------------------------------------------------------------------------------- shared

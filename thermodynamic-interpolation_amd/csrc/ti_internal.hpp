@@ -302,4 +302,31 @@ hipError_t launch_traj_stage_ragged(const TrajRkParams& p, const float* c, int n
                                     const int32_t* n_atoms, hipStream_t st);
 hipError_t launch_traj_advance_ragged(const TrajRkParams& p, const float* c_error, const float* c_mid, const int32_t* n_atoms, hipStream_t st);
 
+// ---- observables (obs_kernels.hip; include/ti_hip.h ti_obs_*)
+struct ObsCvParams {
+    const float* x;                         // [B][m] floats: m = 3A (molecules) or the adw dimension
+    long long B; int A, m, K;
+    const int32_t* desc;                    // [K][5] (kind, i, j, k, l), validated on the host
+    const float* ref;                       // [A][3] RMSD reference frame (NULL without an RMSD descriptor)
+    const int32_t* sel;                     // [A] 0 / 1 RMSD selection, NULL: every atom
+    const int32_t* n_atoms;                 // [B] real atoms per molecule (mixed species), NULL: A
+    float* cv;                              // [B][K]
+};
+// Launch shape of the batch-wide sums: obs_blocks(B) blocks of 256 threads walk the B values grid-stride.  Few blocks on purpose:
+// the per-bin wave sums make a histogram cost O(bins present) shuffles per 64 values whatever the grid, the second pass stays one
+// short loop per column, and at the product's batch sizes (<= 1e5) these calls are bound by their launches, not by their width.
+constexpr int OBS_MAX_BLOCKS = 8;
+int obs_blocks(long long B);
+hipError_t launch_obs_cv(const ObsCvParams& p, hipStream_t st);
+// out[0] = largest finite logw (-inf: none), out[1] = smallest index of a non-finite entry as a double (+inf: none); partial: [OBS_MAX_BLOCKS][2]
+hipError_t launch_obs_logw_max(double* out, double* partial, const float* logw, long long B, hipStream_t st);
+// out[0] = sum w, out[1] = sum w^2, w = exp(logw - *mx)
+hipError_t launch_obs_logw_sums(double* out, double* partial, const float* logw, const double* mx, long long B, hipStream_t st);
+// w[i] = exp(logw[i] - norm[0]) / norm[1]
+hipError_t launch_obs_weights(float* w, const float* logw, const double* norm, long long B, hipStream_t st);
+// out [n_bins + 3]: the histogram of values[i * stride] on [lo, hi) weighted by exp(logw - norm[0]) / norm[1] (logw == NULL: 1 / B),
+// then the weights below lo, at or above hi, and of non-finite values; partial: [OBS_MAX_BLOCKS][n_bins + 3]
+hipError_t launch_obs_whist(double* out, double* partial, const float* values, long long stride, const float* logw, const double* norm, long long B,
+                            int n_bins, double lo, double hi, hipStream_t st);
+
 }  // namespace ti

@@ -11,7 +11,12 @@ name of thermo._common.SUPPORTED works); files are written once per call instead
 'batch'): 'trajectory' gives every molecule / particle its own dopri5 step sizes, so its sample and dlogp equal the reference's at
 batch size 1 whatever ``batch_size`` is.  ``config.divergence`` / ``n_probes`` / ``probe_seed`` (optional, default 'exact' / 1 / 0):
 'hutchinson' estimates dlogp with n_probes Rademacher probes per molecule (MoleculeIntegratorBase); the molecules of successive
-batches then get consecutive trajectory ids, so no two molecules of a run share probes.
+batches then get consecutive trajectory ids, so no two molecules of a run share probes.  ``config.observables`` (optional): a dict
+``{"descriptors": [["rmsd"], ["torsion", 0, 1, 2, 3], ...], "ref": [[x, y, z], ...], "select": [...], "every": k, "bins": n}``
+(observables.py; adw: ``[["coord", 0]]``) writes ``observables_*.npz`` next to the samples file: ``cv`` [rows, B, K], the collective
+variables at the grid points i % every == 0 and at the last one, computed on the GPU during the rollout; ``hist`` [K, bins] and
+``edges`` [K, bins + 1], the histogram of every CV at the end state, weighted by exp(-dlogp) when ``return_dlogp`` is set; ``ess``.
+Without the key exactly the reference's files are written.
 """
 from __future__ import annotations
 
@@ -21,6 +26,7 @@ import os
 
 import numpy as np
 
+from . import observables as _obs
 from .thermo import adw as _adw
 from .thermo import ambient as _amb
 from .thermo import latent as _lat
@@ -46,13 +52,32 @@ def _divergence_kw(config):
                 probe_seed=getattr(config, "probe_seed", 0))
 
 
+def _observe_kw(config):
+    o = getattr(config, "observables", None)
+    if o is None:
+        return {}
+    o = dict(o)
+    o.pop("bins", None)
+    if o.get("ref") is not None:
+        o["ref"] = np.asarray(o["ref"], np.float32)
+    return dict(observe=o)
+
+
+def _write_observables(config, path, cvs, dlogps):
+    """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp)"""
+    cv = np.concatenate([C.to_numpy(c) for c in cvs], axis=1).astype(np.float32)
+    dl = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in dlogps]) if dlogps else None
+    hist, edges, ess = _obs.end_state_summary(np.ascontiguousarray(cv[-1]), dl, bins=int(dict(config.observables).get("bins", 32)))
+    np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess))
+
+
 def sample_ambient(config, b, dataset):
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
                                          save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"),
-                                         **_divergence_kw(config))
-    hutch, traj = integrator.divergence == "hutchinson", 0
+                                         **_divergence_kw(config), **_observe_kw(config))
+    hutch, traj, cvs = integrator.divergence == "hutchinson", 0, []
     latent_noises, latent_dlogps, samples, dlogps, n_fevals = [], [], [], [], 0
     b.eval()
     for batch in dataset.batches(config.batch_size, shuffle=True, seed=config.seed):
@@ -64,7 +89,11 @@ def sample_ambient(config, b, dataset):
         samples.append(_regroup(sample, bidx))
         if config.return_dlogp:
             dlogps.append(C.to_numpy(dlogp)[-1, :])
+        if integrator.observe is not None:
+            cvs.append(integrator.cv)
     name = config.data_save_name
+    if cvs:
+        _write_observables(config, os.path.join(config.data_save_path, f"observables_{name}.npz"), cvs, dlogps)
     np.save(os.path.join(config.data_save_path, f"latent_noises_{name}.npy"), np.concatenate(latent_noises, axis=0))
     np.save(os.path.join(config.data_save_path, f"latent_dlogps_{name}.npy"), np.concatenate(latent_dlogps, axis=0))
     np.save(os.path.join(config.data_save_path, f"samples_{name}.npy"), np.concatenate(samples, axis=0))
@@ -78,8 +107,8 @@ def sample_latent(config, b, dataset):
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
                                          save_every=getattr(config, "save_every", 1), step_control=getattr(config, "step_control", "batch"),
-                                         **_divergence_kw(config))
-    hutch, traj = integrator.divergence == "hutchinson", 0
+                                         **_divergence_kw(config), **_observe_kw(config))
+    hutch, traj, cvs = integrator.divergence == "hutchinson", 0, []
     samples, dlogps = [], []
     b.eval()
     for batch in dataset.batches(config.batch_size, seed=config.seed, drop_last=True):
@@ -88,6 +117,10 @@ def sample_latent(config, b, dataset):
         samples.append(_regroup(sample, bidx))
         if config.return_dlogp:
             dlogps.append(C.to_numpy(dlogp)[-1, :])                     # sample_latent.py:76-77
+        if integrator.observe is not None:
+            cvs.append(integrator.cv)
+    if cvs:
+        _write_observables(config, os.path.join(config.data_save_path, f"observables_{config.data_save_name}_forward.npz"), cvs, dlogps)
     out = np.concatenate(samples, axis=0)
     np.save(os.path.join(config.data_save_path, f"samples_{config.data_save_name}_forward.npy"), out)
     if config.return_dlogp:
@@ -103,8 +136,8 @@ def sample_adw(config, b, x0s_batches):
     assert len(config.beta0s) == len(config.beta1s) == 1            # adw/sample.py:24
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),
-                                         step_control=getattr(config, "step_control", "batch"))
-    initial, samples, dlogps = [], [], []
+                                         step_control=getattr(config, "step_control", "batch"), **_observe_kw(config))
+    initial, samples, dlogps, cvs = [], [], [], []
     b.eval()
     for x0s, beta0s in x0s_batches:
         beta1s = np.ones_like(C.to_numpy(beta0s)) * config.beta1s[0]
@@ -113,6 +146,8 @@ def sample_adw(config, b, x0s_batches):
         samples.append(C.to_numpy(sample))
         if config.return_dlogp:
             dlogps.append(C.to_numpy(dlogp))
+        if integrator.observe is not None:
+            cvs.append(integrator.cv)
     out_dir = os.path.join(config.data_save_path, config.model_save_name, f"beta_{config.beta0s[0]}_to_{config.beta1s[0]}")
     os.makedirs(out_dir, exist_ok=True)
     initial = np.array(initial)[:, :, 0].flatten()
@@ -126,4 +161,7 @@ def sample_adw(config, b, x0s_batches):
     np.save(os.path.join(out_dir, f"samples_epoch_{config.sampling_epoch}.npy"), samples)
     if config.return_dlogp:
         np.save(os.path.join(out_dir, f"dlogps_epoch_{config.sampling_epoch}.npy"), by_step(dlogps))
+    if cvs:
+        _write_observables(config, os.path.join(out_dir, f"observables_epoch_{config.sampling_epoch}.npz"), cvs,
+                           [d[-1] for d in dlogps] if config.return_dlogp else [])
     return initial, samples

@@ -139,6 +139,96 @@ class _Engine:
         _lib.check(_lib.lib().ti_rollout_step_counts(self.h, acc.ctypes.data_as(p), rej.ctypes.data_as(p), int(B)))
         return acc, rej
 
+    # ---- observables (include/ti_hip.h ti_obs_*; the user-facing functions and the descriptor syntax are in observables.py)
+    def _obs_n_atoms(self):
+        return getattr(self, "A", 1)
+
+    def _obs_args(self, descriptors, ref, select):
+        from . import observables as _obs
+        desc = _obs.encode_descriptors(descriptors)
+        A = self._obs_n_atoms()
+        host = lambda a: a.detach().cpu().numpy() if hasattr(a, "data_ptr") else np.asarray(a)
+        r = sel = None
+        if ref is not None:
+            r = np.ascontiguousarray(host(ref), np.float32)
+            if r.shape != (A, 3):
+                raise ValueError(f"ref must be [{A},3], got {r.shape}")
+        if select is not None:
+            sel = np.ascontiguousarray(host(select) != 0, np.int32)
+            if sel.shape != (A,):
+                raise ValueError(f"select must be [{A}], got {sel.shape}")
+        ptr = lambda a, f: None if a is None else f(a)
+        return desc, r, sel, (_lib.iptr(desc), int(desc.shape[0]), ptr(r, _lib.fptr), ptr(sel, _lib.iptr))
+
+    def _obs_x_shape(self, x):
+        raise NotImplementedError
+
+    def collective_variables(self, x, descriptors, ref=None, select=None, out=None):
+        """cv [B, K] float32 of the K descriptors (observables.encode_descriptors) on x; computed on the GPU in fp64.  x: numpy or a
+        CUDA tensor (the result lives where x lives)."""
+        desc, r, sel, (dp, K, rp, sp) = self._obs_args(descriptors, ref, select)
+        B, xs = self._obs_x_shape(x)
+        if out is None:
+            out = _alloc_like(x if hasattr(x, "data_ptr") and x.is_cuda else None, (B, K))
+        (xp, op), dev, keep = self._ptrs((x, xs, False, "x"), (out, (B, K), True, "out"))
+        _lib.check(_lib.lib().ti_obs_cv(self.h, dp, K, rp, sp, xp, B, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return out
+
+    def importance_weights(self, logw):
+        """(w [B] float32 = exp(logw) / sum exp(logw), ess) with a max shift and fixed-order fp64 sums; a non-finite logw raises."""
+        B = int(logw.shape[0])
+        w = _alloc_like(logw if hasattr(logw, "data_ptr") and logw.is_cuda else None, (B,))
+        (lp, wp), dev, keep = self._ptrs((logw, (B,), False, "logw"), (w, (B,), True, "out_w"))
+        ess = C.c_double(0.0)
+        _lib.check(_lib.lib().ti_obs_weights(self.h, lp, B, wp, C.byref(ess), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return w, ess.value
+
+    def weighted_histogram(self, values, logw, bins, range):
+        """(hist [bins] float64, tails [3] float64 = weight below range[0], at or above range[1], of non-finite values).  values: a
+        1-D float32 array or a column view such as cv[:, k] (read in place through its stride); logw None: uniform weights."""
+        from . import observables as _obs
+        bins, lo, hi = _obs.check_bins(bins, range)
+        if len(values.shape) != 1:
+            raise ValueError("values must be 1-D (a column of a CV array is fine: cv[:, k])")
+        B = int(values.shape[0])
+        if hasattr(values, "data_ptr"):
+            if str(values.dtype) != "torch.float32":
+                raise TypeError(f"values must be float32, got {values.dtype}")
+            stride, vp, vdev, keep_v = int(values.stride(0)) if B > 1 else 1, C.c_void_p(values.data_ptr()), bool(values.is_cuda), values
+        else:
+            values = np.asarray(values)
+            if values.dtype != np.float32:
+                values = np.ascontiguousarray(values, np.float32)
+            stride, vp, vdev, keep_v = (values.strides[0] // 4 if B > 1 else 1), C.c_void_p(values.ctypes.data), False, values
+        if stride < 1:
+            raise ValueError("values must have a positive stride")
+        (lp,), ldev, keep = self._ptrs((logw, (B,), False, "logw"))
+        if logw is not None and ldev != vdev:
+            raise ValueError("values and logw must live in the same memory space")
+        if vdev and logw is None:
+            import torch
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        hist, tails = np.zeros(bins, np.float64), np.zeros(3, np.float64)
+        dptr = C.POINTER(C.c_double)
+        _lib.check(_lib.lib().ti_obs_hist(self.h, vp, stride, lp, B, bins, lo, hi, hist.ctypes.data_as(dptr), tails.ctypes.data_as(dptr),
+                                          _lib.MEM_DEVICE if vdev else _lib.MEM_HOST))
+        return hist, tails
+
+    def set_observer(self, descriptors, ref=None, select=None, every=1, out=None):
+        """Attach an observer: every rollout that follows also writes the CVs of the grid points i % every == 0 and of the last one
+        to out [rows, B, K] (float32 numpy array or CUDA tensor, rows = ti_rollout_rows(n_step, every); kept alive here).
+        descriptors None detaches."""
+        if descriptors is None:
+            _lib.check(_lib.lib().ti_obs_set_observer(self.h, None, 0, None, None, 0, None, _lib.MEM_HOST))
+            self._observer_keep = None
+            return
+        desc, r, sel, (dp, K, rp, sp) = self._obs_args(descriptors, ref, select)
+        if out is None or len(out.shape) != 3 or int(out.shape[2]) != K:
+            raise ValueError(f"out must be [rows, B, {K}]")
+        (op,), dev, keep = self._ptrs((out, tuple(out.shape), True, "out"))
+        _lib.check(_lib.lib().ti_obs_set_observer(self.h, dp, K, rp, sp, int(every), op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        self._observer_keep = out
+
     def _times(self, t, B):
         """A 1-D time vector of length B (one time per molecule / row) as a buffer spec, or None for a scalar t."""
         if (tuple(t.shape) if hasattr(t, "shape") else np.shape(t)) == ():
@@ -249,6 +339,10 @@ class PainnEngine(_Engine):
             t = np.ascontiguousarray(t, np.uint8)
         ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
         _lib.check(L.ti_painn_set_molecules(self.h, ptr(n), ptr(m), ptr(t), B, _lib.MEM_HOST))
+
+    def _obs_x_shape(self, x):
+        B = self._check_x(x)
+        return B, (B, self.A, 3)
 
     def _check_x(self, x, name="x"):
         if x is None or len(x.shape) != 3 or tuple(x.shape[1:]) != (self.A, 3):
@@ -403,6 +497,10 @@ class AdwEngine(_Engine):
             self.h = _lib.lib().ti_adw_create_nd(C.byref(self.desc), self.dim, w.ctypes.data_as(C.POINTER(C.c_double)), w.size, self.device)
         if not self.h:
             raise _lib.TiError(-1, _lib.last_error())
+
+    def _obs_x_shape(self, x):
+        B = int(x.shape[0])
+        return B, self._xs(B)
 
     def _xs(self, *lead):
         """shape of a state array: lead dims + (d,) for d > 1; the 1-D engine keeps the flat [.., B] shapes"""

@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import engine as _engine
+from .. import observables as _obs
 from .. import synthetic as _syn
 from .. import weights as _W
 from . import _common as C
@@ -418,15 +419,23 @@ class MoleculeIntegratorBase:
 
     divergence (keyword-only, build-defined; needs return_dlogp=True for 'hutchinson'): 'exact' (default) or 'hutchinson' --
     Hutchinson's estimate with n_probes Rademacher probes per molecule (k tangent passes instead of 3A), drawn from (probe_seed,
-    traj_offset + b) once per rollout and fixed along it.  Unbiased but noisy: each molecule's dlogp carries an estimator error."""
+    traj_offset + b) once per rollout and fixed along it.  Unbiased but noisy: each molecule's dlogp carries an estimator error.
+
+    observe (keyword-only, build-defined): dict(descriptors=[...], ref=None, select=None, every=1) -- collective variables
+    (observables.py) evaluated on the GPU at the grid points i % every == 0 and at the last one, whatever save_every is; after rollout
+    they are in self.cv [rows, B, K] (a CUDA tensor when the batch is one).  Descriptor indices and ref [A, 3] are local to a
+    molecule; in a mixed-species batch A is the largest molecule and a descriptor naming an atom a molecule lacks gives NaN there."""
     SCALE_DLOGP = 1.0      # integrators.py:68 (ambient: 1e2)
     DIV_SCALE = 1.0        # ode_wrapper.py:91 (ambient: 1e-2)
 
     def __init__(self, b, method: str = "dopri5", n_step: int = 100, atol: float = 1e-4, rtol: float = 1e-4, start: float = 0.0,
                  end: float = 1.0, return_dlogp: bool = False, reverse_ode: bool = False, *, eps: float = 0.0, seed: int = 0,
                  save_every: int = 1, com_free_noise: bool = False, step_control: str = "batch", divergence: str = "exact",
-                 n_probes: int = 1, probe_seed: int = 0):
+                 n_probes: int = 1, probe_seed: int = 0, observe=None):
         self.method = C.check_method(method)
+        self.observe, self.cv = _obs.check_observe(observe), None
+        if self.observe is not None and step_control == "trajectory":
+            raise ValueError("observe= is not available with step_control='trajectory' (its rows are written per trajectory)")
         self.step_control = C.check_step_control(step_control, self.method)
         self.divergence, self.n_probes = C.check_divergence(divergence, n_probes, return_dlogp)
         self.probe_seed = int(probe_seed)
@@ -448,6 +457,19 @@ class MoleculeIntegratorBase:
         # without dlogp the reference always integrates on linspace(start, end) (integrators.py:54-55), reverse_ode or not
         grid = _engine.time_grid(self.start, self.end, self.n_step)
         eng = self.b.engine_of(sb)
+        if self.observe is None:
+            return self._rollout_on(eng, sb, batch, x0, gpu, grid, traj_offset)
+        o = self.observe
+        rows = int(_engine._lib.lib().ti_rollout_rows(int(self.n_step), o["every"]))
+        self.cv = _engine._alloc_like(x0 if gpu else None, (rows, B, int(o["descriptors"].shape[0])))
+        eng.set_observer(o["descriptors"], o["ref"], o["select"], o["every"], self.cv)
+        try:
+            return self._rollout_on(eng, sb, batch, x0, gpu, grid, traj_offset)
+        finally:
+            eng.set_observer(None)
+
+    def _rollout_on(self, eng, sb, batch, x0, gpu, grid, traj_offset):
+        B, A = sb.B, sb.A
         if self.return_dlogp:
             if self.reverse_ode:
                 grid = _engine.time_grid(self.end, self.start, self.n_step)

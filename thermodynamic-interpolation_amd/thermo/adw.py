@@ -12,6 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import engine as _engine
+from .. import observables as _obs
 from .. import synthetic as _syn
 from .. import weights as _W
 from . import _common as C
@@ -180,13 +181,19 @@ class StandardIntegrator:
     ``step_control`` (keyword-only): 'batch' (default, one step size per call like the reference's odeint) or 'trajectory'
     (method='dopri5' only: every particle gets the steps the reference takes for it at batch size 1; the per-particle
     (accepted, rejected) counts of the last rollout are then in ``n_steps_per_particle``).
+    ``observe`` (keyword-only): dict(descriptors=[("coord", c), ...], every=1) -- the named components of every particle at the grid
+    points i % every == 0 and at the last one, whatever save_every is; after rollout they are in ``self.cv`` [rows, B, K] (a CUDA
+    tensor when x0s is one).
     """
 
     def __init__(self, b, method: str = "dopri5", n_step: int = 100, atol: float = 1e-4, rtol: float = 1e-4, start: float = 0.0,
                  end: float = 1.0, return_dlogp=False, *, eps: float = 0.0, seed: int = 0, save_every: int = 1,
-                 step_control: str = "batch"):
+                 step_control: str = "batch", observe=None):
         self.method = C.check_method(method)
         self.step_control = C.check_step_control(step_control, self.method)
+        self.observe, self.cv = _obs.check_observe(observe), None
+        if self.observe is not None and step_control == "trajectory":
+            raise ValueError("observe= is not available with step_control='trajectory' (its rows are written per trajectory)")
         self.ode_wrapper = ODEWrapper(b, return_dlogp=return_dlogp)
         self.start, self.end, self.rtol, self.atol = start, end, rtol, atol
         self.n_step, self.return_dlogp = n_step, return_dlogp
@@ -207,10 +214,20 @@ class StandardIntegrator:
             b0 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta0s, np.float32).reshape(-1), (B,)))
             b1 = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta1s, np.float32).reshape(-1), (B,)))
         grid = _engine.time_grid(self.start, self.end, self.n_step)
-        res = self.ode_wrapper.b.engine().rollout(x0, b0, b1, grid, scheme=self.method,
-                                                  save_every=self.save_every, eps=self.eps, seed=self.seed, traj_offset=traj_offset,
-                                                  return_dlogp=bool(self.return_dlogp), rtol=self.rtol, atol=self.atol,
-                                                  step_control=self.step_control)
+        eng = self.ode_wrapper.b.engine()
+        if self.observe is not None:
+            o = self.observe
+            rows = int(_engine._lib.lib().ti_rollout_rows(int(self.n_step), o["every"]))
+            self.cv = _engine._alloc_like(x0 if C.is_cuda(x0) else None, (rows, B, int(o["descriptors"].shape[0])))
+            eng.set_observer(o["descriptors"], None, None, o["every"], self.cv)
+        try:
+            res = eng.rollout(x0, b0, b1, grid, scheme=self.method,
+                              save_every=self.save_every, eps=self.eps, seed=self.seed, traj_offset=traj_offset,
+                              return_dlogp=bool(self.return_dlogp), rtol=self.rtol, atol=self.atol,
+                              step_control=self.step_control)
+        finally:
+            if self.observe is not None:
+                eng.set_observer(None)
         self.n_fevals = res[-1]
         self.n_steps_per_particle = self.ode_wrapper.b.engine().step_counts(B) if self.step_control == "trajectory" else None
         dlogp = C.like(res[1][:, :, None], x0s) if self.return_dlogp else None
