@@ -177,6 +177,19 @@ int ti_adw_rollout(ti_handle* h, const ti_rollout_desc* desc, const float* x0, c
  * d(dlogp)/dt = -div * 1e-2 with the same scheme (any but EM with eps > 0) and writes out_dlogp [rows, B] = dlogp * 1e2 */
 int ti_adw_rollout_dlogp(ti_handle* h, const ti_rollout_desc* desc, const float* x0, const float* beta0, const float* beta1,
                          int64_t B, float* out_path, float* out_dlogp, int64_t* n_fevals);
+/* ti_adw_rollout / ti_adw_rollout_dlogp (out_dlogp != NULL) of a 1-D handle with the whole step loop inside ONE kernel launch: a wave
+ * keeps its 16 particles in registers for all n_step - 1 steps, evaluates `net` (and its d/dx tangent), applies the state update,
+ * draws the EM noise and writes only the rows save_every asks for; the beta embedding of every grid point comes from one launch of
+ * the embedding kernel ahead of it (a table of n_step x distinct (beta0, beta1) pairs, at most 2^24 rows: TI_E_UNSUPPORTED beyond).
+ * Same descriptor, shapes, *n_fevals (n_step - 1, twice that for HEUN) and TI_E_NAN check as the unfused calls, and the same result
+ * BIT FOR BIT: both run one MLP source, the per-step scalars (dt, dt / 2, -dt 1e-2, sqrt(2 eps |dt|)) are computed on the host by
+ * the unfused loop's fp32 expressions, and the updates are the fused multiply-adds its update kernels compile to.
+ * Opt-in: no other call changes what it launches.
+ * TI_E_ARG: a NULL or non-adw handle, NULL buffers with B > 0 (out_dlogp may be NULL).  TI_E_UNSUPPORTED, before any device work: a
+ * handle with dim > 1 (use ti_adw_rollout), a scheme other than EULER / HEUN / EM, EM with eps > 0 together with out_dlogp, an
+ * attached observer (the rows are written inside the kernel).  B = 0: TI_OK, *n_fevals = 0.  Profile slot: TI_KERNEL_ADW (2 launches). */
+int ti_adw_rollout_fused(ti_handle* h, const ti_rollout_desc* desc, const float* x0, const float* beta0, const float* beta1,
+                         int64_t B, float* out_path, float* out_dlogp /* may be NULL */, int64_t* n_fevals);
 
 /* ---- mdqm9: cPaiNN drift over homogeneous molecule batches ------------------------------------------------------ */
 /* edge_src/edge_dst: [E_m] local atom indices of ONE molecule in the reference's (src,dst)-sorted order

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "ti_painn_drift_div_est", "ti_painn_drift_div_est_tv", "ti_painn_rollout_dlogp_est",
     "ti_adw_create_nd", "ti_painn_set_edge_mask", "ti_painn_set_molecules",
     "ti_obs_cv", "ti_obs_weights", "ti_obs_hist", "ti_obs_set_observer",
+    "ti_adw_rollout_fused",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -110,6 +111,7 @@ def lib():
     L.ti_adw_rollout.argtypes = [vp, C.POINTER(RolloutDesc), vp, vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.ti_adw_drift_div.argtypes = [vp, vp, C.c_float, vp, vp, C.c_int64, vp, vp, C.c_int]
     L.ti_adw_rollout_dlogp.argtypes = [vp, C.POINTER(RolloutDesc), vp, vp, vp, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
+    L.ti_adw_rollout_fused.argtypes = [vp, C.POINTER(RolloutDesc), vp, vp, vp, C.c_int64, vp, vp, C.POINTER(C.c_int64)]
     L.ti_destroy.argtypes = [vp]
     L.ti_destroy.restype = None
     L.ti_set_stream.argtypes = [vp, vp, C.c_int]

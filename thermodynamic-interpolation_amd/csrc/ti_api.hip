@@ -221,6 +221,9 @@ struct ti_handle {
     Stream st_be{}, st_net{};
     DevBuf<float> ax, ab1, ab2, axt, aemb_u, abeta0_u, abeta1_u, adl, ad1, ad2; DevBuf<int32_t> aidx;
     DevBuf<float> abeta0_r, abeta1_r, aemb_r, atv;                  // per-row conditioning / beta embedding / times (per-row t)
+    // fused rollout (ti_adw_rollout_fused): embedding-table inputs [n_step * U] and the table itself, the per-step scalars, and the
+    // saved rows of a TI_MEM_HOST call (path, dlogp) ahead of their one copy
+    DevBuf<float> af_b0, af_b1, af_tv, af_emb, af_path, af_dl; DevBuf<AdwFusedStep> af_steps;
 
     // ---- observables (ti_obs_*): descriptor sets as validated and uploaded by obs_upload -- [0] of the last ti_obs_cv call, [1] the
     // attached observer (K == 0: none) with its row stride `every` and the caller's out_cv; staging for host buffers; fp64 scratch:
@@ -995,7 +998,8 @@ void adw_mlp_launch(ti_handle* h, bool embed, const float* a0, const float* in1,
 }
 
 // upload conditioning: dedupe (beta0, beta1) pairs on the host (the driver uses one pair, adw/sample.py:24)
-long long adw_set_cond(ti_handle* h, const float* beta0, const float* beta1, long long B, int mem)
+long long adw_set_cond(ti_handle* h, const float* beta0, const float* beta1, long long B, int mem, std::vector<float>* u0_out = nullptr,
+                       std::vector<float>* u1_out = nullptr)
 {
     std::vector<float> b0(B), b1(B);
     if (mem == TI_MEM_DEVICE) {
@@ -1013,6 +1017,8 @@ long long adw_set_cond(ti_handle* h, const float* beta0, const float* beta1, lon
     }
     h->aidx.upload(idx); h->abeta0_u.upload(u0); h->abeta1_u.upload(u1);
     h->aemb_u.alloc(u0.size());
+    if (u0_out) *u0_out = u0;
+    if (u1_out) *u1_out = u1;
     return (long long)u0.size();
 }
 
@@ -2053,6 +2059,7 @@ ti_handle* ti_adw_create_nd(const ti_adw_desc* d, int32_t dim, const double* wei
         if (pk.empty()) pk.assign(4, 0.f);
         h->flat.upload(nat); h->packed.upload(pk);
         HIP_CHECK(configure_adw_kernels(NB, std::max(1, nl - 1), dim));
+        if (dim == 1) HIP_CHECK(configure_adw_fused_kernels(NB, std::max(1, nl - 1)));
         out = h.release();
         return TI_OK;
     });
@@ -2171,6 +2178,95 @@ int ti_adw_rollout_dlogp(ti_handle* h, const ti_rollout_desc* rd, const float* x
 {
     if (!out_dlogp) return fail(TI_E_ARG, "out_dlogp is NULL");
     return adw_rollout_impl(h, rd, x0, beta0, beta1, B, out_path, out_dlogp, n_fevals);
+}
+
+// A whole Euler / Heun / EM rollout of a 1-D handle in two launches: the beta-embedding table of every grid point (the embedding
+// kernel in its per-row-time mode over n_step * U rows) and adw_rollout_fused_kernel.  Every per-step scalar is computed here with the
+// fp32 expressions of rollout_common; the kernel applies them with the roundings of axpy_kernel / heun_kernel / noise_kernel /
+// scale_kernel, so the result is that of ti_adw_rollout(_dlogp) bit for bit.
+int ti_adw_rollout_fused(ti_handle* h, const ti_rollout_desc* rd, const float* x0, const float* beta0, const float* beta1, int64_t B,
+                         float* out_path, float* out_dlogp, int64_t* n_fevals)
+{
+    if (!h || h->kind != 1) return fail(TI_E_ARG, "not an adw handle");
+    if (int rc = check_rollout_desc(rd)) return rc;
+    if (h->a_dim > 1) return fail(TI_E_UNSUPPORTED, "the fused rollout covers 1-D handles: use ti_adw_rollout for dim = " + std::to_string(h->a_dim));
+    if (rd->scheme != TI_SCHEME_EULER && rd->scheme != TI_SCHEME_HEUN && rd->scheme != TI_SCHEME_EM)
+        return fail(TI_E_UNSUPPORTED, "the fused rollout covers the Euler, Heun and EM schemes: use ti_adw_rollout for the others");
+    if (h->obs[1].K > 0)
+        return fail(TI_E_UNSUPPORTED, "the fused rollout writes its rows inside a kernel: detach the observer (ti_obs_set_observer)");
+    if (B < 0 || (B > 0 && (!x0 || !beta0 || !beta1 || !out_path))) return fail(TI_E_ARG, "NULL buffer");
+    if (out_dlogp && rd->scheme == TI_SCHEME_EM && rd->eps > 0.f)
+        return fail(TI_E_UNSUPPORTED, "dlogp is defined for a deterministic flow: EM needs eps = 0");
+    if (B == 0) { if (n_fevals) *n_fevals = 0; return TI_OK; }
+    return guarded([&]() -> int {
+        set_device(h);
+        ensure_adw_ws(h, B);
+        std::vector<float> u0, u1;
+        const long long U = adw_set_cond(h, beta0, beta1, B, rd->mem, &u0, &u1);
+        const int N = rd->n_step;
+        if ((long long)N * U > (1LL << 24))
+            return fail(TI_E_UNSUPPORTED, "the fused rollout's embedding table is limited to 2^24 rows, n_step * distinct (beta0, beta1) pairs = " +
+                                              std::to_string((long long)N * U) + ": use ti_adw_rollout");
+        hipStream_t st = h->stream;
+        const bool dev = rd->mem == TI_MEM_DEVICE;
+        HIP_CHECK(hipMemcpyAsync(h->ax.p, x0, (size_t)B * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        // beta embedding at every grid point, rows (k, u): one launch of the embedding kernel with one time per row
+        const size_t nt = (size_t)N * U;
+        std::vector<float> tb0(nt), tb1(nt), ttv(nt);
+        for (int k = 0; k < N; ++k)
+            for (long long u = 0; u < U; ++u) { tb0[k * U + u] = u0[u]; tb1[k * U + u] = u1[u]; ttv[k * U + u] = rd->t_grid[k]; }
+        // (the host vectors of this call outlive the stream synchronisation at its end)
+        if (h->af_emb.n < nt) { h->af_b0.alloc(nt); h->af_b1.alloc(nt); h->af_tv.alloc(nt); h->af_emb.alloc(nt); }
+        HIP_CHECK(hipMemcpyAsync(h->af_b0.p, tb0.data(), nt * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(h->af_b1.p, tb1.data(), nt * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(h->af_tv.p, ttv.data(), nt * sizeof(float), hipMemcpyHostToDevice, st));
+        adw_mlp_launch(h, true, h->af_b0.p, h->af_b1.p, h->af_tv.p, nullptr, 0.f, (long long)nt, h->af_emb.p, nullptr);
+        // per-step scalars: the expressions of rollout_common, in fp32
+        const DlogpAux aux;
+        const bool noise = rd->scheme == TI_SCHEME_EM && rd->eps > 0.0f;
+        std::vector<AdwFusedStep> steps(std::max(N - 1, 1));
+        for (int k = 0; k < N - 1; ++k) {
+            const float dt = rd->t_grid[k + 1] - rd->t_grid[k];
+            AdwFusedStep& s = steps[k];
+            s.t = rd->t_grid[k]; s.t_next = rd->t_grid[k + 1];
+            s.dt = dt; s.hdt = 0.5f * dt;
+            s.ndt = -dt * aux.div_scale; s.nhdt = -0.5f * dt * aux.div_scale;
+            s.sigma = noise ? std::sqrt(2.0f * rd->eps * std::fabs(dt)) : 0.0f;
+            s.pad = 0.0f;
+        }
+        if (h->af_steps.n < steps.size()) h->af_steps.alloc(steps.size());
+        HIP_CHECK(hipMemcpyAsync(h->af_steps.p, steps.data(), steps.size() * sizeof(AdwFusedStep), hipMemcpyHostToDevice, st));
+        const size_t rows = (size_t)ti_rollout_rows(N, rd->save_every), nout = rows * (size_t)B;
+        float *pd = out_path, *dd = out_dlogp;
+        if (!dev) {
+            if (h->af_path.n < nout) h->af_path.alloc(nout);
+            pd = h->af_path.p;
+            if (out_dlogp) { if (h->af_dl.n < nout) h->af_dl.alloc(nout); dd = h->af_dl.p; }
+        }
+        AdwFusedParams p{};
+        p.stream = h->S(h->st_net); p.nch = h->st_net.nch; p.vecs = h->F(h->a_net_vecs); p.b_out = h->a_b_out;
+        p.n_hidden = h->ad.num_layers - 1; p.B = B;
+        p.x = h->ax.p; p.idx = h->aidx.p; p.emb = h->af_emb.p; p.U = U; p.steps = h->af_steps.p;
+        p.n_step = N; p.save_every = rd->save_every;
+        p.scheme = rd->scheme == TI_SCHEME_HEUN ? ADW_FUSED_HEUN : noise ? ADW_FUSED_EM : ADW_FUSED_EULER;
+        p.seed = rd->seed; p.traj0 = rd->traj_offset; p.step0 = (int)rd->step_offset;
+        p.out_path = pd; p.out_dlogp = dd; p.out_scale = aux.out_scale;
+        {
+            Timed tm(h, TI_KERNEL_ADW);
+            HIP_CHECK(launch_adw_fused(h->NB, h->ad.precision == TI_PREC_F16X2, p, st));
+        }
+        if (!dev) {
+            HIP_CHECK(hipMemcpyAsync(out_path, pd, nout * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (out_dlogp) HIP_CHECK(hipMemcpyAsync(out_dlogp, dd, nout * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipMemsetAsync(h->nanflag.p, 0, sizeof(int), st));
+        HIP_CHECK(launch_nan_check(h->ax.p, (long long)B, h->nanflag.p, st));
+        int flag = 0;
+        HIP_CHECK(hipMemcpyAsync(&flag, h->nanflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (n_fevals) *n_fevals = (int64_t)(N - 1) * (rd->scheme == TI_SCHEME_HEUN ? 2 : 1);
+        return flag ? fail(TI_E_NAN, "non-finite value in the final state") : TI_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------- observables

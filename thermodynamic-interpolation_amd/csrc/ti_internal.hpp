@@ -213,6 +213,33 @@ struct AdwParams {
 hipError_t launch_adw(int NB, bool split, const AdwParams& p, hipStream_t st);
 hipError_t configure_adw_kernels(int NB, int max_hidden, int dim);
 
+// ---- fused adw rollout (adw_fused_kernels.hip; include/ti_hip.h ti_adw_rollout_fused): one launch runs all n_step - 1 steps of a 1-D
+// handle.  The host fills the per-step scalars with the fp32 expressions of rollout_common (ti_api.hip); the kernel computes none.
+enum { ADW_FUSED_EULER = 0, ADW_FUSED_HEUN = 1, ADW_FUSED_EM = 2 };       // EM: Euler plus the noise term (eps > 0)
+struct AdwFusedStep {                       // step k: t_grid[k] -> t_grid[k + 1]
+    float t, t_next;                        // t_grid[k], t_grid[k + 1]
+    float dt, hdt;                          // t_grid[k + 1] - t_grid[k];  0.5f * dt
+    float ndt, nhdt;                        // -dt * div_scale;  -0.5f * dt * div_scale   (dlogp state)
+    float sigma;                            // sqrt(2 eps |dt|)
+    float pad;
+};
+struct AdwFusedParams {
+    const float4* stream; int nch;          // `net`: as AdwParams
+    const float* vecs;
+    float b_out;
+    int n_hidden; long long B;
+    float* x;                               // [B] in: x0, out: the end state
+    const int32_t* idx;                     // [B] row -> deduplicated (beta0, beta1) pair
+    const float* emb; long long U;          // [n_step][U] beta embedding at every grid point: emb[k * U + idx[row]]
+    const AdwFusedStep* steps;              // [n_step - 1]
+    int n_step, save_every, scheme;         // scheme: ADW_FUSED_*
+    uint64_t seed; long long traj0; int step0;      // EM: ti_normal(seed, traj0 + row, step0 + k, 0)
+    float* out_path;                        // [rows][B]
+    float* out_dlogp; float out_scale;      // non-NULL: [rows][B] = dlogp * out_scale (selects the tangent instantiation)
+};
+hipError_t launch_adw_fused(int NB, bool split, const AdwFusedParams& p, hipStream_t st);
+hipError_t configure_adw_fused_kernels(int NB, int max_hidden);
+
 // ---- integrator kernels (integrate_kernels.hip)
 hipError_t launch_axpy(float* y, const float* x, float a, const float* b, long long n, hipStream_t st);          // y = x + a*b
 hipError_t launch_heun(float* x, float hdt, const float* b1, const float* b2, long long n, hipStream_t st);      // x += hdt*(b1+b2)

@@ -136,7 +136,8 @@ def sample_adw(config, b, x0s_batches):
     assert len(config.beta0s) == len(config.beta1s) == 1            # adw/sample.py:24
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),
-                                         step_control=getattr(config, "step_control", "batch"), **_observe_kw(config))
+                                         step_control=getattr(config, "step_control", "batch"), fused=bool(getattr(config, "fused", False)),
+                                         **_observe_kw(config))
     initial, samples, dlogps, cvs = [], [], [], []
     b.eval()
     for x0s, beta0s in x0s_batches:

@@ -531,9 +531,11 @@ class AdwEngine(_Engine):
         return out, div
 
     def rollout(self, x0, beta0, beta1, t_grid, scheme="euler", save_every=1, eps=0.0, seed=0, traj_offset=0, out=None,
-                return_dlogp=False, rtol=1e-4, atol=1e-4, step_offset=0, step_control="batch"):
+                return_dlogp=False, rtol=1e-4, atol=1e-4, step_offset=0, step_control="batch", *, fused=False):
         """(path [rows,B] ([rows,B,d] for d > 1), n_fevals), or (path, dlogp [rows,B] (already * 1e2 like the reference), n_fevals).
-        step_control='trajectory' (dopri5 only): every particle gets the steps a batch of one would take (see PainnEngine.rollout)."""
+        step_control='trajectory' (dopri5 only): every particle gets the steps a batch of one would take (see PainnEngine.rollout).
+        fused=True: the whole step loop in one kernel launch (ti_adw_rollout_fused: dim = 1, euler / heun / em, no observer; anything
+        else raises TiError with TI_E_UNSUPPORTED) -- the same arrays bit for bit."""
         B = int(x0.shape[0])
         on_gpu = hasattr(x0, "data_ptr") and x0.is_cuda
         rd = _rollout_desc(scheme, t_grid, save_every, _lib.MEM_DEVICE if on_gpu else _lib.MEM_HOST, eps, seed, traj_offset, False, rtol, atol,
@@ -545,6 +547,9 @@ class AdwEngine(_Engine):
         (xp, b0p, b1p, op, dp), dev, keep = self._ptrs((x0, self._xs(B), False, "x0"), (beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1"),
                                                        (out, self._xs(rows, B), True, "out"), (dl, None, True, "out_dlogp"))
         nfe = C.c_int64(0)
+        if fused:
+            _lib.check(_lib.lib().ti_adw_rollout_fused(self.h, C.byref(rd), xp, b0p, b1p, B, op, dp, C.byref(nfe)))
+            return (out, dl, nfe.value) if return_dlogp else (out, nfe.value)
         if not return_dlogp:
             _lib.check(_lib.lib().ti_adw_rollout(self.h, C.byref(rd), xp, b0p, b1p, B, op, C.byref(nfe)))
             return out, nfe.value

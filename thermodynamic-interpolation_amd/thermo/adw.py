@@ -184,11 +184,13 @@ class StandardIntegrator:
     ``observe`` (keyword-only): dict(descriptors=[("coord", c), ...], every=1) -- the named components of every particle at the grid
     points i % every == 0 and at the last one, whatever save_every is; after rollout they are in ``self.cv`` [rows, B, K] (a CUDA
     tensor when x0s is one).
+    ``fused`` (keyword-only, default False): run the whole step loop in one kernel launch (AdwEngine.rollout(fused=True): 1-D model,
+    'euler' | 'heun' | 'em', no ``observe``; anything else raises the library's TI_E_UNSUPPORTED) -- the same result bit for bit.
     """
 
     def __init__(self, b, method: str = "dopri5", n_step: int = 100, atol: float = 1e-4, rtol: float = 1e-4, start: float = 0.0,
                  end: float = 1.0, return_dlogp=False, *, eps: float = 0.0, seed: int = 0, save_every: int = 1,
-                 step_control: str = "batch", observe=None):
+                 step_control: str = "batch", observe=None, fused: bool = False):
         self.method = C.check_method(method)
         self.step_control = C.check_step_control(step_control, self.method)
         self.observe, self.cv = _obs.check_observe(observe), None
@@ -198,6 +200,7 @@ class StandardIntegrator:
         self.start, self.end, self.rtol, self.atol = start, end, rtol, atol
         self.n_step, self.return_dlogp = n_step, return_dlogp
         self.eps, self.seed, self.save_every = eps, seed, save_every
+        self.fused = bool(fused)
 
     def rollout(self, x0s, beta0s, beta1s, traj_offset: int = 0):
         d = self.ode_wrapper.b.dim
@@ -224,7 +227,7 @@ class StandardIntegrator:
             res = eng.rollout(x0, b0, b1, grid, scheme=self.method,
                               save_every=self.save_every, eps=self.eps, seed=self.seed, traj_offset=traj_offset,
                               return_dlogp=bool(self.return_dlogp), rtol=self.rtol, atol=self.atol,
-                              step_control=self.step_control)
+                              step_control=self.step_control, fused=self.fused)
         finally:
             if self.observe is not None:
                 eng.set_observer(None)
