@@ -377,7 +377,8 @@ int ti_painn_debug_read(ti_handle* h, int what, float* out, size_t n_floats);
 /* Test hook for the first-touch accumulators (csrc/painn_edge_kernel.hpp: acc_out): fill the per-atom accumulators dsacc / dvacc / cacc of
  * the workspace for B trajectories with `value` (NaN, 1e30 ...) on the handle's stream.  A following ti_painn_drift must return exactly what
  * a handle created with TI_ZERO_ACC=1 in the environment (zeroing path: memsets + adds only) returns.  Reference counterpart: none
- * (torch_scatter allocates its output, cpainn.py:303-304). */
+ * (torch_scatter allocates its output, cpainn.py:303-304).  The edge state e and the parked edge geometry (encoding, edge_dir) are filled
+ * as well: an evaluation writes every row of them before it reads it, and the pair-major kernel never touches rows of absent pairs. */
 int ti_painn_debug_poison(ti_handle* h, int64_t B, float value);
 /* Device self-test of the MFMA operand/accumulator lane maps the kernels rely on, of both fp32 -> (hi, lo) fp16 operand splits
  * (the 8-instruction forms of formats (a) and (b) against the plain arithmetic, bit for bit, fp16-subnormal residuals included),

@@ -17,6 +17,17 @@
 #ifndef TI_PAIR_STAGGER
 #define TI_PAIR_STAGGER 0
 #endif
+    // Output-stage trims, each measured alone against the kernel without it (profiles/outstage_items.txt, DESIGN.md 3.6):
+#ifndef TI_PAIR_SEED_BIAS
+#define TI_PAIR_SEED_BIAS 1       // out3 starts its accumulators at the bias of the slice (like the hidden layers and the de slice) instead of adding it after the products
+#endif
+#ifndef TI_PAIR_SKIP_INVALID
+#define TI_PAIR_SKIP_INVALID 1    // rows of pairs that do not exist neither load nor store their e rows, their parked encoding and their edge_dir
+#endif
+#ifndef TI_PAIR_GROUP_BASE
+#define TI_PAIR_GROUP_BASE 1      // node rows addressed as (wave-uniform base of the group) + (small per-lane offset): the 64-bit part of every address is scalar work
+                                  // (seeds -1.1 %, absent rows -0.9 % of a launch; the group bases measured neutral)
+#endif
     PipeDMA<NB, T, SC, CH4, WAVES == 8 && TI_PAIR_STAGGER, NBUF> pipe;        // 8 waves: SIMD partners half a phase apart (mfma_chain.hpp)
     pipe.init(reinterpret_cast<const f32x4*>(p.stream), p.nch, lds, wave, lane);
 
@@ -31,6 +42,20 @@
         m = m < p.B ? m : p.B - 1;
         return m * p.A + atom;
     };
+    // TI_PAIR_GROUP_BASE: the group's first node is the same for the whole wave, so the node arrays are addressed from per-group bases
+    // that live in scalar registers, with the node inside the group (< G * A) as an unsigned 32-bit lane offset
+    const long long gnode0 = gi * p.G * (long long)p.A;
+    const unsigned mol_cap = (unsigned)(p.B - 1 - gi * p.G);               // molecules past the batch's end read the last one, as node_of
+    auto lnode_of = [&](int mol_local, int atom) {
+        const unsigned m = (unsigned)mol_local < mol_cap ? (unsigned)mol_local : mol_cap;
+        return m * (unsigned)p.A + (unsigned)atom;
+    };
+    const float* const x_g = p.x + gnode0 * 3;
+    const float* const P_g = p.P + gnode0 * F;
+    const float* const v_g = p.v + gnode0 * 3 * F;
+    float* const ds_g = p.dsacc + gnode0 * F;
+    float* const dv_g = p.dvacc + gnode0 * 3 * F;
+    float* const c_g = p.cacc + gnode0 * 3 * F;
 
     // Diagnostic build only (-DTI_STAMPS; never the product): shader-clock stamps of ONE row block of a few workgroups, and one
     // (s_memtime, s_memrealtime) pair around the whole block loop of every wave for the in-kernel clock (MI355X guide, DVFS item 6).
@@ -52,29 +77,40 @@
         // ---- K1 geometry of this lane's pair row (the 4 quarters compute the same row); direction A: r = x[I] - x[J]
         const uint32_t meta = TI_PAIR_ROWS[blk * 16 + j];
         const long long nI = node_of(prow_molI(meta), prow_atomI(meta)), nJ = node_of(prow_molJ(meta), prow_atomJ(meta));
+        const unsigned lI = lnode_of(prow_molI(meta), prow_atomI(meta)), lJ = lnode_of(prow_molJ(meta), prow_atomJ(meta));   // the same nodes inside the group
+        // row_ok: this lane's pair row exists.  A row that does not contributes nothing (w factor 0) and no valid row reads its e row,
+        // its parked encoding or its edge_dir: with TI_PAIR_SKIP_INVALID it loads none of them (zeros instead) and stores none
+        const bool row_ok = !TI_PAIR_SKIP_INVALID || (meta & 1u) != 0;
         const size_t brow0 = ((size_t)gi * p.nblk + blk) * 16;       // pair rows: parked encoding / edge_dir
         const size_t erowA = brow0 * 2, erowB = erowA + 16;             // e rows of the two directions
         OP enc;
         f32x4* const enc_park = reinterpret_cast<f32x4*>(p.enc) + (brow0 / 16) * (sizeof(OP) / 16) * 64 + lane;
         f32x4* const geo_park = reinterpret_cast<f32x4*>(p.geo) + brow0 + j;
         if constexpr (FIRST) {
-            const float rx = p.x[nI * 3 + 0] - p.x[nJ * 3 + 0];
-            const float ry = p.x[nI * 3 + 1] - p.x[nJ * 3 + 1];
-            const float rz = p.x[nI * 3 + 2] - p.x[nJ * 3 + 2];
+            const float* const xI = TI_PAIR_GROUP_BASE ? x_g + lI * 3u : p.x + nI * 3;
+            const float* const xJ = TI_PAIR_GROUP_BASE ? x_g + lJ * 3u : p.x + nJ * 3;
+            const float rx = xI[0] - xJ[0];
+            const float ry = xI[1] - xJ[1];
+            const float rz = xI[2] - xJ[2];
             const float dist = sqrtf(rx * rx + ry * ry + rz * rz);
             const float den = 1.0f + dist;                       // edge_dir = r / (1 + d)   (not a unit vector)
             if (q == 0) {
                 f32x4 dd = {rx / den, ry / den, rz / den, 0.f};
                 *reinterpret_cast<f32x4*>(scratch + j * 4) = dd;
-                if (group_ok) *geo_park = dd;
+                if (group_ok && row_ok) *geo_park = dd;
             }
             A16 t;
             r16::posenc_set(t, dist / p.length_scale, q);
             enc.set(t);
-            if (group_ok) r16::opnd_store(enc, enc_park);
+            if (group_ok && row_ok) r16::opnd_store(enc, enc_park);
         } else {
-            if (q == 0) *reinterpret_cast<f32x4*>(scratch + j * 4) = *geo_park;
-            r16::opnd_load(enc, enc_park);
+            if (q == 0) {
+                f32x4 dd = {0.f, 0.f, 0.f, 0.f};
+                if (row_ok) dd = *geo_park;
+                *reinterpret_cast<f32x4*>(scratch + j * 4) = dd;
+            }
+            if (TI_PAIR_SKIP_INVALID) __builtin_memset(&enc, 0, sizeof(OP));
+            if (row_ok) r16::opnd_load(enc, enc_park);
         }
         TI_STAMP();
         // ---- w(enc(d)) hidden layers, once per pair
@@ -116,8 +152,14 @@
                 scA = inA.set_scaled(tA);
                 inB = inA; scB = scA;
             } else {
-                r16::load_set(tA, p.e + (erowA + j) * F, q);
-                r16::load_set(tB, p.e + (erowB + j) * F, q);
+                if (TI_PAIR_SKIP_INVALID) {
+#pragma unroll
+                    for (int nb = 0; nb < NBK; ++nb) { tA.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; tB.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+                }
+                if (row_ok) {
+                    r16::load_set(tA, p.e + erowA * F + (unsigned)(j * F), q);
+                    r16::load_set(tB, p.e + erowB * F + (unsigned)(j * F), q);
+                }
                 scA = inA.set_scaled(tA);                                    // e is an un-normalised stream: per-row 2^k
                 scB = inB.set_scaled(tB);
             }
@@ -125,8 +167,10 @@
             TI_STAMP();
 #pragma unroll
             for (int c = 0; c < NB; ++c) {
-                f32x4 a0 = r16::load_state<false>(p.P, (size_t)nI * F, 2 * c, q) * ivA, a1 = r16::load_state<false>(p.P, (size_t)nI * F, 2 * c + 1, q) * ivA;
-                f32x4 b0 = r16::load_state<false>(p.P, (size_t)nJ * F, 2 * c, q) * ivB, b1 = r16::load_state<false>(p.P, (size_t)nJ * F, 2 * c + 1, q) * ivB;
+                const float* const PI = TI_PAIR_GROUP_BASE ? P_g + lI * (unsigned)F : p.P + (size_t)nI * F;
+                const float* const PJ = TI_PAIR_GROUP_BASE ? P_g + lJ * (unsigned)F : p.P + (size_t)nJ * F;
+                f32x4 a0 = r16::load_block(PI, 2 * c, q) * ivA, a1 = r16::load_block(PI, 2 * c + 1, q) * ivA;
+                f32x4 b0 = r16::load_block(PJ, 2 * c, q) * ivB, b1 = r16::load_block(PJ, 2 * c + 1, q) * ivB;
                 r16::gemm_x2_on_pipe<false>(a0, a1, b0, b1, inA, inB, pipe, lane);
                 tA.b[2 * c] = a0 * scA; tA.b[2 * c + 1] = a1 * scA;
                 tB.b[2 * c] = b0 * scB; tB.b[2 * c + 1] = b1 * scB;
@@ -173,24 +217,43 @@
         // atomic variant: the accumulator rows of the two destination atoms, laid out as three arrays (ds [F], dv [3F], c [3F] per node)
         const int qnA = (int)((gi * p.G + slot_mol(snJ)) * p.A) + (snJ & 255), qnB = (int)((gi * p.G + slot_mol(snI)) * p.A) + (snI & 255);
         const bool qfA = (snJ & SLOT_FIRST_TOUCH) != 0, qfB = (snI & SLOT_FIRST_TOUCH) != 0;
-        auto acc_ptr = [&](int node, int off) {                // off as for the partial rows: ds 0.., dv F.., c 4F..   (node < 2^31 / (3 F))
+        // the same nodes inside the group (TI_PAIR_GROUP_BASE); touched only where haveA / haveB hold, i.e. for molecules of the batch
+        const unsigned lnA = (unsigned)slot_mol(snJ) * (unsigned)p.A + (unsigned)(snJ & 255), lnB = (unsigned)slot_mol(snI) * (unsigned)p.A + (unsigned)(snI & 255);
+        auto acc_ptr = [&](int node, unsigned lnode, int off) {   // off as for the partial rows: ds 0.., dv F.., c 4F..   (node < 2^31 / (3 F))
+            if (TI_PAIR_GROUP_BASE)
+                return off < F ? ds_g + (lnode * (unsigned)F + (unsigned)off) : off < 4 * F ? dv_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - F)) : c_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - 4 * F));
             return off < F ? p.dsacc + (size_t)node * F + off : off < 4 * F ? p.dvacc + (size_t)node * 3 * F + (off - F) : p.cacc + (size_t)node * 3 * F + (off - 4 * F);
         };
         const long long nIq = node_of(prow_molI(mi[0]), prow_atomI(mi[0]));      // source of direction A for all four rows of this lane
+        const unsigned lIq = lnode_of(prow_molI(mi[0]), prow_atomI(mi[0]));
 
         // (phi_c + b) of both directions times the shared (w_c + b) for output slice c (0 gates, 1 scale_edge_dir, 2 ds, 3 de,
         // 4 cross gates), features fo .. fo+31 as two 16-feature blocks
         auto out3 = [&](int c, int nbo, f32x4& rA0, f32x4& rA1, f32x4& rB0, f32x4& rB1) {
-            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0}, b0 = {0, 0, 0, 0}, b1 = {0, 0, 0, 0}, w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
-            r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
-            pipe.release();
-            r16::gemm_on_pipe<true>(w0, w1, g2, pipe, lane);
-            pipe.release();
             const float* bp = vec + (EV::P_B2 + c) * F + 32 * nbo + j;
             const float* bw = vec + (EV::W_B2 + c) * F + 32 * nbo + j;
-            w0 = (w0 + bw[0]) * wfac; w1 = (w1 + bw[16]) * wfac;
-            rA0 = (a0 + bp[0]) * w0; rA1 = (a1 + bp[16]) * w1;
-            rB0 = (b0 + bp[0]) * w0; rB1 = (b1 + bp[16]) * w1;
+            if (TI_PAIR_SEED_BIAS) {
+                // the bias is one scalar per lane here (features on lanes) and already carries the scale of its matrix (ti_api.hip: the
+                // message kernel's vector block), i.e. the scale the one-accumulator products carry: it seeds the sums
+                const float p0 = bp[0], p1 = bp[16], q0 = bw[0], q1 = bw[16];
+                f32x4 a0 = {p0, p0, p0, p0}, a1 = {p1, p1, p1, p1}, b0 = a0, b1 = a1, w0 = {q0, q0, q0, q0}, w1 = {q1, q1, q1, q1};
+                r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
+                pipe.release();
+                r16::gemm_on_pipe<true>(w0, w1, g2, pipe, lane);
+                pipe.release();
+                w0 *= wfac; w1 *= wfac;
+                rA0 = a0 * w0; rA1 = a1 * w1;
+                rB0 = b0 * w0; rB1 = b1 * w1;
+            } else {
+                f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0}, b0 = {0, 0, 0, 0}, b1 = {0, 0, 0, 0}, w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
+                r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
+                pipe.release();
+                r16::gemm_on_pipe<true>(w0, w1, g2, pipe, lane);
+                pipe.release();
+                w0 = (w0 + bw[0]) * wfac; w1 = (w1 + bw[16]) * wfac;
+                rA0 = (a0 + bp[0]) * w0; rA1 = (a1 + bp[16]) * w1;
+                rB0 = (b0 + bp[0]) * w0; rB1 = (b1 + bp[16]) * w1;
+            }
         };
         // direction A: sum over the four lane rows (the I slots) for each register (J slot); lane row q' ends with J slot q'
         auto sumA = [&](const f32x4& v) {
@@ -199,11 +262,11 @@
         };
         // off: offset of the quantity inside a partial row (ds 0, dv (1 + c) F, c (4 + c) F) plus the lane's feature
         auto putA = [&](float z0, float z1, int off) {
-            if (TI_PAIR_ACC_ATOMIC) { if (haveA) { float* d = acc_ptr(qnA, off); acc_out(d, z0, qfA); acc_out(d + 16, z1, qfA); } }
+            if (TI_PAIR_ACC_ATOMIC) { if (haveA) { float* d = acc_ptr(qnA, lnA, off); acc_out(d, z0, qfA); acc_out(d + 16, z1, qfA); } }
             else if (haveA) { partA[off] = z0; partA[off + 16] = z1; }
         };
         auto putB = [&](float z0, float z1, int off) {
-            if (TI_PAIR_ACC_ATOMIC) { if (haveB) { float* d = acc_ptr(qnB, off); acc_out(d, z0, qfB); acc_out(d + 16, z1, qfB); } }
+            if (TI_PAIR_ACC_ATOMIC) { if (haveB) { float* d = acc_ptr(qnB, lnB, off); acc_out(d, z0, qfB); acc_out(d + 16, z1, qfB); } }
             else if (haveB) { partB[off] = z0; partB[off + 16] = z1; }
         };
         // direction B: the four registers of a lane are the J slots of ONE destination I[q]
@@ -231,6 +294,7 @@
         f32x4* const zpark = reinterpret_cast<f32x4*>(vec + EV::COUNT * F) + wave * 3 * 64 + lane;     // FOLD: [3][64 lanes] f32x4 per wave
         static_assert(!FOLD || GATHER_EARLY, "the fold crosses with the v[dst] rows that the early gathers hold");
         const long long nJq = snJ >= 0 ? node_of(slot_mol(snJ), snJ & 255) : nIq;   // J slot q's atom: lane row q fetches it for all four
+        const unsigned lJq = snJ >= 0 ? lnode_of(slot_mol(snJ), snJ & 255) : lIq;
         const float wrow = (meta & 1u) ? inv_out : 0.0f;                 // the same row factor in the row layout (lane (j, q): row j)
 
 #pragma unroll 1
@@ -251,23 +315,26 @@
                 f32x4 a0 = r16::load_block(vec + (EV::P_B2 + 3) * F, 2 * nbo, q), a1 = r16::load_block(vec + (EV::P_B2 + 3) * F, 2 * nbo + 1, q);
                 f32x4 b0 = a0, b1 = a1;
                 f32x4 w0 = r16::load_block(vec + (EV::W_B2 + 3) * F, 2 * nbo, q), w1 = r16::load_block(vec + (EV::W_B2 + 3) * F, 2 * nbo + 1, q);
-                float* const ea = p.e + (erowA + j) * F;
-                float* const eb = p.e + (erowB + j) * F;
+                float* const ea = p.e + erowA * F + (unsigned)(j * F);
+                float* const eb = p.e + erowB * F + (unsigned)(j * F);
                 f32x4 oA0, oA1, oB0, oB1;
                 if (FIRST) {
                     const float* em = p.edge_emb + prow_type(meta) * F;
                     oA0 = r16::load_block(em, 2 * nbo, q); oA1 = r16::load_block(em, 2 * nbo + 1, q);
                     oB0 = oA0; oB1 = oA1;
                 } else {
-                    oA0 = r16::load_block(ea, 2 * nbo, q); oA1 = r16::load_block(ea, 2 * nbo + 1, q);
-                    oB0 = r16::load_block(eb, 2 * nbo, q); oB1 = r16::load_block(eb, 2 * nbo + 1, q);
+                    if (TI_PAIR_SKIP_INVALID) oA0 = oA1 = oB0 = oB1 = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (row_ok) {
+                        oA0 = r16::load_block(ea, 2 * nbo, q); oA1 = r16::load_block(ea, 2 * nbo + 1, q);
+                        oB0 = r16::load_block(eb, 2 * nbo, q); oB1 = r16::load_block(eb, 2 * nbo + 1, q);
+                    }
                 }
                 r16::gemm_x2_on_pipe<false>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
                 pipe.release();
                 r16::gemm_on_pipe<false>(w0, w1, g2, pipe, lane);
                 pipe.release();
                 w0 *= wrow; w1 *= wrow;
-                if (group_ok) {
+                if (group_ok && row_ok) {
                     r16::store_block(ea, 2 * nbo, q, oA0 + a0 * w0); r16::store_block(ea, 2 * nbo + 1, q, oA1 + a1 * w1);
                     r16::store_block(eb, 2 * nbo, q, oB0 + b0 * w0); r16::store_block(eb, 2 * nbo + 1, q, oB1 + b1 * w1);
                 }
@@ -278,8 +345,8 @@
                 out3(1, nbo, sA0, sA1, sB0, sB1);
                 float vI[3][2], vJ[3][2];                // v of I[q] (source of direction A for the lane's four rows) and of J[q]
                 if (!FIRST) {
-                    const float* vp = p.v + (size_t)nIq * 3 * F + fo;
-                    const float* vq = p.v + (size_t)nJq * 3 * F + fo;
+                    const float* vp = TI_PAIR_GROUP_BASE ? v_g + (lIq * (unsigned)(3 * F) + (unsigned)fo) : p.v + (size_t)nIq * 3 * F + fo;
+                    const float* vq = TI_PAIR_GROUP_BASE ? v_g + (lJq * (unsigned)(3 * F) + (unsigned)fo) : p.v + (size_t)nJq * 3 * F + fo;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         vI[c][0] = vp[c * F]; vI[c][1] = vp[c * F + 16];
@@ -311,7 +378,8 @@
                         else
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                const float* vr = p.v + (size_t)node_of(prow_molJ(mi[r]), prow_atomJ(mi[r])) * 3 * F + c * F + fo;
+                                const float* vr = TI_PAIR_GROUP_BASE ? v_g + (lnode_of(prow_molJ(mi[r]), prow_atomJ(mi[r])) * (unsigned)(3 * F) + (unsigned)(c * F + fo))
+                                                                     : p.v + (size_t)node_of(prow_molJ(mi[r]), prow_atomJ(mi[r])) * 3 * F + c * F + fo;
                                 j0[r] = vr[0]; j1[r] = vr[16];
                             }
                     }

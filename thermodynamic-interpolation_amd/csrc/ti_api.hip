@@ -1925,6 +1925,12 @@ int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)
         HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->dsacc.p, (int)bits, N * F, h->stream));
         HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->dvacc.p, (int)bits, N * 3 * F, h->stream));
         HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->cacc.p, (int)bits, N * 3 * F, h->stream));
+        // the edge state and the parked geometry as well: every row a launch reads was written earlier in the same evaluation, and the
+        // rows the pair-major kernel skips (pairs that do not exist) are never read
+        static_assert(sizeof(*h->e.p) == 4 && sizeof(*h->enc.p) == 4 && sizeof(*h->geo.p) == 4, "32-bit fills");
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->e.p, (int)bits, h->e.n, h->stream));
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->enc.p, (int)bits, h->enc.n, h->stream));
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->geo.p, (int)bits, h->geo.n, h->stream));
         return TI_OK;
     });
 }

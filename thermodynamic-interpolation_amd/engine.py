@@ -469,7 +469,8 @@ class PainnEngine(_Engine):
         _lib.check(_lib.lib().ti_painn_debug_tap(self.h, int(stage)))
 
     def debug_poison(self, B: int, value: float):
-        """Test hook: fill the per-atom accumulators of the workspace for B molecules with `value` (first-touch test)."""
+        """Test hook: fill the per-atom accumulators of the workspace for B molecules, the edge state and the parked edge geometry
+        with `value` (first-touch accumulators, rows the pair-major kernel skips)."""
         _lib.check(_lib.lib().ti_painn_debug_poison(self.h, int(B), float(value)))
 
     def debug_read(self, what: str, B: int):

@@ -21,8 +21,6 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "thermodynamic-interpolation_amd")
 VDIR = os.path.join(PKG, "build", "variants")
-SOURCES = ["ti_api.hip", "painn_kernels.hip", "painn_edge_nb1.hip", "painn_edge_nb2.hip", "painn_edge_nb4.hip", "painn_edge_nb8.hip",
-           "painn_pair_nb1.hip", "painn_pair_nb2.hip", "painn_pair_nb4.hip", "painn_jvp_kernels.hip", "adw_kernels.hip", "ode_kernels.hip"]
 
 
 def _load_build():
@@ -34,6 +32,7 @@ def _load_build():
 
 
 BUILD = _load_build()
+SOURCES = BUILD.SOURCES                     # every unit of the product library: a variant links all of them
 
 
 def lib_of(tag):
