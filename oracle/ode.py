@@ -1,7 +1,7 @@
 """numpy restatement of the torchdiffeq 0.2.5 solvers the reference calls -- TEST INFRASTRUCTURE ONLY (see oracle/ti_oracle.c).
 
 torchdiffeq is third-party and absent from the reference checkout (ti_env.yml:14 pins 0.2.5), so this file restates its
-published algorithm: parity UNPINNED against the library itself; it pins the GPU host logic (csrc/ti_api.hip rollout_rk).
+published algorithm: parity UNPINNED against the library itself; it pins the GPU host logic (csrc/rollout.hpp rollout_rk).
   dopri5   : rk_common.py RKAdaptiveStepsizeODESolver (_runge_kutta_step, _compute_error_ratio, _optimal_step_size,
              _interp_fit/_interp_evaluate), dopri5.py tableau, misc.py _select_initial_step / _rms_norm / _mixed_norm,
              _PerturbFunc (stages with alpha == 1 are evaluated one fp32 ulp before t1), _ReverseFunc for decreasing grids.

@@ -481,7 +481,7 @@ def check_lnaff_magnitudes(name, g):
         for w_s, w_e, b, P in phi0_inputs(g):
             assert np.abs(w_e).max() < 1e-15 and np.abs(b).max() < 1e-15 and np.abs(w_s).max() > 0.05
             if "bigp" in name:
-                # the power of two of the one-accumulator format tops out at 2^60 (ti_api.hip: matrix_pow2_scale): were P scaled by
+                # the power of two of the one-accumulator format tops out at 2^60 (painn_pack.hip: matrix_pow2_scale): were P scaled by
                 # that, the LayerNorm's fp32 sum of squares over a row of P would leave the fp32 range
                 assert (P ** 2).sum(axis=1).max() * 2.0 ** 120 > np.finfo(np.float32).max
             else:

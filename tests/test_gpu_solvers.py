@@ -1,4 +1,4 @@
-"""GPU: the Runge-Kutta drivers of libti_hip.so (dopri5 / midpoint / rk4 restating torchdiffeq 0.2.5, csrc/ti_api.hip rollout_rk)
+"""GPU: the Runge-Kutta drivers of libti_hip.so (dopri5 / midpoint / rk4 restating torchdiffeq 0.2.5, csrc/rollout.hpp rollout_rk)
 against the numpy restatement of the same algorithm over the CPU oracle drift (oracle/ode.py).  torchdiffeq is absent:
 parity with the library itself is UNPINNED.  Tolerances: fixed-grid schemes follow the drift bar accumulated
 over the steps (2e-5 rel-L2 on the displacement); dopri5 may take a different accept/reject path when an error ratio sits

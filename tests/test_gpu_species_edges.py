@@ -411,7 +411,7 @@ def test_em_noise_at_261_per_entry_and_com_over_real_atoms():
 
 # ------------------------------------------------------------------------------------------- f. chunked tangent passes
 def _budget_gb(D):
-    """TI_JVP_WS_GB that makes a tangent pass with D directions per molecule hold exactly two molecules.  csrc/ti_api.hip: a pass holds
+    """TI_JVP_WS_GB that makes a tangent pass with D directions per molecule hold exactly two molecules.  csrc/painn_host.hip: a pass holds
     floor(budget / (D * bytes)) molecules, rounded down to whole groups of G, with bytes = 4 (12 A F + rows F + 3 A) per virtual
     molecule and rows = P * nblk * 16 / G edge rows per molecule.  At A = 25 on the complete graph both directed layouts have G = 1
     (600 rows in 38 blocks waste 1.3 %, within the 2 % at which the throughput layout stops growing G; the latency layout is G = 1 by

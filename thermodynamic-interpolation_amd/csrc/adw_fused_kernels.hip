@@ -1,6 +1,6 @@
 // adw_fused_kernels.hip -- a whole fixed-step adw rollout (Euler / Heun / Euler-Maruyama, 1-D handles) in one kernel launch.
 //
-// The host-driven rollout (ti_api.hip: rollout_common) launches per step the beta embedding, `net`, one or two update kernels and for EM
+// The host-driven rollout (rollout.hpp: rollout_common) launches per step the beta embedding, `net`, one or two update kernels and for EM
 // the noise kernel; x and b travel through HBM between them.  The particles are independent and the weights already stream through a
 // cyclic LDS ring, so nothing in the arithmetic needs the host between steps: here a wave keeps its 16 particles (x, and the dlogp
 // state with TAN) in registers for all n_step - 1 steps, evaluates `net` through the SAME device function as adw_mlp_kernel

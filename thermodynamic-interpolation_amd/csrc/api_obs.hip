@@ -1,0 +1,174 @@
+// api_obs.hip -- observables (ti_obs_*): collective variables of a state, importance weights, weighted histograms, and the
+// observer a rollout writes CV rows through.
+#include "ti_handle.hpp"
+
+namespace {
+
+// Validates desc [K][5] against the handle (before any device work) and uploads it with ref / select into set `which`.
+int obs_upload(ti_handle* h, int which, const int32_t* desc, int K, const float* ref, const int32_t* select)
+{
+    if (K < 1) return fail(TI_E_ARG, "K must be >= 1");
+    const int A = h->kind == 0 ? h->d.n_atoms : 1, dim = h->a_dim;
+    bool rmsd = false;
+    for (int k = 0; k < K; ++k) {
+        const int32_t* d = desc + 5 * k;
+        const int kind = d[0];
+        if (kind < TI_OBS_RMSD || kind > TI_OBS_COORD) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": unknown kind " + std::to_string(kind));
+        if (h->kind == 1) {
+            if (kind != TI_OBS_COORD) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": an adw handle takes COORD(c) only");
+            if (d[1] < 0 || d[1] >= dim) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": component outside 0.." + std::to_string(dim - 1));
+            continue;
+        }
+        if (kind == TI_OBS_COORD) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": COORD(c) is for adw handles");
+        if (kind == TI_OBS_RMSD) { rmsd = true; continue; }
+        const int na = kind == TI_OBS_DIST ? 2 : kind == TI_OBS_ANGLE ? 3 : 4;
+        for (int j = 0; j < na; ++j)
+            if (d[1 + j] < 0 || d[1 + j] >= A) return fail(TI_E_ARG, "descriptor " + std::to_string(k) + ": atom index outside 0.." + std::to_string(A - 1));
+    }
+    if (rmsd && !ref) return fail(TI_E_ARG, "an RMSD descriptor needs ref");
+    set_device(h);
+    ti_handle::ObsSet& o = h->obs[which];
+    o.K = 0;
+    o.desc.upload(std::vector<int32_t>(desc, desc + 5 * (size_t)K));
+    o.has_ref = rmsd; o.has_sel = rmsd && select;
+    if (o.has_ref) o.ref.upload(std::vector<float>(ref, ref + 3 * (size_t)A));
+    if (o.has_sel) o.sel.upload(std::vector<int32_t>(select, select + A));
+    o.K = K;
+    return TI_OK;
+}
+
+}  // namespace
+
+namespace ti {
+
+// cv_dev [B][K] = the CVs of set `which` on x_dev [B][m]; enqueued on the handle's stream
+void obs_cv_dev(ti_handle* h, int which, const float* x_dev, long long B, float* cv_dev)
+{
+    const ti_handle::ObsSet& o = h->obs[which];
+    if (h->kind == 0 && h->emask_B > 0 && B != h->emask_B)
+        throw std::invalid_argument("the molecule state in force is for " + std::to_string(h->emask_B) + " molecules, the call has " + std::to_string(B));
+    ObsCvParams p{};
+    p.x = x_dev; p.B = B; p.A = h->kind == 0 ? h->d.n_atoms : 1; p.m = obs_floats_per_traj(h); p.K = o.K;
+    p.desc = o.desc.p; p.ref = o.has_ref ? o.ref.p : nullptr; p.sel = o.has_sel ? o.sel.p : nullptr;
+    p.n_atoms = h->kind == 0 && h->ragged ? h->natoms_dev.p : nullptr;
+    p.cv = cv_dev;
+    HIP_CHECK(launch_obs_cv(p, h->stream));
+}
+
+}  // namespace ti
+
+extern "C" {
+
+int ti_obs_cv(ti_handle* h, const int32_t* desc, int32_t K, const float* ref, const int32_t* select, const float* x, int64_t B,
+              float* out_cv, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (!desc) return fail(TI_E_ARG, "desc is NULL");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 0 || (B > 0 && (!x || !out_cv))) return fail(TI_E_ARG, "NULL buffer");
+    return guarded([&]() -> int {
+        if (int rc = obs_upload(h, 0, desc, K, ref, select)) return rc;
+        if (B == 0) return TI_OK;
+        Staged sg(h, mem);
+        const float* xd = sg.in(x, h->obs_x, (size_t)B * obs_floats_per_traj(h));
+        float* od = sg.out(out_cv, h->obs_cv, (size_t)B * K);
+        obs_cv_dev(h, 0, xd, B, od);
+        sg.finish();
+        return TI_OK;
+    });
+}
+
+// (max, first bad index, sum w, sum w^2) of logw_dev into h->obs_red[0..3] and `norm`; TI_E_NAN on a non-finite entry
+static int obs_norm_dev(ti_handle* h, const float* logw_dev, long long B, double norm[4])
+{
+    hipStream_t st = h->stream;
+    grow(h->obs_red, 4 + 259);
+    grow(h->obs_part, (size_t)OBS_MAX_BLOCKS * 259);
+    HIP_CHECK(launch_obs_logw_max(h->obs_red.p, h->obs_part.p, logw_dev, B, st));
+    HIP_CHECK(hipMemcpyAsync(norm, h->obs_red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (norm[1] < (double)B) return fail(TI_E_NAN, "non-finite logw at index " + std::to_string((long long)norm[1]));
+    HIP_CHECK(launch_obs_logw_sums(h->obs_red.p + 2, h->obs_part.p, logw_dev, h->obs_red.p, B, st));
+    HIP_CHECK(hipMemcpyAsync(norm + 2, h->obs_red.p + 2, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    // the kernels that follow read (max, sum w) as one pair
+    HIP_CHECK(hipMemcpyAsync(h->obs_red.p + 1, h->obs_red.p + 2, sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return TI_OK;
+}
+
+int ti_obs_weights(ti_handle* h, const float* logw, int64_t B, float* out_w, double* out_ess, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!logw || !out_ess) return fail(TI_E_ARG, "NULL buffer");
+    return guarded([&]() -> int {
+        set_device(h);
+        Staged sg(h, mem);
+        const float* ld = sg.in(logw, h->obs_logw, (size_t)B);
+        float* wd = out_w ? sg.out(out_w, h->obs_w, (size_t)B) : nullptr;
+        double norm[4];
+        if (int rc = obs_norm_dev(h, ld, B, norm)) return rc;
+        *out_ess = norm[2] * norm[2] / norm[3];
+        if (out_w) {
+            HIP_CHECK(launch_obs_weights(wd, ld, h->obs_red.p, B, h->stream));
+            sg.finish();
+        }
+        return TI_OK;
+    });
+}
+
+int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* logw, int64_t B, int32_t n_bins, double lo, double hi,
+                double* out_hist, double* out_tails, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (n_bins < 1 || n_bins > 256) return fail(TI_E_ARG, "n_bins must be in 1..256");
+    if (!(hi > lo) || !std::isfinite(lo) || !std::isfinite(hi)) return fail(TI_E_ARG, "the range needs finite lo < hi");
+    if (B < 1 || stride < 1) return fail(TI_E_ARG, "B < 1 or stride < 1");
+    if (!values || !out_hist || !out_tails) return fail(TI_E_ARG, "NULL buffer");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const float *vd = values, *ld = logw;
+        long long sd = stride;
+        if (mem == TI_MEM_HOST) {                      // the column only: B floats, not B * stride
+            grow(h->obs_val, (size_t)B);
+            std::vector<float> col((size_t)B);
+            for (int64_t i = 0; i < B; ++i) col[i] = values[i * stride];
+            HIP_CHECK(hipMemcpy(h->obs_val.p, col.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice));
+            vd = h->obs_val.p; sd = 1;
+        }
+        if (logw) ld = Staged(h, mem).in(logw, h->obs_logw, (size_t)B);
+        double norm[4];
+        if (logw) { if (int rc = obs_norm_dev(h, ld, B, norm)) return rc; }
+        else {
+            grow(h->obs_red, 4 + 259);
+            grow(h->obs_part, (size_t)OBS_MAX_BLOCKS * 259);
+        }
+        HIP_CHECK(launch_obs_whist(h->obs_red.p + 4, h->obs_part.p, vd, sd, ld, h->obs_red.p, B, n_bins, lo, hi, st));
+        std::vector<double> out((size_t)n_bins + 3);
+        HIP_CHECK(hipMemcpyAsync(out.data(), h->obs_red.p + 4, out.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::copy(out.begin(), out.begin() + n_bins, out_hist);
+        std::copy(out.begin() + n_bins, out.end(), out_tails);
+        return TI_OK;
+    });
+}
+
+int ti_obs_set_observer(ti_handle* h, const int32_t* desc, int32_t K, const float* ref, const int32_t* select, int32_t every,
+                        float* out_cv, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (!desc) { h->obs[1].K = 0; h->obs_out = nullptr; return TI_OK; }
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (every < 0) return fail(TI_E_ARG, "every must be >= 0");
+    if (!out_cv) return fail(TI_E_ARG, "out_cv is NULL");
+    return guarded([&]() -> int {
+        if (int rc = obs_upload(h, 1, desc, K, ref, select)) return rc;
+        h->obs_every = every; h->obs_mem = mem; h->obs_out = out_cv;
+        return TI_OK;
+    });
+}
+
+}  // extern "C"

@@ -843,7 +843,7 @@ __device__ __forceinline__ void gemm_fl(f32x4& acc0, f32x4& acc1, const Opnd<NBK
 // of the fp16 subnormal range, and it is why the cross terms need their own accumulator and a v_fma per output element to fold it
 // back.  v_mfma_f32_16x16x32_f16 takes subnormal inputs at face value (tools/micro/mfma_denorm.hip), so here
 //   * the WEIGHTS of each matrix are scaled on the host by a power of two S to the top of the fp16 range (max |S w| in [2^13, 2^14):
-//     hi = fp16(S w), lo = fp16(S w - hi) is a normal number for every weight within 2^-16 of the matrix's largest), ti_api.hip;
+//     hi = fp16(S w), lo = fp16(S w - hi) is a normal number for every weight within 2^-16 of the matrix's largest), painn_pack.hip;
 //   * ACTIVATIONS are split unscaled: hi = fp16(x), lo = fp16(x - hi).  Their rows are LayerNorm / SiLU outputs, encodings or rows
 //     normalised by set_scaled: a residual below 2^-14 is resolved to 2^-24, fp32 rounding level for such a row;
 //   * hi.hi, hi.lo and lo.hi accumulate into ONE register set, which then holds S times the product: S cancels in the LayerNorm that

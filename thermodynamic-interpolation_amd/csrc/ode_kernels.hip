@@ -1,4 +1,4 @@
-// ode_kernels.hip -- elementwise pieces of the Runge-Kutta drivers (ti_api.hip): stage combinations, the scaled error /
+// ode_kernels.hip -- elementwise pieces of the Runge-Kutta drivers (rollout.hpp): stage combinations, the scaled error /
 // step-size norms of the adaptive solver (deterministic two-pass reductions), the quartic dense-output fit and evaluation.
 //
 // The adaptive solver restates torchdiffeq 0.2.5 (`dopri5`, /root/reference/ti_env.yml:14 -- third-party, not in the

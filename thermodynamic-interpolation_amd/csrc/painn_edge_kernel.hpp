@@ -51,7 +51,7 @@ __host__ __device__ constexpr int edge_superchunk(int NB, int WAVES, bool H16 = 
 __host__ __device__ constexpr int edge_chunk4(int NB, bool H16) { return (H16 ? 128 : 256) * NB; }            // float4 per weight chunk
 // F = 32 in the storage mode: a 2-chunk superchunk (4 KB) is smaller than one 16-byte lane per thread of the 8-wave build
 // Does this (feature width, precision) run the one-accumulator split format (mfma_chain.hpp: Opnd1)?  TI_PREC_F16X2 at every width;
-// ti_api.hip packs the message streams accordingly.  The F = 256 build (one wave per SIMD, operands partly in AGPRs) faulted on the
+// painn_pack.hip packs the message streams accordingly.  The F = 256 build (one wave per SIMD, operands partly in AGPRs) faulted on the
 // device (memory aperture violation in its first launch) when hipcc spilled SGPRs into VGPR lanes: painn_edge_nb8.hip is compiled
 // with -mllvm -amdgpu-spill-sgpr-to-vgpr=0 (build.py), which removes the fault.
 #ifndef TI_ONE_CHAIN_MAX_NB
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64 * WAVES, (NBK <= 8 ? 2 * 4 / WAVES : 1)) void pa
 #include "painn_edge_kernel_body.inc"
 #undef TI_ROWS_GROUP
 
-// Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words PER (group, part) (ti_api.hip: masked_rows), in which a
+// Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words PER (group, part) (painn_pack.hip: masked_rows), in which a
 // template row whose edge is absent from its molecule has slot 63 -- weight 0 in the per-atom sums, like a padding row.  The slot
 // table and with it the first-touch writes are the template's, so an atom without a present incoming edge ends with zero sums.  The
 // same multipliers as painn_edge_kernel: an all-ones mask gives its bits exactly.  Instantiated in painn_edge_mask_nb*.hip.

@@ -18,7 +18,7 @@
     PipeDMA<NB, T, SC, CH4> pipe;                                                // weights staged SC chunks per barrier
     pipe.init(reinterpret_cast<const f32x4*>(p.stream), p.nch, lds, wave, lane);   // barrier inside: vec is visible after it
 
-    // ONE: accumulators hold S times the product, S = the power of two the host scaled that matrix by (ti_api.hip).  S cancels in
+    // ONE: accumulators hold S times the product, S = the power of two the host scaled that matrix by (painn_pack.hip).  S cancels in
     // the LayerNorm behind a hidden layer (epsilon * S^2; the bias rows of `vec` are already scaled); the output products carry
     // S_phi2 * S_w2, divided out in the row masks of the per-atom sums and in the e update.
     const float eps_w0 = ONE ? 1e-5f * p.wscale[0] * p.wscale[0] : 1e-5f, eps_w1 = ONE ? 1e-5f * p.wscale[1] * p.wscale[1] : 1e-5f;

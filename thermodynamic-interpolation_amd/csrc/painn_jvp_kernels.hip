@@ -11,7 +11,7 @@
 //   virtual molecule vm = vg * G + m  <->  molecule pm = pg * G + m;   virtual node = vm * A + atom.
 // The kernels carry ONLY tangents in HBM (ts, tv, te, tP and three accumulators, laid out like their primal twins over
 // virtual molecules).  Primal state is read from the ordinary drift pipeline, which the host runs in lock step
-// (ti_api.hip: [filter pass ->] tangent edge -> primal edge -> tangent update -> primal update per layer); the primal
+// (painn_host.hip: [filter pass ->] tangent edge -> primal edge -> tangent update -> primal update per layer); the primal
 // activations a tangent needs (LayerNorm statistics, SiLU slopes, gate values) are recomputed in registers next to it, every
 // matrix product runs on a (value, tangent) operand pair against one weight chunk in LDS.
 //
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, 1) void painn_jvp_filter_kernel(const JvpFilte
 #include "painn_jvp_filter_body.inc"
 #undef TI_FILTER_ROWS_GROUP
 
-// Per-molecule edge types (ti_painn_set_molecules): p.rows holds row words per (group, part) (ti_api.hip: masked_rows), whose type bits
+// Per-molecule edge types (ti_painn_set_molecules): p.rows holds row words per (group, part) (painn_pack.hip: masked_rows), whose type bits
 // are each molecule's own.  The filter pass reads nothing else from them that a mask changes (it ignores slots).
 template <int NBK, bool SPLIT>
 __global__ __launch_bounds__(256, 1) void painn_jvp_filter_mask_kernel(const JvpFilterParams p)
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_jvp_edge_kernel
 #include "painn_jvp_edge_body.inc"
 #undef TI_ROWS_GROUP
 
-// Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words per PRIMAL (group, part) (ti_api.hip: masked_rows), in which
+// Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words per PRIMAL (group, part) (painn_pack.hip: masked_rows), in which
 // a template row whose edge is absent from its molecule has slot 63: weight 0 in the tangent sums, like a padding row.  First-touch
 // writes are the template's.  An all-ones mask gives painn_jvp_edge_kernel's bits.
 template <int NBK, bool SPLIT>

@@ -23,7 +23,7 @@
 //     per lane, no atomics.
 // Per 32 directed edges: 84 chunk products and 56 chunk visits instead of 112 and 112, six LayerNorm / SiLU / operand-split phases
 // instead of eight.  What it costs: 4 x 4 tiles cover a complete graph of A atoms with (A - 1) / (4 * ceil((A - 1) / 4)) of their rows
-// at best (ti_api.hip: build_pair_template; 85 % for 18 atoms), and every atom's accumulators are touched from ~ (A - 1) / 4 blocks.
+// at best (painn_pack.hip: build_pair_template; 85 % for 18 atoms), and every atom's accumulators are touched from ~ (A - 1) / 4 blocks.
 // Results are deterministic (one wave owns a group of molecules, fixed order); they differ from the directed kernel's by the order
 // of the per-atom sums only.
 #pragma once
@@ -56,9 +56,9 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(c
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 
-// Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words PER group (ti_api.hip: masked_rows), in which a pair absent
+// Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words PER group (painn_pack.hip: masked_rows), in which a pair absent
 // from its molecule is invalid -- zeroed through the shared w factor, like a pair that does not exist.  Both directions share that
-// factor, so the molecule's edge set must be symmetric (ti_api.hip checks it when the mask is set).  The slot table and the first-touch
+// factor, so the molecule's edge set must be symmetric (painn_host.hip checks it when the mask is set).  The slot table and the first-touch
 // writes are the template's.  Instantiated in painn_pair_mask_nb*.hip.
 template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_mask_kernel(const EdgeParams p)

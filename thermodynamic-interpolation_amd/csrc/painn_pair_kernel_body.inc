@@ -233,7 +233,7 @@
             const float* bp = vec + (EV::P_B2 + c) * F + 32 * nbo + j;
             const float* bw = vec + (EV::W_B2 + c) * F + 32 * nbo + j;
             if (TI_PAIR_SEED_BIAS) {
-                // the bias is one scalar per lane here (features on lanes) and already carries the scale of its matrix (ti_api.hip: the
+                // the bias is one scalar per lane here (features on lanes) and already carries the scale of its matrix (painn_pack.hip: the
                 // message kernel's vector block), i.e. the scale the one-accumulator products carry: it seeds the sums
                 const float p0 = bp[0], p1 = bp[16], q0 = bw[0], q1 = bw[16];
                 f32x4 a0 = {p0, p0, p0, p0}, a1 = {p1, p1, p1, p1}, b0 = a0, b1 = a1, w0 = {q0, q0, q0, q0}, w1 = {q1, q1, q1, q1};

@@ -1,0 +1,273 @@
+// ti_handle.hpp -- private header of the host side of libti_hip.so: error plumbing, device buffers, the handle behind the C ABI
+// (include/ti_hip.h), the staging of host-resident arguments, and the host functions the units call across each other:
+//   painn_pack.hip   weight packing, edge templates          painn_host.hip   PaiNN workspace, drift / divergence drivers, graph state
+//   rollout.hpp      the integrator drivers (templates)      api_*.hip        the extern "C" entry points
+//
+// There is deliberately no CPU fallback in the host code: every entry point either runs the HIP kernels or fails.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "ti_internal.hpp"
+
+namespace ti {
+
+int fail(int code, const std::string& msg);      // sets the calling thread's ti_last_error() text (api_common.hip), returns code
+
+struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };      // -> TI_E_UNSUPPORTED (guarded)
+#define HIP_CHECK(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
+    throw HipError(std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
+
+// refusals more than one entry point gives
+constexpr const char* MSG_NO_FP16_TANGENT = "the fp16 storage mode has no divergence / tangent path (use f32 or f16x2)";
+constexpr const char* MSG_TRAJ_OBSERVER = "TI_SCHEME_DOPRI5_TRAJ writes its rows per trajectory inside a kernel: detach the observer (ti_obs_set_observer)";
+constexpr const char* MSG_TAP_ENTRIES = "debug taps apply to ti_painn_drift / ti_painn_drift_jvp only";
+constexpr const char* MSG_EM_DLOGP = "dlogp is defined for a deterministic flow: EM needs eps = 0";
+
+struct MlpOff { size_t W0, b0, g0, be0, W1, b1, g1, be1, W2, b2; int f_in, f_h, f_out; };
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr; size_t n = 0;
+    void alloc(size_t count) { release(); if (count) { HIP_CHECK(hipMalloc((void**)&p, count * sizeof(T))); n = count; } }
+    void upload(const std::vector<T>& h) { alloc(h.size()); if (n) HIP_CHECK(hipMemcpy(p, h.data(), n * sizeof(T), hipMemcpyHostToDevice)); }
+    void release() { if (p) { (void)hipFree(p); p = nullptr; n = 0; } }
+    ~DevBuf() { release(); }
+};
+
+template <typename T>
+void grow(DevBuf<T>& b, size_t n) { if (b.n < n) b.alloc(n); }      // grow-on-demand scratch: never shrinks, contents are not kept
+
+struct Stream { size_t off4; int nch; };      // offset into the packed buffer in float4 units
+
+}  // namespace ti
+
+using namespace ti;
+
+// ====================================================================================================== handle
+struct ti_handle {
+    int kind = 0;                 // 0 painn, 1 adw
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t wait_ev = nullptr;          // ti_wait_stream
+    // profiling
+    bool prof = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[TI_KERNEL_COUNT];
+    // common device buffers
+    DevBuf<float> flat, packed;
+    DevBuf<int> nanflag;
+    long long cap = 0;            // trajectories the workspace is sized for
+
+    // ---- painn
+    ti_painn_desc d{};
+    int NB = 0, nE = 0, ncond = 0, G = 1, nblk = 0;
+    MlpOff embed{}, readout{}; std::vector<MlpOff> phi, w, upd; std::vector<size_t> U, V;
+    size_t edge_emb = 0, atom_emb = 0, Vr = 0; float b2_gate = 0.f;
+    Stream st_embed16{}; std::vector<Stream> st_edge, st_edge1, st_update;      // st_edge1: the message kernel's one-accumulator format (TI_PREC_F16X2)
+    // edge templates (ti_internal.hpp): [0] throughput (G molecules per group), [1] latency (G = 1, P parts per molecule);
+    // G / P / nblk / rows / slotnode below are those of the ACTIVE one (select_template, once per API call)
+    struct Tpl {
+        int G = 1, P = 1, nblk = 0;
+        DevBuf<uint32_t> rows; DevBuf<int32_t> slotnode;
+        std::vector<uint32_t> rows_h;             // host copy of `rows` (masked_rows)
+        std::vector<int> part_of, part_start, part_len;     // per sorted edge: its part; per part: first sorted edge, edges
+        std::vector<int> pos;                     // row of (molecule-in-group m, sorted edge k) inside its part: pos[m * part_len + (k - part_start)]
+        int max_slots = 0;                        // most destination atoms in any row block (<= EDGE_MAX_SLOTS)
+    } tpl[3];
+    // tpl[2]: the pair-major template (ti_internal.hpp; painn_pair_kernel.hpp), built when the graph is symmetric and the pair kernel
+    // exists for this width / precision.  pair_pos[(m * A + src) * A + dst] = e row of that directed edge of molecule-in-group m inside
+    // its group: (block * 2 + direction) * 16 + pair row
+    bool has_pair = false; std::vector<int> pair_pos; double pair_fill = 0.0;
+    DevBuf<int32_t> pair_plist; int pair_kmax = 0;     // per atom of a group: its partial-sum rows (pair_template.hpp)
+    DevBuf<float> part;                                // [groups * nblk][8][7 F] partial sums of the pair-major kernel
+    int n_tpl = 1, active = 0, parts = 1, max_slots = 0, pinned_tpl = TI_TEMPLATE_AUTO;
+    // every atom has incoming edges: the edge kernels' first touch of an accumulator replaces its contents (ti_internal.hpp
+    // SLOT_FIRST_TOUCH) and nothing zeroes the accumulators between layers or calls; otherwise the update kernel zeroes them as before
+    bool first_touch = false;
+    // per-molecule edge sets (ti_painn_set_edge_mask): [emask_B][A] words, in force for calls over emask_B molecules (0: no mask);
+    // emask_sym: every molecule's set is symmetric over the template (the pair layout is eligible).  mrows[t]: the row words of
+    // template t per (group, part) of those molecules with the absent edges switched off (masked_rows), built on first use.
+    std::vector<uint32_t> emask; long long emask_B = 0; bool emask_sym = true;
+    DevBuf<uint32_t> mrows[3]; bool mrows_ok[3] = {false, false, false};
+    // mixed species (ti_painn_set_molecules), part of the same per-molecule graph state: natoms [emask_B] atom counts (empty: all A),
+    // ptype [emask_B][A][A] edge types (empty: the template's).  ragged: some molecule has pad atoms -- only then the drift runs on
+    // parked copies of x / cond / xdot (xpark, cpark, dpark), zeroes the pad rows of its outputs, and the integrators take their
+    // ragged twins; natoms_dev is the device copy of natoms the kernels read.
+    std::vector<int32_t> natoms; std::vector<uint8_t> ptype; bool ragged = false; long long n_real = 0;
+    DevBuf<int32_t> natoms_dev; DevBuf<float> xpark, cpark, dpark;
+    struct { const uint32_t* p = nullptr; } rows; struct { const int32_t* p = nullptr; } slotnode;
+    DevBuf<int32_t> atom_ids;
+    std::vector<int> perm;        // sorted row -> original edge index
+    std::vector<int32_t> esrc, edst;       // the molecule's directed edges as passed to create
+    DevBuf<float> x, cond, s, P, v, dsacc, dvacc, cacc, e, enc, geo, b1, b2, xt, edge_vecs, edge_vecs1, upd_vecs;
+    std::vector<float> edge_scale;               // [L][6] per-matrix powers of two of the one-accumulator message streams (TI_PREC_F16X2)
+    int tap = -1; long long last_B = 0;
+    // forward-mode derivative (painn_jvp_kernels.hip): tangent twins over virtual molecules, sized on first use
+    std::vector<Stream> st_jvp_update, st_jvp_phi; Stream st_jvp_readout{}; std::vector<int> jvp_phi_pad;
+    DevBuf<float> jvp_ro_vecs, ts, tP, tv, tdsacc, tdvacc, tcacc, te, tout, wq, phist, nodest, divb, dl, dlscaled, div2;
+    long long jvp_cap = 0, last_VB = 0; int last_D = 1;
+    DevBuf<float> probes;                        // Hutchinson probes of the current call [B][k][3A] (painn_make_probes)
+    // Runge-Kutta drivers (rollout_rk): stage derivatives, dense-output coefficients, reduction scratch
+    DevBuf<float> rk_ws; DevBuf<double> rk_red;
+    // per-trajectory dopri5 (rollout_rk_traj): controller state, stage times, status words, grid, host-output staging, and the
+    // accepted / rejected counts of the last such rollout (ti_rollout_step_counts)
+    DevBuf<TrajCtl> rk_ctl; DevBuf<float> rk_tv, rk_path, rk_dpath; DevBuf<int> rk_status; DevBuf<double> rk_grid;
+    std::vector<int64_t> traj_accepted, traj_rejected;
+
+    // ---- adw
+    ti_adw_desc ad{};
+    size_t a_be_vecs = 0, a_net_vecs = 0;          // offsets of the per-MLP vector blocks in `flat`
+    float a_be_b_out = 0.f, a_b_out = 0.f;
+    int a_dim = 1;                                 // d of FCNetMultiBeta(d, d, H, L): floats per particle of x / b
+    Stream st_be{}, st_net{};
+    DevBuf<float> ax, ab1, ab2, axt, aemb_u, abeta0_u, abeta1_u, adl, ad1, ad2; DevBuf<int32_t> aidx;
+    DevBuf<float> abeta0_r, abeta1_r, aemb_r, atv;                  // per-row conditioning / beta embedding / times (per-row t)
+    // fused rollout (ti_adw_rollout_fused): embedding-table inputs [n_step * U] and the table itself, the per-step scalars, and the
+    // saved rows of a TI_MEM_HOST call (path, dlogp) ahead of their one copy
+    DevBuf<float> af_b0, af_b1, af_tv, af_emb, af_path, af_dl; DevBuf<AdwFusedStep> af_steps;
+
+    // ---- observables (ti_obs_*): descriptor sets as validated and uploaded by obs_upload -- [0] of the last ti_obs_cv call, [1] the
+    // attached observer (K == 0: none) with its row stride `every` and the caller's out_cv; staging for host buffers; fp64 scratch:
+    // red = (max, first bad index, sum w, sum w^2, hist [n_bins + 3]), part = per-block partials
+    struct ObsSet { int K = 0; bool has_ref = false, has_sel = false; DevBuf<int32_t> desc, sel; DevBuf<float> ref; } obs[2];
+    int obs_every = 0, obs_mem = TI_MEM_HOST; float* obs_out = nullptr;
+    DevBuf<float> obs_x, obs_cv, obs_val, obs_logw, obs_w; DevBuf<double> obs_red, obs_part;
+
+    ~ti_handle()
+    {
+        for (auto& v2 : ev) for (auto& pr : v2) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+        if (wait_ev) (void)hipEventDestroy(wait_ev);
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+    }
+    const float* F(size_t off) const { return flat.p + off; }
+    const float4* S(const Stream& s2) const { return reinterpret_cast<const float4*>(packed.p) + s2.off4; }
+    MlpVec vec(const MlpOff& m) const { return MlpVec{F(m.b0), F(m.g0), F(m.be0), F(m.b1), F(m.g1), F(m.be1), F(m.b2)}; }
+};
+
+namespace ti {
+
+struct Timed {           // RAII: brackets a launch with HIP events when profiling is on
+    ti_handle* h; int slot; hipEvent_t a = nullptr, b = nullptr;
+    Timed(ti_handle* h_, int slot_) : h(h_), slot(slot_)
+    {
+        if (!h->prof) return;
+        HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
+        HIP_CHECK(hipEventRecord(a, h->stream));
+    }
+    ~Timed()
+    {
+        if (!a) return;
+        (void)hipEventRecord(b, h->stream);
+        h->ev[slot].emplace_back(a, b);
+    }
+};
+
+inline void set_device(const ti_handle* h) { HIP_CHECK(hipSetDevice(h->device)); }
+
+template <typename Fn>
+int guarded(Fn&& fn)
+{
+    try { return fn(); }
+    catch (const HipError& e) { return fail(TI_E_HIP, e.what()); }
+    catch (const Unsupported& e) { return fail(TI_E_UNSUPPORTED, e.what()); }
+    catch (const std::bad_alloc&) { return fail(TI_E_ALLOC, "host allocation failed"); }
+    catch (const std::exception& e) { return fail(TI_E_ARG, e.what()); }
+}
+
+inline ti_handle* new_handle(int kind, int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw HipError("no HIP device available (libti_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
+    HIP_CHECK(hipSetDevice(device));
+    std::unique_ptr<ti_handle> h(new ti_handle());
+    h->kind = kind; h->device = device;
+    HIP_CHECK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    h->stream = h->own_stream;
+    h->nanflag.alloc(1);
+    return h.release();
+}
+
+// The arguments of one API call that live where `mem` says.  TI_MEM_DEVICE: every pointer is used as it is.  TI_MEM_HOST: in()
+// mirrors an input in a buffer of the handle (the copy is enqueued on the handle's stream at once), out() hands out the buffer to
+// compute into, and finish() copies those back in the order they were asked for.  finish() ends the call: it synchronises the stream.
+struct Staged {
+    ti_handle* h; bool host;
+    struct { void* dst; const void* src; size_t bytes; } back[2] = {}; int n_back = 0;
+    Staged(ti_handle* h_, int mem) : h(h_), host(mem == TI_MEM_HOST) {}
+    template <typename T>
+    const T* in(const T* p, DevBuf<T>& b, size_t n)
+    {
+        if (!host) return p;
+        grow(b, n);
+        if (n) HIP_CHECK(hipMemcpyAsync(b.p, p, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+        return b.p;
+    }
+    template <typename T>
+    T* out(T* p, DevBuf<T>& b, size_t n)
+    {
+        if (!host) return p;
+        grow(b, n);
+        back[n_back++] = {p, b.p, n * sizeof(T)};
+        return b.p;
+    }
+    void finish(bool copy_back = true)
+    {
+        for (int i = 0; copy_back && i < n_back; ++i) HIP_CHECK(hipMemcpyAsync(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+};
+
+struct JvpRun {            // one tangent pass riding on a drift evaluation
+    int D;                 // seed directions per molecule
+    const float* xdot;     // D explicit directions [B][D][A][3] (device; D = 1: ti_painn_drift_jvp, D = k: Hutchinson probes); NULL: unit seeds, D = 3A
+    float* tout;           // [B*D*A*3] tangent of the drift (device)
+};
+
+inline int obs_floats_per_traj(const ti_handle* h) { return h->kind == 0 ? 3 * h->d.n_atoms : h->a_dim; }
+
+// ---- painn_pack.hip
+void pack_chunk16(std::vector<float>& dst, const float* W, int ld, int n_rows, int row0, int col0, int NBK);
+void pack_chunk16_split(std::vector<float>& dst, const float* W, int ld, int n_rows, int row0, int col0, int NBK);
+size_t take_mlp(MlpOff& m, size_t o, int f_in, int f_h, int f_out);
+void pack_painn(ti_handle* h, const float* wts);
+void build_templates(ti_handle* h, const int32_t* src, const int32_t* dst, const int32_t* etype);
+bool build_pair_template(ti_handle* h, const int32_t* src, const int32_t* dst, const int32_t* etype);
+int pinned_template(const ti_handle* h);
+bool mask_blocks_pair(const ti_handle* h);
+int template_for(const ti_handle* h, long long B, bool allow_pair = true);
+void select_template(ti_handle* h, long long B, bool allow_pair = true);
+const uint32_t* masked_rows(ti_handle* h, int t);
+size_t edge_row_of(const ti_handle* h, size_t m, size_t k);
+size_t edge_rows_for(const ti_handle* h, long long B, long long copies = 1);
+
+// ---- painn_host.hip
+void ensure_painn_ws(ti_handle* h, long long B);
+void ensure_jvp_ws(ti_handle* h, long long B, int D);
+void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, float* out_dev,
+                     const JvpRun* jr = nullptr, const float* tv = nullptr, long long b0 = 0);
+void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, float* out_dev, float* div_dev,
+                         const float* tv = nullptr);
+void painn_make_probes(ti_handle* h, long long B, int k, uint64_t seed, long long traj0);
+void painn_drift_div_est_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, int k, float* out_dev,
+                             float* est_dev, const float* tv = nullptr);
+int set_graph_state(ti_handle* h, std::vector<uint32_t>& m, std::vector<int32_t>& natoms, std::vector<uint8_t>& ptype, long long B);
+void clear_graph_state(ti_handle* h);
+
+// ---- api_adw.hip, api_obs.hip: what ti_reserve and the rollout drivers need of them
+void ensure_adw_ws(ti_handle* h, long long B);
+void obs_cv_dev(ti_handle* h, int which, const float* x_dev, long long B, float* cv_dev);
+
+}  // namespace ti

@@ -12,13 +12,13 @@
 namespace ti {
 
 // ---- molecule-group edge template -------------------------------------------------------------------------------
-// Two templates are built per handle (ti_api.hip: build_templates): "throughput" (G molecules per group, P = 1: fewest padded
+// Two templates are built per handle (painn_pack.hip: build_templates): "throughput" (G molecules per group, P = 1: fewest padded
 // rows, one wave walks G*E_m rows) and "latency" (G = 1, the destination atoms of a molecule cut into P parts, each part padded
 // to whole row blocks and walked by its own wave: P times the waves for small batches).  A kernel's group index counts
 // (molecule group, part):  gi = mg * parts + part;  rows / slotnode hold [parts][nblk*16] entries.
 // slotnode word: -1 = no such slot, else  atom | molecule-in-group << 8 | SLOT_FIRST_TOUCH: this block is the first one (in the owning
 // wave's program order) that holds rows of the atom -- its sums REPLACE the accumulator contents instead of adding to them, so nobody
-// has to zero the accumulators between layers.  Set only when every atom of the graph has incoming edges (ti_api.hip).
+// has to zero the accumulators between layers.  Set only when every atom of the graph has incoming edges (painn_pack.hip).
 constexpr int32_t SLOT_FIRST_TOUCH = 1 << 30;
 __host__ __device__ inline int slot_mol(int32_t sn) { return (sn >> 8) & 0x3fffff; }
 // The E_m edges of one molecule are sorted by (dst, src); G molecules form a "group" whose G*E_m edge rows are padded
@@ -37,7 +37,7 @@ __host__ __device__ inline int row_dst(uint32_t w) { return (w >> 11) & 31; }
 __host__ __device__ inline int row_type(uint32_t w) { return (w >> 16) & 3; }
 __host__ __device__ inline int row_slot(uint32_t w) { return (w >> 18) & 63; }
 
-// ---- pair-major template (painn_pair_kernel.hpp; ti_api.hip: build_pair_template).  The filter branch w(enc(|r_ij|)) of SE3Message
+// ---- pair-major template (painn_pair_kernel.hpp; painn_pack.hip: build_pair_template).  The filter branch w(enc(|r_ij|)) of SE3Message
 // (cpainn.py:283-289) depends on the edge length only, so the edges i->j and j->i share it bit for bit.  A row block holds 16 atom PAIRS
 // laid out as a 4 x 4 tile: row 4a + b = pair (I[a], J[b]) of up to four "I" atoms and four "J" atoms (slots carry molecule-in-group and
 // atom; rows of pairs that do not exist are invalid).  Direction A is the edge I[a] -> J[b] (src I, dst J), direction B the edge
@@ -122,7 +122,7 @@ struct ReadoutParams {
 // prec = TI_PREC_* of include/ti_hip.h; with TI_PREC_F16 the state tensors s, P, v, e behind the float* fields are fp16
 hipError_t launch_embed(int NB, int nseg, int prec, const EmbedParams& p, hipStream_t st);
 // masked: the masked twins of the message kernels (per-molecule edge sets, ti_painn_set_edge_mask); p.rows then holds row words per
-// (group, part) instead of the template's (ti_api.hip: masked_rows)
+// (group, part) instead of the template's (painn_pack.hip: masked_rows)
 hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false);
 bool edge_uses_one_chain(int NB, int prec);      // message kernel on the one-accumulator split format (painn_edge_kernel.hpp: edge_one_chain)
 // pair-major message kernel (painn_pair_kernel.hpp): same EdgeParams, rows / slotnode of the pair template, same weight stream
@@ -214,7 +214,7 @@ hipError_t launch_adw(int NB, bool split, const AdwParams& p, hipStream_t st);
 hipError_t configure_adw_kernels(int NB, int max_hidden, int dim);
 
 // ---- fused adw rollout (adw_fused_kernels.hip; include/ti_hip.h ti_adw_rollout_fused): one launch runs all n_step - 1 steps of a 1-D
-// handle.  The host fills the per-step scalars with the fp32 expressions of rollout_common (ti_api.hip); the kernel computes none.
+// handle.  The host fills the per-step scalars with the fp32 expressions of rollout_common (rollout.hpp); the kernel computes none.
 enum { ADW_FUSED_EULER = 0, ADW_FUSED_HEUN = 1, ADW_FUSED_EM = 2 };       // EM: Euler plus the noise term (eps > 0)
 struct AdwFusedStep {                       // step k: t_grid[k] -> t_grid[k + 1]
     float t, t_next;                        // t_grid[k], t_grid[k + 1]
@@ -283,7 +283,7 @@ hipError_t launch_interp_fit(float* coef /*[5][n]*/, const float* y0, const floa
                              float dt, long long n, hipStream_t st);
 hipError_t launch_interp_eval(float* out, const float* coef, float x, long long n, hipStream_t st);
 
-// ---- per-trajectory dopri5 (ode_kernels.hip; driver: ti_api.hip rollout_rk_traj).  Every trajectory b runs the shared algorithm
+// ---- per-trajectory dopri5 (ode_kernels.hip; driver: rollout.hpp rollout_rk_traj).  Every trajectory b runs the shared algorithm
 // on its own: segment s holds m_s floats per trajectory (segment 0: x, 3A or 1; segment 1: its dlogp entry, m = 1), laid out
 // trajectory-major.  Controller state is fp64 in the integration variable s = sign * t.  A trajectory whose interval has passed the
 // last grid time is frozen: its state, k and path rows are never written again (it still rides along in the batched drift launches).

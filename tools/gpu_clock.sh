@@ -1,6 +1,6 @@
 #!/bin/bash
 # In-kernel clock of the message kernels (MI355X guide, DVFS item 6): diagnostic build with (s_memtime, s_memrealtime) stamps around the
-# block loop of every wave (variant libti_hip_stamps.so: tools/variant_bench.py build "stamps:-DTI_STAMPS+ONLY=..."), ~2 s of back-to-back
+# block loop of every wave (variant libti_hip_stamps.so: tools/variant_bench.py build "stamps:-DTI_STAMPS+ONLY=painn_host.hip+ONLY=<message kernel units>"), ~2 s of back-to-back
 # launches on the bench data per arm; the clock is the median over the waves of layer 2's launch of the LAST evaluations.
 #   usage: tools/gpu_clock.sh TAG
 set -o pipefail
