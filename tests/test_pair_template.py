@@ -19,18 +19,17 @@ def dump(tmp_path_factory):
         out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split("\n")
         if out[0].strip() == "none":
             return None
-        _, G, nblk, kmax = out[0].split()
-        G, nblk, kmax = int(G), int(nblk), int(kmax)
+        _, G, nblk = out[0].split()
+        G, nblk = int(G), int(nblk)
         rows = np.array(out[1].split(), dtype=np.int64).reshape(nblk, 16)
         slots = np.array(out[2].split(), dtype=np.int64).reshape(nblk, 16)
         pos = np.array(out[3].split(), dtype=np.int64).reshape(G, A, A)
-        plist = np.array(out[4].split(), dtype=np.int64).reshape(G, A, kmax)
-        return G, nblk, rows, slots, pos, plist
+        return G, nblk, rows, slots, pos
     return run
 
 
 def check_template(A, src, dst, et, tpl):
-    G, nblk, rows, slots, pos, plist = tpl
+    G, nblk, rows, slots, pos = tpl
     etype = {(s, d): t for s, d, t in zip(src, dst, et)}
     seen, owner = set(), {}
     for b in range(nblk):
@@ -57,16 +56,16 @@ def check_template(A, src, dst, et, tpl):
                         seen.add(e)
                     assert pos[mI, aI, aJ] == (2 * b) * 16 + 4 * a + c and pos[mI, aJ, aI] == (2 * b + 1) * 16 + 4 * a + c
     assert seen == {(m, s, d) for m in range(G) for s, d in zip(src, dst)}            # every directed edge of every molecule exactly once
-    # the partial lists: every occupied (block, slot) appears in exactly one list, its atom's, in walk order
-    listed = {}
-    for m in range(G):
-        for a in range(A):
-            ids = [int(v) for v in plist[m, a] if v >= 0]
-            assert ids == sorted(ids) and list(plist[m, a][:len(ids)]) == ids              # -1 only as padding at the end
-            for i in ids:
-                assert i not in listed
-                listed[i] = (m, a)
-    assert listed == owner
+    # first touch: of an atom's occupied (block, slot) places in walk order -- blocks ascending, inside a block the J slots 4..7 before the
+    # I slots 0..3 -- exactly the first carries bit 30 (PAIR_SLOT_FIRST_TOUCH: that update replaces the accumulator, the later ones
+    # add); no other slot word does
+    walk = [8 * b + k for b in range(nblk) for k in (4, 5, 6, 7, 0, 1, 2, 3) if 8 * b + k in owner]
+    first = {}
+    for place in walk:
+        first.setdefault(owner[place], place)
+    assert set(first) == set(owner.values())
+    marked = {8 * b + k for b in range(nblk) for k in range(16) if slots[b, k] >= 0 and int(slots[b, k]) >> 30 & 1}
+    assert marked == set(first.values())
     return sum(int(w) & 1 for w in rows.ravel()) / (nblk * 16.0)
 
 

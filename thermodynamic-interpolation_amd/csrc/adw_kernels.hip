@@ -5,6 +5,7 @@
 // (beta_embed: inputs [beta0, beta1, t], n_hidden = 1;  net: inputs [x, t, beta_embed], n_hidden = num_layers-1),
 // so one kernel serves both: hidden activations stay in registers, H x H layers on the matrix cores.
 #include "adw_device.hpp"
+#include "dispatch.hpp"
 #include "mfma_chain.hpp"
 #include "ti_internal.hpp"
 
@@ -199,63 +200,38 @@ static size_t adw_vec_floats(int H, int n_hidden, int dim)
 size_t adw_vec_floats_host(int H, int n_hidden, int dim) { return adw_vec_floats(H, n_hidden, dim); }
 static size_t adw_lds_bytes(int NB, int n_hidden, int dim = 1) { return 2 * (size_t)256 * NB * 16 + adw_vec_floats(32 * NB, n_hidden, dim) * 4; }
 
-#define TI_DISPATCH_NB(NBv, ...) \
-    switch (NBv) {                                                            \
-        case 1: { constexpr int NB = 1; __VA_ARGS__; } break;                 \
-        case 2: { constexpr int NB = 2; __VA_ARGS__; } break;                 \
-        case 4: { constexpr int NB = 4; __VA_ARGS__; } break;                 \
-        case 8: { constexpr int NB = 8; __VA_ARGS__; } break;                 \
-        default: return hipErrorInvalidValue;                                 \
-    }
-
-template <int NBK>
-static hipError_t adw_set_attrs(size_t bytes)
+// The visitor of the family: f(kernel) for every build the values select (EVERY: all of them, dispatch.hpp), until one returns an
+// error.  Every width has the 1-D and the d-dimensional net (nd), each x SPLIT x TAN (with the divergence).  hipErrorInvalidValue: no such width.
+template <class F>
+static hipError_t with_adw_builds(int NB, int nd, int split, int tan, F&& f)
 {
-    hipError_t e;
-#define TI_SET(k) if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) != hipSuccess) return e
-    TI_SET((adw_mlp_kernel<NBK, false, false>)); TI_SET((adw_mlp_kernel<NBK, true, false>));
-    TI_SET((adw_mlp_kernel<NBK, false, true>)); TI_SET((adw_mlp_kernel<NBK, true, true>));
-    constexpr int G = adw_tan_group(NBK);
-    TI_SET((adw_mlp_nd_kernel<NBK, false, false, G>)); TI_SET((adw_mlp_nd_kernel<NBK, true, false, G>));
-    TI_SET((adw_mlp_nd_kernel<NBK, false, true, G>)); TI_SET((adw_mlp_nd_kernel<NBK, true, true, G>));
-#undef TI_SET
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    bool any = false;
+    dispatch_int<1, 2, 4, 8>(NB, [&](auto nc) { dispatch_bool(nd, [&](auto dc) { dispatch_bool(split, [&](auto sc) { dispatch_bool(tan, [&](auto tc) {
+        constexpr int NBK = 2 * decltype(nc)::value;
+        constexpr bool ND = decltype(dc)::value, SPLIT = decltype(sc)::value, TAN = decltype(tc)::value;
+        any = true;
+        if (e != hipSuccess) return;
+        if constexpr (ND) e = f(adw_mlp_nd_kernel<NBK, SPLIT, TAN, adw_tan_group(NBK)>);
+        else e = f(adw_mlp_kernel<NBK, SPLIT, TAN>);
+    }); }); }); });
+    return any ? e : hipErrorInvalidValue;
 }
 
-hipError_t configure_adw_kernels(int NBv, int max_hidden, int dim)
+hipError_t configure_adw_kernels(int NB, int max_hidden, int dim)
 {
-    TI_DISPATCH_NB(NBv, return (adw_set_attrs<2 * NB>(std::max(adw_lds_bytes(NB, max_hidden), adw_lds_bytes(NB, max_hidden, dim)))));
-    return hipSuccess;
+    const size_t bytes = std::max(adw_lds_bytes(NB, max_hidden), adw_lds_bytes(NB, max_hidden, dim));
+    return with_adw_builds(NB, EVERY, EVERY, EVERY, [&](auto kernel) { return set_lds(kernel, bytes); });
 }
 
-hipError_t launch_adw(int NBv, bool split, const AdwParams& p, hipStream_t st)
+hipError_t launch_adw(int NB, bool split, const AdwParams& p, hipStream_t st)
 {
-    TI_DISPATCH_NB(NBv, {
-        const dim3 g((unsigned)((p.B + 63) / 64));
-        const bool tanv = p.out_div != nullptr;
-        if (p.dim > 1) {
-            if (p.dim > ADW_MAX_DIM) return hipErrorInvalidValue;
-            const size_t l = adw_lds_bytes(NB, p.n_hidden, p.dim);
-            constexpr int G = adw_tan_group(2 * NB);
-            if (split) {
-                if (tanv) hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, true, true, G>), g, dim3(256), l, st, p);
-                else hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, true, false, G>), g, dim3(256), l, st, p);
-            } else {
-                if (tanv) hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, false, true, G>), g, dim3(256), l, st, p);
-                else hipLaunchKernelGGL((adw_mlp_nd_kernel<2 * NB, false, false, G>), g, dim3(256), l, st, p);
-            }
-            break;
-        }
-        const size_t l = adw_lds_bytes(NB, p.n_hidden);
-        if (split) {
-            if (tanv) hipLaunchKernelGGL((adw_mlp_kernel<2 * NB, true, true>), g, dim3(256), l, st, p);
-            else hipLaunchKernelGGL((adw_mlp_kernel<2 * NB, true, false>), g, dim3(256), l, st, p);
-        } else {
-            if (tanv) hipLaunchKernelGGL((adw_mlp_kernel<2 * NB, false, true>), g, dim3(256), l, st, p);
-            else hipLaunchKernelGGL((adw_mlp_kernel<2 * NB, false, false>), g, dim3(256), l, st, p);
-        }
+    if (p.dim > ADW_MAX_DIM) return hipErrorInvalidValue;
+    const size_t l = adw_lds_bytes(NB, p.n_hidden, p.dim > 1 ? p.dim : 1);
+    return with_adw_builds(NB, p.dim > 1, split, p.out_div != nullptr, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((p.B + 63) / 64)), dim3(256), l, st, p);
+        return hipGetLastError();
     });
-    return hipGetLastError();
 }
 
 // ================================================================================================== integrator

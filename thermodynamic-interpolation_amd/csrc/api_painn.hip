@@ -54,7 +54,7 @@ ti_handle* ti_painn_create(const ti_painn_desc* d, const float* weights, size_t 
         h->flat.upload(flat);
         h->atom_ids.upload(std::vector<int32_t>(atom_ids, atom_ids + A));
         build_templates(h.get(), edge_src, edge_dst, edge_type);
-        h->has_pair = pair_kernel_exists(h->NB, d->precision) && build_pair_template(h.get(), edge_src, edge_dst, edge_type);
+        h->has_pair = pair_build_exists(h->NB, 4, d->precision) && build_pair_template(h.get(), edge_src, edge_dst, edge_type);
         select_template(h.get(), 1 << 20);
         pack_painn(h.get(), weights);
         HIP_CHECK(configure_painn_kernels(h->NB));

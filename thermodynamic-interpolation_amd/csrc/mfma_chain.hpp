@@ -32,9 +32,6 @@ struct Act {
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
-// row of the 32x32 accumulator held in register i of lane-half h
-__device__ __forceinline__ constexpr int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
 // ---- cross-lane exchanges on the VALU (gfx950 v_permlane16_swap / v_permlane32_swap), never through the LDS crossbar.
 //   swap16(a, b): the odd 16-lane rows of a <-> the even rows of b;   swap32(a, b): rows 2,3 of a <-> rows 0,1 of b.
 // Why not __shfl_xor (ds_bpermute_b32): a ds_bpermute that is still outstanding when EXEC is narrowed returns wrong data on
@@ -60,7 +57,6 @@ __device__ __forceinline__ long long xcd_swizzle(unsigned b, unsigned n)
     return (x < r ? (long long)x * (q + 1) : (long long)r * (q + 1) + (long long)(x - r) * q) + i;
 }
 
-// v + (the value of the lane 32 away), in every lane
 // 1 / sqrt(x) for the LayerNorm scale: v_rsq_f32 (1 ulp) and one Newton step -- 5 instructions, within an ulp of the correctly rounded
 // quotient; `1.0f / sqrtf(x)` compiles to ~25 (IEEE square root + IEEE division fix-ups) once per row and LayerNorm.
 __device__ __forceinline__ float rsqrt_nr(float x)
@@ -68,6 +64,7 @@ __device__ __forceinline__ float rsqrt_nr(float x)
     const float r = __builtin_amdgcn_rsqf(x);
     return r * __builtin_fmaf(-0.5f * x * r, r, 1.5f);
 }
+// v + (the value of the lane 32 away), in every lane
 __device__ __forceinline__ float xhalf_sum(float v)
 {
     float a = v, b = v;
@@ -143,32 +140,16 @@ struct Pipe {
 // staging registers, no ds_write.  The DMA is issued when the first logical chunk of the current superchunk is released
 // (hipcc drains vmcnt(0) at the next use of an ordinary global load while a DMA is in flight, so it is kept away from
 // the GEMM prologues), and is waited for at the superchunk's closing barrier.
-// STAGGER (8-wave workgroups: waves w and w + 4 share a SIMD).  With one barrier per superchunk all eight waves run in lock step:
-// both waves of a SIMD sit in their matrix phase together (the pipe is contended, the VALU idles) and then in their LayerNorm /
-// product / reduction phase together (the VALU is contended, the matrix pipe idles) -- in-kernel stamps of the message kernel show a
-// hidden layer taking 16 k cycles per pair of waves for 6 k cycles of matrix work and 9 k of vector work (profiles/r03c_*).  With
-// STAGGER the first-dispatched half of the waves DEFERS the barrier that closes a superchunk to its next acquire(), i.e. to behind the
-// vector phase that follows the products, while the second half keeps it right behind the products: between two barriers the early
-// half runs [products k | vector phase k], the late half [vector phase k-1 | products k] -- the partners of a SIMD are half a phase
-// apart, one on the matrix pipe while the other is on the VALU.  Every wave still executes exactly one barrier per superchunk, both
-// halves read the SAME buffer between two barriers (two buffers suffice), and the prefetch of superchunk k+1 goes to the buffer
-// every wave left before the previous barrier.
-// NBUF buffers: the superchunk that is NBUF - 1 ahead is requested when the first chunk of the current one is released.  In-kernel
-// stamps of the message kernels (profiles/r03c_*) showed every 4-chunk product phase lasting ~7.5 k cycles whatever its matrix work
-// (3 k for the single products, 6 k for the lock-step pair): with two buffers the 64 KB a workgroup requests per superchunk have
-// three chunk times to arrive, and at full occupancy an LDS-DMA of that size takes ~5 k cycles from issue to landed, so the interval
-// between two barriers was the transfer's latency, not the products.  Closing superchunk k only needs superchunk k+1: the wait is
-// `vmcnt((NBUF - 2) * PER)` -- the counter is in issue order, and the NBUF - 2 younger requests (and any younger loads / stores)
-// may stay in flight.
-template <int NB, int T, int SC, int CHUNK4 = 256 * NB, bool STAGGER = false, int NBUF = 2>      // CHUNK4: float4 per chunk (128 * NB for the hi-only chunks of the fp16 storage mode)
+// (A closing barrier deferred by half the waves of an 8-wave workgroup, and a ring deeper than two buffers, were both measured and
+// lost: DESIGN.md 3.6.)
+template <int NB, int T, int SC, int CHUNK4 = 256 * NB>      // CHUNK4: float4 per chunk (128 * NB for the hi-only chunks of the fp16 storage mode)
 struct PipeDMA {
-    static constexpr int CH4 = CHUNK4, SUP4 = CH4 * SC, PER = SUP4 / T;
+    static constexpr int CH4 = CHUNK4, SUP4 = CH4 * SC, PER = SUP4 / T, NBUF = 2;
     static_assert(SUP4 % T == 0, "superchunk must be a multiple of the workgroup's 16-byte lanes");
-    static_assert(NBUF >= 2 && (NBUF - 2) * PER <= 48, "in-flight requests must fit the 6-bit vmcnt");
     const f32x4* __restrict__ g;
     f32x4* base;
     int nsup, idx, ahead, buf, sub, wave, lane;       // idx: superchunk being consumed, ahead: the next one to request, buf = idx % NBUF
-    bool defer, pending;                    // STAGGER: this wave closes superchunks lazily / a close is outstanding
+                                                      // (nothing reads idx; without it hipcc's code for painn_readout16_kernel<2, 0> changes: DESIGN.md 6 item 5)
 
     __device__ __forceinline__ void dma(const f32x4* src, f32x4* dst) const
     {
@@ -183,32 +164,24 @@ struct PipeDMA {
     {
         g = stream; nsup = n_chunks / SC; idx = 0; buf = 0; sub = 0; wave = wave_; lane = lane_;
         base = lds;
-        defer = STAGGER && wave_ < T / 128;               // the first half of the waves (SIMD partners are w and w + T/128)
-        pending = false;
-        ahead = 0;
-#pragma unroll
-        for (int b = 0; b < NBUF - 1; ++b) {               // superchunks 0 .. NBUF-2 (the stream is cyclic)
-            dma(g + (size_t)ahead * SUP4, base + b * SUP4);
-            ahead = (ahead + 1 == nsup) ? 0 : ahead + 1;
-        }
+        dma(g, base);                                     // superchunk 0 (the stream is cyclic)
+        ahead = (1 == nsup) ? 0 : 1;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
     __device__ __forceinline__ void close()
     {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * PER) : "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
     // Call once at the very end of a kernel: the last release() has a prefetch in flight that nobody will consume, and an
     // LDS-DMA still in flight when the workgroup retires lands in LDS that may already belong to the next workgroup.
     __device__ __forceinline__ void drain()
     {
-        if (STAGGER && pending) { close(); pending = false; }          // every wave executes the same number of barriers
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __device__ __forceinline__ const f32x4* acquire()
     {
-        if (STAGGER && pending) { close(); pending = false; }
         return base + buf * SUP4 + sub * CH4;
     }
     __device__ __forceinline__ void release()
@@ -218,8 +191,7 @@ struct PipeDMA {
             ahead = (ahead + 1 == nsup) ? 0 : ahead + 1;
         }
         if (++sub == SC) {
-            if (STAGGER && defer) pending = true;
-            else close();
+            close();
             idx = (idx + 1 == nsup) ? 0 : idx + 1;
             buf = (buf + 1 == NBUF) ? 0 : buf + 1; sub = 0;
         }
@@ -286,43 +258,12 @@ __device__ __forceinline__ void store_block(float* __restrict__ p, int nb, int h
         *reinterpret_cast<f32x4*>(p + 32 * nb + 8 * g + 4 * h) = t;
     }
 }
-// the same for state tensors that may be fp16 in HBM (H16: the fp16 storage mode); elem0 = element offset of feature 0 of the row
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-template <bool H16>
-__device__ __forceinline__ f32x16 load_block_t(const float* base, size_t elem0, int nb, int h)
-{
-    if constexpr (!H16) return load_block(base + elem0, nb, h);
-    f32x16 r;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const half4 t = *reinterpret_cast<const half4*>(reinterpret_cast<const _Float16*>(base) + elem0 + 32 * nb + 8 * g + 4 * h);
-        r[4 * g + 0] = (float)t[0]; r[4 * g + 1] = (float)t[1]; r[4 * g + 2] = (float)t[2]; r[4 * g + 3] = (float)t[3];
-    }
-    return r;
-}
-template <bool H16>
-__device__ __forceinline__ void store_block_t(float* base, size_t elem0, int nb, int h, const f32x16& r)
-{
-    if constexpr (!H16) { store_block(base + elem0, nb, h, r); return; }
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<half4*>(reinterpret_cast<_Float16*>(base) + elem0 + 32 * nb + 8 * g + 4 * h) =
-            half4{(_Float16)r[4 * g + 0], (_Float16)r[4 * g + 1], (_Float16)r[4 * g + 2], (_Float16)r[4 * g + 3]};
-}
-
 template <int NB>
 __device__ __forceinline__ void load_set(Act<NB>& a, const float* __restrict__ p, int h)
 {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) a.b[nb] = load_block(p, nb, h);
 }
-template <int NB>
-__device__ __forceinline__ void store_set(float* __restrict__ p, int h, const Act<NB>& a)
-{
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) store_block(p, nb, h, a.b[nb]);
-}
-
 // ------------------------------------------------------------------------------------------------ elementwise pieces
 // x * sigmoid(x); v_exp_f32 / v_rcp_f32 are ~1 ulp, far below the 1e-5 parity bar
 __device__ __forceinline__ float silu(float y) { return y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)); }
@@ -396,21 +337,6 @@ __device__ __forceinline__ void posenc_set(Act<NB>& a, float x_over_len, int h)
             a.b[nb][4 * g + 0] = c1; a.b[nb][4 * g + 1] = s1; a.b[nb][4 * g + 2] = c2; a.b[nb][4 * g + 3] = s2;
         }
 }
-
-// dot of a register set with a natural-order vector, summed over all F features of the row
-template <int NB>
-__device__ __forceinline__ float dot_set(const Act<NB>& a, const float* __restrict__ vec, int h)
-{
-    float acc = 0.f;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const f32x16 w = load_block(vec, nb, h);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc = fmaf(a.b[nb][i], w[i], acc);
-    }
-    return xhalf_sum(acc);
-}
-
 
 // ================================================================================================================
 // 16-row variant (namespace r16): the same chaining scheme on v_mfma_f32_16x16x4_f32 (same FLOP rate as 32x32x2).
@@ -675,13 +601,10 @@ __device__ __forceinline__ float xquarters_max(float v)
 // one pair back to back lost low halves now and then (tangent taps off by 4e-5; the probe, with other instructions in between, saw
 // nothing).  Here two pairs are interleaved and the block begins and ends with s_nop: at least two issue slots between every half
 // write and the next read of that register, one in front of the first read of the packed hi pairs.  With it the tangent taps meet
-// their 1e-5 bar with this form in every kernel (tests/test_gpu_divergence.py).  -DTI_SPLIT_REFERENCE=1 builds the 12-instruction
-// form; its drift differs from this one's by 2.5e-7 (|b| ~ 0.1) although the probe finds the same bits for the same input: under
-// hipcc's default -ffp-contract=fast the reference form's `v - hi` fuses with the multiplication that produced v (SiLU's y * rcp),
-// i.e. it splits the unrounded product, while this form splits the rounded fp32 value it is given.
-#ifndef TI_SPLIT_REFERENCE
-#define TI_SPLIT_REFERENCE 0
-#endif
+// their 1e-5 bar with this form in every kernel (tests/test_gpu_divergence.py).  In a kernel the 12-instruction form gives a
+// drift that differs from this one's by 2.5e-7 (|b| ~ 0.1) although the probe finds the same bits for the same input: under
+// hipcc's default -ffp-contract=fast its `v - hi` fuses with the multiplication that produced v (SiLU's y * rcp), i.e. it splits
+// the unrounded product, while this form splits the rounded fp32 value it is given.
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // v[0..3] -> packed fp16 pairs (hi01, hi23) and their scaled residuals (lo01, lo23), as dwords: the operand registers are assembled
@@ -693,23 +616,17 @@ __device__ __forceinline__ void split_quad(const f32x4& v, unsigned& hi01, unsig
 {
     hi01 = __builtin_bit_cast(unsigned, h2{(_Float16)v[0], (_Float16)v[1]});
     hi23 = __builtin_bit_cast(unsigned, h2{(_Float16)v[2], (_Float16)v[3]});
-    if constexpr (TI_SPLIT_REFERENCE) {
-        const h2 a = __builtin_bit_cast(h2, hi01), b = __builtin_bit_cast(h2, hi23);
-        lo01 = __builtin_bit_cast(unsigned, h2{(_Float16)((v[0] - (float)a[0]) * 2048.0f), (_Float16)((v[1] - (float)a[1]) * 2048.0f)});
-        lo23 = __builtin_bit_cast(unsigned, h2{(_Float16)((v[2] - (float)b[0]) * 2048.0f), (_Float16)((v[3] - (float)b[1]) * 2048.0f)});
-    } else {
-        const f32x4 s = v * 2048.0f;
-        const float c = -2048.0f;
-        asm("s_nop 0\n\t"
-            "v_fma_mixlo_f16 %0, %2, %4, %5 op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mixlo_f16 %1, %3, %4, %7 op_sel_hi:[1,0,0]\n\t"
-            "s_nop 0\n\t"
-            "v_fma_mixhi_f16 %0, %2, %4, %6 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mixhi_f16 %1, %3, %4, %8 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-            "s_nop 1"
-            : "=&v"(lo01), "=&v"(lo23)
-            : "v"(hi01), "v"(hi23), "s"(c), "v"(s[0]), "v"(s[1]), "v"(s[2]), "v"(s[3]));
-    }
+    const f32x4 s = v * 2048.0f;
+    const float c = -2048.0f;
+    asm("s_nop 0\n\t"
+        "v_fma_mixlo_f16 %0, %2, %4, %5 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixlo_f16 %1, %3, %4, %7 op_sel_hi:[1,0,0]\n\t"
+        "s_nop 0\n\t"
+        "v_fma_mixhi_f16 %0, %2, %4, %6 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mixhi_f16 %1, %3, %4, %8 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "s_nop 1"
+        : "=&v"(lo01), "=&v"(lo23)
+        : "v"(hi01), "v"(hi23), "s"(c), "v"(s[0]), "v"(s[1]), "v"(s[2]), "v"(s[3]));
 }
 
 template <int NBK, bool SPLIT>
@@ -795,17 +712,15 @@ struct Opnd<NBK, true> {                        // split operand: hi and scaled-
 };
 
 // chunk image: [(blk*(NBK/2) + m)*2 + {0: hi, 1: lo}][lane] of 16-byte h8, i.e. 2*KS "steps" of two fragments each, contiguous.
-// One step = 3 MFMAs (48 matrix cycles) on one (hi, lo) weight fragment pair.  The fragments of step s + TI_FRAG_AHEAD are read
+// One step = 3 MFMAs (48 matrix cycles) on one (hi, lo) weight fragment pair.  The fragments of step s + 1 are read
 // from LDS before the MFMAs of step s issue; the scheduling barriers pin that order (hipcc otherwise sinks each read to just
 // in front of its own MFMAs and waits lgkmcnt(0) there: the wave then sits through a full LDS latency every 48 matrix
 // cycles).  The barrier mask lets VALU / SALU / VMEM instructions cross, DS reads and MFMAs not.
-#ifndef TI_FRAG_AHEAD
-#define TI_FRAG_AHEAD 1
-#endif
+constexpr int FRAG_AHEAD = 1;
 template <int NBK, bool FLIP>
 __device__ __forceinline__ void gemm_split_chunk(f32x4& acc0, f32x4& acc1, const Opnd<NBK, true>& in, const h8* wl, int lane)
 {
-    constexpr int KS = NBK / 2, STEPS = 2 * KS, AH = TI_FRAG_AHEAD < STEPS ? TI_FRAG_AHEAD : STEPS;
+    constexpr int KS = NBK / 2, STEPS = 2 * KS, AH = FRAG_AHEAD < STEPS ? FRAG_AHEAD : STEPS;
     f32x4 x0 = {0, 0, 0, 0}, x1 = {0, 0, 0, 0};
     h8 fh[AH + 1], fl[AH + 1];                       // ring of fragment pairs, statically indexed after unrolling
 #pragma unroll
@@ -902,7 +817,7 @@ struct Opnd1 {
 template <int NBK, bool FLIP>
 __device__ __forceinline__ void gemm_split_chunk1(f32x4& acc0, f32x4& acc1, const Opnd1<NBK>& in, const h8* wl, int lane)
 {
-    constexpr int KS = NBK / 2, STEPS = 2 * KS, AH = TI_FRAG_AHEAD < STEPS ? TI_FRAG_AHEAD : STEPS;
+    constexpr int KS = NBK / 2, STEPS = 2 * KS, AH = FRAG_AHEAD < STEPS ? FRAG_AHEAD : STEPS;
     h8 fh[AH + 1], fl[AH + 1];
 #pragma unroll
     for (int s = 0; s < AH; ++s) { fh[s] = wl[(2 * s) * 64 + lane]; fl[s] = wl[(2 * s + 1) * 64 + lane]; }
@@ -932,7 +847,7 @@ template <int NBK, bool FLIP>
 __device__ __forceinline__ void gemm_split_chunk1_x2(f32x4& a0, f32x4& a1, f32x4& b0, f32x4& b1, const Opnd1<NBK>& inA, const Opnd1<NBK>& inB,
                                                      const h8* wl, int lane)
 {
-    constexpr int KS = NBK / 2, STEPS = 2 * KS, AH = TI_FRAG_AHEAD < STEPS ? TI_FRAG_AHEAD : STEPS;
+    constexpr int KS = NBK / 2, STEPS = 2 * KS, AH = FRAG_AHEAD < STEPS ? FRAG_AHEAD : STEPS;
     h8 fh[AH + 1], fl[AH + 1];
 #pragma unroll
     for (int s = 0; s < AH; ++s) { fh[s] = wl[(2 * s) * 64 + lane]; fl[s] = wl[(2 * s + 1) * 64 + lane]; }
@@ -1075,35 +990,6 @@ template <int NBK>
 __device__ __forceinline__ void gemm_bt(f32x4& acc0, f32x4& acc1, const Opnd<NBK, false>& in, const f32x4* wl, int lane) { gemm_bt(acc0, acc1, in.a, wl, lane); }
 template <int NBK>
 __device__ __forceinline__ void gemm_fl(f32x4& acc0, f32x4& acc1, const Opnd<NBK, false>& in, const f32x4* wl, int lane) { gemm_fl(acc0, acc1, in.a, wl, lane); }
-
-// ---- per-slot row sums of a flipped-layout block as a 16x16 selection product  S[slot][n] = sum_row Sel[slot][row] val[row][n].
-// sel[r] (A operand: lane (slot, q) holds row 4q + r) is 1 where the row's destination is that slot; val (B operand) is the
-// accumulator layout itself (lane (n, q) holds rows 4q + r).  Exact products, fixed summation order -> deterministic.
-// f32: four 16x16x4 products (32 matrix cycles each).  Split mode: the values go through the fp16 pipe as hi + 2^-11 lo, the
-// 0/1 selector is exact in fp16: two 16x16x16 products instead -- the selection sums were a quarter of the split kernel's
-// matrix cycles.
-template <bool SPLIT>
-__device__ __forceinline__ f32x4 select_sum(const f32x4& sel, const f32x4& v)
-{
-    if (SPLIT) {
-        h4 sh, hi, lo;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sh[r] = (_Float16)sel[r];
-            const _Float16 h = (_Float16)v[r];
-            hi[r] = h;
-            lo[r] = (_Float16)((v[r] - (float)h) * 2048.0f);
-        }
-        const f32x4 z = {0, 0, 0, 0};
-        const f32x4 a = __builtin_amdgcn_mfma_f32_16x16x16f16(sh, hi, z, 0, 0, 0);
-        const f32x4 b = __builtin_amdgcn_mfma_f32_16x16x16f16(sh, lo, z, 0, 0, 0);
-        return a + b * 4.8828125e-4f;
-    }
-    f32x4 s = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) s = mfma16(sel[r], v[r], s);
-    return s;
-}
 
 // ---- per-slot row sums of flipped-layout blocks without the matrix core.  A block of 16 edge rows holds at most NS destination
 // atoms ("slots" 0..NS-1; the template builder guarantees NS <= 4).  Lane (n, q) holds rows 4q + r of feature n in v[r].
@@ -1273,26 +1159,8 @@ __device__ __forceinline__ void gemm_bt2_sc(f32x4& a0, f32x4& a1, f32x4& t0, f32
     }
 }
 
-// ---- two operand sets (the two directions of a pair block) against the pipe's current chunk, every matrix path
-template <int NBK, bool FLIP>
-__device__ __forceinline__ void gemm_half_chunk_x2(f32x4& a0, f32x4& a1, f32x4& b0, f32x4& b1, const OpndH<NBK>& inA, const OpndH<NBK>& inB,
-                                                   const h8* wl, int lane)
-{
-    constexpr int KS = NBK / 2, STEPS = 2 * KS;
-    h8 f[2];
-    f[0] = wl[lane];
-#pragma unroll
-    for (int s = 0; s < STEPS; ++s) {
-        if (s + 1 < STEPS) f[(s + 1) & 1] = wl[(s + 1) * 64 + lane];
-        __builtin_amdgcn_sched_barrier(0x16);
-        const int m = s % KS;
-        f32x4& accA = s < KS ? a0 : a1;
-        f32x4& accB = s < KS ? b0 : b1;
-        if (FLIP) { accA = mfma16h(inA.hi[m], f[s & 1], accA); accB = mfma16h(inB.hi[m], f[s & 1], accB); }
-        else      { accA = mfma16h(f[s & 1], inA.hi[m], accA); accB = mfma16h(f[s & 1], inB.hi[m], accB); }
-        __builtin_amdgcn_sched_barrier(0x16);
-    }
-}
+// ---- two operand sets (the two directions of a pair block) against the pipe's current chunk: the f32 and the two split paths (the
+// fp16 storage mode keeps the directed message kernel)
 template <bool FLIP, int NBK>
 __device__ __forceinline__ void gemm_x2(f32x4& a0, f32x4& a1, f32x4& b0, f32x4& b1, const Opnd1<NBK>& inA, const Opnd1<NBK>& inB, const f32x4* wl, int lane)
 {
@@ -1309,11 +1177,6 @@ __device__ __forceinline__ void gemm_x2(f32x4& a0, f32x4& a1, f32x4& b0, f32x4& 
     const h8* wl = reinterpret_cast<const h8*>(wl4);
     gemm_pair_split_block<NBK, FLIP>(a0, b0, inA, inB, wl, lane);
     gemm_pair_split_block<NBK, FLIP>(a1, b1, inA, inB, wl + NBK * 64, lane);
-}
-template <bool FLIP, int NBK>
-__device__ __forceinline__ void gemm_x2(f32x4& a0, f32x4& a1, f32x4& b0, f32x4& b1, const OpndH<NBK>& inA, const OpndH<NBK>& inB, const f32x4* wl, int lane)
-{
-    gemm_half_chunk_x2<NBK, FLIP>(a0, a1, b0, b1, inA, inB, reinterpret_cast<const h8*>(wl), lane);
 }
 template <bool FLIP, class OP, class PIPE>
 __device__ __forceinline__ void gemm_x2_on_pipe(f32x4& a0, f32x4& a1, f32x4& b0, f32x4& b1, const OP& inA, const OP& inB, PIPE& pipe, int lane)

@@ -4,16 +4,11 @@
 #pragma once
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include "dispatch.hpp"
 #include "mfma_chain.hpp"
 #include "ti_internal.hpp"
 
 namespace ti {
-
-template <typename K>
-static hipError_t set_lds_edge(K kernel, size_t bytes)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 // ================================================================================================== edge kernel
 // Per-layer vectors of the two message MLPs, copied once per workgroup into LDS (offsets in floats, F = n_features).
@@ -49,16 +44,15 @@ __device__ __forceinline__ void acc_out(float* p, float v, bool first)
 // the barriers; the chunk counts 56/48/40/32 divide by 8).
 __host__ __device__ constexpr int edge_superchunk(int NB, int WAVES, bool H16 = false) { return ((WAVES == 8 && NB == 4) ? 4 : 2) * (H16 && NB == 4 ? 2 : 1); }
 __host__ __device__ constexpr int edge_chunk4(int NB, bool H16) { return (H16 ? 128 : 256) * NB; }            // float4 per weight chunk
-// F = 32 in the storage mode: a 2-chunk superchunk (4 KB) is smaller than one 16-byte lane per thread of the 8-wave build
-// Does this (feature width, precision) run the one-accumulator split format (mfma_chain.hpp: Opnd1)?  TI_PREC_F16X2 at every width;
-// painn_pack.hip packs the message streams accordingly.  The F = 256 build (one wave per SIMD, operands partly in AGPRs) faulted on the
-// device (memory aperture violation in its first launch) when hipcc spilled SGPRs into VGPR lanes: painn_edge_nb8.hip is compiled
+// The builds of a width: 4 waves with NS = 2 or 4 destination atoms per row block at every precision; 8 waves (NS = 2 only) at
+// F <= 128 -- except F = 32 in the storage mode, where a 2-chunk superchunk (4 KB) is smaller than one 16-byte lane per thread.
+// The one-accumulator split format (edge_one_chain, ti_internal.hpp) at F = 256 (one wave per SIMD, operands partly in AGPRs) faulted on
+// the device (memory aperture violation in its first launch) when hipcc spilled SGPRs into VGPR lanes: painn_edge_nb8.hip is compiled
 // with -mllvm -amdgpu-spill-sgpr-to-vgpr=0 (build.py), which removes the fault.
-#ifndef TI_ONE_CHAIN_MAX_NB
-#define TI_ONE_CHAIN_MAX_NB 8
-#endif
-__host__ __device__ constexpr bool edge_one_chain(int NB, int PREC) { return PREC == 1 && NB <= TI_ONE_CHAIN_MAX_NB; }
-__host__ __device__ constexpr bool edge_build_exists(int NB, int WAVES, int PREC) { return !(PREC == 2 && NB == 1 && WAVES == 8); }
+__host__ __device__ constexpr bool edge_build_exists(int NB, int WAVES, int PREC, int NS)
+{
+    return PREC >= 0 && PREC <= 2 && (WAVES == 4 ? NS == 2 || NS == 4 : WAVES == 8 && NS == 2 && NB <= 4 && !(PREC == 2 && NB == 1));
+}
 template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, int NS>
 __global__ __launch_bounds__(64 * WAVES, (NBK <= 8 ? 2 * 4 / WAVES : 1)) void painn_edge_kernel(const EdgeParams p)
 #define TI_ROWS_GROUP (gi - mg * p.parts)
@@ -79,86 +73,48 @@ __global__ __launch_bounds__(64 * WAVES, (NBK <= 8 ? 2 * 4 / WAVES : 1)) void pa
 static size_t edge_lds_bytes(int NB, int WAVES, bool h16) { return 2 * edge_superchunk(NB, WAVES, h16) * (size_t)edge_chunk4(NB, h16) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4; }
 
 
-// MASK: the masked twins (painn_edge_mask_kernel), instantiated in translation units of their own (painn_edge_mask_nb*.hip)
-template <int NB, int EW, int NS, int PREC, bool MASK>
-static hipError_t configure_edge_prec()
+// Where a message block stands among the layers, as one value to dispatch on: the kernels' (FIRST, LAST) = (pos & 1, pos & 2)
+enum LayerPos { POS_FIRST = 1, POS_MIDDLE = 0, POS_LAST = 2, POS_ONLY = 3 };
+inline int layer_pos(bool first, bool last) { return (first ? 1 : 0) | (last ? 2 : 0); }
+
+// The visitor of the family: f(kernel, waves, LDS bytes) for every build of width NB that the values select (EVERY: all of them,
+// dispatch.hpp), until one returns an error.  MASK: the masked twins (painn_edge_mask_kernel).  hipErrorInvalidValue: no such build.
+template <int NB, bool MASK, class F>
+static hipError_t with_edge_builds(int waves, int ns, int prec, int pos, F&& f)
 {
-    if constexpr (!edge_build_exists(NB, EW, PREC)) return hipSuccess;
-    else if constexpr (MASK) {
-    const size_t be = edge_lds_bytes(NB, EW, PREC == 2);
-    hipError_t e;
-    if ((e = set_lds_edge(painn_edge_mask_kernel<2 * NB, true, false, PREC, EW, NS>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_edge_mask_kernel<2 * NB, false, false, PREC, EW, NS>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_edge_mask_kernel<2 * NB, false, true, PREC, EW, NS>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_edge_mask_kernel<2 * NB, true, true, PREC, EW, NS>, be)) != hipSuccess) return e;
-    return hipSuccess;
-    } else {
-    const size_t be = edge_lds_bytes(NB, EW, PREC == 2);
-    hipError_t e;
-    if ((e = set_lds_edge(painn_edge_kernel<2 * NB, true, false, PREC, EW, NS>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_edge_kernel<2 * NB, false, false, PREC, EW, NS>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_edge_kernel<2 * NB, false, true, PREC, EW, NS>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_edge_kernel<2 * NB, true, true, PREC, EW, NS>, be)) != hipSuccess) return e;
-    return hipSuccess;
-    }
-}
-template <int NB, int EW, int NS, bool MASK>
-static hipError_t configure_edge()
-{
-    hipError_t e;
-    if ((e = configure_edge_prec<NB, EW, NS, 0, MASK>()) != hipSuccess) return e;
-    if ((e = configure_edge_prec<NB, EW, NS, 1, MASK>()) != hipSuccess) return e;
-    return configure_edge_prec<NB, EW, NS, 2, MASK>();
+    hipError_t e = hipSuccess;
+    bool any = false;
+    dispatch_int<4, 8>(waves, [&](auto wc) { dispatch_int<2, 4>(ns, [&](auto nc) { dispatch_int<0, 1, 2>(prec, [&](auto pc) {
+        constexpr int WAVES = decltype(wc)::value, NS = decltype(nc)::value, PREC = decltype(pc)::value;
+        if constexpr (edge_build_exists(NB, WAVES, PREC, NS))
+            dispatch_int<POS_FIRST, POS_MIDDLE, POS_LAST, POS_ONLY>(pos, [&](auto oc) {
+                constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0;
+                any = true;
+                if (e != hipSuccess) return;
+                if constexpr (MASK) e = f(painn_edge_mask_kernel<2 * NB, FIRST, LAST, PREC, WAVES, NS>, WAVES, edge_lds_bytes(NB, WAVES, PREC == 2));
+                else e = f(painn_edge_kernel<2 * NB, FIRST, LAST, PREC, WAVES, NS>, WAVES, edge_lds_bytes(NB, WAVES, PREC == 2));
+            });
+    }); }); });
+    return any ? e : hipErrorInvalidValue;
 }
 
-template <int NB, int EW, int NS, int PREC, bool MASK>
-static void launch_edge_p(bool first, bool last, const EdgeParams& p, hipStream_t st)
+// one feature width (ti_internal.hpp): configure every build / launch the one the call needs
+template <int NB, bool MASK>
+hipError_t configure_edge_unit()
 {
-    if constexpr (edge_build_exists(NB, EW, PREC)) {
-    const dim3 g((unsigned)((p.n_groups + EW - 1) / EW)), t(64 * EW);          // one wave (= one group or part) each
-    const size_t l = edge_lds_bytes(NB, EW, PREC == 2);
-    if constexpr (MASK) {
-    if (first && last) hipLaunchKernelGGL((painn_edge_mask_kernel<2 * NB, true, true, PREC, EW, NS>), g, t, l, st, p);
-    else if (first) hipLaunchKernelGGL((painn_edge_mask_kernel<2 * NB, true, false, PREC, EW, NS>), g, t, l, st, p);
-    else if (last) hipLaunchKernelGGL((painn_edge_mask_kernel<2 * NB, false, true, PREC, EW, NS>), g, t, l, st, p);
-    else hipLaunchKernelGGL((painn_edge_mask_kernel<2 * NB, false, false, PREC, EW, NS>), g, t, l, st, p);
-    } else {
-    if (first && last) hipLaunchKernelGGL((painn_edge_kernel<2 * NB, true, true, PREC, EW, NS>), g, t, l, st, p);
-    else if (first) hipLaunchKernelGGL((painn_edge_kernel<2 * NB, true, false, PREC, EW, NS>), g, t, l, st, p);
-    else if (last) hipLaunchKernelGGL((painn_edge_kernel<2 * NB, false, true, PREC, EW, NS>), g, t, l, st, p);
-    else hipLaunchKernelGGL((painn_edge_kernel<2 * NB, false, false, PREC, EW, NS>), g, t, l, st, p);
-    }
-    }
+    return with_edge_builds<NB, MASK>(EVERY, EVERY, EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
 }
-template <int NB, int EW, int NS, bool MASK>
-static void launch_edge_w(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
-{
-    if (prec == 2) launch_edge_p<NB, EW, NS, 2, MASK>(first, last, p, st);
-    else if (prec == 1) launch_edge_p<NB, EW, NS, 1, MASK>(first, last, p, st);
-    else launch_edge_p<NB, EW, NS, 0, MASK>(first, last, p, st);
-}
-
-// one feature width: configure every instantiation / launch the one the call needs
-template <int NB, bool MASK = false>
-static hipError_t configure_edge_nb()
-{
-    hipError_t e;
-    if ((e = configure_edge<NB, 4, 2, MASK>()) != hipSuccess) return e;
-    if ((e = configure_edge<NB, 4, 4, MASK>()) != hipSuccess) return e;
-    if constexpr (NB <= 4) { if ((e = configure_edge<NB, 8, 2, MASK>()) != hipSuccess) return e; }
-    return hipSuccess;
-}
-template <int NB, bool MASK = false>
-static hipError_t launch_edge_nb(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
+template <int NB, bool MASK>
+hipError_t launch_edge_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
 {
     if (p.max_slots > EDGE_MAX_SLOTS) return hipErrorInvalidValue;          // build_templates never produces such a block
     // 8-wave workgroups: split-fp16 path only (the f32 path is matrix-bound and loses 4 % to the wider barriers), enough groups to
     // fill every CU, and at most two destination atoms per row block (the only form the wide build is instantiated for)
-    const bool wide = NB <= 4 && prec != 0 && p.n_groups >= 2048 && p.max_slots <= 2 && edge_build_exists(NB, 8, prec);
-    if constexpr (NB <= 4) { if (wide) { launch_edge_w<NB, 8, 2, MASK>(first, last, prec, p, st); return hipGetLastError(); } }
-    if (p.max_slots <= 2) launch_edge_w<NB, 4, 2, MASK>(first, last, prec, p, st);
-    else launch_edge_w<NB, 4, 4, MASK>(first, last, prec, p, st);
-    return hipGetLastError();
+    const bool wide = prec != 0 && p.n_groups >= 2048 && p.max_slots <= 2 && edge_build_exists(NB, 8, prec, 2);
+    return with_edge_builds<NB, MASK>(wide ? 8 : 4, p.max_slots <= 2 ? 2 : 4, prec, layer_pos(first, last), [&](auto kernel, int waves, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((p.n_groups + waves - 1) / waves)), dim3(64 * waves), lds, st, p);      // one wave (= one group or part) each
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ti

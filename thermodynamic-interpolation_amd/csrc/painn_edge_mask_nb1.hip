@@ -2,6 +2,6 @@
 #include "painn_edge_kernel.hpp"
 
 namespace ti {
-hipError_t configure_edge_mask_nb1() { return configure_edge_nb<1, true>(); }
-hipError_t launch_edge_mask_nb1(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st) { return launch_edge_nb<1, true>(first, last, prec, p, st); }
+template hipError_t configure_edge_unit<1, true>();
+template hipError_t launch_edge_unit<1, true>(bool, bool, int, const EdgeParams&, hipStream_t);
 }  // namespace ti

@@ -2,6 +2,6 @@
 #include "painn_edge_kernel.hpp"
 
 namespace ti {
-hipError_t configure_edge_nb2() { return configure_edge_nb<2>(); }
-hipError_t launch_edge_nb2(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st) { return launch_edge_nb<2>(first, last, prec, p, st); }
+template hipError_t configure_edge_unit<2, false>();
+template hipError_t launch_edge_unit<2, false>(bool, bool, int, const EdgeParams&, hipStream_t);
 }  // namespace ti

@@ -17,7 +17,6 @@ void ensure_painn_ws(ti_handle* h, long long B)
     // parked geometry of a drift evaluation (painn_edge_kernel.hpp): the encoding operand of every edge row (as many bytes as e) and edge_dir
     h->enc.alloc((edge_rows_for(h, B) * F + se - 1) / se); h->geo.alloc(edge_rows_for(h, B) * 4);
     h->divb.alloc(B); h->div2.alloc(B); h->dl.alloc(B); h->dlscaled.alloc(B);
-    if (h->has_pair && pair_uses_partials()) h->part.alloc((size_t)((B + h->tpl[2].G - 1) / h->tpl[2].G) * h->tpl[2].nblk * 8 * 7 * F);
     h->cap = B;
 }
 
@@ -205,7 +204,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
             p.nblk = h->nblk; p.G = h->G; p.parts = h->parts; p.A = A; p.max_slots = h->max_slots; p.B = B; p.n_groups = groups; p.length_scale = h->d.length_scale;
             p.x = x_dev; p.P = h->P.p; p.v = h->v.p; p.dsacc = h->dsacc.p; p.dvacc = h->dvacc.p; p.cacc = h->cacc.p; p.e = h->e.p; p.enc = h->enc.p; p.geo = h->geo.p;
             for (int i = 0; i < 6; ++i) p.wscale[i] = 1.0f;
-            if (edge_uses_one_chain(NB, prec)) {     // the message kernel's own stream format (the primal pass of the divergence keeps the other one)
+            if (edge_one_chain(prec)) {     // the message kernel's own stream format (the primal pass of the divergence keeps the other one)
                 p.stream = h->S(h->st_edge1[l]); p.nch = h->st_edge1[l].nch; p.vecs = h->edge_vecs1.p + (size_t)l * 21 * F;
                 for (int i = 0; i < 6; ++i) p.wscale[i] = h->edge_scale[(size_t)l * 6 + i];
             }
@@ -215,17 +214,10 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
             if (l == 2) p.stamps = stamps_arm(groups, st);
 #endif
             if (h->active == 2) {
-                p.part = h->part.p;
                 HIP_CHECK(launch_pair(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr));
 #ifdef TI_STAMPS
                 stamps_dump(h, p.stamps, groups, st);
 #endif
-                if (pair_uses_partials()) {
-                PairReduceParams r{};
-                r.part = h->part.p; r.plist = h->pair_plist.p; r.kmax = h->pair_kmax; r.G = h->G; r.A = A; r.F = F; r.nblk = h->nblk;
-                r.has_c = l > 0 && !pair_folds_cross(prec); r.B = B; r.dsacc = h->dsacc.p; r.dvacc = h->dvacc.p; r.cacc = h->cacc.p;
-                HIP_CHECK(launch_pair_reduce(r, st));
-                }
             } else {
                 HIP_CHECK(launch_edge(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr));
 #ifdef TI_STAMPS

@@ -28,9 +28,9 @@
 //   norm      n = |V v|:  n' = (V v).(V v') / n   (0 at n = 0, like torch.norm's backward)
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include "dispatch.hpp"
 #include "mfma_chain.hpp"
 #include "ti_internal.hpp"
-
 
 namespace ti {
 
@@ -617,111 +617,77 @@ static size_t jvp_node_lds(int NB, int count)
     return 4 * (size_t)256 * NB * 16 + (size_t)count * 32 * NB * 4;
 }
 
-template <typename K>
-static hipError_t set_lds(K kernel, size_t bytes)
+// The five kernels of the family and their builds: every width x SPLIT, the filter and the edge kernel also as masked twins.
+enum JvpKernel { JVP_FILTER, JVP_EDGE, JVP_NODE, JVP_UPDATE, JVP_READOUT };
+constexpr bool jvp_build_exists(JvpKernel k, bool mask) { return !mask || k == JVP_FILTER || k == JVP_EDGE; }
+static size_t jvp_lds_bytes(JvpKernel k, int NB)
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return k == JVP_EDGE ? jvp_edge_lds(NB) : jvp_node_lds(NB, k == JVP_FILTER ? EV::COUNT : k == JVP_READOUT ? RV::COUNT : UV::COUNT);
+}
+template <JvpKernel K, int NBK, bool SPLIT, bool MASK>
+constexpr auto jvp_kernel()
+{
+    if constexpr (K == JVP_FILTER && MASK) return painn_jvp_filter_mask_kernel<NBK, SPLIT>;
+    else if constexpr (K == JVP_FILTER) return painn_jvp_filter_kernel<NBK, SPLIT>;
+    else if constexpr (K == JVP_EDGE && MASK) return painn_jvp_edge_mask_kernel<NBK, SPLIT>;
+    else if constexpr (K == JVP_EDGE) return painn_jvp_edge_kernel<NBK, SPLIT>;
+    else if constexpr (K == JVP_NODE) return painn_jvp_node_kernel<NBK, SPLIT>;
+    else if constexpr (K == JVP_UPDATE) return painn_jvp_update_kernel<NBK, SPLIT>;
+    else return painn_jvp_readout_kernel<NBK, SPLIT>;
+}
+// The visitor of the family: f(kernel, LDS bytes) for every build of kernel K that the values select (EVERY: all of them, dispatch.hpp),
+// until one returns an error.  hipErrorInvalidValue: no such build.
+template <JvpKernel K, class F>
+static hipError_t with_jvp_builds(int NB, int masked, int split, F&& f)
+{
+    hipError_t e = hipSuccess;
+    bool any = false;
+    dispatch_int<1, 2, 4, 8>(NB, [&](auto nc) { dispatch_bool(masked, [&](auto mc) { dispatch_bool(split, [&](auto sc) {
+        constexpr int nb = decltype(nc)::value;
+        constexpr bool MASK = decltype(mc)::value, SPLIT = decltype(sc)::value;
+        if constexpr (jvp_build_exists(K, MASK)) {
+            any = true;
+            if (e == hipSuccess) e = f(jvp_kernel<K, 2 * nb, SPLIT, MASK>(), jvp_lds_bytes(K, nb));
+        }
+    }); }); });
+    return any ? e : hipErrorInvalidValue;
+}
+template <JvpKernel K>
+static hipError_t configure_jvp(int NB)
+{
+    return with_jvp_builds<K>(NB, EVERY, EVERY, [](auto kernel, size_t lds) { return set_lds(kernel, lds); });
+}
+// blocks of 4 waves: one wave per group (filter, edge) or per 16 nodes (node, update, readout)
+template <JvpKernel K, class P>
+static hipError_t launch_jvp(int NB, bool split, bool masked, long long blocks, const P& p, hipStream_t st)
+{
+    return with_jvp_builds<K>(NB, masked, split, [&](auto kernel, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st, p);
+        return hipGetLastError();
+    });
 }
 
-#ifdef TI_DEV_NB4_ONLY
-#define TI_SMALL_NB(...)
-#else
-#define TI_SMALL_NB(...) __VA_ARGS__
-#endif
-#define TI_JVP_DISPATCH(NBv, ...) \
-    switch (NBv) {                                                           \
-        TI_SMALL_NB(case 1: { constexpr int NBK = 2; __VA_ARGS__; } break;)  \
-        TI_SMALL_NB(case 2: { constexpr int NBK = 4; __VA_ARGS__; } break;)  \
-        case 4: { constexpr int NBK = 8; __VA_ARGS__; } break;               \
-        TI_SMALL_NB(case 8: { constexpr int NBK = 16; __VA_ARGS__; } break;) \
-        default: return hipErrorInvalidValue;                                \
-    }
-
-template <int NBK>
-static hipError_t configure_jvp_nbk(int NB)
+hipError_t configure_painn_jvp_kernels(int NB)
 {
     hipError_t e;
-    if ((e = set_lds(painn_jvp_filter_kernel<NBK, false>, jvp_node_lds(NB, EV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_filter_kernel<NBK, true>, jvp_node_lds(NB, EV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_filter_mask_kernel<NBK, false>, jvp_node_lds(NB, EV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_filter_mask_kernel<NBK, true>, jvp_node_lds(NB, EV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_edge_kernel<NBK, false>, jvp_edge_lds(NB))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_edge_kernel<NBK, true>, jvp_edge_lds(NB))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_edge_mask_kernel<NBK, false>, jvp_edge_lds(NB))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_edge_mask_kernel<NBK, true>, jvp_edge_lds(NB))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_node_kernel<NBK, false>, jvp_node_lds(NB, UV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_node_kernel<NBK, true>, jvp_node_lds(NB, UV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_update_kernel<NBK, false>, jvp_node_lds(NB, UV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_update_kernel<NBK, true>, jvp_node_lds(NB, UV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_readout_kernel<NBK, false>, jvp_node_lds(NB, RV::COUNT))) != hipSuccess) return e;
-    if ((e = set_lds(painn_jvp_readout_kernel<NBK, true>, jvp_node_lds(NB, RV::COUNT))) != hipSuccess) return e;
-    return hipSuccess;
+    if ((e = configure_jvp<JVP_FILTER>(NB)) != hipSuccess) return e;
+    if ((e = configure_jvp<JVP_EDGE>(NB)) != hipSuccess) return e;
+    if ((e = configure_jvp<JVP_NODE>(NB)) != hipSuccess) return e;
+    if ((e = configure_jvp<JVP_UPDATE>(NB)) != hipSuccess) return e;
+    return configure_jvp<JVP_READOUT>(NB);
 }
 
-hipError_t configure_painn_jvp_kernels(int NBv)
+hipError_t launch_jvp_filter(int NB, bool split, const JvpFilterParams& p, hipStream_t st, bool masked)
 {
-    TI_JVP_DISPATCH(NBv, return configure_jvp_nbk<NBK>(NBv));
-    return hipSuccess;
+    return launch_jvp<JVP_FILTER>(NB, split, masked, (p.n_groups + 3) / 4, p, st);
 }
-
-hipError_t launch_jvp_filter(int NBv, bool split, const JvpFilterParams& p, hipStream_t st, bool masked)
+hipError_t launch_jvp_edge(int NB, bool split, const JvpEdgeParams& p, hipStream_t st, bool masked)
 {
-    const dim3 g((unsigned)((p.n_groups + 3) / 4));
-    const size_t l = jvp_node_lds(NBv, EV::COUNT);
-    TI_JVP_DISPATCH(NBv, {
-        if (masked && split) hipLaunchKernelGGL((painn_jvp_filter_mask_kernel<NBK, true>), g, dim3(256), l, st, p);
-        else if (masked) hipLaunchKernelGGL((painn_jvp_filter_mask_kernel<NBK, false>), g, dim3(256), l, st, p);
-        else if (split) hipLaunchKernelGGL((painn_jvp_filter_kernel<NBK, true>), g, dim3(256), l, st, p);
-        else hipLaunchKernelGGL((painn_jvp_filter_kernel<NBK, false>), g, dim3(256), l, st, p);
-    });
-    return hipGetLastError();
+    return launch_jvp<JVP_EDGE>(NB, split, masked, (p.n_groups + 3) / 4, p, st);
 }
-
-hipError_t launch_jvp_edge(int NBv, bool split, const JvpEdgeParams& p, hipStream_t st, bool masked)
-{
-    const dim3 g((unsigned)((p.n_groups + 3) / 4));
-    const size_t l = jvp_edge_lds(NBv);
-    TI_JVP_DISPATCH(NBv, {
-        if (masked && split) hipLaunchKernelGGL((painn_jvp_edge_mask_kernel<NBK, true>), g, dim3(256), l, st, p);
-        else if (masked) hipLaunchKernelGGL((painn_jvp_edge_mask_kernel<NBK, false>), g, dim3(256), l, st, p);
-        else if (split) hipLaunchKernelGGL((painn_jvp_edge_kernel<NBK, true>), g, dim3(256), l, st, p);
-        else hipLaunchKernelGGL((painn_jvp_edge_kernel<NBK, false>), g, dim3(256), l, st, p);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_jvp_node(int NBv, bool split, const JvpNodeParams& p, hipStream_t st)
-{
-    const dim3 g((unsigned)((p.N + 63) / 64));
-    const size_t l = jvp_node_lds(NBv, UV::COUNT);
-    TI_JVP_DISPATCH(NBv, {
-        if (split) hipLaunchKernelGGL((painn_jvp_node_kernel<NBK, true>), g, dim3(256), l, st, p);
-        else hipLaunchKernelGGL((painn_jvp_node_kernel<NBK, false>), g, dim3(256), l, st, p);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_jvp_update(int NBv, bool split, const JvpUpdateParams& p, hipStream_t st)
-{
-    const dim3 g((unsigned)((p.N + 63) / 64));
-    const size_t l = jvp_node_lds(NBv, UV::COUNT);
-    TI_JVP_DISPATCH(NBv, {
-        if (split) hipLaunchKernelGGL((painn_jvp_update_kernel<NBK, true>), g, dim3(256), l, st, p);
-        else hipLaunchKernelGGL((painn_jvp_update_kernel<NBK, false>), g, dim3(256), l, st, p);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_jvp_readout(int NBv, bool split, const JvpReadoutParams& p, hipStream_t st)
-{
-    const dim3 g((unsigned)((p.N + 63) / 64));
-    const size_t l = jvp_node_lds(NBv, RV::COUNT);
-    TI_JVP_DISPATCH(NBv, {
-        if (split) hipLaunchKernelGGL((painn_jvp_readout_kernel<NBK, true>), g, dim3(256), l, st, p);
-        else hipLaunchKernelGGL((painn_jvp_readout_kernel<NBK, false>), g, dim3(256), l, st, p);
-    });
-    return hipGetLastError();
-}
+hipError_t launch_jvp_node(int NB, bool split, const JvpNodeParams& p, hipStream_t st) { return launch_jvp<JVP_NODE>(NB, split, false, (p.N + 63) / 64, p, st); }
+hipError_t launch_jvp_update(int NB, bool split, const JvpUpdateParams& p, hipStream_t st) { return launch_jvp<JVP_UPDATE>(NB, split, false, (p.N + 63) / 64, p, st); }
+hipError_t launch_jvp_readout(int NB, bool split, const JvpReadoutParams& p, hipStream_t st) { return launch_jvp<JVP_READOUT>(NB, split, false, (p.N + 63) / 64, p, st); }
 
 hipError_t launch_div_reduce(const float* tout, long long B, int D, int G, float* div, hipStream_t st)
 {

@@ -13,28 +13,13 @@
 // order -- deterministic without an ordered reduction tree.
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include "dispatch.hpp"
 #include "mfma_chain.hpp"
 #include "ti_internal.hpp"
 
 namespace ti {
 
-// the edge kernels live in painn_edge_nb{1,2,4,8}.hip (painn_edge_kernel.hpp)
-hipError_t configure_edge_nb1(); hipError_t configure_edge_nb2(); hipError_t configure_edge_nb4(); hipError_t configure_edge_nb8();
-hipError_t launch_edge_nb1(bool, bool, int, const EdgeParams&, hipStream_t); hipError_t launch_edge_nb2(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t launch_edge_nb4(bool, bool, int, const EdgeParams&, hipStream_t); hipError_t launch_edge_nb8(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t configure_pair_nb1(); hipError_t configure_pair_nb2(); hipError_t configure_pair_nb4();
-hipError_t launch_pair_nb1(bool, bool, int, const EdgeParams&, hipStream_t); hipError_t launch_pair_nb2(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t launch_pair_nb4(bool, bool, int, const EdgeParams&, hipStream_t);
-// their masked twins (per-molecule edge sets, ti_painn_set_edge_mask): painn_edge_mask_nb*.hip, painn_pair_mask_nb*.hip
-hipError_t configure_edge_mask_nb1(); hipError_t configure_edge_mask_nb2(); hipError_t configure_edge_mask_nb4(); hipError_t configure_edge_mask_nb8();
-hipError_t launch_edge_mask_nb1(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t launch_edge_mask_nb2(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t launch_edge_mask_nb4(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t launch_edge_mask_nb8(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t configure_pair_mask_nb1(); hipError_t configure_pair_mask_nb2(); hipError_t configure_pair_mask_nb4();
-hipError_t launch_pair_mask_nb1(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t launch_pair_mask_nb2(bool, bool, int, const EdgeParams&, hipStream_t);
-hipError_t launch_pair_mask_nb4(bool, bool, int, const EdgeParams&, hipStream_t);
+// the message kernels live in painn_{edge,pair}[_mask]_nb*.hip (painn_edge_kernel.hpp, painn_pair_kernel.hpp; ti_internal.hpp: *_unit)
 
 // ================================================================================================== update kernel
 // v <- v + dv  with  dv = dvacc + cacc x v   (the cross product with v[dst] factors out of the edge sum),
@@ -441,213 +426,100 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_readout16_kerne
 }
 
 // ================================================================================================== launchers
-template <typename K>
-static hipError_t set_lds(K kernel, size_t bytes)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 static size_t update_lds_bytes(int NB, bool h16) { return 2 * update_superchunk(NB, h16) * (size_t)update_chunk4(NB, h16) * 16 + 10 * (size_t)32 * NB * 4; }
-
-template <int NB, int WAVES>
-static hipError_t configure_nb()
-{
-    hipError_t e;
-    {
-        const size_t n0 = 2 * 2 * (size_t)update_chunk4(NB, false) * 16, n2 = 2 * 2 * (size_t)update_chunk4(NB, true) * 16;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 0>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 0>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 0>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 1>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 1>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 1>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 2>, n2)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 2>, n2)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 2>, n2)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 0, true>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 0, true>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 0, true>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 1, true>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 1, true>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 1, true>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 2, 2, true>, n2)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 3, 2, true>, n2)) != hipSuccess) return e;
-        if ((e = set_lds(painn_embed16_kernel<2 * NB, 4, 2, true>, n2)) != hipSuccess) return e;
-        if ((e = set_lds(painn_readout16_kernel<2 * NB, 0>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_readout16_kernel<2 * NB, 1>, n0)) != hipSuccess) return e;
-        if ((e = set_lds(painn_readout16_kernel<2 * NB, 2>, n2)) != hipSuccess) return e;
-    }
-    if ((e = (NB == 1 ? configure_edge_nb1() : NB == 2 ? configure_edge_nb2() : NB == 4 ? configure_edge_nb4() : configure_edge_nb8())) != hipSuccess) return e;
-    if ((e = (NB == 1 ? configure_pair_nb1() : NB == 2 ? configure_pair_nb2() : NB == 4 ? configure_pair_nb4() : hipSuccess)) != hipSuccess) return e;
-    if ((e = (NB == 1 ? configure_edge_mask_nb1() : NB == 2 ? configure_edge_mask_nb2() : NB == 4 ? configure_edge_mask_nb4() : configure_edge_mask_nb8())) != hipSuccess) return e;
-    if ((e = (NB == 1 ? configure_pair_mask_nb1() : NB == 2 ? configure_pair_mask_nb2() : NB == 4 ? configure_pair_mask_nb4() : hipSuccess)) != hipSuccess) return e;
-    const size_t bu = update_lds_bytes(NB, false), bh = update_lds_bytes(NB, true);
-    if ((e = set_lds(painn_update_kernel<2 * NB, true, 0>, bu)) != hipSuccess) return e;
-    if ((e = set_lds(painn_update_kernel<2 * NB, false, 0>, bu)) != hipSuccess) return e;
-    if ((e = set_lds(painn_update_kernel<2 * NB, true, 1>, bu)) != hipSuccess) return e;
-    if ((e = set_lds(painn_update_kernel<2 * NB, false, 1>, bu)) != hipSuccess) return e;
-    if ((e = set_lds(painn_update_kernel<2 * NB, true, 1, true>, bu)) != hipSuccess) return e;
-    if ((e = set_lds(painn_update_kernel<2 * NB, false, 1, true>, bu)) != hipSuccess) return e;
-    if ((e = set_lds(painn_update_kernel<2 * NB, true, 2>, bh)) != hipSuccess) return e;
-    if ((e = set_lds(painn_update_kernel<2 * NB, false, 2>, bh)) != hipSuccess) return e;
-
-    return hipSuccess;
-}
-
-// NB <= 2: 8 waves / workgroup, 2 per SIMD (<= 256 VGPRs); NB >= 4: 4 waves, 1 per SIMD (512-register budget:
-// three resident activation sets of 16*NB registers plus the compiler's address/staging overhead do not fit in 256)
-#ifdef TI_DEV_NB4_ONLY
-#define TI_SMALL_NB(...)
-#else
-#define TI_SMALL_NB(...) __VA_ARGS__
-#endif
-#define TI_DISPATCH_NB(NBv, ...) \
-    switch (NBv) {                                                            \
-        TI_SMALL_NB(case 1: { constexpr int NB = 1, WAVES = 8; __VA_ARGS__; } break;)             \
-        TI_SMALL_NB(case 2: { constexpr int NB = 2, WAVES = 8; __VA_ARGS__; } break;)             \
-        case 4: { constexpr int NB = 4, WAVES = 4; __VA_ARGS__; } break;             \
-        TI_SMALL_NB(case 8: { constexpr int NB = 8, WAVES = 4; __VA_ARGS__; } break;)             \
-        default: return hipErrorInvalidValue;                                 \
-    }
-
-hipError_t configure_painn_kernels(int NBv)
-{
-    TI_DISPATCH_NB(NBv, return (configure_nb<NB, WAVES>()));
-    return hipSuccess;
-}
-
-
-// prec: include/ti_hip.h TI_PREC_* (0 f32, 1 f16x2, 2 f16 storage mode: the state tensors are fp16)
 static size_t node16_lds_bytes(int NB, bool h16) { return 2 * 2 * (size_t)update_chunk4(NB, h16) * 16; }      // PipeDMA<.., SC = 2>: two superchunks
 
-template <int NB, int PREC, bool TV>
-static void launch_embed16(int nseg, const EmbedParams& p, hipStream_t st)
+// The three node kernels and their builds: every width x precision (prec: include/ti_hip.h TI_PREC_*; 0 f32, 1 f16x2, 2 f16 storage
+// mode: the state tensors are fp16), and per kernel two more arguments (n, flag):
+//   embed16: NSEG = 2, 3, 4 x TV;   update: HAS_NEXT x FOLDED, FOLDED only where the pair kernel folds (pair_folds_cross);   readout: (0, false)
+enum NodeKernel { NODE_EMBED, NODE_UPDATE, NODE_READOUT };
+constexpr bool node_build_exists(NodeKernel k, int PREC, int n, bool flag)
 {
-    const dim3 g((unsigned)((p.N + 63) / 64));                 // 4 waves x 16 atoms per workgroup
-    const size_t l = node16_lds_bytes(NB, PREC == 2);
-    if (nseg == 4) hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 4, PREC, TV>), g, dim3(256), l, st, p);
-    else if (nseg == 3) hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 3, PREC, TV>), g, dim3(256), l, st, p);
-    else hipLaunchKernelGGL((painn_embed16_kernel<2 * NB, 2, PREC, TV>), g, dim3(256), l, st, p);
+    return k == NODE_EMBED ? n >= 2 : k == NODE_UPDATE ? n <= 1 && (!flag || pair_folds_cross(PREC)) : n == 0 && !flag;
 }
-template <int NB, int PREC>
-static void launch_embed16(int nseg, const EmbedParams& p, hipStream_t st)
+template <NodeKernel K, int NBK, int PREC, int N, bool FLAG>
+constexpr auto node_kernel()
 {
-    if (p.tv) launch_embed16<NB, PREC, true>(nseg, p, st);
-    else launch_embed16<NB, PREC, false>(nseg, p, st);
+    if constexpr (K == NODE_EMBED) return painn_embed16_kernel<NBK, N, PREC, FLAG>;
+    else if constexpr (K == NODE_UPDATE) return painn_update_kernel<NBK, N != 0, PREC, FLAG>;
+    else return painn_readout16_kernel<NBK, PREC>;
 }
-
-hipError_t launch_embed(int NBv, int nseg, int prec, const EmbedParams& p, hipStream_t st)
+// The visitor of the family: f(kernel, LDS bytes) for every build of kernel K that the values select (EVERY: all of them, dispatch.hpp),
+// until one returns an error.  hipErrorInvalidValue: no such build.
+template <NodeKernel K, class F>
+static hipError_t with_node_builds(int NB, int prec, int n, int flag, F&& f)
 {
-    TI_DISPATCH_NB(NBv, {
-        (void)WAVES;
-        if (prec == 2) launch_embed16<NB, 2>(nseg, p, st);
-        else if (prec == 1) launch_embed16<NB, 1>(nseg, p, st);
-        else launch_embed16<NB, 0>(nseg, p, st);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_edge(int NBv, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked)
-{
-    if (masked) switch (NBv) {
-        case 1: return launch_edge_mask_nb1(first, last, prec, p, st);
-        case 2: return launch_edge_mask_nb2(first, last, prec, p, st);
-        case 4: return launch_edge_mask_nb4(first, last, prec, p, st);
-        case 8: return launch_edge_mask_nb8(first, last, prec, p, st);
-        default: return hipErrorInvalidValue;
-    }
-    switch (NBv) {
-        case 1: return launch_edge_nb1(first, last, prec, p, st);
-        case 2: return launch_edge_nb2(first, last, prec, p, st);
-        case 4: return launch_edge_nb4(first, last, prec, p, st);
-        case 8: return launch_edge_nb8(first, last, prec, p, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-// ---- pair-major message kernel: per-atom sums of the partial rows (painn_pair_kernel.hpp writes one row of 7 F floats per block and
-// slot).  One thread per float4 of a node's row; the partial rows of an atom are added in walk order: fixed order, no atomics.
-__global__ __launch_bounds__(256) void pair_reduce_kernel(const PairReduceParams p)
-{
-    const int per = 7 * p.F / 4, F4 = p.F / 4;                  // float4 per partial row: ds [0, F4), dv [F4, 4 F4), c [4 F4, 7 F4)
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long node = t / per;
-    const int f4 = (int)(t - node * per);
-    if (node >= p.B * p.A || (!p.has_c && f4 >= 4 * F4)) return;
-    const long long mol = node / p.A;
-    const int atom = (int)(node - mol * p.A);
-    const long long g = mol / p.G;
-    const int32_t* pl = p.plist + ((size_t)(mol - g * p.G) * p.A + atom) * p.kmax;
-    const f32x4* base = reinterpret_cast<const f32x4*>(p.part) + (size_t)g * p.nblk * 8 * per + f4;
-    f32x4 s = {0, 0, 0, 0};
-    for (int k = 0; k < p.kmax; ++k) {
-        const int id = pl[k];
-        if (id < 0) break;
-        s += base[(size_t)id * per];
-    }
-    if (f4 < F4) reinterpret_cast<f32x4*>(p.dsacc)[(size_t)node * F4 + f4] = s;
-    else if (f4 < 4 * F4) reinterpret_cast<f32x4*>(p.dvacc)[(size_t)node * 3 * F4 + (f4 - F4)] = s;
-    else reinterpret_cast<f32x4*>(p.cacc)[(size_t)node * 3 * F4 + (f4 - 4 * F4)] = s;
-}
-hipError_t launch_pair_reduce(const PairReduceParams& p, hipStream_t st)
-{
-    const long long threads = p.B * p.A * (7 * p.F / 4);
-    hipLaunchKernelGGL(pair_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_pair(int NBv, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked)
-{
-    if (masked) switch (NBv) {
-        case 1: return launch_pair_mask_nb1(first, last, prec, p, st);
-        case 2: return launch_pair_mask_nb2(first, last, prec, p, st);
-        case 4: return launch_pair_mask_nb4(first, last, prec, p, st);
-        default: return hipErrorInvalidValue;
-    }
-    switch (NBv) {
-        case 1: return launch_pair_nb1(first, last, prec, p, st);
-        case 2: return launch_pair_nb2(first, last, prec, p, st);
-        case 4: return launch_pair_nb4(first, last, prec, p, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-bool pair_kernel_exists(int NB, int prec) { return NB <= 4 && (prec == TI_PREC_F32 || prec == TI_PREC_F16X2); }
-
-hipError_t launch_update(int NBv, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded)
-{
-    if (folded && !pair_folds_cross(prec)) return hipErrorInvalidValue;
-    TI_DISPATCH_NB(NBv, {
-        (void)WAVES;
-        const dim3 g((unsigned)((p.N + 63) / 64));                 // 4 waves x 16 atoms per workgroup
-        const size_t l = update_lds_bytes(NB, prec == 2);
-        if (prec == 2) {
-            if (has_next) hipLaunchKernelGGL((painn_update_kernel<2 * NB, true, 2>), g, dim3(256), l, st, p);
-            else hipLaunchKernelGGL((painn_update_kernel<2 * NB, false, 2>), g, dim3(256), l, st, p);
-        } else if (prec == 1 && folded) {
-            if (has_next) hipLaunchKernelGGL((painn_update_kernel<2 * NB, true, 1, true>), g, dim3(256), l, st, p);
-            else hipLaunchKernelGGL((painn_update_kernel<2 * NB, false, 1, true>), g, dim3(256), l, st, p);
-        } else if (prec == 1) {
-            if (has_next) hipLaunchKernelGGL((painn_update_kernel<2 * NB, true, 1>), g, dim3(256), l, st, p);
-            else hipLaunchKernelGGL((painn_update_kernel<2 * NB, false, 1>), g, dim3(256), l, st, p);
-        } else {
-            if (has_next) hipLaunchKernelGGL((painn_update_kernel<2 * NB, true, 0>), g, dim3(256), l, st, p);
-            else hipLaunchKernelGGL((painn_update_kernel<2 * NB, false, 0>), g, dim3(256), l, st, p);
+    hipError_t e = hipSuccess;
+    bool any = false;
+    dispatch_int<1, 2, 4, 8>(NB, [&](auto bc) { dispatch_int<0, 1, 2>(prec, [&](auto pc) { dispatch_int<0, 1, 2, 3, 4>(n, [&](auto nc) { dispatch_bool(flag, [&](auto fc) {
+        constexpr int nb = decltype(bc)::value, PREC = decltype(pc)::value, N = decltype(nc)::value;
+        constexpr bool FLAG = decltype(fc)::value;
+        if constexpr (node_build_exists(K, PREC, N, FLAG)) {
+            any = true;
+            if (e == hipSuccess) e = f(node_kernel<K, 2 * nb, PREC, N, FLAG>(), K == NODE_UPDATE ? update_lds_bytes(nb, PREC == 2) : node16_lds_bytes(nb, PREC == 2));
         }
+    }); }); }); });
+    return any ? e : hipErrorInvalidValue;
+}
+template <NodeKernel K>
+static hipError_t configure_node(int NB)
+{
+    return with_node_builds<K>(NB, EVERY, EVERY, EVERY, [](auto kernel, size_t lds) { return set_lds(kernel, lds); });
+}
+template <NodeKernel K, class P>
+static hipError_t launch_node(int NB, int prec, int n, bool flag, const P& p, hipStream_t st)
+{
+    return with_node_builds<K>(NB, prec, n, flag, [&](auto kernel, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((p.N + 63) / 64)), dim3(256), lds, st, p);       // 4 waves x 16 atoms per workgroup
+        return hipGetLastError();
     });
-    return hipGetLastError();
 }
 
-hipError_t launch_readout(int NBv, int prec, const ReadoutParams& p, hipStream_t st)
+// f(NB, MASK as constants) for the one-width units of the message kernels that (NB, masked) select
+template <class F>
+static hipError_t with_message_units(int NB, int masked, F&& f)
 {
-    TI_DISPATCH_NB(NBv, {
-        (void)WAVES;
-        const dim3 g((unsigned)((p.N + 63) / 64));
-        const size_t l = node16_lds_bytes(NB, prec == 2);
-        if (prec == 2) hipLaunchKernelGGL((painn_readout16_kernel<2 * NB, 2>), g, dim3(256), l, st, p);
-        else if (prec == 1) hipLaunchKernelGGL((painn_readout16_kernel<2 * NB, 1>), g, dim3(256), l, st, p);
-        else hipLaunchKernelGGL((painn_readout16_kernel<2 * NB, 0>), g, dim3(256), l, st, p);
+    hipError_t e = hipSuccess;
+    const bool any = dispatch_int<1, 2, 4, 8>(NB, [&](auto bc) { dispatch_bool(masked, [&](auto mc) { if (e == hipSuccess) e = f(bc, mc); }); });
+    return any ? e : hipErrorInvalidValue;
+}
+
+hipError_t configure_painn_kernels(int NB)
+{
+    hipError_t e;
+    if ((e = configure_node<NODE_EMBED>(NB)) != hipSuccess) return e;
+    if ((e = configure_node<NODE_UPDATE>(NB)) != hipSuccess) return e;
+    if ((e = configure_node<NODE_READOUT>(NB)) != hipSuccess) return e;
+    return with_message_units(NB, EVERY, [](auto bc, auto mc) {
+        constexpr int nb = decltype(bc)::value;
+        constexpr bool MASK = decltype(mc)::value;
+        hipError_t e = configure_edge_unit<nb, MASK>();
+        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) { if (e == hipSuccess) e = configure_pair_unit<nb, MASK>(); }
+        return e;
     });
-    return hipGetLastError();
+}
+
+hipError_t launch_embed(int NB, int nseg, int prec, const EmbedParams& p, hipStream_t st)
+{
+    return launch_node<NODE_EMBED>(NB, prec, nseg, p.tv != nullptr, p, st);
+}
+hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded)
+{
+    return launch_node<NODE_UPDATE>(NB, prec, has_next, folded, p, st);
+}
+hipError_t launch_readout(int NB, int prec, const ReadoutParams& p, hipStream_t st) { return launch_node<NODE_READOUT>(NB, prec, 0, false, p, st); }
+
+hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked)
+{
+    return with_message_units(NB, masked, [&](auto bc, auto mc) { return launch_edge_unit<decltype(bc)::value, decltype(mc)::value>(first, last, prec, p, st); });
+}
+hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked)
+{
+    return with_message_units(NB, masked, [&](auto bc, auto mc) {
+        constexpr int nb = decltype(bc)::value;
+        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) return launch_pair_unit<nb, decltype(mc)::value>(first, last, prec, p, st);
+        else return hipErrorInvalidValue;
+    });
 }
 
 }  // namespace ti

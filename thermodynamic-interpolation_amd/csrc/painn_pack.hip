@@ -239,12 +239,11 @@ void build_templates(ti_handle* h, const int32_t* src, const int32_t* dst, const
 bool build_pair_template(ti_handle* h, const int32_t* src, const int32_t* dst, const int32_t* etype)
 {
     ti::PairTemplate pt;
-    if (!ti::build_pair_template(h->d.n_atoms, h->d.n_edges, src, dst, etype, pt, h->first_touch && !pair_uses_partials())) return false;
+    if (!ti::build_pair_template(h->d.n_atoms, h->d.n_edges, src, dst, etype, pt, h->first_touch)) return false;
     ti_handle::Tpl& T = h->tpl[2];
     T.G = pt.G; T.P = 1; T.nblk = pt.nblk; T.max_slots = 4;
     T.rows.upload(pt.rows); T.slotnode.upload(pt.slotnode); T.rows_h = pt.rows;
     h->pair_pos = pt.pair_pos; h->pair_fill = pt.fill;
-    h->pair_plist.upload(pt.plist); h->pair_kmax = pt.kmax;
     return true;
 }
 
@@ -396,7 +395,7 @@ void pack_painn(ti_handle* h, const float* wts)
                 chunk16(h->w[l].W2, F, 5 * F, c * F + 32 * nbo, 0);
             }
         h->st_edge.push_back(end_stream16(o));
-        if (edge_uses_one_chain(NB, prec)) {         // the same chunks in the one-accumulator format, each matrix scaled by its own power of two
+        if (edge_one_chain(prec)) {         // the same chunks in the one-accumulator format, each matrix scaled by its own power of two
             const float S[6] = {matrix_pow2_scale(wts + h->w[l].W0, F, F, 0, F, wts + h->w[l].b0, F), matrix_pow2_scale(wts + h->w[l].W1, F, F, 0, F, wts + h->w[l].b1, F),
                                 matrix_pow2_scale(wts + h->phi[l].W0, 2 * F, F, 0, 2 * F, wts + h->phi[l].b0, F), matrix_pow2_scale(wts + h->phi[l].W1, F, F, 0, F, wts + h->phi[l].b1, F),
                                 matrix_pow2_scale(wts + h->phi[l].W2, F, 5 * F, 0, F, wts + h->phi[l].b2, 5 * F), matrix_pow2_scale(wts + h->w[l].W2, F, 5 * F, 0, F, wts + h->w[l].b2, 5 * F)};
@@ -484,7 +483,7 @@ void pack_painn(ti_handle* h, const float* wts)
         ev.insert(ev.end(), wts + w.b2, wts + w.b2 + 5 * F);
     }
     h->edge_vecs.upload(ev);
-    if (edge_uses_one_chain(NB, prec)) {             // the message kernel's copy: bias rows times the scale of their matrix (EV order: W_B0 = 0, W_B1 = 3, P_B1 = 8, P_B2 = 11..15, W_B2 = 16..20)
+    if (edge_one_chain(prec)) {             // the message kernel's copy: bias rows times the scale of their matrix (EV order: W_B0 = 0, W_B1 = 3, P_B1 = 8, P_B2 = 11..15, W_B2 = 16..20)
         std::vector<float> ev1 = ev;
         for (int l = 0; l < L; ++l) {
             const float* S = h->edge_scale.data() + (size_t)l * 6;

@@ -16,9 +16,8 @@
 //     through the shared w factor (which also carries 1 / (S_phi S_w) of the one-accumulator format).
 //   * Per-atom sums (ds / dv / c): one wave owns a molecule group and walks its blocks in order, so the sums of a (block, slot) go to the
 //     atom's accumulator row with fire-and-forget float atomics, the first touch of a launch replacing the stale contents (acc_out,
-//     painn_edge_kernel.hpp) -- no reduction pass, nothing to zero (TI_PAIR_ACC_ATOMIC = 1, the default: 29.4 ms against 31.5 ms, same
-//     box, for the alternative that is kept behind TI_PAIR_ACC_ATOMIC = 0: per-(block, slot) partial rows with plain stores +
-//     `pair_reduce_kernel`, profiles/r03e_*).  The edge state is updated in the ROW layout (the de slice with the operands the other
+//     painn_edge_kernel.hpp) -- no reduction pass, nothing to zero (DESIGN.md 3.6 has the variant with partial rows and a reduction
+//     kernel that this replaced).  The edge state is updated in the ROW layout (the de slice with the operands the other
 //     way round, like the fp16 storage mode of the directed kernel): each e row has one owner, so e += de is a 16-byte load and store
 //     per lane, no atomics.
 // Per 32 directed edges: 84 chunk products and 56 chunk visits instead of 112 and 112, six LayerNorm / SiLU / operand-split phases
@@ -31,22 +30,15 @@
 
 namespace ti {
 
-__host__ __device__ constexpr bool pair_build_exists(int NB, int WAVES, int PREC) { return PREC != 2 && NB <= 4 && (WAVES == 4 || WAVES == 8); }
-// weight ring (mfma_chain.hpp PipeDMA): 2-chunk superchunks, two of them (64 KB at F = 128) in both builds.  A deeper ring (the stream
-// requested three superchunks ahead: TI_PAIR_NBUF = 4, the round's first choice) buys nothing -- every superchunk barrier drains the
-// wave's memory queue anyway as soon as a store or an atomic is in flight -- and its index arithmetic cost the
-// last-layer kernel 31 spilled registers: 26.16 ms with two buffers against 26.48 with four, same box (profiles/r03l_ring_depth.txt).
-#ifndef TI_PAIR_NBUF
-#define TI_PAIR_NBUF 2
-#endif
+// weight ring (mfma_chain.hpp PipeDMA): two superchunks of two chunks (64 KB at F = 128) in every build (pair_build_exists,
+// ti_internal.hpp); DESIGN.md 3.6 has the deeper ring that lost.
 __host__ __device__ constexpr int pair_superchunk() { return 2; }
-__host__ __device__ constexpr int pair_ring(int WAVES) { return WAVES == 8 ? TI_PAIR_NBUF : 2; }
 // + the builds that fold the cross term (pair_folds_cross): per wave, the 12 dv sums of every lane parked across the cross-gate products.
 // At F = 128 that costs the 4-wave build its second workgroup per CU (87.5 KB); it runs below 2048 groups, where a launch has at most
 // two workgroups per CU to place.
 static size_t pair_lds_bytes(int NB, int WAVES, int PREC)
 {
-    return (size_t)pair_ring(WAVES) * pair_superchunk() * edge_chunk4(NB, false) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4 +
+    return (size_t)2 * pair_superchunk() * edge_chunk4(NB, false) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4 +
            (pair_folds_cross(PREC) ? (size_t)WAVES * 12 * 64 * 4 : 0);
 }
 
@@ -66,68 +58,42 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_mask_ker
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 
-// MASK: the masked twins (painn_pair_mask_kernel), instantiated in translation units of their own (painn_pair_mask_nb*.hip)
-template <int NB, int EW, int PREC, bool MASK>
-static hipError_t configure_pair_prec()
+// The visitor of the family: f(kernel, waves, LDS bytes) for every build of width NB that the values select (EVERY: all of them,
+// dispatch.hpp), until one returns an error.  MASK: the masked twins (painn_pair_mask_kernel).  hipErrorInvalidValue: no such build.
+template <int NB, bool MASK, class F>
+static hipError_t with_pair_builds(int waves, int prec, int pos, F&& f)
 {
-    if constexpr (!pair_build_exists(NB, EW, PREC)) return hipSuccess;
-    else if constexpr (MASK) {
-    const size_t be = pair_lds_bytes(NB, EW, PREC);
-    hipError_t e;
-    if ((e = set_lds_edge(painn_pair_mask_kernel<2 * NB, true, false, PREC, EW>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_pair_mask_kernel<2 * NB, false, false, PREC, EW>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_pair_mask_kernel<2 * NB, false, true, PREC, EW>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_pair_mask_kernel<2 * NB, true, true, PREC, EW>, be)) != hipSuccess) return e;
-    return hipSuccess;
-    } else {
-    const size_t be = pair_lds_bytes(NB, EW, PREC);
-    hipError_t e;
-    if ((e = set_lds_edge(painn_pair_kernel<2 * NB, true, false, PREC, EW>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_pair_kernel<2 * NB, false, false, PREC, EW>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_pair_kernel<2 * NB, false, true, PREC, EW>, be)) != hipSuccess) return e;
-    if ((e = set_lds_edge(painn_pair_kernel<2 * NB, true, true, PREC, EW>, be)) != hipSuccess) return e;
-    return hipSuccess;
-    }
-}
-template <int NB, bool MASK = false>
-static hipError_t configure_pair_nb()
-{
-    hipError_t e;
-    if ((e = configure_pair_prec<NB, 4, 0, MASK>()) != hipSuccess) return e;
-    if ((e = configure_pair_prec<NB, 4, 1, MASK>()) != hipSuccess) return e;
-    return configure_pair_prec<NB, 8, 1, MASK>();
+    hipError_t e = hipSuccess;
+    bool any = false;
+    dispatch_int<4, 8>(waves, [&](auto wc) { dispatch_int<0, 1>(prec, [&](auto pc) {
+        constexpr int WAVES = decltype(wc)::value, PREC = decltype(pc)::value;
+        if constexpr (pair_build_exists(NB, WAVES, PREC))
+            dispatch_int<POS_FIRST, POS_MIDDLE, POS_LAST, POS_ONLY>(pos, [&](auto oc) {
+                constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0;
+                any = true;
+                if (e != hipSuccess) return;
+                if constexpr (MASK) e = f(painn_pair_mask_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
+                else e = f(painn_pair_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
+            });
+    }); });
+    return any ? e : hipErrorInvalidValue;
 }
 
-template <int NB, int EW, int PREC, bool MASK>
-static void launch_pair_p(bool first, bool last, const EdgeParams& p, hipStream_t st)
+// one feature width (ti_internal.hpp): configure every build / launch the one the call needs
+template <int NB, bool MASK>
+hipError_t configure_pair_unit()
 {
-    if constexpr (pair_build_exists(NB, EW, PREC)) {
-    const dim3 g((unsigned)((p.n_groups + EW - 1) / EW)), t(64 * EW);          // one wave = one group of G molecules
-    const size_t l = pair_lds_bytes(NB, EW, PREC);
-    if constexpr (MASK) {
-    if (first && last) hipLaunchKernelGGL((painn_pair_mask_kernel<2 * NB, true, true, PREC, EW>), g, t, l, st, p);
-    else if (first) hipLaunchKernelGGL((painn_pair_mask_kernel<2 * NB, true, false, PREC, EW>), g, t, l, st, p);
-    else if (last) hipLaunchKernelGGL((painn_pair_mask_kernel<2 * NB, false, true, PREC, EW>), g, t, l, st, p);
-    else hipLaunchKernelGGL((painn_pair_mask_kernel<2 * NB, false, false, PREC, EW>), g, t, l, st, p);
-    } else {
-    if (first && last) hipLaunchKernelGGL((painn_pair_kernel<2 * NB, true, true, PREC, EW>), g, t, l, st, p);
-    else if (first) hipLaunchKernelGGL((painn_pair_kernel<2 * NB, true, false, PREC, EW>), g, t, l, st, p);
-    else if (last) hipLaunchKernelGGL((painn_pair_kernel<2 * NB, false, true, PREC, EW>), g, t, l, st, p);
-    else hipLaunchKernelGGL((painn_pair_kernel<2 * NB, false, false, PREC, EW>), g, t, l, st, p);
-    }
-    }
+    return with_pair_builds<NB, MASK>(EVERY, EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
 }
-static bool pair_writes_partials() { return !TI_PAIR_ACC_ATOMIC; }
-template <int NB, bool MASK = false>
-static hipError_t launch_pair_nb(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
+template <int NB, bool MASK>
+hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
 {
-    if (prec != 0 && prec != 1) return hipErrorInvalidValue;
-    // 8-wave workgroups (one weight stream per CU, 4-chunk superchunks at F = 128) for the split path once every CU gets a workgroup
+    // 8-wave workgroups (one weight stream per CU) for the split path once every CU gets a workgroup
     const bool wide = prec == 1 && p.n_groups >= 2048;
-    if (wide) launch_pair_p<NB, 8, 1, MASK>(first, last, p, st);
-    else if (prec == 1) launch_pair_p<NB, 4, 1, MASK>(first, last, p, st);
-    else launch_pair_p<NB, 4, 0, MASK>(first, last, p, st);
-    return hipGetLastError();
+    return with_pair_builds<NB, MASK>(wide ? 8 : 4, prec, layer_pos(first, last), [&](auto kernel, int waves, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((p.n_groups + waves - 1) / waves)), dim3(64 * waves), lds, st, p);      // one wave = one group of G molecules
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ti

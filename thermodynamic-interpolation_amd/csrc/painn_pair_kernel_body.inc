@@ -5,30 +5,16 @@
     static_assert(PREC == 0 || PREC == 1, "the fp16 storage mode keeps the directed message kernel");
     constexpr int F = 16 * NBK, NB = (F + 31) / 32, T = 64 * WAVES, CH4 = edge_chunk4(NB, false);
     using A16 = r16::Act<NBK>;
-    constexpr bool ONE = edge_one_chain(NB, PREC);
+    constexpr bool ONE = edge_one_chain(PREC);
     using OP = std::conditional_t<ONE, r16::Opnd1<NBK>, typename r16::OpSel<NBK, PREC>::type>;
     extern __shared__ f32x4 lds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 15, q = lane >> 4;
-    constexpr int SC = pair_superchunk(), NBUF = pair_ring(WAVES);
+    constexpr int SC = pair_superchunk(), NBUF = 2;                                 // two superchunks in LDS (PipeDMA)
     float* scratch = reinterpret_cast<float*>(lds + NBUF * SC * CH4) + wave * 64;  // [16 pair rows][4] edge_dir of direction A
     float* vec = reinterpret_cast<float*>(lds + NBUF * SC * CH4) + WAVES * 64;     // [EV::COUNT][F]
     for (int i = threadIdx.x; i < EV::COUNT * F / 4; i += T)
         reinterpret_cast<f32x4*>(vec)[i] = reinterpret_cast<const f32x4*>(p.vecs)[i];
-#ifndef TI_PAIR_STAGGER
-#define TI_PAIR_STAGGER 0
-#endif
-    // Output-stage trims, each measured alone against the kernel without it (profiles/outstage_items.txt, DESIGN.md 3.6):
-#ifndef TI_PAIR_SEED_BIAS
-#define TI_PAIR_SEED_BIAS 1       // out3 starts its accumulators at the bias of the slice (like the hidden layers and the de slice) instead of adding it after the products
-#endif
-#ifndef TI_PAIR_SKIP_INVALID
-#define TI_PAIR_SKIP_INVALID 1    // rows of pairs that do not exist neither load nor store their e rows, their parked encoding and their edge_dir
-#endif
-#ifndef TI_PAIR_GROUP_BASE
-#define TI_PAIR_GROUP_BASE 1      // node rows addressed as (wave-uniform base of the group) + (small per-lane offset): the 64-bit part of every address is scalar work
-                                  // (seeds -1.1 %, absent rows -0.9 % of a launch; the group bases measured neutral)
-#endif
-    PipeDMA<NB, T, SC, CH4, WAVES == 8 && TI_PAIR_STAGGER, NBUF> pipe;        // 8 waves: SIMD partners half a phase apart (mfma_chain.hpp)
+    PipeDMA<NB, T, SC, CH4> pipe;        // two buffers, one closing barrier per superchunk (mfma_chain.hpp)
     pipe.init(reinterpret_cast<const f32x4*>(p.stream), p.nch, lds, wave, lane);
 
     const float eps_w0 = ONE ? 1e-5f * p.wscale[0] * p.wscale[0] : 1e-5f, eps_w1 = ONE ? 1e-5f * p.wscale[1] * p.wscale[1] : 1e-5f;
@@ -37,13 +23,17 @@
     const long long gi_raw = (long long)blockIdx.x * WAVES + wave;
     const bool group_ok = gi_raw < p.n_groups;
     const long long gi = group_ok ? gi_raw : p.n_groups - 1;
+    // (node_of and the 64-bit node indices taken from it below -- nI, nJ, nIq, nJq, qnA, qnB -- address nothing any more: they are what is
+    // left of the addressing that the group bases replaced.  Deleting them changes hipcc's register allocation in every pair kernel, so
+    // they stay until a change that may move instructions: profiles/launch_layer_identity.txt, DESIGN.md 6 item 5.)
     auto node_of = [&](int mol_local, int atom) {
         long long m = gi * p.G + mol_local;
         m = m < p.B ? m : p.B - 1;
         return m * p.A + atom;
     };
-    // TI_PAIR_GROUP_BASE: the group's first node is the same for the whole wave, so the node arrays are addressed from per-group bases
-    // that live in scalar registers, with the node inside the group (< G * A) as an unsigned 32-bit lane offset
+    // The group's first node is the same for the whole wave, so the node arrays are addressed from per-group bases that live in scalar
+    // registers, with the node inside the group (< G * A) as an unsigned 32-bit lane offset: the 64-bit part of every address is scalar
+    // work (DESIGN.md 3.6)
     const long long gnode0 = gi * p.G * (long long)p.A;
     const unsigned mol_cap = (unsigned)(p.B - 1 - gi * p.G);               // molecules past the batch's end read the last one, as node_of
     auto lnode_of = [&](int mol_local, int atom) {
@@ -77,18 +67,18 @@
         // ---- K1 geometry of this lane's pair row (the 4 quarters compute the same row); direction A: r = x[I] - x[J]
         const uint32_t meta = TI_PAIR_ROWS[blk * 16 + j];
         const long long nI = node_of(prow_molI(meta), prow_atomI(meta)), nJ = node_of(prow_molJ(meta), prow_atomJ(meta));
-        const unsigned lI = lnode_of(prow_molI(meta), prow_atomI(meta)), lJ = lnode_of(prow_molJ(meta), prow_atomJ(meta));   // the same nodes inside the group
+        const unsigned lI = lnode_of(prow_molI(meta), prow_atomI(meta)), lJ = lnode_of(prow_molJ(meta), prow_atomJ(meta));   // the row's two nodes inside the group
         // row_ok: this lane's pair row exists.  A row that does not contributes nothing (w factor 0) and no valid row reads its e row,
-        // its parked encoding or its edge_dir: with TI_PAIR_SKIP_INVALID it loads none of them (zeros instead) and stores none
-        const bool row_ok = !TI_PAIR_SKIP_INVALID || (meta & 1u) != 0;
+        // its parked encoding or its edge_dir: it loads none of them (zeros instead) and stores none
+        const bool row_ok = (meta & 1u) != 0;
         const size_t brow0 = ((size_t)gi * p.nblk + blk) * 16;       // pair rows: parked encoding / edge_dir
         const size_t erowA = brow0 * 2, erowB = erowA + 16;             // e rows of the two directions
         OP enc;
         f32x4* const enc_park = reinterpret_cast<f32x4*>(p.enc) + (brow0 / 16) * (sizeof(OP) / 16) * 64 + lane;
         f32x4* const geo_park = reinterpret_cast<f32x4*>(p.geo) + brow0 + j;
         if constexpr (FIRST) {
-            const float* const xI = TI_PAIR_GROUP_BASE ? x_g + lI * 3u : p.x + nI * 3;
-            const float* const xJ = TI_PAIR_GROUP_BASE ? x_g + lJ * 3u : p.x + nJ * 3;
+            const float* const xI = x_g + lI * 3u;
+            const float* const xJ = x_g + lJ * 3u;
             const float rx = xI[0] - xJ[0];
             const float ry = xI[1] - xJ[1];
             const float rz = xI[2] - xJ[2];
@@ -109,7 +99,7 @@
                 if (row_ok) dd = *geo_park;
                 *reinterpret_cast<f32x4*>(scratch + j * 4) = dd;
             }
-            if (TI_PAIR_SKIP_INVALID) __builtin_memset(&enc, 0, sizeof(OP));
+            __builtin_memset(&enc, 0, sizeof(OP));
             if (row_ok) r16::opnd_load(enc, enc_park);
         }
         TI_STAMP();
@@ -152,10 +142,8 @@
                 scA = inA.set_scaled(tA);
                 inB = inA; scB = scA;
             } else {
-                if (TI_PAIR_SKIP_INVALID) {
 #pragma unroll
-                    for (int nb = 0; nb < NBK; ++nb) { tA.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; tB.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-                }
+                for (int nb = 0; nb < NBK; ++nb) { tA.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; tB.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
                 if (row_ok) {
                     r16::load_set(tA, p.e + erowA * F + (unsigned)(j * F), q);
                     r16::load_set(tB, p.e + erowB * F + (unsigned)(j * F), q);
@@ -167,8 +155,8 @@
             TI_STAMP();
 #pragma unroll
             for (int c = 0; c < NB; ++c) {
-                const float* const PI = TI_PAIR_GROUP_BASE ? P_g + lI * (unsigned)F : p.P + (size_t)nI * F;
-                const float* const PJ = TI_PAIR_GROUP_BASE ? P_g + lJ * (unsigned)F : p.P + (size_t)nJ * F;
+                const float* const PI = P_g + lI * (unsigned)F;
+                const float* const PJ = P_g + lJ * (unsigned)F;
                 f32x4 a0 = r16::load_block(PI, 2 * c, q) * ivA, a1 = r16::load_block(PI, 2 * c + 1, q) * ivA;
                 f32x4 b0 = r16::load_block(PJ, 2 * c, q) * ivB, b1 = r16::load_block(PJ, 2 * c + 1, q) * ivB;
                 r16::gemm_x2_on_pipe<false>(a0, a1, b0, b1, inA, inB, pipe, lane);
@@ -203,26 +191,17 @@
         f32x4 wfac;                                      // row mask x 1 / (S_phi S_w): rides on the shared w factor
 #pragma unroll
         for (int r = 0; r < 4; ++r) wfac[r] = (mi[r] & 1u) ? inv_out : 0.0f;
-        // partial-sum rows of this lane row: direction A's sums belong to J slot q (row 4 + q of the block's eight), direction B's to I slot q
-#ifndef TI_PAIR_ACC_ATOMIC
-#define TI_PAIR_ACC_ATOMIC 1      // 1 (default, measured 29.4 vs 31.5 ms same box): per-atom sums straight into dsacc / dvacc / cacc with fire-and-forget
-                                  // atomics (first touch replaces), no reduction pass; 0: per-(block, slot) partial rows + pair_reduce_kernel
-#endif
-        float* const part_blk = p.part + ((size_t)gi * p.nblk + blk) * 8 * (7 * F);
+        // the destination atoms of this lane row: direction A's sums belong to J slot q, direction B's to I slot q; molecules of the batch only
         const int snJ = p.slotnode[blk * 16 + 4 + q], snI = p.slotnode[blk * 16 + q];
-        const bool haveA = group_ok && snJ >= 0 && (!TI_PAIR_ACC_ATOMIC || gi * p.G + slot_mol(snJ) < p.B);
-        const bool haveB = group_ok && snI >= 0 && (!TI_PAIR_ACC_ATOMIC || gi * p.G + slot_mol(snI) < p.B);
-        float* const partA = part_blk + (size_t)(4 + q) * (7 * F);
-        float* const partB = part_blk + (size_t)q * (7 * F);
-        // atomic variant: the accumulator rows of the two destination atoms, laid out as three arrays (ds [F], dv [3F], c [3F] per node)
+        const bool haveA = group_ok && snJ >= 0 && gi * p.G + slot_mol(snJ) < p.B;
+        const bool haveB = group_ok && snI >= 0 && gi * p.G + slot_mol(snI) < p.B;
         const int qnA = (int)((gi * p.G + slot_mol(snJ)) * p.A) + (snJ & 255), qnB = (int)((gi * p.G + slot_mol(snI)) * p.A) + (snI & 255);
         const bool qfA = (snJ & SLOT_FIRST_TOUCH) != 0, qfB = (snI & SLOT_FIRST_TOUCH) != 0;
-        // the same nodes inside the group (TI_PAIR_GROUP_BASE); touched only where haveA / haveB hold, i.e. for molecules of the batch
+        // their nodes inside the group; touched only where haveA / haveB hold
         const unsigned lnA = (unsigned)slot_mol(snJ) * (unsigned)p.A + (unsigned)(snJ & 255), lnB = (unsigned)slot_mol(snI) * (unsigned)p.A + (unsigned)(snI & 255);
-        auto acc_ptr = [&](int node, unsigned lnode, int off) {   // off as for the partial rows: ds 0.., dv F.., c 4F..   (node < 2^31 / (3 F))
-            if (TI_PAIR_GROUP_BASE)
-                return off < F ? ds_g + (lnode * (unsigned)F + (unsigned)off) : off < 4 * F ? dv_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - F)) : c_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - 4 * F));
-            return off < F ? p.dsacc + (size_t)node * F + off : off < 4 * F ? p.dvacc + (size_t)node * 3 * F + (off - F) : p.cacc + (size_t)node * 3 * F + (off - 4 * F);
+        // the accumulator rows of a node, laid out as three arrays (ds [F], dv [3F], c [3F] per node); off: ds 0.., dv F.., c 4F..
+        auto acc_ptr = [&](int /*node: see node_of*/, unsigned lnode, int off) {
+            return off < F ? ds_g + (lnode * (unsigned)F + (unsigned)off) : off < 4 * F ? dv_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - F)) : c_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - 4 * F));
         };
         const long long nIq = node_of(prow_molI(mi[0]), prow_atomI(mi[0]));      // source of direction A for all four rows of this lane
         const unsigned lIq = lnode_of(prow_molI(mi[0]), prow_atomI(mi[0]));
@@ -232,42 +211,30 @@
         auto out3 = [&](int c, int nbo, f32x4& rA0, f32x4& rA1, f32x4& rB0, f32x4& rB1) {
             const float* bp = vec + (EV::P_B2 + c) * F + 32 * nbo + j;
             const float* bw = vec + (EV::W_B2 + c) * F + 32 * nbo + j;
-            if (TI_PAIR_SEED_BIAS) {
-                // the bias is one scalar per lane here (features on lanes) and already carries the scale of its matrix (painn_pack.hip: the
-                // message kernel's vector block), i.e. the scale the one-accumulator products carry: it seeds the sums
-                const float p0 = bp[0], p1 = bp[16], q0 = bw[0], q1 = bw[16];
-                f32x4 a0 = {p0, p0, p0, p0}, a1 = {p1, p1, p1, p1}, b0 = a0, b1 = a1, w0 = {q0, q0, q0, q0}, w1 = {q1, q1, q1, q1};
-                r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
-                pipe.release();
-                r16::gemm_on_pipe<true>(w0, w1, g2, pipe, lane);
-                pipe.release();
-                w0 *= wfac; w1 *= wfac;
-                rA0 = a0 * w0; rA1 = a1 * w1;
-                rB0 = b0 * w0; rB1 = b1 * w1;
-            } else {
-                f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0}, b0 = {0, 0, 0, 0}, b1 = {0, 0, 0, 0}, w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
-                r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
-                pipe.release();
-                r16::gemm_on_pipe<true>(w0, w1, g2, pipe, lane);
-                pipe.release();
-                w0 = (w0 + bw[0]) * wfac; w1 = (w1 + bw[16]) * wfac;
-                rA0 = (a0 + bp[0]) * w0; rA1 = (a1 + bp[16]) * w1;
-                rB0 = (b0 + bp[0]) * w0; rB1 = (b1 + bp[16]) * w1;
-            }
+            // the bias is one scalar per lane here (features on lanes) and already carries the scale of its matrix (painn_pack.hip: the
+            // message kernel's vector block), i.e. the scale the one-accumulator products carry: it seeds the sums, like the hidden
+            // layers' and the de slice's
+            const float p0 = bp[0], p1 = bp[16], q0 = bw[0], q1 = bw[16];
+            f32x4 a0 = {p0, p0, p0, p0}, a1 = {p1, p1, p1, p1}, b0 = a0, b1 = a1, w0 = {q0, q0, q0, q0}, w1 = {q1, q1, q1, q1};
+            r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
+            pipe.release();
+            r16::gemm_on_pipe<true>(w0, w1, g2, pipe, lane);
+            pipe.release();
+            w0 *= wfac; w1 *= wfac;
+            rA0 = a0 * w0; rA1 = a1 * w1;
+            rB0 = b0 * w0; rB1 = b1 * w1;
         };
         // direction A: sum over the four lane rows (the I slots) for each register (J slot); lane row q' ends with J slot q'
         auto sumA = [&](const f32x4& v) {
             using QS = r16::QuarterSum<4>;
             return QS::swap32_add(QS::swap16_add(v[0], v[1]), QS::swap16_add(v[2], v[3]));
         };
-        // off: offset of the quantity inside a partial row (ds 0, dv (1 + c) F, c (4 + c) F) plus the lane's feature
+        // off: offset of the quantity inside a node's accumulator rows (ds 0, dv (1 + c) F, c (4 + c) F) plus the lane's feature
         auto putA = [&](float z0, float z1, int off) {
-            if (TI_PAIR_ACC_ATOMIC) { if (haveA) { float* d = acc_ptr(qnA, lnA, off); acc_out(d, z0, qfA); acc_out(d + 16, z1, qfA); } }
-            else if (haveA) { partA[off] = z0; partA[off + 16] = z1; }
+            if (haveA) { float* d = acc_ptr(qnA, lnA, off); acc_out(d, z0, qfA); acc_out(d + 16, z1, qfA); }
         };
         auto putB = [&](float z0, float z1, int off) {
-            if (TI_PAIR_ACC_ATOMIC) { if (haveB) { float* d = acc_ptr(qnB, lnB, off); acc_out(d, z0, qfB); acc_out(d + 16, z1, qfB); } }
-            else if (haveB) { partB[off] = z0; partB[off + 16] = z1; }
+            if (haveB) { float* d = acc_ptr(qnB, lnB, off); acc_out(d, z0, qfB); acc_out(d + 16, z1, qfB); }
         };
         // direction B: the four registers of a lane are the J slots of ONE destination I[q]
         auto sumB = [&](const f32x4& v) { return (v[0] + v[1]) + (v[2] + v[3]); };
@@ -323,7 +290,7 @@
                     oA0 = r16::load_block(em, 2 * nbo, q); oA1 = r16::load_block(em, 2 * nbo + 1, q);
                     oB0 = oA0; oB1 = oA1;
                 } else {
-                    if (TI_PAIR_SKIP_INVALID) oA0 = oA1 = oB0 = oB1 = f32x4{0.f, 0.f, 0.f, 0.f};
+                    oA0 = oA1 = oB0 = oB1 = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (row_ok) {
                         oA0 = r16::load_block(ea, 2 * nbo, q); oA1 = r16::load_block(ea, 2 * nbo + 1, q);
                         oB0 = r16::load_block(eb, 2 * nbo, q); oB1 = r16::load_block(eb, 2 * nbo + 1, q);
@@ -345,8 +312,8 @@
                 out3(1, nbo, sA0, sA1, sB0, sB1);
                 float vI[3][2], vJ[3][2];                // v of I[q] (source of direction A for the lane's four rows) and of J[q]
                 if (!FIRST) {
-                    const float* vp = TI_PAIR_GROUP_BASE ? v_g + (lIq * (unsigned)(3 * F) + (unsigned)fo) : p.v + (size_t)nIq * 3 * F + fo;
-                    const float* vq = TI_PAIR_GROUP_BASE ? v_g + (lJq * (unsigned)(3 * F) + (unsigned)fo) : p.v + (size_t)nJq * 3 * F + fo;
+                    const float* vp = v_g + (lIq * (unsigned)(3 * F) + (unsigned)fo);
+                    const float* vq = v_g + (lJq * (unsigned)(3 * F) + (unsigned)fo);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         vI[c][0] = vp[c * F]; vI[c][1] = vp[c * F + 16];
@@ -378,8 +345,7 @@
                         else
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                const float* vr = TI_PAIR_GROUP_BASE ? v_g + (lnode_of(prow_molJ(mi[r]), prow_atomJ(mi[r])) * (unsigned)(3 * F) + (unsigned)(c * F + fo))
-                                                                     : p.v + (size_t)node_of(prow_molJ(mi[r]), prow_atomJ(mi[r])) * 3 * F + c * F + fo;
+                                const float* vr = v_g + (lnode_of(prow_molJ(mi[r]), prow_atomJ(mi[r])) * (unsigned)(3 * F) + (unsigned)(c * F + fo));
                                 j0[r] = vr[0]; j1[r] = vr[16];
                             }
                     }

@@ -2,6 +2,6 @@
 #include "painn_pair_kernel.hpp"
 
 namespace ti {
-hipError_t configure_pair_mask_nb4() { return configure_pair_nb<4, true>(); }
-hipError_t launch_pair_mask_nb4(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st) { return launch_pair_nb<4, true>(first, last, prec, p, st); }
+template hipError_t configure_pair_unit<4, true>();
+template hipError_t launch_pair_unit<4, true>(bool, bool, int, const EdgeParams&, hipStream_t);
 }  // namespace ti

@@ -2,6 +2,6 @@
 #include "painn_pair_kernel.hpp"
 
 namespace ti {
-hipError_t configure_pair_nb1() { return configure_pair_nb<1>(); }
-hipError_t launch_pair_nb1(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st) { return launch_pair_nb<1>(first, last, prec, p, st); }
+template hipError_t configure_pair_unit<1, false>();
+template hipError_t launch_pair_unit<1, false>(bool, bool, int, const EdgeParams&, hipStream_t);
 }  // namespace ti

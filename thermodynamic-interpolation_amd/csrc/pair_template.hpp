@@ -1,6 +1,6 @@
 // pair_template.hpp -- builds the pair-major edge template of the message kernel (painn_pair_kernel.hpp; word formats in
-// ti_internal.hpp).  Pure host C++ with no HIP dependency: tests/test_host_logic.py compiles it with g++ and checks its invariants
-// on complete and sparse graphs.
+// ti_internal.hpp).  Pure host C++ with no HIP dependency: tests/test_pair_template.py compiles it with g++ (tests/harness/
+// pair_template_dump.cpp) and checks its invariants on complete and sparse graphs.
 //
 // The filter branch w(enc(|r_ij|)) of SE3Message (/root/reference/mdqm9/thermo/ambient/models/cpainn.py:283-289) is shared by the
 // edges i -> j and j -> i, so the kernel walks PAIRS: a row block is a 4 x 4 tile, row 4a + b = pair (I[a], J[b]) of up to four I
@@ -26,9 +26,6 @@ struct PairTemplate {
     std::vector<uint32_t> rows;              // [nblk * 16] row words
     std::vector<int32_t> slotnode;           // [nblk * 16] slot words (k = 0..3 I slots, 4..7 J slots, rest unused = -1)
     std::vector<int> pair_pos;               // [(m * A + src) * A + dst] -> (block * 2 + direction) * 16 + pair row, -1 = no such edge
-    // The kernel writes, per block and slot, the partial sum of that slot's rows (plain stores, no atomics); plist names, per atom of the
-    // group, the partial rows that belong to it, in walk order: [(m * A + atom) * kmax + k] = block * 8 + slot, -1 = end of the list
-    std::vector<int32_t> plist; int kmax = 0;
     double fill = 0.0;                       // valid rows / all rows
 };
 
@@ -44,10 +41,11 @@ struct Blk {
 
 // src / dst / etype: the E directed edges of ONE molecule (A <= 32 atoms).  Returns false (no pair template) when the directed graph
 // is not the symmetric closure of an undirected one with one type per pair.
-// first_touch: mark (PAIR_SLOT_FIRST_TOUCH), per atom, the first slot that holds it in walk order -- inside a block the J slots
-// (direction A) before the I slots (direction B): the order the atomic variant of the kernel issues its accumulator updates in.
+// first_touch: mark (PAIR_SLOT_FIRST_TOUCH), per atom, the first slot that holds it in walk order -- blocks ascending, inside a block
+// the J slots (direction A) before the I slots (direction B): the order the kernel issues its accumulator updates in.  That update
+// replaces the accumulator's stale contents, the later ones add (ti_internal.hpp SLOT_FIRST_TOUCH).
 constexpr int32_t PAIR_SLOT_FIRST_TOUCH = 1 << 30;      // == ti::SLOT_FIRST_TOUCH (ti_internal.hpp)
-inline bool build_pair_template(int A, int E, const int32_t* src, const int32_t* dst, const int32_t* etype, PairTemplate& out, bool first_touch = false)
+inline bool build_pair_template(int A, int E, const int32_t* src, const int32_t* dst, const int32_t* etype, PairTemplate& out, bool first_touch)
 {
     using pair_detail::Blk;
     if (E <= 0 || (E & 1) || A > 32) return false;
@@ -185,18 +183,6 @@ inline bool build_pair_template(int A, int E, const int32_t* src, const int32_t*
                 out.slotnode[(size_t)bi * RB + (side ? k : 4 + k)] = first | ((key / 32) << 8) | (key % 32);
             }
     }
-    // partial-sum lists per atom: slot k of block bi (k < 4: the I slots = direction B's destinations; k >= 4: the J slots = direction
-    // A's), in walk order -- the order the reduction adds them in
-    std::vector<std::vector<int32_t>> lists((size_t)G * A);
-    for (int bi = 0; bi < nblk; ++bi)
-        for (int k = 0; k < 8; ++k) {
-            const int key = k < 4 ? best[bi].I[k] : best[bi].J[k - 4];
-            if (key >= 0) lists[(size_t)(key / 32) * A + key % 32].push_back(bi * 8 + k);
-        }
-    out.kmax = 1;
-    for (auto& l : lists) out.kmax = std::max(out.kmax, (int)l.size());
-    out.plist.assign((size_t)G * A * out.kmax, -1);
-    for (size_t a = 0; a < lists.size(); ++a) std::copy(lists[a].begin(), lists[a].end(), out.plist.begin() + a * out.kmax);
     if (n_valid * 2 != (size_t)G * E) throw std::logic_error("pair template: not every edge was placed exactly once");
     out.fill = (double)n_valid / ((double)nblk * RB);
     return true;

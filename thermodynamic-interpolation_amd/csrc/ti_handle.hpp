@@ -90,8 +90,6 @@ struct ti_handle {
     // exists for this width / precision.  pair_pos[(m * A + src) * A + dst] = e row of that directed edge of molecule-in-group m inside
     // its group: (block * 2 + direction) * 16 + pair row
     bool has_pair = false; std::vector<int> pair_pos; double pair_fill = 0.0;
-    DevBuf<int32_t> pair_plist; int pair_kmax = 0;     // per atom of a group: its partial-sum rows (pair_template.hpp)
-    DevBuf<float> part;                                // [groups * nblk][8][7 F] partial sums of the pair-major kernel
     int n_tpl = 1, active = 0, parts = 1, max_slots = 0, pinned_tpl = TI_TEMPLATE_AUTO;
     // every atom has incoming edges: the edge kernels' first touch of an accumulator replaces its contents (ti_internal.hpp
     // SLOT_FIRST_TOUCH) and nothing zeroes the accumulators between layers or calls; otherwise the update kernel zeroes them as before

@@ -45,8 +45,9 @@ __host__ __device__ inline int row_slot(uint32_t w) { return (w >> 18) & 63; }
 // direction A's is the same across the four lane rows (two lane-swap levels).
 //   row word : bit0 valid | molI<<1 (3b) | atomI<<4 (5b) | molJ<<9 (3b) | atomJ<<12 (5b) | etype<<17 (2b)     (empty slots: a safe atom)
 //   slot word: slotnode[blk*16 + k], k = 0..3 the I slots, k = 4..7 the J slots: -1, or atom | mol<<8
-// No atomics: slot k of block b writes the sum over its rows of (ds | dv | c) into partial row b*8 + k of its group; a reduction
-// (pair_reduce_kernel) adds, per atom, the partial rows the template lists for it (plist), in walk order.
+// Per-atom sums: the wave that owns the group adds the sums of slot k of block b to the atom's accumulator rows with fire-and-forget
+// atomics, in walk order (blocks ascending, inside a block the J slots before the I slots); the first slot that holds an atom in that
+// order carries SLOT_FIRST_TOUCH and replaces the stale contents (pair_template.hpp).
 // e rows: [group][block][direction][16][F]; the parked encoding / edge_dir (direction A's) once per pair: [group][block][16].
 constexpr int PAIR_MAX_G = 8;
 __host__ __device__ inline int prow_molI(uint32_t w) { return (w >> 1) & 7; }
@@ -79,18 +80,8 @@ struct EdgeParams {
     float* enc;                             // [n_groups*nblk][operand registers][64] parked encoding operand of every row block (layer 0 writes, the others read)
     float wscale[6];                        // TI_PREC_F16X2: powers of two the host scaled w.W0, w.W1, phi.W0(e), phi.W1, phi.W2, w.W2 by (else 1)
     float* geo;                             // [n_groups*nblk*16][4] parked edge_dir
-    float* part;                            // pair-major kernel: [n_groups*nblk][8 slots][7][F] partial sums (ds | dv x3 | c x3) of every slot
     unsigned long long* stamps;             // diagnostic builds (-DTI_STAMPS) only: s_memtime / s_memrealtime stamps, a buffer of their own; else NULL
 };
-
-// pair-major kernel: sum of each atom's partial rows (walk order) -> dsacc / dvacc / cacc, which the update kernel then reads
-struct PairReduceParams {
-    const float* part; const int32_t* plist;        // plist [G*A][kmax]: partial rows (block * 8 + slot) of every atom of a group, -1 = end
-    int kmax, G, A, F, nblk, has_c;                 // has_c = 0: the first layer writes no cross-gate sums
-    long long B;
-    float *dsacc, *dvacc, *cacc;
-};
-hipError_t launch_pair_reduce(const PairReduceParams& p, hipStream_t st);
 
 struct EmbedParams {
     const float4* stream; int nch;
@@ -124,11 +115,16 @@ hipError_t launch_embed(int NB, int nseg, int prec, const EmbedParams& p, hipStr
 // masked: the masked twins of the message kernels (per-molecule edge sets, ti_painn_set_edge_mask); p.rows then holds row words per
 // (group, part) instead of the template's (painn_pack.hip: masked_rows)
 hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false);
-bool edge_uses_one_chain(int NB, int prec);      // message kernel on the one-accumulator split format (painn_edge_kernel.hpp: edge_one_chain)
+// The message kernels (directed and pair-major) run TI_PREC_F16X2 on the one-accumulator split format (mfma_chain.hpp: Opnd1), at every
+// width; painn_pack.hip packs their streams and vector blocks to match.
+__host__ __device__ constexpr bool edge_one_chain(int prec) { return prec == TI_PREC_F16X2; }
 // pair-major message kernel (painn_pair_kernel.hpp): same EdgeParams, rows / slotnode of the pair template, same weight stream
 hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false);
-bool pair_kernel_exists(int NB, int prec);
-bool pair_uses_partials();          // the pair kernel writes per-(block, slot) partial sums that launch_pair_reduce adds up (else: atomics, first touch)
+// builds of the pair kernel (painn_pair_kernel.hpp): F <= 128; f32 on 4 waves, split fp16 on 4 and on 8
+__host__ __device__ constexpr bool pair_build_exists(int NB, int WAVES, int PREC)
+{
+    return (NB == 1 || NB == 2 || NB == 4) && (PREC == TI_PREC_F32 ? WAVES == 4 : PREC == TI_PREC_F16X2 && (WAVES == 4 || WAVES == 8));
+}
 // the pair kernel at this precision adds (sum cg*dir) x v[dst] to dvacc itself, per row block and slot (painn_pair_kernel_body.inc,
 // FOLD), and leaves cacc alone: the update kernel after it must be the folded one (launch_update(.., folded = true)).  The split path
 // only: it holds v[dst] of both directions in registers.  Its 4- and 8-wave builds both fold, so that a slice of groups evaluated
@@ -138,6 +134,13 @@ __host__ __device__ constexpr bool pair_folds_cross(int prec) { return prec == T
 hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded = false);
 hipError_t launch_readout(int NB, int prec, const ReadoutParams& p, hipStream_t st);
 hipError_t configure_painn_kernels(int NB);     // dynamic-LDS attributes
+// What the one-width translation units of the message kernels export (painn_{edge,pair}[_mask]_nb*.hip, one unit per width so that they
+// compile in parallel): defined in painn_edge_kernel.hpp / painn_pair_kernel.hpp, explicitly instantiated once per (NB, MASK) in its
+// unit, reached from launch_edge / launch_pair / configure_painn_kernels (painn_kernels.hip).  No pair unit exists for NB = 8.
+template <int NB, bool MASK> hipError_t launch_edge_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
+template <int NB, bool MASK> hipError_t configure_edge_unit();
+template <int NB, bool MASK> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
+template <int NB, bool MASK> hipError_t configure_pair_unit();
 
 // ---- forward-mode derivative of the drift (painn_jvp_kernels.hip; virtual-molecule layout described there).
 // D = 3A and xdot == NULL: unit seeds (direction d -> atom d/3, component d%3); otherwise D explicit directions xdot [B][D][A][3]

@@ -4,7 +4,9 @@
 
 Every kernel symbol of OLD must exist in NEW with the same instructions (branch targets and other addresses masked, since a
 kernel's offset inside its code object moves when others are added next to it).  Prints one line per differing or missing
-kernel, the counts, and the kernels NEW adds; exits 1 if any kernel of OLD differs or is missing.
+kernel, the counts, and the kernels NEW adds; exits 1 if any kernel of OLD differs or is missing.  llvm-objdump's "..." (zero fill it
+skips behind a kernel's last instruction; whether there is any depends on what follows the kernel in its code object) is no instruction
+and is left out.
 """
 import os
 import re
@@ -17,13 +19,13 @@ from test_build_isa import code_objects, kernels as co_kernels  # noqa: E402  (t
 
 def kernels(lib):
     """{demangled kernel symbol: [instructions]} over every gfx950 code object of `lib` (first occurrence of a symbol), branch
-    targets masked."""
+    targets masked, zero-fill marks dropped."""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         for co in code_objects(lib, tmp):
             for name, insns in co_kernels(co).items():
                 if name not in out:
-                    out[name] = [re.sub(r"\b0x[0-9a-f]+\b|<[^>]*>", "#", i) if i.startswith(("s_cbranch", "s_branch")) else i for i in insns]
+                    out[name] = [re.sub(r"\b0x[0-9a-f]+\b|<[^>]*>", "#", i) if i.startswith(("s_cbranch", "s_branch")) else i for i in insns if i != "..."]
     return out
 
 

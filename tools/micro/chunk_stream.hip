@@ -1,6 +1,6 @@
 // Microbenchmark of the weight-chunk stream of the edge kernel alone: LDS-DMA superchunks, barriers, fragment reads and the
 // 3-product split-fp16 MFMA steps of mfma_chain.hpp -- no LayerNorm, no gathers, no atomics.  Reports cycles per chunk.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../thermodynamic-interpolation_amd/csrc [-DTI_FRAG_AHEAD=n] -o chunk_stream chunk_stream.hip
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../thermodynamic-interpolation_amd/csrc -o chunk_stream chunk_stream.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
