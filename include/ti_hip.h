@@ -351,6 +351,51 @@ int ti_obs_weights(ti_handle* h, const float* logw, int64_t B, float* out_w, dou
  * are not binned) -- sum(out_hist) + sum(out_tails) = 1 to round-off.  n_bins outside 1..256 or hi <= lo: TI_E_ARG. */
 int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* logw, int64_t B, int32_t n_bins, double lo, double hi,
                 double* out_hist, double* out_tails, int mem);
+/* Bootstrap of the estimators the reference's analysis reports with a 95 % interval (mdqm9/analysis/results_00031.py gen_ess_*,
+ * gen_free_energy_*), after its IQR outlier filter (utils/sensititvity.py filter_iqr).  v_i = logw[i] = -phi_i, m = max v,
+ * w_i = exp(v_i - m); fp64 arithmetic on the fp32 inputs.  Over a multiset S of sample indices:
+ *   TI_BOOT_ESS    (sum_S w)^2 / sum_S w^2              calc_ESS
+ *   TI_BOOT_TFEP   -(m + ln(sum_S w / |S|))             calc_tfep_dF with unit weights: -ln <exp(-phi)>
+ *   TI_BOOT_MEAN   -(sum_S v) / |S|                     calc_bg_dF: <phi>
+ * Filter: q25, q75 by numpy's default (linear) percentile rule -- at position h = (|S| - 1) p the value x_[h] + (h - [h]) (x_[h]+1 -
+ * x_[h]) of the sorted x -- iqr = q75 - q25, keep q25 - k iqr < x < q75 + k iqr; x = w for ESS and TFEP (the reference filters
+ * exp(v); the rule is scale invariant, so the kept set is the same), x = v for MEAN.  Nothing kept (always so for one sample or a
+ * constant sample, whose iqr is 0): NaN.
+ *   TI_BOOT_FILTER_NONE      the population is all n samples
+ *   TI_BOOT_FILTER_ONCE      (gen_ess_ti, gen_ess_bg) the sample is filtered once; the survivors, in index order, are the population of
+ *                            the point estimate and of every resample
+ *   TI_BOOT_FILTER_RESAMPLE  (gen_free_energy_*) the point estimate is that of the once-filtered sample; every resample draws from all
+ *                            n samples and is filtered by its own quartiles
+ * Draws.  idx == NULL: a resample draws n_draw population indices (n_draw == 0: as many as the population holds).  Draw j of global
+ * resample R = first + r is  (u * n_pop) >> 64  with the 64-bit u = o[2 (j & 1)] | o[2 (j & 1) + 1] << 32 of the four 32-bit words
+ *   o = Philox4x32-10(counter = (j >> 1, R & 0xffffffff, R >> 32, 0x424f4f54), key = (seed & 0xffffffff, seed >> 32)),
+ * so the estimate of resample R depends on (seed, R, the data, the mode) only -- not on n_boot, on first beyond R, or on the GPU
+ * that computes it.  idx != NULL: row r holds the n_draw >= 1 population indices of resample r (the reference's own np.random.choice
+ * rows; with RESAMPLE, n_draw = the kept count and indices below it reproduce the reference drawing only len(filtered) indices over
+ * the unfiltered arrays).  An index row gives the same bits whether it came from the generator or from idx.  Every sum runs in an
+ * order fixed by n_draw; a call repeats bit for bit.
+ * out [4] (host): the point estimate; the (1 - level) / 2 and (1 + level) / 2 percentiles of the n_boot estimates by the same linear
+ * rule (NaN with n_boot == 0 or a NaN estimate, as np.percentile); the kept count of the point estimate.  out_boot [n_boot] fp64
+ * (may be NULL): the estimates.
+ * TI_E_ARG, before anything is written: a NULL handle, logw, d or out; n < 1 or n > 2^31 - 1; an unknown estimator, filter or mem; a
+ * filter with k not finite or <= 0; level outside (0, 1); n_boot < 0 or > 2^20; n_draw < 0; idx with n_draw < 1; an idx entry
+ * outside the population (found on the device; the entry is not followed).  TI_E_NAN: a non-finite logw, as in ti_obs_weights. */
+enum { TI_BOOT_ESS = 0, TI_BOOT_TFEP = 1, TI_BOOT_MEAN = 2 };
+enum { TI_BOOT_FILTER_NONE = 0, TI_BOOT_FILTER_ONCE = 1, TI_BOOT_FILTER_RESAMPLE = 2 };
+#define TI_BOOT_DOMAIN 0x424f4f54u   /* the fourth counter word of the draws ("BOOT") */
+#define TI_BOOT_MAX_RESAMPLES (1 << 20)
+typedef struct {
+    int32_t  estimator, filter;
+    double   k;        /* IQR multiple, finite and > 0; ignored with FILTER_NONE */
+    double   level;    /* 0 < level < 1; the interval is the (1-level)/2 and (1+level)/2 percentiles */
+    int64_t  n_boot;   /* >= 0; 0 = point estimate only */
+    int64_t  first;    /* resample r of this call is global resample first + r (lets ranks split a bootstrap) */
+    uint64_t seed;
+} ti_boot_desc;
+/* logw [n] fp32, idx [n_boot, n_draw] int32 or NULL, out_boot [n_boot] fp64 or NULL: [host|device] by mem.
+   out [4] host double: point estimate, lower, upper, kept count of the point estimate. */
+int ti_obs_bootstrap(ti_handle* h, const float* logw, int64_t n, const ti_boot_desc* d,
+                     const int32_t* idx, int64_t n_draw, double* out, double* out_boot, int mem);
 /* Observer: with one attached, every rollout entry point (ti_painn_rollout, _dlogp, _dlogp_est, ti_adw_rollout, _dlogp) also
  * evaluates the K CVs on the state at the grid points i with i % every == 0 and at the last one -- ti_rollout_rows(n_step, every)
  * rows, whatever save_every is -- and writes them to out_cv [rows, B, K] fp32 ([host|device] by mem; the caller sizes it for the

@@ -35,9 +35,15 @@ ABI_SYMBOLS = [
     "ti_adw_create_nd", "ti_painn_set_edge_mask", "ti_painn_set_molecules",
     "ti_obs_cv", "ti_obs_weights", "ti_obs_hist", "ti_obs_set_observer",
     "ti_adw_rollout_fused",
+    "ti_obs_bootstrap",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
+# ti_obs_bootstrap: estimators (TI_BOOT_*), filter modes (TI_BOOT_FILTER_*), the fourth counter word of the draws, the most resamples of a call
+BOOT_ESTIMATORS = {"ess": 0, "tfep": 1, "mean": 2}
+BOOT_FILTERS = {"none": 0, "once": 1, "resample": 2}
+BOOT_DOMAIN = 0x424F4F54
+BOOT_MAX_RESAMPLES = 1 << 20
 
 
 class PainnDesc(C.Structure):
@@ -54,6 +60,11 @@ class RolloutDesc(C.Structure):
     _fields_ = [("scheme", C.c_int32), ("n_step", C.c_int32), ("save_every", C.c_int32), ("mem", C.c_int32),
                 ("eps", C.c_float), ("com_free_noise", C.c_int32), ("seed", C.c_uint64), ("traj_offset", C.c_int64),
                 ("t_grid", C.POINTER(C.c_float)), ("rtol", C.c_float), ("atol", C.c_float), ("step_offset", C.c_int64)]
+
+
+class BootDesc(C.Structure):
+    _fields_ = [("estimator", C.c_int32), ("filter", C.c_int32), ("k", C.c_double), ("level", C.c_double), ("n_boot", C.c_int64),
+                ("first", C.c_int64), ("seed", C.c_uint64)]
 
 
 class TiError(RuntimeError):
@@ -140,6 +151,7 @@ def lib():
     L.ti_obs_hist.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                               C.c_int]
     L.ti_obs_set_observer.argtypes = [vp, ip, C.c_int32, fp, ip, C.c_int32, vp, C.c_int]
+    L.ti_obs_bootstrap.argtypes = [vp, vp, C.c_int64, C.POINTER(BootDesc), vp, C.c_int64, C.POINTER(C.c_double), vp, C.c_int]
     _lib = L
     return L
 

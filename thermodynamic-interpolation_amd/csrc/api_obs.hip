@@ -118,6 +118,104 @@ int ti_obs_weights(ti_handle* h, const float* logw, int64_t B, float* out_w, dou
     });
 }
 
+// numpy's default percentile of the sorted s at fraction p: linear between the neighbours of position (n - 1) p (numpy's _lerp)
+static double percentile_sorted(const std::vector<double>& s, double p)
+{
+    const double pos = (double)(s.size() - 1) * p, fl = std::floor(pos), t = pos - fl;
+    const size_t i = (size_t)fl;
+    if (i + 1 >= s.size()) return s.back();
+    const double a = s[i], b = s[i + 1];
+    return t >= 0.5 ? b - (b - a) * (1.0 - t) : a + (b - a) * t;
+}
+
+int ti_obs_bootstrap(ti_handle* h, const float* logw, int64_t n, const ti_boot_desc* d, const int32_t* idx, int64_t n_draw, double* out,
+                     double* out_boot, int mem)
+{
+    // the checks that need no device come first, so they can be exercised with a NULL handle; that one is refused last
+    if (!logw || !d || !out) return fail(TI_E_ARG, "NULL buffer");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (n < 1 || n > (int64_t)INT32_MAX) return fail(TI_E_ARG, "n must be in 1..2^31-1");
+    if (d->estimator < TI_BOOT_ESS || d->estimator > TI_BOOT_MEAN) return fail(TI_E_ARG, "unknown estimator");
+    if (d->filter < TI_BOOT_FILTER_NONE || d->filter > TI_BOOT_FILTER_RESAMPLE) return fail(TI_E_ARG, "unknown filter");
+    if (d->filter != TI_BOOT_FILTER_NONE && !(std::isfinite(d->k) && d->k > 0.0)) return fail(TI_E_ARG, "k must be finite and > 0");
+    if (!(d->level > 0.0 && d->level < 1.0)) return fail(TI_E_ARG, "level must be in (0, 1)");
+    if (d->n_boot < 0 || d->n_boot > TI_BOOT_MAX_RESAMPLES) return fail(TI_E_ARG, "n_boot must be in 0..2^20");
+    if (n_draw < 0 || n_draw > (int64_t)INT32_MAX) return fail(TI_E_ARG, "n_draw must be in 0..2^31-1");
+    if (idx && n_draw < 1) return fail(TI_E_ARG, "idx needs n_draw >= 1");
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const long long nb = d->n_boot;
+        const bool mean = d->estimator == TI_BOOT_MEAN, filtered = d->filter != TI_BOOT_FILTER_NONE;
+        Staged sg(h, mem);
+        const float* ld = sg.in(logw, h->obs_logw, (size_t)n);
+        const int32_t* id = idx && nb > 0 ? sg.in(idx, h->boot_idx, (size_t)nb * (size_t)n_draw) : nullptr;
+        // the shift and the refusal of ti_obs_weights
+        grow(h->obs_red, 4 + 259);
+        grow(h->obs_part, (size_t)OBS_MAX_BLOCKS * 259);
+        double norm[2];
+        HIP_CHECK(launch_obs_logw_max(h->obs_red.p, h->obs_part.p, ld, n, st));
+        HIP_CHECK(hipMemcpyAsync(norm, h->obs_red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (norm[1] < (double)n) return fail(TI_E_NAN, "non-finite logw at index " + std::to_string((long long)norm[1]));
+        // the point estimate: the identity row, filtered once; ONCE: its survivors become the population
+        grow(h->boot_pt, 5);
+        grow(h->boot_flag, 1);
+        grow(h->boot_est, (size_t)std::max<long long>(nb, 1));
+        HIP_CHECK(hipMemsetAsync(h->boot_flag.p, 0, sizeof(int), st));
+        BootParams p{};
+        p.v = ld; p.n_pop = n; p.n_draw = n; p.source = BOOT_SRC_IDENTITY;
+        p.estimator = d->estimator; p.filter = filtered; p.k = d->k; p.m = norm[0];
+        p.seed = d->seed; p.first = d->first;
+        p.est = h->boot_pt.p; p.kept = h->boot_pt.p + 1; p.bounds = h->boot_pt.p + 2; p.flag = h->boot_flag.p;
+        HIP_CHECK(launch_obs_boot(p, 1, st));
+        long long n_pop = n;
+        if (d->filter == TI_BOOT_FILTER_ONCE) {
+            grow(h->boot_pop, (size_t)n);
+            HIP_CHECK(launch_obs_boot_compact(h->boot_pop.p, h->boot_pt.p + 4, ld, n, mean, norm[0], h->boot_pt.p + 2, st));
+        }
+        double pt[5] = {0, 0, 0, 0, 0};
+        HIP_CHECK(hipMemcpyAsync(pt, h->boot_pt.p, sizeof(pt), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (d->filter == TI_BOOT_FILTER_ONCE) { n_pop = (long long)pt[4]; p.v = h->boot_pop.p; }
+        // the resamples
+        const long long nd = n_draw > 0 ? n_draw : n_pop;
+        std::vector<double> est((size_t)nb, std::nan(""));
+        if (id && n_pop == 0) return fail(TI_E_ARG, "idx entry outside the population (the filter kept nothing)");
+        if (nb > 0 && n_pop > 0) {
+            p.n_pop = n_pop; p.n_draw = nd; p.source = id ? BOOT_SRC_INDEX : BOOT_SRC_PHILOX; p.idx = id;
+            p.filter = d->filter == TI_BOOT_FILTER_RESAMPLE;
+            p.est = h->boot_est.p; p.kept = nullptr; p.bounds = nullptr;
+            HIP_CHECK(launch_obs_boot(p, nb, st));
+            int flag = 0;
+            HIP_CHECK(hipMemcpyAsync(&flag, h->boot_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(est.data(), h->boot_est.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            if (flag) return fail(TI_E_ARG, "idx entry outside 0.." + std::to_string(n_pop - 1));
+        }
+        double lower = std::nan(""), upper = std::nan("");
+        if (nb > 0 && std::none_of(est.begin(), est.end(), [](double e) { return std::isnan(e); })) {
+            std::vector<double> s(est);
+            std::sort(s.begin(), s.end());
+            lower = percentile_sorted(s, (1.0 - d->level) / 2.0);
+            upper = percentile_sorted(s, (1.0 + d->level) / 2.0);
+        }
+        out[0] = pt[0]; out[1] = lower; out[2] = upper; out[3] = pt[1];
+        if (out_boot && nb > 0) {
+            if (mem == TI_MEM_HOST) std::copy(est.begin(), est.end(), out_boot);
+            else if (n_pop > 0) {
+                HIP_CHECK(hipMemcpyAsync(out_boot, h->boot_est.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice, st));
+                HIP_CHECK(hipStreamSynchronize(st));
+            } else {
+                HIP_CHECK(hipMemcpyAsync(out_boot, est.data(), (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipStreamSynchronize(st));
+            }
+        }
+        return TI_OK;
+    });
+}
+
 int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* logw, int64_t B, int32_t n_bins, double lo, double hi,
                 double* out_hist, double* out_tails, int mem)
 {

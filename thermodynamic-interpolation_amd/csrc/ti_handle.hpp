@@ -142,6 +142,9 @@ struct ti_handle {
     struct ObsSet { int K = 0; bool has_ref = false, has_sel = false; DevBuf<int32_t> desc, sel; DevBuf<float> ref; } obs[2];
     int obs_every = 0, obs_mem = TI_MEM_HOST; float* obs_out = nullptr;
     DevBuf<float> obs_x, obs_cv, obs_val, obs_logw, obs_w; DevBuf<double> obs_red, obs_part;
+    // bootstrap (ti_obs_bootstrap): the once-filtered population, staged index rows, the estimates ahead of their validation, the
+    // point row's (estimate, kept count, lower and upper filter bound, size of the compacted population), the bad-index flag
+    DevBuf<float> boot_pop; DevBuf<int32_t> boot_idx; DevBuf<double> boot_est, boot_pt; DevBuf<int> boot_flag;
 
     ~ti_handle()
     {

@@ -359,4 +359,24 @@ hipError_t launch_obs_weights(float* w, const float* logw, const double* norm, l
 hipError_t launch_obs_whist(double* out, double* partial, const float* values, long long stride, const float* logw, const double* norm, long long B,
                             int n_bins, double lo, double hi, hipStream_t st);
 
+// ---- bootstrap (obs_boot_kernels.hip; include/ti_hip.h ti_obs_bootstrap)
+enum { BOOT_SRC_PHILOX = 0, BOOT_SRC_INDEX = 1, BOOT_SRC_IDENTITY = 2 };
+struct BootParams {
+    const float* v;                         // [n_pop] the population: logw itself, or the survivors of the once-only filter
+    long long n_pop, n_draw;                // draws per resample; IDENTITY: n_draw == n_pop
+    int source;                             // BOOT_SRC_*: where the indices of a resample come from
+    const int32_t* idx;                     // [rows][n_draw] (INDEX)
+    int estimator, filter;                  // TI_BOOT_*; filter != 0: every row is filtered by its own quartiles
+    double k, m;                            // IQR multiple; the shift of the weights (max logw of the whole sample)
+    uint64_t seed; long long first;         // PHILOX: row r is global resample first + r
+    double* est;                            // [rows] estimates (NaN: nothing kept)
+    double* kept;                           // [rows] kept counts (exact in fp64), may be NULL
+    double* bounds;                         // [2] filter bounds of the (single) row, may be NULL
+    int* flag;                              // set to 1 by an explicit index outside 0..n_pop-1 (which is then not followed)
+};
+// one 256-thread group per row
+hipError_t launch_obs_boot(const BootParams& p, long long n_rows, hipStream_t st);
+// out[0 .. *n_out) = the v[i] with bounds[0] < value(v[i]) < bounds[1] in index order (value: v itself if mean, else exp(v - m))
+hipError_t launch_obs_boot_compact(float* out, double* n_out, const float* v, long long n, int mean, double m, const double* bounds, hipStream_t st);
+
 }  // namespace ti

@@ -16,7 +16,8 @@ batches then get consecutive trajectory ids, so no two molecules of a run share 
 (observables.py; adw: ``[["coord", 0]]``) writes ``observables_*.npz`` next to the samples file: ``cv`` [rows, B, K], the collective
 variables at the grid points i % every == 0 and at the last one, computed on the GPU during the rollout; ``hist`` [K, bins] and
 ``edges`` [K, bins + 1], the histogram of every CV at the end state, weighted by exp(-dlogp) when ``return_dlogp`` is set; ``ess``.
-Without the key exactly the reference's files are written.
+An integer ``"bootstrap": n`` in that dict adds ``ess_ci`` [2], the 95 % interval of the ESS from n bootstrap resamples drawn on the
+GPU (observables.bootstrap, seed 0), and ``ess_boot`` [n], their estimates.  Without the key exactly the reference's files are written.
 """
 from __future__ import annotations
 
@@ -58,6 +59,7 @@ def _observe_kw(config):
         return {}
     o = dict(o)
     o.pop("bins", None)
+    o.pop("bootstrap", None)
     if o.get("ref") is not None:
         o["ref"] = np.asarray(o["ref"], np.float32)
     return dict(observe=o)
@@ -68,7 +70,15 @@ def _write_observables(config, path, cvs, dlogps):
     cv = np.concatenate([C.to_numpy(c) for c in cvs], axis=1).astype(np.float32)
     dl = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in dlogps]) if dlogps else None
     hist, edges, ess = _obs.end_state_summary(np.ascontiguousarray(cv[-1]), dl, bins=int(dict(config.observables).get("bins", 32)))
-    np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess))
+    extra = {}
+    n_boot = dict(config.observables).get("bootstrap")
+    if n_boot is not None:                     # the ESS with its 95 % bootstrap interval (observables.bootstrap; B without weights)
+        if isinstance(n_boot, bool) or int(n_boot) != n_boot or int(n_boot) < 1:
+            raise ValueError(f"observables['bootstrap'] must be an integer >= 1, got {n_boot!r}")
+        B = cv.shape[1]
+        res = _obs.bootstrap(-dl if dl is not None else np.zeros(B, np.float32), "ess", n_boot=int(n_boot))
+        extra = dict(ess_ci=np.asarray(res.ci, np.float64), ess_boot=res.estimates)
+    np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
 
 
 def sample_ambient(config, b, dataset):

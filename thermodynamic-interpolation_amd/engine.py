@@ -183,6 +183,43 @@ class _Engine:
         _lib.check(_lib.lib().ti_obs_weights(self.h, lp, B, wp, C.byref(ess), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return w, ess.value
 
+    def bootstrap(self, logw, estimator, filter=0, k=1.0, level=0.95, n_boot=1000, first=0, seed=0, indices=None, out_boot=None):
+        """ti_obs_bootstrap: (point, lower, upper, n_kept, estimates [n_boot] float64) of the estimator / filter codes (TI_BOOT_*) on
+        logw [n] float32.  indices [n_boot, n_draw] int32: explicit population indices instead of the generator's draws.  logw numpy:
+        indices numpy, estimates numpy; logw a CUDA tensor: indices a CUDA int32 tensor, estimates a CUDA float64 tensor."""
+        n, n_boot = int(logw.shape[0]), int(n_boot)
+        dev_in = hasattr(logw, "data_ptr") and logw.is_cuda
+        n_draw, ip, keep_i = 0, None, None
+        if indices is not None:
+            if tuple(indices.shape[:1]) != (n_boot,) or len(indices.shape) != 2:
+                raise ValueError(f"indices must be [n_boot = {n_boot}, n_draw], got {tuple(indices.shape)}")
+            n_draw = int(indices.shape[1])
+            if dev_in:
+                if not (hasattr(indices, "data_ptr") and indices.is_cuda and str(indices.dtype) == "torch.int32" and indices.is_contiguous()):
+                    raise TypeError("indices must be a contiguous CUDA int32 tensor when logw is a CUDA tensor")
+                if (indices.device.index or 0) != self.device:
+                    raise ValueError(f"indices live on {indices.device} but this engine was created on device {self.device}")
+                keep_i, ip = indices, C.c_void_p(indices.data_ptr())
+            else:
+                if hasattr(indices, "data_ptr"):
+                    indices = indices.detach().cpu().numpy()
+                keep_i = np.ascontiguousarray(indices, np.int32)
+                ip = C.c_void_p(keep_i.ctypes.data)
+        if out_boot is None and n_boot > 0:
+            if dev_in:
+                import torch
+                out_boot = torch.empty(n_boot, dtype=torch.float64, device=logw.device)
+            else:
+                out_boot = np.empty(n_boot, np.float64)
+        bp = None
+        if out_boot is not None:
+            bp = C.c_void_p(out_boot.data_ptr() if hasattr(out_boot, "data_ptr") else out_boot.ctypes.data)
+        (lp,), dev, keep = self._ptrs((logw, (n,), False, "logw"))
+        desc = _lib.BootDesc(int(estimator), int(filter), float(k), float(level), n_boot, int(first), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        out = (C.c_double * 4)()
+        _lib.check(_lib.lib().ti_obs_bootstrap(self.h, lp, n, C.byref(desc), ip, n_draw, out, bp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return out[0], out[1], out[2], int(out[3]), out_boot
+
     def weighted_histogram(self, values, logw, bins, range):
         """(hist [bins] float64, tails [3] float64 = weight below range[0], at or above range[1], of non-finite values).  values: a
         1-D float32 array or a column view such as cv[:, k] (read in place through its stride); logw None: uniform weights."""

@@ -10,9 +10,16 @@ A descriptor is a tuple whose first entry names the kind:
 with the conventions of the reference's mdqm9/analysis/utils/mol_geometry.py (compute_distance / compute_angle / compute_torsion).
 Indices are local to a molecule; in a mixed-species batch a descriptor that names an atom a molecule does not have gives NaN there.
 
-No arithmetic happens in this module apart from turning a histogram into a free-energy profile.
+Bootstrap intervals (ti_obs_bootstrap): ``bootstrap`` and the wrappers ``ess_ti``, ``free_energy_tfep``, ``free_energy_bg`` mirror the
+gen_* functions of the reference's mdqm9/analysis/results_00031.py -- a point estimate with a percentile interval over resamples
+drawn and reduced on the GPU, after the reference's IQR outlier filter.
+
+No arithmetic happens in this module apart from turning a histogram into a free-energy profile, forming phi from its terms, and
+the difference of two bootstrap runs in ``free_energy_bg``.
 """
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 
@@ -105,6 +112,77 @@ def weighted_histogram(values, logw, bins, range, engine=None):
     edge goes to the upper bin -- and the weight below, at or above the range, and of non-finite values.  logw None: weights 1 / B."""
     check_bins(bins, range)
     return (engine or _service_engine(_device_of(values, logw))).weighted_histogram(values, logw, bins, range)
+
+
+BootstrapResult = collections.namedtuple("BootstrapResult", "point ci estimates n_kept")
+BootstrapResult.__doc__ = """point: the estimate of the (filtered) sample; ci: (lower, upper) percentiles of the resample estimates;
+estimates [n_boot] float64 (where logw lives); n_kept: samples the point estimate's filter kept."""
+
+
+def bootstrap(logw, estimator, k=None, filter=None, n_boot=1000, seed=0, level=0.95, indices=None, first=0, engine=None):
+    """Point estimate and percentile interval of `estimator` ('ess', 'tfep' = -ln<exp(logw)>, 'mean' = -<logw>) of logw = -phi [n]
+    float32 (numpy or CUDA tensor).  k: the IQR multiple of the reference's filter_iqr, None: no filter.  filter: 'none', 'once' (the
+    sample is filtered once and resampled from the survivors: gen_ess_ti), 'resample' (every resample of the whole sample is filtered
+    by its own quartiles: gen_free_energy_*); default 'none' without k, else 'once' for 'ess' and 'resample' for the free energies, as
+    the reference pairs them.  Resample r is global resample first + r of the stream `seed` (ranks can split one bootstrap);
+    indices [n_boot, n_draw] int32 replaces the generator's draws."""
+    if estimator not in _lib.BOOT_ESTIMATORS:
+        raise ValueError(f"estimator must be one of {sorted(_lib.BOOT_ESTIMATORS)}, got {estimator!r}")
+    if filter is None:
+        filter = "none" if k is None else "once" if estimator == "ess" else "resample"
+    if filter not in _lib.BOOT_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(_lib.BOOT_FILTERS)}, got {filter!r}")
+    if filter != "none" and (k is None or not np.isfinite(k) or k <= 0):
+        raise ValueError(f"filter {filter!r} needs a finite k > 0, got {k!r}")
+    if isinstance(n_boot, bool) or int(n_boot) != n_boot or not 0 <= int(n_boot) <= _lib.BOOT_MAX_RESAMPLES:
+        raise ValueError(f"n_boot must be an integer in 0..{_lib.BOOT_MAX_RESAMPLES}, got {n_boot!r}")
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must be in (0, 1), got {level!r}")
+    if len(logw.shape) != 1 or int(logw.shape[0]) < 1:
+        raise ValueError("logw must be 1-D and non-empty")
+    eng = engine or _service_engine(_device_of(logw))
+    point, lo, hi, kept, est = eng.bootstrap(logw, _lib.BOOT_ESTIMATORS[estimator], _lib.BOOT_FILTERS[filter], 1.0 if k is None else float(k),
+                                             float(level), int(n_boot), int(first), int(seed), indices)
+    return BootstrapResult(point, (lo, hi), est, kept)
+
+
+def _neg_phi(*terms):
+    """-(sum of the terms) formed in fp64 and rounded to fp32 once; a CUDA tensor if any term is one."""
+    if any(hasattr(t, "data_ptr") for t in terms):
+        import torch
+        dev = next((t.device for t in terms if hasattr(t, "data_ptr") and t.is_cuda), None)
+        phi = sum(torch.as_tensor(t, device=dev).to(torch.float64).reshape(-1) for t in terms)
+        return (-phi).to(torch.float32).contiguous()
+    return (-sum(np.asarray(t, np.float64).reshape(-1) for t in terms)).astype(np.float32)
+
+
+def _neg(a):
+    return -a if hasattr(a, "data_ptr") else -np.asarray(a, np.float64)
+
+
+def ess_ti(E0, E1, neg_dlogp, k=None, **kw):
+    """gen_ess_ti: the ESS of the TI map's weights exp(-phi), phi = E1 - E0 + neg_dlogp, filtered once when k is given."""
+    return bootstrap(_neg_phi(E1, _neg(E0), neg_dlogp), "ess", k=k, **kw)
+
+
+def free_energy_tfep(E0, E1, neg_dlogp, k=None, **kw):
+    """gen_free_energy_tfep_md_ti (and, with E_T1 + neg_dlogp_T1 - neg_dlogp_T0 folded into the terms, gen_free_energy_bg_tfep):
+    dF = -ln<exp(-phi)>, phi = E1 - E0 + neg_dlogp; with k every resample is filtered on exp(-phi) by its own quartiles."""
+    return bootstrap(_neg_phi(E1, _neg(E0), neg_dlogp), "tfep", k=k, **kw)
+
+
+def free_energy_bg(E_T0, neg_dlogp_T0, E_T1, neg_dlogp_T1, k=None, seed=0, **kw):
+    """gen_free_energy_bg: dF = <phi1> - <phi0>, phi_i = E_Ti + neg_dlogp_Ti; the two samples are resampled independently (two calls,
+    seeds 2 seed and 2 seed + 1) and the interval is taken over the differences of their estimates."""
+    level = float(kw.get("level", 0.95))
+    r0 = bootstrap(_neg_phi(E_T0, neg_dlogp_T0), "mean", k=k, seed=2 * int(seed), **kw)
+    r1 = bootstrap(_neg_phi(E_T1, neg_dlogp_T1), "mean", k=k, seed=2 * int(seed) + 1, **kw)
+    if r0.estimates is None:
+        return BootstrapResult(r1.point - r0.point, (float("nan"), float("nan")), None, (r0.n_kept, r1.n_kept))
+    diff = r1.estimates - r0.estimates
+    host = diff.detach().cpu().numpy() if hasattr(diff, "data_ptr") else diff
+    ci = (float("nan"), float("nan")) if np.isnan(host).any() else tuple(np.percentile(host, [50 * (1 - level), 50 * (1 + level)]))
+    return BootstrapResult(r1.point - r0.point, ci, diff, (r0.n_kept, r1.n_kept))
 
 
 def free_energy_profile(x, logw, bins=80, range=(-2.5, 2.5), engine=None):
