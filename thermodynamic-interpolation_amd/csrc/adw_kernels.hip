@@ -354,7 +354,10 @@ __global__ void nan_check_kernel(const float* __restrict__ x, long long n, int* 
 }
 
 // MFMA lane-map self-test: D = A * B with A[i][k] = 1 + i + 100k, B[k][j] = 1000 + j - 7k; also returns the
-// accumulator-layout ids so the host can check (reg, lane) -> (row, col) independently.
+// accumulator-layout ids so the host can check (reg, lane) -> (row, col) independently.  On the 32x32x2 f32 instruction, which only
+// this test still issues.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __global__ void selftest_kernel(float* out)
 {
     const int l = threadIdx.x;

@@ -1,36 +1,36 @@
 // mfma_chain.hpp -- gfx950 building blocks shared by the drift kernels.
 //
-// Design: every dense layer of the drift networks is evaluated with the exact-f32 matrix
-// instruction v_mfma_f32_32x32x2_f32.  A wave owns 32 "rows" (edges, atoms or particles) and keeps their
-// activations in registers for the whole MLP chain:
+// Design: a wave owns 16 "rows" (edges, atom pairs, atoms or particles) and keeps their activations in registers
+// for a whole MLP chain; every dense layer is a run of 16x16 matrix instructions.  Everything below the few lane-level helpers
+// lives in namespace r16.
 //
-//   * An activation set Act<NB> holds F = 32*NB features of 32 rows in NB*16 VGPRs per lane.  Lane l = (j, h) with
-//     j = l & 31 (the row) and h = l >> 5; register (nb, i) holds feature  feat(nb,i,h) = 32*nb + 8*(i>>2) + 4*h + (i&3).
-//     This is exactly the C/D accumulator layout of the 32x32 MFMA when the product is computed transposed,
-//     D[n][row] = sum_k W[n][k] * X[row][k]  (weights as the A operand, activations as the B operand), so the output
-//     of one layer is the B operand of the next with no data movement: k-step s uses register s of the input set.
-//   * Because 4 consecutive registers hold 4 consecutive features, a lane loads/stores rows of row-major [row][F]
-//     tensors and per-feature vectors (bias, gamma, beta) as float4 at offset 32*nb + 8*g + 4*h  (g = i>>2).
-//   * Weights are pre-packed on the host (pack.cpp) into "chunks": 32 output features x F inputs, laid out
-//     [k-step/4][lane][4] so that a wave reads one conflict-free ds_read_b128 per 4 MFMAs.  All waves of a workgroup
-//     walk the same chunk stream, double-buffered through LDS (one barrier per chunk).
-//   * The same chunk used with the operands swapped gives the flipped product D[row][n] (features on lanes, rows in
-//     registers), used where a reduction over rows is needed.
+//   * Layout.  An activation set r16::Act<NBK> holds F = 16*NBK features of 16 rows in NBK float4 (4*NBK VGPRs) per lane.
+//     Lane l = (j, q), j = l & 15 (the row), q = l >> 4 (the quarter); register (nb, r) holds feature 16*nb + 4*q + r.  That is
+//     the C/D accumulator layout of the 16x16 MFMA for the transposed product  D[n][row] = sum_k W[n][k] * X[row][k]  (weights
+//     as the A operand, activations as B), so the output of one layer is the B operand of the next with no data movement.
+//     Four consecutive registers hold four consecutive features: rows of row-major [row][F] tensors and per-feature vectors
+//     (bias, gamma, beta) are float4 accesses at 16*nb + 4*q.  A row's statistics are in-lane sums plus two VALU lane swaps over
+//     its four quarters (xquarters).  With the operands swapped the same weights give the flipped product D[row][n]: lane
+//     (n = l & 15, q) register r holds row 4*q + r of feature n; used where a sum over rows follows.
+//   * Operand formats (OpSel; the kernels' PREC).  Opnd<NBK, false>: the fp32 set itself on v_mfma_f32_16x16x4_f32.  The others
+//     run on v_mfma_f32_16x16x32_f16, one instruction per PAIR of 16-feature blocks -- a lane's 8 k-slots are the 8 values it
+//     holds in b[2m], b[2m+1], so the chaining property is kept:  Opnd<NBK, true>, split fp16 x = hi + 2^-11 lo, three products,
+//     the cross terms in an accumulator of their own;  Opnd1<NBK>, unscaled split against weights scaled to the top of the fp16
+//     range, three products into ONE accumulator (message kernels);  OpndH<NBK>, the fp16 storage mode, one product.
+//   * Chunk images.  Weights are packed once on the host (painn_pack.hip) into chunks of 32 output features x F inputs -- two
+//     16-feature blocks -- in the order the lanes read them, one conflict-free 16-byte LDS read per fragment:
+//       fp32 (pack_chunk16):  chunk[(blk*NBK + nbi)*64 + l][r] = W[row0 + 16*blk + (l&15)][col0 + 16*nbi + 4*(l>>4) + r]
+//       split (pack_chunk16_split, pack_chunk16_split1):  [(blk*(NBK/2) + m)*2 + {0: hi, 1: lo}][lane] of 8 halves, the same size
+//       fp16 storage (pack_chunk16_half):  the hi fragments only, half the size
+//   * PipeDMA.  All waves of a workgroup walk the same cyclic chunk stream through two LDS buffers filled by LDS-DMA, one
+//     barrier per superchunk (SC chunks).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace ti {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int NB>
-struct Act {
-    f32x16 b[NB];
-};
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 // ---- cross-lane exchanges on the VALU (gfx950 v_permlane16_swap / v_permlane32_swap), never through the LDS crossbar.
 //   swap16(a, b): the odd 16-lane rows of a <-> the even rows of b;   swap32(a, b): rows 2,3 of a <-> rows 0,1 of b.
@@ -64,80 +64,13 @@ __device__ __forceinline__ float rsqrt_nr(float x)
     const float r = __builtin_amdgcn_rsqf(x);
     return r * __builtin_fmaf(-0.5f * x * r, r, 1.5f);
 }
-// v + (the value of the lane 32 away), in every lane
-__device__ __forceinline__ float xhalf_sum(float v)
-{
-    float a = v, b = v;
-    lane_swap32(a, b);              // a = [lo, lo], b = [hi, hi]
-    return a + b;
-}
 
 // ------------------------------------------------------------------------------------------------ weight chunk pipe
-// A "logical chunk" is 256*NB float4 (32 output features x F inputs).  SC logical chunks are staged per barrier interval
-// (a superchunk): the gap between two MFMA bursts -- drain, ds_write, barrier, first ds_reads -- is paid once per SC chunks.
-// T = threads per workgroup.  Usage: p = acquire(); ...GEMM on p...; release();   (uniform control flow only)
-template <int NB, int T, int SC = 1>
-struct Pipe {
-    static constexpr int CH4 = 256 * NB;            // float4 per logical chunk
-    static constexpr int SUP4 = CH4 * SC;           // float4 per superchunk
-    static constexpr int PER = (SUP4 + T - 1) / T;
-    const f32x4* __restrict__ g;
-    f32x4* l[2];
-    int nsup, idx, par, sub;
-    f32x4 st[PER];
-
-    __device__ __forceinline__ void init(const f32x4* stream, int n_chunks, f32x4* lds)
-    {
-        g = stream; nsup = n_chunks / SC; idx = 0; par = 0; sub = 0;
-        l[0] = lds; l[1] = lds + SUP4;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int o = threadIdx.x + k * T;
-            if (SUP4 % T == 0 || o < SUP4) l[0][o] = g[o];
-        }
-        __syncthreads();
-    }
-    // start of a superchunk: kick off the global load of the following one, return the LDS image of the current one
-    __device__ __forceinline__ const f32x4* begin()
-    {
-        const int next = (idx + 1 == nsup) ? 0 : idx + 1;
-        const f32x4* src = g + (size_t)next * SUP4;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int o = threadIdx.x + k * T;
-            if (SUP4 % T == 0 || o < SUP4) st[k] = src[o];
-        }
-        return l[par];
-    }
-    __device__ __forceinline__ void end()
-    {
-        f32x4* dst = l[par ^ 1];
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int o = threadIdx.x + k * T;
-            if (SUP4 % T == 0 || o < SUP4) dst[o] = st[k];
-        }
-        __syncthreads();
-        idx = (idx + 1 == nsup) ? 0 : idx + 1;
-        par ^= 1;
-    }
-    // logical-chunk cursor on top of begin()/end()
-    __device__ __forceinline__ const f32x4* acquire()
-    {
-        if (SC == 1) return begin();
-        if (sub == 0) cur = begin();
-        return cur + sub * CH4;
-    }
-    __device__ __forceinline__ void release()
-    {
-        if (SC == 1) { end(); return; }
-        if (++sub == SC) { end(); sub = 0; }
-    }
-    const f32x4* cur;
-};
-
-// LDS-DMA variant (global_load_lds_dwordx4): the next superchunk goes straight from L2 into the other LDS buffer -- no
-// staging registers, no ds_write.  The DMA is issued when the first logical chunk of the current superchunk is released
+// A "logical chunk" is CHUNK4 float4 (32 output features x F inputs).  SC logical chunks are staged per barrier interval (a
+// superchunk): the gap between two MFMA bursts -- drain, barrier, first ds_reads -- is paid once per SC chunks.  T = threads per
+// workgroup.  Usage: wl = acquire(); ...GEMM on wl...; release();   (uniform control flow only)
+// The next superchunk goes straight from L2 into the other LDS buffer by LDS-DMA (global_load_lds_dwordx4) -- no staging
+// registers, no ds_write.  The DMA is issued when the first logical chunk of the current superchunk is released
 // (hipcc drains vmcnt(0) at the next use of an ordinary global load while a DMA is in flight, so it is kept away from
 // the GEMM prologues), and is waited for at the superchunk's closing barrier.
 // (A closing barrier deferred by half the waves of an 8-wave workgroup, and a ring deeper than two buffers, were both measured and
@@ -149,7 +82,9 @@ struct PipeDMA {
     const f32x4* __restrict__ g;
     f32x4* base;
     int nsup, idx, ahead, buf, sub, wave, lane;       // idx: superchunk being consumed, ahead: the next one to request, buf = idx % NBUF
-                                                      // (nothing reads idx; without it hipcc's code for painn_readout16_kernel<2, 0> changes: DESIGN.md 6 item 5)
+                                                      // (nothing reads idx, and `buf ^= 1` would say the same as the NBUF arithmetic.  Both stay: without idx hipcc moves
+                                                      // registers in kernels that stream weights, and with the xor form the F = 256 edge kernels spill SGPRs to scratch:
+                                                      // profiles/identity_cleanup_resources.txt)
 
     __device__ __forceinline__ void dma(const f32x4* src, f32x4* dst) const
     {
@@ -198,106 +133,9 @@ struct PipeDMA {
     }
 };
 
-// The weight float4 of k-group s+1 is read from LDS before the 4 MFMAs of group s are issued, so the ds_read latency
-// hides behind 256 cycles of matrix work instead of stalling every 4th MFMA.
-// acc[n][row] += sum_k W[n][k] * in[row][k]      (transposed product; acc is one 32-feature output block)
-template <int NB>
-__device__ __forceinline__ void gemm_bt(f32x16& acc, const Act<NB>& in, const f32x4* wl, int lane)
-{
-    f32x4 w = wl[lane];
-#pragma unroll
-    for (int nbi = 0; nbi < NB; ++nbi)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int nxt = nbi * 4 + g + 1;
-            const f32x4 wn = wl[(nxt < 4 * NB ? nxt : 0) * 64 + lane];
-            acc = mfma32(w.x, in.b[nbi][4 * g + 0], acc);
-            acc = mfma32(w.y, in.b[nbi][4 * g + 1], acc);
-            acc = mfma32(w.z, in.b[nbi][4 * g + 2], acc);
-            acc = mfma32(w.w, in.b[nbi][4 * g + 3], acc);
-            w = wn;
-        }
-}
-
-// acc[row][n] += sum_k in[row][k] * W[n][k]      (flipped: features n on lanes, rows in registers)
-template <int NB>
-__device__ __forceinline__ void gemm_fl(f32x16& acc, const Act<NB>& in, const f32x4* wl, int lane)
-{
-    f32x4 w = wl[lane];
-#pragma unroll
-    for (int nbi = 0; nbi < NB; ++nbi)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int nxt = nbi * 4 + g + 1;
-            const f32x4 wn = wl[(nxt < 4 * NB ? nxt : 0) * 64 + lane];
-            acc = mfma32(in.b[nbi][4 * g + 0], w.x, acc);
-            acc = mfma32(in.b[nbi][4 * g + 1], w.y, acc);
-            acc = mfma32(in.b[nbi][4 * g + 2], w.z, acc);
-            acc = mfma32(in.b[nbi][4 * g + 3], w.w, acc);
-            w = wn;
-        }
-}
-
-// ------------------------------------------------------------------------------------------------ row <-> set moves
-// one 32-feature block of a row-major row / per-feature vector: p points at feature 0
-__device__ __forceinline__ f32x16 load_block(const float* __restrict__ p, int nb, int h)
-{
-    f32x16 r;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p + 32 * nb + 8 * g + 4 * h);
-        r[4 * g + 0] = t.x; r[4 * g + 1] = t.y; r[4 * g + 2] = t.z; r[4 * g + 3] = t.w;
-    }
-    return r;
-}
-__device__ __forceinline__ void store_block(float* __restrict__ p, int nb, int h, const f32x16& r)
-{
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        f32x4 t = {r[4 * g + 0], r[4 * g + 1], r[4 * g + 2], r[4 * g + 3]};
-        *reinterpret_cast<f32x4*>(p + 32 * nb + 8 * g + 4 * h) = t;
-    }
-}
-template <int NB>
-__device__ __forceinline__ void load_set(Act<NB>& a, const float* __restrict__ p, int h)
-{
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) a.b[nb] = load_block(p, nb, h);
-}
 // ------------------------------------------------------------------------------------------------ elementwise pieces
 // x * sigmoid(x); v_exp_f32 / v_rcp_f32 are ~1 ulp, far below the 1e-5 parity bar
 __device__ __forceinline__ float silu(float y) { return y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)); }
-
-// torch.nn.LayerNorm(F, eps=1e-5) + SiLU over the features of each row, in place; `a` already holds x W^T + b.
-template <int NB>
-__device__ __forceinline__ void ln_silu(Act<NB>& a, const float* __restrict__ gamma, const float* __restrict__ beta, int h)
-{
-    constexpr float invF = 1.0f / (32.0f * NB);
-    float sum = 0.f;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sum += a.b[nb][i];
-    sum = xhalf_sum(sum);
-    const float mean = sum * invF;
-    float var = 0.f;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float d = a.b[nb][i] - mean;
-            var = fmaf(d, d, var);
-        }
-    var = xhalf_sum(var);
-    const float rstd = rsqrt_nr(var * invF + 1e-5f);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const f32x16 gm = load_block(gamma, nb, h);
-        const f32x16 bt = load_block(beta, nb, h);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) a.b[nb][i] = silu(fmaf((a.b[nb][i] - mean) * rstd, gm[i], bt[i]));
-    }
-}
 
 // sin and cos of an fp32 angle, branch-free and accurate (~1 ulp) for any |a| < 2^30: the reduction a - n*pi/2 is done with
 // two fp64 FMAs (53-bit pi/2 split), then the fdlibm k_sinf/k_cosf minimax polynomials on [-pi/4, pi/4] in fp32.  The ocml
@@ -319,33 +157,9 @@ __device__ __forceinline__ void sincos_cw(float a, float& s, float& c)
     c = ((q + 1) & 2) ? -cc : cc;
 }
 
-// PositionalEncoder (/root/reference/mdqm9/thermo/ambient/models/embedding.py:127-160) of one scalar per row, written
-// straight into the register layout: features 4m..4m+3 = cos(a(2m+1)), sin(a(2m+1)), cos(a(2m+2)), sin(a(2m+2)) with
-// a(k) = ((x / max_length) * k) * pi evaluated left to right in fp32 like the reference (so the ARGUMENT is bit-identical).
-template <int NB>
-__device__ __forceinline__ void posenc_set(Act<NB>& a, float x_over_len, int h)
-{
-    constexpr float PI_F = 3.14159265358979323846f;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int m = 8 * nb + 2 * g + h;
-            float s1, c1, s2, c2;
-            sincos_cw((x_over_len * (float)(2 * m + 1)) * PI_F, s1, c1);
-            sincos_cw((x_over_len * (float)(2 * m + 2)) * PI_F, s2, c2);
-            a.b[nb][4 * g + 0] = c1; a.b[nb][4 * g + 1] = s1; a.b[nb][4 * g + 2] = c2; a.b[nb][4 * g + 3] = s2;
-        }
-}
-
 // ================================================================================================================
-// 16-row variant (namespace r16): the same chaining scheme on v_mfma_f32_16x16x4_f32 (same FLOP rate as 32x32x2).
-// A wave owns 16 rows; an activation set of F = 16*NBK features is NBK*4 VGPRs per lane -- half the registers of the
-// 32-row layout -- so several independent workgroups fit on a CU and hide each other's LayerNorm / wait phases.
-//   lane l = (j, q), j = l & 15 (row), q = l >> 4;  register (nb, r) holds feature 16*nb + 4*q + r  (float4 at 16nb+4q).
-//   accumulator of the flipped product: lane (n = l & 15, q) register r holds row 4*q + r.
-// A weight chunk is still 32 output features x F inputs (two 16-feature blocks), packed [blk][nbi][lane][4] with
-//   chunk[(blk*NBK + nbi)*64 + l][r] = W[row0 + 16*blk + (l&15)][col0 + 16*nbi + 4*(l>>4) + r]          (pack_chunk16).
+// 16 rows per wave: the layout, the operand formats and the chunk images are described at the top of the file.  Half the registers
+// per activation set of a 32-row tile, so several independent workgroups fit on a CU and hide each other's LayerNorm / wait phases.
 namespace r16 {
 
 template <int NBK>
@@ -432,6 +246,9 @@ __device__ __forceinline__ void ln_silu(Act<NBK>& a, const float* gamma, const f
     }
 }
 
+// PositionalEncoder of the reference model for one scalar per row, written straight into the register layout: features 4m .. 4m+3 =
+// cos(a(2m+1)), sin(a(2m+1)), cos(a(2m+2)), sin(a(2m+2)) with a(k) = ((x / max_length) * k) * pi evaluated left to right in fp32 like
+// the reference (so the ARGUMENT is bit-identical).
 template <int NBK>
 __device__ __forceinline__ void posenc_set(Act<NBK>& a, float x_over_len, int q)
 {

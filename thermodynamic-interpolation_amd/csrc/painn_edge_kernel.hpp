@@ -74,7 +74,7 @@ static size_t edge_lds_bytes(int NB, int WAVES, bool h16) { return 2 * edge_supe
 
 
 // Where a message block stands among the layers, as one value to dispatch on: the kernels' (FIRST, LAST) = (pos & 1, pos & 2)
-enum LayerPos { POS_FIRST = 1, POS_MIDDLE = 0, POS_LAST = 2, POS_ONLY = 3 };
+enum LayerPos { POS_MIDDLE = 0, POS_FIRST = 1, POS_LAST = 2, POS_ONLY = 3 };
 inline int layer_pos(bool first, bool last) { return (first ? 1 : 0) | (last ? 2 : 0); }
 
 // The visitor of the family: f(kernel, waves, LDS bytes) for every build of width NB that the values select (EVERY: all of them,
@@ -87,7 +87,7 @@ static hipError_t with_edge_builds(int waves, int ns, int prec, int pos, F&& f)
     dispatch_int<4, 8>(waves, [&](auto wc) { dispatch_int<2, 4>(ns, [&](auto nc) { dispatch_int<0, 1, 2>(prec, [&](auto pc) {
         constexpr int WAVES = decltype(wc)::value, NS = decltype(nc)::value, PREC = decltype(pc)::value;
         if constexpr (edge_build_exists(NB, WAVES, PREC, NS))
-            dispatch_int<POS_FIRST, POS_MIDDLE, POS_LAST, POS_ONLY>(pos, [&](auto oc) {
+            dispatch_int<POS_MIDDLE, POS_FIRST, POS_LAST, POS_ONLY>(pos, [&](auto oc) {
                 constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0;
                 any = true;
                 if (e != hipSuccess) return;

@@ -68,7 +68,7 @@ static hipError_t with_pair_builds(int waves, int prec, int pos, F&& f)
     dispatch_int<4, 8>(waves, [&](auto wc) { dispatch_int<0, 1>(prec, [&](auto pc) {
         constexpr int WAVES = decltype(wc)::value, PREC = decltype(pc)::value;
         if constexpr (pair_build_exists(NB, WAVES, PREC))
-            dispatch_int<POS_FIRST, POS_MIDDLE, POS_LAST, POS_ONLY>(pos, [&](auto oc) {
+            dispatch_int<POS_MIDDLE, POS_FIRST, POS_LAST, POS_ONLY>(pos, [&](auto oc) {
                 constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0;
                 any = true;
                 if (e != hipSuccess) return;

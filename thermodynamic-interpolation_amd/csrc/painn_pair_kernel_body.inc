@@ -23,19 +23,11 @@
     const long long gi_raw = (long long)blockIdx.x * WAVES + wave;
     const bool group_ok = gi_raw < p.n_groups;
     const long long gi = group_ok ? gi_raw : p.n_groups - 1;
-    // (node_of and the 64-bit node indices taken from it below -- nI, nJ, nIq, nJq, qnA, qnB -- address nothing any more: they are what is
-    // left of the addressing that the group bases replaced.  Deleting them changes hipcc's register allocation in every pair kernel, so
-    // they stay until a change that may move instructions: profiles/launch_layer_identity.txt, DESIGN.md 6 item 5.)
-    auto node_of = [&](int mol_local, int atom) {
-        long long m = gi * p.G + mol_local;
-        m = m < p.B ? m : p.B - 1;
-        return m * p.A + atom;
-    };
     // The group's first node is the same for the whole wave, so the node arrays are addressed from per-group bases that live in scalar
     // registers, with the node inside the group (< G * A) as an unsigned 32-bit lane offset: the 64-bit part of every address is scalar
     // work (DESIGN.md 3.6)
     const long long gnode0 = gi * p.G * (long long)p.A;
-    const unsigned mol_cap = (unsigned)(p.B - 1 - gi * p.G);               // molecules past the batch's end read the last one, as node_of
+    const unsigned mol_cap = (unsigned)(p.B - 1 - gi * p.G);               // molecules past the batch's end read the last one
     auto lnode_of = [&](int mol_local, int atom) {
         const unsigned m = (unsigned)mol_local < mol_cap ? (unsigned)mol_local : mol_cap;
         return m * (unsigned)p.A + (unsigned)atom;
@@ -66,7 +58,6 @@
         TI_STAMP();
         // ---- K1 geometry of this lane's pair row (the 4 quarters compute the same row); direction A: r = x[I] - x[J]
         const uint32_t meta = TI_PAIR_ROWS[blk * 16 + j];
-        const long long nI = node_of(prow_molI(meta), prow_atomI(meta)), nJ = node_of(prow_molJ(meta), prow_atomJ(meta));
         const unsigned lI = lnode_of(prow_molI(meta), prow_atomI(meta)), lJ = lnode_of(prow_molJ(meta), prow_atomJ(meta));   // the row's two nodes inside the group
         // row_ok: this lane's pair row exists.  A row that does not contributes nothing (w factor 0) and no valid row reads its e row,
         // its parked encoding or its edge_dir: it loads none of them (zeros instead) and stores none
@@ -195,16 +186,14 @@
         const int snJ = p.slotnode[blk * 16 + 4 + q], snI = p.slotnode[blk * 16 + q];
         const bool haveA = group_ok && snJ >= 0 && gi * p.G + slot_mol(snJ) < p.B;
         const bool haveB = group_ok && snI >= 0 && gi * p.G + slot_mol(snI) < p.B;
-        const int qnA = (int)((gi * p.G + slot_mol(snJ)) * p.A) + (snJ & 255), qnB = (int)((gi * p.G + slot_mol(snI)) * p.A) + (snI & 255);
         const bool qfA = (snJ & SLOT_FIRST_TOUCH) != 0, qfB = (snI & SLOT_FIRST_TOUCH) != 0;
         // their nodes inside the group; touched only where haveA / haveB hold
         const unsigned lnA = (unsigned)slot_mol(snJ) * (unsigned)p.A + (unsigned)(snJ & 255), lnB = (unsigned)slot_mol(snI) * (unsigned)p.A + (unsigned)(snI & 255);
         // the accumulator rows of a node, laid out as three arrays (ds [F], dv [3F], c [3F] per node); off: ds 0.., dv F.., c 4F..
-        auto acc_ptr = [&](int /*node: see node_of*/, unsigned lnode, int off) {
+        auto acc_ptr = [&](unsigned lnode, int off) {
             return off < F ? ds_g + (lnode * (unsigned)F + (unsigned)off) : off < 4 * F ? dv_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - F)) : c_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - 4 * F));
         };
-        const long long nIq = node_of(prow_molI(mi[0]), prow_atomI(mi[0]));      // source of direction A for all four rows of this lane
-        const unsigned lIq = lnode_of(prow_molI(mi[0]), prow_atomI(mi[0]));
+        const unsigned lIq = lnode_of(prow_molI(mi[0]), prow_atomI(mi[0]));      // source of direction A for all four rows of this lane
 
         // (phi_c + b) of both directions times the shared (w_c + b) for output slice c (0 gates, 1 scale_edge_dir, 2 ds, 3 de,
         // 4 cross gates), features fo .. fo+31 as two 16-feature blocks
@@ -231,10 +220,10 @@
         };
         // off: offset of the quantity inside a node's accumulator rows (ds 0, dv (1 + c) F, c (4 + c) F) plus the lane's feature
         auto putA = [&](float z0, float z1, int off) {
-            if (haveA) { float* d = acc_ptr(qnA, lnA, off); acc_out(d, z0, qfA); acc_out(d + 16, z1, qfA); }
+            if (haveA) { float* d = acc_ptr(lnA, off); acc_out(d, z0, qfA); acc_out(d + 16, z1, qfA); }
         };
         auto putB = [&](float z0, float z1, int off) {
-            if (haveB) { float* d = acc_ptr(qnB, lnB, off); acc_out(d, z0, qfB); acc_out(d + 16, z1, qfB); }
+            if (haveB) { float* d = acc_ptr(lnB, off); acc_out(d, z0, qfB); acc_out(d + 16, z1, qfB); }
         };
         // direction B: the four registers of a lane are the J slots of ONE destination I[q]
         auto sumB = [&](const f32x4& v) { return (v[0] + v[1]) + (v[2] + v[3]); };
@@ -260,8 +249,7 @@
         constexpr bool FOLD = pair_folds_cross(PREC) && !FIRST;
         f32x4* const zpark = reinterpret_cast<f32x4*>(vec + EV::COUNT * F) + wave * 3 * 64 + lane;     // FOLD: [3][64 lanes] f32x4 per wave
         static_assert(!FOLD || GATHER_EARLY, "the fold crosses with the v[dst] rows that the early gathers hold");
-        const long long nJq = snJ >= 0 ? node_of(slot_mol(snJ), snJ & 255) : nIq;   // J slot q's atom: lane row q fetches it for all four
-        const unsigned lJq = snJ >= 0 ? lnode_of(slot_mol(snJ), snJ & 255) : lIq;
+        const unsigned lJq = snJ >= 0 ? lnode_of(slot_mol(snJ), snJ & 255) : lIq;   // J slot q's atom: lane row q fetches it for all four
         const float wrow = (meta & 1u) ? inv_out : 0.0f;                 // the same row factor in the row layout (lane (j, q): row j)
 
 #pragma unroll 1
