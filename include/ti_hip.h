@@ -158,7 +158,11 @@ ti_handle* ti_adw_create(const ti_adw_desc* desc, const double* weights, size_t 
  * With a d-dimensional handle the adw calls below take  x, out, x0: [B, d] row-major;  out_path: [rows, B, d];
  * beta0, beta1, t, out_div: [B];  out_dlogp: [rows, B].  out_div[i] = sum_k d b_ik / d x_ik, the exact divergence (forward mode,
  * d directions).  EM noise: coordinate k of a particle is component k of the TI_SCHEME_EM draw.  DOPRI5_TRAJ: a particle's
- * error ratio is the rms over its d entries, maxed with its dlogp entry's. */
+ * error ratio is the rms over its d entries, maxed with its dlogp entry's.
+ * TI_PREC_F16X2 (both create calls): every weight must be finite and below 65504 in magnitude (TI_E_UNSUPPORTED names the first
+ * that is not; checked before any device call).  The mode holds the f32 path's parity while every hidden activation (SiLU output)
+ * stays below 65504 in magnitude: the split operands are unscaled, so beyond that the affected rows are non-finite and rollouts
+ * report TI_E_NAN.  Tangent rows below ~1e-6 lose relative, not absolute, accuracy in out_div.  TI_PREC_F32 has neither limit. */
 ti_handle* ti_adw_create_nd(const ti_adw_desc* desc, int32_t dim, const double* weights, size_t n_weights, int device);
 /* b[i] = net([x_i, t, beta_embed([beta0_i, beta1_i, t])]);  x,beta0,beta1,out: [B] fp32 [host|device] ([B, d] x / out: see above) */
 int ti_adw_drift(ti_handle* h, const float* x, float t, const float* beta0, const float* beta1, int64_t B, float* out, int mem);

@@ -94,6 +94,10 @@ ti_handle* ti_adw_create_nd(const ti_adw_desc* d, int32_t dim, const double* wei
         const size_t need = (size_t)H * 3 + H + (size_t)H * H + H + H + 1 + (size_t)H * (dim + 2) + H + (size_t)(nl - 1) * ((size_t)H * H + H) +
                             (size_t)dim * H + dim;
         if (n_weights != need) return fail(TI_E_ARG, "weight count mismatch: expected " + std::to_string(need) + ", got " + std::to_string(n_weights));
+        if (d->precision == TI_PREC_F16X2)          // the weights' hi halves are plain fp16: refuse what would round to inf
+            for (size_t i = 0; i < n_weights; ++i)
+                if (!(std::fabs(weights[i]) < 65504.0))
+                    return fail(TI_E_UNSUPPORTED, "precision f16x2 needs every weight to be finite and below 65504 in magnitude (weight " + std::to_string(i) + ")");
         std::unique_ptr<ti_handle> h(new_handle(1, device));
         h->ad = *d; h->NB = H / 32; h->a_dim = dim;
         std::vector<float> w(n_weights);
