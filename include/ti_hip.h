@@ -429,6 +429,17 @@ int ti_painn_debug_read(ti_handle* h, int what, float* out, size_t n_floats);
  * (torch_scatter allocates its output, cpainn.py:303-304).  The edge state e and the parked edge geometry (encoding, edge_dir) are filled
  * as well: an evaluation writes every row of them before it reads it, and the pair-major kernel never touches rows of absent pairs. */
 int ti_painn_debug_poison(ti_handle* h, int64_t B, float value);
+/* Layer-0 phi table.  Entering the first message layer the phi branch sees only the embedding's output and
+ * edge_emb[type]: a function of (atom, that molecule's cond rows, t, edge type).  Molecules of a call whose A x ncond cond values are
+ * bitwise equal form a class; with at most TI_PHI0_MAX_CLASSES classes the branch is evaluated once per (class, atom, type) into a
+ * table and the pair-major message kernel of layer 0 reads it, bit for bit the value it would have computed.  More classes, per-molecule
+ * times, tangent passes, an edge mask / mixed species, a debug tap, precisions other than f16x2, the directed layouts, or
+ * TI_PHI0_TABLE=0 in the environment when the handle is created: the kernels of before run unchanged. */
+#define TI_PHI0_MAX_CLASSES 16
+/* which path layer 0 of the LAST drift evaluation of the handle took (a rollout: its last evaluation): 1 = table, 0 = fallback,
+ * -1 = no evaluation yet.  *n_classes (may be NULL): classes found by the call's class pass (TI_PHI0_MAX_CLASSES + 1: more than the
+ * cap), 0 when the call ran none. */
+int ti_painn_debug_phi0_path(ti_handle* h, int32_t* n_classes);
 /* Device self-test of the MFMA operand/accumulator lane maps the kernels rely on, of both fp32 -> (hi, lo) fp16 operand splits
  * (the 8-instruction forms of formats (a) and (b) against the plain arithmetic, bit for bit, fp16-subnormal residuals included),
  * and of the fp16 matrix instruction keeping subnormal inputs. */

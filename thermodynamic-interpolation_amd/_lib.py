@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "ti_obs_cv", "ti_obs_weights", "ti_obs_hist", "ti_obs_set_observer",
     "ti_adw_rollout_fused",
     "ti_obs_bootstrap",
+    "ti_painn_debug_phi0_path",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -135,6 +136,7 @@ def lib():
     L.ti_painn_debug_tap.argtypes = [vp, C.c_int]
     L.ti_painn_debug_read.argtypes = [vp, C.c_int, fp, C.c_size_t]
     L.ti_painn_debug_poison.argtypes = [vp, C.c_int64, C.c_float]
+    L.ti_painn_debug_phi0_path.argtypes = [vp, ip]
     L.ti_selftest.argtypes = [C.c_int]
     L.ti_painn_drift_tv.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int]
     L.ti_painn_drift_div_tv.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int]

@@ -97,6 +97,8 @@ static int painn_drift_impl(ti_handle* h, DriftMode mode, const float* x, const 
         float* od = sg.out(out, h->b1, n);
         float* otd = jvp ? sg.out(out_tan, h->tout, n) : nullptr;
         float* dd = div ? sg.out(out_div, h->divb, (size_t)B) : nullptr;
+        phi0_begin_call(h, cd, B, mode == DRIFT && !per_mol_t);      // classes of this call's molecules (the table path of layer 0)
+        struct Phi0End { ti_handle* h; ~Phi0End() { phi0_end_call(h); } } phi0_end{h};
         if (mode == DRIFT_DIV_EST) {
             painn_make_probes(h, B, n_probes, probe_seed, traj_offset);
             painn_drift_div_est_dev(h, xd, t, cd, B, n_probes, od, dd, td);
@@ -179,6 +181,9 @@ static int painn_rollout_impl(ti_handle* h, const ti_rollout_desc* rd, DriftMode
         const int saved_tap = h->tap; h->tap = -1;
         const Ragged rg = ragged_of(h);
         if (mode == DRIFT_DIV_EST) painn_make_probes(h, B, n_probes, probe_seed, rd->traj_offset);
+        // cond is constant across a rollout: one class pass for all its steps (TI_SCHEME_DOPRI5_TRAJ evaluates at per-molecule times)
+        phi0_begin_call(h, cd, B, !dlogp && rd->scheme != TI_SCHEME_DOPRI5_TRAJ);
+        struct Phi0End { ti_handle* h; ~Phi0End() { phi0_end_call(h); } } phi0_end{h};
         DlogpAux aux;
         if (dlogp) {
             aux.dl = h->dl.p; aux.d1 = h->divb.p; aux.d2 = h->div2.p; aux.scaled = h->dlscaled.p; aux.out = out_dlogp;
@@ -230,6 +235,13 @@ int ti_painn_debug_tap(ti_handle* h, int stage)
     return TI_OK;
 }
 
+int ti_painn_debug_phi0_path(ti_handle* h, int32_t* n_classes)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (n_classes) *n_classes = h->phi0_found;
+    return h->phi0_last;
+}
+
 int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)
 {
     if (!h || h->kind != 0 || B <= 0) return fail(TI_E_ARG, "not a painn handle / B");
@@ -247,6 +259,8 @@ int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)
         HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->e.p, (int)bits, h->e.n, h->stream));
         HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->enc.p, (int)bits, h->enc.n, h->stream));
         HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->geo.p, (int)bits, h->geo.n, h->stream));
+        // the layer-0 phi table too: every entry an evaluation reads was written by its own table launch
+        if (h->phi0_tab.n) HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->phi0_tab.p, (int)bits, h->phi0_tab.n, h->stream));
         return TI_OK;
     });
 }

@@ -74,7 +74,8 @@ static size_t edge_lds_bytes(int NB, int WAVES, bool h16) { return 2 * edge_supe
 
 
 // Where a message block stands among the layers, as one value to dispatch on: the kernels' (FIRST, LAST) = (pos & 1, pos & 2)
-enum LayerPos { POS_MIDDLE = 0, POS_FIRST = 1, POS_LAST = 2, POS_ONLY = 3 };
+// (+ POS_TABLE: the pair kernel's layer-0 builds that read the phi table, painn_pair_kernel.hpp)
+enum LayerPos { POS_MIDDLE = 0, POS_FIRST = 1, POS_LAST = 2, POS_ONLY = 3, POS_TABLE = 4, POS_FIRST_TABLE = 5, POS_ONLY_TABLE = 7 };
 inline int layer_pos(bool first, bool last) { return (first ? 1 : 0) | (last ? 2 : 0); }
 
 // The visitor of the family: f(kernel, waves, LDS bytes) for every build of width NB that the values select (EVERY: all of them,

@@ -20,6 +20,35 @@ void ensure_painn_ws(ti_handle* h, long long B)
     h->cap = B;
 }
 
+// ---- layer-0 phi table: the class pass of an API call.  Whether a drift of the call then takes the table path is
+// decided per evaluation (painn_drift_dev): here only what holds for the whole call.  The class count comes back to the host once
+// per call -- the device flag for "more classes than the cap" with it -- so every evaluation's launches are chosen on the host.
+void phi0_begin_call(ti_handle* h, const float* cond_dev, long long B, bool eligible)
+{
+    h->phi0_ncls = 0; h->phi0_found = 0; h->phi0_B = 0; h->phi0_cond = nullptr;
+    if (!eligible || !h->phi0_ok || h->active != 2 || h->ragged || h->emask_B > 0 || h->tap >= 0 || h->nblk == 0) return;
+    const int A = h->d.n_atoms, F = h->d.n_features;
+    grow(h->phi0_cls, (size_t)B); grow(h->phi0_state, (size_t)PHI0_STATE_WORDS);
+    grow(h->phi0_tab, (size_t)TI_PHI0_MAX_CLASSES * A * PHI0_TYPES * 3 * F);
+    int32_t state[PHI0_STATE_WORDS];
+    {
+        Timed tm(h, TI_KERNEL_PAINN_EMBED);
+        HIP_CHECK(hipMemsetAsync(h->phi0_state.p, 0xff, sizeof(state), h->stream));
+        Phi0ClassParams p{};
+        p.cond = reinterpret_cast<const uint32_t*>(cond_dev); p.words = A * h->ncond; p.B = B; p.state = h->phi0_state.p; p.cls = h->phi0_cls.p;
+        HIP_CHECK(launch_phi0_classes(p, h->stream));
+    }
+    HIP_CHECK(hipMemcpyAsync(state, h->phi0_state.p, sizeof(state), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    int n = 0;
+    while (n < TI_PHI0_MAX_CLASSES && state[n] >= 0) ++n;
+    const bool over = state[TI_PHI0_MAX_CLASSES] == 1;
+    h->phi0_found = over ? TI_PHI0_MAX_CLASSES + 1 : n;
+    if (over) return;
+    h->phi0_ncls = n; h->phi0_B = B; h->phi0_cond = cond_dev;
+}
+void phi0_end_call(ti_handle* h) { h->phi0_ncls = 0; h->phi0_B = 0; h->phi0_cond = nullptr; }
+
 // ---- forward-mode derivative: tangent workspace over ceil(B/G)*D*G virtual molecules (painn_jvp_kernels.hip header)
 long long jvp_virtual_molecules(const ti_handle* h, long long B, int D) { return (B + h->G - 1) / h->G * D * h->G; }
 
@@ -170,6 +199,19 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
         Timed tm(h, TI_KERNEL_PAINN_EMBED);
         HIP_CHECK(launch_embed(NB, h->nE, prec, p, st));
     }
+    // layer 0 on the phi table: the call's class pass stands for exactly these molecules, t is one for all of them, and nothing that
+    // the table builds do not take is in force (a mask or mixed species, a tap, a tangent pass, a directed layout)
+    const bool table = h->phi0_ncls > 0 && h->phi0_B == B && h->phi0_cond == cond_dev && b0 == 0 && h->active == 2 && !tv && !jr && !nat && !mrows &&
+                       h->tap < 0 && h->nblk > 0 && L > 0;
+    h->phi0_last = table ? 1 : 0;
+    if (table) {
+        Phi0TableParams p{};
+        p.stream = h->S(h->st_phi0_tab); p.nch = h->st_phi0_tab.nch; p.vecs = h->edge_vecs1.p; p.edge_emb = h->F(h->edge_emb);
+        for (int i = 0; i < 6; ++i) p.wscale[i] = h->edge_scale[i];
+        p.P = h->P.p; p.state = h->phi0_state.p; p.n_cls = h->phi0_ncls; p.A = A; p.tab = h->phi0_tab.p;
+        Timed tm(h, TI_KERNEL_PAINN_EMBED);
+        HIP_CHECK(launch_phi0_table(NB, L == 1, p, st));
+    }
     h->last_B = B;
     if (h->tap == 0) return;
     for (int l = 0; l < L; ++l) {
@@ -213,8 +255,13 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
 #ifdef TI_STAMPS
             if (l == 2) p.stamps = stamps_arm(groups, st);
 #endif
+            const bool on_table = table && l == 0;
+            if (on_table) {           // the w chunks alone; phi's three output slices come from the table
+                p.stream = h->S(h->st_phi0_w); p.nch = h->st_phi0_w.nch; p.wpad = h->phi0_wpad;
+                p.phi0_tab = h->phi0_tab.p; p.cls = h->phi0_cls.p;
+            }
             if (h->active == 2) {
-                HIP_CHECK(launch_pair(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr));
+                HIP_CHECK(launch_pair(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr, on_table));
 #ifdef TI_STAMPS
                 stamps_dump(h, p.stamps, groups, st);
 #endif

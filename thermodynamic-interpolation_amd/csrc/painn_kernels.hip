@@ -490,6 +490,7 @@ hipError_t configure_painn_kernels(int NB)
     if ((e = configure_node<NODE_EMBED>(NB)) != hipSuccess) return e;
     if ((e = configure_node<NODE_UPDATE>(NB)) != hipSuccess) return e;
     if ((e = configure_node<NODE_READOUT>(NB)) != hipSuccess) return e;
+    if ((e = configure_phi0_kernels(NB)) != hipSuccess) return e;
     return with_message_units(NB, EVERY, [](auto bc, auto mc) {
         constexpr int nb = decltype(bc)::value;
         constexpr bool MASK = decltype(mc)::value;
@@ -513,11 +514,11 @@ hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams
 {
     return with_message_units(NB, masked, [&](auto bc, auto mc) { return launch_edge_unit<decltype(bc)::value, decltype(mc)::value>(first, last, prec, p, st); });
 }
-hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked)
+hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked, bool table)
 {
     return with_message_units(NB, masked, [&](auto bc, auto mc) {
         constexpr int nb = decltype(bc)::value;
-        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) return launch_pair_unit<nb, decltype(mc)::value>(first, last, prec, p, st);
+        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) return launch_pair_unit<nb, decltype(mc)::value>(first, last, prec, p, st, table);
         else return hipErrorInvalidValue;
     });
 }

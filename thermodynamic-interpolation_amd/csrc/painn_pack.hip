@@ -1,5 +1,6 @@
 // painn_pack.hip -- host side of the PaiNN handle at creation: weight packing into the kernels' chunk streams, and the edge templates
 // (row / slot words of the message kernels) with their per-call selection and per-molecule masked copies.
+#include "message_stream.hpp"
 #include "pair_template.hpp"
 #include "ti_handle.hpp"
 
@@ -399,20 +400,36 @@ void pack_painn(ti_handle* h, const float* wts)
             const float S[6] = {matrix_pow2_scale(wts + h->w[l].W0, F, F, 0, F, wts + h->w[l].b0, F), matrix_pow2_scale(wts + h->w[l].W1, F, F, 0, F, wts + h->w[l].b1, F),
                                 matrix_pow2_scale(wts + h->phi[l].W0, 2 * F, F, 0, 2 * F, wts + h->phi[l].b0, F), matrix_pow2_scale(wts + h->phi[l].W1, F, F, 0, F, wts + h->phi[l].b1, F),
                                 matrix_pow2_scale(wts + h->phi[l].W2, F, 5 * F, 0, F, wts + h->phi[l].b2, 5 * F), matrix_pow2_scale(wts + h->w[l].W2, F, 5 * F, 0, F, wts + h->w[l].b2, 5 * F)};
-            auto layer1 = [&](size_t W, int ld, int n_rows, int col0, float sc) { for (int nbo = 0; nbo < NB; ++nbo) pack_chunk16_split1(pk, wts + W, ld, n_rows, 32 * nbo, col0, NBK, sc); };
-            o = begin_stream();
-            layer1(h->w[l].W0, F, F, 0, S[0]); layer1(h->w[l].W1, F, F, 0, S[1]);
-            layer1(h->phi[l].W0, 2 * F, F, F, S[2]);
-            layer1(h->phi[l].W1, F, F, 0, S[3]);
-            for (int nbo = 0; nbo < NB; ++nbo)
-                for (int c : {2, 3, 1, 0, 4}) {
-                    if (c == 3 && last) continue;
-                    if ((c == 0 || c == 4) && first) continue;
-                    pack_chunk16_split1(pk, wts + h->phi[l].W2, F, 5 * F, c * F + 32 * nbo, 0, NBK, S[4]);
-                    pack_chunk16_split1(pk, wts + h->w[l].W2, F, 5 * F, c * F + 32 * nbo, 0, NBK, S[5]);
+            // one chunk list (message_stream.hpp) for the message kernels' stream and, in layer 0, for the two streams of the phi table path
+            auto pack_message = [&](MsgPart part) {
+                for (const MsgChunk& ch : message_chunks(NB, first, last, part)) {
+                    const size_t W = ch.matrix == MSG_W_W0 ? h->w[l].W0 : ch.matrix == MSG_W_W1 ? h->w[l].W1 : ch.matrix == MSG_PHI_W0E ? h->phi[l].W0
+                                   : ch.matrix == MSG_PHI_W1 ? h->phi[l].W1 : ch.matrix == MSG_PHI_W2 ? h->phi[l].W2 : h->w[l].W2;
+                    const int ld = ch.matrix == MSG_PHI_W0E ? 2 * F : F, n_rows = ch.matrix >= MSG_PHI_W2 ? 5 * F : F, col0 = ch.matrix == MSG_PHI_W0E ? F : 0;
+                    pack_chunk16_split1(pk, wts + W, ld, n_rows, ch.row0, col0, NBK, S[ch.matrix]);
                 }
+            };
+            o = begin_stream();
+            pack_message(MSG_ALL);
             h->st_edge1.push_back(end_stream16(o));
             h->edge_scale.insert(h->edge_scale.end(), S, S + 6);
+            if (first && h->has_pair && pair_table_build_exists(NB, prec, false)) {
+                // layer 0's chunks once more, cut in two for the phi table path (painn_phi0_kernels.hip): the w chunks alone in the walk
+                // order of the pair kernel's table build, the phi chunks alone in the table kernel's; an odd count is padded to whole
+                // superchunks
+                o = begin_stream();
+                pack_message(MSG_W);
+                h->phi0_wpad = end_stream16(o).nch & 1;
+                pad_even(o);
+                h->st_phi0_w = end_stream16(o);
+                o = begin_stream();
+                pack_message(MSG_PHI);
+                pad_even(o);
+                h->st_phi0_tab = end_stream16(o);
+                h->phi0_ok = true;
+                // triage switch, read like TI_ZERO_ACC: TI_PHI0_TABLE=0 at creation pins the kernels of before
+                if (const char* z = std::getenv("TI_PHI0_TABLE")) if (z[0] == '0') h->phi0_ok = false;
+            }
         }
         o = begin_stream();                          // update kernel: 16-row chunk format, order of painn_update_kernel
         layer16(h->V[l], F, F, 0);                                                    // phase A (3 components per visit)

@@ -31,18 +31,22 @@
 namespace ti {
 
 // weight ring (mfma_chain.hpp PipeDMA): two superchunks of two chunks (64 KB at F = 128) in every build (pair_build_exists,
-// ti_internal.hpp); DESIGN.md 3.6 has the deeper ring that lost.
-__host__ __device__ constexpr int pair_superchunk() { return 2; }
+// ti_internal.hpp); DESIGN.md 3.6 has the deeper ring that lost.  The 8-wave table build at F = 128 (TABLE below) walks 20 or 16 w chunks
+// per row block and parks no dv sums: its LDS holds superchunks of four (128 KB), half the closing barriers of its 512 threads.
+__host__ __device__ constexpr int pair_superchunk(int NB = 0, int WAVES = 0, bool TABLE = false) { return TABLE && WAVES == 8 && NB == 4 ? 4 : 2; }
 // + the builds that fold the cross term (pair_folds_cross): per wave, the 12 dv sums of every lane parked across the cross-gate products.
 // At F = 128 that costs the 4-wave build its second workgroup per CU (87.5 KB); it runs below 2048 groups, where a launch has at most
 // two workgroups per CU to place.
-static size_t pair_lds_bytes(int NB, int WAVES, int PREC)
+static size_t pair_lds_bytes(int NB, int WAVES, int PREC, bool TABLE = false)
 {
-    return (size_t)2 * pair_superchunk() * edge_chunk4(NB, false) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4 +
-           (pair_folds_cross(PREC) ? (size_t)WAVES * 12 * 64 * 4 : 0);
+    return (size_t)2 * pair_superchunk(NB, WAVES, TABLE) * edge_chunk4(NB, false) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4 +
+           (pair_folds_cross(PREC) && !TABLE ? (size_t)WAVES * 12 * 64 * 4 : 0);
 }
 
-template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES>
+// TABLE (layer 0 only, the split path: pair_table_build_exists): the phi branch of layer 0 does not see the coordinates, so its three
+// live output slices come from the table painn_phi0_table_kernel wrote for this evaluation (painn_phi0_kernels.hip) -- per row the
+// value the products here would have given, bit for bit -- and the block walks the w chunks alone (EdgeParams: phi0_tab, cls, wpad).
+template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS p.rows
 #include "painn_pair_kernel_body.inc"
@@ -52,7 +56,7 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(c
 // from its molecule is invalid -- zeroed through the shared w factor, like a pair that does not exist.  Both directions share that
 // factor, so the molecule's edge set must be symmetric (painn_host.hip checks it when the mask is set).  The slot table and the first-touch
 // writes are the template's.  Instantiated in painn_pair_mask_nb*.hip.
-template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES>
+template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_mask_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS (p.rows + (size_t)gi * p.nblk * 16)
 #include "painn_pair_kernel_body.inc"
@@ -68,12 +72,14 @@ static hipError_t with_pair_builds(int waves, int prec, int pos, F&& f)
     dispatch_int<4, 8>(waves, [&](auto wc) { dispatch_int<0, 1>(prec, [&](auto pc) {
         constexpr int WAVES = decltype(wc)::value, PREC = decltype(pc)::value;
         if constexpr (pair_build_exists(NB, WAVES, PREC))
-            dispatch_int<POS_MIDDLE, POS_FIRST, POS_LAST, POS_ONLY>(pos, [&](auto oc) {
-                constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0;
-                any = true;
-                if (e != hipSuccess) return;
-                if constexpr (MASK) e = f(painn_pair_mask_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
-                else e = f(painn_pair_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
+            dispatch_int<POS_MIDDLE, POS_FIRST, POS_LAST, POS_ONLY, POS_FIRST_TABLE, POS_ONLY_TABLE>(pos, [&](auto oc) {
+                constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0, TABLE = (decltype(oc)::value & 4) != 0;
+                if constexpr (!TABLE || pair_table_build_exists(NB, PREC, MASK)) {
+                    any = true;
+                    if (e != hipSuccess) return;
+                    if constexpr (MASK) e = f(painn_pair_mask_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
+                    else e = f(painn_pair_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE));
+                }
             });
     }); });
     return any ? e : hipErrorInvalidValue;
@@ -86,11 +92,12 @@ hipError_t configure_pair_unit()
     return with_pair_builds<NB, MASK>(EVERY, EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
 }
 template <int NB, bool MASK>
-hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st)
+hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table)
 {
+    if (table && !first) return hipErrorInvalidValue;
     // 8-wave workgroups (one weight stream per CU) for the split path once every CU gets a workgroup
     const bool wide = prec == 1 && p.n_groups >= 2048;
-    return with_pair_builds<NB, MASK>(wide ? 8 : 4, prec, layer_pos(first, last), [&](auto kernel, int waves, size_t lds) {
+    return with_pair_builds<NB, MASK>(wide ? 8 : 4, prec, layer_pos(first, last) | (table ? POS_TABLE : 0), [&](auto kernel, int waves, size_t lds) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)((p.n_groups + waves - 1) / waves)), dim3(64 * waves), lds, st, p);      // one wave = one group of G molecules
         return hipGetLastError();
     });

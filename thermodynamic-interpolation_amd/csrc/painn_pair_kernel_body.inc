@@ -3,13 +3,14 @@
 // group's in the second, whose per-group row words mark pairs absent from their molecule invalid (w factor 0, like missing pairs).
 {
     static_assert(PREC == 0 || PREC == 1, "the fp16 storage mode keeps the directed message kernel");
+    static_assert(!TABLE || (FIRST && PREC == 1), "the phi table serves layer 0 of the split path");
     constexpr int F = 16 * NBK, NB = (F + 31) / 32, T = 64 * WAVES, CH4 = edge_chunk4(NB, false);
     using A16 = r16::Act<NBK>;
     constexpr bool ONE = edge_one_chain(PREC);
     using OP = std::conditional_t<ONE, r16::Opnd1<NBK>, typename r16::OpSel<NBK, PREC>::type>;
     extern __shared__ f32x4 lds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 15, q = lane >> 4;
-    constexpr int SC = pair_superchunk(), NBUF = 2;                                 // two superchunks in LDS (PipeDMA)
+    constexpr int SC = pair_superchunk(NB, WAVES, TABLE), NBUF = 2;                 // two superchunks in LDS (PipeDMA)
     float* scratch = reinterpret_cast<float*>(lds + NBUF * SC * CH4) + wave * 64;  // [16 pair rows][4] edge_dir of direction A
     float* vec = reinterpret_cast<float*>(lds + NBUF * SC * CH4) + WAVES * 64;     // [EV::COUNT][F]
     for (int i = threadIdx.x; i < EV::COUNT * F / 4; i += T)
@@ -38,6 +39,15 @@
     float* const ds_g = p.dsacc + gnode0 * F;
     float* const dv_g = p.dvacc + gnode0 * 3 * F;
     float* const c_g = p.cacc + gnode0 * 3 * F;
+    // TABLE: the classes of the group's molecules, four bits each, in one scalar word (molecules past the batch's end: the last one's),
+    // and from them the offset of a (molecule in group, atom, edge type) row of the phi table
+    unsigned clsw = 0;
+    if constexpr (TABLE)
+        for (int m = 0; m < p.G; ++m) clsw |= (unsigned)p.cls[gi * p.G + ((unsigned)m < mol_cap ? (unsigned)m : mol_cap)] << (4 * m);
+    auto tab_off = [&](int mol_local, int atom, int type) {
+        const unsigned cls = (clsw >> (4 * mol_local)) & 15u;
+        return ((cls * (unsigned)p.A + (unsigned)atom) * (unsigned)PHI0_TYPES + (unsigned)type) * (unsigned)(3 * F);
+    };
 
     // Diagnostic build only (-DTI_STAMPS; never the product): shader-clock stamps of ONE row block of a few workgroups, and one
     // (s_memtime, s_memrealtime) pair around the whole block loop of every wave for the in-kernel clock (MI355X guide, DVFS item 6).
@@ -123,8 +133,8 @@
             TI_STAMP();
         }
         // ---- phi([s[src] | e]) hidden layers of both directions in lock step; the s[src] half of the first Linear is P[src]
-        OP h2A, h2B;
-        {
+        OP h2A, h2B;                                     // (TABLE: never set, never read)
+        if constexpr (!TABLE) {
             OP inA, inB;
             A16 tA, tB;
             float scA, scB;
@@ -194,6 +204,20 @@
             return off < F ? ds_g + (lnode * (unsigned)F + (unsigned)off) : off < 4 * F ? dv_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - F)) : c_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - 4 * F));
         };
         const unsigned lIq = lnode_of(prow_molI(mi[0]), prow_atomI(mi[0]));      // source of direction A for all four rows of this lane
+        // TABLE: the table rows of this lane's values.  Flipped layout: the four pair rows 4q + r, source I[q] for direction A and J[r]
+        // for direction B (a loose block mixes molecules, hence classes, inside one lane: every row has its own offset); row layout
+        // (the de slice): pair row j.  Rows that do not exist name an atom that does, so what they load is finite (their w factor is 0).
+        unsigned tfA[4], tfB[4], trA = 0, trB = 0;
+        f32x4 tv[3][4];                                  // this 32-feature block's table values: [ds | scale_edge_dir | de][A0, A1, B0, B1]
+        if constexpr (TABLE) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                tfA[r] = tab_off(prow_molI(mi[r]), prow_atomI(mi[r]), prow_type(mi[r])) + (unsigned)j;
+                tfB[r] = tab_off(prow_molJ(mi[r]), prow_atomJ(mi[r]), prow_type(mi[r])) + (unsigned)j;
+            }
+            trA = tab_off(prow_molI(meta), prow_atomI(meta), prow_type(meta));
+            trB = tab_off(prow_molJ(meta), prow_atomJ(meta), prow_type(meta));
+        }
 
         // (phi_c + b) of both directions times the shared (w_c + b) for output slice c (0 gates, 1 scale_edge_dir, 2 ds, 3 de,
         // 4 cross gates), features fo .. fo+31 as two 16-feature blocks
@@ -205,8 +229,13 @@
             // layers' and the de slice's
             const float p0 = bp[0], p1 = bp[16], q0 = bw[0], q1 = bw[16];
             f32x4 a0 = {p0, p0, p0, p0}, a1 = {p1, p1, p1, p1}, b0 = a0, b1 = a1, w0 = {q0, q0, q0, q0}, w1 = {q1, q1, q1, q1};
-            r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
-            pipe.release();
+            if constexpr (TABLE) {
+                const int sl = c == 2 ? 0 : 1;
+                a0 = tv[sl][0]; a1 = tv[sl][1]; b0 = tv[sl][2]; b1 = tv[sl][3];
+            } else {
+                r16::gemm_x2_on_pipe<true>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
+                pipe.release();
+            }
             r16::gemm_on_pipe<true>(w0, w1, g2, pipe, lane);
             pipe.release();
             w0 *= wfac; w1 *= wfac;
@@ -256,6 +285,21 @@
         for (int nbo = 0; nbo < NB; ++nbo) {
             const int fo = 32 * nbo + j;
             TI_STAMP();
+            if constexpr (TABLE) {
+                // every table value of this feature block, fetched ahead of the block's first w product: the table stays in L2
+                const float* const tb = p.phi0_tab + 32 * nbo;
+#pragma unroll
+                for (int sl = 0; sl < 2; ++sl)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        tv[sl][0][r] = tb[tfA[r] + (unsigned)(sl * F)]; tv[sl][1][r] = tb[tfA[r] + (unsigned)(sl * F + 16)];
+                        tv[sl][2][r] = tb[tfB[r] + (unsigned)(sl * F)]; tv[sl][3][r] = tb[tfB[r] + (unsigned)(sl * F + 16)];
+                    }
+                if constexpr (!LAST) {
+                    tv[2][0] = r16::load_block(p.phi0_tab + trA + (unsigned)(2 * F), 2 * nbo, q); tv[2][1] = r16::load_block(p.phi0_tab + trA + (unsigned)(2 * F), 2 * nbo + 1, q);
+                    tv[2][2] = r16::load_block(p.phi0_tab + trB + (unsigned)(2 * F), 2 * nbo, q); tv[2][3] = r16::load_block(p.phi0_tab + trB + (unsigned)(2 * F), 2 * nbo + 1, q);
+                }
+            }
             {   // ds: invariant message, summed over incoming edges
                 f32x4 a0, a1, b0, b1;
                 out3(2, nbo, a0, a1, b0, b1);
@@ -284,8 +328,12 @@
                         oB0 = r16::load_block(eb, 2 * nbo, q); oB1 = r16::load_block(eb, 2 * nbo + 1, q);
                     }
                 }
-                r16::gemm_x2_on_pipe<false>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
-                pipe.release();
+                if constexpr (TABLE) {
+                    a0 = tv[2][0]; a1 = tv[2][1]; b0 = tv[2][2]; b1 = tv[2][3];
+                } else {
+                    r16::gemm_x2_on_pipe<false>(a0, a1, b0, b1, h2A, h2B, pipe, lane);
+                    pipe.release();
+                }
                 r16::gemm_on_pipe<false>(w0, w1, g2, pipe, lane);
                 pipe.release();
                 w0 *= wrow; w1 *= wrow;
@@ -412,6 +460,7 @@
                 }
             }
         }
+        if constexpr (TABLE) { if (p.wpad) pipe.release(); }      // an odd chunk count ends with a pad chunk: whole superchunks per row block
     }
     pipe.drain();
 #ifdef TI_STAMPS

@@ -3,5 +3,5 @@
 
 namespace ti {
 template hipError_t configure_pair_unit<1, true>();
-template hipError_t launch_pair_unit<1, true>(bool, bool, int, const EdgeParams&, hipStream_t);
+template hipError_t launch_pair_unit<1, true>(bool, bool, int, const EdgeParams&, hipStream_t, bool);
 }  // namespace ti

@@ -112,6 +112,15 @@ struct ti_handle {
     DevBuf<float> x, cond, s, P, v, dsacc, dvacc, cacc, e, enc, geo, b1, b2, xt, edge_vecs, edge_vecs1, upd_vecs;
     std::vector<float> edge_scale;               // [L][6] per-matrix powers of two of the one-accumulator message streams (TI_PREC_F16X2)
     int tap = -1; long long last_B = 0;
+    // layer-0 phi table (painn_phi0_kernels.hip).  phi0_ok: the handle can take the table path at all (pair layout, a
+    // table build of the pair kernel, TI_PHI0_TABLE != 0 at creation); st_phi0_w / st_phi0_tab: layer 0's message stream cut in two,
+    // the w chunks in the table build's walk order (phi0_wpad: it ends with a pad chunk) and the phi chunks in the table kernel's.
+    // Per API call (phi0_begin_call ... phi0_end_call): phi0_cls [B] class ids and phi0_state (representatives, overflow flag) from
+    // the class pass, phi0_ncls the class count read back from it (0: no class pass, or more classes than the cap), for phi0_B
+    // molecules whose cond rows start at phi0_cond.  phi0_last: what ti_painn_debug_phi0_path reports.
+    bool phi0_ok = false; Stream st_phi0_w{}, st_phi0_tab{}; int phi0_wpad = 0;
+    DevBuf<uint8_t> phi0_cls; DevBuf<int32_t> phi0_state; DevBuf<float> phi0_tab;
+    int phi0_ncls = 0, phi0_found = 0, phi0_last = -1; long long phi0_B = 0; const float* phi0_cond = nullptr;
     // forward-mode derivative (painn_jvp_kernels.hip): tangent twins over virtual molecules, sized on first use
     std::vector<Stream> st_jvp_update, st_jvp_phi; Stream st_jvp_readout{}; std::vector<int> jvp_phi_pad;
     DevBuf<float> jvp_ro_vecs, ts, tP, tv, tdsacc, tdvacc, tcacc, te, tout, wq, phist, nodest, divb, dl, dlscaled, div2;
@@ -264,6 +273,10 @@ void painn_drift_div_dev(ti_handle* h, const float* x_dev, float t, const float*
 void painn_make_probes(ti_handle* h, long long B, int k, uint64_t seed, long long traj0);
 void painn_drift_div_est_dev(ti_handle* h, const float* x_dev, float t, const float* cond_dev, long long B, int k, float* out_dev,
                              float* est_dev, const float* tv = nullptr);
+// the class pass of an API call over B molecules with cond rows cond_dev (device), where the call (eligible: one t for all molecules,
+// no tangent pass) and the handle's state allow the table path at all; phi0_end_call forgets its result (the next call's cond may differ)
+void phi0_begin_call(ti_handle* h, const float* cond_dev, long long B, bool eligible);
+void phi0_end_call(ti_handle* h);
 int set_graph_state(ti_handle* h, std::vector<uint32_t>& m, std::vector<int32_t>& natoms, std::vector<uint8_t>& ptype, long long B);
 void clear_graph_state(ti_handle* h);
 

@@ -81,7 +81,37 @@ struct EdgeParams {
     float wscale[6];                        // TI_PREC_F16X2: powers of two the host scaled w.W0, w.W1, phi.W0(e), phi.W1, phi.W2, w.W2 by (else 1)
     float* geo;                             // [n_groups*nblk*16][4] parked edge_dir
     unsigned long long* stamps;             // diagnostic builds (-DTI_STAMPS) only: s_memtime / s_memrealtime stamps, a buffer of their own; else NULL
+    // layer-0 phi table (the TABLE builds of the pair kernel, painn_pair_kernel.hpp; NULL / 0 for every other launch): `stream` then
+    // holds the w chunks alone (painn_pack.hip: st_phi0_w)
+    const float* phi0_tab;                  // [class][A][PHI0_TYPES][3][F]: ds | scale_edge_dir | de slices of the phi branch, bias included
+    const uint8_t* cls;                     // [B] class of every molecule (painn_phi0_kernels.hip)
+    int wpad;                               // the w-only stream ends with a pad chunk (odd count), swallowed once per row block
 };
+
+// ---- layer-0 phi table (painn_phi0_kernels.hip; include/ti_hip.h TI_PHI0_MAX_CLASSES)
+constexpr int PHI0_TYPES = 4;               // edge types a row word can name (2 bits): the table holds them all
+static_assert(TI_PHI0_MAX_CLASSES <= 16, "the pair kernel packs the class ids of a group's <= 8 molecules into one 32-bit word");
+// class state on the device: [0 .. CAP) the representative molecule of each class (-1: none yet), [CAP] 1 = more classes than the cap
+constexpr int PHI0_STATE_WORDS = TI_PHI0_MAX_CLASSES + 1;
+struct Phi0ClassParams {
+    const uint32_t* cond; int words;        // [B][words] the cond rows of a molecule as bit patterns (words = A * ncond, may be 0)
+    long long B;
+    int32_t* state;                         // [PHI0_STATE_WORDS], filled with -1 before the launch
+    uint8_t* cls;                           // [B]
+};
+struct Phi0TableParams {
+    const float4* stream; int nch;          // the phi chunks of layer 0 alone (painn_pack.hip: st_phi0_tab)
+    const float* vecs; const float* edge_emb; float wscale[6];      // as EdgeParams (one-accumulator format)
+    const float* P;                         // [B*A][F] of this evaluation's embed launch
+    const int32_t* state;                   // class representatives
+    int n_cls, A;
+    float* tab;
+};
+hipError_t launch_phi0_classes(const Phi0ClassParams& p, hipStream_t st);
+hipError_t launch_phi0_table(int NB, bool last, const Phi0TableParams& p, hipStream_t st);
+hipError_t configure_phi0_kernels(int NB);
+// the table builds of the pair kernel: the split path, unmasked, both wave counts
+__host__ __device__ constexpr bool pair_table_build_exists(int NB, int PREC, bool MASK) { return PREC == TI_PREC_F16X2 && !MASK && (NB == 1 || NB == 2 || NB == 4); }
 
 struct EmbedParams {
     const float4* stream; int nch;
@@ -119,7 +149,8 @@ hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams
 // width; painn_pack.hip packs their streams and vector blocks to match.
 __host__ __device__ constexpr bool edge_one_chain(int prec) { return prec == TI_PREC_F16X2; }
 // pair-major message kernel (painn_pair_kernel.hpp): same EdgeParams, rows / slotnode of the pair template, same weight stream
-hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false);
+// table: layer 0 on the phi table (p.phi0_tab / p.cls / p.wpad set, p.stream the w-only stream; first must hold, pair_table_build_exists)
+hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false, bool table = false);
 // builds of the pair kernel (painn_pair_kernel.hpp): F <= 128; f32 on 4 waves, split fp16 on 4 and on 8
 __host__ __device__ constexpr bool pair_build_exists(int NB, int WAVES, int PREC)
 {
@@ -139,7 +170,7 @@ hipError_t configure_painn_kernels(int NB);     // dynamic-LDS attributes
 // unit, reached from launch_edge / launch_pair / configure_painn_kernels (painn_kernels.hip).  No pair unit exists for NB = 8.
 template <int NB, bool MASK> hipError_t launch_edge_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
 template <int NB, bool MASK> hipError_t configure_edge_unit();
-template <int NB, bool MASK> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
+template <int NB, bool MASK> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table);
 template <int NB, bool MASK> hipError_t configure_pair_unit();
 
 // ---- forward-mode derivative of the drift (painn_jvp_kernels.hip; virtual-molecule layout described there).

@@ -510,6 +510,13 @@ class PainnEngine(_Engine):
         with `value` (first-touch accumulators, rows the pair-major kernel skips)."""
         _lib.check(_lib.lib().ti_painn_debug_poison(self.h, int(B), float(value)))
 
+    def debug_phi0_path(self):
+        """(path, classes) of the last drift evaluation: path 1 = layer 0 read the phi table, 0 = fallback, -1 = none yet;
+        classes = distinct cond classes the call's class pass found (cap + 1: more than the cap; 0: no class pass)."""
+        n = np.zeros(1, np.int32)
+        path = _lib.lib().ti_painn_debug_phi0_path(self.h, _lib.iptr(n))
+        return int(path), int(n[0])
+
     def debug_read(self, what: str, B: int):
         """what: 's' | 'v' | 'e', or 'ts' | 'tv' | 'te' for the tangents of the last jvp() call."""
         shape = {"s": (B, self.A, self.F), "v": (B, self.A, 3, self.F), "e": (B, self.E, self.F)}[what[-1]]
