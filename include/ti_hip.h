@@ -400,6 +400,30 @@ typedef struct {
    out [4] host double: point estimate, lower, upper, kept count of the point estimate. */
 int ti_obs_bootstrap(ti_handle* h, const float* logw, int64_t n, const ti_boot_desc* d,
                      const int32_t* idx, int64_t n_draw, double* out, double* out_boot, int mem);
+/* Gram matrices of random Fourier features over bootstrap resamples: the O(m p^2) part of reversible generator EDMD (the reference's
+ * gedmd/rff.py spectral_analysis_rff_generator, bootstrapped by adw/analysis/reweight_gedmd.py bootstrap_eigenvalues).  With
+ * theta_nk = sum_i x_ni omega_ik (fp64 on the fp32 values, i ascending), M_nk = exp(-i theta_nk) = c_nk - i s_nk and weights
+ * w_n = exp(logw_n - max logw) (logw == NULL: 1), the Gram matrix of a multiset S of sample indices is
+ *   G_kl = sum_S w conj(M_k) M_l:   Re G_kl = sum_S w (c_k c_l + s_k s_l),   Im G_kl = sum_S w (s_k c_l - c_k s_l),
+ * an fp64 contraction on the matrix cores.  The singular values of M^H (weighted by sqrt w) are sqrt(eig G) and its left singular
+ * vectors are the eigenvectors of G, so the whole spectral analysis is host algebra on the p x p result.
+ * values: row n holds the d components x_n0 .. x_n,d-1 at values[n * stride]; stride >= d (an adw state [B,d], or columns of a
+ * [B,K] CV array).  omega [d,p] fp64, host.  1 <= d <= 16, 1 <= p <= 128.  The call keeps a table of cos / sin of 2 n P doubles,
+ * P = p rounded up to 16: n P > 2^27 (2 GiB) is refused with TI_E_ALLOC.
+ * out [1 + n_boot, p, p, 2] fp64 (re, im): row 0 is the point estimate, S = all n samples in order; row 1 + r is resample r.  Draws are
+ * exactly those of ti_obs_bootstrap: idx == NULL: n_draw population indices (0: n) per resample from Philox with counter
+ * (j >> 1, R, TI_BOOT_DOMAIN) and key seed, R = first + r; idx != NULL: row r of idx [n_boot, n_draw].
+ * Every output is exactly Hermitian (the lower triangle is the stored conjugate of the upper, Im of the diagonal is 0).  A row's draws
+ * are cut into segments of 8192; every segment is summed in draw order and the segments are added in order, without atomics: a row
+ * is a function of (its draws, the data, omega, n_draw) only -- not of n_boot, of first beyond R, of generator versus idx, of mem, or
+ * of how many rows share a launch -- and a call repeats bit for bit.
+ * TI_E_ARG, before any device work: a NULL handle, values, omega, g or out; an unknown mem; n < 1 or n > 2^31 - 1; d or p out of range;
+ * stride < d; a non-finite omega; n_boot < 0 or > TI_BOOT_MAX_RESAMPLES; n_draw < 0; idx with n_draw < 1.  TI_E_ARG with out untouched:
+ * an idx entry outside 0..n-1 (found on the device; the entry is not followed).  TI_E_NAN: a non-finite logw, naming its index. */
+typedef struct { int32_t d, p; int64_t n_boot, first; uint64_t seed; } ti_gram_desc;
+/* values [n rows, stride] fp32, logw [n] fp32 or NULL, idx [n_boot, n_draw] int32 or NULL, out fp64: [host|device] by mem. */
+int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
+                    const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem);
 /* Observer: with one attached, every rollout entry point (ti_painn_rollout, _dlogp, _dlogp_est, ti_adw_rollout, _dlogp) also
  * evaluates the K CVs on the state at the grid points i with i % every == 0 and at the last one -- ti_rollout_rows(n_step, every)
  * rows, whatever save_every is -- and writes them to out_cv [rows, B, K] fp32 ([host|device] by mem; the caller sizes it for the

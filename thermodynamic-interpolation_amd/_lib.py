@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "ti_adw_rollout_fused",
     "ti_obs_bootstrap",
     "ti_painn_debug_phi0_path",
+    "ti_obs_rff_gram",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -45,6 +46,8 @@ BOOT_ESTIMATORS = {"ess": 0, "tfep": 1, "mean": 2}
 BOOT_FILTERS = {"none": 0, "once": 1, "resample": 2}
 BOOT_DOMAIN = 0x424F4F54
 BOOT_MAX_RESAMPLES = 1 << 20
+# ti_obs_rff_gram: the limits of d and p, and of the feature table (n * P entries, P = p rounded up to 16)
+GRAM_MAX_D, GRAM_MAX_P, GRAM_MAX_TABLE = 16, 128, 1 << 27
 
 
 class PainnDesc(C.Structure):
@@ -66,6 +69,10 @@ class RolloutDesc(C.Structure):
 class BootDesc(C.Structure):
     _fields_ = [("estimator", C.c_int32), ("filter", C.c_int32), ("k", C.c_double), ("level", C.c_double), ("n_boot", C.c_int64),
                 ("first", C.c_int64), ("seed", C.c_uint64)]
+
+
+class GramDesc(C.Structure):
+    _fields_ = [("d", C.c_int32), ("p", C.c_int32), ("n_boot", C.c_int64), ("first", C.c_int64), ("seed", C.c_uint64)]
 
 
 class TiError(RuntimeError):
@@ -154,6 +161,7 @@ def lib():
                               C.c_int]
     L.ti_obs_set_observer.argtypes = [vp, ip, C.c_int32, fp, ip, C.c_int32, vp, C.c_int]
     L.ti_obs_bootstrap.argtypes = [vp, vp, C.c_int64, C.POINTER(BootDesc), vp, C.c_int64, C.POINTER(C.c_double), vp, C.c_int]
+    L.ti_obs_rff_gram.argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(C.c_double), vp, C.POINTER(GramDesc), vp, C.c_int64, vp, C.c_int]
     _lib = L
     return L
 

@@ -23,9 +23,11 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "pai
            "adw_fused_kernels.hip",
            # bootstrap intervals of the weight estimators (ti_obs_bootstrap): a unit of its own, every older code object stays as it was
            "obs_boot_kernels.hip",
+           # RFF Gram matrices of resamples on the fp64 matrix cores (ti_obs_rff_gram): a unit of its own again
+           "obs_gram_kernels.hip",
            # layer-0 phi table (class pass, table kernel); the pair kernel's table builds live in painn_pair_nb*.hip
            "painn_phi0_kernels.hip"]
-HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "ode_device.hpp", "adw_device.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",
+HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",
            "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
 # -packed-fp32-ops off: v_pk_{fma,mul,add}_f32 do NOT run next to another wave's matrix instructions on gfx950 (a wave of them and a
 # wave of 16x16x32 fp16 MFMAs on one SIMD take the SUM of their times; scalar v_fma_f32, conversions and transcendentals overlap:

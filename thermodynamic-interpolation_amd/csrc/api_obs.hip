@@ -216,6 +216,89 @@ int ti_obs_bootstrap(ti_handle* h, const float* logw, int64_t n, const ti_boot_d
     });
 }
 
+int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
+                    const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem)
+{
+    // the checks that need no device come first, so they can be exercised with a NULL handle; that one is refused last
+    if (!values || !omega || !g || !out) return fail(TI_E_ARG, "NULL buffer");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (n < 1 || n > (int64_t)INT32_MAX) return fail(TI_E_ARG, "n must be in 1..2^31-1");
+    if (g->d < 1 || g->d > 16) return fail(TI_E_ARG, "d must be in 1..16");
+    if (g->p < 1 || g->p > 128) return fail(TI_E_ARG, "p must be in 1..128");
+    if (stride < g->d) return fail(TI_E_ARG, "stride < d");
+    for (int i = 0; i < g->d * g->p; ++i)
+        if (!std::isfinite(omega[i])) return fail(TI_E_ARG, "non-finite omega at entry " + std::to_string(i));
+    if (g->n_boot < 0 || g->n_boot > TI_BOOT_MAX_RESAMPLES) return fail(TI_E_ARG, "n_boot must be in 0..2^20");
+    if (n_draw < 0 || n_draw > (int64_t)INT32_MAX) return fail(TI_E_ARG, "n_draw must be in 0..2^31-1");
+    if (idx && n_draw < 1) return fail(TI_E_ARG, "idx needs n_draw >= 1");
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    const int d = g->d, p = g->p, P = gram_pad(p), T = P / 16, NT = T * (T + 1) / 2;
+    if (n * P > ((int64_t)1 << 27)) return fail(TI_E_ALLOC, "the feature table would exceed 2 GiB (n * P > 2^27, P = p rounded up to 16)");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const long long nb = g->n_boot, nd = n_draw > 0 ? n_draw : n;
+        Staged sg(h, mem);
+        const float* xd = values;
+        long long sd = stride;
+        if (mem == TI_MEM_HOST) {                      // the d columns only
+            std::vector<float> rows((size_t)n * d);
+            for (int64_t i = 0; i < n; ++i) std::copy(values + i * stride, values + i * stride + d, rows.begin() + i * d);
+            grow(h->gram_x, rows.size());
+            HIP_CHECK(hipMemcpy(h->gram_x.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+            xd = h->gram_x.p; sd = d;
+        }
+        const float* ld = logw ? sg.in(logw, h->obs_logw, (size_t)n) : nullptr;
+        const int32_t* id = idx && nb > 0 ? sg.in(idx, h->boot_idx, (size_t)nb * (size_t)n_draw) : nullptr;
+        grow(h->obs_red, 4 + 259);
+        grow(h->obs_part, (size_t)OBS_MAX_BLOCKS * 259);
+        if (ld) {                                      // the shift and the refusal of ti_obs_weights
+            double norm[2];
+            HIP_CHECK(launch_obs_logw_max(h->obs_red.p, h->obs_part.p, ld, n, st));
+            HIP_CHECK(hipMemcpyAsync(norm, h->obs_red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            if (norm[1] < (double)n) return fail(TI_E_NAN, "non-finite logw at index " + std::to_string((long long)norm[1]));
+            grow(h->gram_w, (size_t)n);
+        }
+        h->gram_omega.upload(std::vector<double>(omega, omega + (size_t)d * p));
+        grow(h->gram_z, (size_t)n * 2 * P);
+        HIP_CHECK(launch_obs_gram_features(h->gram_z.p, h->gram_w.p, xd, sd, n, d, p, h->gram_omega.p, ld, h->obs_red.p, st));
+        // rows per launch: the partial tiles of a launch stay within 256 MiB
+        const size_t pp = (size_t)p * p * 2, part_doubles = (size_t)NT * 512, max_parts = std::max<size_t>(((size_t)256 << 20) / (part_doubles * 8), 1);
+        grow(h->gram_out, (size_t)(1 + nb) * pp);
+        grow(h->boot_flag, 1);
+        HIP_CHECK(hipMemsetAsync(h->boot_flag.p, 0, sizeof(int), st));
+        GramParams gp{};
+        gp.z = h->gram_z.p; gp.w = ld ? h->gram_w.p : nullptr; gp.T = T;
+        gp.draw.n_pop = n; gp.draw.seed = g->seed; gp.draw.flag = h->boot_flag.p;
+        auto run = [&](long long rows, long long draws, double* dst) {       // gp.draw.{source, idx, first} set by the caller, rows within the cap
+            gp.draw.n_draw = draws;
+            gp.nseg = (draws + GRAM_SEG - 1) / GRAM_SEG;
+            grow(h->gram_part, (size_t)rows * (size_t)gp.nseg * part_doubles);
+            gp.part = h->gram_part.p;
+            HIP_CHECK(launch_obs_gram(gp, rows, st));
+            HIP_CHECK(launch_obs_gram_reduce(dst, gp.part, rows, gp.nseg, p, st));
+        };
+        gp.draw.source = BOOT_SRC_IDENTITY;
+        run(1, n, h->gram_out.p);
+        const long long nseg = (nd + GRAM_SEG - 1) / GRAM_SEG, chunk = std::max<long long>((long long)max_parts / nseg, 1);
+        for (long long r0 = 0; r0 < nb; r0 += chunk) {
+            gp.draw.source = id ? BOOT_SRC_INDEX : BOOT_SRC_PHILOX;
+            gp.draw.idx = id ? id + r0 * nd : nullptr;
+            gp.draw.first = (long long)((uint64_t)g->first + (uint64_t)r0);
+            run(std::min(chunk, nb - r0), nd, h->gram_out.p + (size_t)(1 + r0) * pp);
+        }
+        int flag = 0;
+        HIP_CHECK(hipMemcpyAsync(&flag, h->boot_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (flag) return fail(TI_E_ARG, "idx entry outside 0.." + std::to_string(n - 1));
+        HIP_CHECK(hipMemcpyAsync(out, h->gram_out.p, (size_t)(1 + nb) * pp * sizeof(double),
+                                 mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return TI_OK;
+    });
+}
+
 int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* logw, int64_t B, int32_t n_bins, double lo, double hi,
                 double* out_hist, double* out_tails, int mem)
 {

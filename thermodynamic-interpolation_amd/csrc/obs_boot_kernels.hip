@@ -9,7 +9,7 @@
 // partial sums go through the fixed tree of ode_device.hpp.  Thread t owns the draw pairs t, t + 256, ... whatever the source of the
 // draws, so the estimate of an index row is a function of the row, the data and the mode only.  No global atomics, no
 // floating-point atomics.  Arithmetic is fp64 on the fp32 inputs.
-#include "adw_device.hpp"
+#include "boot_draw.hpp"
 #include "ode_device.hpp"
 
 namespace ti {
@@ -25,30 +25,6 @@ __device__ __forceinline__ uint32_t boot_key(float v)
     return (b & 0x80000000u) ? ~b : b | 0x80000000u;
 }
 __device__ __forceinline__ float boot_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? k & 0x7fffffffu : ~k); }
-
-// population indices of the draws 2p and 2p + 1 of the group's resample (i1 is not used when 2p + 1 == n_draw).  ok = false: an
-// explicit index outside the population; it is replaced by 0, so nothing is read out of bounds, and the call is refused afterwards.
-__device__ __forceinline__ void boot_draw_pair(const BootParams& p, long long row, uint64_t R, long long pr, long long& i0, long long& i1, bool& ok)
-{
-    const long long j = 2 * pr;
-    if (p.source == BOOT_SRC_IDENTITY) {
-        i0 = j; i1 = j + 1;
-    } else if (p.source == BOOT_SRC_INDEX) {
-        const int32_t* __restrict__ ix = p.idx + row * p.n_draw + j;
-        i0 = ix[0];
-        i1 = j + 1 < p.n_draw ? ix[1] : 0;
-        if (i0 < 0 || i0 >= p.n_pop) { i0 = 0; ok = false; }
-        if (i1 < 0 || i1 >= p.n_pop) { i1 = 0; ok = false; }
-    } else {
-        uint32_t c[4] = {(uint32_t)pr, (uint32_t)R, (uint32_t)(R >> 32), TI_BOOT_DOMAIN};
-        // the key words in vector registers: left uniform, the ten round keys are hoisted into 20 scalar registers and the kernel spills
-        uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
-        asm volatile("" : "+v"(k0), "+v"(k1));
-        philox4x32_10(c, k0, k1);
-        i0 = (long long)__umul64hi(((uint64_t)c[1] << 32) | c[0], (uint64_t)p.n_pop);
-        i1 = (long long)__umul64hi(((uint64_t)c[3] << 32) | c[2], (uint64_t)p.n_pop);
-    }
-}
 
 __device__ __forceinline__ double boot_value(float v, bool mean, double m) { return mean ? (double)v : exp((double)v - m); }
 

@@ -154,6 +154,9 @@ struct ti_handle {
     // bootstrap (ti_obs_bootstrap): the once-filtered population, staged index rows, the estimates ahead of their validation, the
     // point row's (estimate, kept count, lower and upper filter bound, size of the compacted population), the bad-index flag
     DevBuf<float> boot_pop; DevBuf<int32_t> boot_idx; DevBuf<double> boot_est, boot_pt; DevBuf<int> boot_flag;
+    // RFF Gram matrices (ti_obs_rff_gram): the packed values of a host call, Omega, the feature table, the weights, the partial
+    // tiles of one launch, the result ahead of its validation
+    DevBuf<float> gram_x; DevBuf<double> gram_omega, gram_z, gram_w, gram_part, gram_out;
 
     ~ti_handle()
     {

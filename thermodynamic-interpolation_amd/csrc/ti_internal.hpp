@@ -410,4 +410,22 @@ hipError_t launch_obs_boot(const BootParams& p, long long n_rows, hipStream_t st
 // out[0 .. *n_out) = the v[i] with bounds[0] < value(v[i]) < bounds[1] in index order (value: v itself if mean, else exp(v - m))
 hipError_t launch_obs_boot_compact(float* out, double* n_out, const float* v, long long n, int mean, double m, const double* bounds, hipStream_t st);
 
+// ---- RFF Gram matrices of resamples (obs_gram_kernels.hip; include/ti_hip.h ti_obs_rff_gram)
+constexpr long long GRAM_SEG = 8192;        // draws per (row, segment) workgroup; fixed, so a row's sums do not depend on the launch
+inline int gram_pad(int p) { return (p + 15) / 16 * 16; }
+struct GramParams {
+    BootParams draw;                        // the row's draws: source, idx, n_pop, n_draw, seed, first, flag (the rest is not read)
+    const double* z;                        // [n_pop][2 P] feature table (cos | sin), P = gram_pad(p)
+    const double* w;                        // [n_pop] weights, NULL: 1
+    int T;                                  // P / 16
+    long long nseg;                         // ceil(n_draw / GRAM_SEG)
+    double* part;                           // [rows][nseg][T (T + 1) / 2][2][256] partial tiles
+};
+// z [n][2 P], w [n] = exp(logw - *mx) (logw == NULL: w is not written) of x [n] rows of d floats `stride` apart and omega [d][p]
+hipError_t launch_obs_gram_features(double* z, double* w, const float* x, long long stride, long long n, int d, int p, const double* omega,
+                                    const float* logw, const double* mx, hipStream_t st);
+// one 256-thread group per (row, segment); then out [n_rows][p][p][2] = the partials added in segment order, mirrored
+hipError_t launch_obs_gram(const GramParams& g, long long n_rows, hipStream_t st);
+hipError_t launch_obs_gram_reduce(double* out, const double* part, long long n_rows, long long nseg, int p, hipStream_t st);
+
 }  // namespace ti

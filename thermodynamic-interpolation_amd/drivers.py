@@ -17,7 +17,10 @@ batches then get consecutive trajectory ids, so no two molecules of a run share 
 variables at the grid points i % every == 0 and at the last one, computed on the GPU during the rollout; ``hist`` [K, bins] and
 ``edges`` [K, bins + 1], the histogram of every CV at the end state, weighted by exp(-dlogp) when ``return_dlogp`` is set; ``ess``.
 An integer ``"bootstrap": n`` in that dict adds ``ess_ci`` [2], the 95 % interval of the ESS from n bootstrap resamples drawn on the
-GPU (observables.bootstrap, seed 0), and ``ess_boot`` [n], their estimates.  Without the key exactly the reference's files are written.
+GPU (observables.bootstrap, seed 0), and ``ess_boot`` [n], their estimates.  sample_adw only: ``"gedmd": {"p": 50, "sigma": 0.6,
+"nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "potential": [a, b]}`` (every entry optional) adds ``gedmd_eigenvalues`` [nev],
+``gedmd_ci`` [2, nev] and ``gedmd_rank``: the generator spectrum of the reweighted end state with its bootstrap interval
+(observables.gedmd_generator; U = a (x^2 - 1)^2 + b x).  Without the key exactly the reference's files are written.
 """
 from __future__ import annotations
 
@@ -60,13 +63,53 @@ def _observe_kw(config):
     o = dict(o)
     o.pop("bins", None)
     o.pop("bootstrap", None)
+    o.pop("gedmd", None)
     if o.get("ref") is not None:
         o["ref"] = np.asarray(o["ref"], np.float32)
     return dict(observe=o)
 
 
-def _write_observables(config, path, cvs, dlogps):
-    """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp)"""
+GEDMD_KEYS = {"p": 50, "sigma": 0.6, "nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "potential": (4.0, 0.5)}
+
+
+def _gedmd_settings(o):
+    """observables["gedmd"] completed with the defaults above and checked; None without the key."""
+    g = dict(o).get("gedmd")
+    if g is None:
+        return None
+    if not isinstance(g, dict) or set(g) - set(GEDMD_KEYS):
+        raise ValueError(f"observables['gedmd'] must be a dict with keys out of {sorted(GEDMD_KEYS)}, got {g!r}")
+    g = {**GEDMD_KEYS, **g}
+    for k in ("p", "nev", "n_boot", "seed"):
+        if isinstance(g[k], bool) or int(g[k]) != g[k] or int(g[k]) < (0 if k == "seed" else 1):
+            raise ValueError(f"observables['gedmd'][{k!r}] must be an integer >= {0 if k == 'seed' else 1}, got {g[k]!r}")
+        g[k] = int(g[k])
+    if not (np.isfinite(g["sigma"]) and g["sigma"] > 0 and np.isfinite(g["tol"]) and g["tol"] >= 0):
+        raise ValueError("observables['gedmd']: sigma must be finite and > 0, tol finite and >= 0")
+    pot = tuple(float(v) for v in np.asarray(g["potential"], np.float64).reshape(-1))
+    if len(pot) != 2 or not np.isfinite(pot).all():
+        raise ValueError(f"observables['gedmd']['potential'] must be [a, b] of U = a (x^2 - 1)^2 + b x, got {g['potential']!r}")
+    g["potential"] = pot
+    if g["nev"] > g["p"]:
+        raise ValueError("observables['gedmd']: nev must not exceed p")
+    return g
+
+
+def _gedmd_arrays(g, x0, x1, dlogp, beta0, beta1):
+    """gedmd_eigenvalues [nev], gedmd_ci [2, nev], gedmd_rank of the end state x1 [B] reweighted to beta1: logw = beta0 U(x0) -
+    beta1 U(x1) - dlogp in fp64 (calculate_weights of the reference's reweight_gedmd.py, which hard-codes beta0 = 1), a = 2 / beta1."""
+    a, b = g["potential"]
+    U = lambda x: a * (x * x - 1.0) ** 2 + b * x
+    x0, x1 = np.asarray(x0, np.float64).reshape(-1), np.asarray(x1, np.float64).reshape(-1)
+    logw = (float(beta0) * U(x0) - float(beta1) * U(x1) - np.asarray(dlogp, np.float64).reshape(-1)).astype(np.float32)
+    omega = _obs.sample_rff_gaussian(1, g["p"], g["sigma"], g["seed"])
+    res = _obs.gedmd_generator(x1.astype(np.float32), omega, g["nev"], 2.0 / float(beta1), tol=g["tol"], logw=logw, n_boot=g["n_boot"], seed=g["seed"])
+    return dict(gedmd_eigenvalues=res.eigenvalues, gedmd_ci=res.ci, gedmd_rank=np.int64(res.rank))
+
+
+def _write_observables(config, path, cvs, dlogps, gedmd=None):
+    """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp); gedmd: (x0, x1, beta0, beta1)
+    of an adw run whose observables carry the gedmd key"""
     cv = np.concatenate([C.to_numpy(c) for c in cvs], axis=1).astype(np.float32)
     dl = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in dlogps]) if dlogps else None
     hist, edges, ess = _obs.end_state_summary(np.ascontiguousarray(cv[-1]), dl, bins=int(dict(config.observables).get("bins", 32)))
@@ -78,6 +121,11 @@ def _write_observables(config, path, cvs, dlogps):
         B = cv.shape[1]
         res = _obs.bootstrap(-dl if dl is not None else np.zeros(B, np.float32), "ess", n_boot=int(n_boot))
         extra = dict(ess_ci=np.asarray(res.ci, np.float64), ess_boot=res.estimates)
+    g = _gedmd_settings(config.observables)
+    if g is not None:
+        if gedmd is None or dl is None:
+            raise ValueError("observables['gedmd'] is for sample_adw with return_dlogp: the weights need the end-state dlogp")
+        extra.update(_gedmd_arrays(g, gedmd[0], gedmd[1], dl, gedmd[2], gedmd[3]))
     np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
 
 
@@ -174,5 +222,6 @@ def sample_adw(config, b, x0s_batches):
         np.save(os.path.join(out_dir, f"dlogps_epoch_{config.sampling_epoch}.npy"), by_step(dlogps))
     if cvs:
         _write_observables(config, os.path.join(out_dir, f"observables_epoch_{config.sampling_epoch}.npz"), cvs,
-                           [d[-1] for d in dlogps] if config.return_dlogp else [])
+                           [d[-1] for d in dlogps] if config.return_dlogp else [],
+                           gedmd=(initial, samples[-1], config.beta0s[0], config.beta1s[0]))
     return initial, samples

@@ -220,6 +220,65 @@ class _Engine:
         _lib.check(_lib.lib().ti_obs_bootstrap(self.h, lp, n, C.byref(desc), ip, n_draw, out, bp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return out[0], out[1], out[2], int(out[3]), out_boot
 
+    def rff_gram(self, values, omega, logw=None, n_boot=0, first=0, seed=0, indices=None, n_draw=0):
+        """ti_obs_rff_gram: G [1 + n_boot, p, p] complex128 of values [n] or [n, d] float32 (numpy, or a CUDA tensor -- a view with
+        unit stride along d, such as cv[:, :2], is read in place) and omega [d, p] float64 (host).  Row 0 is the point estimate, row
+        1 + r resample first + r of the stream `seed`, or row r of indices [n_boot, n_draw] int32.  Lives where values lives."""
+        n_boot, n_draw = int(n_boot), int(n_draw)
+        om = np.ascontiguousarray(omega, np.float64)
+        if om.ndim != 2:
+            raise ValueError(f"omega must be [d, p], got {om.shape}")
+        d, p = om.shape
+        if len(values.shape) not in (1, 2) or (len(values.shape) == 2 and int(values.shape[1]) != d) or (len(values.shape) == 1 and d != 1):
+            raise ValueError(f"values must be [n, d = {d}] (or [n] with d = 1), got {tuple(values.shape)}")
+        n = int(values.shape[0])
+        dev_in = hasattr(values, "data_ptr") and values.is_cuda
+        if dev_in:
+            if str(values.dtype) != "torch.float32":
+                raise TypeError(f"values must be float32, got {values.dtype}")
+            if len(values.shape) == 2 and d > 1 and values.stride(1) != 1:
+                raise ValueError("values must have unit stride along d")
+            if (values.device.index or 0) != self.device:
+                raise ValueError(f"values live on {values.device} but this engine was created on device {self.device}")
+            stride = max(int(values.stride(0)), d) if n > 1 else d
+            keep_v, vp = values, C.c_void_p(values.data_ptr())
+        else:
+            host = values.detach().cpu().numpy() if hasattr(values, "data_ptr") else values
+            keep_v = np.ascontiguousarray(np.asarray(host, np.float32).reshape(n, d))
+            stride, vp = d, C.c_void_p(keep_v.ctypes.data)
+        ip, keep_i = None, None
+        if indices is not None:
+            if tuple(indices.shape[:1]) != (n_boot,) or len(indices.shape) != 2:
+                raise ValueError(f"indices must be [n_boot = {n_boot}, n_draw], got {tuple(indices.shape)}")
+            n_draw = int(indices.shape[1])
+            if dev_in:
+                if not (hasattr(indices, "data_ptr") and indices.is_cuda and str(indices.dtype) == "torch.int32" and indices.is_contiguous()):
+                    raise TypeError("indices must be a contiguous CUDA int32 tensor when values is a CUDA tensor")
+                keep_i, ip = indices, C.c_void_p(indices.data_ptr())
+            else:
+                if hasattr(indices, "data_ptr"):
+                    indices = indices.detach().cpu().numpy()
+                keep_i = np.ascontiguousarray(indices, np.int32)
+                ip = C.c_void_p(keep_i.ctypes.data)
+        (lp,), ldev, keep = self._ptrs((logw, (n,), False, "logw"))
+        if logw is not None and ldev != dev_in:
+            raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
+        if dev_in:
+            import torch
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)
+            out = torch.empty((1 + n_boot, p, p, 2), dtype=torch.float64, device=values.device)
+            op = C.c_void_p(out.data_ptr())
+        else:
+            out = np.empty((1 + n_boot, p, p, 2), np.float64)
+            op = C.c_void_p(out.ctypes.data)
+        desc = _lib.GramDesc(d, p, n_boot, int(first), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        _lib.check(_lib.lib().ti_obs_rff_gram(self.h, vp, stride, n, om.ctypes.data_as(C.POINTER(C.c_double)), lp, C.byref(desc), ip, n_draw, op,
+                                              _lib.MEM_DEVICE if dev_in else _lib.MEM_HOST))
+        if dev_in:
+            import torch
+            return torch.view_as_complex(out)
+        return out.view(np.complex128)[..., 0]
+
     def weighted_histogram(self, values, logw, bins, range):
         """(hist [bins] float64, tails [3] float64 = weight below range[0], at or above range[1], of non-finite values).  values: a
         1-D float32 array or a column view such as cv[:, k] (read in place through its stride); logw None: uniform weights."""

@@ -14,8 +14,12 @@ Bootstrap intervals (ti_obs_bootstrap): ``bootstrap`` and the wrappers ``ess_ti`
 gen_* functions of the reference's mdqm9/analysis/results_00031.py -- a point estimate with a percentile interval over resamples
 drawn and reduced on the GPU, after the reference's IQR outlier filter.
 
-No arithmetic happens in this module apart from turning a histogram into a free-energy profile, forming phi from its terms, and
-the difference of two bootstrap runs in ``free_energy_bg``.
+Generator EDMD on random Fourier features (ti_obs_rff_gram): ``rff_gram`` contracts the feature Gram matrices of bootstrap resamples
+in fp64 on the GPU; ``gedmd_spectrum`` / ``gedmd_generator`` turn them into the implied-timescale eigenvalues of the reference's
+adw/analysis/reweight_gedmd.py with their bootstrap interval (the p x p algebra is host numpy).
+
+Beyond that p x p algebra the only arithmetic in this module is turning a histogram into a free-energy profile, forming phi from
+its terms, and the difference of two bootstrap runs in ``free_energy_bg``.
 """
 from __future__ import annotations
 
@@ -144,6 +148,99 @@ def bootstrap(logw, estimator, k=None, filter=None, n_boot=1000, seed=0, level=0
     point, lo, hi, kept, est = eng.bootstrap(logw, _lib.BOOT_ESTIMATORS[estimator], _lib.BOOT_FILTERS[filter], 1.0 if k is None else float(k),
                                              float(level), int(n_boot), int(first), int(seed), indices)
     return BootstrapResult(point, (lo, hi), est, kept)
+
+
+def sample_rff_gaussian(d, p, sigma, seed):
+    """Omega [d, p] float64 of a Gaussian kernel of bandwidth sigma: RandomState(seed).randn(d, p) / sigma -- the reference's draw
+    (adw/analysis/reweight_gedmd.py), with a seed."""
+    if int(d) < 1 or int(p) < 1 or not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"need d >= 1, p >= 1 and a finite sigma > 0, got {(d, p, sigma)}")
+    return np.random.RandomState(seed).randn(int(d), int(p)) / float(sigma)
+
+
+def _check_gram_args(values, omega, n_boot):
+    omega = np.asarray(omega, np.float64)
+    if omega.ndim != 2 or not 1 <= omega.shape[0] <= _lib.GRAM_MAX_D or not 1 <= omega.shape[1] <= _lib.GRAM_MAX_P:
+        raise ValueError(f"omega must be [d, p] with 1 <= d <= {_lib.GRAM_MAX_D} and 1 <= p <= {_lib.GRAM_MAX_P}, got {omega.shape}")
+    if not np.isfinite(omega).all():
+        raise ValueError("omega must be finite")
+    if isinstance(n_boot, bool) or int(n_boot) != n_boot or not 0 <= int(n_boot) <= _lib.BOOT_MAX_RESAMPLES:
+        raise ValueError(f"n_boot must be an integer in 0..{_lib.BOOT_MAX_RESAMPLES}, got {n_boot!r}")
+    if len(values.shape) not in (1, 2) or int(values.shape[0]) < 1:
+        raise ValueError("values must be [n] or [n, d] and non-empty")
+    P = -(-omega.shape[1] // 16) * 16
+    if int(values.shape[0]) * P > _lib.GRAM_MAX_TABLE:
+        raise ValueError(f"n * P = {int(values.shape[0]) * P} exceeds the feature table's cap of 2^27 entries (P = p rounded up to 16)")
+    return omega
+
+
+def rff_gram(values, omega, logw=None, n_boot=0, seed=0, first=0, indices=None, engine=None):
+    """G [1 + n_boot, p, p] complex128 (where values lives): the weighted Gram matrices M^H diag(w) M of the random Fourier features
+    M = exp(-i values @ omega) -- values [n] or [n, d] float32, omega [d, p] float64 on the host, w = exp(logw - max logw) (None: 1)
+    -- over all n samples (row 0) and over n_boot bootstrap resamples, drawn as in ``bootstrap`` (or given by indices
+    [n_boot, n_draw] int32), contracted in fp64 on the GPU (ti_obs_rff_gram)."""
+    omega = _check_gram_args(values, omega, n_boot)
+    eng = engine or _service_engine(_device_of(values, logw))
+    return eng.rff_gram(values, omega, logw, int(n_boot), int(first), int(seed), indices)
+
+
+def gedmd_spectrum(gram, omega, a, nev, tol=0.0):
+    """Reversible generator EDMD from Gram matrices (host numpy, batched over the leading axes of gram [.., p, p]): what the
+    reference's gedmd/rff.py spectral_analysis_rff_generator(reversible=True) computes through an SVD of M^H, here from G = M^H M.
+    eigh(G) in descending order, s = sqrt(max(lambda, 0)), r = max(#{s / s_0 >= tol}, nev), L = U[:, :r] / s[:r],
+    R = L^H (-a / 2 (omega^T omega) o G) L, eigh of its Hermitian part; returns (d [.., nev] the last nev eigenvalues in ascending
+    order, W [.., p, nev] = L Wi, r [..]).  a is the constant diffusion (a float, 2 / beta in the reference's use).  Tensor-valued
+    diffusion, the non-reversible branch and finite-lag Koopman estimation are out of scope."""
+    G = np.asarray(gram.detach().cpu().numpy() if hasattr(gram, "data_ptr") else gram, np.complex128)
+    omega = np.asarray(omega, np.float64)
+    p = omega.shape[1]
+    if G.shape[-2:] != (p, p):
+        raise ValueError(f"gram must be [.., {p}, {p}], got {G.shape}")
+    if isinstance(nev, bool) or int(nev) != nev or not 1 <= int(nev) <= p:
+        raise ValueError(f"nev must be an integer in 1..p = {p}, got {nev!r}")
+    if not np.isfinite(a) or not np.isfinite(tol) or tol < 0:
+        raise ValueError(f"a must be finite and tol finite and >= 0, got {(a, tol)}")
+    nev, lead = int(nev), G.shape[:-2]
+    G = G.reshape(-1, p, p)
+    lam, U = np.linalg.eigh(G)
+    lam, U = lam[:, ::-1], U[:, :, ::-1]
+    s = np.sqrt(np.maximum(lam, 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rank = np.maximum((s / s[:, :1] >= tol).sum(axis=1), nev)
+    ML = (-0.5 * float(a)) * (omega.T @ omega) * G
+    d, W = np.zeros((G.shape[0], nev)), np.zeros((G.shape[0], p, nev), np.complex128)
+    for r in np.unique(rank):                          # matrices of one rank share the batched calls
+        sel = np.flatnonzero(rank == r)
+        with np.errstate(divide="ignore"):
+            L = U[sel][:, :, :r] / s[sel][:, None, :r]
+        Rm = np.conj(np.swapaxes(L, 1, 2)) @ ML[sel] @ L
+        di, Wi = np.linalg.eigh(0.5 * (Rm + np.conj(np.swapaxes(Rm, 1, 2))))
+        d[sel] = di[:, -nev:]
+        W[sel] = L @ Wi[:, :, -nev:]
+    return d.reshape(*lead, nev), W.reshape(*lead, p, nev), rank.reshape(lead)
+
+
+GedmdResult = collections.namedtuple("GedmdResult", "eigenvalues ci estimates eigenvectors rank")
+GedmdResult.__doc__ = """eigenvalues [nev]: the generator eigenvalues of the whole sample, ascending (the last is ~0; the reference reports
+their negatives); ci [2, nev]: percentiles of the resample estimates; estimates [n_boot, nev]; eigenvectors [p, nev] and rank of the
+point estimate."""
+
+
+def gedmd_generator(values, omega, nev, a, tol=0.0, logw=None, n_boot=1000, level=0.95, seed=0, first=0, indices=None, engine=None):
+    """The bootstrapped generator spectrum of the reference's adw/analysis/reweight_gedmd.py (bootstrap_eigenvalues over gedmd): the
+    Gram matrices on the GPU (``rff_gram``), the p x p algebra on the host (``gedmd_spectrum``), the interval by numpy's linear
+    percentile rule as in ``bootstrap``.  The reference reweights by weighted resampling and then bootstraps uniformly; here logw
+    enters the Gram matrices directly -- the expectation of that step -- and the bootstrap draws uniformly.  The reference's exact
+    procedure stays reachable through indices."""
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must be in (0, 1), got {level!r}")
+    G = rff_gram(values, omega, logw=logw, n_boot=n_boot, seed=seed, first=first, indices=indices, engine=engine)
+    d, W, r = gedmd_spectrum(G, omega, a, nev, tol)
+    est = d[1:]
+    ci = np.full((2, d.shape[1]), np.nan)
+    if est.shape[0] and not np.isnan(est).any():
+        ci = np.percentile(est, [50 * (1 - float(level)), 50 * (1 + float(level))], axis=0)
+    return GedmdResult(d[0], ci, est, W[0], int(r[0]))
 
 
 def _neg_phi(*terms):

@@ -1,0 +1,85 @@
+#!/usr/bin/env python
+"""Measure the bootstrapped generator spectrum (ti_obs_rff_gram + the host algebra) against the reference's loop in numpy on the same
+machine's CPU.
+
+Shapes: n = 25 000 and n = 400 000 bimodal samples (d = 1, fp32, a device tensor), p = 50 Gaussian features (sigma = 0.6), nev = 4,
+tol = 1e-4, a = 2 / 1.25, 1000 resamples.
+GPU: medians of --reps wall-clock calls after one warm-up of
+  gram       observables.rff_gram alone (the 1001 Gram matrices stay on the device; the call is synchronous)
+  generator  observables.gedmd_generator: the same call, the copy of the Gram matrices to the host, and the host eigh stage
+  host       observables.gedmd_spectrum alone on the copied Gram matrices -- its share of `generator` is printed
+CPU: tests/gedmd_numpy.py svd_route -- the reference's algorithm, an SVD of the [p, m] feature matrix per resample, drawn with
+RandomState.choice -- timed over --cpu-resamples resamples (median of --cpu-reps) and scaled to 1000: the loop is linear in the resamples.
+The Gram kernel's arithmetic per call: 4 MFMAs of 2 * 16 * 16 * 4 flop per upper tile and 4 draws; its gathered bytes: 16 P per draw.
+Prints one JSON line per size.
+
+    python tools/gedmd_bench.py [--reps 7] [--cpu-resamples 5]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def median_ms(fn, reps):
+    fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t)), float(np.min(t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--resamples", type=int, default=1000)
+    ap.add_argument("--cpu-resamples", type=int, default=5)
+    ap.add_argument("--cpu-reps", type=int, default=3)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[25000, 400000])
+    ap.add_argument("--p", type=int, default=50)
+    args = ap.parse_args()
+    import torch
+    import gedmd_numpy as gn
+    ti = importlib.import_module("thermodynamic-interpolation_amd")
+    obs = ti.observables
+    eng = obs._service_engine(0)
+    p, nev, a, tol, nb = args.p, 4, 2 / 1.25, 1e-4, args.resamples
+    omega = obs.sample_rff_gaussian(1, p, 0.6, 0)
+    T = -(-p // 16)
+    for n in args.sizes:
+        rs = np.random.RandomState(n)
+        x = (np.where(rs.random_sample(n) < 0.5, -1.0, 1.0) + 0.35 * rs.standard_normal(n)).astype(np.float32)
+        dev = torch.from_numpy(x).cuda()
+        gram_ms, gram_min = median_ms(lambda: obs.rff_gram(dev, omega, n_boot=nb, seed=1, engine=eng), args.reps)
+        gen_ms, gen_min = median_ms(lambda: obs.gedmd_generator(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng), args.reps)
+        G = obs.rff_gram(dev, omega, n_boot=nb, seed=1, engine=eng).cpu().numpy()
+        host_ms, _ = median_ms(lambda: obs.gedmd_spectrum(G, omega, a, nev, tol), args.reps)
+        res = obs.gedmd_generator(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng)
+        c = []
+        for _ in range(args.cpu_reps):
+            rr = np.random.RandomState(1)
+            t0 = time.perf_counter()
+            for _ in range(args.cpu_resamples):
+                ref = gn.svd_route(x[rr.choice(n, n)], omega, a, nev, tol)
+            c.append((time.perf_counter() - t0) * 1e3 * nb / args.cpu_resamples)
+        flop = (n * (1 + nb) / 4) * (T * (T + 1) / 2) * 4 * 2 * 16 * 16 * 4
+        rec = dict(n=n, p=p, resamples=nb, gram_ms=gram_ms, gram_ms_min=gram_min, generator_ms=gen_ms, generator_ms_min=gen_min, host_eigh_ms=host_ms,
+                   host_share=host_ms / gen_ms, cpu_numpy_ms=float(np.median(c)), cpu_resamples_timed=args.cpu_resamples,
+                   speedup_generator=float(np.median(c) / gen_ms), gram_call_tflops=flop / (gram_ms * 1e-3) / 1e12,
+                   gram_call_gather_GBps=n * (1 + nb) * 16 * 16 * T / (gram_ms * 1e-3) / 1e9, eigenvalues=res.eigenvalues.tolist(),
+                   ci=res.ci.tolist(), rank=res.rank, cpu_last_resample=ref[0].tolist(), device=torch.cuda.get_device_name(0))
+        print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
