@@ -424,6 +424,45 @@ typedef struct { int32_t d, p; int64_t n_boot, first; uint64_t seed; } ti_gram_d
 /* values [n rows, stride] fp32, logw [n] fp32 or NULL, idx [n_boot, n_draw] int32 or NULL, out fp64: [host|device] by mem. */
 int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
                     const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem);
+/* Batched complex-Hermitian fp64 eigensolver on the device: numpy.linalg.eigh(A, UPLO="U") of n_mat matrices of order n <= 64, one
+ * 256-thread workgroup per matrix, A and the accumulated eigenvector matrix V both in LDS (2 m m 16 bytes plus small tables, m = n
+ * rounded up to even: 128 KiB at n = 64; n <= 50 leaves room for two workgroups per CU).
+ * Only the upper triangle of a matrix is read; the real part is taken on the diagonal and the lower triangle is taken to be the
+ * conjugate.  w is ascending; exactly equal eigenvalues are ordered by the diagonal position they converged at.  Column k of v is a
+ * unit eigenvector for w[k]; its phase is unspecified.
+ * Method: parallel cyclic two-sided Jacobi.  A sweep is the m - 1 rounds of the round-robin tournament: slot 0 holds index 0, slot
+ * k >= 1 holds index 1 + (k - 1 + r) mod (m - 1) in round r, slot i is paired with slot m - 1 - i; a pair that contains the pad index
+ * (odd n) is skipped.  The rotation of a pair (p, q), p < q, with b = A[p,q] is skipped when |b| <= 2^-53 scale, scale the largest
+ * |A[k,k]| of the input; otherwise tau = (A[q,q] - A[p,p]) / (2 |b|), t = sign(tau) / (|tau| + sqrt(1 + tau^2)) with sign(0) = +1,
+ * c = 1 / sqrt(1 + t^2), s = t c, e = conj(b) / |b| and U = [[c, s], [-s e, c e]] on columns (p, q).  Every rotation of a round is
+ * computed from the matrix as it stands at the start of that round; then A <- A U and V <- V U on all the round's column pairs, then
+ * A <- U^H A on its row pairs; the annihilated entries are set to exactly 0 and the imaginary parts of the touched diagonal entries
+ * to 0.  fp64 hypot, sqrt and division throughout.  The iteration stops after the first sweep in which no pair was rotated; sweeps
+ * [n_mat] (may be NULL) counts that sweep too: 1 for a diagonal matrix.
+ * No atomics.  The result is a function of the matrix alone -- not of its position in the batch, of n_mat, of mem, or of how a batch
+ * is cut into launches -- and a call repeats bit for bit.  Results go to a buffer of the handle first and reach w, v and sweeps only
+ * when the whole call succeeded.
+ * TI_E_ARG, before any device work: a NULL handle, a or w; an unknown mem; n outside 1..TI_EIGH_MAX_N; n_mat outside
+ * 1..TI_BOOT_MAX_RESAMPLES + 1.  TI_E_NAN, nothing written: a non-finite entry in the triangle that is read (found on the device;
+ * the first such matrix is named).  TI_E_UNSUPPORTED, nothing written: a matrix still rotating after 64 sweeps (named). */
+#define TI_EIGH_MAX_N 64
+/* a [n_mat, n, n, 2] fp64 (re, im), w [n_mat, n] fp64, v [n_mat, n, n, 2] fp64 or NULL, sweeps [n_mat] int32 or NULL: [host|device] by mem */
+int ti_obs_eigh(ti_handle* h, const double* a, int64_t n_mat, int32_t n, double* w, double* v, int32_t* sweeps, int mem);
+/* The p x p algebra of reversible generator EDMD on the device, per Gram matrix G (as ti_obs_rff_gram writes them; the upper triangle
+ * is read, as in ti_obs_eigh): the eigenpairs of G in descending order, s = sqrt(max(lambda, 0)), r = max(#{k : s_k / s_0 >= tol}, nev)
+ * (a division, then the comparison), L = U[:, :r] / s[:r], ML_kl = -a/2 K_kl G_kl with K = omega^T omega (formed once per call on the
+ * host in fp64, i ascending), R = L^H ML L, the eigenpairs of its Hermitian part (real diagonal) from the same Jacobi kernel at order
+ * r; ev = the last nev eigenvalues in ascending order, vec = L Wi[:, -nev:], rank = r.  Limits: 1 <= p <= 64 (a larger p returns
+ * TI_E_UNSUPPORTED: the host route, observables.gedmd_spectrum(solver="host"), has no such limit), 1 <= d <= 16, 1 <= nev <= p, a
+ * finite, tol finite and >= 0, omega finite, n_mat as for ti_obs_eigh; all checked before the handle is looked at.  A Gram matrix
+ * whose largest eigenvalue is not positive, or whose kept s contains 0 (tol = 0 on a rank-deficient G), gives NaN in that matrix's ev
+ * and vec; it is not an error.  TI_E_NAN (a non-finite Gram entry) and TI_E_UNSUPPORTED (64 sweeps) as in ti_obs_eigh, nothing written.
+ * Deterministic in the same sense as ti_obs_eigh. */
+typedef struct { int32_t d, p, nev, reserved; double a, tol; } ti_gedmd_desc;   /* 32 bytes, reserved = 0 */
+/* gram [n_mat, p, p, 2] fp64, ev [n_mat, nev] fp64, vec [n_mat, p, nev, 2] fp64 or NULL, rank [n_mat] int32 or NULL: [host|device] by mem;
+   omega [d, p] fp64, host */
+int ti_obs_gedmd_spectrum(ti_handle* h, const double* gram, int64_t n_mat, const double* omega, const ti_gedmd_desc* g,
+                          double* ev, double* vec, int32_t* rank, int mem);
 /* Observer: with one attached, every rollout entry point (ti_painn_rollout, _dlogp, _dlogp_est, ti_adw_rollout, _dlogp) also
  * evaluates the K CVs on the state at the grid points i with i % every == 0 and at the last one -- ti_rollout_rows(n_step, every)
  * rows, whatever save_every is -- and writes them to out_cv [rows, B, K] fp32 ([host|device] by mem; the caller sizes it for the

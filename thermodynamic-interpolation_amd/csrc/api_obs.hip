@@ -299,6 +299,118 @@ int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n
     });
 }
 
+// the refusals ti_obs_eigh and ti_obs_gedmd_spectrum find in the status words of a solve over n_mat matrices (host copy)
+static int eig_status_refusal(const std::vector<int32_t>& st, const char* what)
+{
+    for (size_t i = 0; i < st.size(); ++i) {
+        if (st[i] < 0) return fail(TI_E_NAN, std::string("non-finite entry in ") + what + " " + std::to_string(i));
+        if (st[i] > EIG_MAX_SWEEPS)
+            return fail(TI_E_UNSUPPORTED, std::string(what) + " " + std::to_string(i) + " is still rotating after " + std::to_string(EIG_MAX_SWEEPS) + " sweeps");
+    }
+    return TI_OK;
+}
+
+static int eig_n_mat_refusal(int64_t n_mat)
+{
+    if (n_mat < 1 || n_mat > (int64_t)TI_BOOT_MAX_RESAMPLES + 1) return fail(TI_E_ARG, "n_mat must be in 1..2^20+1");
+    return TI_OK;
+}
+
+int ti_obs_eigh(ti_handle* h, const double* a, int64_t n_mat, int32_t n, double* w, double* v, int32_t* sweeps, int mem)
+{
+    // the checks that need no device come first, so they can be exercised with a NULL handle; that one is refused last
+    if (!a) return fail(TI_E_ARG, "a is NULL");
+    if (!w) return fail(TI_E_ARG, "w is NULL");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (n < 1 || n > TI_EIGH_MAX_N) return fail(TI_E_ARG, "n must be in 1..64");
+    if (int rc = eig_n_mat_refusal(n_mat)) return rc;
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const size_t nn = (size_t)n * n * 2, N = (size_t)n_mat;
+        Staged sg(h, mem);
+        const double* ad = sg.in(a, h->eig_a, N * nn);
+        grow(h->eig_w, N * n);
+        if (v) grow(h->eig_v, N * nn);
+        grow(h->eig_st, N);
+        HIP_CHECK(launch_obs_eigh(ad, (long long)nn, n, n, nullptr, h->eig_w.p, v ? h->eig_v.p : nullptr, n, h->eig_st.p, n_mat, st));
+        std::vector<int32_t> status(N);
+        HIP_CHECK(hipMemcpyAsync(status.data(), h->eig_st.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (int rc = eig_status_refusal(status, "matrix")) return rc;
+        const hipMemcpyKind kind = mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        HIP_CHECK(hipMemcpyAsync(w, h->eig_w.p, N * n * sizeof(double), kind, st));
+        if (v) HIP_CHECK(hipMemcpyAsync(v, h->eig_v.p, N * nn * sizeof(double), kind, st));
+        if (sweeps && mem == TI_MEM_DEVICE) HIP_CHECK(hipMemcpyAsync(sweeps, h->eig_st.p, N * sizeof(int32_t), kind, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (sweeps && mem == TI_MEM_HOST) std::copy(status.begin(), status.end(), sweeps);
+        return TI_OK;
+    });
+}
+
+int ti_obs_gedmd_spectrum(ti_handle* h, const double* gram, int64_t n_mat, const double* omega, const ti_gedmd_desc* g, double* ev, double* vec,
+                          int32_t* rank, int mem)
+{
+    // the checks that need no device come first, so they can be exercised with a NULL handle; that one is refused last
+    if (!gram) return fail(TI_E_ARG, "gram is NULL");
+    if (!omega) return fail(TI_E_ARG, "omega is NULL");
+    if (!g) return fail(TI_E_ARG, "g is NULL");
+    if (!ev) return fail(TI_E_ARG, "ev is NULL");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (g->p < 1) return fail(TI_E_ARG, "p must be >= 1");
+    if (g->p > TI_EIGH_MAX_N) return fail(TI_E_UNSUPPORTED, "p must be <= 64 on the device: use the host route (observables.gedmd_spectrum, solver=\"host\")");
+    if (g->d < 1 || g->d > 16) return fail(TI_E_ARG, "d must be in 1..16");
+    if (g->nev < 1 || g->nev > g->p) return fail(TI_E_ARG, "nev must be in 1..p");
+    if (g->reserved != 0) return fail(TI_E_ARG, "reserved must be 0");
+    if (!std::isfinite(g->a)) return fail(TI_E_ARG, "a must be finite");
+    if (!(std::isfinite(g->tol) && g->tol >= 0.0)) return fail(TI_E_ARG, "tol must be finite and >= 0");
+    for (int i = 0; i < g->d * g->p; ++i)
+        if (!std::isfinite(omega[i])) return fail(TI_E_ARG, "non-finite omega at entry " + std::to_string(i));
+    if (int rc = eig_n_mat_refusal(n_mat)) return rc;
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const int d = g->d, p = g->p, nev = g->nev;
+        const size_t pp = (size_t)p * p * 2, N = (size_t)n_mat, pv = (size_t)p * nev * 2;
+        std::vector<double> K((size_t)p * p, 0.0);                  // K = omega^T omega, i ascending
+        for (int i = 0; i < d; ++i)
+            for (int k = 0; k < p; ++k)
+                for (int l = 0; l < p; ++l) K[(size_t)k * p + l] += omega[i * p + k] * omega[i * p + l];
+        h->eig_k.upload(K);
+        Staged sg(h, mem);
+        const double* gd = sg.in(gram, h->eig_a, N * pp);
+        // matrices per launch: the eigenvectors and reduced matrices of a launch stay within 3 x 32 MiB whatever n_mat is
+        const size_t chunk = std::min<size_t>(N, 512);
+        grow(h->eig_w, chunk * p); grow(h->eig_v, chunk * pp); grow(h->eig_w2, chunk * p); grow(h->eig_v2, chunk * pp); grow(h->eig_r, chunk * pp);
+        grow(h->eig_st, N); grow(h->eig_st2, N); grow(h->eig_rank, N); grow(h->eig_ev, N * nev);
+        if (vec) grow(h->eig_vec, N * pv);
+        for (size_t m0 = 0; m0 < N; m0 += chunk) {
+            const long long nm = (long long)std::min(chunk, N - m0);
+            int32_t *st1 = h->eig_st.p + m0, *st2 = h->eig_st2.p + m0, *rk = h->eig_rank.p + m0;
+            HIP_CHECK(launch_obs_eigh(gd + m0 * pp, (long long)pp, p, p, nullptr, h->eig_w.p, h->eig_v.p, p, st1, nm, st));
+            HIP_CHECK(launch_obs_gedmd_reduce(gd + m0 * pp, h->eig_w.p, h->eig_v.p, st1, h->eig_k.p, -0.5 * g->a, g->tol, nev, p, h->eig_r.p, rk, nm, st));
+            HIP_CHECK(launch_obs_eigh(h->eig_r.p, (long long)pp, p, p, rk, h->eig_w2.p, h->eig_v2.p, p, st2, nm, st));
+            HIP_CHECK(launch_obs_gedmd_back(h->eig_w.p, h->eig_v.p, h->eig_w2.p, h->eig_v2.p, st2, rk, nev, p, h->eig_ev.p + m0 * nev,
+                                            vec ? h->eig_vec.p + m0 * pv : nullptr, nm, st));
+        }
+        std::vector<int32_t> s1(N), s2(N);
+        HIP_CHECK(hipMemcpyAsync(s1.data(), h->eig_st.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(s2.data(), h->eig_st2.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (int rc = eig_status_refusal(s1, "Gram matrix")) return rc;
+        for (auto& s : s2) s = s < 0 ? 1 : s;                      // a refused reduced matrix is the degenerate input: NaN, not an error
+        if (int rc = eig_status_refusal(s2, "the reduced matrix of Gram matrix")) return rc;
+        const hipMemcpyKind kind = mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        HIP_CHECK(hipMemcpyAsync(ev, h->eig_ev.p, N * nev * sizeof(double), kind, st));
+        if (vec) HIP_CHECK(hipMemcpyAsync(vec, h->eig_vec.p, N * pv * sizeof(double), kind, st));
+        if (rank) HIP_CHECK(hipMemcpyAsync(rank, h->eig_rank.p, N * sizeof(int32_t), kind, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return TI_OK;
+    });
+}
+
 int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* logw, int64_t B, int32_t n_bins, double lo, double hi,
                 double* out_hist, double* out_tails, int mem)
 {

@@ -157,6 +157,9 @@ struct ti_handle {
     // RFF Gram matrices (ti_obs_rff_gram): the packed values of a host call, Omega, the feature table, the weights, the partial
     // tiles of one launch, the result ahead of its validation
     DevBuf<float> gram_x; DevBuf<double> gram_omega, gram_z, gram_w, gram_part, gram_out;
+    // eigensolver and gEDMD algebra (ti_obs_eigh, ti_obs_gedmd_spectrum): the staged input of a host call; eigenvalues, eigenvectors and
+    // status words of the first and second solve; K, the reduced matrices of one launch, the ranks; the results ahead of their validation
+    DevBuf<double> eig_a, eig_w, eig_v, eig_w2, eig_v2, eig_k, eig_r, eig_ev, eig_vec; DevBuf<int32_t> eig_st, eig_st2, eig_rank;
 
     ~ti_handle()
     {

@@ -428,4 +428,18 @@ hipError_t launch_obs_gram_features(double* z, double* w, const float* x, long l
 hipError_t launch_obs_gram(const GramParams& g, long long n_rows, hipStream_t st);
 hipError_t launch_obs_gram_reduce(double* out, const double* part, long long n_rows, long long nseg, int p, hipStream_t st);
 
+// ---- batched Hermitian eigensolver and the gEDMD algebra around it (obs_eig_kernels.hip; include/ti_hip.h ti_obs_eigh, ti_obs_gedmd_spectrum)
+constexpr int EIG_MAX_N = TI_EIGH_MAX_N, EIG_MAX_SWEEPS = 64;
+// one 256-thread group per matrix: a [n_mat] matrices mat_stride doubles apart, row stride ld complex entries, of order n -- or of
+// order nvec [i] <= n (0: the matrix is skipped, status 0); w [n_mat][ldo] ascending, v [n_mat][ldo][ldo][2] or NULL;
+// status [i]: the sweep count, -1 non-finite input, EIG_MAX_SWEEPS + 1 still rotating after the cap
+hipError_t launch_obs_eigh(const double* a, long long mat_stride, int ld, int n, const int* nvec, double* w, double* v, int ldo, int* status,
+                           long long n_mat, hipStream_t st);
+// rmat [n_mat][p][p][2] (upper triangle of order rank [i]) = the Hermitian part of L^H ((coef K) o G) L from the eigenpairs (w1, u1) of G
+hipError_t launch_obs_gedmd_reduce(const double* gram, const double* w1, const double* u1, const int* status1, const double* kmat, double coef,
+                                   double tol, int nev, int p, double* rmat, int* rank, long long n_mat, hipStream_t st);
+// ev [n_mat][nev], vec [n_mat][p][nev][2] or NULL from the eigenpairs (w2, v2) of rmat
+hipError_t launch_obs_gedmd_back(const double* w1, const double* u1, const double* w2, const double* v2, const int* status2, const int* rank,
+                                 int nev, int p, double* ev, double* vec, long long n_mat, hipStream_t st);
+
 }  // namespace ti

@@ -18,7 +18,8 @@ variables at the grid points i % every == 0 and at the last one, computed on the
 ``edges`` [K, bins + 1], the histogram of every CV at the end state, weighted by exp(-dlogp) when ``return_dlogp`` is set; ``ess``.
 An integer ``"bootstrap": n`` in that dict adds ``ess_ci`` [2], the 95 % interval of the ESS from n bootstrap resamples drawn on the
 GPU (observables.bootstrap, seed 0), and ``ess_boot`` [n], their estimates.  sample_adw only: ``"gedmd": {"p": 50, "sigma": 0.6,
-"nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "potential": [a, b]}`` (every entry optional) adds ``gedmd_eigenvalues`` [nev],
+"nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "potential": [a, b], "solver": "host"}`` (every entry optional; solver "device"
+runs the p x p algebra on the GPU too, p <= 64) adds ``gedmd_eigenvalues`` [nev],
 ``gedmd_ci`` [2, nev] and ``gedmd_rank``: the generator spectrum of the reweighted end state with its bootstrap interval
 (observables.gedmd_generator; U = a (x^2 - 1)^2 + b x).  Without the key exactly the reference's files are written.
 """
@@ -70,6 +71,16 @@ def _observe_kw(config):
 
 
 GEDMD_KEYS = {"p": 50, "sigma": 0.6, "nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "potential": (4.0, 0.5)}
+GEDMD_SOLVER = "host"          # default of the key observables.gedmd.solver: "host" (numpy) or "device" (ti_obs_gedmd_spectrum, p <= 64)
+
+
+def _gedmd_solver(o):
+    """observables["gedmd"]["solver"] checked; the default without the key"""
+    g = dict(o).get("gedmd")
+    solver = g.get("solver", GEDMD_SOLVER) if isinstance(g, dict) else GEDMD_SOLVER
+    if solver not in _obs.SOLVERS:
+        raise ValueError(f"observables['gedmd']['solver'] must be one of {_obs.SOLVERS}, got {solver!r}")
+    return solver
 
 
 def _gedmd_settings(o):
@@ -77,9 +88,10 @@ def _gedmd_settings(o):
     g = dict(o).get("gedmd")
     if g is None:
         return None
-    if not isinstance(g, dict) or set(g) - set(GEDMD_KEYS):
-        raise ValueError(f"observables['gedmd'] must be a dict with keys out of {sorted(GEDMD_KEYS)}, got {g!r}")
-    g = {**GEDMD_KEYS, **g}
+    if not isinstance(g, dict) or set(g) - set(GEDMD_KEYS) - {"solver"}:
+        raise ValueError(f"observables['gedmd'] must be a dict with keys out of {sorted(GEDMD_KEYS) + ['solver']}, got {g!r}")
+    solver = _gedmd_solver(o)
+    g = {**GEDMD_KEYS, **{k: v for k, v in g.items() if k != "solver"}}
     for k in ("p", "nev", "n_boot", "seed"):
         if isinstance(g[k], bool) or int(g[k]) != g[k] or int(g[k]) < (0 if k == "seed" else 1):
             raise ValueError(f"observables['gedmd'][{k!r}] must be an integer >= {0 if k == 'seed' else 1}, got {g[k]!r}")
@@ -92,10 +104,12 @@ def _gedmd_settings(o):
     g["potential"] = pot
     if g["nev"] > g["p"]:
         raise ValueError("observables['gedmd']: nev must not exceed p")
+    if solver == "device" and g["p"] > _obs._lib.EIGH_MAX_N:
+        raise ValueError(f"observables['gedmd']: solver 'device' takes p <= {_obs._lib.EIGH_MAX_N}")
     return g
 
 
-def _gedmd_arrays(g, x0, x1, dlogp, beta0, beta1):
+def _gedmd_arrays(g, x0, x1, dlogp, beta0, beta1, solver=GEDMD_SOLVER):
     """gedmd_eigenvalues [nev], gedmd_ci [2, nev], gedmd_rank of the end state x1 [B] reweighted to beta1: logw = beta0 U(x0) -
     beta1 U(x1) - dlogp in fp64 (calculate_weights of the reference's reweight_gedmd.py, which hard-codes beta0 = 1), a = 2 / beta1."""
     a, b = g["potential"]
@@ -103,7 +117,8 @@ def _gedmd_arrays(g, x0, x1, dlogp, beta0, beta1):
     x0, x1 = np.asarray(x0, np.float64).reshape(-1), np.asarray(x1, np.float64).reshape(-1)
     logw = (float(beta0) * U(x0) - float(beta1) * U(x1) - np.asarray(dlogp, np.float64).reshape(-1)).astype(np.float32)
     omega = _obs.sample_rff_gaussian(1, g["p"], g["sigma"], g["seed"])
-    res = _obs.gedmd_generator(x1.astype(np.float32), omega, g["nev"], 2.0 / float(beta1), tol=g["tol"], logw=logw, n_boot=g["n_boot"], seed=g["seed"])
+    res = _obs.gedmd_generator(x1.astype(np.float32), omega, g["nev"], 2.0 / float(beta1), tol=g["tol"], logw=logw, n_boot=g["n_boot"], seed=g["seed"],
+                               solver=solver)
     return dict(gedmd_eigenvalues=res.eigenvalues, gedmd_ci=res.ci, gedmd_rank=np.int64(res.rank))
 
 
@@ -125,7 +140,7 @@ def _write_observables(config, path, cvs, dlogps, gedmd=None):
     if g is not None:
         if gedmd is None or dl is None:
             raise ValueError("observables['gedmd'] is for sample_adw with return_dlogp: the weights need the end-state dlogp")
-        extra.update(_gedmd_arrays(g, gedmd[0], gedmd[1], dl, gedmd[2], gedmd[3]))
+        extra.update(_gedmd_arrays(g, gedmd[0], gedmd[1], dl, gedmd[2], gedmd[3], solver=_gedmd_solver(config.observables)))
     np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
 
 

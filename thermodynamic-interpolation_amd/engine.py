@@ -279,6 +279,81 @@ class _Engine:
             return torch.view_as_complex(out)
         return out.view(np.complex128)[..., 0]
 
+    def _complex_stack(self, a, what):
+        """(pointer, keepalive, is_device, shape) of a stack of complex128 matrices [.., n, n]: numpy (any dtype that converts), or a
+        contiguous CUDA complex128 tensor on this engine's GPU, read in place as (re, im) pairs."""
+        if hasattr(a, "data_ptr") and a.is_cuda:
+            if str(a.dtype) != "torch.complex128" or not a.is_contiguous():
+                raise TypeError(f"{what} must be a contiguous complex128 tensor, got {a.dtype}")
+            if (a.device.index or 0) != self.device:
+                raise ValueError(f"{what} lives on {a.device} but this engine was created on device {self.device}")
+            import torch
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)
+            return C.c_void_p(a.data_ptr()), a, True, tuple(a.shape)
+        host = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "data_ptr") else a, np.complex128)
+        return C.c_void_p(host.ctypes.data), host, False, host.shape
+
+    def _eig_out(self, like, shape, dtype):
+        """An output of ti_obs_eigh / ti_obs_gedmd_spectrum where the input lives: (array or tensor, pointer)"""
+        if like is not None:
+            import torch
+            out = torch.empty(shape, dtype=getattr(torch, dtype), device=like.device)
+            return out, C.c_void_p(out.data_ptr())
+        out = np.empty(shape, getattr(np, dtype))
+        return out, C.c_void_p(out.ctypes.data)
+
+    def eigh(self, a, vectors=True):
+        """ti_obs_eigh: (w [.., n] float64 ascending, v [.., n, n] complex128 or None, sweeps [..] int32) of a stack a [.., n, n] of
+        Hermitian matrices, n <= 64, as numpy.linalg.eigh(a, UPLO="U"): parallel cyclic Jacobi, one workgroup per matrix.  Lives
+        where a lives (numpy, or a CUDA complex128 tensor)."""
+        ap, keep, dev, shape = self._complex_stack(a, "a")
+        if len(shape) < 2 or shape[-1] != shape[-2] or not 1 <= shape[-1] <= _lib.EIGH_MAX_N:
+            raise ValueError(f"a must be [.., n, n] with 1 <= n <= {_lib.EIGH_MAX_N}, got {tuple(shape)}")
+        n, lead = int(shape[-1]), tuple(shape[:-2])
+        n_mat = int(np.prod(lead, dtype=np.int64))
+        if not 1 <= n_mat <= _lib.EIGH_MAX_MATRICES:
+            raise ValueError(f"a must hold 1..{_lib.EIGH_MAX_MATRICES} matrices, got {n_mat}")
+        like = keep if dev else None
+        w, wp = self._eig_out(like, (*lead, n), "float64")
+        v, vp = self._eig_out(like, (*lead, n, n, 2), "float64") if vectors else (None, None)
+        sw, sp = self._eig_out(like, lead, "int32")
+        _lib.check(_lib.lib().ti_obs_eigh(self.h, ap, n_mat, n, wp, vp, sp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        if v is not None:
+            if dev:
+                import torch
+                v = torch.view_as_complex(v)
+            else:
+                v = v.view(np.complex128)[..., 0]
+        return w, v, sw
+
+    def gedmd_spectrum(self, gram, omega, a, nev, tol=0.0, vectors=True):
+        """ti_obs_gedmd_spectrum: (ev [.., nev] float64, vec [.., p, nev] complex128 or None, rank [..] int32) of a stack of Gram
+        matrices [.., p, p], p <= 64 (numpy, or a CUDA complex128 tensor such as ``rff_gram`` returns: it stays on the GPU) and omega
+        [d, p] float64 (host).  Lives where gram lives."""
+        om = np.ascontiguousarray(omega, np.float64)
+        if om.ndim != 2:
+            raise ValueError(f"omega must be [d, p], got {om.shape}")
+        d, p = om.shape
+        gp, keep, dev, shape = self._complex_stack(gram, "gram")
+        if len(shape) < 2 or tuple(shape[-2:]) != (p, p):
+            raise ValueError(f"gram must be [.., {p}, {p}], got {tuple(shape)}")
+        lead, nev = tuple(shape[:-2]), int(nev)
+        n_mat = int(np.prod(lead, dtype=np.int64))
+        like = keep if dev else None
+        ev, ep = self._eig_out(like, (*lead, nev), "float64")
+        vec, vp = self._eig_out(like, (*lead, p, nev, 2), "float64") if vectors else (None, None)
+        rank, rp = self._eig_out(like, lead, "int32")
+        desc = _lib.GedmdDesc(d, p, nev, 0, float(a), float(tol))
+        _lib.check(_lib.lib().ti_obs_gedmd_spectrum(self.h, gp, n_mat, om.ctypes.data_as(C.POINTER(C.c_double)), C.byref(desc), ep, vp, rp,
+                                                    _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        if vec is not None:
+            if dev:
+                import torch
+                vec = torch.view_as_complex(vec)
+            else:
+                vec = vec.view(np.complex128)[..., 0]
+        return ev, vec, rank
+
     def weighted_histogram(self, values, logw, bins, range):
         """(hist [bins] float64, tails [3] float64 = weight below range[0], at or above range[1], of non-finite values).  values: a
         1-D float32 array or a column view such as cv[:, k] (read in place through its stride); logw None: uniform weights."""

@@ -16,7 +16,8 @@ drawn and reduced on the GPU, after the reference's IQR outlier filter.
 
 Generator EDMD on random Fourier features (ti_obs_rff_gram): ``rff_gram`` contracts the feature Gram matrices of bootstrap resamples
 in fp64 on the GPU; ``gedmd_spectrum`` / ``gedmd_generator`` turn them into the implied-timescale eigenvalues of the reference's
-adw/analysis/reweight_gedmd.py with their bootstrap interval (the p x p algebra is host numpy).
+adw/analysis/reweight_gedmd.py with their bootstrap interval.  The p x p algebra is host numpy by default; ``solver="device"`` runs it
+on the GPU too (ti_obs_gedmd_spectrum: a batched Hermitian Jacobi eigensolver in LDS, ``eigh_batched`` on its own), p <= 64.
 
 Beyond that p x p algebra the only arithmetic in this module is turning a histogram into a free-energy profile, forming phi from
 its terms, and the difference of two bootstrap runs in ``free_energy_bg``.
@@ -184,22 +185,46 @@ def rff_gram(values, omega, logw=None, n_boot=0, seed=0, first=0, indices=None, 
     return eng.rff_gram(values, omega, logw, int(n_boot), int(first), int(seed), indices)
 
 
-def gedmd_spectrum(gram, omega, a, nev, tol=0.0):
-    """Reversible generator EDMD from Gram matrices (host numpy, batched over the leading axes of gram [.., p, p]): what the
+SOLVERS = ("host", "device")
+
+
+def _check_solver(solver, p):
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if solver == "device" and p > _lib.EIGH_MAX_N:
+        raise ValueError(f"solver='device' takes p <= {_lib.EIGH_MAX_N} (the matrices live in LDS), got p = {p}: use solver='host'")
+
+
+def eigh_batched(a, vectors=True, engine=None):
+    """(w [.., n] float64 ascending, v [.., n, n] complex128 -- None without vectors --, sweeps [..] int32) of a stack a [.., n, n] of
+    Hermitian matrices, n <= 64, on the GPU (ti_obs_eigh): numpy.linalg.eigh(a, UPLO="U") by parallel cyclic Jacobi, one workgroup
+    per matrix, bit for bit the same for a matrix wherever it stands in the stack.  Lives where a lives."""
+    return (engine or _service_engine(_device_of(a))).eigh(a, vectors=vectors)
+
+
+def gedmd_spectrum(gram, omega, a, nev, tol=0.0, solver="host", engine=None):
+    """Reversible generator EDMD from Gram matrices (batched over the leading axes of gram [.., p, p]; solver "host": numpy, "device":
+    the same algebra on the GPU, p <= 64, a CUDA-tensor gram stays there and only the three results come back): what the
     reference's gedmd/rff.py spectral_analysis_rff_generator(reversible=True) computes through an SVD of M^H, here from G = M^H M.
     eigh(G) in descending order, s = sqrt(max(lambda, 0)), r = max(#{s / s_0 >= tol}, nev), L = U[:, :r] / s[:r],
     R = L^H (-a / 2 (omega^T omega) o G) L, eigh of its Hermitian part; returns (d [.., nev] the last nev eigenvalues in ascending
     order, W [.., p, nev] = L Wi, r [..]).  a is the constant diffusion (a float, 2 / beta in the reference's use).  Tensor-valued
     diffusion, the non-reversible branch and finite-lag Koopman estimation are out of scope."""
-    G = np.asarray(gram.detach().cpu().numpy() if hasattr(gram, "data_ptr") else gram, np.complex128)
     omega = np.asarray(omega, np.float64)
     p = omega.shape[1]
-    if G.shape[-2:] != (p, p):
-        raise ValueError(f"gram must be [.., {p}, {p}], got {G.shape}")
+    _check_solver(solver, p)
+    shape = tuple(gram.shape) if hasattr(gram, "shape") else np.shape(gram)
+    if shape[-2:] != (p, p):
+        raise ValueError(f"gram must be [.., {p}, {p}], got {shape}")
     if isinstance(nev, bool) or int(nev) != nev or not 1 <= int(nev) <= p:
         raise ValueError(f"nev must be an integer in 1..p = {p}, got {nev!r}")
     if not np.isfinite(a) or not np.isfinite(tol) or tol < 0:
         raise ValueError(f"a must be finite and tol finite and >= 0, got {(a, tol)}")
+    if solver == "device":
+        ev, vec, rank = (engine or _service_engine(_device_of(gram))).gedmd_spectrum(gram, omega, a, int(nev), tol)
+        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "data_ptr") else t
+        return host(ev), host(vec), host(rank).astype(np.int64)
+    G = np.asarray(gram.detach().cpu().numpy() if hasattr(gram, "data_ptr") else gram, np.complex128)
     nev, lead = int(nev), G.shape[:-2]
     G = G.reshape(-1, p, p)
     lam, U = np.linalg.eigh(G)
@@ -226,16 +251,17 @@ their negatives); ci [2, nev]: percentiles of the resample estimates; estimates 
 point estimate."""
 
 
-def gedmd_generator(values, omega, nev, a, tol=0.0, logw=None, n_boot=1000, level=0.95, seed=0, first=0, indices=None, engine=None):
+def gedmd_generator(values, omega, nev, a, tol=0.0, logw=None, n_boot=1000, level=0.95, seed=0, first=0, indices=None, engine=None, solver="host"):
     """The bootstrapped generator spectrum of the reference's adw/analysis/reweight_gedmd.py (bootstrap_eigenvalues over gedmd): the
-    Gram matrices on the GPU (``rff_gram``), the p x p algebra on the host (``gedmd_spectrum``), the interval by numpy's linear
-    percentile rule as in ``bootstrap``.  The reference reweights by weighted resampling and then bootstraps uniformly; here logw
+    Gram matrices on the GPU (``rff_gram``), the p x p algebra on the host or, with solver="device", on the GPU as well
+    (``gedmd_spectrum``), the interval by numpy's linear percentile rule as in ``bootstrap``.  The reference reweights by weighted resampling and then bootstraps uniformly; here logw
     enters the Gram matrices directly -- the expectation of that step -- and the bootstrap draws uniformly.  The reference's exact
     procedure stays reachable through indices."""
     if not 0.0 < float(level) < 1.0:
         raise ValueError(f"level must be in (0, 1), got {level!r}")
+    _check_solver(solver, np.shape(omega)[-1] if np.ndim(omega) else 0)
     G = rff_gram(values, omega, logw=logw, n_boot=n_boot, seed=seed, first=first, indices=indices, engine=engine)
-    d, W, r = gedmd_spectrum(G, omega, a, nev, tol)
+    d, W, r = gedmd_spectrum(G, omega, a, nev, tol, solver=solver, engine=engine)
     est = d[1:]
     ci = np.full((2, d.shape[1]), np.nan)
     if est.shape[0] and not np.isnan(est).any():

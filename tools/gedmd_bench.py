@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Measure the bootstrapped generator spectrum (ti_obs_rff_gram + the host algebra) against the reference's loop in numpy on the same
-machine's CPU.
+"""Measure the bootstrapped generator spectrum (ti_obs_rff_gram + the p x p algebra, on the host or with --solver device on the GPU:
+ti_obs_gedmd_spectrum) against the reference's loop in numpy on the same machine's CPU.
 
 Shapes: n = 25 000 and n = 400 000 bimodal samples (d = 1, fp32, a device tensor), p = 50 Gaussian features (sigma = 0.6), nev = 4,
 tol = 1e-4, a = 2 / 1.25, 1000 resamples.
@@ -8,12 +8,14 @@ GPU: medians of --reps wall-clock calls after one warm-up of
   gram       observables.rff_gram alone (the 1001 Gram matrices stay on the device; the call is synchronous)
   generator  observables.gedmd_generator: the same call, the copy of the Gram matrices to the host, and the host eigh stage
   host       observables.gedmd_spectrum alone on the copied Gram matrices -- its share of `generator` is printed
+--solver device: `generator` is gedmd_generator(solver="device") and the spectrum stage (`spectrum_ms`) is observables.gedmd_spectrum
+(solver="device") alone on the device-resident Gram matrices (its three results come back to the host); --cpu-resamples 0 skips the CPU leg.
 CPU: tests/gedmd_numpy.py svd_route -- the reference's algorithm, an SVD of the [p, m] feature matrix per resample, drawn with
 RandomState.choice -- timed over --cpu-resamples resamples (median of --cpu-reps) and scaled to 1000: the loop is linear in the resamples.
 The Gram kernel's arithmetic per call: 4 MFMAs of 2 * 16 * 16 * 4 flop per upper tile and 4 draws; its gathered bytes: 16 P per draw.
 Prints one JSON line per size.
 
-    python tools/gedmd_bench.py [--reps 7] [--cpu-resamples 5]
+    python tools/gedmd_bench.py [--reps 7] [--cpu-resamples 5] [--solver host|device]
 """
 import argparse
 import importlib
@@ -47,6 +49,7 @@ def main():
     ap.add_argument("--cpu-reps", type=int, default=3)
     ap.add_argument("--sizes", type=int, nargs="+", default=[25000, 400000])
     ap.add_argument("--p", type=int, default=50)
+    ap.add_argument("--solver", choices=("host", "device"), default="host")
     args = ap.parse_args()
     import torch
     import gedmd_numpy as gn
@@ -61,12 +64,22 @@ def main():
         x = (np.where(rs.random_sample(n) < 0.5, -1.0, 1.0) + 0.35 * rs.standard_normal(n)).astype(np.float32)
         dev = torch.from_numpy(x).cuda()
         gram_ms, gram_min = median_ms(lambda: obs.rff_gram(dev, omega, n_boot=nb, seed=1, engine=eng), args.reps)
-        gen_ms, gen_min = median_ms(lambda: obs.gedmd_generator(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng), args.reps)
-        G = obs.rff_gram(dev, omega, n_boot=nb, seed=1, engine=eng).cpu().numpy()
+        kw = {} if args.solver == "host" else dict(solver="device")
+        gen_ms, gen_min = median_ms(lambda: obs.gedmd_generator(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng, **kw), args.reps)
+        Gd = obs.rff_gram(dev, omega, n_boot=nb, seed=1, engine=eng)
+        G = Gd.cpu().numpy()
         host_ms, _ = median_ms(lambda: obs.gedmd_spectrum(G, omega, a, nev, tol), args.reps)
-        res = obs.gedmd_generator(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng)
+        res = obs.gedmd_generator(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng, **kw)
+        if args.solver == "device":
+            spec_ms, spec_min = median_ms(lambda: obs.gedmd_spectrum(Gd, omega, a, nev, tol, solver="device", engine=eng), args.reps)
+            _, _, sweeps = obs.eigh_batched(Gd, vectors=False, engine=eng)
+            extra = dict(solver="device", spectrum_ms=spec_ms, spectrum_ms_min=spec_min, spectrum_share=spec_ms / gen_ms, host_over_device=host_ms / spec_ms,
+                         gram_sweeps_mean=float(sweeps.float().mean()), gram_sweeps_max=int(sweeps.max()))
+        else:
+            extra = dict(solver="host", host_share=host_ms / gen_ms, spectrum_ms=host_ms, spectrum_share=host_ms / gen_ms)
         c = []
-        for _ in range(args.cpu_reps):
+        ref = [np.full(nev, np.nan)]
+        for _ in range(args.cpu_reps if args.cpu_resamples > 0 else 0):
             rr = np.random.RandomState(1)
             t0 = time.perf_counter()
             for _ in range(args.cpu_resamples):
@@ -74,8 +87,8 @@ def main():
             c.append((time.perf_counter() - t0) * 1e3 * nb / args.cpu_resamples)
         flop = (n * (1 + nb) / 4) * (T * (T + 1) / 2) * 4 * 2 * 16 * 16 * 4
         rec = dict(n=n, p=p, resamples=nb, gram_ms=gram_ms, gram_ms_min=gram_min, generator_ms=gen_ms, generator_ms_min=gen_min, host_eigh_ms=host_ms,
-                   host_share=host_ms / gen_ms, cpu_numpy_ms=float(np.median(c)), cpu_resamples_timed=args.cpu_resamples,
-                   speedup_generator=float(np.median(c) / gen_ms), gram_call_tflops=flop / (gram_ms * 1e-3) / 1e12,
+                   cpu_numpy_ms=float(np.median(c)) if c else None, cpu_resamples_timed=args.cpu_resamples,
+                   speedup_generator=float(np.median(c) / gen_ms) if c else None, **extra, gram_call_tflops=flop / (gram_ms * 1e-3) / 1e12,
                    gram_call_gather_GBps=n * (1 + nb) * 16 * 16 * T / (gram_ms * 1e-3) / 1e9, eigenvalues=res.eigenvalues.tolist(),
                    ci=res.ci.tolist(), rank=res.rank, cpu_last_resample=ref[0].tolist(), device=torch.cuda.get_device_name(0))
         print(json.dumps(rec), flush=True)
