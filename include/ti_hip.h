@@ -424,6 +424,21 @@ typedef struct { int32_t d, p; int64_t n_boot, first; uint64_t seed; } ti_gram_d
 /* values [n rows, stride] fp32, logw [n] fp32 or NULL, idx [n_boot, n_draw] int32 or NULL, out fp64: [host|device] by mem. */
 int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
                     const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem);
+/* ti_obs_rff_gram for 1 <= p <= TI_GRAM_WIDE_MAX_P (the molecule study's p = 300 and the model-selection grids up to p = 1000 of the
+ * reference's mdqm9/analysis/gedmd.py and the two model_selection.py scripts): the arguments, the output layout [1 + n_boot, p, p, 2], the draws, the
+ * mem modes, the staging, the feature-table cap n P <= 2^27 and every refusal are those of ti_obs_rff_gram; only the range of p differs.
+ * p <= 128 runs the kernels of ti_obs_rff_gram and returns the bits it returns.  Beyond that the P / 16 column tiles are cut into
+ * panels of 8 tiles (the last may be narrower) and one workgroup per (resample row, segment of 8192 draws, panel pair I <= J)
+ * accumulates the pair's tiles -- the upper triangle of a diagonal pair, all of an off-diagonal one -- with both panels of the 16
+ * gathered draws in LDS.  A 16 x 16 tile is summed exactly as ti_obs_rff_gram sums it (four draws per step in draw order, the chunk and
+ * segment boundaries at the same draws), so a tile of the result holds the bits ti_obs_rff_gram gives for that pair of column tiles
+ * of omega.  Every output is exactly Hermitian, Im of the diagonal is 0.  No atomics.
+ * A row is a function of (its draws, the data, omega, n_draw) only.  It does not depend on n_boot, on first beyond R, on generator
+ * versus idx, on mem, or on rows per launch.  A call repeats bit for bit.
+ * An out-of-range idx entry is TI_E_ARG with out untouched.  A non-finite logw is TI_E_NAN with its index. */
+#define TI_GRAM_WIDE_MAX_P 1024
+int ti_obs_rff_gram_wide(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
+                         const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem);
 /* Batched complex-Hermitian fp64 eigensolver on the device: numpy.linalg.eigh(A, UPLO="U") of n_mat matrices of order n <= 64, one
  * 256-thread workgroup per matrix, A and the accumulated eigenvector matrix V both in LDS (2 m m 16 bytes plus small tables, m = n
  * rounded up to even: 128 KiB at n = 64; n <= 50 leaves room for two workgroups per CU).

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "ti_painn_debug_phi0_path",
     "ti_obs_rff_gram",
     "ti_obs_eigh", "ti_obs_gedmd_spectrum",
+    "ti_obs_rff_gram_wide",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -49,6 +50,8 @@ BOOT_DOMAIN = 0x424F4F54
 BOOT_MAX_RESAMPLES = 1 << 20
 # ti_obs_rff_gram: the limits of d and p, and of the feature table (n * P entries, P = p rounded up to 16)
 GRAM_MAX_D, GRAM_MAX_P, GRAM_MAX_TABLE = 16, 128, 1 << 27
+# ti_obs_rff_gram_wide: the same call with the blocked pass behind it (TI_GRAM_WIDE_MAX_P)
+GRAM_WIDE_MAX_P = 1024
 # ti_obs_eigh / ti_obs_gedmd_spectrum: the largest matrix order (TI_EIGH_MAX_N), the sweep cap, the most matrices of a call
 EIGH_MAX_N, EIGH_MAX_SWEEPS, EIGH_MAX_MATRICES = 64, 64, BOOT_MAX_RESAMPLES + 1
 
@@ -169,6 +172,7 @@ def lib():
     L.ti_obs_set_observer.argtypes = [vp, ip, C.c_int32, fp, ip, C.c_int32, vp, C.c_int]
     L.ti_obs_bootstrap.argtypes = [vp, vp, C.c_int64, C.POINTER(BootDesc), vp, C.c_int64, C.POINTER(C.c_double), vp, C.c_int]
     L.ti_obs_rff_gram.argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(C.c_double), vp, C.POINTER(GramDesc), vp, C.c_int64, vp, C.c_int]
+    L.ti_obs_rff_gram_wide.argtypes = L.ti_obs_rff_gram.argtypes
     L.ti_obs_eigh.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int]
     L.ti_obs_gedmd_spectrum.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_double), C.POINTER(GedmdDesc), vp, vp, vp, C.c_int]
     _lib = L

@@ -216,15 +216,17 @@ int ti_obs_bootstrap(ti_handle* h, const float* logw, int64_t n, const ti_boot_d
     });
 }
 
-int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
-                    const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem)
+// ti_obs_rff_gram (max_p = 128) and ti_obs_rff_gram_wide (max_p = TI_GRAM_WIDE_MAX_P): one body, so that the checks, the staging,
+// the draws and the cut into launches are the same statement; more than 8 column tiles take the blocked pass
+static int rff_gram_call(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
+                         const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem, int max_p)
 {
     // the checks that need no device come first, so they can be exercised with a NULL handle; that one is refused last
     if (!values || !omega || !g || !out) return fail(TI_E_ARG, "NULL buffer");
     if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
     if (n < 1 || n > (int64_t)INT32_MAX) return fail(TI_E_ARG, "n must be in 1..2^31-1");
     if (g->d < 1 || g->d > 16) return fail(TI_E_ARG, "d must be in 1..16");
-    if (g->p < 1 || g->p > 128) return fail(TI_E_ARG, "p must be in 1..128");
+    if (g->p < 1 || g->p > max_p) return fail(TI_E_ARG, "p must be in 1.." + std::to_string(max_p));
     if (stride < g->d) return fail(TI_E_ARG, "stride < d");
     for (int i = 0; i < g->d * g->p; ++i)
         if (!std::isfinite(omega[i])) return fail(TI_E_ARG, "non-finite omega at entry " + std::to_string(i));
@@ -276,7 +278,7 @@ int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n
             gp.nseg = (draws + GRAM_SEG - 1) / GRAM_SEG;
             grow(h->gram_part, (size_t)rows * (size_t)gp.nseg * part_doubles);
             gp.part = h->gram_part.p;
-            HIP_CHECK(launch_obs_gram(gp, rows, st));
+            HIP_CHECK(T > 8 ? launch_obs_gram_wide(gp, rows, st) : launch_obs_gram(gp, rows, st));
             HIP_CHECK(launch_obs_gram_reduce(dst, gp.part, rows, gp.nseg, p, st));
         };
         gp.draw.source = BOOT_SRC_IDENTITY;
@@ -297,6 +299,18 @@ int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n
         HIP_CHECK(hipStreamSynchronize(st));
         return TI_OK;
     });
+}
+
+int ti_obs_rff_gram(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
+                    const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem)
+{
+    return rff_gram_call(h, values, stride, n, omega, logw, g, idx, n_draw, out, mem, 128);
+}
+
+int ti_obs_rff_gram_wide(ti_handle* h, const float* values, int64_t stride, int64_t n, const double* omega, const float* logw,
+                         const ti_gram_desc* g, const int32_t* idx, int64_t n_draw, double* out, int mem)
+{
+    return rff_gram_call(h, values, stride, n, omega, logw, g, idx, n_draw, out, mem, TI_GRAM_WIDE_MAX_P);
 }
 
 // the refusals ti_obs_eigh and ti_obs_gedmd_spectrum find in the status words of a solve over n_mat matrices (host copy)

@@ -11,6 +11,8 @@
 // draw order, so a row's partial Gram is a function of (its draws, the data, Omega, n_draw) only.  The partials go to the workspace
 // with plain stores and obs_gram_reduce_kernel adds them in segment order, writes the upper triangle and mirrors it (conjugate)
 // below the diagonal.  No atomics.
+// More than 8 column tiles (128 < p <= 1024, ti_obs_rff_gram_wide) do not fit one group's registers: obs_gram_wide_kernel below cuts
+// them into panel pairs, sums every tile by the same statement (gram_tile_step) and feeds the same reduce kernel.
 #include "boot_draw.hpp"
 
 namespace ti {
@@ -43,6 +45,16 @@ __global__ __launch_bounds__(GRAM_BLOCK) void obs_gram_feature_kernel(double* __
     z[i * 2 * P + k] = c;
     z[i * 2 * P + P + k] = s;
     if (w && k == 0) w[i] = exp((double)logw[i] - mx[0]);
+}
+
+// four draws of one tile: Re += (w c_k) c_l + (w s_k) s_l, Im += (w s_k) c_l - (w c_k) s_l, in this order
+__device__ __forceinline__ void gram_tile_step(double w, double ac, double as, double bc, double bs, f64x4& re, f64x4& im)
+{
+    const double wc = w * ac, wsn = w * as;
+    re = __builtin_amdgcn_mfma_f64_16x16x4f64(wc, bc, re, 0, 0, 0);
+    re = __builtin_amdgcn_mfma_f64_16x16x4f64(wsn, bs, re, 0, 0, 0);
+    im = __builtin_amdgcn_mfma_f64_16x16x4f64(wsn, bc, im, 0, 0, 0);
+    im = __builtin_amdgcn_mfma_f64_16x16x4f64(-wc, bs, im, 0, 0, 0);
 }
 
 // T = P / 16 column tiles, NT = T (T + 1) / 2 upper-triangle tiles; wave v owns the tiles v, v + 4, ...: NSLOT of them at most
@@ -128,12 +140,7 @@ __global__ __launch_bounds__(GRAM_BLOCK) void obs_gram_kernel(GramParams g)
 #pragma unroll
             for (int s = 0; s < NSLOT; ++s) {
                 if (4 * s + wave < NT) {
-                    const double ac = zr[offa[s]], as = zr[P + offa[s]], bc = zr[offb[s]], bs = zr[P + offb[s]];
-                    const double wc = w * ac, wsn = w * as;
-                    re[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(wc, bc, re[s], 0, 0, 0);
-                    re[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(wsn, bs, re[s], 0, 0, 0);
-                    im[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(wsn, bc, im[s], 0, 0, 0);
-                    im[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(-wc, bs, im[s], 0, 0, 0);
+                    gram_tile_step(w, zr[offa[s]], zr[P + offa[s]], zr[offb[s]], zr[P + offb[s]], re[s], im[s]);
                 }
             }
         }
@@ -151,6 +158,158 @@ __global__ __launch_bounds__(GRAM_BLOCK) void obs_gram_kernel(GramParams g)
             for (int reg = 0; reg < 4; ++reg) {
                 out[t * 512 + reg * 64 + lane] = re[s][reg];
                 out[t * 512 + 256 + reg * 64 + lane] = im[s][reg];
+            }
+        }
+    }
+}
+
+// ---- the blocked pass, 128 < p <= 1024 (ti_obs_rff_gram_wide)
+// The T column tiles are cut into panels of GRAM_PANEL = 8 (the last may be narrower); one group per (resample row, segment, panel
+// pair I <= J).  A diagonal pair accumulates the upper-triangle tiles of its panel, an off-diagonal pair all T_I T_J tiles: at most 64,
+// 16 per wave, dealt round robin as above.  Both panels of the 16 gathered draws sit in LDS, a row laid out (cos I | sin I | cos J |
+// sin J).  A tile's sum is gram_tile_step over the segment's draws in draw order, chunk boundaries included: the statement
+// obs_gram_kernel<T> makes, so a tile holds the bits that kernel gives for its pair of column tiles.  The partial of tile (k, l)
+// goes to the slot obs_gram_reduce_kernel reads it from, the upper-triangle number of the whole matrix.
+// Only the last panel can be narrow, so the widths are template arguments -- DIAG: panel I = J of TJ tiles; else panel I of 8 tiles
+// and panel J of TJ -- and a launch covers the pairs of one shape (launch_obs_gram_wide).
+constexpr int GRAM_PANEL = 8;
+
+// grid = rows * nseg * cnt; pair c < cnt of a (row, segment) is, DIAG: (pi0 + c, pi0 + c); else with jfix >= 0: (c, jfix); else pair c
+// of the I < J among the first pi0 panels, row by row
+template <int TJ, bool DIAG>
+__global__ __launch_bounds__(GRAM_BLOCK) void obs_gram_wide_kernel(GramParams g, int pi0, int jfix, int cnt)
+{
+    constexpr int TI = DIAG ? TJ : GRAM_PANEL, WI = 16 * TI, WJ = 16 * TJ, OJ = DIAG ? 0 : 2 * WI;   // OJ: where panel J starts in an LDS row
+    constexpr int NT = DIAG ? TJ * (TJ + 1) / 2 : TI * TJ, NSLOT = (NT + 3) / 4, LD = OJ + 2 * WJ + GRAM_LDPAD;
+    __shared__ double zs[GRAM_CHUNK * LD];
+    __shared__ double ws[GRAM_CHUNK];
+    __shared__ int ixs[2][GRAM_CHUNK];
+    const BootParams& p = g.draw;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, cl = lane & 15;
+    const int T = g.T, P = 16 * T;
+    const long long rs = blockIdx.x / cnt, row = rs / g.nseg, seg = rs - row * g.nseg, nd = p.n_draw;
+    int pi = (int)(blockIdx.x - rs * cnt), pj;
+    if (DIAG) { pi += pi0; pj = pi; }
+    else if (jfix >= 0) pj = jfix;
+    else {
+        int c = pi;
+        pi = 0;
+        while (c >= pi0 - 1 - pi) { c -= pi0 - 1 - pi; ++pi; }
+        pj = pi + 1 + c;
+    }
+    const long long j_begin = seg * GRAM_SEG, j_end = j_begin + GRAM_SEG < nd ? j_begin + GRAM_SEG : nd;
+    const uint64_t R = (uint64_t)p.first + (uint64_t)row;
+    const f64x2* __restrict__ z2 = reinterpret_cast<const f64x2*>(g.z);
+    bool ok = true;
+
+    // the wave's tiles: slot s is tile t = 4 s + wave of the pair, (a, b) = row tile of panel I, column tile of panel J -- the upper
+    // triangle row by row on the diagonal, the TI x TJ rectangle row by row off it; LDS offsets of its A and B operands
+    int ta[NSLOT], tb[NSLOT];
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+        int t = 4 * s + wave, a = 0;
+        if (t >= NT) t = 0;                        // no such tile: the slot is skipped below
+        if (DIAG) {
+            while (t >= TJ - a) { t -= TJ - a; ++a; }
+            t += a;
+        } else {
+            a = t / TJ;
+            t -= a * TJ;
+        }
+        ta[s] = a;
+        tb[s] = t;
+    }
+    f64x4 re[NSLOT], im[NSLOT];
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) { re[s] = f64x4{0, 0, 0, 0}; im[s] = f64x4{0, 0, 0, 0}; }
+
+    // population indices of the 16 draws from j0 on into ixs[b] (-1: past the segment's end), by the first 8 threads
+    auto draw = [&](long long j0, int b) {
+        if (tid < GRAM_CHUNK / 2) {
+            const long long j = j0 + 2 * tid;
+            long long i0 = -1, i1 = -1;
+            if (j < j_end) {
+                boot_draw_pair(p, row, R, j >> 1, i0, i1, ok);
+                if (j + 1 >= j_end) i1 = -1;
+            }
+            ixs[b][2 * tid] = (int)i0;
+            ixs[b][2 * tid + 1] = (int)i1;
+        }
+    };
+    // a fill: 16 threads per draw; unit v = fc + 16 m of a panel of t tiles is 16 bytes, the cos columns 2 v for v < 8 t, else the
+    // sin columns 2 (v - 8 t); a thread takes the units m < t of each panel
+    const int fr = tid >> 4, fc = tid & 15;
+    f64x2 prei[TI], prej[DIAG ? 1 : TJ];
+    double prew = 0.0;
+    auto fetch = [&](int b) {
+        const int i = ixs[b][fr];
+        const f64x2* __restrict__ zi = z2 + (long long)(i < 0 ? 0 : i) * P + (GRAM_PANEL * 8) * pi;
+        const f64x2* __restrict__ zj = z2 + (long long)(i < 0 ? 0 : i) * P + (GRAM_PANEL * 8) * pj;
+#pragma unroll
+        for (int m = 0; m < TI; ++m) {
+            const int v = fc + 16 * m;
+            prei[m] = i >= 0 ? zi[v < 8 * TI ? v : P / 2 + v - 8 * TI] : f64x2{0, 0};
+        }
+        if (!DIAG) {
+#pragma unroll
+            for (int m = 0; m < TJ; ++m) {
+                const int v = fc + 16 * m;
+                prej[m] = i >= 0 ? zj[v < 8 * TJ ? v : P / 2 + v - 8 * TJ] : f64x2{0, 0};
+            }
+        }
+        if (tid < GRAM_CHUNK) {
+            const int iw = ixs[b][tid];
+            prew = iw < 0 ? 0.0 : g.w ? g.w[iw] : 1.0;
+        }
+    };
+
+    draw(j_begin, 0);
+    __syncthreads();
+    fetch(0);
+    int b = 0;
+    for (long long j0 = j_begin; j0 < j_end; j0 += GRAM_CHUNK, b ^= 1) {
+#pragma unroll
+        for (int m = 0; m < TI; ++m) {
+            const int v = fc + 16 * m;
+            *reinterpret_cast<f64x2*>(&zs[fr * LD + (v < 8 * TI ? 2 * v : WI + 2 * (v - 8 * TI))]) = prei[m];
+        }
+        if (!DIAG) {
+#pragma unroll
+            for (int m = 0; m < TJ; ++m) {
+                const int v = fc + 16 * m;
+                *reinterpret_cast<f64x2*>(&zs[fr * LD + OJ + (v < 8 * TJ ? 2 * v : WJ + 2 * (v - 8 * TJ))]) = prej[m];
+            }
+        }
+        if (tid < GRAM_CHUNK) ws[tid] = prew;
+        const bool more = j0 + GRAM_CHUNK < j_end;
+        if (more) draw(j0 + GRAM_CHUNK, b ^ 1);
+        __syncthreads();
+        if (more) fetch(b ^ 1);
+#pragma unroll
+        for (int kk = 0; kk < GRAM_CHUNK / 4; ++kk) {
+            const int r = 4 * kk + q;
+            const double w = ws[r];
+            const double* zr = zs + r * LD + cl;
+#pragma unroll
+            for (int s = 0; s < NSLOT; ++s)
+                if (4 * s + wave < NT)
+                    gram_tile_step(w, zr[16 * ta[s]], zr[WI + 16 * ta[s]], zr[OJ + 16 * tb[s]], zr[OJ + WJ + 16 * tb[s]], re[s], im[s]);
+        }
+        __syncthreads();
+    }
+    if (!ok) *p.flag = 1;                       // plain store of one value: whoever writes, the flag reads 1
+
+    // tile (k, l) of the whole matrix, k <= l, is partial tile k T - k (k - 1) / 2 + (l - k) of this (row, segment)
+    double* __restrict__ out = g.part + rs * ((long long)T * (T + 1) / 2) * 512;
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+        if (4 * s + wave < NT) {
+            const int k = GRAM_PANEL * pi + ta[s], l = GRAM_PANEL * pj + tb[s];
+            double* __restrict__ o = out + (long long)(k * T - k * (k - 1) / 2 + (l - k)) * 512;
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                o[reg * 64 + lane] = re[s][reg];
+                o[256 + reg * 64 + lane] = im[s][reg];
             }
         }
     }
@@ -211,6 +370,44 @@ hipError_t launch_obs_gram(const GramParams& g, long long n_rows, hipStream_t st
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+namespace {
+
+template <bool DIAG>
+hipError_t launch_gram_wide_shape(int tj, const GramParams& g, long long rs, int pi0, int jfix, int cnt, hipStream_t st)
+{
+    const long long blocks = rs * cnt;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(GRAM_BLOCK);
+    switch (tj) {
+    case 1: hipLaunchKernelGGL((obs_gram_wide_kernel<1, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    case 2: hipLaunchKernelGGL((obs_gram_wide_kernel<2, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    case 3: hipLaunchKernelGGL((obs_gram_wide_kernel<3, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    case 4: hipLaunchKernelGGL((obs_gram_wide_kernel<4, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    case 5: hipLaunchKernelGGL((obs_gram_wide_kernel<5, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    case 6: hipLaunchKernelGGL((obs_gram_wide_kernel<6, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    case 7: hipLaunchKernelGGL((obs_gram_wide_kernel<7, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    case 8: hipLaunchKernelGGL((obs_gram_wide_kernel<8, DIAG>), grid, block, 0, st, g, pi0, jfix, cnt); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// nf full panels and, if T is no multiple of 8, a last one of tl tiles: the full diagonal pairs, the last diagonal pair, the pairs of
+// two full panels, the pairs of a full panel and the last -- every upper-triangle tile of the matrix in exactly one launch
+hipError_t launch_obs_gram_wide(const GramParams& g, long long n_rows, hipStream_t st)
+{
+    if (g.T <= GRAM_PANEL || g.T > GRAM_WIDE_MAX_P / 16) return hipErrorInvalidValue;
+    const int nf = g.T / GRAM_PANEL, tl = g.T % GRAM_PANEL;
+    const long long rs = n_rows * g.nseg;
+    hipError_t e = launch_gram_wide_shape<true>(GRAM_PANEL, g, rs, 0, -1, nf, st);
+    if (e == hipSuccess && tl) e = launch_gram_wide_shape<true>(tl, g, rs, nf, -1, 1, st);
+    if (e == hipSuccess && nf > 1) e = launch_gram_wide_shape<false>(GRAM_PANEL, g, rs, nf, -1, nf * (nf - 1) / 2, st);
+    if (e == hipSuccess && tl) e = launch_gram_wide_shape<false>(tl, g, rs, nf, nf, nf, st);
+    return e;
 }
 
 hipError_t launch_obs_gram_reduce(double* out, const double* part, long long n_rows, long long nseg, int p, hipStream_t st)

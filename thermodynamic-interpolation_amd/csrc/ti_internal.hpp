@@ -426,6 +426,10 @@ hipError_t launch_obs_gram_features(double* z, double* w, const float* x, long l
                                     const float* logw, const double* mx, hipStream_t st);
 // one 256-thread group per (row, segment); then out [n_rows][p][p][2] = the partials added in segment order, mirrored
 hipError_t launch_obs_gram(const GramParams& g, long long n_rows, hipStream_t st);
+// the blocked pass of ti_obs_rff_gram_wide, 8 < g.T <= 64: one group per (row, segment, pair of 8-tile column panels I <= J); it
+// fills the same partial-tile layout, so launch_obs_gram_reduce follows it unchanged
+constexpr int GRAM_WIDE_MAX_P = TI_GRAM_WIDE_MAX_P;
+hipError_t launch_obs_gram_wide(const GramParams& g, long long n_rows, hipStream_t st);
 hipError_t launch_obs_gram_reduce(double* out, const double* part, long long n_rows, long long nseg, int p, hipStream_t st);
 
 // ---- batched Hermitian eigensolver and the gEDMD algebra around it (obs_eig_kernels.hip; include/ti_hip.h ti_obs_eigh, ti_obs_gedmd_spectrum)

@@ -21,7 +21,11 @@ GPU (observables.bootstrap, seed 0), and ``ess_boot`` [n], their estimates.  sam
 "nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "potential": [a, b], "solver": "host"}`` (every entry optional; solver "device"
 runs the p x p algebra on the GPU too, p <= 64) adds ``gedmd_eigenvalues`` [nev],
 ``gedmd_ci`` [2, nev] and ``gedmd_rank``: the generator spectrum of the reweighted end state with its bootstrap interval
-(observables.gedmd_generator; U = a (x^2 - 1)^2 + b x).  Without the key exactly the reference's files are written.
+(observables.gedmd_generator; U = a (x^2 - 1)^2 + b x).  sample_ambient / sample_latent: ``"kinetics": {"columns": [...], "p": 300,
+"sigma": 5.0, "nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "temperature": T}`` (columns and temperature required) adds
+``kinetics_eigenvalues`` [nev], ``kinetics_ci`` [2, nev] and ``kinetics_rank``: the unweighted generator spectrum of the selected CV
+columns (the torsions; at most 16) of the end-state row, a = k_B T with k_B = 0.008314462618, as the reference's
+mdqm9/analysis/gedmd.py computes it; the key is checked before the rollout and refused by sample_adw.  Without the keys exactly the reference's files are written.
 """
 from __future__ import annotations
 
@@ -65,6 +69,7 @@ def _observe_kw(config):
     o.pop("bins", None)
     o.pop("bootstrap", None)
     o.pop("gedmd", None)
+    o.pop("kinetics", None)
     if o.get("ref") is not None:
         o["ref"] = np.asarray(o["ref"], np.float32)
     return dict(observe=o)
@@ -122,6 +127,59 @@ def _gedmd_arrays(g, x0, x1, dlogp, beta0, beta1, solver=GEDMD_SOLVER):
     return dict(gedmd_eigenvalues=res.eigenvalues, gedmd_ci=res.ci, gedmd_rank=np.int64(res.rank))
 
 
+KINETICS_KEYS = {"columns": None, "p": 300, "sigma": 5.0, "nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "temperature": None}
+KINETICS_KB = 0.008314462618        # kJ / (mol K), the reference's constant (mdqm9/analysis/gedmd.py)
+
+
+def _kinetics_settings(o, K=None):
+    """observables["kinetics"] completed with the defaults above and checked (columns against K CV columns when given); None without
+    the key."""
+    g = dict(o).get("kinetics")
+    if g is None:
+        return None
+    if not isinstance(g, dict) or set(g) - set(KINETICS_KEYS) or "columns" not in g or "temperature" not in g:
+        raise ValueError(f"observables['kinetics'] must be a dict with 'columns', 'temperature' and keys out of {sorted(KINETICS_KEYS)}, got {g!r}")
+    g = {**KINETICS_KEYS, **g}
+    for k in ("p", "nev", "n_boot", "seed"):
+        if isinstance(g[k], bool) or int(g[k]) != g[k] or int(g[k]) < (0 if k == "seed" else 1):
+            raise ValueError(f"observables['kinetics'][{k!r}] must be an integer >= {0 if k == 'seed' else 1}, got {g[k]!r}")
+        g[k] = int(g[k])
+    cols = list(g["columns"]) if isinstance(g["columns"], (list, tuple)) else None
+    if not cols or len(cols) > _obs._lib.GRAM_MAX_D or any(isinstance(c, bool) or int(c) != c or int(c) < 0 for c in cols) \
+            or (K is not None and max(cols) >= K):
+        raise ValueError(f"observables['kinetics']['columns'] must list 1..{_obs._lib.GRAM_MAX_D} CV columns"
+                         f"{'' if K is None else f' below {K}'}, got {g['columns']!r}")
+    g["columns"] = [int(c) for c in cols]
+    if not (np.isfinite(g["sigma"]) and g["sigma"] > 0 and np.isfinite(g["tol"]) and g["tol"] >= 0):
+        raise ValueError("observables['kinetics']: sigma must be finite and > 0, tol finite and >= 0")
+    if isinstance(g["temperature"], bool) or not (np.isfinite(g["temperature"]) and g["temperature"] > 0):
+        raise ValueError(f"observables['kinetics']['temperature'] must be finite and > 0, got {g['temperature']!r}")
+    if g["p"] > _obs._lib.GRAM_WIDE_MAX_P or g["nev"] > g["p"]:
+        raise ValueError(f"observables['kinetics']: p must not exceed {_obs._lib.GRAM_WIDE_MAX_P} and nev must not exceed p")
+    return g
+
+
+def _check_kinetics(config, molecules=True):
+    """Before the rollout, so that a slip in the key does not cost the run: observables["kinetics"] validated against the descriptor
+    count (sample_ambient / sample_latent), refused in sample_adw (molecules=False), whose analysis is the `gedmd` key."""
+    o = getattr(config, "observables", None)
+    if o is None or dict(o).get("kinetics") is None:
+        return
+    if not molecules:
+        raise ValueError("observables['kinetics'] is for sample_ambient / sample_latent (torsion columns, unweighted); sample_adw takes "
+                         "observables['gedmd']")
+    _kinetics_settings(o, len(dict(o)["descriptors"]))
+
+
+def _kinetics_arrays(g, cv_end):
+    """kinetics_eigenvalues [nev], kinetics_ci [2, nev], kinetics_rank of the selected columns of the end-state CVs cv_end [B, K]:
+    the unweighted generator spectrum of the reference's mdqm9/analysis/gedmd.py, a = k_B T."""
+    x = np.ascontiguousarray(cv_end[:, g["columns"]], np.float32)
+    omega = _obs.sample_rff_gaussian(x.shape[1], g["p"], g["sigma"], g["seed"])
+    res = _obs.gedmd_generator(x, omega, g["nev"], KINETICS_KB * float(g["temperature"]), tol=g["tol"], n_boot=g["n_boot"], seed=g["seed"])
+    return dict(kinetics_eigenvalues=res.eigenvalues, kinetics_ci=res.ci, kinetics_rank=np.int64(res.rank))
+
+
 def _write_observables(config, path, cvs, dlogps, gedmd=None):
     """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp); gedmd: (x0, x1, beta0, beta1)
     of an adw run whose observables carry the gedmd key"""
@@ -141,10 +199,14 @@ def _write_observables(config, path, cvs, dlogps, gedmd=None):
         if gedmd is None or dl is None:
             raise ValueError("observables['gedmd'] is for sample_adw with return_dlogp: the weights need the end-state dlogp")
         extra.update(_gedmd_arrays(g, gedmd[0], gedmd[1], dl, gedmd[2], gedmd[3], solver=_gedmd_solver(config.observables)))
+    k = _kinetics_settings(config.observables, cv.shape[2])
+    if k is not None:
+        extra.update(_kinetics_arrays(k, cv[-1]))
     np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
 
 
 def sample_ambient(config, b, dataset):
+    _check_kinetics(config)
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -176,6 +238,7 @@ def sample_ambient(config, b, dataset):
 
 
 def sample_latent(config, b, dataset):
+    _check_kinetics(config)
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -207,6 +270,7 @@ def sample_adw(config, b, x0s_batches):
         raise NotImplementedError(f"sample_adw writes the 1-D double well's samples (component 0, adw/sample.py:59); "
                                   f"a d = {b.dim} model would lose coordinates: use StandardIntegrator.rollout directly")
     assert len(config.beta0s) == len(config.beta1s) == 1            # adw/sample.py:24
+    _check_kinetics(config, molecules=False)
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),
                                          step_control=getattr(config, "step_control", "batch"), fused=bool(getattr(config, "fused", False)),

@@ -220,7 +220,11 @@ class _Engine:
         _lib.check(_lib.lib().ti_obs_bootstrap(self.h, lp, n, C.byref(desc), ip, n_draw, out, bp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return out[0], out[1], out[2], int(out[3]), out_boot
 
-    def rff_gram(self, values, omega, logw=None, n_boot=0, first=0, seed=0, indices=None, n_draw=0):
+    def rff_gram_wide(self, values, omega, logw=None, n_boot=0, first=0, seed=0, indices=None, n_draw=0):
+        """ti_obs_rff_gram_wide: ``rff_gram`` for p <= 1024 (beyond 128 columns the blocked pass); the same arguments and result."""
+        return self.rff_gram(values, omega, logw, n_boot, first, seed, indices, n_draw, _entry="ti_obs_rff_gram_wide")
+
+    def rff_gram(self, values, omega, logw=None, n_boot=0, first=0, seed=0, indices=None, n_draw=0, _entry="ti_obs_rff_gram"):
         """ti_obs_rff_gram: G [1 + n_boot, p, p] complex128 of values [n] or [n, d] float32 (numpy, or a CUDA tensor -- a view with
         unit stride along d, such as cv[:, :2], is read in place) and omega [d, p] float64 (host).  Row 0 is the point estimate, row
         1 + r resample first + r of the stream `seed`, or row r of indices [n_boot, n_draw] int32.  Lives where values lives."""
@@ -272,8 +276,8 @@ class _Engine:
             out = np.empty((1 + n_boot, p, p, 2), np.float64)
             op = C.c_void_p(out.ctypes.data)
         desc = _lib.GramDesc(d, p, n_boot, int(first), int(seed) & 0xFFFFFFFFFFFFFFFF)
-        _lib.check(_lib.lib().ti_obs_rff_gram(self.h, vp, stride, n, om.ctypes.data_as(C.POINTER(C.c_double)), lp, C.byref(desc), ip, n_draw, op,
-                                              _lib.MEM_DEVICE if dev_in else _lib.MEM_HOST))
+        _lib.check(getattr(_lib.lib(), _entry)(self.h, vp, stride, n, om.ctypes.data_as(C.POINTER(C.c_double)), lp, C.byref(desc), ip, n_draw, op,
+                                               _lib.MEM_DEVICE if dev_in else _lib.MEM_HOST))
         if dev_in:
             import torch
             return torch.view_as_complex(out)

@@ -18,6 +18,9 @@ Generator EDMD on random Fourier features (ti_obs_rff_gram): ``rff_gram`` contra
 in fp64 on the GPU; ``gedmd_spectrum`` / ``gedmd_generator`` turn them into the implied-timescale eigenvalues of the reference's
 adw/analysis/reweight_gedmd.py with their bootstrap interval.  The p x p algebra is host numpy by default; ``solver="device"`` runs it
 on the GPU too (ti_obs_gedmd_spectrum: a batched Hermitian Jacobi eigensolver in LDS, ``eigh_batched`` on its own), p <= 64.
+``rff_gram_wide`` (ti_obs_rff_gram_wide) is the same contraction up to p = 1024, the molecule study's size (mdqm9/analysis/gedmd.py,
+p = 300); ``gedmd_cv`` / ``gedmd_model_selection`` are the reference's cross-validated choice of (sigma, p) (gedmd/rff.py
+cv_generator_rff and the two model_selection.py scripts), scored by ``gedmd_vamp_score`` from held-out Gram matrices.
 
 Beyond that p x p algebra the only arithmetic in this module is turning a histogram into a free-energy profile, forming phi from
 its terms, and the difference of two bootstrap runs in ``free_energy_bg``.
@@ -159,10 +162,10 @@ def sample_rff_gaussian(d, p, sigma, seed):
     return np.random.RandomState(seed).randn(int(d), int(p)) / float(sigma)
 
 
-def _check_gram_args(values, omega, n_boot):
+def _check_gram_args(values, omega, n_boot, max_p=_lib.GRAM_MAX_P):
     omega = np.asarray(omega, np.float64)
-    if omega.ndim != 2 or not 1 <= omega.shape[0] <= _lib.GRAM_MAX_D or not 1 <= omega.shape[1] <= _lib.GRAM_MAX_P:
-        raise ValueError(f"omega must be [d, p] with 1 <= d <= {_lib.GRAM_MAX_D} and 1 <= p <= {_lib.GRAM_MAX_P}, got {omega.shape}")
+    if omega.ndim != 2 or not 1 <= omega.shape[0] <= _lib.GRAM_MAX_D or not 1 <= omega.shape[1] <= max_p:
+        raise ValueError(f"omega must be [d, p] with 1 <= d <= {_lib.GRAM_MAX_D} and 1 <= p <= {max_p}, got {omega.shape}")
     if not np.isfinite(omega).all():
         raise ValueError("omega must be finite")
     if isinstance(n_boot, bool) or int(n_boot) != n_boot or not 0 <= int(n_boot) <= _lib.BOOT_MAX_RESAMPLES:
@@ -183,6 +186,15 @@ def rff_gram(values, omega, logw=None, n_boot=0, seed=0, first=0, indices=None, 
     omega = _check_gram_args(values, omega, n_boot)
     eng = engine or _service_engine(_device_of(values, logw))
     return eng.rff_gram(values, omega, logw, int(n_boot), int(first), int(seed), indices)
+
+
+def rff_gram_wide(values, omega, logw=None, n_boot=0, seed=0, first=0, indices=None, engine=None):
+    """``rff_gram`` for p <= 1024 (ti_obs_rff_gram_wide): the same arguments and the same G [1 + n_boot, p, p] complex128 where values
+    lives.  Up to p = 128 it is ``rff_gram`` bit for bit; beyond, the columns are contracted panel pair by panel pair, and every
+    16 x 16 tile still holds the bits ``rff_gram`` gives for that pair of column tiles of omega."""
+    omega = _check_gram_args(values, omega, n_boot, _lib.GRAM_WIDE_MAX_P)
+    eng = engine or _service_engine(_device_of(values, logw))
+    return eng.rff_gram_wide(values, omega, logw, int(n_boot), int(first), int(seed), indices)
 
 
 SOLVERS = ("host", "device")
@@ -253,20 +265,111 @@ point estimate."""
 
 def gedmd_generator(values, omega, nev, a, tol=0.0, logw=None, n_boot=1000, level=0.95, seed=0, first=0, indices=None, engine=None, solver="host"):
     """The bootstrapped generator spectrum of the reference's adw/analysis/reweight_gedmd.py (bootstrap_eigenvalues over gedmd): the
-    Gram matrices on the GPU (``rff_gram``), the p x p algebra on the host or, with solver="device", on the GPU as well
+    Gram matrices on the GPU (``rff_gram``; ``rff_gram_wide`` for 128 < p <= 1024, the molecule study's size), the p x p algebra on the host or, with solver="device", on the GPU as well
     (``gedmd_spectrum``), the interval by numpy's linear percentile rule as in ``bootstrap``.  The reference reweights by weighted resampling and then bootstraps uniformly; here logw
     enters the Gram matrices directly -- the expectation of that step -- and the bootstrap draws uniformly.  The reference's exact
     procedure stays reachable through indices."""
     if not 0.0 < float(level) < 1.0:
         raise ValueError(f"level must be in (0, 1), got {level!r}")
     _check_solver(solver, np.shape(omega)[-1] if np.ndim(omega) else 0)
-    G = rff_gram(values, omega, logw=logw, n_boot=n_boot, seed=seed, first=first, indices=indices, engine=engine)
+    gram = rff_gram_wide if np.ndim(omega) == 2 and np.shape(omega)[1] > _lib.GRAM_MAX_P else rff_gram
+    G = gram(values, omega, logw=logw, n_boot=n_boot, seed=seed, first=first, indices=indices, engine=engine)
     d, W, r = gedmd_spectrum(G, omega, a, nev, tol, solver=solver, engine=engine)
     est = d[1:]
     ci = np.full((2, d.shape[1]), np.nan)
     if est.shape[0] and not np.isnan(est).any():
         ci = np.percentile(est, [50 * (1 - float(level)), 50 * (1 + float(level))], axis=0)
     return GedmdResult(d[0], ci, est, W[0], int(r[0]))
+
+
+def gedmd_vamp_score(gram_test, omega, a, W):
+    """The VAMP score of the subspace W [.., p, r] on held-out data, from the held-out Gram matrix gram_test [.., p, p] alone (host
+    numpy, batched over the leading axes): the reference's gedmd/rff.py _score_test_data_generator, whose SVD of (M_test W)^H is the
+    eigendecomposition of C = W^H G_test W here.  C's Hermitian part is taken; eigh(C) = (lambda, U0); L0 = W U0 / sqrt(lambda);
+    R = L0^H (-a / 2 (omega^T omega) o G_test) L0; the score is the sum of the eigenvalues of R's Hermitian part.  NaN where a
+    lambda is not positive."""
+    omega = np.asarray(omega, np.float64)
+    if omega.ndim != 2:
+        raise ValueError(f"omega must be [d, p], got {omega.shape}")
+    p = omega.shape[1]
+    host = lambda t: t.detach().cpu().numpy() if hasattr(t, "data_ptr") else t
+    G, W = np.asarray(host(gram_test), np.complex128), np.asarray(host(W), np.complex128)
+    if G.shape[-2:] != (p, p):
+        raise ValueError(f"gram_test must be [.., {p}, {p}], got {G.shape}")
+    if W.ndim < 2 or W.shape[-2] != p or not 1 <= W.shape[-1] <= p or W.shape[:-2] != G.shape[:-2]:
+        raise ValueError(f"W must be [.., {p}, r] with 1 <= r <= {p} and the leading axes of gram_test, got {W.shape}")
+    if not np.isfinite(a):
+        raise ValueError(f"a must be finite, got {a!r}")
+    herm = lambda A: 0.5 * (A + np.conj(np.swapaxes(A, -1, -2)))
+    WH = np.conj(np.swapaxes(W, -1, -2))
+    lam, U0 = np.linalg.eigh(herm(WH @ G @ W))
+    bad = ~(lam > 0.0).all(axis=-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        L0 = (W @ U0) / np.sqrt(lam)[..., None, :]
+    L0 = np.where(bad[..., None, None], 0.0, L0)
+    ML = (-0.5 * float(a)) * (omega.T @ omega) * G
+    score = np.linalg.eigvalsh(herm(np.conj(np.swapaxes(L0, -1, -2)) @ ML @ L0)).sum(axis=-1)
+    return np.where(bad, np.nan, score)
+
+
+GedmdCvResult = collections.namedtuple("GedmdCvResult", "eigenvalues scores rank")
+GedmdCvResult.__doc__ = """eigenvalues [ntest, nev]: the generator eigenvalues of every training set, ascending; scores [ntest]: the VAMP score
+of its eigenvectors on the held-out set; rank [ntest]: the rank the cutoff kept."""
+
+
+def gedmd_cv(values, omega, a, nev, tol=0.0, rtrain=0.75, ntest=20, seed=0, splits=None, logw=None, engine=None):
+    """The reference's gedmd/rff.py cv_generator_rff: ntest random splits of the sample into a training share rtrain and a held-out
+    rest; the generator spectrum of the training set (``gedmd_spectrum``, host algebra) and the VAMP score of its nev eigenvectors
+    on the held-out set (``gedmd_vamp_score``).  Both need the two Gram matrices only: two ``rff_gram_wide`` calls with the splits as
+    indices, on the GPU.
+    splits [ntest, n] int32 holds one permutation of 0..n-1 per row: the first floor(rtrain n) entries are the training set, the
+    rest the held-out set (sklearn's train_test_split sizes for a float train_size).  None: RandomState(seed).permutation(n) per row.
+    The score has the sign of the reference FUNCTION (a sum of generator eigenvalues, <= 0, larger is better); the reference's
+    model_selection.py scripts store its negative."""
+    n = int(values.shape[0])
+    if not 0.0 < float(rtrain) < 1.0:
+        raise ValueError(f"rtrain must be in (0, 1), got {rtrain!r}")
+    ntr = int(np.floor(float(rtrain) * n))
+    if ntr < 1 or n - ntr < 1:
+        raise ValueError(f"rtrain = {rtrain} of n = {n} samples leaves the training or the held-out set empty")
+    if isinstance(nev, bool) or int(nev) != nev or not 1 <= int(nev) <= ntr:
+        raise ValueError(f"nev must be an integer in 1..{ntr} (the training size), got {nev!r}")
+    if splits is None:
+        if isinstance(ntest, bool) or int(ntest) != ntest or int(ntest) < 1:
+            raise ValueError(f"ntest must be an integer >= 1, got {ntest!r}")
+        rs = np.random.RandomState(seed)
+        splits = np.stack([rs.permutation(n) for _ in range(int(ntest))])
+    splits = np.asarray(splits.detach().cpu().numpy() if hasattr(splits, "data_ptr") else splits)
+    if splits.ndim != 2 or splits.shape[1] != n or splits.shape[0] < 1:
+        raise ValueError(f"splits must be [ntest, n = {n}], got {splits.shape}")
+    if not (np.sort(splits, axis=1) == np.arange(n)).all():
+        raise ValueError("every row of splits must be a permutation of 0..n-1")
+    splits = np.ascontiguousarray(splits, np.int32)
+    train, test = np.ascontiguousarray(splits[:, :ntr]), np.ascontiguousarray(splits[:, ntr:])
+    if hasattr(values, "data_ptr") and values.is_cuda:
+        import torch
+        train, test = (torch.from_numpy(t).to(values.device) for t in (train, test))
+    # each call also forms the row of all n samples (row 0), which is dropped: about 1 / (ntest rtrain) extra Gram work, small beside
+    # the host algebra below
+    kw = dict(logw=logw, n_boot=splits.shape[0], engine=engine)
+    Gtr = rff_gram_wide(values, omega, indices=train, **kw)[1:]
+    Gte = rff_gram_wide(values, omega, indices=test, **kw)[1:]
+    d, W, r = gedmd_spectrum(Gtr, omega, a, nev, tol, solver="host")
+    return GedmdCvResult(d, gedmd_vamp_score(Gte, omega, a, W), r)
+
+
+def gedmd_model_selection(values, sigmas, ps, a, nev, tol=0.0, seed=0, rtrain=0.75, ntest=20, logw=None, engine=None):
+    """The double loop of the reference's adw/analysis/model_selection.py and mdqm9/analysis/model_selection.py: ``gedmd_cv`` at every
+    (sigma, p) of the grid, Omega drawn per grid point by ``sample_rff_gaussian``(d, p, sigma, seed) and the splits by `seed`.
+    Returns (EV [len(sigmas), len(ps), ntest, nev], VAMP [len(sigmas), len(ps), ntest])."""
+    sigmas, ps = list(sigmas), [int(p) for p in ps]
+    d = 1 if len(values.shape) == 1 else int(values.shape[1])
+    EV, VAMP = np.zeros((len(sigmas), len(ps), int(ntest), int(nev))), np.zeros((len(sigmas), len(ps), int(ntest)))
+    for i, sigma in enumerate(sigmas):
+        for j, p in enumerate(ps):
+            cv = gedmd_cv(values, sample_rff_gaussian(d, p, float(sigma), seed), a, nev, tol, rtrain, ntest, seed, logw=logw, engine=engine)
+            EV[i, j], VAMP[i, j] = cv.eigenvalues, cv.scores
+    return EV, VAMP
 
 
 def _neg_phi(*terms):
