@@ -518,6 +518,10 @@ int ti_painn_debug_poison(ti_handle* h, int64_t B, float value);
  * -1 = no evaluation yet.  *n_classes (may be NULL): classes found by the call's class pass (TI_PHI0_MAX_CLASSES + 1: more than the
  * cap), 0 when the call ran none. */
 int ti_painn_debug_phi0_path(ti_handle* h, int32_t* n_classes);
+/* The pair-major template of the handle: molecules per group, row blocks per group, and how many of them -- the
+ * leading ones -- are 4 x 4 tiles; the rest are general blocks of 16 unrelated pairs (n_tile == nblk: none, e.g. with TI_PAIR_PACKED=0
+ * in the environment when the handle was created).  Returns 1, or 0 when the handle has no pair template (nothing is written). */
+int ti_painn_debug_pair_blocks(ti_handle* h, int32_t* G, int32_t* nblk, int32_t* n_tile);
 /* Device self-test of the MFMA operand/accumulator lane maps the kernels rely on, of both fp32 -> (hi, lo) fp16 operand splits
  * (the 8-instruction forms of formats (a) and (b) against the plain arithmetic, bit for bit, fp16-subnormal residuals included),
  * and of the fp16 matrix instruction keeping subnormal inputs. */

@@ -242,6 +242,16 @@ int ti_painn_debug_phi0_path(ti_handle* h, int32_t* n_classes)
     return h->phi0_last;
 }
 
+int ti_painn_debug_pair_blocks(ti_handle* h, int32_t* G, int32_t* nblk, int32_t* n_tile)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (!h->has_pair) return 0;
+    if (G) *G = h->tpl[2].G;
+    if (nblk) *nblk = h->tpl[2].nblk;
+    if (n_tile) *n_tile = h->tpl[2].n_tile;
+    return 1;
+}
+
 int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)
 {
     if (!h || h->kind != 0 || B <= 0) return fail(TI_E_ARG, "not a painn handle / B");

@@ -243,7 +243,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
             EdgeParams p{};
             p.stream = h->S(h->st_edge[l]); p.nch = h->st_edge[l].nch; p.vecs = h->edge_vecs.p + (size_t)l * 21 * F;
             p.edge_emb = h->F(h->edge_emb); p.rows = h->rows.p; p.slotnode = h->slotnode.p; p.nslots = nullptr;
-            p.nblk = h->nblk; p.G = h->G; p.parts = h->parts; p.A = A; p.max_slots = h->max_slots; p.B = B; p.n_groups = groups; p.length_scale = h->d.length_scale;
+            p.nblk = h->nblk; p.n_tile = h->n_tile; p.G = h->G; p.parts = h->parts; p.A = A; p.max_slots = h->max_slots; p.B = B; p.n_groups = groups; p.length_scale = h->d.length_scale;
             p.x = x_dev; p.P = h->P.p; p.v = h->v.p; p.dsacc = h->dsacc.p; p.dvacc = h->dvacc.p; p.cacc = h->cacc.p; p.e = h->e.p; p.enc = h->enc.p; p.geo = h->geo.p;
             for (int i = 0; i < 6; ++i) p.wscale[i] = 1.0f;
             if (edge_one_chain(prec)) {     // the message kernel's own stream format (the primal pass of the divergence keeps the other one)

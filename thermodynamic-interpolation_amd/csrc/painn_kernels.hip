@@ -495,7 +495,10 @@ hipError_t configure_painn_kernels(int NB)
         constexpr int nb = decltype(bc)::value;
         constexpr bool MASK = decltype(mc)::value;
         hipError_t e = configure_edge_unit<nb, MASK>();
-        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) { if (e == hipSuccess) e = configure_pair_unit<nb, MASK>(); }
+        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) {
+            if (e == hipSuccess) e = configure_pair_unit<nb, MASK, false>();
+            if constexpr (!MASK) { if (e == hipSuccess) e = configure_pair_unit<nb, false, true>(); }
+        }
         return e;
     });
 }
@@ -518,8 +521,15 @@ hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams
 {
     return with_message_units(NB, masked, [&](auto bc, auto mc) {
         constexpr int nb = decltype(bc)::value;
-        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) return launch_pair_unit<nb, decltype(mc)::value>(first, last, prec, p, st, table);
-        else return hipErrorInvalidValue;
+        if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) {
+            hipError_t e = p.n_tile > 0 ? launch_pair_unit<nb, decltype(mc)::value, false>(first, last, prec, p, st, table) : hipSuccess;
+            if (e == hipSuccess && p.n_tile < p.nblk) {      // the general blocks: one kernel for shared and per-group row words
+                EdgeParams g = p;
+                g.row_stride = masked ? p.nblk * 16 : 0;
+                e = launch_pair_unit<nb, false, true>(first, last, prec, g, st, table);
+            }
+            return e;
+        } else return hipErrorInvalidValue;
     });
 }
 

@@ -240,9 +240,14 @@ void build_templates(ti_handle* h, const int32_t* src, const int32_t* dst, const
 bool build_pair_template(ti_handle* h, const int32_t* src, const int32_t* dst, const int32_t* etype)
 {
     ti::PairTemplate pt;
-    if (!ti::build_pair_template(h->d.n_atoms, h->d.n_edges, src, dst, etype, pt, h->first_touch)) return false;
+    // triage switch, read like TI_PHI0_TABLE: TI_PAIR_PACKED=0 at creation keeps the tile-only template
+    bool packed = ti::pair_general_build_exists(h->d.precision);      // (f32 handles: the tile-only template, ti_internal.hpp)
+    if (const char* z = std::getenv("TI_PAIR_PACKED")) if (z[0] == '0') packed = false;
+    const bool ok = packed ? ti::build_pair_template_packed(h->d.n_atoms, h->d.n_edges, src, dst, etype, pt, h->first_touch)
+                           : ti::build_pair_template(h->d.n_atoms, h->d.n_edges, src, dst, etype, pt, h->first_touch);
+    if (!ok) return false;
     ti_handle::Tpl& T = h->tpl[2];
-    T.G = pt.G; T.P = 1; T.nblk = pt.nblk; T.max_slots = 4;
+    T.G = pt.G; T.P = 1; T.nblk = pt.nblk; T.n_tile = pt.n_tile; T.max_slots = 4;
     T.rows.upload(pt.rows); T.slotnode.upload(pt.slotnode); T.rows_h = pt.rows;
     h->pair_pos = pt.pair_pos; h->pair_fill = pt.fill;
     return true;
@@ -267,11 +272,13 @@ int template_for(const ti_handle* h, long long B, bool allow_pair)
     if (h->n_tpl > 1) dir_pick = (B + h->tpl[0].G - 1) / h->tpl[0].G < 1024 ? 1 : 0;
     const bool pair_ok = h->has_pair && allow_pair && !mask_blocks_pair(h);
     // pair-major rows once they fill the chip (one wave per group of G molecules) and cost less than the directed rows: a pair block
-    // runs 84 chunk products for 16 pairs where a directed block runs 56 for 16 edges, at half the weight-chunk visits per edge
+    // runs 84 chunk products for 16 pairs where a directed block runs 56 for 16 edges, at half the weight-chunk visits per edge; a
+    // general block counts PAIR_GENERAL_WEIGHT tile blocks (pair_template.hpp)
     int pick = dir_pick;
     if (pair_ok) {
         const ti_handle::Tpl &T = h->tpl[2], &D = h->tpl[0];
-        if ((B + T.G - 1) / T.G >= 1024 && 1.5 * T.nblk / T.G <= (double)D.nblk / D.G) pick = 2;
+        const double pair_blocks = T.n_tile + ti::pair_detail::PAIR_GENERAL_WEIGHT * (T.nblk - T.n_tile);
+        if ((B + T.G - 1) / T.G >= 1024 && 1.5 * pair_blocks / T.G <= (double)D.nblk / D.G) pick = 2;
     }
     const int want = pinned_template(h);
     if (want == TI_TEMPLATE_THROUGHPUT) pick = 0;
@@ -289,7 +296,7 @@ void select_template(ti_handle* h, long long B, bool allow_pair)
         throw Unsupported("the pair layout is pinned, and the edge mask in force is not symmetric for every molecule");
     const int pick = template_for(h, B, allow_pair);
     const ti_handle::Tpl& T = h->tpl[pick];
-    h->active = pick; h->G = T.G; h->parts = T.P; h->nblk = T.nblk; h->rows.p = T.rows.p; h->slotnode.p = T.slotnode.p;
+    h->active = pick; h->G = T.G; h->parts = T.P; h->nblk = T.nblk; h->n_tile = pick == 2 ? T.n_tile : T.nblk; h->rows.p = T.rows.p; h->slotnode.p = T.slotnode.p;
     h->max_slots = T.max_slots;
 }
 

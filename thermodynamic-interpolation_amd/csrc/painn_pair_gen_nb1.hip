@@ -1,0 +1,7 @@
+// painn_pair_gen_nb1.hip -- pair-major message kernel instantiations of the general-block builds for n_features = 32 (painn_pair_kernel.hpp)
+#include "painn_pair_kernel.hpp"
+
+namespace ti {
+template hipError_t configure_pair_unit<1, false, true>();
+template hipError_t launch_pair_unit<1, false, true>(bool, bool, int, const EdgeParams&, hipStream_t, bool);
+}  // namespace ti

@@ -22,7 +22,10 @@
 //     per lane, no atomics.
 // Per 32 directed edges: 84 chunk products and 56 chunk visits instead of 112 and 112, six LayerNorm / SiLU / operand-split phases
 // instead of eight.  What it costs: 4 x 4 tiles cover a complete graph of A atoms with (A - 1) / (4 * ceil((A - 1) / 4)) of their rows
-// at best (painn_pack.hip: build_pair_template; 85 % for 18 atoms), and every atom's accumulators are touched from ~ (A - 1) / 4 blocks.
+// at best (pair_template.hpp: build_pair_template; 85 % for 18 atoms), and every atom's accumulators are touched from ~ (A - 1) / 4
+// blocks.  The packed template (build_pair_template_packed) therefore ends with GENERAL blocks -- 16 unrelated pairs, walked by the
+// GENERAL builds below in a launch of their own right after the tile launch -- and reaches 98 % for 18 atoms (36 full tiles and 3
+// general blocks per group of 4 molecules instead of 45 tiles).
 // Results are deterministic (one wave owns a group of molecules, fixed order); they differ from the directed kernel's by the order
 // of the per-atom sums only.
 #pragma once
@@ -37,10 +40,11 @@ __host__ __device__ constexpr int pair_superchunk(int NB = 0, int WAVES = 0, boo
 // + the builds that fold the cross term (pair_folds_cross): per wave, the 12 dv sums of every lane parked across the cross-gate products.
 // At F = 128 that costs the 4-wave build its second workgroup per CU (87.5 KB); it runs below 2048 groups, where a launch has at most
 // two workgroups per CU to place.
-static size_t pair_lds_bytes(int NB, int WAVES, int PREC, bool TABLE = false)
+// (the GENERAL builds park their eight gate / scale products per lane instead: 32 floats)
+static size_t pair_lds_bytes(int NB, int WAVES, int PREC, bool TABLE = false, bool GENERAL = false)
 {
     return (size_t)2 * pair_superchunk(NB, WAVES, TABLE) * edge_chunk4(NB, false) * 16 + WAVES * 256 + 21 * (size_t)32 * NB * 4 +
-           (pair_folds_cross(PREC) && !TABLE ? (size_t)WAVES * 12 * 64 * 4 : 0);
+           (pair_folds_cross(PREC) && !TABLE ? (size_t)WAVES * (GENERAL ? 32 : 12) * 64 * 4 : 0);
 }
 
 // TABLE (layer 0 only, the split path: pair_table_build_exists): the phi branch of layer 0 does not see the coordinates, so its three
@@ -49,8 +53,10 @@ static size_t pair_lds_bytes(int NB, int WAVES, int PREC, bool TABLE = false)
 template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS p.rows
+#define TI_PAIR_GENERAL false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
+#undef TI_PAIR_GENERAL
 
 // Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words PER group (painn_pack.hip: masked_rows), in which a pair absent
 // from its molecule is invalid -- zeroed through the shared w factor, like a pair that does not exist.  Both directions share that
@@ -59,25 +65,42 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(c
 template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_mask_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS (p.rows + (size_t)gi * p.nblk * 16)
+#define TI_PAIR_GENERAL false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
+#undef TI_PAIR_GENERAL
+
+// The general blocks [p.n_tile, p.nblk) of a packed template (pair_template.hpp), every row adding to its own two atoms; the two kernels
+// above walk the tile blocks [0, p.n_tile).  Same body, same weight stream (cyclic per row block), same e / enc / geo rows.  One kernel
+// for both kinds of row words: p.row_stride is 0 with the template's shared rows and nblk * 16 with an edge mask's per-group rows.
+template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
+__global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_general_kernel(const EdgeParams p)
+#define TI_PAIR_ROWS (p.rows + (size_t)gi * p.row_stride)
+#define TI_PAIR_GENERAL true
+#include "painn_pair_kernel_body.inc"
+#undef TI_PAIR_ROWS
+#undef TI_PAIR_GENERAL
 
 // The visitor of the family: f(kernel, waves, LDS bytes) for every build of width NB that the values select (EVERY: all of them,
-// dispatch.hpp), until one returns an error.  MASK: the masked twins (painn_pair_mask_kernel).  hipErrorInvalidValue: no such build.
-template <int NB, bool MASK, class F>
+// dispatch.hpp), until one returns an error.  MASK: the masked twins (painn_pair_mask_kernel).  GENERAL: the builds of the general
+// blocks (painn_pair_general_kernel, one per unmasked tile build of the split path; MASK is then false).  hipErrorInvalidValue: no such
+// build.
+template <int NB, bool MASK, bool GENERAL, class F>
 static hipError_t with_pair_builds(int waves, int prec, int pos, F&& f)
 {
+    static_assert(!(MASK && GENERAL), "the general kernel takes masked row words through p.row_stride");
     hipError_t e = hipSuccess;
     bool any = false;
     dispatch_int<4, 8>(waves, [&](auto wc) { dispatch_int<0, 1>(prec, [&](auto pc) {
         constexpr int WAVES = decltype(wc)::value, PREC = decltype(pc)::value;
-        if constexpr (pair_build_exists(NB, WAVES, PREC))
+        if constexpr (pair_build_exists(NB, WAVES, PREC) && (!GENERAL || pair_general_build_exists(PREC)))
             dispatch_int<POS_MIDDLE, POS_FIRST, POS_LAST, POS_ONLY, POS_FIRST_TABLE, POS_ONLY_TABLE>(pos, [&](auto oc) {
                 constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0, TABLE = (decltype(oc)::value & 4) != 0;
                 if constexpr (!TABLE || pair_table_build_exists(NB, PREC, MASK)) {
                     any = true;
                     if (e != hipSuccess) return;
-                    if constexpr (MASK) e = f(painn_pair_mask_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
+                    if constexpr (GENERAL) e = f(painn_pair_general_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE, true));
+                    else if constexpr (MASK) e = f(painn_pair_mask_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
                     else e = f(painn_pair_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE));
                 }
             });
@@ -86,18 +109,20 @@ static hipError_t with_pair_builds(int waves, int prec, int pos, F&& f)
 }
 
 // one feature width (ti_internal.hpp): configure every build / launch the one the call needs
-template <int NB, bool MASK>
+template <int NB, bool MASK, bool GENERAL>
 hipError_t configure_pair_unit()
 {
-    return with_pair_builds<NB, MASK>(EVERY, EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
+    return with_pair_builds<NB, MASK, GENERAL>(EVERY, EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
 }
-template <int NB, bool MASK>
+// (GENERAL: the launch over the general blocks, the same grid right after the tile launch on the same stream)
+template <int NB, bool MASK, bool GENERAL>
 hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table)
 {
     if (table && !first) return hipErrorInvalidValue;
+    if (p.n_tile < 0 || p.n_tile > p.nblk || (GENERAL && p.n_tile == p.nblk)) return hipErrorInvalidValue;
     // 8-wave workgroups (one weight stream per CU) for the split path once every CU gets a workgroup
     const bool wide = prec == 1 && p.n_groups >= 2048;
-    return with_pair_builds<NB, MASK>(wide ? 8 : 4, prec, layer_pos(first, last) | (table ? POS_TABLE : 0), [&](auto kernel, int waves, size_t lds) {
+    return with_pair_builds<NB, MASK, GENERAL>(wide ? 8 : 4, prec, layer_pos(first, last) | (table ? POS_TABLE : 0), [&](auto kernel, int waves, size_t lds) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)((p.n_groups + waves - 1) / waves)), dim3(64 * waves), lds, st, p);      // one wave = one group of G molecules
         return hipGetLastError();
     });

@@ -1,9 +1,14 @@
 // painn_pair_kernel_body.inc -- the body of the pair-major message kernel (painn_pair_kernel.hpp), included once for painn_pair_kernel
-// and once for its masked twin painn_pair_mask_kernel.  TI_PAIR_ROWS: the wave's row words -- the template's in the first; its own
+// and once for its masked twin painn_pair_mask_kernel, and once for painn_pair_general_kernel (TI_PAIR_GENERAL).  TI_PAIR_ROWS: the wave's row words -- the template's in the first; its own
 // group's in the second, whose per-group row words mark pairs absent from their molecule invalid (w factor 0, like missing pairs).
+// GENERAL: the build that walks the template's general blocks [n_tile, nblk) -- 16 unrelated pairs, no slots -- after the tile build
+// has walked [0, n_tile) (pair_template.hpp).  Everything up to the output products is per row and shared; the output stage then adds
+// every row's contributions of both directions to the row's own two atoms instead of forming slot sums.
 {
     static_assert(PREC == 0 || PREC == 1, "the fp16 storage mode keeps the directed message kernel");
     static_assert(!TABLE || (FIRST && PREC == 1), "the phi table serves layer 0 of the split path");
+    constexpr bool GENERAL = TI_PAIR_GENERAL;
+    static_assert(!GENERAL || pair_general_build_exists(PREC), "general blocks: the split path, which folds the cross term (the f32 path keeps the tile-only template)");
     constexpr int F = 16 * NBK, NB = (F + 31) / 32, T = 64 * WAVES, CH4 = edge_chunk4(NB, false);
     using A16 = r16::Act<NBK>;
     constexpr bool ONE = edge_one_chain(PREC);
@@ -11,6 +16,7 @@
     extern __shared__ f32x4 lds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 15, q = lane >> 4;
     constexpr int SC = pair_superchunk(NB, WAVES, TABLE), NBUF = 2;                 // two superchunks in LDS (PipeDMA)
+    const int blk_lo = GENERAL ? p.n_tile : 0, blk_hi = GENERAL ? p.nblk : p.n_tile;
     float* scratch = reinterpret_cast<float*>(lds + NBUF * SC * CH4) + wave * 64;  // [16 pair rows][4] edge_dir of direction A
     float* vec = reinterpret_cast<float*>(lds + NBUF * SC * CH4) + WAVES * 64;     // [EV::COUNT][F]
     for (int i = threadIdx.x; i < EV::COUNT * F / 4; i += T)
@@ -64,7 +70,7 @@
 #define TI_STAMP() do { } while (0)
 #endif
 
-    for (int blk = 0; blk < p.nblk; ++blk) {
+    for (int blk = blk_lo; blk < blk_hi; ++blk) {
         TI_STAMP();
         // ---- K1 geometry of this lane's pair row (the 4 quarters compute the same row); direction A: r = x[I] - x[J]
         const uint32_t meta = TI_PAIR_ROWS[blk * 16 + j];
@@ -203,6 +209,29 @@
         auto acc_ptr = [&](unsigned lnode, int off) {
             return off < F ? ds_g + (lnode * (unsigned)F + (unsigned)off) : off < 4 * F ? dv_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - F)) : c_g + (lnode * (unsigned)(3 * F) + (unsigned)(off - 4 * F));
         };
+        // GENERAL: the two atoms of each of the lane's four rows -- sources of directions A and B, each the other's destination -- and
+        // whether the row adds anything: it exists (masked twin: in its molecule) and its molecule is one of the batch
+        unsigned gI[4], gJ[4];
+        bool gok[4];
+        if constexpr (GENERAL) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                gI[r] = lnode_of(prow_molI(mi[r]), prow_atomI(mi[r])); gJ[r] = lnode_of(prow_molJ(mi[r]), prow_atomJ(mi[r]));
+                gok[r] = group_ok && (mi[r] & 1u) != 0 && gi * p.G + prow_molI(mi[r]) < p.B;
+            }
+        }
+        // both directions of the lane's four rows: direction A's value goes to the row's J atom, direction B's to its I atom, plain adds
+        // (a general row never carries first touch: both atoms own a slot of an earlier tile block)
+        auto put_rows = [&](const f32x4& a0, const f32x4& a1, const f32x4& b0, const f32x4& b1, int off) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (gok[r]) {
+                    float* dA = acc_ptr(gJ[r], off);
+                    float* dB = acc_ptr(gI[r], off);
+                    acc_out(dA, a0[r], false); acc_out(dA + 16, a1[r], false);
+                    acc_out(dB, b0[r], false); acc_out(dB + 16, b1[r], false);
+                }
+        };
         const unsigned lIq = lnode_of(prow_molI(mi[0]), prow_atomI(mi[0]));      // source of direction A for all four rows of this lane
         // TABLE: the table rows of this lane's values.  Flipped layout: the four pair rows 4q + r, source I[q] for direction A and J[r]
         // for direction B (a loose block mixes molecules, hence classes, inside one lane: every row has its own offset); row layout
@@ -276,7 +305,7 @@
         // the cross-gate slice folded into dv (pair_folds_cross, ti_internal.hpp): the split path, which holds v[dst] of both directions
         // in registers; layer 0 has no such slice.  The f32 path sums cg * dir into cacc for the update kernel to cross.
         constexpr bool FOLD = pair_folds_cross(PREC) && !FIRST;
-        f32x4* const zpark = reinterpret_cast<f32x4*>(vec + EV::COUNT * F) + wave * 3 * 64 + lane;     // FOLD: [3][64 lanes] f32x4 per wave
+        f32x4* const zpark = reinterpret_cast<f32x4*>(vec + EV::COUNT * F) + wave * (GENERAL ? 8 : 3) * 64 + lane;     // FOLD: [3][64 lanes] f32x4 per wave (GENERAL: [8])
         static_assert(!FOLD || GATHER_EARLY, "the fold crosses with the v[dst] rows that the early gathers hold");
         const unsigned lJq = snJ >= 0 ? lnode_of(slot_mol(snJ), snJ & 255) : lIq;   // J slot q's atom: lane row q fetches it for all four
         const float wrow = (meta & 1u) ? inv_out : 0.0f;                 // the same row factor in the row layout (lane (j, q): row j)
@@ -303,8 +332,11 @@
             {   // ds: invariant message, summed over incoming edges
                 f32x4 a0, a1, b0, b1;
                 out3(2, nbo, a0, a1, b0, b1);
-                emitA(a0, a1, fo);
-                emitB(b0, b1, fo);
+                if constexpr (GENERAL) put_rows(a0, a1, b0, b1, fo);
+                else {
+                    emitA(a0, a1, fo);
+                    emitB(b0, b1, fo);
+                }
             }
             TI_STAMP();
             if constexpr (!LAST) {
@@ -343,7 +375,68 @@
                 }
             }
             TI_STAMP();
-            {   // equivariant message: sum_e (sed * dir_e + gates * v[src_e]) -> dvacc ; sum_e cg * dir_e -> cacc, or folded into dvacc
+            if constexpr (GENERAL) {
+                // equivariant message, row by row: sed * dir + gates * v[src] + cg * dir x v[dst] (layer 0: the first term alone) of both
+                // directions to dvacc of the row's two atoms.  The gate and scale products wait in LDS while the cross-gate products
+                // run, like the dv sums of the tile build.
+                f32x4 sA0, sA1, sB0, sB1, gA0 = {0, 0, 0, 0}, gA1 = {0, 0, 0, 0}, gB0 = {0, 0, 0, 0}, gB1 = {0, 0, 0, 0};
+                f32x4 cA0 = {0, 0, 0, 0}, cA1 = {0, 0, 0, 0}, cB0 = {0, 0, 0, 0}, cB1 = {0, 0, 0, 0};
+                out3(1, nbo, sA0, sA1, sB0, sB1);
+                if (!FIRST) out3(0, nbo, gA0, gA1, gB0, gB1);
+                if constexpr (FOLD) {
+                    zpark[0] = sA0; zpark[64] = sA1; zpark[128] = sB0; zpark[192] = sB1;
+                    zpark[256] = gA0; zpark[320] = gA1; zpark[384] = gB0; zpark[448] = gB1;
+                    out3(4, nbo, cA0, cA1, cB0, cB1);
+                    sA0 = zpark[0]; sA1 = zpark[64]; sB0 = zpark[128]; sB1 = zpark[192];
+                    gA0 = zpark[256]; gA1 = zpark[320]; gB0 = zpark[384]; gB1 = zpark[448];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const f32x4 dir = *reinterpret_cast<const f32x4*>(scratch + (4 * q + r) * 4);     // direction A's; B's is its negative
+                    float vI[3][2] = {}, vJ[3][2] = {};
+                    if (!FIRST) {
+                        const float* vp = v_g + (gI[r] * (unsigned)(3 * F) + (unsigned)fo);
+                        const float* vq = v_g + (gJ[r] * (unsigned)(3 * F) + (unsigned)fo);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { vI[c][0] = vp[c * F]; vI[c][1] = vp[c * F + 16]; vJ[c][0] = vq[c * F]; vJ[c][1] = vq[c * F + 16]; }
+                    }
+                    float zA[3][2], zB[3][2];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        zA[c][0] = sA0[r] * dir[c]; zA[c][1] = sA1[r] * dir[c];
+                        zB[c][0] = -(sB0[r] * dir[c]); zB[c][1] = -(sB1[r] * dir[c]);
+                        if (!FIRST) {
+                            zA[c][0] = fmaf(gA0[r], vI[c][0], zA[c][0]); zA[c][1] = fmaf(gA1[r], vI[c][1], zA[c][1]);
+                            zB[c][0] = fmaf(gB0[r], vJ[c][0], zB[c][0]); zB[c][1] = fmaf(gB1[r], vJ[c][1], zB[c][1]);
+                        }
+                    }
+                    if constexpr (FOLD) {
+                        float kA[3][2], kB[3][2];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            kA[c][0] = cA0[r] * dir[c]; kA[c][1] = cA1[r] * dir[c];
+                            kB[c][0] = -(cB0[r] * dir[c]); kB[c][1] = -(cB1[r] * dir[c]);
+                        }
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+#pragma unroll
+                            for (int h = 0; h < 2; ++h) {     // torch.cross(edge_dir, v[dst]): dst J for direction A, I for direction B
+                                zA[c][h] += kA[c1][h] * vJ[c2][h] - kA[c2][h] * vJ[c1][h];
+                                zB[c][h] += kB[c1][h] * vI[c2][h] - kB[c2][h] * vI[c1][h];
+                            }
+                        }
+                    }
+                    if (gok[r])
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            float* dA = acc_ptr(gJ[r], (1 + c) * F + fo);
+                            float* dB = acc_ptr(gI[r], (1 + c) * F + fo);
+                            acc_out(dA, zA[c][0], false); acc_out(dA + 16, zA[c][1], false);
+                            acc_out(dB, zB[c][0], false); acc_out(dB + 16, zB[c][1], false);
+                        }
+                }
+            } else {   // equivariant message: sum_e (sed * dir_e + gates * v[src_e]) -> dvacc ; sum_e cg * dir_e -> cacc, or folded into dvacc
                 f32x4 sA0, sA1, sB0, sB1, gA0 = {0, 0, 0, 0}, gA1 = {0, 0, 0, 0}, gB0 = {0, 0, 0, 0}, gB1 = {0, 0, 0, 0};
                 out3(1, nbo, sA0, sA1, sB0, sB1);
                 float vI[3][2], vJ[3][2];                // v of I[q] (source of direction A for the lane's four rows) and of J[q]

@@ -2,6 +2,6 @@
 #include "painn_pair_kernel.hpp"
 
 namespace ti {
-template hipError_t configure_pair_unit<1, false>();
-template hipError_t launch_pair_unit<1, false>(bool, bool, int, const EdgeParams&, hipStream_t, bool);
+template hipError_t configure_pair_unit<1, false, false>();
+template hipError_t launch_pair_unit<1, false, false>(bool, bool, int, const EdgeParams&, hipStream_t, bool);
 }  // namespace ti

@@ -72,7 +72,7 @@ struct ti_handle {
 
     // ---- painn
     ti_painn_desc d{};
-    int NB = 0, nE = 0, ncond = 0, G = 1, nblk = 0;
+    int NB = 0, nE = 0, ncond = 0, G = 1, nblk = 0, n_tile = 0;
     MlpOff embed{}, readout{}; std::vector<MlpOff> phi, w, upd; std::vector<size_t> U, V;
     size_t edge_emb = 0, atom_emb = 0, Vr = 0; float b2_gate = 0.f;
     Stream st_embed16{}; std::vector<Stream> st_edge, st_edge1, st_update;      // st_edge1: the message kernel's one-accumulator format (TI_PREC_F16X2)
@@ -80,6 +80,7 @@ struct ti_handle {
     // G / P / nblk / rows / slotnode below are those of the ACTIVE one (select_template, once per API call)
     struct Tpl {
         int G = 1, P = 1, nblk = 0;
+        int n_tile = 0;                           // pair template: its leading tile blocks, the rest are general (pair_template.hpp)
         DevBuf<uint32_t> rows; DevBuf<int32_t> slotnode;
         std::vector<uint32_t> rows_h;             // host copy of `rows` (masked_rows)
         std::vector<int> part_of, part_start, part_len;     // per sorted edge: its part; per part: first sorted edge, edges
@@ -87,7 +88,8 @@ struct ti_handle {
         int max_slots = 0;                        // most destination atoms in any row block (<= EDGE_MAX_SLOTS)
     } tpl[3];
     // tpl[2]: the pair-major template (ti_internal.hpp; painn_pair_kernel.hpp), built when the graph is symmetric and the pair kernel
-    // exists for this width / precision.  pair_pos[(m * A + src) * A + dst] = e row of that directed edge of molecule-in-group m inside
+    // exists for this width / precision: the packed one (tile blocks, then general blocks), or with TI_PAIR_PACKED=0 in the environment
+    // at creation the tile-only one of before (same-binary A/B runs, triage).  pair_pos[(m * A + src) * A + dst] = e row of that directed edge of molecule-in-group m inside
     // its group: (block * 2 + direction) * 16 + pair row
     bool has_pair = false; std::vector<int> pair_pos; double pair_fill = 0.0;
     int n_tpl = 1, active = 0, parts = 1, max_slots = 0, pinned_tpl = TI_TEMPLATE_AUTO;

@@ -42,7 +42,8 @@ __host__ __device__ inline int row_slot(uint32_t w) { return (w >> 18) & 63; }
 // laid out as a 4 x 4 tile: row 4a + b = pair (I[a], J[b]) of up to four "I" atoms and four "J" atoms (slots carry molecule-in-group and
 // atom; rows of pairs that do not exist are invalid).  Direction A is the edge I[a] -> J[b] (src I, dst J), direction B the edge
 // J[b] -> I[a].  The per-atom sums need no masks: direction B's destination is the same for the four rows a lane holds (in-lane adds),
-// direction A's is the same across the four lane rows (two lane-swap levels).
+// direction A's is the same across the four lane rows (two lane-swap levels).  A packed template (pair_template.hpp) ends with GENERAL
+// blocks: 16 unrelated pairs named by their row words alone, slot words -1, no first touch; every row adds to its own two atoms.
 //   row word : bit0 valid | molI<<1 (3b) | atomI<<4 (5b) | molJ<<9 (3b) | atomJ<<12 (5b) | etype<<17 (2b)     (empty slots: a safe atom)
 //   slot word: slotnode[blk*16 + k], k = 0..3 the I slots, k = 4..7 the J slots: -1, or atom | mol<<8
 // Per-atom sums: the wave that owns the group adds the sums of slot k of block b to the atom's accumulator rows with fire-and-forget
@@ -67,6 +68,8 @@ struct EdgeParams {
     const uint32_t* rows; const int32_t* slotnode; const int32_t* nslots;
     int nblk, G, parts, A;                  // parts per group (see above); n_groups counts parts
     int max_slots;                          // most destination atoms any row block of the template holds (<= 4)
+    int n_tile;                             // pair launches: blocks [0, n_tile) are tiles, [n_tile, nblk) general (== nblk: tiles only)
+    int row_stride;                         // the general pair launch: row words per group in `rows` (0: the template's, shared by all groups)
     long long B, n_groups;
     float length_scale;
     const float* x;                         // [B*A][3]
@@ -150,12 +153,16 @@ hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams
 __host__ __device__ constexpr bool edge_one_chain(int prec) { return prec == TI_PREC_F16X2; }
 // pair-major message kernel (painn_pair_kernel.hpp): same EdgeParams, rows / slotnode of the pair template, same weight stream
 // table: layer 0 on the phi table (p.phi0_tab / p.cls / p.wpad set, p.stream the w-only stream; first must hold, pair_table_build_exists)
+// Two launches when the template has general blocks (p.n_tile < p.nblk): the tile builds over [0, n_tile), then the general builds.
 hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false, bool table = false);
 // builds of the pair kernel (painn_pair_kernel.hpp): F <= 128; f32 on 4 waves, split fp16 on 4 and on 8
 __host__ __device__ constexpr bool pair_build_exists(int NB, int WAVES, int PREC)
 {
     return (NB == 1 || NB == 2 || NB == 4) && (PREC == TI_PREC_F32 ? WAVES == 4 : PREC == TI_PREC_F16X2 && (WAVES == 4 || WAVES == 8));
 }
+// the builds for the general blocks of a packed pair template (pair_template.hpp): the split path.  The f32 builds, short of registers
+// as they are, spill with eight destination atoms per lane (36 - 56 registers at F = 128): f32 handles keep the tile-only template.
+__host__ __device__ constexpr bool pair_general_build_exists(int PREC) { return PREC == TI_PREC_F16X2; }
 // the pair kernel at this precision adds (sum cg*dir) x v[dst] to dvacc itself, per row block and slot (painn_pair_kernel_body.inc,
 // FOLD), and leaves cacc alone: the update kernel after it must be the folded one (launch_update(.., folded = true)).  The split path
 // only: it holds v[dst] of both directions in registers.  Its 4- and 8-wave builds both fold, so that a slice of groups evaluated
@@ -170,8 +177,9 @@ hipError_t configure_painn_kernels(int NB);     // dynamic-LDS attributes
 // unit, reached from launch_edge / launch_pair / configure_painn_kernels (painn_kernels.hip).  No pair unit exists for NB = 8.
 template <int NB, bool MASK> hipError_t launch_edge_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
 template <int NB, bool MASK> hipError_t configure_edge_unit();
-template <int NB, bool MASK> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table);
-template <int NB, bool MASK> hipError_t configure_pair_unit();
+// (GENERAL: the builds that walk a packed template's general blocks, units painn_pair_gen_nb*.hip; MASK is false for them)
+template <int NB, bool MASK, bool GENERAL> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table);
+template <int NB, bool MASK, bool GENERAL> hipError_t configure_pair_unit();
 
 // ---- forward-mode derivative of the drift (painn_jvp_kernels.hip; virtual-molecule layout described there).
 // D = 3A and xdot == NULL: unit seeds (direction d -> atom d/3, component d%3); otherwise D explicit directions xdot [B][D][A][3]

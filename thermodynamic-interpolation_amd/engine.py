@@ -655,6 +655,14 @@ class PainnEngine(_Engine):
         path = _lib.lib().ti_painn_debug_phi0_path(self.h, _lib.iptr(n))
         return int(path), int(n[0])
 
+    def debug_pair_blocks(self):
+        """(G, nblk, n_tile) of the handle's pair-major template -- molecules per group, row blocks per group, leading tile blocks (the
+        rest are general blocks) -- or None when it has none."""
+        g, n, t = (np.zeros(1, np.int32) for _ in range(3))
+        if _lib.lib().ti_painn_debug_pair_blocks(self.h, _lib.iptr(g), _lib.iptr(n), _lib.iptr(t)) != 1:
+            return None
+        return int(g[0]), int(n[0]), int(t[0])
+
     def debug_read(self, what: str, B: int):
         """what: 's' | 'v' | 'e', or 'ts' | 'tv' | 'te' for the tangents of the last jvp() call."""
         shape = {"s": (B, self.A, self.F), "v": (B, self.A, 3, self.F), "e": (B, self.E, self.F)}[what[-1]]
