@@ -478,6 +478,55 @@ typedef struct { int32_t d, p, nev, reserved; double a, tol; } ti_gedmd_desc;   
    omega [d, p] fp64, host */
 int ti_obs_gedmd_spectrum(ti_handle* h, const double* gram, int64_t n_mat, const double* omega, const ti_gedmd_desc* g,
                           double* ev, double* vec, int32_t* rank, int mem);
+/* Force-field energies: the reduced potential energies the weight estimators above take (E0s, E1s of the reference's
+ * mdqm9/analysis/utils/ess.py:8-10), for what mdqm9/analysis/eval_energy.py evaluates one conformation at a time through OpenMM:
+ * the HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce and NonbondedForce (NoCutoff, vacuum) of
+ * forcefield.createSystem(topology), times 1 / (k_B N_A T).  Energies in kJ/mol, lengths in nm, angles in radians.  Positions are
+ * p = (double)x * to_nm.  The four term sums of a molecule:
+ *   bond     (i, j), (r0, k)                  E = k (r - r0)^2 / 2,  r = |p_j - p_i|
+ *   angle    (i, j, k), (theta0, k)           E = k (theta - theta0)^2 / 2,  theta the TI_OBS_ANGLE angle at j as acos of the cosine
+ *                                             u.v / (|u| |v|) clamped to [-1, 1] (u = p_i - p_j, v = p_k - p_j)
+ *   torsion  (i, j, k, l), (n, phase, k)      E = k (1 + cos(n phi - phase)),  phi the TI_OBS_TORSION angle, n an integer in 1..6
+ *   pair     row i (2A - i - 1) / 2 + (j - i - 1) of the dense table of all A (A - 1) / 2 pairs i < j, (qq, sigma, eps)
+ *                                             E = 4 eps ((sigma / r)^12 - (sigma / r)^6) + coulomb qq / r,  r = |p_j - p_i|
+ *            A row with qq == 0 and eps == 0 is skipped: it contributes exactly 0 and is never evaluated (the 1-2 and 1-3 exclusions
+ *            arrive in that form).  The Lennard-Jones part is formed as 4 eps s (s - 1), s = (sigma / r)^6, and only with eps > 0 and
+ *            sigma > 0; the Coulomb part only with qq != 0.  r = 0: a pair with a Lennard-Jones part is +inf (the wall wins over an
+ *            attractive charge product), a pair of charges alone is coulomb qq / 0.
+ * ti_obs_ff_set copies a force field for the handle's species into a painn handle (an adw handle: TI_E_ARG).  All tables are host
+ * memory, parameters fp64, indices int32: bond_idx [n_bonds][2], bond_par [n_bonds][2], angle_idx [n_angles][3], angle_par
+ * [n_angles][2], torsion_idx [n_torsions][4], torsion_par [n_torsions][3] (n as a double holding an integer), pair_par [n_pairs][3];
+ * a table whose count is 0 may be NULL.  desc == NULL clears the force field.  One force field is one species: a handle with
+ * ti_painn_set_molecules in force gets TI_E_UNSUPPORTED (here and in ti_obs_ff_energy).  TI_E_ARG, before any device work and with
+ * the force field in force left as it was: a count below 0 or above its TI_FF_MAX_* cap, n_pairs != A (A - 1) / 2 (so A <= 25), an
+ * index outside 0..A-1, a repeated atom within one term, a non-finite parameter or coulomb, sigma < 0 or eps < 0, n not an integer
+ * in 1..6, a NULL table with a positive count. */
+#define TI_FF_MAX_BONDS 64
+#define TI_FF_MAX_ANGLES 128
+#define TI_FF_MAX_TORSIONS 512
+#define TI_FF_MAX_PAIRS 300          /* A = 25; every table and four molecules' coordinates take about 25 KB of LDS */
+#define TI_FF_GAS_CONSTANT 0.00831446261815324      /* R = k_B N_A in kJ / (mol K) */
+typedef struct { int32_t n_bonds, n_angles, n_torsions, n_pairs; double coulomb; /* 138.935456: OpenMM's ONE_4PI_EPS0 */ } ti_ff_desc;
+int ti_obs_ff_set(ti_handle* h, const ti_ff_desc* desc, const int32_t* bond_idx, const double* bond_par, const int32_t* angle_idx,
+                  const double* angle_par, const int32_t* torsion_idx, const double* torsion_par, const double* pair_par);
+/* x [B,A,3] fp32 and T [B] fp32 (kelvin, one per molecule; NULL: none) and out_e [B], out_terms [B,4] fp64 (may be NULL):
+ * [host|device] by mem.  out_terms[b] = the bond, angle, torsion and pair sums of molecule b in kJ/mol, each divided by
+ * R T_b (R = TI_FF_GAS_CONSTANT, the product in fp64) when T is given; out_e[b] = ((bond + angle) + torsion) + pair of those four.
+ * One wave per molecule, four molecules per 256-thread workgroup; a workgroup stages the tables in LDS once and loops over its
+ * molecules, whose positions go to LDS as fp64 nm.  Lane l adds terms l, l + 64, ... of a table in that order, the 64 lane sums are
+ * combined by a fixed butterfly; fp64 sqrt, acos, atan2, cos and division; no atomics.  A molecule's outputs are a function of its
+ * coordinates, to_nm, T_b and the tables only -- not of its place in the batch, of B, of mem, or of how the batch is cut into
+ * workgroups -- and a call repeats bit for bit.  Degenerate geometry is not an error: see r = 0 above; a NaN coordinate gives NaN
+ * for that molecule only.
+ * TI_E_ARG, nothing written: a NULL or adw handle, no force field set, B < 0, a NULL x or out_e with B > 0, an unknown mem, a
+ * non-finite to_nm, T_b <= 0 or not finite (found on the device; the message names the first such index). */
+int ti_obs_ff_energy(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_e, double* out_terms, int mem);
+/* The log-weights of the TI map from reduced energies: out_logw[b] = -(u1[b] - u0[b] + neg_dlogp[b]) (the reference's weight is
+ * exp(-(E1 - E0 + neg_dlogp)), ess.py:8-10), formed in fp64 as ((u1 - u0) + neg_dlogp) and rounded once to the fp32 that
+ * ti_obs_weights, ti_obs_hist, ti_obs_bootstrap and ti_obs_rff_gram take.  u0, u1 [B] fp64, neg_dlogp [B] fp32, out_logw [B] fp32:
+ * [host|device] by mem.  u0 == NULL: 0 (the calc_phis_bg form); neg_dlogp == NULL: 0.  Non-finite inputs pass through: the
+ * consumers refuse them by index.  Any handle.  TI_E_ARG: a NULL handle, u1 or out_logw, B < 1, an unknown mem. */
+int ti_obs_ti_logw(ti_handle* h, const double* u0, const double* u1, const float* neg_dlogp, int64_t B, float* out_logw, int mem);
 /* Observer: with one attached, every rollout entry point (ti_painn_rollout, _dlogp, _dlogp_est, ti_adw_rollout, _dlogp) also
  * evaluates the K CVs on the state at the grid points i with i % every == 0 and at the last one -- ti_rollout_rows(n_step, every)
  * rows, whatever save_every is -- and writes them to out_cv [rows, B, K] fp32 ([host|device] by mem; the caller sizes it for the

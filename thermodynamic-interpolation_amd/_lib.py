@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "ti_obs_rff_gram",
     "ti_obs_eigh", "ti_obs_gedmd_spectrum",
     "ti_obs_rff_gram_wide",
+    "ti_obs_ff_set", "ti_obs_ff_energy", "ti_obs_ti_logw",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -54,6 +55,9 @@ GRAM_MAX_D, GRAM_MAX_P, GRAM_MAX_TABLE = 16, 128, 1 << 27
 GRAM_WIDE_MAX_P = 1024
 # ti_obs_eigh / ti_obs_gedmd_spectrum: the largest matrix order (TI_EIGH_MAX_N), the sweep cap, the most matrices of a call
 EIGH_MAX_N, EIGH_MAX_SWEEPS, EIGH_MAX_MATRICES = 64, 64, BOOT_MAX_RESAMPLES + 1
+# ti_obs_ff_set: the caps of the four tables (TI_FF_MAX_*), R in kJ / (mol K) (TI_FF_GAS_CONSTANT), OpenMM's ONE_4PI_EPS0 in kJ nm / (mol e^2)
+FF_MAX_BONDS, FF_MAX_ANGLES, FF_MAX_TORSIONS, FF_MAX_PAIRS = 64, 128, 512, 300
+FF_GAS_CONSTANT, FF_COULOMB = 0.00831446261815324, 138.935456
 
 
 class PainnDesc(C.Structure):
@@ -83,6 +87,10 @@ class GramDesc(C.Structure):
 
 class GedmdDesc(C.Structure):
     _fields_ = [("d", C.c_int32), ("p", C.c_int32), ("nev", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("tol", C.c_double)]
+
+
+class FfDesc(C.Structure):
+    _fields_ = [("n_bonds", C.c_int32), ("n_angles", C.c_int32), ("n_torsions", C.c_int32), ("n_pairs", C.c_int32), ("coulomb", C.c_double)]
 
 
 class TiError(RuntimeError):
@@ -176,6 +184,10 @@ def lib():
     L.ti_obs_rff_gram_wide.argtypes = L.ti_obs_rff_gram.argtypes
     L.ti_obs_eigh.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int]
     L.ti_obs_gedmd_spectrum.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_double), C.POINTER(GedmdDesc), vp, vp, vp, C.c_int]
+    dp = C.POINTER(C.c_double)
+    L.ti_obs_ff_set.argtypes = [vp, C.POINTER(FfDesc), ip, dp, ip, dp, ip, dp, dp]
+    L.ti_obs_ff_energy.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
+    L.ti_obs_ti_logw.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int]
     _lib = L
     return L
 

@@ -1,5 +1,5 @@
-// api_obs.hip -- observables (ti_obs_*): collective variables of a state, importance weights, weighted histograms, and the
-// observer a rollout writes CV rows through.
+// api_obs.hip -- observables (ti_obs_*): collective variables of a state, importance weights, weighted histograms, force-field
+// energies and the TI log-weights formed from them, and the observer a rollout writes CV rows through.
 #include "ti_handle.hpp"
 
 namespace {
@@ -459,6 +459,126 @@ int ti_obs_hist(ti_handle* h, const float* values, int64_t stride, const float* 
         HIP_CHECK(hipStreamSynchronize(st));
         std::copy(out.begin(), out.begin() + n_bins, out_hist);
         std::copy(out.begin() + n_bins, out.end(), out_tails);
+        return TI_OK;
+    });
+}
+
+int ti_obs_ff_set(ti_handle* h, const ti_ff_desc* desc, const int32_t* bond_idx, const double* bond_par, const int32_t* angle_idx,
+                  const double* angle_par, const int32_t* torsion_idx, const double* torsion_par, const double* pair_par)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (!desc) { h->ff_on = false; return TI_OK; }
+    if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
+    const int A = h->d.n_atoms;
+    const int n[4] = {desc->n_bonds, desc->n_angles, desc->n_torsions, desc->n_pairs};
+    const int cap[4] = {TI_FF_MAX_BONDS, TI_FF_MAX_ANGLES, TI_FF_MAX_TORSIONS, TI_FF_MAX_PAIRS};
+    const char* name[4] = {"bond", "angle", "torsion", "pair"};
+    const int32_t* idx[3] = {bond_idx, angle_idx, torsion_idx};
+    const double* par[4] = {bond_par, angle_par, torsion_par, pair_par};
+    for (int t = 0; t < 4; ++t) {
+        if (n[t] < 0 || n[t] > cap[t]) return fail(TI_E_ARG, std::string(name[t]) + " count " + std::to_string(n[t]) + " is outside 0.." + std::to_string(cap[t]));
+        if (n[t] > 0 && (!par[t] || (t < 3 && !idx[t]))) return fail(TI_E_ARG, std::string(name[t]) + " table is NULL");
+    }
+    if (n[3] != A * (A - 1) / 2) return fail(TI_E_ARG, "the pair table must hold all A (A - 1) / 2 = " + std::to_string(A * (A - 1) / 2) + " pairs, got " + std::to_string(n[3]));
+    if (!std::isfinite(desc->coulomb)) return fail(TI_E_ARG, "coulomb must be finite");
+    std::vector<int32_t> words; std::vector<double> pars;
+    for (int t = 0; t < 3; ++t) {                              // bonds (2 atoms, 2 parameters), angles (3, 2), torsions (4, 3)
+        const int na = 2 + t, np = t == 2 ? 3 : 2;
+        for (int k = 0; k < n[t]; ++k) {
+            const std::string what = std::string(name[t]) + " " + std::to_string(k);
+            const int32_t* a = idx[t] + (size_t)na * k;
+            const double* q = par[t] + (size_t)np * k;
+            int32_t w = 0;
+            for (int s = 0; s < na; ++s) {
+                if (a[s] < 0 || a[s] >= A) return fail(TI_E_ARG, what + ": atom index outside 0.." + std::to_string(A - 1));
+                for (int s2 = 0; s2 < s; ++s2)
+                    if (a[s2] == a[s]) return fail(TI_E_ARG, what + ": atom " + std::to_string(a[s]) + " is repeated");
+                w |= a[s] << (5 * s);
+            }
+            for (int s = 0; s < np; ++s)
+                if (!std::isfinite(q[s])) return fail(TI_E_ARG, what + ": non-finite parameter");
+            if (t == 2) {                                      // (n, phase, k): the periodicity goes into the word
+                if (q[0] != std::floor(q[0]) || q[0] < 1.0 || q[0] > 6.0) return fail(TI_E_ARG, what + ": the periodicity must be an integer in 1..6");
+                w |= (int32_t)q[0] << 20;
+                pars.push_back(q[1]); pars.push_back(q[2]);
+            } else {
+                pars.push_back(q[0]); pars.push_back(q[1]);
+            }
+            words.push_back(w);
+        }
+    }
+    for (int i = 0, k = 0; i < A; ++i)                         // row i (2A - i - 1) / 2 + (j - i - 1)
+        for (int j = i + 1; j < A; ++j, ++k) {
+            const double* q = pair_par + 3 * (size_t)k;
+            const std::string what = "pair " + std::to_string(k) + " (" + std::to_string(i) + ", " + std::to_string(j) + ")";
+            if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2])) return fail(TI_E_ARG, what + ": non-finite parameter");
+            if (q[1] < 0.0 || q[2] < 0.0) return fail(TI_E_ARG, what + ": sigma and eps must be >= 0");
+            words.push_back(i | j << 5 | ((q[0] != 0.0 || q[2] != 0.0) ? FF_LIVE : 0));
+            pars.insert(pars.end(), q, q + 3);
+        }
+    return guarded([&]() -> int {
+        set_device(h);
+        h->ff_on = false;
+        h->ff_idx.upload(words);
+        h->ff_par.upload(pars);
+        std::copy(n, n + 4, h->ff_n);
+        h->ff_coulomb = desc->coulomb;
+        h->ff_on = true;
+        return TI_OK;
+    });
+}
+
+int ti_obs_ff_energy(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_e, double* out_terms, int mem)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 0 || (B > 0 && (!x || !out_e))) return fail(TI_E_ARG, "NULL buffer");
+    if (!std::isfinite(to_nm)) return fail(TI_E_ARG, "to_nm must be finite");
+    if (!h->ff_on) return fail(TI_E_ARG, "no force field set (ti_obs_ff_set)");
+    if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
+    if (B == 0) return TI_OK;
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const int A = h->d.n_atoms;
+        Staged sg(h, mem);
+        const float* xd = sg.in(x, h->obs_x, (size_t)B * 3 * A);
+        const float* Td = T ? sg.in(T, h->ff_T, (size_t)B) : nullptr;
+        if (Td) {                                      // refused before anything is written, the index found as ti_obs_weights finds its own
+            grow(h->obs_red, 4 + 259);
+            double bad = 0.0;
+            HIP_CHECK(launch_obs_ff_bad_temperature(h->obs_red.p, Td, B, st));
+            HIP_CHECK(hipMemcpyAsync(&bad, h->obs_red.p, sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            if (bad < (double)B) return fail(TI_E_ARG, "T must be finite and > 0: index " + std::to_string((long long)bad));
+        }
+        FfParams p{};
+        p.x = xd; p.T = Td; p.B = B; p.A = A; p.to_nm = to_nm; p.coulomb = h->ff_coulomb;
+        p.nb = h->ff_n[0]; p.na = h->ff_n[1]; p.nt = h->ff_n[2]; p.np = h->ff_n[3];
+        p.idx = h->ff_idx.p; p.par = h->ff_par.p;
+        p.e = sg.out(out_e, h->ff_e, (size_t)B);
+        p.terms = out_terms ? sg.out(out_terms, h->ff_terms, (size_t)B * 4) : nullptr;
+        HIP_CHECK(launch_obs_ff_energy(p, st));
+        sg.finish();
+        return TI_OK;
+    });
+}
+
+int ti_obs_ti_logw(ti_handle* h, const double* u0, const double* u1, const float* neg_dlogp, int64_t B, float* out_logw, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!u1 || !out_logw) return fail(TI_E_ARG, "NULL buffer");
+    return guarded([&]() -> int {
+        set_device(h);
+        Staged sg(h, mem);
+        const double* u0d = u0 ? sg.in(u0, h->ff_u0, (size_t)B) : nullptr;
+        const double* u1d = sg.in(u1, h->ff_u1, (size_t)B);
+        const float* nd = neg_dlogp ? sg.in(neg_dlogp, h->obs_val, (size_t)B) : nullptr;
+        float* od = sg.out(out_logw, h->obs_logw, (size_t)B);
+        HIP_CHECK(launch_obs_ti_logw(od, u0d, u1d, nd, B, h->stream));
+        sg.finish();
         return TI_OK;
     });
 }

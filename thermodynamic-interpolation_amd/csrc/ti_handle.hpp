@@ -162,6 +162,11 @@ struct ti_handle {
     // eigensolver and gEDMD algebra (ti_obs_eigh, ti_obs_gedmd_spectrum): the staged input of a host call; eigenvalues, eigenvectors and
     // status words of the first and second solve; K, the reduced matrices of one launch, the ranks; the results ahead of their validation
     DevBuf<double> eig_a, eig_w, eig_v, eig_w2, eig_v2, eig_k, eig_r, eig_ev, eig_vec; DevBuf<int32_t> eig_st, eig_st2, eig_rank;
+    // force field (ti_obs_ff_set; painn handles): the term words and parameters of the four tables as validated and packed by the
+    // host (ti_internal.hpp FfParams), their lengths (ff_on: a force field is in force); staging of a host call's temperatures,
+    // energies, term sums, reduced energies and log-weights (ti_obs_ff_energy, ti_obs_ti_logw)
+    bool ff_on = false; int ff_n[4] = {0, 0, 0, 0}; double ff_coulomb = 0.0;
+    DevBuf<int32_t> ff_idx; DevBuf<double> ff_par, ff_e, ff_terms, ff_u0, ff_u1; DevBuf<float> ff_T;
 
     ~ti_handle()
     {

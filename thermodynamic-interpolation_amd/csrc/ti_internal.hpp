@@ -398,6 +398,32 @@ hipError_t launch_obs_weights(float* w, const float* logw, const double* norm, l
 hipError_t launch_obs_whist(double* out, double* partial, const float* values, long long stride, const float* logw, const double* norm, long long B,
                             int n_bins, double lo, double hi, hipStream_t st);
 
+// ---- force-field energies (obs_ff_kernels.hip; include/ti_hip.h ti_obs_ff_*, ti_obs_ti_logw)
+// A term's atoms and flags in one word: i | j << 5 | k << 10 | l << 15 | n << 20 (torsion periodicity) | FF_LIVE (pair rows that are
+// evaluated).  The words of the four tables follow each other (bonds, angles, torsions, pairs), as do their parameters: bonds
+// [nb][2] (r0, k), angles [na][2] (theta0, k), torsions [nt][2] (phase, k), pairs [np][3] (qq, sigma, eps).
+constexpr int FF_WAVES = 4;                 // molecules in flight per 256-thread workgroup, one wave each
+constexpr int FF_MAX_ATOMS = 25;            // TI_FF_MAX_PAIRS = 25 * 24 / 2
+constexpr int32_t FF_LIVE = 1 << 24;
+__host__ __device__ inline int ff_atom(int32_t w, int slot) { return (w >> (5 * slot)) & 31; }
+__host__ __device__ inline int ff_period(int32_t w) { return (w >> 20) & 7; }
+struct FfParams {
+    const float* x;                         // [B][A][3]
+    const float* T;                         // [B] kelvin, NULL: energies in kJ/mol
+    long long B; int A;
+    double to_nm, coulomb;
+    int nb, na, nt, np;                     // table lengths, within the TI_FF_MAX_* caps (checked on the host)
+    const int32_t* idx;                     // [nb + na + nt + np] term words
+    const double* par;                      // [2 nb + 2 na + 2 nt + 3 np]
+    double* e;                              // [B]
+    double* terms;                          // [B][4] or NULL
+};
+hipError_t launch_obs_ff_energy(const FfParams& p, hipStream_t st);
+// out[0] = the smallest index b with T[b] <= 0 or not finite, as a double (+inf: none)
+hipError_t launch_obs_ff_bad_temperature(double* out, const float* T, long long B, hipStream_t st);
+// logw[b] = (float)-((u1[b] - u0[b]) + neg_dlogp[b]) in fp64; u0 / neg_dlogp NULL: 0
+hipError_t launch_obs_ti_logw(float* logw, const double* u0, const double* u1, const float* neg_dlogp, long long B, hipStream_t st);
+
 // ---- bootstrap (obs_boot_kernels.hip; include/ti_hip.h ti_obs_bootstrap)
 enum { BOOT_SRC_PHILOX = 0, BOOT_SRC_INDEX = 1, BOOT_SRC_IDENTITY = 2 };
 struct BootParams {

@@ -25,7 +25,13 @@ runs the p x p algebra on the GPU too, p <= 64) adds ``gedmd_eigenvalues`` [nev]
 "sigma": 5.0, "nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "temperature": T}`` (columns and temperature required) adds
 ``kinetics_eigenvalues`` [nev], ``kinetics_ci`` [2, nev] and ``kinetics_rank``: the unweighted generator spectrum of the selected CV
 columns (the torsions; at most 16) of the end-state row, a = k_B T with k_B = 0.008314462618, as the reference's
-mdqm9/analysis/gedmd.py computes it; the key is checked before the rollout and refused by sample_adw.  Without the keys exactly the reference's files are written.
+mdqm9/analysis/gedmd.py computes it; the key is checked before the rollout and refused by sample_adw.  sample_ambient with ``return_dlogp`` only: ``"energy": {"forcefield":
+<path of an OpenMM system XML, forcefield.ForceField.from_openmm_xml>, "scale": <SCALING_FACTOR of the species>}`` evaluates the
+reduced force-field energies on the GPU (observables.ff_energy at to_nm = 1 / scale, eval_energy.py:77-78): E0 of every x0 at its T0, E1
+of every end state at its T1, written as ``E0s_samples_{name}.npy`` / ``E1s_samples_{name}.npy`` (eval_energy.py:86-87) and, with ``logw``
+= -(E1 - E0 + dlogp) and ``ess_ti`` (the ESS of the full TI weights; with ``bootstrap`` also ``ess_ti_ci``), added to the npz; ``ess``
+keeps its meaning.  The key is checked before the rollout; sample_latent and sample_adw refuse it.  Without the keys exactly the
+reference's files are written.
 """
 from __future__ import annotations
 
@@ -70,6 +76,7 @@ def _observe_kw(config):
     o.pop("bootstrap", None)
     o.pop("gedmd", None)
     o.pop("kinetics", None)
+    o.pop("energy", None)
     if o.get("ref") is not None:
         o["ref"] = np.asarray(o["ref"], np.float32)
     return dict(observe=o)
@@ -180,9 +187,67 @@ def _kinetics_arrays(g, cv_end):
     return dict(kinetics_eigenvalues=res.eigenvalues, kinetics_ci=res.ci, kinetics_rank=np.int64(res.rank))
 
 
-def _write_observables(config, path, cvs, dlogps, gedmd=None):
+ENERGY_KEYS = ("forcefield", "scale")
+
+
+def _check_energy(config, driver="sample_ambient"):
+    """Before the rollout: observables["energy"] validated and its force field read (sample_ambient) -> (ForceField, to_nm), None
+    without the key; refused by the other two drivers, whose weights it cannot complete."""
+    o = getattr(config, "observables", None)
+    g = None if o is None else dict(o).get("energy")
+    if g is None:
+        return None
+    if driver == "sample_latent":
+        raise ValueError("observables['energy'] is for sample_ambient: the latent map's weights also need log p(z0) of the prior "
+                         "(calc_importance_weights), which is not evaluated here")
+    if driver == "sample_adw":
+        raise ValueError("observables['energy'] is for sample_ambient: it evaluates a molecular force field; the double well's potential "
+                         "enters through observables['gedmd']['potential']")
+    if not isinstance(g, dict) or set(g) != set(ENERGY_KEYS):
+        raise ValueError(f"observables['energy'] must be a dict with exactly the keys {list(ENERGY_KEYS)}, got {g!r}")
+    scale = g["scale"]
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"observables['energy']['scale'] must be finite and > 0, got {scale!r}")
+    if not bool(getattr(config, "return_dlogp", False)):
+        raise ValueError("observables['energy'] needs return_dlogp: the TI weights are exp(-(E1 - E0 + dlogp))")
+    from . import forcefield as _ff
+    return _ff.ForceField.from_openmm_xml(os.fspath(g["forcefield"])), 1.0 / float(scale)
+
+
+def _batch_energies(b, batch, sample, ff, to_nm):
+    """(E0, E1) [B] float64 of one batch: the reduced energies of x0 at every molecule's T0 and of the end state at its T1"""
+    from .thermo import _molecule as _mol
+    sb = _mol.split_species_batch(batch, b.ATOM_KEY)
+    if sb.n_atoms is not None:
+        raise ValueError("observables['energy'] takes one species per run (one force field)")
+    B, A = sb.B, sb.A
+    eng = b.engine_of(sb)
+    eng.set_forcefield(ff)
+    x0 = C.as_f32(batch.x0, (B, A, 3))
+    x1 = C.as_f32(sample[-1], (B, A, 3))
+    per_mol = lambda v: C.as_f32(v, (B, A))[:, 0]
+    T0, T1 = per_mol(batch.T0), per_mol(batch.T1)
+    if C.is_cuda(x0):
+        T0, T1 = T0.contiguous(), T1.contiguous()
+    else:
+        T0, T1 = np.ascontiguousarray(T0), np.ascontiguousarray(T1)
+    return C.to_numpy(eng.ff_energy(x0, to_nm, T0)), C.to_numpy(eng.ff_energy(x1, to_nm, T1))
+
+
+def _energy_arrays(config, E0, E1, dl):
+    """E0, E1, logw, ess_ti (and ess_ti_ci with the bootstrap key) of a run's reduced energies and end-state dlogp"""
+    logw = _obs.ti_logw(E0, E1, dl)
+    _, ess = _obs.importance_weights(logw)
+    out = dict(E0=E0, E1=E1, logw=logw, ess_ti=np.float64(ess))
+    n_boot = dict(config.observables).get("bootstrap")
+    if n_boot is not None:
+        out["ess_ti_ci"] = np.asarray(_obs.ess_ti(E0, E1, dl, n_boot=int(n_boot)).ci, np.float64)
+    return out
+
+
+def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None):
     """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp); gedmd: (x0, x1, beta0, beta1)
-    of an adw run whose observables carry the gedmd key"""
+    of an adw run whose observables carry the gedmd key; energy: (E0, E1) [B] of a run with the energy key"""
     cv = np.concatenate([C.to_numpy(c) for c in cvs], axis=1).astype(np.float32)
     dl = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in dlogps]) if dlogps else None
     hist, edges, ess = _obs.end_state_summary(np.ascontiguousarray(cv[-1]), dl, bins=int(dict(config.observables).get("bins", 32)))
@@ -202,11 +267,14 @@ def _write_observables(config, path, cvs, dlogps, gedmd=None):
     k = _kinetics_settings(config.observables, cv.shape[2])
     if k is not None:
         extra.update(_kinetics_arrays(k, cv[-1]))
+    if energy is not None:
+        extra.update(_energy_arrays(config, energy[0], energy[1], dl))
     np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
 
 
 def sample_ambient(config, b, dataset):
     _check_kinetics(config)
+    energy, E0s, E1s = _check_energy(config), [], []
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -226,9 +294,16 @@ def sample_ambient(config, b, dataset):
             dlogps.append(C.to_numpy(dlogp)[-1, :])
         if integrator.observe is not None:
             cvs.append(integrator.cv)
+        if energy is not None:
+            E0, E1 = _batch_energies(b, batch, sample, *energy)
+            E0s.append(E0); E1s.append(E1)
     name = config.data_save_name
+    if energy is not None:
+        energy = (np.concatenate(E0s), np.concatenate(E1s))
+        np.save(os.path.join(config.data_save_path, f"E0s_samples_{name}.npy"), energy[0])
+        np.save(os.path.join(config.data_save_path, f"E1s_samples_{name}.npy"), energy[1])
     if cvs:
-        _write_observables(config, os.path.join(config.data_save_path, f"observables_{name}.npz"), cvs, dlogps)
+        _write_observables(config, os.path.join(config.data_save_path, f"observables_{name}.npz"), cvs, dlogps, energy=energy)
     np.save(os.path.join(config.data_save_path, f"latent_noises_{name}.npy"), np.concatenate(latent_noises, axis=0))
     np.save(os.path.join(config.data_save_path, f"latent_dlogps_{name}.npy"), np.concatenate(latent_dlogps, axis=0))
     np.save(os.path.join(config.data_save_path, f"samples_{name}.npy"), np.concatenate(samples, axis=0))
@@ -239,6 +314,7 @@ def sample_ambient(config, b, dataset):
 
 def sample_latent(config, b, dataset):
     _check_kinetics(config)
+    _check_energy(config, "sample_latent")
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -271,6 +347,7 @@ def sample_adw(config, b, x0s_batches):
                                   f"a d = {b.dim} model would lose coordinates: use StandardIntegrator.rollout directly")
     assert len(config.beta0s) == len(config.beta1s) == 1            # adw/sample.py:24
     _check_kinetics(config, molecules=False)
+    _check_energy(config, "sample_adw")
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),
                                          step_control=getattr(config, "step_control", "batch"), fused=bool(getattr(config, "fused", False)),

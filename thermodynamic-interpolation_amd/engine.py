@@ -404,6 +404,39 @@ class _Engine:
         _lib.check(_lib.lib().ti_obs_set_observer(self.h, dp, K, rp, sp, int(every), op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         self._observer_keep = out
 
+    def _f64_in(self, a, B, what, dev):
+        """(pointer, keepalive) of a [B] float64 input living where the call lives (dev: on this engine's GPU)"""
+        if dev:
+            if not (hasattr(a, "data_ptr") and a.is_cuda and str(a.dtype) == "torch.float64" and a.is_contiguous()):
+                raise TypeError(f"{what} must be a contiguous CUDA float64 tensor when the call's buffers live on the GPU")
+            if (a.device.index or 0) != self.device:
+                raise ValueError(f"{what} lives on {a.device} but this engine was created on device {self.device}")
+            if tuple(a.shape) != (B,):
+                raise ValueError(f"{what} must have shape ({B},), got {tuple(a.shape)}")
+            return C.c_void_p(a.data_ptr()), a
+        host = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "data_ptr") else a, np.float64)
+        if host.shape != (B,):
+            raise ValueError(f"{what} must have shape ({B},), got {host.shape}")
+        return C.c_void_p(host.ctypes.data), host
+
+    def ti_logw(self, u0, u1, neg_dlogp):
+        """ti_obs_ti_logw: logw [B] float32 = -(u1 - u0 + neg_dlogp), formed in fp64 on the GPU and rounded once.  u0, u1 [B] float64
+        (u0 None: 0), neg_dlogp [B] float32 (None: 0); numpy in, numpy out; CUDA tensors in, a CUDA tensor out."""
+        B = int(u1.shape[0])
+        dev = hasattr(u1, "data_ptr") and u1.is_cuda
+        if dev:
+            import torch
+            out = torch.empty(B, dtype=torch.float32, device=u1.device)
+        else:
+            out = np.empty(B, np.float32)
+        (np_, op), ndev, keep = self._ptrs((neg_dlogp, (B,), False, "neg_dlogp"), (out, (B,), True, "out"))
+        if ndev != dev:
+            raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
+        p1, k1 = self._f64_in(u1, B, "u1", dev)
+        p0, k0 = (None, None) if u0 is None else self._f64_in(u0, B, "u0", dev)
+        _lib.check(_lib.lib().ti_obs_ti_logw(self.h, p0, p1, np_, B, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return out
+
     def _times(self, t, B):
         """A 1-D time vector of length B (one time per molecule / row) as a buffer spec, or None for a scalar t."""
         if (tuple(t.shape) if hasattr(t, "shape") else np.shape(t)) == ():
@@ -514,6 +547,42 @@ class PainnEngine(_Engine):
             t = np.ascontiguousarray(t, np.uint8)
         ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
         _lib.check(L.ti_painn_set_molecules(self.h, ptr(n), ptr(m), ptr(t), B, _lib.MEM_HOST))
+
+    def set_forcefield(self, ff):
+        """ti_obs_ff_set: copy a forcefield.ForceField of this engine's species into the handle (None clears it).  The library checks
+        index ranges, repeated atoms, the caps, signs and finiteness; the dense pair table is built here (ForceField.pair_table)."""
+        L = _lib.lib()
+        if ff is None:
+            _lib.check(L.ti_obs_ff_set(self.h, None, None, None, None, None, None, None, None))
+            return
+        pairs = ff.pair_table(self.A)
+        desc = _lib.FfDesc(len(ff.bond_idx), len(ff.angle_idx), len(ff.torsion_idx), len(pairs), float(ff.coulomb))
+        ip = lambda a: _lib.iptr(a) if a.size else None
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
+        _lib.check(L.ti_obs_ff_set(self.h, C.byref(desc), ip(ff.bond_idx), dp(ff.bond_par), ip(ff.angle_idx), dp(ff.angle_par),
+                                   ip(ff.torsion_idx), dp(ff.torsion_par), dp(pairs)))
+
+    def ff_energy(self, x, to_nm=1.0, T=None, terms=False):
+        """ti_obs_ff_energy: E [B] float64 of x [B,A,3] float32 at positions x * to_nm (nm), in kJ/mol -- or, with T [B] float32 kelvin
+        (a scalar: every molecule's), the reduced energy E / (R T).  terms=True: (E, terms [B, 4]) with the bond, angle, torsion and
+        pair sums.  numpy in, numpy out; a CUDA tensor in, CUDA float64 tensors out (no coordinate-sized host copy)."""
+        B = self._check_x(x)
+        dev = hasattr(x, "data_ptr") and x.is_cuda
+        if T is not None and (np.shape(T) if not hasattr(T, "shape") else tuple(T.shape)) == ():
+            T = x.new_full((B,), float(T)) if dev else np.full(B, float(T), np.float32)
+        elif T is not None and not dev and not hasattr(T, "data_ptr"):
+            T = np.ascontiguousarray(T, np.float32)
+        if dev:
+            import torch
+            e = torch.empty(B, dtype=torch.float64, device=x.device)
+            tm = torch.empty((B, 4), dtype=torch.float64, device=x.device) if terms else None
+            ep, tp2 = C.c_void_p(e.data_ptr()), (C.c_void_p(tm.data_ptr()) if terms else None)
+        else:
+            e, tm = np.empty(B, np.float64), (np.empty((B, 4), np.float64) if terms else None)
+            ep, tp2 = C.c_void_p(e.ctypes.data), (C.c_void_p(tm.ctypes.data) if terms else None)
+        (xp, Tp), xdev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), (T, (B,), False, "T"))
+        _lib.check(_lib.lib().ti_obs_ff_energy(self.h, xp, B, float(to_nm), Tp, ep, tp2, _lib.MEM_DEVICE if xdev else _lib.MEM_HOST))
+        return (e, tm) if terms else e
 
     def _obs_x_shape(self, x):
         B = self._check_x(x)

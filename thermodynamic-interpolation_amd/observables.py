@@ -411,6 +411,20 @@ def free_energy_bg(E_T0, neg_dlogp_T0, E_T1, neg_dlogp_T1, k=None, seed=0, **kw)
     return BootstrapResult(r1.point - r0.point, ci, diff, (r0.n_kept, r1.n_kept))
 
 
+def ff_energy(engine, x, to_nm=1.0, T=None, terms=False):
+    """E [B] float64 of x [B,A,3] float32 under the force field set on `engine` (PainnEngine.set_forcefield), evaluated on the GPU in
+    fp64 at the positions x * to_nm: kJ/mol, or with T [B] kelvin the reduced energy E / (R T) the estimators above take as E0s / E1s.
+    terms=True: (E, [B, 4] bond, angle, torsion and pair sums).  Lives where x lives."""
+    return engine.ff_energy(x, to_nm=to_nm, T=T, terms=terms)
+
+
+def ti_logw(u0, u1, neg_dlogp, engine=None):
+    """logw [B] float32 = -(u1 - u0 + neg_dlogp) from reduced energies u0, u1 [B] float64 (u0 None: 0, the calc_phis_bg form) and
+    neg_dlogp [B] float32 (None: 0), formed in fp64 on the GPU and rounded once: what ``importance_weights``, ``weighted_histogram``,
+    ``bootstrap`` and ``rff_gram`` take.  Lives where u1 lives."""
+    return (engine or _service_engine(_device_of(u1))).ti_logw(u0, u1, neg_dlogp)
+
+
 def free_energy_profile(x, logw, bins=80, range=(-2.5, 2.5), engine=None):
     """F [bins] = -ln p_hat, p_hat the weighted histogram of x normalised over the range and divided by the bin width (a density);
     +inf for empty bins."""
