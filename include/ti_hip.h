@@ -527,6 +527,55 @@ int ti_obs_ff_energy(ti_handle* h, const float* x, int64_t B, double to_nm, cons
  * [host|device] by mem.  u0 == NULL: 0 (the calc_phis_bg form); neg_dlogp == NULL: 0.  Non-finite inputs pass through: the
  * consumers refuse them by index.  Any handle.  TI_E_ARG: a NULL handle, u1 or out_logw, B < 1, an unknown mem. */
 int ti_obs_ti_logw(ti_handle* h, const double* u0, const double* u1, const float* neg_dlogp, int64_t B, float* out_logw, int mem);
+/* ---- Z-matrix (internal) coordinates: construct, NeRF rebuild with log|det J|, and the histograms of all columns ------------------
+ * What the reference's mdqm9/analysis/utils/z_matrix.py computes around results_00031.py: construct_z_matrix_batch on the sorted
+ * atoms (ti_obs_zmat), deconstruct_z_matrix_batch -- the batch version, which does not clamp --, its log-determinant
+ * (jacobian=True, compute_jacobian_batch) and the validity screen correct_conf_indexes (ti_obs_zmat_xyz).  fp64 arithmetic on the
+ * fp32 inputs, no atomics; a molecule's outputs are a function of its own inputs and the topology only -- not of its place in the
+ * batch, of B or of mem -- and a call repeats bit for bit.
+ * Topology (host memory, copied per call like desc of ti_obs_cv): order [A] int32 is a permutation, sorted atom s is the caller's
+ * atom order[s] (the reference's atom_order; NULL: the identity); ref [A][3] int32 in SORTED numbering (the reference's ref_atoms):
+ * ref[s] = (r1, r2, r3) gives sorted atom s the distance DIST(s, r1), the angle ANGLE(s, r1, r2) at r1 and the torsion
+ * TORSION(r3, r2, r1, s) of ti_obs_cv -- compute_distance(x4, x3), compute_angle(x4, x3, x2), compute_torsion(x1, x2, x3, x4) of
+ * z_matrix.py:86-93.  Only ref[s][0] is read for s >= 1, ref[s][1] for s >= 2 and ref[s][2] for s >= 3; the slots read must be < s
+ * and distinct.
+ * Both calls take painn handles with 2 <= A <= 32 (an adw handle: TI_E_ARG); with ti_painn_set_molecules in force they return
+ * TI_E_UNSUPPORTED: one topology is one species.  TI_E_ARG, before any device work and with nothing written: order not a
+ * permutation, a slot that is read outside 0..s-1 or repeated, ref == NULL, B < 0, a NULL x / z or output with B > 0, an unknown
+ * mem.  B = 0: TI_OK.
+ *
+ * ti_obs_zmat: x [B,A,3] fp32 -> out_z [B,A-1,3] fp32, both [host|device] by mem.  Row s - 1 is (d, a, t) of sorted atom s; a = 0
+ * in row 0 and t = 0 in rows 0 and 1, exactly (the reference's layout).  One thread per (molecule, row); every value holds the bits
+ * ti_obs_cv returns for the equivalent descriptor on the caller's atoms (the angle is atan2(|u x v|, u.v), not the reference's fp32
+ * acos). */
+int ti_obs_zmat(ti_handle* h, const int32_t* order, const int32_t* ref, const float* x, int64_t B, float* out_z, int mem);
+/* ti_obs_zmat_xyz: z [B,A-1,3] fp32 -> out_x [B,A,3] fp32 in the caller's atom numbering, in the reference's canonical frame; with
+ * (d, a, t) = row s - 1 of z as fp64 and X the placed fp64 positions:
+ *   sorted atom 0 at the origin, sorted atom 1 at (z[0,0], 0, 0),
+ *   sorted atom 2 at (X[ref[2][0]].x - d cos a, d sin a, 0) if ref[2][0] != 0, else at (d cos a, d sin a, 0),
+ *   sorted atom s >= 3 with p3 = X[r1], p2 = X[r2], p1 = X[r3]: e1 = (p3 - p2) / |p3 - p2|, n = (p2 - p1) x e1 / |.|, e2 = n x e1,
+ *   X[s] = p3 - d cos a e1 + d sin a cos t e2 + d sin a sin t n
+ * -- ic_to_xyz of mol_geometry.py with cos(pi - a) = -cos a and sin(pi - a) = sin a, so that no rounded pi enters.  Positions are
+ * rounded to fp32 once, on output.  The structural zeros of z are not read except by out_valid.
+ * out_logdet [B] fp64 (may be NULL): log|z[1,0]| + sum over s >= 3 in ascending s of (2 log|z[s-1,0]| + log|sin z[s-1,1]|), 0 for
+ * A = 2: the closed form of the reference's det J_2 and det J_det (log|det| of the map from the 3A - 6 internal coordinates).
+ * out_valid [B] uint8 (may be NULL): correct_conf_indexes as a mask, 1 iff every one of the A - 1 rows has d > 0, 0 <= a <= pi32 and
+ * -pi32 < t <= pi32, compared in fp32 with pi32 = (float)pi, the structural zeros included as they are given; a NaN gives 0.
+ * out_x, out_logdet, out_valid: [host|device] by mem.
+ * One thread per molecule (the chain is sequential), 64 molecules per workgroup, the placed positions in LDS (1536 A bytes).
+ * Degenerate input is not an error: collinear references, d = 0 or sin a = 0 give NaN or +-inf in that molecule's outputs only. */
+int ti_obs_zmat_xyz(ti_handle* h, const int32_t* order, const int32_t* ref, const float* z, int64_t B, float* out_x, double* out_logdet,
+                    uint8_t* out_valid, int mem);
+/* ti_obs_hist for every column of values [B,K] fp32 in one launch: column c is binned into n_bins equal bins on [lo[c], hi[c])
+ * (lo, hi [K] fp64, host) by the rules of ti_obs_hist -- a value equal to hi[c] is in the upper tail --, 1 <= n_bins <= 256,
+ * 1 <= K <= 128; out_hist [K][n_bins] and out_tails [K][3] (host, double).  The sums of a column are taken in the order ti_obs_hist
+ * takes them: with keep == NULL column c holds the bits of ti_obs_hist(values + c, stride K, ...).
+ * keep [B] uint8 (may be NULL; [host|device] by mem like values and logw): entries with keep[i] == 0 get weight 0, and the max
+ * shift, the normalising sum and the refusal of a non-finite logw run over the kept entries only (logw == NULL: 1 / #kept), so the
+ * kept weights sum to 1.  Any handle.  TI_E_ARG: n_bins, K or a range as above, B < 1, a NULL buffer, an unknown mem, a keep that
+ * keeps nothing; TI_E_NAN: a non-finite kept logw (the message names the first such index). */
+int ti_obs_hist_cols(ti_handle* h, const float* values, int32_t K, const float* logw, const uint8_t* keep, int64_t B, int32_t n_bins,
+                     const double* lo, const double* hi, double* out_hist, double* out_tails, int mem);
 /* Observer: with one attached, every rollout entry point (ti_painn_rollout, _dlogp, _dlogp_est, ti_adw_rollout, _dlogp) also
  * evaluates the K CVs on the state at the grid points i with i % every == 0 and at the last one -- ti_rollout_rows(n_step, every)
  * rows, whatever save_every is -- and writes them to out_cv [rows, B, K] fp32 ([host|device] by mem; the caller sizes it for the

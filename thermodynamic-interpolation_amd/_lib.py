@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "ti_obs_eigh", "ti_obs_gedmd_spectrum",
     "ti_obs_rff_gram_wide",
     "ti_obs_ff_set", "ti_obs_ff_energy", "ti_obs_ti_logw",
+    "ti_obs_zmat", "ti_obs_zmat_xyz", "ti_obs_hist_cols",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -58,6 +59,8 @@ EIGH_MAX_N, EIGH_MAX_SWEEPS, EIGH_MAX_MATRICES = 64, 64, BOOT_MAX_RESAMPLES + 1
 # ti_obs_ff_set: the caps of the four tables (TI_FF_MAX_*), R in kJ / (mol K) (TI_FF_GAS_CONSTANT), OpenMM's ONE_4PI_EPS0 in kJ nm / (mol e^2)
 FF_MAX_BONDS, FF_MAX_ANGLES, FF_MAX_TORSIONS, FF_MAX_PAIRS = 64, 128, 512, 300
 FF_GAS_CONSTANT, FF_COULOMB = 0.00831446261815324, 138.935456
+# ti_obs_zmat / ti_obs_zmat_xyz: the range of A; ti_obs_hist_cols: the most columns of a call
+ZMAT_MIN_ATOMS, ZMAT_MAX_ATOMS, HIST_COLS_MAX = 2, 32, 128
 
 
 class PainnDesc(C.Structure):
@@ -188,6 +191,9 @@ def lib():
     L.ti_obs_ff_set.argtypes = [vp, C.POINTER(FfDesc), ip, dp, ip, dp, ip, dp, dp]
     L.ti_obs_ff_energy.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
     L.ti_obs_ti_logw.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int]
+    L.ti_obs_zmat.argtypes = [vp, ip, ip, vp, C.c_int64, vp, C.c_int]
+    L.ti_obs_zmat_xyz.argtypes = [vp, ip, ip, vp, C.c_int64, vp, vp, vp, C.c_int]
+    L.ti_obs_hist_cols.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int]
     _lib = L
     return L
 

@@ -31,6 +31,8 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "pai
            "obs_eig_kernels.hip",
            # force-field energies of a batch and the TI log-weights from them (ti_obs_ff_energy, ti_obs_ti_logw)
            "obs_ff_kernels.hip",
+           # Z-matrix coordinates both ways and the histograms of all columns in one launch (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols)
+           "obs_zmat_kernels.hip",
            # layer-0 phi table (class pass, table kernel); the pair kernel's table builds live in painn_pair_nb*.hip
            "painn_phi0_kernels.hip"]
 HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",

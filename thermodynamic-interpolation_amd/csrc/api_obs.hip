@@ -1,5 +1,5 @@
 // api_obs.hip -- observables (ti_obs_*): collective variables of a state, importance weights, weighted histograms, force-field
-// energies and the TI log-weights formed from them, and the observer a rollout writes CV rows through.
+// energies and the TI log-weights formed from them, Z-matrix coordinates both ways, and the observer a rollout writes CV rows through.
 #include "ti_handle.hpp"
 
 namespace {
@@ -579,6 +579,137 @@ int ti_obs_ti_logw(ti_handle* h, const double* u0, const double* u1, const float
         float* od = sg.out(out_logw, h->obs_logw, (size_t)B);
         HIP_CHECK(launch_obs_ti_logw(od, u0d, u1d, nd, B, h->stream));
         sg.finish();
+        return TI_OK;
+    });
+}
+
+// The checks ti_obs_zmat and ti_obs_zmat_xyz share, all before any device work; on TI_OK `topo` holds order [A] then ref [A][3].
+static int zmat_check(ti_handle* h, const int32_t* order, const int32_t* ref, int mem, std::vector<int32_t>& topo)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    const int A = h->d.n_atoms;
+    if (A < 2 || A > ZMAT_MAX_ATOMS) return fail(TI_E_ARG, "a Z-matrix needs 2 <= A <= " + std::to_string(ZMAT_MAX_ATOMS) + ", the handle has A = " + std::to_string(A));
+    if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one topology is one species: clear ti_painn_set_molecules first");
+    if (!ref) return fail(TI_E_ARG, "ref is NULL");
+    topo.assign((size_t)4 * A, 0);
+    std::vector<char> seen((size_t)A, 0);
+    for (int s = 0; s < A; ++s) {
+        const int a = order ? order[s] : s;
+        if (a < 0 || a >= A || seen[a]) return fail(TI_E_ARG, "order is not a permutation of 0.." + std::to_string(A - 1) + " (entry " + std::to_string(s) + ")");
+        seen[a] = 1;
+        topo[s] = a;
+    }
+    for (int s = 1; s < A; ++s) {
+        const int n = s < 3 ? s : 3;                           // the slots that are read
+        for (int j = 0; j < n; ++j) {
+            const int r = ref[3 * s + j];
+            if (r < 0 || r >= s) return fail(TI_E_ARG, "ref[" + std::to_string(s) + "][" + std::to_string(j) + "] = " + std::to_string(r) + " is not an earlier sorted atom");
+            for (int j2 = 0; j2 < j; ++j2)
+                if (ref[3 * s + j2] == r) return fail(TI_E_ARG, "ref[" + std::to_string(s) + "] repeats atom " + std::to_string(r));
+            topo[A + 3 * s + j] = r;
+        }
+    }
+    return TI_OK;
+}
+
+int ti_obs_zmat(ti_handle* h, const int32_t* order, const int32_t* ref, const float* x, int64_t B, float* out_z, int mem)
+{
+    std::vector<int32_t> topo;
+    if (int rc = zmat_check(h, order, ref, mem, topo)) return rc;
+    if (B < 0 || (B > 0 && (!x || !out_z))) return fail(TI_E_ARG, "NULL buffer");
+    if (B == 0) return TI_OK;
+    return guarded([&]() -> int {
+        set_device(h);
+        const int A = h->d.n_atoms;
+        h->zm_topo.upload(topo);
+        Staged sg(h, mem);
+        ZmatParams p{};
+        p.x = sg.in(x, h->obs_x, (size_t)B * 3 * A);
+        p.B = B; p.A = A; p.topo = h->zm_topo.p;
+        p.z = sg.out(out_z, h->zm_z, (size_t)B * 3 * (A - 1));
+        HIP_CHECK(launch_obs_zmat(p, h->stream));
+        sg.finish();
+        return TI_OK;
+    });
+}
+
+int ti_obs_zmat_xyz(ti_handle* h, const int32_t* order, const int32_t* ref, const float* z, int64_t B, float* out_x, double* out_logdet,
+                    uint8_t* out_valid, int mem)
+{
+    std::vector<int32_t> topo;
+    if (int rc = zmat_check(h, order, ref, mem, topo)) return rc;
+    if (B < 0 || (B > 0 && (!z || !out_x))) return fail(TI_E_ARG, "NULL buffer");
+    if (B == 0) return TI_OK;
+    return guarded([&]() -> int {
+        set_device(h);
+        const int A = h->d.n_atoms;
+        h->zm_topo.upload(topo);
+        Staged sg(h, mem);
+        ZmatXyzParams p{};
+        p.z = sg.in(z, h->zm_z, (size_t)B * 3 * (A - 1));
+        p.B = B; p.A = A; p.topo = h->zm_topo.p;
+        p.x = sg.out(out_x, h->obs_x, (size_t)B * 3 * A);
+        p.logdet = out_logdet ? sg.out(out_logdet, h->zm_logdet, (size_t)B) : nullptr;
+        p.valid = out_valid ? sg.out(out_valid, h->zm_valid, (size_t)B) : nullptr;
+        HIP_CHECK(launch_obs_zmat_xyz(p, h->stream));
+        sg.finish();
+        return TI_OK;
+    });
+}
+
+int ti_obs_hist_cols(ti_handle* h, const float* values, int32_t K, const float* logw, const uint8_t* keep, int64_t B, int32_t n_bins,
+                     const double* lo, const double* hi, double* out_hist, double* out_tails, int mem)
+{
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (n_bins < 1 || n_bins > 256) return fail(TI_E_ARG, "n_bins must be in 1..256");
+    if (K < 1 || K > HIST_COLS_MAX) return fail(TI_E_ARG, "K must be in 1.." + std::to_string(HIST_COLS_MAX));
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!values || !lo || !hi || !out_hist || !out_tails) return fail(TI_E_ARG, "NULL buffer");
+    for (int c = 0; c < K; ++c)
+        if (!(hi[c] > lo[c]) || !std::isfinite(lo[c]) || !std::isfinite(hi[c])) return fail(TI_E_ARG, "column " + std::to_string(c) + ": the range needs finite lo < hi");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const size_t ncol = (size_t)n_bins + 3;
+        Staged sg(h, mem);
+        const float* vd = sg.in(values, h->obs_val, (size_t)B * K);
+        const float* ld = logw ? sg.in(logw, h->obs_logw, (size_t)B) : nullptr;
+        const uint8_t* kd = keep ? sg.in(keep, h->hc_keep, (size_t)B) : nullptr;
+        std::vector<double> range(lo, lo + K);
+        range.insert(range.end(), hi, hi + K);
+        h->hc_range.upload(range);
+        grow(h->obs_red, 4 + std::max<size_t>((size_t)K * ncol, 259));          // at least what obs_norm_dev asks for: it must not move them
+        grow(h->obs_part, (size_t)OBS_MAX_BLOCKS * std::max<size_t>((size_t)K * ncol, 259));
+        double m = 0.0, tot = (double)B;
+        if (kd) {                                          // the shift, the refusal and the normalising sum over the kept entries
+            double r[3];
+            HIP_CHECK(launch_obs_keep_max(h->obs_red.p, h->obs_part.p, ld, kd, B, st));
+            HIP_CHECK(hipMemcpyAsync(r, h->obs_red.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            if (r[2] < 1.0) return fail(TI_E_ARG, "keep keeps no entry");
+            if (r[1] < (double)B) return fail(TI_E_NAN, "non-finite logw at index " + std::to_string((long long)r[1]));
+            tot = r[2];
+            if (ld) {
+                m = r[0];
+                HIP_CHECK(launch_obs_keep_sum(h->obs_red.p, h->obs_part.p, ld, kd, m, B, st));
+                HIP_CHECK(hipMemcpyAsync(&tot, h->obs_red.p, sizeof(double), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipStreamSynchronize(st));
+            }
+        } else if (ld) {                                   // the reductions of ti_obs_weights / ti_obs_hist
+            double norm[4];
+            if (int rc = obs_norm_dev(h, ld, B, norm)) return rc;
+            m = norm[0]; tot = norm[2];
+        }
+        HIP_CHECK(launch_obs_whist_cols(h->obs_red.p + 4, h->obs_part.p, vd, K, ld, kd, m, tot, B, n_bins, h->hc_range.p, h->hc_range.p + K, st));
+        std::vector<double> out((size_t)K * ncol);
+        HIP_CHECK(hipMemcpyAsync(out.data(), h->obs_red.p + 4, out.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int c = 0; c < K; ++c) {
+            std::copy(out.begin() + c * ncol, out.begin() + c * ncol + n_bins, out_hist + (size_t)c * n_bins);
+            std::copy(out.begin() + c * ncol + n_bins, out.begin() + (c + 1) * ncol, out_tails + (size_t)c * 3);
+        }
         return TI_OK;
     });
 }

@@ -167,6 +167,9 @@ struct ti_handle {
     // energies, term sums, reduced energies and log-weights (ti_obs_ff_energy, ti_obs_ti_logw)
     bool ff_on = false; int ff_n[4] = {0, 0, 0, 0}; double ff_coulomb = 0.0;
     DevBuf<int32_t> ff_idx; DevBuf<double> ff_par, ff_e, ff_terms, ff_u0, ff_u1; DevBuf<float> ff_T;
+    // Z-matrix coordinates and column histograms (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols): the topology of the call (order,
+    // ref), staging of a host call's z, log-determinants, validity and keep masks, the column ranges (lo [K], hi [K])
+    DevBuf<int32_t> zm_topo; DevBuf<float> zm_z; DevBuf<double> zm_logdet, hc_range; DevBuf<uint8_t> zm_valid, hc_keep;
 
     ~ti_handle()
     {
@@ -228,7 +231,7 @@ inline ti_handle* new_handle(int kind, int device)
 // compute into, and finish() copies those back in the order they were asked for.  finish() ends the call: it synchronises the stream.
 struct Staged {
     ti_handle* h; bool host;
-    struct { void* dst; const void* src; size_t bytes; } back[2] = {}; int n_back = 0;
+    struct { void* dst; const void* src; size_t bytes; } back[3] = {}; int n_back = 0;
     Staged(ti_handle* h_, int mem) : h(h_), host(mem == TI_MEM_HOST) {}
     template <typename T>
     const T* in(const T* p, DevBuf<T>& b, size_t n)

@@ -424,6 +424,37 @@ hipError_t launch_obs_ff_bad_temperature(double* out, const float* T, long long 
 // logw[b] = (float)-((u1[b] - u0[b]) + neg_dlogp[b]) in fp64; u0 / neg_dlogp NULL: 0
 hipError_t launch_obs_ti_logw(float* logw, const double* u0, const double* u1, const float* neg_dlogp, long long B, hipStream_t st);
 
+// ---- Z-matrix coordinates and the histograms of all columns (obs_zmat_kernels.hip; include/ti_hip.h ti_obs_zmat, ti_obs_zmat_xyz,
+// ti_obs_hist_cols).  topo: order [A] (sorted atom s is the caller's atom order[s]) followed by ref [A][3] in sorted numbering, both
+// validated on the host (zmat_check_topology): every slot that is read names an earlier sorted atom.
+constexpr int ZMAT_MAX_ATOMS = 32;          // 1536 A bytes of LDS per 64 molecules: 48 KB
+constexpr int HIST_COLS_MAX = 128;
+struct ZmatParams {
+    const float* x;                         // [B][A][3], the caller's atom numbering
+    long long B; int A;
+    const int32_t* topo;                    // [A + 3 A]
+    float* z;                               // [B][A - 1][3]: (d, a, t) of sorted atom s in row s - 1
+};
+struct ZmatXyzParams {
+    const float* z;                         // [B][A - 1][3]
+    long long B; int A;
+    const int32_t* topo;
+    float* x;                               // [B][A][3], the caller's atom numbering
+    double* logdet;                         // [B] or NULL
+    uint8_t* valid;                         // [B] or NULL
+};
+hipError_t launch_obs_zmat(const ZmatParams& p, hipStream_t st);
+hipError_t launch_obs_zmat_xyz(const ZmatXyzParams& p, hipStream_t st);
+// over the entries with keep[i] != 0: out[0] = largest finite logw (-inf: none; logw NULL: 0), out[1] = smallest index of a non-finite
+// logw as a double (+inf: none), out[2] = their number; partial: [OBS_MAX_BLOCKS][3]
+hipError_t launch_obs_keep_max(double* out, double* partial, const float* logw, const uint8_t* keep, long long B, hipStream_t st);
+// out[0] = sum of exp(logw - m) over the entries with keep[i] != 0; partial: [OBS_MAX_BLOCKS]
+hipError_t launch_obs_keep_sum(double* out, double* partial, const float* logw, const uint8_t* keep, double m, long long B, hipStream_t st);
+// out [K][n_bins + 3]: launch_obs_whist of every column c of values [B][K] on [lo[c], hi[c]) in one launch, weights exp(logw - m) / tot
+// (logw NULL: 1 / tot), 0 where keep (may be NULL) is 0; lo, hi: device [K]; partial: [K][OBS_MAX_BLOCKS][n_bins + 3]
+hipError_t launch_obs_whist_cols(double* out, double* partial, const float* values, int K, const float* logw, const uint8_t* keep, double m,
+                                 double tot, long long B, int n_bins, const double* lo, const double* hi, hipStream_t st);
+
 // ---- bootstrap (obs_boot_kernels.hip; include/ti_hip.h ti_obs_bootstrap)
 enum { BOOT_SRC_PHILOX = 0, BOOT_SRC_INDEX = 1, BOOT_SRC_IDENTITY = 2 };
 struct BootParams {

@@ -30,7 +30,16 @@ mdqm9/analysis/gedmd.py computes it; the key is checked before the rollout and r
 reduced force-field energies on the GPU (observables.ff_energy at to_nm = 1 / scale, eval_energy.py:77-78): E0 of every x0 at its T0, E1
 of every end state at its T1, written as ``E0s_samples_{name}.npy`` / ``E1s_samples_{name}.npy`` (eval_energy.py:86-87) and, with ``logw``
 = -(E1 - E0 + dlogp) and ``ess_ti`` (the ESS of the full TI weights; with ``bootstrap`` also ``ess_ti_ci``), added to the npz; ``ess``
-keeps its meaning.  The key is checked before the rollout; sample_latent and sample_adw refuse it.  Without the keys exactly the
+keeps its meaning.  The key is checked before the rollout; sample_latent and sample_adw refuse it.  sample_ambient only:
+``"zmatrix": {"order": [...], "ref_atoms": [[r1, r2, r3], ...], "bins": 64, "length_range": [lo, hi], "scale": s, "iqr_k": k}`` or, in
+place of order / ref_atoms, ``{"bonds": [[i, j], ...], "root": 0, ...}`` (zmatrix.ZMatrix / ZMatrix.from_bonds; bins, length_range,
+scale and iqr_k optional; scale defaults to the energy key's, else 1) computes the Z-matrices of every x0 and every end state on the
+GPU, coordinates divided by scale as in results_00031.py:173-174, and adds ``torsions_0/1`` [B, A-3], ``bond_angles_0/1`` [B, A-2],
+``bond_lengths_0/1`` [B, A-1] (gen_torsions / gen_bond_angles / gen_bond_lengths; 0: x0, 1: the end state), ``zmat_marginals_0/1``
+[3A-6, bins] and ``zmat_ranges`` [3A-6, 2] (observables.zmatrix_marginals: lengths, angles, torsions) to the npz.  The x0 are samples
+of the source ensemble and stay unweighted; the end state's marginals are weighted by the run's ``logw`` when the energy key supplies
+it, and with ``iqr_k`` (which needs the energy key) the reference's filter_iqr(weights, k) mask -- written as ``zmat_keep`` [B] -- is
+applied to them.  The key is checked before the rollout; sample_latent and sample_adw refuse it.  Without the keys exactly the
 reference's files are written.
 """
 from __future__ import annotations
@@ -77,6 +86,7 @@ def _observe_kw(config):
     o.pop("gedmd", None)
     o.pop("kinetics", None)
     o.pop("energy", None)
+    o.pop("zmatrix", None)
     if o.get("ref") is not None:
         o["ref"] = np.asarray(o["ref"], np.float32)
     return dict(observe=o)
@@ -245,7 +255,80 @@ def _energy_arrays(config, E0, E1, dl):
     return out
 
 
-def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None):
+ZMATRIX_KEYS = ("order", "ref_atoms", "bonds", "root", "bins", "length_range", "scale", "iqr_k")
+
+
+def _check_zmatrix(config, driver="sample_ambient"):
+    """Before the rollout: observables["zmatrix"] validated (sample_ambient) -> dict(zm, bins, length_range, scale, iqr_k), None
+    without the key; refused by the other two drivers."""
+    o = getattr(config, "observables", None)
+    g = None if o is None else dict(o).get("zmatrix")
+    if g is None:
+        return None
+    if driver != "sample_ambient":
+        raise ValueError(f"observables['zmatrix'] is for sample_ambient (molecules in Cartesian coordinates with a fixed topology); "
+                         f"{driver} does not take it")
+    from . import zmatrix as _zm
+    if not isinstance(g, dict) or set(g) - set(ZMATRIX_KEYS):
+        raise ValueError(f"observables['zmatrix'] must be a dict with keys out of {list(ZMATRIX_KEYS)}, got {g!r}")
+    explicit, bonded = "ref_atoms" in g, "bonds" in g
+    if explicit == bonded or (bonded and "order" in g) or (explicit and "root" in g):
+        raise ValueError("observables['zmatrix'] takes either 'ref_atoms' (with an optional 'order') or 'bonds' (with an optional 'root')")
+    try:
+        if explicit:
+            zm = _zm.ZMatrix(g.get("order"), np.asarray(g["ref_atoms"]))
+        else:
+            bonds = np.asarray(g["bonds"])
+            if bonds.ndim != 2 or bonds.shape[1:] != (2,) or bonds.dtype.kind not in "iu" or bonds.size == 0:
+                raise ValueError("bonds must be a non-empty integer list [[i, j], ...]")
+            zm = _zm.ZMatrix.from_bonds(bonds, int(bonds.max()) + 1, g.get("root", 0))
+        bins, lo, hi = _obs.check_bins(g.get("bins", 64), g.get("length_range", (0.0, 4.0)))
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"observables['zmatrix']: {e}") from None
+    energy = dict(o).get("energy")
+    scale = g.get("scale", energy["scale"] if isinstance(energy, dict) and "scale" in energy else 1.0)
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"observables['zmatrix']['scale'] must be finite and > 0, got {scale!r}")
+    k = g.get("iqr_k")
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, (int, float, np.integer, np.floating)) or not (np.isfinite(k) and k > 0):
+            raise ValueError(f"observables['zmatrix']['iqr_k'] must be finite and > 0, got {k!r}")
+        if energy is None:
+            raise ValueError("observables['zmatrix']['iqr_k'] filters on the TI weights: it needs observables['energy']")
+    return dict(zm=zm, bins=bins, length_range=(lo, hi), scale=float(scale), iqr_k=None if k is None else float(k))
+
+
+def _batch_zmatrices(b, batch, sample, g):
+    """(z0, z1) [B, A-1, 3] float32 of one batch: the Z-matrices of x0 and of the end state, coordinates divided by the scale"""
+    from .thermo import _molecule as _mol
+    sb = _mol.split_species_batch(batch, b.ATOM_KEY)
+    if sb.n_atoms is not None:
+        raise ValueError("observables['zmatrix'] takes one species per run (one topology)")
+    B, A = sb.B, sb.A
+    if A != g["zm"].A:
+        raise ValueError(f"observables['zmatrix'] describes {g['zm'].A} atoms, the molecules have {A}")
+    eng = b.engine_of(sb)
+    out = []
+    for x in (batch.x0, sample[-1]):
+        x = np.ascontiguousarray(C.to_numpy(C.as_f32(x, (B, A, 3)))) / g["scale"]        # fp32 / python float: fp32, as the reference divides
+        out.append(_obs.zmatrix(eng, np.ascontiguousarray(x, np.float32), g["zm"]))
+    return out[0], out[1]
+
+
+def _zmatrix_arrays(g, z0, z1, logw):
+    """The arrays the zmatrix key adds; logw [B] float32 of the energy key or None"""
+    keep = None if g["iqr_k"] is None else _obs.iqr_keep(logw, g["iqr_k"])
+    m0 = _obs.zmatrix_marginals(z0, None, None, g["bins"], g["length_range"])
+    m1 = _obs.zmatrix_marginals(z1, logw, keep, g["bins"], g["length_range"])
+    out = dict(torsions_0=_obs.torsions(z0), torsions_1=_obs.torsions(z1), bond_angles_0=_obs.bond_angles(z0),
+               bond_angles_1=_obs.bond_angles(z1), bond_lengths_0=_obs.bond_lengths(z0), bond_lengths_1=_obs.bond_lengths(z1),
+               zmat_marginals_0=m0.hist, zmat_marginals_1=m1.hist, zmat_ranges=m0.ranges)
+    if keep is not None:
+        out["zmat_keep"] = keep
+    return out
+
+
+def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=None):
     """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp); gedmd: (x0, x1, beta0, beta1)
     of an adw run whose observables carry the gedmd key; energy: (E0, E1) [B] of a run with the energy key"""
     cv = np.concatenate([C.to_numpy(c) for c in cvs], axis=1).astype(np.float32)
@@ -269,12 +352,15 @@ def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None):
         extra.update(_kinetics_arrays(k, cv[-1]))
     if energy is not None:
         extra.update(_energy_arrays(config, energy[0], energy[1], dl))
+    if zmat is not None:                       # (settings, z0, z1) of a run with the zmatrix key
+        extra.update(_zmatrix_arrays(zmat[0], zmat[1], zmat[2], extra.get("logw")))
     np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
 
 
 def sample_ambient(config, b, dataset):
     _check_kinetics(config)
     energy, E0s, E1s = _check_energy(config), [], []
+    zmat, z0s, z1s = _check_zmatrix(config), [], []
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -297,13 +383,17 @@ def sample_ambient(config, b, dataset):
         if energy is not None:
             E0, E1 = _batch_energies(b, batch, sample, *energy)
             E0s.append(E0); E1s.append(E1)
+        if zmat is not None:
+            z0, z1 = _batch_zmatrices(b, batch, sample, zmat)
+            z0s.append(z0); z1s.append(z1)
     name = config.data_save_name
     if energy is not None:
         energy = (np.concatenate(E0s), np.concatenate(E1s))
         np.save(os.path.join(config.data_save_path, f"E0s_samples_{name}.npy"), energy[0])
         np.save(os.path.join(config.data_save_path, f"E1s_samples_{name}.npy"), energy[1])
     if cvs:
-        _write_observables(config, os.path.join(config.data_save_path, f"observables_{name}.npz"), cvs, dlogps, energy=energy)
+        _write_observables(config, os.path.join(config.data_save_path, f"observables_{name}.npz"), cvs, dlogps, energy=energy,
+                           zmat=None if zmat is None else (zmat, np.concatenate(z0s), np.concatenate(z1s)))
     np.save(os.path.join(config.data_save_path, f"latent_noises_{name}.npy"), np.concatenate(latent_noises, axis=0))
     np.save(os.path.join(config.data_save_path, f"latent_dlogps_{name}.npy"), np.concatenate(latent_dlogps, axis=0))
     np.save(os.path.join(config.data_save_path, f"samples_{name}.npy"), np.concatenate(samples, axis=0))
@@ -315,6 +405,7 @@ def sample_ambient(config, b, dataset):
 def sample_latent(config, b, dataset):
     _check_kinetics(config)
     _check_energy(config, "sample_latent")
+    _check_zmatrix(config, "sample_latent")
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -348,6 +439,7 @@ def sample_adw(config, b, x0s_batches):
     assert len(config.beta0s) == len(config.beta1s) == 1            # adw/sample.py:24
     _check_kinetics(config, molecules=False)
     _check_energy(config, "sample_adw")
+    _check_zmatrix(config, "sample_adw")
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),
                                          step_control=getattr(config, "step_control", "batch"), fused=bool(getattr(config, "fused", False)),

@@ -389,6 +389,44 @@ class _Engine:
                                           _lib.MEM_DEVICE if vdev else _lib.MEM_HOST))
         return hist, tails
 
+    def _u8_in(self, a, B, what, dev):
+        """(pointer, keepalive) of a [B] uint8 input living where the call lives (dev: on this engine's GPU)"""
+        if dev:
+            if not (hasattr(a, "data_ptr") and a.is_cuda and str(a.dtype) in ("torch.uint8", "torch.bool") and a.is_contiguous()):
+                raise TypeError(f"{what} must be a contiguous CUDA uint8 (or bool) tensor when the call's buffers live on the GPU")
+            if (a.device.index or 0) != self.device:
+                raise ValueError(f"{what} lives on {a.device} but this engine was created on device {self.device}")
+            if tuple(a.shape) != (B,):
+                raise ValueError(f"{what} must have shape ({B},), got {tuple(a.shape)}")
+            return C.c_void_p(a.data_ptr()), a
+        host = np.ascontiguousarray(np.asarray(a.detach().cpu().numpy() if hasattr(a, "data_ptr") else a) != 0, np.uint8)
+        if host.shape != (B,):
+            raise ValueError(f"{what} must have shape ({B},), got {host.shape}")
+        return C.c_void_p(host.ctypes.data), host
+
+    def hist_cols(self, values, logw, keep, bins, lo, hi):
+        """ti_obs_hist_cols: (hist [K, bins], tails [K, 3]) float64 of all K columns of values [B, K] float32 (contiguous; numpy or a
+        CUDA tensor) in one launch, column c on [lo[c], hi[c]); logw [B] float32 (None: uniform) and keep [B] uint8 (None: all) live
+        where values lives.  With keep the weights are normalised over the kept entries only."""
+        from . import observables as _obs
+        if len(values.shape) != 2 or int(values.shape[0]) < 1:
+            raise ValueError("values must be [B, K] and non-empty")
+        B, K = int(values.shape[0]), int(values.shape[1])
+        if not 1 <= K <= _lib.HIST_COLS_MAX:
+            raise ValueError(f"values must have 1..{_lib.HIST_COLS_MAX} columns, got {K}")
+        lo, hi = np.ascontiguousarray(lo, np.float64).reshape(-1), np.ascontiguousarray(hi, np.float64).reshape(-1)
+        if lo.shape != (K,) or hi.shape != (K,):
+            raise ValueError(f"lo and hi must have K = {K} entries")
+        for c in range(K):
+            bins = _obs.check_bins(bins, (lo[c], hi[c]))[0]
+        (vp, lp), dev, keep_alive = self._ptrs((values, (B, K), False, "values"), (logw, (B,), False, "logw"))
+        kp, kk = (None, None) if keep is None else self._u8_in(keep, B, "keep", dev)
+        hist, tails = np.zeros((K, bins), np.float64), np.zeros((K, 3), np.float64)
+        dptr = C.POINTER(C.c_double)
+        _lib.check(_lib.lib().ti_obs_hist_cols(self.h, vp, K, lp, kp, B, bins, lo.ctypes.data_as(dptr), hi.ctypes.data_as(dptr),
+                                               hist.ctypes.data_as(dptr), tails.ctypes.data_as(dptr), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return hist, tails
+
     def set_observer(self, descriptors, ref=None, select=None, every=1, out=None):
         """Attach an observer: every rollout that follows also writes the CVs of the grid points i % every == 0 and of the last one
         to out [rows, B, K] (float32 numpy array or CUDA tensor, rows = ti_rollout_rows(n_step, every); kept alive here).
@@ -583,6 +621,49 @@ class PainnEngine(_Engine):
         (xp, Tp), xdev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), (T, (B,), False, "T"))
         _lib.check(_lib.lib().ti_obs_ff_energy(self.h, xp, B, float(to_nm), Tp, ep, tp2, _lib.MEM_DEVICE if xdev else _lib.MEM_HOST))
         return (e, tm) if terms else e
+
+    def _zmat_topology(self, zm):
+        if zm.A != self.A:
+            raise ValueError(f"the Z-matrix is for A = {zm.A} atoms, this engine has A = {self.A}")
+        return _lib.iptr(zm.order), _lib.iptr(zm.ref)
+
+    def zmatrix(self, x, zm, out=None):
+        """ti_obs_zmat: z [B, A-1, 3] float32 of x [B, A, 3] under the topology zm (zmatrix.ZMatrix): row s - 1 holds (d, a, t) of
+        sorted atom s.  numpy in, numpy out; a CUDA tensor in, a CUDA tensor out."""
+        op_, rp = self._zmat_topology(zm)
+        B = self._check_x(x)
+        if out is None:
+            out = _alloc_like(x if hasattr(x, "data_ptr") and x.is_cuda else None, (B, self.A - 1, 3))
+        (xp, zp), dev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), (out, (B, self.A - 1, 3), True, "out"))
+        _lib.check(_lib.lib().ti_obs_zmat(self.h, op_, rp, xp, B, zp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return out
+
+    def zmatrix_xyz(self, z, zm, logdet=False, valid=False):
+        """ti_obs_zmat_xyz: x [B, A, 3] float32 of z [B, A-1, 3] in the caller's atom numbering (NeRF placement in the reference's
+        canonical frame); logdet=True adds log|det J| [B] float64, valid=True the validity mask [B] uint8 (a tuple in that order).
+        numpy in, numpy out; a CUDA tensor in, CUDA tensors out."""
+        op_, rp = self._zmat_topology(zm)
+        if z is None or len(z.shape) != 3 or tuple(z.shape[1:]) != (self.A - 1, 3):
+            raise ValueError(f"z must be [B,{self.A - 1},3]")
+        B = int(z.shape[0])
+        dev_in = hasattr(z, "data_ptr") and z.is_cuda
+        x = _alloc_like(z if dev_in else None, (B, self.A, 3))
+        ld = vd = lp = vp = None
+        if dev_in:
+            import torch
+            if logdet:
+                ld = torch.empty(B, dtype=torch.float64, device=z.device); lp = C.c_void_p(ld.data_ptr())
+            if valid:
+                vd = torch.empty(B, dtype=torch.uint8, device=z.device); vp = C.c_void_p(vd.data_ptr())
+        else:
+            if logdet:
+                ld = np.empty(B, np.float64); lp = C.c_void_p(ld.ctypes.data)
+            if valid:
+                vd = np.empty(B, np.uint8); vp = C.c_void_p(vd.ctypes.data)
+        (zp, xp), dev, keep = self._ptrs((z, (B, self.A - 1, 3), False, "z"), (x, (B, self.A, 3), True, "out"))
+        _lib.check(_lib.lib().ti_obs_zmat_xyz(self.h, op_, rp, zp, B, xp, lp, vp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        res = (x,) + ((ld,) if logdet else ()) + ((vd,) if valid else ())
+        return res[0] if len(res) == 1 else res
 
     def _obs_x_shape(self, x):
         B = self._check_x(x)

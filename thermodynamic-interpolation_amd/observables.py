@@ -22,6 +22,10 @@ on the GPU too (ti_obs_gedmd_spectrum: a batched Hermitian Jacobi eigensolver in
 p = 300); ``gedmd_cv`` / ``gedmd_model_selection`` are the reference's cross-validated choice of (sigma, p) (gedmd/rff.py
 cv_generator_rff and the two model_selection.py scripts), scored by ``gedmd_vamp_score`` from held-out Gram matrices.
 
+Z-matrix coordinates (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols; zmatrix.py, re-exported here): ``zmatrix`` / ``zmatrix_xyz`` are
+the reference's construct_z_matrix_batch / deconstruct_z_matrix_batch with its log-determinant and validity screen,
+``zmatrix_marginals`` the weighted marginals of all 3A - 6 internal coordinates in one call, ``iqr_keep`` its IQR keep mask.
+
 Beyond that p x p algebra the only arithmetic in this module is turning a histogram into a free-energy profile, forming phi from
 its terms, and the difference of two bootstrap runs in ``free_energy_bg``.
 """
@@ -32,6 +36,8 @@ import collections
 import numpy as np
 
 from . import _lib
+from .zmatrix import (ZMatrix, ZMarginals, bond_angles, bond_lengths, iqr_keep, torsions, zmatrix, zmatrix_marginals,  # noqa: F401
+                      zmatrix_xyz)
 
 _ARITY = {"rmsd": 0, "dist": 2, "angle": 3, "torsion": 4, "coord": 1}
 _NAMES = {v: k for k, v in _lib.OBS_KINDS.items()}
