@@ -478,6 +478,40 @@ typedef struct { int32_t d, p, nev, reserved; double a, tol; } ti_gedmd_desc;   
    omega [d, p] fp64, host */
 int ti_obs_gedmd_spectrum(ti_handle* h, const double* gram, int64_t n_mat, const double* omega, const ti_gedmd_desc* g,
                           double* ev, double* vec, int32_t* rank, int mem);
+/* ti_obs_eigh for orders up to TI_EIGH_WIDE_MAX_N: the arguments, the triangle that is read, the order of w, the staging, the mem modes
+ * and the refusals are those of ti_obs_eigh; only the range of n differs.  n <= 64 runs the kernel of ti_obs_eigh and returns the
+ * bits it returns.  Beyond that A and V live in buffers of the handle in global memory and the method is a blocked two-sided Jacobi:
+ *   thr = 2^-53 max_k |A[k,k] of the input|, of the whole matrix.  Blocks are 32 indices wide: nb = ceil(n / 32) of them, the last may
+ *   be narrow; mb = nb rounded up to even.  An outer sweep is the mb - 1 rounds of ti_obs_eigh's tournament over the mb block slots
+ *   (slot 0 holds block 0, slot k >= 1 block 1 + (k - 1 + r) mod (mb - 1), slot i meets slot mb - 1 - i); a pair that holds the pad
+ *   block is skipped.  The block pairs of a round are disjoint and every one is formed from the matrix as it stands at the start of
+ *   the round.
+ *   The visit of a block pair I < J: S = A[idx, idx] on the <= 64 indices idx of I then J.  ONE sweep of ti_obs_eigh's cyclic Jacobi
+ *   is applied to S in LDS -- all rounds of the tournament over its order (rounded up to even), the same rotation formulas, exact
+ *   zeros and real diagonal -- with the threshold thr above, not one derived from S; U is the product of its rotations, accumulated
+ *   from the identity.  Nothing is sorted.  Then, for all pairs of the round, A[:, idx] <- A[:, idx] U and V[:, idx] <- V[:, idx] U,
+ *   then A[idx, :] <- U^H A[idx, :], and A[idx, idx] becomes what the inner sweep left.  The products are real fp64 products on the matrix
+ *   cores (v_mfma_f64_16x16x4_f64, as in ti_obs_rff_gram), summed over the indices of idx in ascending order, four per instruction:
+ *   re += x.re u.re, re += (-x.im) u.im, im += x.re u.im, im += x.im u.re, in this order (x conjugated first where U^H is applied).
+ *   A pair whose inner sweep rotated nothing leaves the matrix as it is.
+ *   The iteration ends after the first outer sweep in which no visit rotated; sweeps counts that sweep too.  w is the diagonal in
+ *   ascending order, equal values by position, v the columns of V in that order.
+ * The host reads one status word per matrix after every outer sweep; workgroups of a finished matrix exit at once.  No atomics, no
+ * waiting of one workgroup on another: kernel boundaries on the handle's stream are the only synchronisation.  A launch takes
+ * ti_obs_eigh_wide_launch_max(n) matrices.  The result is a function of the matrix alone, as for ti_obs_eigh.
+ * TI_E_ARG, before any device work: as ti_obs_eigh with n outside 1..TI_EIGH_WIDE_MAX_N.  TI_E_NAN and TI_E_UNSUPPORTED (64 outer
+ * sweeps) as ti_obs_eigh, nothing written. */
+#define TI_EIGH_WIDE_MAX_N 1024
+int ti_obs_eigh_wide(ti_handle* h, const double* a, int64_t n_mat, int32_t n, double* w, double* v, int32_t* sweeps, int mem);
+/* Matrices per launch of the blocked solver at order n: min(512, 2^31 / (32 n^2)), A and V at 32 n^2 bytes a matrix; 0 for n outside
+ * 1..TI_EIGH_WIDE_MAX_N.  Needs no handle. */
+int64_t ti_obs_eigh_wide_launch_max(int32_t n);
+/* ti_obs_gedmd_spectrum for 1 <= p <= TI_EIGH_WIDE_MAX_N: the same arguments, definitions, outputs and refusals; only the range of p
+ * differs.  p <= 64 is ti_obs_gedmd_spectrum itself and returns its bits.  Beyond that both solves are ti_obs_eigh_wide's (a reduced
+ * matrix of order r <= 64 goes through ti_obs_eigh's kernel), and L, T = ((-a/2) K o G) L and R = L^H T are global-memory products of
+ * plain fp64 multiply-adds, every entry summed over its index in ascending order. */
+int ti_obs_gedmd_spectrum_wide(ti_handle* h, const double* gram, int64_t n_mat, const double* omega, const ti_gedmd_desc* g,
+                               double* ev, double* vec, int32_t* rank, int mem);
 /* Force-field energies: the reduced potential energies the weight estimators above take (E0s, E1s of the reference's
  * mdqm9/analysis/utils/ess.py:8-10), for what mdqm9/analysis/eval_energy.py evaluates one conformation at a time through OpenMM:
  * the HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce and NonbondedForce (NoCutoff, vacuum) of

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "ti_obs_rff_gram_wide",
     "ti_obs_ff_set", "ti_obs_ff_energy", "ti_obs_ti_logw",
     "ti_obs_zmat", "ti_obs_zmat_xyz", "ti_obs_hist_cols",
+    "ti_obs_eigh_wide", "ti_obs_eigh_wide_launch_max", "ti_obs_gedmd_spectrum_wide",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -56,6 +57,13 @@ GRAM_MAX_D, GRAM_MAX_P, GRAM_MAX_TABLE = 16, 128, 1 << 27
 GRAM_WIDE_MAX_P = 1024
 # ti_obs_eigh / ti_obs_gedmd_spectrum: the largest matrix order (TI_EIGH_MAX_N), the sweep cap, the most matrices of a call
 EIGH_MAX_N, EIGH_MAX_SWEEPS, EIGH_MAX_MATRICES = 64, 64, BOOT_MAX_RESAMPLES + 1
+# ti_obs_eigh_wide / ti_obs_gedmd_spectrum_wide: the largest order of the blocked solver (TI_EIGH_WIDE_MAX_N)
+EIGH_WIDE_MAX_N = 1024
+
+
+def eigh_wide_launch_max(n):
+    """Matrices of order n one launch of the blocked solver takes (ti_obs_eigh_wide_launch_max: the library's own statement)"""
+    return int(lib().ti_obs_eigh_wide_launch_max(int(n)))
 # ti_obs_ff_set: the caps of the four tables (TI_FF_MAX_*), R in kJ / (mol K) (TI_FF_GAS_CONSTANT), OpenMM's ONE_4PI_EPS0 in kJ nm / (mol e^2)
 FF_MAX_BONDS, FF_MAX_ANGLES, FF_MAX_TORSIONS, FF_MAX_PAIRS = 64, 128, 512, 300
 FF_GAS_CONSTANT, FF_COULOMB = 0.00831446261815324, 138.935456
@@ -187,6 +195,10 @@ def lib():
     L.ti_obs_rff_gram_wide.argtypes = L.ti_obs_rff_gram.argtypes
     L.ti_obs_eigh.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int]
     L.ti_obs_gedmd_spectrum.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_double), C.POINTER(GedmdDesc), vp, vp, vp, C.c_int]
+    L.ti_obs_eigh_wide.argtypes = L.ti_obs_eigh.argtypes
+    L.ti_obs_eigh_wide_launch_max.restype = C.c_int64
+    L.ti_obs_eigh_wide_launch_max.argtypes = [C.c_int32]
+    L.ti_obs_gedmd_spectrum_wide.argtypes = L.ti_obs_gedmd_spectrum.argtypes
     dp = C.POINTER(C.c_double)
     L.ti_obs_ff_set.argtypes = [vp, C.POINTER(FfDesc), ip, dp, ip, dp, ip, dp, dp]
     L.ti_obs_ff_energy.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]

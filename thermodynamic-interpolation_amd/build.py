@@ -29,6 +29,9 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "pai
            "obs_gram_kernels.hip",
            # batched Hermitian Jacobi eigensolver in LDS and the gEDMD algebra around it (ti_obs_eigh, ti_obs_gedmd_spectrum)
            "obs_eig_kernels.hip",
+           # the blocked eigensolver from global memory for orders 65..1024 and the wide gEDMD algebra (ti_obs_eigh_wide,
+           # ti_obs_gedmd_spectrum_wide): a unit of its own, obs_eig_kernels.hip's code objects stay as they were
+           "obs_eig_wide_kernels.hip",
            # force-field energies of a batch and the TI log-weights from them (ti_obs_ff_energy, ti_obs_ti_logw)
            "obs_ff_kernels.hip",
            # Z-matrix coordinates both ways and the histograms of all columns in one launch (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols)

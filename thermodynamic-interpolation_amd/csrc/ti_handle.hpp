@@ -162,6 +162,11 @@ struct ti_handle {
     // eigensolver and gEDMD algebra (ti_obs_eigh, ti_obs_gedmd_spectrum): the staged input of a host call; eigenvalues, eigenvectors and
     // status words of the first and second solve; K, the reduced matrices of one launch, the ranks; the results ahead of their validation
     DevBuf<double> eig_a, eig_w, eig_v, eig_w2, eig_v2, eig_k, eig_r, eig_ev, eig_vec; DevBuf<int32_t> eig_st, eig_st2, eig_rank;
+    // blocked eigensolver and wide gEDMD algebra (ti_obs_eigh_wide, ti_obs_gedmd_spectrum_wide): A, V, the pair rotations and swept
+    // blocks, thresholds and flag words of one launch; the singular values, L, T, the per-solver orders and the status words of the
+    // second solve by either kernel
+    DevBuf<double> eigw_a, eigw_v, eigw_u, eigw_s, eigw_thr, eigw_sv, eigw_l, eigw_t;
+    DevBuf<int32_t> eigw_rot, eigw_prot, eigw_st, eigw_nvn, eigw_nvw, eigw_live, eigw_st2n;
     // force field (ti_obs_ff_set; painn handles): the term words and parameters of the four tables as validated and packed by the
     // host (ti_internal.hpp FfParams), their lengths (ff_on: a force field is in force); staging of a host call's temperatures,
     // energies, term sums, reduced energies and log-weights (ti_obs_ff_energy, ti_obs_ti_logw)

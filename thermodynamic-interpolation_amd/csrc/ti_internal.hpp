@@ -511,4 +511,45 @@ hipError_t launch_obs_gedmd_reduce(const double* gram, const double* w1, const d
 hipError_t launch_obs_gedmd_back(const double* w1, const double* u1, const double* w2, const double* v2, const int* status2, const int* rank,
                                  int nev, int p, double* ev, double* vec, long long n_mat, hipStream_t st);
 
+// ---- blocked eigensolver from global memory and the wide gEDMD algebra (obs_eig_wide_kernels.hip; include/ti_hip.h ti_obs_eigh_wide,
+// ti_obs_gedmd_spectrum_wide)
+constexpr int EIGW_MAX_N = TI_EIGH_WIDE_MAX_N, EIGW_BLK = 32, EIGW_PAIR = 2 * EIGW_BLK;
+// the one statement of the launch rule (ti_obs_eigh_wide_launch_max): A and V of a launch stay within 2 GiB, 512 matrices at the most
+inline long long eigw_launch_max(int n)
+{
+    if (n < 1 || n > EIGW_MAX_N) return 0;
+    const long long fit = ((long long)1 << 31) / (32LL * n * n);
+    return fit < 512 ? fit : 512;
+}
+inline int eigw_slots(int n) { const int nb = (n + EIGW_BLK - 1) / EIGW_BLK; return nb + (nb & 1); }      // mb: block slots of the tournament
+// The work set of one launch of n_mat matrices of order n (row stride n), or of order nvec [i] <= n (below 65: the matrix is skipped).
+// status [i]: 0 while iterating, then the outer sweep count, -1 non-finite input, EIG_MAX_SWEEPS + 1 still rotating after the cap,
+// -2 skipped (eigw_finish turns it into 0)
+struct EigWide {
+    int n; const int* nvec; long long n_mat;
+    double *A, *V;                          // [n_mat][n][n][2]
+    double *U, *S;                          // [n_mat][eigw_slots(n) / 2][64][64][2]: the rotations and the swept block of every pair of a round
+    double* thr;                            // [n_mat]
+    int *rot, *prot, *status;               // [n_mat] something rotated this sweep, [n_mat][eigw_slots(n) / 2] per pair of the round, [n_mat]
+};
+// A, V = I, thr, status from a [n_mat] matrices mat_stride doubles apart with row stride lda
+hipError_t launch_eigw_init(const EigWide& e, const double* a, long long mat_stride, int lda, hipStream_t st);
+// round r of an outer sweep: the pair visits, then the column updates of A and V, then the row updates of A
+hipError_t launch_eigw_round(const EigWide& e, int r, hipStream_t st);
+// end of outer sweep `sweep`: a matrix that did not rotate gets status = sweep, one still rotating at the cap EIG_MAX_SWEEPS + 1
+hipError_t launch_eigw_sweep_end(const EigWide& e, int sweep, hipStream_t st);
+// w [n_mat][ldo] ascending and v [n_mat][ldo][ldo][2] (or NULL) of the matrices that converged
+hipError_t launch_eigw_finish(const EigWide& e, double* w, double* v, int ldo, hipStream_t st);
+// s [n_mat][p], rank, L [n_mat][p][p][2] (columns < rank) from the eigenpairs (w1, u1) of G; nv_narrow / nv_wide [i] = rank where the
+// second solve of matrix i is ti_obs_eigh's / the blocked one, else 0; live [i] = 1 where T and R are to be formed; a kept s of 0 puts
+// NaN into rmat [i][0][0]
+hipError_t launch_eigw_gedmd_rank(const double* w1, const double* u1, const int* status1, double tol, int nev, int p, double* s, double* L,
+                                  double* rmat, int* rank, int* nv_narrow, int* nv_wide, int* live, long long n_mat, hipStream_t st);
+// T = ((coef K) o G) L, then the upper triangle of the Hermitian part of L^H T into rmat (row stride p)
+hipError_t launch_eigw_gedmd_reduce(const double* gram, const double* kmat, double coef, const double* L, const int* rank, const int* live,
+                                    int p, double* T, double* rmat, long long n_mat, hipStream_t st);
+// ev, vec as launch_obs_gedmd_back; st2a + st2b is the status of the second solve (one of them is 0)
+hipError_t launch_eigw_gedmd_back(const double* L, const double* w2, const double* v2, const int* st2a, const int* st2b, const int* rank,
+                                  int nev, int p, double* ev, double* vec, long long n_mat, hipStream_t st);
+
 }  // namespace ti

@@ -146,6 +146,16 @@ def _gedmd_arrays(g, x0, x1, dlogp, beta0, beta1, solver=GEDMD_SOLVER):
 
 KINETICS_KEYS = {"columns": None, "p": 300, "sigma": 5.0, "nev": 4, "tol": 1e-4, "n_boot": 1000, "seed": 0, "temperature": None}
 KINETICS_KB = 0.008314462618        # kJ / (mol K), the reference's constant (mdqm9/analysis/gedmd.py)
+KINETICS_SOLVER = "host"       # default of the key observables.kinetics.solver: "host" (gedmd_generator) or "device" (gedmd_generator_wide)
+
+
+def _kinetics_solver(o):
+    """observables["kinetics"]["solver"] checked; the default without the key"""
+    g = dict(o).get("kinetics")
+    solver = g.get("solver", KINETICS_SOLVER) if isinstance(g, dict) else KINETICS_SOLVER
+    if solver not in _obs.SOLVERS:
+        raise ValueError(f"observables['kinetics']['solver'] must be one of {_obs.SOLVERS}, got {solver!r}")
+    return solver
 
 
 def _kinetics_settings(o, K=None):
@@ -154,9 +164,10 @@ def _kinetics_settings(o, K=None):
     g = dict(o).get("kinetics")
     if g is None:
         return None
-    if not isinstance(g, dict) or set(g) - set(KINETICS_KEYS) or "columns" not in g or "temperature" not in g:
-        raise ValueError(f"observables['kinetics'] must be a dict with 'columns', 'temperature' and keys out of {sorted(KINETICS_KEYS)}, got {g!r}")
-    g = {**KINETICS_KEYS, **g}
+    if not isinstance(g, dict) or set(g) - set(KINETICS_KEYS) - {"solver"} or "columns" not in g or "temperature" not in g:
+        raise ValueError(f"observables['kinetics'] must be a dict with 'columns', 'temperature' and keys out of {sorted(KINETICS_KEYS) + ['solver']}, got {g!r}")
+    _kinetics_solver(o)
+    g = {**KINETICS_KEYS, **{k: v for k, v in g.items() if k != "solver"}}
     for k in ("p", "nev", "n_boot", "seed"):
         if isinstance(g[k], bool) or int(g[k]) != g[k] or int(g[k]) < (0 if k == "seed" else 1):
             raise ValueError(f"observables['kinetics'][{k!r}] must be an integer >= {0 if k == 'seed' else 1}, got {g[k]!r}")
@@ -188,12 +199,14 @@ def _check_kinetics(config, molecules=True):
     _kinetics_settings(o, len(dict(o)["descriptors"]))
 
 
-def _kinetics_arrays(g, cv_end):
+def _kinetics_arrays(g, cv_end, solver=KINETICS_SOLVER):
     """kinetics_eigenvalues [nev], kinetics_ci [2, nev], kinetics_rank of the selected columns of the end-state CVs cv_end [B, K]:
-    the unweighted generator spectrum of the reference's mdqm9/analysis/gedmd.py, a = k_B T."""
+    the unweighted generator spectrum of the reference's mdqm9/analysis/gedmd.py, a = k_B T.  solver "device": the same arguments to
+    observables.gedmd_generator_wide, the p x p algebra on the GPU as well."""
     x = np.ascontiguousarray(cv_end[:, g["columns"]], np.float32)
     omega = _obs.sample_rff_gaussian(x.shape[1], g["p"], g["sigma"], g["seed"])
-    res = _obs.gedmd_generator(x, omega, g["nev"], KINETICS_KB * float(g["temperature"]), tol=g["tol"], n_boot=g["n_boot"], seed=g["seed"])
+    generator = _obs.gedmd_generator_wide if solver == "device" else _obs.gedmd_generator
+    res = generator(x, omega, g["nev"], KINETICS_KB * float(g["temperature"]), tol=g["tol"], n_boot=g["n_boot"], seed=g["seed"])
     return dict(kinetics_eigenvalues=res.eigenvalues, kinetics_ci=res.ci, kinetics_rank=np.int64(res.rank))
 
 
@@ -349,7 +362,7 @@ def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=
         extra.update(_gedmd_arrays(g, gedmd[0], gedmd[1], dl, gedmd[2], gedmd[3], solver=_gedmd_solver(config.observables)))
     k = _kinetics_settings(config.observables, cv.shape[2])
     if k is not None:
-        extra.update(_kinetics_arrays(k, cv[-1]))
+        extra.update(_kinetics_arrays(k, cv[-1], solver=_kinetics_solver(config.observables)))
     if energy is not None:
         extra.update(_energy_arrays(config, energy[0], energy[1], dl))
     if zmat is not None:                       # (settings, z0, z1) of a run with the zmatrix key

@@ -306,13 +306,13 @@ class _Engine:
         out = np.empty(shape, getattr(np, dtype))
         return out, C.c_void_p(out.ctypes.data)
 
-    def eigh(self, a, vectors=True):
+    def eigh(self, a, vectors=True, _entry="ti_obs_eigh", _max_n=_lib.EIGH_MAX_N):
         """ti_obs_eigh: (w [.., n] float64 ascending, v [.., n, n] complex128 or None, sweeps [..] int32) of a stack a [.., n, n] of
         Hermitian matrices, n <= 64, as numpy.linalg.eigh(a, UPLO="U"): parallel cyclic Jacobi, one workgroup per matrix.  Lives
         where a lives (numpy, or a CUDA complex128 tensor)."""
         ap, keep, dev, shape = self._complex_stack(a, "a")
-        if len(shape) < 2 or shape[-1] != shape[-2] or not 1 <= shape[-1] <= _lib.EIGH_MAX_N:
-            raise ValueError(f"a must be [.., n, n] with 1 <= n <= {_lib.EIGH_MAX_N}, got {tuple(shape)}")
+        if len(shape) < 2 or shape[-1] != shape[-2] or not 1 <= shape[-1] <= _max_n:
+            raise ValueError(f"a must be [.., n, n] with 1 <= n <= {_max_n}, got {tuple(shape)}")
         n, lead = int(shape[-1]), tuple(shape[:-2])
         n_mat = int(np.prod(lead, dtype=np.int64))
         if not 1 <= n_mat <= _lib.EIGH_MAX_MATRICES:
@@ -321,7 +321,7 @@ class _Engine:
         w, wp = self._eig_out(like, (*lead, n), "float64")
         v, vp = self._eig_out(like, (*lead, n, n, 2), "float64") if vectors else (None, None)
         sw, sp = self._eig_out(like, lead, "int32")
-        _lib.check(_lib.lib().ti_obs_eigh(self.h, ap, n_mat, n, wp, vp, sp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        _lib.check(getattr(_lib.lib(), _entry)(self.h, ap, n_mat, n, wp, vp, sp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         if v is not None:
             if dev:
                 import torch
@@ -330,7 +330,16 @@ class _Engine:
                 v = v.view(np.complex128)[..., 0]
         return w, v, sw
 
-    def gedmd_spectrum(self, gram, omega, a, nev, tol=0.0, vectors=True):
+    def eigh_wide(self, a, vectors=True):
+        """ti_obs_eigh_wide: ``eigh`` for n <= 1024.  n <= 64 returns the bits of ``eigh``; beyond that a blocked Jacobi method works
+        from global memory and sweeps counts its outer sweeps."""
+        return self.eigh(a, vectors, _entry="ti_obs_eigh_wide", _max_n=_lib.EIGH_WIDE_MAX_N)
+
+    def gedmd_spectrum_wide(self, gram, omega, a, nev, tol=0.0, vectors=True):
+        """ti_obs_gedmd_spectrum_wide: ``gedmd_spectrum`` for p <= 1024 (p <= 64: the bits of ``gedmd_spectrum``)."""
+        return self.gedmd_spectrum(gram, omega, a, nev, tol, vectors, _entry="ti_obs_gedmd_spectrum_wide")
+
+    def gedmd_spectrum(self, gram, omega, a, nev, tol=0.0, vectors=True, _entry="ti_obs_gedmd_spectrum"):
         """ti_obs_gedmd_spectrum: (ev [.., nev] float64, vec [.., p, nev] complex128 or None, rank [..] int32) of a stack of Gram
         matrices [.., p, p], p <= 64 (numpy, or a CUDA complex128 tensor such as ``rff_gram`` returns: it stays on the GPU) and omega
         [d, p] float64 (host).  Lives where gram lives."""
@@ -348,8 +357,8 @@ class _Engine:
         vec, vp = self._eig_out(like, (*lead, p, nev, 2), "float64") if vectors else (None, None)
         rank, rp = self._eig_out(like, lead, "int32")
         desc = _lib.GedmdDesc(d, p, nev, 0, float(a), float(tol))
-        _lib.check(_lib.lib().ti_obs_gedmd_spectrum(self.h, gp, n_mat, om.ctypes.data_as(C.POINTER(C.c_double)), C.byref(desc), ep, vp, rp,
-                                                    _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        _lib.check(getattr(_lib.lib(), _entry)(self.h, gp, n_mat, om.ctypes.data_as(C.POINTER(C.c_double)), C.byref(desc), ep, vp, rp,
+                                               _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         if vec is not None:
             if dev:
                 import torch

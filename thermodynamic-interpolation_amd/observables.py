@@ -210,7 +210,24 @@ def _check_solver(solver, p):
     if solver not in SOLVERS:
         raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
     if solver == "device" and p > _lib.EIGH_MAX_N:
-        raise ValueError(f"solver='device' takes p <= {_lib.EIGH_MAX_N} (the matrices live in LDS), got p = {p}: use solver='host'")
+        raise ValueError(f"solver='device' takes p <= {_lib.EIGH_MAX_N} (the matrices live in LDS), got p = {p}: use solver='host', or the "
+                         f"blocked device route gedmd_spectrum_wide / gedmd_generator_wide (p <= {_lib.EIGH_WIDE_MAX_N})")
+
+
+def _check_spectrum_args(gram, p, a, nev, tol):
+    shape = tuple(gram.shape) if hasattr(gram, "shape") else np.shape(gram)
+    if shape[-2:] != (p, p):
+        raise ValueError(f"gram must be [.., {p}, {p}], got {shape}")
+    if isinstance(nev, bool) or int(nev) != nev or not 1 <= int(nev) <= p:
+        raise ValueError(f"nev must be an integer in 1..p = {p}, got {nev!r}")
+    if not np.isfinite(a) or not np.isfinite(tol) or tol < 0:
+        raise ValueError(f"a must be finite and tol finite and >= 0, got {(a, tol)}")
+
+
+def _device_spectrum(call, gram, omega, a, nev, tol):
+    ev, vec, rank = call(gram, omega, a, int(nev), tol)
+    host = lambda t: t.detach().cpu().numpy() if hasattr(t, "data_ptr") else t
+    return host(ev), host(vec), host(rank).astype(np.int64)
 
 
 def eigh_batched(a, vectors=True, engine=None):
@@ -231,17 +248,9 @@ def gedmd_spectrum(gram, omega, a, nev, tol=0.0, solver="host", engine=None):
     omega = np.asarray(omega, np.float64)
     p = omega.shape[1]
     _check_solver(solver, p)
-    shape = tuple(gram.shape) if hasattr(gram, "shape") else np.shape(gram)
-    if shape[-2:] != (p, p):
-        raise ValueError(f"gram must be [.., {p}, {p}], got {shape}")
-    if isinstance(nev, bool) or int(nev) != nev or not 1 <= int(nev) <= p:
-        raise ValueError(f"nev must be an integer in 1..p = {p}, got {nev!r}")
-    if not np.isfinite(a) or not np.isfinite(tol) or tol < 0:
-        raise ValueError(f"a must be finite and tol finite and >= 0, got {(a, tol)}")
+    _check_spectrum_args(gram, p, a, nev, tol)
     if solver == "device":
-        ev, vec, rank = (engine or _service_engine(_device_of(gram))).gedmd_spectrum(gram, omega, a, int(nev), tol)
-        host = lambda t: t.detach().cpu().numpy() if hasattr(t, "data_ptr") else t
-        return host(ev), host(vec), host(rank).astype(np.int64)
+        return _device_spectrum((engine or _service_engine(_device_of(gram))).gedmd_spectrum, gram, omega, a, nev, tol)
     G = np.asarray(gram.detach().cpu().numpy() if hasattr(gram, "data_ptr") else gram, np.complex128)
     nev, lead = int(nev), G.shape[:-2]
     G = G.reshape(-1, p, p)
@@ -263,6 +272,25 @@ def gedmd_spectrum(gram, omega, a, nev, tol=0.0, solver="host", engine=None):
     return d.reshape(*lead, nev), W.reshape(*lead, p, nev), rank.reshape(lead)
 
 
+def eigh_batched_wide(a, vectors=True, engine=None):
+    """``eigh_batched`` for n <= 1024 (ti_obs_eigh_wide).  Up to n = 64 it is ``eigh_batched`` bit for bit; beyond, a blocked two-sided
+    Jacobi method works on 32-wide index blocks from global memory (one LDS Jacobi sweep per visit of a block pair) and sweeps counts
+    its outer sweeps.  Bit for bit the same for a matrix wherever it stands in the stack.  Lives where a lives."""
+    return (engine or _service_engine(_device_of(a))).eigh_wide(a, vectors=vectors)
+
+
+def gedmd_spectrum_wide(gram, omega, a, nev, tol=0.0, engine=None):
+    """``gedmd_spectrum`` on the GPU for p <= 1024 (ti_obs_gedmd_spectrum_wide): the same definitions, checks and return types; both
+    solves by ``eigh_batched_wide``'s method.  p <= 64 gives the bits of ``gedmd_spectrum(solver="device")``.  A CUDA-tensor gram
+    stays on the GPU and only the three results come back."""
+    omega = np.asarray(omega, np.float64)
+    p = omega.shape[1]
+    if p > _lib.EIGH_WIDE_MAX_N:
+        raise ValueError(f"gedmd_spectrum_wide takes p <= {_lib.EIGH_WIDE_MAX_N}, got p = {p}: use gedmd_spectrum(solver='host')")
+    _check_spectrum_args(gram, p, a, nev, tol)
+    return _device_spectrum((engine or _service_engine(_device_of(gram))).gedmd_spectrum_wide, gram, omega, a, nev, tol)
+
+
 GedmdResult = collections.namedtuple("GedmdResult", "eigenvalues ci estimates eigenvectors rank")
 GedmdResult.__doc__ = """eigenvalues [nev]: the generator eigenvalues of the whole sample, ascending (the last is ~0; the reference reports
 their negatives); ci [2, nev]: percentiles of the resample estimates; estimates [n_boot, nev]; eigenvectors [p, nev] and rank of the
@@ -280,12 +308,24 @@ def gedmd_generator(values, omega, nev, a, tol=0.0, logw=None, n_boot=1000, leve
     _check_solver(solver, np.shape(omega)[-1] if np.ndim(omega) else 0)
     gram = rff_gram_wide if np.ndim(omega) == 2 and np.shape(omega)[1] > _lib.GRAM_MAX_P else rff_gram
     G = gram(values, omega, logw=logw, n_boot=n_boot, seed=seed, first=first, indices=indices, engine=engine)
-    d, W, r = gedmd_spectrum(G, omega, a, nev, tol, solver=solver, engine=engine)
+    return _generator_result(*gedmd_spectrum(G, omega, a, nev, tol, solver=solver, engine=engine), level)
+
+
+def _generator_result(d, W, r, level):
     est = d[1:]
     ci = np.full((2, d.shape[1]), np.nan)
     if est.shape[0] and not np.isnan(est).any():
         ci = np.percentile(est, [50 * (1 - float(level)), 50 * (1 + float(level))], axis=0)
     return GedmdResult(d[0], ci, est, W[0], int(r[0]))
+
+
+def gedmd_generator_wide(values, omega, nev, a, tol=0.0, logw=None, n_boot=1000, level=0.95, seed=0, first=0, indices=None, engine=None):
+    """``gedmd_generator`` with the whole chain on the GPU for p <= 1024: ``rff_gram_wide``, then ``gedmd_spectrum_wide`` on the Gram
+    stack where it lies, then the same percentile rule.  Only the spectra, the point estimate's eigenvectors and the ranks come back."""
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must be in (0, 1), got {level!r}")
+    G = rff_gram_wide(values, omega, logw=logw, n_boot=n_boot, seed=seed, first=first, indices=indices, engine=engine)
+    return _generator_result(*gedmd_spectrum_wide(G, omega, a, nev, tol, engine=engine), level)
 
 
 def gedmd_vamp_score(gram_test, omega, a, W):

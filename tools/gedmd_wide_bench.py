@@ -17,10 +17,14 @@ CPU: tests/gedmd_numpy.py svd_route -- the reference's algorithm, an SVD of the 
 --cpu-resamples resamples and scaled to 1000: the loop is linear in the resamples.
 The Gram pass's arithmetic per call: 4 MFMAs of 2 * 16 * 16 * 4 flop per upper-triangle tile and 4 draws; its gathered bytes: a diagonal
 panel pair reads its panel's 2 * 8 * 16 columns per draw, an off-diagonal pair both panels'.
+  wide       the blocked device route: observables.gedmd_spectrum_wide alone on the Gram stack where it lies (the spectrum stage) and
+             observables.gedmd_generator_wide (the whole call), medians of --wide-reps calls after one warm-up, with the largest
+             difference of their spectra from the host route's (--wide-reps 0 leaves the stage out)
 --gram-only: two Gram calls per size and nothing else (the run to put under rocprofv3 --kernel-trace --stats).
+--spectrum-only: one Gram call and two gedmd_spectrum_wide calls per size and nothing else (the same, for the blocked solver's kernels).
 Prints one JSON line per size and one per cv.
 
-    python tools/gedmd_wide_bench.py [--reps 7] [--algebra-reps 1] [--cpu-resamples 3] [--gram-only]
+    python tools/gedmd_wide_bench.py [--reps 7] [--algebra-reps 1] [--wide-reps 7] [--cpu-resamples 3] [--gram-only | --spectrum-only]
 """
 import argparse
 import importlib
@@ -69,7 +73,9 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[25000, 100000])
     ap.add_argument("--p", type=int, default=300)
     ap.add_argument("--cv-ps", type=int, nargs="*", default=[300, 1000])
+    ap.add_argument("--wide-reps", type=int, default=7)
     ap.add_argument("--gram-only", action="store_true")
+    ap.add_argument("--spectrum-only", action="store_true")
     args = ap.parse_args()
     import torch
     import gedmd_numpy as gn
@@ -86,6 +92,11 @@ def main():
             for _ in range(2):
                 obs.rff_gram_wide(dev, omega, n_boot=nb, seed=1, engine=eng)
             continue
+        if args.spectrum_only:
+            G = obs.rff_gram_wide(dev, omega, n_boot=nb, seed=1, engine=eng)
+            for _ in range(2):
+                obs.gedmd_spectrum_wide(G, omega, a, nev, tol, engine=eng)
+            continue
         gram_ms, gram_min = timed_ms(lambda: obs.rff_gram_wide(dev, omega, n_boot=nb, seed=1, engine=eng), args.reps, True)
         flop = (n * (1 + nb) / 4) * (T * (T + 1) / 2) * 4 * 2 * 16 * 16 * 4
         rec = dict(n=n, d=d, p=p, resamples=nb, gram_ms=gram_ms, gram_ms_min=gram_min, gram_call_tflops=flop / (gram_ms * 1e-3) / 1e12,
@@ -94,7 +105,19 @@ def main():
         res = []
         gen_ms, _ = timed_ms(lambda: res.append(obs.gedmd_generator(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng)), args.algebra_reps, False)
         G = obs.rff_gram_wide(dev, omega, n_boot=nb, seed=1, engine=eng).cpu().numpy()
-        host_ms, _ = timed_ms(lambda: obs.gedmd_spectrum(G, omega, a, nev, tol), args.algebra_reps, False)
+        host = []
+        host_ms, _ = timed_ms(lambda: host.append(obs.gedmd_spectrum(G, omega, a, nev, tol)), args.algebra_reps, False)
+        if args.wide_reps > 0:
+            host_d = host[-1][0]
+            Gd, wide = obs.rff_gram_wide(dev, omega, n_boot=nb, seed=1, engine=eng), []
+            spec_ms, spec_min = timed_ms(lambda: wide.append(obs.gedmd_spectrum_wide(Gd, omega, a, nev, tol, engine=eng)), args.wide_reps, True)
+            del Gd
+            wgen_ms, wgen_min = timed_ms(lambda: obs.gedmd_generator_wide(dev, omega, nev, a, tol=tol, n_boot=nb, seed=1, engine=eng),
+                                         args.wide_reps, True)
+            rec.update(wide_spectrum_ms=spec_ms, wide_spectrum_ms_min=spec_min, wide_generator_ms=wgen_ms, wide_generator_ms_min=wgen_min,
+                       wide_reps=args.wide_reps, wide_against_host=float(np.abs(wide[-1][0] - host_d).max()),
+                       wide_ranks=[int(wide[-1][2].min()), int(wide[-1][2].max())], speedup_spectrum=host_ms / spec_ms,
+                       speedup_wide_generator=gen_ms / wgen_ms)
         del G
         c, ref = [], [np.full(nev, np.nan)]
         if args.cpu_resamples > 0:
@@ -108,7 +131,7 @@ def main():
                    eigenvalues=res[-1].eigenvalues.tolist(), ci=res[-1].ci.tolist(), rank=res[-1].rank, cpu_last_resample=ref[0].tolist(),
                    device=torch.cuda.get_device_name(0))
         print(json.dumps(rec), flush=True)
-    if args.gram_only:
+    if args.gram_only or args.spectrum_only:
         return
     n = args.sizes[0]
     dev = torch.from_numpy(samples(n, d, n)).cuda()
