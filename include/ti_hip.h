@@ -21,6 +21,8 @@
  *   ti_adw_drift_tv                   FCNetMultiBeta.forward with per-row ts                adw/thermo/models/simple.py:38-41
  *   ti_painn_drift_div_est / _est_tv  no reference counterpart: Hutchinson's estimate of the divergence ODEWrapper.compute_divergence
  *   ti_painn_rollout_dlogp_est        computes exactly (the FFJORD estimator; the reference ships the exact one only)
+ *   ti_painn_vloss / ti_adw_vloss     StandardVelocityLoss / OneSidedVelocityLoss.forward   mdqm9/thermo/{ambient,latent}/losses.py, adw/thermo/losses.py
+ *   + ti_*_vloss_interp               with LinearInterpolant / OneSidedLinearInterpolant    .../interpolants.py (forward evaluation only)
  *   TI_SCHEME_DOPRI5_TRAJ             the reference's dopri5 integration (integrators.py, odeint per mini-batch) evaluated for every
  *   + ti_rollout_step_counts          trajectory as if it were alone in its batch (a batch size of 1)
  *
@@ -658,6 +660,99 @@ int ti_painn_debug_pair_blocks(ti_handle* h, int32_t* G, int32_t* nblk, int32_t*
  * (the 8-instruction forms of formats (a) and (b) against the plain arithmetic, bit for bit, fp16-subnormal residuals included),
  * and of the fp16 matrix instruction keeping subnormal inputs. */
 int ti_selftest(int device);
+
+/* ---- velocity loss: the stochastic-interpolant objective a checkpoint was trained on, forward evaluation only ---------------------
+ * The reference's model-quality number (mdqm9/thermo/{ambient,latent}/losses.py, adw/thermo/losses.py with the interpolants.py beside
+ * them; evaluated on held-out pairs by train_ambient.py:153-157): antithetic states from an interpolant, the drift on both, and a
+ * per-molecule sum.  Three stages on the handle's stream, no atomics, every sum in an order fixed by the shapes alone, so a call
+ * repeats bit for bit.  State rows: a molecule's [A,3] coordinates (painn, m = 3A) or a particle's [d] (adw, m = d).
+ *
+ * Interpolate (fp64 from the fp32 inputs, one rounding to fp32).  With t_b the time of molecule / row b and z the noise:
+ *   TI_VLOSS_STANDARD   xt+- = (1 - t) x0 + t x1 +- gamma(t) z             (LinearInterpolant.calc_antithetic_xts)
+ *   TI_VLOSS_ONE_SIDED  xt+  = t x1 + (1 - t) x0, x0 being the noise itself  (OneSidedLinearInterpolant; the reference computes the
+ *                       minus state and discards it: it is neither written nor evaluated here, and z must be NULL)
+ *   gamma kinds (parameter a):  TI_GAMMA_BROWNIAN  gamma = sqrt(a t (1 - t)),  gamma' = a (1 - 2t) / (2 sqrt(a t (1 - t)))
+ *                               TI_GAMMA_SIN2      gamma = sin^2(pi t),        gamma' = 2 pi sin(pi t) cos(pi t)
+ *                               TI_GAMMA_SIG_SUM   gamma = 2.2 (s(u+) - s(u-) - s(1 - a/2) + s(-1 - a/2)),
+ *                                                  gamma' = 2.2 a ((1 - s(u+)) s(u+) - (1 - s(u-)) s(u-)),  u+- = a (t - 1/2) +- 1,
+ *                                                  s the logistic function; 2.2 is the float32 nearest to it, which is what the
+ *                                                  reference multiplies by (torch.tensor(2.2)).  The reference holds a as a float32
+ *                                                  tensor too: a is used as passed, so pass (double)(float)a to reproduce it (the
+ *                                                  Python mirror does)
+ *   centring:  TI_CENTER_BATCH     the reference's xt - mean(xt, dim=0): the mean over all B A atom rows of the CALL, per component,
+ *                                  separately for the plus and the minus half (so the result depends on how a set is cut into calls);
+ *                                  the column sums are taken over fixed tiles of 1024 rows in row order and the tile sums in tile order
+ *              TI_CENTER_MOLECULE  each molecule's own centre (atoms summed in order): independent of the other molecules
+ *              TI_CENTER_NONE      the only mode of an adw handle
+ *   z == NULL:  z[b,a,c] = N(seed, traj_offset + b, draw, 3a + c) (adw: component k), N the Philox normal of TI_SCHEME_EM with `draw`
+ *               in its step slot, AS THE HOST ORACLE RETURNS IT: oracle.normal regenerates every entry bit for bit.  The counter
+ *               slots and the fp32 Box-Muller expression are those of the EM noise; its logf, sinf and cosf are evaluated here by
+ *               the host libm's own algorithms restated in fp64 (glibc's since 2.28, which are the Arm Optimized Routines':
+ *               csrc/vloss_normal.hpp), where the EM noise kernels call the device's fp32 functions and agree with the oracle to the
+ *               last bits only.  The identity is therefore tied to that libm: an oracle built against another logf / sinf / cosf
+ *               may differ from z in the last bit.
+ *   t:  TI_TDIST_GIVEN  t [B] as passed (t == NULL otherwise).  Drawn times take ONE word per molecule,
+ *         o = Philox4x32-10(counter = (id & 0xffffffff, id >> 32, draw, TI_VLOSS_DOMAIN), key = (seed & 0xffffffff, seed >> 32)),
+ *         id = traj_offset + b,  u = ((o[0] >> 9) + 0.5) 2^-23 -- exact in fp32 and never 0 or 1 -- and
+ *         TI_TDIST_UNIFORM   t = u                                           (torch.rand)
+ *         TI_TDIST_BETA_HALF t = fp32(sin^2(pi u / 2)) in fp64               (Beta(1/2, 1/2), ambient t_distr = "beta")
+ *         TI_TDIST_BETA_2_1  t = fp32(sqrt(u)) in fp64                       (Beta(2, 1), latent t_distr = "beta")
+ *         each capped at 1 - 2^-24, the largest fp32 below 1, so that 0 < t < 1 always.
+ *       These draws follow the reference's DISTRIBUTIONS; they do not reproduce torch's random streams (neither for t nor for z).
+ * Drift.  One evaluation of the per-molecule-time drift (ti_painn_drift_tv / ti_adw_drift_tv) on the device-resident batch
+ *   [xt+; xt-] of 2B (one-sided: xt+, B) with times [t; t] and conditioning [cond; cond].  As for the drift itself, the layout
+ *   follows the evaluated batch size unless it is pinned (ti_painn_set_template).  In a layout that packs G > 1 molecules into a row
+ *   group a molecule's per-atom sums follow its slot in the group, so the batch is laid out with molecule b of either half at slot
+ *   (traj_offset + b) mod G -- up to G - 1 copies of the call's first molecule in front of each half, their results dropped; the
+ *   halves are written where they belong, so no pass over the states is added.  (The padded count is what the layout is chosen
+ *   from; should that choice not settle on one G within eight rounds, the batch is evaluated unaligned.)  With the
+ *   layout pinned and traj_offset the global index of molecule 0, l_b under TI_CENTER_MOLECULE and TI_CENTER_NONE is then the same
+ *   bits however a set is cut into calls (t and z always are); an adw row never depends on the others.  An edge mask in force (for B
+ *   molecules) applies to both halves, which are then evaluated one after the other as two batches of B, without that alignment.
+ * Reduce (fp64, element order).  With d = x1 - x0 and the sum over the m entries of a row:
+ *   STANDARD   l_b = sum [ b+^2 / 2 - (d + gamma' z) b+ + b-^2 / 2 - (d - gamma' z) b- ]        ONE_SIDED   l_b = sum [ b+^2 / 2 - d b+ ]
+ *   *out_mean = sum_b l_b / (B A) for molecules (the reference's mean over atom rows) and / B for adw; the sum over b runs over fixed
+ *   tiles of 1024 in index order, then over the tiles in order.  out_tbins [n_tbins][2]: sum of l_b and count of the molecules with
+ *   floor(t_b n_tbins) = k (t = 1 in the last bin), summed in index order.
+ * Buffers.  x0, x1 [B,m], cond (painn) / beta0, beta1 [B] (adw), t [B], z [B,m], out_t [B], out_z [B,m], out_xt, out_b [2,B,m]
+ *   (plus, then minus; ONE_SIDED writes the first half only) fp32 and out_loss [B] fp64: [host|device] by mem.  out_mean [1] and
+ *   out_tbins [n_tbins,2] fp64: host.  Every out_* but out_loss may be NULL; out_t / out_z return what the kernels used (out_z with
+ *   ONE_SIDED: nothing is written).  Outputs are copied from buffers of the handle after the whole call succeeded.
+ * TI_E_ARG, before any device work, in this order: a NULL descriptor; an unknown kind, gamma, center or t_dist; a <= 0 or not finite
+ *   where gamma uses it (STANDARD with BROWNIAN or SIG_SUM); n_tbins outside 0..TI_VLOSS_MAX_TBINS; B < 1; an unknown mem; ONE_SIDED
+ *   with a non-NULL z; t_dist GIVEN without t, or t with another t_dist; a given t in host memory outside [0, 1] or not finite, or equal
+ *   to 0 or 1 with STANDARD and BROWNIAN (gamma' is infinite there); a NULL buffer; a NULL or wrong-kind handle.
+ * TI_E_UNSUPPORTED: ti_painn_set_molecules in force (one species per call, as for ti_obs_ff_energy); BATCH or MOLECULE on an adw handle.
+ * TI_E_NAN: a non-finite l_b, naming the first such molecule (e.g. a given t in device memory at 0 with BROWNIAN, which is not read on
+ *   the host); no output is copied. */
+enum { TI_VLOSS_STANDARD = 0, TI_VLOSS_ONE_SIDED = 1 };
+enum { TI_GAMMA_BROWNIAN = 0, TI_GAMMA_SIN2 = 1, TI_GAMMA_SIG_SUM = 2 };
+enum { TI_CENTER_BATCH = 0, TI_CENTER_MOLECULE = 1, TI_CENTER_NONE = 2 };
+enum { TI_TDIST_GIVEN = 0, TI_TDIST_UNIFORM = 1, TI_TDIST_BETA_HALF = 2, TI_TDIST_BETA_2_1 = 3 };
+#define TI_VLOSS_DOMAIN 0x564c4f53u   /* the fourth counter word of the time draws ("VLOS") */
+#define TI_VLOSS_MAX_TBINS 1024
+typedef struct ti_vloss_desc {
+    int32_t  kind;         /* TI_VLOSS_* */
+    int32_t  gamma;        /* TI_GAMMA_*; ignored by ONE_SIDED */
+    double   a;            /* gamma's parameter */
+    int32_t  center;       /* TI_CENTER_* */
+    int32_t  t_dist;       /* TI_TDIST_* */
+    uint64_t seed;         /* Philox key of the drawn t and z */
+    int64_t  traj_offset;  /* global index of molecule 0 of this call: the draws do not depend on how a set is cut into calls */
+    int32_t  draw;         /* the draw index (the step slot of the counter) */
+    int32_t  n_tbins;      /* bins of the time profile; 0: none */
+} ti_vloss_desc;
+int ti_painn_vloss(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* cond, const float* t,
+                   const float* z, int64_t B, double* out_loss, double* out_mean, double* out_tbins, float* out_t, float* out_z,
+                   float* out_xt, float* out_b, int mem);
+int ti_adw_vloss(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* beta0, const float* beta1,
+                 const float* t, const float* z, int64_t B, double* out_loss, double* out_mean, double* out_tbins, float* out_t,
+                 float* out_z, float* out_xt, float* out_b, int mem);
+/* stage one alone: out_xt [2,B,m] is required, out_t and out_z may be NULL; same checks */
+int ti_painn_vloss_interp(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* t, const float* z,
+                          int64_t B, float* out_t, float* out_z, float* out_xt, int mem);
+int ti_adw_vloss_interp(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* t, const float* z,
+                        int64_t B, float* out_t, float* out_z, float* out_xt, int mem);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "ti_obs_ff_set", "ti_obs_ff_energy", "ti_obs_ti_logw",
     "ti_obs_zmat", "ti_obs_zmat_xyz", "ti_obs_hist_cols",
     "ti_obs_eigh_wide", "ti_obs_eigh_wide_launch_max", "ti_obs_gedmd_spectrum_wide",
+    "ti_painn_vloss", "ti_adw_vloss", "ti_painn_vloss_interp", "ti_adw_vloss_interp",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -69,6 +70,14 @@ FF_MAX_BONDS, FF_MAX_ANGLES, FF_MAX_TORSIONS, FF_MAX_PAIRS = 64, 128, 512, 300
 FF_GAS_CONSTANT, FF_COULOMB = 0.00831446261815324, 138.935456
 # ti_obs_zmat / ti_obs_zmat_xyz: the range of A; ti_obs_hist_cols: the most columns of a call
 ZMAT_MIN_ATOMS, ZMAT_MAX_ATOMS, HIST_COLS_MAX = 2, 32, 128
+# ti_*_vloss: loss kinds (TI_VLOSS_*), gamma kinds (TI_GAMMA_*), centring (TI_CENTER_*), time distributions (TI_TDIST_*), the fourth
+# counter word of the time draws, the most bins of a time profile
+VLOSS_KINDS = {"standard": 0, "one_sided": 1}
+VLOSS_GAMMAS = {"brownian": 0, "sin2": 1, "sig_sum": 2}
+VLOSS_CENTERS = {"batch": 0, "molecule": 1, "none": 2}
+VLOSS_TDISTS = {"given": 0, "uniform": 1, "beta_half": 2, "beta_2_1": 3}
+VLOSS_DOMAIN = 0x564C4F53
+VLOSS_MAX_TBINS = 1024
 
 
 class PainnDesc(C.Structure):
@@ -102,6 +111,11 @@ class GedmdDesc(C.Structure):
 
 class FfDesc(C.Structure):
     _fields_ = [("n_bonds", C.c_int32), ("n_angles", C.c_int32), ("n_torsions", C.c_int32), ("n_pairs", C.c_int32), ("coulomb", C.c_double)]
+
+
+class VlossDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("gamma", C.c_int32), ("a", C.c_double), ("center", C.c_int32), ("t_dist", C.c_int32),
+                ("seed", C.c_uint64), ("traj_offset", C.c_int64), ("draw", C.c_int32), ("n_tbins", C.c_int32)]
 
 
 class TiError(RuntimeError):
@@ -206,6 +220,11 @@ def lib():
     L.ti_obs_zmat.argtypes = [vp, ip, ip, vp, C.c_int64, vp, C.c_int]
     L.ti_obs_zmat_xyz.argtypes = [vp, ip, ip, vp, C.c_int64, vp, vp, vp, C.c_int]
     L.ti_obs_hist_cols.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int]
+    vd = C.POINTER(VlossDesc)
+    L.ti_painn_vloss.argtypes = [vp, vd, vp, vp, vp, vp, vp, C.c_int64, vp, dp, dp, vp, vp, vp, vp, C.c_int]
+    L.ti_adw_vloss.argtypes = [vp, vd, vp, vp, vp, vp, vp, vp, C.c_int64, vp, dp, dp, vp, vp, vp, vp, C.c_int]
+    L.ti_painn_vloss_interp.argtypes = [vp, vd, vp, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int]
+    L.ti_adw_vloss_interp.argtypes = [vp, vd, vp, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int]
     _lib = L
     return L
 

@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libti_hip.so")
-SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "painn_pack.hip", "painn_host.hip",      # host units (no kernels)
+SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api_vloss.hip", "painn_pack.hip", "painn_host.hip",      # host units (no kernels)
            "painn_kernels.hip", "painn_edge_nb1.hip", "painn_edge_nb2.hip", "painn_edge_nb4.hip", "painn_edge_nb8.hip",
            "painn_pair_nb1.hip", "painn_pair_nb2.hip", "painn_pair_nb4.hip", "painn_jvp_kernels.hip", "adw_kernels.hip", "ode_kernels.hip",
            # masked twins of the message kernels (per-molecule edge sets), in translation units of their own
@@ -36,9 +36,11 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "pai
            "obs_ff_kernels.hip",
            # Z-matrix coordinates both ways and the histograms of all columns in one launch (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols)
            "obs_zmat_kernels.hip",
+           # velocity loss (ti_painn_vloss, ti_adw_vloss): time draws, interpolant states and centring, per-molecule reduction, batch sums
+           "vloss_kernels.hip",
            # layer-0 phi table (class pass, table kernel); the pair kernel's table builds live in painn_pair_nb*.hip
            "painn_phi0_kernels.hip"]
-HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",
+HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "vloss_normal.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",
            "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
 # -packed-fp32-ops off: v_pk_{fma,mul,add}_f32 do NOT run next to another wave's matrix instructions on gfx950 (a wave of them and a
 # wave of 16x16x32 fp16 MFMAs on one SIMD take the SUM of their times; scalar v_fma_f32, conversions and transcendentals overlap:

@@ -50,6 +50,10 @@ void adw_drift_dev(ti_handle* h, const float* x_dev, float t, long long U, long 
     adw_mlp_launch(h, false, x_dev, nullptr, h->aemb_u.p, h->aidx.p, t, B, out_dev, out_div);             // net([x, t, embed])
 }
 
+}  // namespace
+
+namespace ti {
+
 // per-row times: beta_embed([b0_i, b1_i, t_i]) per row (no dedupe: the time differs per row), then net([x_i, t_i, emb_i]).
 // beta0 / beta1 / tv are device pointers [B].
 void adw_drift_tv_dev(ti_handle* h, const float* x_dev, const float* tv, const float* beta0, const float* beta1, long long B, float* out_dev,
@@ -59,10 +63,6 @@ void adw_drift_tv_dev(ti_handle* h, const float* x_dev, const float* tv, const f
     adw_mlp_launch(h, true, beta0, beta1, tv, nullptr, 0.f, B, h->aemb_r.p, nullptr);          // a2 = emb[r] = t_r
     adw_mlp_launch(h, false, x_dev, tv, h->aemb_r.p, nullptr, 0.f, B, out_dev, out_div);       // a1 = in1[r] = t_r
 }
-
-}  // namespace
-
-namespace ti {
 
 void ensure_adw_ws(ti_handle* h, long long B)
 {

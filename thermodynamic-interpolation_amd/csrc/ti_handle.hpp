@@ -175,6 +175,12 @@ struct ti_handle {
     // Z-matrix coordinates and column histograms (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols): the topology of the call (order,
     // ref), staging of a host call's z, log-determinants, validity and keep masks, the column ranges (lo [K], hi [K])
     DevBuf<int32_t> zm_topo; DevBuf<float> zm_z; DevBuf<double> zm_logdet, hc_range; DevBuf<uint8_t> zm_valid, hc_keep;
+    // velocity loss (ti_painn_vloss, ti_adw_vloss): every stage computes into these and the outputs are copied from them at the end.
+    // Staged inputs of a host call (x0, x1, z, conditioning); the times, the noise, the states [2][B][m] and the drift on them; the
+    // times and conditioning of the evaluated batch (both halves, with the pad molecules of a packed layout); the uncentred states, the tile partials, (column sums [32], mean, first
+    // bad index, time profile) and the losses
+    DevBuf<float> vl_x0, vl_x1, vl_zin, vl_c0, vl_c1, vl_t, vl_z, vl_xt, vl_b, vl_t2, vl_c02, vl_c12;
+    DevBuf<double> vl_raw, vl_part, vl_red, vl_loss;
 
     ~ti_handle()
     {
@@ -301,8 +307,10 @@ void phi0_end_call(ti_handle* h);
 int set_graph_state(ti_handle* h, std::vector<uint32_t>& m, std::vector<int32_t>& natoms, std::vector<uint8_t>& ptype, long long B);
 void clear_graph_state(ti_handle* h);
 
-// ---- api_adw.hip, api_obs.hip: what ti_reserve and the rollout drivers need of them
+// ---- api_adw.hip, api_obs.hip: what ti_reserve, the rollout drivers and the velocity loss need of them
 void ensure_adw_ws(ti_handle* h, long long B);
+void adw_drift_tv_dev(ti_handle* h, const float* x_dev, const float* tv, const float* beta0, const float* beta1, long long B, float* out_dev,
+                      float* out_div);
 void obs_cv_dev(ti_handle* h, int which, const float* x_dev, long long B, float* cv_dev);
 
 }  // namespace ti

@@ -552,4 +552,37 @@ hipError_t launch_eigw_gedmd_reduce(const double* gram, const double* kmat, doub
 hipError_t launch_eigw_gedmd_back(const double* L, const double* w2, const double* v2, const int* st2a, const int* st2b, const int* rank,
                                   int nev, int p, double* ev, double* vec, long long n_mat, hipStream_t st);
 
+// ---- velocity loss (vloss_kernels.hip; include/ti_hip.h ti_painn_vloss, ti_adw_vloss and their _interp twins)
+constexpr int VLOSS_TILE = 1024;            // rows per tile of the batch-wide sums: fixed, so a sum does not depend on the launch
+inline long long vloss_tiles(long long n) { return (n + VLOSS_TILE - 1) / VLOSS_TILE; }
+struct VlossParams {
+    int kind, gamma, center; double a;      // TI_VLOSS_*, TI_GAMMA_*, TI_CENTER_*
+    long long B; int m, A;                  // m floats per molecule / row; A atoms (adw: 1), m = A * (m / A) components per atom
+    const float *x0, *x1;                   // [B][m]
+    const float* t;                         // [B]
+    const float* z_in;                      // [B][m] or NULL: drawn
+    uint64_t seed; long long traj0; int draw;
+    float* z;                               // [B][m] the noise used (STANDARD)
+    double* raw;                            // [2][B][m] uncentred states (centre BATCH / MOLECULE)
+    const double* colsum;                   // [2][m / A] column sums of raw over the B A rows (BATCH)
+    float* xt;                              // the plus half [B][m]; the minus half starts `half` floats behind it
+    const float* b;                         // the drift on xt, laid out like xt
+    long long half;                         // B m, or more when pad molecules sit between the halves (api_vloss.hip)
+    double* loss;                           // [B]
+};
+// t [B] from the Philox word of molecule traj0 + b (include/ti_hip.h: TI_TDIST_UNIFORM / BETA_HALF / BETA_2_1)
+hipError_t launch_vloss_draw_t(float* t, int t_dist, uint64_t seed, long long traj0, int draw, long long B, hipStream_t st);
+// stage one, first pass: z and xt (TI_CENTER_NONE) or raw; second pass (the other centrings): xt from raw
+hipError_t launch_vloss_interp(const VlossParams& p, hipStream_t st);
+hipError_t launch_vloss_center(const VlossParams& p, hipStream_t st);
+// out [ncol] = the sums of v [n rows][ncol] over the rows: tiles of VLOSS_TILE rows in row order into partial [tiles][ncol], then the
+// tiles in order; ncol <= 16
+hipError_t launch_vloss_colsum(double* out, double* partial, const double* v, long long n, int ncol, hipStream_t st);
+// loss [B] from (x0, x1, t, z, b) of p
+hipError_t launch_vloss_reduce(const VlossParams& p, hipStream_t st);
+// out[0] = the smallest index of a non-finite loss as a double (+inf: none)
+hipError_t launch_vloss_first_bad(double* out, const double* loss, long long B, hipStream_t st);
+// out [n][2] = (sum of loss, count) of the rows with min(floor(t n), n - 1) == k, in index order
+hipError_t launch_vloss_tbins(double* out, const double* loss, const float* t, long long B, int n, hipStream_t st);
+
 }  // namespace ti

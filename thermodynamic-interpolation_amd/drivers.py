@@ -41,6 +41,11 @@ of the source ensemble and stay unweighted; the end state's marginals are weight
 it, and with ``iqr_k`` (which needs the energy key) the reference's filter_iqr(weights, k) mask -- written as ``zmat_keep`` [B] -- is
 applied to them.  The key is checked before the rollout; sample_latent and sample_adw refuse it.  Without the keys exactly the
 reference's files are written.
+
+  score_checkpoints <- the held-out evaluation of mdqm9/train_ambient.py:153-157, which decides what weights are kept
+Scores checkpoints by the velocity loss they were trained on (thermo.losses, on the GPU) and writes ``val_loss_{data_save_name}.npz``.
+Keys: ``gamma`` ('brownian' | 'sin2' | 'sig_sum') and ``t_distr`` ('uniform' | 'beta'), the reference's names; optional
+``interpolant_a`` (1.0), ``n_draws`` (1), ``center`` ('batch' for molecules; adw is never centred), ``tbins`` (0), ``seed`` (0).
 """
 from __future__ import annotations
 
@@ -55,6 +60,8 @@ from .thermo import adw as _adw
 from .thermo import ambient as _amb
 from .thermo import latent as _lat
 from .thermo import _common as C
+from .thermo import interpolants as _interp
+from .thermo import losses as _losses
 
 
 def load_config(path: str, filename: str, argv=()) -> argparse.Namespace:
@@ -486,3 +493,80 @@ def sample_adw(config, b, x0s_batches):
                            [d[-1] for d in dlogps] if config.return_dlogp else [],
                            gedmd=(initial, samples[-1], config.beta0s[0], config.beta1s[0]))
     return initial, samples
+
+
+def _vloss_settings(config):
+    """The velocity-loss keys of a config, checked (ValueError) before any device work"""
+    g = lambda k, d: getattr(config, k, d)
+    gamma, t_distr, center = g("gamma", "brownian"), g("t_distr", "uniform"), g("center", None)
+    if gamma not in _interp.GAMMAS:
+        raise ValueError(f"config.gamma must be one of {_interp.GAMMAS}, got {gamma!r}")
+    if t_distr not in ("uniform", "beta"):
+        raise ValueError(f"config.t_distr must be 'uniform' or 'beta', got {t_distr!r}")
+    if center not in (None, "batch", "molecule", "none"):
+        raise ValueError(f"config.center must be 'batch', 'molecule' or 'none', got {center!r}")
+    a, n_draws, tbins, seed = g("interpolant_a", 1.0), g("n_draws", 1), g("tbins", 0), g("seed", 0)
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not np.isfinite(a) or a <= 0:
+        raise ValueError(f"config.interpolant_a must be a finite number > 0, got {a!r}")
+    for key, v, lo, hi in (("n_draws", n_draws, 1, 1 << 20), ("tbins", tbins, 0, 1024), ("seed", seed, 0, (1 << 64) - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"config.{key} must be an integer in {lo}..{hi}, got {v!r}")
+    for key in ("data_save_path", "data_save_name"):
+        if not isinstance(g(key, None), str) or not g(key, None):
+            raise ValueError(f"config.{key} must be a non-empty string")
+    return dict(gamma=gamma, t_distr=t_distr, center=center, a=float(a), n_draws=int(n_draws), tbins=int(tbins), seed=int(seed))
+
+
+def _load_state_dict(ck):
+    """A checkpoint: a state dict, the path of an .npz of one, or the path of a torch file (a state dict or a module)"""
+    if isinstance(ck, dict):
+        return ck
+    if str(ck).endswith(".npz"):
+        with np.load(ck) as f:
+            return {k: f[k] for k in f.files}
+    import torch                                  # the one place torch is needed: the reference saves checkpoints with torch.save
+    obj = torch.load(ck, map_location="cpu")
+    return obj.state_dict() if hasattr(obj, "state_dict") else obj
+
+
+def score_checkpoints(config, b, pairs, checkpoints):
+    """Velocity loss (StandardVelocityLoss with LinearInterpolant(interpolant_a, gamma)) of every checkpoint on the held-out `pairs`:
+    (batch0, batch1) per item for an ambient model, (x0s, x1s, beta0s, beta1s) for adw.  Every checkpoint sees the same (t, z): draw
+    d of a pair uses seed = config.seed, draw = d and the pair's running molecule offset.  Writes and returns ``mean`` [K] (per atom
+    row for molecules, per particle for adw), ``sem`` [K] (standard error over molecules of their draw-averaged losses), ``tbins``
+    [K, n, 2] (sum of the per-molecule losses and count per bin of t) and ``best`` (index of the smallest mean)."""
+    s = _vloss_settings(config)
+    pairs = [tuple(p) for p in pairs]
+    checkpoints = list(checkpoints)
+    if not pairs or not checkpoints:
+        raise ValueError("score_checkpoints needs at least one pair and one checkpoint")
+    if any(len(p) not in (2, 4) or len(p) != len(pairs[0]) for p in pairs):
+        raise ValueError("pairs must all be (batch0, batch1) or all (x0s, x1s, beta0s, beta1s)")
+    form = len(pairs[0])
+    loss_fn = _losses.StandardVelocityLoss(_interp.LinearInterpolant(s["a"], s["gamma"]), s["t_distr"])
+    K, n = len(checkpoints), s["tbins"]
+    mean, sem, tb = np.zeros(K), np.zeros(K), np.zeros((K, n, 2))
+    b.eval()
+    for k, ck in enumerate(checkpoints):
+        b.load_state_dict(_load_state_dict(ck))
+        per_mol, offset = [], 0
+        for p in pairs:
+            acc = None
+            for d in range(s["n_draws"]):
+                kw = dict(seed=s["seed"], draw=d, traj_offset=offset, tbins=n, center=s["center"])
+                loss_fn(b, *p, **kw) if form == 4 else loss_fn(*p, b, **kw)
+                last = loss_fn.last
+                l = C.to_numpy(last["loss"]).astype(np.float64)
+                acc = l if acc is None else acc + l
+                if n:
+                    tb[k] += last["tbins"]
+            rows_per = last["rows"] // acc.size                      # A for molecules, 1 for adw: the mean is per atom row
+            per_mol.append(acc / (s["n_draws"] * rows_per))
+            offset += acc.size
+        v = np.concatenate(per_mol)
+        mean[k] = v.mean()
+        sem[k] = v.std(ddof=1) / np.sqrt(v.size) if v.size > 1 else 0.0
+    out = dict(mean=mean, sem=sem, tbins=tb, best=np.int64(np.argmin(mean)))
+    os.makedirs(config.data_save_path, exist_ok=True)
+    np.savez(os.path.join(config.data_save_path, f"val_loss_{config.data_save_name}.npz"), **out)
+    return out

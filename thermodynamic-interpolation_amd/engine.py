@@ -484,6 +484,69 @@ class _Engine:
         _lib.check(_lib.lib().ti_obs_ti_logw(self.h, p0, p1, np_, B, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return out
 
+    # ---- velocity loss (ti_painn_vloss / ti_adw_vloss): the shared part of PainnEngine.velocity_loss and AdwEngine.velocity_loss
+    @staticmethod
+    def _vloss_desc(kind, gamma, a, center, t, t_distr, seed, traj_offset, draw, tbins):
+        for name, table, value in (("kind", _lib.VLOSS_KINDS, kind), ("gamma", _lib.VLOSS_GAMMAS, gamma), ("center", _lib.VLOSS_CENTERS, center),
+                                   ("t_distr", _lib.VLOSS_TDISTS, t_distr)):
+            if value not in table:
+                raise ValueError(f"{name} must be one of {sorted(table)}, got {value!r}")
+        td = _lib.VLOSS_TDISTS["given" if t is not None else t_distr]
+        if t is None and t_distr == "given":
+            raise ValueError("t_distr='given' needs t")
+        return _lib.VlossDesc(_lib.VLOSS_KINDS[kind], _lib.VLOSS_GAMMAS[gamma], float(a), _lib.VLOSS_CENTERS[center], td, int(seed),
+                              int(traj_offset), int(draw), int(tbins))
+
+    def _vloss(self, interp_only, xs, x0, x1, conds, desc, t, z, returns):
+        """xs: the state shape [B, ...]; conds: buffer specs of the conditioning.  -> dict(loss [B] float64, mean, tbins [n, 2] |
+        None, rows = the divisor of mean, and the entries of `returns` among t [B], z, xt [2, ...], b [2, ...]); arrays live where x0 lives."""
+        B = int(xs[0])
+        bad = set(returns) - ({"t", "z", "xt"} if interp_only else {"t", "z", "xt", "b"})
+        if bad:
+            raise ValueError(f"unknown entries in returns: {sorted(bad)}")
+        dev_like = x0 if hasattr(x0, "data_ptr") and x0.is_cuda else None
+        two = desc.kind == _lib.VLOSS_KINDS["standard"]
+        res = {}
+        if "t" in returns or interp_only:
+            res["t"] = _alloc_like(dev_like, (B,))
+        if ("z" in returns or interp_only) and two:
+            res["z"] = _alloc_like(dev_like, xs)
+        if "xt" in returns or interp_only:
+            res["xt"] = _alloc_like(dev_like, (2,) + tuple(xs))
+        if "b" in returns:
+            res["b"] = _alloc_like(dev_like, (2,) + tuple(xs))
+        specs = [(x0, xs, False, "x0"), (x1, xs, False, "x1"), *conds, (t, (B,), False, "t"), (z, xs, False, "z"),
+                 (res.get("t"), (B,), True, "out_t"), (res.get("z"), xs, True, "out_z"), (res.get("xt"), None, True, "out_xt"),
+                 (res.get("b"), None, True, "out_b")]
+        ptrs, dev, keep = self._ptrs(*specs)
+        x0p, x1p, *cp = ptrs[:2 + len(conds)]
+        tp, zp, otp, ozp, oxp, obp = ptrs[2 + len(conds):]
+        mem = _lib.MEM_DEVICE if dev else _lib.MEM_HOST
+        L = _lib.lib()
+        painn = isinstance(self, PainnEngine)
+        if interp_only:
+            fn = L.ti_painn_vloss_interp if painn else L.ti_adw_vloss_interp
+            _lib.check(fn(self.h, C.byref(desc), x0p, x1p, tp, zp, B, otp, ozp, oxp, mem))
+        else:
+            if dev:
+                import torch
+                loss = torch.empty(B, dtype=torch.float64, device=x0.device)
+                lp = C.c_void_p(loss.data_ptr())
+            else:
+                loss = np.empty(B, np.float64)
+                lp = C.c_void_p(loss.ctypes.data)
+            mean = C.c_double(0.0)
+            tb = np.zeros((desc.n_tbins, 2), np.float64) if desc.n_tbins > 0 else None
+            tbp = tb.ctypes.data_as(C.POINTER(C.c_double)) if tb is not None else None
+            fn = L.ti_painn_vloss if painn else L.ti_adw_vloss
+            _lib.check(fn(self.h, C.byref(desc), x0p, x1p, *cp, tp, zp, B, lp, C.byref(mean), tbp, otp, ozp, oxp, obp, mem))
+            res.update(loss=loss, mean=mean.value, tbins=tb, rows=B * (self.A if painn else 1))
+        if not two:                                   # the one-sided loss has no minus half
+            for k in ("xt", "b"):
+                if k in res:
+                    res[k] = res[k][:1]
+        return res
+
     def _times(self, t, B):
         """A 1-D time vector of length B (one time per molecule / row) as a buffer spec, or None for a scalar t."""
         if (tuple(t.shape) if hasattr(t, "shape") else np.shape(t)) == ():
@@ -702,6 +765,25 @@ class PainnEngine(_Engine):
         _lib.check(_lib.lib().ti_painn_drift(self.h, xp, float(t), cp, B, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return out
 
+    def velocity_loss(self, x0, x1, cond=None, *, kind="standard", gamma="brownian", a=1.0, center="batch", t=None, t_distr="uniform",
+                      z=None, seed=0, traj_offset=0, draw=0, tbins=0, returns=()):
+        """ti_painn_vloss: the stochastic-interpolant velocity loss of this model on the pairs (x0, x1) [B,A,3] -- the antithetic states
+        of the interpolant (kind 'standard': (1 - t) x0 + t x1 +- gamma(t) z; 'one_sided': t x1 + (1 - t) x0 with x0 the noise), centred
+        per 'batch' (the reference's mean over all atom rows of the call), per 'molecule' or not at all ('none'), the drift on both, and
+        the per-molecule sums.  t [B] / z [B,A,3] given, or drawn from Philox by (seed, traj_offset + b, draw): t_distr 'uniform',
+        'beta_half' (Beta(1/2, 1/2)) or 'beta_2_1' (Beta(2, 1)).  -> dict: loss [B] float64, mean (sum of loss / (B A)), tbins [n, 2]
+        (sum, count per bin of t) or None, plus the entries named in returns: 't', 'z', 'xt' [2,B,A,3], 'b' [2,B,A,3] (one_sided: [1,...])."""
+        B = self._check_x(x0, "x0")
+        desc = self._vloss_desc(kind, gamma, a, center, t, t_distr, seed, traj_offset, draw, tbins)
+        return self._vloss(False, (B, self.A, 3), x0, x1, [self._cond_spec(cond, B)], desc, t, z, returns)
+
+    def interpolate(self, x0, x1, *, kind="standard", gamma="brownian", a=1.0, center="batch", t=None, t_distr="uniform", z=None, seed=0,
+                    traj_offset=0, draw=0):
+        """ti_painn_vloss_interp: stage one of velocity_loss alone -> dict: t [B], z [B,A,3] (standard), xt [2,B,A,3] (one_sided: [1,...])."""
+        B = self._check_x(x0, "x0")
+        desc = self._vloss_desc(kind, gamma, a, center, t, t_distr, seed, traj_offset, draw, 0)
+        return self._vloss(True, (B, self.A, 3), x0, x1, [], desc, t, z, ())
+
     def rollout(self, x0, cond, t_grid, scheme="euler", save_every=1, eps=0.0, seed=0, traj_offset=0, com_free_noise=False, out=None,
                 rtol=1e-4, atol=1e-4, step_offset=0, step_control="batch"):
         """Returns (path [rows,B,A,3], n_fevals).  scheme: 'euler' | 'heun' | 'em' | 'midpoint' | 'rk4' on the grid, or 'dopri5'
@@ -879,6 +961,21 @@ class AdwEngine(_Engine):
             return out
         _lib.check(_lib.lib().ti_adw_drift_div(self.h, xp, float(t), b0p, b1p, B, op, dp, mem))
         return out, div
+
+    def velocity_loss(self, x0, x1, beta0, beta1, *, kind="standard", gamma="brownian", a=1.0, t=None, t_distr="uniform", z=None, seed=0,
+                      traj_offset=0, draw=0, tbins=0, returns=()):
+        """ti_adw_vloss: PainnEngine.velocity_loss for particles x0, x1 [B] ([B, d] for d > 1) with per-row beta0, beta1 [B]; no centring;
+        mean = sum of loss / B."""
+        B = int(x0.shape[0])
+        desc = self._vloss_desc(kind, gamma, a, "none", t, t_distr, seed, traj_offset, draw, tbins)
+        return self._vloss(False, self._xs(B), x0, x1, [(beta0, (B,), False, "beta0"), (beta1, (B,), False, "beta1")], desc, t, z, returns)
+
+    def interpolate(self, x0, x1, *, kind="standard", gamma="brownian", a=1.0, t=None, t_distr="uniform", z=None, seed=0, traj_offset=0,
+                    draw=0):
+        """ti_adw_vloss_interp: stage one of velocity_loss alone -> dict: t [B], z (standard), xt [2, ...] (one_sided: [1, ...])."""
+        B = int(x0.shape[0])
+        desc = self._vloss_desc(kind, gamma, a, "none", t, t_distr, seed, traj_offset, draw, 0)
+        return self._vloss(True, self._xs(B), x0, x1, [], desc, t, z, ())
 
     def rollout(self, x0, beta0, beta1, t_grid, scheme="euler", save_every=1, eps=0.0, seed=0, traj_offset=0, out=None,
                 return_dlogp=False, rtol=1e-4, atol=1e-4, step_offset=0, step_control="batch", *, fused=False):

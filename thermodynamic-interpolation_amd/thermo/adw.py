@@ -16,6 +16,7 @@ from .. import observables as _obs
 from .. import synthetic as _syn
 from .. import weights as _W
 from . import _common as C
+from . import interpolants, losses  # noqa: F401  (the reference's thermo.interpolants / thermo.losses)
 
 
 class FCNetMultiBeta:

@@ -6,6 +6,7 @@
 from __future__ import annotations
 
 from .. import weights as _W
+from . import interpolants, losses  # noqa: F401  (the reference's thermo.ambient.interpolants / .losses)
 from ._molecule import DEFAULT_TEMPS, MoleculeIntegratorBase, ODEWrapperBase, PaiNNShell
 
 
