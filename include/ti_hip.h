@@ -681,7 +681,8 @@ int ti_selftest(int device);
  *                                                  Python mirror does)
  *   centring:  TI_CENTER_BATCH     the reference's xt - mean(xt, dim=0): the mean over all B A atom rows of the CALL, per component,
  *                                  separately for the plus and the minus half (so the result depends on how a set is cut into calls);
- *                                  the column sums are taken over fixed tiles of 1024 rows in row order and the tile sums in tile order
+ *                                  the column sums are taken over fixed tiles of 1024 rows and then over the tile sums, in the fixed
+ *                                  order stated under Reduce
  *              TI_CENTER_MOLECULE  each molecule's own centre (atoms summed in order): independent of the other molecules
  *              TI_CENTER_NONE      the only mode of an adw handle
  *   z == NULL:  z[b,a,c] = N(seed, traj_offset + b, draw, 3a + c) (adw: component k), N the Philox normal of TI_SCHEME_EM with `draw`
@@ -711,9 +712,15 @@ int ti_selftest(int device);
  *   molecules) applies to both halves, which are then evaluated one after the other as two batches of B, without that alignment.
  * Reduce (fp64, element order).  With d = x1 - x0 and the sum over the m entries of a row:
  *   STANDARD   l_b = sum [ b+^2 / 2 - (d + gamma' z) b+ + b-^2 / 2 - (d - gamma' z) b- ]        ONE_SIDED   l_b = sum [ b+^2 / 2 - d b+ ]
- *   *out_mean = sum_b l_b / (B A) for molecules (the reference's mean over atom rows) and / B for adw; the sum over b runs over fixed
- *   tiles of 1024 in index order, then over the tiles in order.  out_tbins [n_tbins][2]: sum of l_b and count of the molecules with
- *   floor(t_b n_tbins) = k (t = 1 in the last bin), summed in index order.
+ *   Every product, sum and difference of l_b is rounded on its own (no fused multiply-add), the four terms of an entry added in the
+ *   order written: with BROWNIAN, l_b is the plain IEEE double evaluation of this expression from t, z and b.
+ *   *out_mean = sum_b l_b / (B A) for molecules (the reference's mean over atom rows) and / B for adw.  Every batch-wide sum (this
+ *   one, the column sums of TI_CENTER_BATCH, the time profile) is taken by 256 accumulators that start at +0.0 and are then folded
+ *   by one fixed tree: for s = 128, 64, .., 1, accumulator i < s takes accumulator i + s.  Within a tile of 1024 values accumulator
+ *   j adds values 4j .. 4j + 3 of the tile in order; across the tiles accumulator j adds the sums of tiles j, j + 256, .. in order.
+ *   out_tbins [n_tbins][2]: sum of l_b and count of the molecules with floor(t_b n_tbins) = k (t = 1 in the last bin); per bin,
+ *   accumulator j adds the matching molecules among j, j + 256, .. in order (no tiles).  None of these is a plain sequential sum,
+ *   and none depends on anything but the values and their number: not on the launch, the device or the memory space.
  * Buffers.  x0, x1 [B,m], cond (painn) / beta0, beta1 [B] (adw), t [B], z [B,m], out_t [B], out_z [B,m], out_xt, out_b [2,B,m]
  *   (plus, then minus; ONE_SIDED writes the first half only) fp32 and out_loss [B] fp64: [host|device] by mem.  out_mean [1] and
  *   out_tbins [n_tbins,2] fp64: host.  Every out_* but out_loss may be NULL; out_t / out_z return what the kernels used (out_z with

@@ -253,3 +253,111 @@ def test_box_muller_on_philox_words_equals_oracle_normal(normal_lib):
             for i, tr in enumerate(trajs):
                 got = normal_lib.vl_normal_words(int(o[i, 2 * pair]), int(o[i, 2 * pair + 1]), int(comp & 1))
                 assert got == np.float32(oracle.normal(seed, int(tr), step, int(comp))), (tr, step, comp)
+
+
+# ------------------------------------------------------------------------------------------------ the fixed summation order
+def _tree_loop(sm):
+    s = 128
+    while s:
+        for i in range(s):
+            sm[i] += sm[i + s]
+        s >>= 1
+    return sm[0]
+
+
+def _colsum_loop(v):
+    """vloss_tile_sum_kernel and vloss_tile_combine_kernel with ncol = 1, thread by thread"""
+    n, tiles = len(v), max(1, -(-len(v) // 1024))
+    partial = []
+    for tile in range(tiles):
+        sm = [0.0] * 256
+        for j in range(256):
+            for k in range(4):
+                r = tile * 1024 + 4 * j + k
+                if r < n:
+                    sm[j] += v[r]
+        partial.append(_tree_loop(sm))
+    sm = [0.0] * 256
+    for j in range(256):
+        for k in range(j, tiles, 256):
+            sm[j] += partial[k]
+    return _tree_loop(sm)
+
+
+def _sixteen_decades(n, seed):
+    rs = np.random.RandomState(seed)
+    return rs.standard_normal(n) * 10.0 ** rs.uniform(-8.0, 8.0, n)
+
+
+@pytest.mark.parametrize("n", [1, 255, 1024, 1025, 2500, 265145])
+def test_fixed_order_sum_is_the_kernels_loop_and_close_to_fsum(n):
+    """The vectorised restatement against the scalar transcription of the two kernels, bit for bit, on values spread over 16 decades
+    (any other association shows); and against the exact sum within the bound of ANY order, (n - 1) 2^-53 sum|v|."""
+    import math
+    v = _sixteen_decades(n, n)
+    got = vn.fixed_order_sum(v)
+    assert got == _colsum_loop(v.tolist())
+    bound = (n - 1) * U * np.abs(v).sum()
+    print(f"fixed_order_sum n {n}: |sum - fsum| / (2^-53 sum|v|) {abs(got - math.fsum(v)) / (U * np.abs(v).sum()):.3f}")
+    assert abs(got - math.fsum(v)) <= bound
+    assert vn.fixed_order_sum(np.concatenate([v, np.zeros(3)])) == got           # +0.0 rows are not seen: padding is skipping
+
+
+@pytest.mark.parametrize("n", [1, 7, 1024])
+def test_time_bins_fixed_order_against_time_bins(n):
+    B = 2500
+    l = _sixteen_decades(B, 77)
+    t = np.random.RandomState(78).uniform(0.0, 1.0, B).astype(np.float32)
+    t[:3] = (0.0, 1.0, vn.T_MAX)
+    got, ref = vn.time_bins_fixed_order(l, t, n), vn.time_bins(l, t, n)
+    assert got.shape == (n, 2) and np.array_equal(got[:, 1], ref[:, 1]) and got[:, 1].sum() == B
+    assert (np.abs(got[:, 0] - ref[:, 0]) <= B * U * np.abs(l).sum()).all()
+    k = np.minimum(np.floor(t.astype(np.float64) * n).astype(int), n - 1)                # vloss_tbins_kernel, thread by thread, on a few bins
+    for b in sorted({0, n // 2, n - 1}):
+        sm = [0.0] * 256
+        for j in range(256):
+            for i in range(j, B, 256):
+                if k[i] == b:
+                    sm[j] += l[i]
+        assert got[b, 0] == _tree_loop(sm)
+
+
+@pytest.mark.parametrize("B,A", [(513, 2), (171, 6)])
+def test_dyadic_construction_is_exact_in_fp64(B, A):
+    """What the bit-for-bit centring tests of tests/test_gpu_vloss_edges.py rest on, in rational arithmetic: on dyadic_case the one-sided
+    state t x1 + (1 - t) x0 and its column sums are exact in fp64 (so they are the same in any order and under any contraction),
+    colsum / rows is the one correctly rounded division, and raw - mean is the correctly rounded difference of those two numbers."""
+    from fractions import Fraction as Fr
+    x0, x1, t = vn.dyadic_case(B, A, seed=B)
+    raw = vn.interpolate(x0, x1, t, kind="one_sided", center="none")[0][0]
+    exact = [[Fr(float(t[b])) * Fr(float(c1)) + (1 - Fr(float(t[b]))) * Fr(float(c0)) for c0, c1 in zip(x0[b].reshape(-1), x1[b].reshape(-1))] for b in range(B)]
+    assert all(Fr(float(r)) == e for rb, eb in zip(raw.reshape(B, -1), exact) for r, e in zip(rb, eb))
+    rows = B * A
+    cols = [sum(eb[3 * a + c] for eb in exact for a in range(A)) for c in range(3)]
+    flat = raw.reshape(rows, 3)
+    for c in range(3):
+        assert Fr(float(flat[:, c].sum())) == cols[c] and Fr(vn.fixed_order_sum(flat[:, c])) == cols[c] and Fr(float(flat[::-1, c].sum())) == cols[c]
+    mean = flat.sum(axis=0) / rows
+    assert all(float(mean[c]) == float(cols[c] / rows) for c in range(3))                # Fraction -> float rounds correctly
+    xt = vn.interpolate(x0, x1, t, kind="one_sided", center="batch")[0][0].reshape(rows, 3)
+    assert np.array_equal(xt, flat - mean)
+    for r in range(0, rows, 7):
+        for c in range(3):
+            assert float(xt[r, c]) == float(Fr(float(flat[r, c])) - Fr(float(mean[c])))
+    mol = vn.interpolate(x0, x1, t, kind="one_sided", center="molecule")[0][0]
+    for b in range(0, B, 5):
+        for c in range(3):
+            m = sum(exact[b][3 * a + c] for a in range(A)) / A
+            assert all(float(mol[b, a, c]) == float(Fr(float(raw[b, a, c])) - Fr(float(m))) for a in range(A))
+
+
+def test_interpolate_return_abs_leaves_existing_callers_alone():
+    x0, x1, t = vn.dyadic_case(7, 2)
+    z = np.random.RandomState(0).standard_normal(x0.shape)
+    two = vn.interpolate(x0, x1, t, z)
+    xt, S, E = vn.interpolate(x0, x1, t, z, return_abs=True)
+    assert len(two) == 2 and np.array_equal(two[0], xt) and np.array_equal(two[1], S) and E.shape == (2, 3)
+    raw = vn.interpolate(x0, x1, t, z, center="none")[0]
+    assert np.allclose(E, np.abs(raw).reshape(2, -1, 3).sum(axis=1), rtol=1e-15)
+    assert vn.interpolate(x0[:, 0, 0], x1[:, 0, 0], t, kind="one_sided", center="none", return_abs=True)[2].shape == (1,)
+    assert vn.interpolate(x0[:, 0], x1[:, 0], t, kind="one_sided", center="none", return_abs=True)[2].shape == (1, 3)

@@ -42,9 +42,10 @@ def _per_mol(t, x):
     return np.asarray(t, np.float64).reshape((-1,) + (1,) * (np.ndim(x) - 1))
 
 
-def interpolate(x0, x1, t, z=None, *, kind="standard", gamma_kind="brownian", a=1.0, center="batch"):
+def interpolate(x0, x1, t, z=None, *, kind="standard", gamma_kind="brownian", a=1.0, center="batch", return_abs=False):
     """-> (xt [2, ...] float64 (one_sided: [1, ...]), S [2, ...]): the centred states and the magnitude
-    S = |(1 - t) x0| + |t x1| + |gamma z| + |mean| every error bound of stage one is stated in."""
+    S = |(1 - t) x0| + |t x1| + |gamma z| + |mean| every error bound of stage one is stated in.  return_abs: also [halves, components]
+    (adw in one dimension: [halves]), the sum over the rows of |raw| of the uncentred states, which bounds the rounding of a column sum."""
     x0, x1 = np.asarray(x0, np.float64), np.asarray(x1, np.float64)
     tt = _per_mol(t, x0)
     it = (1.0 - tt) * x0 + tt * x1
@@ -64,6 +65,9 @@ def interpolate(x0, x1, t, z=None, *, kind="standard", gamma_kind="brownian", a=
             mean = 0.0
         out.append(x - mean)
         S.append(m + np.abs(mean))
+    if return_abs:
+        rows = lambda x: x.reshape(-1, x.shape[-1]) if x.ndim > 1 else x
+        return np.stack(out), np.stack(S), np.stack([np.abs(rows(x)).sum(axis=0) for x in xs])
     return np.stack(out), np.stack(S)
 
 
@@ -95,6 +99,64 @@ def time_bins(l, t, n):
     np.add.at(out[:, 0], k, np.asarray(l, np.float64))
     np.add.at(out[:, 1], k, 1.0)
     return out
+
+
+VL_BLOCK, VLOSS_TILE = 256, 1024          # csrc/vloss_kernels.hip: accumulators of a batch-wide sum, rows of a tile
+
+
+def _tree(acc):
+    """block_sum: acc [..., 256] folded by sm[i] += sm[i + s] for i < s, s = 128, 64, .., 1 -> [...]"""
+    acc = np.array(acc, np.float64)
+    s = VL_BLOCK // 2
+    while s:
+        acc[..., :s] += acc[..., s:2 * s]
+        s >>= 1
+    return acc[..., 0]
+
+
+def fixed_order_sum(v):
+    """The sum launch_vloss_colsum takes of one column (include/ti_hip.h, Reduce): per tile of 1024 rows accumulator j adds rows
+    4j .. 4j + 3 in order from +0.0, then the tree; across the tiles accumulator j adds tiles j, j + 256, .. in order, then the tree.
+    Rows and tiles past the end are padded with +0.0, which an accumulator that started at +0.0 does not see."""
+    v = np.asarray(v, np.float64).reshape(-1)
+    tiles = max(1, -(-v.size // VLOSS_TILE))
+    per = VLOSS_TILE // VL_BLOCK
+    vv = np.zeros(tiles * VLOSS_TILE)
+    vv[:v.size] = v
+    vv = vv.reshape(tiles, VL_BLOCK, per)
+    acc = np.zeros((tiles, VL_BLOCK))
+    for k in range(per):
+        acc += vv[:, :, k]
+    partial = _tree(acc)
+    rounds = -(-tiles // VL_BLOCK)
+    pp = np.zeros(rounds * VL_BLOCK)
+    pp[:tiles] = partial
+    acc = np.zeros(VL_BLOCK)
+    for row in pp.reshape(rounds, VL_BLOCK):
+        acc += row
+    return float(_tree(acc))
+
+
+def time_bins_fixed_order(l, t, n):
+    """time_bins in the order of vloss_tbins_kernel: per bin accumulator j adds the matching rows among j, j + 256, .. in order, then the tree"""
+    l = np.asarray(l, np.float64)
+    B = l.size
+    k = np.minimum(np.floor(np.asarray(t, np.float32).astype(np.float64) * n).astype(np.int64), n - 1)
+    acc, cnt = np.zeros((n, VL_BLOCK)), np.zeros((n, VL_BLOCK))
+    for r0 in range(0, B, VL_BLOCK):
+        j = np.arange(min(VL_BLOCK, B - r0))                # one row per accumulator and round: the pairs (bin, j) are distinct
+        acc[k[r0:r0 + j.size], j] += l[r0:r0 + j.size]
+        cnt[k[r0:r0 + j.size], j] += 1.0
+    return np.stack([_tree(acc), _tree(cnt)], axis=1)
+
+
+def dyadic_case(B, A, seed=0):
+    """(x0, x1 [B, A, 3], t [B]) float32 on which one-sided interpolation and its column sums are exact in fp64: coordinates are
+    integers in [-64, 64] over 16, t cycles through 1/4, 1/2, 3/4, so every product is a multiple of 2^-6 below 2^3 and a sum of 2^20
+    of them still has fewer than 53 bits (tests/test_vloss_host.py checks this in rational arithmetic)."""
+    rs = np.random.RandomState(seed)
+    x0, x1 = (rs.randint(-64, 65, (B, A, 3)).astype(np.float32) / np.float32(16) for _ in range(2))
+    return x0, x1, np.asarray([0.25, 0.5, 0.75], np.float32)[np.arange(B) % 3]
 
 
 def philox4x32_10(counter, key):

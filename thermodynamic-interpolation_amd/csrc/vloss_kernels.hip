@@ -139,9 +139,13 @@ __global__ __launch_bounds__(VL_BLOCK) void vloss_tile_combine_kernel(double* __
     if (threadIdx.x == 0) out[col] = s;
 }
 
-// one thread per molecule / row, its m entries in order
+// one thread per molecule / row, its m entries in order.  Contraction off: every product and sum below is rounded on its own, so l_b is
+// the IEEE evaluation of the header's expression, operation by operation.  A fused d + gamma' z is the more exact one, but where d and
+// gamma' z cancel it differs from the plain evaluation by far more than the roundings of the terms, and which products fuse would be
+// the compiler's choice.
 __global__ __launch_bounds__(VL_BLOCK) void vloss_reduce_kernel(VlossParams p)
 {
+#pragma clang fp contract(off)
     const long long b = (long long)blockIdx.x * VL_BLOCK + threadIdx.x;
     if (b >= p.B) return;
     const long long n = p.B * p.m, o = b * p.m;
