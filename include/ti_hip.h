@@ -23,6 +23,7 @@
  *   ti_painn_rollout_dlogp_est        computes exactly (the FFJORD estimator; the reference ships the exact one only)
  *   ti_painn_vloss / ti_adw_vloss     StandardVelocityLoss / OneSidedVelocityLoss.forward   mdqm9/thermo/{ambient,latent}/losses.py, adw/thermo/losses.py
  *   + ti_*_vloss_interp               with LinearInterpolant / OneSidedLinearInterpolant    .../interpolants.py (forward evaluation only)
+ *   ti_adw_trainer_create, ti_adw_train_*  the training loop's step: backward, clip_grad_norm_, Adam  adw/train.py:18-100
  *   TI_SCHEME_DOPRI5_TRAJ             the reference's dopri5 integration (integrators.py, odeint per mini-batch) evaluated for every
  *   + ti_rollout_step_counts          trajectory as if it were alone in its batch (a batch size of 1)
  *
@@ -760,6 +761,83 @@ int ti_painn_vloss_interp(ti_handle* h, const ti_vloss_desc* desc, const float* 
                           int64_t B, float* out_t, float* out_z, float* out_xt, int mem);
 int ti_adw_vloss_interp(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* t, const float* z,
                         int64_t B, float* out_t, float* out_z, float* out_xt, int mem);
+
+/* ---- adw trainer: FCNetMultiBeta trained on the velocity loss, on the device --------------------------------------------------------
+ * The training stage of the adw workflow (adw/train.py: StandardVelocityLoss / OneSidedVelocityLoss on FCNetMultiBeta(d, d, H, L),
+ * torch.nn.utils.clip_grad_norm_, torch.optim.Adam with L2 weight decay, the NaN skip of its lines 59-65).  A trainer is a handle of
+ * its own kind, freed by ti_destroy.  It owns, in device memory: the master weights and the Adam moments m, v in fp64 (the reference
+ * trains in float64; fp32 masters would lose the late, small-learning-rate updates), and an fp32 working copy of the weights in the
+ * canonical layout of ti_adw_create_nd, refreshed by the optimiser kernel.  A drift handle stays immutable: every painn / adw entry
+ * point refuses a trainer handle with TI_E_ARG ("not an adw handle"), and the calls below refuse any other handle the same way.
+ * ti_adw_trainer_create takes the descriptor, dim and weights of ti_adw_create_nd with the same checks in the same order, then:
+ * TI_PREC_F16X2 is TI_E_UNSUPPORTED (the trainer takes TI_PREC_F32 only); a NULL train descriptor, lr <= 0, beta1 or beta2 outside
+ * [0, 1), eps <= 0, weight_decay < 0 (or any of them not finite) are TI_E_ARG.  All before any device call.
+ *
+ * Loss.  The states, the drawn t and z, the loss rows l_b and *out_mean = sum_b l_b / B are the velocity-loss block's above, by the
+ *   same kernels (interpolate, reduce, the fixed tree), on the drift the trainer's own forward pass gives.  That pass keeps every
+ *   layer's activation and is a different kernel from the drift's: each pre-activation is one fmaf chain over the layer's inputs in
+ *   order from +0.0, the bias added afterwards.  Its relation to ti_adw_vloss on an f32 drift handle of the same weights is
+ *   therefore closeness (fp32 round-off), not identity.
+ * Backward.  The gradient is of the MEAN loss: d / d b+- = (b+- - target+-) / B with target+- = (x1 - x0) +- gamma'(t) z, computed
+ *   in fp64 and rounded to fp32 once; ONE_SIDED has the plus half only.  Backward through net runs on the 2B rows [xt+; xt-]
+ *   (ONE_SIDED: B).  beta_embed is evaluated once per row b -- (beta0, beta1, t) is shared by the halves -- and receives the
+ *   gradient of net.0's embedding input column of both halves: sum_n W0[n][d+1] (g+_bn + g-_bn), the halves added in that order,
+ *   n in order, in fp64 from the fp32 g and rounded to fp32 once (the halves are antithetic and the sum cancels).  silu'(z) = s +
+ *   silu(z) (1 - s), s the logistic function, as in the tangent code of the drift.  All matrix products run on
+ *   v_mfma_f32_16x16x4_f32, each output element one fmaf chain in index order.  The weight gradient contracts over the rows in
+ *   slices of 512 rows (row order within a slice); the slice results (fp32) are added in fp64 in slice order from +0.0.  A bias
+ *   gradient is the column sum of the layer's g over the rows in fp64: accumulator p of 16 adds rows p, p + 16, .. in order from
+ *   +0.0, then the accumulators are added in order.  No atomics: a gradient is a function of the weights and the batch --
+ *   including the ORDER of its rows -- and not of the launch, the memory space of the inputs, or what ran before.
+ * Clipping (clip_grad_norm_).  norm = sqrt(sum g^2) over all parameters in fp64, the sum by the fixed tree of the velocity-loss
+ *   block over tiles of 1024 entries in canonical order; coef = min(1, max_grad_norm / (norm + 1e-6)); g <- coef g.  max_grad_norm
+ *   <= 0 or inf: no clipping.  Then g <- g + weight_decay p (torch adds the decay inside Adam.step, after the clip; skipped when
+ *   weight_decay == 0).
+ * Adam.  With k = n_applied + 1:  m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) (g g);
+ *   p <- p - (lr / (1 - beta1^k)) (m / (sqrt(v) / sqrt(1 - beta2^k) + eps)).  fp64, every product, sum, quotient and root rounded on
+ *   its own; lr / (1 - beta1^k) and sqrt(1 - beta2^k) are computed on the host (pow of the C library) and passed to the kernel.
+ * NaN skip.  If the step's mean loss or sum g^2 is not finite (any non-finite gradient entry makes it so), nothing changes: not the
+ *   weights, not the moments, not n_applied.  n_skipped is incremented, the step's out_loss entry is NaN, and the following steps
+ *   go on.  Decided by the optimiser kernel from the two sums in device memory, without a host synchronisation.
+ * ti_adw_train_grad: loss rows, their mean, the gradient of the mean loss at the current weights and its norm; nothing is updated.
+ *   out_loss [B] fp64 [host|device] by mem; out_mean, out_grad [n_weights] (canonical layout), out_gnorm fp64 host; any may be NULL.
+ *   Non-finite values are returned as they are.
+ * ti_adw_train_apply: clip + Adam with a GIVEN gradient (host, fp64, canonical layout); *out_skipped = 1 where a non-finite entry
+ *   made the step a skipped one.
+ * ti_adw_train_steps: n_steps optimiser steps enqueued on the handle's stream, one synchronisation at the end.  x0 [n0,d], beta0 [n0],
+ *   x1 [n1,d], beta1 [n1] are the resident sets; step k uses rows idx0[kB .. kB+B-1] of x0 / beta0 and idx1[..] of x1 / beta1 (int64,
+ *   same mem as the data), gathered on the device.  idx0 == idx1 == NULL: n_steps must be 1 and the step uses rows 0..B-1.  (t, z) of
+ *   step k: as ti_adw_vloss draws them with draw = desc->draw + k and id = desc->traj_offset + row in the minibatch; TI_TDIST_GIVEN
+ *   and a given z only with n_steps == 1.  out_loss [n_steps] fp64 host: the mean loss of every step, NaN where skipped;
+ *   *out_skipped: the steps of this call that were skipped.  A skipped step consumes its draw index.
+ *   ti_adw_train_steps with n_steps = 1 is ti_adw_train_grad followed by ti_adw_train_apply of its out_grad, bit for bit.
+ * ti_adw_train_get_state / set_state: master weights and moments [n_weights] fp64 host (NULL: not copied / left as they are) and the
+ *   counters; set_state with w refreshes the fp32 copy.  ti_adw_train_set_lr: the learning rate of the following steps (> 0).
+ * Checks of ti_adw_train_grad / ti_adw_train_steps, before any device work, in this order: every descriptor check of ti_adw_vloss in
+ *   its order (through the given t); B > TI_ADW_TRAIN_MAX_B (TI_E_UNSUPPORTED); steps: n_steps < 1, one of idx0 / idx1 NULL, no
+ *   indices with n_steps != 1, a given t or z with n_steps != 1, n0 or n1 < 1 (without indices: < B); a NULL x0, x1, beta0 or beta1;
+ *   TI_CENTER_BATCH / TI_CENTER_MOLECULE (TI_E_UNSUPPORTED); steps: a host index outside its set (TI_E_ARG; device indices are read
+ *   back and checked before anything is enqueued); a NULL or non-trainer handle.
+ * TI_ADW_TRAIN_MAX_B bounds the activation workspace: 2 * (2B L + 2B) * H fp32 values (y and silu' of net's L hidden layers on 2B
+ *   rows and of beta_embed's two on B) are 1.5 GiB at B = 2^16, H = 256, L = 5, and the weight-gradient slices 2B / 512 * n_weights *
+ *   4 bytes = 340 MB. */
+#define TI_ADW_TRAIN_MAX_B 65536
+typedef struct ti_adw_train_desc {
+    double  lr, beta1, beta2, eps, weight_decay;   /* torch.optim.Adam: lr, betas = (0.9, 0.999), eps = 1e-8, weight_decay = 0 */
+    double  max_grad_norm;                         /* clip_grad_norm_; <= 0 or inf: no clipping */
+} ti_adw_train_desc;
+ti_handle* ti_adw_trainer_create(const ti_adw_desc* desc, int32_t dim, const double* weights, size_t n_weights,
+                                 const ti_adw_train_desc* train, int device);
+int ti_adw_train_grad(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* beta0, const float* beta1,
+                      const float* t, const float* z, int64_t B, double* out_loss, double* out_mean, double* out_grad, double* out_gnorm,
+                      int mem);
+int ti_adw_train_apply(ti_handle* h, const double* grad, int32_t* out_skipped);
+int ti_adw_train_steps(ti_handle* h, const ti_vloss_desc* desc, const float* x0, int64_t n0, const float* x1, int64_t n1,
+                       const float* beta0, const float* beta1, const int64_t* idx0, const int64_t* idx1, const float* t, const float* z,
+                       int64_t B, int64_t n_steps, double* out_loss, int64_t* out_skipped, int mem);
+int ti_adw_train_get_state(ti_handle* h, double* w, double* m, double* v, int64_t* n_applied, int64_t* n_skipped);
+int ti_adw_train_set_state(ti_handle* h, const double* w, const double* m, const double* v, int64_t n_applied);
+int ti_adw_train_set_lr(ti_handle* h, double lr);
 
 #ifdef __cplusplus
 }

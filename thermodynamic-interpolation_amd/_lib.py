@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "ti_obs_zmat", "ti_obs_zmat_xyz", "ti_obs_hist_cols",
     "ti_obs_eigh_wide", "ti_obs_eigh_wide_launch_max", "ti_obs_gedmd_spectrum_wide",
     "ti_painn_vloss", "ti_adw_vloss", "ti_painn_vloss_interp", "ti_adw_vloss_interp",
+    "ti_adw_trainer_create", "ti_adw_train_grad", "ti_adw_train_apply", "ti_adw_train_steps", "ti_adw_train_get_state",
+    "ti_adw_train_set_state", "ti_adw_train_set_lr",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -78,6 +80,8 @@ VLOSS_CENTERS = {"batch": 0, "molecule": 1, "none": 2}
 VLOSS_TDISTS = {"given": 0, "uniform": 1, "beta_half": 2, "beta_2_1": 3}
 VLOSS_DOMAIN = 0x564C4F53
 VLOSS_MAX_TBINS = 1024
+# ti_adw_train_*: the largest minibatch (TI_ADW_TRAIN_MAX_B), the rows of a slice of the weight-gradient contraction
+ADW_TRAIN_MAX_B, ADW_TRAIN_ROW_TILE = 1 << 16, 512
 
 
 class PainnDesc(C.Structure):
@@ -116,6 +120,11 @@ class FfDesc(C.Structure):
 class VlossDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("gamma", C.c_int32), ("a", C.c_double), ("center", C.c_int32), ("t_dist", C.c_int32),
                 ("seed", C.c_uint64), ("traj_offset", C.c_int64), ("draw", C.c_int32), ("n_tbins", C.c_int32)]
+
+
+class AdwTrainDesc(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_grad_norm", C.c_double)]
 
 
 class TiError(RuntimeError):
@@ -225,6 +234,15 @@ def lib():
     L.ti_adw_vloss.argtypes = [vp, vd, vp, vp, vp, vp, vp, vp, C.c_int64, vp, dp, dp, vp, vp, vp, vp, C.c_int]
     L.ti_painn_vloss_interp.argtypes = [vp, vd, vp, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int]
     L.ti_adw_vloss_interp.argtypes = [vp, vd, vp, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int]
+    L.ti_adw_trainer_create.restype = vp
+    L.ti_adw_trainer_create.argtypes = [C.POINTER(AdwDesc), C.c_int32, dp, C.c_size_t, C.POINTER(AdwTrainDesc), C.c_int]
+    L.ti_adw_train_grad.argtypes = [vp, vd, vp, vp, vp, vp, vp, vp, C.c_int64, vp, dp, dp, dp, C.c_int]
+    L.ti_adw_train_apply.argtypes = [vp, dp, C.POINTER(C.c_int32)]
+    L.ti_adw_train_steps.argtypes = [vp, vd, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64, dp,
+                                     C.POINTER(C.c_int64), C.c_int]
+    L.ti_adw_train_get_state.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.ti_adw_train_set_state.argtypes = [vp, dp, dp, dp, C.c_int64]
+    L.ti_adw_train_set_lr.argtypes = [vp, C.c_double]
     _lib = L
     return L
 

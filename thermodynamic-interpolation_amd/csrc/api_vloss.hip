@@ -3,14 +3,17 @@
 // device-resident states, reduce.  Every stage computes into buffers of the handle; the outputs are copied from them once the whole
 // call has succeeded.
 #include "ti_handle.hpp"
+#include "adw_train.hpp"
 
 namespace {
 
 constexpr int RED_COLSUM = 0, RED_MEAN = 32, RED_BAD = 33, RED_TBINS = 34;      // slots of ti_handle::vl_red
 
+}  // namespace
+
 // The checks that need no handle, in the order include/ti_hip.h lists them; the handle is refused after them, so that each can be
-// exercised without a device.
-int vloss_check(const ti_vloss_desc* d, const float* t, const float* z, int64_t B, int mem)
+// exercised without a device.  The adw trainer (api_adw_train.hip) makes the same checks first.
+int ti::vloss_check(const ti_vloss_desc* d, const float* t, const float* z, int64_t B, int mem)
 {
     if (!d) return fail(TI_E_ARG, "desc is NULL");
     if (d->kind != TI_VLOSS_STANDARD && d->kind != TI_VLOSS_ONE_SIDED) return fail(TI_E_ARG, "unknown loss kind " + std::to_string(d->kind));
@@ -34,6 +37,8 @@ int vloss_check(const ti_vloss_desc* d, const float* t, const float* z, int64_t 
     }
     return TI_OK;
 }
+
+namespace {
 
 // c0 / c1: cond / NULL of a painn handle, beta0 / beta1 of an adw handle.  interp_only: stage one alone (out_xt required).
 int vloss_impl(ti_handle* h, int want_kind, const ti_vloss_desc* d, const float* x0, const float* x1, const float* c0, const float* c1,

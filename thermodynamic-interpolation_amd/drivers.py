@@ -46,6 +46,12 @@ reference's files are written.
 Scores checkpoints by the velocity loss they were trained on (thermo.losses, on the GPU) and writes ``val_loss_{data_save_name}.npz``.
 Keys: ``gamma`` ('brownian' | 'sin2' | 'sig_sum') and ``t_distr`` ('uniform' | 'beta'), the reference's names; optional
 ``interpolant_a`` (1.0), ``n_draws`` (1), ``center`` ('batch' for molecules; adw is never centred), ``tbins`` (0), ``seed`` (0).
+
+  train_adw <- /root/reference/adw/train.py:18-100   epoch_{k}.npz, train_state.npz, log.npz under model_save_path/model_save_name/
+The training loop on the GPU (thermo.adw.Trainer).  Keys of the reference: ``hidden_size``, ``num_layers``, ``lr``, ``wd``,
+``batch_size``, ``epochs``, ``a``, ``seed``, ``model_save_path``, ``model_save_name``; of this build, all optional: ``gamma``
+('brownian'), ``t_distr`` ('uniform'), ``dim`` (1), ``max_grad_norm`` (1, the reference's clip).  Checkpoints are .npz state dicts in
+the reference's keys (fp64), which score_checkpoints reads; torch pickles are not written.
 """
 from __future__ import annotations
 
@@ -57,6 +63,7 @@ import numpy as np
 
 from . import observables as _obs
 from .thermo import adw as _adw
+from .thermo import adw_nd as _adw_nd
 from .thermo import ambient as _amb
 from .thermo import latent as _lat
 from .thermo import _common as C
@@ -570,3 +577,136 @@ def score_checkpoints(config, b, pairs, checkpoints):
     os.makedirs(config.data_save_path, exist_ok=True)
     np.savez(os.path.join(config.data_save_path, f"val_loss_{config.data_save_name}.npz"), **out)
     return out
+
+
+class _Plateau:
+    """torch.optim.lr_scheduler.ReduceLROnPlateau(factor, patience) on one learning rate with torch's defaults (mode 'min', threshold
+    1e-4 relative, cooldown 0, min_lr 0, eps 1e-8), on the host"""
+    KEYS = ("lr", "best", "num_bad", "cooldown_counter")
+
+    def __init__(self, lr, factor=0.5, patience=10, threshold=1e-4, cooldown=0, min_lr=0.0, eps=1e-8):
+        self.lr, self.factor, self.patience, self.threshold, self.cooldown, self.min_lr, self.eps = float(lr), factor, patience, threshold, cooldown, min_lr, eps
+        self.best, self.num_bad, self.cooldown_counter = float("inf"), 0, 0
+
+    def step(self, metric):
+        metric = float(metric)
+        if metric < self.best * (1.0 - self.threshold):
+            self.best, self.num_bad = metric, 0
+        else:
+            self.num_bad += 1
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.num_bad = 0
+        if self.num_bad > self.patience:
+            new = max(self.lr * self.factor, self.min_lr)
+            if self.lr - new > self.eps:
+                self.lr = new
+            self.cooldown_counter, self.num_bad = self.cooldown, 0
+        return self.lr
+
+    def state(self):
+        return {f"sched_{k}": np.float64(getattr(self, k)) for k in self.KEYS}
+
+    def load(self, st):
+        self.lr, self.best = float(st["sched_lr"]), float(st["sched_best"])
+        self.num_bad, self.cooldown_counter = int(st["sched_num_bad"]), int(st["sched_cooldown_counter"])
+
+
+def _train_settings(config):
+    """The keys of train_adw, checked (ValueError) before any device work"""
+    g = lambda k, d=None: getattr(config, k, d)
+    out = {}
+    for key, lo, hi, default in (("hidden_size", 1, 1 << 16, None), ("num_layers", 1, 1 << 10, None), ("batch_size", 1, 1 << 16, None),
+                                 ("epochs", 1, 1 << 30, None), ("seed", 0, (1 << 63) - 1, 0), ("dim", 1, 16, 1)):
+        v = g(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"config.{key} must be an integer in {lo}..{hi}, got {v!r}")
+        out[key] = int(v)
+    if out["hidden_size"] not in (32, 64, 128, 256):
+        raise ValueError(f"config.hidden_size must be 32, 64, 128 or 256, got {out['hidden_size']}")
+    for key, positive, default in (("lr", True, None), ("wd", False, 0.0), ("a", True, None), ("max_grad_norm", False, 1.0)):
+        v = g(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or np.isnan(v) or (key != "max_grad_norm" and (not np.isfinite(v) or v < 0)) \
+                or (positive and v <= 0):
+            raise ValueError(f"config.{key} must be a {'finite number > 0' if positive else 'number >= 0'}, got {v!r}")
+        out[key] = float(v)
+    gamma, t_distr = g("gamma", "brownian"), g("t_distr", "uniform")
+    if gamma not in _interp.GAMMAS:
+        raise ValueError(f"config.gamma must be one of {_interp.GAMMAS}, got {gamma!r}")
+    if t_distr not in ("uniform", "beta"):
+        raise ValueError(f"config.t_distr must be 'uniform' or 'beta', got {t_distr!r}")
+    for key in ("model_save_path", "model_save_name"):
+        if not isinstance(g(key), str) or not g(key):
+            raise ValueError(f"config.{key} must be a non-empty string")
+    out.update(gamma=gamma, t_distr=t_distr)
+    return out
+
+
+# The draw index of training step k of epoch e is _TRAIN_DRAW0 + e steps + k; validation uses draw = e.  Both draw with the run's seed
+# and ids that overlap (rows 0 .. B - 1), so sharing a draw index would hand a training step and a validation batch the same (t, z).
+_TRAIN_DRAW0 = 1 << 30
+
+
+def _split_80_10_10(x, beta, d, rng):
+    x = np.ascontiguousarray(C.to_numpy(x, np.float32).reshape((-1,) if d == 1 else (-1, d)))
+    beta = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta, np.float32).reshape(-1), (x.shape[0],)))
+    n = x.shape[0]
+    perm = rng.permutation(n)
+    n_train, n_val = int(0.8 * n), int(0.1 * n)
+    tr, va = perm[:n_train], perm[n_train:n_train + n_val]
+    return (x[tr], beta[tr]), (x[va], beta[va])
+
+
+def train_adw(config, base, target, resume=False):
+    """The loop of adw/train.py:18-100 on the GPU.  base / target: (x, beta) array pairs (x [n] or [n, d], beta [n] or one value).
+    Both sets are split 80 / 10 / 10 by a seeded permutation.  Per epoch: min(n_train) // batch_size optimiser steps on drop_last
+    batches of fresh permutations, in one device loop (Trainer.fit); the validation loss as the mean over the full validation
+    batches, without update, at the draws (seed, draw = the epoch, the running row offset) -- the training steps draw from index 2^30
+    on, so no step shares its (t, z) with a validation batch; ReduceLROnPlateau(factor 0.5, patience 10)
+    on it, then set_lr.  Writes epoch_{k}.npz (the fp64 state dict in the reference's keys), train_state.npz (optimiser and
+    scheduler state, the epochs done) and log.npz (train_loss, val_loss, lr, skipped per epoch); resume=True continues from
+    train_state.npz.  -> the log as a dict."""
+    s = _train_settings(config)
+    d, B = s["dim"], s["batch_size"]
+    mod = _adw if d == 1 else _adw_nd
+    (x0, b0), (v0, vb0) = _split_80_10_10(*base, d, np.random.default_rng([s["seed"], 0]))
+    (x1, b1), (v1, vb1) = _split_80_10_10(*target, d, np.random.default_rng([s["seed"], 1]))
+    steps, n_val = min(x0.shape[0], x1.shape[0]) // B, min(v0.shape[0], v1.shape[0]) // B
+    if steps < 1 or n_val < 1:
+        raise ValueError(f"batch_size {B} leaves no full training or validation batch ({x0.shape[0]} / {v0.shape[0]} rows)")
+    if s["epochs"] * steps > _TRAIN_DRAW0:
+        raise ValueError(f"epochs x steps per epoch = {s['epochs'] * steps} exceeds the {_TRAIN_DRAW0} draw indices of a run")
+    out_dir = os.path.join(config.model_save_path, config.model_save_name)
+    state_path = os.path.join(out_dir, "train_state.npz")
+    b = mod.FCNetMultiBeta(d, d, s["hidden_size"], s["num_layers"])
+    b.load_state_dict(_adw._syn.make_state_dict(b._spec, seed=s["seed"], dtype=np.float64))
+    loss_fn = _losses.StandardVelocityLoss(_interp.LinearInterpolant(s["a"], s["gamma"]), s["t_distr"])
+    trainer = _adw.Trainer(b, loss_fn, s["lr"], weight_decay=s["wd"], max_grad_norm=s["max_grad_norm"])
+    sched = _Plateau(s["lr"])
+    log = dict(train_loss=[], val_loss=[], lr=[], skipped=[])
+    first = 0
+    if resume:
+        with np.load(state_path) as f:
+            st = {k: f[k] for k in f.files}
+        trainer.load_state_dict(st)
+        sched.load(st)
+        first = int(st["epochs_done"])
+        log = {k: list(st["log_" + k]) for k in log}
+    os.makedirs(out_dir, exist_ok=True)
+    for epoch in range(first, s["epochs"]):
+        losses, skipped = trainer.fit(x0, x1, b0, b1, B, steps, [s["seed"], 2, epoch], draw=_TRAIN_DRAW0 + epoch * steps, noise_seed=s["seed"])
+        val = [trainer.loss(v0[k * B:(k + 1) * B], v1[k * B:(k + 1) * B], vb0[k * B:(k + 1) * B], vb1[k * B:(k + 1) * B], seed=s["seed"],
+                            draw=epoch, traj_offset=k * B) for k in range(n_val)]
+        log["train_loss"].append(float(np.nanmean(losses)) if skipped < steps else float("nan"))
+        log["val_loss"].append(float(np.mean(val)))
+        log["skipped"].append(int(skipped))
+        log["lr"].append(trainer.lr)
+        new_lr = sched.step(log["val_loss"][-1])
+        if new_lr != trainer.lr:
+            trainer.set_lr(new_lr)
+        trainer.sync()
+        np.savez(os.path.join(out_dir, f"epoch_{epoch}.npz"), **b.state_dict())
+        st = trainer.state_dict()
+        np.savez(state_path, **st, **sched.state(), epochs_done=np.int64(epoch + 1), **{"log_" + k: np.asarray(v) for k, v in log.items()})
+        np.savez(os.path.join(out_dir, "log.npz"), **{k: np.asarray(v) for k, v in log.items()})
+    return {k: np.asarray(v) for k, v in log.items()}

@@ -1004,5 +1004,139 @@ class AdwEngine(_Engine):
         return out, dl, nfe.value
 
 
+class AdwTrainer(_Engine):
+    """FCNetMultiBeta(d, d, H, L) trained on the velocity loss on the device (ti_adw_train_*): fp64 master weights and Adam moments,
+    forward / backward / weight gradient on the f32 matrix cores, clip_grad_norm_ + torch.optim.Adam (L2 weight_decay) in fp64, the
+    NaN skip of the reference's loop decided on the device.  `flat`: the canonical fp64 weights (weights.flatten_state_dict).
+    Arrays are numpy or CUDA tensors as AdwEngine.velocity_loss takes them: x0, x1 [B] ([B, d] for d > 1), beta0, beta1 [B]."""
+
+    def __init__(self, hidden, layers, flat, dim=1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, device=0,
+                 precision="f32"):
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
+        self.hidden, self.num_layers, self.dim, self.device = int(hidden), int(layers), int(dim), int(device)
+        self.desc = _lib.AdwDesc(self.hidden, self.num_layers, _lib.PRECISIONS[precision])
+        self.train_desc = _lib.AdwTrainDesc(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(max_grad_norm))
+        w = np.ascontiguousarray(flat, np.float64).reshape(-1)
+        self.n_weights = int(w.size)
+        self.h = _lib.lib().ti_adw_trainer_create(C.byref(self.desc), self.dim, w.ctypes.data_as(C.POINTER(C.c_double)), w.size,
+                                                  C.byref(self.train_desc), self.device)
+        if not self.h:
+            raise _lib.TiError(-1, _lib.last_error())
+
+    def _xs(self, *lead):
+        return tuple(lead) + ((self.dim,) if self.dim > 1 else ())
+
+    def _desc(self, kind, gamma, a, t, t_distr, seed, traj_offset, draw):
+        return self._vloss_desc(kind, gamma, a, "none", t, t_distr, seed, traj_offset, draw, 0)
+
+    def grad(self, x0, x1, beta0, beta1, *, kind="standard", gamma="brownian", a=1.0, t=None, t_distr="uniform", z=None, seed=0,
+             traj_offset=0, draw=0):
+        """ti_adw_train_grad -> dict(loss [B] float64 (where x0 lives), mean, grad [n_weights] float64 numpy, gnorm); no update."""
+        B = int(x0.shape[0])
+        xs = self._xs(B)
+        desc = self._desc(kind, gamma, a, t, t_distr, seed, traj_offset, draw)
+        (x0p, x1p, b0p, b1p, tp, zp), dev, keep = self._ptrs((x0, xs, False, "x0"), (x1, xs, False, "x1"), (beta0, (B,), False, "beta0"),
+                                                             (beta1, (B,), False, "beta1"), (t, (B,), False, "t"), (z, xs, False, "z"))
+        if dev:
+            import torch
+            loss = torch.empty(B, dtype=torch.float64, device=x0.device)
+            lp = C.c_void_p(loss.data_ptr())
+        else:
+            loss = np.empty(B, np.float64)
+            lp = C.c_void_p(loss.ctypes.data)
+        g = np.empty(self.n_weights, np.float64)
+        mean, gnorm = C.c_double(0.0), C.c_double(0.0)
+        _lib.check(_lib.lib().ti_adw_train_grad(self.h, C.byref(desc), x0p, x1p, b0p, b1p, tp, zp, B, lp, C.byref(mean),
+                                                g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(gnorm), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return dict(loss=loss, mean=mean.value, grad=g, gnorm=gnorm.value)
+
+    def apply(self, g):
+        """ti_adw_train_apply: clip + Adam with the given fp64 gradient [n_weights] -> True where the step was skipped (non-finite entry)."""
+        g = np.ascontiguousarray(g, np.float64).reshape(-1)
+        if g.size != self.n_weights:
+            raise ValueError(f"g must hold {self.n_weights} entries, got {g.size}")
+        skipped = C.c_int32(0)
+        _lib.check(_lib.lib().ti_adw_train_apply(self.h, g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(skipped)))
+        return bool(skipped.value)
+
+    def steps(self, x0, x1, beta0, beta1, idx0=None, idx1=None, *, n_steps=None, batch=None, kind="standard", gamma="brownian", a=1.0,
+              t=None, t_distr="uniform", z=None, seed=0, traj_offset=0, draw=0):
+        """ti_adw_train_steps -> (loss [n_steps] float64 numpy, NaN where skipped; the number of skipped steps).  idx0, idx1
+        [n_steps, B] int64 (numpy, or CUDA tensors when the data are): step k trains on rows idx0[k] of (x0, beta0) and idx1[k] of
+        (x1, beta1), drawn with draw + k.  Without indices: one step on rows 0 .. batch - 1 (batch defaults to all rows)."""
+        n0, n1 = int(x0.shape[0]), int(x1.shape[0])
+        specs = [(x0, self._xs(n0), False, "x0"), (x1, self._xs(n1), False, "x1"), (beta0, (n0,), False, "beta0"), (beta1, (n1,), False, "beta1")]
+        if (idx0 is None) != (idx1 is None):
+            raise ValueError("idx0 and idx1 must both be given or both be None")
+        if idx0 is None:
+            B, n = int(batch if batch is not None else n0), 1
+            if n_steps not in (None, 1):
+                raise ValueError("without indices a call makes one step")
+        else:
+            if tuple(idx0.shape) != tuple(idx1.shape) or len(idx0.shape) != 2:
+                raise ValueError("idx0 and idx1 must be [n_steps, B] and equally shaped")
+            n, B = int(idx0.shape[0]), int(idx0.shape[1])
+        specs += [(t, (B,), False, "t"), (z, self._xs(B), False, "z")]
+        (x0p, x1p, b0p, b1p, tp, zp), dev, keep = self._ptrs(*specs)
+        ip, ikeep = [None, None], []
+        for k, idx in enumerate((idx0, idx1)):
+            if idx is None:
+                continue
+            if hasattr(idx, "data_ptr"):
+                if not dev or str(idx.dtype) != "torch.int64" or not idx.is_contiguous() or not idx.is_cuda:
+                    raise TypeError("index tensors must be contiguous int64 CUDA tensors, with the data on the GPU too")
+                ip[k] = C.c_void_p(idx.data_ptr()); ikeep.append(idx)
+            else:
+                if dev:
+                    raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
+                arr = np.ascontiguousarray(idx, np.int64)
+                ip[k] = C.c_void_p(arr.ctypes.data); ikeep.append(arr)
+        desc = self._desc(kind, gamma, a, t, t_distr, seed, traj_offset, draw)
+        loss = np.empty(n, np.float64)
+        skipped = C.c_int64(0)
+        _lib.check(_lib.lib().ti_adw_train_steps(self.h, C.byref(desc), x0p, n0, x1p, n1, b0p, b1p, ip[0], ip[1], tp, zp, B, n,
+                                                 loss.ctypes.data_as(C.POINTER(C.c_double)), C.byref(skipped),
+                                                 _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return loss, int(skipped.value)
+
+    def step(self, x0, x1, beta0, beta1, **kw):
+        """One optimiser step on the whole batch -> (mean loss, or NaN where the step was skipped; skipped 0 / 1)."""
+        loss, skipped = self.steps(x0, x1, beta0, beta1, **kw)
+        return float(loss[0]), skipped
+
+    def state(self):
+        """dict(w, m, v [n_weights] float64, n_applied, n_skipped): master weights, Adam moments, counters"""
+        w, m, v = (np.empty(self.n_weights, np.float64) for _ in range(3))
+        na, ns = C.c_int64(0), C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        _lib.check(_lib.lib().ti_adw_train_get_state(self.h, w.ctypes.data_as(dp), m.ctypes.data_as(dp), v.ctypes.data_as(dp), C.byref(na), C.byref(ns)))
+        return dict(w=w, m=m, v=v, n_applied=int(na.value), n_skipped=int(ns.value))
+
+    def load_state(self, w=None, m=None, v=None, n_applied=0, **_):
+        dp = C.POINTER(C.c_double)
+        arrs = []
+        for name, a in (("w", w), ("m", m), ("v", v)):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.float64).reshape(-1)
+            if a.size != self.n_weights:
+                raise ValueError(f"{name} must hold {self.n_weights} entries, got {a.size}")
+            arrs.append(a)
+        ptrs = [None if a is None else a.ctypes.data_as(dp) for a in arrs]
+        _lib.check(_lib.lib().ti_adw_train_set_state(self.h, *ptrs, int(n_applied)))
+
+    def set_lr(self, lr):
+        _lib.check(_lib.lib().ti_adw_train_set_lr(self.h, float(lr)))
+        self.train_desc.lr = float(lr)
+
+    def weights(self):
+        """The fp64 master weights in the canonical layout [n_weights]"""
+        w = np.empty(self.n_weights, np.float64)
+        _lib.check(_lib.lib().ti_adw_train_get_state(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), None, None, None, None))
+        return w
+
+
 def selftest(device: int = 0):
     _lib.check(_lib.lib().ti_selftest(int(device)))

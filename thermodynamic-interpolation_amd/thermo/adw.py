@@ -236,3 +236,82 @@ class StandardIntegrator:
         self.n_steps_per_particle = self.ode_wrapper.b.engine().step_counts(B) if self.step_control == "trajectory" else None
         dlogp = C.like(res[1][:, :, None], x0s) if self.return_dlogp else None
         return C.like(res[0][:, :, None] if d == 1 else res[0], x0s), dlogp
+
+
+def minibatch_indices(n, batch_size, n_steps, rng):
+    """[n_steps, batch_size] int64: rows of a set of n, epoch after epoch a fresh permutation cut into its full batches (drop_last),
+    as a shuffling DataLoader hands them out"""
+    per = n // batch_size
+    if per < 1:
+        raise ValueError(f"a set of {n} rows has no full batch of {batch_size}")
+    out = []
+    while len(out) < n_steps:
+        out.extend(rng.permutation(n)[:per * batch_size].reshape(per, batch_size))
+    return np.ascontiguousarray(np.stack(out[:n_steps]), np.int64)
+
+
+class Trainer:
+    """The optimiser side of adw/train.py:40-74 on the device (engine.AdwTrainer): loss_fn(b, ...) differentiated, clip_grad_norm_ at
+    max_grad_norm, torch.optim.Adam(lr, betas, eps, weight_decay), the NaN skip.  ``b`` is a thermo.adw / thermo.adw_nd
+    FCNetMultiBeta whose weights are the starting point; ``loss_fn`` a thermo.losses loss, which gives the kind, gamma, a and
+    t_distr.  The fp64 master weights live on the device; ``sync()`` writes them back into ``b``."""
+
+    def __init__(self, b, loss_fn, lr, weight_decay=0.0, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8):
+        ip = loss_fn.interpolant
+        self.b, self.loss_fn = b, loss_fn
+        self._kw = dict(kind=loss_fn.KIND, gamma=ip.gamma_name, a=ip.a_param, t_distr="uniform" if loss_fn.t_distr == "uniform" else "beta_half")
+        flat = _W.flatten_state_dict(b._sd, b._spec, dtype=np.float64)
+        self.lr = float(lr)
+        self.engine = _engine.AdwTrainer(b.hidden_size, b.num_layers, flat, dim=b.dim, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                         max_grad_norm=max_grad_norm, device=b._device)
+
+    def _rows(self, x, beta):
+        d = self.b.dim
+        x = np.ascontiguousarray(C.to_numpy(x, np.float32).reshape((-1,) if d == 1 else (-1, d)))
+        beta = np.ascontiguousarray(np.broadcast_to(C.to_numpy(beta, np.float32).reshape(-1), (x.shape[0],)))
+        return x, beta
+
+    def _draws(self, t, z, B):
+        d = self.b.dim
+        tv = None if t is None else np.ascontiguousarray(C.to_numpy(t, np.float32).reshape(B))
+        zv = None if z is None else np.ascontiguousarray(C.to_numpy(z, np.float32).reshape((B,) if d == 1 else (B, d)))
+        return tv, zv
+
+    def step(self, x0s, x1s, beta0s, beta1s, *, t=None, z=None, seed=0, draw=0, traj_offset=0) -> float:
+        """One optimiser step on the batch -> its mean loss (NaN where the step was skipped)"""
+        (x0, b0), (x1, b1) = self._rows(x0s, beta0s), self._rows(x1s, beta1s)
+        tv, zv = self._draws(t, z, x0.shape[0])
+        return self.engine.step(x0, x1, b0, b1, t=tv, z=zv, seed=seed, draw=draw, traj_offset=traj_offset, **self._kw)[0]
+
+    def loss(self, x0s, x1s, beta0s, beta1s, *, t=None, z=None, seed=0, draw=0, traj_offset=0) -> float:
+        """The mean loss of the batch at the current weights by the trainer's own forward pass; nothing is updated"""
+        (x0, b0), (x1, b1) = self._rows(x0s, beta0s), self._rows(x1s, beta1s)
+        tv, zv = self._draws(t, z, x0.shape[0])
+        return self.engine.grad(x0, x1, b0, b1, t=tv, z=zv, seed=seed, draw=draw, traj_offset=traj_offset, **self._kw)["mean"]
+
+    def fit(self, x0_all, x1_all, beta0_all, beta1_all, batch_size, n_steps, seed, *, draw=0, noise_seed=None):
+        """n_steps optimiser steps in one device loop: minibatches from permutations drawn on the host with `seed`
+        (minibatch_indices, independently for the two sets), step k with the (t, z) of draw + k under noise_seed (default: seed).
+        -> (mean loss of every step [n_steps], NaN where skipped; the number of skipped steps)"""
+        (x0, b0), (x1, b1) = self._rows(x0_all, beta0_all), self._rows(x1_all, beta1_all)
+        rng = np.random.default_rng(seed)
+        i0 = minibatch_indices(x0.shape[0], batch_size, n_steps, rng)
+        i1 = minibatch_indices(x1.shape[0], batch_size, n_steps, rng)
+        return self.engine.steps(x0, x1, b0, b1, i0, i1, seed=seed if noise_seed is None else noise_seed, draw=draw, **self._kw)
+
+    def set_lr(self, lr):
+        self.engine.set_lr(lr)
+        self.lr = float(lr)
+
+    def sync(self):
+        """Write the master weights back into ``b`` (load_state_dict: its drift engine is rebuilt on next use) -> b"""
+        return self.b.load_state_dict(_W.unflatten(self.engine.weights(), self.b._spec))
+
+    def state_dict(self):
+        """The optimiser state for resuming: master weights, moments, counters, learning rate"""
+        return dict(self.engine.state(), lr=self.lr)
+
+    def load_state_dict(self, state):
+        self.engine.load_state(w=state["w"], m=state["m"], v=state["v"], n_applied=int(state["n_applied"]))
+        self.set_lr(float(state["lr"]))
+        return self

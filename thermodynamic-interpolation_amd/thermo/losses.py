@@ -1,6 +1,7 @@
 """Mirror of the reference velocity losses (mdqm9/thermo/{ambient,latent}/losses.py, adw/thermo/losses.py) on top of libti_hip.so
 (ti_painn_vloss / ti_adw_vloss): forward evaluation only -- the number that says how good a checkpoint is in the terms it was trained
-in.  No gradients.
+in.  The gradients of the adw forms live in the trainer (thermo.adw.Trainer, engine.AdwTrainer: ti_adw_train_*); the molecule
+forms have none.
 
   StandardVelocityLoss(interpolant, t_distr="uniform")   forward(batch0, batch1, b)             ambient
                                                          forward(b, x0s, x1s, beta0s, beta1s)   adw
