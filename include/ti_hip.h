@@ -839,6 +839,80 @@ int ti_adw_train_get_state(ti_handle* h, double* w, double* m, double* v, int64_
 int ti_adw_train_set_state(ti_handle* h, const double* w, const double* m, const double* v, int64_t n_applied);
 int ti_adw_train_set_lr(ti_handle* h, double lr);
 
+/* ---- molecule trainer: cPaiNN trained on the velocity loss, on the device ----------------------------------------------------------
+ * The optimiser step of the molecule workflow (mdqm9/train_ambient.py:124-149 and its latent twin): StandardVelocityLoss with
+ * LinearInterpolant or OneSidedVelocityLoss with OneSidedLinearInterpolant on cPaiNN, its gradient with respect to every parameter,
+ * clip_grad_norm_, torch.optim.Adam with L2 weight decay, the NaN skip.  All three variants, F in {32, 64, 128, 256}, L >= 1, any
+ * edge template with E >= 1; uniform batches (one species, no edge mask), f32, one GPU.  A trainer is a handle of its own kind (3),
+ * freed by ti_destroy; every painn / adw / adw-trainer entry point refuses it by its kind check, and the calls below refuse every
+ * other handle with TI_E_ARG ("not a painn trainer handle").  It owns the fp64 master weights and both Adam moments, and an fp32
+ * working copy in the canonical layout of ti_painn_create (weights.painn_param_spec), refreshed by the optimiser kernel.
+ * ti_painn_trainer_create: the checks of ti_painn_create in its order (weights are fp64 here; atom_ids may repeat), the weight count,
+ *   then: a precision other than TI_PREC_F32 is TI_E_UNSUPPORTED; n_edges == 0 is TI_E_UNSUPPORTED; the train descriptor's checks
+ *   (those of ti_adw_train_desc) are TI_E_ARG.  All before any device call.
+ *
+ * Rows.  A call evaluates R = 2B molecules [xt+; xt-] (ONE_SIDED: B); the halves share t, cond and the embeddings' inputs.  Node row
+ *   n = r A + a, edge row r E + k with k the template edge.
+ * Forward.  The states, the drawn t and z, the three centrings, the loss rows l_b and *out_mean = sum_b l_b / (B A) are the
+ *   velocity-loss block's above, by the same kernels, on the drift the trainer's own forward pass gives.  That pass keeps every
+ *   intermediate in device memory and is made of other kernels than the fused drift: every Linear is one fmaf chain per output over
+ *   its inputs in order from +0.0 on v_mfma_f32_16x16x4_f32, the bias added afterwards; LayerNorm (eps 1e-5, biased variance) + SiLU,
+ *   the message combine, the per-node sums, the update and the readout are elementwise fp32 kernels.  Its relation to ti_painn_vloss
+ *   on an f32 drift handle of the same weights is therefore closeness (fp32 round-off), not identity.
+ * Backward.  The gradient is of the MEAN loss: d / d b+- = (b+- - target+-) / (B A), target+- = (x1 - x0) +- gamma'(t) z, in fp64 and
+ *   rounded to fp32 once.  The reverse pass runs the forward graph backwards in fp32.  No gradient flows into x, edge_dir, d or the
+ *   centring; d||vv|| / dvv is 0 where vv = 0; the last message layer's de chunk and the readout's first output get zero gradient;
+ *   silu'(u) = s + silu(u) (1 - s).  A per-node sum (the message sums of the forward pass; s[src] and gates v[src] over a node's
+ *   outgoing edges, cross (g x dir) over its incoming ones in the reverse pass) walks the template's edges in order, the identity
+ *   term first.  Every reduction over rows -- a bias, a LayerNorm weight or bias, a row of the atom or edge-type table -- is taken in
+ *   fp64 from the fp32 terms: 16 accumulators, accumulator p adding rows (tables: molecules) p, p + 16, .. in order from +0.0, then
+ *   the accumulators in order; a column sum over rows does so per tile of 2048 rows and adds the tiles in order.  A weight gradient contracts over the rows in slices of 2048 rows (TI_PAINN_TRAIN_SLICE; fixed by the
+ *   shapes alone), each slice one fp32 fmaf chain per entry in row order, the slices added in fp64 in slice order from +0.0.  No
+ *   atomics: a gradient is a function of the weights and the batch -- including the ORDER of its rows -- and not of the launch, the
+ *   memory space of the inputs, or what ran before.
+ * Clipping, Adam, NaN skip: as for the adw trainer above, by the same kernels, with the mean's divisor B A.
+ * ti_painn_train_grad: loss rows, their mean, the gradient of the mean loss at the current weights and its norm; nothing is updated.
+ *   out_loss [B] fp64 [host|device] by mem; out_mean, out_grad [n_weights] (canonical layout), out_gnorm fp64 host; any may be NULL.
+ *   cond [B][A][ncond] as ti_painn_vloss takes it (NULL for the single-T variant).  Non-finite values are returned as they are.
+ * ti_painn_train_apply: clip + Adam with a GIVEN gradient (host, fp64, canonical layout); *out_skipped = 1 where a non-finite entry
+ *   made the step a skipped one.
+ * ti_painn_train_step: one optimiser step enqueued on the handle's stream, the gradient staying on the device; it is
+ *   ti_painn_train_grad followed by ti_painn_train_apply of its out_grad, bit for bit.  *out_mean: the step's mean loss, NaN where
+ *   the step was skipped; *out_skipped 0 / 1.
+ * ti_painn_train_get_state / set_state / set_lr: as ti_adw_train_get_state / set_state / set_lr.
+ * Checks of ti_painn_train_grad / ti_painn_train_step, before any device work, in this order: every descriptor check of
+ *   ti_painn_vloss in its order (through the given t); the workspace of the call above the trainer's max_workspace_bytes
+ *   (TI_E_UNSUPPORTED; the text names both numbers); a NULL x0, x1 or (where the variant has temperatures) cond; a NULL or other
+ *   handle.
+ * ti_painn_train_workspace_bytes: what a call over B molecules of loss kind `kind` (TI_VLOSS_*) needs beside the trainer's state, in
+ *   bytes (< 0: an error code).  Everything is stored, nothing recomputed.  With halves = 2 (STANDARD) or 1, Rn = halves B A,
+ *   Re = halves B E, Rm = max(Rn, Re):
+ *     4 [ Re (4 + F (21 L + 15)) + Rn (F (nE + 23 L + 38) + 19) + 4 F Rm + 3 B A ]        activations and gradient buffers, fp32
+ *   + 4 ceil(max(Re, 3 Rn) / 2048) (8 F^2 + 11 F)                                          weight-gradient slices of one block
+ *   + 8 (5 F ceil(Rm / 2048) + 6 B A + B + max(3 ceil(B A / 1024), ceil(B / 1024), ceil(n_weights / 1024)))      column-sum tiles,
+ *                                                                                          centring, loss rows, tile partials, fp64
+ *   with nE = 4, 3, 2 for the ambient, multi-T and single-T variant.  max_workspace_bytes == 0 means
+ *   TI_PAINN_TRAIN_DEFAULT_WORKSPACE (32 GiB). */
+#define TI_PAINN_TRAIN_SLICE 2048
+#define TI_PAINN_TRAIN_DEFAULT_WORKSPACE (32ull << 30)
+typedef struct ti_painn_train_desc {
+    double   lr, beta1, beta2, eps, weight_decay;  /* torch.optim.Adam: lr, betas = (0.9, 0.999), eps = 1e-8, weight_decay = 0 */
+    double   max_grad_norm;                        /* clip_grad_norm_; <= 0 or inf: no clipping */
+    uint64_t max_workspace_bytes;                  /* the largest workspace a call may take; 0: TI_PAINN_TRAIN_DEFAULT_WORKSPACE */
+} ti_painn_train_desc;
+ti_handle* ti_painn_trainer_create(const ti_painn_desc* desc, const double* weights, size_t n_weights, const int32_t* edge_src,
+                                   const int32_t* edge_dst, const int32_t* edge_type, const int32_t* atom_ids,
+                                   const ti_painn_train_desc* train, int device);
+int ti_painn_train_grad(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* cond, const float* t,
+                        const float* z, int64_t B, double* out_loss, double* out_mean, double* out_grad, double* out_gnorm, int mem);
+int ti_painn_train_apply(ti_handle* h, const double* grad, int32_t* out_skipped);
+int ti_painn_train_step(ti_handle* h, const ti_vloss_desc* desc, const float* x0, const float* x1, const float* cond, const float* t,
+                        const float* z, int64_t B, double* out_mean, int32_t* out_skipped, int mem);
+int ti_painn_train_get_state(ti_handle* h, double* w, double* m, double* v, int64_t* n_applied, int64_t* n_skipped);
+int ti_painn_train_set_state(ti_handle* h, const double* w, const double* m, const double* v, int64_t n_applied);
+int ti_painn_train_set_lr(ti_handle* h, double lr);
+int64_t ti_painn_train_workspace_bytes(ti_handle* h, int64_t B, int32_t kind);
+
 #ifdef __cplusplus
 }
 #endif

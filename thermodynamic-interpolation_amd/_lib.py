@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "ti_painn_vloss", "ti_adw_vloss", "ti_painn_vloss_interp", "ti_adw_vloss_interp",
     "ti_adw_trainer_create", "ti_adw_train_grad", "ti_adw_train_apply", "ti_adw_train_steps", "ti_adw_train_get_state",
     "ti_adw_train_set_state", "ti_adw_train_set_lr",
+    "ti_painn_trainer_create", "ti_painn_train_grad", "ti_painn_train_apply", "ti_painn_train_step", "ti_painn_train_get_state",
+    "ti_painn_train_set_state", "ti_painn_train_set_lr", "ti_painn_train_workspace_bytes",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -82,6 +84,8 @@ VLOSS_DOMAIN = 0x564C4F53
 VLOSS_MAX_TBINS = 1024
 # ti_adw_train_*: the largest minibatch (TI_ADW_TRAIN_MAX_B), the rows of a slice of the weight-gradient contraction
 ADW_TRAIN_MAX_B, ADW_TRAIN_ROW_TILE = 1 << 16, 512
+# ti_painn_train_*: the rows of a slice of the weight-gradient contraction (TI_PAINN_TRAIN_SLICE), the default workspace budget
+PAINN_TRAIN_SLICE, PAINN_TRAIN_DEFAULT_WORKSPACE = 2048, 32 << 30
 
 
 class PainnDesc(C.Structure):
@@ -125,6 +129,10 @@ class VlossDesc(C.Structure):
 class AdwTrainDesc(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double)]
+
+
+class PainnTrainDesc(C.Structure):
+    _fields_ = AdwTrainDesc._fields_ + [("max_workspace_bytes", C.c_uint64)]
 
 
 class TiError(RuntimeError):
@@ -243,6 +251,16 @@ def lib():
     L.ti_adw_train_get_state.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.ti_adw_train_set_state.argtypes = [vp, dp, dp, dp, C.c_int64]
     L.ti_adw_train_set_lr.argtypes = [vp, C.c_double]
+    L.ti_painn_trainer_create.restype = vp
+    L.ti_painn_trainer_create.argtypes = [C.POINTER(PainnDesc), dp, C.c_size_t, ip, ip, ip, ip, C.POINTER(PainnTrainDesc), C.c_int]
+    L.ti_painn_train_grad.argtypes = [vp, vd, vp, vp, vp, vp, vp, C.c_int64, vp, dp, dp, dp, C.c_int]
+    L.ti_painn_train_apply.argtypes = [vp, dp, C.POINTER(C.c_int32)]
+    L.ti_painn_train_step.argtypes = [vp, vd, vp, vp, vp, vp, vp, C.c_int64, dp, C.POINTER(C.c_int32), C.c_int]
+    L.ti_painn_train_get_state.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.ti_painn_train_set_state.argtypes = [vp, dp, dp, dp, C.c_int64]
+    L.ti_painn_train_set_lr.argtypes = [vp, C.c_double]
+    L.ti_painn_train_workspace_bytes.restype = C.c_int64
+    L.ti_painn_train_workspace_bytes.argtypes = [vp, C.c_int64, C.c_int32]
     _lib = L
     return L
 

@@ -31,7 +31,7 @@ int64_t ti_rollout_rows(int32_t n_step, int32_t save_every)
 int ti_reserve(ti_handle* h, int64_t B)
 {
     if (!h || B < 0) return fail(TI_E_ARG, "bad handle / B");
-    if (h->kind == 2) return fail(TI_E_ARG, "an adw trainer handle sizes its workspace per call: ti_reserve takes painn and adw handles");
+    if (h->kind >= 2) return fail(TI_E_ARG, "a trainer handle sizes its workspace per call: ti_reserve takes painn and adw handles");
     return guarded([&]() -> int { set_device(h); if (h->kind == 0) ensure_painn_ws(h, B); else ensure_adw_ws(h, B); return TI_OK; });
 }
 

@@ -7,7 +7,7 @@ namespace {
 // Validates desc [K][5] against the handle (before any device work) and uploads it with ref / select into set `which`.
 int obs_upload(ti_handle* h, int which, const int32_t* desc, int K, const float* ref, const int32_t* select)
 {
-    if (h->kind == 2) return fail(TI_E_ARG, "an adw trainer handle has no trajectories to observe");
+    if (h->kind >= 2) return fail(TI_E_ARG, "a trainer handle has no trajectories to observe");
     if (K < 1) return fail(TI_E_ARG, "K must be >= 1");
     const int A = h->kind == 0 ? h->d.n_atoms : 1, dim = h->a_dim;
     bool rmsd = false;

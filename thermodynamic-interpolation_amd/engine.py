@@ -1138,5 +1138,120 @@ class AdwTrainer(_Engine):
         return w
 
 
+class PainnTrainer(_Engine):
+    """cPaiNN trained on the velocity loss on the device (ti_painn_train_*): fp64 master weights and Adam moments, a forward pass
+    that keeps its intermediates and the reverse pass through every layer, products on the f32 matrix cores, every reduction over
+    rows in fp64, clip_grad_norm_ + torch.optim.Adam (L2 weight_decay) in fp64, the NaN skip decided on the device.  `flat`: the
+    canonical fp64 weights (weights.flatten_state_dict with weights.painn_param_spec).  Arrays are numpy or CUDA tensors as
+    PainnEngine.velocity_loss takes them: x0, x1 [B, A, 3], cond [B, A, ncond] (None for the single-T variant)."""
+
+    def __init__(self, variant, F, L, A, edge_src, edge_dst, edge_type, atom_ids, flat, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, max_grad_norm=1.0, max_workspace_bytes=0, n_types=25, temp_length=10.0, time_length=10.0,
+                 length_scale=10.0, temperatures=(300, 400, 500, 600, 700, 800, 900, 1000), device=0, precision="f32"):
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
+        temps = np.asarray(temperatures, np.float32)
+        es, ed, et, ai = (np.ascontiguousarray(a, np.int32) for a in (edge_src, edge_dst, edge_type, atom_ids))
+        if not (es.shape == ed.shape == et.shape) or es.ndim != 1 or ai.shape != (A,):
+            raise ValueError("edge_src/edge_dst/edge_type must be 1-D and equally long; atom_ids must have A entries")
+        self.variant, self.F, self.L, self.A, self.E = int(variant), int(F), int(L), int(A), int(es.size)
+        self.ncond = W.N_COND[self.variant]
+        self.desc = _lib.PainnDesc(self.variant, self.F, self.L, int(n_types), self.A, self.E, float(temp_length), float(time_length),
+                                   float(length_scale), float(temps.mean(dtype=np.float32)), float(temps.max() - temps.min()), _lib.PRECISIONS[precision])
+        self.train_desc = _lib.PainnTrainDesc(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(max_grad_norm),
+                                              int(max_workspace_bytes))
+        w = np.ascontiguousarray(flat, np.float64).reshape(-1)
+        self.n_weights, self.device = int(w.size), int(device)
+        self.h = _lib.lib().ti_painn_trainer_create(C.byref(self.desc), w.ctypes.data_as(C.POINTER(C.c_double)), w.size, _lib.iptr(es), _lib.iptr(ed),
+                                                    _lib.iptr(et), _lib.iptr(ai), C.byref(self.train_desc), self.device)
+        if not self.h:
+            raise _lib.TiError(-1, _lib.last_error())
+
+    def _call_args(self, x0, x1, cond, t, z):
+        B = int(x0.shape[0])
+        xs = (B, self.A, 3)
+        if (cond is None) != (self.ncond == 0):
+            raise ValueError(f"this variant takes {'no cond' if self.ncond == 0 else f'cond [B, A, {self.ncond}]'}")
+        ptrs, dev, keep = self._ptrs((x0, xs, False, "x0"), (x1, xs, False, "x1"), (cond, (B, self.A, self.ncond), False, "cond"),
+                                     (t, (B,), False, "t"), (z, xs, False, "z"))
+        return B, ptrs, dev, keep
+
+    def grad(self, x0, x1, cond=None, *, kind="standard", gamma="brownian", a=1.0, center="batch", t=None, t_distr="uniform", z=None, seed=0,
+             traj_offset=0, draw=0):
+        """ti_painn_train_grad -> dict(loss [B] float64 (where x0 lives), mean, grad [n_weights] float64 numpy, gnorm); no update."""
+        desc = self._vloss_desc(kind, gamma, a, center, t, t_distr, seed, traj_offset, draw, 0)
+        B, (x0p, x1p, cp, tp, zp), dev, keep = self._call_args(x0, x1, cond, t, z)
+        if dev:
+            import torch
+            loss = torch.empty(B, dtype=torch.float64, device=x0.device)
+            lp = C.c_void_p(loss.data_ptr())
+        else:
+            loss = np.empty(B, np.float64)
+            lp = C.c_void_p(loss.ctypes.data)
+        g = np.empty(self.n_weights, np.float64)
+        mean, gnorm = C.c_double(0.0), C.c_double(0.0)
+        _lib.check(_lib.lib().ti_painn_train_grad(self.h, C.byref(desc), x0p, x1p, cp, tp, zp, B, lp, C.byref(mean),
+                                                  g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(gnorm), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return dict(loss=loss, mean=mean.value, grad=g, gnorm=gnorm.value)
+
+    def apply(self, g):
+        """ti_painn_train_apply: clip + Adam with the given fp64 gradient [n_weights] -> True where the step was skipped (non-finite entry)."""
+        g = np.ascontiguousarray(g, np.float64).reshape(-1)
+        if g.size != self.n_weights:
+            raise ValueError(f"g must hold {self.n_weights} entries, got {g.size}")
+        skipped = C.c_int32(0)
+        _lib.check(_lib.lib().ti_painn_train_apply(self.h, g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(skipped)))
+        return bool(skipped.value)
+
+    def step(self, x0, x1, cond=None, *, kind="standard", gamma="brownian", a=1.0, center="batch", t=None, t_distr="uniform", z=None, seed=0,
+             traj_offset=0, draw=0):
+        """ti_painn_train_step: one optimiser step on the batch -> (mean loss, or NaN where the step was skipped; skipped 0 / 1)."""
+        desc = self._vloss_desc(kind, gamma, a, center, t, t_distr, seed, traj_offset, draw, 0)
+        B, (x0p, x1p, cp, tp, zp), dev, keep = self._call_args(x0, x1, cond, t, z)
+        mean, skipped = C.c_double(0.0), C.c_int32(0)
+        _lib.check(_lib.lib().ti_painn_train_step(self.h, C.byref(desc), x0p, x1p, cp, tp, zp, B, C.byref(mean), C.byref(skipped),
+                                                  _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return mean.value, int(skipped.value)
+
+    def state(self):
+        """dict(w, m, v [n_weights] float64, n_applied, n_skipped): master weights, Adam moments, counters"""
+        w, m, v = (np.empty(self.n_weights, np.float64) for _ in range(3))
+        na, ns = C.c_int64(0), C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        _lib.check(_lib.lib().ti_painn_train_get_state(self.h, w.ctypes.data_as(dp), m.ctypes.data_as(dp), v.ctypes.data_as(dp), C.byref(na), C.byref(ns)))
+        return dict(w=w, m=m, v=v, n_applied=int(na.value), n_skipped=int(ns.value))
+
+    def load_state(self, w=None, m=None, v=None, n_applied=0, **_):
+        dp = C.POINTER(C.c_double)
+        arrs = []
+        for name, a in (("w", w), ("m", m), ("v", v)):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.float64).reshape(-1)
+            if a.size != self.n_weights:
+                raise ValueError(f"{name} must hold {self.n_weights} entries, got {a.size}")
+            arrs.append(a)
+        ptrs = [None if a is None else a.ctypes.data_as(dp) for a in arrs]
+        _lib.check(_lib.lib().ti_painn_train_set_state(self.h, *ptrs, int(n_applied)))
+
+    def set_lr(self, lr):
+        _lib.check(_lib.lib().ti_painn_train_set_lr(self.h, float(lr)))
+        self.train_desc.lr = float(lr)
+
+    def weights(self):
+        """The fp64 master weights in the canonical layout [n_weights]"""
+        w = np.empty(self.n_weights, np.float64)
+        _lib.check(_lib.lib().ti_painn_train_get_state(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), None, None, None, None))
+        return w
+
+    def workspace_bytes(self, B, kind="standard"):
+        """ti_painn_train_workspace_bytes: what a call over B molecules needs beside the trainer's state"""
+        n = int(_lib.lib().ti_painn_train_workspace_bytes(self.h, int(B), _lib.VLOSS_KINDS[kind]))
+        if n < 0:
+            raise _lib.TiError(n, _lib.last_error())
+        return n
+
+
 def selftest(device: int = 0):
     _lib.check(_lib.lib().ti_selftest(int(device)))

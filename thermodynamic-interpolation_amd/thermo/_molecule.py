@@ -490,3 +490,97 @@ class MoleculeIntegratorBase:
         xts = C.like(sb.unpad(path), batch.x0)
         dlogp = batch.x0.new_zeros(B) if gpu else C.like(np.zeros(B, np.float32) * self.SCALE_DLOGP, batch.x0)      # reference: zeros(batch_size) (* 1e2 in ambient)
         return xts, dlogp, nfe
+
+
+class MoleculeTrainerBase:
+    """The optimiser side of mdqm9/train_ambient.py:124-149 and its latent twin on the device (engine.PainnTrainer): loss_fn
+    differentiated with respect to every parameter of cPaiNN, clip_grad_norm_ at max_grad_norm, torch.optim.Adam(lr, betas, eps,
+    weight_decay), the NaN skip.  ``b`` is a thermo cPaiNN whose weights are the starting point; ``loss_fn`` a thermo.losses loss,
+    which gives the kind, gamma, a and t_distr.  The fp64 master weights live on the device; ``sync()`` writes them back into ``b``.
+    A trainer serves one species: the device trainer is built from the first batch's template, and a batch with another template,
+    an edge mask or mixed species is refused."""
+    BETA_NAME = "beta_half"              # what t_distr='beta' means for this workflow's loss
+
+    def __init__(self, b, loss_fn, lr, weight_decay=0.0, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, max_workspace_bytes=0):
+        ip = loss_fn.interpolant
+        self.b, self.loss_fn, self.lr = b, loss_fn, float(lr)
+        self._kw = dict(kind=loss_fn.KIND, gamma=ip.gamma_name, a=ip.a_param, t_distr="uniform" if loss_fn.t_distr == "uniform" else self.BETA_NAME)
+        self._opt = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, max_workspace_bytes=max_workspace_bytes)
+        self.engine, self._key, self._pending = None, None, None
+
+    def _engine_for(self, batch):
+        try:
+            B, A, src, dst, ety, ids = split_batch(batch, self.b.ATOM_KEY)
+        except ValueError as e:
+            raise NotImplementedError(f"the trainer takes uniform batches (one species, one graph, no edge mask): {e}") from None
+        key = (A, src.tobytes(), dst.tobytes(), ety.tobytes(), ids.tobytes())
+        if self.engine is None:
+            b = self.b
+            flat = _W.flatten_state_dict(b._sd, b._spec, dtype=np.float64)
+            self.engine = _engine.PainnTrainer(b.VARIANT, b.n_features, b.score_layers, A, src, dst, ety, ids, flat, n_types=b.n_types,
+                                               temp_length=b.temp_length, time_length=b.time_length, temperatures=b.temperatures,
+                                               device=b._device, **self._opt)
+            self._key = key
+            if self._pending is not None:
+                self.load_state_dict(self._pending)
+        elif key != self._key:
+            raise NotImplementedError("a trainer serves one species: this batch has another template or other atom ids")
+        return B, A
+
+    def _args(self, batch, x0, x1, conds, t, z):
+        from .losses import _molecule_t
+        B, A = self._engine_for(batch)
+        if len(conds) != self.engine.ncond:
+            raise ValueError(f"this model takes {self.engine.ncond} conditioning value(s) per node, the batch form gives {len(conds)}")
+        gpu = C.is_cuda(x0)
+        x0, x1 = C.as_f32(x0, (B, A, 3)), C.as_f32(x1, (B, A, 3))
+        cond = None
+        if conds and gpu:
+            import torch
+            cond = torch.stack([c.detach().to(x0.device, torch.float32).reshape(B, A) for c in conds], dim=-1).contiguous()
+        elif conds:
+            cond = np.ascontiguousarray(np.stack([C.to_numpy(c).astype(np.float32).reshape(B, A) for c in conds], axis=-1))
+        tv, zv = _molecule_t(t, B, A), (None if z is None else C.as_f32(z, (B, A, 3)))
+        if gpu:
+            import torch
+            tv = None if tv is None else torch.from_numpy(tv).to(x0.device)
+            zv = None if zv is None else (zv if C.is_cuda(zv) else torch.from_numpy(zv).to(x0.device))
+        elif zv is not None and C.is_cuda(zv):
+            zv = C.to_numpy(zv, np.float32)
+        return x0, x1, cond, tv, zv
+
+    def _step(self, batch, x0, x1, conds, t, z, seed, draw, traj_offset, center):
+        x0, x1, cond, tv, zv = self._args(batch, x0, x1, conds, t, z)
+        return self.engine.step(x0, x1, cond, center=center or "batch", t=tv, z=zv, seed=seed, draw=draw, traj_offset=traj_offset, **self._kw)[0]
+
+    def _loss(self, batch, x0, x1, conds, t, z, seed, draw, traj_offset, center):
+        x0, x1, cond, tv, zv = self._args(batch, x0, x1, conds, t, z)
+        return self.engine.grad(x0, x1, cond, center=center or "batch", t=tv, z=zv, seed=seed, draw=draw, traj_offset=traj_offset, **self._kw)["mean"]
+
+    def set_lr(self, lr):
+        self.lr = float(lr)
+        self._opt["lr"] = self.lr
+        if self.engine is not None:
+            self.engine.set_lr(lr)
+
+    def sync(self):
+        """Write the master weights back into ``b`` in the reference's keys (load_state_dict: its drift engines are rebuilt on next use) -> b"""
+        if self.engine is None:
+            return self.b
+        return self.b.load_state_dict(_W.unflatten(self.engine.weights(), self.b._spec))
+
+    def state_dict(self):
+        """The optimiser state for resuming: master weights, moments, counters, learning rate"""
+        if self.engine is None:
+            raise RuntimeError("the trainer has seen no batch yet: there is no device state to save")
+        return dict(self.engine.state(), lr=self.lr)
+
+    def load_state_dict(self, state):
+        if self.engine is None:              # applied when the first batch builds the device trainer
+            self._pending = dict(state)
+            self.lr = float(state["lr"]); self._opt["lr"] = self.lr
+            return self
+        self._pending = None
+        self.engine.load_state(w=state["w"], m=state["m"], v=state["v"], n_applied=int(state["n_applied"]))
+        self.set_lr(float(state["lr"]))
+        return self

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 from .. import weights as _W
 from . import interpolants, losses  # noqa: F401  (the reference's thermo.ambient.interpolants / .losses)
-from ._molecule import DEFAULT_TEMPS, MoleculeIntegratorBase, ODEWrapperBase, PaiNNShell
+from ._molecule import DEFAULT_TEMPS, MoleculeIntegratorBase, MoleculeTrainerBase, ODEWrapperBase, PaiNNShell
 
 
 class cPaiNN(PaiNNShell):
@@ -32,3 +32,17 @@ class MoleculeIntegrator(MoleculeIntegratorBase):
     def rollout(self, batch, traj_offset: int = 0):
         xts, dlogp, nfe = self._rollout(batch, traj_offset)
         return xts, dlogp, nfe, batch.batch
+
+
+class Trainer(MoleculeTrainerBase):
+    """Trains an ambient cPaiNN on StandardVelocityLoss (train_ambient.py:124-149): step(batch0, batch1) is one optimiser step on the
+    pair of batches the reference's loader yields (batch0.x at T0, batch1.x at T1; fields as losses.forward reads them)."""
+    BETA_NAME = "beta_half"
+
+    def step(self, batch0, batch1, *, t=None, z=None, seed=0, draw=0, traj_offset=0, center=None) -> float:
+        """One optimiser step -> the batch's mean loss (NaN where the step was skipped)"""
+        return self._step(batch0, batch0.x, batch1.x, (batch0.T, batch1.T), t, z, seed, draw, traj_offset, center)
+
+    def loss(self, batch0, batch1, *, t=None, z=None, seed=0, draw=0, traj_offset=0, center=None) -> float:
+        """The mean loss at the current weights by the trainer's own forward pass; nothing is updated"""
+        return self._loss(batch0, batch0.x, batch1.x, (batch0.T, batch1.T), t, z, seed, draw, traj_offset, center)

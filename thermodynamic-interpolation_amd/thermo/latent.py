@@ -7,7 +7,7 @@ from __future__ import annotations
 
 from .. import weights as _W
 from . import interpolants, losses  # noqa: F401  (the reference's thermo.latent.interpolants / .losses)
-from ._molecule import DEFAULT_TEMPS, MoleculeIntegratorBase, ODEWrapperBase, PaiNNShell
+from ._molecule import DEFAULT_TEMPS, MoleculeIntegratorBase, MoleculeTrainerBase, ODEWrapperBase, PaiNNShell
 
 
 class cPaiNN(PaiNNShell):
@@ -33,3 +33,20 @@ class MoleculeIntegrator(MoleculeIntegratorBase):
     def rollout(self, batch, traj_offset: int = 0):
         xts, dlogp, self.n_fevals = self._rollout(batch, traj_offset)
         return xts, dlogp, batch.batch
+
+
+class Trainer(MoleculeTrainerBase):
+    """Trains a latent cPaiNN on OneSidedVelocityLoss (train_latent.py): step(batch) is one optimiser step on a batch with the noise
+    in batch.x0 and the data in batch.x1 (fields as losses.forward reads them)."""
+    BETA_NAME = "beta_2_1"
+
+    def _conds(self, batch):
+        return tuple(getattr(batch, k) for k in self.b.COND_KEYS)
+
+    def step(self, batch, *, t=None, z=None, seed=0, draw=0, traj_offset=0, center=None) -> float:
+        """One optimiser step -> the batch's mean loss (NaN where the step was skipped)"""
+        return self._step(batch, batch.x0, batch.x1, self._conds(batch), t, z, seed, draw, traj_offset, center)
+
+    def loss(self, batch, *, t=None, z=None, seed=0, draw=0, traj_offset=0, center=None) -> float:
+        """The mean loss at the current weights by the trainer's own forward pass; nothing is updated"""
+        return self._loss(batch, batch.x0, batch.x1, self._conds(batch), t, z, seed, draw, traj_offset, center)
