@@ -913,6 +913,83 @@ int ti_painn_train_set_state(ti_handle* h, const double* w, const double* m, con
 int ti_painn_train_set_lr(ti_handle* h, double lr);
 int64_t ti_painn_train_workspace_bytes(ti_handle* h, int64_t B, int32_t kind);
 
+/* ---- molecule trainer, whole epochs: resident sets, many steps a call, base samples drawn on the device -----------------------------
+ * ti_painn_train_steps: n_steps steps of a painn trainer handle enqueued on its stream with ONE host synchronisation, at the end.
+ *   x0 [n0,A,3] and x1 [n1,A,3] are the resident sets, temp0 [n0] and temp1 [n1] one temperature per molecule (the reference repeats
+ *   it over the atoms); all four, and the indices, live in host or device memory by mem.  Step k takes rows idx0[kB .. kB+B-1] of set 0
+ *   and idx1[..] of set 1 (int64), gathered on the device into the buffers the passes of ti_painn_train_step read; the same kernel
+ *   writes the conditioning: ambient cond[b][a] = (temp0[idx0], temp1[idx1]), multi-T latent cond[b][a] = temp1[idx1] (temp0 is not
+ *   read), single-T none (both temperature pointers must be NULL).  idx0 == idx1 == NULL: n_steps must be 1 and the step uses rows
+ *   0..B-1.  The call takes no t and no z: both are drawn as ti_painn_vloss draws them, with draw = desc->draw + k and id =
+ *   desc->traj_offset + row in the minibatch (TI_TDIST_GIVEN is therefore refused by the descriptor check).  A skipped step consumes
+ *   its draw index.
+ *   Nothing waits inside the call.  The host keeps a mirror of (n_applied, n_skipped), brought up to date at the end of every call that
+ *   steps; from it the Adam bias terms of every count that can occur (n_applied + 1 .. n_applied + n_steps) are uploaded once as a
+ *   table, which the optimiser kernel indexes by the DEVICE counter (after a skip the next step reads the entry the skipped one did not
+ *   use).  The mean loss of step k goes to entry k of a device log; the NaN skip is decided on the device as in ti_painn_train_step.
+ *   After the one synchronisation out_loss [n_steps] (fp64 host; NaN where skipped) and *out_skipped (the steps of this call that were
+ *   skipped) are copied; either may be NULL.
+ *   update == 1, noise == TI_NOISE_GIVEN: the call is, bit for bit, the sequence of ti_painn_train_step calls on the gathered rows
+ *   with draw = desc->draw + k -- master weights, both moments, both counters and every loss.
+ *   update == 0: forward only.  Only the forward pass and the loss reduction run; weights, moments and counters are untouched, and
+ *   out_loss[k] is, bit for bit, the out_mean ti_painn_train_grad returns for that minibatch (non-finite values as they are;
+ *   *out_skipped = 0).
+ *   track_best == 1: after the loss of step k is known and BEFORE its update, a kernel compares it with the best loss held in device
+ *   memory and, where it is strictly smaller, copies the fp64 master weights into the trainer's best_w buffer -- the weights that
+ *   produced that loss, as `copy.deepcopy(model) if loss < epoch_best_loss` keeps them, not the updated ones.  A step that is skipped
+ *   (its out_loss entry is NaN) never wins.
+ *   noise: TI_NOISE_GIVEN takes x0 from set 0.  TI_NOISE_DRAWN / TI_NOISE_ALIGNED (TI_VLOSS_ONE_SIDED only, x0 == NULL; n0, temp0 and
+ *   idx0's VALUES are not used, idx0 must still accompany idx1) produce the minibatch's x0 by the kernels of ti_painn_train_noise from
+ *   the gathered x1 with draw = desc->draw + k: a call is then, bit for bit, the loop of ti_painn_train_noise and ti_painn_train_step.
+ * ti_painn_train_best: the best weights tracked since the last reset: w [n_weights] fp64 host, *loss, *step (the 0-based count of the
+ *   winning step among the steps tracked since the last reset, over all calls); any may be NULL.  reset != 0 then forgets them.
+ *   TI_E_ARG where no call has tracked since the last reset (or the creation).  Where every tracked step was skipped: *step = -1, *loss
+ *   = +inf and w is not written.
+ * ti_painn_train_noise: the latent data set's base samples (mdqm9_latent.py:84-105) for B molecules.
+ *   Draw:    x0[b,a,c] = N(seed, traj_offset + b, draw, 3a + c), the Philox normal the STANDARD loss uses for z (one-sided losses have
+ *            no z, so the slot is free), bit for bit what oracle.normal returns.
+ *   Centre:  each molecule minus its mean over the atoms: the sum in fp64 in atom order from +0.0, divided by A, subtracted in fp64.
+ *            x1 is never modified (the data sets are centred already).
+ *   TI_NOISE_DRAWN:   out_x0 = that fp64 value rounded to fp32 once; x1 is not read and may be NULL.
+ *   TI_NOISE_ALIGNED: the proper rotation R (det +1) that minimises sum_a |x1_a - R x0_a|^2 is applied to the centred fp64 x0 in fp64
+ *            and the result rounded to fp32 once (scipy's Rotation.align_vectors(x1, x0)).  One thread per molecule, fp64 throughout:
+ *            K = sum_a x1_a x0_a^T over the atoms in order; the eigenvectors v_i of K^T K by 12 cyclic Jacobi sweeps over (0,1), (0,2),
+ *            (1,2), sorted by eigenvalue; u_1 = K v_1 / |K v_1|, u_2 = K v_2 made orthogonal to u_1 and normalised, u_3 = +-(u_1 x u_2)
+ *            with the sign of (K v_3) . (u_1 x u_2); R = u_1 v_1^T + u_2 v_2^T + d u_3 v_3^T with the determinant correction d =
+ *            det[u_1 u_2 u_3] det[v_1 v_2 v_3].  out_rot [B,3,3] fp64 (row-major, optional) is R.  Where the two largest eigenvalues of
+ *            Horn's matrix coincide (x1 a mirror image with equal small singular values, collinear atoms) the rotation is not unique and
+ *            one of the minimisers is returned.
+ *   No atomics, a fixed iteration count and order: a molecule's result repeats bit for bit and depends on (seed, traj_offset + b, draw,
+ *   its x1) alone -- not on B, its position, or its neighbours in the batch.  x1, out_x0 [B,A,3] fp32 and out_rot by mem.
+ * Checks of ti_painn_train_steps, before any device work, in this order: every descriptor check of ti_painn_vloss in its order (with
+ *   t == z == NULL); a NULL steps descriptor; n_steps < 1 (or above 2^31 - 1); an unknown update; an unknown noise; an unknown
+ *   track_best; noise != GIVEN with a loss kind other than ONE_SIDED; noise != GIVEN with a non-NULL x0; track_best with update == 0;
+ *   the workspace of the call above max_workspace_bytes (TI_E_UNSUPPORTED); one of idx0 / idx1 NULL; no indices with n_steps != 1;
+ *   n1 < 1 or (noise GIVEN) n0 < 1 (without indices: < B); desc->draw + n_steps - 1 above 2^31 - 1; a NULL x1 or (noise GIVEN) x0; a
+ *   missing temp1 (ambient, multi-T) or temp0 (ambient), or a given one on the single-T variant; a host index outside its set (device
+ *   indices are read back and checked before anything is enqueued); a NULL or other handle; noise != GIVEN on the ambient variant
+ *   (TI_E_UNSUPPORTED: its set 0 is data); TI_NOISE_ALIGNED with A < 3 (TI_E_UNSUPPORTED: the rotation is not unique).  All TI_E_ARG
+ *   unless stated.
+ * Checks of ti_painn_train_noise, in this order: noise neither DRAWN nor ALIGNED; B < 1; draw < 0; an unknown mem; a NULL out_x0;
+ *   ALIGNED with a NULL x1; a NULL or other handle; ALIGNED with A < 3 (TI_E_UNSUPPORTED).
+ * State.  ti_painn_train_workspace_bytes is unchanged.  Beside it a trainer that has served these calls holds, until it is destroyed:
+ *   the staged sets of a host call 4 (3 A (n0 + n1) + n0 + n1) bytes, the staged indices 16 n_steps B, the gathered minibatch
+ *   4 B A (6 + ncond), the loss log 8 n_steps, the bias table 16 n_steps, best_w 8 n_weights + 16, and the noise kernel's centred
+ *   fp64 samples 24 B A. */
+enum { TI_NOISE_GIVEN = 0, TI_NOISE_DRAWN = 1, TI_NOISE_ALIGNED = 2 };
+typedef struct ti_painn_steps_desc {
+    int64_t n_steps;
+    int32_t update;      /* 1: optimiser steps; 0: forward only, the loss of every minibatch at the current weights */
+    int32_t noise;       /* TI_NOISE_*; DRAWN / ALIGNED only with TI_VLOSS_ONE_SIDED, x0 must then be NULL */
+    int32_t track_best;  /* 1: keep the master weights of the step with the smallest loss seen since the last reset */
+} ti_painn_steps_desc;
+int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* desc, const ti_painn_steps_desc* steps, const float* x0, int64_t n0,
+                         const float* temp0, const float* x1, int64_t n1, const float* temp1, const int64_t* idx0, const int64_t* idx1,
+                         int64_t B, double* out_loss, int64_t* out_skipped, int mem);
+int ti_painn_train_best(ti_handle* h, double* w, double* loss, int64_t* step, int reset);
+int ti_painn_train_noise(ti_handle* h, uint64_t seed, int64_t traj_offset, int32_t draw, const float* x1, int64_t B, int32_t noise,
+                         float* out_x0, double* out_rot, int mem);
+
 #ifdef __cplusplus
 }
 #endif

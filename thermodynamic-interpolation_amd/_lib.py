@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "ti_adw_train_set_state", "ti_adw_train_set_lr",
     "ti_painn_trainer_create", "ti_painn_train_grad", "ti_painn_train_apply", "ti_painn_train_step", "ti_painn_train_get_state",
     "ti_painn_train_set_state", "ti_painn_train_set_lr", "ti_painn_train_workspace_bytes",
+    "ti_painn_train_steps", "ti_painn_train_best", "ti_painn_train_noise",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -86,6 +87,8 @@ VLOSS_MAX_TBINS = 1024
 ADW_TRAIN_MAX_B, ADW_TRAIN_ROW_TILE = 1 << 16, 512
 # ti_painn_train_*: the rows of a slice of the weight-gradient contraction (TI_PAINN_TRAIN_SLICE), the default workspace budget
 PAINN_TRAIN_SLICE, PAINN_TRAIN_DEFAULT_WORKSPACE = 2048, 32 << 30
+# ti_painn_train_steps / ti_painn_train_noise: where a minibatch's x0 comes from (TI_NOISE_*)
+PAINN_NOISES = {"given": 0, "drawn": 1, "aligned": 2}
 
 
 class PainnDesc(C.Structure):
@@ -133,6 +136,10 @@ class AdwTrainDesc(C.Structure):
 
 class PainnTrainDesc(C.Structure):
     _fields_ = AdwTrainDesc._fields_ + [("max_workspace_bytes", C.c_uint64)]
+
+
+class PainnStepsDesc(C.Structure):
+    _fields_ = [("n_steps", C.c_int64), ("update", C.c_int32), ("noise", C.c_int32), ("track_best", C.c_int32)]
 
 
 class TiError(RuntimeError):
@@ -261,6 +268,10 @@ def lib():
     L.ti_painn_train_set_lr.argtypes = [vp, C.c_double]
     L.ti_painn_train_workspace_bytes.restype = C.c_int64
     L.ti_painn_train_workspace_bytes.argtypes = [vp, C.c_int64, C.c_int32]
+    L.ti_painn_train_steps.argtypes = [vp, vd, C.POINTER(PainnStepsDesc), vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, dp,
+                                       C.POINTER(C.c_int64), C.c_int]
+    L.ti_painn_train_best.argtypes = [vp, dp, dp, C.POINTER(C.c_int64), C.c_int]
+    L.ti_painn_train_noise.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, C.c_int]
     _lib = L
     return L
 

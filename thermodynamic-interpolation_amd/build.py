@@ -42,9 +42,12 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api
            "adw_train_kernels.hip", "api_adw_train.hip",
            # molecule trainer (ti_painn_train_*): the forward pass that keeps its intermediates and the reverse pass through cPaiNN
            "painn_train_kernels.hip", "api_painn_train.hip",
+           # whole epochs of the molecule trainer (ti_painn_train_steps, ti_painn_train_best, ti_painn_train_noise): the minibatch gather
+           # with its conditioning and the best-weights rule; the latent base samples (Philox draw, centring, fp64 Kabsch rotation)
+           "painn_steps_kernels.hip", "painn_noise_kernels.hip",
            # layer-0 phi table (class pass, table kernel); the pair kernel's table builds live in painn_pair_nb*.hip
            "painn_phi0_kernels.hip"]
-HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "adw_train.hpp", "painn_train.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "vloss_normal.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",
+HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "adw_train.hpp", "painn_train.hpp", "painn_steps.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "vloss_normal.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",
            "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
 # -packed-fp32-ops off: v_pk_{fma,mul,add}_f32 do NOT run next to another wave's matrix instructions on gfx950 (a wave of them and a
 # wave of 16x16x32 fp16 MFMAs on one SIMD take the SUM of their times; scalar v_fma_f32, conversions and transcendentals overlap:

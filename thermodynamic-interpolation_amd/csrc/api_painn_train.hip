@@ -1,11 +1,13 @@
-// api_painn_train.hip -- the molecule trainer of the C ABI (include/ti_hip.h ti_painn_trainer_create .. ti_painn_train_workspace_bytes):
+// api_painn_train.hip -- the molecule trainer of the C ABI (include/ti_hip.h ti_painn_trainer_create .. ti_painn_train_noise):
 // the checks, the workspace plan, and the launch sequence of a training step -- interpolate and centre (vloss_kernels.hip), a forward
 // pass through cPaiNN that keeps every intermediate, loss rows (the velocity loss's own reduce kernel), the reverse pass, the fp64
 // combine of every parameter block, clip + Adam (adw_train_kernels.hip).  The products are the adw trainer's kernel; the column sums are
 // painn_train_kernels.hip's tiled twin of its bias kernel.  A step is enqueued on the handle's stream without a host
 // synchronisation: whether it is skipped is decided by the optimiser kernel from the two batch-wide sums in device memory.
+// ti_painn_train_steps enqueues many such steps on resident sets (painn_steps_kernels.hip gathers each minibatch, painn_noise_kernels.hip
+// draws the latent base samples) and synchronises once.
 #include "ti_handle.hpp"
-#include "painn_train.hpp"
+#include "painn_steps.hpp"
 
 namespace {
 
@@ -32,6 +34,13 @@ struct PainnTrainState {
     DevBuf<float> w32, part, arena, sx0, sx1, sc, tin, zin, t;
     DevBuf<unsigned char> is_bias;               // [nW] 1 where the gradient is written in fp64 directly (biases, LayerNorm, tables)
     DevBuf<int32_t> src, dst, etype, atom_ids;
+    // ti_painn_train_steps: the staged sets and indices of a host call, the gathered minibatch, the noise kernel's centred fp64 draws
+    // and its staged outputs, the best weights with (loss, step) and what the host knows of them
+    DevBuf<float> st0, st1, stt0, stt1, gx0, gx1, gcond, nx1, nout;
+    DevBuf<long long> idx0, idx1;
+    DevBuf<double> nxc, nrot, best_w, best;
+    bool best_tracked = false; long long best_steps = 0;      // a call has tracked since the last reset; the steps tracked since then
+    bool mirror_stale = false;                   // a many-step call did not reach its read-back: the next one reads the counters first
 };
 
 PainnTrainState* state_of(ti_handle* h) { return static_cast<PainnTrainState*>(h->train.get()); }
@@ -189,8 +198,9 @@ void ensure_ws(PainnTrainState* S, const Plan& p, long long B, int halves)
 
 // One forward and reverse pass on the device-resident rows (x0, x1 [B][A][3], cond [B][A][ncond]; t, z given or NULL): afterwards
 // S->loss holds the loss rows, S->red (their sum, the sum of the squared gradient entries) and S->grad the gradient of the mean loss.
+// reverse == false stops behind the loss rows and their sum: S->grad and the sum of squares are left as they were.
 void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, const ti_vloss_desc* d, const float* x0, const float* x1,
-                            const float* cond, const float* t_given, const float* z_given, long long B)
+                            const float* cond, const float* t_given, const float* z_given, long long B, bool reverse = true)
 {
     hipStream_t st = h->stream;
     const bool two = d->kind == TI_VLOSS_STANDARD;
@@ -251,6 +261,7 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
     vp.b = ar + p.bout; vp.loss = S->loss.p;
     HIP_CHECK(launch_vloss_reduce(vp, st));
     HIP_CHECK(launch_vloss_colsum(S->red.p + RED_LOSS, S->part64.p, S->loss.p, B, 1, st));
+    if (!reverse) return;
 
     // ---- reverse
     HIP_CHECK(launch_ptrain_gout(ar + p.gb, vp, st));
@@ -292,11 +303,15 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
     HIP_CHECK(launch_vloss_colsum(S->red.p + RED_SUMSQ, S->part64.p, S->sq.p, (long long)S->nW, 1, st));
 }
 
-// the two bias terms of step n_applied + 1, computed here and read by the optimiser kernel
-void upload_bias(ti_handle* h, PainnTrainState* S, std::vector<double>& tab)
+// the two bias terms of steps n_applied + 1 .. n_applied + n, computed here and indexed on the device by the steps applied so far
+void upload_bias(ti_handle* h, PainnTrainState* S, std::vector<double>& tab, long long n = 1)
 {
-    const double k = (double)(S->n_applied + 1);
-    tab = {S->td.lr / (1.0 - std::pow(S->td.beta1, k)), std::sqrt(1.0 - std::pow(S->td.beta2, k))};
+    tab.resize(2 * (size_t)n);
+    for (long long i = 0; i < n; ++i) {
+        const double k = (double)(S->n_applied + 1 + i);
+        tab[2 * i] = S->td.lr / (1.0 - std::pow(S->td.beta1, k));
+        tab[2 * i + 1] = std::sqrt(1.0 - std::pow(S->td.beta2, k));
+    }
     grow(S->bias, tab.size());
     HIP_CHECK(hipMemcpyAsync(S->bias.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
 }
@@ -551,6 +566,185 @@ int64_t ti_painn_train_workspace_bytes(ti_handle* h, int64_t B, int32_t kind)
     if (B < 1 || (kind != TI_VLOSS_STANDARD && kind != TI_VLOSS_ONE_SIDED)) return fail(TI_E_ARG, "B < 1 or an unknown loss kind");
     if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
     return (int64_t)workspace_bytes(state_of(h), B, kind == TI_VLOSS_STANDARD ? 2 : 1);
+}
+
+int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_steps_desc* sd, const float* x0, int64_t n0, const float* temp0,
+                         const float* x1, int64_t n1, const float* temp1, const int64_t* idx0, const int64_t* idx1, int64_t B,
+                         double* out_loss, int64_t* out_skipped, int mem)
+{
+    if (int rc = vloss_check(d, nullptr, nullptr, B, mem)) return rc;
+    if (!sd) return fail(TI_E_ARG, "steps desc is NULL");
+    if (sd->n_steps < 1 || sd->n_steps > INT32_MAX) return fail(TI_E_ARG, "n_steps must be in 1..2^31 - 1");
+    if (sd->update != 0 && sd->update != 1) return fail(TI_E_ARG, "unknown update " + std::to_string(sd->update));
+    if (sd->noise < TI_NOISE_GIVEN || sd->noise > TI_NOISE_ALIGNED) return fail(TI_E_ARG, "unknown noise " + std::to_string(sd->noise));
+    if (sd->track_best != 0 && sd->track_best != 1) return fail(TI_E_ARG, "unknown track_best " + std::to_string(sd->track_best));
+    const bool given = sd->noise == TI_NOISE_GIVEN;
+    if (!given && d->kind != TI_VLOSS_ONE_SIDED) return fail(TI_E_ARG, "drawn noise is the one-sided loss's x0: the loss kind must be ONE_SIDED");
+    if (!given && x0) return fail(TI_E_ARG, "x0 is drawn by this noise: x0 must be NULL");
+    if (sd->track_best && !sd->update) return fail(TI_E_ARG, "track_best needs update == 1");
+    const bool ours = h && h->kind == 3;
+    if (ours) if (int rc = workspace_check(state_of(h), B, d->kind == TI_VLOSS_STANDARD ? 2 : 1)) return rc;
+    const int64_t n_steps = sd->n_steps;
+    if ((idx0 == nullptr) != (idx1 == nullptr)) return fail(TI_E_ARG, "idx0 and idx1 must both be given or both be NULL");
+    if (!idx0 && n_steps != 1) return fail(TI_E_ARG, "without indices n_steps must be 1");
+    if (n1 < 1 || (given && n0 < 1) || (!idx0 && (n1 < B || (given && n0 < B)))) return fail(TI_E_ARG, "n0 / n1 do not cover the rows of a step");
+    if ((long long)d->draw + (n_steps - 1) > INT32_MAX) return fail(TI_E_ARG, "draw + n_steps overflows the draw index");
+    if (!x1 || (given && !x0)) return fail(TI_E_ARG, "NULL buffer");
+    if (ours) {
+        const int nc = state_of(h)->ncond;
+        if ((nc >= 1 && !temp1) || (nc == 2 && !temp0)) return fail(TI_E_ARG, "NULL temperature buffer");
+        if (nc == 0 && (temp0 || temp1)) return fail(TI_E_ARG, "the single-T variant takes no temperatures: temp0 and temp1 must be NULL");
+    }
+    const size_t n_idx = idx0 ? (size_t)n_steps * (size_t)B : 0;
+    auto idx_check = [&](const int64_t* i0, const int64_t* i1) -> int {
+        for (size_t k = 0; k < n_idx; ++k) {
+            if (given && (i0[k] < 0 || i0[k] >= n0)) return fail(TI_E_ARG, "idx0[" + std::to_string(k) + "] is outside 0..n0-1");
+            if (i1[k] < 0 || i1[k] >= n1) return fail(TI_E_ARG, "idx1[" + std::to_string(k) + "] is outside 0..n1-1");
+        }
+        return TI_OK;
+    };
+    if (idx0 && mem == TI_MEM_HOST) if (int rc = idx_check(idx0, idx1)) return rc;
+    if (!ours) return fail(TI_E_ARG, "not a painn trainer handle");
+    if (!given && state_of(h)->ncond == 2) return fail(TI_E_UNSUPPORTED, "drawn noise on the ambient variant: its set 0 is data");
+    if (sd->noise == TI_NOISE_ALIGNED && h->d.n_atoms < 3) return fail(TI_E_UNSUPPORTED, "TI_NOISE_ALIGNED needs n_atoms >= 3: the rotation is not unique");
+    return guarded([&]() -> int {
+        set_device(h);
+        PainnTrainState* S = state_of(h);
+        hipStream_t st = h->stream;
+        const bool host = mem == TI_MEM_HOST, update = sd->update == 1;
+        const int A = S->d.n_atoms, halves = d->kind == TI_VLOSS_STANDARD ? 2 : 1;
+        const size_t m = (size_t)3 * A;
+        if (idx0 && !host) {                  // device indices: read once and checked here; nothing has been enqueued yet
+            std::vector<int64_t> i0(n_idx), i1(n_idx);
+            HIP_CHECK(hipMemcpy(i0.data(), idx0, n_idx * sizeof(int64_t), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(i1.data(), idx1, n_idx * sizeof(int64_t), hipMemcpyDeviceToHost));
+            if (int rc = idx_check(i0.data(), i1.data())) return rc;
+        }
+        const Plan p = plan(S, B, halves);
+        ensure_ws(S, p, B, halves);
+        grow(S->log, (size_t)n_steps);
+        grow(S->gx0, (size_t)B * m); grow(S->gx1, (size_t)B * m); grow(S->gcond, (size_t)B * A * std::max(S->ncond, 1));
+        if (!given) grow(S->nxc, (size_t)B * m);
+        if (sd->track_best && !S->best_w.p) {
+            S->best_w.alloc(S->nW); S->best.alloc(2);
+            static const double init[2] = {HUGE_VAL, -1.0};
+            HIP_CHECK(hipMemcpyAsync(S->best.p, init, sizeof(init), hipMemcpyHostToDevice, st));
+        }
+        const float *x0d = given ? stage(h, x0, S->st0, (size_t)n0 * m, host) : nullptr, *x1d = stage(h, x1, S->st1, (size_t)n1 * m, host);
+        const float *t0d = S->ncond == 2 ? stage(h, temp0, S->stt0, (size_t)n0, host) : nullptr;
+        const float *t1d = S->ncond >= 1 ? stage(h, temp1, S->stt1, (size_t)n1, host) : nullptr;
+        const long long *i0d = nullptr, *i1d = nullptr;
+        if (idx0) {
+            static_assert(sizeof(long long) == sizeof(int64_t), "index width");
+            i0d = reinterpret_cast<const long long*>(idx0); i1d = reinterpret_cast<const long long*>(idx1);
+            if (host) {
+                grow(S->idx0, n_idx); grow(S->idx1, n_idx);
+                HIP_CHECK(hipMemcpyAsync(S->idx0.p, idx0, n_idx * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(S->idx1.p, idx1, n_idx * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                i0d = S->idx0.p; i1d = S->idx1.p;
+            }
+        }
+        // the bias table and the log are indexed from the host mirror of the counters, which every stepping call brings up to date at
+        // its end; only a call that failed half-way leaves it behind, and then the counters are read first
+        if (S->mirror_stale) read_counters(h, S);
+        S->mirror_stale = true;
+        std::vector<double> tab;
+        if (update) upload_bias(h, S, tab, n_steps);
+        const double divisor = (double)(B * A);
+        const TrAdam a = adam_params(S, true, divisor, S->log.p);
+        ti_vloss_desc dk = *d;
+        for (int64_t k = 0; k < n_steps; ++k) {
+            dk.draw = d->draw + (int32_t)k;
+            PtGather g{};
+            g.gx0 = S->gx0.p; g.gx1 = S->gx1.p; g.cond = S->gcond.p;
+            g.x0 = x0d; g.x1 = x1d; g.temp0 = t0d; g.temp1 = t1d;
+            g.idx0 = given && i0d ? i0d + k * B : nullptr; g.idx1 = i1d ? i1d + k * B : nullptr;
+            g.n0 = given ? n0 : B; g.n1 = n1; g.B = B; g.A = A; g.ncond = S->ncond;
+            HIP_CHECK(launch_ptsteps_gather(g, st));
+            if (!given) {
+                PtNoise q{dk.seed, dk.traj_offset, dk.draw, S->gx1.p, B, A, sd->noise == TI_NOISE_ALIGNED ? 1 : 0, S->nxc.p, S->gx0.p, nullptr};
+                HIP_CHECK(launch_ptnoise(q, st));
+            }
+            train_forward_backward(h, S, p, &dk, S->gx0.p, S->gx1.p, S->ncond ? S->gcond.p : nullptr, nullptr, nullptr, B, update);
+            if (!update) { HIP_CHECK(launch_ptsteps_log(S->log.p + k, S->red.p + RED_LOSS, divisor, st)); continue; }
+            if (sd->track_best) {
+                const PtBest q{S->best_w.p, S->wd.p, S->nW, S->best.p, S->red.p + RED_LOSS, S->red.p + RED_SUMSQ, divisor, (double)(S->best_steps + k)};
+                HIP_CHECK(launch_ptsteps_best_keep(q, st));
+                HIP_CHECK(launch_ptsteps_best_commit(q, st));
+            }
+            HIP_CHECK(launch_train_adam(a, st));
+            HIP_CHECK(launch_train_finish(a, st));
+        }
+        if (out_loss) HIP_CHECK(hipMemcpyAsync(out_loss, S->log.p, (size_t)n_steps * sizeof(double), hipMemcpyDeviceToHost, st));
+        const long long before = S->n_skipped;
+        read_counters(h, S);                  // the one synchronisation of the call
+        S->mirror_stale = false;
+        if (sd->track_best) { S->best_tracked = true; S->best_steps += n_steps; }
+        if (out_skipped) *out_skipped = S->n_skipped - before;
+        return TI_OK;
+    });
+}
+
+int ti_painn_train_best(ti_handle* h, double* w, double* loss, int64_t* step, int reset)
+{
+    if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
+    PainnTrainState* S = state_of(h);
+    if (!S->best_tracked) return fail(TI_E_ARG, "no step has been tracked since the last reset");
+    return guarded([&]() -> int {
+        set_device(h);
+        double meta[2] = {0.0, 0.0};
+        HIP_CHECK(hipMemcpyAsync(meta, S->best.p, sizeof(meta), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        if (w && meta[1] >= 0.0) {
+            HIP_CHECK(hipMemcpyAsync(w, S->best_w.p, S->nW * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        if (loss) *loss = meta[0];
+        if (step) *step = (int64_t)meta[1];
+        if (reset) {
+            const double init[2] = {HUGE_VAL, -1.0};
+            HIP_CHECK(hipMemcpyAsync(S->best.p, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipStreamSynchronize(h->stream));
+            S->best_tracked = false; S->best_steps = 0;
+        }
+        return TI_OK;
+    });
+}
+
+int ti_painn_train_noise(ti_handle* h, uint64_t seed, int64_t traj_offset, int32_t draw, const float* x1, int64_t B, int32_t noise,
+                         float* out_x0, double* out_rot, int mem)
+{
+    if (noise != TI_NOISE_DRAWN && noise != TI_NOISE_ALIGNED) return fail(TI_E_ARG, "noise must be TI_NOISE_DRAWN or TI_NOISE_ALIGNED");
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (draw < 0) return fail(TI_E_ARG, "draw < 0");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (!out_x0) return fail(TI_E_ARG, "NULL buffer");
+    const bool aligned = noise == TI_NOISE_ALIGNED;
+    if (aligned && !x1) return fail(TI_E_ARG, "TI_NOISE_ALIGNED needs x1");
+    if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
+    if (aligned && h->d.n_atoms < 3) return fail(TI_E_UNSUPPORTED, "TI_NOISE_ALIGNED needs n_atoms >= 3: the rotation is not unique");
+    return guarded([&]() -> int {
+        set_device(h);
+        PainnTrainState* S = state_of(h);
+        hipStream_t st = h->stream;
+        const bool host = mem == TI_MEM_HOST;
+        const size_t n = (size_t)B * 3 * S->d.n_atoms;
+        grow(S->nxc, n);
+        const float* x1d = aligned ? stage(h, x1, S->nx1, n, host) : nullptr;
+        float* od = out_x0; double* rd = aligned ? out_rot : nullptr;
+        if (host) {
+            grow(S->nout, n); od = S->nout.p;
+            if (rd) { grow(S->nrot, (size_t)B * 9); rd = S->nrot.p; }
+        }
+        const PtNoise q{seed, traj_offset, draw, x1d, B, S->d.n_atoms, aligned ? 1 : 0, S->nxc.p, od, rd};
+        HIP_CHECK(launch_ptnoise(q, st));
+        if (host) {
+            HIP_CHECK(hipMemcpyAsync(out_x0, od, n * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (rd) HIP_CHECK(hipMemcpyAsync(out_rot, rd, (size_t)B * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        return TI_OK;
+    });
 }
 
 }  // extern "C"

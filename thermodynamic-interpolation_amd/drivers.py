@@ -52,6 +52,13 @@ The training loop on the GPU (thermo.adw.Trainer).  Keys of the reference: ``hid
 ``batch_size``, ``epochs``, ``a``, ``seed``, ``model_save_path``, ``model_save_name``; of this build, all optional: ``gamma``
 ('brownian'), ``t_distr`` ('uniform'), ``dim`` (1), ``max_grad_norm`` (1, the reference's clip).  Checkpoints are .npz state dicts in
 the reference's keys (fp64), which score_checkpoints reads; torch pickles are not written.
+
+  train_ambient, train_latent <- mdqm9/train_ambient.py:99-176, mdqm9/train_latent.py
+  {name}_{epoch}_weights.npz, {name}_best{epoch}_weights.npz, train_state.npz, log.npz under model_save_path/model_save_name/
+The molecule training loops on resident arrays (thermo.ambient.Trainer.fit / thermo.latent.Trainer.fit: an epoch's steps in one
+device call).  Keys of the reference: ``n_features``, ``score_layers``, ``batch_size``, ``n_epochs``, ``learning_rate``,
+``weight_decay``, ``a``, ``gamma``, ``t_distr``, ``seed``, ``align`` (latent), ``model_save_path``, ``model_save_name``; optional
+``temp_length`` (10) and ``temperatures``.  The datasets stay with the caller: the sets are (x [n, A, 3], T [n]) arrays.
 """
 from __future__ import annotations
 
@@ -710,3 +717,131 @@ def train_adw(config, base, target, resume=False):
         np.savez(state_path, **st, **sched.state(), epochs_done=np.int64(epoch + 1), **{"log_" + k: np.asarray(v) for k, v in log.items()})
         np.savez(os.path.join(out_dir, "log.npz"), **{k: np.asarray(v) for k, v in log.items()})
     return {k: np.asarray(v) for k, v in log.items()}
+
+
+def _molecule_train_settings(config, latent):
+    """The keys of train_ambient / train_latent, checked (ValueError) before any device work"""
+    g = lambda k, d=None: getattr(config, k, d)
+    out = {}
+    for key, lo, hi, default in (("n_features", 1, 1 << 16, None), ("score_layers", 1, 1 << 10, None), ("batch_size", 1, 1 << 16, None),
+                                 ("n_epochs", 1, 1 << 30, None), ("seed", 0, (1 << 63) - 1, 0)):
+        v = g(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"config.{key} must be an integer in {lo}..{hi}, got {v!r}")
+        out[key] = int(v)
+    if out["n_features"] not in (32, 64, 128, 256):
+        raise ValueError(f"config.n_features must be 32, 64, 128 or 256, got {out['n_features']}")
+    for key, positive, default in (("learning_rate", True, None), ("weight_decay", False, 0.0), ("a", True, 1.0)):
+        v = g(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v) or v < 0 or (positive and v <= 0):
+            raise ValueError(f"config.{key} must be a {'finite number > 0' if positive else 'finite number >= 0'}, got {v!r}")
+        out[key] = float(v)
+    gamma, t_distr, align = g("gamma", "brownian"), g("t_distr", "uniform"), g("align", False)
+    if gamma not in _interp.GAMMAS:
+        raise ValueError(f"config.gamma must be one of {_interp.GAMMAS}, got {gamma!r}")
+    if t_distr not in ("uniform", "beta"):
+        raise ValueError(f"config.t_distr must be 'uniform' or 'beta', got {t_distr!r}")
+    if not isinstance(align, (bool, np.bool_)) or (align and not latent):
+        raise ValueError(f"config.align must be a bool (and False for the ambient workflow, which draws no base samples), got {align!r}")
+    for key in ("model_save_path", "model_save_name"):
+        if not isinstance(g(key), str) or not g(key):
+            raise ValueError(f"config.{key} must be a non-empty string")
+    out.update(gamma=gamma, t_distr=t_distr, align=bool(align))
+    return out
+
+
+def _molecule_set(s, name):
+    """(x [n, A, 3] float32, T [n] float32) of a resident set, checked"""
+    if not isinstance(s, (tuple, list)) or len(s) != 2:
+        raise ValueError(f"{name} must be (x [n, A, 3], T [n])")
+    x = np.ascontiguousarray(C.to_numpy(s[0], np.float32))
+    if x.ndim != 3 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError(f"{name}: x must be [n, A, 3], got {x.shape}")
+    T = np.ascontiguousarray(np.broadcast_to(C.to_numpy(s[1], np.float32).reshape(-1), (x.shape[0],)))
+    return x, T
+
+
+def _train_molecule(config, set0, set1, template, resume, latent):
+    s = _molecule_train_settings(config, latent)
+    B = s["batch_size"]
+    x1, T1 = _molecule_set(set1, "set1")
+    x0, T0 = _molecule_set(set0, "set0") if not latent else (None, None)
+    steps = (x1.shape[0] if latent else min(x0.shape[0], x1.shape[0])) // B
+    if steps < 1:
+        raise ValueError(f"batch_size {B} leaves no full training batch ({x1.shape[0] if latent else min(x0.shape[0], x1.shape[0])} molecules)")
+    if s["n_epochs"] * 2 * steps > _TRAIN_DRAW0:
+        raise ValueError(f"n_epochs x 2 steps per epoch = {s['n_epochs'] * 2 * steps} exceeds the {_TRAIN_DRAW0} draw indices of a run")
+    name = config.model_save_name
+    out_dir = os.path.join(config.model_save_path, name)
+    state_path = os.path.join(out_dir, "train_state.npz")
+    temps = getattr(config, "temperatures", _amb.DEFAULT_TEMPS)
+    if latent:
+        b = _lat.cPaiNN(s["n_features"], s["score_layers"], temp_length=getattr(config, "temp_length", 10), temperatures=temps)
+        loss_fn = _losses.OneSidedVelocityLoss(_interp.OneSidedLinearInterpolant(), s["t_distr"])
+        trainer = _lat.Trainer(b, loss_fn, s["learning_rate"], weight_decay=s["weight_decay"], max_grad_norm=1.0)
+    else:
+        b = _amb.cPaiNN(s["n_features"], score_layers=s["score_layers"], temp_length=getattr(config, "temp_length", 10), temperatures=temps)
+        loss_fn = _losses.StandardVelocityLoss(_interp.LinearInterpolant(s["a"], s["gamma"]), s["t_distr"])
+        trainer = _amb.Trainer(b, loss_fn, s["learning_rate"], weight_decay=s["weight_decay"], max_grad_norm=1.0)
+    b.load_state_dict(_adw._syn.make_state_dict(b._spec, seed=s["seed"], dtype=np.float64))
+    sched = _Plateau(s["learning_rate"])
+    log = dict(train_loss=[], last_train_loss=[], best_loss=[], lr=[], skipped=[])
+    first = 0
+    if resume:
+        with np.load(state_path) as f:
+            st = {k: f[k] for k in f.files}
+        trainer.load_state_dict(st)
+        sched.load(st)
+        first = int(st["epochs_done"])
+        log = {k: list(st["log_" + k]) for k in log}
+    os.makedirs(out_dir, exist_ok=True)
+    if latent:
+        sets = (x1, T1 if b.COND_KEYS else None)
+        kw = dict(noise="aligned" if s["align"] else "drawn")
+    else:
+        sets, kw = (x0, T0, x1, T1), {}
+    for epoch in range(first, s["n_epochs"]):
+        perm, draw = [s["seed"], 2, epoch], _TRAIN_DRAW0 + epoch * 2 * steps
+        losses, skipped = trainer.fit(*sets, B, steps, perm, draw=draw, noise_seed=s["seed"], template_batch=template, track_best=True, **kw)
+        last = trainer.evaluate(*sets, B, steps, perm, draw=draw + steps, noise_seed=s["seed"], template_batch=template, **kw)
+        best_sd, best_loss, _ = trainer.best_state_dict(reset=True)
+        log["train_loss"].append(float(np.nansum(losses)) / steps)          # the reference adds the losses it applied and divides by len(loader)
+        log["last_train_loss"].append(float(np.sum(last)) / steps)
+        log["best_loss"].append(float(best_loss))
+        log["skipped"].append(int(skipped))
+        log["lr"].append(trainer.lr)
+        new_lr = sched.step(log["train_loss"][-1])
+        if new_lr != trainer.lr:
+            trainer.set_lr(new_lr)
+        trainer.sync()
+        np.savez(os.path.join(out_dir, f"{name}_{epoch}_weights.npz"), **b.state_dict())
+        np.savez(os.path.join(out_dir, f"{name}_best{epoch}_weights.npz"), **({k: np.asarray(v, np.float32) for k, v in best_sd.items()} if best_sd is not None else b.state_dict()))
+        st = trainer.state_dict()
+        np.savez(state_path, **st, **sched.state(), epochs_done=np.int64(epoch + 1), **{"log_" + k: np.asarray(v) for k, v in log.items()})
+        np.savez(os.path.join(out_dir, "log.npz"), **{k: np.asarray(v) for k, v in log.items()})
+    return {k: np.asarray(v) for k, v in log.items()}
+
+
+def train_ambient(config, set0, set1, template, resume=False):
+    """The loop of mdqm9/train_ambient.py:99-176 on the GPU.  set0 / set1: (x [n, A, 3], T [n]) arrays of one species, as
+    data.load_trajectory gives them per temperature, concatenated by the caller; template: one uniform batch of the species (its graph
+    and atom ids build the device trainer).  The sets stay resident on the device.  Per epoch both sets get a fresh seeded permutation
+    (the reference makes new loaders every epoch); min(n0, n1) // batch_size optimiser steps run in ONE device call
+    (thermo.ambient.Trainer.fit), which also keeps the weights of the step with the smallest loss (epoch_best_model); a second,
+    forward-only pass over the same minibatches gives last_train_loss; ReduceLROnPlateau(0.5, 10) acts on the epoch's mean training
+    loss, as the reference schedules it.  Stated differences: the reference's loaders keep the ragged last batch, this loop drops it
+    (drop_last); permutations, t and z come from numpy's and the library's counter-based streams, not torch's.
+    Writes {name}_{epoch}_weights.npz and {name}_best{epoch}_weights.npz (state dicts in the reference's keys, as score_checkpoints
+    reads them), train_state.npz (optimiser and scheduler state, the epochs done) and log.npz (train_loss, last_train_loss, best_loss,
+    lr, skipped per epoch) under model_save_path/model_save_name; resume=True continues from train_state.npz.  Config: n_features,
+    score_layers, batch_size, n_epochs, learning_rate, weight_decay, a, gamma, t_distr, seed, model_save_path, model_save_name
+    (align must be False).  -> the log as a dict."""
+    return _train_molecule(config, set0, set1, template, resume, latent=False)
+
+
+def train_latent(config, set1, template, resume=False):
+    """The loop of mdqm9/train_latent.py on the GPU: train_ambient with OneSidedVelocityLoss on one resident set, n1 // batch_size
+    steps an epoch.  The base samples x0 of every minibatch (mdqm9_latent.py:84-105: randn_like(x1), centred per molecule, with
+    config.align rotated onto x1) are drawn on the device inside the same call, afresh in every epoch; the forward-only pass draws its
+    own.  A model with one temperature ignores T.  Files, config keys and differences as train_ambient, plus align."""
+    return _train_molecule(config, None, set1, template, resume, latent=True)

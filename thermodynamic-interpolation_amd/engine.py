@@ -1213,6 +1213,92 @@ class PainnTrainer(_Engine):
                                                   _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return mean.value, int(skipped.value)
 
+    def steps(self, x0, x1, temp0=None, temp1=None, idx0=None, idx1=None, *, batch=None, update=True, noise="given", track_best=False,
+              kind="standard", gamma="brownian", a=1.0, center="batch", t_distr="uniform", seed=0, traj_offset=0, draw=0):
+        """ti_painn_train_steps -> (loss [n_steps] float64 numpy, NaN where skipped; the number of skipped steps).  x0 [n0, A, 3] and
+        x1 [n1, A, 3] are the resident sets, temp0 [n0] and temp1 [n1] their temperatures (ambient: both, multi-T latent: temp1,
+        single-T: neither); idx0, idx1 [n_steps, B] int64 (numpy, or CUDA tensors when the data are): step k takes rows idx0[k] of set 0
+        and idx1[k] of set 1 and is drawn with draw + k.  Without indices: one step on rows 0 .. batch - 1.  update=False: forward
+        only, the mean loss of every minibatch at the current weights.  noise="drawn" | "aligned" (one-sided loss, x0 None): the
+        minibatch's x0 is drawn on the device as `noise` does.  track_best: keep the weights of the step with the smallest loss
+        (`best`).  One host synchronisation, at the end."""
+        if noise not in _lib.PAINN_NOISES:
+            raise ValueError(f"noise must be one of {sorted(_lib.PAINN_NOISES)}, got {noise!r}")
+        given = noise == "given"
+        if given == (x0 is None):
+            raise ValueError("noise='given' takes x0; a drawn noise takes x0=None")
+        n1 = int(x1.shape[0])
+        n0 = int(x0.shape[0]) if given else n1
+        if (idx0 is None) != (idx1 is None) and given:
+            raise ValueError("idx0 and idx1 must both be given or both be None")
+        if idx0 is None and not given:
+            idx0 = idx1                                  # the values of idx0 are not read without a set 0
+        if idx1 is None:
+            n, B = 1, int(batch if batch is not None else min(n0, n1))
+        else:
+            if tuple(idx0.shape) != tuple(idx1.shape) or len(idx1.shape) != 2:
+                raise ValueError("idx0 and idx1 must be [n_steps, B] and equally shaped")
+            n, B = int(idx1.shape[0]), int(idx1.shape[1])
+        (x0p, x1p, t0p, t1p), dev, keep = self._ptrs((x0, (n0, self.A, 3), False, "x0"), (x1, (n1, self.A, 3), False, "x1"),
+                                                     (temp0, (n0,), False, "temp0"), (temp1, (n1,), False, "temp1"))
+        ip, ikeep = [None, None], []
+        for k, idx in enumerate((idx0, idx1)):
+            if idx is None:
+                continue
+            if hasattr(idx, "data_ptr"):
+                if not dev or str(idx.dtype) != "torch.int64" or not idx.is_contiguous() or not idx.is_cuda:
+                    raise TypeError("index tensors must be contiguous int64 CUDA tensors, with the data on the GPU too")
+                ip[k] = C.c_void_p(idx.data_ptr()); ikeep.append(idx)
+            else:
+                if dev:
+                    raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
+                arr = np.ascontiguousarray(idx, np.int64)
+                ip[k] = C.c_void_p(arr.ctypes.data); ikeep.append(arr)
+        desc = self._vloss_desc(kind, gamma, a, center, None, t_distr, seed, traj_offset, draw, 0)
+        sd = _lib.PainnStepsDesc(n, int(bool(update)), _lib.PAINN_NOISES[noise], int(bool(track_best)))
+        loss = np.empty(n, np.float64)
+        skipped = C.c_int64(0)
+        _lib.check(_lib.lib().ti_painn_train_steps(self.h, C.byref(desc), C.byref(sd), x0p, n0, t0p, x1p, n1, t1p, ip[0], ip[1], B,
+                                                   loss.ctypes.data_as(C.POINTER(C.c_double)), C.byref(skipped),
+                                                   _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return loss, int(skipped.value)
+
+    def noise(self, x1=None, *, B=None, aligned=False, seed=0, traj_offset=0, draw=0, return_rot=False):
+        """ti_painn_train_noise: the latent base samples of B molecules -> x0 [B, A, 3] float32 (where x1 lives; numpy without x1), and
+        with return_rot the rotations [B, 3, 3] float64.  Drawn as N(seed, traj_offset + b, draw, 3 a + c), centred per molecule;
+        aligned=True rotates each onto its x1 by the proper rotation that minimises sum_a |x1_a - R x0_a|^2."""
+        if x1 is None and (aligned or B is None):
+            raise ValueError("aligned noise needs x1; without x1 pass B")
+        B = int(x1.shape[0]) if x1 is not None else int(B)
+        (x1p,), dev, keep = self._ptrs((x1, (B, self.A, 3), False, "x1"))
+        rot = None
+        if dev:
+            import torch
+            out = torch.empty((B, self.A, 3), dtype=torch.float32, device=x1.device)
+            op = C.c_void_p(out.data_ptr())
+            if return_rot and aligned:
+                rot = torch.empty((B, 3, 3), dtype=torch.float64, device=x1.device)
+            rp = C.c_void_p(rot.data_ptr()) if rot is not None else None
+        else:
+            out = np.empty((B, self.A, 3), np.float32)
+            op = C.c_void_p(out.ctypes.data)
+            if return_rot and aligned:
+                rot = np.empty((B, 3, 3), np.float64)
+            rp = C.c_void_p(rot.ctypes.data) if rot is not None else None
+        _lib.check(_lib.lib().ti_painn_train_noise(self.h, int(seed), int(traj_offset), int(draw), x1p if aligned else None, B,
+                                                   _lib.PAINN_NOISES["aligned" if aligned else "drawn"], op, rp,
+                                                   _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return (out, rot) if return_rot else out
+
+    def best(self, reset=False):
+        """ti_painn_train_best -> dict(w [n_weights] float64 | None, loss, step): the master weights BEFORE the update of the step
+        with the smallest loss tracked since the last reset (steps(track_best=True)), that loss, and the step's 0-based count since
+        the reset (w None, step -1 where every tracked step was skipped).  reset=True then forgets them."""
+        w = np.empty(self.n_weights, np.float64)
+        loss, step = C.c_double(0.0), C.c_int64(0)
+        _lib.check(_lib.lib().ti_painn_train_best(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(loss), C.byref(step), int(bool(reset))))
+        return dict(w=w if step.value >= 0 else None, loss=loss.value, step=int(step.value))
+
     def state(self):
         """dict(w, m, v [n_weights] float64, n_applied, n_skipped): master weights, Adam moments, counters"""
         w, m, v = (np.empty(self.n_weights, np.float64) for _ in range(3))

@@ -557,6 +557,64 @@ class MoleculeTrainerBase:
         x0, x1, cond, tv, zv = self._args(batch, x0, x1, conds, t, z)
         return self.engine.grad(x0, x1, cond, center=center or "batch", t=tv, z=zv, seed=seed, draw=draw, traj_offset=traj_offset, **self._kw)["mean"]
 
+    def _resident(self, x0, x1, temps0, temps1, template_batch):
+        """The resident sets of fit / evaluate as the device call takes them: x [n, A, 3] float32 and one temperature per molecule,
+        numpy or CUDA tensors (all in one memory space).  template_batch builds the device trainer when no step has done so yet."""
+        if self.engine is None:
+            if template_batch is None:
+                raise ValueError("the trainer has seen no batch yet: pass template_batch, one uniform batch of the species")
+            self._engine_for(template_batch)
+        A = self.engine.A
+
+        def arr(v, shape, what):
+            if v is None:
+                return None
+            if C.is_cuda(v):
+                import torch
+                return v.detach().to(torch.float32).reshape(shape).contiguous()
+            return np.ascontiguousarray(C.to_numpy(v, np.float32).reshape(shape))
+
+        x0, x1 = arr(x0, (-1, A, 3), "x0"), arr(x1, (-1, A, 3), "x1")
+        t0 = None if x0 is None else arr(temps0, (x0.shape[0],), "temps0")
+        return x0, x1, t0, arr(temps1, (x1.shape[0],), "temps1")
+
+    def _fit(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, update, track_best):
+        from .adw import minibatch_indices
+        x0, x1, t0, t1 = self._resident(x0, x1, temps0, temps1, template_batch)
+        rng = np.random.default_rng(seed)
+        i0 = minibatch_indices(x0.shape[0], batch_size, n_steps, rng) if x0 is not None else None
+        i1 = minibatch_indices(x1.shape[0], batch_size, n_steps, rng)
+        if C.is_cuda(x1):
+            import torch
+            i0, i1 = (None if i is None else torch.from_numpy(i).to(x1.device) for i in (i0, i1))
+        return self.engine.steps(x0, x1, t0, t1, i0, i1, update=update, noise=noise, track_best=track_best, center=center or "batch",
+                                 seed=seed if noise_seed is None else noise_seed, draw=draw, **self._kw)
+
+    def fit(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, *, draw=0, noise_seed=None, center=None, template_batch=None,
+            noise="given", track_best=True):
+        """n_steps optimiser steps in one device call on resident sets (engine.PainnTrainer.steps): minibatches from permutations drawn
+        on the host with `seed` (thermo.adw.minibatch_indices, set 0 first, independently for the two sets), step k with the (t, z) of
+        draw + k under noise_seed (default: seed).  x0 [n0, A, 3], x1 [n1, A, 3]; temps0 [n0], temps1 [n1] or None as the model takes
+        them.  noise="drawn" | "aligned" with x0=None: the base samples of every minibatch are drawn on the device.  track_best keeps the
+        weights of the step with the smallest loss (best_state_dict).  -> (mean loss of every step [n_steps], NaN where skipped; the
+        number of skipped steps)"""
+        return self._fit(x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, True, track_best)
+
+    def evaluate(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, *, draw=0, noise_seed=None, center=None, template_batch=None,
+                 noise="given"):
+        """fit without the update: the forward pass and the loss of the same minibatches at the current weights; nothing changes.
+        -> the mean loss of every minibatch [n_steps]"""
+        return self._fit(x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, False, False)[0]
+
+    def best_state_dict(self, reset=False):
+        """(state dict in the reference's keys, loss, step) of the step with the smallest loss since the last reset: the weights that
+        produced that loss, as `copy.deepcopy(model) if loss < epoch_best_loss` keeps them.  (None, inf, -1) where every step was skipped."""
+        if self.engine is None:
+            raise RuntimeError("the trainer has seen no batch yet: there are no best weights")
+        r = self.engine.best(reset=reset)
+        sd = None if r["w"] is None else _W.unflatten(r["w"], self.b._spec)
+        return sd, r["loss"], r["step"]
+
     def set_lr(self, lr):
         self.lr = float(lr)
         self._opt["lr"] = self.lr

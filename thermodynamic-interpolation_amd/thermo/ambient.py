@@ -46,3 +46,12 @@ class Trainer(MoleculeTrainerBase):
     def loss(self, batch0, batch1, *, t=None, z=None, seed=0, draw=0, traj_offset=0, center=None) -> float:
         """The mean loss at the current weights by the trainer's own forward pass; nothing is updated"""
         return self._loss(batch0, batch0.x, batch1.x, (batch0.T, batch1.T), t, z, seed, draw, traj_offset, center)
+
+    def fit(self, x0, temps0, x1, temps1, batch_size, n_steps, seed, **kw):
+        """n_steps optimiser steps in one device call on the resident sets (x0 [n0, A, 3] at temps0 [n0], x1 [n1, A, 3] at temps1 [n1]):
+        MoleculeTrainerBase.fit.  -> (mean loss of every step, the number of skipped steps)"""
+        return MoleculeTrainerBase.fit(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, **kw)
+
+    def evaluate(self, x0, temps0, x1, temps1, batch_size, n_steps, seed, **kw):
+        """The loss of the same minibatches at the current weights, nothing updated -> [n_steps]"""
+        return MoleculeTrainerBase.evaluate(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, **kw)

@@ -50,3 +50,19 @@ class Trainer(MoleculeTrainerBase):
     def loss(self, batch, *, t=None, z=None, seed=0, draw=0, traj_offset=0, center=None) -> float:
         """The mean loss at the current weights by the trainer's own forward pass; nothing is updated"""
         return self._loss(batch, batch.x0, batch.x1, self._conds(batch), t, z, seed, draw, traj_offset, center)
+
+    @staticmethod
+    def _noise(noise):
+        return (None, noise) if isinstance(noise, str) else (noise, "given")
+
+    def fit(self, x1, temps1, batch_size, n_steps, seed, *, noise="drawn", **kw):
+        """n_steps optimiser steps in one device call on the resident set x1 [n, A, 3] (temps1 [n], None for a single-temperature
+        model).  noise: "drawn" or "aligned" (the base samples of mdqm9_latent.py:84-105 drawn on the device for every minibatch, the
+        latter rotated onto x1), or a given x0 [n0, A, 3].  -> (mean loss of every step, the number of skipped steps)"""
+        x0, noise = self._noise(noise)
+        return MoleculeTrainerBase.fit(self, x0, x1, None, temps1, batch_size, n_steps, seed, noise=noise, **kw)
+
+    def evaluate(self, x1, temps1, batch_size, n_steps, seed, *, noise="drawn", **kw):
+        """The loss of the same minibatches at the current weights, nothing updated -> [n_steps]"""
+        x0, noise = self._noise(noise)
+        return MoleculeTrainerBase.evaluate(self, x0, x1, None, temps1, batch_size, n_steps, seed, noise=noise, **kw)
