@@ -558,6 +558,62 @@ int ti_obs_ff_set(ti_handle* h, const ti_ff_desc* desc, const int32_t* bond_idx,
  * TI_E_ARG, nothing written: a NULL or adw handle, no force field set, B < 0, a NULL x or out_e with B > 0, an unknown mem, a
  * non-finite to_nm, T_b <= 0 or not finite (found on the device; the message names the first such index). */
 int ti_obs_ff_energy(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_e, double* out_terms, int mem);
+/* The analytic forces of the same force field: out_f[b,a,c] = -dE_b / d(p[b,a,c]) in kJ / (mol nm) at p = (double)x * to_nm, and with
+ * out_e != NULL the energy of the same pass ((bond + angle) + torsion) + pair; with T both are divided by R T_b.  x [B,A,3] fp32,
+ * T [B] fp32 or NULL, out_f [B,A,3] fp64, out_e [B] fp64 or NULL: [host|device] by mem.  Per term (u, v, b1, b2, b3, m = b1 x b2, n = b2 x b3 as above):
+ *   bond     on j: -k (r - r0) (p_j - p_i) / r; on i its negative
+ *   angle    through d theta / d cos = -1 / sin theta, sin theta = sqrt((1 - cos)(1 + cos)) of the clamped cosine:
+ *            on i: k (theta - theta0) / (sin theta |u|) (v / |v| - cos u / |u|), on k the same with u and v exchanged, on j minus both
+ *   torsion  k n sin(n phi - phase) d phi / dx with d phi / dx1 = -|b2| m / |m|^2, d phi / dx4 = |b2| n / |n|^2,
+ *            d phi / dx2 = -(1 + b1.b2 / |b2|^2) d phi / dx1 + (b3.b2 / |b2|^2) d phi / dx4,
+ *            d phi / dx3 = -(1 + b3.b2 / |b2|^2) d phi / dx4 + (b1.b2 / |b2|^2) d phi / dx1 (no division by sin phi)
+ *   pair     on i: (24 eps s (2 s - 1) / r^2 + coulomb qq / r^3) (p_i - p_j), s = (sigma / r)^6, under the energy's rules for which
+ *            part exists and which rows are evaluated; on j its negative
+ * r = 0, a collinear angle, collinear b1, b2 or b2, b3 give a non-finite force for that molecule only; a NaN coordinate gives NaN for
+ * its molecule only.  One wave per molecule, no atomics, no contraction: an atom's component is the running sum of its bonded
+ * contributions in the order bonds, angles, torsions, ascending term index, plus its pair force, which is the sum over partners
+ * 0 .. h-1 plus the sum over partners h .. A-1 (h = (A + 1) / 2), each ascending.  A molecule's outputs are a function of its
+ * coordinates, to_nm, T_b and the tables only, and a call repeats bit for bit.  out_e is not promised to equal ti_obs_ff_energy bit
+ * for bit.  Refusals: those of ti_obs_ff_energy in its order, nothing written. */
+int ti_obs_ff_forces(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_f, double* out_e, int mem);
+/* The masses [A] (host memory, amu) of the species of the force field in force, for ti_obs_ff_langevin.  TI_E_ARG, the masses in
+ * force left alone: no force field, a mass that is not finite and > 0.  m == NULL clears them; ti_obs_ff_set clears them too. */
+int ti_obs_ff_set_masses(ti_handle* h, const double* m);
+/* Langevin dynamics of B replicas of the species under the force field in force, OpenMM's "middle" discretisation; units nm, ps, amu,
+ * kJ/mol.  Step s of the call has the global index step_offset + s:
+ *   v += dt f(x) / m;  x += (dt / 2) v;  v = a v + sqrt((1 - a^2) R T_b / m) xi;  x += (dt / 2) v,   a = exp(-friction dt)
+ * xi[a,c] = the Philox normal (seed, id_b, step_offset + s, 3a + c) of TI_SCHEME_EM as the velocity loss draws it (oracle.normal bit
+ * for bit; the step index enters through its low 32 bits), promoted to fp64; id_b = ids[b] or traj_offset + b.  friction == 0:
+ * a = 1, no draw, plain leapfrog.  draw_velocities: vel is not read; v[a,c] = sqrt(R T_b / m_a) times the normal (seed, id_b,
+ * step_offset, 3A + 3a + c).  One wave per replica; positions, velocities and forces stay in LDS as fp64 for a whole launch; the host
+ * cuts the call into launches of at most steps_per_launch steps (0: TI_MD_DEFAULT_STEPS_PER_LAUNCH), the state passes through global
+ * memory exactly and the noise is keyed by the global step, so the cut does not change a bit, and neither does a call chained from
+ * two with step_offset advanced.  The forces are those of ti_obs_ff_forces (one body).
+ * Frames: n_frames = n_steps / stride (0 with stride == 0); after every stride-th step of the call out_frames[b,k] = (x - mean of x
+ * over the atoms, an fp64 sum in atom order) / to_nm rounded once to fp32, out_epot[b,k] the potential energy there in kJ/mol,
+ * out_ekin[b,k] = sum m v^2 / 2 of the velocities there.  The state itself is never centred.
+ * pos, vel [B,A,3] fp64 in/out, T [B] fp32, ids [B] int64 or NULL, out_frames [B,n_frames,A,3] fp32, out_epot, out_ekin
+ * [B,n_frames] fp64 (each may be NULL): [host|device] by mem.  A replica whose positions or velocities turn non-finite stops
+ * advancing; the call then returns TI_E_NAN naming the first such replica and the launch, pos and vel are not written (frames in
+ * device memory may be partly written).  One wait for the verdict; a host call waits once more for its results.
+ * TI_E_ARG before any device work: a NULL or adw handle, unknown mem, NULL d, pos or T, NULL vel without draw_velocities, dt <= 0 or
+ * not finite, friction < 0 or not finite, a negative n_steps, stride, step_offset or steps_per_launch, stride > 0 with every output
+ * NULL, B < 1, to_nm 0 or not finite, no force field, no masses.  TI_E_UNSUPPORTED: ti_painn_set_molecules in force.  TI_E_ARG with
+ * nothing written: T_b <= 0 or not finite (found on the device as ti_obs_ff_energy finds it). */
+#define TI_MD_DEFAULT_STEPS_PER_LAUNCH 1024
+typedef struct {
+    double dt;               /* ps, > 0 */
+    double friction;         /* 1/ps, >= 0; 0 = no thermostat (NVE) */
+    int64_t n_steps;         /* >= 0 */
+    int64_t stride;          /* a frame after every stride-th step; 0 = no frames */
+    int64_t step_offset;     /* first step's index, for chained calls */
+    int64_t traj_offset;     /* replica b has id traj_offset + b unless ids is given */
+    uint64_t seed;
+    int32_t draw_velocities; /* 1: vel is drawn from N(0, R T_b / m_a) before the first step and not read */
+    int32_t steps_per_launch;/* 0 = default; > 0: the host cuts the call into launches of at most this many steps */
+} ti_md_desc;
+int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* vel, const float* T, const int64_t* ids, int64_t B,
+                       double to_nm, float* out_frames, double* out_epot, double* out_ekin, int mem);
 /* The log-weights of the TI map from reduced energies: out_logw[b] = -(u1[b] - u0[b] + neg_dlogp[b]) (the reference's weight is
  * exp(-(E1 - E0 + neg_dlogp)), ess.py:8-10), formed in fp64 as ((u1 - u0) + neg_dlogp) and rounded once to the fp32 that
  * ti_obs_weights, ti_obs_hist, ti_obs_bootstrap and ti_obs_rff_gram take.  u0, u1 [B] fp64, neg_dlogp [B] fp32, out_logw [B] fp32:

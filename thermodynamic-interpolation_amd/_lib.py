@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "ti_painn_trainer_create", "ti_painn_train_grad", "ti_painn_train_apply", "ti_painn_train_step", "ti_painn_train_get_state",
     "ti_painn_train_set_state", "ti_painn_train_set_lr", "ti_painn_train_workspace_bytes",
     "ti_painn_train_steps", "ti_painn_train_best", "ti_painn_train_noise",
+    "ti_obs_ff_forces", "ti_obs_ff_set_masses", "ti_obs_ff_langevin",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -73,6 +74,8 @@ def eigh_wide_launch_max(n):
 # ti_obs_ff_set: the caps of the four tables (TI_FF_MAX_*), R in kJ / (mol K) (TI_FF_GAS_CONSTANT), OpenMM's ONE_4PI_EPS0 in kJ nm / (mol e^2)
 FF_MAX_BONDS, FF_MAX_ANGLES, FF_MAX_TORSIONS, FF_MAX_PAIRS = 64, 128, 512, 300
 FF_GAS_CONSTANT, FF_COULOMB = 0.00831446261815324, 138.935456
+# ti_obs_ff_langevin: the most steps of one launch when the descriptor leaves it open (TI_MD_DEFAULT_STEPS_PER_LAUNCH)
+MD_DEFAULT_STEPS_PER_LAUNCH = 1024
 # ti_obs_zmat / ti_obs_zmat_xyz: the range of A; ti_obs_hist_cols: the most columns of a call
 ZMAT_MIN_ATOMS, ZMAT_MAX_ATOMS, HIST_COLS_MAX = 2, 32, 128
 # ti_*_vloss: loss kinds (TI_VLOSS_*), gamma kinds (TI_GAMMA_*), centring (TI_CENTER_*), time distributions (TI_TDIST_*), the fourth
@@ -122,6 +125,11 @@ class GedmdDesc(C.Structure):
 
 class FfDesc(C.Structure):
     _fields_ = [("n_bonds", C.c_int32), ("n_angles", C.c_int32), ("n_torsions", C.c_int32), ("n_pairs", C.c_int32), ("coulomb", C.c_double)]
+
+
+class MdDesc(C.Structure):
+    _fields_ = [("dt", C.c_double), ("friction", C.c_double), ("n_steps", C.c_int64), ("stride", C.c_int64), ("step_offset", C.c_int64),
+                ("traj_offset", C.c_int64), ("seed", C.c_uint64), ("draw_velocities", C.c_int32), ("steps_per_launch", C.c_int32)]
 
 
 class VlossDesc(C.Structure):
@@ -241,6 +249,9 @@ def lib():
     L.ti_obs_ff_set.argtypes = [vp, C.POINTER(FfDesc), ip, dp, ip, dp, ip, dp, dp]
     L.ti_obs_ff_energy.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
     L.ti_obs_ti_logw.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int]
+    L.ti_obs_ff_forces.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
+    L.ti_obs_ff_set_masses.argtypes = [vp, dp]
+    L.ti_obs_ff_langevin.argtypes = [vp, C.POINTER(MdDesc), vp, vp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
     L.ti_obs_zmat.argtypes = [vp, ip, ip, vp, C.c_int64, vp, C.c_int]
     L.ti_obs_zmat_xyz.argtypes = [vp, ip, ip, vp, C.c_int64, vp, vp, vp, C.c_int]
     L.ti_obs_hist_cols.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int]

@@ -1,0 +1,159 @@
+// api_ff_md.hip -- C ABI of the force-field forces and of Langevin dynamics with them (include/ti_hip.h ti_obs_ff_forces,
+// ti_obs_ff_set_masses, ti_obs_ff_langevin): checks, staging and the launch cut.  Kernels: obs_ff_md_kernels.hip.
+#include "ti_handle.hpp"
+#include "ff_device.hpp"
+
+#include <cmath>
+
+using namespace ti;
+
+namespace ti {
+
+std::vector<int32_t> ff_build_incidence(const std::vector<int32_t>& words, const int* n, int A)
+{
+    const int chunks = ff_chunks(n[0]) + ff_chunks(n[1]) + ff_chunks(n[2]);
+    std::vector<uint16_t> off((size_t)chunks * A + 1, 0);
+    std::vector<uint8_t> entries;
+    int q = 0, first = 0;
+    for (int t = 0; t < 3; first += n[t], ++t)
+        for (int base = 0; base < n[t]; base += FF_CHUNK, ++q)
+            for (int a = 0; a < A; ++a) {
+                off[(size_t)q * A + a] = (uint16_t)entries.size();
+                for (int l = 0; l < FF_CHUNK && base + l < n[t]; ++l)              // ascending term, then slot
+                    for (int s = 0; s < 2 + t; ++s)
+                        if (ff_atom(words[first + base + l], s) == a) entries.push_back((uint8_t)(l << 2 | s));
+            }
+    off[(size_t)chunks * A] = (uint16_t)entries.size();
+    std::vector<int32_t> out((size_t)FF_INC_OFF_WORDS + (entries.size() + 3) / 4, 0);
+    std::memcpy(out.data(), off.data(), off.size() * sizeof(uint16_t));
+    if (!entries.empty()) std::memcpy(out.data() + FF_INC_OFF_WORDS, entries.data(), entries.size());
+    return out;
+}
+
+}  // namespace ti
+
+static FfTablesDev ff_tables(const ti_handle* h)
+{
+    FfTablesDev t{};
+    t.A = h->d.n_atoms; t.nb = h->ff_n[0]; t.na = h->ff_n[1]; t.nt = h->ff_n[2]; t.np = h->ff_n[3];
+    t.coulomb = h->ff_coulomb; t.idx = h->ff_idx.p; t.par = h->ff_par.p; t.inc = h->ff_inc.p; t.inc_words = (int)h->ff_inc.n;
+    return t;
+}
+
+int ti_obs_ff_forces(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_f, double* out_e, int mem)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 0 || (B > 0 && (!x || !out_f))) return fail(TI_E_ARG, "NULL buffer");
+    if (!std::isfinite(to_nm)) return fail(TI_E_ARG, "to_nm must be finite");
+    if (!h->ff_on) return fail(TI_E_ARG, "no force field set (ti_obs_ff_set)");
+    if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
+    if (B == 0) return TI_OK;
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const int A = h->d.n_atoms;
+        Staged sg(h, mem);
+        const float* xd = sg.in(x, h->obs_x, (size_t)B * 3 * A);
+        const float* Td = T ? sg.in(T, h->ff_T, (size_t)B) : nullptr;
+        if (Td) {                                      // refused before anything is written, as ti_obs_ff_energy does it
+            grow(h->obs_red, 4 + 259);
+            double bad = 0.0;
+            HIP_CHECK(launch_obs_ff_bad_temperature(h->obs_red.p, Td, B, st));
+            HIP_CHECK(hipMemcpyAsync(&bad, h->obs_red.p, sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            if (bad < (double)B) return fail(TI_E_ARG, "T must be finite and > 0: index " + std::to_string((long long)bad));
+        }
+        FfForceParams p{};
+        p.t = ff_tables(h);
+        p.x = xd; p.T = Td; p.B = B; p.to_nm = to_nm;
+        p.f = sg.out(out_f, h->ff_f, (size_t)B * 3 * A);
+        p.e = out_e ? sg.out(out_e, h->ff_e, (size_t)B) : nullptr;
+        HIP_CHECK(launch_obs_ff_forces(p, st));
+        sg.finish();
+        return TI_OK;
+    });
+}
+
+int ti_obs_ff_set_masses(ti_handle* h, const double* m)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (!m) { h->ff_mass_on = false; return TI_OK; }
+    if (!h->ff_on) return fail(TI_E_ARG, "no force field set (ti_obs_ff_set): the masses go with it");
+    const int A = h->d.n_atoms;
+    for (int a = 0; a < A; ++a)
+        if (!(std::isfinite(m[a]) && m[a] > 0.0)) return fail(TI_E_ARG, "mass " + std::to_string(a) + " must be finite and > 0");
+    return guarded([&]() -> int {
+        set_device(h);
+        h->ff_mass_on = false;
+        h->ff_mass.upload(std::vector<double>(m, m + A));
+        h->ff_mass_on = true;
+        return TI_OK;
+    });
+}
+
+int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* vel, const float* T, const int64_t* ids, int64_t B,
+                       double to_nm, float* out_frames, double* out_epot, double* out_ekin, int mem)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (!d || !pos || !T) return fail(TI_E_ARG, "NULL desc, pos or T");
+    if (!vel && !d->draw_velocities) return fail(TI_E_ARG, "vel is NULL and draw_velocities is off");
+    if (!(std::isfinite(d->dt) && d->dt > 0.0)) return fail(TI_E_ARG, "dt must be finite and > 0");
+    if (!(std::isfinite(d->friction) && d->friction >= 0.0)) return fail(TI_E_ARG, "friction must be finite and >= 0");
+    if (d->n_steps < 0 || d->stride < 0 || d->step_offset < 0 || d->steps_per_launch < 0) return fail(TI_E_ARG, "a negative count");
+    if (d->stride > 0 && !out_frames && !out_epot && !out_ekin) return fail(TI_E_ARG, "stride > 0 needs out_frames, out_epot or out_ekin");
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!(std::isfinite(to_nm) && to_nm != 0.0)) return fail(TI_E_ARG, "to_nm must be finite and not 0");
+    if (!h->ff_on) return fail(TI_E_ARG, "no force field set (ti_obs_ff_set)");
+    if (!h->ff_mass_on) return fail(TI_E_ARG, "no masses set (ti_obs_ff_set_masses)");
+    if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const int A = h->d.n_atoms;
+        const size_t n_state = (size_t)B * 3 * A;
+        const long long n_frames = d->stride > 0 ? d->n_steps / d->stride : 0;
+        const hipMemcpyKind in_kind = mem == TI_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        const hipMemcpyKind out_kind = mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        Staged sg(h, mem);
+        const float* Td = sg.in(T, h->ff_T, (size_t)B);
+        const int64_t* idd = ids ? sg.in(ids, h->md_ids, (size_t)B) : nullptr;
+        // the state is advanced in a working copy: pos / vel change only when the whole call succeeds
+        grow(h->md_pos, n_state); grow(h->md_vel, n_state); grow(h->md_flag, (size_t)B + 2); grow(h->obs_red, 4 + 259);
+        HIP_CHECK(hipMemcpyAsync(h->md_pos.p, pos, n_state * sizeof(double), in_kind, st));
+        if (!d->draw_velocities) HIP_CHECK(hipMemcpyAsync(h->md_vel.p, vel, n_state * sizeof(double), in_kind, st));
+        HIP_CHECK(hipMemsetAsync(h->md_flag.p, 0, (size_t)B * sizeof(int), st));
+        HIP_CHECK(launch_obs_ff_bad_temperature(h->obs_red.p, Td, B, st));       // the launches below return at once on a bad T
+        MdParams p{};
+        p.t = ff_tables(h);
+        p.pos = h->md_pos.p; p.vel = h->md_vel.p; p.T = Td; p.ids = reinterpret_cast<const long long*>(idd); p.mass = h->ff_mass.p;
+        p.B = B; p.traj_offset = d->traj_offset; p.dt = d->dt; p.a = d->friction > 0.0 ? std::exp(-d->friction * d->dt) : 1.0; p.to_nm = to_nm;
+        p.stride = d->stride; p.n_frames = n_frames; p.seed = d->seed; p.bad_T = h->obs_red.p; p.flag = h->md_flag.p;
+        p.frames = out_frames && n_frames ? sg.out(out_frames, h->md_frames, (size_t)B * n_frames * 3 * A) : nullptr;
+        p.epot = out_epot && n_frames ? sg.out(out_epot, h->md_epot, (size_t)B * n_frames) : nullptr;
+        p.ekin = out_ekin && n_frames ? sg.out(out_ekin, h->md_ekin, (size_t)B * n_frames) : nullptr;
+        const long long per = d->steps_per_launch > 0 ? d->steps_per_launch : TI_MD_DEFAULT_STEPS_PER_LAUNCH;
+        long long done = 0;
+        for (int launch = 0; launch == 0 || done < d->n_steps; ++launch) {      // n_steps = 0: one launch (it may draw the velocities)
+            p.n_steps = std::min<long long>(per, d->n_steps - done);
+            p.steps_before = done; p.step0 = d->step_offset + done; p.launch = launch; p.draw = launch == 0 && d->draw_velocities;
+            HIP_CHECK(launch_obs_ff_langevin(p, st));
+            done += p.n_steps;
+        }
+        std::vector<int> flag((size_t)B);
+        double bad = 0.0;
+        HIP_CHECK(hipMemcpyAsync(&bad, h->obs_red.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(flag.data(), h->md_flag.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));           // the one wait of the call that does not move results
+        if (bad < (double)B) return fail(TI_E_ARG, "T must be finite and > 0: index " + std::to_string((long long)bad));
+        for (int64_t b = 0; b < B; ++b)
+            if (flag[b])
+                return fail(TI_E_NAN, "replica " + std::to_string((long long)b) + ": the state turned non-finite in launch " + std::to_string(flag[b] - 1) +
+                                          " (pos and vel are left as they were)");
+        HIP_CHECK(hipMemcpyAsync(pos, h->md_pos.p, n_state * sizeof(double), out_kind, st));
+        if (vel) HIP_CHECK(hipMemcpyAsync(vel, h->md_vel.p, n_state * sizeof(double), out_kind, st));
+        sg.finish();
+        return TI_OK;
+    });
+}

@@ -606,7 +606,7 @@ int ti_obs_ff_set(ti_handle* h, const ti_ff_desc* desc, const int32_t* bond_idx,
                   const double* angle_par, const int32_t* torsion_idx, const double* torsion_par, const double* pair_par)
 {
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
-    if (!desc) { h->ff_on = false; return TI_OK; }
+    if (!desc) { h->ff_on = false; h->ff_mass_on = false; return TI_OK; }
     if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
     const int A = h->d.n_atoms;
     const int n[4] = {desc->n_bonds, desc->n_angles, desc->n_torsions, desc->n_pairs};
@@ -655,11 +655,14 @@ int ti_obs_ff_set(ti_handle* h, const ti_ff_desc* desc, const int32_t* bond_idx,
             words.push_back(i | j << 5 | ((q[0] != 0.0 || q[2] != 0.0) ? FF_LIVE : 0));
             pars.insert(pars.end(), q, q + 3);
         }
+    const std::vector<int32_t> inc = ff_build_incidence(words, n, A);      // of the bonded terms, for ti_obs_ff_forces / ti_obs_ff_langevin
     return guarded([&]() -> int {
         set_device(h);
         h->ff_on = false;
+        h->ff_mass_on = false;                                 // the masses go with the force field (ti_obs_ff_set_masses)
         h->ff_idx.upload(words);
         h->ff_par.upload(pars);
+        h->ff_inc.upload(inc);
         std::copy(n, n + 4, h->ff_n);
         h->ff_coulomb = desc->coulomb;
         h->ff_on = true;

@@ -172,6 +172,11 @@ struct ti_handle {
     // energies, term sums, reduced energies and log-weights (ti_obs_ff_energy, ti_obs_ti_logw)
     bool ff_on = false; int ff_n[4] = {0, 0, 0, 0}; double ff_coulomb = 0.0;
     DevBuf<int32_t> ff_idx; DevBuf<double> ff_par, ff_e, ff_terms, ff_u0, ff_u1; DevBuf<float> ff_T;
+    // forces and Langevin dynamics (ti_obs_ff_forces, ti_obs_ff_set_masses, ti_obs_ff_langevin): the incidence list of the bonded
+    // terms, built with the force field (ff_device.hpp); the masses (ff_mass_on: in force; cleared with the force field); staging of a
+    // host call's forces; the working copy of the state, the replica ids, frames, frame energies and stop flags of a Langevin call
+    DevBuf<int32_t> ff_inc; bool ff_mass_on = false;
+    DevBuf<double> ff_mass, ff_f, md_pos, md_vel, md_epot, md_ekin; DevBuf<float> md_frames; DevBuf<int64_t> md_ids; DevBuf<int> md_flag;
     // Z-matrix coordinates and column histograms (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols): the topology of the call (order,
     // ref), staging of a host call's z, log-determinants, validity and keep masks, the column ranges (lo [K], hi [K])
     DevBuf<int32_t> zm_topo; DevBuf<float> zm_z; DevBuf<double> zm_logdet, hc_range; DevBuf<uint8_t> zm_valid, hc_keep;
@@ -278,6 +283,9 @@ struct JvpRun {            // one tangent pass riding on a drift evaluation
 };
 
 inline int obs_floats_per_traj(const ti_handle* h) { return h->kind == 0 ? 3 * h->d.n_atoms : h->a_dim; }
+
+// ---- api_ff_md.hip: the packed incidence list of the bonded term words (bonds, angles, torsions of lengths n[0..2]; ff_device.hpp)
+std::vector<int32_t> ff_build_incidence(const std::vector<int32_t>& words, const int* n, int A);
 
 // ---- painn_pack.hip
 void pack_chunk16(std::vector<float>& dst, const float* W, int ld, int n_rows, int row0, int col0, int NBK);

@@ -424,6 +424,38 @@ hipError_t launch_obs_ff_bad_temperature(double* out, const float* T, long long 
 // logw[b] = (float)-((u1[b] - u0[b]) + neg_dlogp[b]) in fp64; u0 / neg_dlogp NULL: 0
 hipError_t launch_obs_ti_logw(float* logw, const double* u0, const double* u1, const float* neg_dlogp, long long B, hipStream_t st);
 
+// ---- force-field forces and Langevin dynamics (obs_ff_md_kernels.hip, ff_device.hpp; include/ti_hip.h ti_obs_ff_forces,
+// ti_obs_ff_langevin).  The tables are those of FfParams plus the incidence list of the bonded terms (ff_device.hpp).
+struct FfTablesDev {
+    int A, nb, na, nt, np;
+    double coulomb;
+    const int32_t* idx; const double* par;  // as in FfParams
+    const int32_t* inc; int inc_words;      // the packed incidence list
+};
+struct FfForceParams {
+    FfTablesDev t;
+    const float* x; const float* T;         // [B][A][3]; [B] kelvin or NULL
+    long long B; double to_nm;
+    double* f; double* e;                   // [B][A][3]; [B] or NULL
+};
+hipError_t launch_obs_ff_forces(const FfForceParams& p, hipStream_t st);
+struct MdParams {
+    FfTablesDev t;
+    double *pos, *vel;                      // [B][A][3] fp64 nm, nm/ps: the state, read at the start and written at the end of a launch
+    const float* T; const long long* ids;   // [B] kelvin; [B] or NULL (replica b: traj_offset + b)
+    const double* mass;                     // [A] amu
+    long long B, traj_offset;
+    double dt, a, to_nm;                    // a = exp(-friction dt) (1: no thermostat, no draw)
+    long long n_steps, steps_before, stride, n_frames;      // this launch's steps; the call's steps before it; frames of the call
+    long long step0;                        // global index of this launch's first step
+    unsigned long long seed;
+    int draw, launch;                       // draw: velocities drawn before the first step (first launch only)
+    float* frames; double *epot, *ekin;     // [B][n_frames][A][3]; [B][n_frames]; each may be NULL
+    int* flag;                              // [B]: 0, or 1 + the launch in which the replica's state turned non-finite
+    const double* bad_T;                    // launch_obs_ff_bad_temperature's output: below B, the launch does nothing
+};
+hipError_t launch_obs_ff_langevin(const MdParams& p, hipStream_t st);
+
 // ---- Z-matrix coordinates and the histograms of all columns (obs_zmat_kernels.hip; include/ti_hip.h ti_obs_zmat, ti_obs_zmat_xyz,
 // ti_obs_hist_cols).  topo: order [A] (sorted atom s is the caller's atom order[s]) followed by ref [A][3] in sorted numbering, both
 // validated on the host (zmat_check_topology): every slot that is read names an earlier sorted atom.

@@ -59,6 +59,14 @@ The molecule training loops on resident arrays (thermo.ambient.Trainer.fit / the
 device call).  Keys of the reference: ``n_features``, ``score_layers``, ``batch_size``, ``n_epochs``, ``learning_rate``,
 ``weight_decay``, ``a``, ``gamma``, ``t_distr``, ``seed``, ``align`` (latent), ``model_save_path``, ``model_save_name``; optional
 ``temp_length`` (10) and ``temperatures``.  The datasets stay with the caller: the sets are (x [n, A, 3], T [n]) arrays.
+
+  generate_md   (no counterpart in the reference: its trajectory files come from its authors)
+  {traj_path}/{split}/{traj_filename} per split, {traj_path}/md_log.npz
+Langevin dynamics under a force field on the GPU (md.LangevinSampler) into the multi-temperature layout data.load_trajectory reads.
+Keys: ``forcefield`` (the XML of an OpenMM System), ``x0`` (.npy [A, 3] or [n, A, 3] starting geometries in model units, used in
+turn), ``scale`` or ``to_nm`` (model units per nm as the energy key has it, or nm per model unit), ``temperatures`` (each in
+data.TEMPERATURES), ``n_replicas`` (per temperature), ``dt`` (ps), ``friction`` (1/ps), ``n_equil``, ``n_frames``, ``stride``,
+``seed``, ``splits`` ({name: fraction of the replicas}), ``traj_path``, ``traj_filename``.
 """
 from __future__ import annotations
 
@@ -845,3 +853,86 @@ def train_latent(config, set1, template, resume=False):
     config.align rotated onto x1) are drawn on the device inside the same call, afresh in every epoch; the forward-only pass draws its
     own.  A model with one temperature ignores T.  Files, config keys and differences as train_ambient, plus align."""
     return _train_molecule(config, None, set1, template, resume, latent=True)
+
+
+MD_KEYS = ("forcefield", "x0", "temperatures", "n_replicas", "dt", "friction", "n_equil", "n_frames", "stride", "seed", "splits",
+           "traj_path", "traj_filename")
+
+
+def _md_settings(config):
+    """The keys of generate_md, checked before anything is read or run"""
+    from . import data as _data
+    missing = [k for k in MD_KEYS if getattr(config, k, None) is None]
+    if missing:
+        raise ValueError(f"generate_md needs the keys {missing}")
+    scale, to_nm = getattr(config, "scale", None), getattr(config, "to_nm", None)
+    if (scale is None) == (to_nm is None):
+        raise ValueError("generate_md needs exactly one of 'scale' (model units per nm) and 'to_nm' (nm per model unit)")
+    v = float(scale if to_nm is None else to_nm)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError("'scale' / 'to_nm' must be finite and > 0")
+    temps = [int(t) for t in config.temperatures]
+    if not temps or len(set(temps)) != len(temps) or any(t not in _data.TEMPERATURES for t in temps):
+        raise ValueError(f"'temperatures' must be distinct members of {list(_data.TEMPERATURES)}, got {list(config.temperatures)}")
+    n_rep, n_frames, stride, n_equil = int(config.n_replicas), int(config.n_frames), int(config.stride), int(config.n_equil)
+    if n_rep < 1 or n_frames < 1 or stride < 1 or n_equil < 0:
+        raise ValueError("'n_replicas', 'n_frames' and 'stride' must be >= 1 and 'n_equil' >= 0")
+    splits = dict(config.splits)
+    frac = np.array([float(f) for f in splits.values()])
+    if not len(frac) or (frac <= 0).any() or frac.sum() > 1.0 + 1e-12:
+        raise ValueError("'splits' must map split names to positive fractions of the replicas that sum to at most 1")
+    counts = np.floor(frac * n_rep + 1e-9).astype(int)          # whole replicas: the splits are independent trajectories
+    if (counts < 1).any():
+        raise ValueError(f"'splits' {splits} leave a split without a replica at n_replicas = {n_rep}")
+    return (1.0 / v if to_nm is None else v), temps, n_rep, n_frames, stride, n_equil, dict(zip(splits, counts.tolist()))
+
+
+def _md_engine(b, A):
+    """The engine that runs the dynamics: `b` itself when it is one (a PainnEngine of the species), else the model's engine for the
+    fully connected template of A atoms -- the force field needs the species size only"""
+    if hasattr(b, "langevin"):
+        return b
+    from . import synthetic as _syn
+    src, dst, et = _syn.fully_connected_template(A)
+    return b.engine_for(A, src, dst, et, np.arange(A))
+
+
+def generate_md(config, b):
+    """One batch of Langevin replicas -- n_replicas at every temperature, all advanced together -- written as the training sets of
+    train_ambient / train_latent: ``{traj_path}/{split}/{traj_filename}`` float32 [8, n_replicas_in_split * n_frames, A, 3], row
+    data.TEMPERATURES.index(T) holding that temperature's frames replica-major (a split takes whole replicas), the rows of
+    temperatures that were not simulated NaN; and ``{traj_path}/md_log.npz`` with the per-frame energies, the settings and the seed.
+    The frames are centred and in the model's length unit before `scale` (the file load_trajectory(..., scale=False) returns as
+    it is).  Returns {split: path}."""
+    from . import data as _data
+    from . import forcefield as _ff
+    from . import md as _md
+    to_nm, temps, n_rep, n_frames, stride, n_equil, counts = _md_settings(config)
+    ff = _ff.ForceField.from_openmm_xml(os.fspath(config.forcefield))
+    A = ff.n_atoms
+    x0 = np.load(os.fspath(config.x0))
+    x0 = x0[None] if x0.ndim == 2 else x0
+    if x0.ndim != 3 or x0.shape[1:] != (A, 3) or not np.isfinite(x0).all():
+        raise ValueError(f"'x0' must hold finite [{A}, 3] or [n, {A}, 3] geometries, got {x0.shape}")
+    B = len(temps) * n_rep                                       # replica r of temperature k is row k * n_replicas + r, its id too
+    T = np.repeat(np.asarray(temps, np.float32), n_rep)
+    start = x0[np.arange(B) % len(x0)]
+    sampler = _md.LangevinSampler(_md_engine(b, A), ff, to_nm, float(config.dt), float(config.friction), int(config.seed))
+    sampler.start(start, T)
+    sampler.equilibrate(n_equil)
+    frames, epot, ekin = (C.to_numpy(a) for a in sampler.sample(n_frames, stride))
+    frames = frames.reshape(len(temps), n_rep, n_frames, A, 3)
+    paths, first = {}, 0
+    for split, n in counts.items():
+        out = np.full((len(_data.TEMPERATURES), n * n_frames, A, 3), np.nan, np.float32)
+        for k, temp in enumerate(temps):
+            out[_data.TEMPERATURES.index(temp)] = frames[k, first:first + n].reshape(n * n_frames, A, 3)
+        os.makedirs(os.path.join(config.traj_path, split), exist_ok=True)
+        paths[split] = os.path.join(config.traj_path, split, config.traj_filename)
+        np.save(paths[split], out)
+        first += n
+    np.savez(os.path.join(config.traj_path, "md_log.npz"), epot=epot.reshape(len(temps), n_rep, n_frames),
+             ekin=ekin.reshape(len(temps), n_rep, n_frames), temperatures=np.asarray(temps), n_replicas=n_rep, dt=float(config.dt),
+             friction=float(config.friction), n_equil=n_equil, n_frames=n_frames, stride=stride, seed=int(config.seed), to_nm=to_nm,
+             split_names=np.array(list(counts)), split_replicas=np.array(list(counts.values())))
+    return paths

@@ -660,8 +660,10 @@ class PainnEngine(_Engine):
 
     def set_forcefield(self, ff):
         """ti_obs_ff_set: copy a forcefield.ForceField of this engine's species into the handle (None clears it).  The library checks
-        index ranges, repeated atoms, the caps, signs and finiteness; the dense pair table is built here (ForceField.pair_table)."""
+        index ranges, repeated atoms, the caps, signs and finiteness; the dense pair table is built here (ForceField.pair_table).  The
+        masses are uploaded when the force field has them (ti_obs_ff_set_masses)."""
         L = _lib.lib()
+        self._ff_set, self._ff_constraints, self._ff_masses = False, False, False
         if ff is None:
             _lib.check(L.ti_obs_ff_set(self.h, None, None, None, None, None, None, None, None))
             return
@@ -671,6 +673,12 @@ class PainnEngine(_Engine):
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None
         _lib.check(L.ti_obs_ff_set(self.h, C.byref(desc), ip(ff.bond_idx), dp(ff.bond_par), ip(ff.angle_idx), dp(ff.angle_par),
                                    ip(ff.torsion_idx), dp(ff.torsion_par), dp(pairs)))
+        self._ff_set, self._ff_constraints = True, bool(getattr(ff, "has_constraints", False))
+        m = getattr(ff, "masses", None)                           # for langevin only, which refuses a missing or zero mass itself
+        if m is not None and len(m) == self.A and np.isfinite(m).all() and (np.asarray(m) > 0).all():
+            m = np.ascontiguousarray(m, np.float64)
+            _lib.check(L.ti_obs_ff_set_masses(self.h, dp(m)))
+            self._ff_masses = True
 
     def ff_energy(self, x, to_nm=1.0, T=None, terms=False):
         """ti_obs_ff_energy: E [B] float64 of x [B,A,3] float32 at positions x * to_nm (nm), in kJ/mol -- or, with T [B] float32 kelvin
@@ -693,6 +701,85 @@ class PainnEngine(_Engine):
         (xp, Tp), xdev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), (T, (B,), False, "T"))
         _lib.check(_lib.lib().ti_obs_ff_energy(self.h, xp, B, float(to_nm), Tp, ep, tp2, _lib.MEM_DEVICE if xdev else _lib.MEM_HOST))
         return (e, tm) if terms else e
+
+    def ff_forces(self, x, to_nm=1.0, T=None, energy=False):
+        """ti_obs_ff_forces: F [B,A,3] float64 = -dE / d(position in nm) of x [B,A,3] float32 at positions x * to_nm, in kJ / (mol nm)
+        -- or, with T [B] float32 kelvin (a scalar: every molecule's), divided by R T.  energy=True: (F, E [B]) with the energy of the
+        same pass.  numpy in, numpy out; a CUDA tensor in, CUDA float64 tensors out."""
+        B = self._check_x(x)
+        dev = hasattr(x, "data_ptr") and x.is_cuda
+        if T is not None and (np.shape(T) if not hasattr(T, "shape") else tuple(T.shape)) == ():
+            T = x.new_full((B,), float(T)) if dev else np.full(B, float(T), np.float32)
+        elif T is not None and not dev and not hasattr(T, "data_ptr"):
+            T = np.ascontiguousarray(T, np.float32)
+        if dev:
+            import torch
+            f = torch.empty((B, self.A, 3), dtype=torch.float64, device=x.device)
+            e = torch.empty(B, dtype=torch.float64, device=x.device) if energy else None
+            fp, ep = C.c_void_p(f.data_ptr()), (C.c_void_p(e.data_ptr()) if energy else None)
+        else:
+            f, e = np.empty((B, self.A, 3), np.float64), (np.empty(B, np.float64) if energy else None)
+            fp, ep = C.c_void_p(f.ctypes.data), (C.c_void_p(e.ctypes.data) if energy else None)
+        (xp, Tp), xdev, keep = self._ptrs((x, (B, self.A, 3), False, "x"), (T, (B,), False, "T"))
+        _lib.check(_lib.lib().ti_obs_ff_forces(self.h, xp, B, float(to_nm), Tp, fp, ep, _lib.MEM_DEVICE if xdev else _lib.MEM_HOST))
+        return (f, e) if energy else f
+
+    def langevin(self, pos, vel, T, dt, friction, n_steps, stride=0, step_offset=0, traj_offset=0, seed=0, ids=None, to_nm=1.0,
+                 draw_velocities=False, steps_per_launch=0, frames=True, energies=True):
+        """ti_obs_ff_langevin: n_steps of OpenMM's Langevin "middle" scheme for the replicas pos [B,A,3] float64 (nm), vel [B,A,3]
+        float64 (nm/ps; None with draw_velocities) at the temperatures T [B] kelvin (a scalar: every replica's) under the force field
+        and masses set with set_forcefield; dt in ps, friction in 1/ps (0: NVE).  Returns (pos, vel, frames, epot, ekin): the new state
+        (the inputs are not changed), frames [B, n_steps // stride, A, 3] float32 in model units nm / to_nm, centred, and the potential
+        and kinetic energies [B, n_steps // stride] float64 at the frames (None where frames / energies is off or stride is 0).  numpy
+        in, numpy out; CUDA tensors in, CUDA tensors out.  Raises ValueError for a force field with constraints (they are not
+        integrated) and for missing masses."""
+        if not getattr(self, "_ff_set", False):
+            raise ValueError("langevin needs a force field (set_forcefield)")
+        if self._ff_constraints:
+            raise ValueError("the force field lists constraints, which are not integrated: export the System without them (rigidWater=False, constraints=None)")
+        if not self._ff_masses:
+            raise ValueError("langevin needs a force field with masses, every one > 0 (ForceField.masses)")
+        if pos is None or len(pos.shape) != 3 or tuple(pos.shape[1:]) != (self.A, 3):
+            raise ValueError(f"pos must be [B,{self.A},3]")
+        B = int(pos.shape[0])
+        dev = hasattr(pos, "data_ptr") and pos.is_cuda
+        if vel is None and not draw_velocities:
+            raise ValueError("vel is None and draw_velocities is off")
+        n_frames = int(n_steps) // int(stride) if stride and stride > 0 else 0
+        if dev:
+            import torch
+            if pos.device.index != self.device:
+                raise ValueError(f"pos lives on {pos.device} but this engine was created on device {self.device}")
+            t64 = lambda a: a.detach().to(dtype=torch.float64, copy=True).contiguous()
+            p = t64(pos)
+            v = torch.empty_like(p) if draw_velocities else t64(vel)
+            Td = torch.full((B,), float(T), dtype=torch.float32, device=pos.device) if not hasattr(T, "shape") or tuple(T.shape) == () \
+                else torch.as_tensor(T, dtype=torch.float32, device=pos.device).contiguous()
+            idd = None if ids is None else torch.as_tensor(ids, dtype=torch.int64, device=pos.device).contiguous()
+            new = lambda shape, dt_: torch.empty(shape, dtype=dt_, device=pos.device)
+            fr = new((B, n_frames, self.A, 3), torch.float32) if frames and n_frames else None
+            ep = new((B, n_frames), torch.float64) if energies and n_frames else None
+            ek = new((B, n_frames), torch.float64) if energies and n_frames else None
+            ptr = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)      # behind the copies and fills above
+        else:
+            p = np.array(pos, np.float64, order="C")
+            v = np.empty_like(p) if draw_velocities else np.array(vel, np.float64, order="C")
+            Td = np.full(B, float(T), np.float32) if np.shape(T) == () else np.ascontiguousarray(T, np.float32)
+            idd = None if ids is None else np.ascontiguousarray(ids, np.int64)
+            fr = np.empty((B, n_frames, self.A, 3), np.float32) if frames and n_frames else None
+            ep = np.empty((B, n_frames), np.float64) if energies and n_frames else None
+            ek = np.empty((B, n_frames), np.float64) if energies and n_frames else None
+            ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        if tuple(v.shape) != (B, self.A, 3) or tuple(Td.shape) != (B,) or (idd is not None and tuple(idd.shape) != (B,)):
+            raise ValueError(f"vel must be [{B},{self.A},3], T and ids [{B}]")
+        if fr is None and ep is None:                             # no frame is asked for or none falls into the call
+            stride = 0
+        desc = _lib.MdDesc(float(dt), float(friction), int(n_steps), int(stride), int(step_offset), int(traj_offset), int(seed),
+                           int(bool(draw_velocities)), int(steps_per_launch))
+        _lib.check(_lib.lib().ti_obs_ff_langevin(self.h, C.byref(desc), ptr(p), ptr(v), ptr(Td), ptr(idd), B, float(to_nm), ptr(fr), ptr(ep),
+                                                 ptr(ek), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return p, v, fr, ep, ek
 
     def _zmat_topology(self, zm):
         if zm.A != self.A:

@@ -46,13 +46,18 @@ class ForceField:
     check (ti_obs_ff_set): they depend on the engine."""
 
     def __init__(self, bond_idx=None, bond_par=None, angle_idx=None, angle_par=None, torsion_idx=None, torsion_par=None,
-                 particles=None, exceptions=None, coulomb=COULOMB):
+                 particles=None, exceptions=None, coulomb=COULOMB, masses=None, has_constraints=False):
         self.bond_idx, self.bond_par = _table(bond_idx, 2, np.int32, "bond_idx"), _table(bond_par, 2, np.float64, "bond_par")
         self.angle_idx, self.angle_par = _table(angle_idx, 3, np.int32, "angle_idx"), _table(angle_par, 2, np.float64, "angle_par")
         self.torsion_idx, self.torsion_par = _table(torsion_idx, 4, np.int32, "torsion_idx"), _table(torsion_par, 3, np.float64, "torsion_par")
         self.particles = _table(particles, 3, np.float64, "particles")
         self.exceptions = _table(exceptions, 5, np.float64, "exceptions")
         self.coulomb = float(coulomb)
+        # for dynamics only (PainnEngine.langevin): [A] float64 amu or None, and whether the source listed constraints (not integrated)
+        self.masses = None if masses is None else np.ascontiguousarray(masses, np.float64).reshape(-1)
+        self.has_constraints = bool(has_constraints)
+        if self.masses is not None and len(self.masses) != len(self.particles):
+            raise ValueError(f"masses must be [{len(self.particles)}], got {self.masses.shape}")
         for name in ("bond", "angle", "torsion"):
             if len(getattr(self, name + "_idx")) != len(getattr(self, name + "_par")):
                 raise ValueError(f"{name}_idx and {name}_par differ in length")
@@ -81,7 +86,8 @@ class ForceField:
     @classmethod
     def from_openmm_xml(cls, path_or_text, coulomb=COULOMB):
         """The force field of a serialized OpenMM System (XmlSerializer.serialize(system)); a path or the XML text.  Reads
-        HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce and NonbondedForce, ignores CMMotionRemover, and raises
+        HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce and NonbondedForce and the particle masses (``masses``), ignores
+        CMMotionRemover and -- for the energies -- <Constraints>, whose presence is recorded (``has_constraints``), and raises
         ValueError -- naming the offender -- for anything that would change the energy and is not evaluated: another force type, a
         NonbondedForce method other than 0 (NoCutoff), global parameters or parameter offsets."""
         text = path_or_text
@@ -94,7 +100,11 @@ class ForceField:
         forces = root.find("Forces")
         if root.tag != "System" or forces is None:
             raise ValueError("not a serialized OpenMM System (no <System><Forces>)")
-        n_particles = len(root.findall("./Particles/Particle"))
+        system_particles = root.findall("./Particles/Particle")
+        n_particles = len(system_particles)
+        masses = [float(p.attrib["mass"]) for p in system_particles] if all("mass" in p.attrib for p in system_particles) else None
+        constraints = root.find("Constraints")
+        has_constraints = constraints is not None and len(list(constraints)) > 0
         tab = {k: [] for k in ("bi", "bp", "ai", "ap", "ti", "tp", "pa", "ex")}
         seen_nb = False
         num = lambda el, k: float(el.attrib[k])
@@ -135,4 +145,5 @@ class ForceField:
             raise ValueError("the system has no NonbondedForce")
         if n_particles and len(tab["pa"]) != n_particles:
             raise ValueError(f"the system has {n_particles} particles, its NonbondedForce {len(tab['pa'])}")
-        return cls(tab["bi"], tab["bp"], tab["ai"], tab["ap"], tab["ti"], tab["tp"], tab["pa"], tab["ex"], coulomb=coulomb)
+        return cls(tab["bi"], tab["bp"], tab["ai"], tab["ap"], tab["ti"], tab["tp"], tab["pa"], tab["ex"], coulomb=coulomb,
+                   masses=masses if n_particles else None, has_constraints=has_constraints)

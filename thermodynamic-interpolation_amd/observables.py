@@ -464,6 +464,13 @@ def ff_energy(engine, x, to_nm=1.0, T=None, terms=False):
     return engine.ff_energy(x, to_nm=to_nm, T=T, terms=terms)
 
 
+def ff_forces(engine, x, to_nm=1.0, T=None, energy=False):
+    """F [B,A,3] float64 = -dE / d(position in nm) of x [B,A,3] float32 under the force field set on `engine`, evaluated on the GPU in
+    fp64 at the positions x * to_nm: kJ / (mol nm), or with T [B] kelvin divided by R T.  energy=True: (F, E [B]) with the energy of the
+    same pass.  Lives where x lives."""
+    return engine.ff_forces(x, to_nm=to_nm, T=T, energy=energy)
+
+
 def ti_logw(u0, u1, neg_dlogp, engine=None):
     """logw [B] float32 = -(u1 - u0 + neg_dlogp) from reduced energies u0, u1 [B] float64 (u0 None: 0, the calc_phis_bg form) and
     neg_dlogp [B] float32 (None: 0), formed in fp64 on the GPU and rounded once: what ``importance_weights``, ``weighted_histogram``,
