@@ -2,25 +2,21 @@
 // staging, and the launch sequence of a training step -- interpolate (vloss_kernels.hip), forward, loss rows (the velocity loss's own
 // reduce kernel), backward, combine, clip + Adam (adw_train_kernels.hip).  A step is enqueued on the handle's stream without a host
 // synchronisation: whether it is skipped is decided by the optimiser kernel from the two batch-wide sums in device memory.
-#include "ti_handle.hpp"
-#include "adw_train.hpp"
+// The optimiser shell -- master state, counters, clip + Adam, the state entry points, index handling -- is train_optim.hpp's, shared
+// with api_painn_train.hip.
+#include "train_optim.hpp"
 
 namespace {
 
-constexpr int RED_LOSS = 0, RED_SUMSQ = 1;      // slots of AdwTrainState::red
-
 struct TrLayer { int K, N; size_t w_off, b_off; bool act; };      // Linear(K -> N) at its canonical offsets, SiLU behind it or not
 
-struct AdwTrainState {
-    ti_adw_train_desc td{};
+struct AdwTrainState : Optim {                  // is_bias: 1 at the bias entries, whose gradients launch_train_bias writes in fp64
     int H = 0, L = 0, dim = 1;
-    size_t nW = 0, n_embed = 0;
+    size_t n_embed = 0;
     std::vector<TrLayer> emb, net;
-    long long n_applied = 0, n_skipped = 0;     // host mirror of ctr, read back at the end of every call that steps
-    DevBuf<double> w, m, v, grad, sq, red, part64, loss, log, bias;
-    DevBuf<long long> ctr, idx0, idx1;
-    DevBuf<float> w32, part;
-    DevBuf<unsigned char> is_bias;              // [nW] 1 at the bias entries: their gradients are written in fp64 by launch_train_bias
+    DevBuf<double> loss;
+    DevBuf<int64_t> idx0, idx1;
+    DevBuf<float> part;
     // staged sets of a host call, the gathered minibatch, times, noise, states; activations (y, silu') of every hidden layer, the
     // inputs of both MLPs, the embedding, the drift; the two gradient buffers the backward pass alternates between, the input
     // gradient of net.0, the output gradient of beta_embed
@@ -32,17 +28,6 @@ AdwTrainState* state_of(ti_handle* h) { return static_cast<AdwTrainState*>(h->tr
 size_t adw_weight_count(int H, int nl, int dim)
 {
     return (size_t)H * 3 + H + (size_t)H * H + H + H + 1 + (size_t)H * (dim + 2) + H + (size_t)(nl - 1) * ((size_t)H * H + H) + (size_t)dim * H + dim;
-}
-
-int train_desc_check(const ti_adw_train_desc* t)
-{
-    if (!t) return fail(TI_E_ARG, "train desc is NULL");
-    if (!(std::isfinite(t->lr) && t->lr > 0.0)) return fail(TI_E_ARG, "lr must be finite and > 0");
-    if (!(t->beta1 >= 0.0 && t->beta1 < 1.0) || !(t->beta2 >= 0.0 && t->beta2 < 1.0)) return fail(TI_E_ARG, "beta1 and beta2 must be in [0, 1)");
-    if (!(std::isfinite(t->eps) && t->eps > 0.0)) return fail(TI_E_ARG, "eps must be finite and > 0");
-    if (!(std::isfinite(t->weight_decay) && t->weight_decay >= 0.0)) return fail(TI_E_ARG, "weight_decay must be finite and >= 0");
-    if (std::isnan(t->max_grad_norm)) return fail(TI_E_ARG, "max_grad_norm is NaN");
-    return TI_OK;
 }
 
 // the checks of ti_adw_train_grad / ti_adw_train_steps that need no handle, in the order include/ti_hip.h lists them
@@ -157,52 +142,6 @@ void train_forward_backward(ti_handle* h, AdwTrainState* S, const ti_vloss_desc*
     HIP_CHECK(launch_vloss_colsum(S->red.p + RED_SUMSQ, S->part64.p, S->sq.p, (long long)S->nW, 1, st));
 }
 
-// the two bias terms of steps base + 1 .. base + n, computed here and indexed on the device by the steps applied so far
-void upload_bias(ti_handle* h, AdwTrainState* S, long long n, std::vector<double>& tab)
-{
-    tab.resize(2 * (size_t)n);
-    for (long long i = 0; i < n; ++i) {
-        const double k = (double)(S->n_applied + 1 + i);
-        tab[2 * i] = S->td.lr / (1.0 - std::pow(S->td.beta1, k));
-        tab[2 * i + 1] = std::sqrt(1.0 - std::pow(S->td.beta2, k));
-    }
-    grow(S->bias, tab.size());
-    HIP_CHECK(hipMemcpyAsync(S->bias.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-}
-
-TrAdam adam_params(AdwTrainState* S, bool with_loss, long long B, double* log)
-{
-    TrAdam a{};
-    a.w = S->w.p; a.m = S->m.p; a.v = S->v.p; a.w32 = S->w32.p; a.grad = S->grad.p; a.n = S->nW;
-    a.sumsq = S->red.p + RED_SUMSQ; a.loss_sum = with_loss ? S->red.p + RED_LOSS : nullptr; a.B = (double)B;
-    a.beta1 = S->td.beta1; a.beta2 = S->td.beta2; a.eps = S->td.eps; a.weight_decay = S->td.weight_decay; a.max_norm = S->td.max_grad_norm;
-    a.bias = S->bias.p; a.ctr = S->ctr.p; a.base = S->n_applied; a.base_skip = S->n_skipped; a.log = log;
-    return a;
-}
-
-void read_counters(ti_handle* h, AdwTrainState* S)
-{
-    long long c[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(c, S->ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    S->n_applied = c[0]; S->n_skipped = c[1];
-}
-
-void write_counters(ti_handle* h, AdwTrainState* S)
-{
-    const long long c[2] = {S->n_applied, S->n_skipped};
-    HIP_CHECK(hipMemcpyAsync(S->ctr.p, c, sizeof(c), hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-}
-
-const float* stage(ti_handle* h, const float* p, DevBuf<float>& buf, size_t n, bool host)
-{
-    if (!p || !host) return p;
-    grow(buf, n);
-    HIP_CHECK(hipMemcpyAsync(buf.p, p, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    return buf.p;
-}
-
 }  // namespace
 
 extern "C" {
@@ -221,11 +160,13 @@ ti_handle* ti_adw_trainer_create(const ti_adw_desc* d, int32_t dim, const double
         if (d->precision != TI_PREC_F32) return fail(TI_E_UNSUPPORTED, "the trainer takes TI_PREC_F32 only");
         const size_t need = adw_weight_count(H, nl, dim);
         if (n_weights != need) return fail(TI_E_ARG, "weight count mismatch: expected " + std::to_string(need) + ", got " + std::to_string(n_weights));
-        if (int rc2 = train_desc_check(td)) return rc2;
+        if (!td) return fail(TI_E_ARG, "train desc is NULL");
+        const AdamDesc ad{td->lr, td->beta1, td->beta2, td->eps, td->weight_decay, td->max_grad_norm};
+        if (int rc2 = adam_desc_check(ad)) return rc2;
         std::unique_ptr<ti_handle> h(new_handle(2, device));
         h->ad = *d; h->NB = H / 32; h->a_dim = dim;
         auto S = std::make_shared<AdwTrainState>();
-        S->td = *td; S->H = H; S->L = nl; S->dim = dim; S->nW = need;
+        S->H = H; S->L = nl; S->dim = dim;
         size_t o = 0;
         auto take = [&](std::vector<TrLayer>& v, int K, int N, bool act) {
             v.push_back(TrLayer{K, N, o, o + (size_t)N * K, act});
@@ -236,18 +177,10 @@ ti_handle* ti_adw_trainer_create(const ti_adw_desc* d, int32_t dim, const double
         take(S->net, dim + 2, H, true);
         for (int l = 1; l < nl; ++l) take(S->net, H, H, true);
         take(S->net, H, dim, false);
-        S->w.alloc(need); S->m.alloc(need); S->v.alloc(need); S->grad.alloc(need); S->sq.alloc(need); S->w32.alloc(need);
-        S->red.alloc(2); S->ctr.alloc(2);
         std::vector<unsigned char> mask(need, 0);
         for (const auto* v : {&S->emb, &S->net})
             for (const TrLayer& ly : *v) std::fill(mask.begin() + ly.b_off, mask.begin() + ly.b_off + ly.N, (unsigned char)1);
-        S->is_bias.upload(mask);
-        HIP_CHECK(hipMemcpyAsync(S->w.p, weights, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemsetAsync(S->m.p, 0, need * sizeof(double), h->stream));
-        HIP_CHECK(hipMemsetAsync(S->v.p, 0, need * sizeof(double), h->stream));
-        HIP_CHECK(hipMemsetAsync(S->ctr.p, 0, 2 * sizeof(long long), h->stream));
-        HIP_CHECK(launch_train_refresh(S->w32.p, S->w.p, need, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        S->setup(ad, weights, mask, 2, 0, h->stream);
         h->train = S;
         out = h.release();
         return TI_OK;
@@ -265,22 +198,14 @@ int ti_adw_train_grad(ti_handle* h, const ti_vloss_desc* d, const float* x0, con
     return guarded([&]() -> int {
         set_device(h);
         AdwTrainState* S = state_of(h);
-        hipStream_t st = h->stream;
-        const bool host = mem == TI_MEM_HOST;
+        Staged sg(h, mem);
         const size_t n = (size_t)B * S->dim;
         ensure_train_ws(S, B, d->kind == TI_VLOSS_STANDARD ? 2 : 1);
-        const float *x0d = stage(h, x0, S->sx0, n, host), *x1d = stage(h, x1, S->sx1, n, host);
-        const float *b0d = stage(h, beta0, S->sb0, (size_t)B, host), *b1d = stage(h, beta1, S->sb1, (size_t)B, host);
-        const float *td = stage(h, t, S->tin, (size_t)B, host), *zd = stage(h, z, S->zin, n, host);
+        const float *x0d = sg.in(x0, S->sx0, n), *x1d = sg.in(x1, S->sx1, n);
+        const float *b0d = sg.in(beta0, S->sb0, (size_t)B), *b1d = sg.in(beta1, S->sb1, (size_t)B);
+        const float *td = sg.in(t, S->tin, (size_t)B), *zd = sg.in(z, S->zin, n);
         train_forward_backward(h, S, d, x0d, x1d, b0d, b1d, td, zd, B, d->draw);
-        double red[2];
-        HIP_CHECK(hipMemcpyAsync(red, S->red.p, sizeof(red), hipMemcpyDeviceToHost, st));
-        if (out_loss) HIP_CHECK(hipMemcpyAsync(out_loss, S->loss.p, (size_t)B * sizeof(double), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-        if (out_grad) HIP_CHECK(hipMemcpyAsync(out_grad, S->grad.p, S->nW * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (out_mean) *out_mean = red[RED_LOSS] / (double)B;
-        if (out_gnorm) *out_gnorm = std::sqrt(red[RED_SUMSQ]);
-        return TI_OK;
+        return S->grad_readback(out_loss, out_mean, out_grad, out_gnorm, B, (double)B, mem, S->loss.p, h->stream);
     });
 }
 
@@ -288,25 +213,7 @@ int ti_adw_train_apply(ti_handle* h, const double* grad, int32_t* out_skipped)
 {
     if (!grad) return fail(TI_E_ARG, "NULL buffer");
     if (!h || h->kind != 2) return fail(TI_E_ARG, "not an adw trainer handle");
-    return guarded([&]() -> int {
-        set_device(h);
-        AdwTrainState* S = state_of(h);
-        hipStream_t st = h->stream;
-        grow(S->part64, (size_t)vloss_tiles((long long)S->nW));
-        HIP_CHECK(hipMemcpyAsync(S->grad.p, grad, S->nW * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_CHECK(launch_train_combine(S->grad.p, S->sq.p, nullptr, S->is_bias.p, 0, S->nW, S->n_embed, 0, 0, st));
-        HIP_CHECK(launch_vloss_colsum(S->red.p + RED_SUMSQ, S->part64.p, S->sq.p, (long long)S->nW, 1, st));
-        read_counters(h, S);                  // a call that failed half-way may have left the host mirror behind the device
-        std::vector<double> tab;
-        upload_bias(h, S, 1, tab);
-        const TrAdam a = adam_params(S, false, 1, nullptr);
-        HIP_CHECK(launch_train_adam(a, st));
-        HIP_CHECK(launch_train_finish(a, st));
-        const long long before = S->n_skipped;
-        read_counters(h, S);
-        if (out_skipped) *out_skipped = (int32_t)(S->n_skipped - before);
-        return TI_OK;
-    });
+    return guarded([&]() -> int { set_device(h); return state_of(h)->apply(grad, out_skipped, state_of(h)->n_embed, h->stream); });
 }
 
 int ti_adw_train_steps(ti_handle* h, const ti_vloss_desc* d, const float* x0, int64_t n0, const float* x1, int64_t n1, const float* beta0,
@@ -323,48 +230,25 @@ int ti_adw_train_steps(ti_handle* h, const ti_vloss_desc* d, const float* x0, in
     if (!x0 || !x1 || !beta0 || !beta1) return fail(TI_E_ARG, "NULL buffer");
     if (d->center != TI_CENTER_NONE) return fail(TI_E_UNSUPPORTED, "an adw trainer takes TI_CENTER_NONE only");
     const size_t n_idx = idx0 ? (size_t)n_steps * (size_t)B : 0;
-    auto idx_check = [&](const int64_t* i0, const int64_t* i1) -> int {
-        for (size_t k = 0; k < n_idx; ++k) {
-            if (i0[k] < 0 || i0[k] >= n0) return fail(TI_E_ARG, "idx0[" + std::to_string(k) + "] is outside 0..n0-1");
-            if (i1[k] < 0 || i1[k] >= n1) return fail(TI_E_ARG, "idx1[" + std::to_string(k) + "] is outside 0..n1-1");
-        }
-        return TI_OK;
-    };
-    if (idx0 && mem == TI_MEM_HOST) if (int rc = idx_check(idx0, idx1)) return rc;
+    if (idx0 && mem == TI_MEM_HOST) if (int rc = train_idx_check(idx0, idx1, n_idx, n0, n1, true, mem)) return rc;
     if (!h || h->kind != 2) return fail(TI_E_ARG, "not an adw trainer handle");
     return guarded([&]() -> int {
         set_device(h);
         AdwTrainState* S = state_of(h);
         hipStream_t st = h->stream;
-        const bool host = mem == TI_MEM_HOST;
+        Staged sg(h, mem);
         const int m = S->dim;
-        if (idx0 && !host) {                  // device indices: read once and checked here; nothing has been enqueued yet
-            std::vector<int64_t> i0(n_idx), i1(n_idx);
-            HIP_CHECK(hipMemcpy(i0.data(), idx0, n_idx * sizeof(int64_t), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(i1.data(), idx1, n_idx * sizeof(int64_t), hipMemcpyDeviceToHost));
-            if (int rc = idx_check(i0.data(), i1.data())) return rc;
-        }
+        if (idx0 && !sg.host) if (int rc = train_idx_check(idx0, idx1, n_idx, n0, n1, true, mem)) return rc;      // nothing has been enqueued yet
         ensure_train_ws(S, B, d->kind == TI_VLOSS_STANDARD ? 2 : 1);
         grow(S->log, (size_t)n_steps);
-        const float *x0d = stage(h, x0, S->sx0, (size_t)n0 * m, host), *x1d = stage(h, x1, S->sx1, (size_t)n1 * m, host);
-        const float *b0d = stage(h, beta0, S->sb0, (size_t)n0, host), *b1d = stage(h, beta1, S->sb1, (size_t)n1, host);
-        const float *td = stage(h, t, S->tin, (size_t)B, host), *zd = stage(h, z, S->zin, (size_t)B * m, host);
-        const long long *i0d = nullptr, *i1d = nullptr;
-        if (idx0) {
-            static_assert(sizeof(long long) == sizeof(int64_t), "index width");
-            i0d = reinterpret_cast<const long long*>(idx0); i1d = reinterpret_cast<const long long*>(idx1);
-            if (host) {
-                grow(S->idx0, n_idx); grow(S->idx1, n_idx);
-                HIP_CHECK(hipMemcpyAsync(S->idx0.p, idx0, n_idx * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync(S->idx1.p, idx1, n_idx * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                i0d = S->idx0.p; i1d = S->idx1.p;
-            }
-            grow(S->gx0, (size_t)B * m); grow(S->gx1, (size_t)B * m); grow(S->gb0, (size_t)B); grow(S->gb1, (size_t)B);
-        }
-        read_counters(h, S);                  // as in ti_adw_train_apply: bias and log are indexed from these
-        std::vector<double> tab;
-        upload_bias(h, S, n_steps, tab);
-        const TrAdam a = adam_params(S, true, B, S->log.p);
+        const float *x0d = sg.in(x0, S->sx0, (size_t)n0 * m), *x1d = sg.in(x1, S->sx1, (size_t)n1 * m);
+        const float *b0d = sg.in(beta0, S->sb0, (size_t)n0), *b1d = sg.in(beta1, S->sb1, (size_t)n1);
+        const float *td = sg.in(t, S->tin, (size_t)B), *zd = sg.in(z, S->zin, (size_t)B * m);
+        const long long *i0d = idx_ll(sg.in(idx0, S->idx0, n_idx)), *i1d = idx_ll(sg.in(idx1, S->idx1, n_idx));
+        if (idx0) { grow(S->gx0, (size_t)B * m); grow(S->gx1, (size_t)B * m); grow(S->gb0, (size_t)B); grow(S->gb1, (size_t)B); }
+        S->read_counters(st);                 // as in ti_adw_train_apply: bias and log are indexed from these
+        S->upload_bias(n_steps, st);
+        const TrAdam a = S->adam_params(true, (double)B, S->log.p);
         for (int64_t k = 0; k < n_steps; ++k) {
             const float *xa = x0d, *xb = x1d, *ba = b0d, *bb = b1d;
             if (idx0) {
@@ -378,10 +262,7 @@ int ti_adw_train_steps(ti_handle* h, const ti_vloss_desc* d, const float* x0, in
             HIP_CHECK(launch_train_adam(a, st));
             HIP_CHECK(launch_train_finish(a, st));
         }
-        if (out_loss) HIP_CHECK(hipMemcpyAsync(out_loss, S->log.p, (size_t)n_steps * sizeof(double), hipMemcpyDeviceToHost, st));
-        const long long before = S->n_skipped;
-        read_counters(h, S);
-        if (out_skipped) *out_skipped = S->n_skipped - before;
+        S->steps_readback(out_loss, out_skipped, n_steps, st);
         return TI_OK;
     });
 }
@@ -389,41 +270,19 @@ int ti_adw_train_steps(ti_handle* h, const ti_vloss_desc* d, const float* x0, in
 int ti_adw_train_get_state(ti_handle* h, double* w, double* m, double* v, int64_t* n_applied, int64_t* n_skipped)
 {
     if (!h || h->kind != 2) return fail(TI_E_ARG, "not an adw trainer handle");
-    return guarded([&]() -> int {
-        set_device(h);
-        AdwTrainState* S = state_of(h);
-        const size_t bytes = S->nW * sizeof(double);
-        if (w) HIP_CHECK(hipMemcpyAsync(w, S->w.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (m) HIP_CHECK(hipMemcpyAsync(m, S->m.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (v) HIP_CHECK(hipMemcpyAsync(v, S->v.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (n_applied) *n_applied = S->n_applied;
-        if (n_skipped) *n_skipped = S->n_skipped;
-        return TI_OK;
-    });
+    return guarded([&]() -> int { set_device(h); return state_of(h)->get_state(w, m, v, n_applied, n_skipped, h->stream); });
 }
 
 int ti_adw_train_set_state(ti_handle* h, const double* w, const double* m, const double* v, int64_t n_applied)
 {
     if (n_applied < 0) return fail(TI_E_ARG, "n_applied < 0");
     if (!h || h->kind != 2) return fail(TI_E_ARG, "not an adw trainer handle");
-    return guarded([&]() -> int {
-        set_device(h);
-        AdwTrainState* S = state_of(h);
-        const size_t bytes = S->nW * sizeof(double);
-        if (w) HIP_CHECK(hipMemcpyAsync(S->w.p, w, bytes, hipMemcpyHostToDevice, h->stream));
-        if (m) HIP_CHECK(hipMemcpyAsync(S->m.p, m, bytes, hipMemcpyHostToDevice, h->stream));
-        if (v) HIP_CHECK(hipMemcpyAsync(S->v.p, v, bytes, hipMemcpyHostToDevice, h->stream));
-        if (w) HIP_CHECK(launch_train_refresh(S->w32.p, S->w.p, S->nW, h->stream));
-        S->n_applied = n_applied;
-        write_counters(h, S);
-        return TI_OK;
-    });
+    return guarded([&]() -> int { set_device(h); return state_of(h)->set_state(w, m, v, n_applied, h->stream); });
 }
 
 int ti_adw_train_set_lr(ti_handle* h, double lr)
 {
-    if (!(std::isfinite(lr) && lr > 0.0)) return fail(TI_E_ARG, "lr must be finite and > 0");
+    if (int rc = lr_check(lr)) return rc;
     if (!h || h->kind != 2) return fail(TI_E_ARG, "not an adw trainer handle");
     state_of(h)->td.lr = lr;
     return TI_OK;

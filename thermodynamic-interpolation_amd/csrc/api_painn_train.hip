@@ -6,12 +6,14 @@
 // synchronisation: whether it is skipped is decided by the optimiser kernel from the two batch-wide sums in device memory.
 // ti_painn_train_steps enqueues many such steps on resident sets (painn_steps_kernels.hip gathers each minibatch, painn_noise_kernels.hip
 // draws the latent base samples) and synchronises once.
-#include "ti_handle.hpp"
+// The optimiser shell -- master state, counters, clip + Adam, the state entry points, index handling -- is train_optim.hpp's, shared
+// with api_adw_train.hip.
+#include "train_optim.hpp"
 #include "painn_steps.hpp"
 
 namespace {
 
-constexpr int RED_LOSS = 0, RED_SUMSQ = 1, RED_COLSUM = 2;      // slots of PainnTrainState::red (the column sums take 6)
+constexpr int RED_COLSUM = 2;      // slots of PainnTrainState::red behind RED_LOSS and RED_SUMSQ (the column sums take 6)
 
 struct Rec { size_t z1, y1, z2, y2; };       // what an MLP keeps: the two pre-LayerNorm rows and the two activations
 struct LayerAct { size_t s_in, v_in, e_in, phi_in, P, Wd, s_m, v_m, uv, vv, up_in, gqa, s_out, v_out; Rec phi, w, upd; };
@@ -23,38 +25,25 @@ struct Plan {
     size_t total = 0;
 };
 
-struct PainnTrainState {
-    ti_painn_desc d{}; ti_painn_train_desc td{};
+struct PainnTrainState : Optim {                 // is_bias: 1 at the biases, LayerNorm entries and tables; red holds 8 (RED_COLSUM)
+    ti_painn_desc d{};
+    unsigned long long max_workspace_bytes = 0;  // the train descriptor's
     int nE = 0, ncond = 0;
-    size_t nW = 0, edge_emb = 0, atom_emb = 0, Vr = 0, max_block = 0;
-    MlpOff embed{}, readout{}; std::vector<MlpOff> phi, w, upd; std::vector<size_t> U, V;
-    long long n_applied = 0, n_skipped = 0;      // host mirror of ctr, read back at the end of every call that steps
-    DevBuf<double> wd, m, v, grad, sq, red, part64, loss, log, bias, raw, colpart;      // colpart: the tile partials of a column sum
-    DevBuf<long long> ctr;
-    DevBuf<float> w32, part, arena, sx0, sx1, sc, tin, zin, t;
-    DevBuf<unsigned char> is_bias;               // [nW] 1 where the gradient is written in fp64 directly (biases, LayerNorm, tables)
+    size_t edge_emb = 0, atom_emb = 0, Vr = 0, max_block = 0;
+    MlpOff embed{}, readout{}; std::vector<MlpOff> phi, filt, upd; std::vector<size_t> U, V;      // filt: the filter MLP (w of ti_handle)
+    DevBuf<double> loss, raw, colpart;           // colpart: the tile partials of a column sum
+    DevBuf<float> part, arena, sx0, sx1, sc, tin, zin, t;
     DevBuf<int32_t> src, dst, etype, atom_ids;
     // ti_painn_train_steps: the staged sets and indices of a host call, the gathered minibatch, the noise kernel's centred fp64 draws
     // and its staged outputs, the best weights with (loss, step) and what the host knows of them
     DevBuf<float> st0, st1, stt0, stt1, gx0, gx1, gcond, nx1, nout;
-    DevBuf<long long> idx0, idx1;
+    DevBuf<int64_t> idx0, idx1;
     DevBuf<double> nxc, nrot, best_w, best;
     bool best_tracked = false; long long best_steps = 0;      // a call has tracked since the last reset; the steps tracked since then
     bool mirror_stale = false;                   // a many-step call did not reach its read-back: the next one reads the counters first
 };
 
 PainnTrainState* state_of(ti_handle* h) { return static_cast<PainnTrainState*>(h->train.get()); }
-
-int train_desc_check(const ti_painn_train_desc* t)
-{
-    if (!t) return fail(TI_E_ARG, "train desc is NULL");
-    if (!(std::isfinite(t->lr) && t->lr > 0.0)) return fail(TI_E_ARG, "lr must be finite and > 0");
-    if (!(t->beta1 >= 0.0 && t->beta1 < 1.0) || !(t->beta2 >= 0.0 && t->beta2 < 1.0)) return fail(TI_E_ARG, "beta1 and beta2 must be in [0, 1)");
-    if (!(std::isfinite(t->eps) && t->eps > 0.0)) return fail(TI_E_ARG, "eps must be finite and > 0");
-    if (!(std::isfinite(t->weight_decay) && t->weight_decay >= 0.0)) return fail(TI_E_ARG, "weight_decay must be finite and >= 0");
-    if (std::isnan(t->max_grad_norm)) return fail(TI_E_ARG, "max_grad_norm is NaN");
-    return TI_OK;
-}
 
 Plan plan(const PainnTrainState* S, long long B, int halves)
 {
@@ -104,7 +93,7 @@ unsigned long long workspace_bytes(const PainnTrainState* S, long long B, int ha
 
 int workspace_check(const PainnTrainState* S, long long B, int halves)
 {
-    const unsigned long long need = workspace_bytes(S, B, halves), cap = S->td.max_workspace_bytes ? S->td.max_workspace_bytes : TI_PAINN_TRAIN_DEFAULT_WORKSPACE;
+    const unsigned long long need = workspace_bytes(S, B, halves), cap = S->max_workspace_bytes ? S->max_workspace_bytes : TI_PAINN_TRAIN_DEFAULT_WORKSPACE;
     if (need > cap)
         return fail(TI_E_UNSUPPORTED, "the call needs a workspace of " + std::to_string(need) + " bytes, above max_workspace_bytes = " + std::to_string(cap));
     return TI_OK;
@@ -243,7 +232,7 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
         const LayerAct& a = p.layers[l];
         HIP_CHECK(launch_ptrain_phi_in(ar + a.phi_in, ar + a.s_in, ar + a.e_in, g, st));
         run.mlp_forward(S->phi[l], ar + a.phi_in, Re, a.phi, ar + a.P);
-        run.mlp_forward(S->w[l], ar + p.enc, Re, a.w, ar + a.Wd);
+        run.mlp_forward(S->filt[l], ar + p.enc, Re, a.w, ar + a.Wd);
         HIP_CHECK(launch_ptrain_msg_fwd(ar + a.s_m, ar + a.v_m, ar + a.s_in, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, st));
         if (l + 1 < L) HIP_CHECK(launch_ptrain_e_fwd(ar + p.layers[l + 1].e_in, ar + a.e_in, ar + a.P, ar + a.Wd, g, st));
         run.lin(ar + a.v_m, F, S->U[l], nullptr, F, 3 * Rn, ar + a.uv);
@@ -289,7 +278,7 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
         // message
         HIP_CHECK(launch_ptrain_msg_bwd_edge(ar + p.gP, ar + p.gWd, ar + p.gs[cur], ar + p.gv[cur], ge, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, st));
         run.mlp_backward(S->phi[l], p, ar + a.phi_in, Re, a.phi, ar + p.gP, ar + p.gin_phi, 2 * F, run.sl_e);
-        run.mlp_backward(S->w[l], p, ar + p.enc, Re, a.w, ar + p.gWd, nullptr, 0, run.sl_e);
+        run.mlp_backward(S->filt[l], p, ar + p.enc, Re, a.w, ar + p.gWd, nullptr, 0, run.sl_e);
         HIP_CHECK(launch_ptrain_msg_bwd_node(ar + p.gs[1 - cur], ar + p.gv[1 - cur], ar + p.gs[cur], ar + p.gv[cur], ar + p.gin_phi, ar + a.P, ar + a.Wd,
                                              ar + p.dir, g, st));
         HIP_CHECK(launch_ptrain_e_bwd(ar + p.ge[ecur], ge, ar + p.gin_phi, g, st));
@@ -301,45 +290,6 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
     HIP_CHECK(launch_ptrain_table(S->grad.p + S->atom_emb, ar + p.gin_emb, F, S->atom_ids.p, A, S->d.n_types, R, F, st));
     HIP_CHECK(launch_train_combine(S->grad.p, S->sq.p, nullptr, S->is_bias.p, 0, S->nW, 0, 0, 0, st));
     HIP_CHECK(launch_vloss_colsum(S->red.p + RED_SUMSQ, S->part64.p, S->sq.p, (long long)S->nW, 1, st));
-}
-
-// the two bias terms of steps n_applied + 1 .. n_applied + n, computed here and indexed on the device by the steps applied so far
-void upload_bias(ti_handle* h, PainnTrainState* S, std::vector<double>& tab, long long n = 1)
-{
-    tab.resize(2 * (size_t)n);
-    for (long long i = 0; i < n; ++i) {
-        const double k = (double)(S->n_applied + 1 + i);
-        tab[2 * i] = S->td.lr / (1.0 - std::pow(S->td.beta1, k));
-        tab[2 * i + 1] = std::sqrt(1.0 - std::pow(S->td.beta2, k));
-    }
-    grow(S->bias, tab.size());
-    HIP_CHECK(hipMemcpyAsync(S->bias.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-}
-
-TrAdam adam_params(PainnTrainState* S, bool with_loss, double divisor, double* log)
-{
-    TrAdam a{};
-    a.w = S->wd.p; a.m = S->m.p; a.v = S->v.p; a.w32 = S->w32.p; a.grad = S->grad.p; a.n = S->nW;
-    a.sumsq = S->red.p + RED_SUMSQ; a.loss_sum = with_loss ? S->red.p + RED_LOSS : nullptr; a.B = divisor;
-    a.beta1 = S->td.beta1; a.beta2 = S->td.beta2; a.eps = S->td.eps; a.weight_decay = S->td.weight_decay; a.max_norm = S->td.max_grad_norm;
-    a.bias = S->bias.p; a.ctr = S->ctr.p; a.base = S->n_applied; a.base_skip = S->n_skipped; a.log = log;
-    return a;
-}
-
-void read_counters(ti_handle* h, PainnTrainState* S)
-{
-    long long c[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(c, S->ctr.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    S->n_applied = c[0]; S->n_skipped = c[1];
-}
-
-const float* stage(ti_handle* h, const float* p, DevBuf<float>& buf, size_t n, bool host)
-{
-    if (!p || !host) return p;
-    grow(buf, n);
-    HIP_CHECK(hipMemcpyAsync(buf.p, p, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    return buf.p;
 }
 
 // the checks ti_painn_train_grad and ti_painn_train_step share, in the order include/ti_hip.h lists them
@@ -358,14 +308,14 @@ int call_check(ti_handle* h, const ti_vloss_desc* d, const float* x0, const floa
 void run_passes(ti_handle* h, PainnTrainState* S, const ti_vloss_desc* d, const float* x0, const float* x1, const float* cond, const float* t,
                 const float* z, int64_t B, int mem)
 {
-    const bool host = mem == TI_MEM_HOST;
+    Staged sg(h, mem);
     const int halves = d->kind == TI_VLOSS_STANDARD ? 2 : 1;
     const size_t n = (size_t)B * 3 * S->d.n_atoms;
     const Plan p = plan(S, B, halves);
     ensure_ws(S, p, B, halves);
-    const float *x0d = stage(h, x0, S->sx0, n, host), *x1d = stage(h, x1, S->sx1, n, host);
-    const float* cd = stage(h, cond, S->sc, (size_t)B * S->d.n_atoms * S->ncond, host);
-    const float *td = stage(h, t, S->tin, (size_t)B, host), *zd = stage(h, z, S->zin, n, host);
+    const float *x0d = sg.in(x0, S->sx0, n), *x1d = sg.in(x1, S->sx1, n);
+    const float* cd = sg.in(cond, S->sc, (size_t)B * S->d.n_atoms * S->ncond);
+    const float *td = sg.in(t, S->tin, (size_t)B), *zd = sg.in(z, S->zin, n);
     train_forward_backward(h, S, p, d, x0d, x1d, cd, td, zd, B);
 }
 
@@ -399,9 +349,9 @@ ti_handle* ti_painn_trainer_create(const ti_painn_desc* d, const double* weights
         size_t o = 0;
         S->edge_emb = o; o += 4 * (size_t)F; S->atom_emb = o; o += (size_t)d->n_types * F;
         o = take_mlp(S->embed, o, S->nE * F, F, F);
-        S->phi.resize(L); S->w.resize(L); S->upd.resize(L); S->U.resize(L); S->V.resize(L);
+        S->phi.resize(L); S->filt.resize(L); S->upd.resize(L); S->U.resize(L); S->V.resize(L);
         for (int l = 0; l < L; ++l) {
-            o = take_mlp(S->phi[l], o, 2 * F, F, 5 * F); o = take_mlp(S->w[l], o, F, F, 5 * F);
+            o = take_mlp(S->phi[l], o, 2 * F, F, 5 * F); o = take_mlp(S->filt[l], o, F, F, 5 * F);
             S->U[l] = o; o += (size_t)F * F; S->V[l] = o; o += (size_t)F * F;
             o = take_mlp(S->upd[l], o, 2 * F, F, 3 * F);
         }
@@ -410,13 +360,13 @@ ti_handle* ti_painn_trainer_create(const ti_painn_desc* d, const double* weights
         if (o != n_weights) return fail(TI_E_ARG, "weight count mismatch: expected " + std::to_string(o) + ", got " + std::to_string(n_weights));
         if (d->precision != TI_PREC_F32) return fail(TI_E_UNSUPPORTED, "the trainer takes TI_PREC_F32 only");
         if (E == 0) return fail(TI_E_UNSUPPORTED, "the trainer needs an edge template: n_edges == 0");
-        if (int rc2 = train_desc_check(td)) return rc2;
-        S->td = *td; S->nW = o;
+        if (!td) return fail(TI_E_ARG, "train desc is NULL");
+        const AdamDesc ad{td->lr, td->beta1, td->beta2, td->eps, td->weight_decay, td->max_grad_norm};
+        if (int rc2 = adam_desc_check(ad)) return rc2;
+        S->max_workspace_bytes = td->max_workspace_bytes;
         S->max_block = (size_t)8 * F * F + (size_t)11 * F;          // phi's MLP, the largest parameter block
         std::unique_ptr<ti_handle> h(new_handle(3, device));
         h->d = *d;
-        S->wd.alloc(o); S->m.alloc(o); S->v.alloc(o); S->grad.alloc(o); S->sq.alloc(o); S->w32.alloc(o);
-        S->red.alloc(8); S->ctr.alloc(2); S->log.alloc(1);
         std::vector<unsigned char> mask(o, 1);
         auto weights_of = [&](const MlpOff& m) {
             std::fill(mask.begin() + m.W0, mask.begin() + m.b0, (unsigned char)0);
@@ -425,20 +375,13 @@ ti_handle* ti_painn_trainer_create(const ti_painn_desc* d, const double* weights
         };
         weights_of(S->embed); weights_of(S->readout);
         for (int l = 0; l < L; ++l) {
-            weights_of(S->phi[l]); weights_of(S->w[l]); weights_of(S->upd[l]);
+            weights_of(S->phi[l]); weights_of(S->filt[l]); weights_of(S->upd[l]);
             std::fill(mask.begin() + S->U[l], mask.begin() + S->U[l] + (size_t)2 * F * F, (unsigned char)0);
         }
         std::fill(mask.begin() + S->Vr, mask.begin() + S->Vr + F, (unsigned char)0);
-        S->is_bias.upload(mask);
+        S->setup(ad, weights, mask, 8, 1, h->stream);
         S->src.upload(std::vector<int32_t>(edge_src, edge_src + E)); S->dst.upload(std::vector<int32_t>(edge_dst, edge_dst + E));
         S->etype.upload(std::vector<int32_t>(edge_type, edge_type + E)); S->atom_ids.upload(std::vector<int32_t>(atom_ids, atom_ids + A));
-        HIP_CHECK(hipMemcpyAsync(S->wd.p, weights, o * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemsetAsync(S->m.p, 0, o * sizeof(double), h->stream));
-        HIP_CHECK(hipMemsetAsync(S->v.p, 0, o * sizeof(double), h->stream));
-        HIP_CHECK(hipMemsetAsync(S->grad.p, 0, o * sizeof(double), h->stream));
-        HIP_CHECK(hipMemsetAsync(S->ctr.p, 0, 2 * sizeof(long long), h->stream));
-        HIP_CHECK(launch_train_refresh(S->w32.p, S->wd.p, o, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
         h->train = S;
         out = h.release();
         return TI_OK;
@@ -453,16 +396,8 @@ int ti_painn_train_grad(ti_handle* h, const ti_vloss_desc* d, const float* x0, c
     return guarded([&]() -> int {
         set_device(h);
         PainnTrainState* S = state_of(h);
-        hipStream_t st = h->stream;
         run_passes(h, S, d, x0, x1, cond, t, z, B, mem);
-        double red[2];
-        HIP_CHECK(hipMemcpyAsync(red, S->red.p, sizeof(red), hipMemcpyDeviceToHost, st));
-        if (out_loss) HIP_CHECK(hipMemcpyAsync(out_loss, S->loss.p, (size_t)B * sizeof(double), mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-        if (out_grad) HIP_CHECK(hipMemcpyAsync(out_grad, S->grad.p, S->nW * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (out_mean) *out_mean = red[RED_LOSS] / (double)(B * S->d.n_atoms);
-        if (out_gnorm) *out_gnorm = std::sqrt(red[RED_SUMSQ]);
-        return TI_OK;
+        return S->grad_readback(out_loss, out_mean, out_grad, out_gnorm, B, (double)(B * S->d.n_atoms), mem, S->loss.p, h->stream);
     });
 }
 
@@ -470,25 +405,7 @@ int ti_painn_train_apply(ti_handle* h, const double* grad, int32_t* out_skipped)
 {
     if (!grad) return fail(TI_E_ARG, "NULL buffer");
     if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
-    return guarded([&]() -> int {
-        set_device(h);
-        PainnTrainState* S = state_of(h);
-        hipStream_t st = h->stream;
-        grow(S->part64, (size_t)vloss_tiles((long long)S->nW));
-        HIP_CHECK(hipMemcpyAsync(S->grad.p, grad, S->nW * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_CHECK(launch_train_combine(S->grad.p, S->sq.p, nullptr, S->is_bias.p, 0, S->nW, 0, 0, 0, st));
-        HIP_CHECK(launch_vloss_colsum(S->red.p + RED_SUMSQ, S->part64.p, S->sq.p, (long long)S->nW, 1, st));
-        read_counters(h, S);                  // a call that failed half-way may have left the host mirror behind the device
-        std::vector<double> tab;
-        upload_bias(h, S, tab);
-        const TrAdam a = adam_params(S, false, 1.0, nullptr);
-        HIP_CHECK(launch_train_adam(a, st));
-        HIP_CHECK(launch_train_finish(a, st));
-        const long long before = S->n_skipped;
-        read_counters(h, S);
-        if (out_skipped) *out_skipped = (int32_t)(S->n_skipped - before);
-        return TI_OK;
-    });
+    return guarded([&]() -> int { set_device(h); return state_of(h)->apply(grad, out_skipped, 0, h->stream); });
 }
 
 int ti_painn_train_step(ti_handle* h, const ti_vloss_desc* d, const float* x0, const float* x1, const float* cond, const float* t,
@@ -499,17 +416,16 @@ int ti_painn_train_step(ti_handle* h, const ti_vloss_desc* d, const float* x0, c
         set_device(h);
         PainnTrainState* S = state_of(h);
         hipStream_t st = h->stream;
-        read_counters(h, S);
-        std::vector<double> tab;
-        upload_bias(h, S, tab);
+        S->read_counters(st);
+        S->upload_bias(1, st);
         run_passes(h, S, d, x0, x1, cond, t, z, B, mem);
-        const TrAdam a = adam_params(S, true, (double)(B * S->d.n_atoms), S->log.p);
+        const TrAdam a = S->adam_params(true, (double)(B * S->d.n_atoms), S->log.p);
         HIP_CHECK(launch_train_adam(a, st));
         HIP_CHECK(launch_train_finish(a, st));
         double mean = 0.0;
         HIP_CHECK(hipMemcpyAsync(&mean, S->log.p, sizeof(double), hipMemcpyDeviceToHost, st));
         const long long before = S->n_skipped;
-        read_counters(h, S);
+        S->read_counters(st);
         if (out_mean) *out_mean = mean;
         if (out_skipped) *out_skipped = (int32_t)(S->n_skipped - before);
         return TI_OK;
@@ -519,43 +435,19 @@ int ti_painn_train_step(ti_handle* h, const ti_vloss_desc* d, const float* x0, c
 int ti_painn_train_get_state(ti_handle* h, double* w, double* m, double* v, int64_t* n_applied, int64_t* n_skipped)
 {
     if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
-    return guarded([&]() -> int {
-        set_device(h);
-        PainnTrainState* S = state_of(h);
-        const size_t bytes = S->nW * sizeof(double);
-        if (w) HIP_CHECK(hipMemcpyAsync(w, S->wd.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (m) HIP_CHECK(hipMemcpyAsync(m, S->m.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (v) HIP_CHECK(hipMemcpyAsync(v, S->v.p, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (n_applied) *n_applied = S->n_applied;
-        if (n_skipped) *n_skipped = S->n_skipped;
-        return TI_OK;
-    });
+    return guarded([&]() -> int { set_device(h); return state_of(h)->get_state(w, m, v, n_applied, n_skipped, h->stream); });
 }
 
 int ti_painn_train_set_state(ti_handle* h, const double* w, const double* m, const double* v, int64_t n_applied)
 {
     if (n_applied < 0) return fail(TI_E_ARG, "n_applied < 0");
     if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
-    return guarded([&]() -> int {
-        set_device(h);
-        PainnTrainState* S = state_of(h);
-        const size_t bytes = S->nW * sizeof(double);
-        if (w) HIP_CHECK(hipMemcpyAsync(S->wd.p, w, bytes, hipMemcpyHostToDevice, h->stream));
-        if (m) HIP_CHECK(hipMemcpyAsync(S->m.p, m, bytes, hipMemcpyHostToDevice, h->stream));
-        if (v) HIP_CHECK(hipMemcpyAsync(S->v.p, v, bytes, hipMemcpyHostToDevice, h->stream));
-        if (w) HIP_CHECK(launch_train_refresh(S->w32.p, S->wd.p, S->nW, h->stream));
-        S->n_applied = n_applied;
-        const long long c[2] = {S->n_applied, S->n_skipped};
-        HIP_CHECK(hipMemcpyAsync(S->ctr.p, c, sizeof(c), hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        return TI_OK;
-    });
+    return guarded([&]() -> int { set_device(h); return state_of(h)->set_state(w, m, v, n_applied, h->stream); });
 }
 
 int ti_painn_train_set_lr(ti_handle* h, double lr)
 {
-    if (!(std::isfinite(lr) && lr > 0.0)) return fail(TI_E_ARG, "lr must be finite and > 0");
+    if (int rc = lr_check(lr)) return rc;
     if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
     state_of(h)->td.lr = lr;
     return TI_OK;
@@ -596,14 +488,7 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_st
         if (nc == 0 && (temp0 || temp1)) return fail(TI_E_ARG, "the single-T variant takes no temperatures: temp0 and temp1 must be NULL");
     }
     const size_t n_idx = idx0 ? (size_t)n_steps * (size_t)B : 0;
-    auto idx_check = [&](const int64_t* i0, const int64_t* i1) -> int {
-        for (size_t k = 0; k < n_idx; ++k) {
-            if (given && (i0[k] < 0 || i0[k] >= n0)) return fail(TI_E_ARG, "idx0[" + std::to_string(k) + "] is outside 0..n0-1");
-            if (i1[k] < 0 || i1[k] >= n1) return fail(TI_E_ARG, "idx1[" + std::to_string(k) + "] is outside 0..n1-1");
-        }
-        return TI_OK;
-    };
-    if (idx0 && mem == TI_MEM_HOST) if (int rc = idx_check(idx0, idx1)) return rc;
+    if (idx0 && mem == TI_MEM_HOST) if (int rc = train_idx_check(idx0, idx1, n_idx, n0, n1, given, mem)) return rc;
     if (!ours) return fail(TI_E_ARG, "not a painn trainer handle");
     if (!given && state_of(h)->ncond == 2) return fail(TI_E_UNSUPPORTED, "drawn noise on the ambient variant: its set 0 is data");
     if (sd->noise == TI_NOISE_ALIGNED && h->d.n_atoms < 3) return fail(TI_E_UNSUPPORTED, "TI_NOISE_ALIGNED needs n_atoms >= 3: the rotation is not unique");
@@ -611,15 +496,11 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_st
         set_device(h);
         PainnTrainState* S = state_of(h);
         hipStream_t st = h->stream;
-        const bool host = mem == TI_MEM_HOST, update = sd->update == 1;
+        Staged sg(h, mem);
+        const bool update = sd->update == 1;
         const int A = S->d.n_atoms, halves = d->kind == TI_VLOSS_STANDARD ? 2 : 1;
         const size_t m = (size_t)3 * A;
-        if (idx0 && !host) {                  // device indices: read once and checked here; nothing has been enqueued yet
-            std::vector<int64_t> i0(n_idx), i1(n_idx);
-            HIP_CHECK(hipMemcpy(i0.data(), idx0, n_idx * sizeof(int64_t), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(i1.data(), idx1, n_idx * sizeof(int64_t), hipMemcpyDeviceToHost));
-            if (int rc = idx_check(i0.data(), i1.data())) return rc;
-        }
+        if (idx0 && !sg.host) if (int rc = train_idx_check(idx0, idx1, n_idx, n0, n1, given, mem)) return rc;      // nothing has been enqueued yet
         const Plan p = plan(S, B, halves);
         ensure_ws(S, p, B, halves);
         grow(S->log, (size_t)n_steps);
@@ -630,28 +511,17 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_st
             static const double init[2] = {HUGE_VAL, -1.0};
             HIP_CHECK(hipMemcpyAsync(S->best.p, init, sizeof(init), hipMemcpyHostToDevice, st));
         }
-        const float *x0d = given ? stage(h, x0, S->st0, (size_t)n0 * m, host) : nullptr, *x1d = stage(h, x1, S->st1, (size_t)n1 * m, host);
-        const float *t0d = S->ncond == 2 ? stage(h, temp0, S->stt0, (size_t)n0, host) : nullptr;
-        const float *t1d = S->ncond >= 1 ? stage(h, temp1, S->stt1, (size_t)n1, host) : nullptr;
-        const long long *i0d = nullptr, *i1d = nullptr;
-        if (idx0) {
-            static_assert(sizeof(long long) == sizeof(int64_t), "index width");
-            i0d = reinterpret_cast<const long long*>(idx0); i1d = reinterpret_cast<const long long*>(idx1);
-            if (host) {
-                grow(S->idx0, n_idx); grow(S->idx1, n_idx);
-                HIP_CHECK(hipMemcpyAsync(S->idx0.p, idx0, n_idx * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync(S->idx1.p, idx1, n_idx * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                i0d = S->idx0.p; i1d = S->idx1.p;
-            }
-        }
+        const float *x0d = given ? sg.in(x0, S->st0, (size_t)n0 * m) : nullptr, *x1d = sg.in(x1, S->st1, (size_t)n1 * m);
+        const float *t0d = S->ncond == 2 ? sg.in(temp0, S->stt0, (size_t)n0) : nullptr;
+        const float *t1d = S->ncond >= 1 ? sg.in(temp1, S->stt1, (size_t)n1) : nullptr;
+        const long long *i0d = idx_ll(sg.in(idx0, S->idx0, n_idx)), *i1d = idx_ll(sg.in(idx1, S->idx1, n_idx));
         // the bias table and the log are indexed from the host mirror of the counters, which every stepping call brings up to date at
         // its end; only a call that failed half-way leaves it behind, and then the counters are read first
-        if (S->mirror_stale) read_counters(h, S);
+        if (S->mirror_stale) S->read_counters(st);
         S->mirror_stale = true;
-        std::vector<double> tab;
-        if (update) upload_bias(h, S, tab, n_steps);
+        if (update) S->upload_bias(n_steps, st);
         const double divisor = (double)(B * A);
-        const TrAdam a = adam_params(S, true, divisor, S->log.p);
+        const TrAdam a = S->adam_params(true, divisor, S->log.p);
         ti_vloss_desc dk = *d;
         for (int64_t k = 0; k < n_steps; ++k) {
             dk.draw = d->draw + (int32_t)k;
@@ -668,19 +538,16 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_st
             train_forward_backward(h, S, p, &dk, S->gx0.p, S->gx1.p, S->ncond ? S->gcond.p : nullptr, nullptr, nullptr, B, update);
             if (!update) { HIP_CHECK(launch_ptsteps_log(S->log.p + k, S->red.p + RED_LOSS, divisor, st)); continue; }
             if (sd->track_best) {
-                const PtBest q{S->best_w.p, S->wd.p, S->nW, S->best.p, S->red.p + RED_LOSS, S->red.p + RED_SUMSQ, divisor, (double)(S->best_steps + k)};
+                const PtBest q{S->best_w.p, S->w.p, S->nW, S->best.p, S->red.p + RED_LOSS, S->red.p + RED_SUMSQ, divisor, (double)(S->best_steps + k)};
                 HIP_CHECK(launch_ptsteps_best_keep(q, st));
                 HIP_CHECK(launch_ptsteps_best_commit(q, st));
             }
             HIP_CHECK(launch_train_adam(a, st));
             HIP_CHECK(launch_train_finish(a, st));
         }
-        if (out_loss) HIP_CHECK(hipMemcpyAsync(out_loss, S->log.p, (size_t)n_steps * sizeof(double), hipMemcpyDeviceToHost, st));
-        const long long before = S->n_skipped;
-        read_counters(h, S);                  // the one synchronisation of the call
+        S->steps_readback(out_loss, out_skipped, n_steps, st);      // the one synchronisation of the call
         S->mirror_stale = false;
         if (sd->track_best) { S->best_tracked = true; S->best_steps += n_steps; }
-        if (out_skipped) *out_skipped = S->n_skipped - before;
         return TI_OK;
     });
 }
@@ -730,7 +597,7 @@ int ti_painn_train_noise(ti_handle* h, uint64_t seed, int64_t traj_offset, int32
         const bool host = mem == TI_MEM_HOST;
         const size_t n = (size_t)B * 3 * S->d.n_atoms;
         grow(S->nxc, n);
-        const float* x1d = aligned ? stage(h, x1, S->nx1, n, host) : nullptr;
+        const float* x1d = aligned ? Staged(h, mem).in(x1, S->nx1, n) : nullptr;
         float* od = out_x0; double* rd = aligned ? out_rot : nullptr;
         if (host) {
             grow(S->nout, n); od = S->nout.p;

@@ -58,7 +58,7 @@ using namespace ti;
 
 // ====================================================================================================== handle
 struct ti_handle {
-    int kind = 0;                 // 0 painn, 1 adw, 2 adw trainer (api_adw_train.hip), 3 painn trainer (api_painn_train.hip); every painn / adw entry point refuses a trainer by kind
+    int kind = 0;                 // 0 painn, 1 adw, 2 adw trainer (api_adw_train.hip), 3 painn trainer (api_painn_train.hip), both on train_optim.hpp; every painn / adw entry point refuses a trainer by kind
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipEvent_t wait_ev = nullptr;          // ti_wait_stream
@@ -187,8 +187,8 @@ struct ti_handle {
     DevBuf<float> vl_x0, vl_x1, vl_zin, vl_c0, vl_c1, vl_t, vl_z, vl_xt, vl_b, vl_t2, vl_c02, vl_c12;
     DevBuf<double> vl_raw, vl_part, vl_red, vl_loss;
 
-    // ---- trainers (kind 2, 3): the AdwTrainState / PainnTrainState of api_adw_train.hip / api_painn_train.hip, owned here so that
-    // ti_destroy frees it with the handle
+    // ---- trainers (kind 2, 3): the AdwTrainState / PainnTrainState of api_adw_train.hip / api_painn_train.hip (either an Optim of
+    // train_optim.hpp with the trainer's own buffers), owned here so that ti_destroy frees it with the handle
     std::shared_ptr<void> train;
 
     ~ti_handle()
@@ -256,7 +256,7 @@ struct Staged {
     template <typename T>
     const T* in(const T* p, DevBuf<T>& b, size_t n)
     {
-        if (!host) return p;
+        if (!host || !p) return p;          // an optional input that is absent stays NULL (the trainers' t, z, sets)
         grow(b, n);
         if (n) HIP_CHECK(hipMemcpyAsync(b.p, p, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
         return b.p;

@@ -672,6 +672,23 @@ def _split_80_10_10(x, beta, d, rng):
     return (x[tr], beta[tr]), (x[va], beta[va])
 
 
+def _train_resume(out_dir, trainer, sched, log):
+    """Puts trainer and scheduler back from train_state.npz -> (the epochs done, the log's lists so far)"""
+    with np.load(os.path.join(out_dir, "train_state.npz")) as f:
+        st = {k: f[k] for k in f.files}
+    trainer.load_state_dict(st)
+    sched.load(st)
+    return int(st["epochs_done"]), {k: list(st["log_" + k]) for k in log}
+
+
+def _train_checkpoint(out_dir, trainer, sched, log, epochs_done):
+    """train_state.npz (optimiser and scheduler state, the epochs done, the log) and log.npz after an epoch"""
+    arrs = {k: np.asarray(v) for k, v in log.items()}
+    np.savez(os.path.join(out_dir, "train_state.npz"), **trainer.state_dict(), **sched.state(), epochs_done=np.int64(epochs_done),
+             **{"log_" + k: v for k, v in arrs.items()})
+    np.savez(os.path.join(out_dir, "log.npz"), **arrs)
+
+
 def train_adw(config, base, target, resume=False):
     """The loop of adw/train.py:18-100 on the GPU.  base / target: (x, beta) array pairs (x [n] or [n, d], beta [n] or one value).
     Both sets are split 80 / 10 / 10 by a seeded permutation.  Per epoch: min(n_train) // batch_size optimiser steps on drop_last
@@ -692,21 +709,13 @@ def train_adw(config, base, target, resume=False):
     if s["epochs"] * steps > _TRAIN_DRAW0:
         raise ValueError(f"epochs x steps per epoch = {s['epochs'] * steps} exceeds the {_TRAIN_DRAW0} draw indices of a run")
     out_dir = os.path.join(config.model_save_path, config.model_save_name)
-    state_path = os.path.join(out_dir, "train_state.npz")
     b = mod.FCNetMultiBeta(d, d, s["hidden_size"], s["num_layers"])
     b.load_state_dict(_adw._syn.make_state_dict(b._spec, seed=s["seed"], dtype=np.float64))
     loss_fn = _losses.StandardVelocityLoss(_interp.LinearInterpolant(s["a"], s["gamma"]), s["t_distr"])
     trainer = _adw.Trainer(b, loss_fn, s["lr"], weight_decay=s["wd"], max_grad_norm=s["max_grad_norm"])
     sched = _Plateau(s["lr"])
     log = dict(train_loss=[], val_loss=[], lr=[], skipped=[])
-    first = 0
-    if resume:
-        with np.load(state_path) as f:
-            st = {k: f[k] for k in f.files}
-        trainer.load_state_dict(st)
-        sched.load(st)
-        first = int(st["epochs_done"])
-        log = {k: list(st["log_" + k]) for k in log}
+    first, log = _train_resume(out_dir, trainer, sched, log) if resume else (0, log)
     os.makedirs(out_dir, exist_ok=True)
     for epoch in range(first, s["epochs"]):
         losses, skipped = trainer.fit(x0, x1, b0, b1, B, steps, [s["seed"], 2, epoch], draw=_TRAIN_DRAW0 + epoch * steps, noise_seed=s["seed"])
@@ -721,9 +730,7 @@ def train_adw(config, base, target, resume=False):
             trainer.set_lr(new_lr)
         trainer.sync()
         np.savez(os.path.join(out_dir, f"epoch_{epoch}.npz"), **b.state_dict())
-        st = trainer.state_dict()
-        np.savez(state_path, **st, **sched.state(), epochs_done=np.int64(epoch + 1), **{"log_" + k: np.asarray(v) for k, v in log.items()})
-        np.savez(os.path.join(out_dir, "log.npz"), **{k: np.asarray(v) for k, v in log.items()})
+        _train_checkpoint(out_dir, trainer, sched, log, epoch + 1)
     return {k: np.asarray(v) for k, v in log.items()}
 
 
@@ -781,7 +788,6 @@ def _train_molecule(config, set0, set1, template, resume, latent):
         raise ValueError(f"n_epochs x 2 steps per epoch = {s['n_epochs'] * 2 * steps} exceeds the {_TRAIN_DRAW0} draw indices of a run")
     name = config.model_save_name
     out_dir = os.path.join(config.model_save_path, name)
-    state_path = os.path.join(out_dir, "train_state.npz")
     temps = getattr(config, "temperatures", _amb.DEFAULT_TEMPS)
     if latent:
         b = _lat.cPaiNN(s["n_features"], s["score_layers"], temp_length=getattr(config, "temp_length", 10), temperatures=temps)
@@ -794,14 +800,7 @@ def _train_molecule(config, set0, set1, template, resume, latent):
     b.load_state_dict(_adw._syn.make_state_dict(b._spec, seed=s["seed"], dtype=np.float64))
     sched = _Plateau(s["learning_rate"])
     log = dict(train_loss=[], last_train_loss=[], best_loss=[], lr=[], skipped=[])
-    first = 0
-    if resume:
-        with np.load(state_path) as f:
-            st = {k: f[k] for k in f.files}
-        trainer.load_state_dict(st)
-        sched.load(st)
-        first = int(st["epochs_done"])
-        log = {k: list(st["log_" + k]) for k in log}
+    first, log = _train_resume(out_dir, trainer, sched, log) if resume else (0, log)
     os.makedirs(out_dir, exist_ok=True)
     if latent:
         sets = (x1, T1 if b.COND_KEYS else None)
@@ -824,9 +823,7 @@ def _train_molecule(config, set0, set1, template, resume, latent):
         trainer.sync()
         np.savez(os.path.join(out_dir, f"{name}_{epoch}_weights.npz"), **b.state_dict())
         np.savez(os.path.join(out_dir, f"{name}_best{epoch}_weights.npz"), **({k: np.asarray(v, np.float32) for k, v in best_sd.items()} if best_sd is not None else b.state_dict()))
-        st = trainer.state_dict()
-        np.savez(state_path, **st, **sched.state(), epochs_done=np.int64(epoch + 1), **{"log_" + k: np.asarray(v) for k, v in log.items()})
-        np.savez(os.path.join(out_dir, "log.npz"), **{k: np.asarray(v) for k, v in log.items()})
+        _train_checkpoint(out_dir, trainer, sched, log, epoch + 1)
     return {k: np.asarray(v) for k, v in log.items()}
 
 

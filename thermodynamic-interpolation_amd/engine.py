@@ -1091,11 +1091,92 @@ class AdwEngine(_Engine):
         return out, dl, nfe.value
 
 
-class AdwTrainer(_Engine):
+class _Trainer(_Engine):
+    """What AdwTrainer and PainnTrainer share: the optimiser entry points ti_{adw,painn}_train_{apply,get_state,set_state,set_lr}
+    (`_PREFIX` names the family) and the argument plumbing of their gradient and many-step calls."""
+    _PREFIX = None
+
+    def _fn(self, name):
+        return getattr(_lib.lib(), f"{self._PREFIX}_{name}")
+
+    def _created(self):
+        if not self.h:
+            raise _lib.TiError(-1, _lib.last_error())
+
+    def _loss_out(self, B, like):
+        """The fp64 [B] loss buffer where `like` lives (None: numpy) and its pointer"""
+        if like is not None:
+            import torch
+            loss = torch.empty(B, dtype=torch.float64, device=like.device)
+            return loss, C.c_void_p(loss.data_ptr())
+        loss = np.empty(B, np.float64)
+        return loss, C.c_void_p(loss.ctypes.data)
+
+    def _index_ptrs(self, idx0, idx1, dev):
+        """The pointers of a many-step call's index arrays (None where absent), and what keeps them alive"""
+        ip, ikeep = [None, None], []
+        for k, idx in enumerate((idx0, idx1)):
+            if idx is None:
+                continue
+            if hasattr(idx, "data_ptr"):
+                if not dev or str(idx.dtype) != "torch.int64" or not idx.is_contiguous() or not idx.is_cuda:
+                    raise TypeError("index tensors must be contiguous int64 CUDA tensors, with the data on the GPU too")
+                ip[k] = C.c_void_p(idx.data_ptr()); ikeep.append(idx)
+            else:
+                if dev:
+                    raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
+                arr = np.ascontiguousarray(idx, np.int64)
+                ip[k] = C.c_void_p(arr.ctypes.data); ikeep.append(arr)
+        return ip, ikeep
+
+    def apply(self, g):
+        """ti_{adw,painn}_train_apply: clip + Adam with the given fp64 gradient [n_weights] -> True where the step was skipped (non-finite entry)."""
+        g = np.ascontiguousarray(g, np.float64).reshape(-1)
+        if g.size != self.n_weights:
+            raise ValueError(f"g must hold {self.n_weights} entries, got {g.size}")
+        skipped = C.c_int32(0)
+        _lib.check(self._fn("apply")(self.h, g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(skipped)))
+        return bool(skipped.value)
+
+    def state(self):
+        """dict(w, m, v [n_weights] float64, n_applied, n_skipped): master weights, Adam moments, counters"""
+        w, m, v = (np.empty(self.n_weights, np.float64) for _ in range(3))
+        na, ns = C.c_int64(0), C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        _lib.check(self._fn("get_state")(self.h, w.ctypes.data_as(dp), m.ctypes.data_as(dp), v.ctypes.data_as(dp), C.byref(na), C.byref(ns)))
+        return dict(w=w, m=m, v=v, n_applied=int(na.value), n_skipped=int(ns.value))
+
+    def load_state(self, w=None, m=None, v=None, n_applied=0, **_):
+        dp = C.POINTER(C.c_double)
+        arrs = []
+        for name, a in (("w", w), ("m", m), ("v", v)):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.float64).reshape(-1)
+            if a.size != self.n_weights:
+                raise ValueError(f"{name} must hold {self.n_weights} entries, got {a.size}")
+            arrs.append(a)
+        ptrs = [None if a is None else a.ctypes.data_as(dp) for a in arrs]
+        _lib.check(self._fn("set_state")(self.h, *ptrs, int(n_applied)))
+
+    def set_lr(self, lr):
+        _lib.check(self._fn("set_lr")(self.h, float(lr)))
+        self.train_desc.lr = float(lr)
+
+    def weights(self):
+        """The fp64 master weights in the canonical layout [n_weights]"""
+        w = np.empty(self.n_weights, np.float64)
+        _lib.check(self._fn("get_state")(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), None, None, None, None))
+        return w
+
+
+class AdwTrainer(_Trainer):
     """FCNetMultiBeta(d, d, H, L) trained on the velocity loss on the device (ti_adw_train_*): fp64 master weights and Adam moments,
     forward / backward / weight gradient on the f32 matrix cores, clip_grad_norm_ + torch.optim.Adam (L2 weight_decay) in fp64, the
     NaN skip of the reference's loop decided on the device.  `flat`: the canonical fp64 weights (weights.flatten_state_dict).
     Arrays are numpy or CUDA tensors as AdwEngine.velocity_loss takes them: x0, x1 [B] ([B, d] for d > 1), beta0, beta1 [B]."""
+    _PREFIX = "ti_adw_train"
 
     def __init__(self, hidden, layers, flat, dim=1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, device=0,
                  precision="f32"):
@@ -1108,8 +1189,7 @@ class AdwTrainer(_Engine):
         self.n_weights = int(w.size)
         self.h = _lib.lib().ti_adw_trainer_create(C.byref(self.desc), self.dim, w.ctypes.data_as(C.POINTER(C.c_double)), w.size,
                                                   C.byref(self.train_desc), self.device)
-        if not self.h:
-            raise _lib.TiError(-1, _lib.last_error())
+        self._created()
 
     def _xs(self, *lead):
         return tuple(lead) + ((self.dim,) if self.dim > 1 else ())
@@ -1125,27 +1205,12 @@ class AdwTrainer(_Engine):
         desc = self._desc(kind, gamma, a, t, t_distr, seed, traj_offset, draw)
         (x0p, x1p, b0p, b1p, tp, zp), dev, keep = self._ptrs((x0, xs, False, "x0"), (x1, xs, False, "x1"), (beta0, (B,), False, "beta0"),
                                                              (beta1, (B,), False, "beta1"), (t, (B,), False, "t"), (z, xs, False, "z"))
-        if dev:
-            import torch
-            loss = torch.empty(B, dtype=torch.float64, device=x0.device)
-            lp = C.c_void_p(loss.data_ptr())
-        else:
-            loss = np.empty(B, np.float64)
-            lp = C.c_void_p(loss.ctypes.data)
+        loss, lp = self._loss_out(B, x0 if dev else None)
         g = np.empty(self.n_weights, np.float64)
         mean, gnorm = C.c_double(0.0), C.c_double(0.0)
         _lib.check(_lib.lib().ti_adw_train_grad(self.h, C.byref(desc), x0p, x1p, b0p, b1p, tp, zp, B, lp, C.byref(mean),
                                                 g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(gnorm), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return dict(loss=loss, mean=mean.value, grad=g, gnorm=gnorm.value)
-
-    def apply(self, g):
-        """ti_adw_train_apply: clip + Adam with the given fp64 gradient [n_weights] -> True where the step was skipped (non-finite entry)."""
-        g = np.ascontiguousarray(g, np.float64).reshape(-1)
-        if g.size != self.n_weights:
-            raise ValueError(f"g must hold {self.n_weights} entries, got {g.size}")
-        skipped = C.c_int32(0)
-        _lib.check(_lib.lib().ti_adw_train_apply(self.h, g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(skipped)))
-        return bool(skipped.value)
 
     def steps(self, x0, x1, beta0, beta1, idx0=None, idx1=None, *, n_steps=None, batch=None, kind="standard", gamma="brownian", a=1.0,
               t=None, t_distr="uniform", z=None, seed=0, traj_offset=0, draw=0):
@@ -1166,19 +1231,7 @@ class AdwTrainer(_Engine):
             n, B = int(idx0.shape[0]), int(idx0.shape[1])
         specs += [(t, (B,), False, "t"), (z, self._xs(B), False, "z")]
         (x0p, x1p, b0p, b1p, tp, zp), dev, keep = self._ptrs(*specs)
-        ip, ikeep = [None, None], []
-        for k, idx in enumerate((idx0, idx1)):
-            if idx is None:
-                continue
-            if hasattr(idx, "data_ptr"):
-                if not dev or str(idx.dtype) != "torch.int64" or not idx.is_contiguous() or not idx.is_cuda:
-                    raise TypeError("index tensors must be contiguous int64 CUDA tensors, with the data on the GPU too")
-                ip[k] = C.c_void_p(idx.data_ptr()); ikeep.append(idx)
-            else:
-                if dev:
-                    raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
-                arr = np.ascontiguousarray(idx, np.int64)
-                ip[k] = C.c_void_p(arr.ctypes.data); ikeep.append(arr)
+        ip, ikeep = self._index_ptrs(idx0, idx1, dev)
         desc = self._desc(kind, gamma, a, t, t_distr, seed, traj_offset, draw)
         loss = np.empty(n, np.float64)
         skipped = C.c_int64(0)
@@ -1192,45 +1245,14 @@ class AdwTrainer(_Engine):
         loss, skipped = self.steps(x0, x1, beta0, beta1, **kw)
         return float(loss[0]), skipped
 
-    def state(self):
-        """dict(w, m, v [n_weights] float64, n_applied, n_skipped): master weights, Adam moments, counters"""
-        w, m, v = (np.empty(self.n_weights, np.float64) for _ in range(3))
-        na, ns = C.c_int64(0), C.c_int64(0)
-        dp = C.POINTER(C.c_double)
-        _lib.check(_lib.lib().ti_adw_train_get_state(self.h, w.ctypes.data_as(dp), m.ctypes.data_as(dp), v.ctypes.data_as(dp), C.byref(na), C.byref(ns)))
-        return dict(w=w, m=m, v=v, n_applied=int(na.value), n_skipped=int(ns.value))
 
-    def load_state(self, w=None, m=None, v=None, n_applied=0, **_):
-        dp = C.POINTER(C.c_double)
-        arrs = []
-        for name, a in (("w", w), ("m", m), ("v", v)):
-            if a is None:
-                arrs.append(None)
-                continue
-            a = np.ascontiguousarray(a, np.float64).reshape(-1)
-            if a.size != self.n_weights:
-                raise ValueError(f"{name} must hold {self.n_weights} entries, got {a.size}")
-            arrs.append(a)
-        ptrs = [None if a is None else a.ctypes.data_as(dp) for a in arrs]
-        _lib.check(_lib.lib().ti_adw_train_set_state(self.h, *ptrs, int(n_applied)))
-
-    def set_lr(self, lr):
-        _lib.check(_lib.lib().ti_adw_train_set_lr(self.h, float(lr)))
-        self.train_desc.lr = float(lr)
-
-    def weights(self):
-        """The fp64 master weights in the canonical layout [n_weights]"""
-        w = np.empty(self.n_weights, np.float64)
-        _lib.check(_lib.lib().ti_adw_train_get_state(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), None, None, None, None))
-        return w
-
-
-class PainnTrainer(_Engine):
+class PainnTrainer(_Trainer):
     """cPaiNN trained on the velocity loss on the device (ti_painn_train_*): fp64 master weights and Adam moments, a forward pass
     that keeps its intermediates and the reverse pass through every layer, products on the f32 matrix cores, every reduction over
     rows in fp64, clip_grad_norm_ + torch.optim.Adam (L2 weight_decay) in fp64, the NaN skip decided on the device.  `flat`: the
     canonical fp64 weights (weights.flatten_state_dict with weights.painn_param_spec).  Arrays are numpy or CUDA tensors as
     PainnEngine.velocity_loss takes them: x0, x1 [B, A, 3], cond [B, A, ncond] (None for the single-T variant)."""
+    _PREFIX = "ti_painn_train"
 
     def __init__(self, variant, F, L, A, edge_src, edge_dst, edge_type, atom_ids, flat, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, max_grad_norm=1.0, max_workspace_bytes=0, n_types=25, temp_length=10.0, time_length=10.0,
@@ -1251,8 +1273,7 @@ class PainnTrainer(_Engine):
         self.n_weights, self.device = int(w.size), int(device)
         self.h = _lib.lib().ti_painn_trainer_create(C.byref(self.desc), w.ctypes.data_as(C.POINTER(C.c_double)), w.size, _lib.iptr(es), _lib.iptr(ed),
                                                     _lib.iptr(et), _lib.iptr(ai), C.byref(self.train_desc), self.device)
-        if not self.h:
-            raise _lib.TiError(-1, _lib.last_error())
+        self._created()
 
     def _call_args(self, x0, x1, cond, t, z):
         B = int(x0.shape[0])
@@ -1268,27 +1289,12 @@ class PainnTrainer(_Engine):
         """ti_painn_train_grad -> dict(loss [B] float64 (where x0 lives), mean, grad [n_weights] float64 numpy, gnorm); no update."""
         desc = self._vloss_desc(kind, gamma, a, center, t, t_distr, seed, traj_offset, draw, 0)
         B, (x0p, x1p, cp, tp, zp), dev, keep = self._call_args(x0, x1, cond, t, z)
-        if dev:
-            import torch
-            loss = torch.empty(B, dtype=torch.float64, device=x0.device)
-            lp = C.c_void_p(loss.data_ptr())
-        else:
-            loss = np.empty(B, np.float64)
-            lp = C.c_void_p(loss.ctypes.data)
+        loss, lp = self._loss_out(B, x0 if dev else None)
         g = np.empty(self.n_weights, np.float64)
         mean, gnorm = C.c_double(0.0), C.c_double(0.0)
         _lib.check(_lib.lib().ti_painn_train_grad(self.h, C.byref(desc), x0p, x1p, cp, tp, zp, B, lp, C.byref(mean),
                                                   g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(gnorm), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return dict(loss=loss, mean=mean.value, grad=g, gnorm=gnorm.value)
-
-    def apply(self, g):
-        """ti_painn_train_apply: clip + Adam with the given fp64 gradient [n_weights] -> True where the step was skipped (non-finite entry)."""
-        g = np.ascontiguousarray(g, np.float64).reshape(-1)
-        if g.size != self.n_weights:
-            raise ValueError(f"g must hold {self.n_weights} entries, got {g.size}")
-        skipped = C.c_int32(0)
-        _lib.check(_lib.lib().ti_painn_train_apply(self.h, g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(skipped)))
-        return bool(skipped.value)
 
     def step(self, x0, x1, cond=None, *, kind="standard", gamma="brownian", a=1.0, center="batch", t=None, t_distr="uniform", z=None, seed=0,
              traj_offset=0, draw=0):
@@ -1328,19 +1334,7 @@ class PainnTrainer(_Engine):
             n, B = int(idx1.shape[0]), int(idx1.shape[1])
         (x0p, x1p, t0p, t1p), dev, keep = self._ptrs((x0, (n0, self.A, 3), False, "x0"), (x1, (n1, self.A, 3), False, "x1"),
                                                      (temp0, (n0,), False, "temp0"), (temp1, (n1,), False, "temp1"))
-        ip, ikeep = [None, None], []
-        for k, idx in enumerate((idx0, idx1)):
-            if idx is None:
-                continue
-            if hasattr(idx, "data_ptr"):
-                if not dev or str(idx.dtype) != "torch.int64" or not idx.is_contiguous() or not idx.is_cuda:
-                    raise TypeError("index tensors must be contiguous int64 CUDA tensors, with the data on the GPU too")
-                ip[k] = C.c_void_p(idx.data_ptr()); ikeep.append(idx)
-            else:
-                if dev:
-                    raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
-                arr = np.ascontiguousarray(idx, np.int64)
-                ip[k] = C.c_void_p(arr.ctypes.data); ikeep.append(arr)
+        ip, ikeep = self._index_ptrs(idx0, idx1, dev)
         desc = self._vloss_desc(kind, gamma, a, center, None, t_distr, seed, traj_offset, draw, 0)
         sd = _lib.PainnStepsDesc(n, int(bool(update)), _lib.PAINN_NOISES[noise], int(bool(track_best)))
         loss = np.empty(n, np.float64)
@@ -1385,38 +1379,6 @@ class PainnTrainer(_Engine):
         loss, step = C.c_double(0.0), C.c_int64(0)
         _lib.check(_lib.lib().ti_painn_train_best(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(loss), C.byref(step), int(bool(reset))))
         return dict(w=w if step.value >= 0 else None, loss=loss.value, step=int(step.value))
-
-    def state(self):
-        """dict(w, m, v [n_weights] float64, n_applied, n_skipped): master weights, Adam moments, counters"""
-        w, m, v = (np.empty(self.n_weights, np.float64) for _ in range(3))
-        na, ns = C.c_int64(0), C.c_int64(0)
-        dp = C.POINTER(C.c_double)
-        _lib.check(_lib.lib().ti_painn_train_get_state(self.h, w.ctypes.data_as(dp), m.ctypes.data_as(dp), v.ctypes.data_as(dp), C.byref(na), C.byref(ns)))
-        return dict(w=w, m=m, v=v, n_applied=int(na.value), n_skipped=int(ns.value))
-
-    def load_state(self, w=None, m=None, v=None, n_applied=0, **_):
-        dp = C.POINTER(C.c_double)
-        arrs = []
-        for name, a in (("w", w), ("m", m), ("v", v)):
-            if a is None:
-                arrs.append(None)
-                continue
-            a = np.ascontiguousarray(a, np.float64).reshape(-1)
-            if a.size != self.n_weights:
-                raise ValueError(f"{name} must hold {self.n_weights} entries, got {a.size}")
-            arrs.append(a)
-        ptrs = [None if a is None else a.ctypes.data_as(dp) for a in arrs]
-        _lib.check(_lib.lib().ti_painn_train_set_state(self.h, *ptrs, int(n_applied)))
-
-    def set_lr(self, lr):
-        _lib.check(_lib.lib().ti_painn_train_set_lr(self.h, float(lr)))
-        self.train_desc.lr = float(lr)
-
-    def weights(self):
-        """The fp64 master weights in the canonical layout [n_weights]"""
-        w = np.empty(self.n_weights, np.float64)
-        _lib.check(_lib.lib().ti_painn_train_get_state(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), None, None, None, None))
-        return w
 
     def workspace_bytes(self, B, kind="standard"):
         """ti_painn_train_workspace_bytes: what a call over B molecules needs beside the trainer's state"""
