@@ -1,6 +1,7 @@
 """numpy restatement of the force-field forces and of the Langevin integrator the library computes (include/ti_hip.h ti_obs_ff_forces,
 ti_obs_ff_langevin), written from the header's formulas next to the energy restatement (tests/ff_numpy.py): the oracle of
-tests/test_ff_forces_host.py, tests/test_gpu_ff_forces.py and tests/test_gpu_md.py.  It runs in any float type (fp64, np.longdouble for
+tests/test_ff_forces_host.py, tests/test_gpu_ff_forces.py, tests/test_gpu_md.py and their edge files (tests/test_gpu_ff_edges.py,
+tests/test_gpu_md_edges.py).  It runs in any float type (fp64, np.longdouble for
 the conditioning checks).  Nothing here runs on a GPU or needs the package."""
 import numpy as np
 

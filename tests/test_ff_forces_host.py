@@ -1,6 +1,7 @@
 """Force-field forces and Langevin dynamics on the host: the numpy restatement (tests/ff_forces_numpy.py) against central differences
 of the pinned energy and against itself in np.longdouble on the fixtures the GPU tests compare on, the integrator's restatement
-(energy conservation, chaining, the noise keys, its own fp64 error d64), the masses and constraints of the XML reader, and
+(energy conservation, chaining, the noise keys, its own fp64 error d64), the dense tables of tests/ff_dense_numpy.py (their shape facts,
+their conditioning, the runs beyond 64 components), the masses and constraints of the XML reader, and
 drivers.generate_md against a stub engine.  No GPU."""
 import functools
 import os
@@ -12,6 +13,7 @@ import pytest
 from conftest import GOLDEN, pkg
 import ff_numpy as fn
 import ff_forces_numpy as ffn
+import ff_dense_numpy as fd
 from test_forcefield import gpu_fixtures
 
 XML = os.path.join(GOLDEN, "ff_small.xml")
@@ -161,6 +163,123 @@ def md_d64(name):
     p64, v64, _, _, _ = ffn.langevin(pos, None, T, ids, **kw)
     p80, v80, _, _, _ = ffn.langevin(pos, None, T, ids, ft=LD, **kw)
     return float(max(np.abs(p64 - p80).max(), np.abs(v64 - v80).max()))
+
+
+# ---- 2b. the dense tables and the runs beyond 64 components (tests/test_gpu_ff_edges.py, tests/test_gpu_md_edges.py) -----------------
+def test_the_dense_cases_sit_on_their_edges():
+    """the shape facts each case of ff_dense_numpy.CASES exists for, so that an edit of the builder cannot move one off its edge"""
+    chunks = lambda n: (n + 63) // 64
+    for name, (A, nb, na, nt, hub) in fd.CASES.items():
+        ff, x, to_nm = fd.dense_case(name)
+        assert x.shape == (fd.B_DENSE, A, 3) and x.dtype == np.float32 and fd.B_DENSE == 9, name
+        assert [len(ff[k]) for k in ("bond_idx", "angle_idx", "torsion_idx")] == [nb, na, nt], name
+        assert len(ff["bond_par"]) == nb and len(ff["angle_par"]) == na and ff["torsion_par"].shape == (nt, 3), name
+        for key, slots in (("bond_idx", 2), ("angle_idx", 3), ("torsion_idx", 4)):                 # what ti_obs_ff_set accepts
+            idx = np.asarray(ff[key])
+            assert idx.shape == (len(idx), slots) and (idx >= 0).all() and (idx < A).all(), (name, key)
+            assert all(len(set(row)) == slots for row in idx.tolist()), (name, key)
+        assert set(ff["torsion_par"][:, 0].tolist()) <= {1.0, 2.0, 3.0, 4.0, 5.0, 6.0} and set(ff["torsion_par"][:, 1].tolist()) <= {0.0, np.pi}, name
+        inc = fd.incidence(ff, A)
+        assert inc.shape == (chunks(nb) + chunks(na) + chunks(nt), A) and inc.sum() == 2 * nb + 3 * na + 4 * nt, name
+        again = fd.dense_forcefield(A, nb, na, nt, fd.B_DENSE, seed=0, hub=hub)                    # deterministic
+        assert all(np.array_equal(ff[k], again[0][k]) for k in ff if k != "coulomb") and np.array_equal(x, again[1]), name
+    counts = {name: (c[0], tuple(c[1:4])) for name, c in fd.CASES.items()}
+    assert counts["all_caps"] == (25, (64, 128, 512)) and fd.incidence(fd.dense_case("all_caps")[0], 25).shape[0] == 11
+    assert fd.incidence(fd.dense_case("all_caps")[0], 25).sum() == 2560                           # the incidence bytes at their cap
+    assert counts["angles_2nd"] == (25, (24, 65, 64)) and counts["no_bonds"] == (25, (0, 65, 65)) and counts["tors_only"] == (25, (0, 0, 129))
+    assert counts["pairs_only"] == (24, (0, 0, 0)) and fd.incidence(fd.dense_case("pairs_only")[0], 24).shape == (0, 24)
+    assert fn.pair_table(fd.dense_case("pairs_only")[0], 24)[:, [0, 2]].any()                      # and live pairs
+    assert counts["below_half"] == (21, (63, 128, 129)) and 3 * 21 == 63 and (21 + 1) // 2 % 2 == 1
+    assert counts["three_atoms"] == (3, (2, 3, 0)) and (3 + 1) // 2 == 2
+    assert counts["hub"] == (22, (64, 64, 65)) and fd.CASES["hub"][4] and 3 * 22 == 66
+    ff = fd.dense_case("hub")[0]
+    inc = fd.incidence(ff, 22)
+    assert (ff["bond_idx"][:, 0] == 0).all() and inc[0, 0] == 64 and inc[0].sum() == 128          # atom 0 in all 64 terms of chunk 0
+    assert (inc[0, 12:] == 0).all() and (inc[0] == 0).sum() >= 10                                  # and atoms with no entry in it
+    for name in ("all_caps", "angles_2nd", "no_bonds", "tors_only"):                              # both components of a lane
+        assert 3 * fd.CASES[name][0] > 64
+
+
+@wide
+def test_the_dense_cases_are_well_conditioned():
+    """The restatement on the dense tables against itself in np.longdouble: |F64 - F80| <= 1e-13 S^F and |E64 - E80| <= 1e-13 S_b, the
+    bars of the tree fixtures, with and without T (measured: 2.8e-15 and 1.9e-15 at worst)"""
+    T = np.where(np.arange(fd.B_DENSE) % 2, 1000.0, 300.0).astype(np.float32)
+    worst_f = worst_e = 0.0
+    for name in fd.CASES:
+        ff, x, to_nm = fd.dense_case(name)
+        for temps in (None, T):
+            F64, S, E64 = ffn.forces(x, to_nm, ff, T=temps)
+            F80, _, E80 = ffn.forces(x, to_nm, ff, T=temps, ft=LD)
+            E64n, s64, Sb, _ = fn.energies(x, to_nm, ff, T=temps)
+            E80n, s80, _, _ = fn.energies(x, to_nm, ff, T=temps, ft=LD)
+            Sb = Sb if temps is None else Sb / (fn.R_GAS * temps.astype(np.float64))[:, None]
+            assert np.isfinite(F64).all() and np.isfinite(E64).all() and np.isfinite(E64n).all(), name
+            rf = float((np.abs((F64 - F80).astype(np.float64)) / S[..., None]).max())
+            re = float(max((np.abs((E64 - E80).astype(np.float64)) / Sb.sum(axis=1)).max(),
+                           (np.abs((E64n - E80n).astype(np.float64)) / Sb.sum(axis=1)).max(),
+                           (np.abs((s64 - s80).astype(np.float64)) / np.maximum(Sb, 1.0)).max()))
+            worst_f, worst_e = max(worst_f, rf), max(worst_e, re)
+            assert rf <= 1e-13 and re <= 1e-13, (name, rf, re)
+    print(f"dense tables, fp64 against 80-bit: worst |dF| / S^F = {worst_f:.2e}, |dE| / S_b = {worst_e:.2e}")
+
+
+BIG_IDS = np.array([7, 2 ** 32 + 1, 2 ** 40 + 9, 2 ** 62 + 3, -2], np.int64)
+BIG_SEED = 2 ** 40 + 11
+SMALL_DT = dict(dt=1e-5, friction=1.0, n_steps=16, stride=4, seed=11)
+
+
+@functools.lru_cache(maxsize=None)
+def md_edge_case(name):
+    """(ff, masses, pos [5, A, 3] nm, T [5], ids [5], to_nm, run) of the integrator's runs beyond 64 components and with 64-bit keys:
+    "A25" (the tree fixture, three torsion chunks), "hub" (A = 22, dense), "all_caps" (A = 25, every table at its cap, 4 steps) at
+    dt = 0.01 fs -- the tree geometries carry Lennard-Jones contacts with forces of order 1e8 kJ / (mol nm), under which the
+    restatement itself flies apart at the 0.5 fs of the A4 / A9 runs (A9 with these keys: a coordinate moves by 18 nm in 16 steps) --
+    and "A9_ids": the A9 fixture at the same dt with replica ids and a seed beyond 32 bits."""
+    B = 5
+    T = np.where(np.arange(B) % 2, 1000.0, 300.0).astype(np.float32)
+    ids = np.arange(B, dtype=np.int64) * 3 + 7
+    run = dict(SMALL_DT)
+    if name in ("A25", "A9_ids"):
+        ff, x, to_nm = next((ff, x, to_nm) for n, ff, x, to_nm in fixtures() if n == name.split("_")[0])
+        m = ffn.masses_for(ff)
+        if name == "A9_ids":
+            ids, run = BIG_IDS.copy(), dict(SMALL_DT, seed=BIG_SEED)
+    else:
+        ff, x, to_nm = fd.dense_case(name)
+        m = np.full(x.shape[1], 12.0)
+        if name == "all_caps":
+            run.update(n_steps=4, stride=2)
+    return ff, m, x[:B].astype(np.float64) * to_nm, T, ids, to_nm, run
+
+
+def md_edge_d64(name):
+    """(d64, the restatement's largest displacement of an atom's coordinate over the run, in nm)"""
+    ff, m, pos, T, ids, to_nm, run = md_edge_case(name)
+    kw = dict(ff=ff, masses=m, to_nm=to_nm, draw=True, **run)
+    p64, v64, _, _, _ = ffn.langevin(pos, None, T, ids, **kw)
+    p80, v80, _, _, _ = ffn.langevin(pos, None, T, ids, ft=LD, **kw)
+    one = dict(kw, n_steps=1, stride=0, draw=False)
+    p, v, moved = pos, ffn.draw_velocities(T, ids, m, run["seed"], 0), 0.0
+    for s in range(run["n_steps"]):                            # the same run a step at a time (chaining repeats it bit for bit)
+        p, v, _, _, _ = ffn.langevin(p, v, T, ids, step_offset=s, **one)
+        moved = max(moved, float(np.abs(p - pos).max()))
+    assert np.array_equal(p, p64) and np.array_equal(v, v64)
+    return float(max(np.abs(p64 - p80).max(), np.abs(v64 - v80).max())), moved
+
+
+@wide
+def test_md_edge_runs_stay_bounded_and_conditioned():
+    """What makes the GPU comparison of tests/test_gpu_md_edges.py meaningful: over each run the restatement moves no coordinate by more
+    than 0.5 nm and its own fp64 error d64 is at most 1e-10.  Measured: A25 0.21 nm, d64 8.1e-13; hub 0.013 nm, 1.1e-13; all_caps
+    0.012 nm, 2.3e-13; A9_ids 0.052 nm, 3.8e-13."""
+    for name in ("A25", "hub", "all_caps", "A9_ids"):
+        A = md_edge_case(name)[2].shape[1]
+        assert 3 * A > 64 or name == "A9_ids", name               # components 64 .. 3A - 1, velocity draws up to 6A - 1
+        d, moved = md_edge_d64(name)
+        print(f"{name}: d64 = {d:.3e}, largest displacement {moved:.3e} nm")
+        assert 0 < d <= 1e-10 and moved <= 0.5, (name, d, moved)
+    assert 6 * 25 - 1 == 149
 
 
 # ---- 3. the reader ----------------------------------------------------------------------------------------------------------------

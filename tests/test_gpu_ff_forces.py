@@ -49,13 +49,14 @@ def with_ff(name):
     return eng, x, to_nm, T, r0, r1
 
 
-@pytest.mark.parametrize("name", ["A2", "A4", "A9", "A25"])
-def test_force_parity_and_bitwise_contract(name):
-    torch = pytest.importorskip("torch")
-    eng, x, to_nm, T, ref0, ref1 = with_ff(name)
+def check_forces(name, eng, ff, x, to_nm, T, ref0, ref1, batches=BATCHES, alone=(0, 3, 4, 65, 66)):
+    """The parity and the bitwise contract of ti_obs_ff_forces for one species: x [n, A, 3] with n = the largest of `batches`, the
+    references (F, S^F, E, S_b) without and with T.  Appends the measured ratios to $TI_FF_FORCES_PARITY_OUT."""
+    import torch
     worst_f = worst_e = 0.0
     full = {}
-    for n in BATCHES:
+    n_full = max(batches)
+    for n in batches:
         for temps, ref in ((None, ref0), (T, ref1)):
             tn = None if temps is None else temps[:n]
             F, S, E, Sb = (a[:n] for a in ref)
@@ -79,23 +80,31 @@ def test_force_parity_and_bitwise_contract(name):
             fd, ed = eng.ff_forces(xd, to_nm, td, energy=True)                                       # device memory
             assert fd.is_cuda and fd.dtype == torch.float64 and tuple(fd.shape) == (n, x.shape[1], 3)
             np.testing.assert_array_equal(bits(fd.cpu().numpy()), bits(f)); np.testing.assert_array_equal(bits(ed.cpu().numpy()), bits(e))
-            if n == B_FULL:
+            if n == n_full:
                 full[temps is None] = (f, e)
+    xf = x[:n_full]
     for temps in (None, T):
+        tf = None if temps is None else temps[:n_full]
         f, e = full[temps is None]
-        for b in (0, 3, 4, 65, 66):                                                                  # molecule b alone
-            fb, eb = eng.ff_forces(x[b:b + 1], to_nm, None if temps is None else temps[b:b + 1], energy=True)
+        for b in alone:                                                                              # molecule b alone
+            fb, eb = eng.ff_forces(xf[b:b + 1], to_nm, None if tf is None else tf[b:b + 1], energy=True)
             assert (bits(fb)[0] == bits(f)[b]).all() and bits(eb)[0] == bits(e)[b]
-        fr, er = eng.ff_forces(np.ascontiguousarray(x[::-1]), to_nm, None if temps is None else np.ascontiguousarray(temps[::-1]), energy=True)
+        fr, er = eng.ff_forces(np.ascontiguousarray(xf[::-1]), to_nm, None if tf is None else np.ascontiguousarray(tf[::-1]), energy=True)
         np.testing.assert_array_equal(bits(fr[::-1]), bits(f)); np.testing.assert_array_equal(bits(er[::-1]), bits(e))
-        for n in BATCHES[:2]:                                                                        # the batch size does not enter
-            np.testing.assert_array_equal(bits(eng.ff_forces(x[:n], to_nm, None if temps is None else temps[:n])), bits(f[:n]))
+        for n in [n for n in batches if n < n_full]:                                                 # the batch size does not enter
+            np.testing.assert_array_equal(bits(eng.ff_forces(x[:n], to_nm, None if tf is None else tf[:n])), bits(f[:n]))
     out = os.environ.get("TI_FF_FORCES_PARITY_OUT")
     if out:
         with open(out, "a") as fh:
-            ff = cases()[name][0]
             fh.write(f"{name:4s} bonds {len(ff['bond_idx']):3d} angles {len(ff['angle_idx']):3d} torsions {len(ff['torsion_idx']):3d} "
                      f"pairs {x.shape[1] * (x.shape[1] - 1) // 2:3d}  largest |GPU - numpy| / S^F = {worst_f:.3e}, |dE| / S_b = {worst_e:.3e}\n")
+
+
+@pytest.mark.parametrize("name", ["A2", "A4", "A9", "A25"])
+def test_force_parity_and_bitwise_contract(name):
+    pytest.importorskip("torch")
+    eng, x, to_nm, T, ref0, ref1 = with_ff(name)
+    check_forces(name, eng, cases()[name][0], x, to_nm, T, ref0, ref1)
 
 
 def test_scalar_temperature_and_the_observables_entry():

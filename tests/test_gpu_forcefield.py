@@ -83,12 +83,13 @@ def check(name, e, terms, ref, n):
         np.testing.assert_array_equal(bits(e), bits(((terms[:, 0] + terms[:, 1]) + terms[:, 2]) + terms[:, 3]))
 
 
-@pytest.mark.parametrize("name", ["A2", "A4", "A9", "A25", "A25_t64", "A25_t65"])
-def test_energy_parity_and_bitwise_contract(name):
-    torch = pytest.importorskip("torch")
-    eng, x, to_nm, T, ref0, ref1 = with_ff(name)
+def check_energies(name, eng, x, to_nm, T, ref0, ref1, batches=BATCHES, alone=(0, 3, 4, 65, 66)):
+    """The parity and the bitwise contract of ti_obs_ff_energy for one species: x [n, A, 3] with n = the largest of `batches`, the
+    references (E, sums, S) without and with T"""
+    import torch
     full = {}
-    for n in BATCHES:
+    n_full = max(batches)
+    for n in batches:
         for temps, ref in ((None, ref0), (T, ref1)):
             tn = None if temps is None else temps[:n]
             e, terms = eng.ff_energy(x[:n], to_nm, tn, terms=True)
@@ -102,18 +103,27 @@ def test_energy_parity_and_bitwise_contract(name):
             assert ed.is_cuda and ed.dtype == torch.float64 and tuple(termsd.shape) == (n, 4)
             np.testing.assert_array_equal(bits(ed.cpu().numpy()), bits(e)); np.testing.assert_array_equal(bits(termsd.cpu().numpy()), bits(terms))
             np.testing.assert_array_equal(bits(eng.ff_energy(xd, to_nm, td).cpu().numpy()), bits(e))
-            if n == B_FULL:
+            if n == n_full:
                 full[temps is None] = (e, terms)
+    xf = x[:n_full]
     for temps in (None, T):
+        tf = None if temps is None else temps[:n_full]
         e, terms = full[temps is None]
-        for b in (0, 3, 4, 65, 66):                                                                # molecule b alone
-            eb, tb = eng.ff_energy(x[b:b + 1], to_nm, None if temps is None else temps[b:b + 1], terms=True)
+        for b in alone:                                                                            # molecule b alone
+            eb, tb = eng.ff_energy(xf[b:b + 1], to_nm, None if tf is None else tf[b:b + 1], terms=True)
             assert bits(eb)[0] == bits(e)[b] and (bits(tb)[0] == bits(terms)[b]).all()
-        er, tr = eng.ff_energy(np.ascontiguousarray(x[::-1]), to_nm, None if temps is None else np.ascontiguousarray(temps[::-1]), terms=True)
+        er, tr = eng.ff_energy(np.ascontiguousarray(xf[::-1]), to_nm, None if tf is None else np.ascontiguousarray(tf[::-1]), terms=True)
         np.testing.assert_array_equal(bits(er[::-1]), bits(e)); np.testing.assert_array_equal(bits(tr[::-1]), bits(terms))
-        for n in BATCHES[:2]:                                                                      # the batch size does not enter
-            np.testing.assert_array_equal(bits(eng.ff_energy(x[:n], to_nm, None if temps is None else temps[:n])), bits(e[:n]))
+        for n in [n for n in batches if n < n_full]:                                               # the batch size does not enter
+            np.testing.assert_array_equal(bits(eng.ff_energy(x[:n], to_nm, None if tf is None else tf[:n])), bits(e[:n]))
     print(f"{name}: largest |GPU - numpy| / S_b = {RATIOS[name]:.3e} (bound {TOL:.0e})")
+
+
+@pytest.mark.parametrize("name", ["A2", "A4", "A9", "A25", "A25_t64", "A25_t65"])
+def test_energy_parity_and_bitwise_contract(name):
+    pytest.importorskip("torch")
+    eng, x, to_nm, T, ref0, ref1 = with_ff(name)
+    check_energies(name, eng, x, to_nm, T, ref0, ref1)
     out = os.environ.get("TI_FF_PARITY_OUT")
     if out:
         with open(out, "a") as f:

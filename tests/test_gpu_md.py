@@ -56,21 +56,21 @@ RUN = dict(dt=5e-4, friction=1.0, n_steps=16, stride=4, seed=11)
 
 
 # ---- the trajectory against the restatement ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["A4", "A9"])
-def test_trajectory_parity(name):
-    if np.finfo(LD).eps >= np.finfo(np.float64).eps:
-        pytest.skip("np.longdouble is no wider than float64 here: d64 cannot be formed")
-    eng, ff, m, pos, T, ids, to_nm = case(name)
-    kw = dict(ff=ff, masses=m, to_nm=to_nm, draw=True, **RUN)
+def check_trajectory(name, eng, ff, m, pos, T, ids, to_nm, run=RUN):
+    """One run with drawn velocities against the restatement: the drawn velocities exactly, the state within 100 d64, the frames and
+    their energies within the bounds derived below.  Appends the measured ratio to $TI_MD_PARITY_OUT; returns it."""
+    B, n_frames = len(pos), run["n_steps"] // run["stride"]
+    kw = dict(ff=ff, masses=m, to_nm=to_nm, draw=True, **run)
     p64, v64, f64, e64, k64 = ffn.langevin(pos, None, T, ids, **kw)
     p80, v80, _, _, _ = ffn.langevin(pos, None, T, ids, ft=LD, **kw)
     d64 = float(max(np.abs(p64 - p80).max(), np.abs(v64 - v80).max()))
     # the drawn velocities: sqrt(R T / m) times the Philox normal, correctly rounded operations only -- exactly the restatement's
-    _, v0, _, _, _ = eng.langevin(pos, None, T, RUN["dt"], RUN["friction"], 0, seed=RUN["seed"], ids=ids, to_nm=to_nm, draw_velocities=True)
-    np.testing.assert_array_equal(bits(v0), bits(ffn.draw_velocities(T, ids, m, RUN["seed"], 0)))
-    p, v, fr, ep, ek = eng.langevin(pos, None, T, RUN["dt"], RUN["friction"], RUN["n_steps"], stride=RUN["stride"], seed=RUN["seed"], ids=ids,
+    _, v0, _, _, _ = eng.langevin(pos, None, T, run["dt"], run["friction"], 0, seed=run["seed"], ids=ids, to_nm=to_nm, draw_velocities=True)
+    np.testing.assert_array_equal(bits(v0), bits(ffn.draw_velocities(T, ids, m, run["seed"], 0)))
+    p, v, fr, ep, ek = eng.langevin(pos, None, T, run["dt"], run["friction"], run["n_steps"], stride=run["stride"], seed=run["seed"], ids=ids,
                                     to_nm=to_nm, draw_velocities=True)
-    assert fr.shape == (5, 4, pos.shape[1], 3) and fr.dtype == np.float32 and ep.shape == ek.shape == (5, 4)
+    assert fr.shape == (B, n_frames, pos.shape[1], 3) and fr.dtype == np.float32 and ep.shape == ek.shape == (B, n_frames)
+    assert np.isfinite(p).all() and np.isfinite(v).all()
     dp, dv = float(np.abs(p - p64).max()), float(np.abs(v - v64).max())
     # a frame is the fp64 value rounded once to fp32: within the state's bar in model units, plus one fp32 rounding step of the value
     tol_f = 100 * d64 / to_nm + np.spacing(np.abs(f64))
@@ -79,18 +79,27 @@ def test_trajectory_parity(name):
     out = os.environ.get("TI_MD_PARITY_OUT")
     if out:
         with open(out, "a") as fh:
-            fh.write(f"{name}: B = 5, 16 steps, dt = 0.5 fs, friction = 1 / ps: d64 = {d64:.3e}, |dpos| = {dp:.3e} nm, |dvel| = {dv:.3e} nm/ps, "
-                     f"largest ratio to d64 = {max(dp, dv) / d64:.2f} (bar 100)\n")
+            fh.write(f"{name}: B = {B}, {run['n_steps']} steps, dt = {run['dt'] * 1e3:g} fs, friction = {run['friction']:g} / ps: d64 = {d64:.3e}, "
+                     f"|dpos| = {dp:.3e} nm, |dvel| = {dv:.3e} nm/ps, largest ratio to d64 = {max(dp, dv) / d64:.2f} (bar 100)\n")
     assert max(dp, dv) <= 100 * d64, (name, dp, dv, d64)
     assert df <= 1.0, (name, df)
     # the frame energies.  Potential: the energy tests' bar plus what 100 d64 of position error moves it, |dE| <= sum |F| |dx|, with
     # sum_a S^F_a >= sum |F|.  Kinetic: |dK| <= sum m |v| |dv| <= sqrt(3A m_max 2K) 100 d64, plus the arithmetic's 1e-11 (1 + K).
-    for k in range(4):
+    for k in range(n_frames):
         _, SF, _ = ffn.forces(f64[:, k], to_nm, ff)
         Sb = fn.energies(f64[:, k], to_nm, ff)[2].sum(axis=1)
         assert (np.abs(ep[:, k] - e64[:, k]) <= 1e-11 * Sb + 100 * d64 * np.sqrt(3.0) * SF.sum(axis=1)).all(), (name, k)
     assert (np.abs(ek - k64) <= 1e-11 * (1 + k64) + 100 * d64 * np.sqrt(3 * len(m) * m.max() * 2 * k64)).all(), name
     assert np.abs(fr.astype(np.float64).mean(axis=2)).max() <= 2e-7 * np.abs(fr).max()          # centred to fp32 round-off
+    return max(dp, dv) / d64
+
+
+@pytest.mark.parametrize("name", ["A4", "A9"])
+def test_trajectory_parity(name):
+    if np.finfo(LD).eps >= np.finfo(np.float64).eps:
+        pytest.skip("np.longdouble is no wider than float64 here: d64 cannot be formed")
+    eng, ff, m, pos, T, ids, to_nm = case(name)
+    check_trajectory(name, eng, ff, m, pos, T, ids, to_nm)
 
 
 # ---- bits ------------------------------------------------------------------------------------------------------------------------
@@ -106,41 +115,50 @@ def same(a, b):
         np.testing.assert_array_equal(bits(u), bits(w))
 
 
-def test_bitwise_contract():
-    torch = pytest.importorskip("torch")
-    eng, ff, m, pos, T, ids, to_nm = case("A9")
-    ref = run(eng, pos, None, T, ids, to_nm)
+def check_bits(eng, pos, T, ids, to_nm, strides=(4, 5, 3, 16, 17), **base):
+    """the bitwise contract of one 16-step run (RUN with `base` over it): repeat, device memory, alone, reversed, ids NULL, chained,
+    launch cut, strides"""
+    import torch
+    go = lambda *a, **over: run(eng, *a, **dict(base, **over))
+    ref = go(pos, None, T, ids, to_nm)
     assert all(np.isfinite(a).all() for a in ref)
-    same(run(eng, pos, None, T, ids, to_nm), ref)                                                # the same call twice
-    dev = run(eng, torch.from_numpy(pos).cuda(), None, torch.from_numpy(T).cuda(), torch.from_numpy(ids).cuda(), to_nm)
+    same(go(pos, None, T, ids, to_nm), ref)                                                      # the same call twice
+    dev = go(torch.from_numpy(pos).cuda(), None, torch.from_numpy(T).cuda(), torch.from_numpy(ids).cuda(), to_nm)
     assert all(a.is_cuda for a in dev) and dev[0].dtype == torch.float64 and dev[2].dtype == torch.float32
     same([a.cpu().numpy() for a in dev], ref)                                                    # device memory
     for b in (0, 3, 4):                                                                          # a replica alone, with its id
-        same(run(eng, pos[b:b + 1], None, T[b:b + 1], ids[b:b + 1], to_nm), [a[b:b + 1] for a in ref])
-    rev = run(eng, pos[::-1].copy(), None, T[::-1].copy(), ids[::-1].copy(), to_nm)              # reversed batch, reversed ids
+        same(go(pos[b:b + 1], None, T[b:b + 1], ids[b:b + 1], to_nm), [a[b:b + 1] for a in ref])
+    rev = go(pos[::-1].copy(), None, T[::-1].copy(), ids[::-1].copy(), to_nm)                    # reversed batch, reversed ids
     same([a[::-1] for a in rev], ref)
-    off = run(eng, pos, None, T, None, to_nm, traj_offset=7)                                     # ids NULL: traj_offset + b
+    off = go(pos, None, T, None, to_nm, traj_offset=int(ids[0]))                                 # ids NULL: traj_offset + b
     same([a[:1] for a in off], [a[:1] for a in ref])
     # 16 steps against 8 + 8 chained with step_offset (given velocities, so that only the first call draws), frames included
-    p0, v0, _, _, _ = run(eng, pos, None, T, ids, to_nm, n_steps=0, stride=0)
-    whole = run(eng, p0, v0, T, ids, to_nm, step_offset=100)
-    a = run(eng, p0, v0, T, ids, to_nm, n_steps=8, step_offset=100)
-    b = run(eng, a[0], a[1], T, ids, to_nm, n_steps=8, step_offset=108)
+    p0, v0, _, _, _ = go(pos, None, T, ids, to_nm, n_steps=0, stride=0)
+    whole = go(p0, v0, T, ids, to_nm, step_offset=100)
+    a = go(p0, v0, T, ids, to_nm, n_steps=8, step_offset=100)
+    b = go(a[0], a[1], T, ids, to_nm, n_steps=8, step_offset=108)
     same(b[:2], whole[:2])
     same([np.concatenate([u, w], axis=1) for u, w in zip(a[2:], b[2:])], whole[2:])
-    same(run(eng, pos, None, T, ids, to_nm, steps_per_launch=5), ref)                            # launches of 5, 5, 5, 1
-    same(run(eng, pos, None, T, ids, to_nm, steps_per_launch=16), ref)
+    same(go(pos, None, T, ids, to_nm, steps_per_launch=5), ref)                                  # launches of 5, 5, 5, 1
+    same(go(pos, None, T, ids, to_nm, steps_per_launch=16), ref)
     # strides that do not divide n_steps: the frames are those of the stride-1 run at the same steps
-    every = run(eng, pos, None, T, ids, to_nm, stride=1)
+    every = go(pos, None, T, ids, to_nm, stride=1)
     same(every[:2], ref[:2])
-    for stride in (4, 5, 3, 16, 17):
-        got = run(eng, pos, None, T, ids, to_nm, stride=stride, steps_per_launch=7)
+    for stride in strides:
+        got = go(pos, None, T, ids, to_nm, stride=stride, steps_per_launch=7)
         n = 16 // stride
         if n == 0:
             assert got[2] is None and got[3] is None
             continue
         assert got[2].shape[1] == n
         same(got[2:], [a[:, stride - 1::stride][:, :n] for a in every[2:]])
+
+
+def test_bitwise_contract():
+    pytest.importorskip("torch")
+    eng, ff, m, pos, T, ids, to_nm = case("A9")
+    assert int(ids[0]) == 7
+    check_bits(eng, pos, T, ids, to_nm)
 
 
 # ---- NVE -------------------------------------------------------------------------------------------------------------------------
