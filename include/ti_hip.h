@@ -713,6 +713,16 @@ int ti_painn_debug_phi0_path(ti_handle* h, int32_t* n_classes);
  * leading ones -- are 4 x 4 tiles; the rest are general blocks of 16 unrelated pairs (n_tile == nblk: none, e.g. with TI_PAIR_PACKED=0
  * in the environment when the handle was created).  Returns 1, or 0 when the handle has no pair template (nothing is written). */
 int ti_painn_debug_pair_blocks(ti_handle* h, int32_t* G, int32_t* nblk, int32_t* n_tile);
+/* Seeded accumulators.  A packed pair template is seeded when its general rows name every atom of every molecule of a
+ * group exactly once (the complete graph on 18 atoms: the 36 twin pairs of 4 molecules).  The message layers of an evaluation in the
+ * pair layout then launch the general blocks FIRST -- each row stores its two contributions, every atom's first of the layer, no
+ * atomic and no read -- and the tile blocks after them, which only add.  Every other evaluation keeps the order of before (tiles whose
+ * first touch replaces the accumulator, then general rows that add): f32 handles, an edge mask or mixed species in force (a mask that
+ * removes no edge of any molecule leaves the template's rows as they are and counts as none here), the directed layouts, a template
+ * that is not seeded, or TI_PAIR_SEEDED=0 in the environment when the handle is created.
+ * Returns which order the LAST drift evaluation of the handle took (a rollout: its last evaluation): 1 = seeded, 0 = the order of
+ * before, -1 = no evaluation yet.  *template_seeded (may be NULL): 1 when the handle's pair template is seeded, else 0. */
+int ti_painn_debug_pair_seeded(ti_handle* h, int32_t* template_seeded);
 /* Device self-test of the MFMA operand/accumulator lane maps the kernels rely on, of both fp32 -> (hi, lo) fp16 operand splits
  * (the 8-instruction forms of formats (a) and (b) against the plain arithmetic, bit for bit, fp16-subnormal residuals included),
  * and of the fp16 matrix instruction keeping subnormal inputs. */

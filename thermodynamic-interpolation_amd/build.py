@@ -17,6 +17,9 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api
            "painn_pair_mask_nb1.hip", "painn_pair_mask_nb2.hip", "painn_pair_mask_nb4.hip",
            # the pair kernel's builds for the general blocks of a packed template (pair_template.hpp), units of their own like the above
            "painn_pair_gen_nb1.hip", "painn_pair_gen_nb2.hip", "painn_pair_gen_nb4.hip",
+           # the seeded twins of the unmasked split-path builds, tile and general (painn_pair_kernel.hpp: SEEDED): units of their own
+           # again, so that every older code object stays as it was and the widths compile in parallel
+           "painn_pair_seed_nb1.hip", "painn_pair_seed_nb2.hip", "painn_pair_seed_nb4.hip",
            # ragged twins of the adaptive-solver kernels (mixed-species batches): a unit of their own, ode_kernels.hip's code stays put
            "ode_ragged_kernels.hip",
            # observables (ti_obs_*): collective variables, importance weights, weighted histograms

@@ -252,6 +252,13 @@ int ti_painn_debug_pair_blocks(ti_handle* h, int32_t* G, int32_t* nblk, int32_t*
     return 1;
 }
 
+int ti_painn_debug_pair_seeded(ti_handle* h, int32_t* template_seeded)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (template_seeded) *template_seeded = h->has_pair && h->pair_seeded ? 1 : 0;
+    return h->seeded_last;
+}
+
 int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)
 {
     if (!h || h->kind != 0 || B <= 0) return fail(TI_E_ARG, "not a painn handle / B");

@@ -212,6 +212,13 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
         Timed tm(h, TI_KERNEL_PAINN_EMBED);
         HIP_CHECK(launch_phi0_table(NB, L == 1, p, st));
     }
+    // seeded accumulators: the pair layout on a seeded template, and nothing in force that can take a general row away from its two
+    // atoms or that the seeded builds do not take (an edge mask or mixed species; f32 handles have no general blocks at all).  A mask
+    // that removes nothing (emask_full) leaves every row word the template's: the message launches are then those of an unmasked batch,
+    // so that the two agree bit for bit as they always have (the masked twins add in the first-touch order)
+    const bool mask_off = mrows && h->emask_full;
+    const bool seeded = h->active == 2 && h->pair_seeded_on && h->n_tile > 0 && h->n_tile < h->nblk && pair_general_build_exists(prec) && (!mrows || mask_off) && !nat && L > 0;
+    h->seeded_last = seeded ? 1 : 0;
     h->last_B = B;
     if (h->tap == 0) return;
     for (int l = 0; l < L; ++l) {
@@ -250,7 +257,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
                 p.stream = h->S(h->st_edge1[l]); p.nch = h->st_edge1[l].nch; p.vecs = h->edge_vecs1.p + (size_t)l * 21 * F;
                 for (int i = 0; i < 6; ++i) p.wscale[i] = h->edge_scale[(size_t)l * 6 + i];
             }
-            if (mrows) p.rows = mrows;
+            if (mrows && !seeded) p.rows = mrows;      // (seeded under a mask that removes nothing: the template's own row words)
             Timed tm(h, TI_KERNEL_PAINN_EDGE);
 #ifdef TI_STAMPS
             if (l == 2) p.stamps = stamps_arm(groups, st);
@@ -261,7 +268,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
                 p.phi0_tab = h->phi0_tab.p; p.cls = h->phi0_cls.p;
             }
             if (h->active == 2) {
-                HIP_CHECK(launch_pair(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr, on_table));
+                HIP_CHECK(launch_pair(NB, l == 0, l == L - 1, prec, p, st, mrows != nullptr && !seeded, on_table, seeded));
 #ifdef TI_STAMPS
                 stamps_dump(h, p.stamps, groups, st);
 #endif
@@ -403,7 +410,10 @@ int set_graph_state(ti_handle* h, std::vector<uint32_t>& m, std::vector<int32_t>
             }
     if (h->emask_B == B && m == h->emask && natoms == h->natoms && ptype == h->ptype) return TI_OK;      // the same state again (a mirror class sets it before every call)
     HIP_CHECK(hipStreamSynchronize(h->stream));                   // no launch in flight still reads the row words about to be replaced
-    h->emask.swap(m); h->emask_B = B; h->emask_sym = sym;
+    bool full = ptype.empty() && !ragged;                        // nothing removed: every template edge of every molecule is present
+    for (long long b = 0; b < B && full; ++b)
+        for (int d = 0; d < A && full; ++d) full = (m[(size_t)b * A + d] & in_tpl[d]) == in_tpl[d];
+    h->emask.swap(m); h->emask_B = B; h->emask_sym = sym; h->emask_full = full;
     h->natoms.swap(natoms); h->ptype.swap(ptype); h->ragged = ragged; h->n_real = n_real;
     if (ragged) h->natoms_dev.upload(h->natoms); else h->natoms_dev.release();
     for (int t = 0; t < 3; ++t) h->mrows_ok[t] = false;
@@ -412,7 +422,7 @@ int set_graph_state(ti_handle* h, std::vector<uint32_t>& m, std::vector<int32_t>
 
 void clear_graph_state(ti_handle* h)
 {
-    h->emask_B = 0; h->emask_sym = true; h->emask.clear(); h->natoms.clear(); h->ptype.clear(); h->ragged = false; h->n_real = 0;
+    h->emask_B = 0; h->emask_sym = true; h->emask_full = false; h->emask.clear(); h->natoms.clear(); h->ptype.clear(); h->ragged = false; h->n_real = 0;
     for (int t = 0; t < 3; ++t) { h->mrows_ok[t] = false; h->mrows[t].release(); }
 }
 

@@ -497,7 +497,11 @@ hipError_t configure_painn_kernels(int NB)
         hipError_t e = configure_edge_unit<nb, MASK>();
         if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) {
             if (e == hipSuccess) e = configure_pair_unit<nb, MASK, false>();
-            if constexpr (!MASK) { if (e == hipSuccess) e = configure_pair_unit<nb, false, true>(); }
+            if constexpr (!MASK) {
+                if (e == hipSuccess) e = configure_pair_unit<nb, false, true>();
+                if (e == hipSuccess) e = configure_pair_unit<nb, false, false, true>();
+                if (e == hipSuccess) e = configure_pair_unit<nb, false, true, true>();
+            }
         }
         return e;
     });
@@ -517,11 +521,18 @@ hipError_t launch_edge(int NB, bool first, bool last, int prec, const EdgeParams
 {
     return with_message_units(NB, masked, [&](auto bc, auto mc) { return launch_edge_unit<decltype(bc)::value, decltype(mc)::value>(first, last, prec, p, st); });
 }
-hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked, bool table)
+hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked, bool table, bool seeded)
 {
+    if (seeded && (masked || !pair_general_build_exists(prec) || p.n_tile <= 0 || p.n_tile >= p.nblk)) return hipErrorInvalidValue;
     return with_message_units(NB, masked, [&](auto bc, auto mc) {
         constexpr int nb = decltype(bc)::value;
         if constexpr (pair_build_exists(nb, 4, TI_PREC_F32)) {
+            if (seeded) {          // the general blocks first: they store; the kernel boundary orders the tile launch's adds behind them
+                EdgeParams g = p;
+                g.row_stride = 0;
+                hipError_t e = launch_pair_unit<nb, false, true, true>(first, last, prec, g, st, table);
+                return e == hipSuccess ? launch_pair_unit<nb, false, false, true>(first, last, prec, p, st, table) : e;
+            }
             hipError_t e = p.n_tile > 0 ? launch_pair_unit<nb, decltype(mc)::value, false>(first, last, prec, p, st, table) : hipSuccess;
             if (e == hipSuccess && p.n_tile < p.nblk) {      // the general blocks: one kernel for shared and per-group row words
                 EdgeParams g = p;

@@ -250,6 +250,9 @@ bool build_pair_template(ti_handle* h, const int32_t* src, const int32_t* dst, c
     T.G = pt.G; T.P = 1; T.nblk = pt.nblk; T.n_tile = pt.n_tile; T.max_slots = 4;
     T.rows.upload(pt.rows); T.slotnode.upload(pt.slotnode); T.rows_h = pt.rows;
     h->pair_pos = pt.pair_pos; h->pair_fill = pt.fill;
+    // triage switch, read like TI_PAIR_PACKED: TI_PAIR_SEEDED=0 at creation keeps the first-touch order on a seeded template
+    h->pair_seeded = pt.seeded; h->pair_seeded_on = pt.seeded;
+    if (const char* z = std::getenv("TI_PAIR_SEEDED")) if (z[0] == '0') h->pair_seeded_on = false;
     return true;
 }
 

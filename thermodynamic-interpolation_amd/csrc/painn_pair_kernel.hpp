@@ -25,7 +25,9 @@
 // at best (pair_template.hpp: build_pair_template; 85 % for 18 atoms), and every atom's accumulators are touched from ~ (A - 1) / 4
 // blocks.  The packed template (build_pair_template_packed) therefore ends with GENERAL blocks -- 16 unrelated pairs, walked by the
 // GENERAL builds below in a launch of their own right after the tile launch -- and reaches 98 % for 18 atoms (36 full tiles and 3
-// general blocks per group of 4 molecules instead of 45 tiles).
+// general blocks per group of 4 molecules instead of 45 tiles).  Where that template is SEEDED (its general rows name every atom of a
+// group exactly once: the twin rows of 18 atoms) the order turns round for plain split-path batches: the general launch first, storing
+// every atom's first contribution of the layer, then tile blocks that only add (the SEEDED builds below).
 // Results are deterministic (one wave owns a group of molecules, fixed order); they differ from the directed kernel's by the order
 // of the per-atom sums only.
 #pragma once
@@ -54,9 +56,11 @@ template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = fals
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS p.rows
 #define TI_PAIR_GENERAL false
+#define TI_PAIR_SEEDED false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
+#undef TI_PAIR_SEEDED
 
 // Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words PER group (painn_pack.hip: masked_rows), in which a pair absent
 // from its molecule is invalid -- zeroed through the shared w factor, like a pair that does not exist.  Both directions share that
@@ -66,9 +70,11 @@ template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = fals
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_mask_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS (p.rows + (size_t)gi * p.nblk * 16)
 #define TI_PAIR_GENERAL false
+#define TI_PAIR_SEEDED false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
+#undef TI_PAIR_SEEDED
 
 // The general blocks [p.n_tile, p.nblk) of a packed template (pair_template.hpp), every row adding to its own two atoms; the two kernels
 // above walk the tile blocks [0, p.n_tile).  Same body, same weight stream (cyclic per row block), same e / enc / geo rows.  One kernel
@@ -77,29 +83,59 @@ template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = fals
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_general_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS (p.rows + (size_t)gi * p.row_stride)
 #define TI_PAIR_GENERAL true
+#define TI_PAIR_SEEDED false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
+#undef TI_PAIR_SEEDED
+
+// The SEEDED builds (painn_pair_kernel_body.inc): a seeded template (pair_template.hpp) on the split path, plain batches -- no edge mask,
+// one species.  The general launch of a layer runs FIRST and stores each row's two contributions, every atom's first of the layer; the
+// tile launch follows on the same stream and only adds.  Two launches, never one: a store followed by an atomic to the same address
+// from one wave inside one kernel has no ordering (the atomics execute at the memory side); the kernel boundary orders them.
+// Instantiated in painn_pair_seed_nb*.hip.
+template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
+__global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_seeded_kernel(const EdgeParams p)
+#define TI_PAIR_ROWS p.rows
+#define TI_PAIR_GENERAL false
+#define TI_PAIR_SEEDED true
+#include "painn_pair_kernel_body.inc"
+#undef TI_PAIR_ROWS
+#undef TI_PAIR_GENERAL
+#undef TI_PAIR_SEEDED
+
+template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
+__global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_general_seeded_kernel(const EdgeParams p)
+#define TI_PAIR_ROWS p.rows
+#define TI_PAIR_GENERAL true
+#define TI_PAIR_SEEDED true
+#include "painn_pair_kernel_body.inc"
+#undef TI_PAIR_ROWS
+#undef TI_PAIR_GENERAL
+#undef TI_PAIR_SEEDED
 
 // The visitor of the family: f(kernel, waves, LDS bytes) for every build of width NB that the values select (EVERY: all of them,
 // dispatch.hpp), until one returns an error.  MASK: the masked twins (painn_pair_mask_kernel).  GENERAL: the builds of the general
-// blocks (painn_pair_general_kernel, one per unmasked tile build of the split path; MASK is then false).  hipErrorInvalidValue: no such
-// build.
-template <int NB, bool MASK, bool GENERAL, class F>
+// blocks (painn_pair_general_kernel, one per unmasked tile build of the split path; MASK is then false).  SEEDED: the seeded twins of
+// the unmasked split-path builds, tile and general.  hipErrorInvalidValue: no such build.
+template <int NB, bool MASK, bool GENERAL, bool SEEDED, class F>
 static hipError_t with_pair_builds(int waves, int prec, int pos, F&& f)
 {
     static_assert(!(MASK && GENERAL), "the general kernel takes masked row words through p.row_stride");
+    static_assert(!(MASK && SEEDED), "an edge mask can take a general row away from its atoms: masked batches are never seeded");
     hipError_t e = hipSuccess;
     bool any = false;
     dispatch_int<4, 8>(waves, [&](auto wc) { dispatch_int<0, 1>(prec, [&](auto pc) {
         constexpr int WAVES = decltype(wc)::value, PREC = decltype(pc)::value;
-        if constexpr (pair_build_exists(NB, WAVES, PREC) && (!GENERAL || pair_general_build_exists(PREC)))
+        if constexpr (pair_build_exists(NB, WAVES, PREC) && (!(GENERAL || SEEDED) || pair_general_build_exists(PREC)))
             dispatch_int<POS_MIDDLE, POS_FIRST, POS_LAST, POS_ONLY, POS_FIRST_TABLE, POS_ONLY_TABLE>(pos, [&](auto oc) {
                 constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0, TABLE = (decltype(oc)::value & 4) != 0;
                 if constexpr (!TABLE || pair_table_build_exists(NB, PREC, MASK)) {
                     any = true;
                     if (e != hipSuccess) return;
-                    if constexpr (GENERAL) e = f(painn_pair_general_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE, true));
+                    if constexpr (GENERAL && SEEDED) e = f(painn_pair_general_seeded_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE, true));
+                    else if constexpr (SEEDED) e = f(painn_pair_seeded_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE));
+                    else if constexpr (GENERAL) e = f(painn_pair_general_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE, true));
                     else if constexpr (MASK) e = f(painn_pair_mask_kernel<2 * NB, FIRST, LAST, PREC, WAVES>, WAVES, pair_lds_bytes(NB, WAVES, PREC));
                     else e = f(painn_pair_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE));
                 }
@@ -109,20 +145,21 @@ static hipError_t with_pair_builds(int waves, int prec, int pos, F&& f)
 }
 
 // one feature width (ti_internal.hpp): configure every build / launch the one the call needs
-template <int NB, bool MASK, bool GENERAL>
+template <int NB, bool MASK, bool GENERAL, bool SEEDED>
 hipError_t configure_pair_unit()
 {
-    return with_pair_builds<NB, MASK, GENERAL>(EVERY, EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
+    return with_pair_builds<NB, MASK, GENERAL, SEEDED>(EVERY, EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
 }
-// (GENERAL: the launch over the general blocks, the same grid right after the tile launch on the same stream)
-template <int NB, bool MASK, bool GENERAL>
+// (GENERAL: the launch over the general blocks, the same grid on the same stream: right after the tile launch, or with SEEDED right
+// before it)
+template <int NB, bool MASK, bool GENERAL, bool SEEDED>
 hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table)
 {
     if (table && !first) return hipErrorInvalidValue;
-    if (p.n_tile < 0 || p.n_tile > p.nblk || (GENERAL && p.n_tile == p.nblk)) return hipErrorInvalidValue;
+    if (p.n_tile < 0 || p.n_tile > p.nblk || ((GENERAL || SEEDED) && p.n_tile == p.nblk)) return hipErrorInvalidValue;
     // 8-wave workgroups (one weight stream per CU) for the split path once every CU gets a workgroup
     const bool wide = prec == 1 && p.n_groups >= 2048;
-    return with_pair_builds<NB, MASK, GENERAL>(wide ? 8 : 4, prec, layer_pos(first, last) | (table ? POS_TABLE : 0), [&](auto kernel, int waves, size_t lds) {
+    return with_pair_builds<NB, MASK, GENERAL, SEEDED>(wide ? 8 : 4, prec, layer_pos(first, last) | (table ? POS_TABLE : 0), [&](auto kernel, int waves, size_t lds) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)((p.n_groups + waves - 1) / waves)), dim3(64 * waves), lds, st, p);      // one wave = one group of G molecules
         return hipGetLastError();
     });

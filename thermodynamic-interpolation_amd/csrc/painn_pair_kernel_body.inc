@@ -4,11 +4,17 @@
 // GENERAL: the build that walks the template's general blocks [n_tile, nblk) -- 16 unrelated pairs, no slots -- after the tile build
 // has walked [0, n_tile) (pair_template.hpp).  Everything up to the output products is per row and shared; the output stage then adds
 // every row's contributions of both directions to the row's own two atoms instead of forming slot sums.
+// TI_PAIR_SEEDED: the seeded twins (painn_pair_seeded_kernel, painn_pair_general_seeded_kernel): general rows store, tile slots only add.
 {
     static_assert(PREC == 0 || PREC == 1, "the fp16 storage mode keeps the directed message kernel");
     static_assert(!TABLE || (FIRST && PREC == 1), "the phi table serves layer 0 of the split path");
     constexpr bool GENERAL = TI_PAIR_GENERAL;
     static_assert(!GENERAL || pair_general_build_exists(PREC), "general blocks: the split path, which folds the cross term (the f32 path keeps the tile-only template)");
+    // SEEDED (a seeded template, pair_template.hpp; plain split-path batches): the general launch runs first and every valid general row
+    // is its two atoms' first contribution of the layer -- GENERAL && SEEDED writes dsacc / dvacc with plain stores, no atomic and no
+    // read; the tile launch after it (!GENERAL && SEEDED) finds every accumulator row seeded and only adds: no first touch
+    constexpr bool SEEDED = TI_PAIR_SEEDED;
+    static_assert(!SEEDED || pair_general_build_exists(PREC), "seeded accumulators: the split path, whose templates have general blocks");
     constexpr int F = 16 * NBK, NB = (F + 31) / 32, T = 64 * WAVES, CH4 = edge_chunk4(NB, false);
     using A16 = r16::Act<NBK>;
     constexpr bool ONE = edge_one_chain(PREC);
@@ -202,7 +208,7 @@
         const int snJ = p.slotnode[blk * 16 + 4 + q], snI = p.slotnode[blk * 16 + q];
         const bool haveA = group_ok && snJ >= 0 && gi * p.G + slot_mol(snJ) < p.B;
         const bool haveB = group_ok && snI >= 0 && gi * p.G + slot_mol(snI) < p.B;
-        const bool qfA = (snJ & SLOT_FIRST_TOUCH) != 0, qfB = (snI & SLOT_FIRST_TOUCH) != 0;
+        const bool qfA = !SEEDED && (snJ & SLOT_FIRST_TOUCH) != 0, qfB = !SEEDED && (snI & SLOT_FIRST_TOUCH) != 0;      // SEEDED: every put adds
         // their nodes inside the group; touched only where haveA / haveB hold
         const unsigned lnA = (unsigned)slot_mol(snJ) * (unsigned)p.A + (unsigned)(snJ & 255), lnB = (unsigned)slot_mol(snI) * (unsigned)p.A + (unsigned)(snI & 255);
         // the accumulator rows of a node, laid out as three arrays (ds [F], dv [3F], c [3F] per node); off: ds 0.., dv F.., c 4F..
@@ -221,15 +227,20 @@
             }
         }
         // both directions of the lane's four rows: direction A's value goes to the row's J atom, direction B's to its I atom, plain adds
-        // (a general row never carries first touch: both atoms own a slot of an earlier tile block)
+        // (a general row never carries first touch: both atoms own a slot of an earlier tile block).  SEEDED: plain stores -- the row is
+        // the only one of this launch that names either atom, and the tile launch that adds to them starts after this one has ended
+        auto row_out = [&](float* d, float z) {
+            if constexpr (SEEDED) *d = z;
+            else acc_out(d, z, false);
+        };
         auto put_rows = [&](const f32x4& a0, const f32x4& a1, const f32x4& b0, const f32x4& b1, int off) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (gok[r]) {
                     float* dA = acc_ptr(gJ[r], off);
                     float* dB = acc_ptr(gI[r], off);
-                    acc_out(dA, a0[r], false); acc_out(dA + 16, a1[r], false);
-                    acc_out(dB, b0[r], false); acc_out(dB + 16, b1[r], false);
+                    row_out(dA, a0[r]); row_out(dA + 16, a1[r]);
+                    row_out(dB, b0[r]); row_out(dB + 16, b1[r]);
                 }
         };
         const unsigned lIq = lnode_of(prow_molI(mi[0]), prow_atomI(mi[0]));      // source of direction A for all four rows of this lane
@@ -432,8 +443,8 @@
                         for (int c = 0; c < 3; ++c) {
                             float* dA = acc_ptr(gJ[r], (1 + c) * F + fo);
                             float* dB = acc_ptr(gI[r], (1 + c) * F + fo);
-                            acc_out(dA, zA[c][0], false); acc_out(dA + 16, zA[c][1], false);
-                            acc_out(dB, zB[c][0], false); acc_out(dB + 16, zB[c][1], false);
+                            row_out(dA, zA[c][0]); row_out(dA + 16, zA[c][1]);
+                            row_out(dB, zB[c][0]); row_out(dB + 16, zB[c][1]);
                         }
                 }
             } else {   // equivariant message: sum_e (sed * dir_e + gates * v[src_e]) -> dvacc ; sum_e cg * dir_e -> cacc, or folded into dvacc

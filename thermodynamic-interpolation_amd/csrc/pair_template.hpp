@@ -40,7 +40,27 @@ struct PairTemplate {
     std::vector<int32_t> slotnode;           // [nblk * 16] slot words (k = 0..3 I slots, 4..7 J slots, rest unused = -1)
     std::vector<int> pair_pos;               // [(m * A + src) * A + dst] -> (block * 2 + direction) * 16 + pair row, -1 = no such edge
     double fill = 0.0;                       // valid rows / all rows
+    bool seeded = false;                     // the general rows name every atom of every molecule of the group exactly once (pair_template_seeded)
 };
+
+// SEEDED: the valid rows of the general blocks [n_tile, nblk) name each of the group's G * A atoms exactly once.  A general launch that
+// runs BEFORE the tile launch then meets every accumulator row as the atom's first contribution of the layer: it stores, and the tile
+// blocks only add (painn_pair_kernel.hpp: the SEEDED builds).  Counted from the row words, never assumed: the twin rows of the complete
+// graph on 18 atoms have it (36 pairs = 72 atoms at G = 4); a tile-only template has no general row and never does.
+inline bool pair_template_seeded(const PairTemplate& t, int A)
+{
+    if (t.n_tile >= t.nblk || A <= 0 || A > 32) return false;
+    std::vector<int> hits((size_t)t.G * 32, 0);
+    for (size_t r = (size_t)t.n_tile * 16; r < (size_t)t.nblk * 16; ++r) {
+        const uint32_t w = t.rows[r];
+        if (!(w & 1u)) continue;
+        const int mI = (w >> 1) & 7, aI = (w >> 4) & 31, mJ = (w >> 9) & 7, aJ = (w >> 12) & 31;
+        if (mI >= t.G || mJ >= t.G || aI >= A || aJ >= A) return false;
+        ++hits[(size_t)mI * 32 + aI]; ++hits[(size_t)mJ * 32 + aJ];
+    }
+    for (int m = 0; m < t.G; ++m) for (int a = 0; a < A; ++a) if (hits[(size_t)m * 32 + a] != 1) return false;
+    return true;
+}
 
 namespace pair_detail {
 struct Blk {
@@ -221,6 +241,7 @@ inline void emit(int A, int E, const std::vector<int>& pt, int G, const std::vec
     }
     if (n_valid * 2 != (size_t)G * E) throw std::logic_error("pair template: not every edge was placed exactly once");
     out.fill = (double)n_valid / ((double)nblk * RB);
+    out.seeded = pair_template_seeded(out, A);
 }
 
 // the pairs every tile block owns (emit's rule: the first block that could hold a pair)

@@ -92,6 +92,11 @@ struct ti_handle {
     // at creation the tile-only one of before (same-binary A/B runs, triage).  pair_pos[(m * A + src) * A + dst] = e row of that directed edge of molecule-in-group m inside
     // its group: (block * 2 + direction) * 16 + pair row
     bool has_pair = false; std::vector<int> pair_pos; double pair_fill = 0.0;
+    // seeded accumulators.  pair_seeded: the pair template's general rows name every atom of a group exactly once
+    // (pair_template.hpp: pair_template_seeded).  pair_seeded_on: the handle may then run the general launch of a layer first, with
+    // plain stores, and tile launches that only add -- unless TI_PAIR_SEEDED=0 was in the environment at creation (same-binary A/B
+    // runs, triage).  Plain split-path evaluations only (painn_host.hip).  seeded_last: what ti_painn_debug_pair_seeded reports.
+    bool pair_seeded = false, pair_seeded_on = false; int seeded_last = -1;
     int n_tpl = 1, active = 0, parts = 1, max_slots = 0, pinned_tpl = TI_TEMPLATE_AUTO;
     // every atom has incoming edges: the edge kernels' first touch of an accumulator replaces its contents (ti_internal.hpp
     // SLOT_FIRST_TOUCH) and nothing zeroes the accumulators between layers or calls; otherwise the update kernel zeroes them as before
@@ -100,6 +105,9 @@ struct ti_handle {
     // emask_sym: every molecule's set is symmetric over the template (the pair layout is eligible).  mrows[t]: the row words of
     // template t per (group, part) of those molecules with the absent edges switched off (masked_rows), built on first use.
     std::vector<uint32_t> emask; long long emask_B = 0; bool emask_sym = true;
+    // emask_full: the state in force removes nothing -- every template edge of every molecule is present, no per-molecule edge types, no
+    // pad atoms -- so its row words are the template's (painn_host.hip: a seeded pair layout then keeps the launches of an unmasked batch)
+    bool emask_full = false;
     DevBuf<uint32_t> mrows[3]; bool mrows_ok[3] = {false, false, false};
     // mixed species (ti_painn_set_molecules), part of the same per-molecule graph state: natoms [emask_B] atom counts (empty: all A),
     // ptype [emask_B][A][A] edge types (empty: the template's).  ragged: some molecule has pad atoms -- only then the drift runs on

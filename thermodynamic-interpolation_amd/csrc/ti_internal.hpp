@@ -154,7 +154,10 @@ __host__ __device__ constexpr bool edge_one_chain(int prec) { return prec == TI_
 // pair-major message kernel (painn_pair_kernel.hpp): same EdgeParams, rows / slotnode of the pair template, same weight stream
 // table: layer 0 on the phi table (p.phi0_tab / p.cls / p.wpad set, p.stream the w-only stream; first must hold, pair_table_build_exists)
 // Two launches when the template has general blocks (p.n_tile < p.nblk): the tile builds over [0, n_tile), then the general builds.
-hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false, bool table = false);
+// seeded (a seeded template, pair_template.hpp; split path, unmasked, one species): the seeded general builds FIRST -- plain stores,
+// every atom's first contribution of the layer -- then the seeded tile builds, which only add.
+hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool masked = false, bool table = false,
+                       bool seeded = false);
 // builds of the pair kernel (painn_pair_kernel.hpp): F <= 128; f32 on 4 waves, split fp16 on 4 and on 8
 __host__ __device__ constexpr bool pair_build_exists(int NB, int WAVES, int PREC)
 {
@@ -177,9 +180,10 @@ hipError_t configure_painn_kernels(int NB);     // dynamic-LDS attributes
 // unit, reached from launch_edge / launch_pair / configure_painn_kernels (painn_kernels.hip).  No pair unit exists for NB = 8.
 template <int NB, bool MASK> hipError_t launch_edge_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st);
 template <int NB, bool MASK> hipError_t configure_edge_unit();
-// (GENERAL: the builds that walk a packed template's general blocks, units painn_pair_gen_nb*.hip; MASK is false for them)
-template <int NB, bool MASK, bool GENERAL> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table);
-template <int NB, bool MASK, bool GENERAL> hipError_t configure_pair_unit();
+// (GENERAL: the builds that walk a packed template's general blocks, units painn_pair_gen_nb*.hip; MASK is false for them.
+// SEEDED: the seeded twins of the unmasked tile and general builds, units painn_pair_seed_nb*.hip)
+template <int NB, bool MASK, bool GENERAL, bool SEEDED = false> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table);
+template <int NB, bool MASK, bool GENERAL, bool SEEDED = false> hipError_t configure_pair_unit();
 
 // ---- forward-mode derivative of the drift (painn_jvp_kernels.hip; virtual-molecule layout described there).
 // D = 3A and xdot == NULL: unit seeds (direction d -> atom d/3, component d%3); otherwise D explicit directions xdot [B][D][A][3]

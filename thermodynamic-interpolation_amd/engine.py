@@ -991,6 +991,14 @@ class PainnEngine(_Engine):
             return None
         return int(g[0]), int(n[0]), int(t[0])
 
+    def debug_pair_seeded(self):
+        """(path, template) of the seeded accumulators: path 1 = the message launches of the last drift evaluation ran general
+        launch first with plain stores, then tiles that only add; 0 = the first-touch order; -1 = none yet.  template 1 = the
+        handle's pair template is seeded (its general rows name every atom of a group exactly once), else 0."""
+        s = np.zeros(1, np.int32)
+        path = _lib.lib().ti_painn_debug_pair_seeded(self.h, _lib.iptr(s))
+        return int(path), int(s[0])
+
     def debug_read(self, what: str, B: int):
         """what: 's' | 'v' | 'e', or 'ts' | 'tv' | 'te' for the tangents of the last jvp() call."""
         shape = {"s": (B, self.A, self.F), "v": (B, self.A, 3, self.F), "e": (B, self.E, self.F)}[what[-1]]
