@@ -614,6 +614,47 @@ typedef struct {
 } ti_md_desc;
 int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* vel, const float* T, const int64_t* ids, int64_t B,
                        double to_nm, float* out_frames, double* out_epot, double* out_ekin, int mem);
+/* Replica exchange: the Langevin dynamics of ti_obs_ff_langevin with Metropolis exchanges of neighbouring rungs of a temperature
+ * ladder in between.  B = n_ladders * K rows, K = n_rungs; row l K + k is rung k of ladder l, and T[l K + k] stays the temperature
+ * of that row for ever: a row is a temperature, what moves is the configuration.  pos, vel, T, ids, the frames and their energies
+ * mean what they mean in ti_obs_ff_langevin, and the steps between two attempts are its launches, unchanged: the host cuts the call
+ * at every attempt and after every steps_per_launch steps since the last cut.
+ * An attempt follows global step count g (steps step_offset .. g - 1 done, g > step_offset) whenever g % exchange_every == 0; its
+ * index is n = g / exchange_every, so one call and any chain of calls with step_offset advanced run the same attempts.  A frame due
+ * at the same g is written first: it shows the state before the exchange.  Attempt n pairs the rungs (k, k + 1) with
+ * k % 2 == n % 2 and k + 1 < K.  E_k = ((bond + angle) + torsion) + pair of the force pass at the fp64 state of row l K + k: the bits
+ * out_epot reports for a frame at that step.  In fp64 without contraction:
+ *   beta_k = 1 / (R (double)T_k),  delta = (beta_k - beta_k1) (E_k - E_k1),  k1 = k + 1
+ *   u = the uniform ((w >> 8) + 0.5) 2^-24 (fp32) of word k & 3 of Philox4x32-10 under the key seed on the counter
+ *       {lo32(ladder id), hi32(ladder id), (uint32_t)n, TI_REMD_DOMAIN + (k >> 2)}, ladder id = ladder_ids[l] or l
+ *       (the noise and velocity draws of the same seed have a fourth word below 64)
+ *   accept iff E_k and E_k1 are finite, neither row has stopped, and delta >= 0 or (double)logf(u) < delta
+ * (logf: the host libm's, as the Philox normals evaluate it).  On acceptance the rows exchange pos, vel and walker, the velocities
+ * rescaled in fp64 at the positions' time.  The "middle" scheme stores v = w - h, w the velocity at the positions and
+ * h = (dt / 2) f(x) / m half a kick (its step starts with the whole kick), and it is w that is Maxwell-distributed and independent
+ * of x.  With h_k the half kick of the configuration at row k, of the same force pass as E_k:
+ *   row k  receives (v(k1) + h_k1) sqrt((double)T_k / (double)T_k1) - h_k1,
+ *   row k1 receives (v(k)  + h_k)  sqrt((double)T_k1 / (double)T_k) - h_k.
+ * (Rescaling the stored v alone leaves the cold rung of a harmonic bond 16 % short of its positional variance at dt = 1 fs,
+ * friction 0.1 / ps and an exchange every 14 steps: profiles/remd_mutations.txt.)
+ * walker [B] int32, in and out: the rung at which the configuration now at row b started; NULL: the identity, nothing returned.
+ * out_walker [n_attempts][B]: walker after each attempt of the call; out_counts [n_ladders][K-1][2] int64: the attempts and
+ * acceptances of pair (k, k + 1) in this call; n_attempts = (step_offset + n_steps) / exchange_every - step_offset / exchange_every.
+ * ladder_ids [n_ladders] int64 or NULL.  All arrays [host|device] by mem; each output may be NULL.
+ * One wave per pair, four pairs per workgroup, one launch per attempt; the energies stay on the chip; each pair's counts and labels
+ * are owned by one wave (ordinary stores, no atomics).  A row's outputs are a function of its ladder's inputs only: repeating the
+ * call, cutting it into launches, chaining it, moving a ladder within the batch and host against device memory do not change a bit,
+ * and a call in which no attempt falls is ti_obs_ff_langevin bit for bit.
+ * A replica stopped by the Langevin kernel takes part in no further pair; the call returns TI_E_NAN as ti_obs_ff_langevin does and
+ * pos, vel and walker are not written.  Refusals: those of ti_obs_ff_langevin in its order; then TI_E_ARG before any device work for
+ * r == NULL, n_rungs < 2 or > TI_REMD_MAX_RUNGS, B % n_rungs != 0, exchange_every < 1, reserved != 0, a walker entry outside
+ * 0 .. K-1 (host memory; in device memory it is found on the device like a bad T, nothing written). */
+#define TI_REMD_MAX_RUNGS 64
+#define TI_REMD_DOMAIN 0x52454D44u     /* fourth Philox counter word of the exchange draws */
+typedef struct { int32_t n_rungs; int32_t reserved; int64_t exchange_every; } ti_remd_desc;
+int ti_obs_ff_remd(ti_handle* h, const ti_md_desc* d, const ti_remd_desc* r, double* pos, double* vel, const float* T,
+                   const int64_t* ids, const int64_t* ladder_ids, int64_t B, double to_nm, int32_t* walker,
+                   float* out_frames, double* out_epot, double* out_ekin, int32_t* out_walker, int64_t* out_counts, int mem);
 /* The log-weights of the TI map from reduced energies: out_logw[b] = -(u1[b] - u0[b] + neg_dlogp[b]) (the reference's weight is
  * exp(-(E1 - E0 + neg_dlogp)), ess.py:8-10), formed in fp64 as ((u1 - u0) + neg_dlogp) and rounded once to the fp32 that
  * ti_obs_weights, ti_obs_hist, ti_obs_bootstrap and ti_obs_rff_gram take.  u0, u1 [B] fp64, neg_dlogp [B] fp32, out_logw [B] fp32:

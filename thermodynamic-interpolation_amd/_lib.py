@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "ti_painn_train_set_state", "ti_painn_train_set_lr", "ti_painn_train_workspace_bytes",
     "ti_painn_train_steps", "ti_painn_train_best", "ti_painn_train_noise",
     "ti_obs_ff_forces", "ti_obs_ff_set_masses", "ti_obs_ff_langevin",
+    "ti_obs_ff_remd",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -76,6 +77,8 @@ FF_MAX_BONDS, FF_MAX_ANGLES, FF_MAX_TORSIONS, FF_MAX_PAIRS = 64, 128, 512, 300
 FF_GAS_CONSTANT, FF_COULOMB = 0.00831446261815324, 138.935456
 # ti_obs_ff_langevin: the most steps of one launch when the descriptor leaves it open (TI_MD_DEFAULT_STEPS_PER_LAUNCH)
 MD_DEFAULT_STEPS_PER_LAUNCH = 1024
+# ti_obs_ff_remd: the most rungs of a ladder (TI_REMD_MAX_RUNGS), the fourth counter word of the exchange draws (TI_REMD_DOMAIN)
+REMD_MAX_RUNGS, REMD_DOMAIN = 64, 0x52454D44
 # ti_obs_zmat / ti_obs_zmat_xyz: the range of A; ti_obs_hist_cols: the most columns of a call
 ZMAT_MIN_ATOMS, ZMAT_MAX_ATOMS, HIST_COLS_MAX = 2, 32, 128
 # ti_*_vloss: loss kinds (TI_VLOSS_*), gamma kinds (TI_GAMMA_*), centring (TI_CENTER_*), time distributions (TI_TDIST_*), the fourth
@@ -130,6 +133,10 @@ class FfDesc(C.Structure):
 class MdDesc(C.Structure):
     _fields_ = [("dt", C.c_double), ("friction", C.c_double), ("n_steps", C.c_int64), ("stride", C.c_int64), ("step_offset", C.c_int64),
                 ("traj_offset", C.c_int64), ("seed", C.c_uint64), ("draw_velocities", C.c_int32), ("steps_per_launch", C.c_int32)]
+
+
+class RemdDesc(C.Structure):
+    _fields_ = [("n_rungs", C.c_int32), ("reserved", C.c_int32), ("exchange_every", C.c_int64)]
 
 
 class VlossDesc(C.Structure):
@@ -253,6 +260,8 @@ def lib():
     L.ti_obs_ff_forces.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
     L.ti_obs_ff_set_masses.argtypes = [vp, dp]
     L.ti_obs_ff_langevin.argtypes = [vp, C.POINTER(MdDesc), vp, vp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
+    L.ti_obs_ff_remd.argtypes = [vp, C.POINTER(MdDesc), C.POINTER(RemdDesc), vp, vp, vp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp, vp,
+                                 C.c_int]
     L.ti_obs_zmat.argtypes = [vp, ip, ip, vp, C.c_int64, vp, C.c_int]
     L.ti_obs_zmat_xyz.argtypes = [vp, ip, ip, vp, C.c_int64, vp, vp, vp, C.c_int]
     L.ti_obs_hist_cols.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int]

@@ -1,5 +1,6 @@
 // api_ff_md.hip -- C ABI of the force-field forces and of Langevin dynamics with them (include/ti_hip.h ti_obs_ff_forces,
-// ti_obs_ff_set_masses, ti_obs_ff_langevin): checks, staging and the launch cut.  Kernels: obs_ff_md_kernels.hip.
+// ti_obs_ff_set_masses, ti_obs_ff_langevin) and of replica exchange between its launches (ti_obs_ff_remd): checks, staging and the
+// launch cut.  Kernels: obs_ff_md_kernels.hip, obs_ff_remd_kernels.hip.
 #include "ti_handle.hpp"
 #include "ff_device.hpp"
 
@@ -92,8 +93,9 @@ int ti_obs_ff_set_masses(ti_handle* h, const double* m)
     });
 }
 
-int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* vel, const float* T, const int64_t* ids, int64_t B,
-                       double to_nm, float* out_frames, double* out_epot, double* out_ekin, int mem)
+// The refusals of ti_obs_ff_langevin that need no device, in the header's order; ti_obs_ff_remd gives them first
+static int md_refusal(const ti_handle* h, const ti_md_desc* d, const double* pos, const double* vel, const float* T, int64_t B, double to_nm,
+                      const float* out_frames, const double* out_epot, const double* out_ekin, int mem)
 {
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
     if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
@@ -108,6 +110,19 @@ int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* v
     if (!h->ff_on) return fail(TI_E_ARG, "no force field set (ti_obs_ff_set)");
     if (!h->ff_mass_on) return fail(TI_E_ARG, "no masses set (ti_obs_ff_set_masses)");
     if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
+    return TI_OK;
+}
+
+// what replica exchange adds to a Langevin call (r == NULL: none of it)
+struct RemdArgs {
+    const ti_remd_desc* r; const int64_t* ladder_ids; int32_t* walker; int32_t* out_walker; int64_t* out_counts;
+};
+
+// The body of ti_obs_ff_langevin and ti_obs_ff_remd: the Langevin launches of the call, cut after every steps_per_launch steps and,
+// with x.r, at every exchange attempt, which is one launch of its own between two of them
+static int md_run(ti_handle* h, const ti_md_desc* d, const RemdArgs& x, double* pos, double* vel, const float* T, const int64_t* ids, int64_t B,
+                  double to_nm, float* out_frames, double* out_epot, double* out_ekin, int mem)
+{
     return guarded([&]() -> int {
         set_device(h);
         hipStream_t st = h->stream;
@@ -116,6 +131,7 @@ int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* v
         const long long n_frames = d->stride > 0 ? d->n_steps / d->stride : 0;
         const hipMemcpyKind in_kind = mem == TI_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
         const hipMemcpyKind out_kind = mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        const bool host = mem == TI_MEM_HOST;
         Staged sg(h, mem);
         const float* Td = sg.in(T, h->ff_T, (size_t)B);
         const int64_t* idd = ids ? sg.in(ids, h->md_ids, (size_t)B) : nullptr;
@@ -133,19 +149,51 @@ int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* v
         p.frames = out_frames && n_frames ? sg.out(out_frames, h->md_frames, (size_t)B * n_frames * 3 * A) : nullptr;
         p.epot = out_epot && n_frames ? sg.out(out_epot, h->md_epot, (size_t)B * n_frames) : nullptr;
         p.ekin = out_ekin && n_frames ? sg.out(out_ekin, h->md_ekin, (size_t)B * n_frames) : nullptr;
+        // replica exchange: the labels advance in a working copy too; the history and the counts of a host call are staged
+        const long long every = x.r ? x.r->exchange_every : 0;
+        const long long n_attempts = x.r ? (d->step_offset + d->n_steps) / every - d->step_offset / every : 0;
+        const size_t n_counts = x.r ? (size_t)(B / x.r->n_rungs) * (x.r->n_rungs - 1) * 2 : 0;
+        RemdParams q{};
+        int32_t* hist = nullptr;
+        if (x.r) {
+            grow(h->md_walker, (size_t)B);
+            const int32_t* win = x.walker && host ? sg.in(x.walker, h->md_walker_in, (size_t)B) : x.walker;
+            HIP_CHECK(launch_obs_ff_remd_walker(h->md_walker.p, win, B, x.r->n_rungs, h->obs_red.p, st));      // behind the T check
+            q.t = p.t; q.pos = p.pos; q.vel = p.vel; q.T = Td; q.B = B; q.K = x.r->n_rungs; q.seed = d->seed; q.mass = h->ff_mass.p; q.dt = d->dt;
+            q.ladder_ids = reinterpret_cast<const long long*>(x.ladder_ids ? sg.in(x.ladder_ids, h->md_ladder_ids, (size_t)(B / x.r->n_rungs)) : nullptr);
+            q.walker = h->md_walker.p; q.flag = h->md_flag.p; q.bad_T = h->obs_red.p;
+            if (x.out_walker && n_attempts) {
+                if (host) grow(h->md_out_walker, (size_t)n_attempts * B);
+                hist = host ? h->md_out_walker.p : x.out_walker;
+            }
+            if (x.out_counts) {
+                if (host) grow(h->md_counts, n_counts);
+                q.counts = reinterpret_cast<long long*>(host ? h->md_counts.p : x.out_counts);
+                HIP_CHECK(hipMemsetAsync(q.counts, 0, n_counts * sizeof(int64_t), st));
+            }
+        }
         const long long per = d->steps_per_launch > 0 ? d->steps_per_launch : TI_MD_DEFAULT_STEPS_PER_LAUNCH;
-        long long done = 0;
+        long long done = 0, attempts = 0;
         for (int launch = 0; launch == 0 || done < d->n_steps; ++launch) {      // n_steps = 0: one launch (it may draw the velocities)
             p.n_steps = std::min<long long>(per, d->n_steps - done);
-            p.steps_before = done; p.step0 = d->step_offset + done; p.launch = launch; p.draw = launch == 0 && d->draw_velocities;
+            const long long g = d->step_offset + done;                          // steps behind the state, over all chained calls
+            if (x.r) p.n_steps = std::min<long long>(p.n_steps, (g / every + 1) * every - g);
+            p.steps_before = done; p.step0 = g; p.launch = launch; p.draw = launch == 0 && d->draw_velocities;
             HIP_CHECK(launch_obs_ff_langevin(p, st));
             done += p.n_steps;
+            if (x.r && p.n_steps > 0 && (g + p.n_steps) % every == 0) {         // a frame due here is written: it shows the state before
+                q.attempt = (g + p.n_steps) / every;
+                q.out_walker = hist ? hist + (size_t)attempts * B : nullptr;
+                HIP_CHECK(launch_obs_ff_remd(q, st));
+                ++attempts;
+            }
         }
         std::vector<int> flag((size_t)B);
         double bad = 0.0;
         HIP_CHECK(hipMemcpyAsync(&bad, h->obs_red.p, sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(flag.data(), h->md_flag.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));           // the one wait of the call that does not move results
+        if (bad < 0.0) return fail(TI_E_ARG, "walker must lie in 0 .. n_rungs - 1: index " + std::to_string((long long)(-1.0 - bad)));
         if (bad < (double)B) return fail(TI_E_ARG, "T must be finite and > 0: index " + std::to_string((long long)bad));
         for (int64_t b = 0; b < B; ++b)
             if (flag[b])
@@ -153,7 +201,34 @@ int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* v
                                           " (pos and vel are left as they were)");
         HIP_CHECK(hipMemcpyAsync(pos, h->md_pos.p, n_state * sizeof(double), out_kind, st));
         if (vel) HIP_CHECK(hipMemcpyAsync(vel, h->md_vel.p, n_state * sizeof(double), out_kind, st));
+        if (x.r && x.walker) HIP_CHECK(hipMemcpyAsync(x.walker, h->md_walker.p, (size_t)B * sizeof(int32_t), out_kind, st));
+        if (hist && host) HIP_CHECK(hipMemcpyAsync(x.out_walker, hist, (size_t)n_attempts * B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (q.counts && host) HIP_CHECK(hipMemcpyAsync(x.out_counts, q.counts, n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         sg.finish();
         return TI_OK;
     });
 }
+
+int ti_obs_ff_langevin(ti_handle* h, const ti_md_desc* d, double* pos, double* vel, const float* T, const int64_t* ids, int64_t B,
+                       double to_nm, float* out_frames, double* out_epot, double* out_ekin, int mem)
+{
+    if (int rc = md_refusal(h, d, pos, vel, T, B, to_nm, out_frames, out_epot, out_ekin, mem)) return rc;
+    return md_run(h, d, RemdArgs{}, pos, vel, T, ids, B, to_nm, out_frames, out_epot, out_ekin, mem);
+}
+
+int ti_obs_ff_remd(ti_handle* h, const ti_md_desc* d, const ti_remd_desc* r, double* pos, double* vel, const float* T, const int64_t* ids,
+                   const int64_t* ladder_ids, int64_t B, double to_nm, int32_t* walker, float* out_frames, double* out_epot, double* out_ekin,
+                   int32_t* out_walker, int64_t* out_counts, int mem)
+{
+    if (int rc = md_refusal(h, d, pos, vel, T, B, to_nm, out_frames, out_epot, out_ekin, mem)) return rc;
+    if (!r) return fail(TI_E_ARG, "NULL remd desc");
+    if (r->n_rungs < 2 || r->n_rungs > TI_REMD_MAX_RUNGS) return fail(TI_E_ARG, "n_rungs must lie in 2 .. " + std::to_string(TI_REMD_MAX_RUNGS));
+    if (B % r->n_rungs != 0) return fail(TI_E_ARG, "B must be a multiple of n_rungs");
+    if (r->exchange_every < 1) return fail(TI_E_ARG, "exchange_every < 1");
+    if (r->reserved != 0) return fail(TI_E_ARG, "reserved must be 0");
+    if (walker && mem == TI_MEM_HOST)
+        for (int64_t b = 0; b < B; ++b)
+            if (walker[b] < 0 || walker[b] >= r->n_rungs) return fail(TI_E_ARG, "walker must lie in 0 .. n_rungs - 1: index " + std::to_string((long long)b));
+    return md_run(h, d, RemdArgs{r, ladder_ids, walker, out_walker, out_counts}, pos, vel, T, ids, B, to_nm, out_frames, out_epot, out_ekin, mem);
+}
+

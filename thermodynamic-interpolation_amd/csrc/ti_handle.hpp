@@ -185,6 +185,9 @@ struct ti_handle {
     // host call's forces; the working copy of the state, the replica ids, frames, frame energies and stop flags of a Langevin call
     DevBuf<int32_t> ff_inc; bool ff_mass_on = false;
     DevBuf<double> ff_mass, ff_f, md_pos, md_vel, md_epot, md_ekin; DevBuf<float> md_frames; DevBuf<int64_t> md_ids; DevBuf<int> md_flag;
+    // replica exchange (ti_obs_ff_remd): the ladder ids, the working copy of the walker labels, and staging of a host call's walker
+    // history and pair counts
+    DevBuf<int64_t> md_ladder_ids, md_counts; DevBuf<int32_t> md_walker, md_walker_in, md_out_walker;
     // Z-matrix coordinates and column histograms (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols): the topology of the call (order,
     // ref), staging of a host call's z, log-determinants, validity and keep masks, the column ranges (lo [K], hi [K])
     DevBuf<int32_t> zm_topo; DevBuf<float> zm_z; DevBuf<double> zm_logdet, hc_range; DevBuf<uint8_t> zm_valid, hc_keep;

@@ -460,6 +460,28 @@ struct MdParams {
 };
 hipError_t launch_obs_ff_langevin(const MdParams& p, hipStream_t st);
 
+// ---- replica exchange between Langevin launches (obs_ff_remd_kernels.hip; include/ti_hip.h ti_obs_ff_remd).  Row l K + k is rung k
+// of ladder l; one launch is one attempt: it evaluates the energies of the rows of its pairs, decides and exchanges them in place.
+struct RemdParams {
+    FfTablesDev t;
+    double *pos, *vel;                      // [B][A][3]: the working state of the Langevin launches
+    const float* T;                         // [B] kelvin
+    const long long* ladder_ids;            // [B / K] or NULL (ladder l: l)
+    const double* mass; double dt;          // [A] amu and the step: the half kick (dt / 2) f / m between stored and on-step velocities
+    long long B; int K;
+    long long attempt;                      // n: pairs (k, k + 1) with k % 2 == n % 2; its low 32 bits are the third counter word
+    unsigned long long seed;
+    int32_t* walker;                        // [B]: the working labels, exchanged with the state
+    int32_t* out_walker;                    // [B]: the labels after this attempt, or NULL
+    long long* counts;                      // [B / K][K - 1][2]: attempts and acceptances of the call so far, or NULL
+    const int* flag;                        // MdParams::flag: a stopped replica takes part in no pair
+    const double* bad_T;                    // below B (a refused temperature or walker label): the launch does nothing
+};
+hipError_t launch_obs_ff_remd(const RemdParams& p, hipStream_t st);
+// work[b] = in ? in[b] : b % K.  A label outside 0 .. K-1 at index i (the first such) is reported as bad[0] = -1 - i, unless bad[0]
+// already names a refused temperature (launch_obs_ff_bad_temperature ran before): every later launch of the call then does nothing.
+hipError_t launch_obs_ff_remd_walker(int32_t* work, const int32_t* in, long long B, int K, double* bad, hipStream_t st);
+
 // ---- Z-matrix coordinates and the histograms of all columns (obs_zmat_kernels.hip; include/ti_hip.h ti_obs_zmat, ti_obs_zmat_xyz,
 // ti_obs_hist_cols).  topo: order [A] (sorted atom s is the caller's atom order[s]) followed by ref [A][3] in sorted numbering, both
 // validated on the host (zmat_check_topology): every slot that is read names an earlier sorted atom.

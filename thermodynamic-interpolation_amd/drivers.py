@@ -881,7 +881,12 @@ def _md_settings(config):
     counts = np.floor(frac * n_rep + 1e-9).astype(int)          # whole replicas: the splits are independent trajectories
     if (counts < 1).any():
         raise ValueError(f"'splits' {splits} leave a split without a replica at n_replicas = {n_rep}")
-    return (1.0 / v if to_nm is None else v), temps, n_rep, n_frames, stride, n_equil, dict(zip(splits, counts.tolist()))
+    every = getattr(config, "exchange_every", None)             # optional: absent or 0, independent chains
+    if every is not None and (isinstance(every, bool) or every != int(every) or int(every) < 0):
+        raise ValueError(f"'exchange_every' must be a whole number of steps >= 0 (0: no replica exchange), got {every!r}")
+    if every and len(temps) < 2:
+        raise ValueError("'exchange_every' needs at least two 'temperatures': a ladder has two rungs or more")
+    return (1.0 / v if to_nm is None else v), temps, n_rep, n_frames, stride, n_equil, dict(zip(splits, counts.tolist())), int(every or 0)
 
 
 def _md_engine(b, A):
@@ -900,11 +905,14 @@ def generate_md(config, b):
     data.TEMPERATURES.index(T) holding that temperature's frames replica-major (a split takes whole replicas), the rows of
     temperatures that were not simulated NaN; and ``{traj_path}/md_log.npz`` with the per-frame energies, the settings and the seed.
     The frames are centred and in the model's length unit before `scale` (the file load_trajectory(..., scale=False) returns as
-    it is).  Returns {split: path}."""
+    it is).  With the optional key ``exchange_every`` > 0, replica r of every temperature forms one temperature ladder with replica
+    exchange after every exchange_every-th step (md.ReplicaExchangeSampler); the files keep their layout and md_log.npz gains
+    exchange_every, accept_counts [n_replicas, n_temperatures - 1, 2] (temperatures ascending) and round_trips [n_replicas].
+    Returns {split: path}."""
     from . import data as _data
     from . import forcefield as _ff
     from . import md as _md
-    to_nm, temps, n_rep, n_frames, stride, n_equil, counts = _md_settings(config)
+    to_nm, temps, n_rep, n_frames, stride, n_equil, counts, every = _md_settings(config)
     ff = _ff.ForceField.from_openmm_xml(os.fspath(config.forcefield))
     A = ff.n_atoms
     x0 = np.load(os.fspath(config.x0))
@@ -914,10 +922,23 @@ def generate_md(config, b):
     B = len(temps) * n_rep                                       # replica r of temperature k is row k * n_replicas + r, its id too
     T = np.repeat(np.asarray(temps, np.float32), n_rep)
     start = x0[np.arange(B) % len(x0)]
-    sampler = _md.LangevinSampler(_md_engine(b, A), ff, to_nm, float(config.dt), float(config.friction), int(config.seed))
-    sampler.start(start, T)
-    sampler.equilibrate(n_equil)
-    frames, epot, ekin = (C.to_numpy(a) for a in sampler.sample(n_frames, stride))
+    extra = {}
+    if not every:
+        sampler = _md.LangevinSampler(_md_engine(b, A), ff, to_nm, float(config.dt), float(config.friction), int(config.seed))
+        sampler.start(start, T)
+        sampler.equilibrate(n_equil)
+        frames, epot, ekin = (C.to_numpy(a) for a in sampler.sample(n_frames, stride))
+    else:
+        # replica exchange: ladder r is made of the rows (T_k, replica r) in ascending temperature.  The library wants the rows
+        # ladder-major; every row keeps the id it has above, so a run in which no attempt falls writes the files of the other branch
+        order = np.argsort(np.asarray(temps), kind="stable")
+        rows = (order[None, :] * n_rep + np.arange(n_rep)[:, None]).reshape(-1)      # ladder-major position -> row
+        sampler = _md.ReplicaExchangeSampler(_md_engine(b, A), ff, to_nm, float(config.dt), float(config.friction), int(config.seed), every)
+        sampler.start(start[rows], np.asarray(temps, np.float32)[order], n_rep, ids=rows.astype(np.int64))
+        sampler.equilibrate(n_equil)
+        back = np.argsort(rows)
+        frames, epot, ekin = (C.to_numpy(a)[back] for a in sampler.sample(n_frames, stride))
+        extra = dict(exchange_every=every, accept_counts=sampler.counts, round_trips=_md.round_trips(sampler.walkers))
     frames = frames.reshape(len(temps), n_rep, n_frames, A, 3)
     paths, first = {}, 0
     for split, n in counts.items():
@@ -931,5 +952,5 @@ def generate_md(config, b):
     np.savez(os.path.join(config.traj_path, "md_log.npz"), epot=epot.reshape(len(temps), n_rep, n_frames),
              ekin=ekin.reshape(len(temps), n_rep, n_frames), temperatures=np.asarray(temps), n_replicas=n_rep, dt=float(config.dt),
              friction=float(config.friction), n_equil=n_equil, n_frames=n_frames, stride=stride, seed=int(config.seed), to_nm=to_nm,
-             split_names=np.array(list(counts)), split_replicas=np.array(list(counts.values())))
+             split_names=np.array(list(counts)), split_replicas=np.array(list(counts.values())), **extra)
     return paths

@@ -733,6 +733,25 @@ class PainnEngine(_Engine):
         and kinetic energies [B, n_steps // stride] float64 at the frames (None where frames / energies is off or stride is 0).  numpy
         in, numpy out; CUDA tensors in, CUDA tensors out.  Raises ValueError for a force field with constraints (they are not
         integrated) and for missing masses."""
+        return self._md(None, pos, vel, T, dt, friction, n_steps, stride, step_offset, traj_offset, seed, ids, to_nm, draw_velocities,
+                        steps_per_launch, frames, energies)
+
+    def remd(self, pos, vel, T, n_rungs, exchange_every, dt, friction, n_steps, stride=0, step_offset=0, traj_offset=0, seed=0, ids=None,
+             ladder_ids=None, walker=None, to_nm=1.0, draw_velocities=False, steps_per_launch=0, frames=True, energies=True):
+        """ti_obs_ff_remd: langevin with Metropolis exchanges of neighbouring rungs after every exchange_every-th global step.  The B
+        rows are n_ladders ladders of n_rungs rungs, row l * n_rungs + k rung k of ladder l; T [B] is the temperature of each row and
+        stays with the row, the configurations move.  ladder_ids [n_ladders] int64 key the exchange draws (None: 0, 1, ...); walker
+        [B] int32 says at which rung the configuration now at a row started (None: the identity).  Returns (pos, vel, frames, epot,
+        ekin, walker, walkers, counts): langevin's five, the labels after the call, after each of its attempts [n_attempts, B] and the
+        attempts and acceptances of every neighbouring pair in this call [n_ladders, n_rungs - 1, 2] int64.  A frame due at the step of
+        an attempt shows the state before the exchange.  numpy in, numpy out; CUDA tensors in, CUDA tensors out; langevin's
+        ValueErrors."""
+        return self._md((int(n_rungs), int(exchange_every), ladder_ids, walker), pos, vel, T, dt, friction, n_steps, stride, step_offset,
+                        traj_offset, seed, ids, to_nm, draw_velocities, steps_per_launch, frames, energies)
+
+    def _md(self, remd, pos, vel, T, dt, friction, n_steps, stride, step_offset, traj_offset, seed, ids, to_nm, draw_velocities,
+            steps_per_launch, frames, energies):
+        """langevin (remd None) or remd ((n_rungs, exchange_every, ladder_ids, walker)): the checks, the buffers and the call"""
         if not getattr(self, "_ff_set", False):
             raise ValueError("langevin needs a force field (set_forcefield)")
         if self._ff_constraints:
@@ -777,9 +796,31 @@ class PainnEngine(_Engine):
             stride = 0
         desc = _lib.MdDesc(float(dt), float(friction), int(n_steps), int(stride), int(step_offset), int(traj_offset), int(seed),
                            int(bool(draw_velocities)), int(steps_per_launch))
-        _lib.check(_lib.lib().ti_obs_ff_langevin(self.h, C.byref(desc), ptr(p), ptr(v), ptr(Td), ptr(idd), B, float(to_nm), ptr(fr), ptr(ep),
-                                                 ptr(ek), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
-        return p, v, fr, ep, ek
+        if remd is None:
+            _lib.check(_lib.lib().ti_obs_ff_langevin(self.h, C.byref(desc), ptr(p), ptr(v), ptr(Td), ptr(idd), B, float(to_nm), ptr(fr), ptr(ep),
+                                                     ptr(ek), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+            return p, v, fr, ep, ek
+        K, every, ladder_ids, walker = remd
+        if K < 2 or B % K or every < 1:
+            raise ValueError(f"n_rungs must be >= 2 and divide B = {B}, exchange_every must be >= 1")
+        n_att = (int(step_offset) + int(n_steps)) // every - int(step_offset) // every
+        if dev:
+            lid = None if ladder_ids is None else torch.as_tensor(ladder_ids, dtype=torch.int64, device=pos.device).contiguous()
+            wk = torch.arange(B, dtype=torch.int32, device=pos.device) % K if walker is None \
+                else torch.as_tensor(walker, device=pos.device).to(dtype=torch.int32, copy=True).contiguous()
+            hist, cnt = new((n_att, B), torch.int32), new((B // K, K - 1, 2), torch.int64)
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        else:
+            lid = None if ladder_ids is None else np.ascontiguousarray(ladder_ids, np.int64)
+            wk = (np.arange(B) % K).astype(np.int32) if walker is None else np.array(walker, np.int32, order="C")
+            hist, cnt = np.empty((n_att, B), np.int32), np.empty((B // K, K - 1, 2), np.int64)
+        if tuple(wk.shape) != (B,) or (lid is not None and tuple(lid.shape) != (B // K,)):
+            raise ValueError(f"walker must be [{B}], ladder_ids [{B // K}]")
+        rd = _lib.RemdDesc(K, 0, every)
+        _lib.check(_lib.lib().ti_obs_ff_remd(self.h, C.byref(desc), C.byref(rd), ptr(p), ptr(v), ptr(Td), ptr(idd), ptr(lid), B, float(to_nm),
+                                             ptr(wk), ptr(fr), ptr(ep), ptr(ek), ptr(hist) if n_att else None, ptr(cnt),
+                                             _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return p, v, fr, ep, ek, wk, hist, cnt
 
     def _zmat_topology(self, zm):
         if zm.A != self.A:
