@@ -764,6 +764,21 @@ int ti_painn_debug_pair_blocks(ti_handle* h, int32_t* G, int32_t* nblk, int32_t*
  * Returns which order the LAST drift evaluation of the handle took (a rollout: its last evaluation): 1 = seeded, 0 = the order of
  * before, -1 = no evaluation yet.  *template_seeded (may be NULL): 1 when the handle's pair template is seeded, else 0. */
 int ti_painn_debug_pair_seeded(ti_handle* h, int32_t* template_seeded);
+/* Merged tails.  The last general block of a seeded template may hold r < 16 valid rows (18 atoms at G = 4: 36 twin
+ * pairs = 16 + 16 + 4).  Where r is a multiple of 4 that divides 16, the seeded general launch gives one wave S = 16 / r groups: it
+ * walks their full general blocks, then their S last blocks as ONE block of 16 rows.  Storage, row words and results are those of the
+ * walk of one group per wave, bit for bit.  TI_PAIR_TAILS=0 in the environment when the handle is created keeps that walk.
+ * Returns which walk the general launches of the LAST drift evaluation took: 1 = merged tails, 0 = one group per wave (or no seeded
+ * launch at all), -1 = no evaluation yet.  *groups_per_wave (may be NULL): S of the handle's pair template, 0 when it has no such tails. */
+int ti_painn_debug_pair_tails(ti_handle* h, int32_t* groups_per_wave);
+/* Embed per class.  On the phi table path the embedding is read twice: P of the class representatives by the table
+ * kernel, s once by layer 0's update kernel; the embed rows of a class's molecules agree bit for bit.  The embed launch of such an
+ * evaluation then covers the (class, atom) rows alone, the table kernel reads them, and layer 0's update kernel reads s through the
+ * class map and is the first to write the full s and P: bit for bit the result of the launch over every atom.  Every evaluation off
+ * the table path, or TI_EMBED_CLASSES=0 in the environment when the handle is created: the embed launch of before.
+ * Returns which embed launch the LAST drift evaluation of the handle ran (a rollout: its last evaluation): 1 = per class, 0 = every
+ * atom, -1 = no evaluation yet.  ti_painn_debug_poison fills the full s and P as well, which such an evaluation must not read. */
+int ti_painn_debug_embed_path(ti_handle* h);
 /* Device self-test of the MFMA operand/accumulator lane maps the kernels rely on, of both fp32 -> (hi, lo) fp16 operand splits
  * (the 8-instruction forms of formats (a) and (b) against the plain arithmetic, bit for bit, fp16-subnormal residuals included),
  * and of the fp16 matrix instruction keeping subnormal inputs. */

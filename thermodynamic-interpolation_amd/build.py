@@ -20,6 +20,8 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api
            # the seeded twins of the unmasked split-path builds, tile and general (painn_pair_kernel.hpp: SEEDED): units of their own
            # again, so that every older code object stays as it was and the widths compile in parallel
            "painn_pair_seed_nb1.hip", "painn_pair_seed_nb2.hip", "painn_pair_seed_nb4.hip",
+           # the merged-tails builds of the seeded general launch (painn_pair_kernel.hpp: TAILS), units of their own once more
+           "painn_pair_tails_nb1.hip", "painn_pair_tails_nb2.hip", "painn_pair_tails_nb4.hip",
            # ragged twins of the adaptive-solver kernels (mixed-species batches): a unit of their own, ode_kernels.hip's code stays put
            "ode_ragged_kernels.hip",
            # observables (ti_obs_*): collective variables, importance weights, weighted histograms
@@ -57,7 +59,7 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api
            # lives in api_ff_md.hip next to ti_obs_ff_langevin's, the table staging both kernel units share in ff_stage.hpp
            "obs_ff_remd_kernels.hip"]
 HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "adw_train.hpp", "painn_train.hpp", "painn_steps.hpp", "train_optim.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "vloss_normal.hpp", "ff_device.hpp", "ff_stage.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp",
-           "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
+           "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_update_kernel_body.inc", "painn_embed_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
 # -packed-fp32-ops off: v_pk_{fma,mul,add}_f32 do NOT run next to another wave's matrix instructions on gfx950 (a wave of them and a
 # wave of 16x16x32 fp16 MFMAs on one SIMD take the SUM of their times; scalar v_fma_f32, conversions and transcendentals overlap:
 # tools/micro/coexec_classes.hip, profiles/r03i_microbench_coexec.txt), and register pairs cost the message kernels registers (pair

@@ -259,6 +259,19 @@ int ti_painn_debug_pair_seeded(ti_handle* h, int32_t* template_seeded)
     return h->seeded_last;
 }
 
+int ti_painn_debug_pair_tails(ti_handle* h, int32_t* groups_per_wave)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (groups_per_wave) *groups_per_wave = h->has_pair ? h->pair_tail_S : 0;
+    return h->tails_last;
+}
+
+int ti_painn_debug_embed_path(ti_handle* h)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    return h->embed_cls_last;
+}
+
 int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)
 {
     if (!h || h->kind != 0 || B <= 0) return fail(TI_E_ARG, "not a painn handle / B");
@@ -278,6 +291,13 @@ int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)
         HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->geo.p, (int)bits, h->geo.n, h->stream));
         // the layer-0 phi table too: every entry an evaluation reads was written by its own table launch
         if (h->phi0_tab.n) HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->phi0_tab.p, (int)bits, h->phi0_tab.n, h->stream));
+        // s and P, and their per-class twins: an evaluation whose embed launch covers the classes alone must not read the full rows
+        // before layer 0's update has written them (every other evaluation's embed launch replaces them first)
+        static_assert(sizeof(*h->s.p) == 4 && sizeof(*h->P.p) == 4, "32-bit fills");
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->s.p, (int)bits, h->s.n, h->stream));
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->P.p, (int)bits, h->P.n, h->stream));
+        if (h->s_cls.n) HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->s_cls.p, (int)bits, h->s_cls.n, h->stream));
+        if (h->P_cls.n) HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)h->P_cls.p, (int)bits, h->P_cls.n, h->stream));
         return TI_OK;
     });
 }

@@ -30,6 +30,7 @@ void phi0_begin_call(ti_handle* h, const float* cond_dev, long long B, bool elig
     const int A = h->d.n_atoms, F = h->d.n_features;
     grow(h->phi0_cls, (size_t)B); grow(h->phi0_state, (size_t)PHI0_STATE_WORDS);
     grow(h->phi0_tab, (size_t)TI_PHI0_MAX_CLASSES * A * PHI0_TYPES * 3 * F);
+    if (h->embed_cls_on) { grow(h->s_cls, (size_t)TI_PHI0_MAX_CLASSES * A * F); grow(h->P_cls, (size_t)TI_PHI0_MAX_CLASSES * A * F); }
     int32_t state[PHI0_STATE_WORDS];
     {
         Timed tm(h, TI_KERNEL_PAINN_EMBED);
@@ -189,6 +190,15 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
         HIP_CHECK(hipMemsetAsync(h->dvacc.p, 0, vbytes, st));
         HIP_CHECK(hipMemsetAsync(h->dsacc.p, 0, (size_t)N * F * sizeof(float), st));
     }
+    // layer 0 on the phi table: the call's class pass stands for exactly these molecules, t is one for all of them, and nothing that
+    // the table builds do not take is in force (a mask or mixed species, a tap, a tangent pass, a directed layout)
+    const bool table = h->phi0_ncls > 0 && h->phi0_B == B && h->phi0_cond == cond_dev && b0 == 0 && h->active == 2 && !tv && !jr && !nat && !mrows &&
+                       h->tap < 0 && h->nblk > 0 && L > 0;
+    h->phi0_last = table ? 1 : 0;
+    // embed per class: on the table path the embedding has two readers, the table kernel (P of the class representatives) and layer 0's
+    // update (s, once), and a class's rows agree bit for bit -- the launch covers (class, atom) rows alone, into s_cls / P_cls
+    const bool embed_cls = table && h->embed_cls_on;
+    h->embed_cls_last = embed_cls ? 1 : 0;
     {
         EmbedParams p{};
         p.stream = h->S(h->st_embed16); p.nch = h->st_embed16.nch; p.mlp = h->vec(h->embed);
@@ -196,19 +206,16 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
         p.atom_emb = h->F(h->atom_emb); p.atom_ids = h->atom_ids.p; p.cond = cond_dev; p.ncond = h->ncond; p.A = A; p.N = N;
         p.t = t; p.tv = tv; p.temp_length = h->d.temp_length; p.time_length = h->d.time_length; p.temp_mean = h->d.temp_mean; p.temp_range = h->d.temp_range;
         p.s = h->s.p; p.P = h->P.p;
+        if (embed_cls) { p.N = (long long)h->phi0_ncls * A; p.rep = h->phi0_state.p; p.s = h->s_cls.p; p.P = h->P_cls.p; }
         Timed tm(h, TI_KERNEL_PAINN_EMBED);
         HIP_CHECK(launch_embed(NB, h->nE, prec, p, st));
     }
-    // layer 0 on the phi table: the call's class pass stands for exactly these molecules, t is one for all of them, and nothing that
-    // the table builds do not take is in force (a mask or mixed species, a tap, a tangent pass, a directed layout)
-    const bool table = h->phi0_ncls > 0 && h->phi0_B == B && h->phi0_cond == cond_dev && b0 == 0 && h->active == 2 && !tv && !jr && !nat && !mrows &&
-                       h->tap < 0 && h->nblk > 0 && L > 0;
-    h->phi0_last = table ? 1 : 0;
     if (table) {
         Phi0TableParams p{};
         p.stream = h->S(h->st_phi0_tab); p.nch = h->st_phi0_tab.nch; p.vecs = h->edge_vecs1.p; p.edge_emb = h->F(h->edge_emb);
         for (int i = 0; i < 6; ++i) p.wscale[i] = h->edge_scale[i];
         p.P = h->P.p; p.state = h->phi0_state.p; p.n_cls = h->phi0_ncls; p.A = A; p.tab = h->phi0_tab.p;
+        if (embed_cls) { p.P = h->P_cls.p; p.state = nullptr; }
         Timed tm(h, TI_KERNEL_PAINN_EMBED);
         HIP_CHECK(launch_phi0_table(NB, L == 1, p, st));
     }
@@ -219,6 +226,8 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
     const bool mask_off = mrows && h->emask_full;
     const bool seeded = h->active == 2 && h->pair_seeded_on && h->n_tile > 0 && h->n_tile < h->nblk && pair_general_build_exists(prec) && (!mrows || mask_off) && !nat && L > 0;
     h->seeded_last = seeded ? 1 : 0;
+    const bool tails = seeded && h->pair_tails_on;      // the seeded general launch on super-groups, their last blocks merged
+    h->tails_last = tails ? 1 : 0;
     h->last_B = B;
     if (h->tap == 0) return;
     for (int l = 0; l < L; ++l) {
@@ -257,6 +266,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
                 p.stream = h->S(h->st_edge1[l]); p.nch = h->st_edge1[l].nch; p.vecs = h->edge_vecs1.p + (size_t)l * 21 * F;
                 for (int i = 0; i < 6; ++i) p.wscale[i] = h->edge_scale[(size_t)l * 6 + i];
             }
+            if (tails) { p.tail_S = h->pair_tail_S; p.tail_r = h->pair_tail_r; }
             if (mrows && !seeded) p.rows = mrows;      // (seeded under a mask that removes nothing: the template's own row words)
             Timed tm(h, TI_KERNEL_PAINN_EDGE);
 #ifdef TI_STAMPS
@@ -303,6 +313,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
             p.stream = h->S(h->st_update[l]); p.nch = h->st_update[l].nch; p.vecs = h->upd_vecs.p + (size_t)l * 10 * F;
             p.N = N; p.s = h->s.p; p.v = h->v.p; p.dsacc = h->dsacc.p; p.dvacc = h->dvacc.p; p.cacc = h->cacc.p; p.P = h->P.p;
             p.first_layer = l == 0; p.zero_acc = !ft;
+            if (embed_cls && l == 0) { p.s_cls = h->s_cls.p; p.cls = h->phi0_cls.p; p.A = A; }      // the full s is first written here
             // after a pair launch that folded the cross term into dvacc, the update kernel that reads neither cacc nor its cross product
             // (cacc is then not written in this layer; the tangent passes, which read it, run on directed launches only)
             const bool folded = h->nblk > 0 && h->active == 2 && l > 0 && pair_folds_cross(prec);

@@ -38,212 +38,16 @@ __host__ __device__ constexpr int update_superchunk(int NB, bool H16) { return H
 __host__ __device__ constexpr int update_chunk4(int NB, bool H16) { return (H16 ? 128 : 256) * NB; }
 template <int NBK, bool HAS_NEXT, int PREC, bool FOLDED = false>
 __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_kernel(const UpdateParams p)
-{
-    constexpr bool H16 = PREC == 2;                 // s, v, P are fp16 in HBM (the accumulators stay fp32), hi-only weight chunks
-    constexpr int F = 16 * NBK, NB = (F + 31) / 32, WAVES = 4, T = 64 * WAVES, CH4 = update_chunk4(NB, H16);
-    using A16 = r16::Act<NBK>;
-    using OP = typename r16::OpSel<NBK, PREC>::type;
-    extern __shared__ f32x4 lds[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 15, q = lane >> 4;
-    constexpr int SC = update_superchunk(NB, H16);
-    float* vec = reinterpret_cast<float*>(lds + 2 * SC * CH4);                     // [UV::COUNT][F]
-    for (int i = threadIdx.x; i < UV::COUNT * F / 4; i += T)
-        reinterpret_cast<f32x4*>(vec)[i] = reinterpret_cast<const f32x4*>(p.vecs)[i];
-    PipeDMA<NB, T, SC, CH4> pipe;
-    pipe.init(reinterpret_cast<const f32x4*>(p.stream), p.nch, lds, wave, lane);
+#define TI_UPDATE_SCLS false
+#include "painn_update_kernel_body.inc"
+#undef TI_UPDATE_SCLS
 
-    const long long node = ((long long)blockIdx.x * WAVES + wave) * 16 + j;
-    const bool ok = node < p.N;
-    const size_t nd = (size_t)(ok ? node : p.N - 1);
-    const size_t vo = nd * 3 * F, so_ = nd * F;   // element offsets of this node's v / s rows (fp32 or fp16 storage)
-    float* db = p.dvacc + nd * 3 * F;
-    float* cb = p.cacc + nd * 3 * F;
-    float* ab = p.dsacc + nd * F;                 // sum of the invariant messages of this layer (edge kernel)
-
-    // ---- phase A: v_eff = v + dvacc + cacc x v (parked in dvacc), n2 = |V v_eff|^2 over the 3 components
-    A16 n2;
-    {
-        OP ve[3];
-        float vsc[3];                               // v is an un-normalised stream: per-row scales of the split operands
-        {
-            A16 t[3];                               // feature block outermost: v, dvacc and cacc are each read ONCE (all three components of a
-#pragma unroll                                      // block are needed for the cross product; re-reading them per component missed L2)
-            for (int nb = 0; nb < NBK; ++nb) {
-                f32x4 vv[3], kk[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    vv[c] = p.first_layer ? f32x4{0, 0, 0, 0} : r16::load_state<H16>(p.v, vo + c * F, nb, q);
-                    kk[c] = p.first_layer || FOLDED ? f32x4{0, 0, 0, 0} : r16::load_block(cb + c * F, nb, q);
-                }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
-                    const f32x4 dd = r16::load_block(db + c * F, nb, q);
-                    if (FOLDED) t[c].b[nb] = vv[c] + dd;
-                    else t[c].b[nb] = (vv[c] + dd) + (kk[c1] * vv[c2] - kk[c2] * vv[c1]);      // torch.cross(edge_dir, v[dst]) summed over edges
-                    if (ok) r16::store_block(db + c * F, nb, q, t[c].b[nb]);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) vsc[c] = ve[c].set_scaled(t[c]);
-        }
-#pragma unroll
-        for (int nb = 0; nb < NBK; ++nb) n2.b[nb] = f32x4{0, 0, 0, 0};
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
-                r16::gemm_bt(a0, a1, ve[c], wl, lane);                   // vv = V v  (of the scaled rows)
-                a0 *= vsc[c]; a1 *= vsc[c];
-                n2.b[2 * ch] += a0 * a0; n2.b[2 * ch + 1] += a1 * a1;
-            }
-            pipe.release();
-        }
-    }
-    // ---- phase B: MLP([ |vv| , s ])
-    A16 snew;                                       // s + ds, then s after the update (phase D's operand): read once, kept in registers
-    OP h2;
-    {
-        A16 t;
-#pragma unroll
-        for (int nb = 0; nb < NBK; ++nb) t.b[nb] = r16::load_block(vec + UV::B0 * F, nb, q);
-        {
-            OP nn;
-            float nsc;
-            {
-                A16 u;
-#pragma unroll
-                for (int nb = 0; nb < NBK; ++nb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) u.b[nb][r] = sqrtf(n2.b[nb][r]);
-                nsc = nn.set_scaled(u);
-            }
-#pragma unroll
-            for (int ch = 0; ch < NB; ++ch) {
-                const f32x4* wl = pipe.acquire();
-                f32x4 g0 = {0, 0, 0, 0}, g1 = {0, 0, 0, 0};
-                r16::gemm_bt(g0, g1, nn, wl, lane);
-                t.b[2 * ch] += g0 * nsc; t.b[2 * ch + 1] += g1 * nsc;
-                pipe.release();
-            }
-        }
-        {
-            OP ss;
-            float ssc;
-#pragma unroll
-            for (int nb = 0; nb < NBK; ++nb) snew.b[nb] = r16::load_state<H16>(p.s, so_, nb, q) + r16::load_block(ab, nb, q);      // s += ds
-            ssc = ss.set_scaled(snew);
-#pragma unroll
-            for (int ch = 0; ch < NB; ++ch) {
-                const f32x4* wl = pipe.acquire();
-                f32x4 g0 = {0, 0, 0, 0}, g1 = {0, 0, 0, 0};
-                r16::gemm_bt(g0, g1, ss, wl, lane);
-                t.b[2 * ch] += g0 * ssc; t.b[2 * ch + 1] += g1 * ssc;
-                pipe.release();
-            }
-        }
-        r16::ln_silu(t, vec + UV::G0 * F, vec + UV::BE0 * F, q);
-        OP h1;
-        h1.set(t);
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-            f32x4 a0 = r16::load_block(vec + UV::B1 * F, 2 * ch, q), a1 = r16::load_block(vec + UV::B1 * F, 2 * ch + 1, q);
-            r16::gemm_bt(a0, a1, h1, wl, lane);
-            t.b[2 * ch] = a0; t.b[2 * ch + 1] = a1;
-            pipe.release();
-        }
-        r16::ln_silu(t, vec + UV::G1 * F, vec + UV::BE1 * F, q);
-        h2.set(t);
-    }
-    // output chunks: [scale_squared_norm, add_invariant] per 32-feature block, then gates
-#pragma unroll
-    for (int ch = 0; ch < NB; ++ch) {
-        const f32x4* wl = pipe.acquire();
-        f32x4 q0 = r16::load_block(vec + (UV::B2 + 1) * F, 2 * ch, q), q1 = r16::load_block(vec + (UV::B2 + 1) * F, 2 * ch + 1, q);
-        r16::gemm_bt(q0, q1, h2, wl, lane);
-        pipe.release();
-        wl = pipe.acquire();
-        f32x4 a0 = r16::load_block(vec + (UV::B2 + 2) * F, 2 * ch, q), a1 = r16::load_block(vec + (UV::B2 + 2) * F, 2 * ch + 1, q);
-        r16::gemm_bt(a0, a1, h2, wl, lane);
-        pipe.release();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int nb = 2 * ch + k;
-            f32x4 so = snew.b[nb];
-            const f32x4 qq = k ? q1 : q0, aa = k ? a1 : a0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float n = sqrtf(n2.b[nb][r]);
-                so[r] = so[r] + ((n * n) * qq[r] + aa[r]);              // s += vv_norm**2 * scale + add
-            }
-            snew.b[nb] = so;
-            if (ok) {
-                r16::store_state<H16>(p.s, so_, nb, q, so);
-                if (p.zero_acc) r16::store_block(ab, nb, q, f32x4{0, 0, 0, 0});
-            }
-        }
-    }
-    A16 gg;
-#pragma unroll
-    for (int ch = 0; ch < NB; ++ch) {
-        const f32x4* wl = pipe.acquire();
-        f32x4 a0 = r16::load_block(vec + UV::B2 * F, 2 * ch, q), a1 = r16::load_block(vec + UV::B2 * F, 2 * ch + 1, q);
-        r16::gemm_bt(a0, a1, h2, wl, lane);
-        gg.b[2 * ch] = a0; gg.b[2 * ch + 1] = a1;
-        pipe.release();
-    }
-    // ---- phase C: v = v_eff + (U v_eff) * gates ; reset the accumulators for the next layer.  One spatial component at a time (the
-    // stream holds U three times): the parked v_eff row is read once and serves as operand AND as the value the update is added to
-    // -- with the three components sharing each chunk visit it had to be read a second time, and that read missed L2.
-#pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-        A16 t;
-        r16::load_set(t, db + c * F, q);
-        OP vc;
-        const float usc = vc.set_scaled(t);
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
-            r16::gemm_bt(a0, a1, vc, wl, lane);
-            a0 *= usc; a1 *= usc;
-            if (ok) {
-                r16::store_state<H16>(p.v, vo + c * F, 2 * ch, q, t.b[2 * ch] + a0 * gg.b[2 * ch]);
-                r16::store_state<H16>(p.v, vo + c * F, 2 * ch + 1, q, t.b[2 * ch + 1] + a1 * gg.b[2 * ch + 1]);
-                if (p.zero_acc) {
-                    r16::store_block(db + c * F, 2 * ch, q, f32x4{0, 0, 0, 0});
-                    r16::store_block(db + c * F, 2 * ch + 1, q, f32x4{0, 0, 0, 0});
-                    if (!FOLDED) {
-                        r16::store_block(cb + c * F, 2 * ch, q, f32x4{0, 0, 0, 0});
-                        r16::store_block(cb + c * F, 2 * ch + 1, q, f32x4{0, 0, 0, 0});
-                    }
-                }
-            }
-            pipe.release();
-        }
-    }
-    // ---- phase D: P for the next message block
-    if (HAS_NEXT) {
-        OP sn;
-        float psc;
-        {
-            psc = sn.set_scaled(snew);               // the rows written above, still in registers
-        }
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
-            r16::gemm_bt(a0, a1, sn, wl, lane);
-            a0 = r16::load_block(vec + UV::PB0 * F, 2 * ch, q) + a0 * psc; a1 = r16::load_block(vec + UV::PB0 * F, 2 * ch + 1, q) + a1 * psc;
-            pipe.release();
-            if (ok) { r16::store_state<H16>(p.P, nd * F, 2 * ch, q, a0); r16::store_state<H16>(p.P, nd * F, 2 * ch + 1, q, a1); }
-        }
-    }
-    pipe.drain();
-}
+// layer 0's update after an embed per class (painn_host.hip): s comes in through the class map (painn_update_kernel_body.inc: SCLS)
+template <int NBK, bool HAS_NEXT, int PREC = 1, bool FOLDED = false>
+__global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_cls_kernel(const UpdateParams p)
+#define TI_UPDATE_SCLS true
+#include "painn_update_kernel_body.inc"
+#undef TI_UPDATE_SCLS
 
 // ================================================================================================== embed / readout kernels
 // embed:   s = MLP([atom_emb | enc(T0) | enc(T1) | enc(t)]),  P = s @ phi0.W0[:, :F]^T + phi0.b0
@@ -254,102 +58,16 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_kernel(c
 // TV: the time of node nd is p.tv[nd / A] (one time per molecule, the reference's per-node batch.t); else the scalar p.t.
 template <int NBK, int NSEG, int PREC, bool TV = false>
 __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_embed16_kernel(const EmbedParams p)
-{
-    constexpr bool H16 = PREC == 2;
-    constexpr int F = 16 * NBK, NB = (F + 31) / 32, WAVES = 4, T = 64 * WAVES, CH4 = update_chunk4(NB, H16);
-    using A16 = r16::Act<NBK>;
-    using OP = typename r16::OpSel<NBK, PREC>::type;
-    extern __shared__ f32x4 lds[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = lane & 15, q = lane >> 4;
-    PipeDMA<NB, T, 2, CH4> pipe;
-    pipe.init(reinterpret_cast<const f32x4*>(p.stream), p.nch, lds, wave, lane);
-    const long long node = ((long long)blockIdx.x * WAVES + wave) * 16 + j;
-    const bool ok = node < p.N;
-    const long long nd = ok ? node : p.N - 1;
+#define TI_EMBED_REP false
+#include "painn_embed_kernel_body.inc"
+#undef TI_EMBED_REP
 
-    A16 acc;
-#pragma unroll
-    for (int nb = 0; nb < NBK; ++nb) acc.b[nb] = r16::load_block(p.mlp.b0, nb, q);
-#pragma unroll
-    for (int seg = 0; seg < NSEG; ++seg) {
-        OP op;
-        float sc = 1.0f;
-        {
-            A16 in;
-            if (seg == 0) {
-                r16::load_set(in, p.atom_emb + (size_t)p.atom_ids[nd % p.A] * F, q);
-                sc = op.set_scaled(in);                          // an embedding table: any magnitude
-            } else if (seg < NSEG - 1) {
-                // TemperatureEncoder.forward: (T - mean(temps)) / (max - min), then PositionalEncoder(max_length=temp_length)
-                float u = p.cond[nd * p.ncond + (seg - 1)] - p.temp_mean;
-                u = u / p.temp_range;
-                r16::posenc_set(in, u / p.temp_length, q);
-                op.set(in);
-            } else {
-                const float tn = TV ? p.tv[nd / p.A] : p.t;     // batch.t = t * ones_like(atoms), or one t per molecule
-                r16::posenc_set(in, tn / p.time_length, q);
-                op.set(in);
-            }
-        }
-        const float inv = r16::pow2_inverse(sc);
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-            f32x4 a0 = acc.b[2 * ch] * inv, a1 = acc.b[2 * ch + 1] * inv;     // exact: sc is a power of two
-            r16::gemm_bt(a0, a1, op, wl, lane);
-            acc.b[2 * ch] = a0 * sc; acc.b[2 * ch + 1] = a1 * sc;
-            pipe.release();
-        }
-    }
-    r16::ln_silu(acc, p.mlp.g0, p.mlp.be0, q);
-    A16 t;
-    {
-        OP h1;
-        h1.set(acc);
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-            f32x4 a0 = r16::load_block(p.mlp.b1, 2 * ch, q), a1 = r16::load_block(p.mlp.b1, 2 * ch + 1, q);
-            r16::gemm_bt(a0, a1, h1, wl, lane);
-            t.b[2 * ch] = a0; t.b[2 * ch + 1] = a1;
-            pipe.release();
-        }
-    }
-    r16::ln_silu(t, p.mlp.g1, p.mlp.be1, q);
-    A16 sset;
-    {
-        OP h2;
-        h2.set(t);
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-            f32x4 a0 = r16::load_block(p.mlp.b2, 2 * ch, q), a1 = r16::load_block(p.mlp.b2, 2 * ch + 1, q);
-            r16::gemm_bt(a0, a1, h2, wl, lane);
-            sset.b[2 * ch] = a0; sset.b[2 * ch + 1] = a1;
-            pipe.release();
-        }
-    }
-    if (ok) {
-#pragma unroll
-        for (int nb = 0; nb < NBK; ++nb) r16::store_state<H16>(p.s, (size_t)node * F, nb, q, sset.b[nb]);
-    }
-    {
-        OP sn;
-        const float psc = sn.set_scaled(sset), pinv = r16::pow2_inverse(psc);
-#pragma unroll
-        for (int ch = 0; ch < NB; ++ch) {
-            const f32x4* wl = pipe.acquire();
-            f32x4 a0 = r16::load_block(p.pb0, 2 * ch, q) * pinv, a1 = r16::load_block(p.pb0, 2 * ch + 1, q) * pinv;
-            r16::gemm_bt(a0, a1, sn, wl, lane);
-            pipe.release();
-            if (ok) {
-                r16::store_state<H16>(p.P, (size_t)node * F, 2 * ch, q, a0 * psc);
-                r16::store_state<H16>(p.P, (size_t)node * F, 2 * ch + 1, q, a1 * psc);
-            }
-        }
-    }
-    pipe.drain();
-}
+// the embed launch over (class, atom) rows alone (painn_embed_kernel_body.inc: REP)
+template <int NBK, int NSEG, int PREC = 1, bool TV = false>
+__global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_embed16_cls_kernel(const EmbedParams p)
+#define TI_EMBED_REP true
+#include "painn_embed_kernel_body.inc"
+#undef TI_EMBED_REP
 
 template <int NBK, int PREC>
 __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_readout16_kernel(const ReadoutParams p)
@@ -432,9 +150,11 @@ static size_t node16_lds_bytes(int NB, bool h16) { return 2 * 2 * (size_t)update
 // The three node kernels and their builds: every width x precision (prec: include/ti_hip.h TI_PREC_*; 0 f32, 1 f16x2, 2 f16 storage
 // mode: the state tensors are fp16), and per kernel two more arguments (n, flag):
 //   embed16: NSEG = 2, 3, 4 x TV;   update: HAS_NEXT x FOLDED, FOLDED only where the pair kernel folds (pair_folds_cross);   readout: (0, false)
-enum NodeKernel { NODE_EMBED, NODE_UPDATE, NODE_READOUT };
-constexpr bool node_build_exists(NodeKernel k, int PREC, int n, bool flag)
+enum NodeKernel { NODE_EMBED, NODE_UPDATE, NODE_READOUT, NODE_EMBED_CLS, NODE_UPDATE_CLS };
+// the per-class builds (embed per class and the first update after it): where the layer-0 phi table exists, (n, false) as their twins
+constexpr bool node_build_exists(NodeKernel k, int nb, int PREC, int n, bool flag)
 {
+    if (k == NODE_EMBED_CLS || k == NODE_UPDATE_CLS) return pair_table_build_exists(nb, PREC, false) && !flag && (k == NODE_EMBED_CLS ? n >= 2 : n <= 1);
     return k == NODE_EMBED ? n >= 2 : k == NODE_UPDATE ? n <= 1 && (!flag || pair_folds_cross(PREC)) : n == 0 && !flag;
 }
 template <NodeKernel K, int NBK, int PREC, int N, bool FLAG>
@@ -442,6 +162,8 @@ constexpr auto node_kernel()
 {
     if constexpr (K == NODE_EMBED) return painn_embed16_kernel<NBK, N, PREC, FLAG>;
     else if constexpr (K == NODE_UPDATE) return painn_update_kernel<NBK, N != 0, PREC, FLAG>;
+    else if constexpr (K == NODE_EMBED_CLS) return painn_embed16_cls_kernel<NBK, N>;
+    else if constexpr (K == NODE_UPDATE_CLS) return painn_update_cls_kernel<NBK, N != 0>;
     else return painn_readout16_kernel<NBK, PREC>;
 }
 // The visitor of the family: f(kernel, LDS bytes) for every build of kernel K that the values select (EVERY: all of them, dispatch.hpp),
@@ -454,9 +176,9 @@ static hipError_t with_node_builds(int NB, int prec, int n, int flag, F&& f)
     dispatch_int<1, 2, 4, 8>(NB, [&](auto bc) { dispatch_int<0, 1, 2>(prec, [&](auto pc) { dispatch_int<0, 1, 2, 3, 4>(n, [&](auto nc) { dispatch_bool(flag, [&](auto fc) {
         constexpr int nb = decltype(bc)::value, PREC = decltype(pc)::value, N = decltype(nc)::value;
         constexpr bool FLAG = decltype(fc)::value;
-        if constexpr (node_build_exists(K, PREC, N, FLAG)) {
+        if constexpr (node_build_exists(K, nb, PREC, N, FLAG)) {
             any = true;
-            if (e == hipSuccess) e = f(node_kernel<K, 2 * nb, PREC, N, FLAG>(), K == NODE_UPDATE ? update_lds_bytes(nb, PREC == 2) : node16_lds_bytes(nb, PREC == 2));
+            if (e == hipSuccess) e = f(node_kernel<K, 2 * nb, PREC, N, FLAG>(), K == NODE_UPDATE || K == NODE_UPDATE_CLS ? update_lds_bytes(nb, PREC == 2) : node16_lds_bytes(nb, PREC == 2));
         }
     }); }); }); });
     return any ? e : hipErrorInvalidValue;
@@ -490,6 +212,10 @@ hipError_t configure_painn_kernels(int NB)
     if ((e = configure_node<NODE_EMBED>(NB)) != hipSuccess) return e;
     if ((e = configure_node<NODE_UPDATE>(NB)) != hipSuccess) return e;
     if ((e = configure_node<NODE_READOUT>(NB)) != hipSuccess) return e;
+    if (pair_table_build_exists(NB, TI_PREC_F16X2, false)) {
+        if ((e = configure_node<NODE_EMBED_CLS>(NB)) != hipSuccess) return e;
+        if ((e = configure_node<NODE_UPDATE_CLS>(NB)) != hipSuccess) return e;
+    }
     if ((e = configure_phi0_kernels(NB)) != hipSuccess) return e;
     return with_message_units(NB, EVERY, [](auto bc, auto mc) {
         constexpr int nb = decltype(bc)::value;
@@ -501,6 +227,7 @@ hipError_t configure_painn_kernels(int NB)
                 if (e == hipSuccess) e = configure_pair_unit<nb, false, true>();
                 if (e == hipSuccess) e = configure_pair_unit<nb, false, false, true>();
                 if (e == hipSuccess) e = configure_pair_unit<nb, false, true, true>();
+                if (e == hipSuccess) e = configure_pair_tails_unit<nb>();
             }
         }
         return e;
@@ -509,10 +236,12 @@ hipError_t configure_painn_kernels(int NB)
 
 hipError_t launch_embed(int NB, int nseg, int prec, const EmbedParams& p, hipStream_t st)
 {
+    if (p.rep) return p.tv ? hipErrorInvalidValue : launch_node<NODE_EMBED_CLS>(NB, prec, nseg, false, p, st);
     return launch_node<NODE_EMBED>(NB, prec, nseg, p.tv != nullptr, p, st);
 }
 hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded)
 {
+    if (p.s_cls) return folded ? hipErrorInvalidValue : launch_node<NODE_UPDATE_CLS>(NB, prec, has_next, false, p, st);
     return launch_node<NODE_UPDATE>(NB, prec, has_next, folded, p, st);
 }
 hipError_t launch_readout(int NB, int prec, const ReadoutParams& p, hipStream_t st) { return launch_node<NODE_READOUT>(NB, prec, 0, false, p, st); }
@@ -530,7 +259,7 @@ hipError_t launch_pair(int NB, bool first, bool last, int prec, const EdgeParams
             if (seeded) {          // the general blocks first: they store; the kernel boundary orders the tile launch's adds behind them
                 EdgeParams g = p;
                 g.row_stride = 0;
-                hipError_t e = launch_pair_unit<nb, false, true, true>(first, last, prec, g, st, table);
+                hipError_t e = p.tail_S > 0 ? launch_pair_tails_unit<nb>(first, last, g, st, table) : launch_pair_unit<nb, false, true, true>(first, last, prec, g, st, table);
                 return e == hipSuccess ? launch_pair_unit<nb, false, false, true>(first, last, prec, p, st, table) : e;
             }
             hipError_t e = p.n_tile > 0 ? launch_pair_unit<nb, decltype(mc)::value, false>(first, last, prec, p, st, table) : hipSuccess;

@@ -253,6 +253,12 @@ bool build_pair_template(ti_handle* h, const int32_t* src, const int32_t* dst, c
     // triage switch, read like TI_PAIR_PACKED: TI_PAIR_SEEDED=0 at creation keeps the first-touch order on a seeded template
     h->pair_seeded = pt.seeded; h->pair_seeded_on = pt.seeded;
     if (const char* z = std::getenv("TI_PAIR_SEEDED")) if (z[0] == '0') h->pair_seeded_on = false;
+    // merged tails of the seeded general launch: where the template has them and the kernel takes them (whole lane rows per group: r a
+    // multiple of 4); TI_PAIR_TAILS=0 at creation, read the same way, keeps the walk of one group per wave
+    const ti::PairTails tails = ti::pair_template_tails(pt, h->d.n_atoms);
+    h->pair_tail_S = tails.r % 4 == 0 ? tails.S : 0; h->pair_tail_r = tails.r % 4 == 0 ? tails.r : 0;
+    h->pair_tails_on = h->pair_tail_S > 0;
+    if (const char* z = std::getenv("TI_PAIR_TAILS")) if (z[0] == '0') h->pair_tails_on = false;
     return true;
 }
 
@@ -439,6 +445,9 @@ void pack_painn(ti_handle* h, const float* wts)
                 h->phi0_ok = true;
                 // triage switch, read like TI_ZERO_ACC: TI_PHI0_TABLE=0 at creation pins the kernels of before
                 if (const char* z = std::getenv("TI_PHI0_TABLE")) if (z[0] == '0') h->phi0_ok = false;
+                // and, read the same way, TI_EMBED_CLASSES=0: the table path keeps the embed launch over every atom
+                h->embed_cls_on = true;
+                if (const char* z = std::getenv("TI_EMBED_CLASSES")) if (z[0] == '0') h->embed_cls_on = false;
             }
         }
         o = begin_stream();                          // update kernel: 16-row chunk format, order of painn_update_kernel

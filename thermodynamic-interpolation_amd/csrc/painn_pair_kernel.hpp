@@ -57,10 +57,12 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_kernel(c
 #define TI_PAIR_ROWS p.rows
 #define TI_PAIR_GENERAL false
 #define TI_PAIR_SEEDED false
+#define TI_PAIR_TAILS false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
 #undef TI_PAIR_SEEDED
+#undef TI_PAIR_TAILS
 
 // Per-molecule edge sets (ti_painn_set_edge_mask): p.rows holds row words PER group (painn_pack.hip: masked_rows), in which a pair absent
 // from its molecule is invalid -- zeroed through the shared w factor, like a pair that does not exist.  Both directions share that
@@ -71,10 +73,12 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_mask_ker
 #define TI_PAIR_ROWS (p.rows + (size_t)gi * p.nblk * 16)
 #define TI_PAIR_GENERAL false
 #define TI_PAIR_SEEDED false
+#define TI_PAIR_TAILS false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
 #undef TI_PAIR_SEEDED
+#undef TI_PAIR_TAILS
 
 // The general blocks [p.n_tile, p.nblk) of a packed template (pair_template.hpp), every row adding to its own two atoms; the two kernels
 // above walk the tile blocks [0, p.n_tile).  Same body, same weight stream (cyclic per row block), same e / enc / geo rows.  One kernel
@@ -84,10 +88,12 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_general_
 #define TI_PAIR_ROWS (p.rows + (size_t)gi * p.row_stride)
 #define TI_PAIR_GENERAL true
 #define TI_PAIR_SEEDED false
+#define TI_PAIR_TAILS false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
 #undef TI_PAIR_SEEDED
+#undef TI_PAIR_TAILS
 
 // The SEEDED builds (painn_pair_kernel_body.inc): a seeded template (pair_template.hpp) on the split path, plain batches -- no edge mask,
 // one species.  The general launch of a layer runs FIRST and stores each row's two contributions, every atom's first of the layer; the
@@ -99,20 +105,41 @@ __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_seeded_k
 #define TI_PAIR_ROWS p.rows
 #define TI_PAIR_GENERAL false
 #define TI_PAIR_SEEDED true
+#define TI_PAIR_TAILS false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
 #undef TI_PAIR_SEEDED
+#undef TI_PAIR_TAILS
 
 template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
 __global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_general_seeded_kernel(const EdgeParams p)
 #define TI_PAIR_ROWS p.rows
 #define TI_PAIR_GENERAL true
 #define TI_PAIR_SEEDED true
+#define TI_PAIR_TAILS false
 #include "painn_pair_kernel_body.inc"
 #undef TI_PAIR_ROWS
 #undef TI_PAIR_GENERAL
 #undef TI_PAIR_SEEDED
+#undef TI_PAIR_TAILS
+
+// MERGED TAILS (painn_pair_kernel_body.inc: TAILS): the seeded general launch on a template whose last general block holds r valid
+// rows, r < 16 a multiple of 4 that divides 16 (pair_template.hpp: pair_template_tails; the twin rows of 18 atoms: r = 4).  One wave
+// owns S = 16 / r groups, walks their full general blocks and then their S last blocks as ONE: 9 blocks per 4 groups instead of 12 at
+// 18 atoms.  Storage, row words and results are those of painn_pair_general_seeded_kernel, bit for bit.  Split path only.
+// Instantiated in painn_pair_tails_nb*.hip.
+template <int NBK, bool FIRST, bool LAST, int PREC, int WAVES, bool TABLE = false>
+__global__ __launch_bounds__(64 * WAVES, 2 * 4 / WAVES) void painn_pair_general_tails_kernel(const EdgeParams p)
+#define TI_PAIR_ROWS p.rows
+#define TI_PAIR_GENERAL true
+#define TI_PAIR_SEEDED true
+#define TI_PAIR_TAILS true
+#include "painn_pair_kernel_body.inc"
+#undef TI_PAIR_ROWS
+#undef TI_PAIR_GENERAL
+#undef TI_PAIR_SEEDED
+#undef TI_PAIR_TAILS
 
 // The visitor of the family: f(kernel, waves, LDS bytes) for every build of width NB that the values select (EVERY: all of them,
 // dispatch.hpp), until one returns an error.  MASK: the masked twins (painn_pair_mask_kernel).  GENERAL: the builds of the general
@@ -161,6 +188,44 @@ hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p
     const bool wide = prec == 1 && p.n_groups >= 2048;
     return with_pair_builds<NB, MASK, GENERAL, SEEDED>(wide ? 8 : 4, prec, layer_pos(first, last) | (table ? POS_TABLE : 0), [&](auto kernel, int waves, size_t lds) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)((p.n_groups + waves - 1) / waves)), dim3(64 * waves), lds, st, p);      // one wave = one group of G molecules
+        return hipGetLastError();
+    });
+}
+
+// the merged-tails builds of one width: the visitor, configure and launch of painn_pair_general_tails_kernel, as above
+template <int NB, class F>
+static hipError_t with_pair_tails_builds(int waves, int pos, F&& f)
+{
+    hipError_t e = hipSuccess;
+    bool any = false;
+    dispatch_int<4, 8>(waves, [&](auto wc) {
+        constexpr int WAVES = decltype(wc)::value, PREC = TI_PREC_F16X2;
+        if constexpr (pair_build_exists(NB, WAVES, PREC) && pair_general_build_exists(PREC))
+            dispatch_int<POS_MIDDLE, POS_FIRST, POS_LAST, POS_ONLY, POS_FIRST_TABLE, POS_ONLY_TABLE>(pos, [&](auto oc) {
+                constexpr bool FIRST = (decltype(oc)::value & 1) != 0, LAST = (decltype(oc)::value & 2) != 0, TABLE = (decltype(oc)::value & 4) != 0;
+                if constexpr (!TABLE || pair_table_build_exists(NB, PREC, false)) {
+                    any = true;
+                    if (e == hipSuccess) e = f(painn_pair_general_tails_kernel<2 * NB, FIRST, LAST, PREC, WAVES, TABLE>, WAVES, pair_lds_bytes(NB, WAVES, PREC, TABLE, true));
+                }
+            });
+    });
+    return any ? e : hipErrorInvalidValue;
+}
+template <int NB>
+hipError_t configure_pair_tails_unit()
+{
+    return with_pair_tails_builds<NB>(EVERY, EVERY, [](auto kernel, int, size_t lds) { return set_lds(kernel, lds); });
+}
+// one wave = one super-group of p.tail_S groups; the wave count follows the rule of the launches above, so that a layer's general and
+// tile launch switch shapes at the same batch
+template <int NB>
+hipError_t launch_pair_tails_unit(bool first, bool last, const EdgeParams& p, hipStream_t st, bool table)
+{
+    if (table && !first) return hipErrorInvalidValue;
+    if (p.n_tile < 0 || p.n_tile >= p.nblk || p.tail_S < 2 || p.tail_r < 4 || p.tail_r % 4 || p.tail_S * p.tail_r != 16) return hipErrorInvalidValue;
+    const long long supers = (p.n_groups + p.tail_S - 1) / p.tail_S;
+    return with_pair_tails_builds<NB>(p.n_groups >= 2048 ? 8 : 4, layer_pos(first, last) | (table ? POS_TABLE : 0), [&](auto kernel, int waves, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((supers + waves - 1) / waves)), dim3(64 * waves), lds, st, p);
         return hipGetLastError();
     });
 }

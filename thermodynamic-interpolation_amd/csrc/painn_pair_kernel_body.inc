@@ -15,6 +15,14 @@
     // read; the tile launch after it (!GENERAL && SEEDED) finds every accumulator row seeded and only adds: no first touch
     constexpr bool SEEDED = TI_PAIR_SEEDED;
     static_assert(!SEEDED || pair_general_build_exists(PREC), "seeded accumulators: the split path, whose templates have general blocks");
+    // TAILS (painn_pair_general_tails_kernel: GENERAL && SEEDED on a template with merged tails, pair_template.hpp): one wave owns a
+    // SUPER-GROUP of S = p.tail_S groups.  It walks the full general blocks [n_tile, nblk - 1) of each of them as the seeded general
+    // build does, then ONE merged block for the S last blocks, which hold r = p.tail_r = 16 / S valid rows each: merged row j is row
+    // j % r of the last block of group j / r.  The owning group is then per lane -- j / r in the row layout, (4q) / r in the flipped
+    // one (r is a multiple of 4: the four rows of a lane row belong to one group) -- and so is everything derived from it.  A row's
+    // value does not depend on its block mates, every row keeps its storage, so the results are those of the unmerged walk bit for bit.
+    constexpr bool TAILS = TI_PAIR_TAILS;
+    static_assert(!TAILS || (GENERAL && SEEDED), "merged tails: the seeded general launch");
     constexpr int F = 16 * NBK, NB = (F + 31) / 32, T = 64 * WAVES, CH4 = edge_chunk4(NB, false);
     using A16 = r16::Act<NBK>;
     constexpr bool ONE = edge_one_chain(PREC);
@@ -33,9 +41,9 @@
     const float eps_w0 = ONE ? 1e-5f * p.wscale[0] * p.wscale[0] : 1e-5f, eps_w1 = ONE ? 1e-5f * p.wscale[1] * p.wscale[1] : 1e-5f;
     const float eps_p0 = ONE ? 1e-5f * p.wscale[2] * p.wscale[2] : 1e-5f, eps_p1 = ONE ? 1e-5f * p.wscale[3] * p.wscale[3] : 1e-5f;
     const float s_p0 = ONE ? p.wscale[2] : 1.0f, inv_out = ONE ? 1.0f / (p.wscale[4] * p.wscale[5]) : 1.0f;
-    const long long gi_raw = (long long)blockIdx.x * WAVES + wave;
-    const bool group_ok = gi_raw < p.n_groups;
-    const long long gi = group_ok ? gi_raw : p.n_groups - 1;
+    const long long gi_raw = (long long)blockIdx.x * WAVES + wave;                // TAILS: the wave's super-group, gi its first group
+    const bool group_ok = (TAILS ? gi_raw * p.tail_S : gi_raw) < p.n_groups;
+    const long long gi = group_ok ? (TAILS ? gi_raw * p.tail_S : gi_raw) : p.n_groups - 1;
     // The group's first node is the same for the whole wave, so the node arrays are addressed from per-group bases that live in scalar
     // registers, with the node inside the group (< G * A) as an unsigned 32-bit lane offset: the 64-bit part of every address is scalar
     // work (DESIGN.md 3.6)
@@ -54,10 +62,14 @@
     // TABLE: the classes of the group's molecules, four bits each, in one scalar word (molecules past the batch's end: the last one's),
     // and from them the offset of a (molecule in group, atom, edge type) row of the phi table
     unsigned clsw = 0;
-    if constexpr (TABLE)
+    if constexpr (TABLE && !TAILS)
         for (int m = 0; m < p.G; ++m) clsw |= (unsigned)p.cls[gi * p.G + ((unsigned)m < mol_cap ? (unsigned)m : mol_cap)] << (4 * m);
     auto tab_off = [&](int mol_local, int atom, int type) {
         const unsigned cls = (clsw >> (4 * mol_local)) & 15u;
+        return ((cls * (unsigned)p.A + (unsigned)atom) * (unsigned)PHI0_TYPES + (unsigned)type) * (unsigned)(3 * F);
+    };
+    auto tab_off_of = [&](unsigned word, int mol_local, int atom, int type) {      // TAILS: the class word is the lane's group's
+        const unsigned cls = (word >> (4 * mol_local)) & 15u;
         return ((cls * (unsigned)p.A + (unsigned)atom) * (unsigned)PHI0_TYPES + (unsigned)type) * (unsigned)(3 * F);
     };
 
@@ -76,19 +88,51 @@
 #define TI_STAMP() do { } while (0)
 #endif
 
-    for (int blk = blk_lo; blk < blk_hi; ++blk) {
+    // TAILS: the walk is S * (full general blocks) + 1 steps, the same for every wave of the workgroup (they share the weight ring);
+    // step `it` is block n_tile + it % n_full of group gi + it / n_full, the last step the merged block (stored as block nblk - 1)
+    const int n_full = TAILS ? p.nblk - 1 - p.n_tile : 1, n_walk = TAILS ? p.tail_S * n_full + 1 : 0;
+    const int tail_sh = TAILS ? __builtin_ctz((unsigned)p.tail_r) : 0;            // r is a power of two
+    auto walk_blk = [&](int it) { return it == n_walk - 1 ? p.nblk - 1 : p.n_tile + it % n_full; };
+    for (int blk = TAILS ? walk_blk(0) : blk_lo, it = 0; TAILS ? it < n_walk : blk < blk_hi; TAILS ? (void)(++it, blk = walk_blk(it)) : (void)++blk) {
         TI_STAMP();
+        // TAILS: who owns the rows of this step.  gi is the super-group's FIRST group and every per-group base above stays a scalar; the
+        // lane's group is gi + subR in the row layout (lane (j, q): row j) and gi + subF in the flipped one (rows 4q + r), and reaches
+        // the node arrays, the class map and the row storage (rsub rows on) as a 32-bit lane offset from those bases.  okR / okF: that
+        // group exists.  rowj / frow0: the rows' places in their block's storage.  Every other build: the wave's group, rows j, 4q + r.
+        int subR = 0, subF = 0, rowj = 0, frow0 = 0;
+        bool okR = false, okF = false;
+        unsigned rsub = 0, erow_l = 0, clswR = 0, clswF = 0;
+        if constexpr (TAILS) {
+            const bool merged = it == n_walk - 1;
+            subR = merged ? j >> tail_sh : it / n_full; subF = merged ? (4 * q) >> tail_sh : it / n_full;
+            okR = group_ok && gi + subR < p.n_groups; okF = group_ok && gi + subF < p.n_groups;
+            if (!okR) subR = 0;
+            if (!okF) subF = 0;
+            rowj = merged ? j & (p.tail_r - 1) : j; frow0 = merged ? (4 * q) & (p.tail_r - 1) : 4 * q;
+            rsub = (unsigned)(subR * p.nblk * 16);
+            erow_l = (2u * rsub + (unsigned)rowj) * (unsigned)F;             // the lane's e row from erowA / erowB
+            if constexpr (TABLE)
+                for (int m = 0; m < p.G; ++m) {
+                    const unsigned mR = (unsigned)(subR * p.G + m), mF = (unsigned)(subF * p.G + m);
+                    clswR |= (unsigned)p.cls[gi * p.G + (mR < mol_cap ? mR : mol_cap)] << (4 * m);
+                    clswF |= (unsigned)p.cls[gi * p.G + (mF < mol_cap ? mF : mol_cap)] << (4 * m);
+                }
+        }
+        auto lnode_r = [&](int mol_local, int atom) { return lnode_of(subR * p.G + mol_local, atom); };
+        auto lnode_f = [&](int mol_local, int atom) { return lnode_of(subF * p.G + mol_local, atom); };
         // ---- K1 geometry of this lane's pair row (the 4 quarters compute the same row); direction A: r = x[I] - x[J]
-        const uint32_t meta = TI_PAIR_ROWS[blk * 16 + j];
-        const unsigned lI = lnode_of(prow_molI(meta), prow_atomI(meta)), lJ = lnode_of(prow_molJ(meta), prow_atomJ(meta));   // the row's two nodes inside the group
+        const uint32_t meta = TI_PAIR_ROWS[blk * 16 + (TAILS ? rowj : j)];
+        const unsigned lI = TAILS ? lnode_r(prow_molI(meta), prow_atomI(meta)) : lnode_of(prow_molI(meta), prow_atomI(meta)), lJ = TAILS ? lnode_r(prow_molJ(meta), prow_atomJ(meta)) : lnode_of(prow_molJ(meta), prow_atomJ(meta));   // the row's two nodes inside the group
         // row_ok: this lane's pair row exists.  A row that does not contributes nothing (w factor 0) and no valid row reads its e row,
         // its parked encoding or its edge_dir: it loads none of them (zeros instead) and stores none
-        const bool row_ok = (meta & 1u) != 0;
+        // (TAILS: nor does a row of a group past the batch's end)
+        const bool row_ok = TAILS ? (meta & 1u) != 0 && okR : (meta & 1u) != 0;
         const size_t brow0 = ((size_t)gi * p.nblk + blk) * 16;       // pair rows: parked encoding / edge_dir
         const size_t erowA = brow0 * 2, erowB = erowA + 16;             // e rows of the two directions
         OP enc;
-        f32x4* const enc_park = reinterpret_cast<f32x4*>(p.enc) + (brow0 / 16) * (sizeof(OP) / 16) * 64 + lane;
-        f32x4* const geo_park = reinterpret_cast<f32x4*>(p.geo) + brow0 + j;
+        f32x4* const enc_park = TAILS ? reinterpret_cast<f32x4*>(p.enc) + (brow0 / 16) * (sizeof(OP) / 16) * 64 + ((rsub / 16) * (unsigned)(sizeof(OP) / 16 * 64) + (unsigned)(16 * q + rowj))
+                                      : reinterpret_cast<f32x4*>(p.enc) + (brow0 / 16) * (sizeof(OP) / 16) * 64 + lane;
+        f32x4* const geo_park = TAILS ? reinterpret_cast<f32x4*>(p.geo) + brow0 + (rsub + (unsigned)rowj) : reinterpret_cast<f32x4*>(p.geo) + brow0 + j;
         if constexpr (FIRST) {
             const float* const xI = x_g + lI * 3u;
             const float* const xJ = x_g + lJ * 3u;
@@ -100,12 +144,12 @@
             if (q == 0) {
                 f32x4 dd = {rx / den, ry / den, rz / den, 0.f};
                 *reinterpret_cast<f32x4*>(scratch + j * 4) = dd;
-                if (group_ok && row_ok) *geo_park = dd;
+                if ((TAILS ? okR : group_ok) && row_ok) *geo_park = dd;
             }
             A16 t;
             r16::posenc_set(t, dist / p.length_scale, q);
             enc.set(t);
-            if (group_ok && row_ok) r16::opnd_store(enc, enc_park);
+            if ((TAILS ? okR : group_ok) && row_ok) r16::opnd_store(enc, enc_park);
         } else {
             if (q == 0) {
                 f32x4 dd = {0.f, 0.f, 0.f, 0.f};
@@ -158,8 +202,8 @@
 #pragma unroll
                 for (int nb = 0; nb < NBK; ++nb) { tA.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; tB.b[nb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
                 if (row_ok) {
-                    r16::load_set(tA, p.e + erowA * F + (unsigned)(j * F), q);
-                    r16::load_set(tB, p.e + erowB * F + (unsigned)(j * F), q);
+                    r16::load_set(tA, p.e + erowA * F + (TAILS ? erow_l : (unsigned)(j * F)), q);
+                    r16::load_set(tB, p.e + erowB * F + (TAILS ? erow_l : (unsigned)(j * F)), q);
                 }
                 scA = inA.set_scaled(tA);                                    // e is an un-normalised stream: per-row 2^k
                 scB = inB.set_scaled(tB);
@@ -200,7 +244,7 @@
         // ---- output layer, flipped: features on lanes (l & 15), pair rows 4q + r in registers: I slot q, J slots r
         uint32_t mi[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) mi[r] = TI_PAIR_ROWS[blk * 16 + 4 * q + r];
+        for (int r = 0; r < 4; ++r) mi[r] = TI_PAIR_ROWS[blk * 16 + (TAILS ? frow0 + r : 4 * q + r)];
         f32x4 wfac;                                      // row mask x 1 / (S_phi S_w): rides on the shared w factor
 #pragma unroll
         for (int r = 0; r < 4; ++r) wfac[r] = (mi[r] & 1u) ? inv_out : 0.0f;
@@ -222,8 +266,13 @@
         if constexpr (GENERAL) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                gI[r] = lnode_of(prow_molI(mi[r]), prow_atomI(mi[r])); gJ[r] = lnode_of(prow_molJ(mi[r]), prow_atomJ(mi[r]));
-                gok[r] = group_ok && (mi[r] & 1u) != 0 && gi * p.G + prow_molI(mi[r]) < p.B;
+                if constexpr (TAILS) {
+                    gI[r] = lnode_f(prow_molI(mi[r]), prow_atomI(mi[r])); gJ[r] = lnode_f(prow_molJ(mi[r]), prow_atomJ(mi[r]));
+                    gok[r] = okF && (mi[r] & 1u) != 0 && (gi + subF) * p.G + prow_molI(mi[r]) < p.B;
+                } else {
+                    gI[r] = lnode_of(prow_molI(mi[r]), prow_atomI(mi[r])); gJ[r] = lnode_of(prow_molJ(mi[r]), prow_atomJ(mi[r]));
+                    gok[r] = group_ok && (mi[r] & 1u) != 0 && gi * p.G + prow_molI(mi[r]) < p.B;
+                }
             }
         }
         // both directions of the lane's four rows: direction A's value goes to the row's J atom, direction B's to its I atom, plain adds
@@ -252,11 +301,11 @@
         if constexpr (TABLE) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                tfA[r] = tab_off(prow_molI(mi[r]), prow_atomI(mi[r]), prow_type(mi[r])) + (unsigned)j;
-                tfB[r] = tab_off(prow_molJ(mi[r]), prow_atomJ(mi[r]), prow_type(mi[r])) + (unsigned)j;
+                tfA[r] = (TAILS ? tab_off_of(clswF, prow_molI(mi[r]), prow_atomI(mi[r]), prow_type(mi[r])) : tab_off(prow_molI(mi[r]), prow_atomI(mi[r]), prow_type(mi[r]))) + (unsigned)j;
+                tfB[r] = (TAILS ? tab_off_of(clswF, prow_molJ(mi[r]), prow_atomJ(mi[r]), prow_type(mi[r])) : tab_off(prow_molJ(mi[r]), prow_atomJ(mi[r]), prow_type(mi[r]))) + (unsigned)j;
             }
-            trA = tab_off(prow_molI(meta), prow_atomI(meta), prow_type(meta));
-            trB = tab_off(prow_molJ(meta), prow_atomJ(meta), prow_type(meta));
+            trA = TAILS ? tab_off_of(clswR, prow_molI(meta), prow_atomI(meta), prow_type(meta)) : tab_off(prow_molI(meta), prow_atomI(meta), prow_type(meta));
+            trB = TAILS ? tab_off_of(clswR, prow_molJ(meta), prow_atomJ(meta), prow_type(meta)) : tab_off(prow_molJ(meta), prow_atomJ(meta), prow_type(meta));
         }
 
         // (phi_c + b) of both directions times the shared (w_c + b) for output slice c (0 gates, 1 scale_edge_dir, 2 ds, 3 de,
@@ -357,8 +406,8 @@
                 f32x4 a0 = r16::load_block(vec + (EV::P_B2 + 3) * F, 2 * nbo, q), a1 = r16::load_block(vec + (EV::P_B2 + 3) * F, 2 * nbo + 1, q);
                 f32x4 b0 = a0, b1 = a1;
                 f32x4 w0 = r16::load_block(vec + (EV::W_B2 + 3) * F, 2 * nbo, q), w1 = r16::load_block(vec + (EV::W_B2 + 3) * F, 2 * nbo + 1, q);
-                float* const ea = p.e + erowA * F + (unsigned)(j * F);
-                float* const eb = p.e + erowB * F + (unsigned)(j * F);
+                float* const ea = p.e + erowA * F + (TAILS ? erow_l : (unsigned)(j * F));
+                float* const eb = p.e + erowB * F + (TAILS ? erow_l : (unsigned)(j * F));
                 f32x4 oA0, oA1, oB0, oB1;
                 if (FIRST) {
                     const float* em = p.edge_emb + prow_type(meta) * F;
@@ -380,7 +429,7 @@
                 r16::gemm_on_pipe<false>(w0, w1, g2, pipe, lane);
                 pipe.release();
                 w0 *= wrow; w1 *= wrow;
-                if (group_ok && row_ok) {
+                if ((TAILS ? okR : group_ok) && row_ok) {
                     r16::store_block(ea, 2 * nbo, q, oA0 + a0 * w0); r16::store_block(ea, 2 * nbo + 1, q, oA1 + a1 * w1);
                     r16::store_block(eb, 2 * nbo, q, oB0 + b0 * w0); r16::store_block(eb, 2 * nbo + 1, q, oB1 + b1 * w1);
                 }

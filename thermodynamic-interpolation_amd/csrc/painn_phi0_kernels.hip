@@ -6,7 +6,7 @@
 //   * painn_phi0_class_kernel gives every molecule of a call a class id -- molecules whose A x ncond cond values are bitwise equal share
 //     one -- once per API call, whatever the order of the molecules;
 //   * painn_phi0_table_kernel evaluates, after every embed launch, the branch once per (class, atom, edge type) from P of the class's
-//     representative with the pair kernel's own primitives, operand formats, chain order and product orientations, and writes its
+//     representative (embed per class, painn_host.hip: from the class's rows of P_cls) with the pair kernel's own primitives, operand formats, chain order and product orientations, and writes its
 //     three live output slices, bias included, to a table the TABLE builds of the pair kernel read instead of computing them per pair.
 // A row's result does not depend on the rows it shares a tile with, so every entry is bit for bit what the pair kernel computes.
 #include "painn_edge_kernel.hpp"
@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256) void painn_phi0_table_kernel(const Phi0TablePa
     const int n_rows = p.n_cls * p.A * PHI0_TYPES, row0 = (blockIdx.x * WAVES + wave) * 16;      // rows past the table's end compute its last row and store nothing
     const int row = row0 + j < n_rows ? row0 + j : n_rows - 1;
     const int type = row % PHI0_TYPES, atom = (row / PHI0_TYPES) % p.A, cls = row / (PHI0_TYPES * p.A);
-    const float* const PI = p.P + ((size_t)p.state[cls] * p.A + atom) * F;
+    // the class's P rows: its representative's in the full P, or (no p.state: embed per class) row `cls` of the compact P_cls
+    const float* const PI = p.P + ((size_t)(p.state ? p.state[cls] : cls) * p.A + atom) * F;
 
     OP h2A;
     {

@@ -62,6 +62,29 @@ inline bool pair_template_seeded(const PairTemplate& t, int A)
     return true;
 }
 
+// MERGED TAILS: a seeded template whose LAST general block holds r valid rows -- its leading ones -- with r < 16 and 16 % r == 0.  The
+// last blocks of S = 16 / r neighbouring groups then fill one block between them: merged row j is row j % r of the last block of
+// group j / r of the S (painn_pair_kernel.hpp: painn_pair_general_tails_kernel walks them so; storage and row words stay as they are).
+// Counted from the row words, like pair_template_seeded: the twin rows of 18 atoms at G = 4 leave r = 4 (36 = 16 + 16 + 4), S = 4.
+// r == 0: no merge.
+struct PairTails {
+    int r = 0, S = 0;
+    std::vector<std::array<int, 3>> map;      // [16] merged row -> (group in super-group, block, row in block)
+};
+inline PairTails pair_template_tails(const PairTemplate& t, int A)
+{
+    PairTails out;
+    if (!pair_template_seeded(t, A)) return out;
+    const size_t last = (size_t)(t.nblk - 1) * 16;
+    int r = 0;
+    for (int k = 0; k < 16; ++k) r += (int)(t.rows[last + k] & 1u);
+    if (r <= 0 || r >= 16 || 16 % r) return out;
+    for (int k = 0; k < r; ++k) if (!(t.rows[last + k] & 1u)) return out;      // valid rows lead the block
+    out.r = r; out.S = 16 / r;
+    for (int j = 0; j < 16; ++j) out.map.push_back({j / r, t.nblk - 1, j % r});
+    return out;
+}
+
 namespace pair_detail {
 struct Blk {
     int I[4], J[4];                          // slot keys mol * 32 + atom, -1 = empty

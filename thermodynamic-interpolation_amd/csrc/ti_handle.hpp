@@ -97,6 +97,11 @@ struct ti_handle {
     // plain stores, and tile launches that only add -- unless TI_PAIR_SEEDED=0 was in the environment at creation (same-binary A/B
     // runs, triage).  Plain split-path evaluations only (painn_host.hip).  seeded_last: what ti_painn_debug_pair_seeded reports.
     bool pair_seeded = false, pair_seeded_on = false; int seeded_last = -1;
+    // merged tails (pair_template.hpp: pair_template_tails).  pair_tail_S / pair_tail_r: groups per super-group and valid rows of the
+    // last general block, 0 when the template has none the kernel takes.  pair_tails_on: the seeded general launch then walks super-
+    // groups, the S last blocks as one -- unless TI_PAIR_TAILS=0 was in the environment at creation.  tails_last: what
+    // ti_painn_debug_pair_tails reports.
+    int pair_tail_S = 0, pair_tail_r = 0; bool pair_tails_on = false; int tails_last = -1;
     int n_tpl = 1, active = 0, parts = 1, max_slots = 0, pinned_tpl = TI_TEMPLATE_AUTO;
     // every atom has incoming edges: the edge kernels' first touch of an accumulator replaces its contents (ti_internal.hpp
     // SLOT_FIRST_TOUCH) and nothing zeroes the accumulators between layers or calls; otherwise the update kernel zeroes them as before
@@ -131,6 +136,12 @@ struct ti_handle {
     bool phi0_ok = false; Stream st_phi0_w{}, st_phi0_tab{}; int phi0_wpad = 0;
     DevBuf<uint8_t> phi0_cls; DevBuf<int32_t> phi0_state; DevBuf<float> phi0_tab;
     int phi0_ncls = 0, phi0_found = 0, phi0_last = -1; long long phi0_B = 0; const float* phi0_cond = nullptr;
+    // embed per class: on the table path only the table kernel (P of the representatives) and layer 0's update (s, once)
+    // read the embedding, and the rows of a class agree bit for bit.  embed_cls_on: the embed launch of such an evaluation then covers
+    // the classes alone -- s_cls / P_cls [class][atom][F] -- and layer 0's update reads s through phi0_cls; the full s / P are first
+    // written by that update.  Off with TI_EMBED_CLASSES=0 in the environment at creation (same-binary A/B runs, triage).
+    // embed_cls_last: what ti_painn_debug_embed_path reports.
+    bool embed_cls_on = false; int embed_cls_last = -1; DevBuf<float> s_cls, P_cls;
     // forward-mode derivative (painn_jvp_kernels.hip): tangent twins over virtual molecules, sized on first use
     std::vector<Stream> st_jvp_update, st_jvp_phi; Stream st_jvp_readout{}; std::vector<int> jvp_phi_pad;
     DevBuf<float> jvp_ro_vecs, ts, tP, tv, tdsacc, tdvacc, tcacc, te, tout, wq, phist, nodest, divb, dl, dlscaled, div2;

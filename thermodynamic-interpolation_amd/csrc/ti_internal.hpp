@@ -89,6 +89,9 @@ struct EdgeParams {
     const float* phi0_tab;                  // [class][A][PHI0_TYPES][3][F]: ds | scale_edge_dir | de slices of the phi branch, bias included
     const uint8_t* cls;                     // [B] class of every molecule (painn_phi0_kernels.hip)
     int wpad;                               // the w-only stream ends with a pad chunk (odd count), swallowed once per row block
+    // merged tails (painn_pair_general_tails_kernel; pair_template.hpp: pair_template_tails; 0 for every other launch): a wave owns
+    // tail_S groups, whose last general blocks hold tail_r = 16 / tail_S valid rows each and are walked as one block
+    int tail_S, tail_r;
 };
 
 // ---- layer-0 phi table (painn_phi0_kernels.hip; include/ti_hip.h TI_PHI0_MAX_CLASSES)
@@ -105,8 +108,8 @@ struct Phi0ClassParams {
 struct Phi0TableParams {
     const float4* stream; int nch;          // the phi chunks of layer 0 alone (painn_pack.hip: st_phi0_tab)
     const float* vecs; const float* edge_emb; float wscale[6];      // as EdgeParams (one-accumulator format)
-    const float* P;                         // [B*A][F] of this evaluation's embed launch
-    const int32_t* state;                   // class representatives
+    const float* P;                         // [B*A][F] of this evaluation's embed launch; state == NULL: the compact P_cls [n_cls*A][F]
+    const int32_t* state;                   // class representatives; NULL: P holds the classes' rows themselves (embed per class)
     int n_cls, A;
     float* tab;
 };
@@ -124,6 +127,7 @@ struct EmbedParams {
     float t, temp_length, time_length, temp_mean, temp_range;
     const float* tv;                        // non-NULL: per-molecule times [B] (node nd reads tv[nd / A]) instead of t
     float* s; float* P;
+    const int32_t* rep;                     // REP builds: class representatives; node n = (class, atom) reads molecule rep[n / A]'s cond rows, s / P are [n_cls*A][F]
 };
 
 struct UpdateParams {
@@ -133,6 +137,8 @@ struct UpdateParams {
     float *s, *v, *dsacc, *dvacc, *cacc, *P;
     int first_layer;                        // v and cacc are zero by definition (nothing has written them yet): not read
     int zero_acc;                           // reset the accumulators after use (0 when the edge kernels overwrite on first touch)
+    // SCLS builds (layer 0 after an embed per class): the incoming s is s_cls[cls[node / A]][node % A] instead of s[node]
+    const float* s_cls; const uint8_t* cls; int A;
 };
 
 struct ReadoutParams {
@@ -144,6 +150,7 @@ struct ReadoutParams {
 
 // launchers (painn_kernels.hip).  F = 32*NB; return hipError_t of the launch.
 // prec = TI_PREC_* of include/ti_hip.h; with TI_PREC_F16 the state tensors s, P, v, e behind the float* fields are fp16
+// p.rep non-NULL: the per-class build (f16x2, scalar t), p.N = n_cls * A rows
 hipError_t launch_embed(int NB, int nseg, int prec, const EmbedParams& p, hipStream_t st);
 // masked: the masked twins of the message kernels (per-molecule edge sets, ti_painn_set_edge_mask); p.rows then holds row words per
 // (group, part) instead of the template's (painn_pack.hip: masked_rows)
@@ -184,6 +191,9 @@ template <int NB, bool MASK> hipError_t configure_edge_unit();
 // SEEDED: the seeded twins of the unmasked tile and general builds, units painn_pair_seed_nb*.hip)
 template <int NB, bool MASK, bool GENERAL, bool SEEDED = false> hipError_t launch_pair_unit(bool first, bool last, int prec, const EdgeParams& p, hipStream_t st, bool table);
 template <int NB, bool MASK, bool GENERAL, bool SEEDED = false> hipError_t configure_pair_unit();
+// (the merged-tails builds of the seeded general launch, units painn_pair_tails_nb*.hip)
+template <int NB> hipError_t launch_pair_tails_unit(bool first, bool last, const EdgeParams& p, hipStream_t st, bool table);
+template <int NB> hipError_t configure_pair_tails_unit();
 
 // ---- forward-mode derivative of the drift (painn_jvp_kernels.hip; virtual-molecule layout described there).
 // D = 3A and xdot == NULL: unit seeds (direction d -> atom d/3, component d%3); otherwise D explicit directions xdot [B][D][A][3]

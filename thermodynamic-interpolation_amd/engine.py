@@ -1040,6 +1040,18 @@ class PainnEngine(_Engine):
         path = _lib.lib().ti_painn_debug_pair_seeded(self.h, _lib.iptr(s))
         return int(path), int(s[0])
 
+    def debug_pair_tails(self):
+        """(path, S) of the merged tails: path 1 = the seeded general launches of the last drift evaluation walked super-groups of S
+        groups, their last general blocks as one; 0 = one group per wave; -1 = none yet.  S = 0: the template has no such tails."""
+        s = np.zeros(1, np.int32)
+        path = _lib.lib().ti_painn_debug_pair_tails(self.h, _lib.iptr(s))
+        return int(path), int(s[0])
+
+    def debug_embed_path(self):
+        """Which embed launch the last drift evaluation ran: 1 = per class (the table path: (class, atom) rows alone, layer 0's
+        update reads s through the class map), 0 = every atom, -1 = none yet."""
+        return int(_lib.lib().ti_painn_debug_embed_path(self.h))
+
     def debug_read(self, what: str, B: int):
         """what: 's' | 'v' | 'e', or 'ts' | 'tv' | 'te' for the tangents of the last jvp() call."""
         shape = {"s": (B, self.A, self.F), "v": (B, self.A, 3, self.F), "e": (B, self.E, self.F)}[what[-1]]
