@@ -779,6 +779,13 @@ int ti_painn_debug_pair_tails(ti_handle* h, int32_t* groups_per_wave);
  * Returns which embed launch the LAST drift evaluation of the handle ran (a rollout: its last evaluation): 1 = per class, 0 = every
  * atom, -1 = no evaluation yet.  ti_painn_debug_poison fills the full s and P as well, which such an evaluation must not read. */
 int ti_painn_debug_embed_path(ti_handle* h);
+/* Update launches that keep v_eff in registers.  The update kernel forms v_eff = v + dv in its first phase and needs it
+ * again in its last; the builds of before park it in the dv accumulator in between.  The f16x2 builds up to F = 128 have twins that
+ * keep components of it in fp32 registers instead -- the same values in the same expressions, bit for bit the results of before --
+ * and a handle launches those unless TI_UPDATE_KEEP=0 is in the environment when it is created.
+ * Returns how many of the three components the update launches of the LAST drift evaluation kept: 1..3, 0 = the builds of before (the
+ * switch, f32, the fp16 storage mode, F = 256), -1 = no evaluation yet. */
+int ti_painn_debug_update_keep(ti_handle* h);
 /* Device self-test of the MFMA operand/accumulator lane maps the kernels rely on, of both fp32 -> (hi, lo) fp16 operand splits
  * (the 8-instruction forms of formats (a) and (b) against the plain arithmetic, bit for bit, fp16-subnormal residuals included),
  * and of the fp16 matrix instruction keeping subnormal inputs. */

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "ti_obs_cv", "ti_obs_weights", "ti_obs_hist", "ti_obs_set_observer",
     "ti_adw_rollout_fused",
     "ti_obs_bootstrap",
-    "ti_painn_debug_phi0_path", "ti_painn_debug_pair_blocks", "ti_painn_debug_pair_seeded", "ti_painn_debug_embed_path", "ti_painn_debug_pair_tails",
+    "ti_painn_debug_phi0_path", "ti_painn_debug_pair_blocks", "ti_painn_debug_pair_seeded", "ti_painn_debug_embed_path", "ti_painn_debug_pair_tails", "ti_painn_debug_update_keep",
     "ti_obs_rff_gram",
     "ti_obs_eigh", "ti_obs_gedmd_spectrum",
     "ti_obs_rff_gram_wide",
@@ -229,6 +229,7 @@ def lib():
     L.ti_painn_debug_pair_blocks.argtypes = [vp, ip, ip, ip]
     L.ti_painn_debug_pair_seeded.argtypes = [vp, ip]
     L.ti_painn_debug_embed_path.argtypes = [vp]
+    L.ti_painn_debug_update_keep.argtypes = [vp]
     L.ti_painn_debug_pair_tails.argtypes = [vp, ip]
     L.ti_selftest.argtypes = [C.c_int]
     L.ti_painn_drift_tv.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int]

@@ -57,6 +57,10 @@ ti_handle* ti_painn_create(const ti_painn_desc* d, const float* weights, size_t 
         h->has_pair = pair_build_exists(h->NB, 4, d->precision) && build_pair_template(h.get(), edge_src, edge_dst, edge_type);
         select_template(h.get(), 1 << 20);
         pack_painn(h.get(), weights);
+        // the update builds that keep v_eff in registers, where the precision and the width have them; triage switch, read like
+        // TI_EMBED_CLASSES: TI_UPDATE_KEEP=0 at creation pins the update kernels of before
+        h->update_keep_on = update_keep_components(h->NB, d->precision) > 0;
+        if (const char* z = std::getenv("TI_UPDATE_KEEP")) if (z[0] == '0') h->update_keep_on = false;
         HIP_CHECK(configure_painn_kernels(h->NB));
         HIP_CHECK(configure_painn_jvp_kernels(h->NB));
         out = h.release();
@@ -270,6 +274,12 @@ int ti_painn_debug_embed_path(ti_handle* h)
 {
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
     return h->embed_cls_last;
+}
+
+int ti_painn_debug_update_keep(ti_handle* h)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    return h->update_keep_last;
 }
 
 int ti_painn_debug_poison(ti_handle* h, int64_t B, float value)

@@ -228,6 +228,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
     h->seeded_last = seeded ? 1 : 0;
     const bool tails = seeded && h->pair_tails_on;      // the seeded general launch on super-groups, their last blocks merged
     h->tails_last = tails ? 1 : 0;
+    h->update_keep_last = h->update_keep_on && L > 0 ? update_keep_components(NB, prec) : 0;
     h->last_B = B;
     if (h->tap == 0) return;
     for (int l = 0; l < L; ++l) {
@@ -318,7 +319,7 @@ void painn_drift_dev(ti_handle* h, const float* x_dev, float t, const float* con
             // (cacc is then not written in this layer; the tangent passes, which read it, run on directed launches only)
             const bool folded = h->nblk > 0 && h->active == 2 && l > 0 && pair_folds_cross(prec);
             Timed tm(h, TI_KERNEL_PAINN_UPDATE);
-            HIP_CHECK(launch_update(NB, l + 1 < L, prec, p, st, folded));
+            HIP_CHECK(launch_update(NB, l + 1 < L, prec, p, st, folded, h->update_keep_on));
         }
         if (h->tap == 2 + 2 * l) return;
     }

@@ -15,6 +15,7 @@
 
 #include "dispatch.hpp"
 #include "mfma_chain.hpp"
+#include "painn_update_kernel.hpp"
 #include "ti_internal.hpp"
 
 namespace ti {
@@ -27,18 +28,11 @@ namespace ti {
 // FOLDED: the message kernel has already added the cross term to dvacc (pair_folds_cross, ti_internal.hpp): dv = dvacc, cacc unused.
 // 16 atoms per wave on the r16 primitives (f32 or split-fp16 matrix path), 4 waves per workgroup, 2 workgroups per CU.
 // The three spatial components share every visit of the U / V weight chunks.
-struct UV {                                         // per-layer vector block in LDS, x F floats
-    static constexpr int B0 = 0, G0 = 1, BE0 = 2, B1 = 3, G1 = 4, BE1 = 5, B2 = 6 /* 3F: gates | scale | add */, PB0 = 9, COUNT = 10;
-};
-
-// weight chunks per barrier.  4 (64 KB in flight per workgroup) was tried for the latency regime: no change (A = 9, B = 12: 59 vs 60 us),
-// the stream of a lone workgroup runs at the ~12 B/clk a CU gets from beyond L2, not at the number of bytes in flight
-// (the fp16 storage mode's hi-only chunks are half the size: four per barrier at F = 128, same LDS bytes)
-__host__ __device__ constexpr int update_superchunk(int NB, bool H16) { return H16 && NB == 4 ? 4 : 2; }
-__host__ __device__ constexpr int update_chunk4(int NB, bool H16) { return (H16 ? 128 : 256) * NB; }
+// (struct UV, update_superchunk, update_chunk4, update_lds_bytes: painn_update_kernel.hpp, shared with painn_update_keep.hip)
 template <int NBK, bool HAS_NEXT, int PREC, bool FOLDED = false>
 __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_kernel(const UpdateParams p)
 #define TI_UPDATE_SCLS false
+#define TI_UPDATE_KEEP 0
 #include "painn_update_kernel_body.inc"
 #undef TI_UPDATE_SCLS
 
@@ -48,6 +42,8 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_update_cls_kern
 #define TI_UPDATE_SCLS true
 #include "painn_update_kernel_body.inc"
 #undef TI_UPDATE_SCLS
+#undef TI_UPDATE_KEEP
+// (their twins that keep v_eff in registers: painn_update_keep.hip, a unit of its own so that these code objects stay as they were)
 
 // ================================================================================================== embed / readout kernels
 // embed:   s = MLP([atom_emb | enc(T0) | enc(T1) | enc(t)]),  P = s @ phi0.W0[:, :F]^T + phi0.b0
@@ -144,7 +140,6 @@ __global__ __launch_bounds__(256, (NBK <= 8 ? 2 : 1)) void painn_readout16_kerne
 }
 
 // ================================================================================================== launchers
-static size_t update_lds_bytes(int NB, bool h16) { return 2 * update_superchunk(NB, h16) * (size_t)update_chunk4(NB, h16) * 16 + 10 * (size_t)32 * NB * 4; }
 static size_t node16_lds_bytes(int NB, bool h16) { return 2 * 2 * (size_t)update_chunk4(NB, h16) * 16; }      // PipeDMA<.., SC = 2>: two superchunks
 
 // The three node kernels and their builds: every width x precision (prec: include/ti_hip.h TI_PREC_*; 0 f32, 1 f16x2, 2 f16 storage
@@ -212,6 +207,7 @@ hipError_t configure_painn_kernels(int NB)
     if ((e = configure_node<NODE_EMBED>(NB)) != hipSuccess) return e;
     if ((e = configure_node<NODE_UPDATE>(NB)) != hipSuccess) return e;
     if ((e = configure_node<NODE_READOUT>(NB)) != hipSuccess) return e;
+    if ((e = configure_update_keep(NB)) != hipSuccess) return e;
     if (pair_table_build_exists(NB, TI_PREC_F16X2, false)) {
         if ((e = configure_node<NODE_EMBED_CLS>(NB)) != hipSuccess) return e;
         if ((e = configure_node<NODE_UPDATE_CLS>(NB)) != hipSuccess) return e;
@@ -239,8 +235,9 @@ hipError_t launch_embed(int NB, int nseg, int prec, const EmbedParams& p, hipStr
     if (p.rep) return p.tv ? hipErrorInvalidValue : launch_node<NODE_EMBED_CLS>(NB, prec, nseg, false, p, st);
     return launch_node<NODE_EMBED>(NB, prec, nseg, p.tv != nullptr, p, st);
 }
-hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded)
+hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded, bool keep)
 {
+    if (keep) return launch_update_keep(NB, has_next, prec, p, st, folded);
     if (p.s_cls) return folded ? hipErrorInvalidValue : launch_node<NODE_UPDATE_CLS>(NB, prec, has_next, false, p, st);
     return launch_node<NODE_UPDATE>(NB, prec, has_next, folded, p, st);
 }

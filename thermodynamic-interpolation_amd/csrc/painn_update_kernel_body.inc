@@ -2,8 +2,14 @@
 // for painn_update_cls_kernel (TI_UPDATE_SCLS), so that the builds of before keep their names and their code.
 // SCLS (layer 0 after an embed per class, painn_host.hip): the incoming s row of a node is its class's, s_cls[cls[molecule]][atom]; the
 // full s is still written.  Rows of one class agree bit for bit (painn_phi0_kernels.hip), so the result is that of the full embed.
+// KEEP (TI_UPDATE_KEEP; 0 in the builds of before, whose code it leaves instruction for instruction what it was; 1..3 in their
+// *_keep_kernel twins of the split path, painn_update_keep.hip): components c < KEEP of v_eff stay in
+// fp32 registers from phase A to phase C instead of being parked in dvacc and read back -- the same fp32 values in the same
+// expressions, so the results agree bit for bit with KEEP = 0 -- and components c >= KEEP keep the park (DESIGN.md 4.0k).
 {
     constexpr bool SCLS = TI_UPDATE_SCLS;
+    constexpr int KEEP = TI_UPDATE_KEEP;
+    static_assert(KEEP >= 0 && KEEP <= 3 && (KEEP == 0 || (PREC == 1 && NBK <= 8)), "kept rows: the split path up to F = 128");
     static_assert(!SCLS || (PREC == 1 && !FOLDED), "s per class: layer 0 of the split path");
     constexpr bool H16 = PREC == 2;                 // s, v, P are fp16 in HBM (the accumulators stay fp32), hi-only weight chunks
     constexpr int F = 16 * NBK, NB = (F + 31) / 32, WAVES = 4, T = 64 * WAVES, CH4 = update_chunk4(NB, H16);
@@ -28,8 +34,9 @@
     const float* s_in = nullptr;                  // SCLS: the node's incoming s row, its class's
     if constexpr (SCLS) s_in = p.s_cls + ((size_t)p.cls[nd / (size_t)p.A] * (size_t)p.A + nd % (size_t)p.A) * F;
 
-    // ---- phase A: v_eff = v + dvacc + cacc x v (parked in dvacc), n2 = |V v_eff|^2 over the 3 components
+    // ---- phase A: v_eff = v + dvacc + cacc x v (parked in dvacc, or kept in tk), n2 = |V v_eff|^2 over the 3 components
     A16 n2;
+    A16 tk[KEEP > 0 ? KEEP : 1];                    // the kept v_eff rows, live until phase C
     {
         OP ve[3];
         float vsc[3];                               // v is an un-normalised stream: per-row scales of the split operands
@@ -49,11 +56,18 @@
                     const f32x4 dd = r16::load_block(db + c * F, nb, q);
                     if (FOLDED) t[c].b[nb] = vv[c] + dd;
                     else t[c].b[nb] = (vv[c] + dd) + (kk[c1] * vv[c2] - kk[c2] * vv[c1]);      // torch.cross(edge_dir, v[dst]) summed over edges
-                    if (ok) r16::store_block(db + c * F, nb, q, t[c].b[nb]);
+                    if (ok && c >= KEEP) r16::store_block(db + c * F, nb, q, t[c].b[nb]);
+                    // a kept block has no store that needs it here: pinned, or the compiler sinks the sum to its first use and keeps
+                    // its up to seven addends alive in its place -- the rows then spill (profiles/update_keep_resources.txt)
+                    if constexpr (KEEP > 0) { if (c < KEEP) asm volatile("" : "+v"(t[c].b[nb])); }
                 }
             }
 #pragma unroll
-            for (int c = 0; c < 3; ++c) vsc[c] = ve[c].set_scaled(t[c]);
+            for (int c = 0; c < 3; ++c) {
+                if constexpr (KEEP == 0) vsc[c] = ve[c].set_scaled(t[c]);
+                else if (c >= KEEP) vsc[c] = ve[c].set_scaled(t[c]);
+                else tk[c] = t[c];
+            }
         }
 #pragma unroll
         for (int nb = 0; nb < NBK; ++nb) n2.b[nb] = f32x4{0, 0, 0, 0};
@@ -62,6 +76,9 @@
             const f32x4* wl = pipe.acquire();
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
+                // a kept row's operand is rebuilt at every chunk visit (set_scaled of the same row gives the same bits): holding the three
+                // operands beside the three rows does not fit the register budget of two workgroups per CU
+                if constexpr (KEEP > 0) { if (c < KEEP) vsc[c] = ve[c].set_scaled(tk[c]); }
                 f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
                 r16::gemm_bt(a0, a1, ve[c], wl, lane);                   // vv = V v  (of the scaled rows)
                 a0 *= vsc[c]; a1 *= vsc[c];
@@ -167,8 +184,9 @@
         pipe.release();
     }
     // ---- phase C: v = v_eff + (U v_eff) * gates ; reset the accumulators for the next layer.  One spatial component at a time (the
-    // stream holds U three times): the parked v_eff row is read once and serves as operand AND as the value the update is added to
+    // stream holds U three times): the v_eff row (kept, or parked and read once) serves as operand AND as the value the update is added to
     // -- with the three components sharing each chunk visit it had to be read a second time, and that read missed L2.
+    if constexpr (KEEP == 0) {
 #pragma unroll 1
     for (int c = 0; c < 3; ++c) {
         A16 t;
@@ -195,6 +213,41 @@
             }
             pipe.release();
         }
+    }
+    } else {
+    // the same component step for a kept row (unrolled: registers are not indexed at run time) and for a parked one, read back as above
+    const auto component = [&](const int c, const A16& t) {
+        OP vc;
+        const float usc = vc.set_scaled(t);
+#pragma unroll
+        for (int ch = 0; ch < NB; ++ch) {
+            const f32x4* wl = pipe.acquire();
+            f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+            r16::gemm_bt(a0, a1, vc, wl, lane);
+            a0 *= usc; a1 *= usc;
+            if (ok) {
+                r16::store_state<H16>(p.v, vo + c * F, 2 * ch, q, t.b[2 * ch] + a0 * gg.b[2 * ch]);
+                r16::store_state<H16>(p.v, vo + c * F, 2 * ch + 1, q, t.b[2 * ch + 1] + a1 * gg.b[2 * ch + 1]);
+                if (p.zero_acc) {
+                    r16::store_block(db + c * F, 2 * ch, q, f32x4{0, 0, 0, 0});
+                    r16::store_block(db + c * F, 2 * ch + 1, q, f32x4{0, 0, 0, 0});
+                    if (!FOLDED) {
+                        r16::store_block(cb + c * F, 2 * ch, q, f32x4{0, 0, 0, 0});
+                        r16::store_block(cb + c * F, 2 * ch + 1, q, f32x4{0, 0, 0, 0});
+                    }
+                }
+            }
+            pipe.release();
+        }
+    };
+#pragma unroll
+    for (int c = 0; c < KEEP; ++c) component(c, tk[c]);
+#pragma unroll 1
+    for (int c = KEEP; c < 3; ++c) {
+        A16 t;
+        r16::load_set(t, db + c * F, q);
+        component(c, t);
+    }
     }
     // ---- phase D: P for the next message block
     if (HAS_NEXT) {

@@ -142,6 +142,10 @@ struct ti_handle {
     // written by that update.  Off with TI_EMBED_CLASSES=0 in the environment at creation (same-binary A/B runs, triage).
     // embed_cls_last: what ti_painn_debug_embed_path reports.
     bool embed_cls_on = false; int embed_cls_last = -1; DevBuf<float> s_cls, P_cls;
+    // update launches on the builds that keep v_eff in registers (painn_update_keep.hip): the split
+    // path up to F = 128.  Off with TI_UPDATE_KEEP=0 in the environment at creation (same-binary A/B runs, triage).
+    // update_keep_last: what ti_painn_debug_update_keep reports.
+    bool update_keep_on = false; int update_keep_last = -1;
     // forward-mode derivative (painn_jvp_kernels.hip): tangent twins over virtual molecules, sized on first use
     std::vector<Stream> st_jvp_update, st_jvp_phi; Stream st_jvp_readout{}; std::vector<int> jvp_phi_pad;
     DevBuf<float> jvp_ro_vecs, ts, tP, tv, tdsacc, tdvacc, tcacc, te, tout, wq, phist, nodest, divb, dl, dlscaled, div2;

@@ -179,7 +179,12 @@ __host__ __device__ constexpr bool pair_general_build_exists(int PREC) { return 
 // alone stays bit for bit what it is in a larger batch.  The f32 path keeps the cross-gate sums in cacc.
 __host__ __device__ constexpr bool pair_folds_cross(int prec) { return prec == TI_PREC_F16X2; }
 // folded: the message launch before it already added the cross term to dvacc (pair_folds_cross); cacc is then neither read nor reset
-hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded = false);
+// keep: the twin build that keeps v_eff in registers between its phases instead of parking it in dvacc (painn_update_keep.hip; the same
+// results bit for bit); update_keep_components: how many of the three components that build keeps, 0 where there is no such build
+hipError_t launch_update(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded = false, bool keep = false);
+int update_keep_components(int NB, int prec);
+hipError_t configure_update_keep(int NB);                                        // painn_update_keep.hip
+hipError_t launch_update_keep(int NB, bool has_next, int prec, const UpdateParams& p, hipStream_t st, bool folded);
 hipError_t launch_readout(int NB, int prec, const ReadoutParams& p, hipStream_t st);
 hipError_t configure_painn_kernels(int NB);     // dynamic-LDS attributes
 // What the one-width translation units of the message kernels export (painn_{edge,pair}[_mask]_nb*.hip, one unit per width so that they

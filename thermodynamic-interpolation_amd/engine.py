@@ -1052,6 +1052,12 @@ class PainnEngine(_Engine):
         update reads s through the class map), 0 = every atom, -1 = none yet."""
         return int(_lib.lib().ti_painn_debug_embed_path(self.h))
 
+    def debug_update_keep(self):
+        """How many of the three v_eff components the update launches of the last drift evaluation kept in registers: 1..3,
+        0 = the builds that park all of it in the dv accumulator (TI_UPDATE_KEEP=0 at creation, f32, fp16 storage, F = 256),
+        -1 = none yet."""
+        return int(_lib.lib().ti_painn_debug_update_keep(self.h))
+
     def debug_read(self, what: str, B: int):
         """what: 's' | 'v' | 'e', or 'ts' | 'tv' | 'te' for the tangents of the last jvp() call."""
         shape = {"s": (B, self.A, self.F), "v": (B, self.A, 3, self.F), "e": (B, self.E, self.F)}[what[-1]]
