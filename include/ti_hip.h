@@ -661,6 +661,35 @@ int ti_obs_ff_remd(ti_handle* h, const ti_md_desc* d, const ti_remd_desc* r, dou
  * [host|device] by mem.  u0 == NULL: 0 (the calc_phis_bg form); neg_dlogp == NULL: 0.  Non-finite inputs pass through: the
  * consumers refuse them by index.  Any handle.  TI_E_ARG: a NULL handle, u1 or out_logw, B < 1, an unknown mem. */
 int ti_obs_ti_logw(ti_handle* h, const double* u0, const double* u1, const float* neg_dlogp, int64_t B, float* out_logw, int mem);
+/* The log-weights of a Boltzmann generator, and of a latent -> ambient chain, from the prior samples the run started from (the
+ * reference's weight is exp(-E1 - log N(z0; 0, I) - (neg_dlogp_bg + neg_dlogp_ti)), ess.py:13-29 calc_log_mvnormal_pzs and
+ * calc_importance_weights).  All in fp64:
+ *   out_logpz[b] = -(0.5 * S_b) - (m * TI_BG_HALF_LOG_2PI),   S_b = sum_j (double)z[b][j]^2
+ *   out_logw[b]  = -(((u1[b] + out_logpz[b]) + neg_dlogp_bg[b]) + neg_dlogp_ti[b])
+ * out_logw rounded once to the fp32 that ti_obs_weights, ti_obs_hist, ti_obs_bootstrap and ti_obs_rff_gram take.  z [B][m] fp32,
+ * one row per molecule (a molecule handle: m = 3A; m is an argument, so the d-dimensional toy models can call it too); u1 [B] fp64
+ * the reduced energy of the generated state (NULL: 0); neg_dlogp_bg, neg_dlogp_ti [B] fp32 (NULL: 0); out_logpz [B] fp64 and
+ * out_logw [B] fp32, either may be NULL but not both.  All [host|device] by mem.  Any handle.
+ * One wave per molecule, four molecules per workgroup: lane l adds the squares of components l, l + 64, ... in that order and the
+ * 64 lane sums are combined by the fixed butterfly with offsets 32 .. 1; no atomics.  Every term of S_b is exact (the square of an
+ * fp32 value fits fp64's mantissa) and m * TI_BG_HALF_LOG_2PI is rounded before the subtraction (no contraction), so a molecule's
+ * outputs are a function of its row and m only -- not of B, of the row's place in the batch, of mem or of the launch -- and a numpy
+ * restatement reproduces them bit for bit.  Non-finite inputs pass through to that molecule only: the consumers refuse them by
+ * index.  TI_E_ARG, nothing written: a NULL handle, z == NULL, both outputs NULL, B < 1, m < 1 or m > TI_BG_MAX_M, an unknown mem. */
+#define TI_BG_MAX_M 65536
+#define TI_BG_HALF_LOG_2PI 0.9189385332046727
+int ti_obs_bg_logw(ti_handle* h, const float* z, int64_t B, int64_t m, const double* u1, const float* neg_dlogp_bg, const float* neg_dlogp_ti,
+                   double* out_logpz, float* out_logw, int mem);
+/* The effective sample size (sum w)^2 / sum w^2 (the reference's calc_ESS) of the same weights from their UNROUNDED fp64 logarithms
+ * l[b] = -(((u1[b] + logpz[b]) + neg_dlogp_bg[b]) + neg_dlogp_ti[b]), logpz [B] fp64 as ti_obs_bg_logw returns it, over the molecules
+ * with keep[b] != 0 (keep [B] uint8; NULL: all -- the once-filtered sample of gen_ess_bg).  The one fp32 rounding of out_logw moves an
+ * ESS by up to 2e-6 relative; this entry has no such term and agrees with calc_ESS of the reference's fp64 weights to the summation
+ * error.  w = exp(l - max l).  One workgroup: thread t walks molecules t, t + 256, ... in that order, the 256 partial results meet in
+ * a fixed tree; fp64, no atomics, so a call repeats bit for bit.  Arrays [host|device] by mem; out_ess and out_kept (may be NULL)
+ * are host scalars.  Any handle.  TI_E_NAN with the index for a non-finite kept l; TI_E_ARG: NULL logpz or out_ess, an unknown mem,
+ * B < 1, a NULL handle, a keep that leaves no molecule. */
+int ti_obs_bg_ess(ti_handle* h, const double* logpz, int64_t B, const double* u1, const float* neg_dlogp_bg, const float* neg_dlogp_ti,
+                  const uint8_t* keep, double* out_ess, int64_t* out_kept, int mem);
 /* ---- Z-matrix (internal) coordinates: construct, NeRF rebuild with log|det J|, and the histograms of all columns ------------------
  * What the reference's mdqm9/analysis/utils/z_matrix.py computes around results_00031.py: construct_z_matrix_batch on the sorted
  * atoms (ti_obs_zmat), deconstruct_z_matrix_batch -- the batch version, which does not clamp --, its log-determinant

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "ti_painn_train_steps", "ti_painn_train_best", "ti_painn_train_noise",
     "ti_obs_ff_forces", "ti_obs_ff_set_masses", "ti_obs_ff_langevin",
     "ti_obs_ff_remd",
+    "ti_obs_bg_logw", "ti_obs_bg_ess",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -75,6 +76,8 @@ def eigh_wide_launch_max(n):
 # ti_obs_ff_set: the caps of the four tables (TI_FF_MAX_*), R in kJ / (mol K) (TI_FF_GAS_CONSTANT), OpenMM's ONE_4PI_EPS0 in kJ nm / (mol e^2)
 FF_MAX_BONDS, FF_MAX_ANGLES, FF_MAX_TORSIONS, FF_MAX_PAIRS = 64, 128, 512, 300
 FF_GAS_CONSTANT, FF_COULOMB = 0.00831446261815324, 138.935456
+# ti_obs_bg_logw: the most components of a row (TI_BG_MAX_M), log(2 pi) / 2 as the kernel holds it (TI_BG_HALF_LOG_2PI)
+BG_MAX_M, BG_HALF_LOG_2PI = 65536, 0.9189385332046727
 # ti_obs_ff_langevin: the most steps of one launch when the descriptor leaves it open (TI_MD_DEFAULT_STEPS_PER_LAUNCH)
 MD_DEFAULT_STEPS_PER_LAUNCH = 1024
 # ti_obs_ff_remd: the most rungs of a ladder (TI_REMD_MAX_RUNGS), the fourth counter word of the exchange draws (TI_REMD_DOMAIN)
@@ -260,6 +263,8 @@ def lib():
     L.ti_obs_ff_set.argtypes = [vp, C.POINTER(FfDesc), ip, dp, ip, dp, ip, dp, dp]
     L.ti_obs_ff_energy.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
     L.ti_obs_ti_logw.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int]
+    L.ti_obs_bg_logw.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int]
+    L.ti_obs_bg_ess.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
     L.ti_obs_ff_forces.argtypes = [vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
     L.ti_obs_ff_set_masses.argtypes = [vp, dp]
     L.ti_obs_ff_langevin.argtypes = [vp, C.POINTER(MdDesc), vp, vp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]

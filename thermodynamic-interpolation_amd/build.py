@@ -39,6 +39,8 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api
            "obs_eig_wide_kernels.hip",
            # force-field energies of a batch and the TI log-weights from them (ti_obs_ff_energy, ti_obs_ti_logw)
            "obs_ff_kernels.hip",
+           # Boltzmann-generator log-weights: log N(z; 0, I) of the prior samples and the weight formed from it (ti_obs_bg_logw)
+           "obs_bg_kernels.hip",
            # Z-matrix coordinates both ways and the histograms of all columns in one launch (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols)
            "obs_zmat_kernels.hip",
            # velocity loss (ti_painn_vloss, ti_adw_vloss): time draws, interpolant states and centring, per-molecule reduction, batch sums

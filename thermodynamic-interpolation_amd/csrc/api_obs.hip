@@ -1,5 +1,6 @@
 // api_obs.hip -- observables (ti_obs_*): collective variables of a state, importance weights, weighted histograms, force-field
-// energies and the TI log-weights formed from them, Z-matrix coordinates both ways, and the observer a rollout writes CV rows through.
+// energies and the TI log-weights formed from them, the Boltzmann-generator log-weights, Z-matrix coordinates both ways, and the
+// observer a rollout writes CV rows through.
 #include "ti_handle.hpp"
 
 namespace {
@@ -721,6 +722,64 @@ int ti_obs_ti_logw(ti_handle* h, const double* u0, const double* u1, const float
         float* od = sg.out(out_logw, h->obs_logw, (size_t)B);
         HIP_CHECK(launch_obs_ti_logw(od, u0d, u1d, nd, B, h->stream));
         sg.finish();
+        return TI_OK;
+    });
+}
+
+int ti_obs_bg_logw(ti_handle* h, const float* z, int64_t B, int64_t m, const double* u1, const float* neg_dlogp_bg, const float* neg_dlogp_ti,
+                   double* out_logpz, float* out_logw, int mem)
+{
+    // the checks that need no device come first, so they can be exercised with a NULL handle; that one is refused last
+    if (!z) return fail(TI_E_ARG, "z is NULL");
+    if (!out_logpz && !out_logw) return fail(TI_E_ARG, "out_logpz and out_logw are both NULL");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (m < 1 || m > TI_BG_MAX_M) return fail(TI_E_ARG, "m must be in 1.." + std::to_string(TI_BG_MAX_M));
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    return guarded([&]() -> int {
+        set_device(h);
+        Staged sg(h, mem);
+        BgParams p{};
+        p.B = B; p.m = (int)m;
+        p.z = sg.in(z, h->obs_x, (size_t)B * (size_t)m);
+        p.u1 = u1 ? sg.in(u1, h->ff_u1, (size_t)B) : nullptr;
+        p.nd_bg = neg_dlogp_bg ? sg.in(neg_dlogp_bg, h->obs_val, (size_t)B) : nullptr;
+        p.nd_ti = neg_dlogp_ti ? sg.in(neg_dlogp_ti, h->bg_nt, (size_t)B) : nullptr;
+        p.logpz = out_logpz ? sg.out(out_logpz, h->bg_logpz, (size_t)B) : nullptr;
+        p.logw = out_logw ? sg.out(out_logw, h->obs_logw, (size_t)B) : nullptr;
+        HIP_CHECK(launch_obs_bg_logw(p, h->stream));
+        sg.finish();
+        return TI_OK;
+    });
+}
+
+int ti_obs_bg_ess(ti_handle* h, const double* logpz, int64_t B, const double* u1, const float* neg_dlogp_bg, const float* neg_dlogp_ti,
+                  const uint8_t* keep, double* out_ess, int64_t* out_kept, int mem)
+{
+    if (!logpz || !out_ess) return fail(TI_E_ARG, "NULL buffer");
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    if (B < 1) return fail(TI_E_ARG, "B < 1");
+    if (!h) return fail(TI_E_ARG, "NULL handle");
+    return guarded([&]() -> int {
+        set_device(h);
+        Staged sg(h, mem);
+        BgEssParams p{};
+        p.B = B;
+        p.logpz = sg.in(logpz, h->bg_logpz, (size_t)B);
+        p.u1 = u1 ? sg.in(u1, h->ff_u1, (size_t)B) : nullptr;
+        p.nd_bg = neg_dlogp_bg ? sg.in(neg_dlogp_bg, h->obs_val, (size_t)B) : nullptr;
+        p.nd_ti = neg_dlogp_ti ? sg.in(neg_dlogp_ti, h->bg_nt, (size_t)B) : nullptr;
+        p.keep = keep ? sg.in(keep, h->hc_keep, (size_t)B) : nullptr;
+        grow(h->obs_red, 4 + 259);
+        p.out = h->obs_red.p;
+        HIP_CHECK(launch_obs_bg_ess(p, h->stream));
+        double r[3];
+        HIP_CHECK(hipMemcpyAsync(r, h->obs_red.p, sizeof r, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        if (r[1] < 1.0) return fail(TI_E_ARG, "keep leaves no molecule");
+        if (r[2] < (double)B) return fail(TI_E_NAN, "non-finite log-weight at index " + std::to_string((long long)r[2]));
+        *out_ess = r[0];
+        if (out_kept) *out_kept = (int64_t)r[1];
         return TI_OK;
     });
 }

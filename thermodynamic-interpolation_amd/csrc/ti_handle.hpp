@@ -195,6 +195,9 @@ struct ti_handle {
     // energies, term sums, reduced energies and log-weights (ti_obs_ff_energy, ti_obs_ti_logw)
     bool ff_on = false; int ff_n[4] = {0, 0, 0, 0}; double ff_coulomb = 0.0;
     DevBuf<int32_t> ff_idx; DevBuf<double> ff_par, ff_e, ff_terms, ff_u0, ff_u1; DevBuf<float> ff_T;
+    // Boltzmann-generator log-weights (ti_obs_bg_logw): staging of a host call's second dlogp and of log p(z); the rest of its
+    // buffers are those of the calls above (obs_x, ff_u1, obs_val, obs_logw)
+    DevBuf<float> bg_nt; DevBuf<double> bg_logpz;
     // forces and Langevin dynamics (ti_obs_ff_forces, ti_obs_ff_set_masses, ti_obs_ff_langevin): the incidence list of the bonded
     // terms, built with the force field (ff_device.hpp); the masses (ff_mass_on: in force; cleared with the force field); staging of a
     // host call's forces; the working copy of the state, the replica ids, frames, frame energies and stop flags of a Langevin call

@@ -443,6 +443,26 @@ hipError_t launch_obs_ff_bad_temperature(double* out, const float* T, long long 
 // logw[b] = (float)-((u1[b] - u0[b]) + neg_dlogp[b]) in fp64; u0 / neg_dlogp NULL: 0
 hipError_t launch_obs_ti_logw(float* logw, const double* u0, const double* u1, const float* neg_dlogp, long long B, hipStream_t st);
 
+// ---- Boltzmann-generator log-weights (obs_bg_kernels.hip; include/ti_hip.h ti_obs_bg_logw)
+struct BgParams {
+    const float* z;                         // [B][m] prior samples
+    long long B; int m;
+    const double* u1;                       // [B] reduced energy of the generated state, NULL: 0
+    const float *nd_bg, *nd_ti;             // [B] each, NULL: 0
+    double* logpz;                          // [B] or NULL: -(0.5 sum z^2) - (m HALF_LOG_2PI)
+    float* logw;                            // [B] or NULL: (float)-(((u1 + logpz) + nd_bg) + nd_ti)
+};
+hipError_t launch_obs_bg_logw(const BgParams& p, hipStream_t st);
+// the ESS of the unrounded fp64 log-weights of the kept molecules (include/ti_hip.h ti_obs_bg_ess)
+struct BgEssParams {
+    const double *logpz, *u1;               // [B]; u1 NULL: 0
+    const float *nd_bg, *nd_ti;             // [B] each, NULL: 0
+    const uint8_t* keep;                    // [B] or NULL: all
+    long long B;
+    double* out;                            // (ess, kept count, first index of a non-finite kept log-weight or +inf)
+};
+hipError_t launch_obs_bg_ess(const BgEssParams& p, hipStream_t st);
+
 // ---- force-field forces and Langevin dynamics (obs_ff_md_kernels.hip, ff_device.hpp; include/ti_hip.h ti_obs_ff_forces,
 // ti_obs_ff_langevin).  The tables are those of FfParams plus the incidence list of the bonded terms (ff_device.hpp).
 struct FfTablesDev {

@@ -200,6 +200,7 @@ class MDQM9SamplerDataset:
         else:
             self.data = load_trajectory(traj_path, split, traj_filename, T0, scale)
             self.data0, self.dlogp0 = np.zeros_like(self.data), np.zeros(len(self.data), np.float32)      # dummies, like the reference
+        self.use_latent_trajs = bool(use_latent_trajs)         # drivers: the bg key needs the real latent_z
         self.T0, self.T1 = float(T0), float(T1)
         if bond_index is None and sdf_path is not None:
             bond_index, bonds = bonds_from_molblock(read_sdf_record(os.path.join(sdf_path, sdf_filename), int(traj_filename.split(".")[0])))

@@ -39,8 +39,17 @@ GPU, coordinates divided by scale as in results_00031.py:173-174, and adds ``tor
 [3A-6, bins] and ``zmat_ranges`` [3A-6, 2] (observables.zmatrix_marginals: lengths, angles, torsions) to the npz.  The x0 are samples
 of the source ensemble and stay unweighted; the end state's marginals are weighted by the run's ``logw`` when the energy key supplies
 it, and with ``iqr_k`` (which needs the energy key) the reference's filter_iqr(weights, k) mask -- written as ``zmat_keep`` [B] -- is
-applied to them.  The key is checked before the rollout; sample_latent and sample_adw refuse it.  Without the keys exactly the
-reference's files are written.
+applied to them.  The key is checked before the rollout; sample_latent and sample_adw refuse it.  sample_latent with ``return_dlogp`` only:
+``"bg": {"forcefield": <path>, "scale": <s>}`` (the keys and checks of the energy key) evaluates the Boltzmann-generator weights on the
+GPU: per batch E1 of the end state at each molecule's T (observables.ff_energy at to_nm = 1 / scale), log p(z0) of the batch's starting
+noise and ``logw_bg`` = -(E1 + log p(z0) + dlogp) (observables.bg_logw, the log of calc_importance_weights); it writes
+``E1s_samples_{name}_forward.npy`` and ``bg_{name}_forward.npz`` with ``E1``, ``log_pz``, ``logw_bg``, ``ess_bg`` (gen_ess_bg, k = None)
+and, with ``bootstrap``, ``ess_bg_ci`` -- with or without CV descriptors.  sample_ambient: ``"bg": true`` (needs the energy key and a
+dataset built with ``use_latent_trajs``) adds to the npz, for the latent -> ambient chain, ``log_pz`` = log p(latent_z), ``logw_bg`` =
+-(E1 + log p(latent_z) + latent_dlogp + dlogp), ``ess_bg`` and, with ``bootstrap``, ``ess_bg_ci``.  As in the reference, log p(z0) is
+the full 3A-dimensional normal although the noise is centred, and the constant Jacobian of ``scale`` is dropped: both are constants of
+a run and cancel in normalised weights and the ESS.  One species per run; the key is checked before the rollout; sample_adw refuses it.
+Without the keys exactly the reference's files are written.
 
   score_checkpoints <- the held-out evaluation of mdqm9/train_ambient.py:153-157, which decides what weights are kept
 Scores checkpoints by the velocity loss they were trained on (thermo.losses, on the GPU) and writes ``val_loss_{data_save_name}.npz``.
@@ -116,6 +125,8 @@ def _observe_kw(config):
     o.pop("kinetics", None)
     o.pop("energy", None)
     o.pop("zmatrix", None)
+    if o.pop("bg", None) is not None and not o:
+        return {}                              # the bg key alone: weights without collective variables, no observer
     if o.get("ref") is not None:
         o["ref"] = np.asarray(o["ref"], np.float32)
     return dict(observe=o)
@@ -251,7 +262,7 @@ def _check_energy(config, driver="sample_ambient"):
         return None
     if driver == "sample_latent":
         raise ValueError("observables['energy'] is for sample_ambient: the latent map's weights also need log p(z0) of the prior "
-                         "(calc_importance_weights), which is not evaluated here")
+                         "(calc_importance_weights), which is not evaluated here; observables['bg'] evaluates both")
     if driver == "sample_adw":
         raise ValueError("observables['energy'] is for sample_ambient: it evaluates a molecular force field; the double well's potential "
                          "enters through observables['gedmd']['potential']")
@@ -264,6 +275,74 @@ def _check_energy(config, driver="sample_ambient"):
         raise ValueError("observables['energy'] needs return_dlogp: the TI weights are exp(-(E1 - E0 + dlogp))")
     from . import forcefield as _ff
     return _ff.ForceField.from_openmm_xml(os.fspath(g["forcefield"])), 1.0 / float(scale)
+
+
+def _check_bg(config, driver, dataset=None):
+    """Before the rollout: observables["bg"] validated; None without the key.  sample_latent: a dict with the keys of the energy key
+    and their checks -> (ForceField, to_nm).  sample_ambient: true, with the energy key and a dataset built with use_latent_trajs
+    (else latent_z is the zero placeholder) -> True.  sample_adw refuses it."""
+    o = getattr(config, "observables", None)
+    g = None if o is None else dict(o).get("bg")
+    if g is None or (g is False and driver == "sample_ambient"):
+        return None
+    if driver == "sample_adw":
+        raise ValueError("observables['bg'] is for sample_latent / sample_ambient: it weights molecules by a force field and the normal "
+                         "prior; the double well's potential enters through observables['gedmd']['potential']")
+    if driver == "sample_ambient":
+        if g is not True:
+            raise ValueError(f"observables['bg'] must be true in sample_ambient (the force field is the energy key's), got {g!r}")
+        if dict(o).get("energy") is None:
+            raise ValueError("observables['bg'] needs observables['energy'] in sample_ambient: the chain's weights are "
+                             "exp(-(E1 + log p(z0) + latent_dlogp + dlogp))")
+        if "descriptors" not in dict(o):
+            raise ValueError("observables['bg'] adds to the observables npz in sample_ambient, which needs observables['descriptors']")
+        if not getattr(dataset, "use_latent_trajs", False):
+            raise ValueError("observables['bg'] needs a dataset built with use_latent_trajs: without it latent_z is the zero placeholder, "
+                             "not the noise the chain started from")
+        return True
+    if not isinstance(g, dict) or set(g) != set(ENERGY_KEYS):
+        raise ValueError(f"observables['bg'] must be a dict with exactly the keys {list(ENERGY_KEYS)}, got {g!r}")
+    scale = g["scale"]
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"observables['bg']['scale'] must be finite and > 0, got {scale!r}")
+    if not bool(getattr(config, "return_dlogp", False)):
+        raise ValueError("observables['bg'] needs return_dlogp: the weights are exp(-(E1 + log p(z0) + dlogp))")
+    from . import forcefield as _ff
+    return _ff.ForceField.from_openmm_xml(os.fspath(g["forcefield"])), 1.0 / float(scale)
+
+
+def _batch_bg(b, batch, sample, ff, to_nm):
+    """(E1, z0) of one sample_latent batch: the reduced energies [B] float64 of the end state at every molecule's T, and the noise
+    [B, A, 3] float32 the batch started from"""
+    from .thermo import _molecule as _mol
+    sb = _mol.split_species_batch(batch, b.ATOM_KEY)
+    if sb.n_atoms is not None:
+        raise ValueError("observables['bg'] takes one species per run (one force field)")
+    if not hasattr(batch, "T"):
+        raise ValueError("observables['bg'] needs the batch's temperatures (batch.T): the energies are reduced by R T")
+    B, A = sb.B, sb.A
+    eng = b.engine_of(sb)
+    eng.set_forcefield(ff)
+    x1 = C.as_f32(sample[-1], (B, A, 3))
+    T = C.as_f32(batch.T, (B, A))[:, 0]
+    T = T.contiguous() if C.is_cuda(x1) else np.ascontiguousarray(T)
+    return C.to_numpy(eng.ff_energy(x1, to_nm, T)), np.ascontiguousarray(C.to_numpy(C.as_f32(batch.x0, (B, A, 3))))
+
+
+def _bg_arrays(config, z0, E1, nd_bg, nd_ti=None):
+    """log_pz, logw_bg, ess_bg (and ess_bg_ci with the bootstrap key) of a run's prior samples z0 [B, A, 3], reduced end-state energies
+    and end-state dlogps (nd_ti: the ambient map's, on a latent -> ambient chain)"""
+    z0 = np.ascontiguousarray(z0, np.float32)
+    logw = _obs.bg_logw(z0, E1, nd_bg, nd_ti)
+    _obs.importance_weights(logw)                  # refuses a non-finite log-weight by index, as every consumer of logw_bg would
+    ess = _obs.ess_bg(z0, E1, nd_bg, nd_ti, n_boot=0).point
+    out = dict(log_pz=_obs.log_prior(z0), logw_bg=logw, ess_bg=np.float64(ess))
+    n_boot = dict(config.observables).get("bootstrap")
+    if n_boot is not None:
+        if isinstance(n_boot, bool) or int(n_boot) != n_boot or int(n_boot) < 1:
+            raise ValueError(f"observables['bootstrap'] must be an integer >= 1, got {n_boot!r}")
+        out["ess_bg_ci"] = np.asarray(_obs.ess_bg(z0, E1, nd_bg, nd_ti, n_boot=int(n_boot)).ci, np.float64)
+    return out
 
 
 def _batch_energies(b, batch, sample, ff, to_nm):
@@ -370,9 +449,10 @@ def _zmatrix_arrays(g, z0, z1, logw):
     return out
 
 
-def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=None):
+def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=None, bg=None):
     """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp); gedmd: (x0, x1, beta0, beta1)
-    of an adw run whose observables carry the gedmd key; energy: (E0, E1) [B] of a run with the energy key"""
+    of an adw run whose observables carry the gedmd key; energy: (E0, E1) [B] of a run with the energy key; bg: (latent_z [B, A, 3],
+    latent_dlogp [B]) of a sample_ambient run with the bg key"""
     cv = np.concatenate([C.to_numpy(c) for c in cvs], axis=1).astype(np.float32)
     dl = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in dlogps]) if dlogps else None
     hist, edges, ess = _obs.end_state_summary(np.ascontiguousarray(cv[-1]), dl, bins=int(dict(config.observables).get("bins", 32)))
@@ -394,6 +474,8 @@ def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=
         extra.update(_kinetics_arrays(k, cv[-1], solver=_kinetics_solver(config.observables)))
     if energy is not None:
         extra.update(_energy_arrays(config, energy[0], energy[1], dl))
+        if bg is not None:                     # (latent_z, latent_dlogp) of a chained run with the bg key
+            extra.update(_bg_arrays(config, bg[0], energy[1], bg[1], dl))
     if zmat is not None:                       # (settings, z0, z1) of a run with the zmatrix key
         extra.update(_zmatrix_arrays(zmat[0], zmat[1], zmat[2], extra.get("logw")))
     np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
@@ -403,6 +485,7 @@ def sample_ambient(config, b, dataset):
     _check_kinetics(config)
     energy, E0s, E1s = _check_energy(config), [], []
     zmat, z0s, z1s = _check_zmatrix(config), [], []
+    bg = _check_bg(config, "sample_ambient", dataset)
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -435,7 +518,8 @@ def sample_ambient(config, b, dataset):
         np.save(os.path.join(config.data_save_path, f"E1s_samples_{name}.npy"), energy[1])
     if cvs:
         _write_observables(config, os.path.join(config.data_save_path, f"observables_{name}.npz"), cvs, dlogps, energy=energy,
-                           zmat=None if zmat is None else (zmat, np.concatenate(z0s), np.concatenate(z1s)))
+                           zmat=None if zmat is None else (zmat, np.concatenate(z0s), np.concatenate(z1s)),
+                           bg=None if bg is None else (np.concatenate(latent_noises, axis=0), np.concatenate(latent_dlogps, axis=0)))
     np.save(os.path.join(config.data_save_path, f"latent_noises_{name}.npy"), np.concatenate(latent_noises, axis=0))
     np.save(os.path.join(config.data_save_path, f"latent_dlogps_{name}.npy"), np.concatenate(latent_dlogps, axis=0))
     np.save(os.path.join(config.data_save_path, f"samples_{name}.npy"), np.concatenate(samples, axis=0))
@@ -448,6 +532,7 @@ def sample_latent(config, b, dataset):
     _check_kinetics(config)
     _check_energy(config, "sample_latent")
     _check_zmatrix(config, "sample_latent")
+    bg, E1s, z0s = _check_bg(config, "sample_latent"), [], []
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
                                          n_step=config.n_steps, return_dlogp=bool(config.return_dlogp), reverse_ode=False,
@@ -464,8 +549,16 @@ def sample_latent(config, b, dataset):
             dlogps.append(C.to_numpy(dlogp)[-1, :])                     # sample_latent.py:76-77
         if integrator.observe is not None:
             cvs.append(integrator.cv)
+        if bg is not None:
+            E1, z0 = _batch_bg(b, batch, sample, *bg)
+            E1s.append(E1); z0s.append(z0)
     if cvs:
         _write_observables(config, os.path.join(config.data_save_path, f"observables_{config.data_save_name}_forward.npz"), cvs, dlogps)
+    if bg is not None:
+        E1 = np.concatenate(E1s)
+        np.save(os.path.join(config.data_save_path, f"E1s_samples_{config.data_save_name}_forward.npy"), E1)
+        np.savez(os.path.join(config.data_save_path, f"bg_{config.data_save_name}_forward.npz"), E1=E1,
+                 **_bg_arrays(config, np.concatenate(z0s), E1, np.concatenate(dlogps, axis=0)))
     out = np.concatenate(samples, axis=0)
     np.save(os.path.join(config.data_save_path, f"samples_{config.data_save_name}_forward.npy"), out)
     if config.return_dlogp:
@@ -482,6 +575,7 @@ def sample_adw(config, b, x0s_batches):
     _check_kinetics(config, molecules=False)
     _check_energy(config, "sample_adw")
     _check_zmatrix(config, "sample_adw")
+    _check_bg(config, "sample_adw")
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),
                                          step_control=getattr(config, "step_control", "batch"), fused=bool(getattr(config, "fused", False)),

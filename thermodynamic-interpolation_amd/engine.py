@@ -484,6 +484,59 @@ class _Engine:
         _lib.check(_lib.lib().ti_obs_ti_logw(self.h, p0, p1, np_, B, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return out
 
+    def bg_logw(self, z, u1=None, neg_dlogp_bg=None, neg_dlogp_ti=None, logpz=False):
+        """ti_obs_bg_logw: logw [B] float32 = -(u1 + log N(z; 0, I) + neg_dlogp_bg + neg_dlogp_ti), formed in fp64 on the GPU and
+        rounded once (the log of the reference's calc_importance_weights).  z [B, ...] float32, flattened per row; u1 [B] float64
+        (None: 0); neg_dlogp_bg, neg_dlogp_ti [B] float32 (None: 0).  logpz=True: (logw, log N(z; 0, I) [B] float64).  numpy in,
+        numpy out; CUDA tensors in, CUDA tensors out."""
+        if len(z.shape) < 1 or int(z.shape[0]) < 1:
+            raise ValueError("z must be [B, ...] and non-empty")
+        B = int(z.shape[0])
+        m = int(np.prod(z.shape[1:], dtype=np.int64))
+        if not 1 <= m <= _lib.BG_MAX_M:
+            raise ValueError(f"z must hold 1..{_lib.BG_MAX_M} components per row, got {m}")
+        dev = hasattr(z, "data_ptr") and z.is_cuda
+        if hasattr(z, "data_ptr"):
+            if str(z.dtype) != "torch.float32" or not z.is_contiguous():
+                raise TypeError("z must be a contiguous float32 tensor")
+            z2 = z.reshape(B, m)
+        else:
+            z2 = np.ascontiguousarray(z, np.float32).reshape(B, m)
+        if dev:
+            import torch
+            out = torch.empty(B, dtype=torch.float32, device=z.device)
+            lp = torch.empty(B, dtype=torch.float64, device=z.device) if logpz else None
+        else:
+            out = np.empty(B, np.float32)
+            lp = np.empty(B, np.float64) if logpz else None
+        (zp, bp, tp, op), adev, keep = self._ptrs((z2, (B, m), False, "z"), (neg_dlogp_bg, (B,), False, "neg_dlogp_bg"),
+                                                  (neg_dlogp_ti, (B,), False, "neg_dlogp_ti"), (out, (B,), True, "out"))
+        if adev != dev:
+            raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
+        p1, k1 = (None, None) if u1 is None else self._f64_in(u1, B, "u1", dev)
+        lpp = None if lp is None else C.c_void_p(lp.data_ptr() if dev else lp.ctypes.data)
+        _lib.check(_lib.lib().ti_obs_bg_logw(self.h, zp, B, m, p1, bp, tp, lpp, op, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return (out, lp) if logpz else out
+
+    def bg_ess(self, logpz, u1=None, neg_dlogp_bg=None, neg_dlogp_ti=None, keep=None):
+        """ti_obs_bg_ess: (ess, kept) -- calc_ESS of the weights exp(-(u1 + logpz + neg_dlogp_bg + neg_dlogp_ti)) from their unrounded
+        fp64 logarithms, over the molecules keep [B] marks (None: all).  logpz [B] float64 as ``bg_logw(..., logpz=True)`` returns
+        it; the other arrays as in ``bg_logw``; all where logpz lives."""
+        B = int(logpz.shape[0])
+        dev = hasattr(logpz, "data_ptr") and logpz.is_cuda
+        (bp, tp), adev, keepalive = self._ptrs((neg_dlogp_bg, (B,), False, "neg_dlogp_bg"), (neg_dlogp_ti, (B,), False, "neg_dlogp_ti"))
+        if (neg_dlogp_bg is not None or neg_dlogp_ti is not None) and adev != dev:
+            raise ValueError("all buffers of a call must live in the same memory space (all host or all on the GPU)")
+        if dev and neg_dlogp_bg is None and neg_dlogp_ti is None:
+            import torch
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        lp, k0 = self._f64_in(logpz, B, "logpz", dev)
+        p1, k1 = (None, None) if u1 is None else self._f64_in(u1, B, "u1", dev)
+        kp, k2 = (None, None) if keep is None else self._u8_in(keep, B, "keep", dev)
+        ess, kept = C.c_double(0.0), C.c_int64(0)
+        _lib.check(_lib.lib().ti_obs_bg_ess(self.h, lp, B, p1, bp, tp, kp, C.byref(ess), C.byref(kept), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return ess.value, kept.value
+
     # ---- velocity loss (ti_painn_vloss / ti_adw_vloss): the shared part of PainnEngine.velocity_loss and AdwEngine.velocity_loss
     @staticmethod
     def _vloss_desc(kind, gamma, a, center, t, t_distr, seed, traj_offset, draw, tbins):

@@ -478,6 +478,42 @@ def ti_logw(u0, u1, neg_dlogp, engine=None):
     return (engine or _service_engine(_device_of(u1))).ti_logw(u0, u1, neg_dlogp)
 
 
+def log_prior(z, engine=None):
+    """log N(z; 0, I) [B] float64 of the prior samples z [B, ...] float32, each row flattened (the reference's calc_log_mvnormal_pzs):
+    -(sum z^2) / 2 - m log(2 pi) / 2 in fp64 on the GPU, a function of the row alone (ti_obs_bg_logw).  Lives where z lives."""
+    return (engine or _service_engine(_device_of(z))).bg_logw(z, logpz=True)[1]
+
+
+def bg_logw(z0, E1, neg_dlogp_bg, neg_dlogp_ti=None, engine=None):
+    """logw [B] float32 = -(E1 + log N(z0; 0, I) + neg_dlogp_bg + neg_dlogp_ti): the log of the reference's calc_importance_weights,
+    the weight of a Boltzmann generator's sample (neg_dlogp_ti None) or of a latent -> ambient chain's.  z0 [B, ...] float32, E1 [B]
+    float64 reduced energies of the generated state (None: 0), the dlogps [B] float32 (None: 0); formed in fp64 on the GPU and
+    rounded once: what ``importance_weights``, ``weighted_histogram``, ``bootstrap`` and ``rff_gram`` take.  Lives where z0 lives."""
+    return (engine or _service_engine(_device_of(z0))).bg_logw(z0, E1, neg_dlogp_bg, neg_dlogp_ti)
+
+
+def ess_bg(z0, E1, neg_dlogp_bg, neg_dlogp_ti=None, k=None, **kw):
+    """gen_ess_bg: the ESS of the Boltzmann-generator weights, filtered once when k is given.  The interval and the resample
+    estimates are ``bootstrap(bg_logw(...), "ess", k=k)``; the point estimate is taken from the unrounded fp64 log-weights
+    (ti_obs_bg_ess) over the sample the filter kept, so that it is calc_ESS of the reference's fp64 weights to the summation error --
+    the one fp32 rounding of ``bg_logw`` alone would move it by up to 2e-6 relative."""
+    eng = kw.get("engine") or _service_engine(_device_of(z0))
+    logw, logpz = eng.bg_logw(z0, E1, neg_dlogp_bg, neg_dlogp_ti, logpz=True)
+    r = bootstrap(logw, "ess", k=k, **kw)
+    keep = None if k is None else iqr_keep(logw, k)
+    if keep is not None and hasattr(logw, "data_ptr") and logw.is_cuda:
+        import torch
+        keep = torch.from_numpy(keep).to(logw.device)
+    point, _ = eng.bg_ess(logpz, E1, neg_dlogp_bg, neg_dlogp_ti, keep)
+    return BootstrapResult(point, r.ci, r.estimates, r.n_kept)
+
+
+def free_energy_bg_tfep(E_T0, neg_dlogp_T0, E_T1, neg_dlogp_T1, k=None, **kw):
+    """gen_free_energy_bg_tfep: dF = -ln<exp(-phi)>, phi = E_T1 + neg_dlogp_T1 - E_T0 - neg_dlogp_T0 (calc_phis_bg_tfep), the fold
+    ``free_energy_tfep`` names; with k every resample is filtered on exp(-phi) by its own quartiles."""
+    return bootstrap(_neg_phi(E_T1, neg_dlogp_T1, _neg(E_T0), _neg(neg_dlogp_T0)), "tfep", k=k, **kw)
+
+
 def free_energy_profile(x, logw, bins=80, range=(-2.5, 2.5), engine=None):
     """F [bins] = -ln p_hat, p_hat the weighted histogram of x normalised over the range and divided by the bin width (a density);
     +inf for empty bins."""

@@ -34,6 +34,41 @@ class MoleculeIntegrator(MoleculeIntegratorBase):
         xts, dlogp, self.n_fevals = self._rollout(batch, traj_offset)
         return xts, dlogp, batch.batch
 
+    def log_prob(self, batch):
+        """log p_model(x) [B] float64 of the conformations in batch.x0 (where rollout reads its start state), the model being this
+        map applied to N(0, I) noise.  Build-defined: the reference has no such function; -log_prob on held-out MD frames is a
+        Boltzmann generator's usual validation number.  One rollout with return_dlogp=True on this integrator's own method, step
+        count, tolerances and divergence settings carries x back along the same field, (b, -div b) on the grid from `end` down to
+        `start`, to z_end with the end-state dlogp d; then, in fp64,
+            log_prob = observables.log_prior(z_end) - d.
+        The sign follows from one identity: a forward run from z0 to x1 with end-state neg_dlogp has log p_model(x1) =
+        log_prior(z0) + neg_dlogp (the second state integrates -div b), and on the way back the same pair over negative steps
+        integrates +div b, so d = -neg_dlogp up to the solver's error.  reverse_ode=True is NOT this inverse: as in the reference
+        (ode_wrapper.py:49, integrators.py:40-43) it negates b AND descends the grid, which pushes x forward a second time -- on
+        the CPU oracle its z_end misses z0 by O(1) and the composed density misses the identity by 1.4 where this rollout meets it to
+        9e-5 (div_latent_multi, heun, 9 grid points).  As in ``observables.bg_logw`` the prior is the full 3A-dimensional normal.
+        One species per call.  Lives where batch.x0 lives."""
+        import numpy as np
+        from .. import observables as _obs
+        from . import _common as C
+        from ._molecule import split_species_batch
+        sb = split_species_batch(batch, self.b.ATOM_KEY)
+        if sb.n_atoms is not None:
+            raise ValueError("log_prob takes one species per call (the prior's dimension is 3A)")
+        saved = self.return_dlogp, self.reverse_ode, self.start, self.end
+        self.return_dlogp, self.reverse_ode, self.start, self.end = True, False, self.end, self.start
+        try:
+            xts, dlogp, self.n_fevals = self._rollout(batch)
+        finally:
+            self.return_dlogp, self.reverse_ode, self.start, self.end = saved
+        z_end = C.as_f32(xts[-1], (sb.B, 3 * sb.A))
+        d = dlogp[-1]
+        lp = _obs.log_prior(z_end, engine=self.b.engine_of(sb))
+        if C.is_cuda(z_end):
+            import torch
+            return lp - d.to(torch.float64)
+        return C.like(lp - C.to_numpy(d).astype(np.float64), batch.x0)
+
 
 class Trainer(MoleculeTrainerBase):
     """Trains a latent cPaiNN on OneSidedVelocityLoss (train_latent.py): step(batch) is one optimiser step on a batch with the noise
