@@ -143,6 +143,28 @@ def test_narrow_spectra_through_the_wide_entry_are_the_narrow_call(eng):
     assert bits(*obs.gedmd_spectrum_wide(G, omega, 2.0, 4, 1e-4, engine=eng)) == bits(*obs.gedmd_spectrum(G, omega, 2.0, 4, 1e-4, solver="device", engine=eng))
 
 
+def test_wide_spectra_give_the_same_bits_from_host_and_device_memory(eng):
+    """p = 66 (the first blocked order), d = 2, nev = 3 on the two Gram matrices of rff_gram_wide over 200 samples with one resample:
+    eigenvalues, eigenvectors and ranks of a call on host arrays against the call on the device stack, so that the per-matrix
+    offsets of all three outputs count; without the eigenvectors the eigenvalues and ranks keep their bits."""
+    import torch
+    obs = pkg().observables
+    x = np.random.RandomState(66).standard_normal((200, 2)).astype(np.float32)
+    omega = obs.sample_rff_gaussian(2, 66, 0.8, 4)
+    Gd = obs.rff_gram_wide(torch.from_numpy(x).cuda(), omega, n_boot=1, seed=3, engine=eng)
+    assert Gd.is_cuda and tuple(Gd.shape) == (2, 66, 66)
+    G = Gd.cpu().numpy()
+    ev, vec, rank = eng.gedmd_spectrum_wide(G, omega, 1.6, 3, 1e-4)
+    evd, vecd, rankd = eng.gedmd_spectrum_wide(Gd, omega, 1.6, 3, 1e-4)
+    assert evd.is_cuda and vecd.is_cuda and rankd.is_cuda and vecd.dtype == torch.complex128
+    assert ev.shape == (2, 3) and vec.shape == (2, 66, 3) and rank.shape == (2,) and rank.dtype == np.int32
+    assert np.isfinite(ev).all() and np.isfinite(vec).all() and (rank >= 3).all() and (rank <= 66).all()
+    assert bits(evd, vecd, rankd) == bits(ev, vec, rank)
+    assert bits(ev[0]) != bits(ev[1])                                # two different matrices
+    ev2, none, rank2 = eng.gedmd_spectrum_wide(G, omega, 1.6, 3, 1e-4, vectors=False)
+    assert none is None and bits(ev2, rank2) == bits(ev, rank)
+
+
 def test_fixture_rows_reproduce_the_reference_and_the_host_route(eng):
     """gedmd_generator_wide with the reference's own index rows (p = 300 twice, 513, 130 and the narrower cases): eigenvalues within
     64 ev_dev of the recorded ones, ranks exactly; and gedmd_spectrum_wide on the device Gram stack against gedmd_spectrum(solver="host")

@@ -251,6 +251,37 @@ def test_weighted_histogram_and_ess(Bn, bins, lo, hi):
         np.testing.assert_allclose(f, on.free_energy_profile(v, logw, bins, lo, hi), rtol=0, atol=1e-9)
 
 
+def test_a_strided_column_gives_the_same_bits_from_host_and_device_memory():
+    """ti_obs_hist on column 1 of a [70, 3] array, 8 bins: a host call packs the column before the upload, a device call reads it in
+    place through the stride.  Both give the bits of the contiguous column, with weights (the shift and the sums run first) and
+    without (the scratch is sized by the call itself).  The neighbouring columns lie outside the range, so a wrong stride or a
+    wrong column would move weight into the tails; the bound against the restatement is the module's, 1e-12 B."""
+    import torch
+    eng = pkg().observables._service_engine(0)
+    Bn, bins, lo, hi = 70, 8, -1.0, 3.0
+    rs = np.random.RandomState(70)
+    v = rs.uniform(lo - 0.8, hi + 0.8, Bn)
+    v[on.edge_clearance(v.astype(np.float32), bins, lo, hi) < 2e-6] += 4e-6
+    v = v.astype(np.float32)
+    assert (on.edge_clearance(v, bins, lo, hi) > 1e-6).all()
+    logw = rs.uniform(-30.0, 30.0, Bn).astype(np.float32)
+    cv = np.empty((Bn, 3), np.float32)
+    cv[:, 0], cv[:, 1], cv[:, 2] = lo - 5.0, v, hi + 5.0
+    cvd = torch.from_numpy(cv).cuda()
+    assert cv[:, 1].strides == (12,) and cvd[:, 1].stride(0) == 3
+    for lw in (logw, None):
+        h_ref, t_ref = on.weighted_histogram(v, lw, bins, lo, hi)
+        hh, th = eng.weighted_histogram(cv[:, 1], lw, bins, (lo, hi))
+        hd, td = eng.weighted_histogram(cvd[:, 1], None if lw is None else torch.from_numpy(lw).cuda(), bins, (lo, hi))
+        hc, tc = eng.weighted_histogram(v, lw, bins, (lo, hi))
+        print(f"weighted={lw is not None}: max |hist - ref| {np.abs(hh - h_ref).max():.3e}, tails {th}")
+        assert np.abs(hh - h_ref).max() <= 1e-12 * Bn and np.abs(th - t_ref).max() <= 1e-12 * Bn
+        assert th[0] > 0 and th[1] > 0 and hh.min() > 0
+        for h2, t2 in ((hd, td), (hc, tc)):
+            np.testing.assert_array_equal(hh.view(np.uint64), h2.view(np.uint64))
+            np.testing.assert_array_equal(th.view(np.uint64), t2.view(np.uint64))
+
+
 def test_non_finite_logw_is_refused_with_its_index():
     ti = pkg()
     eng = ti.observables._service_engine(0)

@@ -9,7 +9,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libti_hip.so")
-SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api_vloss.hip", "painn_pack.hip", "painn_host.hip",      # host units (no kernels)
+SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_vloss.hip", "painn_pack.hip", "painn_host.hip",      # host units (no kernels)
+           # host units of the observables (ti_obs_*), one per concern: CVs and the observer, weights, histograms, TI and Boltzmann-
+           # generator log-weights, with the reductions the others share; bootstrap and RFF Gram matrices; the eigensolvers and the gEDMD
+           # spectra; Z-matrix coordinates; the force field whole (tables, energies, forces, Langevin dynamics, replica exchange)
+           "api_obs.hip", "api_obs_resample.hip", "api_obs_eig.hip", "api_obs_zmat.hip", "api_ff.hip",
            "painn_kernels.hip", "painn_edge_nb1.hip", "painn_edge_nb2.hip", "painn_edge_nb4.hip", "painn_edge_nb8.hip",
            "painn_pair_nb1.hip", "painn_pair_nb2.hip", "painn_pair_nb4.hip", "painn_jvp_kernels.hip", "adw_kernels.hip", "ode_kernels.hip",
            # masked twins of the message kernels (per-molecule edge sets), in translation units of their own
@@ -54,11 +58,11 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_obs.hip", "api
            "painn_steps_kernels.hip", "painn_noise_kernels.hip",
            # layer-0 phi table (class pass, table kernel); the pair kernel's table builds live in painn_pair_nb*.hip
            "painn_phi0_kernels.hip",
-           # force-field forces and Langevin dynamics with them (ti_obs_ff_forces, ti_obs_ff_set_masses, ti_obs_ff_langevin): the host
-           # unit and the kernels, which share the per-term gradients of ff_device.hpp; obs_ff_kernels.hip's code object stays as it was
-           "api_ff_md.hip", "obs_ff_md_kernels.hip",
+           # force-field forces and Langevin dynamics with them (ti_obs_ff_forces, ti_obs_ff_set_masses, ti_obs_ff_langevin): the
+           # kernels, which share the per-term gradients of ff_device.hpp; obs_ff_kernels.hip's code object stays as it was
+           "obs_ff_md_kernels.hip",
            # replica exchange between the Langevin launches (ti_obs_ff_remd): the attempt kernel, a unit of its own; its entry point
-           # lives in api_ff_md.hip next to ti_obs_ff_langevin's, the table staging both kernel units share in ff_stage.hpp
+           # lives in api_ff.hip next to ti_obs_ff_langevin's, the table staging both kernel units share in ff_stage.hpp
            "obs_ff_remd_kernels.hip",
            # the update kernel's builds that keep v_eff in registers (painn_update_kernel_body.inc: KEEP): a unit of its own, the code
            # objects of painn_kernels.hip stay as they were

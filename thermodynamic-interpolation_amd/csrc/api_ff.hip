@@ -1,16 +1,11 @@
-// api_ff_md.hip -- C ABI of the force-field forces and of Langevin dynamics with them (include/ti_hip.h ti_obs_ff_forces,
-// ti_obs_ff_set_masses, ti_obs_ff_langevin) and of replica exchange between its launches (ti_obs_ff_remd): checks, staging and the
-// launch cut.  Kernels: obs_ff_md_kernels.hip, obs_ff_remd_kernels.hip.
+// api_ff.hip -- C ABI of the force field (include/ti_hip.h): its tables and energies (ti_obs_ff_set, ti_obs_ff_energy), its forces
+// (ti_obs_ff_forces), Langevin dynamics with them (ti_obs_ff_set_masses, ti_obs_ff_langevin) and replica exchange between its launches
+// (ti_obs_ff_remd): checks, staging and the launch cut.  Kernels: obs_ff_kernels.hip, obs_ff_md_kernels.hip, obs_ff_remd_kernels.hip.
 #include "ti_handle.hpp"
 #include "ff_device.hpp"
 
-#include <cmath>
-
-using namespace ti;
-
-namespace ti {
-
-std::vector<int32_t> ff_build_incidence(const std::vector<int32_t>& words, const int* n, int A)
+// the packed incidence list of the bonded term words (bonds, angles, torsions of lengths n[0..2]; ff_device.hpp)
+static std::vector<int32_t> ff_build_incidence(const std::vector<int32_t>& words, const int* n, int A)
 {
     const int chunks = ff_chunks(n[0]) + ff_chunks(n[1]) + ff_chunks(n[2]);
     std::vector<uint16_t> off((size_t)chunks * A + 1, 0);
@@ -31,8 +26,6 @@ std::vector<int32_t> ff_build_incidence(const std::vector<int32_t>& words, const
     return out;
 }
 
-}  // namespace ti
-
 static FfTablesDev ff_tables(const ti_handle* h)
 {
     FfTablesDev t{};
@@ -41,14 +34,103 @@ static FfTablesDev ff_tables(const ti_handle* h)
     return t;
 }
 
-int ti_obs_ff_forces(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_f, double* out_e, int mem)
+// The refusal of a call with per-molecule temperatures T_dev [B], before anything is written: one launch and one wait, the index
+// found as ti_obs_weights finds its own
+static int ff_temperature_refusal(ti_handle* h, const float* T_dev, long long B)
+{
+    hipStream_t st = h->stream;
+    obs_scratch(h);
+    double bad = 0.0;
+    HIP_CHECK(launch_obs_ff_bad_temperature(h->obs_red.p, T_dev, B, st));
+    HIP_CHECK(hipMemcpyAsync(&bad, h->obs_red.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (bad < (double)B) return fail(TI_E_ARG, "T must be finite and > 0: index " + std::to_string((long long)bad));
+    return TI_OK;
+}
+
+int ti_obs_ff_set(ti_handle* h, const ti_ff_desc* desc, const int32_t* bond_idx, const double* bond_par, const int32_t* angle_idx,
+                  const double* angle_par, const int32_t* torsion_idx, const double* torsion_par, const double* pair_par)
+{
+    if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
+    if (!desc) { h->ff_on = false; h->ff_mass_on = false; return TI_OK; }
+    if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
+    const int A = h->d.n_atoms;
+    const int n[4] = {desc->n_bonds, desc->n_angles, desc->n_torsions, desc->n_pairs};
+    const int cap[4] = {TI_FF_MAX_BONDS, TI_FF_MAX_ANGLES, TI_FF_MAX_TORSIONS, TI_FF_MAX_PAIRS};
+    const char* name[4] = {"bond", "angle", "torsion", "pair"};
+    const int32_t* idx[3] = {bond_idx, angle_idx, torsion_idx};
+    const double* par[4] = {bond_par, angle_par, torsion_par, pair_par};
+    for (int t = 0; t < 4; ++t) {
+        if (n[t] < 0 || n[t] > cap[t]) return fail(TI_E_ARG, std::string(name[t]) + " count " + std::to_string(n[t]) + " is outside 0.." + std::to_string(cap[t]));
+        if (n[t] > 0 && (!par[t] || (t < 3 && !idx[t]))) return fail(TI_E_ARG, std::string(name[t]) + " table is NULL");
+    }
+    if (n[3] != A * (A - 1) / 2) return fail(TI_E_ARG, "the pair table must hold all A (A - 1) / 2 = " + std::to_string(A * (A - 1) / 2) + " pairs, got " + std::to_string(n[3]));
+    if (!std::isfinite(desc->coulomb)) return fail(TI_E_ARG, "coulomb must be finite");
+    std::vector<int32_t> words; std::vector<double> pars;
+    for (int t = 0; t < 3; ++t) {                              // bonds (2 atoms, 2 parameters), angles (3, 2), torsions (4, 3)
+        const int na = 2 + t, np = t == 2 ? 3 : 2;
+        for (int k = 0; k < n[t]; ++k) {
+            const std::string what = std::string(name[t]) + " " + std::to_string(k);
+            const int32_t* a = idx[t] + (size_t)na * k;
+            const double* q = par[t] + (size_t)np * k;
+            int32_t w = 0;
+            for (int s = 0; s < na; ++s) {
+                if (a[s] < 0 || a[s] >= A) return fail(TI_E_ARG, what + ": atom index outside 0.." + std::to_string(A - 1));
+                for (int s2 = 0; s2 < s; ++s2)
+                    if (a[s2] == a[s]) return fail(TI_E_ARG, what + ": atom " + std::to_string(a[s]) + " is repeated");
+                w |= a[s] << (5 * s);
+            }
+            for (int s = 0; s < np; ++s)
+                if (!std::isfinite(q[s])) return fail(TI_E_ARG, what + ": non-finite parameter");
+            if (t == 2) {                                      // (n, phase, k): the periodicity goes into the word
+                if (q[0] != std::floor(q[0]) || q[0] < 1.0 || q[0] > 6.0) return fail(TI_E_ARG, what + ": the periodicity must be an integer in 1..6");
+                w |= (int32_t)q[0] << 20;
+                pars.push_back(q[1]); pars.push_back(q[2]);
+            } else {
+                pars.push_back(q[0]); pars.push_back(q[1]);
+            }
+            words.push_back(w);
+        }
+    }
+    for (int i = 0, k = 0; i < A; ++i)                         // row i (2A - i - 1) / 2 + (j - i - 1)
+        for (int j = i + 1; j < A; ++j, ++k) {
+            const double* q = pair_par + 3 * (size_t)k;
+            const std::string what = "pair " + std::to_string(k) + " (" + std::to_string(i) + ", " + std::to_string(j) + ")";
+            if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2])) return fail(TI_E_ARG, what + ": non-finite parameter");
+            if (q[1] < 0.0 || q[2] < 0.0) return fail(TI_E_ARG, what + ": sigma and eps must be >= 0");
+            words.push_back(i | j << 5 | ((q[0] != 0.0 || q[2] != 0.0) ? FF_LIVE : 0));
+            pars.insert(pars.end(), q, q + 3);
+        }
+    const std::vector<int32_t> inc = ff_build_incidence(words, n, A);      // of the bonded terms, for ti_obs_ff_forces / ti_obs_ff_langevin
+    return guarded([&]() -> int {
+        set_device(h);
+        h->ff_on = false;
+        h->ff_mass_on = false;                                 // the masses go with the force field (ti_obs_ff_set_masses)
+        h->ff_idx.upload(words);
+        h->ff_par.upload(pars);
+        h->ff_inc.upload(inc);
+        std::copy(n, n + 4, h->ff_n);
+        h->ff_coulomb = desc->coulomb;
+        h->ff_on = true;
+        return TI_OK;
+    });
+}
+
+// the refusals of ti_obs_ff_energy and ti_obs_ff_forces, in the header's order; out: the output the call cannot do without
+static int ff_eval_refusal(const ti_handle* h, const float* x, const double* out, int64_t B, double to_nm, int mem)
 {
     if (!h || h->kind != 0) return fail(TI_E_ARG, "not a painn handle");
     if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
-    if (B < 0 || (B > 0 && (!x || !out_f))) return fail(TI_E_ARG, "NULL buffer");
+    if (B < 0 || (B > 0 && (!x || !out))) return fail(TI_E_ARG, "NULL buffer");
     if (!std::isfinite(to_nm)) return fail(TI_E_ARG, "to_nm must be finite");
     if (!h->ff_on) return fail(TI_E_ARG, "no force field set (ti_obs_ff_set)");
     if (!h->natoms.empty()) return fail(TI_E_UNSUPPORTED, "one force field is one species: clear ti_painn_set_molecules first");
+    return TI_OK;
+}
+
+int ti_obs_ff_energy(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_e, double* out_terms, int mem)
+{
+    if (int rc = ff_eval_refusal(h, x, out_e, B, to_nm, mem)) return rc;
     if (B == 0) return TI_OK;
     return guarded([&]() -> int {
         set_device(h);
@@ -57,14 +139,31 @@ int ti_obs_ff_forces(ti_handle* h, const float* x, int64_t B, double to_nm, cons
         Staged sg(h, mem);
         const float* xd = sg.in(x, h->obs_x, (size_t)B * 3 * A);
         const float* Td = T ? sg.in(T, h->ff_T, (size_t)B) : nullptr;
-        if (Td) {                                      // refused before anything is written, as ti_obs_ff_energy does it
-            grow(h->obs_red, 4 + 259);
-            double bad = 0.0;
-            HIP_CHECK(launch_obs_ff_bad_temperature(h->obs_red.p, Td, B, st));
-            HIP_CHECK(hipMemcpyAsync(&bad, h->obs_red.p, sizeof(double), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            if (bad < (double)B) return fail(TI_E_ARG, "T must be finite and > 0: index " + std::to_string((long long)bad));
-        }
+        if (Td) { if (int rc = ff_temperature_refusal(h, Td, B)) return rc; }
+        FfParams p{};
+        p.x = xd; p.T = Td; p.B = B; p.A = A; p.to_nm = to_nm; p.coulomb = h->ff_coulomb;
+        p.nb = h->ff_n[0]; p.na = h->ff_n[1]; p.nt = h->ff_n[2]; p.np = h->ff_n[3];
+        p.idx = h->ff_idx.p; p.par = h->ff_par.p;
+        p.e = sg.out(out_e, h->ff_e, (size_t)B);
+        p.terms = out_terms ? sg.out(out_terms, h->ff_terms, (size_t)B * 4) : nullptr;
+        HIP_CHECK(launch_obs_ff_energy(p, st));
+        sg.finish();
+        return TI_OK;
+    });
+}
+
+int ti_obs_ff_forces(ti_handle* h, const float* x, int64_t B, double to_nm, const float* T, double* out_f, double* out_e, int mem)
+{
+    if (int rc = ff_eval_refusal(h, x, out_f, B, to_nm, mem)) return rc;
+    if (B == 0) return TI_OK;
+    return guarded([&]() -> int {
+        set_device(h);
+        hipStream_t st = h->stream;
+        const int A = h->d.n_atoms;
+        Staged sg(h, mem);
+        const float* xd = sg.in(x, h->obs_x, (size_t)B * 3 * A);
+        const float* Td = T ? sg.in(T, h->ff_T, (size_t)B) : nullptr;
+        if (Td) { if (int rc = ff_temperature_refusal(h, Td, B)) return rc; }
         FfForceParams p{};
         p.t = ff_tables(h);
         p.x = xd; p.T = Td; p.B = B; p.to_nm = to_nm;
@@ -129,18 +228,17 @@ static int md_run(ti_handle* h, const ti_md_desc* d, const RemdArgs& x, double* 
         const int A = h->d.n_atoms;
         const size_t n_state = (size_t)B * 3 * A;
         const long long n_frames = d->stride > 0 ? d->n_steps / d->stride : 0;
-        const hipMemcpyKind in_kind = mem == TI_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        const hipMemcpyKind out_kind = mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
         const bool host = mem == TI_MEM_HOST;
         Staged sg(h, mem);
         const float* Td = sg.in(T, h->ff_T, (size_t)B);
         const int64_t* idd = ids ? sg.in(ids, h->md_ids, (size_t)B) : nullptr;
         // the state is advanced in a working copy: pos / vel change only when the whole call succeeds
-        grow(h->md_pos, n_state); grow(h->md_vel, n_state); grow(h->md_flag, (size_t)B + 2); grow(h->obs_red, 4 + 259);
-        HIP_CHECK(hipMemcpyAsync(h->md_pos.p, pos, n_state * sizeof(double), in_kind, st));
-        if (!d->draw_velocities) HIP_CHECK(hipMemcpyAsync(h->md_vel.p, vel, n_state * sizeof(double), in_kind, st));
+        grow(h->md_pos, n_state); grow(h->md_vel, n_state); grow(h->md_flag, (size_t)B + 2); obs_scratch(h);
+        HIP_CHECK(hipMemcpyAsync(h->md_pos.p, pos, n_state * sizeof(double), in_kind(mem), st));
+        if (!d->draw_velocities) HIP_CHECK(hipMemcpyAsync(h->md_vel.p, vel, n_state * sizeof(double), in_kind(mem), st));
         HIP_CHECK(hipMemsetAsync(h->md_flag.p, 0, (size_t)B * sizeof(int), st));
-        HIP_CHECK(launch_obs_ff_bad_temperature(h->obs_red.p, Td, B, st));       // the launches below return at once on a bad T
+        // not ff_temperature_refusal: the launches below read the flag and return at once on a bad T, the host waits once, at the end
+        HIP_CHECK(launch_obs_ff_bad_temperature(h->obs_red.p, Td, B, st));
         MdParams p{};
         p.t = ff_tables(h);
         p.pos = h->md_pos.p; p.vel = h->md_vel.p; p.T = Td; p.ids = reinterpret_cast<const long long*>(idd); p.mass = h->ff_mass.p;
@@ -199,9 +297,9 @@ static int md_run(ti_handle* h, const ti_md_desc* d, const RemdArgs& x, double* 
             if (flag[b])
                 return fail(TI_E_NAN, "replica " + std::to_string((long long)b) + ": the state turned non-finite in launch " + std::to_string(flag[b] - 1) +
                                           " (pos and vel are left as they were)");
-        HIP_CHECK(hipMemcpyAsync(pos, h->md_pos.p, n_state * sizeof(double), out_kind, st));
-        if (vel) HIP_CHECK(hipMemcpyAsync(vel, h->md_vel.p, n_state * sizeof(double), out_kind, st));
-        if (x.r && x.walker) HIP_CHECK(hipMemcpyAsync(x.walker, h->md_walker.p, (size_t)B * sizeof(int32_t), out_kind, st));
+        HIP_CHECK(hipMemcpyAsync(pos, h->md_pos.p, n_state * sizeof(double), out_kind(mem), st));
+        if (vel) HIP_CHECK(hipMemcpyAsync(vel, h->md_vel.p, n_state * sizeof(double), out_kind(mem), st));
+        if (x.r && x.walker) HIP_CHECK(hipMemcpyAsync(x.walker, h->md_walker.p, (size_t)B * sizeof(int32_t), out_kind(mem), st));
         if (hist && host) HIP_CHECK(hipMemcpyAsync(x.out_walker, hist, (size_t)n_attempts * B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (q.counts && host) HIP_CHECK(hipMemcpyAsync(x.out_counts, q.counts, n_counts * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         sg.finish();

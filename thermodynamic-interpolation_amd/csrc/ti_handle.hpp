@@ -2,6 +2,13 @@
 // (include/ti_hip.h), the staging of host-resident arguments, and the host functions the units call across each other:
 //   painn_pack.hip   weight packing, edge templates          painn_host.hip   PaiNN workspace, drift / divergence drivers, graph state
 //   rollout.hpp      the integrator drivers (templates)      api_*.hip        the extern "C" entry points
+// The observables' entry points by unit:
+//   api_obs.hip           states or log-weights into per-sample numbers and histograms (CVs and the observer, weights, histograms,
+//                         TI and Boltzmann-generator log-weights); the reductions the other units share (obs_scratch, logw_shift_dev)
+//   api_obs_resample.hip  bootstrap intervals, RFF Gram matrices of resamples
+//   api_obs_eig.hip       both eigensolvers, both gEDMD spectra
+//   api_obs_zmat.hip      Z-matrix coordinates both ways
+//   api_ff.hip            the force field: tables, energies, forces, Langevin dynamics, replica exchange
 //
 // There is deliberately no CPU fallback in the host code: every entry point either runs the HIP kernels or fails.
 #pragma once
@@ -298,12 +305,28 @@ struct Staged {
         back[n_back++] = {p, b.p, n * sizeof(T)};
         return b.p;
     }
+    // The first d columns of the n rows of p, `stride` floats apart.  TI_MEM_HOST: packed densely into b, so that only they cross the
+    // bus (a blocking copy: the packed rows are a pageable temporary), and stride becomes d.
+    const float* in_cols(const float* p, long long& stride, long long n, int d, DevBuf<float>& b)
+    {
+        if (!host) return p;
+        std::vector<float> rows((size_t)n * d);
+        for (long long i = 0; i < n; ++i) std::copy(p + i * stride, p + i * stride + d, rows.begin() + i * d);
+        grow(b, rows.size());
+        HIP_CHECK(hipMemcpy(b.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+        stride = d;
+        return b.p;
+    }
     void finish(bool copy_back = true)
     {
         for (int i = 0; copy_back && i < n_back; ++i) HIP_CHECK(hipMemcpyAsync(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
     }
 };
+
+// the direction of a copy between the handle's buffers and a caller's array that lives where `mem` says, for the calls that copy by hand
+inline hipMemcpyKind in_kind(int mem) { return mem == TI_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice; }
+inline hipMemcpyKind out_kind(int mem) { return mem == TI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice; }
 
 struct JvpRun {            // one tangent pass riding on a drift evaluation
     int D;                 // seed directions per molecule
@@ -312,9 +335,6 @@ struct JvpRun {            // one tangent pass riding on a drift evaluation
 };
 
 inline int obs_floats_per_traj(const ti_handle* h) { return h->kind == 0 ? 3 * h->d.n_atoms : h->a_dim; }
-
-// ---- api_ff_md.hip: the packed incidence list of the bonded term words (bonds, angles, torsions of lengths n[0..2]; ff_device.hpp)
-std::vector<int32_t> ff_build_incidence(const std::vector<int32_t>& words, const int* n, int A);
 
 // ---- painn_pack.hip
 void pack_chunk16(std::vector<float>& dst, const float* W, int ld, int n_rows, int row0, int col0, int NBK);
@@ -348,10 +368,12 @@ void phi0_end_call(ti_handle* h);
 int set_graph_state(ti_handle* h, std::vector<uint32_t>& m, std::vector<int32_t>& natoms, std::vector<uint8_t>& ptype, long long B);
 void clear_graph_state(ti_handle* h);
 
-// ---- api_adw.hip, api_obs.hip: what ti_reserve, the rollout drivers and the velocity loss need of them
+// ---- api_adw.hip, api_obs.hip: what ti_reserve, the rollout drivers, the velocity loss and the other observables units need of them
 void ensure_adw_ws(ti_handle* h, long long B);
 void adw_drift_tv_dev(ti_handle* h, const float* x_dev, const float* tv, const float* beta0, const float* beta1, long long B, float* out_dev,
                       float* out_div);
 void obs_cv_dev(ti_handle* h, int which, const float* x_dev, long long B, float* cv_dev);
+void obs_scratch(ti_handle* h, size_t words = 259);
+int logw_shift_dev(ti_handle* h, const float* logw_dev, long long n, double out[2]);
 
 }  // namespace ti
