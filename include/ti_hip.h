@@ -739,6 +739,56 @@ int ti_obs_zmat_xyz(ti_handle* h, const int32_t* order, const int32_t* ref, cons
  * keeps nothing; TI_E_NAN: a non-finite kept logw (the message names the first such index). */
 int ti_obs_hist_cols(ti_handle* h, const float* values, int32_t K, const float* logw, const uint8_t* keep, int64_t B, int32_t n_bins,
                      const double* lo, const double* hi, double* out_hist, double* out_tails, int mem);
+/* Time-lagged independent component analysis (TICA) of featurised trajectories: what the reference's mdqm9/plots/10506_main.ipynb
+ * (cell 3) does with deeptime.decomposition.TICA(lagtime, dim) on the (cos, sin) encoding of the torsions.  The estimator is
+ * defined here, after deeptime's documented reversible one; parity with deeptime's own numbers is not pinned.
+ * Inputs.  values fp32: feature column k of frame i is values[i * stride + k * cstride], cstride >= 1, stride >= (K - 1) cstride + 1
+ * (the torsion column of a [B, A-1, 3] Z-matrix array is read in place: base offset 8, cstride 3, stride 3 (A - 1)); 1 <= K <=
+ * TI_TICA_MAX_K.  encode = 1: d = 2 K, feature 2k = cos x_k, 2k + 1 = sin x_k (fp64 sincos of the fp32 value); encode = 0: d = K, the
+ * value itself.  d <= TI_EIGH_MAX_N.  traj_off [n_traj + 1] int64, host: strictly ascending, traj_off[0] = 0, traj_off[n_traj] = n;
+ * frames traj_off[t] .. traj_off[t + 1] - 1 are trajectory t in time order (ragged trajectories are allowed).  lags [n_lag] int32,
+ * host, each >= 1, 1 <= n_lag <= TI_TICA_MAX_LAGS.
+ * Pairs.  The pairs of lag tau are (i, i + tau) with both frames in one trajectory, ordered trajectory-major, then i ascending;
+ * N_tau their count.  A trajectory of length <= tau contributes none.  N_tau < 2 is refused.
+ * Moments.  With X the first and Y the second frames of the pairs: sx = sum X, sy = sum Y, Sxx = X^T X, Syy = Y^T Y, Sxy = X^T Y, fp64.
+ * ti_obs_tica_moments: count [n_lag] int64 = N_tau, sum [n_lag, 2, d] = (sx, sy), cov [n_lag, 3, d, d] = (Sxx, Syy, Sxy).  A feature
+ * pass writes an fp64 table [n][D] once per call, D = d rounded up to 16: n D > 2^27 is TI_E_ALLOC.  One 256-thread workgroup per
+ * (lag, segment of 8192 pairs) contracts on v_mfma_f64_16x16x4_f64, four pairs per step, the two table rows of 16 pairs at a time
+ * staged through LDS (upper-triangle 16 x 16 tiles of Sxx and Syy, all tiles of Sxy; the column sums as one more product).  Every
+ * tile and every sum runs over a segment's pairs in pair order, the segments are added in order by a second kernel, Sxx and Syy are
+ * mirrored and exactly symmetric, and there are no atomics: a lag's result is a function of (the data, traj_off, tau) only -- not
+ * of the other lags of the call, of mem, or of how the lags share launches -- and a call repeats bit for bit.
+ * TI_E_ARG, before any device work: a NULL handle or buffer; an unknown mem; K, d, n_lag, n, n_traj or the strides out of range; encode
+ * not 0 or 1; a lag < 1; a traj_off that is not as above; N_tau < 2 (the lag is named).  TI_E_NAN, nothing written: a non-finite
+ * value (found on the device; the first such row is named).
+ * Model (ti_obs_tica_fit), per lag, with N = N_tau: mu = (sx + sy) / (2 N), C00 = (Sxx + Syy) / (2 N) - mu mu^T, C0t = (Sxy + Sxy^T) /
+ * (2 N) - mu mu^T.  The eigenpairs (s, V) of C00 in descending order, r = #{s_k > epsilon} (epsilon absolute), L = V[:, :r] /
+ * sqrt(s[:r]), Kt = L^T C0t L of which the upper triangle is read, its eigenpairs (lambda, U) in descending order, R = L U[:, :dim].
+ * In each column of R the entry of largest magnitude is made positive (among exactly equal magnitudes the lowest feature index
+ * decides); scaling = 1 ("kinetic map") then multiplies column k by lambda_k, scaling = 0 leaves it.  Columns and eigenvalues at index
+ * >= r are NaN; rank = r is returned and that is not an error.  Both solves are ti_obs_eigh's Jacobi kernel on the real symmetric
+ * matrix as a Hermitian one with zero imaginary part: its order, its tie rule, its TI_E_UNSUPPORTED after 64 sweeps.  Around them
+ * run fixed-order fp64 kernels, one workgroup per lag.  Results reach the outputs only when the whole call succeeded.
+ * TI_E_ARG, before any device work: a NULL handle or buffer, an unknown mem, n_lag or d out of range, dim outside 1..d, a non-finite
+ * or negative epsilon, scaling not 0 or 1, reserved not 0; then a count < 2.  TI_E_NAN: a non-finite moment.
+ * Projection (ti_obs_tica_transform), all lags in one launch: y_k = sum_f (phi_f(x) - mu_f) R_fk in fp64, f ascending, rounded once
+ * to fp32; a non-finite value in a row gives NaN in that row's outputs; a row's output is a function of the row and the model
+ * alone.  TI_E_ARG: a NULL handle or buffer, an unknown mem, B < 1, K, d (which must be K or 2 K by encode), dim, n_lag or the
+ * strides out of range. */
+#define TI_TICA_MAX_LAGS 32
+#define TI_TICA_MAX_K 32
+typedef struct { int32_t dim, scaling, reserved; double epsilon; } ti_tica_desc;   /* 24 bytes, reserved = 0 */
+/* values fp32, count int64, sum, cov fp64: [host|device] by mem; traj_off int64 and lags int32: host */
+int ti_obs_tica_moments(ti_handle* h, const float* values, int64_t stride, int64_t cstride, int64_t n, int32_t K, int32_t encode,
+                        const int64_t* traj_off, int64_t n_traj, const int32_t* lags, int32_t n_lag, int64_t* count, double* sum, double* cov,
+                        int mem);
+/* count, sum, cov as ti_obs_tica_moments writes them; mean [n_lag, d], ev [n_lag, dim], comp [n_lag, d, dim] fp64, rank [n_lag] int32:
+   [host|device] by mem */
+int ti_obs_tica_fit(ti_handle* h, const int64_t* count, const double* sum, const double* cov, int32_t n_lag, int32_t d, const ti_tica_desc* desc,
+                    double* mean, double* ev, double* comp, int32_t* rank, int mem);
+/* values fp32 (B rows), mean, comp fp64, out [n_lag, B, dim] fp32: [host|device] by mem */
+int ti_obs_tica_transform(ti_handle* h, const float* values, int64_t stride, int64_t cstride, int64_t B, int32_t K, int32_t encode,
+                          const double* mean, const double* comp, int32_t n_lag, int32_t d, int32_t dim, float* out, int mem);
 /* Observer: with one attached, every rollout entry point (ti_painn_rollout, _dlogp, _dlogp_est, ti_adw_rollout, _dlogp) also
  * evaluates the K CVs on the state at the grid points i with i % every == 0 and at the last one -- ti_rollout_rows(n_step, every)
  * rows, whatever save_every is -- and writes them to out_cv [rows, B, K] fp32 ([host|device] by mem; the caller sizes it for the

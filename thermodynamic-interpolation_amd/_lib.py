@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "ti_obs_ff_forces", "ti_obs_ff_set_masses", "ti_obs_ff_langevin",
     "ti_obs_ff_remd",
     "ti_obs_bg_logw", "ti_obs_bg_ess",
+    "ti_obs_tica_moments", "ti_obs_tica_fit", "ti_obs_tica_transform",
 ]
 # CV descriptor kinds (TI_OBS_*)
 OBS_KINDS = {"rmsd": 0, "dist": 1, "angle": 2, "torsion": 3, "coord": 4}
@@ -84,6 +85,9 @@ MD_DEFAULT_STEPS_PER_LAUNCH = 1024
 REMD_MAX_RUNGS, REMD_DOMAIN = 64, 0x52454D44
 # ti_obs_zmat / ti_obs_zmat_xyz: the range of A; ti_obs_hist_cols: the most columns of a call
 ZMAT_MIN_ATOMS, ZMAT_MAX_ATOMS, HIST_COLS_MAX = 2, 32, 128
+# ti_obs_tica_*: the most lags of a call (TI_TICA_MAX_LAGS), the most value columns (TI_TICA_MAX_K), the scalings of the components
+TICA_MAX_LAGS, TICA_MAX_K = 32, 32
+TICA_SCALINGS = {"none": 0, "kinetic_map": 1}
 # ti_*_vloss: loss kinds (TI_VLOSS_*), gamma kinds (TI_GAMMA_*), centring (TI_CENTER_*), time distributions (TI_TDIST_*), the fourth
 # counter word of the time draws, the most bins of a time profile
 VLOSS_KINDS = {"standard": 0, "one_sided": 1}
@@ -127,6 +131,10 @@ class GramDesc(C.Structure):
 
 class GedmdDesc(C.Structure):
     _fields_ = [("d", C.c_int32), ("p", C.c_int32), ("nev", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("tol", C.c_double)]
+
+
+class TicaDesc(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("scaling", C.c_int32), ("reserved", C.c_int32), ("epsilon", C.c_double)]
 
 
 class FfDesc(C.Structure):
@@ -273,6 +281,10 @@ def lib():
     L.ti_obs_zmat.argtypes = [vp, ip, ip, vp, C.c_int64, vp, C.c_int]
     L.ti_obs_zmat_xyz.argtypes = [vp, ip, ip, vp, C.c_int64, vp, vp, vp, C.c_int]
     L.ti_obs_hist_cols.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int]
+    i64p = C.POINTER(C.c_int64)
+    L.ti_obs_tica_moments.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, i64p, C.c_int64, ip, C.c_int32, vp, vp, vp, C.c_int]
+    L.ti_obs_tica_fit.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(TicaDesc), vp, vp, vp, vp, C.c_int]
+    L.ti_obs_tica_transform.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int]
     vd = C.POINTER(VlossDesc)
     L.ti_painn_vloss.argtypes = [vp, vd, vp, vp, vp, vp, vp, C.c_int64, vp, dp, dp, vp, vp, vp, vp, C.c_int]
     L.ti_adw_vloss.argtypes = [vp, vd, vp, vp, vp, vp, vp, vp, C.c_int64, vp, dp, dp, vp, vp, vp, vp, C.c_int]

@@ -66,7 +66,10 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_vloss.hip", "p
            "obs_ff_remd_kernels.hip",
            # the update kernel's builds that keep v_eff in registers (painn_update_kernel_body.inc: KEEP): a unit of its own, the code
            # objects of painn_kernels.hip stay as they were
-           "painn_update_keep.hip"]
+           "painn_update_keep.hip",
+           # TICA (ti_obs_tica_moments, ti_obs_tica_fit, ti_obs_tica_transform): the lagged moments on the fp64 matrix cores, the
+           # algebra around the two solves of obs_eig_kernels.hip and the projection; its entry points, a host unit of their own
+           "obs_tica_kernels.hip", "api_obs_tica.hip"]
 HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "adw_train.hpp", "painn_train.hpp", "painn_steps.hpp", "train_optim.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "vloss_normal.hpp", "ff_device.hpp", "ff_stage.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp", "painn_update_kernel.hpp",
            "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_update_kernel_body.inc", "painn_embed_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
 # -packed-fp32-ops off: v_pk_{fma,mul,add}_f32 do NOT run next to another wave's matrix instructions on gfx950 (a wave of them and a

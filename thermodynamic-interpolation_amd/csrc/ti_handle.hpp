@@ -8,6 +8,7 @@
 //   api_obs_resample.hip  bootstrap intervals, RFF Gram matrices of resamples
 //   api_obs_eig.hip       both eigensolvers, both gEDMD spectra
 //   api_obs_zmat.hip      Z-matrix coordinates both ways
+//   api_obs_tica.hip      TICA: lagged moments, the model, the projection
 //   api_ff.hip            the force field: tables, energies, forces, Langevin dynamics, replica exchange
 //
 // There is deliberately no CPU fallback in the host code: every entry point either runs the HIP kernels or fails.
@@ -216,6 +217,12 @@ struct ti_handle {
     // Z-matrix coordinates and column histograms (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols): the topology of the call (order,
     // ref), staging of a host call's z, log-determinants, validity and keep masks, the column ranges (lo [K], hi [K])
     DevBuf<int32_t> zm_topo; DevBuf<float> zm_z; DevBuf<double> zm_logdet, hc_range; DevBuf<uint8_t> zm_valid, hc_keep;
+    // TICA (ti_obs_tica_moments, ti_obs_tica_fit, ti_obs_tica_transform): the packed values of a host call; the feature table, the
+    // partial tiles of one launch, the moments ahead of their validation; traj_off, the cumulative pair counts of one launch, the
+    // per-block and the first bad row; the staged moments of a host fit, C0t, L and the model ahead of its validation; the staged
+    // model and the output of a host transform.  The solves use the eig_* buffers above.
+    DevBuf<float> tica_x, tica_y; DevBuf<double> tica_f, tica_part, tica_sum, tica_cov, tica_c0t, tica_l, tica_mean, tica_ev, tica_comp;
+    DevBuf<long long> tica_off, tica_cum, tica_bad, tica_cnt; DevBuf<int32_t> tica_flag;
     // velocity loss (ti_painn_vloss, ti_adw_vloss): every stage computes into these and the outputs are copied from them at the end.
     // Staged inputs of a host call (x0, x1, z, conditioning); the times, the noise, the states [2][B][m] and the drift on them; the
     // times and conditioning of the evaluated batch (both halves, with the pad molecules of a packed layout); the uncentred states, the tile partials, (column sums [32], mean, first

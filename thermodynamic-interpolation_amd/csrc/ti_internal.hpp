@@ -645,6 +645,36 @@ hipError_t launch_eigw_gedmd_reduce(const double* gram, const double* kmat, doub
 hipError_t launch_eigw_gedmd_back(const double* L, const double* w2, const double* v2, const int* st2a, const int* st2b, const int* rank,
                                   int nev, int p, double* ev, double* vec, long long n_mat, hipStream_t st);
 
+// ---- TICA (obs_tica_kernels.hip; include/ti_hip.h ti_obs_tica_moments, ti_obs_tica_fit, ti_obs_tica_transform)
+constexpr long long TICA_SEG = 8192;        // pairs per (lag, segment) workgroup; fixed, so a lag's sums do not depend on the launch
+constexpr int TICA_MAX_LAGS = TI_TICA_MAX_LAGS;
+inline int tica_tiles(int T) { return T * (T + 1) + T * T + 2 * T; }      // 16 x 16 tiles of a segment's partial: Sxx, Syy, Sxy, sum X, sum Y
+inline long long tica_feature_blocks(long long n, int encode, int D) { return (n * (encode ? D / 2 : D) + 255) / 256; }
+struct TicaParams {                         // one contraction launch over n_lag lags
+    const double* f;                        // [n][D] feature table
+    const long long* traj_off;              // [n_traj + 1]
+    const long long* cum;                   // [n_lag][n_traj + 1] cumulative pair counts of the launch's lags
+    int n_traj, n_lag;
+    int lag[TICA_MAX_LAGS];
+    int seg_off[TICA_MAX_LAGS + 1];         // first workgroup of lag l; [n_lag]: the grid
+    double* part;                           // [seg_off[n_lag]][tica_tiles(T)][256] partial tiles
+};
+// f [n][D] and first_bad[0] = the smallest row with a non-finite value (LLONG_MAX: none); bad [tica_feature_blocks] is scratch
+hipError_t launch_tica_features(double* f, long long* bad, long long* first_bad, const float* x, long long stride, long long cstride, long long n,
+                                int K, int encode, int D, hipStream_t st);
+// one 256-thread group per (lag, segment); then sum [n_lag][2][d], cov [n_lag][3][d][d] = the partials added in segment order
+hipError_t launch_tica_moments(const TicaParams& g, int T, double* sum, double* cov, int d, hipStream_t st);
+// the model algebra around the two solves of launch_obs_eigh, one group per lag
+hipError_t launch_tica_fit_prep(const long long* count, const double* sum, const double* cov, int d, double* mean, double* a, double* c0t, int* flag,
+                                int n_lag, hipStream_t st);
+hipError_t launch_tica_fit_reduce(const double* w1, const double* v1, const int* status1, const double* c0t, double epsilon, int d, double* lmat,
+                                  double* rmat, int* rank, int n_lag, hipStream_t st);
+hipError_t launch_tica_fit_back(const double* lmat, const double* w2, const double* v2, const int* rank, int d, int dim, int scaling, double* ev,
+                                double* comp, int n_lag, hipStream_t st);
+// out [n_lag][B][dim] fp32
+hipError_t launch_tica_transform(float* out, const float* x, long long stride, long long cstride, long long B, int K, int encode, int d, int dim,
+                                 const double* mean, const double* comp, int n_lag, hipStream_t st);
+
 // ---- velocity loss (vloss_kernels.hip; include/ti_hip.h ti_painn_vloss, ti_adw_vloss and their _interp twins)
 constexpr int VLOSS_TILE = 1024;            // rows per tile of the batch-wide sums: fixed, so a sum does not depend on the launch
 inline long long vloss_tiles(long long n) { return (n + VLOSS_TILE - 1) / VLOSS_TILE; }

@@ -49,6 +49,15 @@ dataset built with ``use_latent_trajs``) adds to the npz, for the latent -> ambi
 -(E1 + log p(latent_z) + latent_dlogp + dlogp), ``ess_bg`` and, with ``bootstrap``, ``ess_bg_ci``.  As in the reference, log p(z0) is
 the full 3A-dimensional normal although the noise is centred, and the constant Jacobian of ``scale`` is dropped: both are constants of
 a run and cancel in normalised weights and the ESS.  One species per run; the key is checked before the rollout; sample_adw refuses it.
+sample_ambient only, next to the zmatrix key (whose topology it uses): ``"tica": {"traj": <.npy as generate_md writes it>, "n_frames":
+<frames per replica>, "temperature": T, "lags": [...], "dim": 2, "bins": 80, "range": [lo, hi], "epsilon": 1e-6}`` (traj, n_frames,
+temperature and lags required) fits TICA on the (cos, sin)-encoded torsions of that temperature's MD frames at every lag on the GPU
+(observables.tica_fit; the replicas are the trajectories; a torsion does not depend on the length unit, so no scale is needed; a NaN
+row -- a temperature that was not simulated -- is refused) and adds ``tica_lags``, ``tica_eigenvalues``, ``tica_timescales``,
+``tica_rank``, ``tica_mean``, ``tica_components`` and the marginals of the projections [n_lag, dim, bins] ``tica_hist_md`` (the fitted
+frames, unweighted), ``tica_hist_0`` (the x0, unweighted), ``tica_hist_1`` (the end state, weighted by the run's ``logw`` and masked by
+``zmat_keep`` where those exist) with ``tica_edges`` to the npz.  The key is checked before the rollout; sample_latent and sample_adw
+refuse it.
 Without the keys exactly the reference's files are written.
 
   score_checkpoints <- the held-out evaluation of mdqm9/train_ambient.py:153-157, which decides what weights are kept
@@ -85,6 +94,7 @@ import os
 
 import numpy as np
 
+from . import _lib
 from . import observables as _obs
 from .thermo import adw as _adw
 from .thermo import adw_nd as _adw_nd
@@ -125,6 +135,7 @@ def _observe_kw(config):
     o.pop("kinetics", None)
     o.pop("energy", None)
     o.pop("zmatrix", None)
+    o.pop("tica", None)
     if o.pop("bg", None) is not None and not o:
         return {}                              # the bg key alone: weights without collective variables, no observer
     if o.get("ref") is not None:
@@ -449,10 +460,90 @@ def _zmatrix_arrays(g, z0, z1, logw):
     return out
 
 
-def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=None, bg=None):
+TICA_KEYS = {"traj": None, "n_frames": None, "temperature": None, "lags": None, "dim": 2, "bins": 80, "range": (-2.5, 2.5), "epsilon": 1e-6}
+
+
+def _check_tica(config, driver="sample_ambient"):
+    """Before the rollout: observables["tica"] validated (sample_ambient) -> dict(frames [m, A, 3] float32 of the temperature,
+    traj_off, lags, dim, bins, range, epsilon), None without the key; refused by the other two drivers."""
+    o = getattr(config, "observables", None)
+    g = None if o is None else dict(o).get("tica")
+    if g is None:
+        return None
+    if driver != "sample_ambient":
+        raise ValueError(f"observables['tica'] is for sample_ambient (it fits on the torsions of an MD trajectory of the species); "
+                         f"{driver} does not take it")
+    from . import data as _data
+    required = [k for k, v in TICA_KEYS.items() if v is None]
+    if not isinstance(g, dict) or set(g) - set(TICA_KEYS) or any(k not in g for k in required):
+        raise ValueError(f"observables['tica'] must be a dict with the keys {required} and optionally "
+                         f"{[k for k in TICA_KEYS if k not in required]}, got {g!r}")
+    if dict(o).get("zmatrix") is None:
+        raise ValueError("observables['tica'] needs observables['zmatrix']: the torsions are those of its topology")
+    if dict(o).get("descriptors") is None:
+        raise ValueError("observables['tica'] adds to the observables npz, which needs observables['descriptors']")
+    nf, T = g["n_frames"], g["temperature"]
+    if isinstance(nf, bool) or not isinstance(nf, (int, np.integer)) or nf < 1:
+        raise ValueError(f"observables['tica']['n_frames'] must be an integer >= 1, got {nf!r}")
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or int(T) not in _data.TEMPERATURES:
+        raise ValueError(f"observables['tica']['temperature'] must be one of {list(_data.TEMPERATURES)}, got {T!r}")
+    lags = np.asarray(g["lags"])
+    if lags.ndim != 1 or lags.size < 1 or lags.dtype.kind not in "iu" or np.any(lags < 1) or np.any(lags >= int(nf)):
+        raise ValueError(f"observables['tica']['lags'] must be a list of integers in 1..n_frames - 1, got {g['lags']!r}")
+    dim, eps = g.get("dim", 2), g.get("epsilon", 1e-6)
+    if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or dim < 1:
+        raise ValueError(f"observables['tica']['dim'] must be an integer >= 1, got {dim!r}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not (np.isfinite(eps) and eps >= 0):
+        raise ValueError(f"observables['tica']['epsilon'] must be finite and >= 0, got {eps!r}")
+    try:
+        bins, lo, hi = _obs.check_bins(g.get("bins", 80), g.get("range", (-2.5, 2.5)))
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"observables['tica']: {e}") from None
+    try:
+        traj = np.load(os.fspath(g["traj"]), mmap_mode="r")
+    except (OSError, ValueError, TypeError) as e:
+        raise ValueError(f"observables['tica']['traj']: {e}") from None
+    if traj.ndim != 4 or traj.shape[0] != len(_data.TEMPERATURES) or traj.shape[3] != 3 or traj.shape[1] < 1 or traj.shape[1] % int(nf):
+        raise ValueError(f"observables['tica']['traj'] must hold [{len(_data.TEMPERATURES)}, n_replicas * n_frames, A, 3] with n_frames = {nf}, "
+                         f"got {traj.shape}")
+    frames = np.ascontiguousarray(traj[_data.TEMPERATURES.index(int(T))], np.float32)
+    if not np.isfinite(frames).all():
+        raise ValueError(f"observables['tica']: the frames at {T} K are not finite (a temperature that was not simulated is a NaN row)")
+    A = frames.shape[1]
+    if not 4 <= A <= _lib.TICA_MAX_K + 3:
+        raise ValueError(f"observables['tica'] takes molecules of 4..{_lib.TICA_MAX_K + 3} atoms (1..{_lib.TICA_MAX_K} torsions), got {A}")
+    if lags.size > _lib.TICA_MAX_LAGS:
+        raise ValueError(f"observables['tica']['lags'] takes at most {_lib.TICA_MAX_LAGS} lags, got {lags.size}")
+    if int(dim) > 2 * (A - 3):
+        raise ValueError(f"observables['tica']['dim'] must be <= {2 * (A - 3)} (two features per torsion), got {dim}")
+    return dict(frames=frames, traj_off=np.arange(0, frames.shape[0] + 1, int(nf), dtype=np.int64), lags=lags.astype(np.int32), dim=int(dim),
+                bins=bins, range=(lo, hi), epsilon=float(eps))
+
+
+def _tica_md_zmatrix(b, batch, t, zmat):
+    """z [m, A-1, 3] of the MD frames the tica key fits on, on the engine of the batch's species.  A torsion does not depend on the
+    length unit, so the frames are taken as they are."""
+    from .thermo import _molecule as _mol
+    sb = _mol.split_species_batch(batch, b.ATOM_KEY)
+    return _obs.zmatrix(b.engine_of(sb), t["frames"], zmat["zm"])
+
+
+def _tica_arrays(t, z_md, z0, z1, logw, keep):
+    """The arrays the tica key adds: the model fitted on the torsions of the MD frames and the marginals of the projected MD frames, x0
+    and end state (the latter weighted by logw [B] float32 and masked by keep [B] uint8 where they exist)"""
+    tor = lambda z: _obs.torsions(C.to_numpy(z))                    # the strided view z[:, 2:, 2]: read in place, no copy
+    m = _obs.tica_fit(tor(z_md), t["traj_off"], t["lags"], dim=t["dim"], epsilon=t["epsilon"])
+    kw = dict(bins=t["bins"], range=t["range"])
+    h_md, h_0, h_1 = (_obs.tica_marginals(m, tor(z), lw, kp, **kw) for z, lw, kp in ((z_md, None, None), (z0, None, None), (z1, logw, keep)))
+    return dict(tica_lags=m.lags, tica_eigenvalues=m.eigenvalues, tica_timescales=m.timescales, tica_rank=m.rank, tica_mean=m.mean,
+                tica_components=m.components, tica_hist_md=h_md.hist, tica_hist_0=h_0.hist, tica_hist_1=h_1.hist, tica_edges=h_md.edges)
+
+
+def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=None, bg=None, tica=None):
     """cvs: per-batch [rows, B_i, K]; dlogps: per-batch end-state [B_i] (empty without return_dlogp); gedmd: (x0, x1, beta0, beta1)
     of an adw run whose observables carry the gedmd key; energy: (E0, E1) [B] of a run with the energy key; bg: (latent_z [B, A, 3],
-    latent_dlogp [B]) of a sample_ambient run with the bg key"""
+    latent_dlogp [B]) of a sample_ambient run with the bg key; tica: (settings, z [m, A-1, 3] of the MD frames) of a sample_ambient run
+    with the tica key"""
     cv = np.concatenate([C.to_numpy(c) for c in cvs], axis=1).astype(np.float32)
     dl = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in dlogps]) if dlogps else None
     hist, edges, ess = _obs.end_state_summary(np.ascontiguousarray(cv[-1]), dl, bins=int(dict(config.observables).get("bins", 32)))
@@ -478,6 +569,8 @@ def _write_observables(config, path, cvs, dlogps, gedmd=None, energy=None, zmat=
             extra.update(_bg_arrays(config, bg[0], energy[1], bg[1], dl))
     if zmat is not None:                       # (settings, z0, z1) of a run with the zmatrix key
         extra.update(_zmatrix_arrays(zmat[0], zmat[1], zmat[2], extra.get("logw")))
+        if tica is not None:
+            extra.update(_tica_arrays(tica[0], tica[1], zmat[1], zmat[2], extra.get("logw"), extra.get("zmat_keep")))
     np.savez(path, cv=cv, hist=hist, edges=edges, ess=np.float64(ess), **extra)
 
 
@@ -485,6 +578,9 @@ def sample_ambient(config, b, dataset):
     _check_kinetics(config)
     energy, E0s, E1s = _check_energy(config), [], []
     zmat, z0s, z1s = _check_zmatrix(config), [], []
+    tica, z_md = _check_tica(config), None
+    if tica is not None and tica["frames"].shape[1] != zmat["zm"].A:
+        raise ValueError(f"observables['tica']['traj'] holds {tica['frames'].shape[1]} atoms, the zmatrix key describes {zmat['zm'].A}")
     bg = _check_bg(config, "sample_ambient", dataset)
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _amb.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
@@ -511,6 +607,8 @@ def sample_ambient(config, b, dataset):
         if zmat is not None:
             z0, z1 = _batch_zmatrices(b, batch, sample, zmat)
             z0s.append(z0); z1s.append(z1)
+            if tica is not None and z_md is None:
+                z_md = _tica_md_zmatrix(b, batch, tica, zmat)
     name = config.data_save_name
     if energy is not None:
         energy = (np.concatenate(E0s), np.concatenate(E1s))
@@ -519,7 +617,8 @@ def sample_ambient(config, b, dataset):
     if cvs:
         _write_observables(config, os.path.join(config.data_save_path, f"observables_{name}.npz"), cvs, dlogps, energy=energy,
                            zmat=None if zmat is None else (zmat, np.concatenate(z0s), np.concatenate(z1s)),
-                           bg=None if bg is None else (np.concatenate(latent_noises, axis=0), np.concatenate(latent_dlogps, axis=0)))
+                           bg=None if bg is None else (np.concatenate(latent_noises, axis=0), np.concatenate(latent_dlogps, axis=0)),
+                           tica=None if tica is None else (tica, z_md))
     np.save(os.path.join(config.data_save_path, f"latent_noises_{name}.npy"), np.concatenate(latent_noises, axis=0))
     np.save(os.path.join(config.data_save_path, f"latent_dlogps_{name}.npy"), np.concatenate(latent_dlogps, axis=0))
     np.save(os.path.join(config.data_save_path, f"samples_{name}.npy"), np.concatenate(samples, axis=0))
@@ -532,6 +631,7 @@ def sample_latent(config, b, dataset):
     _check_kinetics(config)
     _check_energy(config, "sample_latent")
     _check_zmatrix(config, "sample_latent")
+    _check_tica(config, "sample_latent")
     bg, E1s, z0s = _check_bg(config, "sample_latent"), [], []
     os.makedirs(config.data_save_path, exist_ok=True)
     integrator = _lat.MoleculeIntegrator(b=b, method=getattr(config, "method", "dopri5"), rtol=config.rtol, atol=config.atol,
@@ -575,6 +675,7 @@ def sample_adw(config, b, x0s_batches):
     _check_kinetics(config, molecules=False)
     _check_energy(config, "sample_adw")
     _check_zmatrix(config, "sample_adw")
+    _check_tica(config, "sample_adw")
     _check_bg(config, "sample_adw")
     integrator = _adw.StandardIntegrator(b=b, method=getattr(config, "method", None) or config.solver_type, rtol=config.rtol,
                                          atol=config.atol, n_step=config.n_step, return_dlogp=bool(config.return_dlogp),

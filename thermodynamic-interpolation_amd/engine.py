@@ -436,6 +436,107 @@ class _Engine:
                                                hist.ctypes.data_as(dptr), tails.ctypes.data_as(dptr), _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
         return hist, tails
 
+    def _tica_values(self, values, what="values"):
+        """(pointer, keepalive, is_device, n, K, stride, cstride) of values [n, K] float32 read in place through its strides: numpy,
+        or a CUDA tensor -- a view such as z[:, 2:, 2] of a Z-matrix array is fine, its strides must be positive."""
+        if len(values.shape) != 2 or int(values.shape[0]) < 1 or not 1 <= int(values.shape[1]) <= _lib.TICA_MAX_K:
+            raise ValueError(f"{what} must be [n >= 1, 1 <= K <= {_lib.TICA_MAX_K}], got {tuple(values.shape)}")
+        n, K = int(values.shape[0]), int(values.shape[1])
+        if hasattr(values, "data_ptr") and values.is_cuda:
+            if str(values.dtype) != "torch.float32":
+                raise TypeError(f"{what} must be float32, got {values.dtype}")
+            if (values.device.index or 0) != self.device:
+                raise ValueError(f"{what} live on {values.device} but this engine was created on device {self.device}")
+            cs = int(values.stride(1)) if K > 1 else 1
+            s = int(values.stride(0)) if n > 1 else (K - 1) * cs + 1
+            import torch
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)
+            ptr, keep, dev = C.c_void_p(values.data_ptr()), values, True
+        else:
+            host = np.asarray(values.detach().cpu().numpy() if hasattr(values, "data_ptr") else values)
+            if host.dtype != np.float32:
+                host = np.ascontiguousarray(host, np.float32)
+            cs = host.strides[1] // 4 if K > 1 else 1
+            s = host.strides[0] // 4 if n > 1 else (K - 1) * cs + 1
+            ptr, keep, dev = C.c_void_p(host.ctypes.data), host, False
+        if cs < 1 or s < (K - 1) * cs + 1:
+            raise ValueError(f"{what} must have positive strides with rows that do not overlap")
+        return ptr, keep, dev, n, K, s, cs
+
+    def _typed_in(self, a, shape, dtype, dev, what):
+        """(pointer, keepalive) of an input of the given shape and dtype name living where the call lives"""
+        if dev:
+            if not (hasattr(a, "data_ptr") and a.is_cuda and str(a.dtype) == "torch." + dtype and a.is_contiguous()):
+                raise TypeError(f"{what} must be a contiguous CUDA {dtype} tensor when the call's buffers live on the GPU")
+            if (a.device.index or 0) != self.device:
+                raise ValueError(f"{what} lives on {a.device} but this engine was created on device {self.device}")
+            keep, ptr = a, C.c_void_p(a.data_ptr())
+        else:
+            keep = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "data_ptr") else a, getattr(np, dtype))
+            ptr = C.c_void_p(keep.ctypes.data)
+        if tuple(keep.shape) != tuple(shape):
+            raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(keep.shape)}")
+        return ptr, keep
+
+    def tica_moments(self, values, traj_offsets, lags, encode=True):
+        """ti_obs_tica_moments: (count [n_lag] int64, sum [n_lag, 2, d] float64, cov [n_lag, 3, d, d] float64) of the lagged pairs of
+        values [n, K] float32 (numpy or a CUDA tensor, read in place through its strides) over the trajectories traj_offsets
+        [n_traj + 1] at the lags [n_lag] (both host).  encode: d = 2 K, (cos, sin) of every value; else d = K.  cov holds (Sxx, Syy, Sxy).
+        Lives where values lives."""
+        vp, keep, dev, n, K, s, cs = self._tica_values(values)
+        off = np.ascontiguousarray(traj_offsets, np.int64).reshape(-1)
+        lg = np.ascontiguousarray(lags, np.int32).reshape(-1)
+        if off.size < 2:
+            raise ValueError("traj_offsets must have n_traj + 1 >= 2 entries")
+        if not 1 <= lg.size <= _lib.TICA_MAX_LAGS:
+            raise ValueError(f"lags must have 1..{_lib.TICA_MAX_LAGS} entries, got {lg.size}")
+        d, L = (2 * K if encode else K), int(lg.size)
+        like = keep if dev else None
+        count, cp = self._eig_out(like, (L,), "int64")
+        sm, sp = self._eig_out(like, (L, 2, d), "float64")
+        cov, vp2 = self._eig_out(like, (L, 3, d, d), "float64")
+        _lib.check(_lib.lib().ti_obs_tica_moments(self.h, vp, s, cs, n, K, int(bool(encode)), off.ctypes.data_as(C.POINTER(C.c_int64)), off.size - 1,
+                                                  _lib.iptr(lg), L, cp, sp, vp2, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return count, sm, cov
+
+    def tica_fit(self, count, sum, cov, dim=2, epsilon=1e-6, scaling=1):
+        """ti_obs_tica_fit: (mean [n_lag, d], eigenvalues [n_lag, dim], components [n_lag, d, dim] float64, rank [n_lag] int32) of the
+        moments ``tica_moments`` returns (numpy, or CUDA tensors: they stay on the GPU).  scaling 1: kinetic map, 0: none."""
+        dev = hasattr(cov, "data_ptr") and cov.is_cuda
+        if len(cov.shape) != 4 or int(cov.shape[1]) != 3 or int(cov.shape[2]) != int(cov.shape[3]):
+            raise ValueError(f"cov must be [n_lag, 3, d, d], got {tuple(cov.shape)}")
+        L, d, dim = int(cov.shape[0]), int(cov.shape[2]), int(dim)
+        if dev:
+            import torch
+            self.wait_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        cp, k0 = self._typed_in(count, (L,), "int64", dev, "count")
+        sp, k1 = self._typed_in(sum, (L, 2, d), "float64", dev, "sum")
+        vp, k2 = self._typed_in(cov, (L, 3, d, d), "float64", dev, "cov")
+        like = k2 if dev else None
+        mean, mp = self._eig_out(like, (L, d), "float64")
+        ev, ep = self._eig_out(like, (L, max(dim, 0)), "float64")
+        comp, op = self._eig_out(like, (L, d, max(dim, 0)), "float64")
+        rank, rp = self._eig_out(like, (L,), "int32")
+        desc = _lib.TicaDesc(dim, int(scaling), 0, float(epsilon))
+        _lib.check(_lib.lib().ti_obs_tica_fit(self.h, cp, sp, vp, L, d, C.byref(desc), mp, ep, op, rp, _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return mean, ev, comp, rank
+
+    def tica_transform(self, values, mean, comp, encode=True):
+        """ti_obs_tica_transform: out [n_lag, B, dim] float32 = the projections of values [B, K] (as in ``tica_moments``) onto the
+        components comp [n_lag, d, dim] about mean [n_lag, d] (float64, living where values lives)."""
+        vp, keep, dev, B, K, s, cs = self._tica_values(values)
+        if len(comp.shape) != 3:
+            raise ValueError(f"comp must be [n_lag, d, dim], got {tuple(comp.shape)}")
+        L, d, dim = (int(v) for v in comp.shape)
+        if d != (2 * K if encode else K):
+            raise ValueError(f"comp has d = {d} features but values has K = {K} columns (encode = {bool(encode)})")
+        mp, k0 = self._typed_in(mean, (L, d), "float64", dev, "mean")
+        cp, k1 = self._typed_in(comp, (L, d, dim), "float64", dev, "comp")
+        out, op = self._eig_out(keep if dev else None, (L, B, dim), "float32")
+        _lib.check(_lib.lib().ti_obs_tica_transform(self.h, vp, s, cs, B, K, int(bool(encode)), mp, cp, L, d, dim, op,
+                                                    _lib.MEM_DEVICE if dev else _lib.MEM_HOST))
+        return out
+
     def set_observer(self, descriptors, ref=None, select=None, every=1, out=None):
         """Attach an observer: every rollout that follows also writes the CVs of the grid points i % every == 0 and of the last one
         to out [rows, B, K] (float32 numpy array or CUDA tensor, rows = ti_rollout_rows(n_step, every); kept alive here).

@@ -26,6 +26,11 @@ Z-matrix coordinates (ti_obs_zmat, ti_obs_zmat_xyz, ti_obs_hist_cols; zmatrix.py
 the reference's construct_z_matrix_batch / deconstruct_z_matrix_batch with its log-determinant and validity screen,
 ``zmatrix_marginals`` the weighted marginals of all 3A - 6 internal coordinates in one call, ``iqr_keep`` its IQR keep mask.
 
+TICA (ti_obs_tica_moments, ti_obs_tica_fit, ti_obs_tica_transform): ``tica_fit`` is the reference's
+deeptime.decomposition.TICA(lagtime, dim) on the (cos, sin) encoding of torsions (mdqm9/plots/10506_main.ipynb, cell 3) at many lags
+in one call over ragged trajectories, ``tica_transform`` the projection, ``tica_marginals`` the weighted histograms of the projected
+samples; the estimator is restated in include/ti_hip.h and parity with deeptime's own numbers is not pinned.
+
 Beyond that p x p algebra the only arithmetic in this module is turning a histogram into a free-energy profile, forming phi from
 its terms, and the difference of two bootstrap runs in ``free_energy_bg``.
 """
@@ -548,3 +553,125 @@ def end_state_summary(cv, dlogp, bins=32, engine=None):
         hists[k], _ = weighted_histogram(cv[:, int(k)], logw, bins, (lo, float(hi)), engine=engine)
         edges[k] = lo + (float(hi) - lo) * np.arange(bins + 1) / bins
     return hists, edges, ess
+
+
+# ---- TICA (ti_obs_tica_moments, ti_obs_tica_fit, ti_obs_tica_transform)
+TicaModel = collections.namedtuple("TicaModel", "lags mean eigenvalues components rank timescales encode")
+TicaModel.__doc__ = """lags [n_lag] int32; mean [n_lag, d], eigenvalues [n_lag, dim], components [n_lag, d, dim] float64 (where the fitted
+values live); rank [n_lag] int32; timescales [n_lag, dim] float64 (numpy): -lag / ln(lambda) in frames for 0 < lambda < 1, else NaN;
+encode: "torsion" (d = 2 K, (cos, sin) of every value) or "none" (d = K)."""
+
+_TICA_ENCODINGS = {"torsion": 1, "none": 0}
+
+
+def _check_tica_args(values, traj_offsets, lags, encode):
+    """(traj_offsets int64, lags int32, encode flag) of a TICA request, checked before any device call"""
+    if encode not in _TICA_ENCODINGS:
+        raise ValueError(f"encode must be one of {sorted(_TICA_ENCODINGS)}, got {encode!r}")
+    if len(values.shape) != 2 or int(values.shape[0]) < 1:
+        raise ValueError(f"values must be [n, K], got {tuple(values.shape)}")
+    n, K = int(values.shape[0]), int(values.shape[1])
+    if not 1 <= K <= _lib.TICA_MAX_K:
+        raise ValueError(f"values must have 1..{_lib.TICA_MAX_K} columns, got {K}")
+    if K * (2 if _TICA_ENCODINGS[encode] else 1) > _lib.EIGH_MAX_N:
+        raise ValueError(f"at most {_lib.EIGH_MAX_N} features: K = {K} with encode = {encode!r} gives {2 * K}")
+    off = np.asarray(traj_offsets)
+    if off.ndim != 1 or off.size < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError("traj_offsets must be a 1-D integer array of n_traj + 1 >= 2 entries")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != n or np.any(np.diff(off) <= 0):
+        raise ValueError(f"traj_offsets must ascend strictly from 0 to n = {n}")
+    lg = np.asarray(lags)
+    if lg.ndim != 1 or not 1 <= lg.size <= _lib.TICA_MAX_LAGS or not np.issubdtype(lg.dtype, np.integer):
+        raise ValueError(f"lags must be a 1-D integer array of 1..{_lib.TICA_MAX_LAGS} entries")
+    if np.any(lg < 1) or np.any(lg > np.iinfo(np.int32).max):
+        raise ValueError("every lag must be >= 1")
+    lens = np.diff(off)
+    for tau in lg:
+        pairs = int(np.maximum(lens - int(tau), 0).sum())
+        if pairs < 2:
+            raise ValueError(f"lag {int(tau)} has {pairs} pairs: at least 2 are needed")
+    return off, lg.astype(np.int32), _TICA_ENCODINGS[encode]
+
+
+def tica_moments(values, traj_offsets, lags, encode="torsion", engine=None):
+    """(count [n_lag] int64, sum [n_lag, 2, d], cov [n_lag, 3, d, d] float64): the lagged moments (sx, sy) and (Sxx, Syy, Sxy) of
+    values [n, K] float32 -- numpy or a CUDA tensor, read through its strides: torsions z[:, 2:, 2] of a Z-matrix array are fine --
+    over the trajectories traj_offsets [n_traj + 1] (frames traj_offsets[t] .. traj_offsets[t + 1] - 1 in time order: the
+    replica-major layout generate_md writes) at the lags.  Lives where values lives."""
+    off, lg, enc = _check_tica_args(values, traj_offsets, lags, encode)
+    return (engine or _service_engine(_device_of(values))).tica_moments(values, off, lg, enc)
+
+
+def _check_tica_model_args(dim, epsilon, scaling, d):
+    if isinstance(dim, bool) or int(dim) != dim or not 1 <= int(dim) <= d:
+        raise ValueError(f"dim must be an integer in 1..{d}, got {dim!r}")
+    if not (np.isfinite(epsilon) and epsilon >= 0):
+        raise ValueError(f"epsilon must be finite and >= 0, got {epsilon!r}")
+    if scaling not in _lib.TICA_SCALINGS:
+        raise ValueError(f"scaling must be one of {sorted(_lib.TICA_SCALINGS)}, got {scaling!r}")
+
+
+def tica_timescales(lags, eigenvalues):
+    """[n_lag, dim] float64: -lag / ln(lambda) in frames where 0 < lambda < 1, NaN elsewhere"""
+    ev = np.asarray(eigenvalues.detach().cpu().numpy() if hasattr(eigenvalues, "data_ptr") else eigenvalues, np.float64)
+    out = np.full(ev.shape, np.nan)
+    ok = (ev > 0) & (ev < 1)
+    tau = np.broadcast_to(np.asarray(lags, np.float64)[:, None], ev.shape)
+    out[ok] = -tau[ok] / np.log(ev[ok])
+    return out
+
+
+def tica_fit(values, traj_offsets, lags, dim=2, epsilon=1e-6, scaling="kinetic_map", encode="torsion", engine=None):
+    """TICA of values [n, K] at every lag (deeptime's documented reversible estimator, restated in include/ti_hip.h; parity with
+    deeptime's own numbers is not pinned): a ``TicaModel`` living where values lives.  The moments never leave the device: host
+    values are uploaded once (their K columns only), both stages run on device memory, and only the model comes back -- the bits a
+    CUDA tensor of the same values gives."""
+    off, lg, enc = _check_tica_args(values, traj_offsets, lags, encode)
+    _check_tica_model_args(dim, epsilon, scaling, int(values.shape[1]) * (2 if enc else 1))
+    eng = engine or _service_engine(_device_of(values))
+    dev = hasattr(values, "data_ptr") and values.is_cuda
+    if not dev:
+        import torch
+        host = values.detach().numpy() if hasattr(values, "data_ptr") else values
+        values = torch.from_numpy(np.ascontiguousarray(host, np.float32)).to(f"cuda:{eng.device}")
+    count, sm, cov = eng.tica_moments(values, off, lg, enc)
+    out = eng.tica_fit(count, sm, cov, int(dim), float(epsilon), _lib.TICA_SCALINGS[scaling])
+    mean, ev, comp, rank = out if dev else (a.cpu().numpy() for a in out)
+    return TicaModel(lg, mean, ev, comp, rank, tica_timescales(lg, ev), encode)
+
+
+def tica_transform(model, values, engine=None):
+    """[n_lag, B, dim] float32: values [B, K] projected onto the model's components at every lag; lives where values lives."""
+    if len(values.shape) != 2 or int(values.shape[0]) < 1:
+        raise ValueError(f"values must be [B, K], got {tuple(values.shape)}")
+    d = int(model.components.shape[1])
+    if int(values.shape[1]) * (2 if _TICA_ENCODINGS[model.encode] else 1) != d:
+        raise ValueError(f"the model has {d} features (encode = {model.encode!r}) but values has {int(values.shape[1])} columns")
+    dev = hasattr(values, "data_ptr") and values.is_cuda
+    mean, comp = model.mean, model.components
+    if dev != (hasattr(comp, "data_ptr") and comp.is_cuda):
+        if dev:
+            import torch
+            mean, comp = (torch.as_tensor(np.asarray(a), device=values.device) for a in (mean, comp))
+        else:
+            mean, comp = mean.detach().cpu().numpy(), comp.detach().cpu().numpy()
+    return (engine or _service_engine(_device_of(values))).tica_transform(values, mean, comp, _TICA_ENCODINGS[model.encode])
+
+
+TicaMarginals = collections.namedtuple("TicaMarginals", "hist tails edges")
+TicaMarginals.__doc__ = """hist [n_lag, dim, bins], tails [n_lag, dim, 3] (below, at or above, non-finite) float64; edges [bins + 1]"""
+
+
+def tica_marginals(model, values, logw=None, keep=None, bins=80, range=(-2.5, 2.5), engine=None):
+    """The weighted marginal histograms of the projections of values onto every component at every lag (the panels of the
+    reference's mdqm9/plots/10506_main.ipynb, cell 3): ti_obs_hist_cols, one call per lag over that lag's dim columns.  logw and keep
+    as in ``zmatrix_marginals``."""
+    bins, lo, hi = check_bins(bins, range)
+    y = tica_transform(model, values, engine=engine)
+    eng = engine or _service_engine(_device_of(values))
+    L, dim = int(y.shape[0]), int(y.shape[2])
+    hist, tails = np.empty((L, dim, bins)), np.empty((L, dim, 3))
+    for l in np.arange(L):
+        hist[l], tails[l] = eng.hist_cols(y[int(l)], logw, keep, bins, np.full(dim, lo), np.full(dim, hi))
+    return TicaMarginals(hist, tails, np.linspace(lo, hi, bins + 1))
