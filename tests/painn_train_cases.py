@@ -155,6 +155,73 @@ FLOAT32_DECIDES = (2, 4)
 MATRIX_IDS = ["-".join(str(v) for v in cell[:10]) for cell in MATRIX]
 
 
+# The edge cells: the shapes the study trains (F = 128 / 256, L = 5, A = 18), the caps, and the row counts at which the trainer's
+# tiling changes path.  Same layout as MATRIX, the same rule for the seed.  With R = halves x B molecules a call (halves = 2 for the
+# standard loss, 1 for the one-sided), a cell has R A node rows, 3 R A vector rows and R E edge rows:
+#   0  F = 256 at all: LayerNorm's fourth entry a lane, products with K = 1024 / 512 and N = 1280 / 768
+#   1  the study's ambient model: L = 5 (`ge` chained through four layers), E = 306
+#   2  F = 256 through five layers on the latent variant, R = 3
+#   3  the atom cap: E = 992, in-degree 31, repeated atom ids
+#   4  exact slice multiples: 2048 node rows, 6144 vector rows, 63 488 = 31 x 2048 edge rows; R = 64 = 4 x 16 table rounds
+#   5  one row over: 2049 node rows, 6147 vector rows; 683 molecules through the table accumulators
+#   6  R = 1, two node rows: one partial 16-row product tile, one table accumulator in use
+#   7, 8  R = 16 and 17: the end of the first accumulator round and one molecule into the second
+EDGE_MATRIX = [
+    (0, 256, 1, 3, 2, "full", "standard", "sin2", 1.0, "molecule", False, 8),
+    (0, 128, 5, 18, 2, "full", "standard", "sin2", 1.0, "batch", False, 9),
+    (1, 256, 5, 18, 3, "full", "one_sided", "brownian", 1.0, "none", False, 7),
+    (2, 64, 2, 32, 2, "full", "standard", "sig_sum", 4.0, "batch", True, 1),
+    (0, 32, 1, 32, 32, "full", "standard", "brownian", 0.9, "molecule", False, 0),
+    (1, 32, 1, 3, 683, "sparse", "one_sided", "brownian", 1.0, "batch", False, 0),
+    (1, 32, 1, 2, 1, "full", "one_sided", "brownian", 1.0, "none", False, 0),
+    (2, 32, 1, 3, 16, "sparse", "one_sided", "brownian", 1.0, "molecule", True, 0),
+    (2, 32, 1, 3, 17, "sparse", "one_sided", "brownian", 1.0, "batch", False, 0),
+]
+EDGE_IDS = ["-".join(str(v) for v in cell[:10]) for cell in EDGE_MATRIX]
+EDGE_EXACT, EDGE_ONE_OVER = 4, 5
+# Edge cells in which no seed of ten (0..9) keeps every tensor's float32 distance below 1e-5 / 3; the kept seed is the one with the
+# smallest worst distance.  Both are F = 256 cells with few rows (12 and 54 node rows; the float32 products run over K = 512 and
+# 1024), and in both the distances lie densely around a third.  The float32 restatement does not give the same bits on every
+# host: between an Intel Xeon and an AMD EPYC 9575F the distances of these tensors differ by up to 11 %.  So a cell's record is
+# {tensor: the larger of the two hosts' distances} for every tensor that came within EDGE_HOST_SPREAD of a third on either host
+# (above a third: 5 and 7 tensors of cell 0, 13 and 12 of cell 2).  For a tensor above a third 3 x its float32 distance is the bar.
+# tests/test_painn_train_host.py asserts that nothing outside the record exceeds a third, that the record holds nothing far below
+# it, and that every tensor stays below 1e-5.
+EDGE_HOST_SPREAD = 1.25
+EDGE_FLOAT32_DECIDES = {
+    0: {
+        "net.8.layers.1.v.linear.weight": 7.111e-06, "net.8.layers.0.w.mlp.0.weight": 3.865e-06,
+        "net.8.layers.0.w.mlp.3.weight": 3.621e-06, "net.8.layers.0.w.mlp.1.weight": 3.566e-06,
+        "net.8.layers.0.w.mlp.4.weight": 3.454e-06, "net.2.embedding.weight": 3.376e-06, "net.8.layers.0.phi.mlp.1.weight": 3.342e-06,
+        "net.8.layers.0.phi.mlp.0.weight": 3.321e-06, "net.8.layers.0.w.mlp.6.weight": 3.228e-06,
+        "net.8.layers.1.u.linear.weight": 3.196e-06, "net.8.layers.0.phi.mlp.3.weight": 3.151e-06,
+        "net.8.layers.0.w.mlp.0.bias": 3.100e-06, "net.8.layers.0.phi.mlp.6.weight": 3.020e-06,
+        "net.8.layers.0.phi.mlp.1.bias": 2.998e-06, "net.8.layers.0.phi.mlp.0.bias": 2.988e-06,
+        "net.8.layers.0.w.mlp.1.bias": 2.986e-06, "net.8.layers.0.phi.mlp.4.weight": 2.959e-06,
+        "net.8.layers.0.w.mlp.3.bias": 2.905e-06, "net.8.layers.2.V.linear.weight": 2.854e-06,
+        "net.8.layers.0.phi.mlp.3.bias": 2.799e-06, "net.3.embedding.weight": 2.786e-06, "net.8.layers.0.phi.mlp.6.bias": 2.762e-06,
+        "net.8.layers.0.phi.mlp.4.bias": 2.742e-06, "net.8.layers.0.w.mlp.4.bias": 2.705e-06},
+    2: {
+        "net.7.layers.7.v.linear.weight": 5.089e-06, "net.3.embedding.weight": 4.926e-06, "net.7.layers.1.v.linear.weight": 4.727e-06,
+        "net.7.layers.8.w.mlp.0.weight": 4.648e-06, "net.7.layers.0.w.mlp.0.weight": 4.619e-06,
+        "net.7.layers.6.w.mlp.0.weight": 4.616e-06, "net.7.layers.9.v.linear.weight": 4.465e-06,
+        "net.7.layers.5.v.linear.weight": 4.398e-06, "net.7.layers.4.w.mlp.0.weight": 4.092e-06,
+        "net.7.layers.2.w.mlp.0.weight": 4.071e-06, "net.7.layers.3.v.linear.weight": 3.973e-06, "net.6.mlp.mlp.0.weight": 3.617e-06,
+        "net.6.mlp.mlp.3.weight": 3.421e-06, "net.7.layers.0.phi.mlp.1.weight": 3.158e-06, "net.6.mlp.mlp.6.weight": 2.886e-06,
+        "net.7.layers.0.phi.mlp.0.weight": 2.871e-06, "net.6.mlp.mlp.1.weight": 2.798e-06},
+}
+
+
+def halves(kind):
+    return 2 if kind == "standard" else 1
+
+
+def row_counts(c):
+    """(node rows, vector rows, edge rows) of a call on case c"""
+    R = halves(c["lk"]["kind"]) * c["B"]
+    return R * c["A"], 3 * R * c["A"], R * int(c["model"]["src"].size)
+
+
 def matrix_case(cell):
     variant, F, L, A, B, tpl, kind, gamma, a, center, rep, seed = cell
     return make_case(variant, F, L, A, B, tpl=tpl, kind=kind, gamma=gamma, a=a, center=center, seed=seed, repeat_ids=rep)

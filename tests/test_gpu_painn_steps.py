@@ -19,20 +19,21 @@ F, B, N0, N1, STEPS = 32, 5, 23, 31, 7
 SEED, OFF, DRAW = 77, (1 << 32) + 9, 40            # ids above 2^32: the high counter word of the draws
 
 
-def _pool(variant, kind, A, L, seed=0, center="batch"):
+def _pool(variant, kind, A, L, seed=0, center="batch", F=F, B=B, N0=N0, N1=N1):
     """A model and two resident sets of 23 and 31 molecules with their temperatures, and [7, 5] indices that cross both sets
-    unevenly: a row that holds one molecule twice, and molecules that come back in a later step"""
+    unevenly: a row that holds one molecule twice, and molecules that come back in a later step (other F, B and set sizes on request)"""
     c = pc.make_case(variant, F, L, A, N1, tpl="sparse", kind=kind, gamma="sin2", center=center, seed=seed)
     rs = np.random.RandomState(50 + seed)
     c["set0"], c["set1"] = np.ascontiguousarray(c["x0"][:N0]), np.ascontiguousarray(c["x1"])
     c["temp0"] = (300.0 + 100.0 * (np.arange(N0) % 8)).astype(np.float32)
     c["temp1"] = (300.0 + 100.0 * (np.arange(N1) % 6)).astype(np.float32)
     i0 = np.stack([rs.permutation(N0)[:B] for _ in range(STEPS)]).astype(np.int64)
-    i1 = np.stack([rs.permutation(N1 - 1)[:B] for _ in range(STEPS)]).astype(np.int64)      # molecule 30 is kept for the NaN test
+    i1 = np.stack([rs.permutation(N1 - 1)[:B] for _ in range(STEPS)]).astype(np.int64)      # the last molecule is kept for the NaN test
     i0[1, 3] = i0[1, 0]; i1[2, 4] = i1[2, 1]                                                # a molecule twice in one minibatch
     i0[5] = i0[0][::-1]; i1[6, :3] = i1[0, :3]                                              # molecules reused by a later step
     c["idx0"], c["idx1"] = i0, i1
     c["ncond"] = {0: 2, 1: 1, 2: 0}[variant]
+    c["batch"] = B
     c["kw"] = dict(kind=kind, gamma="sin2", a=1.0, center=center, t_distr="beta_half", seed=SEED, traj_offset=OFF)
     return c
 
@@ -67,14 +68,22 @@ def _same_state(a, b):
 
 
 CASES = [(0, "standard", 7, 2), (0, "one_sided", 3, 1), (1, "standard", 3, 1), (1, "one_sided", 7, 2), (2, "standard", 7, 1), (2, "one_sided", 3, 2)]
+# the trainer's edges (tests/painn_train_cases.py EDGE_MATRIX) through this entry point: F = 256, and a minibatch of 683 molecules of
+# three atoms from sets of 690 and 700, whose 2049 node rows and 6147 vector rows lie one row and one triple over a slice
+EDGE_CASES = [((0, "standard", 3, 1), dict(F=256), "F256"), ((1, "one_sided", 3, 1), dict(B=683, N0=690, N1=700), "B683")]
 
 
 # ------------------------------------------------------------------------------------------------ steps equal the loop
-@pytest.mark.parametrize("variant,kind,A,L", CASES, ids=[f"v{v}-{k}-A{a}-L{l}" for v, k, a, l in CASES])
-def test_steps_equal_the_loop_of_single_steps(variant, kind, A, L):
+@pytest.mark.parametrize("variant,kind,A,L,shape", [case + ({},) for case in CASES] + [case + (shape,) for case, shape, _ in EDGE_CASES],
+                         ids=[f"v{v}-{k}-A{a}-L{l}" for v, k, a, l in CASES] + [f"v{v}-{k}-A{a}-L{l}-{tag}" for (v, k, a, l), _, tag in EDGE_CASES])
+def test_steps_equal_the_loop_of_single_steps(variant, kind, A, L, shape):
     """One call on host sets, one on device sets and indices, and seven ti_painn_train_step calls on the host-gathered rows: the same
     master weights, moments, counters and losses, bit for bit.  Then n_steps = 1 without indices against a step on rows 0..B-1."""
-    c = _pool(variant, kind, A, L, seed=variant + (0 if kind == "standard" else 3), center="molecule" if variant == 1 else "batch")
+    c = _pool(variant, kind, A, L, seed=variant + (0 if kind == "standard" else 3), center="molecule" if variant == 1 else "batch", **shape)
+    B = c["batch"]
+    if "B" in shape:
+        S = pkg()._lib.PAINN_TRAIN_SLICE
+        assert kind == "one_sided" and B * A == S + 1 and 3 * B * A == 3 * S + 3          # node and vector rows one over a slice
     t0, t1 = _temps(c)
     host, loop, dev = (pc.make_trainer(c, lr=1e-3) for _ in range(3))
     lh, sh = host.steps(c["set0"], c["set1"], t0, t1, c["idx0"], c["idx1"], draw=DRAW, **c["kw"])

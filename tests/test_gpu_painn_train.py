@@ -86,8 +86,8 @@ def test_gradients_against_the_reference(name, case):
 
 
 # ------------------------------------------------------------------------------------------------ a shape matrix against the restatement
-@pytest.mark.parametrize("cell", pc.MATRIX, ids=pc.MATRIX_IDS)
-def test_gradient_matrix(cell):
+def _check_cell(cell):
+    """One cell of a shape matrix against the restatement: every tensor under its bar, the zero pattern, gnorm, the loss -> the case"""
     c = pc.matrix_case(cell)
     rows, mean, g64, g32 = _reference(cell, c)
     r = pc.make_trainer(c).grad(c["x0"], c["x1"], c["cond"], **pc.call_kw(c))
@@ -95,10 +95,43 @@ def test_gradient_matrix(cell):
     bars = {k: bar for k, _, bar in pc.tensor_errors(g32, g64, g32) if bar > 0.0}
     _check_grad(c, r, g64, bars)
     _check_loss(c, r, rows, mean)
+    return c
+
+
+@pytest.mark.parametrize("cell", pc.MATRIX, ids=pc.MATRIX_IDS)
+def test_gradient_matrix(cell):
+    c = _check_cell(cell)
     if cell[4] == 37 and cell[5] == "full":
         ti = pkg()
         n_rows = 2 * c["B"] * c["model"]["src"].size
         assert n_rows > 2 * ti._lib.PAINN_TRAIN_SLICE and n_rows % ti._lib.PAINN_TRAIN_SLICE      # three slices, the last one ragged
+
+
+def _slice_premise(which, c):
+    """The row counts the two slice cells are there for, stated against the library's constant: should the slice change, the cell
+    says that its premise is gone."""
+    S = pkg()._lib.PAINN_TRAIN_SLICE
+    nodes, vectors, edges = pc.row_counts(c)
+    if which == pc.EDGE_EXACT:                                # every row count a whole number of slices, none of them a single one but the nodes'
+        assert nodes == S and vectors == 3 * S and edges % S == 0 and edges // S == 31
+    elif which == pc.EDGE_ONE_OVER:                           # one node row and one vector triple over; the edge rows ragged in a second slice
+        assert nodes == S + 1 and vectors == 3 * S + 3 and S < edges < 2 * S
+
+
+@pytest.mark.parametrize("cell", pc.EDGE_MATRIX, ids=pc.EDGE_IDS)
+def test_gradient_edge_matrix(cell):
+    """The cells of pc.EDGE_MATRIX through the body of test_gradient_matrix, with the premises of the cells that are there for a
+    row count: the slice cells, and R = 1 / 16 / 17 molecules against the 16 accumulators of the table and column sums."""
+    c = _check_cell(cell)
+    which = pc.EDGE_MATRIX.index(cell)
+    _slice_premise(which, c)
+    R = pc.halves(c["lk"]["kind"]) * c["B"]
+    if which in (6, 7, 8):
+        assert R == {6: 1, 7: 16, 8: 17}[which]
+    if which == 6:
+        assert R * c["A"] < 16                                # a single partial 16-row tile of the product kernel
+    if which == 3:
+        assert c["A"] == 32 and np.bincount(c["model"]["dst"]).min() == 31 and len(set(c["model"]["atom_ids"].tolist())) < c["A"]
 
 
 # ------------------------------------------------------------------------------------------------ bits
@@ -131,6 +164,25 @@ def test_gradient_bits_do_not_depend_on_the_call():
     for k in ga:
         if np.any(ga[k]):
             assert np.linalg.norm(gp[k] - ga[k]) <= 1e-5 * np.linalg.norm(ga[k]), k
+
+
+@pytest.mark.parametrize("which,more", [(pc.EDGE_EXACT, 1), (pc.EDGE_ONE_OVER, 17)], ids=["exact-multiple", "one-over"])
+def test_gradient_bits_at_the_slice_edges(which, more):
+    """The slices exist so that a gradient does not depend on the call: at a row count that is a whole number of slices and at one row
+    over, the same call twice and again after a larger call on the same trainer give the same bits."""
+    cell = pc.EDGE_MATRIX[which]
+    c = pc.matrix_case(cell)
+    _slice_premise(which, c)
+    tr = pc.make_trainer(c)
+    kw = pc.call_kw(c)
+    a = tr.grad(c["x0"], c["x1"], c["cond"], **kw)
+    b = tr.grad(c["x0"], c["x1"], c["cond"], **kw)
+    same = lambda p, q: np.array_equal(p["grad"], q["grad"]) and np.array_equal(np.asarray(p["loss"]), np.asarray(q["loss"])) and p["mean"] == q["mean"]
+    assert same(a, b) and np.isfinite(a["grad"]).all() and a["gnorm"] > 0.0
+    big = pc.matrix_case(cell[:4] + (cell[4] + more,) + cell[5:11] + (cell[11] + 1,))
+    g = tr.grad(big["x0"], big["x1"], big["cond"], **pc.call_kw(big))
+    assert not np.array_equal(g["grad"], a["grad"])
+    assert same(a, tr.grad(c["x0"], c["x1"], c["cond"], **kw))
 
 
 def test_outputs_end_where_they_should():

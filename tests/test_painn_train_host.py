@@ -65,18 +65,33 @@ def test_restated_optimiser_reaches_the_three_reference_steps():
     assert np.max(np.abs(want - c["flat"])) > 0.5 * lr
 
 
-@pytest.mark.parametrize("cell", pc.MATRIX, ids=pc.MATRIX_IDS)
+@pytest.mark.parametrize("cell", pc.MATRIX + pc.EDGE_MATRIX, ids=pc.MATRIX_IDS + pc.EDGE_IDS)
 def test_float32_restatement_stays_inside_a_third_of_the_bar(cell):
     """The inputs of the GPU shape matrix are kept only where the plain float32 model stays below 1e-5 / 3 per tensor, so that the
     1e-5 floor decides there and not the luck of a cancelling sum.  In the cells of FLOAT32_DECIDES the tensors
-    above it are the `v.linear.weight` ones alone, and they stay below 1e-5 (the bar there is 3 x this distance)."""
+    above it are the `v.linear.weight` ones alone, and they stay below 1e-5 (the bar there is 3 x this distance).  The edge cells
+    follow the same rule; in those of EDGE_FLOAT32_DECIDES the tensors above a third are among the recorded ones, every recorded one
+    is close to a third or above it, and every tensor stays below 1e-5."""
     c = pc.matrix_case(cell)
     _, _, g64 = pc.reference(c)
     _, _, g32 = pc.reference(c, torch.float32)
     errs = pc.tensor_errors(g32, g64)
     worst = max(errs, key=lambda r: r[1])
     print(f"{cell}: float32 restatement worst {worst[0]} {worst[1]:.3e}")
-    if pc.MATRIX.index(cell) in pc.FLOAT32_DECIDES:
+    edge = cell in pc.EDGE_MATRIX
+    if edge and pc.EDGE_MATRIX.index(cell) in pc.EDGE_FLOAT32_DECIDES:
+        recorded = pc.EDGE_FLOAT32_DECIDES[pc.EDGE_MATRIX.index(cell)]
+        now = {k: e for k, e, _ in errs}
+        over = {k for k, e in now.items() if e > 1e-5 / 3}
+        for k in sorted(over | set(recorded)):
+            print(f"   {k}: {now[k]:.3e} (recorded {recorded.get(k, float('nan')):.3e})")
+        # the float32 restatement is not the same bits on every host (pc.EDGE_FLOAT32_DECIDES has the spread that was measured), so the
+        # recorded set reaches that spread below a third: what is above a third here is recorded, and nothing is recorded that is
+        # not close to a third here
+        assert over <= set(recorded), sorted(over - set(recorded))
+        assert all(now[k] >= 1e-5 / 3 / pc.EDGE_HOST_SPREAD ** 2 for k in recorded)
+        assert worst[1] <= 1e-5 and all(d <= 1e-5 for d in recorded.values())
+    elif not edge and pc.MATRIX.index(cell) in pc.FLOAT32_DECIDES:
         assert all(e <= 1e-5 / 3 or (k.endswith("v.linear.weight") and e <= 1e-5) for k, e, _ in errs)
     else:
         assert worst[1] <= 1e-5 / 3
