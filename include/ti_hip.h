@@ -1051,7 +1051,8 @@ int ti_adw_train_set_lr(ti_handle* h, double lr);
  * The optimiser step of the molecule workflow (mdqm9/train_ambient.py:124-149 and its latent twin): StandardVelocityLoss with
  * LinearInterpolant or OneSidedVelocityLoss with OneSidedLinearInterpolant on cPaiNN, its gradient with respect to every parameter,
  * clip_grad_norm_, torch.optim.Adam with L2 weight decay, the NaN skip.  All three variants, F in {32, 64, 128, 256}, L >= 1, any
- * edge template with E >= 1; uniform batches (one species, no edge mask), f32, one GPU.  A trainer is a handle of its own kind (3),
+ * edge template with E >= 1; uniform batches (one species, no edge mask) -- or per-molecule graphs over the template through
+ * ti_painn_train_set_graphs, at the end of this header --, f32, one GPU.  A trainer is a handle of its own kind (3),
  * freed by ti_destroy; every painn / adw / adw-trainer entry point refuses it by its kind check, and the calls below refuse every
  * other handle with TI_E_ARG ("not a painn trainer handle").  It owns the fp64 master weights and both Adam moments, and an fp32
  * working copy in the canonical layout of ti_painn_create (weights.painn_param_spec), refreshed by the optimiser kernel.
@@ -1197,6 +1198,43 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* desc, const ti_painn
 int ti_painn_train_best(ti_handle* h, double* w, double* loss, int64_t* step, int reset);
 int ti_painn_train_noise(ti_handle* h, uint64_t seed, int64_t traj_offset, int32_t draw, const float* x1, int64_t B, int32_t noise,
                          float* out_x0, double* out_rot, int mem);
+
+/* ---- molecule trainer on per-molecule graphs: edge masks and mixed species ----------------------------------------------------------
+ * ti_painn_train_set_graphs: a table of n per-molecule graphs over the TRAINER's template (handle kind 3; ti_painn_set_edge_mask and
+ *   ti_painn_set_molecules keep refusing a trainer), in the conventions of ti_painn_set_molecules: n_atoms [n] each in 1..A (NULL:
+ *   every molecule has A atoms), atoms a >= n_atoms[b] are PAD atoms; mask [n][A], bit s of mask[b*A + d] = the edge s -> d exists
+ *   (NULL: every template edge between real atoms; s up to 31); pair_type [n][A][A] bytes 0..3, pair_type[(b*A + s)*A + d] the type of
+ *   s -> d (NULL: the template's types).  The library clears every bit that touches a pad atom; bits of pairs outside the template
+ *   are ignored.  All three NULL clears the table.  The arrays are copied into the handle; `mem` says where all three live.
+ *   Checks, before any device work, in this order: a NULL or other handle; n < 1 with a non-NULL array; a count outside 1..A; a type
+ *   above 3 (host arrays; device arrays are checked after their copy, before the table changes); an unknown mem.  All TI_E_ARG.
+ *   Which row a molecule reads.  ti_painn_train_grad / _step: molecule b uses row b, both halves [xt+; xt-] the row of b = r % B; a
+ *   table with n != B is TI_E_ARG.  ti_painn_train_steps with TI_NOISE_GIVEN: minibatch molecule j of step k uses row idx0[kB + j]
+ *   (without indices rows 0..B-1) -- the graph is batch0's, as in the reference's loss -- gathered on the device by the kernel that
+ *   expands the rows; n != n0 is TI_E_ARG.  Pairing an x1 row of the same species is the caller's business.  A table in force with
+ *   TI_NOISE_DRAWN / _ALIGNED is TI_E_UNSUPPORTED.  ti_painn_train_noise is unchanged.
+ * Semantics with a table in force (N = sum_b n_atoms[row of b], the real node rows of the call):
+ *   Pad atoms.  The passes run on a copy in which pad atom a of molecule b sits at xt[b][0] + (100 (a - n_b + 1), 0, 0) with cond 0 (the
+ *     drift's rule above), so every row of the dense layout is finite.  The library never reads a pad entry of x0, x1, cond or z: every
+ *     result is bit-identical whatever finite values they hold.
+ *   Interpolation and draws run over real entries only; a real component keeps its Philox key (seed, id, draw, 3a + c); pads draw
+ *     nothing.  TI_CENTER_BATCH takes the column means over the N real node rows (the reference's mean(dim=0) over its flat [N,3]):
+ *     the fp64 scheme above with pad rows entering as +0.0, divided by N.  TI_CENTER_MOLECULE runs over the n_b real atoms.
+ *   Loss.  l_b runs over the real entries; *out_mean = sum_b l_b / N; the output gradient is (b - target) / N on real rows and +0 on
+ *     pads; clip, Adam and the NaN skip use the divisor N.
+ *   Forward.  The edge-embedding row is pair_type[b][s][d]'s where given.  Per-node sums skip DEAD edges: those whose bit is clear or
+ *     that touch a pad.  Dead edge rows and pad node rows are computed like any other (finite), nothing reads them into a real row.
+ *   Reverse.  The per-node sums skip dead edges; the gP and gWd rows of dead edges are written as +0, so every weight-gradient
+ *     product, column sum and LayerNorm reverse receives exact zeros from dead rows and from pad node rows.  The dense products are
+ *     not compacted.  The edge-type table gradient is indexed by each molecule's own type per edge.
+ *   No atomics: the determinism paragraph above holds as it stands.
+ *   Identities, bit for bit: (a) a full table (n_atoms = A or NULL, every template bit set, pair_type NULL) gives the outputs of the
+ *     call without a table; (b) with update == 1 and TI_NOISE_GIVEN ti_painn_train_steps is the loop of ti_painn_train_set_graphs on
+ *     the gathered rows and ti_painn_train_step.  Without a table every call runs the kernels it ran before.
+ * State.  ti_painn_train_workspace_bytes and its formula are unchanged.  Beside the workspace the table takes n (4 + 4 A + A^2) bytes
+ *   (n (4 + 4 A) where pair_type is NULL: the types are then not stored) and a call with a table B (E + 4) bytes of per-call flags:
+ *   one byte per (molecule, template edge) -- bit 7 dead, bits 0..1 the type -- and the atom count. */
+int ti_painn_train_set_graphs(ti_handle* h, const int32_t* n_atoms, const uint32_t* mask, const uint8_t* pair_type, int64_t n, int mem);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,7 @@ ABI_SYMBOLS = [
     "ti_adw_train_set_state", "ti_adw_train_set_lr",
     "ti_painn_trainer_create", "ti_painn_train_grad", "ti_painn_train_apply", "ti_painn_train_step", "ti_painn_train_get_state",
     "ti_painn_train_set_state", "ti_painn_train_set_lr", "ti_painn_train_workspace_bytes",
-    "ti_painn_train_steps", "ti_painn_train_best", "ti_painn_train_noise",
+    "ti_painn_train_steps", "ti_painn_train_best", "ti_painn_train_noise", "ti_painn_train_set_graphs",
     "ti_obs_ff_forces", "ti_obs_ff_set_masses", "ti_obs_ff_langevin",
     "ti_obs_ff_remd",
     "ti_obs_bg_logw", "ti_obs_bg_ess",
@@ -313,6 +313,7 @@ def lib():
                                        C.POINTER(C.c_int64), C.c_int]
     L.ti_painn_train_best.argtypes = [vp, dp, dp, C.POINTER(C.c_int64), C.c_int]
     L.ti_painn_train_noise.argtypes = [vp, C.c_uint64, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, C.c_int]
+    L.ti_painn_train_set_graphs.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int]
     _lib = L
     return L
 

@@ -8,8 +8,11 @@
 // draws the latent base samples) and synchronises once.
 // The optimiser shell -- master state, counters, clip + Adam, the state entry points, index handling -- is train_optim.hpp's, shared
 // with api_adw_train.hip.
+// With a table of per-molecule graphs in force (ti_painn_train_set_graphs) a call expands the rows it reads into per-call flags and
+// takes painn_train_graph_kernels.hip's twins where a kernel reads the graph or a molecule's entries; every other launch is the same.
 #include "train_optim.hpp"
 #include "painn_steps.hpp"
+#include "painn_train_graph.hpp"
 
 namespace {
 
@@ -41,6 +44,10 @@ struct PainnTrainState : Optim {                 // is_bias: 1 at the biases, La
     DevBuf<double> nxc, nrot, best_w, best;
     bool best_tracked = false; long long best_steps = 0;      // a call has tracked since the last reset; the steps tracked since then
     bool mirror_stale = false;                   // a many-step call did not reach its read-back: the next one reads the counters first
+    // ti_painn_train_set_graphs: the table of gn per-molecule graphs (0: none) -- counts, mask words, pair types (empty: the
+    // template's) -- with the host copy of the counts (a call's N), and the flags and counts of the call in flight
+    long long gn = 0; std::vector<int32_t> g_nat;
+    DevBuf<int32_t> gt_nat, gnat; DevBuf<uint32_t> gt_mask; DevBuf<uint8_t> gt_ptype, gflag;
 };
 
 PainnTrainState* state_of(ti_handle* h) { return static_cast<PainnTrainState*>(h->train.get()); }
@@ -189,7 +196,8 @@ void ensure_ws(PainnTrainState* S, const Plan& p, long long B, int halves)
 // S->loss holds the loss rows, S->red (their sum, the sum of the squared gradient entries) and S->grad the gradient of the mean loss.
 // reverse == false stops behind the loss rows and their sum: S->grad and the sum of squares are left as they were.
 void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, const ti_vloss_desc* d, const float* x0, const float* x1,
-                            const float* cond, const float* t_given, const float* z_given, long long B, bool reverse = true)
+                            const float* cond, const float* t_given, const float* z_given, long long B, bool reverse = true,
+                            const PtLive* lv = nullptr)
 {
     hipStream_t st = h->stream;
     const bool two = d->kind == TI_VLOSS_STANDARD;
@@ -214,18 +222,20 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
     vp.seed = d->seed; vp.traj0 = d->traj_offset; vp.draw = d->draw;
     vp.z = two ? ar + p.z : nullptr; vp.raw = S->raw.p; vp.colsum = S->red.p + RED_COLSUM;
     vp.xt = ar + p.xt; vp.half = (long long)n;
-    HIP_CHECK(launch_vloss_interp(vp, st));
+    HIP_CHECK(lv ? launch_ptg_interp(vp, *lv, st) : launch_vloss_interp(vp, st));
     if (d->center == TI_CENTER_BATCH)
         for (int hf = 0; hf < halves; ++hf)
             HIP_CHECK(launch_vloss_colsum(S->red.p + RED_COLSUM + hf * 3, S->part64.p, S->raw.p + (size_t)hf * n, B * A, 3, st));
-    if (d->center != TI_CENTER_NONE) HIP_CHECK(launch_vloss_center(vp, st));
+    if (d->center != TI_CENTER_NONE) HIP_CHECK(lv ? launch_ptg_center(vp, *lv, st) : launch_vloss_center(vp, st));
+    if (lv) HIP_CHECK(launch_ptg_pad(ar + p.xt, (long long)n, halves, A, *lv, st));
 
     // ---- forward
     HIP_CHECK(launch_ptrain_geom(ar + p.dir, ar + p.dist, ar + p.xt, g, st));
     HIP_CHECK(launch_ptrain_enc(ar + p.enc, ar + p.dist, S->d.length_scale, g, st));
     PtEmbedIn ei{w + S->atom_emb, cond, td, S->atom_ids.p, S->ncond, S->nE, B, S->d.temp_length, S->d.time_length, S->d.temp_mean, S->d.temp_range};
-    HIP_CHECK(launch_ptrain_embed_in(ar + p.s_in0, ei, g, st));
-    HIP_CHECK(launch_ptrain_edge_emb(ar + p.layers[0].e_in, w + S->edge_emb, S->etype.p, g, st));
+    HIP_CHECK(lv ? launch_ptg_embed_in(ar + p.s_in0, ei, g, *lv, st) : launch_ptrain_embed_in(ar + p.s_in0, ei, g, st));
+    HIP_CHECK(lv ? launch_ptg_edge_emb(ar + p.layers[0].e_in, w + S->edge_emb, g, *lv, st)
+                 : launch_ptrain_edge_emb(ar + p.layers[0].e_in, w + S->edge_emb, S->etype.p, g, st));
     HIP_CHECK(hipMemsetAsync(ar + p.layers[0].v_in, 0, (size_t)3 * Rn * F * sizeof(float), st));
     run.mlp_forward(S->embed, ar + p.s_in0, Rn, p.emb, ar + p.layers[0].s_in);
     for (int l = 0; l < L; ++l) {
@@ -233,7 +243,8 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
         HIP_CHECK(launch_ptrain_phi_in(ar + a.phi_in, ar + a.s_in, ar + a.e_in, g, st));
         run.mlp_forward(S->phi[l], ar + a.phi_in, Re, a.phi, ar + a.P);
         run.mlp_forward(S->filt[l], ar + p.enc, Re, a.w, ar + a.Wd);
-        HIP_CHECK(launch_ptrain_msg_fwd(ar + a.s_m, ar + a.v_m, ar + a.s_in, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, st));
+        HIP_CHECK(lv ? launch_ptg_msg_fwd(ar + a.s_m, ar + a.v_m, ar + a.s_in, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, *lv, st)
+                     : launch_ptrain_msg_fwd(ar + a.s_m, ar + a.v_m, ar + a.s_in, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, st));
         if (l + 1 < L) HIP_CHECK(launch_ptrain_e_fwd(ar + p.layers[l + 1].e_in, ar + a.e_in, ar + a.P, ar + a.Wd, g, st));
         run.lin(ar + a.v_m, F, S->U[l], nullptr, F, 3 * Rn, ar + a.uv);
         run.lin(ar + a.v_m, F, S->V[l], nullptr, F, 3 * Rn, ar + a.vv);
@@ -248,12 +259,12 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
 
     // ---- the loss rows by the velocity loss's own kernel, their sum by its fixed tree
     vp.b = ar + p.bout; vp.loss = S->loss.p;
-    HIP_CHECK(launch_vloss_reduce(vp, st));
+    HIP_CHECK(lv ? launch_ptg_reduce(vp, *lv, st) : launch_vloss_reduce(vp, st));
     HIP_CHECK(launch_vloss_colsum(S->red.p + RED_LOSS, S->part64.p, S->loss.p, B, 1, st));
     if (!reverse) return;
 
     // ---- reverse
-    HIP_CHECK(launch_ptrain_gout(ar + p.gb, vp, st));
+    HIP_CHECK(lv ? launch_ptg_gout(ar + p.gb, vp, *lv, st) : launch_ptrain_gout(ar + p.gb, vp, st));
     int cur = 0;
     HIP_CHECK(launch_ptrain_readout_bwd(ar + p.gro, ar + p.gVv, ar + p.gv[cur], ar + p.gb, ar + p.Vv, ar + p.ro_out, w + S->Vr, g, st));
     run.wgrad(ar + p.gVv, 1, v_fin, F, S->Vr, S->Vr, (size_t)F, 3 * Rn, run.sl_v);
@@ -276,16 +287,20 @@ void train_forward_backward(ti_handle* h, PainnTrainState* S, const Plan& p, con
         HIP_CHECK(launch_ptrain_add3(ar + p.gv[1 - cur], ar + p.gv[cur], ar + p.tmp1, ar + p.tmp2, 3 * Rn * F, st));
         cur = 1 - cur;
         // message
-        HIP_CHECK(launch_ptrain_msg_bwd_edge(ar + p.gP, ar + p.gWd, ar + p.gs[cur], ar + p.gv[cur], ge, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, st));
+        HIP_CHECK(lv ? launch_ptg_msg_bwd_edge(ar + p.gP, ar + p.gWd, ar + p.gs[cur], ar + p.gv[cur], ge, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, *lv, st)
+                     : launch_ptrain_msg_bwd_edge(ar + p.gP, ar + p.gWd, ar + p.gs[cur], ar + p.gv[cur], ge, ar + a.v_in, ar + a.P, ar + a.Wd, ar + p.dir, g, st));
         run.mlp_backward(S->phi[l], p, ar + a.phi_in, Re, a.phi, ar + p.gP, ar + p.gin_phi, 2 * F, run.sl_e);
         run.mlp_backward(S->filt[l], p, ar + p.enc, Re, a.w, ar + p.gWd, nullptr, 0, run.sl_e);
-        HIP_CHECK(launch_ptrain_msg_bwd_node(ar + p.gs[1 - cur], ar + p.gv[1 - cur], ar + p.gs[cur], ar + p.gv[cur], ar + p.gin_phi, ar + a.P, ar + a.Wd,
-                                             ar + p.dir, g, st));
+        HIP_CHECK(lv ? launch_ptg_msg_bwd_node(ar + p.gs[1 - cur], ar + p.gv[1 - cur], ar + p.gs[cur], ar + p.gv[cur], ar + p.gin_phi, ar + a.P, ar + a.Wd,
+                                               ar + p.dir, g, *lv, st)
+                     : launch_ptrain_msg_bwd_node(ar + p.gs[1 - cur], ar + p.gv[1 - cur], ar + p.gs[cur], ar + p.gv[cur], ar + p.gin_phi, ar + a.P, ar + a.Wd,
+                                                  ar + p.dir, g, st));
         HIP_CHECK(launch_ptrain_e_bwd(ar + p.ge[ecur], ge, ar + p.gin_phi, g, st));
         ge = ar + p.ge[ecur]; ecur = 1 - ecur;
         cur = 1 - cur;
     }
-    HIP_CHECK(launch_ptrain_table(S->grad.p + S->edge_emb, ge, F, S->etype.p, E, 4, R, F, st));
+    HIP_CHECK(lv ? launch_ptg_table(S->grad.p + S->edge_emb, ge, F, g, *lv, st)
+                 : launch_ptrain_table(S->grad.p + S->edge_emb, ge, F, S->etype.p, E, 4, R, F, st));
     run.mlp_backward(S->embed, p, ar + p.s_in0, Rn, p.emb, ar + p.gs[cur], ar + p.gin_emb, F, run.sl_n);
     HIP_CHECK(launch_ptrain_table(S->grad.p + S->atom_emb, ar + p.gin_emb, F, S->atom_ids.p, A, S->d.n_types, R, F, st));
     HIP_CHECK(launch_train_combine(S->grad.p, S->sq.p, nullptr, S->is_bias.p, 0, S->nW, 0, 0, 0, st));
@@ -301,12 +316,32 @@ int call_check(ti_handle* h, const ti_vloss_desc* d, const float* x0, const floa
     if (ours) if (int rc = workspace_check(state_of(h), B, d->kind == TI_VLOSS_STANDARD ? 2 : 1)) return rc;
     if (!x0 || !x1 || (ours && state_of(h)->ncond > 0 && !cond)) return fail(TI_E_ARG, "NULL buffer");
     if (!ours) return fail(TI_E_ARG, "not a painn trainer handle");
+    if (state_of(h)->gn && state_of(h)->gn != B)
+        return fail(TI_E_ARG, "the table of ti_painn_train_set_graphs has " + std::to_string(state_of(h)->gn) + " rows, the call B = " + std::to_string(B));
     return TI_OK;
 }
 
-// stages the inputs of a host call and runs the two passes
-void run_passes(ti_handle* h, PainnTrainState* S, const ti_vloss_desc* d, const float* x0, const float* x1, const float* cond, const float* t,
-                const float* z, int64_t B, int mem)
+// With a table in force: the flags and counts of a call over B molecules that reads the table rows idx (idx_dev where the kernel
+// reads them, idx_host for N; both NULL: rows 0..B-1), enqueued on the stream.  gflag and gnat have been grown by the caller.
+PtLive expand_graphs(ti_handle* h, PainnTrainState* S, const long long* idx_dev, const int64_t* idx_host, long long B)
+{
+    const PtTable t{S->gt_nat.p, S->gt_mask.p, S->gt_ptype.p, idx_dev, S->gn};
+    const PtGraph g{S->src.p, S->dst.p, S->d.n_atoms, S->d.n_edges, S->d.n_features, 0};
+    HIP_CHECK(launch_ptg_expand(S->gflag.p, S->gnat.p, t, S->etype.p, g, B, h->stream));
+    long long N = 0;
+    for (long long b = 0; b < B; ++b) N += S->g_nat[(size_t)(idx_host ? idx_host[b] : b)];
+    return PtLive{S->gflag.p, S->gnat.p, B, (double)N};
+}
+
+void grow_graph_flags(PainnTrainState* S, long long B)
+{
+    grow(S->gflag, (size_t)B * S->d.n_edges);
+    grow(S->gnat, (size_t)B);
+}
+
+// stages the inputs of a host call and runs the two passes -> the divisor of the mean: B A, or N with a table in force
+double run_passes(ti_handle* h, PainnTrainState* S, const ti_vloss_desc* d, const float* x0, const float* x1, const float* cond, const float* t,
+                  const float* z, int64_t B, int mem)
 {
     Staged sg(h, mem);
     const int halves = d->kind == TI_VLOSS_STANDARD ? 2 : 1;
@@ -316,7 +351,11 @@ void run_passes(ti_handle* h, PainnTrainState* S, const ti_vloss_desc* d, const 
     const float *x0d = sg.in(x0, S->sx0, n), *x1d = sg.in(x1, S->sx1, n);
     const float* cd = sg.in(cond, S->sc, (size_t)B * S->d.n_atoms * S->ncond);
     const float *td = sg.in(t, S->tin, (size_t)B), *zd = sg.in(z, S->zin, n);
-    train_forward_backward(h, S, p, d, x0d, x1d, cd, td, zd, B);
+    if (!S->gn) { train_forward_backward(h, S, p, d, x0d, x1d, cd, td, zd, B); return (double)(B * S->d.n_atoms); }
+    grow_graph_flags(S, B);
+    const PtLive lv = expand_graphs(h, S, nullptr, nullptr, B);
+    train_forward_backward(h, S, p, d, x0d, x1d, cd, td, zd, B, true, &lv);
+    return lv.N;
 }
 
 }  // namespace
@@ -396,8 +435,8 @@ int ti_painn_train_grad(ti_handle* h, const ti_vloss_desc* d, const float* x0, c
     return guarded([&]() -> int {
         set_device(h);
         PainnTrainState* S = state_of(h);
-        run_passes(h, S, d, x0, x1, cond, t, z, B, mem);
-        return S->grad_readback(out_loss, out_mean, out_grad, out_gnorm, B, (double)(B * S->d.n_atoms), mem, S->loss.p, h->stream);
+        const double divisor = run_passes(h, S, d, x0, x1, cond, t, z, B, mem);
+        return S->grad_readback(out_loss, out_mean, out_grad, out_gnorm, B, divisor, mem, S->loss.p, h->stream);
     });
 }
 
@@ -418,8 +457,8 @@ int ti_painn_train_step(ti_handle* h, const ti_vloss_desc* d, const float* x0, c
         hipStream_t st = h->stream;
         S->read_counters(st);
         S->upload_bias(1, st);
-        run_passes(h, S, d, x0, x1, cond, t, z, B, mem);
-        const TrAdam a = S->adam_params(true, (double)(B * S->d.n_atoms), S->log.p);
+        const double divisor = run_passes(h, S, d, x0, x1, cond, t, z, B, mem);
+        const TrAdam a = S->adam_params(true, divisor, S->log.p);
         HIP_CHECK(launch_train_adam(a, st));
         HIP_CHECK(launch_train_finish(a, st));
         double mean = 0.0;
@@ -492,6 +531,9 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_st
     if (!ours) return fail(TI_E_ARG, "not a painn trainer handle");
     if (!given && state_of(h)->ncond == 2) return fail(TI_E_UNSUPPORTED, "drawn noise on the ambient variant: its set 0 is data");
     if (sd->noise == TI_NOISE_ALIGNED && h->d.n_atoms < 3) return fail(TI_E_UNSUPPORTED, "TI_NOISE_ALIGNED needs n_atoms >= 3: the rotation is not unique");
+    if (state_of(h)->gn && !given) return fail(TI_E_UNSUPPORTED, "a table of ti_painn_train_set_graphs is in force: drawn base samples on per-molecule graphs are not built");
+    if (state_of(h)->gn && state_of(h)->gn != n0)
+        return fail(TI_E_ARG, "the table of ti_painn_train_set_graphs has " + std::to_string(state_of(h)->gn) + " rows, set 0 n0 = " + std::to_string(n0));
     return guarded([&]() -> int {
         set_device(h);
         PainnTrainState* S = state_of(h);
@@ -504,6 +546,19 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_st
         const Plan p = plan(S, B, halves);
         ensure_ws(S, p, B, halves);
         grow(S->log, (size_t)n_steps);
+        // a table in force: the rows a step reads are idx0's, which the host needs for the step's N (device indices are read back here,
+        // before anything is enqueued)
+        std::vector<int64_t> gidx;
+        const int64_t* gidx_h = nullptr;
+        if (S->gn) {
+            grow_graph_flags(S, B);
+            if (idx0 && sg.host) gidx_h = idx0;
+            else if (idx0) {
+                gidx.resize(n_idx);
+                HIP_CHECK(hipMemcpy(gidx.data(), idx0, n_idx * sizeof(int64_t), hipMemcpyDeviceToHost));
+                gidx_h = gidx.data();
+            }
+        }
         grow(S->gx0, (size_t)B * m); grow(S->gx1, (size_t)B * m); grow(S->gcond, (size_t)B * A * std::max(S->ncond, 1));
         if (!given) grow(S->nxc, (size_t)B * m);
         if (sd->track_best && !S->best_w.p) {
@@ -535,15 +590,21 @@ int ti_painn_train_steps(ti_handle* h, const ti_vloss_desc* d, const ti_painn_st
                 PtNoise q{dk.seed, dk.traj_offset, dk.draw, S->gx1.p, B, A, sd->noise == TI_NOISE_ALIGNED ? 1 : 0, S->nxc.p, S->gx0.p, nullptr};
                 HIP_CHECK(launch_ptnoise(q, st));
             }
-            train_forward_backward(h, S, p, &dk, S->gx0.p, S->gx1.p, S->ncond ? S->gcond.p : nullptr, nullptr, nullptr, B, update);
-            if (!update) { HIP_CHECK(launch_ptsteps_log(S->log.p + k, S->red.p + RED_LOSS, divisor, st)); continue; }
+            double div_k = divisor;
+            TrAdam ak = a;
+            if (S->gn) {
+                const PtLive lv = expand_graphs(h, S, g.idx0, gidx_h ? gidx_h + k * B : nullptr, B);
+                div_k = ak.B = lv.N;
+                train_forward_backward(h, S, p, &dk, S->gx0.p, S->gx1.p, S->ncond ? S->gcond.p : nullptr, nullptr, nullptr, B, update, &lv);
+            } else train_forward_backward(h, S, p, &dk, S->gx0.p, S->gx1.p, S->ncond ? S->gcond.p : nullptr, nullptr, nullptr, B, update);
+            if (!update) { HIP_CHECK(launch_ptsteps_log(S->log.p + k, S->red.p + RED_LOSS, div_k, st)); continue; }
             if (sd->track_best) {
-                const PtBest q{S->best_w.p, S->w.p, S->nW, S->best.p, S->red.p + RED_LOSS, S->red.p + RED_SUMSQ, divisor, (double)(S->best_steps + k)};
+                const PtBest q{S->best_w.p, S->w.p, S->nW, S->best.p, S->red.p + RED_LOSS, S->red.p + RED_SUMSQ, div_k, (double)(S->best_steps + k)};
                 HIP_CHECK(launch_ptsteps_best_keep(q, st));
                 HIP_CHECK(launch_ptsteps_best_commit(q, st));
             }
-            HIP_CHECK(launch_train_adam(a, st));
-            HIP_CHECK(launch_train_finish(a, st));
+            HIP_CHECK(launch_train_adam(ak, st));
+            HIP_CHECK(launch_train_finish(ak, st));
         }
         S->steps_readback(out_loss, out_skipped, n_steps, st);      // the one synchronisation of the call
         S->mirror_stale = false;
@@ -610,6 +671,57 @@ int ti_painn_train_noise(ti_handle* h, uint64_t seed, int64_t traj_offset, int32
             if (rd) HIP_CHECK(hipMemcpyAsync(out_rot, rd, (size_t)B * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
         }
         HIP_CHECK(hipStreamSynchronize(st));
+        return TI_OK;
+    });
+}
+
+int ti_painn_train_set_graphs(ti_handle* h, const int32_t* n_atoms, const uint32_t* mask, const uint8_t* pair_type, int64_t n, int mem)
+{
+    if (!h || h->kind != 3) return fail(TI_E_ARG, "not a painn trainer handle");
+    const bool any = n_atoms || mask || pair_type;
+    if (any && n < 1) return fail(TI_E_ARG, "n < 1");
+    PainnTrainState* S = state_of(h);
+    const int A = S->d.n_atoms;
+    auto counts_check = [&](const int32_t* na) {
+        for (int64_t b = 0; na && b < n; ++b)
+            if (na[b] < 1 || na[b] > A) return fail(TI_E_ARG, "n_atoms[" + std::to_string(b) + "] = " + std::to_string(na[b]) + " is outside 1.." + std::to_string(A));
+        return (int)TI_OK;
+    };
+    auto types_check = [&](const uint8_t* pt) {
+        const size_t per = (size_t)A * A;
+        for (size_t i = 0; pt && i < (size_t)n * per; ++i) if (pt[i] > 3) return fail(TI_E_ARG, "pair_type above 3 (molecule " + std::to_string(i / per) + ")");
+        return (int)TI_OK;
+    };
+    if (any && mem != TI_MEM_DEVICE) {      // the stated order puts these ahead of the mem check: what is not TI_MEM_DEVICE is read as host arrays
+        if (int rc = counts_check(n_atoms)) return rc;
+        if (int rc = types_check(pair_type)) return rc;
+    }
+    if (mem != TI_MEM_HOST && mem != TI_MEM_DEVICE) return fail(TI_E_ARG, "unknown mem");
+    return guarded([&]() -> int {
+        set_device(h);
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        if (!any) {
+            S->gn = 0; S->g_nat.clear();
+            S->gt_nat.release(); S->gt_mask.release(); S->gt_ptype.release();
+            return TI_OK;
+        }
+        auto fetch = [&](void* dst, const void* src, size_t bytes) {
+            if (mem == TI_MEM_DEVICE) HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+            else std::memcpy(dst, src, bytes);
+        };
+        std::vector<int32_t> na((size_t)n, A);
+        if (n_atoms) fetch(na.data(), n_atoms, na.size() * sizeof(int32_t));
+        std::vector<uint8_t> pt;
+        if (pair_type) { pt.resize((size_t)n * A * A); fetch(pt.data(), pair_type, pt.size()); }
+        if (mem == TI_MEM_DEVICE) {
+            if (int rc = counts_check(na.data())) return rc;
+            if (int rc = types_check(pair_type ? pt.data() : nullptr)) return rc;
+        }
+        std::vector<uint32_t> m((size_t)n * A, 0xffffffffu);       // NULL: every template edge (the expansion clears what touches a pad)
+        if (mask) fetch(m.data(), mask, m.size() * sizeof(uint32_t));
+        S->gt_nat.upload(na); S->gt_mask.upload(m);
+        if (pair_type) S->gt_ptype.upload(pt); else S->gt_ptype.release();
+        S->g_nat = std::move(na); S->gn = n;
         return TI_OK;
     });
 }

@@ -956,8 +956,37 @@ def _molecule_train_settings(config, latent):
     for key in ("model_save_path", "model_save_name"):
         if not isinstance(g(key), str) or not g(key):
             raise ValueError(f"config.{key} must be a non-empty string")
-    out.update(gamma=gamma, t_distr=t_distr, align=bool(align))
+    radius, cutoff = g("radius_graphs", False), None
+    if not isinstance(radius, (bool, np.bool_)) or (radius and latent):
+        raise ValueError(f"config.radius_graphs must be a bool (and False for the latent workflow, whose base samples have no graph), got {radius!r}")
+    if radius:
+        cutoff = g("cutoff")
+        if isinstance(cutoff, bool) or not isinstance(cutoff, (int, float, np.integer, np.floating)) or not np.isfinite(cutoff) or cutoff <= 0:
+            raise ValueError(f"config.radius_graphs needs config.cutoff, a finite number > 0, got {cutoff!r}")
+        cutoff = float(cutoff)
+    out.update(gamma=gamma, t_distr=t_distr, align=bool(align), radius_graphs=bool(radius), cutoff=cutoff)
     return out
+
+
+def _radius_masks(x, cutoff, template, atom_key):
+    """masks [n, A] uint32 of a resident set over the template of `template`: bit s of masks[i, d] is set when row i has the edge
+    s -> d -- the pairs data.radius_edges gives at `cutoff` (|x_d - x_s| <= cutoff in float64, no self loops), and the template's
+    bonded pairs (type > 0), which the reference's bond graph puts into every sample whatever the cutoff."""
+    from .thermo._molecule import split_batch
+    _, A, src, dst, ety, _ = split_batch(template, atom_key)
+    if x.shape[1] != A:
+        raise ValueError(f"set0 has {x.shape[1]} atoms per molecule, the template {A}")
+    if A > 32:
+        raise ValueError(f"per-molecule edge sets need A <= 32 atoms, got {A}")
+    bonds = np.zeros(A, np.uint64)
+    np.bitwise_or.at(bonds, dst[ety > 0], np.uint64(1) << src[ety > 0].astype(np.uint64))
+    bit = np.uint64(1) << np.arange(A, dtype=np.uint64)
+    masks = np.empty((x.shape[0], A), np.uint32)
+    for lo in range(0, x.shape[0], 4096):
+        xs = np.asarray(x[lo:lo + 4096], np.float64)
+        near = (np.linalg.norm(xs[:, :, None, :] - xs[:, None, :, :], axis=-1) <= cutoff) & ~np.eye(A, dtype=bool)      # [i, d, s]
+        masks[lo:lo + 4096] = ((near * bit).sum(axis=-1, dtype=np.uint64) | bonds).astype(np.uint32)
+    return masks
 
 
 def _molecule_set(s, name):
@@ -1002,6 +1031,8 @@ def _train_molecule(config, set0, set1, template, resume, latent):
         kw = dict(noise="aligned" if s["align"] else "drawn")
     else:
         sets, kw = (x0, T0, x1, T1), {}
+        if s["radius_graphs"]:                  # the graphs of set 0, once: a minibatch molecule trains on the graph of its set-0 row
+            kw = dict(masks=_radius_masks(x0, s["cutoff"], template, b.ATOM_KEY))
     for epoch in range(first, s["n_epochs"]):
         perm, draw = [s["seed"], 2, epoch], _TRAIN_DRAW0 + epoch * 2 * steps
         losses, skipped = trainer.fit(*sets, B, steps, perm, draw=draw, noise_seed=s["seed"], template_batch=template, track_best=True, **kw)
@@ -1035,7 +1066,11 @@ def train_ambient(config, set0, set1, template, resume=False):
     reads them), train_state.npz (optimiser and scheduler state, the epochs done) and log.npz (train_loss, last_train_loss, best_loss,
     lr, skipped per epoch) under model_save_path/model_save_name; resume=True continues from train_state.npz.  Config: n_features,
     score_layers, batch_size, n_epochs, learning_rate, weight_decay, a, gamma, t_distr, seed, model_save_path, model_save_name
-    (align must be False).  -> the log as a dict."""
+    (align must be False).  Optional radius_graphs (default False; without it the run is what it was): every sample of set 0 trains on
+    its own radius graph at config.cutoff (finite, > 0), as the reference's data set builds one per sample and its loss evaluates both
+    states on batch0's graph -- masks over the template's edges, built once on the host by the rule of data.radius_edges plus the
+    template's bonds, passed to fit / evaluate; the template should then hold every pair a sample can have (the complete graph with
+    the species' bond types).  -> the log as a dict."""
     return _train_molecule(config, set0, set1, template, resume, latent=False)
 
 

@@ -1601,6 +1601,66 @@ class PainnTrainer(_Trainer):
         _lib.check(_lib.lib().ti_painn_train_best(self.h, w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(loss), C.byref(step), int(bool(reset))))
         return dict(w=w if step.value >= 0 else None, loss=loss.value, step=int(step.value))
 
+    def set_graphs(self, n_atoms=None, mask=None, pair_type=None):
+        """ti_painn_train_set_graphs: a table of n per-molecule graphs over this trainer's template, as PainnEngine.set_molecules takes
+        them: n_atoms [n] in 1..A (None: all A; atoms a >= n_atoms[b] are pad atoms, whose x0 / x1 / cond / z entries are never read),
+        mask [n, A] uint32 or int32, bit s of mask[b, d] set when the edge s -> d exists (None: every template edge between real
+        atoms), pair_type [n, A, A] in 0..3 at [b, s, d] (None: the template's types).  grad / step then take B = n molecules, molecule
+        b on row b; steps (noise='given') takes n = n0 and reads row idx0[k, j].  All None clears the table.  Numpy arrays (or CPU
+        tensors) are copied from the host; CUDA tensors, all of them then, are read on the device."""
+        L = _lib.lib()
+        given = [a for a in (n_atoms, mask, pair_type) if a is not None]
+        if not given:
+            _lib.check(L.ti_painn_train_set_graphs(self.h, None, None, None, 0, _lib.MEM_HOST))
+            return
+        on_gpu = [hasattr(a, "data_ptr") and a.is_cuda for a in given]
+        if any(on_gpu) != all(on_gpu):
+            raise ValueError("all arrays of a call must live in the same memory space (all host or all on the GPU)")
+        n = int(given[0].shape[0]) if hasattr(given[0], "shape") else len(given[0])
+        shapes = ((n,), (n, self.A), (n, self.A, self.A))
+        names = ("n_atoms", "mask", "pair_type")
+        if all(on_gpu):
+            import torch
+            want = (("torch.int32",), ("torch.int32", "torch.uint32"), ("torch.uint8",))
+            ptrs, keep = [], []
+            for a, shape, name, dts in zip((n_atoms, mask, pair_type), shapes, names, want):
+                if a is None:
+                    ptrs.append(None)
+                    continue
+                if str(a.dtype) not in dts:
+                    raise TypeError(f"{name} must be {' or '.join(dts)}, got {a.dtype}")
+                if tuple(a.shape) != shape:
+                    raise ValueError(f"{name} must be {list(shape)}, got {tuple(a.shape)}")
+                if a.device.index != self.device:
+                    raise ValueError(f"{name} lives on cuda:{a.device.index} but this trainer was created on device {self.device}")
+                a = a.contiguous()
+                keep.append(a); ptrs.append(C.c_void_p(a.data_ptr()))
+            torch.cuda.current_stream(self.device).synchronize()
+            _lib.check(L.ti_painn_train_set_graphs(self.h, *ptrs, n, _lib.MEM_DEVICE))
+            return
+        host = lambda a: a.detach().numpy() if hasattr(a, "data_ptr") else np.asarray(a)
+        na = m = t = None
+        if n_atoms is not None:
+            na = np.ascontiguousarray(host(n_atoms), np.int32)
+            if na.shape != shapes[0]:
+                raise ValueError(f"n_atoms must be [{n}], got {na.shape}")
+        if mask is not None:
+            m = host(mask)
+            if m.dtype not in (np.uint32, np.int32):
+                raise TypeError(f"mask must be uint32 or int32, got {m.dtype}")
+            if m.shape != shapes[1]:
+                raise ValueError(f"mask must be [{n},{self.A}], got {m.shape}")
+            m = np.ascontiguousarray(m.view(np.uint32))
+        if pair_type is not None:
+            t = host(pair_type)
+            if t.shape != shapes[2]:
+                raise ValueError(f"pair_type must be [{n},{self.A},{self.A}], got {t.shape}")
+            if t.size and (t.min() < 0 or t.max() > 255):
+                raise ValueError("pair_type entries must be in 0..3")
+            t = np.ascontiguousarray(t, np.uint8)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        _lib.check(L.ti_painn_train_set_graphs(self.h, ptr(na), ptr(m), ptr(t), n, _lib.MEM_HOST))
+
     def workspace_bytes(self, B, kind="standard"):
         """ti_painn_train_workspace_bytes: what a call over B molecules needs beside the trainer's state"""
         n = int(_lib.lib().ti_painn_train_workspace_bytes(self.h, int(B), _lib.VLOSS_KINDS[kind]))

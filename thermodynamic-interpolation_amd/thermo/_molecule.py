@@ -498,7 +498,8 @@ class MoleculeTrainerBase:
     weight_decay), the NaN skip.  ``b`` is a thermo cPaiNN whose weights are the starting point; ``loss_fn`` a thermo.losses loss,
     which gives the kind, gamma, a and t_distr.  The fp64 master weights live on the device; ``sync()`` writes them back into ``b``.
     A trainer serves one species: the device trainer is built from the first batch's template, and a batch with another template,
-    an edge mask or mixed species is refused."""
+    an edge mask or mixed species is refused -- unless with_batches("per_molecule", max_atoms=A) was chosen, which trains one model on
+    batches whose molecules differ in size, graph and bond types."""
     BETA_NAME = "beta_half"              # what t_distr='beta' means for this workflow's loss
 
     def __init__(self, b, loss_fn, lr, weight_decay=0.0, max_grad_norm=1.0, betas=(0.9, 0.999), eps=1e-8, max_workspace_bytes=0):
@@ -507,6 +508,96 @@ class MoleculeTrainerBase:
         self._kw = dict(kind=loss_fn.KIND, gamma=ip.gamma_name, a=ip.a_param, t_distr="uniform" if loss_fn.t_distr == "uniform" else self.BETA_NAME)
         self._opt = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, max_workspace_bytes=max_workspace_bytes)
         self.engine, self._key, self._pending = None, None, None
+        self.batches, self.max_atoms = "uniform", None
+
+    def with_batches(self, batches="uniform", max_atoms=None):
+        """How the trainer reads its batches -> self.  "uniform" (the default): one species, one graph, anything else is refused.
+        "per_molecule" with max_atoms=A: the device trainer is built on the fully connected template over A atoms with atom ids
+        0 .. A - 1 (the reference's distinguish=True features), and step / loss take whatever split_species_batch takes -- molecules
+        of different size, graph and bond types, padded as SpeciesBatch pads them -- through engine.PainnTrainer.set_graphs.  Chosen
+        before the first batch."""
+        if batches not in ("uniform", "per_molecule"):
+            raise ValueError(f"batches must be 'uniform' or 'per_molecule', got {batches!r}")
+        if self.engine is not None:
+            raise RuntimeError("the device trainer exists already: choose the batch form before the first batch")
+        if batches == "per_molecule":
+            if max_atoms is None or not 1 <= int(max_atoms) <= 32:
+                raise ValueError("batches='per_molecule' needs max_atoms in 1..32, the largest molecule the trainer will see")
+            if int(max_atoms) > self.b.n_types:
+                raise ValueError(f"max_atoms = {int(max_atoms)} but the model embeds n_types = {self.b.n_types} atom ids")
+        elif max_atoms is not None:
+            raise ValueError("max_atoms belongs to batches='per_molecule'")
+        self.batches, self.max_atoms = batches, None if max_atoms is None else int(max_atoms)
+        return self
+
+    def _build(self, A, src, dst, ety, ids, key):
+        b = self.b
+        flat = _W.flatten_state_dict(b._sd, b._spec, dtype=np.float64)
+        self.engine = _engine.PainnTrainer(b.VARIANT, b.n_features, b.score_layers, A, src, dst, ety, ids, flat, n_types=b.n_types,
+                                           temp_length=b.temp_length, time_length=b.time_length, temperatures=b.temperatures,
+                                           device=b._device, **self._opt)
+        self._key = key
+        if self._pending is not None:
+            self.load_state_dict(self._pending)
+
+    def _per_molecule_engine(self):
+        """The device trainer of batches='per_molecule': the complete directed graph on max_atoms atoms in (src, dst) order, type 0"""
+        if self.engine is None:
+            A = self.max_atoms
+            s_all, d_all = np.nonzero(~np.eye(A, dtype=bool))
+            if not s_all.size:
+                raise ValueError("batches='per_molecule' needs max_atoms >= 2: the trainer needs an edge template")
+            self._build(A, s_all.astype(np.int32), d_all.astype(np.int32), np.zeros(s_all.size, np.int32), np.arange(A, dtype=np.int32), ("per_molecule", A))
+        return self.engine
+
+    def _graphs_of(self, sb):
+        """(n_atoms [B], mask [B, A], pair_type [B, A, A]) of a SpeciesBatch over the trainer's max_atoms = A"""
+        A, a = self.max_atoms, sb.A
+        if a > A:
+            raise ValueError(f"the batch's largest molecule has {a} atoms, the trainer was built for max_atoms = {A}")
+        if sb.n_atoms is None and not np.array_equal(sb.atom_ids, np.arange(a)):
+            raise ValueError("batches='per_molecule' needs every molecule's atom ids to be 0 .. n_atoms - 1 (distinguish=True)")
+        n = np.full(sb.B, a, np.int32) if sb.n_atoms is None else np.asarray(sb.n_atoms, np.int32)
+        mask = np.zeros((sb.B, A), np.uint32)
+        if sb.mask is not None:
+            mask[:, :a] = sb.mask
+        else:
+            mask[:, :a] = np.bincount(sb.dst, weights=np.ldexp(1.0, sb.src), minlength=a).astype(np.uint32)[None]
+        pt = np.zeros((sb.B, A, A), np.uint8)
+        if sb.pair_type is not None:
+            pt[:, :a, :a] = sb.pair_type
+        else:
+            pt[:, sb.src, sb.dst] = sb.etype.astype(np.uint8)[None]
+        return n, mask, pt
+
+    def _args_per_molecule(self, batch, x0, x1, conds, t, z):
+        """_args for batches='per_molecule': the padded arrays of the call, with the batch's graphs set on the device trainer"""
+        sb = split_species_batch(batch, self.b.ATOM_KEY)
+        eng = self._per_molecule_engine()
+        if len(conds) != eng.ncond:
+            raise ValueError(f"this model takes {eng.ncond} conditioning value(s) per node, the batch form gives {len(conds)}")
+        eng.set_graphs(*self._graphs_of(sb))
+        B, A = sb.B, self.max_atoms
+
+        def padded(flat, comps):
+            out = np.zeros((B, A, comps), np.float32)
+            out[:, :sb.A] = sb.pad(C.to_numpy(flat, np.float32), comps)
+            return out
+
+        cond = np.ascontiguousarray(np.concatenate([padded(c, 1) for c in conds], axis=-1)) if conds else None
+        tv = None
+        if t is not None:
+            tn = C.to_numpy(t, np.float32).reshape(-1)
+            if tn.size == B:
+                tv = np.ascontiguousarray(tn)
+            elif tn.size != sb.N:
+                raise ValueError(f"t must hold one value per molecule ({B}) or per node ({sb.N}), got {tn.size}")
+            else:
+                per = sb.molecule_values(tn).reshape(B, sb.A)
+                if np.any(per != per[:, :1]):
+                    raise ValueError("t must be constant within each molecule")
+                tv = np.ascontiguousarray(per[:, 0])
+        return padded(x0, 3), padded(x1, 3), cond, tv, None if z is None else padded(z, 3)
 
     def _engine_for(self, batch):
         try:
@@ -515,20 +606,15 @@ class MoleculeTrainerBase:
             raise NotImplementedError(f"the trainer takes uniform batches (one species, one graph, no edge mask): {e}") from None
         key = (A, src.tobytes(), dst.tobytes(), ety.tobytes(), ids.tobytes())
         if self.engine is None:
-            b = self.b
-            flat = _W.flatten_state_dict(b._sd, b._spec, dtype=np.float64)
-            self.engine = _engine.PainnTrainer(b.VARIANT, b.n_features, b.score_layers, A, src, dst, ety, ids, flat, n_types=b.n_types,
-                                               temp_length=b.temp_length, time_length=b.time_length, temperatures=b.temperatures,
-                                               device=b._device, **self._opt)
-            self._key = key
-            if self._pending is not None:
-                self.load_state_dict(self._pending)
+            self._build(A, src, dst, ety, ids, key)
         elif key != self._key:
             raise NotImplementedError("a trainer serves one species: this batch has another template or other atom ids")
         return B, A
 
     def _args(self, batch, x0, x1, conds, t, z):
         from .losses import _molecule_t
+        if self.batches == "per_molecule":
+            return self._args_per_molecule(batch, x0, x1, conds, t, z)
         B, A = self._engine_for(batch)
         if len(conds) != self.engine.ncond:
             raise ValueError(f"this model takes {self.engine.ncond} conditioning value(s) per node, the batch form gives {len(conds)}")
@@ -560,6 +646,8 @@ class MoleculeTrainerBase:
     def _resident(self, x0, x1, temps0, temps1, template_batch):
         """The resident sets of fit / evaluate as the device call takes them: x [n, A, 3] float32 and one temperature per molecule,
         numpy or CUDA tensors (all in one memory space).  template_batch builds the device trainer when no step has done so yet."""
+        if self.engine is None and self.batches == "per_molecule":
+            self._per_molecule_engine()
         if self.engine is None:
             if template_batch is None:
                 raise ValueError("the trainer has seen no batch yet: pass template_batch, one uniform batch of the species")
@@ -578,9 +666,19 @@ class MoleculeTrainerBase:
         t0 = None if x0 is None else arr(temps0, (x0.shape[0],), "temps0")
         return x0, x1, t0, arr(temps1, (x1.shape[0],), "temps1")
 
-    def _fit(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, update, track_best):
+    def _fit(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, update, track_best,
+             masks=None):
         from .adw import minibatch_indices
         x0, x1, t0, t1 = self._resident(x0, x1, temps0, temps1, template_batch)
+        if masks is not None:
+            if noise != "given" or x0 is None:
+                raise ValueError("masks are the graphs of the resident set 0: they need noise='given' and an x0")
+            m = masks if C.is_cuda(masks) else np.ascontiguousarray(C.to_numpy(masks))
+            if tuple(m.shape) != (int(x0.shape[0]), self.engine.A):
+                raise ValueError(f"masks must be [n0, A] = [{int(x0.shape[0])}, {self.engine.A}], got {tuple(m.shape)}")
+            self.engine.set_graphs(None, m, None)              # one species: every count A, the template's types
+        else:
+            self.engine.set_graphs()                           # the table a per-molecule step may have left
         rng = np.random.default_rng(seed)
         i0 = minibatch_indices(x0.shape[0], batch_size, n_steps, rng) if x0 is not None else None
         i1 = minibatch_indices(x1.shape[0], batch_size, n_steps, rng)
@@ -591,20 +689,24 @@ class MoleculeTrainerBase:
                                  seed=seed if noise_seed is None else noise_seed, draw=draw, **self._kw)
 
     def fit(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, *, draw=0, noise_seed=None, center=None, template_batch=None,
-            noise="given", track_best=True):
+            noise="given", track_best=True, masks=None):
         """n_steps optimiser steps in one device call on resident sets (engine.PainnTrainer.steps): minibatches from permutations drawn
         on the host with `seed` (thermo.adw.minibatch_indices, set 0 first, independently for the two sets), step k with the (t, z) of
         draw + k under noise_seed (default: seed).  x0 [n0, A, 3], x1 [n1, A, 3]; temps0 [n0], temps1 [n1] or None as the model takes
         them.  noise="drawn" | "aligned" with x0=None: the base samples of every minibatch are drawn on the device.  track_best keeps the
-        weights of the step with the smallest loss (best_state_dict).  -> (mean loss of every step [n_steps], NaN where skipped; the
-        number of skipped steps)"""
-        return self._fit(x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, True, track_best)
+        weights of the step with the smallest loss (best_state_dict).  masks [n0, A] uint32 (noise="given", one species): the edge
+        sets of the resident set 0 over the trainer's template, bit s of masks[i, d] set when row i has the edge s -> d; a minibatch
+        molecule takes the graph of its set-0 row, as the reference's loss evaluates both states on batch0's graph.
+        -> (mean loss of every step [n_steps], NaN where skipped; the number of skipped steps)"""
+        return self._fit(x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, True, track_best,
+                         masks)
 
     def evaluate(self, x0, x1, temps0, temps1, batch_size, n_steps, seed, *, draw=0, noise_seed=None, center=None, template_batch=None,
-                 noise="given"):
+                 noise="given", masks=None):
         """fit without the update: the forward pass and the loss of the same minibatches at the current weights; nothing changes.
         -> the mean loss of every minibatch [n_steps]"""
-        return self._fit(x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, False, False)[0]
+        return self._fit(x0, x1, temps0, temps1, batch_size, n_steps, seed, draw, noise_seed, center, template_batch, noise, False, False,
+                         masks)[0]
 
     def best_state_dict(self, reset=False):
         """(state dict in the reference's keys, loss, step) of the step with the smallest loss since the last reset: the weights that

@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--graphs", action="store_true", help="also time `step` with a full table of per-molecule graphs in force "
+                    "(ti_painn_train_set_graphs: the masked twins on rows none of which is dead; profiles/painn_train_graphs_bench.txt)")
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch
@@ -48,7 +50,11 @@ def main():
             print(B, tr.step(x0, x1, cond, seed=1, draw=0))
             continue
         res = {}
-        for name, fn in (("grad", lambda k: tr.grad(x0, x1, cond, seed=1, draw=k)), ("step", lambda k: tr.step(x0, x1, cond, seed=1, draw=k))):
+        calls = [("grad", lambda k: tr.grad(x0, x1, cond, seed=1, draw=k)), ("step", lambda k: tr.step(x0, x1, cond, seed=1, draw=k))]
+        if a.graphs:
+            calls.append(("step, full table", lambda k: tr.step(x0, x1, cond, seed=1, draw=k)))
+        for name, fn in calls:
+            tr.set_graphs(np.full(B, A, np.int32)) if name.endswith("table") else tr.set_graphs()
             for k in range(a.warmup):
                 fn(k)
             ms = []
@@ -58,7 +64,8 @@ def main():
                 fn(a.warmup + k)
                 ms.append((time.perf_counter() - t0) * 1e3)
             res[name] = f"{name} {np.median(ms):.2f} ({min(ms):.2f} .. {max(ms):.2f}) ms"
-        lines.append(f"B {B}: {res['grad']}, {res['step']}; workspace {tr.workspace_bytes(B) / 2 ** 30:.2f} GiB, {2 * B * src.size} edge rows")
+        tr.set_graphs()
+        lines.append(f"B {B}: {', '.join(res.values())}; workspace {tr.workspace_bytes(B) / 2 ** 30:.2f} GiB, {2 * B * src.size} edge rows")
         print(lines[-1], flush=True)
     text = "\n".join(lines) + "\n"
     if a.out and not a.once:
