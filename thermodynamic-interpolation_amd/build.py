@@ -71,10 +71,12 @@ SOURCES = ["api_common.hip", "api_painn.hip", "api_adw.hip", "api_vloss.hip", "p
            # algebra around the two solves of obs_eig_kernels.hip and the projection; its entry points, a host unit of their own
            "obs_tica_kernels.hip", "api_obs_tica.hip",
            # the molecule trainer on per-molecule graphs (ti_painn_train_set_graphs): masked / ragged twins of the trainer's kernels
-           # that read the graph or the loss rows, a unit of their own; the code objects of painn_train_kernels.hip stay as they were
+           # that read the graph or the loss rows, a unit of their own.  A twin and its parent are one body (vloss_state_body.inc,
+           # painn_train_graph_body.inc) included by both units, so the code objects of vloss_kernels.hip and painn_train_kernels.hip
+           # stay as they were by construction: there every predicate is `false`, nothing or the plain expression
            "painn_train_graph_kernels.hip"]
-HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "adw_train.hpp", "painn_train.hpp", "painn_train_graph.hpp", "painn_steps.hpp", "train_optim.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "vloss_normal.hpp", "ff_device.hpp", "ff_stage.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp", "painn_update_kernel.hpp",
-           "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_update_kernel_body.inc", "painn_embed_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
+HEADERS = ["ti_handle.hpp", "rollout.hpp", "mfma_chain.hpp", "dispatch.hpp", "ti_internal.hpp", "adw_train.hpp", "painn_train.hpp", "painn_train_graph.hpp", "painn_steps.hpp", "train_optim.hpp", "ode_device.hpp", "adw_device.hpp", "boot_draw.hpp", "vloss_normal.hpp", "vloss_device.hpp", "ff_device.hpp", "ff_stage.hpp", "painn_edge_kernel.hpp", "painn_pair_kernel.hpp", "pair_template.hpp", "message_stream.hpp", "painn_update_kernel.hpp",
+           "painn_edge_kernel_body.inc", "painn_pair_kernel_body.inc", "painn_update_kernel_body.inc", "painn_embed_kernel_body.inc", "painn_jvp_edge_body.inc", "painn_jvp_filter_body.inc", "vloss_state_body.inc", "painn_train_graph_body.inc", os.path.join("..", "..", "include", "ti_hip.h")]
 # -packed-fp32-ops off: v_pk_{fma,mul,add}_f32 do NOT run next to another wave's matrix instructions on gfx950 (a wave of them and a
 # wave of 16x16x32 fp16 MFMAs on one SIMD take the SUM of their times; scalar v_fma_f32, conversions and transcendentals overlap:
 # tools/micro/coexec_classes.hip, profiles/r03i_microbench_coexec.txt), and register pairs cost the message kernels registers (pair

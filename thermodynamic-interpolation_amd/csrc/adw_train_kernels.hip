@@ -8,8 +8,9 @@
 // a result depends on the values alone.  The weight gradient is cut into slices of TRAIN_ROW_TILE rows (blockIdx.z), each slice
 // written to its own place and the slices added in fp64 in order: no atomics anywhere.  The two sums that cancel -- a bias gradient
 // (the column sum of g) and the gradient handed to beta_embed (both antithetic halves of a row) -- are taken in fp64 by kernels of
-// their own.
+// their own.  gamma'(t) of the output gradient is the velocity loss's (vloss_device.hpp).
 #include "adw_train.hpp"
+#include "vloss_device.hpp"
 
 namespace ti {
 
@@ -17,7 +18,6 @@ namespace {
 
 constexpr int TR_BLOCK = 256;
 constexpr int TR_KU = 8;                       // chain links per round of the product kernel
-constexpr double TR_PI = 3.14159265358979323846;
 typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ tr_f32x4 tr_mfma(float a, float b, tr_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
@@ -110,16 +110,6 @@ __global__ __launch_bounds__(TR_BLOCK) void adwtr_net_in_kernel(float* __restric
     a0[i] = cc < d ? xt[r * d + cc] : cc == d ? t[b] : emb[b];
 }
 
-// gamma'(t) as vloss_kernels.hip evaluates it (include/ti_hip.h TI_GAMMA_*)
-__device__ __forceinline__ double tr_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ double tr_gamma_dot(int kind, double a, double t)
-{
-    if (kind == TI_GAMMA_BROWNIAN) return a * (1.0 - 2.0 * t) / (2.0 * sqrt(a * t * (1.0 - t)));
-    if (kind == TI_GAMMA_SIN2) return 2.0 * TR_PI * sin(TR_PI * t) * cos(TR_PI * t);
-    const double sp = tr_sigmoid(a * (t - 0.5) + 1.0), sm = tr_sigmoid(a * (t - 0.5) - 1.0);
-    return (double)2.2f * a * ((1.0 - sp) * sp - (1.0 - sm) * sm);
-}
-
 __global__ __launch_bounds__(TR_BLOCK) void adwtr_gout_kernel(float* __restrict__ gz, const VlossParams p)
 {
 #pragma clang fp contract(off)
@@ -128,7 +118,7 @@ __global__ __launch_bounds__(TR_BLOCK) void adwtr_gout_kernel(float* __restrict_
     const long long b = i / p.m;
     const double d = (double)p.x1[i] - (double)p.x0[i], inv = (double)p.B;
     if (p.kind == TI_VLOSS_ONE_SIDED) { gz[i] = (float)(((double)p.b[i] - d) / inv); return; }
-    const double gzv = tr_gamma_dot(p.gamma, p.a, (double)p.t[b]) * (double)p.z[i];
+    const double gzv = vl_gamma_dot(p.gamma, p.a, (double)p.t[b]) * (double)p.z[i];
     gz[i] = (float)(((double)p.b[i] - (d + gzv)) / inv);
     gz[n + i] = (float)(((double)p.b[p.half + i] - (d - gzv)) / inv);
 }

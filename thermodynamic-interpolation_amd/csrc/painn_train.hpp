@@ -1,6 +1,7 @@
 // painn_train.hpp -- private header of the molecule trainer (include/ti_hip.h ti_painn_trainer_create .. ti_painn_train_workspace_bytes):
-// the launchers of painn_train_kernels.hip.  Shared by painn_train_kernels.hip and api_painn_train.hip only.  The matrix products,
-// the combine of the weight-gradient slices and clip + Adam are the adw trainer's (adw_train.hpp).
+// the launchers of painn_train_kernels.hip.  Shared by painn_train_kernels.hip and api_painn_train.hip, and through
+// painn_train_graph.hpp by painn_train_graph_kernels.hip, which is why the positional encoding both kernel units evaluate is stated
+// here.  The matrix products, the combine of the weight-gradient slices and clip + Adam are the adw trainer's (adw_train.hpp).
 //
 // Rows: a call evaluates R = halves B molecules, molecule r = half B + b.  Node row n = r A + a, edge row r E + k (k the template
 // edge).  Per-node vectors v lie as [n][3][F], so that U v and V v are products over 3 R A rows of F.
@@ -13,6 +14,14 @@ namespace ti {
 // chain per entry, the slices are added in fp64.
 constexpr int PTRAIN_SLICE = 2048;
 inline long long ptrain_slices(long long rows) { return (rows + PTRAIN_SLICE - 1) / PTRAIN_SLICE; }
+
+// feature f of PositionalEncoder: cos, sin interleaved per k = f / 2 + 1
+constexpr float PT_PI = 3.14159265358979323846f;
+__device__ __forceinline__ float pt_posenc(float x_over_len, int f)
+{
+    const float arg = (x_over_len * (float)(f / 2 + 1)) * PT_PI;
+    return (f & 1) ? sinf(arg) : cosf(arg);
+}
 
 struct PtGraph {
     const int32_t *src, *dst;   // [E] the template

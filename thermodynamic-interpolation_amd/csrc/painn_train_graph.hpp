@@ -1,6 +1,7 @@
 // painn_train_graph.hpp -- private header of the molecule trainer on per-molecule graphs (include/ti_hip.h
 // ti_painn_train_set_graphs): the launchers of painn_train_graph_kernels.hip, the masked / ragged twins of the kernels a call with a
-// table in force cannot take as they stand.  Shared by that unit and api_painn_train.hip only.  Everything else of such a call -- the
+// table in force cannot take as they stand.  Shared by that unit and api_painn_train.hip only.  A twin and its parent are one body
+// (vloss_state_body.inc, painn_train_graph_body.inc); the notes at the launchers say what the twin's predicates do.  Everything else of such a call -- the
 // geometry, the encodings, the products, LayerNorm, the update, the readout, the column sums -- is the kernels of a call without a
 // table: they run over the dense layout, in which every row is finite and dead rows carry exact zeros where a sum would take them.
 #pragma once

@@ -5,26 +5,45 @@
 //
 // One thread per (row, feature) throughout, except LayerNorm (one wave per row, a fixed shuffle tree) and the table gradient
 // and the column sums (the accumulator scheme of adwtr_bias_kernel, per tile of rows).  No atomics: a per-node sum walks the template's edges in order.
+// The six kernels that per-molecule graphs change have their bodies in painn_train_graph_body.inc, which painn_train_graph_kernels.hip
+// includes as well; gamma'(t) of the output gradient is the velocity loss's (vloss_device.hpp).
 #include "painn_train.hpp"
+#include "vloss_device.hpp"
 
 namespace ti {
 
 namespace {
 
 constexpr int PT_BLOCK = 256;
-constexpr float PT_PI = 3.14159265358979323846f;
-constexpr double PT_PI_D = 3.14159265358979323846;
 
 unsigned pt_blocks(long long n) { return (unsigned)((n + PT_BLOCK - 1) / PT_BLOCK); }
 
 __device__ __forceinline__ long long pt_index() { return (long long)blockIdx.x * PT_BLOCK + threadIdx.x; }
 
-// feature f of PositionalEncoder: cos, sin interleaved per k = f / 2 + 1
-__device__ __forceinline__ float pt_posenc(float x_over_len, int f)
-{
-    const float arg = (x_over_len * (float)(f / 2 + 1)) * PT_PI;
-    return (f & 1) ? sinf(arg) : cosf(arg);
-}
+// The kernels that read the graph or run over a molecule's entries: pt_embed_in_kernel, pt_edge_emb_kernel, pt_msg_fwd_kernel,
+// pt_msg_bwd_edge_kernel, pt_msg_bwd_node_kernel and pt_gout_kernel.  Every molecule is the whole template here: no pads, no dead
+// edges, the template's edge types; painn_train_graph_kernels.hip takes the same text with each molecule's own
+#define TI_TWIN_KERNEL(stem) pt_##stem##_kernel
+#define TI_TWIN_BLOCK PT_BLOCK
+#define TI_TWIN_LIVE_PARAM
+#define TI_PAD_ATOM(a, b) false
+#define TI_PAD_ENTRY(k, b) false
+#define TI_BATCH_ATOMS (double)(p.B * p.A)
+#define TI_EDGE_TYPES_PARAM const int32_t* __restrict__ etype,
+#define TI_EDGE_TYPE(row) etype[(row) % g.E]
+#define TI_EDGE_FLAGS(r)
+#define TI_EDGE_DEAD(k) false
+#include "painn_train_graph_body.inc"
+#undef TI_TWIN_KERNEL
+#undef TI_TWIN_BLOCK
+#undef TI_TWIN_LIVE_PARAM
+#undef TI_PAD_ATOM
+#undef TI_PAD_ENTRY
+#undef TI_BATCH_ATOMS
+#undef TI_EDGE_TYPES_PARAM
+#undef TI_EDGE_TYPE
+#undef TI_EDGE_FLAGS
+#undef TI_EDGE_DEAD
 
 __global__ __launch_bounds__(PT_BLOCK) void pt_geom_kernel(float* __restrict__ dir, float* __restrict__ dist, const float* __restrict__ x, const PtGraph g)
 {
@@ -46,32 +65,6 @@ __global__ __launch_bounds__(PT_BLOCK) void pt_enc_kernel(float* __restrict__ en
     if (i >= g.R * g.E * g.F) return;
     const long long row = i / g.F;
     enc[i] = pt_posenc(dist[row] / length_scale, (int)(i - row * g.F));
-}
-
-__global__ __launch_bounds__(PT_BLOCK) void pt_embed_in_kernel(float* __restrict__ s_in, const PtEmbedIn e, const PtGraph g)
-{
-    const int K = e.nE * g.F;
-    const long long i = pt_index();
-    if (i >= g.R * g.A * K) return;
-    const long long n = i / K, r = n / g.A, b = r % e.B;
-    const int j = (int)(i - n * K), a = (int)(n - r * g.A), seg = j / g.F, f = j - seg * g.F;
-    float v;
-    if (seg == 0) v = e.atom_emb[(size_t)e.atom_ids[a] * g.F + f];
-    else if (seg < e.nE - 1) {
-        float u = e.cond[(b * g.A + a) * e.ncond + (seg - 1)] - e.temp_mean;
-        u = u / e.temp_range;
-        v = pt_posenc(u / e.temp_length, f);
-    } else v = pt_posenc(e.t[b] / e.time_length, f);
-    s_in[i] = v;
-}
-
-__global__ __launch_bounds__(PT_BLOCK) void pt_edge_emb_kernel(float* __restrict__ e0, const float* __restrict__ table, const int32_t* __restrict__ etype,
-                                                               const PtGraph g)
-{
-    const long long i = pt_index();
-    if (i >= g.R * g.E * g.F) return;
-    const long long row = i / g.F;
-    e0[i] = table[(size_t)etype[row % g.E] * g.F + (i - row * g.F)];
 }
 
 __device__ __forceinline__ float pt_wave_sum(float v)
@@ -154,32 +147,6 @@ __global__ __launch_bounds__(PT_BLOCK) void pt_phi_in_kernel(float* __restrict__
     phi_in[i] = j < g.F ? s[(r * g.A + g.src[k]) * g.F + j] : e[row * g.F + (j - g.F)];
 }
 
-__global__ __launch_bounds__(PT_BLOCK) void pt_msg_fwd_kernel(float* __restrict__ s_out, float* __restrict__ v_out, const float* __restrict__ s,
-                                                              const float* __restrict__ v, const float* __restrict__ P, const float* __restrict__ Wd,
-                                                              const float* __restrict__ dir, const PtGraph g)
-{
-    const int F = g.F;
-    const long long i = pt_index();
-    if (i >= g.R * g.A * F) return;
-    const long long n = i / F, r = n / g.A;
-    const int f = (int)(i - n * F), a = (int)(n - r * g.A);
-    const float vn0 = v[(n * 3) * F + f], vn1 = v[(n * 3 + 1) * F + f], vn2 = v[(n * 3 + 2) * F + f];
-    float ds = 0.f, dv0 = 0.f, dv1 = 0.f, dv2 = 0.f;
-    for (int k = 0; k < g.E; ++k) {
-        if (g.dst[k] != a) continue;
-        const long long row = r * g.E + k, ns = r * g.A + g.src[k], o = row * 5 * F + f;
-        const float gates = P[o] * Wd[o], scale = P[o + F] * Wd[o + F], cross = P[o + 4 * F] * Wd[o + 4 * F];
-        const float d0 = dir[3 * row], d1 = dir[3 * row + 1], d2 = dir[3 * row + 2];
-        const float c0 = d1 * vn2 - d2 * vn1, c1 = d2 * vn0 - d0 * vn2, c2 = d0 * vn1 - d1 * vn0;
-        dv0 += scale * d0 + gates * v[(ns * 3) * F + f] + cross * c0;
-        dv1 += scale * d1 + gates * v[(ns * 3 + 1) * F + f] + cross * c1;
-        dv2 += scale * d2 + gates * v[(ns * 3 + 2) * F + f] + cross * c2;
-        ds += P[o + 2 * F] * Wd[o + 2 * F];
-    }
-    s_out[i] = s[i] + ds;
-    v_out[(n * 3) * F + f] = vn0 + dv0; v_out[(n * 3 + 1) * F + f] = vn1 + dv1; v_out[(n * 3 + 2) * F + f] = vn2 + dv2;
-}
-
 __global__ __launch_bounds__(PT_BLOCK) void pt_e_fwd_kernel(float* __restrict__ e_out, const float* __restrict__ e, const float* __restrict__ P,
                                                             const float* __restrict__ Wd, const PtGraph g)
 {
@@ -187,65 +154,6 @@ __global__ __launch_bounds__(PT_BLOCK) void pt_e_fwd_kernel(float* __restrict__ 
     if (i >= g.R * g.E * g.F) return;
     const long long row = i / g.F, o = row * 5 * g.F + 3 * g.F + (i - row * g.F);
     e_out[i] = e[i] + P[o] * Wd[o];
-}
-
-__global__ __launch_bounds__(PT_BLOCK) void pt_msg_bwd_edge_kernel(float* __restrict__ gP, float* __restrict__ gWd, const float* __restrict__ gs,
-                                                                   const float* __restrict__ gv, const float* __restrict__ ge, const float* __restrict__ v,
-                                                                   const float* __restrict__ P, const float* __restrict__ Wd, const float* __restrict__ dir,
-                                                                   const PtGraph g)
-{
-    const int F = g.F;
-    const long long i = pt_index();
-    if (i >= g.R * g.E * F) return;
-    const long long row = i / F, r = row / g.E;
-    const int f = (int)(i - row * F), k = (int)(row - r * g.E);
-    const long long ns = r * g.A + g.src[k], nd = r * g.A + g.dst[k], o = row * 5 * F + f;
-    const float g0 = gv[(nd * 3) * F + f], g1 = gv[(nd * 3 + 1) * F + f], g2 = gv[(nd * 3 + 2) * F + f];
-    const float s0 = v[(ns * 3) * F + f], s1 = v[(ns * 3 + 1) * F + f], s2 = v[(ns * 3 + 2) * F + f];
-    const float t0 = v[(nd * 3) * F + f], t1 = v[(nd * 3 + 1) * F + f], t2 = v[(nd * 3 + 2) * F + f];
-    const float d0 = dir[3 * row], d1 = dir[3 * row + 1], d2 = dir[3 * row + 2];
-    const float c0 = d1 * t2 - d2 * t1, c1 = d2 * t0 - d0 * t2, c2 = d0 * t1 - d1 * t0;
-    float gh[5];
-    gh[0] = g0 * s0 + g1 * s1 + g2 * s2;                // gates
-    gh[1] = g0 * d0 + g1 * d1 + g2 * d2;                // scale
-    gh[2] = gs[nd * F + f];                             // ds
-    gh[3] = ge ? ge[row * F + f] : 0.0f;                // de
-    gh[4] = g0 * c0 + g1 * c1 + g2 * c2;                // cross gates
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        gP[o + j * F] = gh[j] * Wd[o + j * F];
-        gWd[o + j * F] = gh[j] * P[o + j * F];
-    }
-}
-
-__global__ __launch_bounds__(PT_BLOCK) void pt_msg_bwd_node_kernel(float* __restrict__ gs_out, float* __restrict__ gv_out, const float* __restrict__ gs,
-                                                                   const float* __restrict__ gv, const float* __restrict__ gin_phi,
-                                                                   const float* __restrict__ P, const float* __restrict__ Wd, const float* __restrict__ dir,
-                                                                   const PtGraph g)
-{
-    const int F = g.F;
-    const long long i = pt_index();
-    if (i >= g.R * g.A * F) return;
-    const long long n = i / F, r = n / g.A;
-    const int f = (int)(i - n * F), a = (int)(n - r * g.A);
-    const float g0 = gv[(n * 3) * F + f], g1 = gv[(n * 3 + 1) * F + f], g2 = gv[(n * 3 + 2) * F + f];
-    float as = gs[i], a0 = g0, a1 = g1, a2 = g2;
-    for (int k = 0; k < g.E; ++k) {
-        const long long row = r * g.E + k, o = row * 5 * F + f;
-        if (g.src[k] == a) {                                               // an outgoing edge: s[src] of phi's input, gates v[src]
-            const long long nd = r * g.A + g.dst[k];
-            const float gates = P[o] * Wd[o];
-            as += gin_phi[row * 2 * F + f];
-            a0 += gates * gv[(nd * 3) * F + f]; a1 += gates * gv[(nd * 3 + 1) * F + f]; a2 += gates * gv[(nd * 3 + 2) * F + f];
-        }
-        if (g.dst[k] == a) {
-            const float cross = P[o + 4 * F] * Wd[o + 4 * F];              // an incoming edge: cross (dir x v[dst]) -> cross (g x dir)
-            const float d0 = dir[3 * row], d1 = dir[3 * row + 1], d2 = dir[3 * row + 2];
-            a0 += cross * (g1 * d2 - g2 * d1); a1 += cross * (g2 * d0 - g0 * d2); a2 += cross * (g0 * d1 - g1 * d0);
-        }
-    }
-    gs_out[i] = as;
-    gv_out[(n * 3) * F + f] = a0; gv_out[(n * 3 + 1) * F + f] = a1; gv_out[(n * 3 + 2) * F + f] = a2;
 }
 
 __global__ __launch_bounds__(PT_BLOCK) void pt_e_bwd_kernel(float* __restrict__ ge_out, const float* __restrict__ ge, const float* __restrict__ gin_phi,
@@ -334,29 +242,6 @@ __global__ __launch_bounds__(PT_BLOCK) void pt_readout_kernel(float* __restrict_
 {
     const long long i = pt_index();
     if (i < nodes * 3) b[i] = Vv[i] * ro[(i / 3) * 2 + 1];
-}
-
-// gamma'(t) as vloss_kernels.hip evaluates it (include/ti_hip.h TI_GAMMA_*)
-__device__ __forceinline__ double pt_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ double pt_gamma_dot(int kind, double a, double t)
-{
-    if (kind == TI_GAMMA_BROWNIAN) return a * (1.0 - 2.0 * t) / (2.0 * sqrt(a * t * (1.0 - t)));
-    if (kind == TI_GAMMA_SIN2) return 2.0 * PT_PI_D * sin(PT_PI_D * t) * cos(PT_PI_D * t);
-    const double sp = pt_sigmoid(a * (t - 0.5) + 1.0), sm = pt_sigmoid(a * (t - 0.5) - 1.0);
-    return (double)2.2f * a * ((1.0 - sp) * sp - (1.0 - sm) * sm);
-}
-
-__global__ __launch_bounds__(PT_BLOCK) void pt_gout_kernel(float* __restrict__ gz, const VlossParams p)
-{
-#pragma clang fp contract(off)
-    const long long n = p.B * p.m, i = pt_index();
-    if (i >= n) return;
-    const long long b = i / p.m;
-    const double d = (double)p.x1[i] - (double)p.x0[i], inv = (double)(p.B * p.A);
-    if (p.kind == TI_VLOSS_ONE_SIDED) { gz[i] = (float)(((double)p.b[i] - d) / inv); return; }
-    const double gzv = pt_gamma_dot(p.gamma, p.a, (double)p.t[b]) * (double)p.z[i];
-    gz[i] = (float)(((double)p.b[i] - (d + gzv)) / inv);
-    gz[n + i] = (float)(((double)p.b[p.half + i] - (d - gzv)) / inv);
 }
 
 __global__ __launch_bounds__(PT_BLOCK) void pt_readout_bwd_kernel(float* __restrict__ gro, float* __restrict__ gVv, float* __restrict__ gv,

@@ -4,9 +4,9 @@
 // reduction work in fp64 on fp32 inputs, bound by memory; the drift between the two stages is the existing per-molecule-time path.
 // No atomics: a batch-wide sum is taken over tiles of VLOSS_TILE rows in row order and over the tiles in order, each by the fixed
 // tree of block_sum, so it is a function of the values and their number only -- not of the launch.
-#include "ti_internal.hpp"
-#include "adw_device.hpp"
-#include "vloss_normal.hpp"
+// gamma, gamma' and the z draw are vloss_device.hpp's, shared with the trainers; the states, the centring and the reduction have
+// their bodies in vloss_state_body.inc, which the molecule trainer's per-molecule graphs include as well.
+#include "vloss_device.hpp"
 
 namespace ti {
 
@@ -14,37 +14,6 @@ namespace {
 
 constexpr int VL_BLOCK = 256;
 constexpr int VL_ROWS_PER_THREAD = VLOSS_TILE / VL_BLOCK;
-constexpr double VL_PI = 3.14159265358979323846;
-
-__device__ __forceinline__ double vl_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-
-// gamma(t) and its derivative (include/ti_hip.h TI_GAMMA_*); VL_SIG_SCALE: the reference holds its 2.2 as a float32 tensor
-constexpr double VL_SIG_SCALE = (double)2.2f;
-__device__ __forceinline__ void vl_gamma(int kind, double a, double t, double& g, double& gd)
-{
-    if (kind == TI_GAMMA_BROWNIAN) {
-        g = sqrt(a * t * (1.0 - t));
-        gd = a * (1.0 - 2.0 * t) / (2.0 * g);
-    } else if (kind == TI_GAMMA_SIN2) {
-        const double s = sin(VL_PI * t), c = cos(VL_PI * t);
-        g = s * s;
-        gd = 2.0 * VL_PI * s * c;
-    } else {
-        const double sp = vl_sigmoid(a * (t - 0.5) + 1.0), sm = vl_sigmoid(a * (t - 0.5) - 1.0);
-        g = VL_SIG_SCALE * (sp - sm - vl_sigmoid(1.0 - 0.5 * a) + vl_sigmoid(-1.0 - 0.5 * a));
-        gd = VL_SIG_SCALE * a * ((1.0 - sp) * sp - (1.0 - sm) * sm);
-    }
-}
-
-// the Philox normal of (seed, trajectory, step, component) exactly as oracle.normal returns it: the counter slots of TI_SCHEME_EM
-// (adw_device.hpp ti_normal), Box-Muller by vloss_normal.hpp
-__device__ __forceinline__ float vl_normal(uint64_t seed, long long traj, int step, int comp)
-{
-    uint32_t c[4] = {(uint32_t)traj, (uint32_t)((uint64_t)traj >> 32), (uint32_t)step, (uint32_t)(comp >> 2)};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const int pair = (comp & 3) >> 1;
-    return vl_box_muller(c[2 * pair], c[2 * pair + 1], comp & 1);
-}
 
 // the sum of one value per thread of a VL_BLOCK-thread block, valid in thread 0: a fixed tree over the thread index
 __device__ __forceinline__ double block_sum(double v, double* sm)
@@ -75,46 +44,23 @@ __global__ __launch_bounds__(VL_BLOCK) void vloss_draw_t_kernel(float* __restric
     t[b] = fminf(v, 0.99999994f);                                          // 1 - 2^-24
 }
 
-__global__ __launch_bounds__(VL_BLOCK) void vloss_interp_kernel(VlossParams p)
-{
-    const long long n = p.B * p.m, i = (long long)blockIdx.x * VL_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const long long b = i / p.m;
-    const int comp = (int)(i - b * p.m);
-    const double t = (double)p.t[b], x0 = (double)p.x0[i], x1 = (double)p.x1[i];
-    double xp, xm = 0.0;
-    if (p.kind == TI_VLOSS_ONE_SIDED) xp = t * x1 + (1.0 - t) * x0;
-    else {
-        const float z = p.z_in ? p.z_in[i] : vl_normal(p.seed, p.traj0 + b, p.draw, comp);
-        p.z[i] = z;
-        double g, gd;
-        vl_gamma(p.gamma, p.a, t, g, gd);
-        const double it = (1.0 - t) * x0 + t * x1, gz = g * (double)z;
-        xp = it + gz; xm = it - gz;
-    }
-    const bool two = p.kind != TI_VLOSS_ONE_SIDED;
-    if (p.center == TI_CENTER_NONE) { p.xt[i] = (float)xp; if (two) p.xt[p.half + i] = (float)xm; }
-    else { p.raw[i] = xp; if (two) p.raw[n + i] = xm; }
-}
-
-// blockIdx.y: the half (plus, minus)
-__global__ __launch_bounds__(VL_BLOCK) void vloss_center_kernel(VlossParams p)
-{
-    const long long n = p.B * p.m, i = (long long)blockIdx.x * VL_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int half = blockIdx.y, nc = p.m / p.A;
-    const long long b = i / p.m;
-    const int c = (int)(i - b * p.m) % nc;
-    const double* raw = p.raw + (size_t)half * n;
-    double mean;
-    if (p.center == TI_CENTER_BATCH) mean = p.colsum[half * nc + c] / (double)(p.B * p.A);
-    else {
-        double s = 0.0;
-        for (int a = 0; a < p.A; ++a) s += raw[b * p.m + a * nc + c];
-        mean = s / (double)p.A;
-    }
-    p.xt[(size_t)half * p.half + i] = (float)(raw[i] - mean);
-}
+// the interpolant's states, their centring and the per-molecule reduction: vloss_interp_kernel, vloss_center_kernel, vloss_reduce_kernel.
+// Every molecule has p.A atoms here; the molecule trainer's per-molecule graphs take the same text with atom counts of their own
+#define TI_TWIN_KERNEL(stem) vloss_##stem##_kernel
+#define TI_TWIN_BLOCK VL_BLOCK
+#define TI_TWIN_LIVE_PARAM
+#define TI_MOL_ATOMS(b) p.A
+#define TI_MOL_ENTRIES(b) p.m
+#define TI_PAD_ENTRY(k, b) false
+#define TI_BATCH_ATOMS (double)(p.B * p.A)
+#include "vloss_state_body.inc"
+#undef TI_TWIN_KERNEL
+#undef TI_TWIN_BLOCK
+#undef TI_TWIN_LIVE_PARAM
+#undef TI_MOL_ATOMS
+#undef TI_MOL_ENTRIES
+#undef TI_PAD_ENTRY
+#undef TI_BATCH_ATOMS
 
 // partial [tile][col] = sum of v [row][col] over the tile's rows: thread j adds rows 4j .. 4j + 3 of the tile in order.  grid (tiles, ncol)
 __global__ __launch_bounds__(VL_BLOCK) void vloss_tile_sum_kernel(double* __restrict__ partial, const double* __restrict__ v, long long n, int ncol)
@@ -137,33 +83,6 @@ __global__ __launch_bounds__(VL_BLOCK) void vloss_tile_combine_kernel(double* __
     for (long long k = threadIdx.x; k < tiles; k += VL_BLOCK) s += partial[k * ncol + col];
     s = block_sum(s, sm);
     if (threadIdx.x == 0) out[col] = s;
-}
-
-// one thread per molecule / row, its m entries in order.  Contraction off: every product and sum below is rounded on its own, so l_b is
-// the IEEE evaluation of the header's expression, operation by operation.  A fused d + gamma' z is the more exact one, but where d and
-// gamma' z cancel it differs from the plain evaluation by far more than the roundings of the terms, and which products fuse would be
-// the compiler's choice.
-__global__ __launch_bounds__(VL_BLOCK) void vloss_reduce_kernel(VlossParams p)
-{
-#pragma clang fp contract(off)
-    const long long b = (long long)blockIdx.x * VL_BLOCK + threadIdx.x;
-    if (b >= p.B) return;
-    const long long n = p.B * p.m, o = b * p.m;
-    const bool two = p.kind != TI_VLOSS_ONE_SIDED;
-    double g = 0.0, gd = 0.0;
-    if (two) vl_gamma(p.gamma, p.a, (double)p.t[b], g, gd);
-    double acc = 0.0;
-    for (int k = 0; k < p.m; ++k) {
-        const double d = (double)p.x1[o + k] - (double)p.x0[o + k], bp = (double)p.b[o + k];
-        acc += 0.5 * bp * bp;
-        if (two) {
-            const double gz = gd * (double)p.z[o + k], bm = (double)p.b[p.half + o + k];
-            acc -= (d + gz) * bp;
-            acc += 0.5 * bm * bm;
-            acc -= (d - gz) * bm;
-        } else acc -= d * bp;
-    }
-    p.loss[b] = acc;
 }
 
 __global__ __launch_bounds__(VL_BLOCK) void vloss_first_bad_kernel(double* __restrict__ out, const double* __restrict__ loss, long long B)
